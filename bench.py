@@ -14,7 +14,11 @@ synthetic batch resident in HBM before the timed region, weights from a fixed se
 forward -> MSE -> backward -> [all-reduce] -> Adam, nothing skipped; every timed step draws FRESH resampling randomness on
 the host with the reference's generator calls (model.py:392-393, 399-402) and uploads it from pinned memory, non-blocking.
 
-Rank 0 prints ONE JSON line (contract in the task statement).  Besides the contract's fields:
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times the --steps steps (no profiling
+brackets in them) and prints it; --dump-outputs DIR also writes what the last timed step computes from the state the run started
+from (dump_outputs; the same every run).  Every other
+measurement and check is taken with --full only (and each of them can still be switched off there by its own --no-* option); without
+it their fields below are null.  Besides the contract's fields:
   config.products   the product format of the contractions (the default mode is fp32 storage / accumulation with every
                     product formed from an fp16 x 2 split on the 16-bit matrix pipe: 22 significand bits, see the header)
   roofline          the kernel class with the most GPU time in the timed region (hipEvent brackets on the launch streams,
@@ -24,6 +28,8 @@ Rank 0 prints ONE JSON line (contract in the task statement).  Besides the contr
   alt_precisions    the same step with the GEMMs on the exact bf16 x 3 split (recurrences still fp16 x 2), and with EVERY product on the fp32 MFMA
   solver_loop       Solver.train() iterations/s through the device-side batch producer (loader-to-loss, N=1 only)
   cpu_baseline      the oracle on the host cores: batch 64 on the box's CPU share, plus the 1-thread figure
+  dp_collectives    (data parallel, native RCCL) where each bucket's collective sat relative to the end of the backward
+  dp_replicas       (data parallel) whether every rank holds bit-identical weights after the run
 """
 import argparse
 import json
@@ -203,6 +209,23 @@ def solver_loop(B, T, iters=120, warm=8):
             'what': f'speechsplit_amd.solver.Solver.train(), {iters} iterations, batch {B} x {T}, DeviceBatcher + DevicePrefetcher, loss read every 10 iterations'}
 
 
+def dump_outputs(eng, out_dir, cap=1 << 22):
+    """What a training step left its caller, as float32 .npy files: loss.npy (the loss it returned), params.npy (the updated
+    parameter arena) and grads.npy (the gradient arena Adam applied).  An arena of more than `cap` elements (Generator_3: 19.4 M) is
+    written at the same `cap` positions every run, a seeded sample in ascending order: 2 x 16 MB at most."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    n = eng.params.numel()
+    idx = None
+    if n > cap:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:cap].sort().values.to(eng.device)
+    for name, t in (('loss', eng.loss), ('params', eng.params), ('grads', eng.grads)):
+        if idx is not None and t.numel() == n:
+            t = t[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().to(torch.float32).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -229,6 +252,12 @@ def main():
                          "stream shares a hardware queue with one of the engine's.  (Generator_6 always takes the torch path.)")
     ap.add_argument('--no-profile', action='store_true', help='no hipEvent brackets in the timed region (to measure their cost)')
     ap.add_argument('--tune', action='append', default=[], metavar='KEY=VALUE', help='experiment knob of the HIP library (ss_tune)')
+    ap.add_argument('--full', action='store_true',
+                    help='also everything beyond the headline: the kernel-class survey and the roofline / recurrence brackets in the timed steps, '
+                         'alt_precisions, solver_loop, dp_collectives, dp_replicas and cpu_baseline.  Default: the timed steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, run the last one again from the start state (initial weights, fresh Adam) and write what it '
+                         'computed to DIR/{loss,params,grads}.npy (float32; see dump_outputs)')
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -260,7 +289,10 @@ def main():
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         os.environ.setdefault('MASTER_PORT', '29511')
         dist.init_process_group('nccl', rank=rank, world_size=world, device_id=dev)
-    eng.set_adam(1e-4, 0.9, 0.999, 1e-8, 0)
+    adam = (1e-4, 0.9, 0.999, 1e-8, 0)
+    eng.set_adam(*adam)
+    # --dump-outputs: the state every run starts from, for the replay of the last timed step (see below)
+    start = eng.params.clone() if args.dump_outputs else None
     eng.set_precision(args.precision)
     native = dp and args.dp_backend == 'native'             # the engine's own RCCL communicator, both generators (round 3: ss_g6_dp_train_step)
     if native:
@@ -282,15 +314,24 @@ def main():
         loader = buckets.BucketedDeviceBatcher(hp, corpus, 96, 192, rank=rank, world=world, seed=11, steps_per_epoch=10 ** 9)
         stream = staging.DevicePrefetcher(loader, dev)
 
-    def step():
-        # fresh randomness every step: one global draw stream (the reference's generator calls), each rank takes its utterances' slice
-        sc, ls = draw_interp(B * world, ncalls, hp)
-        if world > 1:
-            sc = sc.view(ncalls, world, B * S)[:, rank]
-            ls = ls.view(ncalls, world, B * S)[:, rank]
-        if stream is not None:                       # config 5: the next length-bucketed batch, already staged on the device
-            bm, be, bf, bl = next(stream)
-            frames_done[0] += bm.shape[1]
+    last = [None]                                   # the draws (and config 5 batch) of the latest step
+
+    def step(replay=None):
+        if replay is None:
+            # fresh randomness every step: one global draw stream (the reference's generator calls), each rank takes its utterances' slice
+            sc, ls = draw_interp(B * world, ncalls, hp)
+            if world > 1:
+                sc = sc.view(ncalls, world, B * S)[:, rank]
+                ls = ls.view(ncalls, world, B * S)[:, rank]
+            batch = None
+            if stream is not None:                   # config 5: the next length-bucketed batch, already staged on the device
+                batch = next(stream)
+                frames_done[0] += batch[0].shape[1]
+            last[0] = (sc, ls, batch)
+        else:
+            sc, ls, batch = replay
+        if stream is not None:
+            bm, be, bf, bl = batch
             if native:
                 eng.dp_train_step_native(bm, bf, be, bl, (sc, ls), bucket=True)
             elif dp:
@@ -343,19 +384,33 @@ def main():
     # stream time (the launch behind it waits for the one in front to retire), all 71 per step +4.5 %, these 18 +2.9 % if every
     # step carried them (5.44 vs 5.29 ms measured in one call) -- sampled, under 0.6 %
     PROF_EVERY = 5
+    profile = args.full and not args.no_profile
     top, survey = None, None
-    if not args.no_profile:
+    if profile:
         timed(6, 2, True)
         survey = (eng.profile_read(), 6)
         top = dominant_class(survey[0])
-    dt = timed(args.steps, args.warmup, None if args.no_profile else [top, 'rec_fwd', 'rec_bwd'], PROF_EVERY)
+    dt = timed(args.steps, args.warmup, [top, 'rec_fwd', 'rec_bwd'] if profile else None, PROF_EVERY)
     bracketed = (args.steps + PROF_EVERY - 1) // PROF_EVERY      # steps of the timed region that carried the brackets
     eng.check()                  # outside the timed region: no persistent kernel reported a bounded-wait expiry
     fallbacks = eng.scratch_fallbacks()      # launches that ran out of scratch and took a slower path: must be 0
+    if args.dump_outputs:
+        # The timed steps' weights and Adam moments drift apart from run to run: split-K atomics commit in arrival order, and Adam turns
+        # that last-bit noise in near-zero gradients into whole lr-sized moves that the next steps carry on.  So the step that is dumped
+        # starts from the state every run starts from (initial weights, Adam moments and step counter zero) and takes the last timed
+        # step's batch and draws: the same inputs every run, through the same path (every rank: the collectives must match)
+        eng.params.copy_(start)
+        eng.adam_m.zero_()
+        eng.adam_v.zero_()
+        eng.set_adam(*adam)
+        step(last[0])
+        eng.check()
+        if rank == 0:
+            dump_outputs(eng, args.dump_outputs)
     # data parallel, native path: where every bucket's collective sat relative to the end of the backward -- hipEvent brackets on the
     # communication stream (ss_dp_profile) over a few steps OUTSIDE the timed region; the record of the last one, from real RCCL kernels
     dp_coll = None
-    if native:
+    if native and args.full:
         eng.dp_profile(True)
         for _ in range(3):
             step()
@@ -373,7 +428,7 @@ def main():
     # data parallel: every rank saw different utterances, so the replicas' weights agree bit for bit only if every bucket was reduced over all
     # ranks and the same update applied -- a 64-bit sum over the weights' bit patterns, gathered from all ranks (outside the timed region)
     dp_rep = None
-    if dist is not None:
+    if dist is not None and args.full:
         torch.cuda.synchronize()
         mine = eng.params.view(torch.int32).to(torch.int64).sum().reshape(1)
         every = [torch.zeros_like(mine) for _ in range(world)]
@@ -393,7 +448,7 @@ def main():
             roof['bracketed_steps'] = f'{bracketed} of the {args.steps} timed steps (every {PROF_EVERY}th: a bracket holds the next launch back by 4-8 us)'
         print(f'[bench] roofline: {roof}', file=sys.stderr, flush=True)
     alt = None
-    if not args.no_extras and args.precision == 'f32' and kind == 'G3' and args.workload == 'fixed':
+    if args.full and not args.no_extras and args.precision == 'f32' and kind == 'G3' and args.workload == 'fixed':
         # the same step with the other product formats of the fp32 mode (every rank runs them: the collectives must match).  Keys say what they
         # switch: the headline multiplies fp16 x 2 pieces (22 significand bits) everywhere;
         #   gemms_bf16x3: the GEMMs on the exact 3-way bf16 split (6 MFMAs), the six persistent recurrences STILL fp16 x 2 (32 % of the MACs);
@@ -408,7 +463,7 @@ def main():
         for name, knobs, restore, peak, basis, what in modes:
             for k, v in knobs.items():
                 tune(k, v)
-            prof = [top] if (top and not args.no_profile) else False
+            prof = [top] if top else False
             ms_alt = round(timed(8, 2, prof) / 8 * 1e3, 3)
             rec_alt = {'ms_per_step': ms_alt, 'utterances_per_s': round(B * world / ms_alt * 1e3, 1), 'what': what}
             if prof and rank == 0:
@@ -422,7 +477,7 @@ def main():
                 tune(k, v)
         eng.check()
     sl = None
-    if rank == 0 and not (args.no_extras or world > 1 or kind != 'G3' or args.workload != 'fixed'):
+    if rank == 0 and args.full and not (args.no_extras or world > 1 or kind != 'G3' or args.workload != 'fixed'):
         # Solver builds its own engine: release this one first (its four streams would otherwise change which hardware queues the
         # second engine's streams land on -- measured 7.4 vs 6.7 ms per iteration)
         eng_hp = eng.hp
@@ -448,7 +503,7 @@ def main():
             'step_tflops': round(3 * 2 * (MAC_PER_FRAME_G3 if kind == 'G3' else MAC_PER_FRAME_G6) * mean_T * B * world / (dt / args.steps) / 1e12, 2),
             'roofline': roof, 'kernel_classes': classes, 'recurrence': recur, 'alt_precisions': alt,
             'solver_loop': sl, 'dp_collectives': dp_coll, 'dp_replicas': dp_rep, 'scratch_fallbacks': fallbacks,
-            'cpu_baseline': None if args.no_cpu_baseline else cpu_baseline(T),
+            'cpu_baseline': cpu_baseline(T) if args.full and not args.no_cpu_baseline else None,
         }
         print(json.dumps(out), flush=True)
     if dist is not None:

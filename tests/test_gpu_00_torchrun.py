@@ -29,7 +29,7 @@ def _free_port():
 def test_bench_dp_path_under_torchrun(extra):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--force-dp', '--steps', '4', '--warmup', '2',
-           '--no-cpu-baseline', '--no-extras'] + extra
+           '--full', '--no-cpu-baseline', '--no-extras'] + extra
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -49,3 +49,35 @@ def test_bench_dp_path_under_torchrun(extra):
         assert dc and len(dc['buckets']) >= 3 and dc['buckets'][-1]['arena_offset'] == -1
         assert all(b['end_us'] >= b['start_us'] for b in dc['buckets'])
         assert sum(b['mbytes'] for b in dc['buckets']) > 10          # the whole gradient arena went through collectives (13.9 / 77.8 MB)
+
+
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, takes none of the --full measurements, and --dump-outputs writes the last
+    timed step's loss and (sampled) parameter / gradient arenas as float32 .npy files, 64 MB at most.  Two runs with the same arguments
+    dump the same outputs up to the summation-order noise of one step: the timed steps' weights drift apart from run to run (split-K
+    atomics, amplified by Adam), so a dump that followed them would differ by whole learning-rate moves."""
+    import numpy as np
+    from conftest import assert_same_trajectory
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f'out{run}'
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '12', '--warmup', '2', '--dump-outputs', str(out_dir)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+        assert out['steps'] == 12 and out['warmup'] == 2 and out['n_gpus'] == 1
+        assert out['unit'] == 'utterances/s' and out['higher_is_better'] is True and out['dtype'].startswith('f32')
+        assert out['ms_per_step'] > 0 and abs(out['value'] - 64 / out['ms_per_step'] * 1e3) <= 1e-3 * out['value'] + 0.1
+        for k in ('roofline', 'kernel_classes', 'recurrence', 'alt_precisions', 'solver_loop', 'cpu_baseline'):
+            assert out[k] is None, k
+        files = {f: np.load(out_dir / f'{f}.npy') for f in ('loss', 'params', 'grads')}
+        assert sum(os.path.getsize(out_dir / f'{f}.npy') for f in files) <= 64 << 20
+        assert files['loss'].shape == (1,) and files['params'].shape == files['grads'].shape == (1 << 22,)
+        for f, a in files.items():
+            assert a.dtype == np.float32 and np.isfinite(a).all(), f
+        assert float(files['loss'][0]) > 0 and np.abs(files['grads']).max() > 0
+        dumps.append(files)
+    a, b = dumps
+    assert abs(float(a['loss'][0]) - float(b['loss'][0])) <= 1e-6 * float(a['loss'][0])
+    assert float(np.abs(a['grads'] - b['grads']).max()) <= 1e-5 * float(np.abs(a['grads']).max())
+    assert_same_trajectory(a['params'], b['params'], steps=1, tag='dumped parameters')

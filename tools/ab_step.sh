@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of ss_tune settings on the training step, one process per setting, same box: bash tools/ab_step.sh <outdir> "k=v k=v" "k=v" ...
-# prints ms/step per setting (bench.py --no-cpu-baseline --no-extras)
+# prints ms/step per setting (bench.py --full --no-cpu-baseline --no-extras)
 O=gpurun_out/$1
 shift
 mkdir -p $O
@@ -8,7 +8,7 @@ i=0
 for cfg in "$@"; do
   args=""
   for kv in $cfg; do [ "$kv" != "-" ] && args="$args --tune $kv"; done
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-extras $args > $O/ab_$i.json 2> $O/ab_$i.err || { echo "FAILED: $cfg"; tail -3 $O/ab_$i.err; }
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-extras $args > $O/ab_$i.json 2> $O/ab_$i.err || { echo "FAILED: $cfg"; tail -3 $O/ab_$i.err; }
   python - "$cfg" $O/ab_$i.json <<'P'
 import json, sys
 try:
