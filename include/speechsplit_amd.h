@@ -74,6 +74,14 @@ int ss_g3_forward(ss_engine* e, const float* x_f0_dev, const float* x_org_dev, c
                   void* stream);
 /* loss.backward() for the last ss_g3_forward: d_out [B,T,80] -> grads arena (overwritten, not accumulated). */
 int ss_g3_backward(ss_engine* e, const float* d_out_dev, void* stream);
+/* ss_g3_backward and, in the same call, the gradients w.r.t. the forward's INPUTS (what x_f0.grad / x_org.grad / c_trg.grad hold after
+ * loss.backward() in the reference): dx_f0 [B,T,337] (80 mel columns, then the 257 one-hot columns), dx_org [B,T,80], dc_trg [B,82] --
+ * caller-owned, dense, overwritten; B and T those of the last ss_g3_forward, training or eval mode alike (training: through each encoder
+ * layer's resampling).  Every output pointer may be NULL; with all three NULL the call is ss_g3_backward, launch for launch.  The parameter
+ * gradients are those of ss_g3_backward.  The input gradients come from the layer-0 convolutions' input-gradient GEMMs (on the streams of
+ * their blocks, joined before the call returns) and one kernel that sums decoder layer 0's gate gradients over time and contracts them with
+ * the speaker columns of W_ih (fixed-order fp32 sums).  Errors (nothing enqueued): a Generator_6 engine, no preceding forward. */
+int ss_g3_backward_inputs(ss_engine* e, const float* d_out_dev, float* dx_f0_dev, float* dx_org_dev, float* dc_trg_dev, void* stream);
 /* G.rhythm(x_org) (model.py:316-320): codes [B, T/8, 2] */
 int ss_g3_rhythm(ss_engine* e, const float* x_org_dev, int B, int T, float* codes_dev, void* stream);
 
@@ -82,6 +90,9 @@ int ss_g3_rhythm(ss_engine* e, const float* x_org_dev, int B, int T, float* code
 int ss_g6_forward(ss_engine* e, const float* x_org_dev, const float* f0_trg_dev, const float* scales_dev,
                   const int* len_seg_dev, int B, int T, int training, float* out_dev, void* stream);
 int ss_g6_backward(ss_engine* e, const float* d_out_dev, void* stream);
+/* ss_g6_backward and the input gradients dx_org [B,T,80], df0_trg [B,T,257] (dense, caller-owned, each may be NULL; all NULL: exactly
+ * ss_g6_backward), as ss_g3_backward_inputs.  Errors (nothing enqueued): a Generator_3 engine, no preceding forward. */
+int ss_g6_backward_inputs(ss_engine* e, const float* d_out_dev, float* dx_org_dev, float* df0_trg_dev, void* stream);
 
 /* ---- Solver.train step body (solver.py:157-172), fused: cat(mel,f0) -> InterpLnr -> quantize_f0 -> G -> mse(mean)
  *      -> backward -> Adam.  mel [B,T,80], f0 [B,T,1] (-1e10 = unvoiced), emb [B,82], len_org i32[B];

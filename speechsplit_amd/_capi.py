@@ -36,9 +36,11 @@ SYMBOLS = {
     'ss_bind': (_i, [_vp, _fp, _fp, _fp, _fp, _vp, _l, _vp]),
     'ss_g3_forward': (_i, [_vp, _fp, _fp, _fp, _fp, _ip, _i, _i, _i, _fp, _vp]),
     'ss_g3_backward': (_i, [_vp, _fp, _vp]),
+    'ss_g3_backward_inputs': (_i, [_vp, _fp, _fp, _fp, _fp, _vp]),
     'ss_g3_rhythm': (_i, [_vp, _fp, _i, _i, _fp, _vp]),
     'ss_g6_forward': (_i, [_vp, _fp, _fp, _fp, _ip, _i, _i, _i, _fp, _vp]),
     'ss_g6_backward': (_i, [_vp, _fp, _vp]),
+    'ss_g6_backward_inputs': (_i, [_vp, _fp, _fp, _fp, _vp]),
     'ss_g3_train_step': (_i, [_vp, _fp, _fp, _fp, _ip, _fp, _ip, _i, _i, _f, _i, _fp, _vp]),
     'ss_g6_train_step': (_i, [_vp, _fp, _fp, _ip, _fp, _ip, _i, _i, _f, _i, _fp, _vp]),
     'ss_train_finish': (_i, [_vp, _f, _i, _vp]),

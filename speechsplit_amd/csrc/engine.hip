@@ -161,6 +161,11 @@ struct ConvBlk {
     int amax_i = -1;                       // slot in ss_engine::amax
     int scale_i = -1;                      // slot in ss_engine::act_scale (scale of the fp16 x 2 split of this block's OUTPUT)
     bool need_dx = false;
+    // input gradient w.r.t. the NETWORK input (layer-0 blocks, ss_g*_backward_inputs): wb0 holds the flipped taps [Ci][5][Co] (packed
+    // when asked); dx_out (null: not asked) receives it dense, row stride dx_ld, [B][T] rows -- set for one backward call only
+    float* wb0 = nullptr;
+    float* dx_out = nullptr;
+    long dx_ld = 0;
     bool img_ok() const { return Cp % 8 == 0 && Co % 8 == 0; }       // wf_img / wb_img are written (rows of whole image groups)
 };
 
@@ -617,6 +622,9 @@ long ss_engine::carve(int B, int T, bool assign) {
         plan[i].counts = (int*)take((long)B * 4);
         plan[i].start = (int*)take((long)B * (T + 1) * 4);
     }
+    // flipped taps of the layer-0 blocks' input-gradient GEMMs (ss_g*_backward_inputs only): last in the plan, so every slab above
+    // keeps its place.  Three blocks may run at once on different streams, hence one each (2.3 MB for Generator_3).
+    for (ConvBlk* cb : {&c1[0], &c2[0], &ct}) cb->wb0 = cb->Co ? (float*)take((long)cb->Ci * 5 * cb->Co * 4) : nullptr;
     return off;
 }
 
@@ -1207,6 +1215,28 @@ conv_dw_done:
         g.amax_a = am;
         g.want = g_conv_want;
         flatten_rows(g, B, T);
+        PGEMM_ON(SS_PROF_CONV_DX, g, s);
+    }
+    if (cb.dx_out) {
+        // the block's input is the network input (ss_g*_backward_inputs): the same contraction against taps packed for this call (the forward
+        // packs none for layer 0), stored straight into the caller's dense [B][T] rows -- per-utterance batches of T rows, so no halo row is
+        // ever computed or stored, and the halo rows of dy (zero) are what the taps past either end of an utterance read
+        if (!cb.wb0) return fail("internal: input gradient asked of a conv block without its tap buffer");
+        HIPCHK(conv_pack_dx(e->P + cb.w, cb.Co, cb.Ci, cb.wb0, s));
+        GemmDesc g{};
+        g.A = {dy.p, dy.ld, TP * dy.ld, cb.Co, dy.ld};
+        g.B = {cb.wb0, 5L * cb.Co, 0, 0, 0};
+        g.C = cb.dx_out;
+        g.ldc = cb.dx_ld;
+        g.cstride = (long)T * cb.dx_ld;
+        g.M = T;
+        g.N = cb.Ci;
+        g.K = 5 * cb.Co;
+        g.batch = B;
+        g.ksplit = 1;
+        g.flags = am ? GEMM_F16X2 : 0;
+        g.amax_a = am;
+        g.want = g_conv_want;
         PGEMM_ON(SS_PROF_CONV_DX, g, s);
     }
     return 0;
@@ -2394,6 +2424,33 @@ int backward_core(ss_engine* e, hipStream_t s) {
     return backward_encoder(e, s);
 }
 
+// Generator_3's speaker embedding enters decoder layer 0 as the last dim_spk_emb columns of every frame's input row (model.py:308-309):
+// dc[b][j] = sum_t sum_g dG0[b][t][g] * W_ih0[g][xcols + j] over both directions' gate rows.  dG0 summed over time first -- from the
+// block sums of the compact layer 0, or from the layer's full pre-activation gradient slab -- then contracted with the 82 columns.
+int speaker_input_grad(ss_engine* e, float* dc, hipStream_t s) {
+    LstmBlk& lb = e->ld;
+    const int B = e->curB, T = e->curT, H = lb.H;
+    const long TP = T + 2 * HALO;
+    const bool compact = dec_compact(e);
+    const float* dg = compact ? lb.dgs : lb.gates[0] + HALO * 8L * H;
+    const long bs = compact ? (long)(T / lb.xf) * 8 * H : TP * 8L * H;
+    const int rows = compact ? T / lb.xf : T;
+    if (!compact && (e->dg32_skipped & 1)) return fail("internal: decoder layer 0's fp32 gradient slab was not written");
+    HIPCHK(spk_grad(dg, 8L * H, bs, rows, e->P + lb.pd[0].wih, e->P + lb.pd[1].wih, lb.In, lb.xcols, 4 * H, e->hp.dim_spk_emb, dc, B, s));
+    return 0;
+}
+
+// one ss_g*_backward_inputs call: the layer-0 blocks' input-gradient targets are set for its backward and cleared on every way out
+struct InputGradTargets {
+    ss_engine* e;
+    ~InputGradTargets() {
+        for (ConvBlk* cb : {&e->c1[0], &e->c2[0], &e->ct}) {
+            cb->dx_out = nullptr;
+            cb->dx_ld = 0;
+        }
+    }
+};
+
 }  // namespace
 
 // ================================================================================================ C ABI
@@ -2670,6 +2727,26 @@ int ss_g3_backward(ss_engine* e, const float* d_out, void* stream) {
     return backward_core(e, s);
 }
 
+int ss_g3_backward_inputs(ss_engine* e, const float* d_out, float* dx_f0, float* dx_org, float* dc_trg, void* stream) {
+    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_backward_inputs on a Generator_6 engine");
+    if (!e->have_fwd) return fail("backward without a preceding forward");
+    Own own(e, stream);
+    hipStream_t s = own.s;
+    const ss_hparams& h = e->hp;
+    const int CI = h.dim_freq + h.dim_f0;
+    InputGradTargets tg{e};
+    e->c1[0].dx_out = dx_f0;                                 // x_f0 = [mel 80 | f0 one-hot 257]: the content stack's input ...
+    e->c1[0].dx_ld = CI;
+    e->c2[0].dx_out = dx_f0 ? dx_f0 + h.dim_freq : nullptr;  // ... and the pitch stack's, side by side in one row
+    e->c2[0].dx_ld = CI;
+    e->ct.dx_out = dx_org;
+    e->ct.dx_ld = h.dim_freq;
+    CHK(import_dout(e, d_out, e->curB, e->curT, s));
+    CHK(backward_core(e, s));
+    if (dc_trg) CHK(speaker_input_grad(e, dc_trg, s));
+    return 0;
+}
+
 int ss_g3_rhythm(ss_engine* e, const float* x_org, int B, int T, float* codes, void* stream) {
     if (e->kind != SS_GENERATOR_3) return fail("ss_g3_rhythm on a Generator_6 engine");
     Own own(e, stream);
@@ -2721,6 +2798,20 @@ int ss_g6_backward(ss_engine* e, const float* d_out, void* stream) {
     Own own(e, stream);
     hipStream_t s = own.s;
     if (!e->have_fwd) return fail("backward without a preceding forward");
+    CHK(import_dout(e, d_out, e->curB, e->curT, s));
+    return backward_core(e, s);
+}
+
+int ss_g6_backward_inputs(ss_engine* e, const float* d_out, float* dx_org, float* df0_trg, void* stream) {
+    if (e->kind != SS_GENERATOR_6) return fail("ss_g6_backward_inputs on a Generator_3 engine");
+    if (!e->have_fwd) return fail("backward without a preceding forward");
+    Own own(e, stream);
+    hipStream_t s = own.s;
+    InputGradTargets tg{e};
+    e->c2[0].dx_out = df0_trg;                               // Encoder_6's stack (model.py:123-140)
+    e->c2[0].dx_ld = e->hp.dim_f0;
+    e->ct.dx_out = dx_org;                                   // Encoder_t
+    e->ct.dx_ld = e->hp.dim_freq;
     CHK(import_dout(e, d_out, e->curB, e->curT, s));
     return backward_core(e, s);
 }

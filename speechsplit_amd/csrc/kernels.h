@@ -254,4 +254,12 @@ int lstm_seq_free_xcds(int B, int H);
 // narrow ones [rows][cn] (cell states; output gradient), both ends of the sequence first.  Meant for a side stream, beside the recurrence.
 hipError_t slab_prewarm(const float* wide, int cw, const float* n0, const float* n1, int cn, float* sink, int B, int T, bool time_major, hipStream_t s);
 
+// ---------------------------------------------------------------- input_grads.hip (gradients w.r.t. the network inputs, on request)
+// conv weight [Co][Ci][5] -> input-gradient pack wb [Ci][5][Co] (taps flipped) alone, any Ci / Co (the layer-0 blocks)
+hipError_t conv_pack_dx(const float* w, int Co, int Ci, float* wb, hipStream_t s);
+// out[b][j] = sum_{r < rows} sum_{g < 2 * H4} dg[b * b_stride + r * ld + g] * W(g, col0 + j), W = [w_f ; w_r] ([H4][w_ld] each), j < E:
+// the gradient of a per-utterance input row that a BLSTM layer sees at every frame (the decoder's speaker columns).  Fixed-order fp32 sums.
+hipError_t spk_grad(const float* dg, long ld, long b_stride, int rows, const float* w_f, const float* w_r, long w_ld, int col0, int H4, int E,
+                    float* out, int B, hipStream_t s);
+
 }  // namespace ss

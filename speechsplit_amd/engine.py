@@ -41,6 +41,7 @@ class Engine:
         self.max_batch = int(max_batch)
         self.max_frames = int(max_frames or hp.max_len_pad)
         self._stagers = {}
+        self._fwd_bt = None                # (B, T) of the last g3_forward / g6_forward; None after any other forward
         self._hps = _capi.hparams_struct(hp)
         self.h = self.lib.ss_create(KIND[kind], C.byref(self._hps), self.max_batch, self.max_frames)
         if not self.h:
@@ -124,15 +125,42 @@ class Engine:
             c_trg = c_trg.expand(B, -1).contiguous()
         sc, ls = self._draws(draws)
         out = torch.empty(B, T, self.hp.dim_freq, device=self.device)
+        self._fwd_bt = None
         _capi.check(self.lib.ss_g3_forward(self.h, _ptr(x_f0), _ptr(x_org), _ptr(c_trg), _ptr(sc), _ptr(ls), B, T,
                                            int(training), _ptr(out), _stream()))
+        self._fwd_bt = (B, T)
         return out
 
-    def g3_backward(self, d_out):
+    G3_INPUTS = ('x_f0', 'x_org', 'c_trg')
+    G6_INPUTS = ('x_org', 'f0_trg')
+
+    def _input_grad_buffers(self, names, inputs):
+        """Fresh dense outputs for the requested input gradients of the last forward, in the entry point's order (None: not asked for)."""
+        unknown = set(inputs) - set(names)
+        if unknown:
+            raise ValueError(f'speechsplit_amd: no input named {sorted(unknown)} (expected some of {names})')
+        if self._fwd_bt is None:
+            raise RuntimeError('speechsplit_amd: input gradients need a preceding g3_forward / g6_forward on this engine')
+        B, T = self._fwd_bt
+        hp = self.hp
+        shape = {'x_f0': (B, T, hp.dim_freq + hp.dim_f0), 'x_org': (B, T, hp.dim_freq), 'c_trg': (B, hp.dim_spk_emb),
+                 'f0_trg': (B, T, hp.dim_f0)}
+        return tuple(torch.empty(shape[n], device=self.device) if n in inputs else None for n in names)
+
+    def g3_backward(self, d_out, inputs=()):
+        """loss.backward() for the last g3_forward: parameter gradients into the arena.  inputs: names among G3_INPUTS whose gradients
+        are wanted as well (ss_g3_backward_inputs); they come back as fresh tensors (dx_f0, dx_org, dc_trg), None where not asked for.
+        Without inputs the call is ss_g3_backward and returns None."""
         d_out = self._f(d_out)
-        _capi.check(self.lib.ss_g3_backward(self.h, _ptr(d_out), _stream()))
+        if not inputs:
+            _capi.check(self.lib.ss_g3_backward(self.h, _ptr(d_out), _stream()))
+            return None
+        dx_f0, dx_org, dc_trg = self._input_grad_buffers(self.G3_INPUTS, inputs)
+        _capi.check(self.lib.ss_g3_backward_inputs(self.h, _ptr(d_out), _ptr(dx_f0), _ptr(dx_org), _ptr(dc_trg), _stream()))
+        return dx_f0, dx_org, dc_trg
 
     def g3_rhythm(self, x_org):
+        self._fwd_bt = None
         B, T, _ = x_org.shape
         x_org = self._f(x_org)
         codes = torch.empty(B, T // self.hp.freq_2, 2 * self.hp.dim_neck_2, device=self.device)
@@ -144,6 +172,7 @@ class Engine:
         self.grad_split) are complete; train_finish() then runs the encoder backward (data-parallel overlap).
         bucket: the batch's frame count is its length bucket and the step runs with max_len_pad = T (SS_STEP_BUCKET)."""
         B, T, _ = mel.shape
+        self._fwd_bt = None
         mel, f0, emb, len_org = self._f(mel), self._f(f0), self._f(emb), self._i(len_org)
         sc, ls = self._draws(draws)
         assert sc.shape[0] == 4 and ls.shape[0] == 4
@@ -175,6 +204,7 @@ class Engine:
         schedule='join': SS_STEP_SPLIT_BACKWARD joins the engine streams, first bucket reduced right away (+0.6 ms at world 1:
             the decoder's weight-gradient GEMMs then run alone instead of beside the encoder backward)."""
         from . import dist as D
+        self._fwd_bt = None
         k = self.grad_split
         plan = D.bucket_plan(self.grads.numel(), k)
         side = self.lib.ss_side_stream(self.h) if schedule == 'overlap' else None
@@ -263,6 +293,7 @@ class Engine:
     def dp_train_step_native(self, mel, f0, emb, len_org, draws, bucket=False):
         """ss_g3_dp_train_step: the overlapped two-bucket schedule with the collectives launched by the engine itself, the
         decoder bucket ON the engine stream that carries the decoder's weight-gradient GEMMs."""
+        self._fwd_bt = None
         B, T, _ = mel.shape
         mel, f0, emb, len_org = self._f(mel), self._f(f0), self._f(emb), self._i(len_org)
         sc, ls = self._draws(draws)
@@ -276,15 +307,24 @@ class Engine:
         x_org, f0_trg = self._f(x_org), self._f(f0_trg)
         sc, ls = self._draws(draws)
         out = torch.empty(B, T, self.hp.dim_f0, device=self.device)
+        self._fwd_bt = None
         _capi.check(self.lib.ss_g6_forward(self.h, _ptr(x_org), _ptr(f0_trg), _ptr(sc), _ptr(ls), B, T, int(training),
                                            _ptr(out), _stream()))
+        self._fwd_bt = (B, T)
         return out
 
-    def g6_backward(self, d_out):
+    def g6_backward(self, d_out, inputs=()):
+        """As g3_backward for Generator_6: inputs among G6_INPUTS, returns (dx_org, df0_trg) when any is asked for."""
         d_out = self._f(d_out)
-        _capi.check(self.lib.ss_g6_backward(self.h, _ptr(d_out), _stream()))
+        if not inputs:
+            _capi.check(self.lib.ss_g6_backward(self.h, _ptr(d_out), _stream()))
+            return None
+        dx_org, df0_trg = self._input_grad_buffers(self.G6_INPUTS, inputs)
+        _capi.check(self.lib.ss_g6_backward_inputs(self.h, _ptr(d_out), _ptr(dx_org), _ptr(df0_trg), _stream()))
+        return dx_org, df0_trg
 
     def g6_train_step(self, mel, f0_onehot, target_idx, draws, grad_scale=1.0, no_adam=False, bucket=False):
+        self._fwd_bt = None
         B, T, _ = mel.shape
         mel, f0_onehot, target_idx = self._f(mel), self._f(f0_onehot), self._i(target_idx)
         sc, ls = self._draws(draws)
@@ -295,6 +335,7 @@ class Engine:
     def g6_dp_train_step_native(self, mel, f0_onehot, target_idx, draws, bucket=False):
         """ss_g6_dp_train_step: Generator_6's data-parallel step with the engine's own RCCL communicator (per-layer buckets on the
         engine's communication stream), as dp_train_step_native for Generator_3."""
+        self._fwd_bt = None
         B, T, _ = mel.shape
         mel, f0_onehot, target_idx = self._f(mel), self._f(f0_onehot), self._i(target_idx)
         sc, ls = self._draws(draws)

@@ -108,10 +108,31 @@ def init_weights(kind, hp, seed=0):
         return {name: _init_tensor(shape, init) for name, shape, init in _spec(kind, hp)}
 
 
+def _input_grads(ctx, grads):
+    """The engine's input gradients in the inputs' own shape, dtype and device.  An input the engine broadcast over the batch (a [1, C]
+    speaker row with B > 1, Engine.g3_forward) gets the sum over the batch."""
+    out = []
+    for i, g in enumerate(grads):
+        if g is None:
+            out.append(None)
+            continue
+        shape, dtype, device = ctx.in_meta[i]
+        if g.shape[0] != shape[0]:
+            g = g.sum(0, keepdim=True)
+        out.append(g.reshape(shape).to(device=device, dtype=dtype))
+    return tuple(out)
+
+
+def _wanted(ctx, first, names):
+    """Names of the inputs (autograd positions first, first + 1, ...) whose gradient autograd asks for."""
+    return tuple(n for i, n in enumerate(names) if ctx.needs_input_grad[first + i])
+
+
 class _G3Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, x_f0, x_org, c_trg, draws, *params):
         ctx.mod = mod
+        ctx.in_meta = [(t.shape, t.dtype, t.device) for t in (x_f0, x_org, c_trg)]
         out = mod._eng.g3_forward(x_f0, x_org, c_trg, draws, training=mod.training)
         ctx.nparams = len(params)
         return out
@@ -119,25 +140,32 @@ class _G3Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_out):
         mod = ctx.mod
-        mod._eng.g3_backward(d_out.contiguous())
+        names = mod._eng.G3_INPUTS
+        want = _wanted(ctx, 1, names)
+        gi = mod._eng.g3_backward(d_out.contiguous(), inputs=want)
+        dx = _input_grads(ctx, gi) if want else (None, None, None)
         flat = mod._eng.grads.clone()                 # fresh storage: autograd may keep or accumulate these
         gv = mod._eng.views(flat)
-        return (None, None, None, None, None) + tuple(gv[n] for n in mod._names)
+        return (None,) + dx + (None,) + tuple(gv[n] for n in mod._names)
 
 
 class _G6Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, x_org, f0_trg, draws, *params):
         ctx.mod = mod
+        ctx.in_meta = [(t.shape, t.dtype, t.device) for t in (x_org, f0_trg)]
         return mod._eng.g6_forward(x_org, f0_trg, draws, training=mod.training)
 
     @staticmethod
     def backward(ctx, d_out):
         mod = ctx.mod
-        mod._eng.g6_backward(d_out.contiguous())
+        names = mod._eng.G6_INPUTS
+        want = _wanted(ctx, 1, names)
+        gi = mod._eng.g6_backward(d_out.contiguous(), inputs=want)
+        dx = _input_grads(ctx, gi) if want else (None, None)
         flat = mod._eng.grads.clone()
         gv = mod._eng.views(flat)
-        return (None, None, None, None) + tuple(gv[n] for n in mod._names)
+        return (None,) + dx + (None,) + tuple(gv[n] for n in mod._names)
 
 
 class _EngineModule(nn.Module):
