@@ -9,7 +9,12 @@
  *   - return value 0 = ok, negative = error, text via ss_last_error() (no C++ exceptions cross the ABI);
  *   - one engine per device per process; an engine is not thread-safe;
  *   - tensors are contiguous fp32, batch-first [B, T, C] exactly as the reference passes them (model.py:297,337);
- *   - T must be a multiple of the code down-sampling factor 8 (model.py:87,223-227) and <= max_frames;
+ *   - T must be a multiple of the code down-sampling factor 8 (model.py:87,223-227) and <= max_frames, except in the
+ *     eval-mode forwards (ss_g3_forward / ss_g6_forward with training == 0, ss_g3_rhythm), which take any T up to
+ *     SS_MAX_EVAL_FRAMES whose plan (ss_plan_bytes) fits the bound workspace -- long utterances, as the reference runs them
+ *     (InterpLnr is the identity in eval mode, model.py:382-383).  Everything that trains or differentiates (train-mode
+ *     forwards, ss_*_backward*, ss_*_train_step, the data-parallel steps, SS_STEP_BUCKET, ss_interp_*) keeps T <= max_frames
+ *     (<= 256) and refuses more up front, nothing enqueued, the engine usable afterwards;
  *   - the random-resampling draws of InterpLnr (model.py:392-393 rand(B*7)+0.5; :399-402 randint) are INPUTS:
  *     `scales` f32 and `len_seg` i32, one [B*7] row per InterpLnr call in call order.  Given equal draws the
  *     index path is bit-exact against the reference.
@@ -47,6 +52,8 @@ typedef struct ss_hparams {
                              encoders' len_org equals it, model.py:105,157,370).  T % 8 == 0, T <= max_frames.  A
                              bucket change re-plans the workspace (one memset, 0.1 - 0.2 ms at batch 64). */
 
+#define SS_MAX_EVAL_FRAMES 8192 /* longest T an eval-mode forward accepts (131 s at a 16 ms hop) */
+
 const char* ss_last_error(void);
 int ss_abi_version(void);
 
@@ -60,11 +67,21 @@ int ss_num_params(const ss_engine* e);
 int ss_param_info(const ss_engine* e, int index, char* name, int name_cap, long* offset, int* ndim, long shape[3]);
 long ss_arena_numel(const ss_engine* e);     /* floats per arena, alignment gaps included */
 long ss_workspace_bytes(const ss_engine* e); /* activation workspace for (max_batch, max_frames) */
+/* Workspace bytes an eval-mode forward of shape (B, T) needs (its activation plan plus the split-K scratch; host only, nothing
+ * touched): 1 <= B <= max_batch, 8 <= T <= SS_MAX_EVAL_FRAMES, T a multiple of the code factors.  -1 (ss_last_error) otherwise.
+ * ss_plan_bytes(e, max_batch, max_frames) == ss_workspace_bytes(e).  A bound workspace serves every (B, T) whose plan fits it:
+ * a 16 x 192 Generator_3 workspace holds a 1 x 2000 forward. */
+long ss_plan_bytes(const ss_engine* e, int B, int T);
 
 /* .to(device) (solver.py:65): adopt caller-allocated device memory.  All four arenas hold ss_arena_numel floats.
  * The workspace is zero-filled here. */
 int ss_bind(ss_engine* e, float* params_dev, float* grads_dev, float* adam_m_dev, float* adam_v_dev, void* workspace_dev,
             long workspace_bytes, void* stream);
+/* Move a bound engine to another (larger) workspace, e.g. of ss_plan_bytes(e, B, T) bytes for a long eval-mode forward.  At least
+ * ss_workspace_bytes(e) bytes, 256-byte aligned.  The Adam state (step count, hyper-parameters) carries across; the parameter,
+ * gradient and Adam arenas stay where they are; the rest of the new workspace is zero-filled and the next call re-plans its shape.
+ * Synchronises `stream` and the engine's own streams first: the old workspace is unused once the call returns. */
+int ss_set_workspace(ss_engine* e, void* workspace_dev, long workspace_bytes, void* stream);
 
 /* ---- Generator_3 (model.py:297-320) ---- */
 /* G(x_f0, x_org, c_trg): x_f0 [B,T,337] = [mel 80 | f0 one-hot 257], x_org [B,T,80], c_trg [B,82] -> out [B,T,80].
@@ -256,7 +273,8 @@ int ss_op_gemm_img(const float* a_img_dev, long lda, const float* b_img_dev, lon
                    const void* zeros_dev, void* stream);
 /* One relu(GroupNorm(ConvNorm(x))) block (model.py:61-67,76-77; 16 channels per group) through the engine's own block
  * routines, forward and -- when dy is given -- backward.  x [B,T,Ci], w [Co,Ci,5], bias/gamma/beta [Co], y/dy [B,T,Co],
- * dx [B,T,Ci] (nullable), gw [Co,Ci,5], gb/ggamma/gbeta [Co]; scratch of ss_op_conv_block_scratch() floats. */
+ * dx [B,T,Ci] (nullable), gw [Co,Ci,5], gb/ggamma/gbeta [Co]; scratch of ss_op_conv_block_scratch() floats.  T <= 256 with a
+ * backward; forward only (dy NULL) up to SS_MAX_EVAL_FRAMES, where the GroupNorm runs the chunked long-sequence kernels. */
 long ss_op_conv_block_scratch(int B, int T, int Ci, int Co);
 int ss_op_conv_block(const float* x_dev, const float* w_dev, const float* bias_dev, const float* gamma_dev, const float* beta_dev,
                      const float* dy_dev, float* y_dev, float* dx_dev, float* gw_dev, float* gb_dev, float* ggamma_dev,

@@ -33,6 +33,8 @@ SYMBOLS = {
     'ss_param_info': (_i, [_vp, _i, C.c_char_p, _i, C.POINTER(_l), C.POINTER(_i), C.POINTER(_l * 3)]),
     'ss_arena_numel': (_l, [_vp]),
     'ss_workspace_bytes': (_l, [_vp]),
+    'ss_plan_bytes': (_l, [_vp, _i, _i]),
+    'ss_set_workspace': (_i, [_vp, _vp, _l, _vp]),
     'ss_bind': (_i, [_vp, _fp, _fp, _fp, _fp, _vp, _l, _vp]),
     'ss_g3_forward': (_i, [_vp, _fp, _fp, _fp, _fp, _ip, _i, _i, _i, _fp, _vp]),
     'ss_g3_backward': (_i, [_vp, _fp, _vp]),

@@ -16,6 +16,15 @@ from .utils import pad_seq_to_2, quantize_f0_numpy
 CONDITIONS = ['R', 'F', 'U', 'RF', 'RU', 'FU', 'RFU']
 
 
+def conversion_frames(lengths, max_len_pad=192):
+    """Frames every utterance of one conversion is padded to.  The notebook's ``max_len_pad`` (192) when all of them fit, so
+    short pairs give the notebook's results; otherwise the smallest multiple of 8 (the code down-sampling factor) that holds the
+    longest: the batched Generator_3 call needs one T for both utterances, as the reference's does.  Frames beyond the engine's
+    max_frames run in eval mode (Engine.reserve grows the workspace)."""
+    longest = max(int(n) for n in lengths)
+    return int(max_len_pad) if longest <= max_len_pad else -(-longest // 8) * 8
+
+
 def _prepare(entry, max_len_pad, device):
     mel, f0, length, uid = entry[2]
     mel_pad, _ = pad_seq_to_2(mel[np.newaxis, :, :], max_len_pad)
@@ -26,7 +35,11 @@ def _prepare(entry, max_len_pad, device):
 
 
 def convert_f0(P, uttr_org_pad, f0_trg_onehot):
-    """Generator_6 as F0 converter: logits -> argmax -> one-hot [1, T, 257]; also returns the class indices."""
+    """Generator_6 as F0 converter: logits -> argmax -> one-hot [1, T, 257]; also returns the class indices.  Both inputs are
+    padded to one T (conversion_frames: any length, eval mode); a mismatch is refused."""
+    if uttr_org_pad.shape[1] != f0_trg_onehot.shape[1]:
+        raise ValueError('convert_f0: pad both utterances to conversion_frames() of their lengths '
+                         f'(got {uttr_org_pad.shape[1]} and {f0_trg_onehot.shape[1]} frames)')
     with torch.no_grad():
         f0_pred = P(uttr_org_pad, f0_trg_onehot)[0]
         idx = f0_pred.argmax(dim=-1)
@@ -35,9 +48,11 @@ def convert_f0(P, uttr_org_pad, f0_trg_onehot):
 
 
 def demo_conversion(G, P, sbmt_i, sbmt_j, max_len_pad=192, device='cuda:0', conditions=CONDITIONS):
-    """G: Generator_3, P: Generator_6 (both in eval mode, on `device`).  Returns [(name, mel ndarray[len, 80])]."""
-    x_org, oh_org, emb_org, len_org, uid_org = _prepare(sbmt_i, max_len_pad, device)
-    x_trg, oh_trg, emb_trg, len_trg, _ = _prepare(sbmt_j, max_len_pad, device)
+    """G: Generator_3, P: Generator_6 (both in eval mode, on `device`).  Returns [(name, mel ndarray[len, 80])].
+    Both utterances are padded to conversion_frames(): max_len_pad when they fit, else one common multiple of 8."""
+    T = conversion_frames((sbmt_i[2][2], sbmt_j[2][2]), max_len_pad)
+    x_org, oh_org, emb_org, len_org, uid_org = _prepare(sbmt_i, T, device)
+    x_trg, oh_trg, emb_trg, len_trg, _ = _prepare(sbmt_j, T, device)
     oh_con, _ = convert_f0(P, x_org, oh_trg)
     xf_org, xf_trg = torch.cat((x_org, oh_org), -1), torch.cat((x_org, oh_con), -1)
     x_f0 = torch.cat([xf_trg if 'F' in c else xf_org for c in conditions])

@@ -98,6 +98,126 @@ __global__ __launch_bounds__(256) void gn_relu_fwd_kernel(const float* __restric
     }
 }
 
+// ---- GroupNorm + ReLU forward for T > 16 * GN_MAXIT (eval-mode inference of long utterances)
+// The (T x 64) slab no longer fits in registers, so the sequence is cut into chunks of GN_CHUNK rows and three launches walk it, one
+// workgroup per (chunk, 64 channels, utterance): (1) float64 group sums per chunk, (2) float64 sums of (x - mean)^2 per chunk with the
+// mean of (1), (3) normalise + affine + ReLU.  Launches (2) and (3) each reduce the chunk partials of their four groups in chunk order,
+// so every workgroup computes the same mean / rstd bits and repeated runs are identical (no atomics).  The statistics take the register
+// kernel's roundings: mean = float(sum) * inv_n, var = float(sum of squares) * inv_n, rstd = 1 / sqrtf(var + eps); outputs go through
+// gn_h / gn_z.  Thread (rg, l16) as in gn_relu_fwd_kernel: float4 channel slot l16 of rows rg, rg + 16, ... of the chunk.
+constexpr int GN_CHUNK = 64;
+constexpr int GN_MAXCH = 128;    // chunks: T <= 8192 (SS_MAX_EVAL_FRAMES)
+
+// the four group sums of the workgroup in float64, in a fixed order: red[256] partials, thread tid < 4 returns group tid's sum
+__device__ __forceinline__ double block_group_sum_d(double v, double* red, int tid) {
+    red[tid] = v;
+    __syncthreads();
+    double s = 0.0;
+    if (tid < 4)
+        for (int rg = 0; rg < 16; ++rg)
+#pragma unroll
+            for (int l = 0; l < 4; ++l) s += red[rg * 16 + tid * 4 + l];
+    return s;
+}
+
+// the chunk partials of the workgroup's four groups (rows grow0 .. grow0 + 3 of part), loaded by the whole workgroup into ps; thread
+// tid < 4 then returns group tid's sum, added in chunk order
+__device__ __forceinline__ double chunk_sum(const double* __restrict__ part, long grow0, int nch, double* ps, int tid) {
+    for (int i = tid; i < 4 * nch; i += 256) ps[i] = part[grow0 * nch + i];
+    __syncthreads();
+    double s = 0.0;
+    if (tid < 4)
+        for (int k = 0; k < nch; ++k) s += ps[tid * nch + k];
+    return s;
+}
+
+// pass 0: sum of x; pass 1: sum of (x - mean)^2 (mean from the pass-0 partials in part0).  part_out[(b * C/16 + g) * nch + chunk]
+template <int PASS>
+__global__ __launch_bounds__(256) void gn_long_stats_kernel(const float* __restrict__ x, long x_ld, long x_bs, const double* __restrict__ part0,
+                                                            double* __restrict__ part_out, int T, int C) {
+    __shared__ double red[256];
+    __shared__ double ps[4 * GN_MAXCH];
+    __shared__ float m4[4];
+    const int tid = threadIdx.x, l16 = tid & 15, rg = tid >> 4;
+    const int chunk = blockIdx.x, nch = gridDim.x, b = blockIdx.z;
+    const int c = blockIdx.y * 64 + l16 * 4;
+    const long G = C >> 4;
+    const long grow0 = (long)b * G + blockIdx.y * 4;          // first of the workgroup's four groups
+    const float inv_n = 1.0f / (16.0f * (float)T);
+    if (PASS == 1) {
+        const double sum = chunk_sum(part0, grow0, nch, ps, tid);
+        if (tid < 4) m4[tid] = (float)sum * inv_n;
+        __syncthreads();
+    }
+    const float mean = PASS == 1 ? m4[l16 >> 2] : 0.f;
+    const float* xb = x + b * x_bs + (long)HALO * x_ld + c;
+    double s = 0.0;
+#pragma unroll
+    for (int it = 0; it < GN_CHUNK / 16; ++it) {
+        const int t = chunk * GN_CHUNK + rg + it * 16;
+        if (t < T) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (long)t * x_ld);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (PASS == 0) {
+                    s += (double)v[j];
+                } else {
+                    const double d = (double)__fsub_rn(v[j], mean);
+                    s += d * d;
+                }
+            }
+        }
+    }
+    const double gs = block_group_sum_d(s, red, tid);
+    if (tid < 4) part_out[(grow0 + tid) * nch + chunk] = gs;
+}
+
+__global__ __launch_bounds__(256) void gn_long_out_kernel(const float* __restrict__ x, long x_ld, long x_bs, float* __restrict__ y, long y_ld, long y_bs,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ stats,
+                                                          const double* __restrict__ part0, const double* __restrict__ part1, int T, int C) {
+    __shared__ double ps[2][4 * GN_MAXCH];
+    __shared__ float m4[4], r4[4];
+    const int tid = threadIdx.x, l16 = tid & 15, rg = tid >> 4;
+    const int chunk = blockIdx.x, nch = gridDim.x, b = blockIdx.z;
+    const int c = blockIdx.y * 64 + l16 * 4;
+    const long G = C >> 4;
+    const long grow0 = (long)b * G + blockIdx.y * 4;
+    const float inv_n = 1.0f / (16.0f * (float)T);
+    const double sum = chunk_sum(part0, grow0, nch, ps[0], tid);
+    const double sum2 = chunk_sum(part1, grow0, nch, ps[1], tid);
+    if (tid < 4) {
+        const float mean = (float)sum * inv_n;
+        const float var = (float)sum2 * inv_n;
+        const float rstd = 1.0f / sqrtf(var + GN_EPS);
+        m4[tid] = mean;
+        r4[tid] = rstd;
+        if (chunk == 0) {
+            stats[(grow0 + tid) * 2 + 0] = mean;
+            stats[(grow0 + tid) * 2 + 1] = rstd;
+        }
+    }
+    __syncthreads();
+    const float mean = m4[l16 >> 2], rstd = r4[l16 >> 2];
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c);
+    const f32x4 be = *reinterpret_cast<const f32x4*>(beta + c);
+    const float* xb = x + b * x_bs + (long)HALO * x_ld + c;
+    float* yb = y + b * y_bs + (long)HALO * y_ld + c;
+#pragma unroll
+    for (int it = 0; it < GN_CHUNK / 16; ++it) {
+        const int t = chunk * GN_CHUNK + rg + it * 16;
+        if (t < T) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (long)t * x_ld);
+            f32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float z = gn_z(gn_h(v[j], mean, rstd), ga[j], be[j]);
+                o[j] = z > 0.f ? z : 0.f;
+            }
+            *reinterpret_cast<f32x4*>(yb + (long)t * y_ld) = o;
+        }
+    }
+}
+
 // GroupNorm + ReLU + the random resampling that follows it in a training forward (model.py:164-170 then 199-206), one pass: the
 // (T x 64) tile is normalised in registers exactly as gn_relu_fwd_kernel does, left in LDS (row T stays zero: the halo row the
 // gather's i0 + 1 may touch), and the output rows r < nrows[b] are (1 - lam) * tile[i0] + lam * tile[i0 + 1] with the gather's three
@@ -789,11 +909,28 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 }  // namespace
 
 hipError_t gn_relu_fwd(const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, const float* gamma,
-                       const float* beta, float* stats, int B, int T, int C, hipStream_t s) {
-    if (C % 64 != 0 || T > 16 * GN_MAXIT) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gn_relu_fwd_kernel, dim3(C / 64, B), dim3(256), 0, s, x, x_ld, x_bs, y, y_ld, y_bs, gamma, beta, stats,
-                       T, C);
+                       const float* beta, float* stats, int B, int T, int C, hipStream_t s, double* scratch) {
+    if (C % 64 != 0 || T < 1) return hipErrorInvalidValue;
+    if (T <= 16 * GN_MAXIT) {
+        hipLaunchKernelGGL(gn_relu_fwd_kernel, dim3(C / 64, B), dim3(256), 0, s, x, x_ld, x_bs, y, y_ld, y_bs, gamma, beta, stats,
+                           T, C);
+        return hipGetLastError();
+    }
+    // long sequence: chunk partials in scratch (gn_relu_fwd_scratch_bytes), three launches
+    const int nch = (T + GN_CHUNK - 1) / GN_CHUNK;
+    if (!scratch || nch > GN_MAXCH || x_ld % 4 || x_bs % 4 || y_ld % 4 || y_bs % 4) return hipErrorInvalidValue;
+    double* part0 = scratch;
+    double* part1 = scratch + (long)B * (C / 16) * nch;
+    const dim3 grid(nch, C / 64, B);
+    hipLaunchKernelGGL(gn_long_stats_kernel<0>, grid, dim3(256), 0, s, x, x_ld, x_bs, nullptr, part0, T, C);
+    hipLaunchKernelGGL(gn_long_stats_kernel<1>, grid, dim3(256), 0, s, x, x_ld, x_bs, part0, part1, T, C);
+    hipLaunchKernelGGL(gn_long_out_kernel, grid, dim3(256), 0, s, x, x_ld, x_bs, y, y_ld, y_bs, gamma, beta, stats, part0, part1, T, C);
     return hipGetLastError();
+}
+
+long gn_relu_fwd_scratch_bytes(int B, int T, int C) {
+    if (T <= 16 * GN_MAXIT) return 0;
+    return 2L * B * (C / 16) * ((T + GN_CHUNK - 1) / GN_CHUNK) * (long)sizeof(double);
 }
 
 hipError_t gn_relu_gather(const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, float* y_img, const float* img_scale,

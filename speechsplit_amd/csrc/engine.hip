@@ -633,9 +633,16 @@ namespace {
 hipStream_t S(void* s) { return (hipStream_t)s; }
 
 
-int geometry(ss_engine* e, int B, int T, hipStream_t s) {
+// eval: the call is an eval-mode forward (ss_g3_forward / ss_g6_forward with training == 0, ss_g3_rhythm).  Those may run T beyond
+// max_frames, up to SS_MAX_EVAL_FRAMES, whenever the plan for (B, T) fits the bound workspace; everything that trains or differentiates
+// keeps T <= max_frames (<= 256: the register-resident GroupNorm backward and the fused gathers).
+int geometry(ss_engine* e, int B, int T, hipStream_t s, bool eval = false) {
     if (!e->ws) return fail("engine is not bound (call ss_bind first)");
-    if (B < 1 || B > e->maxB || T < 1 || T > e->maxT) return fail("batch / frames outside the limits given to ss_create");
+    if (B < 1 || B > e->maxB || T < 1) return fail("batch / frames outside the limits given to ss_create");
+    if (T > e->maxT && (!eval || e->kind == SS_INTERP_ONLY))
+        return fail("batch / frames outside the limits given to ss_create: frames above max_frames run in eval-mode forwards only "
+                    "(training, backward and InterpLnr keep T <= max_frames <= 256)");
+    if (T > SS_MAX_EVAL_FRAMES) return fail("eval-mode forward: T above SS_MAX_EVAL_FRAMES (8192)");
     if (e->kind != SS_INTERP_ONLY && (T % e->hp.freq || T % e->hp.freq_2 || T % e->hp.freq_3))
         return fail("T must be a multiple of the code down-sampling factors (model.py:87,223-227)");
     if (B == e->curB && T == e->curT) return 0;
@@ -644,7 +651,7 @@ int geometry(ss_engine* e, int B, int T, hipStream_t s) {
         ss_engine tmp = *e;
         need = tmp.carve(B, T, false);
     }
-    if (need > e->ws_bytes) return fail("workspace too small");
+    if (need > e->ws_bytes) return fail("workspace too small for this batch / frames: grow it to ss_plan_bytes(B, T) with ss_set_workspace");
     // new geometry: halo rows move, so everything the new plan uses, except the Adam state (first 256 bytes), is re-zeroed
     // (0.1 - 0.2 ms per switch at batch 64: the price of a length-bucket change, SS_STEP_BUCKET)
     HIPCHK(hipMemsetAsync(e->ws + 256, 0, need - 256, s));
@@ -1124,8 +1131,17 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
         prof_end(e, pa_, s); }
         return 0;
     }
+    // T > 256 (eval only): the chunked GroupNorm takes its float64 partials from the step's scratch (one region per block: blocks run
+    // side by side on different streams)
+    double* gn_scratch = nullptr;
+    if (const long gb = gn_relu_fwd_scratch_bytes(B, T, cb.Co)) {
+        const long need = (gb / 4 + 63) & ~63L;
+        if (!e->part || e->part_off + need > e->part_cap) return fail("conv_block_fwd: no scratch left for the long-sequence GroupNorm");
+        gn_scratch = (double*)(e->part + e->part_off);          // part_off is kept at multiples of 64 floats
+        e->part_off += need;
+    }
     { const int pa_ = prof_begin(e, SS_PROF_GN, s, 0.0);
-    HIPCHK(gn_relu_fwd(cb.cout, cb.Co, TP * cb.Co, y.p, y.ld, TP * y.ld, e->P + cb.ga, e->P + cb.be, cb.stats, B, T, cb.Co, s));
+    HIPCHK(gn_relu_fwd(cb.cout, cb.Co, TP * cb.Co, y.p, y.ld, TP * y.ld, e->P + cb.ga, e->P + cb.be, cb.stats, B, T, cb.Co, s, gn_scratch));
     prof_end(e, pa_, s); }
     return 0;
 }
@@ -2585,6 +2601,41 @@ static long plan_bytes(const ss_engine* e) {
 }
 long ss_workspace_bytes(const ss_engine* e) { return plan_bytes(e) + part_floats(e) * 4; }
 
+long ss_plan_bytes(const ss_engine* e, int B, int T) {
+    if (!e) return fail("ss_plan_bytes: null engine");
+    if (B < 1 || B > e->maxB) return fail("ss_plan_bytes: batch outside 1 .. max_batch");
+    if (T < 8 || T > SS_MAX_EVAL_FRAMES) return fail("ss_plan_bytes: frames outside 8 .. SS_MAX_EVAL_FRAMES");
+    if (e->kind != SS_INTERP_ONLY && (T % e->hp.freq || T % e->hp.freq_2 || T % e->hp.freq_3))
+        return fail("ss_plan_bytes: T must be a multiple of the code down-sampling factors (model.py:87,223-227)");
+    ss_engine tmp = *e;             // dry run on a copy, as plan_bytes
+    return ((tmp.carve(B, T, false) + 255) & ~255L) + part_floats(e) * 4;
+}
+
+static_assert(sizeof(AdamState) <= 256, "the Adam state is the workspace's first 256 bytes");
+int ss_set_workspace(ss_engine* e, void* ws_dev, long bytes, void* stream) {
+    if (!e || !e->ws) return fail("ss_set_workspace: engine is not bound (call ss_bind first)");
+    if (!ws_dev || ((uintptr_t)ws_dev & 255)) return fail("ss_set_workspace: the workspace must be 256-byte aligned");
+    if (bytes < ss_workspace_bytes(e)) return fail("ss_set_workspace: workspace smaller than ss_workspace_bytes()");
+    // nothing may still run on the old workspace once the caller frees it: every stream the engine enqueues on drains first
+    HIPCHK(hipStreamSynchronize(S(stream)));
+    for (hipStream_t st : {e->main_s, e->side, e->side2, e->side3, e->comm_s})
+        if (st) HIPCHK(hipStreamSynchronize(st));
+    char* old = e->ws;
+    e->ws = (char*)ws_dev;
+    e->ws_bytes = ((bytes - part_floats(e) * 4) & ~255L);
+    e->part = (float*)(e->ws + e->ws_bytes);
+    e->part_cap = part_floats(e);
+    e->part_off = 0;
+    e->curB = e->curT = 0;          // the next call plans (and zeroes) its geometry in the new workspace
+    e->have_fwd = false;
+    // the head of the workspace (the Adam state at offset 0, 256 bytes) survives, as across geometry changes; the rest starts zero
+    HIPCHK(hipMemcpyAsync(e->ws, old, 256, hipMemcpyDeviceToDevice, S(stream)));
+    HIPCHK(hipMemsetAsync(e->ws + 256, 0, e->ws_bytes - 256, S(stream)));
+    e->carve(e->maxB, e->maxT, true);
+    HIPCHK(hipStreamSynchronize(S(stream)));
+    return 0;
+}
+
 int ss_bind(ss_engine* e, float* params, float* grads, float* m, float* v, void* workspace, long ws_bytes, void* stream) {
     if (!workspace || (e->kind != SS_INTERP_ONLY && (!params || !grads))) return fail("ss_bind: null arena");
     if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)m | (uintptr_t)v | (uintptr_t)workspace) & 255)
@@ -2702,16 +2753,26 @@ int ss_zero_grads(ss_engine* e, void* stream) {
     return 0;
 }
 
+// every backward: a forward to differentiate, and one that ran within max_frames (nothing is enqueued otherwise)
+static int backward_check(const ss_engine* e) {
+    if (!e->have_fwd) return fail("backward without a preceding forward");
+    if (e->curT > e->maxT)
+        return fail("backward: the last forward ran T above max_frames, which is eval-only (GroupNorm backward, training and input "
+                    "gradients keep T <= max_frames <= 256)");
+    return 0;
+}
+
 int ss_g3_forward(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, const float* scales,
                   const int* len_seg, int B, int T, int training, float* out, void* stream) {
     if (e->kind != SS_GENERATOR_3) return fail("ss_g3_forward on a Generator_6 engine");
     CHK(entry_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;
+    if (training && T > e->maxT) return fail("train-mode forward: T above max_frames; longer sequences run in eval mode only");
     if (training && T != e->hp.max_len_pad)
         return fail("train-mode forward needs T == max_len_pad (InterpLnr pads to max_len_pad, model.py:370)");
     if (training && (!scales || !len_seg)) return fail("train-mode forward needs the InterpLnr draws");
-    CHK(geometry(e, B, T, s));
+    CHK(geometry(e, B, T, s, !training));
     CHK(stage_g3_inputs(e, x_f0, x_org, c_trg, B, T, s));
     CHK(forward_core(e, training != 0, scales, len_seg, 0, s));
     if (out) CHK(export_out(e, out, B, T, s));
@@ -2720,16 +2781,16 @@ int ss_g3_forward(ss_engine* e, const float* x_f0, const float* x_org, const flo
 
 int ss_g3_backward(ss_engine* e, const float* d_out, void* stream) {
     if (e->kind != SS_GENERATOR_3) return fail("ss_g3_backward on a Generator_6 engine");
+    CHK(backward_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;
-    if (!e->have_fwd) return fail("backward without a preceding forward");
     CHK(import_dout(e, d_out, e->curB, e->curT, s));
     return backward_core(e, s);
 }
 
 int ss_g3_backward_inputs(ss_engine* e, const float* d_out, float* dx_f0, float* dx_org, float* dc_trg, void* stream) {
     if (e->kind != SS_GENERATOR_3) return fail("ss_g3_backward_inputs on a Generator_6 engine");
-    if (!e->have_fwd) return fail("backward without a preceding forward");
+    CHK(backward_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;
     const ss_hparams& h = e->hp;
@@ -2751,7 +2812,8 @@ int ss_g3_rhythm(ss_engine* e, const float* x_org, int B, int T, float* codes, v
     if (e->kind != SS_GENERATOR_3) return fail("ss_g3_rhythm on a Generator_6 engine");
     Own own(e, stream);
     hipStream_t s = own.s;
-    CHK(geometry(e, B, T, s));
+    CHK(geometry(e, B, T, s, true));
+    e->part_off = 0;           // step scratch (long-sequence GroupNorm): as at the start of forward_core
     const ss_hparams& h = e->hp;
     const long TP = T + 2 * HALO;
     HIPCHK(copy_rows(x_org, h.dim_freq, (long)T * h.dim_freq, e->org + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq, B, T,
@@ -2780,9 +2842,10 @@ int ss_g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, const f
     CHK(entry_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;
+    if (training && T > e->maxT) return fail("train-mode forward: T above max_frames; longer sequences run in eval mode only");
     if (training && T != e->hp.max_len_pad) return fail("train-mode forward needs T == max_len_pad (model.py:370)");
     if (training && (!scales || !len_seg)) return fail("train-mode forward needs the InterpLnr draws");
-    CHK(geometry(e, B, T, s));
+    CHK(geometry(e, B, T, s, !training));
     const ss_hparams& h = e->hp;
     const long TP = T + 2 * HALO;
     HIPCHK(copy_rows(x_org, h.dim_freq, (long)T * h.dim_freq, e->org + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq, B, T,
@@ -2795,16 +2858,16 @@ int ss_g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, const f
 
 int ss_g6_backward(ss_engine* e, const float* d_out, void* stream) {
     if (e->kind != SS_GENERATOR_6) return fail("ss_g6_backward on a Generator_3 engine");
+    CHK(backward_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;
-    if (!e->have_fwd) return fail("backward without a preceding forward");
     CHK(import_dout(e, d_out, e->curB, e->curT, s));
     return backward_core(e, s);
 }
 
 int ss_g6_backward_inputs(ss_engine* e, const float* d_out, float* dx_org, float* df0_trg, void* stream) {
     if (e->kind != SS_GENERATOR_6) return fail("ss_g6_backward_inputs on a Generator_3 engine");
-    if (!e->have_fwd) return fail("backward without a preceding forward");
+    CHK(backward_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;
     InputGradTargets tg{e};
@@ -2862,6 +2925,7 @@ static int g3_step_body(ss_engine* e, const float* mel, const float* f0, const f
 // engine was created with again, whatever bucket came before (a loader that mixes buckets with full-length batches sends the
 // latter without the flag: speechsplit_amd/solver.py).
 static int apply_bucket(ss_engine* e, int T, int flags) {
+    if (T > e->maxT) return fail("training: T above max_frames; frames above max_frames (<= 256) run in eval-mode forwards only");
     int want = e->bound_max_len_pad;
     if (flags & SS_STEP_BUCKET) {      // this batch's length bucket: the step runs with max_len_pad = T
         if (T < 8 || T > e->maxT || T % 8) return fail("SS_STEP_BUCKET: T must be a multiple of 8 within the engine's max_frames");
@@ -2893,6 +2957,7 @@ int ss_train_finish(ss_engine* e, float grad_scale, int flags, void* stream) {
     Own own(e, stream);
     hipStream_t s = own.s;
     if (!e->have_fwd) return fail("ss_train_finish without a preceding ss_*_train_step(SS_STEP_SPLIT_BACKWARD)");
+    CHK(backward_check(e));
     CHK(backward_encoder(e, s));
     if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_enqueue(e, grad_scale, s));
     return 0;
@@ -2963,7 +3028,7 @@ int ss_interp_forward(ss_engine* e, const float* x, const int* len_seq, const fl
     Own own(e, stream);
     hipStream_t s = own.s;
     if (!e->ws) return fail("engine is not bound");
-    if (B > e->maxB || T > e->maxT) return fail("ss_interp_forward: batch / frames exceed the engine limits");
+    if (B > e->maxB || T > e->maxT) return fail("ss_interp_forward: batch / frames exceed the engine limits (InterpLnr keeps T <= max_frames)");
     if (!e->curB) CHK(geometry(e, e->maxB, e->maxT, s));
     InterpPlan pl = e->plan[3];     // standalone calls use the last plan slot with their own T
     pl.T = T;
@@ -2981,6 +3046,7 @@ int ss_interp_backward(ss_engine* e, const float* dy, int B, int T, int C, float
     Own own(e, stream);
     hipStream_t s = own.s;
     if (!e->ws || !e->curB) return fail("ss_interp_backward without ss_interp_forward");
+    if (B > e->maxB || T > e->maxT) return fail("ss_interp_backward: batch / frames exceed the engine limits (InterpLnr keeps T <= max_frames)");
     InterpPlan pl = e->plan[3];
     pl.T = T;
     const int P = pl.P;
@@ -3347,7 +3413,8 @@ int ss_debug_relu_mask(ss_engine* e, const char* block, float* mask, void* strea
 long ss_op_conv_block_scratch(int B, int T, int Ci, int Co) {
     const long Cp = align4(Ci), R = (long)B * (T + 2 * HALO);
     const long np = align4((long)Co * Ci * 5) + 3L * Co;
-    return 2 * np + 2L * Co * 5 * Cp + (long)Ci * 5 * Co + R * (2 * Cp + 3L * Co) + 2L * B * (Co / 16) + 64;
+    const long gn = T > 256 ? ((gn_relu_fwd_scratch_bytes(B, T, Co) / 4 + 63) & ~63L) + 4 : 0;       // long-sequence GroupNorm partials (forward only)
+    return 2 * np + 2L * Co * 5 * Cp + (long)Ci * 5 * Co + R * (2 * Cp + 3L * Co) + 2L * B * (Co / 16) + 64 + gn;
 }
 
 int ss_op_conv_block(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, const float* dy,
@@ -3355,7 +3422,9 @@ int ss_op_conv_block(const float* x, const float* w, const float* bias, const fl
                      int B, int T, int Ci, int Co, void* stream) {
     hipStream_t s = S(stream);
     if (!x || !w || !bias || !gamma || !beta || !y || !scratch) return fail("ss_op_conv_block: null pointer");
-    if (Co % 64 || T < 1 || T > 256 || B < 1) return fail("ss_op_conv_block: needs Co % 64 == 0 and 1 <= T <= 256");
+    if (Co % 64 || T < 1 || B < 1) return fail("ss_op_conv_block: needs Co % 64 == 0, B >= 1 and T >= 1");
+    if (T > 256 && (dy || T > SS_MAX_EVAL_FRAMES))
+        return fail("ss_op_conv_block: T > 256 runs the forward only (dy == nullptr), up to SS_MAX_EVAL_FRAMES");
     if (scratch_floats < ss_op_conv_block_scratch(B, T, Ci, Co)) return fail("ss_op_conv_block: scratch too small");
     // a stack engine that holds nothing but this block: the product's own conv_block_fwd / conv_block_bwd do the work
     ss_engine e{};
@@ -3392,6 +3461,10 @@ int ss_op_conv_block(const float* x, const float* w, const float* bias, const fl
     float* dys = take(R * Co);
     cb.stats = take(2L * B * (Co / 16));
     e.amax = take(16);
+    if (const long gn = (gn_relu_fwd_scratch_bytes(B, T, Co) / 4 + 63) & ~63L) {     // conv_block_fwd takes the GroupNorm's partials from the step scratch
+        e.part = take(gn);
+        e.part_cap = gn;
+    }
     cb.amax_i = 0;
     HIPCHK(hipMemcpyAsync(e.P + cb.w, w, (long)Co * Ci * 5 * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(e.P + cb.b, bias, Co * 4L, hipMemcpyDeviceToDevice, s));
@@ -3738,6 +3811,7 @@ int ss_g6_dp_train_step(ss_engine* e, const float* mel, const float* f0_onehot, 
                         int B, int T, int flags, float* loss, void* stream) {
     if (e->kind != SS_GENERATOR_6) return fail("ss_g6_dp_train_step on a Generator_3 engine");
     if (!e->comm && g_dp_model < 2) return fail("ss_g6_dp_train_step: call ss_comm_init first");
+    if (T > e->maxT) return fail("training: T above max_frames; frames above max_frames (<= 256) run in eval-mode forwards only");
     CHK(entry_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;

@@ -37,7 +37,11 @@ hipError_t interp_scatter(const InterpPlan& p, const float* dy, long dy_ld, long
 // ---------------------------------------------------------------- elementwise.hip
 // GroupNorm(16 channels per group, eps 1e-5, biased variance over 16 x T) + ReLU on rows [HALO, HALO+T) of haloed slabs.
 hipError_t gn_relu_fwd(const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, const float* gamma,
-                       const float* beta, float* stats /*[B, C/16, 2] mean, rstd*/, int B, int T, int C, hipStream_t s);
+                       const float* beta, float* stats /*[B, C/16, 2] mean, rstd*/, int B, int T, int C, hipStream_t s,
+                       double* scratch = nullptr);
+// T <= 256: one register-resident kernel, scratch unused.  T > 256 (eval-mode inference only; no backward exists for it): three
+// chunked launches that need gn_relu_fwd_scratch_bytes(B, T, C) bytes of scratch (8-byte aligned) for their float64 chunk partials.
+long gn_relu_fwd_scratch_bytes(int B, int T, int C);
 // the same followed by the training forward's random resampling of the block output (interp_gather), in one pass: y / y_img are the
 // resampled slab and its image AT the first real row and the block's first column (p.P output rows); bit-identical to the two kernels
 // img_bf16: y_img is the plain bf16 tensor (element offsets, 2 bytes each) instead of a format-v2 image (common.h ss_store_img4)

@@ -93,6 +93,30 @@ class Engine:
     def set_adam(self, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, step=0):
         _capi.check(self.lib.ss_set_adam(self.h, lr, beta1, beta2, eps, int(step), _stream()))
 
+    # ------------------------------------------------------------------ workspace
+    def plan_bytes(self, B, T):
+        """Workspace bytes an eval-mode forward of shape (B, T) needs (ss_plan_bytes); raises for a shape the engine cannot run."""
+        n = self.lib.ss_plan_bytes(self.h, int(B), int(T))
+        if n < 0:
+            raise RuntimeError('speechsplit_amd: ' + self.lib.ss_last_error().decode())
+        return int(n)
+
+    def reserve(self, B, T):
+        """Make the workspace hold an eval-mode forward of (B, T): grow it through ss_set_workspace when the plan does not fit (the
+        engine, its parameter arenas and the Adam state stay as they are), never shrink it.  Returns True when it grew."""
+        need = self.plan_bytes(B, T)
+        if need <= self.ws.numel():
+            return False
+        with torch.cuda.device(self.device):
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _capi.check(self.lib.ss_set_workspace(self.h, _ptr(ws), ws.numel(), _stream()))
+        self.ws = ws                                   # the call synchronised: nothing runs on the old workspace any more
+        return True
+
+    def _reserve_eval(self, B, T, training):
+        if not training and T > self.max_frames:       # frames beyond max_frames: eval-mode forwards only (ss_plan_bytes)
+            self.reserve(B, T)
+
     # ------------------------------------------------------------------ helpers
     def _f(self, t):
         return t.to(device=self.device, dtype=torch.float32).contiguous()
@@ -126,6 +150,7 @@ class Engine:
         sc, ls = self._draws(draws)
         out = torch.empty(B, T, self.hp.dim_freq, device=self.device)
         self._fwd_bt = None
+        self._reserve_eval(B, T, training)
         _capi.check(self.lib.ss_g3_forward(self.h, _ptr(x_f0), _ptr(x_org), _ptr(c_trg), _ptr(sc), _ptr(ls), B, T,
                                            int(training), _ptr(out), _stream()))
         self._fwd_bt = (B, T)
@@ -162,6 +187,7 @@ class Engine:
     def g3_rhythm(self, x_org):
         self._fwd_bt = None
         B, T, _ = x_org.shape
+        self._reserve_eval(B, T, False)
         x_org = self._f(x_org)
         codes = torch.empty(B, T // self.hp.freq_2, 2 * self.hp.dim_neck_2, device=self.device)
         _capi.check(self.lib.ss_g3_rhythm(self.h, _ptr(x_org), B, T, _ptr(codes), _stream()))
@@ -308,6 +334,7 @@ class Engine:
         sc, ls = self._draws(draws)
         out = torch.empty(B, T, self.hp.dim_f0, device=self.device)
         self._fwd_bt = None
+        self._reserve_eval(B, T, training)
         _capi.check(self.lib.ss_g6_forward(self.h, _ptr(x_org), _ptr(f0_trg), _ptr(sc), _ptr(ls), B, T, int(training),
                                            _ptr(out), _stream()))
         self._fwd_bt = (B, T)
