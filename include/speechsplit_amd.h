@@ -57,7 +57,9 @@ typedef struct ss_hparams {
 const char* ss_last_error(void);
 int ss_abi_version(void);
 
-/* model.py:285-295 / 327-334 (constructor).  No device memory is touched until ss_bind. */
+/* model.py:285-295 / 327-334 (constructor).  No device memory is touched until ss_bind.
+ * The bottleneck widths hp->dim_neck, dim_neck_2 and dim_neck_3 may each be any of 1..32 (the reference takes any positive value; wider
+ * bottlenecks are refused).  The down-sampling factors freq, freq_2 and freq_3 may differ; every T must be a multiple of all three. */
 ss_engine* ss_create(int kind, const ss_hparams* hp, int max_batch, int max_frames);
 void ss_destroy(ss_engine* e);
 
@@ -239,7 +241,8 @@ int ss_set_lockstep(ss_engine* e, int on);
 int ss_op_gemm(const float* a_dev, long lda, const float* b_dev, long ldb, float* c_dev, long ldc, const float* bias_dev,
                int M, int N, int K, int flags, int ksplit, void* stream);
 /* One bidirectional LSTM recurrence on haloed slabs (speechsplit_amd/csrc/kernels.h): gates [B,T+4,8H] holds
- * x.W_ih^T + b on entry and the activated gates on exit; out / csave [B,T+4,2H]; whh_* [4H,H].  H <= 32 runs the
+ * x.W_ih^T + b on entry and the activated gates on exit; out / csave [B,T+4,2H]; whh_* [4H,H].  For H <= 32 not a power of
+ * two the rows of out / csave / d_out are 2H rounded up to a multiple of 4 floats apart (columns past 2H untouched).  H <= 32 runs the
  * single-launch kernel, H in {64,128,256,512} one launch per time step and needs scratch of at least
  * 8*H*H + 4*ceil16(B)*H floats (forward) / 8*H*H + 16*ceil16(B)*H + 2*B*H floats (backward).  H in {256,512} with
  * 2*ceil(B/16)*(H/16) <= 256 runs as ONE persistent launch (the engine's schedule) when, for the backward, scratch also
@@ -252,7 +255,7 @@ int ss_op_lstm_bwd(float* gates_dev, const float* whh_f_dev, const float* whh_b_
 /* Test hook for the fused weight / bias gradient kernel of the encoder BLSTMs (csrc/lstm_wgrad.hip; hidden size <= 32): from the pre-activation
  * gradients dg [R][8H], the layer input x [R][In] (row stride x_ld) and the layer output hout [R][2H] (haloed slabs flattened to R rows, halo
  * rows zero) ACCUMULATE dW_ih [2][4H][In], dW_hh [2][4H][H] and the bias gradients gb [2][2][4H] (b_ih, b_hh per direction).  scratch:
- * >= 16 * 4096 * tiles + 64 floats with tiles = ceil(8H / 64) * (ceil(In / 64) + (H >= 16 ? 1 : 2)). */
+ * >= 16 * 4096 * tiles + 64 floats with tiles = ceil(8H / 64) * (ceil(In / 64) + (4H % 64 == 0 ? 1 : 2)); H in 1..32, hout rows 2H apart. */
 int ss_op_lstm_wgrad(const float* dg_dev, const float* x_dev, long x_ld, const float* hout_dev, float* gwih_dev, float* gwhh_dev, float* gb_dev,
                      float* scratch_dev, long scratch_floats, long R, int H, int In, void* stream);
 /* The GEMM over operand images (speechsplit_amd/csrc/gemm_img.hip), the engine's default for every large contraction: an IMAGE has the

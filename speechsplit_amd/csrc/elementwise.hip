@@ -732,7 +732,7 @@ __global__ __launch_bounds__(256) void build_dec_in_kernel(CodeSrcPack p, const 
                     const int blk = t / f;
                     // forward half sampled at the END of each block, backward half at its START (model.py:223-227)
                     const int ts = cc < H ? blk * f + f - 1 : blk * f;
-                    v = p.s[i].o[((long)b * TP + ts + HALO) * (2 * H) + cc];
+                    v = p.s[i].o[((long)b * TP + ts + HALO) * p.s[i].ld + cc];
                 }
             }
         }
@@ -757,7 +757,7 @@ __global__ __launch_bounds__(256) void build_dec_in_compact_kernel(CodeSrcPack p
                 if (c >= col && c < col + 2 * H) {
                     const int cc = c - col;
                     const int ts = cc < H ? blk * f + f - 1 : blk * f;      // as build_dec_in_kernel
-                    v = p.s[i].o[((long)b * TP + ts + HALO) * (2 * H) + cc];
+                    v = p.s[i].o[((long)b * TP + ts + HALO) * p.s[i].ld + cc];
                 }
             }
         }
@@ -771,7 +771,7 @@ __global__ __launch_bounds__(128) void dec_in_grad_compact_kernel(CodeSrcPack p,
     const int TP = T + 2 * HALO;
     for (int i = 0; i < p.n; ++i) {
         const int H = p.s[i].H, col = p.s[i].col;
-        float* drow = p.s[i].d_o + ((long)b * TP + t + HALO) * (2 * H);
+        float* drow = p.s[i].d_o + ((long)b * TP + t + HALO) * p.s[i].ld;
         for (int cc = threadIdx.x; cc < 2 * H; cc += 128) {
             const bool sampled = cc < H ? (t % f == f - 1) : (t % f == 0);
             drow[cc] = sampled ? d_xc[((long)b * (T / f) + t / f) * ld + col + cc] : 0.f;
@@ -785,7 +785,7 @@ __global__ __launch_bounds__(128) void dec_in_grad_kernel(CodeSrcPack p, const f
     const int TP = T + 2 * HALO;
     for (int i = 0; i < p.n; ++i) {
         const int H = p.s[i].H, f = p.s[i].freq, col = p.s[i].col;
-        float* drow = p.s[i].d_o + ((long)b * TP + t + HALO) * (2 * H);
+        float* drow = p.s[i].d_o + ((long)b * TP + t + HALO) * p.s[i].ld;
         for (int cc = threadIdx.x; cc < 2 * H; cc += 128) {
             const bool sampled = cc < H ? (t % f == f - 1) : (t % f == 0);
             float v = 0.f;

@@ -207,6 +207,8 @@ struct LstmBlk {
     // image of the stacked W_ih of layer l (written by lstm_prep when its rows are whole image groups)
     const float* wimg(int l) const { return (!wcat_img.empty() && wcat_img[l] && in_of(l) % 8 == 0) ? wcat_img[l] : nullptr; }
     int in_of(int l) const { return l == 0 ? In : 2 * H; }
+    // row stride of the out / csave / dmid slabs and of the block's output-gradient slab: 2H, padded for odd hidden sizes (kernels.h)
+    long ow() const { return lstm_small_ld(H); }
 };
 
 struct Slab {   // view of a haloed slab: p points at slab row 0, first channel of interest
@@ -491,8 +493,8 @@ long ss_engine::carve(int B, int T, bool assign) {
         lb.csave.assign(lb.L, nullptr);
         for (int l = 0; l < lb.L; ++l) {
             lb.gates[l] = slab((name + ".gates" + std::to_string(l)).c_str(), 8L * lb.H);
-            lb.out[l] = slab((name + ".out" + std::to_string(l)).c_str(), 2L * lb.H);
-            lb.csave[l] = slab((name + ".c" + std::to_string(l)).c_str(), 2L * lb.H);
+            lb.out[l] = slab((name + ".out" + std::to_string(l)).c_str(), lb.ow());
+            lb.csave[l] = slab((name + ".c" + std::to_string(l)).c_str(), lb.ow());
         }
         lb.out_img.assign(lb.L, nullptr);
         if (lb.big())
@@ -521,8 +523,8 @@ long ss_engine::carve(int B, int T, bool assign) {
             lb.zb = (char*)take(lb.zb_bytes);
         }
         if (lb.L > 1) {
-            lb.dmid[0] = slab((name + ".dmid0").c_str(), 2L * lb.H);
-            lb.dmid[1] = slab((name + ".dmid1").c_str(), 2L * lb.H);
+            lb.dmid[0] = slab((name + ".dmid0").c_str(), lb.ow());
+            lb.dmid[1] = slab((name + ".dmid1").c_str(), lb.ow());
         }
     };
     adam = (AdamState*)take(sizeof(AdamState));        // first: survives geometry changes (offset 0)
@@ -586,9 +588,9 @@ long ss_engine::carve(int B, int T, bool assign) {
     lstm_ws(lt, "enc2.lstm");
     lstm_ws(ld, "dec.lstm");
     for (int l = 0; l < ld.L && l < 3; ++l) dg_img[l] = ld.big() ? slab(nullptr, 8L * ld.H) : nullptr;
-    if (l1.L) d_o1 = slab("enc1.d_o1", 2L * l1.H);
-    d_o2 = slab("enc.d_o2", 2L * l2.H);
-    d_ot = slab("enc2.d_ot", 2L * lt.H);
+    if (l1.L) d_o1 = slab("enc1.d_o1", l1.ow());
+    d_o2 = slab("enc.d_o2", l2.ow());
+    d_ot = slab("enc2.d_ot", lt.ow());
     dec_in = slab("dec.in", dec_in_dim);
     d_dec_in = slab("dec.d_in", dec_in_dim);
     {
@@ -1389,7 +1391,7 @@ int lstm_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
     const long TP = T + 2 * HALO;
     for (int l = 0; l < lb.L; ++l) {
         const int In = lb.in_of(l);
-        Slab xi = l == 0 ? x : Slab{lb.out[l - 1], 2L * H};
+        Slab xi = l == 0 ? x : Slab{lb.out[l - 1], lb.ow()};      // layer 1: K = 2H real columns of the (possibly padded) rows
         {   // both directions in one GEMM (stacked W_ih and summed biases from lstm_prep)
             GemmDesc d{};
             d.A = {xi.p + HALO * xi.ld, xi.ld, TP * xi.ld, 0, 0};
@@ -1482,7 +1484,7 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
         // encoder BLSTMs: one fused fp32 kernel for the weight and bias gradients of every layer (lstm_wgrad.hip)
         WgradTask& t = e->wg.t[e->wg.n];
         t = WgradTask{dG, xi.p, xi.ld, lb.out[l], e->G + p0.wih, e->G + p1.wih, e->G + p0.whh, e->G + p1.whh, e->G + p0.bih, e->G + p0.bhh, e->G + p1.bih,
-                      e->G + p1.bhh, H, In, R, e->wg.tiles_total};
+                      e->G + p1.bhh, H, In, R, e->wg.tiles_total, (int)lb.ow()};
         e->wg.tiles_total += lstm_small_wgrad_tiles(H, In);
         ++e->wg.n;
         if (!e->wg_defer) CHK(wgrad_flush(e, ws));
@@ -1532,7 +1534,7 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
         if (!compact && part != 2) PGEMM_ON(lb.big() ? SS_PROF_DEC_DW : SS_PROF_ENC_LSTM, a, ws);
         GemmDesc h{};
         h.A = {dG + 8L * H, 8L * H, 4L * H - 8L * H, 0, 0};                    // forward: rows 1 .., reverse: rows 0 .. of its own columns
-        h.B = {lb.out[l], 2L * H, 2L * H + H, 0, 0};                           // forward: rows 0 .. of h_f, reverse: rows 1 .. of h_b
+        h.B = {lb.out[l], lb.ow(), lb.ow() + H, 0, 0};                         // forward: rows 0 .. of h_f, reverse: rows 1 .. of h_b
         if (dimg) {
             h.a_pre = e->ioff(dimg, 8L * H);
             h.a_pre_scale = dsc;
@@ -1610,7 +1612,7 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
             h.a_pre = e->ioff(dimg, h.A.p - dG);
             h.a_pre_scale = dsc;
         }
-        h.B = {dir == 0 ? lb.out[l] : lb.out[l] + 2L * H + H, 2L * H, 0, 0, 0};
+        h.B = {dir == 0 ? lb.out[l] : lb.out[l] + lb.ow() + H, lb.ow(), 0, 0, 0};
         if (img_ok) h.b_pre = dir == 0 ? lb.out_img[l] : e->ioff(lb.out_img[l], 2L * H + H);
         h.C = e->G + pd.whh;
         h.ldc = H;
@@ -1733,8 +1735,8 @@ int lstm_bwd(ss_engine* e, LstmBlk& lb, const float* d_top, Slab x, Slab dx, hip
                          !g_deterministic && !e->dp_on && e->wq_pool && lstm_seq_free_xcds(B, H) >= 2 && lb.out_img_valid;
     bool early_ready[4] = {false, false, false, false};
     for (int l = lb.L - 1; l >= 0; --l) {
-        Slab xi = l == 0 ? x : Slab{lb.out[l - 1], 2L * H};
-        Slab dxi = l == 0 ? dx : Slab{lb.dmid[l & 1], 2L * H};
+        Slab xi = l == 0 ? x : Slab{lb.out[l - 1], lb.ow()};
+        Slab dxi = l == 0 ? dx : Slab{lb.dmid[l & 1], lb.ow()};
         float* dG = lb.gates[l];
         hipStream_t ws = s;
         // fp16 x 2 gradient GEMMs need the slab's maximum, which only the persistent kernel measures
@@ -1860,7 +1862,7 @@ int lstm_late_weights(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t ws, int l_h
     const bool persist = lb.big() && g_persist && lstm_seq_supported(e->curB, H);
     for (int l = l_hi < 0 ? lb.L - 1 : l_hi; l >= l_lo; --l) {       // layers l_hi .. l_lo (default: all, last first)
         if (&lb == &e->ld && ((e->dec_w_done >> l) & 1)) continue;        // went out beside a recurrence (early_dw)
-        Slab xi = l == 0 ? x : Slab{lb.out[l - 1], 2L * H};
+        Slab xi = l == 0 ? x : Slab{lb.out[l - 1], lb.ow()};
         float* am = (persist && g_bwd_f16x2 && lb.amax0 >= 0) ? e->amax + lb.amax0 + l : nullptr;
         const bool bias_in_kernel = persist && !g_deterministic && lb.pd[l * 2].bhh == lb.pd[l * 2].bih + 4L * H && lb.pd[l * 2 + 1].bhh == lb.pd[l * 2 + 1].bih + 4L * H;
         e->dp_dir_buckets = false;
@@ -2080,9 +2082,9 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     int n = 0;
     const ss_hparams& h = e->hp;
     if (g3) {
-        src[n++] = {e->l1.out[1], e->d_o1, h.dim_neck, h.freq, 0};
-        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 2 * h.dim_neck};
-        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck + 2 * h.dim_neck_2};
+        src[n++] = {e->l1.out[1], e->d_o1, h.dim_neck, h.freq, 0, (int)e->l1.ow()};
+        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 2 * h.dim_neck, (int)e->lt.ow()};
+        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck + 2 * h.dim_neck_2, (int)e->l2.ow()};
         if (dec_compact(e))
             HIPCHK(build_dec_in_compact(src, n, e->emb, h.dim_spk_emb, 2 * h.dim_neck + 2 * h.dim_neck_2 + 2 * h.dim_neck_3, e->ld.xc,
                                         e->dec_in_dim, B, T, e->ld.xf, s));
@@ -2090,8 +2092,8 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
             HIPCHK(build_dec_in(src, n, e->emb, h.dim_spk_emb, 2 * h.dim_neck + 2 * h.dim_neck_2 + 2 * h.dim_neck_3, e->dec_in,
                                 e->dec_in_dim, B, T, s));
     } else {
-        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 0};
-        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck_2};
+        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 0, (int)e->lt.ow()};
+        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck_2, (int)e->l2.ow()};
         if (dec_compact(e)) HIPCHK(build_dec_in_compact(src, n, nullptr, 0, e->dec_in_dim, e->ld.xc, e->dec_in_dim, B, T, e->ld.xf, s));
         else HIPCHK(build_dec_in(src, n, nullptr, 0, e->dec_in_dim, e->dec_in, e->dec_in_dim, B, T, s));
     }
@@ -2232,12 +2234,12 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
     CodeSrc src[3];
     int n = 0;
     if (g3) {
-        src[n++] = {e->l1.out[1], e->d_o1, h.dim_neck, h.freq, 0};
-        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 2 * h.dim_neck};
-        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck + 2 * h.dim_neck_2};
+        src[n++] = {e->l1.out[1], e->d_o1, h.dim_neck, h.freq, 0, (int)e->l1.ow()};
+        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 2 * h.dim_neck, (int)e->lt.ow()};
+        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck + 2 * h.dim_neck_2, (int)e->l2.ow()};
     } else {
-        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 0};
-        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck_2};
+        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 0, (int)e->lt.ow()};
+        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck_2, (int)e->l2.ow()};
     }
     if (dec_compact(e)) HIPCHK(dec_in_grad_compact(src, n, e->ld.d_xc, e->dec_in_dim, B, T, e->ld.xf, s));
     else HIPCHK(dec_in_grad(src, n, e->d_dec_in, e->dec_in_dim, B, T, s));
@@ -2521,8 +2523,8 @@ ss_engine* ss_create(int kind, const ss_hparams* hp, int max_batch, int max_fram
         return nullptr;
     }
     for (int hdim : {hp->dim_neck, hp->dim_neck_2, hp->dim_neck_3}) {
-        if (hdim != 1 && hdim != 2 && hdim != 4 && hdim != 8 && hdim != 16 && hdim != 32) {
-            fail("ss_create: bottleneck widths must be one of 1,2,4,8,16,32");
+        if (hdim < 1 || hdim > 32) {      // the encoder BLSTMs' single-launch recurrences and fused weight gradients (H <= 32)
+            fail("ss_create: bottleneck widths (dim_neck, dim_neck_2, dim_neck_3) must be in 1..32");
             return nullptr;
         }
     }
@@ -2827,11 +2829,13 @@ int ss_g3_rhythm(ss_engine* e, const float* x_org, int B, int T, float* codes, v
     CHK(act_scales_all(e, s));
     CHK(conv_block_fwd(e, e->ct, Slab{e->org, h.dim_freq}, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, s));
     CHK(lstm_fwd(e, e->lt, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, s));
-    // codes = cat(fwd[:, 7::8], bwd[:, ::8]) (model.py:84-87): reuse the decoder-input assembler on a 2H-wide row and pick t % freq == 0
-    CodeSrc src{e->lt.out[0], nullptr, h.dim_neck_2, h.freq_2, 0};
-    HIPCHK(build_dec_in(&src, 1, nullptr, 0, 2 * h.dim_neck_2, e->d_ot, 2 * h.dim_neck_2, B, T, s));
+    // codes = cat(fwd[:, 7::8], bwd[:, ::8]) (model.py:84-87): reuse the decoder-input assembler on a 2H-wide row (in d_ot's own geometry:
+    // padding columns written zero, halo rows untouched) and pick t % freq == 0
     const int W = 2 * h.dim_neck_2;
-    HIPCHK(copy_rows(e->d_ot + HALO * W, (long)h.freq_2 * W, TP * W, codes, W, (long)(T / h.freq_2) * W, B, T / h.freq_2, W, s));
+    const long OW = e->lt.ow();
+    CodeSrc src{e->lt.out[0], nullptr, h.dim_neck_2, h.freq_2, 0, (int)OW};
+    HIPCHK(build_dec_in(&src, 1, nullptr, 0, W, e->d_ot, (int)OW, B, T, s));
+    HIPCHK(copy_rows(e->d_ot + HALO * OW, (long)h.freq_2 * OW, TP * OW, codes, W, (long)(T / h.freq_2) * W, B, T / h.freq_2, W, s));
     e->have_fwd = false;
     return 0;
 }
@@ -3357,7 +3361,7 @@ int ss_op_lstm_wgrad(const float* dg, const float* x, long x_ld, const float* ho
     w.ctr = (unsigned*)(scratch + need);
     HIPCHK(hipMemsetAsync(w.ctr, 0, ctr_floats * 4, S(stream)));
     // gwih [2][4H][In], gwhh [2][4H][H], gb [2][2][4H] (b_ih then b_hh per direction): accumulated into, as the engine's gradient arena is
-    w.t[0] = WgradTask{dg, x, x_ld, hout, gwih, gwih + 4L * H * In, gwhh, gwhh + 4L * H * H, gb, gb + 4L * H, gb + 8L * H, gb + 12L * H, H, In, R, 0};
+    w.t[0] = WgradTask{dg, x, x_ld, hout, gwih, gwih + 4L * H * In, gwhh, gwhh + 4L * H * H, gb, gb + 4L * H, gb + 8L * H, gb + 12L * H, H, In, R, 0, 2 * H};
     HIPCHK(lstm_small_wgrad(w, S(stream)));
     return 0;
 }

@@ -121,9 +121,10 @@ struct PrepTable {
 hipError_t prep_run(const PrepTable& tb, hipStream_t s);
 
 struct CodeSrc {          // one encoder BLSTM output feeding the decoder input (model.py:87, 223-227, 301-309)
-    const float* o;       // [B, TP, 2*H]
+    const float* o;       // [B, TP, ld], the 2*H real columns first
     float* d_o;           // gradient slab of the same shape (backward only)
     int H, freq, col;     // col: first column inside the decoder input
+    int ld;               // row stride of o / d_o (lstm_small_ld(H))
 };
 hipError_t build_dec_in(const CodeSrc* src, int nsrc, const float* emb, int emb_dim, int emb_col, float* dec_in, int ld,
                         int B, int T, hipStream_t s);
@@ -181,11 +182,15 @@ hipError_t melspec(const double* x, int n, const double* mel, int n_mels, float*
 hipError_t f0_normalize(const double* f0, int n, float* out, hipStream_t s);
 
 // ---------------------------------------------------------------- lstm_small.hip  (hidden <= 32: whole recurrence in one launch)
+// Row stride of a small BLSTM's output, cell-state and output-gradient slabs: 2H for H a power of two (the default widths keep their
+// layout), else 2H rounded up to a multiple of 4 floats (16-byte rows: vector loads and the GEMMs' aligned path).  The padding columns
+// are never written: zero, like the halo rows.  (Hidden sizes above 32 use 2H: the decoder's 256 / 512.)
+constexpr int lstm_small_ld(int H) { return (H > 32 || (H & (H - 1)) == 0) ? 2 * H : (2 * H + 3) & ~3; }
 // gates: [B, TP, 8H] holds x.W_ih^T + b_ih + b_hh on entry (column = dir*4H + gate*H + j, gate order i,f,g,o) and the
-// activated gates on exit.  out: [B, TP, 2H].  csave: [B, TP, 2H] cell states.  whh: [2][4H][H].
+// activated gates on exit.  out: [B, TP, lstm_small_ld(H)].  csave: the cell states, same geometry.  whh: [2][4H][H].  H in 1..32.
 hipError_t lstm_small_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, int B, int T,
                           int H, hipStream_t s);
-// d_out: [B, TP, 2H] gradient of out.  gates is replaced in place by the pre-activation gradients.
+// d_out: [B, TP, lstm_small_ld(H)] gradient of out.  gates is replaced in place by the pre-activation gradients.
 hipError_t lstm_small_bwd(float* gates, const float* whh_f, const float* whh_b, const float* d_out, const float* csave,
                           int B, int T, int H, hipStream_t s);
 
@@ -232,13 +237,14 @@ struct WgradTask {
     const float* dG;          // pre-activation gradients [R][8H] (halo rows zero)
     const float* X;           // the layer's input rows [R][In], row stride x_ld
     long x_ld;
-    const float* Hout;        // the layer's output [R][2H] (halo rows zero)
+    const float* Hout;        // the layer's output [R][2H], row stride h_ld (halo rows zero)
     float *gwih0, *gwih1;     // += dW_ih of the forward / reverse direction [4H][In]
     float *gwhh0, *gwhh1;     // += dW_hh [4H][H]
     float *gbih0, *gbhh0, *gbih1, *gbhh1;      // += bias gradients [4H] (b_ih and b_hh have the same gradient)
     int H, In;
     long R;
     int tile0;                // first blockIdx.y of this task: lstm_small_wgrad_tiles(H, In) tiles each
+    int h_ld;                 // row stride of Hout (>= 2H)
 };
 struct WgradTable {
     WgradTask t[WGRAD_MAX];

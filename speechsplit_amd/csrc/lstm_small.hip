@@ -1,5 +1,5 @@
-// Bidirectional LSTM recurrences with a tiny hidden size (the encoder bottlenecks: hidden 1, 8 and 32;
-// reference model.py:71, 119, 174, 189).  W_hh is at most 128 x 32 floats, so one workgroup per (utterance,
+// Bidirectional LSTM recurrences with a tiny hidden size (the encoder bottlenecks: hidden 1, 8 and 32 by default, any of 1..32;
+// reference model.py:71, 119, 174, 189), one instantiation per hidden size.  W_hh is at most 128 x 32 floats, so one workgroup per (utterance,
 // direction) keeps its gate row (forward) / gate column (backward) of W_hh in registers and walks all
 // T steps in a single launch: no per-step launch, no inter-workgroup traffic.  These recurrences are pure latency:
 // a step is a few hundred cycles of arithmetic, far less than one trip to memory, so the *_lds kernels first pull the
@@ -11,6 +11,9 @@
 // initial state; the reverse direction walks t = T-1..0.  The input projection x.W_ih^T + b_ih + b_hh arrives
 // precomputed in `gates` (one GEMM for all T), which this kernel overwrites with the activated gates, and the
 // backward kernel overwrites again with the pre-activation gradients (consumed by the weight-gradient GEMMs).
+#include <array>
+#include <utility>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -31,6 +34,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_kern
                                                                                    float* __restrict__ out,
                                                                                    float* __restrict__ csave, int T, int prio) {
     if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (ss_tune("small_prio"))
+    constexpr int OS = lstm_small_ld(H);           // row stride of out / csave
     __shared__ float hs[H];
     __shared__ float gs[4 * H];
     const int b = blockIdx.x, dir = blockIdx.y, n = threadIdx.x;
@@ -63,7 +67,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_kern
             c = gs[H + n] * c + gs[n] * gs[2 * H + n];
             const float h = gs[3 * H + n] * ss_tanh(c);
             hs[n] = h;
-            const long o = ((long)b * TP + tau) * (2 * H) + dir * H + n;
+            const long o = ((long)b * TP + tau) * OS + dir * H + n;
             out[o] = h;
             csave[o] = c;
         }
@@ -78,6 +82,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_bwd_kern
                                                                                    const float* __restrict__ d_out,
                                                                                    const float* __restrict__ csave, int T, int prio) {
     if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (ss_tune("small_prio"))
+    constexpr int OS = lstm_small_ld(H);           // row stride of d_out / csave
     __shared__ float dg[4 * H];
     __shared__ float part[4 * H];
     const int b = blockIdx.x, dir = blockIdx.y, n = threadIdx.x;
@@ -89,7 +94,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_bwd_kern
     for (int q = 0; q < H; ++q) wcol[q] = n < 4 * H ? whh[((n / H) * H + q) * H + n % H] : 0.f;
     const bool cell_thread = n < H;
     float* grow = gates + (long)b * TP * (8 * H) + dir * 4 * H + n;
-    const long obase = (long)b * TP * (2 * H) + dir * H + n;
+    const long obase = (long)b * TP * OS + dir * H + n;
     auto tau_of = [&](int s) { return HALO + (dir == 0 ? T - 1 - s : s); };
     float dh_rec = 0.f, dc_rec = 0.f;
     // operands of the step being processed, fetched one step ahead
@@ -97,13 +102,13 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_bwd_kern
     auto fetch = [&](int s, float c_known, bool have_c) {
         const int tau = tau_of(s);
         const int tau_prev = dir == 0 ? tau - 1 : tau + 1;       // previous step in FORWARD order (halo row = 0)
-        p_do = d_out[obase + (long)tau * (2 * H)];
+        p_do = d_out[obase + (long)tau * OS];
         p_i = grow[(long)tau * (8 * H)];
         p_f = grow[(long)tau * (8 * H) + H];
         p_g = grow[(long)tau * (8 * H) + 2 * H];
         p_o = grow[(long)tau * (8 * H) + 3 * H];
-        p_c = have_c ? c_known : csave[obase + (long)tau * (2 * H)];
-        p_cp = csave[obase + (long)tau_prev * (2 * H)];
+        p_c = have_c ? c_known : csave[obase + (long)tau * OS];
+        p_cp = csave[obase + (long)tau_prev * OS];
     };
     if (cell_thread) fetch(0, 0.f, false);
     __syncthreads();
@@ -175,6 +180,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_lds_
                                                                                        float* __restrict__ csave, int T, int prio) {
     if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (ss_tune("small_prio"))
     constexpr int NT = 4 * H > 64 ? 4 * H : 64;
+    constexpr int OS = lstm_small_ld(H);
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     float* xs = dyn;
     __shared__ float hs[H];
@@ -209,7 +215,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_lds_
             c = gs[H + n] * c + gs[n] * gs[2 * H + n];
             const float h = gs[3 * H + n] * ss_tanh(c);
             hs[n] = h;
-            const long o = ((long)b * TP + tau) * (2 * H) + dir * H + n;
+            const long o = ((long)b * TP + tau) * OS + dir * H + n;
             out[o] = h;
             csave[o] = c;
         }
@@ -227,6 +233,7 @@ __global__ __launch_bounds__(64) void lstm_small_fwd_wave_kernel(float* __restri
                                                                  float* __restrict__ csave, int T, int prio) {
     if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (ss_tune("small_prio"))
     static_assert(4 * H <= 64, "one wave");
+    constexpr int OS = lstm_small_ld(H);
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     float* xs = dyn;
     const int b = blockIdx.x, dir = blockIdx.y, n = threadIdx.x;
@@ -253,12 +260,12 @@ __global__ __launch_bounds__(64) void lstm_small_fwd_wave_kernel(float* __restri
         const float act = ss_gate(acc, (nn / H == 2) ? 2.0f : 1.0f);
         if (gate_thread) grow[(long)tau * (8 * H)] = act;
         // unit u's gates sit in lanes u, u+H, u+2H, u+3H; lanes >= H compute along (their c / h are never used)
-        const int u = n & (H - 1);
+        const int u = n % H;
         const float gi = __shfl(act, u), gf = __shfl(act, u + H), gg = __shfl(act, u + 2 * H), go = __shfl(act, u + 3 * H);
         c = gf * c + gi * gg;
         h = go * ss_tanh(c);
         if (n < H) {
-            const long o = ((long)b * TP + tau) * (2 * H) + dir * H + n;
+            const long o = ((long)b * TP + tau) * OS + dir * H + n;
             out[o] = h;
             csave[o] = c;
         }
@@ -275,6 +282,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_bwd_lds_
                                                                                        const float* __restrict__ csave, int T, int prio) {
     if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (ss_tune("small_prio"))
     constexpr int NT = 4 * H > 64 ? 4 * H : 64;
+    constexpr int OS = lstm_small_ld(H);
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     float* ga = dyn;
     float* dd = ga + (long)T * 4 * H;
@@ -289,10 +297,11 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_bwd_lds_
     for (int q = 0; q < H; ++q) wcol[q] = n < 4 * H ? whh[((n / H) * H + q) * H + n % H] : 0.f;
     const bool cell_thread = n < H;
     float* g0 = gates + (long)b * TP * (8 * H) + dir * 4 * H;
-    const long obase = (long)b * TP * (2 * H) + dir * H;
+    const long obase = (long)b * TP * OS + dir * H;
     auto tau_of = [&](int s) { return HALO + (dir == 0 ? T - 1 - s : s); };      // s == T: the halo row next to the walk's end
     stage_rows<NT, H, 16>(reinterpret_cast<const float4*>(g0), reinterpret_cast<float4*>(ga), T, n, tau_of);
     if constexpr (H % 4 == 0) {                        // rows of H floats as H/4 float4 (row stride 2H floats = H/2 float4)
+        static_assert(OS == 2 * H, "even H: unpadded rows");
         stage_rows<NT, H / 4, 8>(reinterpret_cast<const float4*>(d_out + obase), reinterpret_cast<float4*>(dd), T, n, tau_of);
         stage_rows<NT, H / 4, 8>(reinterpret_cast<const float4*>(csave + obase), reinterpret_cast<float4*>(cc), T + 1, n, tau_of);
     } else {
@@ -301,8 +310,8 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_bwd_lds_
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int i = base + u * NT;
-                if (i < (T + 1) * H) rc[u] = csave[obase + (long)tau_of(i / H) * (2 * H) + i % H];
-                if (i < T * H) rd[u] = d_out[obase + (long)tau_of(i / H) * (2 * H) + i % H];
+                if (i < (T + 1) * H) rc[u] = csave[obase + (long)tau_of(i / H) * OS + i % H];
+                if (i < T * H) rd[u] = d_out[obase + (long)tau_of(i / H) * OS + i % H];
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -396,32 +405,28 @@ hipError_t bwd_t(float* gates, const float* wf, const float* wb, const float* d_
     return hipGetLastError();
 }
 
+// one instantiation per hidden size 1..32, dispatched through a table (the six power-of-two sizes compile exactly as they did behind a switch)
+using FwdFn = hipError_t (*)(float*, const float*, const float*, float*, float*, int, int, hipStream_t);
+using BwdFn = hipError_t (*)(float*, const float*, const float*, const float*, const float*, int, int, hipStream_t);
+template <int... I>
+constexpr std::array<FwdFn, sizeof...(I)> fwd_table(std::integer_sequence<int, I...>) { return {fwd_t<I + 1>...}; }
+template <int... I>
+constexpr std::array<BwdFn, sizeof...(I)> bwd_table(std::integer_sequence<int, I...>) { return {bwd_t<I + 1>...}; }
+constexpr auto kFwd = fwd_table(std::make_integer_sequence<int, 32>{});
+constexpr auto kBwd = bwd_table(std::make_integer_sequence<int, 32>{});
+
 }  // namespace
 
 hipError_t lstm_small_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, int B, int T,
                           int H, hipStream_t s) {
-    switch (H) {
-        case 1: return fwd_t<1>(gates, whh_f, whh_b, out, csave, B, T, s);
-        case 2: return fwd_t<2>(gates, whh_f, whh_b, out, csave, B, T, s);
-        case 4: return fwd_t<4>(gates, whh_f, whh_b, out, csave, B, T, s);
-        case 8: return fwd_t<8>(gates, whh_f, whh_b, out, csave, B, T, s);
-        case 16: return fwd_t<16>(gates, whh_f, whh_b, out, csave, B, T, s);
-        case 32: return fwd_t<32>(gates, whh_f, whh_b, out, csave, B, T, s);
-        default: return hipErrorInvalidValue;
-    }
+    if (H < 1 || H > 32) return hipErrorInvalidValue;
+    return kFwd[H - 1](gates, whh_f, whh_b, out, csave, B, T, s);
 }
 
 hipError_t lstm_small_bwd(float* gates, const float* whh_f, const float* whh_b, const float* d_out, const float* csave,
                           int B, int T, int H, hipStream_t s) {
-    switch (H) {
-        case 1: return bwd_t<1>(gates, whh_f, whh_b, d_out, csave, B, T, s);
-        case 2: return bwd_t<2>(gates, whh_f, whh_b, d_out, csave, B, T, s);
-        case 4: return bwd_t<4>(gates, whh_f, whh_b, d_out, csave, B, T, s);
-        case 8: return bwd_t<8>(gates, whh_f, whh_b, d_out, csave, B, T, s);
-        case 16: return bwd_t<16>(gates, whh_f, whh_b, d_out, csave, B, T, s);
-        case 32: return bwd_t<32>(gates, whh_f, whh_b, d_out, csave, B, T, s);
-        default: return hipErrorInvalidValue;
-    }
+    if (H < 1 || H > 32) return hipErrorInvalidValue;
+    return kBwd[H - 1](gates, whh_f, whh_b, d_out, csave, B, T, s);
 }
 
 }  // namespace ss

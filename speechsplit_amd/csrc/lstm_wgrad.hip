@@ -1,9 +1,10 @@
-// Weight and bias gradients of the ENCODER BLSTMs (hidden size 1, 8, 32; model.py:71, 174-175, 116) in ONE launch for every layer of every block.
+// Weight and bias gradients of the ENCODER BLSTMs (hidden size 1, 8, 32 by default, any of 1..32; model.py:71, 174-175, 116) in ONE launch for every
+// layer of every block.
 //
 // They used to be a confetti of tiny MFMA GEMMs -- per layer dW_ih and dW_hh (both directions batched) plus a column sum: 12-14 launches per
 // step of 64 x 64-tile kernels for a few MFLOP each, 32-way split-K met through fp32 atomics (round-3 review: 8.4 TFLOP/s, "these are
 // bandwidth problems, not MFMA problems").  Here one kernel reads every layer's pre-activation gradients dG [R][8H], its input X [R][In] and
-// its output Hout [R][2H] once and produces, for both directions d,
+// its output Hout [R][2H] (row stride h_ld) once and produces, for both directions d,
 //     dW_ih[d][n][k] = sum_r dG[r][d*4H + n] * X[r][k]
 //     dW_hh[0][n][k] = sum_r dG[r + 1][n] * Hout[r][k]              h(t-1) of the forward direction is one slab row earlier
 //     dW_hh[1][n][k] = sum_r dG[r][4H + n] * Hout[r + 1][H + k]     ... of the reverse direction one row later
@@ -14,6 +15,8 @@
 // accurate than the 32 arrival-order atomics of 6-MFMA split products it replaces.
 //
 // Work item = (task, 64-row block of the 8H gate units, 64-column tile of [X | h-part + bias], row group); 256 threads own 4 x 4 patches.
+// A block gets one h tile per direction when 4H is not a multiple of 64 (its rows may belong to both directions: H < 16, or H = 17..31, where a
+// block straddles the boundary at row 4H); a tile whose direction has no rows in its block ends at once.
 #include "common.h"
 #include "kernels.h"
 
@@ -51,11 +54,12 @@ __global__ __launch_bounds__(256) void lstm_small_wgrad_kernel(const WgradTable 
     tile -= t.tile0;
     const int H = t.H, NROW = 8 * H, In = t.In;
     const int xtiles = (In + 63) / 64;
-    const int hpb = 4 * H >= 64 ? 1 : 2;                      // h tiles per 64-row block: one when the block lies in one direction, else one per direction
+    const int hpb = (4 * H) % 64 == 0 ? 1 : 2;               // h tiles per 64-row block: one when every block lies in one direction, else one per direction
     const int nb = tile / (xtiles + hpb), ct = tile % (xtiles + hpb);       // ct < xtiles: columns 64 ct .. of X; else an h tile (hidden units + bias column)
     const bool htile = ct >= xtiles;
     const int n0 = nb * 64;                                   // first gate unit (of 8H) of this block
     const int hdir = !htile ? -1 : (hpb == 1 ? (n0 >= 4 * H ? 1 : 0) : ct - xtiles);      // the direction an h tile serves (rows of the other one are ignored)
+    if (hpb == 2 && htile && (hdir == 0 ? n0 >= 4 * H : n0 + 63 < 4 * H)) return;          // no row of hdir in this block (whole workgroup: before any barrier)
     const int tid = threadIdx.x, tk = tid & 15, tn = tid >> 4;
     const long R = t.R;
     const int RG = gridDim.x;
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(256) void lstm_small_wgrad_kernel(const WgradTable 
             for (int i = tid; i < RC * 64; i += 256) {
                 const int rr = i >> 6, c = i & 63;
                 const long r = r0 + rr + (hdir == 1 ? 1 : 0);
-                b_s[rr][c] = c < H ? (r < R ? t.Hout[r * 2 * H + hdir * H + c] : 0.f) : (c == 32 ? 1.0f : 0.f);
+                b_s[rr][c] = c < H ? (r < R ? t.Hout[r * t.h_ld + hdir * H + c] : 0.f) : (c == 32 ? 1.0f : 0.f);
             }
         }
         __syncthreads();
@@ -185,13 +189,13 @@ __global__ __launch_bounds__(256) void lstm_small_wgrad_kernel(const WgradTable 
 
 }  // namespace
 
-int lstm_small_wgrad_tiles(int H, int In) { return ((8 * H + 63) / 64) * ((In + 63) / 64 + (4 * H >= 64 ? 1 : 2)); }
+int lstm_small_wgrad_tiles(int H, int In) { return ((8 * H + 63) / 64) * ((In + 63) / 64 + ((4 * H) % 64 == 0 ? 1 : 2)); }
 
 hipError_t lstm_small_wgrad(const WgradTable& tb, hipStream_t s) {
     if (tb.n <= 0) return hipSuccess;
     if (tb.n > WGRAD_MAX || !tb.part || !tb.ctr || tb.row_groups < 1 || tb.tiles_total < 1) return hipErrorInvalidValue;
     for (int i = 0; i < tb.n; ++i)
-        if (tb.t[i].H < 1 || tb.t[i].H > 32 || tb.t[i].In < 1) return hipErrorInvalidValue;
+        if (tb.t[i].H < 1 || tb.t[i].H > 32 || tb.t[i].In < 1 || tb.t[i].h_ld < 2 * tb.t[i].H) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lstm_small_wgrad_kernel, dim3(tb.row_groups, tb.tiles_total), dim3(256), 0, s, tb);
     return hipGetLastError();
 }

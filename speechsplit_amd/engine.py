@@ -564,12 +564,18 @@ def lstm_wgrad(dg, x, hout):
     R, H8 = dg.shape
     H, In = H8 // 8, x.shape[1]
     dev = dg.device
-    tiles = ((8 * H + 63) // 64) * ((In + 63) // 64 + (1 if H >= 16 else 2))
+    tiles = ((8 * H + 63) // 64) * ((In + 63) // 64 + (1 if (4 * H) % 64 == 0 else 2))
     scratch = torch.empty(16 * 4096 * tiles + 256, device=dev)
     gwih, gwhh, gb = torch.zeros(2, 4 * H, In, device=dev), torch.zeros(2, 4 * H, H, device=dev), torch.zeros(2, 2, 4 * H, device=dev)
     _capi.check(lib.ss_op_lstm_wgrad(_ptr(dg), _ptr(x), x.stride(0), _ptr(hout), _ptr(gwih), _ptr(gwhh), _ptr(gb), _ptr(scratch), scratch.numel(), R, H, In,
                                      _stream()))
     return gwih, gwhh, gb
+
+
+def small_lstm_ld(H):
+    """Row stride of the output / cell-state / output-gradient slabs of a BLSTM layer (kernels.h lstm_small_ld): 2H, rounded up to a
+    multiple of 4 floats when H <= 32 is not a power of two."""
+    return 2 * H if H > 32 or H & (H - 1) == 0 else (2 * H + 3) // 4 * 4
 
 
 def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None):
@@ -579,6 +585,7 @@ def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None):
     lib = _capi.lib()
     B, T, In = x.shape
     H = w_hh[0].shape[1]
+    OW = small_lstm_ld(H)                                                   # row stride of out / csave / d_out
     dev = x.device
     wcat = torch.cat([w_ih[0], w_ih[1]], 0).contiguous()                    # [8H, In]
     bsum = torch.cat([b_ih[0] + b_hh[0], b_ih[1] + b_hh[1]]).contiguous()
@@ -589,18 +596,18 @@ def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None):
     gates.copy_(g_real)
     gates.view(B, T + 4, 8 * H)[:, :2] = 0
     gates.view(B, T + 4, 8 * H)[:, T + 2:] = 0
-    out = torch.zeros(B, T + 4, 2 * H, device=dev)
-    csave = torch.zeros(B, T + 4, 2 * H, device=dev)
+    out = torch.zeros(B, T + 4, OW, device=dev)
+    csave = torch.zeros(B, T + 4, OW, device=dev)
     B16 = (B + 15) // 16 * 16
     nscr = 8 * H * H + 16 * B16 * H + 2 * B * H + (4 * ((B + 15) // 16) * (H // 16) ** 2 * 1024 + 8192) // 4 + 4096
     scratch = torch.zeros(max(nscr, 1), device=dev)
     whf, whb = w_hh[0].contiguous(), w_hh[1].contiguous()
     _capi.check(lib.ss_op_lstm_fwd(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(out), _ptr(csave), _ptr(scratch), scratch.numel(),
                                    B, T, H, _stream()))
-    y = out[:, 2:2 + T].clone()
+    y = out[:, 2:2 + T, :2 * H].clone()
     if d_out is None:
         return y
-    ds = _slab(d_out.to(dev))
+    ds = _slab(torch.nn.functional.pad(d_out.to(dev), (0, OW - 2 * H)))
     scratch.zero_()
     _capi.check(lib.ss_op_lstm_bwd(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(ds), _ptr(csave), _ptr(scratch), scratch.numel(),
                                    B, T, H, _stream()))
@@ -608,7 +615,7 @@ def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None):
     dx = gemm(dG, wcat, tb=True).view(B, T + 4, In)[:, 2:2 + T].clone()     # dX = dG . W_ih (both directions)
     grads = []
     flat_x = xs.view(R, In)
-    flat_o = out.view(R, 2 * H)
+    flat_o = out.view(R, OW)
     for d in range(2):
         dGd = dG[:, d * 4 * H:(d + 1) * 4 * H].contiguous()
         gw_ih = gemm(dGd, flat_x, ta=True, tb=True)                         # [4H, In] = dG^T . X
@@ -616,7 +623,7 @@ def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None):
         if d == 0:
             hprev[1:] = flat_o[:-1, :H]                                     # forward: h(t-1) is one slab row earlier
         else:
-            hprev[:-1] = flat_o[1:, H:]
+            hprev[:-1] = flat_o[1:, H:2 * H]
         gw_hh = gemm(dGd, hprev, ta=True, tb=True)
         grads.append((gw_ih, gw_hh, dGd.sum(0)))
     return y, dx, grads
