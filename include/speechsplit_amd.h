@@ -237,7 +237,12 @@ int ss_clear_abort(ss_engine* e, void* stream);
 int ss_set_lockstep(ss_engine* e, int on);
 
 /* ---- test / profiling hooks ---- */
-/* C[M,N] = A . B^T style fp32 MFMA GEMM used by every contraction on the path (flags: 1 = A stored [K,M], 2 = B stored [K,N], 8 = bf16-rounded operands) */
+/* C[M,N] = A . B^T style fp32 MFMA GEMM used by every contraction on the path (flags: 1 = A stored [K,M], 2 = B stored [K,N], 8 = bf16-rounded
+ * operands, 16 = fp16 x 2 split).  Any base address and row stride: operands on 16-byte aligned bases with strides that are multiples of 4 floats
+ * take the vector kernels, everything else the scalar instances of the fp32-MFMA kernel; c_dev rows are ldc >= N floats apart and nothing
+ * outside the M x N extent is written.  Flag 1 without flag 2 (no contraction of the step has that form) runs on the fp32-MFMA kernel in every
+ * arithmetic mode; flag 8 rounds the operands to bf16 on whichever kernel runs.  ksplit > 1 ADDS the partial products into C (atomics): C must
+ * hold zeros (or the value to accumulate onto) on entry. */
 int ss_op_gemm(const float* a_dev, long lda, const float* b_dev, long ldb, float* c_dev, long ldc, const float* bias_dev,
                int M, int N, int K, int flags, int ksplit, void* stream);
 /* One bidirectional LSTM recurrence on haloed slabs (speechsplit_amd/csrc/kernels.h): gates [B,T+4,8H] holds
@@ -255,7 +260,8 @@ int ss_op_lstm_bwd(float* gates_dev, const float* whh_f_dev, const float* whh_b_
 /* Test hook for the fused weight / bias gradient kernel of the encoder BLSTMs (csrc/lstm_wgrad.hip; hidden size <= 32): from the pre-activation
  * gradients dg [R][8H], the layer input x [R][In] (row stride x_ld) and the layer output hout [R][2H] (haloed slabs flattened to R rows, halo
  * rows zero) ACCUMULATE dW_ih [2][4H][In], dW_hh [2][4H][H] and the bias gradients gb [2][2][4H] (b_ih, b_hh per direction).  scratch:
- * >= 16 * 4096 * tiles + 64 floats with tiles = ceil(8H / 64) * (ceil(In / 64) + (4H % 64 == 0 ? 1 : 2)); H in 1..32, hout rows 2H apart. */
+ * >= 16 * 4096 * tiles + roundup(tiles, 64) floats with tiles = ceil(8H / 64) * (ceil(In / 64) + (4H % 64 == 0 ? 1 : 2)) -- the partial
+ * slabs and one arrival counter per tile; H in 1..32, hout rows 2H apart. */
 int ss_op_lstm_wgrad(const float* dg_dev, const float* x_dev, long x_ld, const float* hout_dev, float* gwih_dev, float* gwhh_dev, float* gb_dev,
                      float* scratch_dev, long scratch_floats, long R, int H, int In, void* stream);
 /* The GEMM over operand images (speechsplit_amd/csrc/gemm_img.hip), the engine's default for every large contraction: an IMAGE has the
@@ -320,7 +326,9 @@ int ss_tune(const char* key, int value);
  *       |p| >= 2048, checked inside every forward (there is no silent overflow and no automatic change of split).
  *     bf16 x 3 (head, encoder BLSTMs, unaligned shapes; everything with ss_tune("fwd_f16x2" / "bwd_f16x2", 0)): exact
  *       3-way truncation split x = h + m + l, 6 v_mfma_f32_32x32x16_bf16 per k-step, dropped terms <= 2^-24 relative.
- *     ss_tune("gemm_mode", 0): true fp32 MFMA (v_mfma_f32_32x32x2_f32), the A/B reference.
+ *     ss_tune("gemm_mode", 0): true fp32 MFMA (v_mfma_f32_32x32x2_f32), the A/B reference.  (In SS_PRECISION_BF16 the contractions carry the
+ *       bf16 flag and this kernel rounds their operands to bf16 like every other: the products are then fp32-wide over bf16-rounded
+ *       operands, not the unrounded fp32 reference -- take that in SS_PRECISION_F32.)
  *   Against fp64 the three measure 1.3-2.2e-6, 1.2e-6 and 1.3e-6 of max|C| (profiles/r02/f16x2_error.txt).
  *   ss_tune("gemm_mode", 0) together with ss_tune("persist", 0) (the decoder recurrences as one fp32-MFMA launch per time step) is the mode in
  *   which EVERY product of the step is fp32-wide -- the reference's arithmetic; bench.py times it as alt_precisions.all_fp32_mfma.

@@ -27,6 +27,14 @@ namespace {
 
 constexpr int PADL = 4;
 
+// GEMM_BF16 on this kernel (operands the 16-bit kernel does not take: unaligned bases, odd strides, A^T . B^T): round to bf16, nearest even,
+// as gemm_bf16x3.hip's single-piece form does, and multiply the rounded values on the fp32 pipe
+__device__ __forceinline__ float bf16_rne(float x) {
+    unsigned r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %1" : "=v"(r) : "v"(x));
+    return __uint_as_float(r << 16);
+}
+
 template <bool VEC>
 __device__ __forceinline__ f32x4 load4(const Operand& op, const float* base, int row, int col, int R, int C) {
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -181,6 +189,16 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmDesc d) {
             if (VEC) rb[i] = fetch(d.B, pb[i], wb[i], okb[i], TB, TB ? k0 + f / (BN / 4) : k0 + (f % (BK / 4)) * 4, d.N);
             else if (!TB) rb[i] = load4<false>(d.B, Bb, n0 + f / (BK / 4), k0 + (f % (BK / 4)) * 4, d.N, kend);
             else rb[i] = load4<false>(d.B, Bb, k0 + f / (BN / 4), n0 + (f % (BN / 4)) * 4, kend, d.N);
+        }
+        if (d.flags & GEMM_BF16) {
+#pragma unroll
+            for (int i = 0; i < NA; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ra[i][j] = bf16_rne(ra[i][j]);
+#pragma unroll
+            for (int i = 0; i < NB; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) rb[i][j] = bf16_rne(rb[i][j]);
         }
     };
     auto sstore = [&](f32x4(&ra)[NA], f32x4(&rb)[NB], int buf) {
@@ -340,16 +358,18 @@ hipError_t launch_gemm(const GemmDesc& din, hipStream_t s) {
     // (its fp32 atomics would commit in arrival order).  Round 2 dropped split-K altogether there: 2.2x the default step.
     const bool vec = vec_ok(d.A) && vec_ok(d.B);
     const bool seg_ok = (d.A.seglen == 0 || d.A.seglen >= 32) && (d.B.seglen == 0 || d.B.seglen >= 32);   // one wrap per k-tile
-    const bool split_kernel = vec && seg_ok && g_gemm_mode == 1;            // the bf16 x 3 / fp16 x 2 kernel: the one with the partial-slab split-K
+    const bool ta = d.flags & GEMM_TA, tb = d.flags & GEMM_TB;
+    // the bf16 x 3 / fp16 x 2 kernel: the one with the partial-slab split-K.  It has no instances for A stored [K,M] with B stored [N,K] (no
+    // contraction of the step has that form): that layout runs on the fp32-MFMA kernel below in every mode
+    const bool split_kernel = vec && seg_ok && g_gemm_mode == 1 && !(ta && !tb);
     if (d.ksplit < 1 || (g_deterministic && !(d.part && split_kernel))) d.ksplit = 1;
     if (d.ksplit > 1 && !(d.flags & GEMM_ACCUM)) return hipErrorInvalidValue;   // split-K needs a zeroed / live C
     if (split_kernel) return launch_gemm_bf16x3(d, s);
     d.part = nullptr;              // the fp32-MFMA kernel's split-K meets in C through atomics
-    const bool ta = d.flags & GEMM_TA, tb = d.flags & GEMM_TB;
     if (!ta && !tb) return launch_layout<false, false>(d, vec, s);
     if (!ta && tb) return launch_layout<false, true>(d, vec, s);
     if (ta && tb) return launch_layout<true, true>(d, vec, s);
-    return hipErrorInvalidValue;   // (TA, !TB) is not used on this path
+    return launch_layout<true, false>(d, vec, s);
 }
 
 }  // namespace ss

@@ -31,7 +31,10 @@ def draw_interp(batch, ncalls, hp, generator=None):
 
 
 class Engine:
-    def __init__(self, kind, hp, max_batch, max_frames=None, device=None):
+    def __init__(self, kind, hp, max_batch, max_frames=None, device=None, alloc=None):
+        """alloc(name, shape, dtype): optional provider of every device buffer the engine owns or returns -- the arenas 'params' / 'grads' /
+        'adam_m' / 'adam_v' (zero-filled by the provider), the workspace 'ws' (uint8, 256-byte aligned, any contents), 'loss', and the
+        outputs of the forwards and input-gradient backwards ('out', 'dx_f0', ...) -- for callers that place them themselves."""
         if not torch.cuda.is_available():
             raise RuntimeError('speechsplit_amd.Engine needs a ROCm GPU (no CPU fallback)')
         self.lib = _capi.lib()
@@ -41,6 +44,7 @@ class Engine:
         self.max_batch = int(max_batch)
         self.max_frames = int(max_frames or hp.max_len_pad)
         self._stagers = {}
+        self._alloc = alloc
         self._fwd_bt = None                # (B, T) of the last g3_forward / g6_forward; None after any other forward
         self._hps = _capi.hparams_struct(hp)
         self.h = self.lib.ss_create(KIND[kind], C.byref(self._hps), self.max_batch, self.max_frames)
@@ -54,14 +58,21 @@ class Engine:
             self.table.append((name.value.decode(), off.value, tuple(shp[k] for k in range(nd.value))))
         n = self.lib.ss_arena_numel(self.h)
         with torch.cuda.device(self.device):
-            self.params = torch.zeros(n, device=self.device)
-            self.grads = torch.zeros(n, device=self.device)
-            self.adam_m = torch.zeros(n, device=self.device)
-            self.adam_v = torch.zeros(n, device=self.device)
-            self.ws = torch.empty(self.lib.ss_workspace_bytes(self.h), dtype=torch.uint8, device=self.device)
-            self.loss = torch.zeros(1, device=self.device)
+            self.params = self._new('params', (n,), zero=True)
+            self.grads = self._new('grads', (n,), zero=True)
+            self.adam_m = self._new('adam_m', (n,), zero=True)
+            self.adam_v = self._new('adam_v', (n,), zero=True)
+            self.ws = self._new('ws', (self.lib.ss_workspace_bytes(self.h),), torch.uint8)
+            self.loss = self._new('loss', (1,), zero=True)
             _capi.check(self.lib.ss_bind(self.h, _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
                                          _ptr(self.ws), self.ws.numel(), _stream()))
+
+    def _new(self, name, shape, dtype=torch.float32, zero=False):
+        if self._alloc is not None:
+            t = self._alloc(name, tuple(shape), dtype)
+            assert t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.dtype == dtype, name
+            return t
+        return (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self.device)
 
     def __del__(self):
         try:
@@ -108,7 +119,7 @@ class Engine:
         if need <= self.ws.numel():
             return False
         with torch.cuda.device(self.device):
-            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._new('ws', (need,), torch.uint8)
             _capi.check(self.lib.ss_set_workspace(self.h, _ptr(ws), ws.numel(), _stream()))
         self.ws = ws                                   # the call synchronised: nothing runs on the old workspace any more
         return True
@@ -148,7 +159,7 @@ class Engine:
         if c_trg.shape[0] != B:
             c_trg = c_trg.expand(B, -1).contiguous()
         sc, ls = self._draws(draws)
-        out = torch.empty(B, T, self.hp.dim_freq, device=self.device)
+        out = self._new('out', (B, T, self.hp.dim_freq))
         self._fwd_bt = None
         self._reserve_eval(B, T, training)
         _capi.check(self.lib.ss_g3_forward(self.h, _ptr(x_f0), _ptr(x_org), _ptr(c_trg), _ptr(sc), _ptr(ls), B, T,
@@ -170,7 +181,7 @@ class Engine:
         hp = self.hp
         shape = {'x_f0': (B, T, hp.dim_freq + hp.dim_f0), 'x_org': (B, T, hp.dim_freq), 'c_trg': (B, hp.dim_spk_emb),
                  'f0_trg': (B, T, hp.dim_f0)}
-        return tuple(torch.empty(shape[n], device=self.device) if n in inputs else None for n in names)
+        return tuple(self._new('d' + n, shape[n]) if n in inputs else None for n in names)
 
     def g3_backward(self, d_out, inputs=()):
         """loss.backward() for the last g3_forward: parameter gradients into the arena.  inputs: names among G3_INPUTS whose gradients
@@ -189,7 +200,7 @@ class Engine:
         B, T, _ = x_org.shape
         self._reserve_eval(B, T, False)
         x_org = self._f(x_org)
-        codes = torch.empty(B, T // self.hp.freq_2, 2 * self.hp.dim_neck_2, device=self.device)
+        codes = self._new('codes', (B, T // self.hp.freq_2, 2 * self.hp.dim_neck_2))
         _capi.check(self.lib.ss_g3_rhythm(self.h, _ptr(x_org), B, T, _ptr(codes), _stream()))
         return codes
 
@@ -332,7 +343,7 @@ class Engine:
         B, T, _ = x_org.shape
         x_org, f0_trg = self._f(x_org), self._f(f0_trg)
         sc, ls = self._draws(draws)
-        out = torch.empty(B, T, self.hp.dim_f0, device=self.device)
+        out = self._new('out', (B, T, self.hp.dim_f0))
         self._fwd_bt = None
         self._reserve_eval(B, T, training)
         _capi.check(self.lib.ss_g6_forward(self.h, _ptr(x_org), _ptr(f0_trg), _ptr(sc), _ptr(ls), B, T, int(training),
@@ -393,23 +404,29 @@ class Engine:
     def zero_grads(self):
         _capi.check(self.lib.ss_zero_grads(self.h, _stream()))
 
-    def interp_forward(self, x, len_seq, scales, len_seg, want_plan=False):
+    def interp_forward(self, x, len_seq, scales, len_seg, want_plan=False, out=None):
+        """out: optional pre-placed dense outputs (y, i0, lam, counts) instead of fresh ones (i0 / lam / counts may be None)."""
         B, T, Cc = x.shape
         P = self.hp.max_len_pad
         x, len_seq = self._f(x), self._i(torch.as_tensor(len_seq))
         sc, ls = self._f(torch.as_tensor(scales)), self._i(torch.as_tensor(len_seg))
-        y = torch.empty(B, P, Cc, device=self.device)
-        i0 = torch.empty(B, P, dtype=torch.int32, device=self.device) if want_plan else None
-        lam = torch.empty(B, P, device=self.device) if want_plan else None
-        cnt = torch.empty(B, dtype=torch.int32, device=self.device) if want_plan else None
+        if out is not None:
+            y, i0, lam, cnt = out
+            assert all(t is None or t.is_contiguous() for t in out) and tuple(y.shape) == (B, P, Cc)
+        else:
+            y = torch.empty(B, P, Cc, device=self.device)
+            i0 = torch.empty(B, P, dtype=torch.int32, device=self.device) if want_plan else None
+            lam = torch.empty(B, P, device=self.device) if want_plan else None
+            cnt = torch.empty(B, dtype=torch.int32, device=self.device) if want_plan else None
         _capi.check(self.lib.ss_interp_forward(self.h, _ptr(x), _ptr(len_seq), _ptr(sc), _ptr(ls), B, T, Cc, _ptr(y),
                                                _ptr(i0), _ptr(lam), _ptr(cnt), _stream()))
         return (y, i0, lam, cnt) if want_plan else y
 
-    def interp_backward(self, dy, T):
+    def interp_backward(self, dy, T, out=None):
         B, P, Cc = dy.shape
         dy = self._f(dy)
-        dx = torch.empty(B, T, Cc, device=self.device)
+        dx = torch.empty(B, T, Cc, device=self.device) if out is None else out
+        assert dx.is_contiguous() and tuple(dx.shape) == (B, T, Cc)
         _capi.check(self.lib.ss_interp_backward(self.h, _ptr(dy), B, T, Cc, _ptr(dx), _stream()))
         return dx
 
@@ -478,23 +495,27 @@ class Engine:
         names = self.PROF_CLASSES + self.PROF_TIMELINE
         return [(names[int(buf[3 * i]) % 100], buf[3 * i + 1], buf[3 * i + 2], int(buf[3 * i]) // 100) for i in range(n)]
 
-    def debug_buffer(self, name, B, T):
-        """Real frames of an internal haloed slab as a [B, T, C] tensor (copy)."""
+    def debug_buffer(self, name, B, T, halo=False):
+        """Real frames of an internal haloed slab as a [B, T, C] tensor (copy); halo=True: the whole slab [B, T + 4, C], halo rows included."""
         p, rows, cols = C.c_void_p(), C.c_long(), C.c_long()
         _capi.check(self.lib.ss_debug_buffer(self.h, name.encode(), C.byref(p), C.byref(rows), C.byref(cols)))
         off = p.value - self.ws.data_ptr()
         n = rows.value * cols.value
         flat = self.ws[off:off + 4 * n].view(torch.float32)
-        return flat.view(B, T + 4, cols.value)[:, 2:2 + T].clone()
+        slab = flat.view(B, T + 4, cols.value)
+        return slab.clone() if halo else slab[:, 2:2 + T].clone()
 
 
-def split_image(x, scale=16.0):
+def split_image(x, scale=16.0, out=None):
     """Test hook (ss_op_split_image): fp32 [rows, cols] (cols % 8 == 0) -> its operand image, a float32-typed tensor of the same shape whose
-    bytes are, per 8 elements, 16 B of fp16 hi pieces and 16 B of fp16 lo pieces of scale * x (csrc/common.h, image format v2)."""
+    bytes are, per 8 elements, 16 B of fp16 hi pieces and 16 B of fp16 lo pieces of scale * x (csrc/common.h, image format v2).  x may be a
+    row-strided view (its row stride is passed on); out: a pre-placed image tensor of the same shape (row stride a multiple of 8)."""
     lib = _capi.lib()
     rows, cols = x.shape
-    x = x.contiguous()
-    img = torch.empty_like(x)
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    img = torch.empty(rows, cols, device=x.device) if out is None else out
+    assert tuple(img.shape) == (rows, cols) and img.stride(1) == 1
     _capi.check(lib.ss_op_split_image(_ptr(x), x.stride(0), rows, cols, float(scale), _ptr(img), img.stride(0), _stream()))
     return img
 
@@ -503,7 +524,7 @@ _ZEROS = {}
 
 
 def gemm_img(a_img, b_img, ta=False, tb=False, bias=None, ksplit=1, cfg=-1, scale_a=16.0, scale_b=16.0, out=None, accumulate=False, a_seg=(0, 0),
-             M=None, K=None, part=None):
+             M=None, K=None, part=None, zeros=None):
     """Test hook (ss_op_gemm_img): C[M,N] = A(m,k) B(n,k) over operand images.  a_img [M,K] ([K,M] if ta), b_img [N,K] ([K,N] if tb).
     torch.bfloat16 operands select the single-piece form (plain bf16 matrices, no scales)."""
     lib = _capi.lib()
@@ -518,16 +539,18 @@ def gemm_img(a_img, b_img, ta=False, tb=False, bias=None, ksplit=1, cfg=-1, scal
     c = torch.zeros(M, N, device=dev) if out is None else out
     if ksplit > 1 and part is None:
         part = torch.empty(ksplit * M * N, device=dev)
-    z = _ZEROS.setdefault(str(dev), torch.zeros(1024, device=dev))
+    z = _ZEROS.setdefault(str(dev), torch.zeros(1024, device=dev)) if zeros is None else zeros     # zeros_dev: >= 1 KB of zero bytes
     _capi.check(lib.ss_op_gemm_img(_ptr(a_img), a_img.stride(0), _ptr(b_img), b_img.stride(0), _ptr(c), c.stride(0), _ptr(bias), M, N, K,
                                    (1 if ta else 0) | (2 if tb else 0) | (4 if accumulate else 0) | (8 if bf16 else 0), int(ksplit), int(cfg), float(scale_a),
                                    float(scale_b), int(a_seg[0]), int(a_seg[1]), _ptr(part), _ptr(z), _stream()))
     return c
 
 
-def conv_block(x, w, bias, gamma, beta, dy=None, need_dx=True):
+def conv_block(x, w, bias, gamma, beta, dy=None, need_dx=True, scratch=None, out=None):
     """Test hook (ss_op_conv_block): relu(GroupNorm(conv5(x))) of one block through the engine's block routines.
-    x [B,T,Ci] -> y [B,T,Co]; with dy also (dx, gw, gb, ggamma, gbeta)."""
+    x [B,T,Ci] -> y [B,T,Co]; with dy also (dx, gw, gb, ggamma, gbeta).  The C ABI takes dense tensors: contiguous operands are passed where
+    they lie (any base), others are copied.  scratch: pre-placed, at least ss_op_conv_block_scratch() floats; out: dict of pre-placed dense
+    outputs by name (y, dx, gw, gb, ggamma, gbeta)."""
     lib = _capi.lib()
     B, T, Ci = x.shape
     Co = w.shape[0]
@@ -535,15 +558,26 @@ def conv_block(x, w, bias, gamma, beta, dy=None, need_dx=True):
     f = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
     x, w, bias, gamma, beta = f(x), f(w), f(bias), f(gamma), f(beta)
     n = lib.ss_op_conv_block_scratch(B, T, Ci, Co)
-    scratch = torch.empty(n, device=dev)
-    y = torch.empty(B, T, Co, device=dev)
+    if scratch is None:
+        scratch = torch.empty(n, device=dev)
+    assert scratch.is_contiguous() and scratch.numel() >= n
+    n = scratch.numel()
+    out = out or {}
+
+    def o(name, *shape):
+        t = out.get(name)
+        if t is None:
+            return torch.empty(*shape, device=dev)
+        assert tuple(t.shape) == shape and t.is_contiguous(), name
+        return t
+    y = o('y', B, T, Co)
     if dy is None:
         _capi.check(lib.ss_op_conv_block(_ptr(x), _ptr(w), _ptr(bias), _ptr(gamma), _ptr(beta), None, _ptr(y), None, None, None,
                                          None, None, _ptr(scratch), n, B, T, Ci, Co, _stream()))
         return y
     dy = f(dy)
-    dx = torch.empty(B, T, Ci, device=dev) if need_dx else None
-    gw, gb, gg, gbe = torch.empty_like(w), torch.empty_like(bias), torch.empty_like(gamma), torch.empty_like(beta)
+    dx = o('dx', B, T, Ci) if need_dx else None
+    gw, gb, gg, gbe = o('gw', *w.shape), o('gb', Co), o('ggamma', Co), o('gbeta', Co)
     _capi.check(lib.ss_op_conv_block(_ptr(x), _ptr(w), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(dy), _ptr(y), _ptr(dx), _ptr(gw),
                                      _ptr(gb), _ptr(gg), _ptr(gbe), _ptr(scratch), n, B, T, Ci, Co, _stream()))
     return y, dx, gw, gb, gg, gbe
@@ -557,16 +591,27 @@ def _slab(x):
     return s
 
 
-def lstm_wgrad(dg, x, hout):
+def lstm_wgrad_scratch(H, In):
+    """Scratch floats ss_op_lstm_wgrad needs (include/speechsplit_amd.h): 16 * 4096 * tiles partial slabs + one arrival counter per tile,
+    rounded up to 64."""
+    tiles = ((8 * H + 63) // 64) * ((In + 63) // 64 + (1 if (4 * H) % 64 == 0 else 2))
+    return 16 * 4096 * tiles + (tiles + 63) // 64 * 64
+
+
+def lstm_wgrad(dg, x, hout, scratch=None, out=None):
     """Test hook (ss_op_lstm_wgrad): the fused weight / bias gradient kernel of the encoder BLSTMs.  dg [R, 8H], x [R, In] (may be a
-    column view of a wider tensor), hout [R, 2H] -> (gw_ih [2, 4H, In], gw_hh [2, 4H, H], gb [2, 2, 4H])."""
+    column view of a wider tensor), hout [R, 2H] -> (gw_ih [2, 4H, In], gw_hh [2, 4H, H], gb [2, 2, 4H]).  scratch: pre-placed, at least
+    lstm_wgrad_scratch(H, In) floats; out: pre-placed dense (gw_ih, gw_hh, gb), which the kernel ACCUMULATES into."""
     lib = _capi.lib()
     R, H8 = dg.shape
     H, In = H8 // 8, x.shape[1]
     dev = dg.device
-    tiles = ((8 * H + 63) // 64) * ((In + 63) // 64 + (1 if (4 * H) % 64 == 0 else 2))
-    scratch = torch.empty(16 * 4096 * tiles + 256, device=dev)
-    gwih, gwhh, gb = torch.zeros(2, 4 * H, In, device=dev), torch.zeros(2, 4 * H, H, device=dev), torch.zeros(2, 2, 4 * H, device=dev)
+    if scratch is None:
+        scratch = torch.empty(lstm_wgrad_scratch(H, In) + 256, device=dev)
+    if out is None:
+        out = torch.zeros(2, 4 * H, In, device=dev), torch.zeros(2, 4 * H, H, device=dev), torch.zeros(2, 2, 4 * H, device=dev)
+    gwih, gwhh, gb = out
+    assert dg.is_contiguous() and hout.is_contiguous() and x.stride(1) == 1 and all(t.is_contiguous() for t in out) and scratch.is_contiguous()
     _capi.check(lib.ss_op_lstm_wgrad(_ptr(dg), _ptr(x), x.stride(0), _ptr(hout), _ptr(gwih), _ptr(gwhh), _ptr(gb), _ptr(scratch), scratch.numel(), R, H, In,
                                      _stream()))
     return gwih, gwhh, gb
@@ -578,10 +623,29 @@ def small_lstm_ld(H):
     return 2 * H if H > 32 or H & (H - 1) == 0 else (2 * H + 3) // 4 * 4
 
 
-def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None):
+def lstm_scratch(B, H, backward, persist=True):
+    """Scratch floats ss_op_lstm_fwd / ss_op_lstm_bwd need, by the header's formulas (include/speechsplit_amd.h): none for H <= 32; else
+    8 H^2 + 4 ceil16(B) H (forward) or 8 H^2 + 16 ceil16(B) H + 2 B H (backward), and for the backward as ONE persistent launch
+    (H in {256, 512}) at least its exchange tiles and flags, 4 ceil(B / 16) (H / 16)^2 * 1024 + 8192 bytes."""
+    if H <= 32:
+        return 0
+    B16 = (B + 15) // 16 * 16
+    if not backward:
+        return 8 * H * H + 4 * B16 * H
+    n = 8 * H * H + 16 * B16 * H + 2 * B * H
+    if persist and H in (256, 512):
+        n = max(n, (4 * (B16 // 16) * (H // 16) ** 2 * 1024 + 8192) // 4)
+    return n
+
+
+def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None, place=None):
     """Test hook: one bidirectional LSTM layer through ss_op_lstm_fwd / ss_op_lstm_bwd (the engine's recurrence kernels) with
     the input projection and the weight / input gradients on the engine's GEMM (ss_op_gemm).  w_ih etc. are (forward, reverse)
-    pairs with PyTorch's shapes.  Returns out [B,T,2H]; with d_out also (dx, [(gw_ih, gw_hh, gb) per direction])."""
+    pairs with PyTorch's shapes.  Returns out [B,T,2H]; with d_out also (dx, [(gw_ih, gw_hh, gb) per direction]).
+    place(name, shape): optional allocator of the recurrences' operands -- 'gates' [R,8H], 'out' / 'csave' / 'd_out' [B,T+4,ld] and
+    'scratch_fwd' / 'scratch_bwd' [lstm_scratch(...) floats, at least 1] -- for callers that pre-place them.  It returns a dense tensor that
+    the CALLER has initialised as the kernels' contracts ask (halo rows of out / csave / d_out zero, scratch of a persistent recurrence
+    zero); the hook fills gates entirely and the real frames' 2H columns of d_out, nothing else."""
     lib = _capi.lib()
     B, T, In = x.shape
     H = w_hh[0].shape[1]
@@ -591,25 +655,37 @@ def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None):
     bsum = torch.cat([b_ih[0] + b_hh[0], b_ih[1] + b_hh[1]]).contiguous()
     xs = _slab(x)
     R = B * (T + 4)
-    gates = torch.zeros(R, 8 * H, device=dev)
+    gates = torch.zeros(R, 8 * H, device=dev) if place is None else place('gates', (R, 8 * H))
     g_real = gemm(xs.view(R, In), wcat, bsum)                               # all rows, halo rows are then re-zeroed
     gates.copy_(g_real)
     gates.view(B, T + 4, 8 * H)[:, :2] = 0
     gates.view(B, T + 4, 8 * H)[:, T + 2:] = 0
-    out = torch.zeros(B, T + 4, OW, device=dev)
-    csave = torch.zeros(B, T + 4, OW, device=dev)
     B16 = (B + 15) // 16 * 16
-    nscr = 8 * H * H + 16 * B16 * H + 2 * B * H + (4 * ((B + 15) // 16) * (H // 16) ** 2 * 1024 + 8192) // 4 + 4096
-    scratch = torch.zeros(max(nscr, 1), device=dev)
+    if place is None:
+        out = torch.zeros(B, T + 4, OW, device=dev)
+        csave = torch.zeros(B, T + 4, OW, device=dev)
+        nscr = 8 * H * H + 16 * B16 * H + 2 * B * H + (4 * ((B + 15) // 16) * (H // 16) ** 2 * 1024 + 8192) // 4 + 4096
+        scratch = scratch_b = torch.zeros(max(nscr, 1), device=dev)
+    else:
+        out, csave = place('out', (B, T + 4, OW)), place('csave', (B, T + 4, OW))
+        scratch = place('scratch_fwd', (max(lstm_scratch(B, H, False), 1),))
+        scratch_b = place('scratch_bwd', (max(lstm_scratch(B, H, True), 1),)) if d_out is not None else None
+        for t in (gates, out, csave, scratch):
+            assert t.is_contiguous()
     whf, whb = w_hh[0].contiguous(), w_hh[1].contiguous()
     _capi.check(lib.ss_op_lstm_fwd(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(out), _ptr(csave), _ptr(scratch), scratch.numel(),
                                    B, T, H, _stream()))
     y = out[:, 2:2 + T, :2 * H].clone()
     if d_out is None:
         return y
-    ds = _slab(torch.nn.functional.pad(d_out.to(dev), (0, OW - 2 * H)))
-    scratch.zero_()
-    _capi.check(lib.ss_op_lstm_bwd(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(ds), _ptr(csave), _ptr(scratch), scratch.numel(),
+    if place is None:
+        ds = _slab(torch.nn.functional.pad(d_out.to(dev), (0, OW - 2 * H)))
+        scratch_b.zero_()
+    else:
+        ds = place('d_out', (B, T + 4, OW))
+        assert ds.is_contiguous() and scratch_b.is_contiguous()
+        ds[:, 2:2 + T, :2 * H] = d_out.to(dev)
+    _capi.check(lib.ss_op_lstm_bwd(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(ds), _ptr(csave), _ptr(scratch_b), scratch_b.numel(),
                                    B, T, H, _stream()))
     dG = gates.view(R, 8 * H)                                               # pre-activation gradients, halo rows zero
     dx = gemm(dG, wcat, tb=True).view(B, T + 4, In)[:, 2:2 + T].clone()     # dX = dG . W_ih (both directions)
@@ -642,6 +718,7 @@ def gemm(a, b, bias=None, ta=False, tb=False, ksplit=1, out=None, bf16=False, f1
     N = b.shape[1] if tb else b.shape[0]
     assert (b.shape[0] if tb else b.shape[1]) == K
     c = torch.zeros(M, N, device=a.device) if out is None else out
-    _capi.check(lib.ss_op_gemm(_ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(c), N, _ptr(bias), M, N, K,
+    assert tuple(c.shape) == (M, N) and c.stride(1) == 1
+    _capi.check(lib.ss_op_gemm(_ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(c), c.stride(0), _ptr(bias), M, N, K,
                                (1 if ta else 0) | (2 if tb else 0) | (8 if bf16 else 0) | (16 if f16x2 else 0), ksplit, _stream()))
     return c
