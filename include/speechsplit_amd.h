@@ -293,21 +293,18 @@ int ss_op_conv_block(const float* x_dev, const float* w_dev, const float* bias_d
  * of 0 may fall on either side in two correct implementations; parity tests hand this mask to the oracle so that the
  * comparison of gradients does not depend on that coin flip. */
 int ss_debug_relu_mask(ss_engine* e, const char* block, float* mask_dev, void* stream);
-/* tuning knobs (process-global; every value leaves the results correct): "lstm_nw" 4|8|16, "lstm_g" 0..16, "gemm_bk" 16|32,
- * "gemm_want" >= 1, "overlap" 0|1, "persist" 0|1, "split" 0|1, "gemm_mode" 0 (fp32 MFMA) | 1 (split arithmetic on
+/* tuning knobs (process-global; every value leaves the results correct): "lstm_nw" 4|8|16, "lstm_g" 0..16,
+ * "gemm_want" >= 1, "overlap" 0|1, "persist" 0|1, "gemm_mode" 0 (fp32 MFMA) | 1 (split arithmetic on
  * the 16-bit pipe), "fwd_f16x2" / "bwd_f16x2" 0|1 (fp16 x 2 instead of bf16 x 3 for the forward / the scaled gradient
  * contractions), "seq_spin_log2" 0..24 (log2 of the persistent kernels' bounded wait; 0 makes it expire at once -- how the
  * tests exercise the abort path), "deterministic" 0|1, "seq_tag" 0|1 (forward persistent recurrence: step tag in the hand-off
- * payload where every group sits on one XCD | always the flag line), "seq_wlead" 0..31 (backward persistent recurrence: steps
- * between a warm-up read and the operand request it serves, 0 = the kernel's default), "seq_var" 0|2|4 (... form of those warm-up
+ * payload where every group sits on one XCD | always the flag line), "seq_var" 0|2|4 (backward persistent recurrence: form of its warm-up
  * reads: whole 1 KB runs | one dword per 128-byte line (default) | one per 64 bytes; results bit-identical), "gemm_ws" 0|1|2 (wave-specialised form of
- * the 128 x 128 fp16 x 2 GEMM: never | where it measured faster in isolation | always), "img" 0|1 and "img_mask" (bit = SS_PROF_* class: which contractions run on the image GEMM, csrc/gemm_img.hip; default decoder projections, conv forward, conv input gradients), "dp_model" 0|2..64 and "dp_buckets" 0|1 (data-parallel schedule, see ss_g3_dp_train_step), "presplit" 0..15 (operand images for the fp16 x 2 GEMMs: bit 0 weights, bit 1 decoder hidden states, bit 2 trunk
- * activations), "compact0" 0|1 (decoder layer 0 on one row per block of repeated input frames), "trunk_indep" 0|1, "batch_dirs" 0..2,
- * "prewarm" 0..3 (streaming pre-read of a decoder layer's operand slabs on a side stream beside its
- * persistent recurrence: bit 1 forward, bit 0 backward), "op_time_major" 0|1 (ss_op_lstm_fwd / _bwd
+ * the 128 x 128 fp16 x 2 GEMM: never | where it measured faster in isolation | always), "dp_model" 0|2..64 and "dp_buckets" 0|1 (data-parallel schedule, see ss_g3_dp_train_step),
+ * "compact0" 0|1 (decoder layer 0 on one row per block of repeated input frames), "op_time_major" 0|1 (ss_op_lstm_fwd / _bwd
  * read their slabs as [T+4,B,C]; persistent kernels only -- a layout experiment); schedule of the end of the backward (round 4,
- * tools/real_timeline.py): "dec_tail_split" 0..6 (which stream takes the decoder's layer-0 / layer-1 and the head's weight gradients; default 2),
- * "enc_t_first" 0|1, "conv_dw_off" 0|1 (Generator_6: conv weight gradients off the trunk's dependent chain), "early_dw" 0|1 (16-bit mode: a decoder
+ * tools/real_timeline.py): "dec_tail_split" 0..10 (which stream takes the decoder's layer-0 / layer-1 and the head's weight gradients; default 9),
+ * "conv_dw_off" 0|1 (Generator_6: conv weight gradients off the trunk's dependent chain), "early_dw" 0|1 (16-bit mode: a decoder
  * layer's weight gradients beside the next backward recurrence, off).  The timing experiments that produce WRONG results ("lstm_mode",
  * "gemm_diag", "seq_prio" > 1) are compiled out of this library; `make -C speechsplit_amd/csrc diag` builds
  * libspeechsplit_hip_diag.so with them for tools/ (never loaded by the package unless SS_DIAG_LIB=1 is set). */
@@ -342,7 +339,7 @@ int ss_tune(const char* key, int value);
  *   cell state, gate pre-activations, GroupNorm statistics, losses, the resampling index path (bit-exact as in the fp32 mode), Adam.
  *   Contractions without images (layer-0 convolutions over the 80 / 264-channel inputs, the decoder's 164-column layer-0 input, the head's
  *   weights, the encoder BLSTM projections) round their fp32 operands to bf16 inside round 2's GEMM kernel; the encoder BLSTMs' weight
- *   gradients are exact fp32 sums in both modes (csrc/lstm_wgrad.hip).  ss_tune("bf16_img", 0) / ("seq_hi", 0) select round 3's form of the
+ *   gradients are exact fp32 sums in both modes (csrc/lstm_wgrad.hip).  ss_tune("bf16_img", 0) selects round 3's form of the
  *   mode (fp32 slabs only, operands rounded inside the GEMM, fp16 x 2 recurrences) for A/B runs. */
 #define SS_PRECISION_F32 0
 #define SS_PRECISION_BF16 1

@@ -6,7 +6,6 @@
 namespace ss {
 
 extern int g_deterministic;
-int g_gn_part = 0;       // GroupNorm backward: per-utterance affine / bias gradient sums to scratch + ordered reduce instead of f32 atomics (ss_tune("gn_part"))
 
 namespace {
 
@@ -954,7 +953,7 @@ hipError_t gn_relu_bwd(const float* x, long x_ld, long x_bs, float* dy, long dy_
     if (C % 64 != 0 || T > 16 * GN_MAXIT) return hipErrorInvalidValue;
     if (dy_img && (dy_ld % 8 || dy_bs % 8 || (((size_t)dy_img) & 7))) return hipErrorInvalidValue;
     if (scatter && (!src || scatter->T != T || scatter->P > 16 * GN_MAXIT + 2 || src_ld % 4 || src_bs % 4 || (((size_t)src) & 15))) return hipErrorInvalidValue;
-    if (!g_deterministic && !g_gn_part) part = nullptr;
+    if (!g_deterministic) part = nullptr;      // per-utterance sums to scratch + ordered reduce only where the order matters; f32 atomics otherwise
     // (an 8-iteration instantiation for T <= 128 makes hipcc hoist every source-row load: 418 registers unbounded, spills when bounded)
     auto kern = T <= 192 ? gn_relu_bwd_kernel<12> : gn_relu_bwd_kernel<GN_MAXIT>;
     const int lds = scatter ? scatter->P * 64 * 4 : 0;                    // the utterance's source rows of the block's 64 channels

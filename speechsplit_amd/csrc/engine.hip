@@ -22,27 +22,15 @@
 using namespace ss;
 
 namespace ss {
-extern int g_small_lds, g_small_prio, g_gemm_tr, g_deterministic, g_gn_part;
-extern int g_img_cfg;
-extern int g_lstm_nw, g_lstm_g, g_lstm_mode, g_gemm_bk, g_gemm_want, g_gemm_diag, g_seq_prio, g_gemm_mode, g_seq_spin_log2, g_seq_tag, g_seq_wlead, g_seq_var, g_gemm_ws;
+extern int g_small_lds, g_gemm_tr, g_deterministic;
+extern int g_lstm_nw, g_lstm_g, g_lstm_mode, g_gemm_want, g_gemm_diag, g_seq_prio, g_gemm_mode, g_seq_spin_log2, g_seq_tag, g_seq_var, g_gemm_ws;
 int g_fwd_f16x2 = 1;   // 1: forward contractions (operands bounded by construction: mel, one-hot, GroupNorm/ReLU outputs, |h| < 1, weights)
                        //    use the fp16 x 2 split (3 MFMAs) instead of bf16 x 3 (6 MFMAs); gradients keep bf16 x 3 (their range is not bounded)
 int g_bwd_f16x2 = 1;   // 1: the decoder's and the conv trunk's gradient GEMMs also use fp16 x 2: the gradient operand is scaled by the power
                        //    of two its producer kernel measured (max |value| of the slab), the activation / weight operand by the fixed one
 int g_overlap = 1;     // 1: weight-gradient GEMMs on the side stream
 int g_dx_batched = 2;  // input-gradient GEMMs per utterance without halo rows; 2: with 128 x 128 tiles from 512 workgroups on
-int g_conv_small_old = 1;  // see try_img_gemm
-int g_conv_want = 256;    // experiment: workgroup target of the conv GEMMs' tile choice (0: library default)
 int g_defer_dw = 1;    // 1: the decoder's weight-gradient GEMMs start after its last input gradient (see lstm_bwd)
-int g_side_prio = 0;   // 1: create the side stream with the lowest priority (read at ss_bind).  Measured: 2.3x SLOWER
-                       //    (35 ms vs 14.8 ms per step): the low-priority queue starves behind 768 tiny step launches.
-int g_branch_low = 0;      // experiment: the probed branch streams are created with the lowest priority (read at ss_bind); measured 5.78 vs 5.80 ms, off
-int g_trunk_indep = 1;     // Encoder_7 forward: content and pitch conv stacks run as two INDEPENDENT chains (they share only the resampling plans)
-int g_img = 1;             // 1: contractions whose two operands exist as images run on the image GEMM (gemm_img.hip); 0: round 2's kernels only
-int g_img_mask = (1 << SS_PROF_DEC_PROJ) | (1 << SS_PROF_CONV_FWD) | (1 << SS_PROF_CONV_DX);     // ... per profile class (bit SS_PROF_*): which classes may take the image GEMM (A/B runs)
-int g_img_batch = 1;       // image GEMM: the decoder's weight gradients of both directions in one launch per matrix
-int g_img_dw_cfg = -1;     // experiment: tile configuration of the split-K (weight-gradient) image GEMMs (-1: the rule in try_img_gemm)
-int g_img_dw_wgs = 256;    // ... and the number of workgroups their split aims at
 int g_dp_emulate = 0;      // with dp_model = N: the stand-in collectives multiply their range by N (the sum of N identical ranks), see dp_scale_kernel
 int g_dp_model = 0;        // > 1: MODEL a data-parallel run of that many ranks on one GPU: every collective is replaced by a stand-in kernel of
                            // the modelled duration (tools/dp_timeline.sh); no communicator needed
@@ -51,26 +39,11 @@ int g_cur_klass = -1;      // profile class of the contraction being launched (s
 int g_bf16_img = 1;        // SS_PRECISION_BF16: the 16-bit data path (round 4) -- operand images are plain bf16 tensors written by their producers (weights,
                            // hidden states, resampled activations, pre-activation / conv-output gradients) and the contractions over them run on the
                            // single-piece form of the image GEMM; 0: round 3's bf16 mode (fp32 slabs, operands rounded inside the GEMM)
-int g_seq_skip32 = 1;      // ... and a decoder layer whose gradient consumers all read the bf16 tensor does not get the fp32 copy of its pre-activation gradients
-int g_seq_hi = 1;          // ... and the persistent recurrences multiply the high fp16 pieces only (one MFMA per product, half the forward's payload)
-int g_bf16_img_mask = ~0;  // ... per profile class (bit SS_PROF_*), for A/B runs
-int g_wgrad_fused = 1;     // the encoder BLSTMs' weight and bias gradients (H <= 32) in one fused fp32 launch (lstm_wgrad.hip) instead of 12-14 tiny GEMMs + column sums
-int g_trunk_bwd_par = 1;   // Encoder_7 backward: the pitch conv stack's blocks stay on the stream of lstm_2's backward (second branch stream), beside the content
-                           // stack on the main stream, through all three layers (the two stacks are independent chains; round 3 did this for layer 0 only).
-                           // 64 x 128 unchanged (that phase is throughput-bound), 32 x 128 bf16 3.16 -> 3.02 ms, 16 x 128 fp32 3.44 -> 3.29.
-                           // (Measured and rejected beside it: each block's weight-gradient GEMM on the side stream beside its input-gradient GEMM --
-                           // +8 % at B <= 32: the two cross-stream event hops per block cost more than the overlap gains.)
-int g_pack_one = 1;        // every conv block's per-step weight re-layout in one launch at the start of the forward (conv_pack_many)
-int g_presplit = 7;        // weights (and, bit 1, the decoder's hidden states) reach the fp16 x 2 GEMMs as pre-split images: bit 0 weights, bit 1 the decoder's hidden states, bit 2 the trunk's resampled activations
+                           // (a decoder layer whose gradient consumers all read the bf16 tensor does not get the fp32 copy of its pre-activation gradients,
+                           // and the persistent recurrences multiply the high fp16 pieces only: one MFMA per product, half the forward's payload)
 int g_compact0 = 1;        // decoder layer 0: input projections, input gradient and W_ih gradient once per block of repeated input frames
-int g_batch_dirs = 1;      // BLSTM weight gradients: both directions of a layer in one launch per matrix (batch = 2) + one bias kernel:
-                           // 1 = the encoder BLSTMs (36 -> 14 launches), 2 = the decoder too (measured: step +0.18 ms), 0 = never
-int g_prewarm = 2;         // streaming pre-read of a decoder layer's operand slabs on a side stream beside its persistent recurrence: bit 1 forward
-                           // (step -0.08 ms), bit 0 backward (no gain in the step, off; neither one recurrence ahead: +0.08 ms)
 int g_op_time_major = 0;   // experiment: ss_op_lstm_fwd / _bwd take time-major slabs [T+4, B, C] (persistent kernels only)
 int g_persist = 1;     // 1: decoder recurrences run as ONE persistent launch per layer (lstm_seq.hip) when the batch fits
-int g_split = 0;       // 1: decoder recurrences run as two batch-half chains on two streams (GEMMs of one half fill the
-                       //    machine while the other half sits in its latency-bound time loop)
 // (hipGraph capture + replay of the fused step: built and measured in rounds 1-3 -- no gain while the step is GPU-bound, and a crash inside
 // the ROCm 7.2 runtime's hipGraphLaunch with more parallel branches -- and deleted in round 4; the step is enqueued eagerly.)
 int g_own_streams = 0; // 1: every C-ABI call runs on the ENGINE's own main stream (created back to back with its three branch streams at
@@ -79,7 +52,6 @@ int g_own_streams = 0; // 1: every C-ABI call runs on the ENGINE's own main stre
                        //    least-loaded of its 4 hardware queues, and which engine stream ends up sharing a queue with the caller's still
                        //    moves the step by 5 % either way (profiles/r02/stream_order_effect.txt: 6.70 - 7.13 ms owned, 6.69 - 7.38 not).
                        //    Off by default until the engine can measure and pick its queue placement.
-int g_flat_rows = 1;   // 1: batched-per-utterance GEMMs run flat over the slab rows when T % 128 != 0 (flatten_rows)
 int g_prio_order = 1;  // 1: within every phase the critical-path launches are ENQUEUED first and the work that only has to be done by the end of
                        //    the step (decoder / encoder-BLSTM weight gradients, Encoder_t) last.  HIP multiplexes streams onto 4 in-order hardware
                        //    queues; when two engine streams share one (other streams in the process, e.g. RCCL's, shift the assignment), enqueue
@@ -87,15 +59,10 @@ int g_prio_order = 1;  // 1: within every phase the critical-path launches are E
 int g_probe_queues = 1; // 1: ss_bind measures which candidate streams share a hardware queue and picks branch streams that do not (pick_streams)
 static unsigned* g_img_wq = nullptr;      // queue words (+ placement log) of the test hook's work-queue launches
 constexpr long IMG_WQ_BYTES = 16 + 16 * 1024;
-int g_part_splitk = 1;  // split-K weight gradients of the in-loop-split kernel through partial slabs + an ordered reduce instead of fp32 atomics
-int g_unpack_later = 1; // one-GPU step: the conv weight gradients' re-layouts in one launch at the end of the backward
 int g_gn_gather = 1;    // training forward of the independent trunk chains: GroupNorm + ReLU + resampling gather in one kernel (gn_relu_gather)
-int g_enc_t_first = 1;      // prio schedule, third branch stream: Encoder_t's backward chain (waits for dec_in_grad only) in FRONT of the encoder BLSTMs' weight
-                        // gradients, which then go out in ONE fused launch with Encoder_t's.  Generator_6 32 x 192 bf16 2.26 -> 2.23 ms, 16 x 128 3.20 -> 3.18,
-                        // headline unchanged
 int g_conv_dw_off = 1;      // Generator_6 (one trunk chain, the second branch stream idle behind lstm's backward): the conv blocks' weight-gradient GEMMs leave
                         // the dependent chain gn backward -> input gradient -> next block for that stream; every block then keeps its own conv-output
-                        // gradient slab (d_act_l).  With enc_t_first: 2.26 -> 2.17 ms (bf16), 2.50 -> 2.47 (fp32).  Generator_3 has no idle stream there
+                        // gradient slab (d_act_l).  With Encoder_t's backward in front of the BLSTMs' weight gradients (backward_encoder): 2.26 -> 2.17 ms (bf16), 2.50 -> 2.47 (fp32).  Generator_3 has no idle stream there
                         // (tools/real_timeline.py: its four streams end within ~100 us of each other)
 int g_dec_tail_split = 9;   // one-GPU step: on the side stream alone the decoder's twelve weight-gradient GEMMs end ~450 us after every other stream
                         // (tools/real_timeline.py).  Layer 0's and the head's leave it for 1: the pitch chain's stream (behind the chain), 2: the third
@@ -121,10 +88,6 @@ int g_xcd_dw = 0;       // decoder W_ih gradients beside the backward recurrence
                         // pass and the split-K reduce land beside the input-gradient GEMM on the critical path, and at B <= 32 the encoder
                         // backward that loses the work is chain-bound, not throughput-bound (profiles/r03/xcd_overlap.txt)
 int g_img_xcc = 0;      // ss_op_gemm_img (test hook): run the image GEMM in its work-queue form on the XCDs of this mask
-int g_adam_early = 1;   // one-GPU fused steps: the decoder + head range of Adam beside the encoder backward (ss_tune("adam_early"))
-int g_exp = 0;         // bits that switch individual schedule choices back for same-box A/B runs (bench.py --tune exp=N); 0 in production
-int g_conv_par = 1;    // 1: the two conv streams of an Encoder_7 layer (and the layer's resampling plan) run on two engine streams in the forward
-int g_early_join = 1;  // 1: join events of branch streams are recorded right behind the last kernel the consumer needs (lstm_bwd's dx_ready)
 }
 
 namespace {
@@ -183,9 +146,10 @@ struct LstmBlk {
     std::vector<float*> wcat_img;          // per layer: pre-split image of wcat (decoder-size blocks only)
     std::vector<float*> wcat;              // per layer: [W_ih forward ; W_ih reverse] stacked, [8H][In] (input-gradient GEMM over both directions)
     std::vector<float*> wfrag;             // per layer: fragment-major W_hh (forward) / W_hh^T (backward), 2*4H*H floats
-    float* hf[2] = {nullptr, nullptr};     // per batch-half chain: ping-pong fragment-major h(t),  2 x [2][ceil16(B)][H]
-    float* gf[2] = {nullptr, nullptr};     // per chain: ping-pong fragment-major da(t), 2 x [2][ceil16(B)][4H]
-    float* dc[2] = {nullptr, nullptr};     // per chain: [2][B][H]
+    // one launch per time step (persist = 0, or a batch the persistent kernels do not take):
+    float* hf = nullptr;                   // ping-pong fragment-major h(t),  2 x [2][ceil16(B)][H]
+    float* gf = nullptr;                   // ping-pong fragment-major da(t), 2 x [2][ceil16(B)][4H]
+    float* dc = nullptr;                   // [2][B][H]
     unsigned* sync = nullptr;              // persistent kernels: group counters + abort word (one-off ops path)
     // persistent schedule: per-layer start state, contiguous so ONE memset per pass readies every layer's launch.
     //   zf = [L][LSTM_SEQ_SYNC_WORDS] ++ [L][hf]      (forward)        zb = [L][LSTM_SEQ_SYNC_WORDS] ++ [L][exchange tiles]   (backward)
@@ -331,7 +295,7 @@ struct ss_engine {
     std::string stream_report;            // what pick_streams found (ss_stream_report)
     hipStream_t main_s = nullptr;         // the stream the step's dependency chain runs on (see g_own_streams)
     hipStream_t side = nullptr;
-    hipStream_t side2 = nullptr;          // independent branches (per-step weight re-layouts, Encoder_t, second encoder BLSTM); second batch-half chain
+    hipStream_t side2 = nullptr;          // independent branches (per-step weight re-layouts, Encoder_t, second encoder BLSTM)
     hipStream_t side3 = nullptr;          // third independent branch of the encoder backward (Encoder_t)
     hipEvent_t ev_io[2] = {};             // caller stream <-> engine main stream ordering (own_streams)
     hipEvent_t ev_join[4] = {};           // events recorded early: [0] lstm_2 branch's input gradient, [1] decoder chain done, [2] dec_in_grad done, [3] lstm_1 chain done
@@ -509,11 +473,9 @@ long ss_engine::carve(int B, int T, bool assign) {
             const long B16 = ((B + 15) / 16) * 16;
             lb.wfrag.assign(lb.L, nullptr);
             for (int l = 0; l < lb.L; ++l) lb.wfrag[l] = (float*)take(2L * lb.H * 4 * lb.H * 4);
-            for (int c = 0; c < 2; ++c) {
-                lb.hf[c] = (float*)take(2L * 2 * B16 * lb.H * 4);
-                lb.gf[c] = (float*)take(2L * 2 * B16 * 4 * lb.H * 4);
-                lb.dc[c] = (float*)take(2L * B * lb.H * 4);
-            }
+            lb.hf = (float*)take(2L * 2 * B16 * lb.H * 4);
+            lb.gf = (float*)take(2L * 2 * B16 * 4 * lb.H * 4);
+            lb.dc = (float*)take(2L * B * lb.H * 4);
             lb.sync = (unsigned*)take(LSTM_SEQ_SYNC_WORDS * 4);
             lb.hf_bytes = lstm_seq_xbytes(B, lb.H, false);       // exchange buffers of the persistent kernels
             lb.gf_bytes = lstm_seq_xbytes(B, lb.H, true);
@@ -664,29 +626,32 @@ int geometry(ss_engine* e, int B, int T, hipStream_t s, bool eval = false) {
     return 0;
 }
 
-int g_dw_wgs = 384;        // workgroups a split-K weight-gradient launch aims at (round 2: 384 = 1.5 per CU measured best in the step, 5.38 vs 5.48 ms at 512; 256: 5.5, 768+: 5.7)
+constexpr int DW_WGS = 384;       // workgroups a split-K weight-gradient launch aims at (round 2: 384 = 1.5 per CU measured best in the step, 5.38 vs 5.48 ms at 512; 256: 5.5, 768+: 5.7)
 int pick_ksplit(int M, int N, long K) {
     const long tiles = (long)cdiv(M, 128) * cdiv(N, 128);
-    long ks = g_dw_wgs / (tiles > 0 ? tiles : 1);
+    long ks = DW_WGS / (tiles > 0 ? tiles : 1);
     if (ks > K / 256) ks = K / 256;
     if (ks > 32) ks = 32;
     if (ks < 1) ks = 1;
     return (int)ks;
 }
 
+// fp32 mode: the profile classes (bit SS_PROF_*) whose contractions take the image GEMM -- the decoder's input projections, the conv trunk's
+// forward and input-gradient GEMMs.  The weight-gradient classes stay on round 2's kernel (split-K through partial slabs, gemm_on).
+constexpr int IMG_CLASSES = (1 << SS_PROF_DEC_PROJ) | (1 << SS_PROF_CONV_FWD) | (1 << SS_PROF_CONV_DX);
+constexpr int IMG_DW_WGS = 256;       // workgroups the split of a split-K (weight-gradient) image GEMM aims at
+
 // Image GEMM (gemm_img.hip) for a contraction whose two operands exist as images.  Returns 1 when it was launched, 0 when the
 // contraction has to take round 2's kernels (no images, shape outside what the image kernel supports), < 0 on error.
 int try_img_gemm(ss_engine* e, const GemmDesc& d, hipStream_t st) {
-    if (!g_img || !d.a_pre || !d.b_pre) return 0;
+    if (!d.a_pre || !d.b_pre) return 0;
     const bool b16 = e->img16();                     // the images are plain bf16 tensors: single-piece form, every class that has both
-    if (b16) {
-        if (g_cur_klass >= 0 && !((g_bf16_img_mask >> g_cur_klass) & 1)) return 0;
-    } else {
+    if (!b16) {
         if (!(d.flags & GEMM_F16X2) || (d.flags & GEMM_BF16)) return 0;
-        if (g_cur_klass >= 0 && !((g_img_mask >> g_cur_klass) & 1) && !d.queue) return 0;
+        if (g_cur_klass >= 0 && !((IMG_CLASSES >> g_cur_klass) & 1) && !d.queue) return 0;
         // conv trunk at B x T <= 2048 rows: the image kernel's smallest tile (128 x 128) gives a 512-channel layer 64 workgroups; round 2's kernel
         // on 64 x 64 tiles fills the chip (16 x 128: 3.22 -> 3.17 ms, 12 x 128: 3.08 -> 3.04; equal at 8 x 128 and from 32 x 128 on)
-        if ((g_cur_klass == SS_PROF_CONV_FWD || g_cur_klass == SS_PROF_CONV_DX) && g_conv_small_old && (long)e->curB * e->curT <= 2048) return 0;
+        if ((g_cur_klass == SS_PROF_CONV_FWD || g_cur_klass == SS_PROF_CONV_DX) && (long)e->curB * e->curT <= 2048) return 0;
     }
     ImgGemmDesc g{};
     g.bf16 = b16 ? 1 : 0;
@@ -739,9 +704,8 @@ int try_img_gemm(ss_engine* e, const GemmDesc& d, hipStream_t st) {
         // weight-gradient GEMMs on the dependent chain queue for CUs behind the decoder's on the side streams (real_timeline: 147 us for a 32-us
         // launch).  32 x 128: 2.96 -> 2.91 ms, 64 x 128: 3.75 -> 3.69; the work-queue form keeps one workgroup per CU by design
         if (b16 && !d.queue) g.cfg = 1;
-        if (g_img_dw_cfg >= 0) g.cfg = g_img_dw_cfg;
-        const long t = (g.cfg == 2 || g.cfg == 3) ? wgs(256, 128) : (g.cfg == 0 ? wgs(256, 256) : wgs(128, 128));
-        long ks = ((d.queue ? 2 * g_img_dw_wgs : g_img_dw_wgs) + t / 2) / (t > 0 ? t : 1);       // work-queue form: twice the tiles (finer hand-over when the recurrence beside it ends)
+        const long t = g.cfg == 2 ? wgs(256, 128) : wgs(128, 128);
+        long ks = ((d.queue ? 2 * IMG_DW_WGS : IMG_DW_WGS) + t / 2) / (t > 0 ? t : 1);       // work-queue form: twice the tiles (finer hand-over when the recurrence beside it ends)
         if (ks > g.K / 512) ks = g.K / 512;
         if (ks > 16) ks = 16;
         if (ks < 1) ks = 1;
@@ -799,7 +763,7 @@ int wgrad_flush(ss_engine* e, hipStream_t st) {
     if (!e->part || !e->colsum_ctr || w.tiles_total > ss_engine::COLSUM_CTRS || e->part_off + need > e->part_cap) {
         w.n = 0;
         w.tiles_total = 0;
-        return fail("wgrad_flush: no scratch left for the fused encoder-BLSTM weight gradients (ss_tune(\"wgrad_fused\", 0) selects the GEMM path)");
+        return fail("wgrad_flush: no scratch left for the fused encoder-BLSTM weight gradients");
     }
     w.part = e->part + e->part_off;
     e->part_off += (need + 63) & ~63L;
@@ -826,11 +790,11 @@ int gemm_on(ss_engine* e, GemmDesc& d, hipStream_t st) {
             const long R8 = (long)e->curB * (e->curT + 2 * HALO) * 8L * e->ld.H;
             for (int l = 0; l < e->ld.L && l < 3; ++l)
                 if (((e->dg32_skipped >> l) & 1) && ((d.A.p >= e->ld.gates[l] && d.A.p < e->ld.gates[l] + R8) || (d.B.p >= e->ld.gates[l] && d.B.p < e->ld.gates[l] + R8)))
-                    return fail("internal: a contraction fell back to the fp32 gradient slab of a decoder layer that was only written as bf16 (ss_tune(\"seq_skip32\", 0))");
+                    return fail("internal: a contraction fell back to the fp32 gradient slab of a decoder layer that was only written as bf16");
         }
-        // split-K weight gradients: partial slabs + ordered reduce instead of fp32 atomics (ss_tune("part_splitk")), scratch from the step's bump allocator
+        // split-K weight gradients: partial slabs + ordered reduce instead of fp32 atomics, scratch from the step's bump allocator
         // (not for the encoder BLSTMs' tiny matrices: a one-block reduce over 32 slices is 17 us of latency, their atomics are nothing)
-        if (g_part_splitk && d.ksplit > 1 && (d.flags & GEMM_TA) && (d.flags & GEMM_TB) && (d.flags & GEMM_ACCUM) && !d.row_period && !d.bias && d.N % 4 == 0 &&
+        if (d.ksplit > 1 && (d.flags & GEMM_TA) && (d.flags & GEMM_TB) && (d.flags & GEMM_ACCUM) && !d.row_period && !d.bias && d.N % 4 == 0 &&
             ((long)d.M * d.N >= 65536 || g_deterministic) && e->part) {        // deterministic mode: every split reduction through ordered slabs (small ones too)
             int ks = d.ksplit;
             const long need = (long)ks * d.M * d.N * (d.batch < 1 ? 1 : d.batch);
@@ -971,10 +935,8 @@ int pick_streams(ss_engine* e, hipStream_t main) {
     hipStream_t(&pool)[POOL] = gd.pool;
     hipEvent_t(&ev)[3] = gd.ev;
     for (auto& x : ev) HIPCHK(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-    int least = 0, greatest = 0;
-    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
     for (auto& st : pool) {
-        HIPCHK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, g_branch_low ? least : 0));
+        HIPCHK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, 0));      // (created with the lowest priority instead: measured 5.78 vs 5.80 ms, not done)
         hipLaunchKernelGGL(queue_probe_nop_kernel, dim3(1), dim3(1), 0, st);      // first use of a stream sets its queue up: not inside a measurement
     }
     hipLaunchKernelGGL(queue_probe_nop_kernel, dim3(1), dim3(1), 0, main);
@@ -1065,7 +1027,7 @@ double gemm_flops_of(const ss_engine* e, const GemmDesc& d) {
 // Worth it whenever T is not a multiple of the 128-row tile.  The A operand's rows are addressed exactly as before (row m of the
 // flat matrix is slab row m + HALO, taps reach into the neighbouring rows; rows computed for halo positions are never stored).
 void flatten_rows(GemmDesc& d, int B, int T) {
-    if (T % 128 == 0 || d.batch != B || B < 2 || g_flat_rows == 0) return;
+    if (T % 128 == 0 || d.batch != B || B < 2) return;
     const int TP = T + 2 * HALO;
     d.M = B * TP - 2 * HALO;
     d.batch = 1;
@@ -1083,6 +1045,8 @@ int conv_pack_all(ss_engine* e, ConvBlk& cb, hipStream_t s) {
     HIPCHK(conv_pack(e->P + cb.w, cb.Co, cb.Ci, cb.Cp, cb.wf, cb.wb, img ? cb.wf_img : nullptr, img ? cb.wb_img : nullptr, s, e->img16()));
     return 0;
 }
+
+constexpr int CONV_WANT = 256;    // workgroup target of the conv GEMMs' tile choice (GemmDesc::want)
 
 int zero_conv_grads(ss_engine* e, hipStream_t s) {
     HIPCHK(hipMemsetAsync(e->gp_all, 0, e->gp_bytes, s));
@@ -1112,7 +1076,7 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
     d.a_pre = x.img;
     d.a_pre_scale = x.scale;
     d.B = {cb.wf, 5L * cb.Cp, 0, 0, 0};
-    d.b_pre = ((g_presplit & 1) && cb.img_ok()) ? cb.wf_img : nullptr;
+    d.b_pre = cb.img_ok() ? cb.wf_img : nullptr;
     d.C = cb.cout + HALO * cb.Co;
     d.ldc = cb.Co;
     d.cstride = TP * cb.Co;
@@ -1122,7 +1086,7 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
     d.K = 5 * cb.Cp;
     d.batch = B;
     d.ksplit = 1;
-    d.want = g_conv_want;
+    d.want = CONV_WANT;
     flatten_rows(d, B, T);
     PGEMM_FWD_ON(SS_PROF_CONV_FWD, d, s);
     if (gather) {
@@ -1163,7 +1127,7 @@ int conv_block_bwd(ss_engine* e, ConvBlk& cb, Slab dy, Slab x, Slab dx, hipStrea
     const bool i16 = e->img16();
     // 16-bit data path: the GroupNorm backward writes the gradient's bf16 image itself (the image's halo rows are zero since the geometry
     // was planned and nobody writes them); fp32 mode: a split_image pass with the scale gn_relu_bwd has just measured
-    float* im16 = (i16 && g_img && cb.Co % 8 == 0 && dy.ld % 8 == 0) ? grad_img_of(e, dy.p, R) : nullptr;
+    float* im16 = (i16 && cb.Co % 8 == 0 && dy.ld % 8 == 0) ? grad_img_of(e, dy.p, R) : nullptr;
     { const int pa_ = prof_begin(e, SS_PROF_GN, s, 0.0);
     HIPCHK(gn_relu_bwd(cb.cout, cb.Co, TP * cb.Co, dy.p, dy.ld, TP * dy.ld, e->P + cb.ga, e->P + cb.be, cb.stats,
                        e->G + cb.ga, e->G + cb.be, e->G + cb.b, am, cb.part, B, T, cb.Co, s, scatter, src, src_ld, TP * src_ld, im16));
@@ -1171,7 +1135,7 @@ int conv_block_bwd(ss_engine* e, ConvBlk& cb, Slab dy, Slab x, Slab dx, hipStrea
     // the conv-output gradient as an image for the image GEMM (scale: the power of two for the maximum gn_relu_bwd has just measured)
     const float* dimg = im16;
     const float* dsc = nullptr;
-    if (!i16 && g_img && (g_img_mask & ((1 << SS_PROF_CONV_DW) | (1 << SS_PROF_CONV_DX))) && am && e->precision == SS_PRECISION_F32 && cb.Co % 8 == 0 && dy.ld % 8 == 0) {
+    if (!i16 && am && e->precision == SS_PRECISION_F32 && cb.Co % 8 == 0 && dy.ld % 8 == 0) {
         float* im = grad_img_of(e, dy.p, R);
         if (im) {
             HIPCHK(split_image(dy.p, dy.ld, R, cb.Co, am, 0.f, im, dy.ld, e->gscale + cb.amax_i, s));
@@ -1198,15 +1162,9 @@ int conv_block_bwd(ss_engine* e, ConvBlk& cb, Slab dy, Slab x, Slab dx, hipStrea
     d.flags = GEMM_TA | GEMM_TB | GEMM_ACCUM | (am ? GEMM_F16X2 : 0);
     d.amax_a = am;                                  // gradient operand: measured scale; the block input is O(1)
     d.ksplit = pick_ksplit(d.M, d.N, d.K);
-#ifdef SS_DIAG
-    if (g_exp & 8) goto conv_dw_done;            // what-if timing run (WRONG gradients): without the conv weight-gradient GEMMs
-#endif
     if (dws && dws != s) CHK(fork_join(e, s, dws));
     else dws = s;
     PGEMM_ON(SS_PROF_CONV_DW, d, dws);
-#ifdef SS_DIAG
-conv_dw_done:
-#endif
     // packed [Co][5][Cp] -> the parameter's [Co][Ci][5]: nobody reads it before the optimiser (or, data parallel, the layer's bucket), so the
     // one-GPU step collects the blocks and unpacks them all in one launch at the end of the backward (backward_encoder) instead of seven
     // small launches on the trunk's dependent chain
@@ -1220,7 +1178,7 @@ conv_dw_done:
             g.a_pre_scale = dsc;
         }
         g.B = {cb.wb, 5L * cb.Co, 0, 0, 0};
-        g.b_pre = ((g_presplit & 1) && cb.img_ok()) ? cb.wb_img : nullptr;
+        g.b_pre = cb.img_ok() ? cb.wb_img : nullptr;
         g.C = dx.p + HALO * dx.ld;
         g.ldc = dx.ld;
         g.cstride = TP * dx.ld;
@@ -1231,7 +1189,7 @@ conv_dw_done:
         g.ksplit = 1;
         g.flags = am ? GEMM_F16X2 : 0;
         g.amax_a = am;
-        g.want = g_conv_want;
+        g.want = CONV_WANT;
         flatten_rows(g, B, T);
         PGEMM_ON(SS_PROF_CONV_DX, g, s);
     }
@@ -1254,29 +1212,13 @@ conv_dw_done:
         g.ksplit = 1;
         g.flags = am ? GEMM_F16X2 : 0;
         g.amax_a = am;
-        g.want = g_conv_want;
+        g.want = CONV_WANT;
         PGEMM_ON(SS_PROF_CONV_DX, g, s);
     }
     return 0;
 }
 
 // ---- BLSTM block -------------------------------------------------------------------------------------------
-struct Chain {
-    int b0, nb;
-    hipStream_t st;
-};
-
-int make_chains(ss_engine* e, int B, hipStream_t s, Chain ch[2]) {
-    if (g_split && e->side2 && B >= 32) {
-        const int bA = ((B / 2 + 15) / 16) * 16;
-        ch[0] = {0, bA, s};
-        ch[1] = {bA, B - bA, e->side2};
-        return 2;
-    }
-    ch[0] = {0, B, s};
-    return 1;
-}
-
 // Per-step re-layouts of one BLSTM block's weights: b_ih + b_hh per (layer, direction) and, for the decoder-size blocks,
 // the fragment-major W_hh of the forward recurrence.  Independent of the activations, so the schedule runs it on a branch.
 int lstm_prep(ss_engine* e, LstmBlk& lb, PrepTable& tb, hipStream_t s) {
@@ -1297,66 +1239,55 @@ int lstm_prep(ss_engine* e, LstmBlk& lb, PrepTable& tb, hipStream_t s) {
     return 0;
 }
 
-// Decoder-size BLSTM (one launch per time step).  The batch is cut in two halves that run as independent chains on
-// two streams through ALL layers: every operator is per-utterance, so nothing couples them until the head.
+// Decoder-size BLSTM: one persistent launch per layer, or one launch per time step (persist = 0 / a batch the persistent kernels do not take).
 int lstm_big_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
     const int B = e->curB, T = e->curT, H = lb.H;
     const long TP = T + 2 * HALO;
-    Chain ch[2];
     const bool persist = g_persist && lstm_seq_supported(B, H);
-    const int nch = persist ? 1 : make_chains(e, B, s, ch);
-    if (persist) ch[0] = {0, B, s};
-    if (nch == 2) CHK(fork_join(e, s, ch[1].st));
     // only fp16 x 2 GEMMs read the hidden states' pre-split images, and only the persistent recurrences write them
-    lb.out_img_valid = persist && (g_presplit & 2) && ((e->precision == SS_PRECISION_F32 && g_fwd_f16x2) || e->img16()) && !lb.out_img.empty() && lb.out_img[0];
+    lb.out_img_valid = persist && ((e->precision == SS_PRECISION_F32 && g_fwd_f16x2) || e->img16()) && !lb.out_img.empty() && lb.out_img[0];
+    const long half = 2L * (((B + 15) / 16) * 16) * H;       // one of the two ping-pong h(t) tiles of the per-step schedule
     for (int l = 0; l < lb.L; ++l) {
         const int In = lb.in_of(l);
         Slab xi = l == 0 ? x : Slab{lb.out[l - 1], 2L * H};
         const bool compact = l == 0 && lb.xf && persist && x.p == lb.xc;       // the input repeats in blocks of xf frames: one projection row per block
-        for (int c = 0; c < nch; ++c) {
-            const long r0 = (long)ch[c].b0 * TP;
-            if (compact) {
-                GemmDesc d{};
-                d.A = {lb.xc, In, 0, 0, 0};
-                d.B = {lb.wcat[l], In, 0, 0, 0};
-                d.b_pre = (g_presplit & 1) ? lb.wimg(l) : nullptr;
-                d.C = lb.xp0;
-                d.ldc = 8L * H;
-                d.bias = lb.bsum + (long)l * 8 * H;
-                d.M = B * (T / lb.xf);
-                d.N = 8 * H;
-                d.K = In;
-                d.batch = 1;
-                d.ksplit = 1;
-                PGEMM_FWD_ON(SS_PROF_DEC_PROJ0, d, ch[c].st);
-            } else {   // both directions in one GEMM against the stacked W_ih / summed biases of lstm_prep (N = 8H)
-                GemmDesc d{};
-                d.A = {xi.p + (r0 + HALO) * xi.ld, xi.ld, TP * xi.ld, 0, 0};
-                if (l > 0 && lb.out_img_valid) d.a_pre = e->ioff(lb.out_img[l - 1], (r0 + HALO) * xi.ld);       // written by the layer below's recurrence
-                d.B = {lb.wcat[l], In, 0, 0, 0};
-                d.b_pre = (g_presplit & 1) ? lb.wimg(l) : nullptr;
-                d.C = lb.gates[l] + (r0 + HALO) * 8L * H;
-                d.ldc = 8L * H;
-                d.cstride = TP * 8L * H;
-                d.bias = lb.bsum + (long)l * 8 * H;
-                d.M = T;
-                d.N = 8 * H;
-                d.K = In;
-                d.batch = ch[c].nb;
-                d.ksplit = 1;
-                if (nch == 1) flatten_rows(d, B, T);
-                PGEMM_FWD_ON(l > 0 ? SS_PROF_DEC_PROJ : SS_PROF_DEC_PROJ0, d, ch[c].st);
-            }
-            if (!persist) {
-                const long half = 2L * (((ch[c].nb + 15) / 16) * 16) * H;
-                HIPCHK(hipMemsetAsync(lb.hf[c], 0, 2 * half * 4, ch[c].st));
-            }
+        if (compact) {
+            GemmDesc d{};
+            d.A = {lb.xc, In, 0, 0, 0};
+            d.B = {lb.wcat[l], In, 0, 0, 0};
+            d.b_pre = lb.wimg(l);
+            d.C = lb.xp0;
+            d.ldc = 8L * H;
+            d.bias = lb.bsum + (long)l * 8 * H;
+            d.M = B * (T / lb.xf);
+            d.N = 8 * H;
+            d.K = In;
+            d.batch = 1;
+            d.ksplit = 1;
+            PGEMM_FWD_ON(SS_PROF_DEC_PROJ0, d, s);
+        } else {   // both directions in one GEMM against the stacked W_ih / summed biases of lstm_prep (N = 8H)
+            GemmDesc d{};
+            d.A = {xi.p + HALO * xi.ld, xi.ld, TP * xi.ld, 0, 0};
+            if (l > 0 && lb.out_img_valid) d.a_pre = e->ioff(lb.out_img[l - 1], HALO * xi.ld);       // written by the layer below's recurrence
+            d.B = {lb.wcat[l], In, 0, 0, 0};
+            d.b_pre = lb.wimg(l);
+            d.C = lb.gates[l] + HALO * 8L * H;
+            d.ldc = 8L * H;
+            d.cstride = TP * 8L * H;
+            d.bias = lb.bsum + (long)l * 8 * H;
+            d.M = T;
+            d.N = 8 * H;
+            d.K = In;
+            d.batch = B;
+            d.ksplit = 1;
+            flatten_rows(d, B, T);
+            PGEMM_FWD_ON(l > 0 ? SS_PROF_DEC_PROJ : SS_PROF_DEC_PROJ0, d, s);
         }
         if (persist) {   // start state zeroed by lstm_prep
             // the input projections the GEMM has just written are read once more, in whole lines, beside the recurrence (lstm_seq.hip)
             // (worth it from ~48 utterances on: 64 x 128 -0.08 ms; at 32 and 16 the fork / join around the recurrence costs more than warm operands
             // gain: 32 x 128 bf16 3.00 vs 2.97 ms without, 16 x 128 3.28 vs 3.26)
-            const bool pw = (g_prewarm & 2) && e->side3 && g_overlap && !compact && B > 32;
+            const bool pw = e->side3 && g_overlap && !compact && B > 32;
             if (pw) {
                 CHK(fork_join(e, s, e->side3));
                 HIPCHK(slab_prewarm(lb.gates[l], 8 * H, nullptr, nullptr, 2 * H, e->amax, B, T, false, e->side3));
@@ -1364,21 +1295,15 @@ int lstm_big_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
             const int pi = prof_begin(e, SS_PROF_REC_FWD, s, 2.0 * 2 * B * T * 4.0 * H * H);
             HIPCHK(lstm_seq_fwd(lb.gates[l], e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.hf_l(l), lb.out[l], lb.csave[l],
                                 lb.sync_f(l), e->sticky, compact ? lb.xp0 : nullptr, compact ? lb.xf : 0, lb.out_img_valid ? lb.out_img[l] : nullptr, B, T, H,
-                                false, false, s, (e->img16() ? 1 : 0) | (e->img16() && g_seq_hi ? 2 : 0)));
+                                false, false, s, e->img16() ? 1 | 2 : 0));      // 16-bit data path: bf16 images (1), products of the high fp16 pieces only (2)
             prof_end(e, pi, s);
             if (pw) CHK(fork_join(e, e->side3, s));
             continue;
         }
+        HIPCHK(hipMemsetAsync(lb.hf, 0, 2 * half * 4, s));
         for (int st = 0; st < T; ++st)
-            for (int c = 0; c < nch; ++c) {
-                const long r0 = (long)ch[c].b0 * TP;
-                const long half = 2L * (((ch[c].nb + 15) / 16) * 16) * H;
-                HIPCHK(lstm_step_fwd(lb.gates[l] + r0 * 8L * H, lb.wfrag[l], lb.hf[c] + (st & 1) * half,
-                                     lb.hf[c] + ((st & 1) ^ 1) * half, lb.out[l] + r0 * 2L * H, lb.csave[l] + r0 * 2L * H,
-                                     ch[c].nb, T, H, st, ch[c].st));
-            }
+            HIPCHK(lstm_step_fwd(lb.gates[l], lb.wfrag[l], lb.hf + (st & 1) * half, lb.hf + ((st & 1) ^ 1) * half, lb.out[l], lb.csave[l], B, T, H, st, s));
     }
-    if (nch == 2) CHK(fork_join(e, ch[1].st, s));
     return 0;
 }
 
@@ -1397,7 +1322,7 @@ int lstm_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
             d.A = {xi.p + HALO * xi.ld, xi.ld, TP * xi.ld, 0, 0};
             d.a_pre_scale = xi.scale;                  // conv-block output (layer 0); hidden states |h| < 1 take the fixed 16
             d.B = {lb.wcat[l], In, 0, 0, 0};
-            d.b_pre = (g_presplit & 1) ? lb.wimg(l) : nullptr;
+            d.b_pre = lb.wimg(l);
             d.C = lb.gates[l] + HALO * 8L * H;
             d.ldc = 8L * H;
             d.cstride = TP * 8L * H;
@@ -1425,7 +1350,7 @@ int lstm_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
 // the layer input's image (the hidden states of layer l - 1, written by the forward recurrence).  `gate` (nullable): the sync words of the
 // persistent recurrence the launch is meant to run beside -- the GEMM is dispatched once that grid is resident (seq_gate).
 bool lstm_wih_queue_ok(ss_engine* e, LstmBlk& lb, int l, const float* am) {
-    if (!g_img || !am || &lb != &e->ld || l < 1 || l >= 3 || !e->dg_img[l] || e->precision != SS_PRECISION_F32 || !g_bwd_f16x2) return false;
+    if (!am || &lb != &e->ld || l < 1 || l >= 3 || !e->dg_img[l] || e->precision != SS_PRECISION_F32 || !g_bwd_f16x2) return false;
     if (!lb.out_img_valid || !lb.out_img[l - 1] || !e->wq_pool || e->wq_next >= ss_engine::WQ_SLOTS) return false;
     return lb.pd[l * 2 + 1].wih > lb.pd[l * 2].wih;
 }
@@ -1470,18 +1395,14 @@ int lstm_wih_gemm_queued(ss_engine* e, LstmBlk& lb, int l, const float* am, cons
 
 // part: 0 everything; 2 everything except the W_ih gradient (it went out through lstm_wih_grad_queued)
 int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am, bool bias_done, hipStream_t ws, int part = 0) {
-#ifdef SS_DIAG      // what-if timing runs (WRONG gradients; -DSS_DIAG library only): the step without the decoder's / the encoder BLSTMs' weight-gradient launches
-    if ((g_exp & 4) && lb.big()) return 0;
-    if ((g_exp & 16) && !lb.big()) return 0;
-#endif
     const int B = e->curB, T = e->curT, H = lb.H;
     const long TP = T + 2 * HALO, R = (long)B * TP;
     const int In = lb.in_of(l);
     float* dG = lb.gates[l];
     const LstmDir &p0 = lb.pd[l * 2], &p1 = lb.pd[l * 2 + 1];
-    if (!lb.big() && g_wgrad_fused && H <= 32 && !bias_done && e->part && e->colsum_ctr && e->wg.n < WGRAD_MAX &&
+    if (!lb.big() && H <= 32 && !bias_done && e->part && e->colsum_ctr && e->wg.n < WGRAD_MAX &&
         e->part_off + (long)(e->wg.tiles_total + lstm_small_wgrad_tiles(H, In)) * 16 * 4096 <= e->part_cap) {
-        // encoder BLSTMs: one fused fp32 kernel for the weight and bias gradients of every layer (lstm_wgrad.hip)
+        // encoder BLSTMs: one fused fp32 kernel for the weight and bias gradients of every layer (lstm_wgrad.hip) instead of 12-14 tiny GEMMs + column sums
         WgradTask& t = e->wg.t[e->wg.n];
         t = WgradTask{dG, xi.p, xi.ld, lb.out[l], e->G + p0.wih, e->G + p1.wih, e->G + p0.whh, e->G + p1.whh, e->G + p0.bih, e->G + p0.bhh, e->G + p1.bih,
                       e->G + p1.bhh, H, In, R, e->wg.tiles_total, (int)lb.ow()};
@@ -1493,23 +1414,17 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
     const bool compact = l == 0 && lb.xf && xi.p == lb.xc;     // dW_ih from the block sums and one input row per block (K / xf)
     // the hidden-state slabs of a decoder-size block on the persistent kernels also exist as pre-split images (written by the forward)
     const bool img_ok = lb.out_img_valid && lb.out_img[l];
-    // the decoder's pre-activation gradients as an image for the image GEMM (scale: the power of two for the maximum the recurrence measured)
+    // 16-bit data path: the decoder's pre-activation gradients as a bf16 image for the image GEMM, written by the backward recurrence's storing
+    // wave.  (fp32 mode: the weight gradients are not in the image class set, IMG_CLASSES, and stay on round 2's kernel.)
     const float* dimg = nullptr;
-    const float* dsc = nullptr;
-    const bool i16 = e->img16();
-    if (i16) {
-        if (g_img && &lb == &e->ld && l < 3 && ((e->dg16_written >> l) & 1) && img_ok) dimg = e->dg_img[l];      // written by the backward recurrence's storing wave
-    } else if (g_img && ((g_img_mask >> SS_PROF_DEC_DW) & 1) && am && &lb == &e->ld && l < 3 && e->dg_img[l] && e->precision == SS_PRECISION_F32 && img_ok) {
-        HIPCHK(split_image(dG, 8L * H, R, 8 * H, am, 0.f, e->dg_img[l], 8L * H, e->gscale + lb.amax0 + l, ws));
-        dimg = e->dg_img[l];
-        dsc = e->gscale + lb.amax0 + l;
-    }
+    if (e->img16() && &lb == &e->ld && l < 3 && ((e->dg16_written >> l) & 1) && img_ok) dimg = e->dg_img[l];
     // Both directions in ONE launch each (batch = 2) when their parameters sit at one stride in the arena (PyTorch's order: they do).
     // dW_hh: h_prev is `out` one row earlier (forward) / later (reverse), so the forward direction reads dG one row later instead.
     // (With the image GEMM the decoder's launches are batched as well: 64 + 32 tile jobs per layer instead of 4 x (32 or 16) halve the
     // split-K factor, i.e. the partial-slab traffic and the number of reduce passes.)
-    const bool img_batch = dimg && g_img_batch && (i16 ? ((g_bf16_img_mask >> SS_PROF_DEC_DW) & 1) != 0 : ((g_img_mask >> SS_PROF_DEC_DW) & 1) != 0);
-    if ((!compact || img_batch) && (g_batch_dirs == 2 || (g_batch_dirs == 1 && !lb.big()) || img_batch) && p1.wih - p0.wih == p1.whh - p0.whh && p1.wih > p0.wih) {
+    // The encoder BLSTMs always (36 -> 14 launches); the decoder only with images (without: measured step +0.18 ms).
+    const bool img_batch = dimg != nullptr;
+    if ((!compact || img_batch) && (!lb.big() || img_batch) && p1.wih - p0.wih == p1.whh - p0.whh && p1.wih > p0.wih) {
         const long pstride = p1.wih - p0.wih;
         GemmDesc a{};
         a.A = {dG, 8L * H, 4L * H, 0, 0};
@@ -1528,7 +1443,6 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
         a.queue = e->wq_mode ? 1 : 0;
         if (dimg && l > 0) {
             a.a_pre = dimg;
-            a.a_pre_scale = dsc;
             a.b_pre = lb.out_img[l - 1];
         }
         if (!compact && part != 2) PGEMM_ON(lb.big() ? SS_PROF_DEC_DW : SS_PROF_ENC_LSTM, a, ws);
@@ -1537,7 +1451,6 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
         h.B = {lb.out[l], lb.ow(), lb.ow() + H, 0, 0};                         // forward: rows 0 .. of h_f, reverse: rows 1 .. of h_b
         if (dimg) {
             h.a_pre = e->ioff(dimg, 8L * H);
-            h.a_pre_scale = dsc;
             h.b_pre = lb.out_img[l];
         }
         h.C = e->G + p0.whh;
@@ -1588,10 +1501,7 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
         // dW_ih[n][k] = sum_r dG[r][n] * X[r][k]
         GemmDesc a{};
         a.A = {compact ? lb.dgs + dir * 4L * H : dGd, 8L * H, 0, 0, 0};
-        if (dimg && !compact) {
-            a.a_pre = e->ioff(dimg, a.A.p - dG);
-            a.a_pre_scale = dsc;
-        }
+        if (dimg && !compact) a.a_pre = e->ioff(dimg, a.A.p - dG);
         a.B = {xi.p, xi.ld, 0, 0, 0};
         if (img_ok && l > 0) a.b_pre = lb.out_img[l - 1];
         a.C = e->G + pd.wih;
@@ -1608,10 +1518,7 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
         // dW_hh[n][k] = sum_r dG[r][n] * h_prev[r][k];  h_prev = out one row earlier (fwd) / later (reverse)
         GemmDesc h{};
         h.A = {dir == 0 ? dGd + 8L * H : dGd, 8L * H, 0, 0, 0};
-        if (dimg) {
-            h.a_pre = e->ioff(dimg, h.A.p - dG);
-            h.a_pre_scale = dsc;
-        }
+        if (dimg) h.a_pre = e->ioff(dimg, h.A.p - dG);
         h.B = {dir == 0 ? lb.out[l] : lb.out[l] + lb.ow() + H, lb.ow(), 0, 0, 0};
         if (img_ok) h.b_pre = dir == 0 ? lb.out_img[l] : e->ioff(lb.out_img[l], 2L * H + H);
         h.C = e->G + pd.whh;
@@ -1652,7 +1559,7 @@ int lstm_input_grad(ss_engine* e, LstmBlk& lb, int l, Slab dxi, long r0, long nr
         GemmDesc g{};
         g.A = {lb.dgs, 8L * H, 0, 0, 0};
         g.B = {lb.wcat[0], In, 0, 0, 0};
-        g.b_pre = (g_presplit & 1) ? lb.wimg(0) : nullptr;
+        g.b_pre = lb.wimg(0);
         g.C = lb.d_xc;
         g.ldc = In;
         g.M = (int)R8;
@@ -1674,8 +1581,8 @@ int lstm_input_grad(ss_engine* e, LstmBlk& lb, int l, Slab dxi, long r0, long nr
     g.A = {lb.gates[l] + r0 * 8L * H, 8L * H, 0, 0, 0};
     g.B = {lb.wcat[l], In, 0, 0, 0};
     // (round 2's kernel measured SLOWER with the weight image in format v2 on this transposing-read operand -- 573 us per step with it, 532
-    // without -- so it only gets that image when asked to, presplit bit 3)
-    g.b_pre = (((g_presplit & 8) || e->img16()) && (g_presplit & 1)) ? lb.wimg(l) : nullptr;
+    // without -- so only the 16-bit data path, whose image GEMM reads it, passes that image)
+    g.b_pre = e->img16() ? lb.wimg(l) : nullptr;
     const bool dg16 = e->img16() && &lb == &e->ld && l < 3 && ((e->dg16_written >> l) & 1);      // the gradient slab's bf16 image (backward recurrence's storing wave)
     if (dg16) g.a_pre = e->ioff(e->dg_img[l], r0 * 8L * H);
     g.C = dxi.p + r0 * dxi.ld;
@@ -1720,18 +1627,14 @@ int lstm_bwd(ss_engine* e, LstmBlk& lb, const float* d_top, Slab x, Slab dx, hip
     const int B = e->curB, T = e->curT, H = lb.H;
     const long TP = T + 2 * HALO, R = (long)B * TP;
     const float* dcur = d_top;
-    Chain ch[2];
-    ch[0] = {0, B, s};
     const bool persist = lb.big() && g_persist && lstm_seq_supported(B, H);
-    const int nch = (lb.big() && !persist) ? make_chains(e, B, s, ch) : 1;
-    if (lb.big() && nch == 2) CHK(fork_join(e, s, ch[1].st));
     // see ss_engine::wq_pool: only with the weight gradients deferred (their usual schedule), on the decoder, where XCDs stay free
     const bool xcd = persist && &lb == &e->ld && g_xcd_dw && e->side && g_overlap && (g_defer_dw || late_w) && !g_deterministic &&
                      lstm_seq_free_xcds(B, H) >= 2;
     bool xcd_split[4] = {false, false, false, false};
     // 16-bit data path: the recurrence writes the gradient image itself and every weight-gradient GEMM of a layer is one image launch per
     // operand pair, so the WHOLE layer above goes out beside this layer's recurrence (work-queue form: 144 KB workgroups, one per free CU)
-    const bool early16 = persist && &lb == &e->ld && g_early_dw && e->img16() && g_img && g_img_batch && e->side && g_overlap && (g_defer_dw || late_w) &&
+    const bool early16 = persist && &lb == &e->ld && g_early_dw && e->img16() && e->side && g_overlap && (g_defer_dw || late_w) &&
                          !g_deterministic && !e->dp_on && e->wq_pool && lstm_seq_free_xcds(B, H) >= 2 && lb.out_img_valid;
     bool early_ready[4] = {false, false, false, false};
     for (int l = lb.L - 1; l >= 0; --l) {
@@ -1745,36 +1648,25 @@ int lstm_bwd(ss_engine* e, LstmBlk& lb, const float* d_top, Slab x, Slab dx, hip
         const bool bias_in_kernel = persist && !g_deterministic && lb.pd[l * 2].bhh == lb.pd[l * 2].bih + 4L * H &&
                                     lb.pd[l * 2 + 1].bhh == lb.pd[l * 2 + 1].bih + 4L * H;
         if (lb.big()) {
-            for (int c = 0; c < nch && !persist; ++c) {
-                const long half = 2L * (((ch[c].nb + 15) / 16) * 16) * 4 * H;
-                HIPCHK(hipMemsetAsync(lb.gf[c], 0, 2 * half * 4, ch[c].st));
-            }
             // persistent: start state zeroed by backward_decoder
             if (persist) {
-                // activated gates and cell states of the forward pass are long gone from the caches: one streaming read beside the
-                // recurrence puts them into the memory-side cache ahead of its 64-byte requests (lstm_seq.hip, slab_prewarm_kernel)
-                const bool pw = (g_prewarm & 1) && e->side3 && g_overlap;
-                if (pw) {
-                    CHK(fork_join(e, s, e->side3));
-                    HIPCHK(slab_prewarm(dG, 8 * H, lb.csave[l], dcur, 2 * H, e->amax, B, T, false, e->side3));
-                }
-                const bool dg16 = e->img16() && g_img && &lb == &e->ld && l < 3 && e->dg_img[l] && nch == 1;
+                // (a streaming pre-read of the activated gates and cell states beside the recurrence, as the forward does for its input
+                // projections, was measured: no gain in the step; neither one recurrence ahead: +0.08 ms)
+                const bool dg16 = e->img16() && &lb == &e->ld && l < 3 && e->dg_img[l];
                 // only as bf16 when every reader takes the image: weight gradients and input gradient on the image GEMM (layers >= 1: aligned
                 // shapes, both images present; layer 0: compact form -- dW_ih and dX from the block sums, dW_hh from the image), bias sums in the
                 // kernel (not the deterministic mode's column sum over the fp32 slab), weight gradients deferred or not: same readers
                 const bool compact0 = l == 0 && lb.xf && dx.p == lb.d_xc;
-                const bool skip32 = dg16 && g_seq_skip32 && bias_in_kernel && lb.out_img_valid && lb.out_img[l] && g_img_batch &&
-                                    ((g_bf16_img_mask >> SS_PROF_DEC_DW) & 1) && ((g_bf16_img_mask >> SS_PROF_DEC_DX) & 1) &&
-                                    (l == 0 ? compact0 : (lb.wimg(l) != nullptr && (g_presplit & 1) && lb.in_of(l) % 64 == 0)) && H % 64 == 0;
+                const bool skip32 = dg16 && bias_in_kernel && lb.out_img_valid && lb.out_img[l] &&
+                                    (l == 0 ? compact0 : (lb.wimg(l) != nullptr && lb.in_of(l) % 64 == 0)) && H % 64 == 0;
                 const int pi = prof_begin(e, SS_PROF_REC_BWD, s, 2.0 * 2 * B * T * 4.0 * H * H);
                 HIPCHK(lstm_seq_bwd(dG, e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.px_l(l), dcur, lb.csave[l], lb.sync_b(l),
                                     e->sticky, am, bias_in_kernel ? e->G + lb.pd[l * 2].bih : nullptr,
                                     bias_in_kernel ? e->G + lb.pd[l * 2 + 1].bih : nullptr, (l == 0 && lb.xf && dx.p == lb.d_xc) ? lb.dgs : nullptr,
-                                    (l == 0 && lb.xf && dx.p == lb.d_xc) ? lb.xf : 0, B, T, H, false, false, s, dg16 ? e->dg_img[l] : nullptr, (e->img16() && g_seq_hi ? 1 : 0) | (skip32 ? 4 : 0)));
+                                    (l == 0 && lb.xf && dx.p == lb.d_xc) ? lb.xf : 0, B, T, H, false, false, s, dg16 ? e->dg_img[l] : nullptr, (e->img16() ? 1 : 0) | (skip32 ? 4 : 0)));      // 1: products of the high fp16 pieces only (16-bit data path)
                 if (dg16) e->dg16_written |= 1 << l;
                 if (skip32) e->dg32_skipped |= 1 << l;
                 prof_end(e, pi, s);
-                if (pw) CHK(fork_join(e, e->side3, s));
                 if (early16) {
                     if (l + 1 < lb.L && early_ready[l + 1]) {
                         HIPCHK(seq_gate(lb.sync_b(l), B, H, e->side));          // dispatched once this recurrence's grid is resident
@@ -1804,13 +1696,12 @@ int lstm_bwd(ss_engine* e, LstmBlk& lb, const float* d_top, Slab x, Slab dx, hip
                     }
                 }
             }
-            for (int st = 0; st < T && !persist; ++st)
-                for (int c = 0; c < nch; ++c) {
-                    const long r0 = (long)ch[c].b0 * TP;
-                    const long half = 2L * (((ch[c].nb + 15) / 16) * 16) * 4 * H;
-                    HIPCHK(lstm_step_bwd(dG + r0 * 8L * H, lb.wfrag[l], lb.gf[c] + (st & 1) * half, lb.gf[c] + ((st & 1) ^ 1) * half,
-                                         dcur + r0 * 2L * H, lb.csave[l] + r0 * 2L * H, lb.dc[c], ch[c].nb, T, H, st, ch[c].st));
-                }
+            if (!persist) {      // one launch per time step
+                const long half = 2L * (((B + 15) / 16) * 16) * 4 * H;
+                HIPCHK(hipMemsetAsync(lb.gf, 0, 2 * half * 4, s));
+                for (int st = 0; st < T; ++st)
+                    HIPCHK(lstm_step_bwd(dG, lb.wfrag[l], lb.gf + (st & 1) * half, lb.gf + ((st & 1) ^ 1) * half, dcur, lb.csave[l], lb.dc, B, T, H, st, s));
+            }
         } else {
             { const int pa_ = prof_begin(e, SS_PROF_ENC_REC, s, 0.0);
             HIPCHK(lstm_small_bwd(dG, e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, dcur, lb.csave[l], B, T, H, s));
@@ -1821,33 +1712,27 @@ int lstm_bwd(ss_engine* e, LstmBlk& lb, const float* d_top, Slab x, Slab dx, hip
         // they stretch the latency-bound recurrence steps and halve the rate of the input-gradient GEMMs on the critical
         // path (measured: chain 2.95 ms with the GEMMs beside it against 1.93 ms alone + 0.78 ms of GEMMs), whereas the
         // encoder backward that follows is a string of small launches they can run beside.
-        const bool defer = (persist && e->side && g_overlap && g_defer_dw) || (late_w && nch == 1);
+        const bool defer = (persist && e->side && g_overlap && g_defer_dw) || late_w;
         if (defer) {
             if (dxi.p) CHK(lstm_input_grad(e, lb, l, dxi, 0, R, am, s));
             if (l == 0 && dx_ready) HIPCHK(hipEventRecord(dx_ready, s));
             dcur = dxi.p;
             continue;
         }
-        // the pre-activation gradients of this layer are complete once every chain has passed this point
+        // the pre-activation gradients of this layer are complete behind this point
         if (e->side && g_overlap) {
             // decoder: the side stream.  Encoder BLSTMs (a string of ~36 tiny split-K launches): the third branch stream, so
             // that they do not queue behind the decoder's weight gradients, which drain on the side stream until late
             ws = (!lb.big() && e->side3) ? e->side3 : e->side;
-            for (int c = 0; c < nch; ++c)
-                if (ch[c].st != ws) CHK(fork_join(e, ch[c].st, ws));
+            if (s != ws) CHK(fork_join(e, s, ws));
             if (ws == e->side) e->side_used = true;
-        } else if (nch == 2) {
-            CHK(fork_join(e, ch[1].st, s));        // weight gradients run on s and need both halves
         }
-        // input gradient first (the next layer's recurrence needs it), per chain on its own rows
-        if (dxi.p)
-            for (int c = 0; c < nch; ++c)
-                CHK(lstm_input_grad(e, lb, l, dxi, (long)ch[c].b0 * TP, nch == 2 ? (long)ch[c].nb * TP : R, am, ch[c].st));
-        if (l == 0 && dx_ready && nch == 1) HIPCHK(hipEventRecord(dx_ready, ch[0].st));
+        // input gradient first (the next layer's recurrence needs it)
+        if (dxi.p) CHK(lstm_input_grad(e, lb, l, dxi, 0, R, am, s));
+        if (l == 0 && dx_ready) HIPCHK(hipEventRecord(dx_ready, s));
         CHK(lstm_weight_grads(e, lb, l, xi, am, bias_in_kernel, ws));
         dcur = dxi.p;
     }
-    if (nch == 2) CHK(fork_join(e, ch[1].st, s));
     if (persist && e->side && g_overlap && g_defer_dw && !late_w) {
         CHK(fork_join(e, s, e->side));
         e->side_used = true;
@@ -1917,8 +1802,7 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     hipStream_t b1 = par ? e->side : s, b2 = par ? e->side2 : s;
     e->grads_zeroed = false;               // set again below when this forward belongs to a fused training step
     e->bwd_sync_zeroed = false;
-    const bool pack_one = g_pack_one;
-    if (pack_one) {
+    {   // every conv block's per-step weight re-layout (and the images of the packed weights) in one launch
         ConvPackTable pt{};
         pt.img_bf16 = e->img16();
         ConvBlk* all[7] = {&e->c1[0], &e->c2[0], &e->c1[1], &e->c2[1], &e->c1[2], &e->c2[2], &e->ct};
@@ -1927,12 +1811,9 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
             const bool img = cb->img_ok();
             pt.t[pt.n++] = {e->P + cb->w, cb->wf, cb->wb, img ? cb->wf_img : nullptr, img ? cb->wb_img : nullptr, cb->Co, cb->Ci, cb->Cp};
         }
-        { const int pa_ = prof_begin(e, SS_PROF_PREP, s, 0.0);
+        const int pa_ = prof_begin(e, SS_PROF_PREP, s, 0.0);
         HIPCHK(conv_pack_many(pt, s));
-        prof_end(e, pa_, s); }
-    } else {
-        if (g3) CHK(conv_pack_all(e, e->c1[0], s));
-        CHK(conv_pack_all(e, e->c2[0], s));
+        prof_end(e, pa_, s);
     }
     CHK(act_scales_all(e, s));             // before every branch forks: the scale words of the conv blocks' outputs
     if (par) CHK(fork_join(e, s, b2));
@@ -1943,11 +1824,11 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
         if (e->late_emb) HIPCHK(hipMemcpyAsync(e->emb, e->late_emb, (long)B * hh.dim_spk_emb * 4, hipMemcpyDeviceToDevice, b2));
     }
     // Encoder_7's content (512 ch) and pitch (256 ch) stacks only share the random-resampling PLAN of each layer (model.py:199-206: one
-    // warp applied to the concatenation), and the plans depend on the draws alone.  With g_trunk_indep the plans are computed first thing
+    // warp applied to the concatenation), and the plans depend on the draws alone.  With branch streams the plans are computed first thing
     // on the branch stream and the two stacks run as independent chains on `s` and `b1` -- conv, GroupNorm, gather of their OWN columns --
     // down to their BLSTMs, instead of meeting before every gather.
-    const bool indep = g3 && par && g_conv_par && g_trunk_indep;
-    e->xf_img_valid = indep && training && (g_presplit & 4) && e->xf_img[0] && ((e->precision == SS_PRECISION_F32 && g_fwd_f16x2) || (e->img16() && g_gn_gather));     // only fp16 x 2 / 16-bit-path GEMMs read images
+    const bool indep = g3 && par;
+    e->xf_img_valid = indep && training && e->xf_img[0] && ((e->precision == SS_PRECISION_F32 && g_fwd_f16x2) || (e->img16() && g_gn_gather));     // only fp16 x 2 / 16-bit-path GEMMs read images
     hipEvent_t plans = nullptr;
     if (indep && training) {
         for (int i = 0; i < 3; ++i)
@@ -1958,17 +1839,6 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
         HIPCHK(hipEventRecord(plans, b2));
     }
     if (indep) CHK(fork_join(e, s, b1));
-    for (int i = 1; i < 3 && !pack_one; ++i) {
-        if (g3) CHK(conv_pack_all(e, e->c1[i], b2));
-        CHK(conv_pack_all(e, e->c2[i], b2));
-    }
-    if (!pack_one) CHK(conv_pack_all(e, e->ct, b2));
-    hipEvent_t packed = nullptr;
-    if (par && !pack_one) {
-        packed = e->ev[e->ev_next];
-        e->ev_next = (e->ev_next + 1) & 15;
-        HIPCHK(hipEventRecord(packed, b2));
-    }
     // The branch stream's work that nobody needs before the trunk is through: bias sums / W_ih stackings, start state of the
     // persistent recurrences, the gradient-arena memset, the parameter guard, and Encoder_t (model.py:74-89).  With g_prio_order it
     // is ENQUEUED behind the trunk's three layers (it still runs beside them: the host is far ahead of the GPU), so that on a shared
@@ -1989,7 +1859,7 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
             e->grads_zeroed = true;
             // the backward recurrences' group words and exchange tiles (nothing in the forward touches them): zeroed here, the backward
             // needs no fork / memset / join between the head's gradient and its first recurrence (two event hops on the critical path)
-            if (e->ld.big() && g_persist && lstm_seq_supported(e->curB, e->ld.H) && !(g_exp & 32)) {      // (exp & 32: A/B switch, both schedules are correct)
+            if (e->ld.big() && g_persist && lstm_seq_supported(e->curB, e->ld.H)) {
                 HIPCHK(hipMemsetAsync(e->ld.zb, 0, e->ld.zb_bytes, b2));
                 if (e->wq_pool) HIPCHK(hipMemsetAsync(e->wq_pool, 0, ss_engine::WQ_SLOTS * 16, b2));
                 e->bwd_sync_zeroed = true;
@@ -2007,14 +1877,10 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     };
     for (int i = 0; i < 3; ++i) {
         float* y = training ? e->act : e->xf[i];
-        if (i == 1) {
-            // Issue order matters: a cross-stream wait on ROCm holds for everything the other stream had been handed when
-            // the WAIT was issued, not only up to the recorded event (measured: the trunk stalled ~250 us behind the tiny
-            // launches below).  So: first trunk layer, the wait for the re-layouts, and only then the rest of b2's work.
-            if (packed) HIPCHK(hipStreamWaitEvent(s, packed, 0));
-            if (packed && indep) HIPCHK(hipStreamWaitEvent(b1, packed, 0));
-            if (!prio_fwd) CHK(branch_work());
-        }
+        // Issue order matters: a cross-stream wait on ROCm holds for everything the other stream had been handed when
+        // the WAIT was issued, not only up to the recorded event (measured: the trunk stalled ~250 us behind the tiny
+        // launches of b2's work).  So: first trunk layer, and only then the rest of b2's work.
+        if (i == 1 && !prio_fwd) CHK(branch_work());
         if (indep) {
             const float* im = (e->xf_img_valid && i > 0) ? e->xf_img[i - 1] : nullptr;
             Slab x1 = i == 0 ? Slab{e->in_mel, e->hp.dim_freq} : Slab{e->xf[i - 1], CE, im, e->act_scale + e->c1[i - 1].scale_i};
@@ -2041,30 +1907,18 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
             }
             continue;
         }
-        // The content (512 ch) and pitch (256 ch) blocks of a layer are independent: with g_conv_par the pitch block and the layer's
-        // resampling plan run on the first branch stream beside the content block.
-        const bool cpar = g3 && par && g_conv_par;
-        hipStream_t sp = cpar ? b1 : s;
-        if (cpar) CHK(fork_join(e, s, b1));
+        // one chain on `s` (Generator_6's single stack; Generator_3 without branch streams)
         if (g3) {
             Slab x1 = i == 0 ? Slab{e->in_mel, e->hp.dim_freq} : Slab{e->xf[i - 1], CE, nullptr, e->act_scale + e->c1[i - 1].scale_i};
-            if (!cpar) CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s));
+            CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s));
         }
         Slab x2 = i == 0 ? Slab{e->in_f0, e->f0p} : Slab{e->xf[i - 1] + off2, CE, nullptr, e->act_scale + e->c2[i - 1].scale_i};
-        CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, sp));
+        CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, s));
         if (training) {
             // one warp for both streams (model.py:202-206), len_seq = max_len_pad for every utterance (:105,157,203)
             InterpPlan& pl = e->plan[draw0 + i];
             HIPCHK(interp_plan(pl, scales + (long)(draw0 + i) * B * S7, len_seg + (long)(draw0 + i) * B * S7, nullptr,
-                               e->hp.max_len_pad, B, sp));
-        }
-        if (cpar) {
-            Slab x1 = i == 0 ? Slab{e->in_mel, e->hp.dim_freq} : Slab{e->xf[i - 1], CE, nullptr, e->act_scale + e->c1[i - 1].scale_i};
-            CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s));
-            CHK(fork_join(e, b1, s));
-        }
-        if (training) {
-            InterpPlan& pl = e->plan[draw0 + i];
+                               e->hp.max_len_pad, B, s));
             HIPCHK(interp_gather(pl, e->act + HALO * CE, CE, TP * CE, e->xf[i] + HALO * CE, CE, TP * CE, CE, B, s));
         }
     }
@@ -2220,7 +2074,7 @@ int backward_decoder(ss_engine* e, hipStream_t s, bool late = false) {
 // offsets below the decoder's, so a data-parallel caller can all-reduce the decoder range meanwhile.
 int backward_encoder(ss_engine* e, hipStream_t s) {
     e->unpack.n = 0;
-    e->unpack_later = !e->dp_on && g_unpack_later;       // (data parallel: a trunk layer's bucket leaves right behind its block)
+    e->unpack_later = !e->dp_on;       // (data parallel: a trunk layer's bucket leaves right behind its block)
     struct UnpackOff {
         ss_engine* e;
         ~UnpackOff() { e->unpack_later = false; }
@@ -2266,10 +2120,10 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
         if (!prio) CHK(fork_join(e, s, b3));
     }
     CHK(zero_conv_grads(e, b2));                   // long done when the first conv weight gradient starts (b2 joins s, b3 forks after)
-    if (prio && g_enc_t_first && b3 != b2) CHK(fork_join(e, b2, b3));      // Encoder_t's conv weight gradient accumulates into its zeroed image before b3 sees lstm_2's event
+    if (prio && b3 != b2) CHK(fork_join(e, b2, b3));      // Encoder_t's conv weight gradient accumulates into its zeroed image before b3 sees lstm_2's event
     if (par && !prio) CHK(fork_join(e, b2, b3));
     // encoder BLSTMs -> gradient of the last fused slab
-    const bool early = par && !e->l2.big() && g_early_join;         // the join event of the lstm_2 branch is taken as soon as its last kernel is queued
+    const bool early = par && !e->l2.big();         // the join event of the lstm_2 branch is taken as soon as its last kernel is queued
     CHK(lstm_bwd(e, e->l2, e->d_o2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, Slab{e->d_xf + off2, CE}, b2, (early || prio) ? e->ev_join[0] : nullptr, prio));
     if (g3) {
         CHK(lstm_bwd(e, e->l1, e->d_o1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, Slab{e->d_xf, CE}, s, nullptr, prio));
@@ -2299,10 +2153,7 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
         } over_scope{e};
         e->dw_over[0] = over_ih;
         e->dw_over[1] = over_hh;
-        if (dec_next == e->ld.L - 1) {
-            if (g_exp & 1) CHK(fork_join(e, s, e->side));      // experiment: ... and behind the conv trunk's backward as well (the two chains run one after the other)
-            HIPCHK(hipStreamWaitEvent(e->side, e->ev_join[1], 0));
-        }
+        if (dec_next == e->ld.L - 1) HIPCHK(hipStreamWaitEvent(e->side, e->ev_join[1], 0));
         if (ws != e->side) {
             if (dec_other[0] != ws && dec_other[1] != ws) dec_other[dec_other[0] ? 1 : 0] = ws;
             HIPCHK(hipStreamWaitEvent(ws, e->ev_join[1], 0));
@@ -2314,7 +2165,7 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
             e->dec_w_pending = false;
             for (hipStream_t o : dec_other)
                 if (o) CHK(fork_join(e, o, e->side));      // one join for the end of the step; the early optimiser update below reads what they wrote
-            if (e->adam_early && g_adam_early && !e->dp_on && e->Mm && e->Vv) {
+            if (e->adam_early && !e->dp_on && e->Mm && e->Vv) {
                 // every persistent recurrence and the parameter guard ran before the event this stream waited for: the status word is final
                 const long from = ss_grad_split(e);
                 if (from % 4 == 0 && from < e->arena) {
@@ -2334,12 +2185,16 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
     // instead of every decoder bucket in front of (or behind) every trunk bucket.  (One GPU: the decoder's weight gradients stay behind
     // the trunk in enqueue order, see prio_order.)
     if (e->dp_on) CHK(dec_late(e->ld.L - 1));
-    // Encoder_7's content (512 ch) and pitch (256 ch) stacks are independent chains in the backward as in the forward (forward_core, trunk_indep):
+    // Encoder_7's content (512 ch) and pitch (256 ch) stacks are independent chains in the backward as in the forward (forward_core):
     // each block's output gradient comes from its own BLSTM / its own upper block, its input gradient goes to its own lower block, and the two
-    // write disjoint columns of the shared slabs.  With g_trunk_bwd_par the pitch chain never leaves the stream lstm_2's backward ran on.
+    // write disjoint columns of the shared slabs.  The pitch chain never leaves the stream lstm_2's backward ran on (second branch stream), beside the
+    // content stack on the main stream, through all three layers (round 3 did this for layer 0 only): 64 x 128 unchanged (that phase is
+    // throughput-bound), 32 x 128 bf16 3.16 -> 3.02 ms, 16 x 128 fp32 3.44 -> 3.29.  (Measured and rejected beside it: each block's weight-gradient
+    // GEMM on the side stream beside its input-gradient GEMM -- +8 % at B <= 32: the two cross-stream event hops per block cost more than the
+    // overlap gains.)
     // Data parallel: that stream carries the collectives, so the pitch chain takes the third branch stream instead (behind the event of lstm_2's
     // input gradient; Encoder_t's backward and the fused weight gradients queue behind it there).
-    const bool chain_par = g_trunk_bwd_par && training && g3 && par && (g_exp & 2) == 0 && g_gn_gather && (!e->dp_on || (prio && b3 != s && b3 != b2));
+    const bool chain_par = training && g3 && par && g_gn_gather && (!e->dp_on || (prio && b3 != s && b3 != b2));
     hipStream_t cs = e->dp_on ? b3 : b2;
     if (chain_par && e->dp_on) HIPCHK(hipStreamWaitEvent(b3, e->ev_join[0], 0));      // d_xf's pitch columns (lstm_2's input gradient) and the zeroed conv images
     // weight gradients off the dependent chain (g_conv_dw_off): Generator_6's single chain, the second branch stream is idle behind lstm's backward
@@ -2360,7 +2215,7 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
         float* dxbuf = training ? e->d_xf : e->d_act;
         // the resampled activations also exist as pre-split images when the forward's gathers wrote them (training, independent trunk chains)
         const float* bim = (training && e->xf_img_valid && i > 0) ? e->xf_img[i - 1] : nullptr;
-        if (!chain_par && i == 0 && g3 && par && !e->dp_on && (g_exp & 2) == 0) CHK(fork_join(e, s, b2));      // tail_par below: the pitch block's stream forks BEFORE the content block is enqueued
+        if (!chain_par && i == 0 && g3 && par && !e->dp_on) CHK(fork_join(e, s, b2));      // tail_par below: the pitch block's stream forks BEFORE the content block is enqueued
         if (g3) {
             Slab x1 = i == 0 ? Slab{e->in_mel, h.dim_freq} : Slab{e->xf[i - 1], CE, bim, e->act_scale + e->c1[i - 1].scale_i};
             CHK(conv_block_bwd(e, e->c1[i], Slab{dy, CE}, x1, i > 0 ? Slab{dxbuf, CE} : Slab{nullptr, 0}, s, sc, sc_src, CE));
@@ -2369,7 +2224,7 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
         // Layer 0 is the step's tail: the decoder's weight gradients are through by then, and each of its two weight-gradient GEMMs alone
         // fills half the chip's workgroup slots -- the pitch block runs on the second branch stream beside the content block.  (Not under
         // data parallelism, where that stream carries the collectives.)
-        const bool tail_par = chain_par || (i == 0 && g3 && par && !e->dp_on && (g_exp & 2) == 0);
+        const bool tail_par = chain_par || (i == 0 && g3 && par && !e->dp_on);
         hipStream_t s2 = tail_par ? (chain_par ? cs : b2) : s;
         CHK(conv_block_bwd(e, e->c2[i], Slab{dy + off2, CE}, x2, i > 0 ? Slab{dxbuf + off2, CE} : Slab{nullptr, 0}, s2, sc, sc_src + off2, CE, (dw_off && i > 0) ? dw_s : nullptr));
         if (tail_par && (!chain_par || (i == 0 && !e->dp_on))) CHK(fork_join(e, b2, s));      // (chain_par: the two chains meet once, behind layer 0; data parallel: where the third branch stream joins below)
@@ -2403,25 +2258,15 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
     if (prio) {
         // Encoder_t's backward first: its input (d_ot from dec_in_grad) is the earliest thing this stream waits for, and it is a dependent chain of
         // five launches; the BLSTMs' weight gradients (all three blocks: ONE fused launch) only have to be done by the end of the step
+        // (Generator_6 32 x 192 bf16 2.26 -> 2.23 ms, 16 x 128 3.20 -> 3.18 against the BLSTMs' weight gradients in front; headline unchanged)
         HIPCHK(hipStreamWaitEvent(b3, e->ev_join[2], 0));                   // d_ot from dec_in_grad
-        if (!g_enc_t_first) {
-            HIPCHK(hipStreamWaitEvent(b3, e->ev_join[0], 0));
-            CHK(lstm_late_weights(e, e->l2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, b3));
-            if (g3) {
-                HIPCHK(hipStreamWaitEvent(b3, e->ev_join[3], 0));
-                CHK(lstm_late_weights(e, e->l1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, b3));
-            }
-            CHK(wgrad_flush(e, b3));
-        }
         CHK(lstm_bwd(e, e->lt, e->d_ot, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, Slab{e->d_act_t, h.dim_enc_2}, b3));
         CHK(conv_block_bwd(e, e->ct, Slab{e->d_act_t, h.dim_enc_2}, Slab{e->org, h.dim_freq}, Slab{nullptr, 0}, b3));
-        if (g_enc_t_first) {
-            HIPCHK(hipStreamWaitEvent(b3, e->ev_join[0], 0));                   // lstm_2's pre-activation gradients (and the zeroed conv images)
-            CHK(lstm_late_weights(e, e->l2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, b3));
-            if (g3) {
-                HIPCHK(hipStreamWaitEvent(b3, e->ev_join[3], 0));
-                CHK(lstm_late_weights(e, e->l1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, b3));
-            }
+        HIPCHK(hipStreamWaitEvent(b3, e->ev_join[0], 0));                   // lstm_2's pre-activation gradients (and the zeroed conv images)
+        CHK(lstm_late_weights(e, e->l2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, b3));
+        if (g3) {
+            HIPCHK(hipStreamWaitEvent(b3, e->ev_join[3], 0));
+            CHK(lstm_late_weights(e, e->l1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, b3));
         }
         CHK(wgrad_flush(e, b3));                   // Encoder_t's, lstm_2's and both layers of lstm_1's: one launch
         e->wg_defer = false;
@@ -2667,13 +2512,13 @@ int ss_bind(ss_engine* e, float* params, float* grads, float* m, float* v, void*
         // main + three branch streams, created back to back: HIP deals a process's streams onto its hardware queues in creation
         // order, so these four get one queue each no matter how many streams (PyTorch's, RCCL's) existed before
         if (g_own_streams) HIPCHK(hipStreamCreateWithFlags(&e->main_s, hipStreamNonBlocking));
-        if (g_probe_queues && !g_side_prio) {
+        if (g_probe_queues) {
             // branch streams chosen by MEASURING which candidates share a hardware queue with the stream the step will be issued on
             CHK(pick_streams(e, (g_own_streams && e->main_s) ? e->main_s : S(stream)));
         } else {
-            int least = 0, greatest = 0;
-            HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIPCHK(hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, g_side_prio ? least : 0));
+            // (the side stream at the lowest priority: measured 2.3x SLOWER, 35 ms vs 14.8 ms per step -- the low-priority queue starves
+            // behind 768 tiny step launches)
+            HIPCHK(hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, 0));
             HIPCHK(hipStreamCreateWithFlags(&e->side2, hipStreamNonBlocking));
             HIPCHK(hipStreamCreateWithFlags(&e->side3, hipStreamNonBlocking));
             e->stream_report = "branch streams as created (probe off)";
@@ -3218,88 +3063,65 @@ int ss_debug_gemm_phases(unsigned long long* out24, int reset) {
 }
 
 int ss_tune(const char* key, int value) {
-    const std::string k = key ? key : "";
-    if (k == "lstm_nw" && (value == 4 || value == 8 || value == 16)) g_lstm_nw = value;
-    else if (k == "lstm_g" && value >= 0 && value <= 16) g_lstm_g = value;
+    struct Key {
+        const char* name;
+        int* target;
+        int lo, hi;      // accepted values: lo <= value <= hi
+    };
+    constexpr int MAXV = 0x7fffffff;
+    static const Key keys[] = {
+        {"lstm_nw", &g_lstm_nw, 4, 16},      // 4, 8 or 16 (checked below)
+        {"lstm_g", &g_lstm_g, 0, 16},
 #ifdef SS_DIAG
-    else if (k == "lstm_mode" && value >= 0 && value <= 4) g_lstm_mode = value;
-    else if (k == "gemm_diag" && value >= 0 && value < 2048) g_gemm_diag = value;
-    else if (k == "seq_prio" && value >= 0 && value < 65536) g_seq_prio = value;
+        {"lstm_mode", &g_lstm_mode, 0, 4},
+        {"gemm_diag", &g_gemm_diag, 0, 2047},
+        {"seq_prio", &g_seq_prio, 0, 65535},
 #else
-    else if (k == "seq_prio" && (value == 0 || value == 1)) g_seq_prio = value;
+        {"seq_prio", &g_seq_prio, 0, 1},
 #endif
-    else if (k == "seq_tag" && (value == 0 || value == 1)) g_seq_tag = value;
-    else if (k == "op_time_major" && (value == 0 || value == 1)) g_op_time_major = value;
-    else if (k == "seq_wlead" && value >= 0 && value < 32) g_seq_wlead = value;
-    else if (k == "seq_var" && value >= 0 && value < 16) g_seq_var = value;
-    else if (k == "prewarm" && value >= 0 && value <= 3) g_prewarm = value;
-    else if (k == "batch_dirs" && value >= 0 && value <= 2) g_batch_dirs = value;
-    else if (k == "compact0" && (value == 0 || value == 1)) g_compact0 = value;
-    else if (k == "presplit" && value >= 0 && value <= 15) g_presplit = value;
-    else if (k == "bf16_img" && (value == 0 || value == 1)) g_bf16_img = value;
-    else if (k == "bf16_img_mask") g_bf16_img_mask = value;
-    else if (k == "seq_hi" && (value == 0 || value == 1)) g_seq_hi = value;
-    else if (k == "seq_skip32" && (value == 0 || value == 1)) g_seq_skip32 = value;
-    else if (k == "pack_one" && (value == 0 || value == 1)) g_pack_one = value;
-    else if (k == "trunk_bwd_par" && (value == 0 || value == 1)) g_trunk_bwd_par = value;
-    else if (k == "wgrad_fused" && (value == 0 || value == 1)) g_wgrad_fused = value;
-    else if (k == "img" && (value == 0 || value == 1)) g_img = value;
-    else if (k == "img_mask" && value >= 0 && value < 2048) g_img_mask = value;
-    else if (k == "img_batch" && (value == 0 || value == 1)) g_img_batch = value;
-    else if (k == "dp_model" && value >= 0 && value <= 64) g_dp_model = value;
-    else if (k == "dp_buckets" && (value == 0 || value == 1)) g_dp_buckets = value;
-    else if (k == "img_dw_cfg" && value >= -1 && value <= 3) g_img_dw_cfg = value;
-    else if (k == "img_dw_wgs" && value >= 32 && value <= 4096) g_img_dw_wgs = value;
-    else if (k == "img_cfg" && value >= -1 && value <= 3) g_img_cfg = value;
-    else if (k == "dw_wgs" && value >= 64 && value <= 4096) g_dw_wgs = value;
-    else if (k == "trunk_indep" && (value == 0 || value == 1)) g_trunk_indep = value;
-    else if (k == "branch_low" && (value == 0 || value == 1)) g_branch_low = value;
-    else if (k == "gemm_ws" && value >= 0 && value <= 2) g_gemm_ws = value;
-    else if (k == "seq_spin_log2" && value >= 0 && value <= 24) g_seq_spin_log2 = value;
-    else if (k == "overlap" && (value == 0 || value == 1)) g_overlap = value;
-    else if (k == "defer_dw" && (value == 0 || value == 1)) g_defer_dw = value;
-    else if (k == "dx_batched" && value >= 0 && value <= 2) g_dx_batched = value;
-    else if (k == "conv_want" && value >= 0) g_conv_want = value;
-    else if (k == "conv_small_old" && (value == 0 || value == 1)) g_conv_small_old = value;
-    else if (k == "small_lds" && value >= 0 && value <= 2) g_small_lds = value;
-    else if (k == "small_prio" && (value == 0 || value == 1)) g_small_prio = value;
-    else if (k == "gemm_tr" && value >= 0 && value <= 2) g_gemm_tr = value;
-#ifdef SS_DIAG
-#endif
-    else if (k == "own_streams" && (value == 0 || value == 1)) g_own_streams = value;
-    else if (k == "early_join" && (value == 0 || value == 1)) g_early_join = value;
-    else if (k == "conv_par" && (value == 0 || value == 1)) g_conv_par = value;
-    else if (k == "exp" && value >= 0) g_exp = value;
-    else if (k == "adam_early" && (value == 0 || value == 1)) g_adam_early = value;
-    else if (k == "enc_t_first" && (value == 0 || value == 1)) g_enc_t_first = value;
-    else if (k == "conv_dw_off" && value >= 0 && value <= 3) g_conv_dw_off = value;
-    else if (k == "dec_tail_split" && value >= 0 && value <= 10) g_dec_tail_split = value;
-    else if (k == "early_dw" && (value == 0 || value == 1)) g_early_dw = value;
-    else if (k == "xcd_dw" && (value == 0 || value == 1)) g_xcd_dw = value;
-    else if (k == "dp_emulate" && (value == 0 || value == 1)) g_dp_emulate = value;
-    else if (k == "gn_gather" && (value == 0 || value == 1)) g_gn_gather = value;
-    else if (k == "unpack_later" && (value == 0 || value == 1)) g_unpack_later = value;
-    else if (k == "part_splitk" && (value == 0 || value == 1)) g_part_splitk = value;
-    else if (k == "gn_part" && (value == 0 || value == 1)) g_gn_part = value;
-    else if (k == "img_xcc" && value >= 0 && value <= 511) g_img_xcc = value;      // bit 8: keep a placement log (ss_debug_img_wq)
-    else if (k == "probe_queues" && (value == 0 || value == 1)) g_probe_queues = value;
-    else if (k == "prio_order" && (value == 0 || value == 1)) g_prio_order = value;
-    else if (k == "flat_rows" && (value == 0 || value == 1)) g_flat_rows = value;
-    else if (k == "deterministic" && (value == 0 || value == 1)) g_deterministic = value;
-    else if (k == "split" && (value == 0 || value == 1)) g_split = value;
-    else if (k == "persist" && (value == 0 || value == 1)) g_persist = value;
-    else if (k == "side_prio" && (value == 0 || value == 1)) g_side_prio = value;
-    else if (k == "gemm_bk" && (value == 16 || value == 32)) g_gemm_bk = value;
-    else if (k == "gemm_want" && value >= 1) g_gemm_want = value;
-    else if (k == "gemm_mode" && (value == 0 || value == 1)) g_gemm_mode = value;
-    else if (k == "fwd_f16x2" && (value == 0 || value == 1)) g_fwd_f16x2 = value;
-    else if (k == "bwd_f16x2" && (value == 0 || value == 1)) g_bwd_f16x2 = value;
-    else return fail("ss_tune: unknown key or bad value: " + k
+        {"seq_tag", &g_seq_tag, 0, 1},
+        {"op_time_major", &g_op_time_major, 0, 1},
+        {"seq_var", &g_seq_var, 0, 15},
+        {"compact0", &g_compact0, 0, 1},
+        {"bf16_img", &g_bf16_img, 0, 1},
+        {"dp_model", &g_dp_model, 0, 64},
+        {"dp_buckets", &g_dp_buckets, 0, 1},
+        {"gemm_ws", &g_gemm_ws, 0, 2},
+        {"seq_spin_log2", &g_seq_spin_log2, 0, 24},
+        {"overlap", &g_overlap, 0, 1},
+        {"defer_dw", &g_defer_dw, 0, 1},
+        {"dx_batched", &g_dx_batched, 0, 2},
+        {"small_lds", &g_small_lds, 0, 2},
+        {"gemm_tr", &g_gemm_tr, 0, 2},
+        {"own_streams", &g_own_streams, 0, 1},
+        {"conv_dw_off", &g_conv_dw_off, 0, 3},
+        {"dec_tail_split", &g_dec_tail_split, 0, 10},
+        {"early_dw", &g_early_dw, 0, 1},
+        {"xcd_dw", &g_xcd_dw, 0, 1},
+        {"dp_emulate", &g_dp_emulate, 0, 1},
+        {"gn_gather", &g_gn_gather, 0, 1},
+        {"img_xcc", &g_img_xcc, 0, 511},      // bit 8: keep a placement log (ss_debug_img_wq)
+        {"probe_queues", &g_probe_queues, 0, 1},
+        {"prio_order", &g_prio_order, 0, 1},
+        {"deterministic", &g_deterministic, 0, 1},
+        {"persist", &g_persist, 0, 1},
+        {"gemm_want", &g_gemm_want, 1, MAXV},
+        {"gemm_mode", &g_gemm_mode, 0, 1},
+        {"fwd_f16x2", &g_fwd_f16x2, 0, 1},
+        {"bwd_f16x2", &g_bwd_f16x2, 0, 1},
+    };
+    const std::string k = key ? key : "";
+    for (const Key& t : keys) {
+        if (k != t.name) continue;
+        if (value < t.lo || value > t.hi || (t.target == &g_lstm_nw && value != 4 && value != 8 && value != 16)) break;
+        *t.target = value;
+        return 0;
+    }
+    return fail("ss_tune: unknown key or bad value: " + k
 #ifndef SS_DIAG
                      + " (the wrong-result timing modes lstm_mode / gemm_diag / seq_prio > 1 exist only in the -DSS_DIAG build: make diag)"
 #endif
     );
-    return 0;
 }
 
 int ss_op_lstm_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch,

@@ -15,7 +15,6 @@
 
 namespace ss {
 
-int g_gemm_bk = 16;        // (unused: BK = 32 measured slower; kept so ss_tune("gemm_bk") stays valid)
 int g_gemm_want = 1024;
 int g_deterministic = 0;   // ss_tune("deterministic", 1): run-to-run bit-identical results -- split-K only through ordered partial slabs (fp32 atomics commit in arrival
                            // order), ordered bias / affine gradient sums (elementwise.hip), bias gradients of the persistent recurrence

@@ -30,8 +30,6 @@
 
 namespace ss {
 
-int g_img_cfg = -1;       // experiment: force a tile configuration (-1: launch_gemm_img chooses)
-
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -561,7 +559,6 @@ hipError_t launch_gemm_img(const ImgGemmDesc& din, hipStream_t s) {
     if (d.ksplit > 1 && !d.part) return hipErrorInvalidValue;
     const bool ta = d.flags & GEMM_TA, tb = d.flags & GEMM_TB;
     int cfg = d.cfg;
-    if (g_img_cfg >= 0) cfg = g_img_cfg;
     if (cfg < 0 || cfg > 3) {
         // the largest tile that still gives every CU a workgroup
         auto wgs = [&](int bm, int bn) { return (long)cdiv(d.M, bm) * cdiv(d.N, bn) * d.batch * d.ksplit; };

@@ -56,7 +56,6 @@ int g_seq_var = 2;     // backward kernel, warm-up reads: 2 one dword per 128-by
                        // whichever of its bytes is asked for), 4 one dword per 64 bytes (two instructions), 0 round 2's six 1 KB reads.  What the
                        // warm-up costs is its return traffic through the CU's one vector-memory path, which the polls share: 6 KB -> 192 bytes per
                        // step takes the isolated step from 3.05 to 2.78 us (64 x 128), the training step 5.23 -> 5.21 ms (all shapes -0.02..-0.04)
-int g_seq_wlead = 0;   // backward kernel: steps between a warm-up read and the operand request it serves (0: the kernel's default)
 int g_seq_spin_log2 = 18;   // bounded wait of the group hand-off: 2^18 polls ~ tens of ms.  ss_tune("seq_spin_log2", 4) makes the
                             // first wait of a launch expire, which is how the tests exercise the abort path on hardware
 
@@ -1074,7 +1073,7 @@ long lstm_seq_xbytes(int B, int H, bool backward) {
 
 static int seq_slots(int nbt) { return 2 * nbt <= 8 ? 8 : 2 * nbt; }       // group slots per member index (see the kernels)
 static int seq_prio_arg(bool time_major, bool img_bf16 = false) {
-    return (int)((unsigned)(g_seq_prio & 0xFFFF) | ((unsigned)(g_seq_spin_log2 & 31) << 16) | (time_major ? 1u << 21 : 0u) | ((unsigned)(g_seq_wlead & 31) << 22) |
+    return (int)((unsigned)(g_seq_prio & 0xFFFF) | ((unsigned)(g_seq_spin_log2 & 31) << 16) | (time_major ? 1u << 21 : 0u) |      // (bits 22-26, the backward kernel's warm-up lead: 0 = its default)
                  ((unsigned)(g_seq_var & 15) << 27) | (img_bf16 ? 1u << 31 : 0u));
 }
 

@@ -19,7 +19,7 @@
 
 namespace ss {
 
-int g_small_prio = 1;    // the small recurrences run at s_setprio 3
+constexpr int SMALL_PRIO = 1;   // kernels' launch argument: the small recurrences run at s_setprio 3
 int g_small_lds = 1;     // 1: LDS-staged kernels (single-wave variant where it applies), 2: LDS-staged without the single-wave variant,
                         // 0: always the streaming kernels (A/B experiments)
 
@@ -33,7 +33,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_kern
                                                                                    const float* __restrict__ whh_b,
                                                                                    float* __restrict__ out,
                                                                                    float* __restrict__ csave, int T, int prio) {
-    if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (ss_tune("small_prio"))
+    if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (SMALL_PRIO)
     constexpr int OS = lstm_small_ld(H);           // row stride of out / csave
     __shared__ float hs[H];
     __shared__ float gs[4 * H];
@@ -81,7 +81,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_bwd_kern
                                                                                    const float* __restrict__ whh_b,
                                                                                    const float* __restrict__ d_out,
                                                                                    const float* __restrict__ csave, int T, int prio) {
-    if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (ss_tune("small_prio"))
+    if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (SMALL_PRIO)
     constexpr int OS = lstm_small_ld(H);           // row stride of d_out / csave
     __shared__ float dg[4 * H];
     __shared__ float part[4 * H];
@@ -178,7 +178,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_lds_
                                                                                        const float* __restrict__ whh_b,
                                                                                        float* __restrict__ out,
                                                                                        float* __restrict__ csave, int T, int prio) {
-    if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (ss_tune("small_prio"))
+    if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (SMALL_PRIO)
     constexpr int NT = 4 * H > 64 ? 4 * H : 64;
     constexpr int OS = lstm_small_ld(H);
     extern __shared__ __attribute__((aligned(16))) float dyn[];
@@ -231,7 +231,7 @@ template <int H>
 __global__ __launch_bounds__(64) void lstm_small_fwd_wave_kernel(float* __restrict__ gates, const float* __restrict__ whh_f,
                                                                  const float* __restrict__ whh_b, float* __restrict__ out,
                                                                  float* __restrict__ csave, int T, int prio) {
-    if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (ss_tune("small_prio"))
+    if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (SMALL_PRIO)
     static_assert(4 * H <= 64, "one wave");
     constexpr int OS = lstm_small_ld(H);
     extern __shared__ __attribute__((aligned(16))) float dyn[];
@@ -280,7 +280,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_bwd_lds_
                                                                                        const float* __restrict__ whh_b,
                                                                                        const float* __restrict__ d_out,
                                                                                        const float* __restrict__ csave, int T, int prio) {
-    if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (ss_tune("small_prio"))
+    if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (SMALL_PRIO)
     constexpr int NT = 4 * H > 64 ? 4 * H : 64;
     constexpr int OS = lstm_small_ld(H);
     extern __shared__ __attribute__((aligned(16))) float dyn[];
@@ -377,17 +377,17 @@ hipError_t fwd_t(float* gates, const float* wf, const float* wb, float* out, flo
         if (g_small_lds == 1 && bytes <= LDS_BUDGET) {
             hipError_t e = allow_lds(lstm_small_fwd_wave_kernel<H>, bytes);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((lstm_small_fwd_wave_kernel<H>), dim3(B, 2), dim3(64), bytes, s, gates, wf, wb, out, csave, T, g_small_prio);
+            hipLaunchKernelGGL((lstm_small_fwd_wave_kernel<H>), dim3(B, 2), dim3(64), bytes, s, gates, wf, wb, out, csave, T, SMALL_PRIO);
             return hipGetLastError();
         }
     }
     if (g_small_lds && bytes <= LDS_BUDGET) {
         hipError_t e = allow_lds(lstm_small_fwd_lds_kernel<H>, bytes);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((lstm_small_fwd_lds_kernel<H>), dim3(B, 2), dim3(NT), bytes, s, gates, wf, wb, out, csave, T, g_small_prio);
+        hipLaunchKernelGGL((lstm_small_fwd_lds_kernel<H>), dim3(B, 2), dim3(NT), bytes, s, gates, wf, wb, out, csave, T, SMALL_PRIO);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((lstm_small_fwd_kernel<H>), dim3(B, 2), dim3(NT), 0, s, gates, wf, wb, out, csave, T, g_small_prio);
+    hipLaunchKernelGGL((lstm_small_fwd_kernel<H>), dim3(B, 2), dim3(NT), 0, s, gates, wf, wb, out, csave, T, SMALL_PRIO);
     return hipGetLastError();
 }
 template <int H>
@@ -398,10 +398,10 @@ hipError_t bwd_t(float* gates, const float* wf, const float* wb, const float* d_
     if (g_small_lds && bytes <= LDS_BUDGET) {
         hipError_t e = allow_lds(lstm_small_bwd_lds_kernel<H>, bytes);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((lstm_small_bwd_lds_kernel<H>), dim3(B, 2), dim3(NT), bytes, s, gates, wf, wb, d_out, csave, T, g_small_prio);
+        hipLaunchKernelGGL((lstm_small_bwd_lds_kernel<H>), dim3(B, 2), dim3(NT), bytes, s, gates, wf, wb, d_out, csave, T, SMALL_PRIO);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((lstm_small_bwd_kernel<H>), dim3(B, 2), dim3(NT), 0, s, gates, wf, wb, d_out, csave, T, g_small_prio);
+    hipLaunchKernelGGL((lstm_small_bwd_kernel<H>), dim3(B, 2), dim3(NT), 0, s, gates, wf, wb, d_out, csave, T, SMALL_PRIO);
     return hipGetLastError();
 }
 

@@ -257,9 +257,23 @@ def test_roofline_traffic_profile_matches_kernel_sources():
     assert dw and all(r['hbm_read_bytes'] > 0 and r['hbm_write_bytes'] > 0 for r in dw)
 
 
+# ss_tune's keys.  Retired: settled schedule experiments whose default became the only behaviour; ss_tune refuses them like any unknown key.
+# Kept: every key of the product library (the -DSS_DIAG build adds lstm_mode and gemm_diag), with its default value.
+RETIRED_TUNE_KEYS = ('img', 'img_mask', 'bf16_img_mask', 'img_batch', 'img_cfg', 'img_dw_cfg', 'img_dw_wgs', 'dw_wgs', 'conv_want', 'conv_small_old',
+                     'presplit', 'part_splitk', 'flat_rows', 'gemm_bk', 'seq_hi', 'seq_skip32', 'pack_one', 'trunk_indep', 'conv_par', 'prewarm',
+                     'batch_dirs', 'wgrad_fused', 'trunk_bwd_par', 'enc_t_first', 'early_join', 'unpack_later', 'adam_early', 'split', 'exp',
+                     'side_prio', 'branch_low', 'small_prio', 'seq_wlead', 'gn_part')
+KEPT_TUNE_KEYS = {'persist': 1, 'gemm_mode': 1, 'fwd_f16x2': 1, 'bwd_f16x2': 1, 'deterministic': 0, 'seq_spin_log2': 18, 'seq_tag': 1, 'seq_var': 2,
+                  'img_xcc': 0, 'small_lds': 1, 'defer_dw': 1, 'dx_batched': 2, 'gemm_tr': 1, 'compact0': 1, 'gn_gather': 1, 'xcd_dw': 0, 'early_dw': 0,
+                  'dec_tail_split': 9, 'conv_dw_off': 1, 'dp_model': 0, 'dp_emulate': 0, 'dp_buckets': 1, 'bf16_img': 1, 'overlap': 1,
+                  'op_time_major': 0, 'own_streams': 0, 'prio_order': 1, 'probe_queues': 1, 'gemm_want': 1024, 'gemm_ws': 0, 'lstm_nw': 16,
+                  'lstm_g': 0, 'seq_prio': 1}
+
+
 def test_ss_tune_env_hook_applies_knobs_at_load():
     """SS_TUNE="key=value,..." is applied once when the library is loaded (A/B runs of tests and tools); an unknown key is an error, not a silently
-    ignored typo.  (ss_tune only sets process-global knobs: no GPU needed.)"""
+    ignored typo.  Every retired key is such an unknown key, every kept key accepts its default.  (ss_tune only sets process-global knobs: no
+    GPU needed.)"""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -268,3 +282,14 @@ def test_ss_tune_env_hook_applies_knobs_at_load():
     assert ok.returncode == 0 and 'loaded' in ok.stdout, ok.stderr[-500:]
     bad = subprocess.run([sys.executable, '-c', code], cwd=root, env=dict(os.environ, SS_TUNE='no_such_knob=1'), capture_output=True, text=True)
     assert bad.returncode != 0 and 'SS_TUNE' in bad.stderr and 'unknown key' in bad.stderr
+    assert len(RETIRED_TUNE_KEYS) == 34 and len(KEPT_TUNE_KEYS) == 33 and not set(RETIRED_TUNE_KEYS) & set(KEPT_TUNE_KEYS)
+    code = ('from speechsplit_amd import _capi; lib = _capi.lib()\n'
+            f'for k in {RETIRED_TUNE_KEYS!r}:\n'
+            '    for v in (0, 1):\n'
+            '        assert lib.ss_tune(k.encode(), v) != 0 and "unknown key" in lib.ss_last_error().decode(), ("retired key accepted", k, v)\n'
+            f'for k, v in {KEPT_TUNE_KEYS!r}.items():\n'
+            '    assert lib.ss_tune(k.encode(), v) == 0, ("kept key refused at its default", k, v, lib.ss_last_error().decode())\n'
+            'print("keys ok")')
+    env = {k: v for k, v in os.environ.items() if k not in ('SS_TUNE', 'SS_DIAG_LIB')}
+    keys = subprocess.run([sys.executable, '-c', code], cwd=root, env=env, capture_output=True, text=True)
+    assert keys.returncode == 0 and 'keys ok' in keys.stdout, keys.stderr[-800:]
