@@ -183,6 +183,30 @@ int ss_set_adam(ss_engine* e, double lr, double beta1, double beta2, double eps,
 int ss_adam_step(ss_engine* e, float grad_scale, void* stream);
 int ss_zero_grads(ss_engine* e, void* stream);
 
+/* ---- clipping by global norm, and refusing non-finite gradients (nothing to mirror: the reference's solver never clips; the semantics are
+ *      those of torch.nn.utils.clip_grad_norm_(G.parameters(), max_norm), norm_type 2, placed between backward and optimizer.step()) ----
+ * ss_set_grad_clip: max_norm 0 = off (the default; every step is then enqueued exactly as without this call), > 0 = every optimiser step
+ *   scales the gradients by coef = min(1, max_norm / (norm + 1e-6)), +inf = measure and guard only (coef is exactly 1).  Negative or NaN is
+ *   refused with nothing enqueued, as is an engine that is not bound.  Resets the two counters of ss_grad_clip_stats.  ss_bind switches it off.
+ *   The norm is grad_scale * the 2-norm of the PARAMETER elements of the gradient arena: the alignment gaps between tensors (behind the 257-float
+ *   head bias) and the status slot in the arena's last four floats are never read, so a caller need not zero them.  Under data parallelism it is
+ *   the norm of the ALL-REDUCED arena with the 1/world mean folded in through grad_scale: every rank computes the same coefficient.  float64 sums,
+ *   one partial per workgroup added in a fixed order, no atomics: the same bits on every run and on every route to the optimiser (fused step,
+ *   SS_STEP_NO_ADAM + ss_adam_step, ss_train_finish, SS_STEP_BUCKET, both data-parallel steps, both generators, both precisions).  Everything
+ *   stays on the device; the fused one-GPU step sums the decoder + head range beside the encoder backward where it otherwise updates that range
+ *   early, and updates the whole arena in one launch once the norm is known.
+ *   SKIP: a norm that is not finite (one inf or NaN anywhere among the parameter elements) skips THAT optimiser step on the device -- parameters,
+ *   both moments and the step counter untouched, exactly as for the status word -- but unlike the status word it is per step: no status bit is
+ *   set, nothing is refused afterwards, and the next step runs normally.  The skipped counter is how a caller learns of it.
+ * ss_grad_norm: stand-alone, *norm_dev = grad_scale * that norm of the arena as it is now (one device float); works whether or not clipping is on
+ *   and changes neither the clip state nor the counters.
+ * ss_grad_clip_stats: asynchronous device-to-device copy of four floats {norm of the last optimiser step before clipping, coefficient applied
+ *   (0: the step was skipped), optimiser steps clipped (coef < 1), optimiser steps skipped as non-finite} since ss_set_grad_clip.  No
+ *   synchronisation: read it the way the loss is read.  (The counters are floats: exact up to 2^24 steps.) */
+int ss_set_grad_clip(ss_engine* e, float max_norm, void* stream);
+int ss_grad_norm(ss_engine* e, float grad_scale, float* norm_dev, void* stream);
+int ss_grad_clip_stats(ss_engine* e, float* out4_dev, void* stream);
+
 /* ---- InterpLnr as a standalone module (model.py:355-436; solver.py:59,161) ---- */
 /* x [B,T,C], len_seq i32[B], draws [B*7] -> y [B,max_len_pad,C].  Optional outputs (may be NULL): i0 i32[B,P],
  * lam f32[B,P], counts i32[B] (un-truncated, model.py:418). */

@@ -59,6 +59,9 @@ SYMBOLS = {
     'ss_set_adam': (_i, [_vp, _d, _d, _d, _d, _l, _vp]),
     'ss_adam_step': (_i, [_vp, _f, _vp]),
     'ss_zero_grads': (_i, [_vp, _vp]),
+    'ss_set_grad_clip': (_i, [_vp, _f, _vp]),
+    'ss_grad_norm': (_i, [_vp, _f, _fp, _vp]),
+    'ss_grad_clip_stats': (_i, [_vp, _fp, _vp]),
     'ss_interp_forward': (_i, [_vp, _fp, _ip, _fp, _ip, _i, _i, _i, _fp, _ip, _fp, _ip, _vp]),
     'ss_interp_backward': (_i, [_vp, _fp, _i, _i, _i, _fp, _vp]),
     'ss_check': (_i, [_vp, _vp]),

@@ -879,10 +879,13 @@ __global__ void adam_prepare_kernel(AdamState* st, unsigned* sticky, const float
     st->f_eps = (float)st->eps;
 }
 
+// CLIP: the gradient is also multiplied by the clip coefficient adam_prepare_clip_kernel left in device memory (exactly 1.0f: the same bits)
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, long n4,
-                                                   const AdamState* __restrict__ st, float gscale) {
+                                                   const AdamState* __restrict__ st, float gscale, const float* __restrict__ coef_p) {
     if (st->skip) return;
+    const float coef = CLIP ? *coef_p : 1.0f;
     const float step_size = st->step_size, bc2s = st->bc2_sqrt, b1 = st->f_beta1, b2 = st->f_beta2, eps = st->f_eps;
     const float w1 = (float)(1.0 - st->beta1), w2 = (float)(1.0 - st->beta2);
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
@@ -892,7 +895,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float gg = gv[j] * gscale;
+            const float gg = CLIP ? (gv[j] * gscale) * coef : gv[j] * gscale;
             mv[j] = mv[j] + w1 * (gg - mv[j]);
             vv[j] = vv[j] * b2 + w2 * gg * gg;
             const float denom = sqrtf(vv[j]) / bc2s + eps;
@@ -903,6 +906,94 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         reinterpret_cast<f32x4*>(m)[i] = mv;
         reinterpret_cast<f32x4*>(v)[i] = vv;
     }
+}
+
+// ------------------------------------------------------------------------------------------------ gradient norm / clipping
+// 256 float64 values -> their sum in every thread's view of red[0]: butterfly inside each wavefront, then the four wave sums in index
+// order -- a fixed tree, the same bits on every run
+__device__ __forceinline__ double block_sum_f64(double x, double* red) {
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// Per-workgroup float64 sum of squares of the parameter elements of g inside [lo, hi) (GradSegTable: the arena's runs of parameter
+// elements, so alignment gaps and the status slot are never read).  HBM-bound: one 16-byte load per thread and iteration, the squares
+// exact in float64.  The table rides in the kernel arguments: run bounds are wave-uniform scalar loads.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, const GradSegTable tb, long lo, long hi,
+                                                         double* __restrict__ partials) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int k = 0; k < tb.n; ++k) {
+        const long a = tb.start[k] > lo ? tb.start[k] : lo;
+        const long end = tb.start[k] + tb.len[k];
+        const long b = end < hi ? end : hi;
+        if (b <= a) continue;
+        const long n4 = (b - a) >> 2;
+        const f32x4* g4 = reinterpret_cast<const f32x4*>(g + a);
+        for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+            const f32x4 x = g4[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = fma((double)x[j], (double)x[j], acc);
+        }
+        // the run's last 1..3 elements when it does not end on a float4 boundary (the floats behind them are a gap: not read)
+        const long t = a + 4 * n4 + threadIdx.x;
+        if (blockIdx.x == 0 && t < b) acc = fma((double)g[t], (double)g[t], acc);
+    }
+    const double tot = block_sum_f64(acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+}
+
+// sum of n partials in a fixed order: thread t adds partials t, t + 256, .. in index order, then the block tree
+__device__ __forceinline__ double partials_sum(const double* __restrict__ partials, int n, double* red) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += partials[i];
+    return block_sum_f64(acc, red);
+}
+
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ partials, int n, float gscale, float* __restrict__ out) {
+    __shared__ double red[4];
+    const double tot = partials_sum(partials, n, red);
+    if (threadIdx.x == 0) *out = (float)((double)gscale * sqrt(tot));
+}
+
+// adam_prepare_kernel with the global norm in front (one workgroup; thread 0 does what adam_prepare_kernel's only thread does)
+__global__ __launch_bounds__(256) void adam_prepare_clip_kernel(AdamState* st, ClipState* clip, unsigned* sticky, const float* status,
+                                                                const double* __restrict__ partials, int n, float gscale, float max_norm) {
+    __shared__ double red[4];
+    const double tot = partials_sum(partials, n, red);
+    if (threadIdx.x != 0) return;
+    const float norm = (float)((double)gscale * sqrt(tot));
+    clip->norm = norm;
+    const unsigned mine = sticky ? __hip_atomic_load(sticky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
+    const bool remote = status && *status != 0.f;
+    if (mine || remote) {          // as adam_prepare_kernel: the status word wins, and stays
+        st->skip = 1u;
+        clip->coef = 0.f;
+        if (remote && sticky && !(mine & SS_STICKY_ABORT)) __hip_atomic_fetch_or(sticky, SS_STICKY_REMOTE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        return;
+    }
+    if (!(fabsf(norm) <= 3.402823466e+38f)) {      // inf or NaN somewhere in the arena: this step only -- the status word is left alone
+        st->skip = 1u;
+        clip->coef = 0.f;
+        clip->skipped += 1.f;
+        return;
+    }
+    // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1 (max_norm = +inf: exactly 1)
+    const float coef = fminf(1.0f, max_norm / (norm + 1e-6f));
+    clip->coef = coef;
+    if (coef < 1.0f) clip->clipped += 1.f;
+    st->skip = 0u;
+    st->step += 1;
+    const double t = (double)st->step;
+    const double bc1 = 1.0 - pow(st->beta1, t);
+    const double bc2 = 1.0 - pow(st->beta2, t);
+    st->step_size = (float)(st->lr / bc1);
+    st->bc2_sqrt = (float)sqrt(bc2);
+    st->f_beta1 = (float)st->beta1;
+    st->f_beta2 = (float)st->beta2;
+    st->f_eps = (float)st->eps;
 }
 
 }  // namespace
@@ -1202,7 +1293,31 @@ hipError_t adam_range(float* p, const float* g, float* m, float* v, long n, Adam
     if (n == 0) return hipSuccess;
     long blocks = (n / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adam_kernel, dim3((int)blocks), dim3(256), 0, s, p, g, m, v, n / 4, st, grad_scale);
+    hipLaunchKernelGGL(adam_kernel<false>, dim3((int)blocks), dim3(256), 0, s, p, g, m, v, n / 4, st, grad_scale, (const float*)nullptr);
+    return hipGetLastError();
+}
+hipError_t adam_range_clip(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, const float* coef,
+                           hipStream_t s) {
+    if (!coef || n % 4 != 0 || (((size_t)p | (size_t)g | (size_t)m | (size_t)v) & 15)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    long blocks = (n / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(adam_kernel<true>, dim3((int)blocks), dim3(256), 0, s, p, g, m, v, n / 4, st, grad_scale, coef);
+    return hipGetLastError();
+}
+
+hipError_t grad_sumsq(const float* g, const GradSegTable& tb, long lo, long hi, double* partials, hipStream_t s) {
+    if (lo % 4 != 0 || hi < lo || ((size_t)g & 15) || tb.n < 0 || tb.n > GRAD_SEG_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(grad_sumsq_wgs(hi - lo)), dim3(256), 0, s, g, tb, lo, hi, partials);
+    return hipGetLastError();
+}
+hipError_t grad_norm_finish(const double* partials, int n, float grad_scale, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, s, partials, n, grad_scale, out);
+    return hipGetLastError();
+}
+hipError_t adam_prepare_clip(AdamState* st, ClipState* clip, unsigned* sticky, const float* status, const double* partials, int n,
+                             float grad_scale, float max_norm, hipStream_t s) {
+    hipLaunchKernelGGL(adam_prepare_clip_kernel, dim3(1), dim3(256), 0, s, st, clip, sticky, status, partials, n, grad_scale, max_norm);
     return hipGetLastError();
 }
 

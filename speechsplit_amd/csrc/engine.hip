@@ -248,6 +248,15 @@ struct ss_engine {
     bool adam_early = false;               // this step wants it (set by the fused train steps)
     float adam_early_gs = 1.0f;
     long adam_early_from = -1;             // >= 0: the range [adam_early_from, arena) has been enqueued, the step state prepared
+    // Clipping by global norm (ss_set_grad_clip): the norm needs the whole arena before the first element is updated, so the early range
+    // sends the PARTIAL SUMS of its squares to the side stream instead of its update; adam_enqueue adds the encoder range's, finalises
+    // (norm, coefficient, skip) and updates the arena in one launch.  Partials: [0, wgs(split)) encoder range, then the decoder + head range.
+    float clip_max = 0.0f;                 // 0 off, > 0 clip to this norm, +inf measure and refuse non-finite gradients only
+    long clip_early_from = -1;             // >= 0: the partials of [clip_early_from, status_off) have been enqueued (side stream) in this step
+    ClipState* clip = nullptr;             // workspace byte 128, beside the Adam state
+    double* clip_part = nullptr;
+    GradSegTable segs{};                   // runs of parameter elements of the arena (build_table)
+    bool segs_ok = false;
     bool prezero = false;                  // fused training step: zero the gradient arena on a branch stream during the forward
     bool grads_zeroed = false;             // ... done: backward_decoder must not zero it again
     bool bwd_sync_zeroed = false;          // the same for the backward recurrences' sync words / exchange tiles and the work-queue words
@@ -414,6 +423,20 @@ void build_table(ss_engine* e) {
     e->ld.amax0 = 0;                      // decoder layers: slots 0..2 of ss_engine::amax (the convs follow from 3)
     e->status_off = align4(tb.off);
     e->arena = e->status_off + 4;
+    // runs of parameter elements (grad_sumsq): tensors that follow each other without an alignment gap merge into one run
+    e->segs.n = 0;
+    e->segs_ok = true;
+    for (const ParamInfo& p : e->params) {
+        GradSegTable& g = e->segs;
+        if (g.n && g.start[g.n - 1] + g.len[g.n - 1] == p.offset && (long)g.len[g.n - 1] + p.numel() < (1L << 31)) {
+            g.len[g.n - 1] += (int)p.numel();
+        } else if (g.n < GRAD_SEG_MAX && p.numel() < (1L << 31)) {
+            g.start[g.n] = p.offset;
+            g.len[g.n++] = (int)p.numel();
+        } else {
+            e->segs_ok = false;
+        }
+    }
     e->f0p = (int)((h.dim_f0 + 7) & ~7);      // a multiple of 8: the packed conv weights of convolutions_2[0] then have rows of whole image groups
     for (int i = 0; i < 3; ++i) {
         e->c1[i].need_dx = i > 0;
@@ -490,6 +513,8 @@ long ss_engine::carve(int B, int T, bool assign) {
         }
     };
     adam = (AdamState*)take(sizeof(AdamState));        // first: survives geometry changes (offset 0)
+    clip = assign ? (ClipState*)((char*)adam + CLIP_STATE_BYTE) : nullptr;      // same 256 bytes
+    if (kind != SS_INTERP_ONLY) clip_part = (double*)take(2L * GRAD_SUMSQ_MAX_WGS * sizeof(double));     // scratch, geometry-independent (offset 256)
     if (kind == SS_INTERP_ONLY) {                      // a bare InterpLnr module only needs one plan
         for (int i = 0; i < 4; ++i) {
             plan[i].S = hp.max_len_seq / hp.min_len_seg + 1;
@@ -752,6 +777,13 @@ bool colsum_scratch(ss_engine* e, int cols, double** part, unsigned** ctr) {
 
 int prof_begin(ss_engine* e, int klass, hipStream_t st, double flops);
 void prof_end(ss_engine* e, int i, hipStream_t st);
+// gradient norm (ss_set_grad_clip / ss_grad_norm): the arena is summed as [0, split) and [split, status_off), split = ss_grad_split when
+// that is a float4 boundary -- the same two ranges on every route, so the norm has the same bits on every route
+long clip_split(const ss_engine* e) {
+    const long k = ss_grad_split(e);
+    return (k % 4 == 0 && k > 0 && k < e->status_off) ? k : 0;
+}
+int clip_wgs_lo(const ss_engine* e) { return clip_split(e) > 0 ? grad_sumsq_wgs(clip_split(e)) : 0; }
 
 // launch the pending encoder-BLSTM weight-gradient tasks (one kernel for all of them) on `st`: everything they read must be complete in
 // st's order.  Scratch: partial tiles from the step's bump allocator, arrival counters from the column sums' ring.
@@ -2168,7 +2200,16 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
             if (e->adam_early && !e->dp_on && e->Mm && e->Vv) {
                 // every persistent recurrence and the parameter guard ran before the event this stream waited for: the status word is final
                 const long from = ss_grad_split(e);
-                if (from % 4 == 0 && from < e->arena) {
+                if (e->clip_max > 0.0f) {
+                    // clipping: no element may be updated before the norm of the whole arena is known -- this range's share of the sum
+                    // of squares takes the early update's place beside the encoder backward (adam_enqueue finalises)
+                    if (from == clip_split(e)) {
+                        { const int pa_ = prof_begin(e, SS_PROF_ADAM, e->side, 0.0);
+                        HIPCHK(grad_sumsq(e->G, e->segs, from, e->status_off, e->clip_part + clip_wgs_lo(e), e->side));
+                        prof_end(e, pa_, e->side); }
+                        e->clip_early_from = from;
+                    }
+                } else if (from % 4 == 0 && from < e->arena) {
                     HIPCHK(adam_prepare(e->adam, e->sticky, nullptr, e->side));
                     { const int pa_ = prof_begin(e, SS_PROF_ADAM, e->side, 0.0);
                     HIPCHK(adam_range(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, e->adam_early_gs, e->side));
@@ -2459,6 +2500,8 @@ long ss_plan_bytes(const ss_engine* e, int B, int T) {
 }
 
 static_assert(sizeof(AdamState) <= 256, "the Adam state is the workspace's first 256 bytes");
+static_assert(sizeof(AdamState) <= CLIP_STATE_BYTE && CLIP_STATE_BYTE + sizeof(ClipState) <= 256 && CLIP_STATE_BYTE % 16 == 0,
+              "the clip state shares those 256 bytes (ss_set_adam rewrites sizeof(AdamState) of them, no more)");
 int ss_set_workspace(ss_engine* e, void* ws_dev, long bytes, void* stream) {
     if (!e || !e->ws) return fail("ss_set_workspace: engine is not bound (call ss_bind first)");
     if (!ws_dev || ((uintptr_t)ws_dev & 255)) return fail("ss_set_workspace: the workspace must be 256-byte aligned");
@@ -2528,6 +2571,8 @@ int ss_bind(ss_engine* e, float* params, float* grads, float* m, float* v, void*
         for (auto& ev : e->ev_dec) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         for (auto& ev : e->ev_join) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
+    e->clip_max = 0.0f;       // the workspace (clip state included) starts zero: clipping is off until ss_set_grad_clip
+    e->clip_early_from = -1;
     AdamState st{};
     st.lr = 1e-4;
     st.beta1 = 0.9;
@@ -2552,10 +2597,36 @@ int ss_set_adam(ss_engine* e, double lr, double b1, double b2, double eps, long 
     return 0;
 }
 
+// partial sums of the squared gradients the norm still needs on stream s ([split, status_off) unless have_hi says they are there), SS_PROF_ADAM;
+// returns the number of partials through *n
+static int grad_norm_partials(ss_engine* e, bool have_hi, hipStream_t s, int* n) {
+    if (!e->segs_ok) return fail("gradient norm: the parameter table has more runs than GRAD_SEG_MAX");
+    const long k = clip_split(e);
+    const int nlo = clip_wgs_lo(e);
+    { const int pa_ = prof_begin(e, SS_PROF_ADAM, s, 0.0);
+    if (k > 0) HIPCHK(grad_sumsq(e->G, e->segs, 0, k, e->clip_part, s));
+    if (!have_hi) HIPCHK(grad_sumsq(e->G, e->segs, k, e->status_off, e->clip_part + nlo, s));
+    prof_end(e, pa_, s); }
+    *n = nlo + grad_sumsq_wgs(e->status_off - k);
+    return 0;
+}
+
 // enqueue only: the host-side status check belongs to the ABI entry points, never to the middle of a step being enqueued
 // (the device-side guard in adam_prepare_kernel is what protects the parameters)
 static int adam_enqueue(ss_engine* e, float grad_scale, hipStream_t s) {
     if (!e->ws || !e->Mm || !e->Vv) return fail("ss_adam_step: Adam arenas are not bound");
+    if (e->clip_max > 0.0f) {              // global norm over the whole (all-reduced) arena, then ONE update launch with the coefficient
+        const bool have_hi = e->clip_early_from >= 0 && e->clip_early_from == clip_split(e);
+        e->clip_early_from = -1;
+        e->adam_early_from = -1;
+        int n = 0;
+        CHK(grad_norm_partials(e, have_hi, s, &n));
+        { const int pa_ = prof_begin(e, SS_PROF_ADAM, s, 0.0);
+        HIPCHK(adam_prepare_clip(e->adam, e->clip, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s));
+        HIPCHK(adam_range_clip(e->P, e->G, e->Mm, e->Vv, e->arena, e->adam, grad_scale, &e->clip->coef, s));
+        prof_end(e, pa_, s); }
+        return 0;
+    }
     if (e->adam_early_from >= 0) {         // the decoder + head range went out beside the encoder backward (backward_encoder): the rest, same step state
         const long n = e->adam_early_from;
         e->adam_early_from = -1;
@@ -2576,6 +2647,7 @@ struct AdamEarly {
         e->adam_early = on;
         e->adam_early_gs = gs;
         e->adam_early_from = -1;
+        e->clip_early_from = -1;
     }
     // A step that returns with an error behind the early range (decoder + head already updated on the side stream) must not leave the field
     // set: a later ss_adam_step would then update [0, from) only, with that step's prepared state.  The failed step's partial update stands
@@ -2583,14 +2655,49 @@ struct AdamEarly {
     ~AdamEarly() {
         e->adam_early = false;
         e->adam_early_from = -1;
+        e->clip_early_from = -1;
     }
 };
 
 int ss_adam_step(ss_engine* e, float grad_scale, void* stream) {
     CHK(entry_check(e));
     e->adam_early_from = -1;               // a stand-alone optimiser step always covers the whole arena
+    e->clip_early_from = -1;
     Own own(e, stream);
     return adam_enqueue(e, grad_scale, own.s);
+}
+
+int ss_set_grad_clip(ss_engine* e, float max_norm, void* stream) {
+    if (!e) return fail("ss_set_grad_clip: null engine");
+    if (!(max_norm >= 0.0f)) return fail("ss_set_grad_clip: max_norm must be 0 (off), positive or +inf; negative and NaN are refused");
+    if (e->kind == SS_INTERP_ONLY) return fail("ss_set_grad_clip: an InterpLnr-only engine has no gradient arena");
+    if (!e->ws || !e->G) return fail("ss_set_grad_clip: engine is not bound (call ss_bind first)");
+    if (!e->segs_ok) return fail("ss_set_grad_clip: the parameter table has more runs than GRAD_SEG_MAX");
+    Own own(e, stream);
+    HIPCHK(hipMemsetAsync(e->clip, 0, sizeof(ClipState), own.s));      // norm, coefficient and both counters start again
+    e->clip_max = max_norm;
+    e->clip_early_from = -1;
+    return 0;
+}
+
+int ss_grad_norm(ss_engine* e, float grad_scale, float* norm_dev, void* stream) {
+    if (!e || !norm_dev) return fail("ss_grad_norm: null pointer");
+    if (e->kind == SS_INTERP_ONLY || !e->ws || !e->G) return fail("ss_grad_norm: engine is not bound (call ss_bind first)");
+    Own own(e, stream);
+    int n = 0;
+    CHK(grad_norm_partials(e, false, own.s, &n));
+    { const int pa_ = prof_begin(e, SS_PROF_ADAM, own.s, 0.0);
+    HIPCHK(grad_norm_finish(e->clip_part, n, grad_scale, norm_dev, own.s));
+    prof_end(e, pa_, own.s); }
+    return 0;
+}
+
+int ss_grad_clip_stats(ss_engine* e, float* out4_dev, void* stream) {
+    if (!e || !out4_dev) return fail("ss_grad_clip_stats: null pointer");
+    if (e->kind == SS_INTERP_ONLY || !e->ws) return fail("ss_grad_clip_stats: engine is not bound (call ss_bind first)");
+    Own own(e, stream);
+    HIPCHK(hipMemcpyAsync(out4_dev, e->clip, sizeof(ClipState), hipMemcpyDeviceToDevice, own.s));
+    return 0;
 }
 
 int ss_zero_grads(ss_engine* e, void* stream) {

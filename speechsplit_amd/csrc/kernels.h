@@ -159,6 +159,43 @@ hipError_t adam_prepare(AdamState* st, unsigned* sticky, const float* status, hi
 hipError_t adam_range(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, hipStream_t s);
 hipError_t adam_step(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, unsigned* sticky,
                      const float* status, hipStream_t s);
+// ---- gradient clipping by global norm (torch.nn.utils.clip_grad_norm_, norm_type 2; no statement of the reference: its solver never clips)
+// Device-resident beside AdamState in the workspace's first 256 bytes (byte 128), so it survives what the Adam state survives.
+struct ClipState {
+    float norm;           // grad_scale * ||g|| of the last optimiser step, BEFORE clipping (parameter elements only)
+    float coef;           // min(1, max_norm / (norm + 1e-6)) that step applied; 0 when it was skipped as non-finite
+    float clipped;        // optimiser steps with coef < 1 since ss_set_grad_clip   (floats: the four words are handed out as one float4;
+    float skipped;        // optimiser steps skipped because the norm was not finite   exact up to 2^24 steps)
+};
+constexpr long CLIP_STATE_BYTE = 128;
+// The runs of PARAMETER elements of the arena: neighbouring tensors without an alignment gap between them are one run.  Every start is
+// a multiple of 4 floats; the gaps behind tensors whose element count is not (the 257-float head bias) and the status slot are in no run.
+constexpr int GRAD_SEG_MAX = 96;
+struct GradSegTable {
+    int n;
+    int len[GRAD_SEG_MAX];
+    long start[GRAD_SEG_MAX];
+};
+// Workgroups (= float64 partials) of one grad_sumsq launch over n floats: a function of n alone, so every schedule that splits the
+// arena at the same offsets adds the same partials in the same order.
+constexpr int GRAD_SUMSQ_MAX_WGS = 512;
+inline int grad_sumsq_wgs(long n) {
+    const long w = (n / 4 + 2047) / 2048;            // >= 8 float4 per thread before a second workgroup is worth its launch slot
+    return (int)(w < 1 ? 1 : (w > GRAD_SUMSQ_MAX_WGS ? GRAD_SUMSQ_MAX_WGS : w));
+}
+// partials[0 .. grad_sumsq_wgs(hi - lo)) = per-workgroup float64 sums of g[i]^2 over the table's elements inside [lo, hi)
+// (lo a multiple of 4; float4 loads, grid-stride, no atomics)
+hipError_t grad_sumsq(const float* g, const GradSegTable& tb, long lo, long hi, double* partials, hipStream_t s);
+// *out = grad_scale * sqrt(partials[0] + .. + partials[n - 1])   (one workgroup, fixed order)
+hipError_t grad_norm_finish(const double* partials, int n, float grad_scale, float* out, hipStream_t s);
+// adam_prepare with the clip in front: norm as grad_norm_finish into clip->norm, clip->coef = min(1, max_norm / (norm + 1e-6)).
+// A norm that is not finite sets st->skip for THIS step only (parameters, moments, step counter untouched; clip->skipped + 1; neither
+// sticky nor the status slot is set); the sticky / status skip of adam_prepare comes first and counts as neither.
+hipError_t adam_prepare_clip(AdamState* st, ClipState* clip, unsigned* sticky, const float* status, const double* partials, int n,
+                             float grad_scale, float max_norm, hipStream_t s);
+// adam_range with g * grad_scale * *coef (a coefficient of exactly 1.0f gives adam_range's bits)
+hipError_t adam_range_clip(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, const float* coef,
+                           hipStream_t s);
 // *status = (*sticky != 0)   (one thread; enqueued behind the decoder's recurrences, in front of the all-reduce that sums it)
 hipError_t status_publish(const unsigned* sticky, float* status, hipStream_t s);
 // Scale of the fp16 x 2 split for the OUTPUT of each conv block (GroupNorm + ReLU, then resampled: a convex combination), from its affine

@@ -385,6 +385,25 @@ class Engine:
     def adam_step(self, grad_scale=1.0):
         _capi.check(self.lib.ss_adam_step(self.h, float(grad_scale), _stream()))
 
+    def set_grad_clip(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_(parameters, max_norm) inside every optimiser step of this engine, on the device (ss_set_grad_clip):
+        None / 0 off (default), > 0 clip to that global norm, inf measure only.  With it on, a step whose gradient norm is not finite is
+        skipped (parameters, moments and step counter untouched) and counted; the counters of grad_clip_stats() start again."""
+        _capi.check(self.lib.ss_set_grad_clip(self.h, float(max_norm or 0.0), _stream()))
+
+    def grad_norm(self, grad_scale=1.0):
+        """grad_scale * 2-norm of the parameter elements of the gradient arena as it is now: a one-element device tensor (ss_grad_norm)."""
+        out = self._new('grad_norm', (1,))
+        _capi.check(self.lib.ss_grad_norm(self.h, float(grad_scale), _ptr(out), _stream()))
+        return out
+
+    def grad_clip_stats(self):
+        """Device tensor [4], no synchronisation (ss_grad_clip_stats): norm of the last optimiser step before clipping, coefficient applied
+        (0: skipped), optimiser steps clipped, optimiser steps skipped as non-finite -- the counts since set_grad_clip."""
+        out = self._new('grad_clip_stats', (4,))
+        _capi.check(self.lib.ss_grad_clip_stats(self.h, _ptr(out), _stream()))
+        return out
+
     def check(self):
         """Synchronise and raise if a kernel reported an asynchronous failure."""
         _capi.check(self.lib.ss_check(self.h, _stream()))

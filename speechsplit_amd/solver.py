@@ -44,6 +44,13 @@ class Solver(object):
         if self.dp_backend not in ('native', 'torch'):
             raise ValueError("dp_backend must be 'native' or 'torch', got {!r}".format(self.dp_backend))
         self.dp_schedule = getattr(config, 'dp_schedule', None) or os.environ.get('SS_DP_SCHEDULE', 'overlap')
+        # clip_grad_norm_(G.parameters(), grad_clip) between backward and optimizer.step(), inside the engine's step (Engine.set_grad_clip):
+        # config.grad_clip, or -- for the unchanged main.py, whose config has no such attribute -- SS_GRAD_CLIP.  None / 0: no clipping, no norm,
+        # the reference's log line; 'inf': no clipping, but the norm is logged and a step with non-finite gradients is skipped.
+        clip = getattr(config, 'grad_clip', None) if hasattr(config, 'grad_clip') else (os.environ.get('SS_GRAD_CLIP') or None)
+        self.grad_clip = float(clip) if clip is not None else 0.0
+        if not self.grad_clip >= 0.0:
+            raise ValueError('grad_clip must be 0 / None (off), positive or inf, got {!r}'.format(clip))
         self.use_cuda = torch.cuda.is_available()
         if not self.use_cuda:
             raise RuntimeError('speechsplit_amd.Solver needs a ROCm GPU (the engine has no CPU fallback)')
@@ -69,6 +76,8 @@ class Solver(object):
         self.eng = self.G._eng
         self.eng.set_adam(self.g_lr, self.beta1, self.beta2, 1e-8, 0)      # solver.py:62
         self.step_count = 0
+        if self.grad_clip:
+            self.eng.set_grad_clip(self.grad_clip)
         if self.world > 1:
             _dist.init('nccl', self.device)
             import torch.distributed as dist
@@ -198,17 +207,25 @@ class Solver(object):
         # (non-blocking) and the line is printed once that copy has landed -- an iteration or two later, same text, same order.  A blocking
         # .item() every log_step iterations left the GPU waiting for the host to enqueue the next step again: 0.2 ms per iteration at
         # log_step = 10 (bench.py solver_loop: 5.51 vs 5.29 ms for the bare step).
-        pending = []                                              # (copy-done event, pinned loss, iteration, elapsed text)
+        pending = []                                              # (copy-done event, pinned loss, iteration, elapsed text, pinned clip stats or None)
+        skipped_seen = 0
 
         def flush(block):
+            nonlocal skipped_seen
             while pending and (block or pending[0][0].query()):
-                ev, host_loss, it, et = pending.pop(0)
+                ev, host_loss, it, et, host_clip = pending.pop(0)
                 ev.synchronize()
                 if self.rank == 0:
                     log = "Elapsed [{}], Iteration [{}/{}]".format(et, it, self.num_iters)
                     for tag in keys:
                         log += ", {}: {:.8f}".format(tag, float(host_loss))
+                    if host_clip is not None:                     # {norm before clipping, coefficient, steps clipped, steps skipped}
+                        log += ", G/grad_norm: {:.8f}".format(float(host_clip[0]))
                     print(log)
+                    if host_clip is not None and int(host_clip[3]) > skipped_seen:
+                        print('Warning: {} optimiser step(s) skipped so far: their gradients were not finite (by iteration {})'.format(
+                            int(host_clip[3]), it))
+                        skipped_seen = int(host_clip[3])
 
         for i in range(start_iters, self.num_iters):
             batch = next(data_iter)
@@ -229,9 +246,13 @@ class Solver(object):
                     self.eng.check()                              # waiting in an earlier step has said so by now (raises)
                 host_loss = torch.empty((), dtype=torch.float32).pin_memory()
                 host_loss.copy_(t.reshape(()), non_blocking=True)
+                host_clip = None
+                if self.grad_clip:                                # the same pinned non-blocking copy as the loss
+                    host_clip = torch.empty(4, dtype=torch.float32).pin_memory()
+                    host_clip.copy_(self.eng.grad_clip_stats(), non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream(self.device))
-                pending.append((ev, host_loss, i + 1, str(datetime.timedelta(seconds=time.time() - start_time))[:-7]))
+                pending.append((ev, host_loss, i + 1, str(datetime.timedelta(seconds=time.time() - start_time))[:-7], host_clip))
             flush(self.world > 1)
             if (i + 1) % self.model_save_step == 0 and self.rank == 0:
                 flush(True)
