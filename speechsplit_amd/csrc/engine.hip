@@ -11,6 +11,7 @@
 #include <vector>
 #include <algorithm>
 #include <utility>
+#include <type_traits>
 #include <functional>
 #include <cstring>
 #include <cstdio>
@@ -35,7 +36,6 @@ int g_dp_emulate = 0;      // with dp_model = N: the stand-in collectives multip
 int g_dp_model = 0;        // > 1: MODEL a data-parallel run of that many ranks on one GPU: every collective is replaced by a stand-in kernel of
                            // the modelled duration (tools/dp_timeline.sh); no communicator needed
 int g_dp_buckets = 1;      // 1: per-layer gradient buckets on the communication stream; 0: round 2's two buckets
-int g_cur_klass = -1;      // profile class of the contraction being launched (set by the PGEMM macros)
 int g_bf16_img = 1;        // SS_PRECISION_BF16: the 16-bit data path (round 4) -- operand images are plain bf16 tensors written by their producers (weights,
                            // hidden states, resampled activations, pre-activation / conv-output gradients) and the contractions over them run on the
                            // single-piece form of the image GEMM; 0: round 3's bf16 mode (fp32 slabs, operands rounded inside the GEMM)
@@ -125,10 +125,8 @@ struct ConvBlk {
     int scale_i = -1;                      // slot in ss_engine::act_scale (scale of the fp16 x 2 split of this block's OUTPUT)
     bool need_dx = false;
     // input gradient w.r.t. the NETWORK input (layer-0 blocks, ss_g*_backward_inputs): wb0 holds the flipped taps [Ci][5][Co] (packed
-    // when asked); dx_out (null: not asked) receives it dense, row stride dx_ld, [B][T] rows -- set for one backward call only
+    // when asked; the target travels in that call's Backward)
     float* wb0 = nullptr;
-    float* dx_out = nullptr;
-    long dx_ld = 0;
     bool img_ok() const { return Cp % 8 == 0 && Co % 8 == 0; }       // wf_img / wb_img are written (rows of whole image groups)
 };
 
@@ -182,6 +180,48 @@ struct Slab {   // view of a haloed slab: p points at slab row 0, first channel 
     const float* scale = nullptr;    // device word: power-of-two scale of the fp16 x 2 split of this slab's values (null: 16); conv-block outputs carry one
 };
 
+// What the functions of ONE backward pass (and the optimiser step behind it) tell each other.  The ABI entry point makes one on its stack
+// and hands it down; a default-constructed one is the plain backward (nothing early, no input gradients), and nothing outlives the call.
+struct Backward {
+    // ---- asked by the entry point
+    // ss_g*_backward_inputs: the layer-0 blocks whose input gradient goes, dense ([B][T] rows, row stride ld), to a caller buffer
+    struct InputGrad {
+        const ConvBlk* cb = nullptr;
+        float* p = nullptr;
+        long ld = 0;
+    } in_grad[3];
+    const InputGrad* input_grad_of(const ConvBlk& cb) const {
+        for (const InputGrad& t : in_grad)
+            if (t.cb == &cb && t.p) return &t;
+        return nullptr;
+    }
+    // Early Adam (one GPU, Adam inside the step): the decoder + head range of the arenas (80 % of the bytes) is updated on the side stream
+    // right behind its last weight-gradient GEMM, beside the encoder backward (GEMM-bound, HBM mostly idle), instead of at the step's end
+    bool adam_early = false;               // the fused train steps want it
+    float adam_gs = 1.0f;
+    // ---- recorded by the pass
+    bool dec_w_pending = false;            // backward_decoder(late): the decoder's + head's weight gradients are still to be enqueued (backward_encoder)
+    long adam_early_from = -1;             // >= 0: the range [adam_early_from, arena) has been enqueued, the step state prepared
+    long clip_early_from = -1;             // >= 0: the squares' partial sums of [clip_early_from, status_off) have been enqueued (side stream)
+    WgradTable wg{};                       // encoder-BLSTM weight gradients waiting for their fused launch (lstm_wgrad.hip): lstm_weight_grads appends, wgrad_flush launches
+    bool wg_defer = false;                 // backward_encoder collects every small block's layers and flushes once at the end
+    ConvUnpackTable unpack{};              // conv weight gradients waiting for their re-layout (conv_block_bwd)
+    bool unpack_later = false;
+};
+
+// what the fused training step adds to its forward
+struct FusedForward {
+    const float *late_org = nullptr, *late_emb = nullptr;   // x_org / emb still to be copied in (done on the Encoder_t branch)
+    bool prezero = false;                  // zero the gradient arena (and the backward recurrences' start state) on a branch stream meanwhile
+};
+
+// how one lstm_weight_grads call differs from the plain one
+struct DwRoute {
+    int part = 0;                          // 0 everything; 2 everything except the W_ih gradient (it went out through lstm_wih_gemm_queued)
+    bool queue = false;                    // image GEMMs in the work-queue form
+    hipStream_t over_ih = nullptr, over_hh = nullptr;   // unbatched decoder path: the reverse direction's dW_ih / dW_hh go to these streams (tail split)
+};
+
 }  // namespace
 
 struct ss_engine {
@@ -196,7 +236,9 @@ struct ss_engine {
                                            // all-reduce sums it, so every rank's Adam kernel sees a non-zero value and skips
     void* comm = nullptr;                  // ncclComm_t of ss_comm_init (RCCL, dlopen'd)
     int comm_rank = 0, comm_world = 1;
-    // data-parallel step in flight: gradient ranges are all-reduced on comm_s as soon as their producers are through (dp_bucket)
+    // data-parallel step in flight: gradient ranges are all-reduced on comm_s as soon as their producers are through (dp_bucket).
+    // One step long, but kept on the engine: on the Generator_6 route dp_step's body is the PUBLIC ss_g6_train_step, whose signature
+    // cannot carry it, and dp_done / dp_rec below are filled under it and read after the body (dp_finish, ss_dp_profile_read)
     bool dp_on = false;
     hipStream_t comm_s = nullptr;
     hipEvent_t ev_comm = nullptr;
@@ -220,48 +262,43 @@ struct ss_engine {
     char* ws = nullptr;
     long ws_bytes = 0;
     int curB = 0, curT = 0;
-    bool fwd_training = false;
-    const float *late_org = nullptr, *late_emb = nullptr;   // fused training step: x_org / emb still to be copied in (done on the Encoder_t branch)
-    bool dec_w_pending = false;            // backward_decoder(late): the decoder's + head's weight gradients are still to be enqueued
-    bool dp_dir_buckets = false;           // lstm_weight_grads handed each direction of the layer to a collective itself
-    ConvUnpackTable unpack{};              // conv weight gradients waiting for their re-layout (conv_block_bwd)
-    bool unpack_later = false;
+    // ---- what a forward leaves for its backward (possibly a later ABI call): set by forward_core, cleared as a whole wherever the
+    // geometry or the workspace changes
+    struct FwdState {
+        bool have = false;                 // there is a forward to differentiate
+        bool training = false;
+        int enc_plan0 = 0;                 // plan[] index of the first encoder InterpLnr call
+        bool xf_img_valid = false;         // its gathers wrote xf_img
+        bool grads_zeroed = false;         // fused training step: the gradient arena was zeroed on a branch stream during the forward
+        bool bwd_sync_zeroed = false;      // the same for the backward recurrences' sync words / exchange tiles and the work-queue words
+    } fwd;
+    // ---- bookkeeping of the backward in flight: written by the decoder's lstm_bwd, read later in the same backward (and by
+    // speaker_input_grad behind it); backward_decoder starts it from zero
+    struct BwdMarks {
+        int dec_ih_done = 0;               // bit l: decoder layer l's W_ih gradient went out beside a recurrence (lstm_late_weights skips it)
+        int dec_w_done = 0;                // bit l: ALL of decoder layer l's weight gradients went out beside a recurrence (early_dw)
+        int dg16_written = 0;              // 16-bit data path: bit l = decoder layer l's backward recurrence wrote dg_img[l] (plain bf16)
+        int dg32_skipped = 0;              // ... and NOT the fp32 slab: gates[l] still holds the forward's activated gates (gemm_on refuses to read it)
+        int wq_next = 0;                   // work-queue launches handed out of wq_pool
+    } bwd;
     // XCD-aware weight gradients (lstm_bwd, ss_tune("xcd_dw")): where the decoder's persistent backward recurrences leave XCDs free
     // (B <= 48: 2 * ceil(B / 16) groups, one XCD each), the W_ih gradient of layer l + 1 runs as a work-queue image GEMM BESIDE the
     // recurrence of layer l -- on the free XCDs, because its 128-144 KB workgroups cannot be dispatched to a CU a recurrence workgroup holds
     unsigned* wq_pool = nullptr;           // zeroed per backward pass: 4 words per work-queue launch
+    static constexpr int WQ_SLOTS = 16;
     // column sums (bias gradients): float64 chunk partials from the step's scratch (part) + a ring of arrival counters, zero at rest
     unsigned* colsum_ctr = nullptr;
     static constexpr int COLSUM_CTRS = 2048;
     int colsum_next = 0;
-    // encoder-BLSTM weight gradients waiting for their fused launch (lstm_wgrad.hip): lstm_weight_grads appends, wgrad_flush launches
-    WgradTable wg{};
-    bool wg_defer = false;                 // backward_encoder collects every small block's layers and flushes once at the end
-    int wq_next = 0;
-    static constexpr int WQ_SLOTS = 16;
-    int dec_w_done = 0;                    // bit l: ALL of decoder layer l's weight gradients went out beside a recurrence (early_dw)
-    hipStream_t dw_over[2] = {nullptr, nullptr};   // lstm_weight_grads, unbatched decoder path: the reverse direction's dW_ih / dW_hh go to these streams (tail split)
-    bool wq_mode = false;                  // lstm_weight_grads: image GEMMs in the work-queue form
-    int dec_ih_done = 0;                   // bit l: decoder layer l's W_ih gradient went out beside a recurrence (lstm_late_weights skips it)
-    // Early Adam (one GPU, Adam inside the step): the decoder + head range of the arenas (80 % of the bytes) is updated on the side stream
-    // right behind its last weight-gradient GEMM, beside the encoder backward (GEMM-bound, HBM mostly idle), instead of at the step's end
-    bool adam_early = false;               // this step wants it (set by the fused train steps)
-    float adam_early_gs = 1.0f;
-    long adam_early_from = -1;             // >= 0: the range [adam_early_from, arena) has been enqueued, the step state prepared
-    // Clipping by global norm (ss_set_grad_clip): the norm needs the whole arena before the first element is updated, so the early range
-    // sends the PARTIAL SUMS of its squares to the side stream instead of its update; adam_enqueue adds the encoder range's, finalises
-    // (norm, coefficient, skip) and updates the arena in one launch.  Partials: [0, wgs(split)) encoder range, then the decoder + head range.
+    // Clipping by global norm (ss_set_grad_clip): the norm needs the whole arena before the first element is updated, so a fused step's
+    // early range (Backward) sends the PARTIAL SUMS of its squares to the side stream instead of its update; adam_enqueue adds the encoder
+    // range's, finalises (norm, coefficient, skip) and updates the arena in one launch.  Partials: [0, wgs(split)) encoder range, then the
+    // decoder + head range.
     float clip_max = 0.0f;                 // 0 off, > 0 clip to this norm, +inf measure and refuse non-finite gradients only
-    long clip_early_from = -1;             // >= 0: the partials of [clip_early_from, status_off) have been enqueued (side stream) in this step
     ClipState* clip = nullptr;             // workspace byte 128, beside the Adam state
     double* clip_part = nullptr;
     GradSegTable segs{};                   // runs of parameter elements of the arena (build_table)
     bool segs_ok = false;
-    bool prezero = false;                  // fused training step: zero the gradient arena on a branch stream during the forward
-    bool grads_zeroed = false;             // ... done: backward_decoder must not zero it again
-    bool bwd_sync_zeroed = false;          // the same for the backward recurrences' sync words / exchange tiles and the work-queue words
-    bool have_fwd = false;
-    int enc_plan0 = 0;                     // plan[] index of the first encoder InterpLnr call of the last forward
 
     // components
     ConvBlk c1[3], c2[3], ct;              // Encoder_7 stream 1 / stream 2 (or Encoder_6 in c2), Encoder_t
@@ -274,7 +311,6 @@ struct ss_engine {
     int f0p = 0;                           // padded one-hot width (264)
     float *act = nullptr, *d_act = nullptr, *d_xf = nullptr, *xf[3] = {nullptr, nullptr, nullptr};
     float* xf_img[3] = {nullptr, nullptr, nullptr};     // pre-split images of xf[0], xf[1] (training forward only: written by the gathers)
-    bool xf_img_valid = false;                          // the last forward wrote them
     float *act_t = nullptr, *d_act_t = nullptr;
     float *dec_in = nullptr, *d_dec_in = nullptr, *d_top = nullptr;
     float *d_o1 = nullptr, *d_o2 = nullptr, *d_ot = nullptr;
@@ -282,8 +318,6 @@ struct ss_engine {
     float* gp_all = nullptr;               // packed conv weight-gradient images (all blocks)
     // gradient slabs as images for the image GEMM: written by split_image with the measured scale (gscale[i] beside amax[i])
     float* dg_img[3] = {nullptr, nullptr, nullptr};       // decoder layers' pre-activation gradients [B, TP, 8H]
-    int dg32_skipped = 0;                                 // ... bit l = and NOT the fp32 slab: gates[l] still holds the forward's activated gates (gemm_on refuses to read it)
-    int dg16_written = 0;                                 // 16-bit data path: bit l = decoder layer l's backward recurrence wrote dg_img[l] (plain bf16) in this backward
     float *d_act_l[2] = {nullptr, nullptr}, *d_img_l[2] = {nullptr, nullptr};      // conv-output gradients of trunk layers 1 and 2 when their weight gradients run off the chain (conv_dw_off)
     float *d_img = nullptr, *d_img_t = nullptr;           // conv-output gradients of the trunk [B, TP, CE] / Encoder_t [B, TP, dim_enc_2]
     float* gscale = nullptr;               // [16]
@@ -328,7 +362,6 @@ struct ss_engine {
     int prof_every = 1, prof_ctr = 0;     // ss_profile_sample: brackets only in every prof_every-th training step
     bool prof_live = true;                // this step is one of them
 
-    long carve(int B, int T, bool assign);
     // 16-bit data path: the operand images are plain bf16 tensors (2 bytes per element) instead of format-v2 images (4)
     bool img16() const { return precision == SS_PRECISION_BF16 && g_bf16_img; }
     // image pointer `elems` ELEMENTS behind `base` (an image has its tensor's geometry; the bytes per element depend on the format)
@@ -370,6 +403,7 @@ struct TableBuilder {
         lb.H = hid;
         lb.L = layers;
         lb.pd.clear();
+        for (std::vector<float*>* v : {&lb.gates, &lb.out, &lb.csave, &lb.out_img, &lb.wcat_img, &lb.wcat, &lb.wfrag}) v->assign(layers, nullptr);      // filled by carve
         for (int l = 0; l < layers; ++l) {
             const int i = l == 0 ? in : 2 * hid;
             for (int d = 0; d < 2; ++d) {
@@ -448,174 +482,186 @@ void build_table(ss_engine* e) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ workspace plan
-long ss_engine::carve(int B, int T, bool assign) {
+namespace {
+
+// The plan of geometry (B, T): every slab in a fixed order, 256-byte aligned; returns its size in bytes.  On an engine it places the
+// slabs in e.ws and records every pointer and size; on a CONST engine it is the dry run, which only adds up and cannot write.
+template <class E>
+long carve(E& e, int B, int T) {
+    constexpr bool assign = !std::is_const_v<E>;
+    const ss_hparams& hp = e.hp;
     const long TP = T + 2 * HALO;
     const long R = (long)B * TP;
     long off = 0;
-    dbg.clear();
+    if constexpr (assign) e.dbg.clear();
     auto take = [&](long bytes) -> char* {
-        char* p = assign ? ws + off : nullptr;
+        char* p = assign ? e.ws + off : nullptr;
         off += (bytes + 255) & ~255L;
         return p;
     };
-    auto slab = [&](const char* name, long cols) -> float* {
-        float* p = (float*)take(R * cols * 4);
-        if (assign && name) dbg[name] = {p, cols};
-        return p;
+    auto put = [&](auto& dst, long bytes) {
+        char* p = take(bytes);
+        if constexpr (assign) dst = (std::remove_reference_t<decltype(dst)>)p;
     };
-    auto conv_ws = [&](ConvBlk& cb, const std::string& name) {
+    auto slab = [&](auto& dst, const char* name, long cols) {
+        put(dst, R * cols * 4);
+        if constexpr (assign)
+            if (name) e.dbg[name] = {dst, cols};
+    };
+    auto conv_ws = [&](auto& cb, const std::string& name) {
         if (cb.Co == 0) return;
-        cb.wf = (float*)take((long)cb.Co * 5 * cb.Cp * 4);
-        cb.wb = cb.need_dx ? (float*)take((long)cb.Ci * 5 * cb.Co * 4) : nullptr;
-        cb.wf_img = (float*)take((long)cb.Co * 5 * cb.Cp * 4);
-        cb.wb_img = cb.need_dx ? (float*)take((long)cb.Ci * 5 * cb.Co * 4) : nullptr;
-        cb.cout = slab((name + ".conv").c_str(), cb.Co);
-        cb.stats = (float*)take((long)B * (cb.Co / 16) * 2 * 4);
-        cb.part = (float*)take((long)B * 3 * cb.Co * 4);          // deterministic mode: per-utterance affine / bias gradient sums
+        put(cb.wf, (long)cb.Co * 5 * cb.Cp * 4);
+        if (cb.need_dx) put(cb.wb, (long)cb.Ci * 5 * cb.Co * 4);
+        put(cb.wf_img, (long)cb.Co * 5 * cb.Cp * 4);
+        if (cb.need_dx) put(cb.wb_img, (long)cb.Ci * 5 * cb.Co * 4);
+        slab(cb.cout, (name + ".conv").c_str(), cb.Co);
+        put(cb.stats, (long)B * (cb.Co / 16) * 2 * 4);
+        put(cb.part, (long)B * 3 * cb.Co * 4);          // deterministic mode: per-utterance affine / bias gradient sums
     };
-    auto lstm_ws = [&](LstmBlk& lb, const std::string& name) {
+    auto lstm_ws = [&](auto& lb, const std::string& name) {      // (the per-layer vectors have their L entries since build_table)
         if (lb.L == 0) return;
-        lb.gates.assign(lb.L, nullptr);
-        lb.out.assign(lb.L, nullptr);
-        lb.csave.assign(lb.L, nullptr);
         for (int l = 0; l < lb.L; ++l) {
-            lb.gates[l] = slab((name + ".gates" + std::to_string(l)).c_str(), 8L * lb.H);
-            lb.out[l] = slab((name + ".out" + std::to_string(l)).c_str(), lb.ow());
-            lb.csave[l] = slab((name + ".c" + std::to_string(l)).c_str(), lb.ow());
+            slab(lb.gates[l], (name + ".gates" + std::to_string(l)).c_str(), 8L * lb.H);
+            slab(lb.out[l], (name + ".out" + std::to_string(l)).c_str(), lb.ow());
+            slab(lb.csave[l], (name + ".c" + std::to_string(l)).c_str(), lb.ow());
         }
-        lb.out_img.assign(lb.L, nullptr);
         if (lb.big())
-            for (int l = 0; l < lb.L; ++l) lb.out_img[l] = slab(nullptr, 2L * lb.H);       // halo rows stay zero like those of out
-        lb.bsum = (float*)take((long)lb.L * 2 * 4 * lb.H * 4);
-        lb.wcat.assign(lb.L, nullptr);
-        for (int l = 0; l < lb.L; ++l) lb.wcat[l] = (float*)take(8L * lb.H * lb.in_of(l) * 4);
-        lb.wcat_img.assign(lb.L, nullptr);
+            for (int l = 0; l < lb.L; ++l) slab(lb.out_img[l], nullptr, 2L * lb.H);       // halo rows stay zero like those of out
+        put(lb.bsum, (long)lb.L * 2 * 4 * lb.H * 4);
+        for (int l = 0; l < lb.L; ++l) put(lb.wcat[l], 8L * lb.H * lb.in_of(l) * 4);
         if (lb.big())
-            for (int l = 0; l < lb.L; ++l) lb.wcat_img[l] = (float*)take(8L * lb.H * lb.in_of(l) * 4);
+            for (int l = 0; l < lb.L; ++l) put(lb.wcat_img[l], 8L * lb.H * lb.in_of(l) * 4);
         if (lb.big()) {
             const long B16 = ((B + 15) / 16) * 16;
-            lb.wfrag.assign(lb.L, nullptr);
-            for (int l = 0; l < lb.L; ++l) lb.wfrag[l] = (float*)take(2L * lb.H * 4 * lb.H * 4);
-            lb.hf = (float*)take(2L * 2 * B16 * lb.H * 4);
-            lb.gf = (float*)take(2L * 2 * B16 * 4 * lb.H * 4);
-            lb.dc = (float*)take(2L * B * lb.H * 4);
-            lb.sync = (unsigned*)take(LSTM_SEQ_SYNC_WORDS * 4);
-            lb.hf_bytes = lstm_seq_xbytes(B, lb.H, false);       // exchange buffers of the persistent kernels
-            lb.gf_bytes = lstm_seq_xbytes(B, lb.H, true);
-            lb.zf_bytes = lb.L * (4L * LSTM_SEQ_SYNC_WORDS + lb.hf_bytes);
-            lb.zb_bytes = lb.L * (4L * LSTM_SEQ_SYNC_WORDS + lb.gf_bytes);
-            lb.zf = (char*)take(lb.zf_bytes);
-            lb.zb = (char*)take(lb.zb_bytes);
+            for (int l = 0; l < lb.L; ++l) put(lb.wfrag[l], 2L * lb.H * 4 * lb.H * 4);
+            put(lb.hf, 2L * 2 * B16 * lb.H * 4);
+            put(lb.gf, 2L * 2 * B16 * 4 * lb.H * 4);
+            put(lb.dc, 2L * B * lb.H * 4);
+            put(lb.sync, LSTM_SEQ_SYNC_WORDS * 4);
+            const long hf_bytes = lstm_seq_xbytes(B, lb.H, false);       // exchange buffers of the persistent kernels
+            const long gf_bytes = lstm_seq_xbytes(B, lb.H, true);
+            const long zf_bytes = lb.L * (4L * LSTM_SEQ_SYNC_WORDS + hf_bytes);
+            const long zb_bytes = lb.L * (4L * LSTM_SEQ_SYNC_WORDS + gf_bytes);
+            put(lb.zf, zf_bytes);
+            put(lb.zb, zb_bytes);
+            if constexpr (assign) {
+                lb.hf_bytes = hf_bytes;
+                lb.gf_bytes = gf_bytes;
+                lb.zf_bytes = zf_bytes;
+                lb.zb_bytes = zb_bytes;
+            }
         }
         if (lb.L > 1) {
-            lb.dmid[0] = slab((name + ".dmid0").c_str(), lb.ow());
-            lb.dmid[1] = slab((name + ".dmid1").c_str(), lb.ow());
+            slab(lb.dmid[0], (name + ".dmid0").c_str(), lb.ow());
+            slab(lb.dmid[1], (name + ".dmid1").c_str(), lb.ow());
         }
     };
-    adam = (AdamState*)take(sizeof(AdamState));        // first: survives geometry changes (offset 0)
-    clip = assign ? (ClipState*)((char*)adam + CLIP_STATE_BYTE) : nullptr;      // same 256 bytes
-    if (kind != SS_INTERP_ONLY) clip_part = (double*)take(2L * GRAD_SUMSQ_MAX_WGS * sizeof(double));     // scratch, geometry-independent (offset 256)
-    if (kind == SS_INTERP_ONLY) {                      // a bare InterpLnr module only needs one plan
-        for (int i = 0; i < 4; ++i) {
-            plan[i].S = hp.max_len_seq / hp.min_len_seg + 1;
-            plan[i].ncand = 2 * hp.max_len_seg;
-            plan[i].P = hp.max_len_pad;
-            plan[i].T = T;
+    auto interp_ws = [&](auto& pl, bool storage) {
+        if constexpr (assign) {
+            pl.S = hp.max_len_seq / hp.min_len_seg + 1;     // model.py:365
+            pl.ncand = 2 * hp.max_len_seg;                  // model.py:389
+            pl.P = hp.max_len_pad;
+            pl.T = T;
         }
-        plan[3].i0 = (int*)take((long)B * hp.max_len_pad * 4);
-        plan[3].lam = (float*)take((long)B * hp.max_len_pad * 4);
-        plan[3].nrows = (int*)take((long)B * 4);
-        plan[3].counts = (int*)take((long)B * 4);
-        plan[3].start = (int*)take((long)B * (T + 1) * 4);
+        if (!storage) return;
+        put(pl.i0, (long)B * hp.max_len_pad * 4);
+        put(pl.lam, (long)B * hp.max_len_pad * 4);
+        put(pl.nrows, (long)B * 4);
+        put(pl.counts, (long)B * 4);
+        put(pl.start, (long)B * (T + 1) * 4);
+    };
+    put(e.adam, sizeof(AdamState));                    // first: survives geometry changes (offset 0)
+    if constexpr (assign) e.clip = (ClipState*)((char*)e.adam + CLIP_STATE_BYTE);      // same 256 bytes
+    if (e.kind != SS_INTERP_ONLY) put(e.clip_part, 2L * GRAD_SUMSQ_MAX_WGS * sizeof(double));     // scratch, geometry-independent (offset 256)
+    if (e.kind == SS_INTERP_ONLY) {                    // a bare InterpLnr module only needs one plan
+        for (int i = 0; i < 4; ++i) interp_ws(e.plan[i], i == 3);
         return off;
     }
-    in_mel = slab("in.mel", hp.dim_freq);
-    in_f0 = slab("in.f0", f0p);
-    org = slab("in.org", hp.dim_freq);
-    emb = (float*)take((long)B * hp.dim_spk_emb * 4);
+    slab(e.in_mel, "in.mel", hp.dim_freq);
+    slab(e.in_f0, "in.f0", e.f0p);
+    slab(e.org, "in.org", hp.dim_freq);
+    put(e.emb, (long)B * hp.dim_spk_emb * 4);
     for (int i = 0; i < 3; ++i) {
-        conv_ws(c1[i], "enc1.c1_" + std::to_string(i));
-        conv_ws(c2[i], (kind == SS_GENERATOR_3 ? "enc1.c2_" : "enc3.c_") + std::to_string(i));
-        xf[i] = slab(("enc.xf" + std::to_string(i)).c_str(), CE);
-        xf_img[i] = i < 2 ? slab(nullptr, CE) : nullptr;       // pre-split images of the resampled activations the next layer's convs read
+        conv_ws(e.c1[i], "enc1.c1_" + std::to_string(i));
+        conv_ws(e.c2[i], (e.kind == SS_GENERATOR_3 ? "enc1.c2_" : "enc3.c_") + std::to_string(i));
+        slab(e.xf[i], ("enc.xf" + std::to_string(i)).c_str(), e.CE);
+        if (i < 2) slab(e.xf_img[i], nullptr, e.CE);           // pre-split images of the resampled activations the next layer's convs read
     }
-    act = slab("enc.act", CE);
-    d_act = slab("enc.d_act", CE);
-    d_img = slab(nullptr, CE);
+    slab(e.act, "enc.act", e.CE);
+    slab(e.d_act, "enc.d_act", e.CE);
+    slab(e.d_img, nullptr, e.CE);
     for (int i = 0; i < 2; ++i) {
-        d_act_l[i] = slab(nullptr, CE);
-        d_img_l[i] = slab(nullptr, CE);
+        slab(e.d_act_l[i], nullptr, e.CE);
+        slab(e.d_img_l[i], nullptr, e.CE);
     }
-    d_img_t = slab(nullptr, hp.dim_enc_2);
-    gscale = (float*)take(16 * 4);
-    act_scale = (float*)take(8 * 4);
-    zeros = take(1024);
-    d_xf = slab("enc.d_xf", CE);
-    conv_ws(ct, "enc2.c");
+    slab(e.d_img_t, nullptr, hp.dim_enc_2);
+    put(e.gscale, 16 * 4);
+    put(e.act_scale, 8 * 4);
+    put(e.zeros, 1024);
+    slab(e.d_xf, "enc.d_xf", e.CE);
+    conv_ws(e.ct, "enc2.c");
     {   // packed weight-gradient images of every conv, contiguous so one memset per backward zeroes them all
         long tot = 0;
-        ConvBlk* all[7] = {&c1[0], &c1[1], &c1[2], &c2[0], &c2[1], &c2[2], &ct};
-        for (ConvBlk* cb : all) tot += align4((long)cb->Co * 5 * cb->Cp);
-        float* p = (float*)take(tot * 4);
-        gp_all = p;
-        gp_bytes = tot * 4;
-        amax = (float*)take(16 * 4);
-        int slot = 3;
-        for (ConvBlk* cb : all) {
-            cb->gp = cb->Co ? p : nullptr;
-            cb->scale_i = slot - 3;
-            cb->amax_i = slot++;
-            p += align4((long)cb->Co * 5 * cb->Cp);
+        for (auto* cb : {&e.c1[0], &e.c1[1], &e.c1[2], &e.c2[0], &e.c2[1], &e.c2[2], &e.ct}) tot += align4((long)cb->Co * 5 * cb->Cp);
+        put(e.gp_all, tot * 4);
+        put(e.amax, 16 * 4);
+        if constexpr (assign) {
+            e.gp_bytes = tot * 4;
+            float* p = e.gp_all;
+            int slot = 3;
+            for (ConvBlk* cb : {&e.c1[0], &e.c1[1], &e.c1[2], &e.c2[0], &e.c2[1], &e.c2[2], &e.ct}) {
+                cb->gp = cb->Co ? p : nullptr;
+                cb->scale_i = slot - 3;
+                cb->amax_i = slot++;
+                p += align4((long)cb->Co * 5 * cb->Cp);
+            }
         }
     }
-    act_t = slab("enc2.act", hp.dim_enc_2);
-    d_act_t = slab("enc2.d_act", hp.dim_enc_2);
-    lstm_ws(l1, "enc1.lstm1");
-    lstm_ws(l2, kind == SS_GENERATOR_3 ? "enc1.lstm2" : "enc3.lstm");
-    lstm_ws(lt, "enc2.lstm");
-    lstm_ws(ld, "dec.lstm");
-    for (int l = 0; l < ld.L && l < 3; ++l) dg_img[l] = ld.big() ? slab(nullptr, 8L * ld.H) : nullptr;
-    if (l1.L) d_o1 = slab("enc1.d_o1", l1.ow());
-    d_o2 = slab("enc.d_o2", l2.ow());
-    d_ot = slab("enc2.d_ot", lt.ow());
-    dec_in = slab("dec.in", dec_in_dim);
-    d_dec_in = slab("dec.d_in", dec_in_dim);
+    slab(e.act_t, "enc2.act", hp.dim_enc_2);
+    slab(e.d_act_t, "enc2.d_act", hp.dim_enc_2);
+    lstm_ws(e.l1, "enc1.lstm1");
+    lstm_ws(e.l2, e.kind == SS_GENERATOR_3 ? "enc1.lstm2" : "enc3.lstm");
+    lstm_ws(e.lt, "enc2.lstm");
+    lstm_ws(e.ld, "dec.lstm");
+    if (e.ld.big())
+        for (int l = 0; l < e.ld.L && l < 3; ++l) slab(e.dg_img[l], nullptr, 8L * e.ld.H);
+    if (e.l1.L) slab(e.d_o1, "enc1.d_o1", e.l1.ow());
+    slab(e.d_o2, "enc.d_o2", e.l2.ow());
+    slab(e.d_ot, "enc2.d_ot", e.lt.ow());
+    slab(e.dec_in, "dec.in", e.dec_in_dim);
+    slab(e.d_dec_in, "dec.d_in", e.dec_in_dim);
     {
         const int F = hp.freq_2;
-        const bool same = hp.freq_3 == F && (kind != SS_GENERATOR_3 || hp.freq == F);
-        ld.xf = (same && F > 1 && T % F == 0 && ld.big()) ? F : 0;       // structurally possible; ss_tune("compact0") decides per step
-        ld.xcols = kind == SS_GENERATOR_3 ? dec_in_dim - hp.dim_spk_emb : 0;
-        if (ld.xf) {
+        const bool same = hp.freq_3 == F && (e.kind != SS_GENERATOR_3 || hp.freq == F);
+        const int xf = (same && F > 1 && T % F == 0 && e.ld.big()) ? F : 0;       // structurally possible; ss_tune("compact0") decides per step
+        if constexpr (assign) {
+            e.ld.xf = xf;
+            e.ld.xcols = e.kind == SS_GENERATOR_3 ? e.dec_in_dim - hp.dim_spk_emb : 0;
+        }
+        if (xf) {
             const long R8 = (long)B * (T / F);
-            ld.xc = (float*)take(R8 * dec_in_dim * 4);
-            ld.xp0 = (float*)take(R8 * 8 * ld.H * 4);
-            ld.dgs = (float*)take(R8 * 8 * ld.H * 4);
-            ld.d_xc = (float*)take(R8 * dec_in_dim * 4);
+            put(e.ld.xc, R8 * e.dec_in_dim * 4);
+            put(e.ld.xp0, R8 * 8 * e.ld.H * 4);
+            put(e.ld.dgs, R8 * 8 * e.ld.H * 4);
+            put(e.ld.d_xc, R8 * e.dec_in_dim * 4);
         }
     }
-    d_top = slab("dec.d_top", 2L * ld.H);
-    out_slab = slab("out", head_out);
-    d_out_slab = slab("d_out", head_out);
-    loss_part = (float*)take(((long)B * T + 8L * B) * 4);
-    qidx = (int*)take((long)B * TP * 4);
-    wq_pool = (unsigned*)take(WQ_SLOTS * 16);
-    colsum_ctr = (unsigned*)take(COLSUM_CTRS * 4);
-    for (int i = 0; i < 4; ++i) {
-        plan[i].S = hp.max_len_seq / hp.min_len_seg + 1;     // model.py:365
-        plan[i].ncand = 2 * hp.max_len_seg;                  // model.py:389
-        plan[i].P = hp.max_len_pad;
-        plan[i].T = T;
-        plan[i].i0 = (int*)take((long)B * hp.max_len_pad * 4);
-        plan[i].lam = (float*)take((long)B * hp.max_len_pad * 4);
-        plan[i].nrows = (int*)take((long)B * 4);
-        plan[i].counts = (int*)take((long)B * 4);
-        plan[i].start = (int*)take((long)B * (T + 1) * 4);
-    }
+    slab(e.d_top, "dec.d_top", 2L * e.ld.H);
+    slab(e.out_slab, "out", e.head_out);
+    slab(e.d_out_slab, "d_out", e.head_out);
+    put(e.loss_part, ((long)B * T + 8L * B) * 4);
+    put(e.qidx, (long)B * TP * 4);
+    put(e.wq_pool, ss_engine::WQ_SLOTS * 16);
+    put(e.colsum_ctr, ss_engine::COLSUM_CTRS * 4);
+    for (int i = 0; i < 4; ++i) interp_ws(e.plan[i], true);
     // flipped taps of the layer-0 blocks' input-gradient GEMMs (ss_g*_backward_inputs only): last in the plan, so every slab above
     // keeps its place.  Three blocks may run at once on different streams, hence one each (2.3 MB for Generator_3).
-    for (ConvBlk* cb : {&c1[0], &c2[0], &ct}) cb->wb0 = cb->Co ? (float*)take((long)cb->Ci * 5 * cb->Co * 4) : nullptr;
+    for (auto* cb : {&e.c1[0], &e.c2[0], &e.ct})
+        if (cb->Co) put(cb->wb0, (long)cb->Ci * 5 * cb->Co * 4);
     return off;
 }
+
+}  // namespace
 
 namespace {
 
@@ -635,19 +681,15 @@ int geometry(ss_engine* e, int B, int T, hipStream_t s, bool eval = false) {
     if (e->kind != SS_INTERP_ONLY && (T % e->hp.freq || T % e->hp.freq_2 || T % e->hp.freq_3))
         return fail("T must be a multiple of the code down-sampling factors (model.py:87,223-227)");
     if (B == e->curB && T == e->curT) return 0;
-    long need;
-    {
-        ss_engine tmp = *e;
-        need = tmp.carve(B, T, false);
-    }
+    const long need = carve(std::as_const(*e), B, T);
     if (need > e->ws_bytes) return fail("workspace too small for this batch / frames: grow it to ss_plan_bytes(B, T) with ss_set_workspace");
     // new geometry: halo rows move, so everything the new plan uses, except the Adam state (first 256 bytes), is re-zeroed
     // (0.1 - 0.2 ms per switch at batch 64: the price of a length-bucket change, SS_STEP_BUCKET)
     HIPCHK(hipMemsetAsync(e->ws + 256, 0, need - 256, s));
-    e->carve(B, T, true);
+    carve(*e, B, T);
     e->curB = B;
     e->curT = T;
-    e->have_fwd = false;
+    e->fwd = {};
     return 0;
 }
 
@@ -668,15 +710,16 @@ constexpr int IMG_DW_WGS = 256;       // workgroups the split of a split-K (weig
 
 // Image GEMM (gemm_img.hip) for a contraction whose two operands exist as images.  Returns 1 when it was launched, 0 when the
 // contraction has to take round 2's kernels (no images, shape outside what the image kernel supports), < 0 on error.
-int try_img_gemm(ss_engine* e, const GemmDesc& d, hipStream_t st) {
+// klass: profile class of the contraction (SS_PROF_*; -1: none)
+int try_img_gemm(ss_engine* e, const GemmDesc& d, hipStream_t st, int klass) {
     if (!d.a_pre || !d.b_pre) return 0;
     const bool b16 = e->img16();                     // the images are plain bf16 tensors: single-piece form, every class that has both
     if (!b16) {
         if (!(d.flags & GEMM_F16X2) || (d.flags & GEMM_BF16)) return 0;
-        if (g_cur_klass >= 0 && !((IMG_CLASSES >> g_cur_klass) & 1) && !d.queue) return 0;
+        if (klass >= 0 && !((IMG_CLASSES >> klass) & 1) && !d.queue) return 0;
         // conv trunk at B x T <= 2048 rows: the image kernel's smallest tile (128 x 128) gives a 512-channel layer 64 workgroups; round 2's kernel
         // on 64 x 64 tiles fills the chip (16 x 128: 3.22 -> 3.17 ms, 12 x 128: 3.08 -> 3.04; equal at 8 x 128 and from 32 x 128 on)
-        if ((g_cur_klass == SS_PROF_CONV_FWD || g_cur_klass == SS_PROF_CONV_DX) && (long)e->curB * e->curT <= 2048) return 0;
+        if ((klass == SS_PROF_CONV_FWD || klass == SS_PROF_CONV_DX) && (long)e->curB * e->curT <= 2048) return 0;
     }
     ImgGemmDesc g{};
     g.bf16 = b16 ? 1 : 0;
@@ -743,11 +786,11 @@ int try_img_gemm(ss_engine* e, const GemmDesc& d, hipStream_t st) {
     } else {
         g.cfg = wgs(256, 256) >= 256 ? 0 : (wgs(256, 128) >= 224 ? 2 : 1);
     }
-    if (d.queue && e->wq_pool && e->wq_next < ss_engine::WQ_SLOTS) {
+    if (d.queue && e->wq_pool && e->bwd.wq_next < ss_engine::WQ_SLOTS) {
         // work-queue form on every XCD that will give it a CU; one workgroup per CU (128 / 144 KB of LDS), so that none fits beside a
         // recurrence workgroup
         if (g.cfg == 1) g.cfg = 2;
-        g.wq = e->wq_pool + 4 * e->wq_next++;
+        g.wq = e->wq_pool + 4 * e->bwd.wq_next++;
         g.xcc_allow = 0xFFu;
     }
     if (!gemm_img_supported(g)) return 0;
@@ -777,6 +820,16 @@ bool colsum_scratch(ss_engine* e, int cols, double** part, unsigned** ctr) {
 
 int prof_begin(ss_engine* e, int klass, hipStream_t st, double flops);
 void prof_end(ss_engine* e, int i, hipStream_t st);
+// ss_profile bracket round the launches of one scope: the start event where it is made, the end event where the scope ends (on every way out)
+struct Prof {
+    ss_engine* e;
+    hipStream_t st;
+    int i;
+    Prof(ss_engine* e_, int klass, hipStream_t st_, double flops = 0.0) : e(e_), st(st_), i(prof_begin(e_, klass, st_, flops)) {}
+    ~Prof() { prof_end(e, i, st); }
+    Prof(const Prof&) = delete;
+    Prof& operator=(const Prof&) = delete;
+};
 // gradient norm (ss_set_grad_clip / ss_grad_norm): the arena is summed as [0, split) and [split, status_off), split = ss_grad_split when
 // that is a float4 boundary -- the same two ranges on every route, so the norm has the same bits on every route
 long clip_split(const ss_engine* e) {
@@ -787,41 +840,38 @@ int clip_wgs_lo(const ss_engine* e) { return clip_split(e) > 0 ? grad_sumsq_wgs(
 
 // launch the pending encoder-BLSTM weight-gradient tasks (one kernel for all of them) on `st`: everything they read must be complete in
 // st's order.  Scratch: partial tiles from the step's bump allocator, arrival counters from the column sums' ring.
-int wgrad_flush(ss_engine* e, hipStream_t st) {
-    if (e->wg.n == 0) return 0;
-    WgradTable& w = e->wg;
+int wgrad_flush(ss_engine* e, Backward& bw, hipStream_t st) {
+    WgradTable& w = bw.wg;
+    if (w.n == 0) return 0;
     w.row_groups = 16;
     const long need = (long)w.tiles_total * w.row_groups * 4096;
-    if (!e->part || !e->colsum_ctr || w.tiles_total > ss_engine::COLSUM_CTRS || e->part_off + need > e->part_cap) {
-        w.n = 0;
-        w.tiles_total = 0;
+    if (!e->part || !e->colsum_ctr || w.tiles_total > ss_engine::COLSUM_CTRS || e->part_off + need > e->part_cap)
         return fail("wgrad_flush: no scratch left for the fused encoder-BLSTM weight gradients");
-    }
     w.part = e->part + e->part_off;
     e->part_off += (need + 63) & ~63L;
     if (e->colsum_next + w.tiles_total > ss_engine::COLSUM_CTRS) e->colsum_next = 0;
     w.ctr = e->colsum_ctr + e->colsum_next;
     e->colsum_next += w.tiles_total;
-    const int pa_ = prof_begin(e, SS_PROF_WGRAD, st, 0.0);
-    const hipError_t rc = lstm_small_wgrad(w, st);
-    prof_end(e, pa_, st);
-    w.n = 0;
+    {
+        Prof pr(e, SS_PROF_WGRAD, st);
+        HIPCHK(lstm_small_wgrad(w, st));
+    }
+    w.n = 0;               // (an error above ends the backward, and the table with it)
     w.tiles_total = 0;
-    HIPCHK(rc);
     return 0;
 }
 
 // every contraction of the engine honours its precision mode (ss_set_precision)
-int gemm_on(ss_engine* e, GemmDesc& d, hipStream_t st) {
+int gemm_on(ss_engine* e, GemmDesc& d, hipStream_t st, int klass) {
     if (e->precision == SS_PRECISION_BF16) d.flags |= GEMM_BF16;
-    const int r = try_img_gemm(e, d, st);
+    const int r = try_img_gemm(e, d, st, klass);
     if (r < 0) return r;
     if (r == 0) {
         if (e->img16()) d.a_pre = d.b_pre = nullptr;        // plain bf16 tensors: not the format-v2 images round 2's kernel can take
-        if (e->dg32_skipped) {                              // a decoder layer's fp32 gradient slab was not written: nothing may read it as an operand
+        if (e->bwd.dg32_skipped) {                              // a decoder layer's fp32 gradient slab was not written: nothing may read it as an operand
             const long R8 = (long)e->curB * (e->curT + 2 * HALO) * 8L * e->ld.H;
             for (int l = 0; l < e->ld.L && l < 3; ++l)
-                if (((e->dg32_skipped >> l) & 1) && ((d.A.p >= e->ld.gates[l] && d.A.p < e->ld.gates[l] + R8) || (d.B.p >= e->ld.gates[l] && d.B.p < e->ld.gates[l] + R8)))
+                if (((e->bwd.dg32_skipped >> l) & 1) && ((d.A.p >= e->ld.gates[l] && d.A.p < e->ld.gates[l] + R8) || (d.B.p >= e->ld.gates[l] && d.B.p < e->ld.gates[l] + R8)))
                     return fail("internal: a contraction fell back to the fp32 gradient slab of a decoder layer that was only written as bf16");
         }
         // split-K weight gradients: partial slabs + ordered reduce instead of fp32 atomics, scratch from the step's bump allocator
@@ -839,15 +889,6 @@ int gemm_on(ss_engine* e, GemmDesc& d, hipStream_t st) {
     }
     return 0;
 }
-#define GEMM(d) GEMM_ON(d, s)
-#define GEMM_ON(d, st) CHK(gemm_on(e, d, st))
-// forward contraction: both operands are O(1) by construction
-#define GEMM_FWD_ON(d, st)                              \
-    do {                                                \
-        if (g_fwd_f16x2) (d).flags |= GEMM_F16X2;       \
-        GEMM_ON(d, st);                                 \
-    } while (0)
-
 // Data parallel: the gradient range [off, off + count) is final once everything enqueued on `producer` so far has run -- hand it to a
 // collective on the communication stream right away.  No-op outside a data-parallel step.
 int dp_bucket(ss_engine* e, long off, long count, hipStream_t producer);
@@ -1036,21 +1077,16 @@ double gemm_flops_of(const ss_engine* e, const GemmDesc& d) {
 }
 #define gemm_flops(d) gemm_flops_of(e, d)
 // GEMM launch bracketed as profile class `k`
-#define PGEMM_ON(k, d, st)                                   \
-    do {                                                     \
-        const int _pi = prof_begin(e, k, st, gemm_flops(d)); \
-        g_cur_klass = k;                                     \
-        GEMM_ON(d, st);                                      \
-        g_cur_klass = -1;                                    \
-        prof_end(e, _pi, st);                                \
+#define PGEMM_ON(k, d, st)                          \
+    do {                                            \
+        Prof _pr(e, k, st, gemm_flops(d));          \
+        CHK(gemm_on(e, d, st, k));                  \
     } while (0)
-#define PGEMM_FWD_ON(k, d, st)                               \
-    do {                                                     \
-        const int _pi = prof_begin(e, k, st, gemm_flops(d)); \
-        g_cur_klass = k;                                     \
-        GEMM_FWD_ON(d, st);                                  \
-        g_cur_klass = -1;                                    \
-        prof_end(e, _pi, st);                                \
+// forward contraction: both operands are O(1) by construction
+#define PGEMM_FWD_ON(k, d, st)                      \
+    do {                                            \
+        if (g_fwd_f16x2) (d).flags |= GEMM_F16X2;   \
+        PGEMM_ON(k, d, st);                         \
     } while (0)
 
 // A per-utterance batched contraction over haloed slabs (M = T rows per batch entry, A / C pointing at slab row HALO) rewritten as
@@ -1123,10 +1159,11 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
     PGEMM_FWD_ON(SS_PROF_CONV_FWD, d, s);
     if (gather) {
         if (gather_ready) HIPCHK(hipStreamWaitEvent(s, gather_ready, 0));
-        { const int pa_ = prof_begin(e, SS_PROF_GN, s, 0.0);
-        HIPCHK(gn_relu_gather(cb.cout, cb.Co, TP * cb.Co, gy, gy_ld, TP * gy_ld, gy_img, e->act_scale + cb.scale_i, e->P + cb.ga, e->P + cb.be, cb.stats,
-                              *gather, B, T, cb.Co, s, e->img16()));
-        prof_end(e, pa_, s); }
+        {
+            Prof pr(e, SS_PROF_GN, s);
+            HIPCHK(gn_relu_gather(cb.cout, cb.Co, TP * cb.Co, gy, gy_ld, TP * gy_ld, gy_img, e->act_scale + cb.scale_i, e->P + cb.ga, e->P + cb.be, cb.stats,
+                                  *gather, B, T, cb.Co, s, e->img16()));
+        }
         return 0;
     }
     // T > 256 (eval only): the chunked GroupNorm takes its float64 partials from the step's scratch (one region per block: blocks run
@@ -1138,9 +1175,10 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
         gn_scratch = (double*)(e->part + e->part_off);          // part_off is kept at multiples of 64 floats
         e->part_off += need;
     }
-    { const int pa_ = prof_begin(e, SS_PROF_GN, s, 0.0);
-    HIPCHK(gn_relu_fwd(cb.cout, cb.Co, TP * cb.Co, y.p, y.ld, TP * y.ld, e->P + cb.ga, e->P + cb.be, cb.stats, B, T, cb.Co, s, gn_scratch));
-    prof_end(e, pa_, s); }
+    {
+        Prof pr(e, SS_PROF_GN, s);
+        HIPCHK(gn_relu_fwd(cb.cout, cb.Co, TP * cb.Co, y.p, y.ld, TP * y.ld, e->P + cb.ga, e->P + cb.be, cb.stats, B, T, cb.Co, s, gn_scratch));
+    }
     return 0;
 }
 
@@ -1151,7 +1189,8 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
 // writes dy
 // dws (nullable): the weight-gradient GEMM goes to that stream behind an event, the chain on `s` does not wait for it -- the caller keeps dy
 // untouched until dws is joined
-int conv_block_bwd(ss_engine* e, ConvBlk& cb, Slab dy, Slab x, Slab dx, hipStream_t s, const InterpPlan* scatter = nullptr, const float* src = nullptr,
+// bw: collects the weight gradient's re-layout (unpack_later) and names the caller buffer of a layer-0 block's input gradient
+int conv_block_bwd(ss_engine* e, Backward& bw, ConvBlk& cb, Slab dy, Slab x, Slab dx, hipStream_t s, const InterpPlan* scatter = nullptr, const float* src = nullptr,
                    long src_ld = 0, hipStream_t dws = nullptr) {
     const int B = e->curB, T = e->curT;
     const long TP = T + 2 * HALO, R = (long)B * TP;
@@ -1160,10 +1199,11 @@ int conv_block_bwd(ss_engine* e, ConvBlk& cb, Slab dy, Slab x, Slab dx, hipStrea
     // 16-bit data path: the GroupNorm backward writes the gradient's bf16 image itself (the image's halo rows are zero since the geometry
     // was planned and nobody writes them); fp32 mode: a split_image pass with the scale gn_relu_bwd has just measured
     float* im16 = (i16 && cb.Co % 8 == 0 && dy.ld % 8 == 0) ? grad_img_of(e, dy.p, R) : nullptr;
-    { const int pa_ = prof_begin(e, SS_PROF_GN, s, 0.0);
-    HIPCHK(gn_relu_bwd(cb.cout, cb.Co, TP * cb.Co, dy.p, dy.ld, TP * dy.ld, e->P + cb.ga, e->P + cb.be, cb.stats,
-                       e->G + cb.ga, e->G + cb.be, e->G + cb.b, am, cb.part, B, T, cb.Co, s, scatter, src, src_ld, TP * src_ld, im16));
-    prof_end(e, pa_, s); }
+    {
+        Prof pr(e, SS_PROF_GN, s);
+        HIPCHK(gn_relu_bwd(cb.cout, cb.Co, TP * cb.Co, dy.p, dy.ld, TP * dy.ld, e->P + cb.ga, e->P + cb.be, cb.stats,
+                           e->G + cb.ga, e->G + cb.be, e->G + cb.b, am, cb.part, B, T, cb.Co, s, scatter, src, src_ld, TP * src_ld, im16));
+    }
     // the conv-output gradient as an image for the image GEMM (scale: the power of two for the maximum gn_relu_bwd has just measured)
     const float* dimg = im16;
     const float* dsc = nullptr;
@@ -1200,7 +1240,7 @@ int conv_block_bwd(ss_engine* e, ConvBlk& cb, Slab dy, Slab x, Slab dx, hipStrea
     // packed [Co][5][Cp] -> the parameter's [Co][Ci][5]: nobody reads it before the optimiser (or, data parallel, the layer's bucket), so the
     // one-GPU step collects the blocks and unpacks them all in one launch at the end of the backward (backward_encoder) instead of seven
     // small launches on the trunk's dependent chain
-    if (e->unpack_later && e->unpack.n < CONV_UNPACK_MAX) e->unpack.t[e->unpack.n++] = {cb.gp, e->G + cb.w, cb.Co, cb.Ci, cb.Cp};
+    if (bw.unpack_later && bw.unpack.n < CONV_UNPACK_MAX) bw.unpack.t[bw.unpack.n++] = {cb.gp, e->G + cb.w, cb.Co, cb.Ci, cb.Cp};
     else HIPCHK(conv_unpack_grad(cb.gp, cb.Co, cb.Ci, cb.Cp, e->G + cb.w, dws));
     if (dx.p) {
         GemmDesc g{};
@@ -1225,7 +1265,7 @@ int conv_block_bwd(ss_engine* e, ConvBlk& cb, Slab dy, Slab x, Slab dx, hipStrea
         flatten_rows(g, B, T);
         PGEMM_ON(SS_PROF_CONV_DX, g, s);
     }
-    if (cb.dx_out) {
+    if (const Backward::InputGrad* tg = bw.input_grad_of(cb)) {
         // the block's input is the network input (ss_g*_backward_inputs): the same contraction against taps packed for this call (the forward
         // packs none for layer 0), stored straight into the caller's dense [B][T] rows -- per-utterance batches of T rows, so no halo row is
         // ever computed or stored, and the halo rows of dy (zero) are what the taps past either end of an utterance read
@@ -1234,9 +1274,9 @@ int conv_block_bwd(ss_engine* e, ConvBlk& cb, Slab dy, Slab x, Slab dx, hipStrea
         GemmDesc g{};
         g.A = {dy.p, dy.ld, TP * dy.ld, cb.Co, dy.ld};
         g.B = {cb.wb0, 5L * cb.Co, 0, 0, 0};
-        g.C = cb.dx_out;
-        g.ldc = cb.dx_ld;
-        g.cstride = (long)T * cb.dx_ld;
+        g.C = tg->p;
+        g.ldc = tg->ld;
+        g.cstride = (long)T * tg->ld;
         g.M = T;
         g.N = cb.Ci;
         g.K = 5 * cb.Co;
@@ -1324,11 +1364,12 @@ int lstm_big_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
                 CHK(fork_join(e, s, e->side3));
                 HIPCHK(slab_prewarm(lb.gates[l], 8 * H, nullptr, nullptr, 2 * H, e->amax, B, T, false, e->side3));
             }
-            const int pi = prof_begin(e, SS_PROF_REC_FWD, s, 2.0 * 2 * B * T * 4.0 * H * H);
-            HIPCHK(lstm_seq_fwd(lb.gates[l], e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.hf_l(l), lb.out[l], lb.csave[l],
-                                lb.sync_f(l), e->sticky, compact ? lb.xp0 : nullptr, compact ? lb.xf : 0, lb.out_img_valid ? lb.out_img[l] : nullptr, B, T, H,
-                                false, false, s, e->img16() ? 1 | 2 : 0));      // 16-bit data path: bf16 images (1), products of the high fp16 pieces only (2)
-            prof_end(e, pi, s);
+            {
+                Prof pr(e, SS_PROF_REC_FWD, s, 2.0 * 2 * B * T * 4.0 * H * H);
+                HIPCHK(lstm_seq_fwd(lb.gates[l], e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.hf_l(l), lb.out[l], lb.csave[l],
+                                    lb.sync_f(l), e->sticky, compact ? lb.xp0 : nullptr, compact ? lb.xf : 0, lb.out_img_valid ? lb.out_img[l] : nullptr, B, T, H,
+                                    false, false, s, e->img16() ? 1 | 2 : 0));      // 16-bit data path: bf16 images (1), products of the high fp16 pieces only (2)
+            }
             if (pw) CHK(fork_join(e, e->side3, s));
             continue;
         }
@@ -1367,10 +1408,11 @@ int lstm_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
             flatten_rows(d, B, T);
             PGEMM_FWD_ON(SS_PROF_ENC_LSTM, d, s);
         }
-        { const int pa_ = prof_begin(e, SS_PROF_ENC_REC, s, 0.0);
-        HIPCHK(lstm_small_fwd(lb.gates[l], e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.out[l], lb.csave[l], B, T, H,
-                              s));
-        prof_end(e, pa_, s); }
+        {
+            Prof pr(e, SS_PROF_ENC_REC, s);
+            HIPCHK(lstm_small_fwd(lb.gates[l], e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.out[l], lb.csave[l], B, T, H,
+                                  s));
+        }
     }
     return 0;
 }
@@ -1383,7 +1425,7 @@ int lstm_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
 // persistent recurrence the launch is meant to run beside -- the GEMM is dispatched once that grid is resident (seq_gate).
 bool lstm_wih_queue_ok(ss_engine* e, LstmBlk& lb, int l, const float* am) {
     if (!am || &lb != &e->ld || l < 1 || l >= 3 || !e->dg_img[l] || e->precision != SS_PRECISION_F32 || !g_bwd_f16x2) return false;
-    if (!lb.out_img_valid || !lb.out_img[l - 1] || !e->wq_pool || e->wq_next >= ss_engine::WQ_SLOTS) return false;
+    if (!lb.out_img_valid || !lb.out_img[l - 1] || !e->wq_pool || e->bwd.wq_next >= ss_engine::WQ_SLOTS) return false;
     return lb.pd[l * 2 + 1].wih > lb.pd[l * 2].wih;
 }
 int lstm_wih_split(ss_engine* e, LstmBlk& lb, int l, const float* am, hipStream_t ws) {
@@ -1414,33 +1456,34 @@ int lstm_wih_gemm_queued(ss_engine* e, LstmBlk& lb, int l, const float* am, cons
     a.amax_a = am;
     a.ksplit = 4;                   // > 1: the image path cuts the reduction into partial slabs
     a.queue = 1;
-    const int pi = prof_begin(e, SS_PROF_DEC_DW, ws, 2.0 * a.M * a.N * (double)B * T * a.batch);
-    g_cur_klass = SS_PROF_DEC_DW;
-    const int r = try_img_gemm(e, a, ws);
-    g_cur_klass = -1;
-    prof_end(e, pi, ws);
+    int r;
+    {
+        Prof pr(e, SS_PROF_DEC_DW, ws, 2.0 * a.M * a.N * (double)B * T * a.batch);
+        r = try_img_gemm(e, a, ws, SS_PROF_DEC_DW);
+    }
     if (r < 0) return r;
     if (r == 0) return fail("lstm_wih_gemm_queued: the image GEMM refused a shape the engine planned for it");
-    e->dec_ih_done |= 1 << l;
+    e->bwd.dec_ih_done |= 1 << l;
     return 0;
 }
 
-// part: 0 everything; 2 everything except the W_ih gradient (it went out through lstm_wih_grad_queued)
-int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am, bool bias_done, hipStream_t ws, int part = 0) {
+// Returns 1 when each direction of the layer has been handed to a data-parallel collective here (the caller's per-layer bucket then has
+// nothing left to send), 0 when not, < 0 on error.
+int lstm_weight_grads(ss_engine* e, Backward& bw, LstmBlk& lb, int l, Slab xi, const float* am, bool bias_done, hipStream_t ws, DwRoute route = {}) {
     const int B = e->curB, T = e->curT, H = lb.H;
     const long TP = T + 2 * HALO, R = (long)B * TP;
     const int In = lb.in_of(l);
     float* dG = lb.gates[l];
     const LstmDir &p0 = lb.pd[l * 2], &p1 = lb.pd[l * 2 + 1];
-    if (!lb.big() && H <= 32 && !bias_done && e->part && e->colsum_ctr && e->wg.n < WGRAD_MAX &&
-        e->part_off + (long)(e->wg.tiles_total + lstm_small_wgrad_tiles(H, In)) * 16 * 4096 <= e->part_cap) {
+    if (!lb.big() && H <= 32 && !bias_done && e->part && e->colsum_ctr && bw.wg.n < WGRAD_MAX &&
+        e->part_off + (long)(bw.wg.tiles_total + lstm_small_wgrad_tiles(H, In)) * 16 * 4096 <= e->part_cap) {
         // encoder BLSTMs: one fused fp32 kernel for the weight and bias gradients of every layer (lstm_wgrad.hip) instead of 12-14 tiny GEMMs + column sums
-        WgradTask& t = e->wg.t[e->wg.n];
+        WgradTask& t = bw.wg.t[bw.wg.n];
         t = WgradTask{dG, xi.p, xi.ld, lb.out[l], e->G + p0.wih, e->G + p1.wih, e->G + p0.whh, e->G + p1.whh, e->G + p0.bih, e->G + p0.bhh, e->G + p1.bih,
-                      e->G + p1.bhh, H, In, R, e->wg.tiles_total, (int)lb.ow()};
-        e->wg.tiles_total += lstm_small_wgrad_tiles(H, In);
-        ++e->wg.n;
-        if (!e->wg_defer) CHK(wgrad_flush(e, ws));
+                      e->G + p1.bhh, H, In, R, bw.wg.tiles_total, (int)lb.ow()};
+        bw.wg.tiles_total += lstm_small_wgrad_tiles(H, In);
+        ++bw.wg.n;
+        if (!bw.wg_defer) CHK(wgrad_flush(e, bw, ws));
         return 0;
     }
     const bool compact = l == 0 && lb.xf && xi.p == lb.xc;     // dW_ih from the block sums and one input row per block (K / xf)
@@ -1449,7 +1492,39 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
     // 16-bit data path: the decoder's pre-activation gradients as a bf16 image for the image GEMM, written by the backward recurrence's storing
     // wave.  (fp32 mode: the weight gradients are not in the image class set, IMG_CLASSES, and stay on round 2's kernel.)
     const float* dimg = nullptr;
-    if (e->img16() && &lb == &e->ld && l < 3 && ((e->dg16_written >> l) & 1) && img_ok) dimg = e->dg_img[l];
+    if (e->img16() && &lb == &e->ld && l < 3 && ((e->bwd.dg16_written >> l) & 1) && img_ok) dimg = e->dg_img[l];
+    const int klass = lb.big() ? SS_PROF_DEC_DW : SS_PROF_ENC_LSTM;
+    // Every contraction here is  dW[n][k] += sum_r dG[r][n] * X[r][k]  into the gradient arena at w_off: 4H rows, N columns (the row length
+    // of W), reduced over K slab rows; batch = 2: both directions in one launch, their parameters one stride apart.  The gradient slab
+    // carries its measured scale; the layer input is O(1).
+    auto dw_desc = [&](Operand A, Operand X, long w_off, int N, long K, int batch) {
+        GemmDesc d{};
+        d.A = A;
+        d.B = X;
+        d.C = e->G + w_off;
+        d.ldc = N;
+        d.cstride = batch > 1 ? p1.wih - p0.wih : 0;
+        d.M = 4 * H;
+        d.N = N;
+        d.K = (int)K;
+        d.batch = batch;
+        d.flags = GEMM_TA | GEMM_TB | GEMM_ACCUM | (am ? GEMM_F16X2 : 0);
+        d.amax_a = am;
+        d.ksplit = pick_ksplit(d.M, d.N, d.K);
+        d.queue = (batch > 1 && route.queue) ? 1 : 0;
+        return d;
+    };
+    // data parallel: one direction's parameters (W_ih, W_hh, b_ih, b_hh: contiguous in the arena) are final on its stream -- half a layer per
+    // collective keeps the communication stream busy 140 us earlier than a bucket per layer (modelled N = 8: the last collective ends
+    // closer to the backward's end)
+    bool dir_buckets = false;
+    auto dir_bucket = [&](const LstmDir& pd, hipStream_t st_ih, hipStream_t st) -> int {
+        if (&lb != &e->ld || !e->dp_on || route.part != 0 || pd.bhh + 4L * H <= pd.wih) return 0;
+        if (st_ih != st) return fail("internal: a direction's weight gradients on two streams under data parallelism");
+        CHK(dp_bucket(e, pd.wih, pd.bhh + 4L * H - pd.wih, st));
+        dir_buckets = true;
+        return 0;
+    };
     // Both directions in ONE launch each (batch = 2) when their parameters sit at one stride in the arena (PyTorch's order: they do).
     // dW_hh: h_prev is `out` one row earlier (forward) / later (reverse), so the forward direction reads dG one row later instead.
     // (With the image GEMM the decoder's launches are batched as well: 64 + 32 tile jobs per layer instead of 4 x (32 or 16) halve the
@@ -1457,46 +1532,22 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
     // The encoder BLSTMs always (36 -> 14 launches); the decoder only with images (without: measured step +0.18 ms).
     const bool img_batch = dimg != nullptr;
     if ((!compact || img_batch) && (!lb.big() || img_batch) && p1.wih - p0.wih == p1.whh - p0.whh && p1.wih > p0.wih) {
-        const long pstride = p1.wih - p0.wih;
-        GemmDesc a{};
-        a.A = {dG, 8L * H, 4L * H, 0, 0};
-        a.B = {xi.p, xi.ld, 0, 0, 0};
-        a.b_pre_scale = l == 0 ? xi.scale : nullptr;      // a conv block's output carries its own split scale (act_scales): right whichever product mode runs
-        a.C = e->G + p0.wih;
-        a.ldc = In;
-        a.cstride = pstride;
-        a.M = 4 * H;
-        a.N = In;
-        a.K = (int)R;
-        a.batch = 2;
-        a.flags = GEMM_TA | GEMM_TB | GEMM_ACCUM | (am ? GEMM_F16X2 : 0);
-        a.amax_a = am;                              // gradient slab: measured scale; the layer input is O(1)
-        a.ksplit = pick_ksplit(a.M, a.N, a.K);
-        a.queue = e->wq_mode ? 1 : 0;
-        if (dimg && l > 0) {
-            a.a_pre = dimg;
-            a.b_pre = lb.out_img[l - 1];
+        if (!compact && route.part != 2) {
+            GemmDesc a = dw_desc({dG, 8L * H, 4L * H, 0, 0}, {xi.p, xi.ld, 0, 0, 0}, p0.wih, In, R, 2);
+            a.b_pre_scale = l == 0 ? xi.scale : nullptr;      // a conv block's output carries its own split scale (act_scales): right whichever product mode runs
+            if (dimg && l > 0) {
+                a.a_pre = dimg;
+                a.b_pre = lb.out_img[l - 1];
+            }
+            PGEMM_ON(klass, a, ws);
         }
-        if (!compact && part != 2) PGEMM_ON(lb.big() ? SS_PROF_DEC_DW : SS_PROF_ENC_LSTM, a, ws);
-        GemmDesc h{};
-        h.A = {dG + 8L * H, 8L * H, 4L * H - 8L * H, 0, 0};                    // forward: rows 1 .., reverse: rows 0 .. of its own columns
-        h.B = {lb.out[l], lb.ow(), lb.ow() + H, 0, 0};                         // forward: rows 0 .. of h_f, reverse: rows 1 .. of h_b
+        GemmDesc h = dw_desc({dG + 8L * H, 8L * H, 4L * H - 8L * H, 0, 0},                    // forward: rows 1 .., reverse: rows 0 .. of its own columns
+                             {lb.out[l], lb.ow(), lb.ow() + H, 0, 0}, p0.whh, H, R - 1, 2);    // forward: rows 0 .. of h_f, reverse: rows 1 .. of h_b
         if (dimg) {
             h.a_pre = e->ioff(dimg, 8L * H);
             h.b_pre = lb.out_img[l];
         }
-        h.C = e->G + p0.whh;
-        h.ldc = H;
-        h.cstride = pstride;
-        h.M = 4 * H;
-        h.N = H;
-        h.K = (int)(R - 1);
-        h.batch = 2;
-        h.flags = GEMM_TA | GEMM_TB | GEMM_ACCUM | (am ? GEMM_F16X2 : 0);
-        h.amax_a = am;
-        h.ksplit = pick_ksplit(h.M, h.N, h.K);
-        h.queue = e->wq_mode ? 1 : 0;
-        PGEMM_ON(lb.big() ? SS_PROF_DEC_DW : SS_PROF_ENC_LSTM, h, ws);
+        PGEMM_ON(klass, h, ws);
         if (!bias_done) {
             double* cpart;
             unsigned* cctr;
@@ -1507,62 +1558,27 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
         // compact layer 0: dW_hh went out batched above, dW_ih comes from the block sums below, per direction
         for (int dir = 0; dir < 2; ++dir) {
             const LstmDir& pd = lb.pd[l * 2 + dir];
-            GemmDesc c{};
-            c.A = {lb.dgs + dir * 4L * H, 8L * H, 0, 0, 0};
-            c.B = {xi.p, xi.ld, 0, 0, 0};
-            c.C = e->G + pd.wih;
-            c.ldc = In;
-            c.M = 4 * H;
-            c.N = In;
-            c.K = B * (T / lb.xf);
-            c.batch = 1;
-            c.flags = GEMM_TA | GEMM_TB | GEMM_ACCUM | (am ? GEMM_F16X2 : 0);
-            c.amax_a = am;
-            c.ksplit = pick_ksplit(c.M, c.N, c.K);
+            GemmDesc c = dw_desc({lb.dgs + dir * 4L * H, 8L * H, 0, 0, 0}, {xi.p, xi.ld, 0, 0, 0}, pd.wih, In, B * (T / lb.xf), 1);
             PGEMM_ON(SS_PROF_DEC_DW, c, ws);
-            if (&lb == &e->ld && e->dp_on && part == 0 && pd.bhh + 4L * H > pd.wih) {      // data parallel: half a layer per collective (see below)
-                CHK(dp_bucket(e, pd.wih, pd.bhh + 4L * H - pd.wih, ws));
-                e->dp_dir_buckets = true;
-            }
+            CHK(dir_bucket(pd, ws, ws));
         }
-        return 0;
+        return dir_buckets ? 1 : 0;
     }
     for (int dir = 0; dir < 2; ++dir) {
         const LstmDir& pd = lb.pd[l * 2 + dir];
         const float* dGd = dG + dir * 4L * H;
-        // dW_ih[n][k] = sum_r dG[r][n] * X[r][k]
-        GemmDesc a{};
-        a.A = {compact ? lb.dgs + dir * 4L * H : dGd, 8L * H, 0, 0, 0};
-        if (dimg && !compact) a.a_pre = e->ioff(dimg, a.A.p - dG);
-        a.B = {xi.p, xi.ld, 0, 0, 0};
-        if (img_ok && l > 0) a.b_pre = lb.out_img[l - 1];
-        a.C = e->G + pd.wih;
-        a.ldc = In;
-        a.M = 4 * H;
-        a.N = In;
-        a.K = compact ? B * (T / lb.xf) : (int)R;
-        a.batch = 1;
-        a.flags = GEMM_TA | GEMM_TB | GEMM_ACCUM | (am ? GEMM_F16X2 : 0);
-        a.amax_a = am;                              // gradient slab: measured scale; the layer input is O(1)
-        a.ksplit = pick_ksplit(a.M, a.N, a.K);
-        hipStream_t wa = (dir == 1 && e->dw_over[0]) ? e->dw_over[0] : ws, wh = (dir == 1 && e->dw_over[1]) ? e->dw_over[1] : ws;
-        if (part != 2 || compact) PGEMM_ON(lb.big() ? SS_PROF_DEC_DW : SS_PROF_ENC_LSTM, a, wa);
+        hipStream_t wa = (dir == 1 && route.over_ih) ? route.over_ih : ws, wh = (dir == 1 && route.over_hh) ? route.over_hh : ws;
+        if (route.part != 2 || compact) {      // dW_ih[n][k] = sum_r dG[r][n] * X[r][k]
+            GemmDesc a = dw_desc({compact ? lb.dgs + dir * 4L * H : dGd, 8L * H, 0, 0, 0}, {xi.p, xi.ld, 0, 0, 0}, pd.wih, In, compact ? B * (T / lb.xf) : R, 1);
+            if (dimg && !compact) a.a_pre = e->ioff(dimg, a.A.p - dG);
+            if (img_ok && l > 0) a.b_pre = lb.out_img[l - 1];
+            PGEMM_ON(klass, a, wa);
+        }
         // dW_hh[n][k] = sum_r dG[r][n] * h_prev[r][k];  h_prev = out one row earlier (fwd) / later (reverse)
-        GemmDesc h{};
-        h.A = {dir == 0 ? dGd + 8L * H : dGd, 8L * H, 0, 0, 0};
+        GemmDesc h = dw_desc({dir == 0 ? dGd + 8L * H : dGd, 8L * H, 0, 0, 0}, {dir == 0 ? lb.out[l] : lb.out[l] + lb.ow() + H, lb.ow(), 0, 0, 0}, pd.whh, H, R - 1, 1);
         if (dimg) h.a_pre = e->ioff(dimg, h.A.p - dG);
-        h.B = {dir == 0 ? lb.out[l] : lb.out[l] + lb.ow() + H, lb.ow(), 0, 0, 0};
         if (img_ok) h.b_pre = dir == 0 ? lb.out_img[l] : e->ioff(lb.out_img[l], 2L * H + H);
-        h.C = e->G + pd.whh;
-        h.ldc = H;
-        h.M = 4 * H;
-        h.N = H;
-        h.K = (int)(R - 1);
-        h.batch = 1;
-        h.flags = GEMM_TA | GEMM_TB | GEMM_ACCUM | (am ? GEMM_F16X2 : 0);
-        h.amax_a = am;
-        h.ksplit = pick_ksplit(h.M, h.N, h.K);
-        PGEMM_ON(lb.big() ? SS_PROF_DEC_DW : SS_PROF_ENC_LSTM, h, wh);
+        PGEMM_ON(klass, h, wh);
         if (!bias_done) {     // the persistent backward kernel accumulates both bias gradients itself
             double* cpart;
             unsigned* cctr;
@@ -1570,16 +1586,9 @@ int lstm_weight_grads(ss_engine* e, LstmBlk& lb, int l, Slab xi, const float* am
             HIPCHK(colsum_acc(dGd, 8L * H, (int)R, 4 * H, e->G + pd.bih, cpart, cctr, ws));
             HIPCHK(hipMemcpyAsync(e->G + pd.bhh, e->G + pd.bih, 4L * H * 4, hipMemcpyDeviceToDevice, ws));
         }
-        // data parallel: this direction's parameters (W_ih, W_hh, b_ih, b_hh: contiguous in the arena) are final -- half a layer per
-        // collective keeps the communication stream busy 140 us earlier than a bucket per layer (modelled N = 8: the last collective ends
-        // closer to the backward's end)
-        if (&lb == &e->ld && e->dp_on && part == 0 && pd.bhh + 4L * H > pd.wih) {
-            if (wa != wh) return fail("internal: a direction's weight gradients on two streams under data parallelism");
-            CHK(dp_bucket(e, pd.wih, pd.bhh + 4L * H - pd.wih, wh));
-            e->dp_dir_buckets = true;
-        }
+        CHK(dir_bucket(pd, wa, wh));
     }
-    return 0;
+    return dir_buckets ? 1 : 0;
 }
 
 // input gradient of one layer for the slab rows [r0, r0 + nr):  dX = dG . W_ih  (both directions accumulate)
@@ -1615,7 +1624,7 @@ int lstm_input_grad(ss_engine* e, LstmBlk& lb, int l, Slab dxi, long r0, long nr
     // (round 2's kernel measured SLOWER with the weight image in format v2 on this transposing-read operand -- 573 us per step with it, 532
     // without -- so only the 16-bit data path, whose image GEMM reads it, passes that image)
     g.b_pre = e->img16() ? lb.wimg(l) : nullptr;
-    const bool dg16 = e->img16() && &lb == &e->ld && l < 3 && ((e->dg16_written >> l) & 1);      // the gradient slab's bf16 image (backward recurrence's storing wave)
+    const bool dg16 = e->img16() && &lb == &e->ld && l < 3 && ((e->bwd.dg16_written >> l) & 1);      // the gradient slab's bf16 image (backward recurrence's storing wave)
     if (dg16) g.a_pre = e->ioff(e->dg_img[l], r0 * 8L * H);
     g.C = dxi.p + r0 * dxi.ld;
     g.ldc = dxi.ld;
@@ -1651,11 +1660,11 @@ int lstm_input_grad(ss_engine* e, LstmBlk& lb, int l, Slab dxi, long r0, long nr
 // launches go to their branch stream.  A consumer that waits for it is not held up by whatever else shares a hardware queue with
 // `s`: an event recorded later would sit in that queue behind every packet enqueued in between (measured: the conv trunk's
 // backward idled 0.88 ms behind ~36 tiny weight-gradient launches of a sibling stream, profiles/r02/step_timeline_before.txt).
-int lstm_late_weights(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t ws, int l_hi = -1, int l_lo = 0);
+int lstm_late_weights(ss_engine* e, Backward& bw, LstmBlk& lb, Slab x, hipStream_t ws, int l_hi = -1, int l_lo = 0, DwRoute route = {});
 
 // late_w: enqueue the recurrence chain and the input gradients only; the caller enqueues the block's weight gradients later
 // (lstm_late_weights) -- after the phase's critical path -- on a stream it has ordered behind this chain.
-int lstm_bwd(ss_engine* e, LstmBlk& lb, const float* d_top, Slab x, Slab dx, hipStream_t s, hipEvent_t dx_ready = nullptr, bool late_w = false) {
+int lstm_bwd(ss_engine* e, Backward& bw, LstmBlk& lb, const float* d_top, Slab x, Slab dx, hipStream_t s, hipEvent_t dx_ready = nullptr, bool late_w = false) {
     const int B = e->curB, T = e->curT, H = lb.H;
     const long TP = T + 2 * HALO, R = (long)B * TP;
     const float* dcur = d_top;
@@ -1691,24 +1700,24 @@ int lstm_bwd(ss_engine* e, LstmBlk& lb, const float* d_top, Slab x, Slab dx, hip
                 const bool compact0 = l == 0 && lb.xf && dx.p == lb.d_xc;
                 const bool skip32 = dg16 && bias_in_kernel && lb.out_img_valid && lb.out_img[l] &&
                                     (l == 0 ? compact0 : (lb.wimg(l) != nullptr && lb.in_of(l) % 64 == 0)) && H % 64 == 0;
-                const int pi = prof_begin(e, SS_PROF_REC_BWD, s, 2.0 * 2 * B * T * 4.0 * H * H);
-                HIPCHK(lstm_seq_bwd(dG, e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.px_l(l), dcur, lb.csave[l], lb.sync_b(l),
-                                    e->sticky, am, bias_in_kernel ? e->G + lb.pd[l * 2].bih : nullptr,
-                                    bias_in_kernel ? e->G + lb.pd[l * 2 + 1].bih : nullptr, (l == 0 && lb.xf && dx.p == lb.d_xc) ? lb.dgs : nullptr,
-                                    (l == 0 && lb.xf && dx.p == lb.d_xc) ? lb.xf : 0, B, T, H, false, false, s, dg16 ? e->dg_img[l] : nullptr, (e->img16() ? 1 : 0) | (skip32 ? 4 : 0)));      // 1: products of the high fp16 pieces only (16-bit data path)
-                if (dg16) e->dg16_written |= 1 << l;
-                if (skip32) e->dg32_skipped |= 1 << l;
-                prof_end(e, pi, s);
+                {
+                    Prof pr(e, SS_PROF_REC_BWD, s, 2.0 * 2 * B * T * 4.0 * H * H);
+                    HIPCHK(lstm_seq_bwd(dG, e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.px_l(l), dcur, lb.csave[l], lb.sync_b(l),
+                                        e->sticky, am, bias_in_kernel ? e->G + lb.pd[l * 2].bih : nullptr,
+                                        bias_in_kernel ? e->G + lb.pd[l * 2 + 1].bih : nullptr, (l == 0 && lb.xf && dx.p == lb.d_xc) ? lb.dgs : nullptr,
+                                        (l == 0 && lb.xf && dx.p == lb.d_xc) ? lb.xf : 0, B, T, H, false, false, s, dg16 ? e->dg_img[l] : nullptr, (e->img16() ? 1 : 0) | (skip32 ? 4 : 0)));      // 1: products of the high fp16 pieces only (16-bit data path)
+                }
+                if (dg16) e->bwd.dg16_written |= 1 << l;
+                if (skip32) e->bwd.dg32_skipped |= 1 << l;
                 if (early16) {
                     if (l + 1 < lb.L && early_ready[l + 1]) {
                         HIPCHK(seq_gate(lb.sync_b(l), B, H, e->side));          // dispatched once this recurrence's grid is resident
-                        e->wq_mode = true;
-                        const int rc = lstm_weight_grads(e, lb, l + 1, Slab{lb.out[l], 2L * H}, am ? e->amax + lb.amax0 + l + 1 : nullptr, true, e->side);
-                        e->wq_mode = false;
-                        CHK(rc);
-                        e->dec_w_done |= 1 << (l + 1);
+                        DwRoute queued;
+                        queued.queue = true;
+                        if (const int r = lstm_weight_grads(e, bw, lb, l + 1, Slab{lb.out[l], 2L * H}, am ? e->amax + lb.amax0 + l + 1 : nullptr, true, e->side, queued); r < 0) return r;
+                        e->bwd.dec_w_done |= 1 << (l + 1);
                     }
-                    if (l >= 1 && l < 3 && dg16 && bias_in_kernel && lb.out_img[l] && lb.out_img[l - 1] && e->wq_next + 2 <= ss_engine::WQ_SLOTS) {
+                    if (l >= 1 && l < 3 && dg16 && bias_in_kernel && lb.out_img[l] && lb.out_img[l - 1] && e->bwd.wq_next + 2 <= ss_engine::WQ_SLOTS) {
                         CHK(fork_join(e, s, e->side));        // layer l's slab and image are complete behind this point
                         early_ready[l] = true;
                         e->side_used = true;
@@ -1735,9 +1744,10 @@ int lstm_bwd(ss_engine* e, LstmBlk& lb, const float* d_top, Slab x, Slab dx, hip
                     HIPCHK(lstm_step_bwd(dG, lb.wfrag[l], lb.gf + (st & 1) * half, lb.gf + ((st & 1) ^ 1) * half, dcur, lb.csave[l], lb.dc, B, T, H, st, s));
             }
         } else {
-            { const int pa_ = prof_begin(e, SS_PROF_ENC_REC, s, 0.0);
-            HIPCHK(lstm_small_bwd(dG, e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, dcur, lb.csave[l], B, T, H, s));
-            prof_end(e, pa_, s); }
+            {
+                Prof pr(e, SS_PROF_ENC_REC, s);
+                HIPCHK(lstm_small_bwd(dG, e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, dcur, lb.csave[l], B, T, H, s));
+            }
         }
         // Decoder on the persistent kernels: its weight-gradient GEMMs are held back until the whole recurrence chain
         // (layer L-1 .. 0 and the input gradients between them) is through.  Co-scheduled they do not fill idle cycles:
@@ -1762,31 +1772,32 @@ int lstm_bwd(ss_engine* e, LstmBlk& lb, const float* d_top, Slab x, Slab dx, hip
         // input gradient first (the next layer's recurrence needs it)
         if (dxi.p) CHK(lstm_input_grad(e, lb, l, dxi, 0, R, am, s));
         if (l == 0 && dx_ready) HIPCHK(hipEventRecord(dx_ready, s));
-        CHK(lstm_weight_grads(e, lb, l, xi, am, bias_in_kernel, ws));
+        if (const int r = lstm_weight_grads(e, bw, lb, l, xi, am, bias_in_kernel, ws); r < 0) return r;
         dcur = dxi.p;
     }
     if (persist && e->side && g_overlap && g_defer_dw && !late_w) {
         CHK(fork_join(e, s, e->side));
         e->side_used = true;
-        CHK(lstm_late_weights(e, lb, x, e->side));
+        CHK(lstm_late_weights(e, bw, lb, x, e->side));
     }
     return 0;
 }
 
 // all layers' weight / bias gradients of a block whose chain ran with deferred weights (the decoder's deferred batch; every block under late_w)
-int lstm_late_weights(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t ws, int l_hi, int l_lo) {
+int lstm_late_weights(ss_engine* e, Backward& bw, LstmBlk& lb, Slab x, hipStream_t ws, int l_hi, int l_lo, DwRoute route) {
     const int H = lb.H;
     const bool persist = lb.big() && g_persist && lstm_seq_supported(e->curB, H);
     for (int l = l_hi < 0 ? lb.L - 1 : l_hi; l >= l_lo; --l) {       // layers l_hi .. l_lo (default: all, last first)
-        if (&lb == &e->ld && ((e->dec_w_done >> l) & 1)) continue;        // went out beside a recurrence (early_dw)
+        if (&lb == &e->ld && ((e->bwd.dec_w_done >> l) & 1)) continue;        // went out beside a recurrence (early_dw)
         Slab xi = l == 0 ? x : Slab{lb.out[l - 1], lb.ow()};
         float* am = (persist && g_bwd_f16x2 && lb.amax0 >= 0) ? e->amax + lb.amax0 + l : nullptr;
         const bool bias_in_kernel = persist && !g_deterministic && lb.pd[l * 2].bhh == lb.pd[l * 2].bih + 4L * H && lb.pd[l * 2 + 1].bhh == lb.pd[l * 2 + 1].bih + 4L * H;
-        e->dp_dir_buckets = false;
-        CHK(lstm_weight_grads(e, lb, l, xi, am, bias_in_kernel, ws, (&lb == &e->ld && ((e->dec_ih_done >> l) & 1)) ? 2 : 0));
+        route.part = (&lb == &e->ld && ((e->bwd.dec_ih_done >> l) & 1)) ? 2 : 0;
+        const int dir_buckets = lstm_weight_grads(e, bw, lb, l, xi, am, bias_in_kernel, ws, route);
+        if (dir_buckets < 0) return dir_buckets;
         // this layer's gradients (both directions: W_ih, W_hh, b_ih, b_hh -- contiguous in the arena) are final (unless each direction has
         // already gone out on its own)
-        if (&lb == &e->ld && !e->dp_dir_buckets) CHK(dp_bucket(e, lb.pd[l * 2].wih, lb.pd[l * 2 + 1].bhh + 4L * H - lb.pd[l * 2].wih, ws));
+        if (&lb == &e->ld && !dir_buckets) CHK(dp_bucket(e, lb.pd[l * 2].wih, lb.pd[l * 2 + 1].bhh + 4L * H - lb.pd[l * 2].wih, ws));
     }
     return 0;
 }
@@ -1820,7 +1831,7 @@ int act_scales_all(ss_engine* e, hipStream_t s) {
 
 // ---- whole-model schedules ---------------------------------------------------------------------------------
 // Encoder_7 (G3) / Encoder_6 (G6) trunk + their LSTMs, Encoder_t, decoder, head.  Inputs already in in_mel/in_f0/org/emb.
-int forward_core(ss_engine* e, bool training, const float* scales, const int* len_seg, int draw0, hipStream_t s) {
+int forward_core(ss_engine* e, bool training, const float* scales, const int* len_seg, int draw0, hipStream_t s, const FusedForward& fused = {}) {
     const int B = e->curB, T = e->curT;
     e->part_off = 0;           // split-K scratch: every launch of a step gets its own region; the previous step is through (stream order) when this one's first kernel runs
     const long TP = T + 2 * HALO;
@@ -1832,8 +1843,8 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     // only); after the trunk the two encoder BLSTMs run side by side (`s`, `b1`).  Everything joins at the decoder input.
     const bool par = e->side && e->side2 && g_overlap;
     hipStream_t b1 = par ? e->side : s, b2 = par ? e->side2 : s;
-    e->grads_zeroed = false;               // set again below when this forward belongs to a fused training step
-    e->bwd_sync_zeroed = false;
+    e->fwd.grads_zeroed = false;               // set again below when this forward belongs to a fused training step
+    e->fwd.bwd_sync_zeroed = false;
     {   // every conv block's per-step weight re-layout (and the images of the packed weights) in one launch
         ConvPackTable pt{};
         pt.img_bf16 = e->img16();
@@ -1843,24 +1854,23 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
             const bool img = cb->img_ok();
             pt.t[pt.n++] = {e->P + cb->w, cb->wf, cb->wb, img ? cb->wf_img : nullptr, img ? cb->wb_img : nullptr, cb->Co, cb->Ci, cb->Cp};
         }
-        const int pa_ = prof_begin(e, SS_PROF_PREP, s, 0.0);
+        Prof pr(e, SS_PROF_PREP, s);
         HIPCHK(conv_pack_many(pt, s));
-        prof_end(e, pa_, s);
     }
     CHK(act_scales_all(e, s));             // before every branch forks: the scale words of the conv blocks' outputs
     if (par) CHK(fork_join(e, s, b2));
-    if (e->late_org) {
+    if (fused.late_org) {
         const ss_hparams& hh = e->hp;
-        HIPCHK(copy_rows(e->late_org, hh.dim_freq, (long)T * hh.dim_freq, e->org + HALO * hh.dim_freq, hh.dim_freq, TP * hh.dim_freq, B, T,
+        HIPCHK(copy_rows(fused.late_org, hh.dim_freq, (long)T * hh.dim_freq, e->org + HALO * hh.dim_freq, hh.dim_freq, TP * hh.dim_freq, B, T,
                          hh.dim_freq, b2));
-        if (e->late_emb) HIPCHK(hipMemcpyAsync(e->emb, e->late_emb, (long)B * hh.dim_spk_emb * 4, hipMemcpyDeviceToDevice, b2));
+        if (fused.late_emb) HIPCHK(hipMemcpyAsync(e->emb, fused.late_emb, (long)B * hh.dim_spk_emb * 4, hipMemcpyDeviceToDevice, b2));
     }
     // Encoder_7's content (512 ch) and pitch (256 ch) stacks only share the random-resampling PLAN of each layer (model.py:199-206: one
     // warp applied to the concatenation), and the plans depend on the draws alone.  With branch streams the plans are computed first thing
     // on the branch stream and the two stacks run as independent chains on `s` and `b1` -- conv, GroupNorm, gather of their OWN columns --
     // down to their BLSTMs, instead of meeting before every gather.
     const bool indep = g3 && par;
-    e->xf_img_valid = indep && training && e->xf_img[0] && ((e->precision == SS_PRECISION_F32 && g_fwd_f16x2) || (e->img16() && g_gn_gather));     // only fp16 x 2 / 16-bit-path GEMMs read images
+    e->fwd.xf_img_valid = indep && training && e->xf_img[0] && ((e->precision == SS_PRECISION_F32 && g_fwd_f16x2) || (e->img16() && g_gn_gather));     // only fp16 x 2 / 16-bit-path GEMMs read images
     hipEvent_t plans = nullptr;
     if (indep && training) {
         for (int i = 0; i < 3; ++i)
@@ -1885,16 +1895,16 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
         CHK(lstm_prep(e, e->lt, tb, b2));
         CHK(lstm_prep(e, e->ld, tb, b2));
         HIPCHK(prep_run(tb, b2));
-        if (e->prezero) {        // nothing touches the gradient arena before the decoder backward; b2 is joined long before
+        if (fused.prezero) {     // nothing touches the gradient arena before the decoder backward; b2 is joined long before
             HIPCHK(hipMemsetAsync(e->G, 0, e->arena * 4, b2));
             HIPCHK(hipMemsetAsync(e->amax, 0, 16 * 4, b2));
-            e->grads_zeroed = true;
+            e->fwd.grads_zeroed = true;
             // the backward recurrences' group words and exchange tiles (nothing in the forward touches them): zeroed here, the backward
             // needs no fork / memset / join between the head's gradient and its first recurrence (two event hops on the critical path)
             if (e->ld.big() && g_persist && lstm_seq_supported(e->curB, e->ld.H)) {
                 HIPCHK(hipMemsetAsync(e->ld.zb, 0, e->ld.zb_bytes, b2));
                 if (e->wq_pool) HIPCHK(hipMemsetAsync(e->wq_pool, 0, ss_engine::WQ_SLOTS * 16, b2));
-                e->bwd_sync_zeroed = true;
+                e->fwd.bwd_sync_zeroed = true;
             }
         }
         // fp16 x 2 products scale WEIGHTS by a fixed 16 (forward and gradient contractions alike, and the persistent recurrences' W_hh):
@@ -1914,12 +1924,12 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
         // launches of b2's work).  So: first trunk layer, and only then the rest of b2's work.
         if (i == 1 && !prio_fwd) CHK(branch_work());
         if (indep) {
-            const float* im = (e->xf_img_valid && i > 0) ? e->xf_img[i - 1] : nullptr;
+            const float* im = (e->fwd.xf_img_valid && i > 0) ? e->xf_img[i - 1] : nullptr;
             Slab x1 = i == 0 ? Slab{e->in_mel, e->hp.dim_freq} : Slab{e->xf[i - 1], CE, im, e->act_scale + e->c1[i - 1].scale_i};
             Slab x2 = i == 0 ? Slab{e->in_f0, e->f0p} : Slab{e->xf[i - 1] + off2, CE, im ? e->ioff(im, off2) : nullptr, e->act_scale + e->c2[i - 1].scale_i};
             if (training && g_gn_gather) {       // conv -> [GroupNorm + ReLU + gather] per stack: the normalised slab is never written
                 InterpPlan& pl = e->plan[draw0 + i];
-                float* gi = (e->xf_img_valid && e->xf_img[i]) ? e->ioff(e->xf_img[i], HALO * CE) : nullptr;
+                float* gi = (e->fwd.xf_img_valid && e->xf_img[i]) ? e->ioff(e->xf_img[i], HALO * CE) : nullptr;
                 CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, b1, &pl, e->xf[i] + HALO * CE + off2, CE, gi ? e->ioff(gi, off2) : nullptr, i == 0 ? plans : nullptr));
                 CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s, &pl, e->xf[i] + HALO * CE, CE, gi, i == 0 ? plans : nullptr));
                 continue;
@@ -1932,7 +1942,7 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
                     HIPCHK(hipStreamWaitEvent(b1, plans, 0));
                     HIPCHK(hipStreamWaitEvent(s, plans, 0));
                 }
-                float* gi = (e->xf_img_valid && !e->img16() && e->xf_img[i]) ? e->xf_img[i] + HALO * CE : nullptr;      // (the separate gather writes format-v2 images only)
+                float* gi = (e->fwd.xf_img_valid && !e->img16() && e->xf_img[i]) ? e->xf_img[i] + HALO * CE : nullptr;      // (the separate gather writes format-v2 images only)
                 HIPCHK(interp_gather(pl, e->act + HALO * CE + off2, CE, TP * CE, e->xf[i] + HALO * CE + off2, CE, TP * CE, CE - off2, B, b1,
                                      gi ? gi + off2 : nullptr, e->act_scale + e->c2[i].scale_i));
                 HIPCHK(interp_gather(pl, e->act + HALO * CE, CE, TP * CE, e->xf[i] + HALO * CE, CE, TP * CE, off2, B, s, gi, e->act_scale + e->c1[i].scale_i));
@@ -2002,9 +2012,9 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     d.ksplit = 1;
     flatten_rows(d, B, T);
     PGEMM_FWD_ON(SS_PROF_HEAD, d, s);
-    e->fwd_training = training;
-    e->enc_plan0 = draw0;
-    e->have_fwd = true;
+    e->fwd.training = training;
+    e->fwd.enc_plan0 = draw0;
+    e->fwd.have = true;
     return 0;
 }
 
@@ -2038,27 +2048,23 @@ int head_weight_grads(ss_engine* e, hipStream_t st) {
 
 // late: only the critical chain is enqueued here (head input gradient, recurrences, input gradients); the decoder's and the head's
 // weight gradients are enqueued by backward_encoder behind ITS critical path, ordered after the chain through ev_join[1]
-int backward_decoder(ss_engine* e, hipStream_t s, bool late = false) {
-    if (!e->have_fwd) return fail("backward without a preceding forward");
+int backward_decoder(ss_engine* e, Backward& bw, hipStream_t s, bool late = false) {
+    if (!e->fwd.have) return fail("backward without a preceding forward");
     const int B = e->curB, T = e->curT;
     const long TP = T + 2 * HALO, R = (long)B * TP;
-    if (!e->grads_zeroed) {
+    if (!e->fwd.grads_zeroed) {
         HIPCHK(hipMemsetAsync(e->G, 0, e->arena * 4, s));
         HIPCHK(hipMemsetAsync(e->amax, 0, 16 * 4, s));
     }
-    e->grads_zeroed = false;
+    e->fwd.grads_zeroed = false;
     // fragment-major W_hh^T of the decoder recurrences (overwrites the forward layout, no longer needed), beside the head
     const bool persist_dec = e->ld.big() && g_persist && lstm_seq_supported(e->curB, e->ld.H);
-    const bool prezeroed = e->bwd_sync_zeroed && persist_dec;       // the fused step's forward has done it on its branch stream
-    e->bwd_sync_zeroed = false;
+    const bool prezeroed = e->fwd.bwd_sync_zeroed && persist_dec;       // the fused step's forward has done it on its branch stream
+    e->fwd.bwd_sync_zeroed = false;
     const bool par = e->side2 && g_overlap && !prezeroed;
     hipStream_t b2 = par ? e->side2 : s;
     if (par) CHK(fork_join(e, s, b2));
-    e->dec_ih_done = 0;
-    e->dec_w_done = 0;
-    e->dg16_written = 0;
-    e->dg32_skipped = 0;
-    e->wq_next = 0;
+    e->bwd = {};
     if (e->ld.big() && !prezeroed) {
         if (g_persist && lstm_seq_supported(e->curB, e->ld.H)) {
             // the group counters of every layer and their exchange tiles (tags start at 0)
@@ -2074,7 +2080,7 @@ int backward_decoder(ss_engine* e, hipStream_t s, bool late = false) {
     const long HD = 2L * e->ld.H;
     const bool defer_head = e->ld.big() && g_persist && lstm_seq_supported(B, e->ld.H) && e->side && g_overlap && g_defer_dw;
     late = late && defer_head;
-    e->dec_w_pending = late;
+    bw.dec_w_pending = late;
     {
         if (!defer_head) CHK(head_weight_grads(e, s));
         GemmDesc g{};
@@ -2091,8 +2097,8 @@ int backward_decoder(ss_engine* e, hipStream_t s, bool late = false) {
         PGEMM_ON(SS_PROF_HEAD, g, s);
     }
     if (par) CHK(fork_join(e, b2, s));
-    if (dec_compact(e)) CHK(lstm_bwd(e, e->ld, e->d_top, Slab{e->ld.xc, e->dec_in_dim}, Slab{e->ld.d_xc, e->dec_in_dim}, s, nullptr, late));
-    else CHK(lstm_bwd(e, e->ld, e->d_top, Slab{e->dec_in, e->dec_in_dim}, Slab{e->d_dec_in, e->dec_in_dim}, s, nullptr, late));
+    if (dec_compact(e)) CHK(lstm_bwd(e, bw, e->ld, e->d_top, Slab{e->ld.xc, e->dec_in_dim}, Slab{e->ld.d_xc, e->dec_in_dim}, s, nullptr, late));
+    else CHK(lstm_bwd(e, bw, e->ld, e->d_top, Slab{e->dec_in, e->dec_in_dim}, Slab{e->d_dec_in, e->dec_in_dim}, s, nullptr, late));
     if (late) HIPCHK(hipEventRecord(e->ev_join[1], s));          // the chain is through: what the side stream's batch waits for
     else if (defer_head) CHK(head_weight_grads(e, e->side));      // behind the decoder's weight gradients, ordered after the chain by lstm_bwd's fork
                                                             // (measured: on the third branch stream instead 6.395 vs 6.365 ms)
@@ -2104,18 +2110,13 @@ int backward_decoder(ss_engine* e, hipStream_t s, bool late = false) {
 
 // everything below the decoder input: code gradients, encoder BLSTMs, conv trunks.  Touches only gradient-arena
 // offsets below the decoder's, so a data-parallel caller can all-reduce the decoder range meanwhile.
-int backward_encoder(ss_engine* e, hipStream_t s) {
-    e->unpack.n = 0;
-    e->unpack_later = !e->dp_on;       // (data parallel: a trunk layer's bucket leaves right behind its block)
-    struct UnpackOff {
-        ss_engine* e;
-        ~UnpackOff() { e->unpack_later = false; }
-    } unpack_off{e};
+int backward_encoder(ss_engine* e, Backward& bw, hipStream_t s) {
+    bw.unpack_later = !e->dp_on;       // (data parallel: a trunk layer's bucket leaves right behind its block)
     const int B = e->curB, T = e->curT;
     const long TP = T + 2 * HALO, R = (long)B * TP;
     const int CE = e->CE;
     const bool g3 = e->kind == SS_GENERATOR_3;
-    const bool training = e->fwd_training;
+    const bool training = e->fwd.training;
     const ss_hparams& h = e->hp;
     CodeSrc src[3];
     int n = 0;
@@ -2139,13 +2140,7 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
     // Encoder_t's whole backward) follow below, each ordered behind its producer by an event that was recorded when the producer
     // was enqueued.
     const bool prio = par && g_prio_order && !e->l2.big() && !e->l1.big() && !e->lt.big();
-    struct WgDefer {           // the small blocks' weight gradients of this backward: collected, launched once on b3 below (prio schedule)
-        ss_engine* e;
-        ~WgDefer() { e->wg_defer = false; e->wg.n = 0; e->wg.tiles_total = 0; }
-    } wg_scope{e};
-    e->wg.n = 0;
-    e->wg.tiles_total = 0;
-    e->wg_defer = prio;
+    bw.wg_defer = prio;        // the small blocks' weight gradients of this backward: collected, launched once on b3 below (prio schedule)
     if (par) {
         if (prio) HIPCHK(hipEventRecord(e->ev_join[2], s));                 // dec_in_grad done: what Encoder_t's backward needs
         CHK(fork_join(e, s, b2));
@@ -2156,20 +2151,20 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
     if (par && !prio) CHK(fork_join(e, b2, b3));
     // encoder BLSTMs -> gradient of the last fused slab
     const bool early = par && !e->l2.big();         // the join event of the lstm_2 branch is taken as soon as its last kernel is queued
-    CHK(lstm_bwd(e, e->l2, e->d_o2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, Slab{e->d_xf + off2, CE}, b2, (early || prio) ? e->ev_join[0] : nullptr, prio));
+    CHK(lstm_bwd(e, bw, e->l2, e->d_o2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, Slab{e->d_xf + off2, CE}, b2, (early || prio) ? e->ev_join[0] : nullptr, prio));
     if (g3) {
-        CHK(lstm_bwd(e, e->l1, e->d_o1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, Slab{e->d_xf, CE}, s, nullptr, prio));
+        CHK(lstm_bwd(e, bw, e->l1, e->d_o1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, Slab{e->d_xf, CE}, s, nullptr, prio));
         if (prio) HIPCHK(hipEventRecord(e->ev_join[3], s));                 // lstm_1's chain done: its weight gradients may start
     }
     if (!prio) {
         // Encoder_t
-        CHK(lstm_bwd(e, e->lt, e->d_ot, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, Slab{e->d_act_t, h.dim_enc_2}, b3));
-        CHK(conv_block_bwd(e, e->ct, Slab{e->d_act_t, h.dim_enc_2}, Slab{e->org, h.dim_freq}, Slab{nullptr, 0}, b3));
+        CHK(lstm_bwd(e, bw, e->lt, e->d_ot, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, Slab{e->d_act_t, h.dim_enc_2}, b3));
+        CHK(conv_block_bwd(e, bw, e->ct, Slab{e->d_act_t, h.dim_enc_2}, Slab{e->org, h.dim_freq}, Slab{nullptr, 0}, b3));
     }
     if (early || prio) HIPCHK(hipStreamWaitEvent(s, e->ev_join[0], 0));
     else if (par) CHK(fork_join(e, b2, s));
     // backward_decoder(late): the decoder's (layers l_hi .. l_lo) and, with its layer 0, the head's weight gradients, behind the decoder chain
-    int dec_next = e->dec_w_pending ? e->ld.L - 1 : -1;       // next decoder layer whose weight gradients are still to be enqueued
+    int dec_next = bw.dec_w_pending ? e->ld.L - 1 : -1;       // next decoder layer whose weight gradients are still to be enqueued
     hipStream_t dec_other[2] = {nullptr, nullptr};      // streams other than the side stream that carry decoder weight gradients (tail split)
     auto dec_late = [&](int l_lo, hipStream_t ws = nullptr, hipStream_t over_ih = nullptr, hipStream_t over_hh = nullptr) -> int {
         if (dec_next < l_lo) return 0;
@@ -2179,42 +2174,41 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
                 if (dec_other[0] != o && dec_other[1] != o) dec_other[dec_other[0] ? 1 : 0] = o;
                 HIPCHK(hipStreamWaitEvent(o, e->ev_join[1], 0));
             }
-        struct Over {
-            ss_engine* e;
-            ~Over() { e->dw_over[0] = e->dw_over[1] = nullptr; }
-        } over_scope{e};
-        e->dw_over[0] = over_ih;
-        e->dw_over[1] = over_hh;
         if (dec_next == e->ld.L - 1) HIPCHK(hipStreamWaitEvent(e->side, e->ev_join[1], 0));
         if (ws != e->side) {
             if (dec_other[0] != ws && dec_other[1] != ws) dec_other[dec_other[0] ? 1 : 0] = ws;
             HIPCHK(hipStreamWaitEvent(ws, e->ev_join[1], 0));
         }
-        CHK(lstm_late_weights(e, e->ld, dec_compact(e) ? Slab{e->ld.xc, e->dec_in_dim} : Slab{e->dec_in, e->dec_in_dim}, ws, dec_next, l_lo));
+        DwRoute route;
+        route.over_ih = over_ih;
+        route.over_hh = over_hh;
+        CHK(lstm_late_weights(e, bw, e->ld, dec_compact(e) ? Slab{e->ld.xc, e->dec_in_dim} : Slab{e->dec_in, e->dec_in_dim}, ws, dec_next, l_lo, route));
         dec_next = l_lo - 1;
         if (l_lo == 0) {
             CHK(head_weight_grads(e, ws));
-            e->dec_w_pending = false;
+            bw.dec_w_pending = false;
             for (hipStream_t o : dec_other)
                 if (o) CHK(fork_join(e, o, e->side));      // one join for the end of the step; the early optimiser update below reads what they wrote
-            if (e->adam_early && !e->dp_on && e->Mm && e->Vv) {
+            if (bw.adam_early && !e->dp_on && e->Mm && e->Vv) {
                 // every persistent recurrence and the parameter guard ran before the event this stream waited for: the status word is final
                 const long from = ss_grad_split(e);
                 if (e->clip_max > 0.0f) {
                     // clipping: no element may be updated before the norm of the whole arena is known -- this range's share of the sum
                     // of squares takes the early update's place beside the encoder backward (adam_enqueue finalises)
                     if (from == clip_split(e)) {
-                        { const int pa_ = prof_begin(e, SS_PROF_ADAM, e->side, 0.0);
-                        HIPCHK(grad_sumsq(e->G, e->segs, from, e->status_off, e->clip_part + clip_wgs_lo(e), e->side));
-                        prof_end(e, pa_, e->side); }
-                        e->clip_early_from = from;
+                        {
+                            Prof pr(e, SS_PROF_ADAM, e->side);
+                            HIPCHK(grad_sumsq(e->G, e->segs, from, e->status_off, e->clip_part + clip_wgs_lo(e), e->side));
+                        }
+                        bw.clip_early_from = from;
                     }
                 } else if (from % 4 == 0 && from < e->arena) {
                     HIPCHK(adam_prepare(e->adam, e->sticky, nullptr, e->side));
-                    { const int pa_ = prof_begin(e, SS_PROF_ADAM, e->side, 0.0);
-                    HIPCHK(adam_range(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, e->adam_early_gs, e->side));
-                    prof_end(e, pa_, e->side); }
-                    e->adam_early_from = from;
+                    {
+                        Prof pr(e, SS_PROF_ADAM, e->side);
+                        HIPCHK(adam_range(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, bw.adam_gs, e->side));
+                    }
+                    bw.adam_early_from = from;
                 }
             }
         }
@@ -2239,27 +2233,27 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
     hipStream_t cs = e->dp_on ? b3 : b2;
     if (chain_par && e->dp_on) HIPCHK(hipStreamWaitEvent(b3, e->ev_join[0], 0));      // d_xf's pitch columns (lstm_2's input gradient) and the zeroed conv images
     // weight gradients off the dependent chain (g_conv_dw_off): Generator_6's single chain, the second branch stream is idle behind lstm's backward
-    const bool dw_off = g_conv_dw_off == 1 && training && !g3 && par && prio && !e->dp_on && g_gn_gather && e->unpack_later && b2 != s && e->d_act_l[0] && e->d_act_l[1];
+    const bool dw_off = g_conv_dw_off == 1 && training && !g3 && par && prio && !e->dp_on && g_gn_gather && bw.unpack_later && b2 != s && e->d_act_l[0] && e->d_act_l[1];
     hipStream_t dw_s = dw_off ? b2 : nullptr;
     // conv trunk, last layer first
     for (int i = 2; i >= 0; --i) {
         float* dy = e->d_xf;
         // training: the adjoint of the layer's resampling, d_xf -> d_act; fused into each block's GroupNorm backward (g_gn_gather) or as a pass of its own
-        const InterpPlan* sc = (training && g_gn_gather) ? &e->plan[e->enc_plan0 + i] : nullptr;
+        const InterpPlan* sc = (training && g_gn_gather) ? &e->plan[e->fwd.enc_plan0 + i] : nullptr;
         const float* sc_src = e->d_xf + HALO * CE;
         if (training) {
-            if (!sc) HIPCHK(interp_scatter(e->plan[e->enc_plan0 + i], e->d_xf + HALO * CE, CE, TP * CE, e->d_act + HALO * CE, CE, TP * CE, CE, B, s));
+            if (!sc) HIPCHK(interp_scatter(e->plan[e->fwd.enc_plan0 + i], e->d_xf + HALO * CE, CE, TP * CE, e->d_act + HALO * CE, CE, TP * CE, CE, B, s));
             dy = (dw_off && i > 0) ? e->d_act_l[i - 1] : e->d_act;
         }
         // input gradients of layer i become d_xf (the gradient of xf[i-1]); dy is consumed before it is overwritten
         // only when dy != d_xf, so in eval mode the input gradient goes through d_act instead.
         float* dxbuf = training ? e->d_xf : e->d_act;
         // the resampled activations also exist as pre-split images when the forward's gathers wrote them (training, independent trunk chains)
-        const float* bim = (training && e->xf_img_valid && i > 0) ? e->xf_img[i - 1] : nullptr;
+        const float* bim = (training && e->fwd.xf_img_valid && i > 0) ? e->xf_img[i - 1] : nullptr;
         if (!chain_par && i == 0 && g3 && par && !e->dp_on) CHK(fork_join(e, s, b2));      // tail_par below: the pitch block's stream forks BEFORE the content block is enqueued
         if (g3) {
             Slab x1 = i == 0 ? Slab{e->in_mel, h.dim_freq} : Slab{e->xf[i - 1], CE, bim, e->act_scale + e->c1[i - 1].scale_i};
-            CHK(conv_block_bwd(e, e->c1[i], Slab{dy, CE}, x1, i > 0 ? Slab{dxbuf, CE} : Slab{nullptr, 0}, s, sc, sc_src, CE));
+            CHK(conv_block_bwd(e, bw, e->c1[i], Slab{dy, CE}, x1, i > 0 ? Slab{dxbuf, CE} : Slab{nullptr, 0}, s, sc, sc_src, CE));
         }
         Slab x2 = i == 0 ? Slab{e->in_f0, e->f0p} : Slab{e->xf[i - 1] + off2, CE, bim ? e->ioff(bim, off2) : nullptr, e->act_scale + e->c2[i - 1].scale_i};
         // Layer 0 is the step's tail: the decoder's weight gradients are through by then, and each of its two weight-gradient GEMMs alone
@@ -2267,7 +2261,7 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
         // data parallelism, where that stream carries the collectives.)
         const bool tail_par = chain_par || (i == 0 && g3 && par && !e->dp_on);
         hipStream_t s2 = tail_par ? (chain_par ? cs : b2) : s;
-        CHK(conv_block_bwd(e, e->c2[i], Slab{dy + off2, CE}, x2, i > 0 ? Slab{dxbuf + off2, CE} : Slab{nullptr, 0}, s2, sc, sc_src + off2, CE, (dw_off && i > 0) ? dw_s : nullptr));
+        CHK(conv_block_bwd(e, bw, e->c2[i], Slab{dy + off2, CE}, x2, i > 0 ? Slab{dxbuf + off2, CE} : Slab{nullptr, 0}, s2, sc, sc_src + off2, CE, (dw_off && i > 0) ? dw_s : nullptr));
         if (tail_par && (!chain_par || (i == 0 && !e->dp_on))) CHK(fork_join(e, b2, s));      // (chain_par: the two chains meet once, behind layer 0; data parallel: where the third branch stream joins below)
         if (i > 0) {           // the two wide layers' parameters (weight, bias, GroupNorm affine: contiguous) are final; layer 0 rides the last bucket
             if (g3) CHK(dp_bucket(e, e->c1[i].w, e->c1[i].be + e->c1[i].Co - e->c1[i].w, s));
@@ -2282,7 +2276,7 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
     // ---- everything that only has to be finished by the end of the step
     // (tail split: on the side stream alone the decoder's twelve weight-gradient GEMMs end ~450 us after every other stream -- its last layer and
     // the head go behind a stream that ends early instead)
-    if (!e->dp_on && prio && chain_par && e->dec_w_pending && e->ld.L == 3 && g_dec_tail_split) {
+    if (!e->dp_on && prio && chain_par && bw.dec_w_pending && e->ld.L == 3 && g_dec_tail_split) {
         const int m = g_dec_tail_split;
         //                              m:        1        2        3    4        5        6
         hipStream_t for_l1 = m == 4 || m == 5 ? b3 : (m == 6 ? b2 : nullptr);                    // layer 1 (nullptr: side stream)
@@ -2301,31 +2295,27 @@ int backward_encoder(ss_engine* e, hipStream_t s) {
         // five launches; the BLSTMs' weight gradients (all three blocks: ONE fused launch) only have to be done by the end of the step
         // (Generator_6 32 x 192 bf16 2.26 -> 2.23 ms, 16 x 128 3.20 -> 3.18 against the BLSTMs' weight gradients in front; headline unchanged)
         HIPCHK(hipStreamWaitEvent(b3, e->ev_join[2], 0));                   // d_ot from dec_in_grad
-        CHK(lstm_bwd(e, e->lt, e->d_ot, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, Slab{e->d_act_t, h.dim_enc_2}, b3));
-        CHK(conv_block_bwd(e, e->ct, Slab{e->d_act_t, h.dim_enc_2}, Slab{e->org, h.dim_freq}, Slab{nullptr, 0}, b3));
+        CHK(lstm_bwd(e, bw, e->lt, e->d_ot, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, Slab{e->d_act_t, h.dim_enc_2}, b3));
+        CHK(conv_block_bwd(e, bw, e->ct, Slab{e->d_act_t, h.dim_enc_2}, Slab{e->org, h.dim_freq}, Slab{nullptr, 0}, b3));
         HIPCHK(hipStreamWaitEvent(b3, e->ev_join[0], 0));                   // lstm_2's pre-activation gradients (and the zeroed conv images)
-        CHK(lstm_late_weights(e, e->l2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, b3));
+        CHK(lstm_late_weights(e, bw, e->l2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, b3));
         if (g3) {
             HIPCHK(hipStreamWaitEvent(b3, e->ev_join[3], 0));
-            CHK(lstm_late_weights(e, e->l1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, b3));
+            CHK(lstm_late_weights(e, bw, e->l1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, b3));
         }
-        CHK(wgrad_flush(e, b3));                   // Encoder_t's, lstm_2's and both layers of lstm_1's: one launch
-        e->wg_defer = false;
+        CHK(wgrad_flush(e, bw, b3));               // Encoder_t's, lstm_2's and both layers of lstm_1's: one launch
     }
 
     if (par) CHK(fork_join(e, b3, s));
     if (dw_off) CHK(fork_join(e, dw_s, s));
     CHK(join_side(e, s));
-    if (e->unpack.n) {
-        HIPCHK(conv_unpack_grads(e->unpack, s));
-        e->unpack.n = 0;
-    }
+    if (bw.unpack.n) HIPCHK(conv_unpack_grads(bw.unpack, s));
     return 0;
 }
 
-int backward_core(ss_engine* e, hipStream_t s) {
-    CHK(backward_decoder(e, s, g_prio_order));
-    return backward_encoder(e, s);
+int backward_core(ss_engine* e, Backward& bw, hipStream_t s) {
+    CHK(backward_decoder(e, bw, s, g_prio_order));
+    return backward_encoder(e, bw, s);
 }
 
 // Generator_3's speaker embedding enters decoder layer 0 as the last dim_spk_emb columns of every frame's input row (model.py:308-309):
@@ -2339,21 +2329,10 @@ int speaker_input_grad(ss_engine* e, float* dc, hipStream_t s) {
     const float* dg = compact ? lb.dgs : lb.gates[0] + HALO * 8L * H;
     const long bs = compact ? (long)(T / lb.xf) * 8 * H : TP * 8L * H;
     const int rows = compact ? T / lb.xf : T;
-    if (!compact && (e->dg32_skipped & 1)) return fail("internal: decoder layer 0's fp32 gradient slab was not written");
+    if (!compact && (e->bwd.dg32_skipped & 1)) return fail("internal: decoder layer 0's fp32 gradient slab was not written");
     HIPCHK(spk_grad(dg, 8L * H, bs, rows, e->P + lb.pd[0].wih, e->P + lb.pd[1].wih, lb.In, lb.xcols, 4 * H, e->hp.dim_spk_emb, dc, B, s));
     return 0;
 }
-
-// one ss_g*_backward_inputs call: the layer-0 blocks' input-gradient targets are set for its backward and cleared on every way out
-struct InputGradTargets {
-    ss_engine* e;
-    ~InputGradTargets() {
-        for (ConvBlk* cb : {&e->c1[0], &e->c2[0], &e->ct}) {
-            cb->dx_out = nullptr;
-            cb->dx_ld = 0;
-        }
-    }
-};
 
 }  // namespace
 
@@ -2483,10 +2462,7 @@ long ss_arena_numel(const ss_engine* e) { return e->arena; }
 // split-K scratch of the image GEMM behind the planned workspace (never zeroed, independent of the geometry): partial slabs have the
 // size of weight tensors, so 16 arenas' worth holds a step's launches at ksplit <= 8 with room to spare
 static long part_floats(const ss_engine* e) { return e->kind == SS_INTERP_ONLY ? 0 : 16 * ((e->arena + 63) & ~63L) + (32L << 20); }      // + 32 M floats: the small generator's deterministic mode, column sums, fused encoder weight gradients
-static long plan_bytes(const ss_engine* e) {
-    ss_engine tmp = *e;             // dry run on a copy: carve() assigns the slab pointers
-    return (tmp.carve(e->maxB, e->maxT, false) + 255) & ~255L;
-}
+static long plan_bytes(const ss_engine* e) { return (carve(*e, e->maxB, e->maxT) + 255) & ~255L; }
 long ss_workspace_bytes(const ss_engine* e) { return plan_bytes(e) + part_floats(e) * 4; }
 
 long ss_plan_bytes(const ss_engine* e, int B, int T) {
@@ -2495,8 +2471,7 @@ long ss_plan_bytes(const ss_engine* e, int B, int T) {
     if (T < 8 || T > SS_MAX_EVAL_FRAMES) return fail("ss_plan_bytes: frames outside 8 .. SS_MAX_EVAL_FRAMES");
     if (e->kind != SS_INTERP_ONLY && (T % e->hp.freq || T % e->hp.freq_2 || T % e->hp.freq_3))
         return fail("ss_plan_bytes: T must be a multiple of the code down-sampling factors (model.py:87,223-227)");
-    ss_engine tmp = *e;             // dry run on a copy, as plan_bytes
-    return ((tmp.carve(B, T, false) + 255) & ~255L) + part_floats(e) * 4;
+    return ((carve(*e, B, T) + 255) & ~255L) + part_floats(e) * 4;
 }
 
 static_assert(sizeof(AdamState) <= 256, "the Adam state is the workspace's first 256 bytes");
@@ -2517,11 +2492,11 @@ int ss_set_workspace(ss_engine* e, void* ws_dev, long bytes, void* stream) {
     e->part_cap = part_floats(e);
     e->part_off = 0;
     e->curB = e->curT = 0;          // the next call plans (and zeroes) its geometry in the new workspace
-    e->have_fwd = false;
+    e->fwd = {};
     // the head of the workspace (the Adam state at offset 0, 256 bytes) survives, as across geometry changes; the rest starts zero
     HIPCHK(hipMemcpyAsync(e->ws, old, 256, hipMemcpyDeviceToDevice, S(stream)));
     HIPCHK(hipMemsetAsync(e->ws + 256, 0, e->ws_bytes - 256, S(stream)));
-    e->carve(e->maxB, e->maxT, true);
+    carve(*e, e->maxB, e->maxT);
     HIPCHK(hipStreamSynchronize(S(stream)));
     return 0;
 }
@@ -2542,9 +2517,9 @@ int ss_bind(ss_engine* e, float* params, float* grads, float* m, float* v, void*
     e->part_cap = part_floats(e);
     e->part_off = 0;
     e->curB = e->curT = 0;
-    e->have_fwd = false;
+    e->fwd = {};
     HIPCHK(hipMemsetAsync(e->ws, 0, e->ws_bytes, S(stream)));
-    e->carve(e->maxB, e->maxT, true);
+    carve(*e, e->maxB, e->maxT);
     if (!e->sticky) {       // host-coherent pinned word: kernels OR into it (system scope), the host reads it without a sync
         void* p = nullptr;
         HIPCHK(hipHostMalloc(&p, 64, hipHostMallocDefault));
@@ -2572,7 +2547,6 @@ int ss_bind(ss_engine* e, float* params, float* grads, float* m, float* v, void*
         for (auto& ev : e->ev_join) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
     e->clip_max = 0.0f;       // the workspace (clip state included) starts zero: clipping is off until ss_set_grad_clip
-    e->clip_early_from = -1;
     AdamState st{};
     st.lr = 1e-4;
     st.beta1 = 0.9;
@@ -2603,68 +2577,45 @@ static int grad_norm_partials(ss_engine* e, bool have_hi, hipStream_t s, int* n)
     if (!e->segs_ok) return fail("gradient norm: the parameter table has more runs than GRAD_SEG_MAX");
     const long k = clip_split(e);
     const int nlo = clip_wgs_lo(e);
-    { const int pa_ = prof_begin(e, SS_PROF_ADAM, s, 0.0);
-    if (k > 0) HIPCHK(grad_sumsq(e->G, e->segs, 0, k, e->clip_part, s));
-    if (!have_hi) HIPCHK(grad_sumsq(e->G, e->segs, k, e->status_off, e->clip_part + nlo, s));
-    prof_end(e, pa_, s); }
+    {
+        Prof pr(e, SS_PROF_ADAM, s);
+        if (k > 0) HIPCHK(grad_sumsq(e->G, e->segs, 0, k, e->clip_part, s));
+        if (!have_hi) HIPCHK(grad_sumsq(e->G, e->segs, k, e->status_off, e->clip_part + nlo, s));
+    }
     *n = nlo + grad_sumsq_wgs(e->status_off - k);
     return 0;
 }
 
 // enqueue only: the host-side status check belongs to the ABI entry points, never to the middle of a step being enqueued
 // (the device-side guard in adam_prepare_kernel is what protects the parameters)
-static int adam_enqueue(ss_engine* e, float grad_scale, hipStream_t s) {
+// bw: the backward this update follows, for what it has already sent to the side stream (a fresh one: nothing, the whole arena here)
+static int adam_enqueue(ss_engine* e, const Backward& bw, float grad_scale, hipStream_t s) {
     if (!e->ws || !e->Mm || !e->Vv) return fail("ss_adam_step: Adam arenas are not bound");
     if (e->clip_max > 0.0f) {              // global norm over the whole (all-reduced) arena, then ONE update launch with the coefficient
-        const bool have_hi = e->clip_early_from >= 0 && e->clip_early_from == clip_split(e);
-        e->clip_early_from = -1;
-        e->adam_early_from = -1;
+        const bool have_hi = bw.clip_early_from >= 0 && bw.clip_early_from == clip_split(e);
         int n = 0;
         CHK(grad_norm_partials(e, have_hi, s, &n));
-        { const int pa_ = prof_begin(e, SS_PROF_ADAM, s, 0.0);
-        HIPCHK(adam_prepare_clip(e->adam, e->clip, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s));
-        HIPCHK(adam_range_clip(e->P, e->G, e->Mm, e->Vv, e->arena, e->adam, grad_scale, &e->clip->coef, s));
-        prof_end(e, pa_, s); }
+        {
+            Prof pr(e, SS_PROF_ADAM, s);
+            HIPCHK(adam_prepare_clip(e->adam, e->clip, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s));
+            HIPCHK(adam_range_clip(e->P, e->G, e->Mm, e->Vv, e->arena, e->adam, grad_scale, &e->clip->coef, s));
+        }
         return 0;
     }
-    if (e->adam_early_from >= 0) {         // the decoder + head range went out beside the encoder backward (backward_encoder): the rest, same step state
-        const long n = e->adam_early_from;
-        e->adam_early_from = -1;
-        { const int pa_ = prof_begin(e, SS_PROF_ADAM, s, 0.0);
-        HIPCHK(adam_range(e->P, e->G, e->Mm, e->Vv, n, e->adam, grad_scale, s));
-        prof_end(e, pa_, s); }
+    if (bw.adam_early_from >= 0) {         // the decoder + head range went out beside the encoder backward (backward_encoder): the rest, same step state
+        Prof pr(e, SS_PROF_ADAM, s);
+        HIPCHK(adam_range(e->P, e->G, e->Mm, e->Vv, bw.adam_early_from, e->adam, grad_scale, s));
         return 0;
     }
-    { const int pa_ = prof_begin(e, SS_PROF_ADAM, s, 0.0);
+    Prof pr(e, SS_PROF_ADAM, s);
     HIPCHK(adam_step(e->P, e->G, e->Mm, e->Vv, e->arena, e->adam, grad_scale, e->sticky, e->G + e->status_off, s));
-    prof_end(e, pa_, s); }
     return 0;
 }
-// a fused training step announces that Adam follows its backward inside the same call
-struct AdamEarly {
-    ss_engine* e;
-    AdamEarly(ss_engine* e_, bool on, float gs) : e(e_) {
-        e->adam_early = on;
-        e->adam_early_gs = gs;
-        e->adam_early_from = -1;
-        e->clip_early_from = -1;
-    }
-    // A step that returns with an error behind the early range (decoder + head already updated on the side stream) must not leave the field
-    // set: a later ss_adam_step would then update [0, from) only, with that step's prepared state.  The failed step's partial update stands
-    // (its caller has an error in hand); the next optimiser call starts clean.
-    ~AdamEarly() {
-        e->adam_early = false;
-        e->adam_early_from = -1;
-        e->clip_early_from = -1;
-    }
-};
 
 int ss_adam_step(ss_engine* e, float grad_scale, void* stream) {
     CHK(entry_check(e));
-    e->adam_early_from = -1;               // a stand-alone optimiser step always covers the whole arena
-    e->clip_early_from = -1;
     Own own(e, stream);
-    return adam_enqueue(e, grad_scale, own.s);
+    return adam_enqueue(e, Backward{}, grad_scale, own.s);      // a stand-alone optimiser step always covers the whole arena
 }
 
 int ss_set_grad_clip(ss_engine* e, float max_norm, void* stream) {
@@ -2676,7 +2627,6 @@ int ss_set_grad_clip(ss_engine* e, float max_norm, void* stream) {
     Own own(e, stream);
     HIPCHK(hipMemsetAsync(e->clip, 0, sizeof(ClipState), own.s));      // norm, coefficient and both counters start again
     e->clip_max = max_norm;
-    e->clip_early_from = -1;
     return 0;
 }
 
@@ -2686,9 +2636,10 @@ int ss_grad_norm(ss_engine* e, float grad_scale, float* norm_dev, void* stream) 
     Own own(e, stream);
     int n = 0;
     CHK(grad_norm_partials(e, false, own.s, &n));
-    { const int pa_ = prof_begin(e, SS_PROF_ADAM, own.s, 0.0);
-    HIPCHK(grad_norm_finish(e->clip_part, n, grad_scale, norm_dev, own.s));
-    prof_end(e, pa_, own.s); }
+    {
+        Prof pr(e, SS_PROF_ADAM, own.s);
+        HIPCHK(grad_norm_finish(e->clip_part, n, grad_scale, norm_dev, own.s));
+    }
     return 0;
 }
 
@@ -2709,7 +2660,7 @@ int ss_zero_grads(ss_engine* e, void* stream) {
 
 // every backward: a forward to differentiate, and one that ran within max_frames (nothing is enqueued otherwise)
 static int backward_check(const ss_engine* e) {
-    if (!e->have_fwd) return fail("backward without a preceding forward");
+    if (!e->fwd.have) return fail("backward without a preceding forward");
     if (e->curT > e->maxT)
         return fail("backward: the last forward ran T above max_frames, which is eval-only (GroupNorm backward, training and input "
                     "gradients keep T <= max_frames <= 256)");
@@ -2739,7 +2690,8 @@ int ss_g3_backward(ss_engine* e, const float* d_out, void* stream) {
     Own own(e, stream);
     hipStream_t s = own.s;
     CHK(import_dout(e, d_out, e->curB, e->curT, s));
-    return backward_core(e, s);
+    Backward bw;
+    return backward_core(e, bw, s);
 }
 
 int ss_g3_backward_inputs(ss_engine* e, const float* d_out, float* dx_f0, float* dx_org, float* dc_trg, void* stream) {
@@ -2749,15 +2701,12 @@ int ss_g3_backward_inputs(ss_engine* e, const float* d_out, float* dx_f0, float*
     hipStream_t s = own.s;
     const ss_hparams& h = e->hp;
     const int CI = h.dim_freq + h.dim_f0;
-    InputGradTargets tg{e};
-    e->c1[0].dx_out = dx_f0;                                 // x_f0 = [mel 80 | f0 one-hot 257]: the content stack's input ...
-    e->c1[0].dx_ld = CI;
-    e->c2[0].dx_out = dx_f0 ? dx_f0 + h.dim_freq : nullptr;  // ... and the pitch stack's, side by side in one row
-    e->c2[0].dx_ld = CI;
-    e->ct.dx_out = dx_org;
-    e->ct.dx_ld = h.dim_freq;
+    Backward bw;
+    bw.in_grad[0] = {&e->c1[0], dx_f0, CI};                                       // x_f0 = [mel 80 | f0 one-hot 257]: the content stack's input ...
+    bw.in_grad[1] = {&e->c2[0], dx_f0 ? dx_f0 + h.dim_freq : nullptr, CI};        // ... and the pitch stack's, side by side in one row
+    bw.in_grad[2] = {&e->ct, dx_org, h.dim_freq};
     CHK(import_dout(e, d_out, e->curB, e->curT, s));
-    CHK(backward_core(e, s));
+    CHK(backward_core(e, bw, s));
     if (dc_trg) CHK(speaker_input_grad(e, dc_trg, s));
     return 0;
 }
@@ -2788,7 +2737,7 @@ int ss_g3_rhythm(ss_engine* e, const float* x_org, int B, int T, float* codes, v
     CodeSrc src{e->lt.out[0], nullptr, h.dim_neck_2, h.freq_2, 0, (int)OW};
     HIPCHK(build_dec_in(&src, 1, nullptr, 0, W, e->d_ot, (int)OW, B, T, s));
     HIPCHK(copy_rows(e->d_ot + HALO * OW, (long)h.freq_2 * OW, TP * OW, codes, W, (long)(T / h.freq_2) * W, B, T / h.freq_2, W, s));
-    e->have_fwd = false;
+    e->fwd.have = false;
     return 0;
 }
 
@@ -2818,7 +2767,8 @@ int ss_g6_backward(ss_engine* e, const float* d_out, void* stream) {
     Own own(e, stream);
     hipStream_t s = own.s;
     CHK(import_dout(e, d_out, e->curB, e->curT, s));
-    return backward_core(e, s);
+    Backward bw;
+    return backward_core(e, bw, s);
 }
 
 int ss_g6_backward_inputs(ss_engine* e, const float* d_out, float* dx_org, float* df0_trg, void* stream) {
@@ -2826,13 +2776,11 @@ int ss_g6_backward_inputs(ss_engine* e, const float* d_out, float* dx_org, float
     CHK(backward_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;
-    InputGradTargets tg{e};
-    e->c2[0].dx_out = df0_trg;                               // Encoder_6's stack (model.py:123-140)
-    e->c2[0].dx_ld = e->hp.dim_f0;
-    e->ct.dx_out = dx_org;                                   // Encoder_t
-    e->ct.dx_ld = e->hp.dim_freq;
+    Backward bw;
+    bw.in_grad[0] = {&e->c2[0], df0_trg, e->hp.dim_f0};      // Encoder_6's stack (model.py:123-140)
+    bw.in_grad[1] = {&e->ct, dx_org, e->hp.dim_freq};        // Encoder_t
     CHK(import_dout(e, d_out, e->curB, e->curT, s));
-    return backward_core(e, s);
+    return backward_core(e, bw, s);
 }
 
 static int g3_step_body(ss_engine* e, const float* mel, const float* f0, const float* emb, const int* len_org,
@@ -2846,18 +2794,13 @@ static int g3_step_body(ss_engine* e, const float* mel, const float* f0, const f
     HIPCHK(interp_quant(e->plan[0], mel, f0, h.dim_freq, e->in_mel + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq,
                         e->in_f0 + HALO * e->f0p, e->f0p, TP * e->f0p, h.dim_f0, e->qidx, B, s));
     // x_org and the speaker embedding are first read by Encoder_t / the decoder input: their copies ride on the branch stream
-    e->late_org = mel;
-    e->late_emb = emb;
-    e->prezero = true;
-    const int frc = forward_core(e, true, scales, len_seg, 1, s);                           // solver.py:165
-    e->prezero = false;
-    e->late_org = e->late_emb = nullptr;
-    CHK(frc);
+    CHK(forward_core(e, true, scales, len_seg, 1, s, FusedForward{mel, emb, true}));        // solver.py:165
     const int C = e->head_out;
     HIPCHK(mse_loss(e->out_slab + HALO * C, C, TP * C, e->org + HALO * C, C, TP * C, e->d_out_slab + HALO * C, C, TP * C, B, T,
                     C, 1.0f, e->loss_part, loss, s));                                       // solver.py:166
+    Backward bw;
     if (flags & SS_STEP_SPLIT_BACKWARD) {         // data parallel: stop once the decoder + head gradients are complete
-        CHK(backward_decoder(e, s));
+        CHK(backward_decoder(e, bw, s));          // (not late: nothing of it is left pending for ss_train_finish's backward_encoder)
         if (!(flags & SS_STEP_SPLIT_NO_JOIN)) return join_side(e, s);
         // the weight-gradient GEMMs stay on the side stream (joined by backward_encoder, as in the one-call step);
         // ss_wait_decoder_grads() orders the consumer of the decoder range behind both parts
@@ -2869,11 +2812,10 @@ static int g3_step_body(ss_engine* e, const float* mel, const float* f0, const f
         }
         return 0;
     }
-    {
-        AdamEarly ae(e, !(flags & SS_STEP_NO_ADAM), grad_scale);      // (its scope covers the optimiser call: the early range's bookkeeping ends with it)
-        CHK(backward_core(e, s));                                                           // solver.py:170-171
-        if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_enqueue(e, grad_scale, s));                // solver.py:172
-    }
+    bw.adam_early = !(flags & SS_STEP_NO_ADAM);   // Adam follows inside this call: its decoder + head range may go out early
+    bw.adam_gs = grad_scale;
+    CHK(backward_core(e, bw, s));                                                           // solver.py:170-171
+    if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_enqueue(e, bw, grad_scale, s));                // solver.py:172
     return 0;
 }
 
@@ -2912,10 +2854,11 @@ int ss_g3_train_step(ss_engine* e, const float* mel, const float* f0, const floa
 int ss_train_finish(ss_engine* e, float grad_scale, int flags, void* stream) {
     Own own(e, stream);
     hipStream_t s = own.s;
-    if (!e->have_fwd) return fail("ss_train_finish without a preceding ss_*_train_step(SS_STEP_SPLIT_BACKWARD)");
+    if (!e->fwd.have) return fail("ss_train_finish without a preceding ss_*_train_step(SS_STEP_SPLIT_BACKWARD)");
     CHK(backward_check(e));
-    CHK(backward_encoder(e, s));
-    if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_enqueue(e, grad_scale, s));
+    Backward bw;               // a backward of its own: the decoder half (an earlier call) left nothing pending, and nothing goes out early
+    CHK(backward_encoder(e, bw, s));
+    if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_enqueue(e, bw, grad_scale, s));
     return 0;
 }
 
@@ -2948,11 +2891,11 @@ int ss_g6_train_step(ss_engine* e, const float* mel, const float* f0_onehot, con
     const int C = e->head_out;
     HIPCHK(ce_loss(e->out_slab + HALO * C, C, TP * C, target_idx, e->d_out_slab + HALO * C, C, TP * C, B, T, C, 1.0f,
                    e->loss_part, loss, s));
-    {
-        AdamEarly ae(e, !(flags & SS_STEP_NO_ADAM), grad_scale);
-        CHK(backward_core(e, s));
-        if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_enqueue(e, grad_scale, s));
-    }
+    Backward bw;
+    bw.adam_early = !(flags & SS_STEP_NO_ADAM);
+    bw.adam_gs = grad_scale;
+    CHK(backward_core(e, bw, s));
+    if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_enqueue(e, bw, grad_scale, s));
     return 0;
 }
 
@@ -3410,7 +3353,8 @@ int ss_op_conv_block(const float* x, const float* w, const float* bias, const fl
     if (dy) {
         if (!gw || !gb || !ggamma || !gbeta) return fail("ss_op_conv_block: backward needs the gradient outputs");
         HIPCHK(copy_rows(dy, Co, (long)T * Co, dys + HALO * Co, Co, TP * Co, B, T, Co, s));
-        CHK(conv_block_bwd(&e, cb, Slab{dys, Co}, Slab{xs, cb.Cp}, dx ? Slab{dxs, cb.Cp} : Slab{nullptr, 0}, s));
+        Backward bw;
+        CHK(conv_block_bwd(&e, bw, cb, Slab{dys, Co}, Slab{xs, cb.Cp}, dx ? Slab{dxs, cb.Cp} : Slab{nullptr, 0}, s));
         HIPCHK(hipMemcpyAsync(gw, e.G + cb.w, (long)Co * Ci * 5 * 4, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipMemcpyAsync(gb, e.G + cb.b, Co * 4L, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipMemcpyAsync(ggamma, e.G + cb.ga, Co * 4L, hipMemcpyDeviceToDevice, s));
@@ -3685,7 +3629,7 @@ static int dp_step(ss_engine* e, hipStream_t s, const std::function<int(hipStrea
             CHK(allreduce_range(e, k, e->arena - k, s));
             CHK(allreduce_range(e, 0, k, s));
         }
-        return adam_enqueue(e, gs, s);
+        return adam_enqueue(e, Backward{}, gs, s);
     }
     e->dp_done.clear();
     e->dp_rec.clear();              // ss_dp_profile keeps the LAST step's record
@@ -3695,7 +3639,7 @@ static int dp_step(ss_engine* e, hipStream_t s, const std::function<int(hipStrea
     e->dp_on = false;
     CHK(rc);
     CHK(dp_finish(e, s));
-    return adam_enqueue(e, gs, s);                          // the mean is folded into the Adam kernel
+    return adam_enqueue(e, Backward{}, gs, s);              // the whole arena; the mean is folded into the Adam kernel
 }
 
 int ss_g3_dp_train_step(ss_engine* e, const float* mel, const float* f0, const float* emb, const int* len_org, const float* scales,

@@ -398,3 +398,39 @@ def test_history_independence_is_bit_exact_in_deterministic_mode(E, kind):
         assert torch.equal(a.params, b.params), kind
     finally:
         E.tune('deterministic', 0)
+
+
+def test_input_gradient_targets_die_with_their_call(E):
+    """A train-mode forward + ss_g3_backward_inputs into three caller buffers, then, on the same engine, another forward + plain
+    ss_g3_backward of a DIFFERENT batch and output gradient (a target that outlived its call would be written again, with other values):
+    the second pass's gradient arena is bit-identical to the same forward + backward on a fresh engine, and the three buffers keep the bits
+    the first call gave them.  Deterministic mode, fp32, 2 x 128."""
+    B, T = 2, 128
+    hp = W.default_hparams(max_len_pad=T)
+    emb = torch.nn.functional.one_hot(torch.arange(B), hp.dim_spk_emb).float()
+
+    def pass_inputs(seed):
+        mel, onehot, _, d3 = g6_batch(seed, B, T)
+        d_out = torch.randn(B, T, hp.dim_freq, generator=torch.Generator().manual_seed(seed)) * 0.1
+        return torch.cat((mel, onehot), -1), mel, d3, d_out
+
+    x1, org1, draws1, dout1 = pass_inputs(301)
+    x2, org2, draws2, dout2 = pass_inputs(302)
+    E.tune('deterministic', 1)
+    try:
+        fresh, used = plain(E, 'G3', hp, B, T), plain(E, 'G3', hp, B, T)
+        used.g3_forward(x1, org1, emb, draws1, training=True)
+        dx = used.g3_backward(dout1, inputs=E.Engine.G3_INPUTS)
+        used.check()
+        kept = [t.clone() for t in dx]
+        assert all(bool(torch.isfinite(t).all()) and bool(t.any()) for t in kept)
+        for e in (used, fresh):
+            e.g3_forward(x2, org2, emb.flip(0), draws2, training=True)
+            assert e.g3_backward(dout2) is None
+            e.check()
+        assert torch.equal(used.grads.view(torch.int32), fresh.grads.view(torch.int32))
+        assert bool(fresh.grads.any())
+        for n, t, k in zip(E.Engine.G3_INPUTS, dx, kept):
+            assert torch.equal(t.view(torch.int32), k.view(torch.int32)), n
+    finally:
+        E.tune('deterministic', 0)
