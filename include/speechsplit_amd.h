@@ -14,7 +14,9 @@
  *     SS_MAX_EVAL_FRAMES whose plan (ss_plan_bytes) fits the bound workspace -- long utterances, as the reference runs them
  *     (InterpLnr is the identity in eval mode, model.py:382-383).  Everything that trains or differentiates (train-mode
  *     forwards, ss_*_backward*, ss_*_train_step, the data-parallel steps, SS_STEP_BUCKET, ss_interp_*) keeps T <= max_frames
- *     (<= 256) and refuses more up front, nothing enqueued, the engine usable afterwards;
+ *     (<= 256) and refuses more up front, nothing enqueued, the engine usable afterwards.  That range, 8 <= T <= 256 in steps
+ *     of 8, is tested end to end on the GPU: train steps, gradients and ss_interp_* at 8, 200 and 256 frames as well as at the
+ *     64..192 frames of the benchmark configurations (tests/test_gpu_frame_range.py);
  *   - the random-resampling draws of InterpLnr (model.py:392-393 rand(B*7)+0.5; :399-402 randint) are INPUTS:
  *     `scales` f32 and `len_seg` i32, one [B*7] row per InterpLnr call in call order.  Given equal draws the
  *     index path is bit-exact against the reference.

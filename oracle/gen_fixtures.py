@@ -122,6 +122,96 @@ def demo_conversion(ref_model, ref_utils):
     print('demo_conversion.npz written:', {k: v.shape for k, v in d.items()})
 
 
+TRAIN_STEPS = (('b2_t128', 2, 128, 3, 31, 41, 3), ('b2_t192', 2, 192, 3, 32, 42, 1), ('b8_t128', 8, 128, 3, 33, 43, 1),
+               ('b2_t256', 2, 256, 3, 34, 44, 1), ('b2_t8', 2, 8, 3, 35, 45, 1))
+
+
+def train_len_lo(T):
+    """Shortest utterance of a train-step fixture's batch: 64 at 128 frames, else 96, and never more than T."""
+    return min(T, 64 if T == 128 else 96)
+
+
+JSON_TAGS = ('b2_t128', 'b2_t192', 'b8_t128')         # records kept in train_steps.json; every later tag has a binary file of its own
+
+
+def save_train_rec(tag, rec):
+    """One train-step record as tests/golden/train_<tag>_stats.npz: the scalars, and per statistics table the tensors' sum / l2 / amax
+    and their sampled positions and values, concatenated in the order of `names`."""
+    d = {k: np.int64(rec[k]) for k in ('B', 'T', 'wseed', 'bseed', 'dseed')}
+    d['losses'] = np.array(rec['losses'], np.float64)
+    d['names'] = np.array(list(rec['grads']))
+    for key in ('grads', 'params_after'):
+        st = [rec[key][n] for n in rec['grads']]
+        for f in ('sum', 'l2', 'amax'):
+            d[f'{key}_{f}'] = np.array([s[f] for s in st], np.float64)
+        d[f'{key}_npos'] = np.array([len(s['pos']) for s in st], np.int64)
+        d[f'{key}_pos'] = np.array([p for s in st for p in s['pos']], np.int64)
+        d[f'{key}_val'] = np.array([v for s in st for v in s['val']], np.float64)
+    np.savez_compressed(os.path.join(GOLD, f'train_{tag}_stats.npz'), **d)
+
+
+def load_train_rec(tag, gold=GOLD):
+    """The train-step record of `tag` as the dict train_steps.json holds, from that file or from train_<tag>_stats.npz."""
+    if tag in JSON_TAGS:
+        return json.load(open(os.path.join(gold, 'train_steps.json')))[tag]
+    z = np.load(os.path.join(gold, f'train_{tag}_stats.npz'))
+    rec = {k: int(z[k]) for k in ('B', 'T', 'wseed', 'bseed', 'dseed')}
+    rec['losses'] = z['losses'].tolist()
+    for key in ('grads', 'params_after'):
+        ends = np.cumsum(z[f'{key}_npos'])
+        rec[key] = {str(n): dict(sum=float(z[f'{key}_sum'][i]), l2=float(z[f'{key}_l2'][i]), amax=float(z[f'{key}_amax'][i]),
+                                 pos=z[f'{key}_pos'][ends[i] - z[f'{key}_npos'][i]:ends[i]].tolist(),
+                                 val=z[f'{key}_val'][ends[i] - z[f'{key}_npos'][i]:ends[i]].tolist())
+                    for i, n in enumerate(z['names'])}
+    return rec
+
+
+def train_steps(ref_model, ref_utils, only=None):
+    """F4/F5: full Generator_3 train steps of the reference (statistics + first output).  only: tags to (re)generate; the other
+    records are kept as they are."""
+    path = os.path.join(GOLD, 'train_steps.json')
+    steps = json.load(open(path)) if only else {}
+    for tag, B, T, wseed, bseed, dseed, nsteps in TRAIN_STEPS:
+        if only and tag not in only:
+            continue
+        hp = W.default_hparams(max_len_pad=T)
+        w = W.make_weights('G3', hp, wseed)
+        M = ref_model.Generator_3(hp)
+        M.load_state_dict({**{k: torch.from_numpy(v) for k, v in w.items()},
+                           'encoder_1.len_org': torch.tensor(T)})
+        I = ref_model.InterpLnr(hp)
+        opt = torch.optim.Adam(M.parameters(), 1e-4, [0.9, 0.999])                # solver.py:62
+        mel, f0, emb, lens = synth_batch(bseed, B, T, train_len_lo(T))
+        rec = dict(B=B, T=T, wseed=wseed, bseed=bseed, dseed=dseed, losses=[])
+        torch.manual_seed(dseed)
+        for it in range(nsteps):
+            M.train()
+            x_f0 = torch.cat((mel, f0), -1)                                       # solver.py:160
+            xi = I(x_f0, lens)                                                    # :161
+            q = ref_utils.quantize_f0_torch(xi[:, :, -1])[0]                      # :162
+            x_in = torch.cat((xi[:, :, :-1], q), -1)                              # :163
+            out = M(x_in, mel, emb)                                               # :165
+            loss = torch.nn.functional.mse_loss(mel, out, reduction='mean')       # :166
+            opt.zero_grad()
+            loss.backward()
+            if it == 0:
+                rec['grads'] = {n: tensor_stats(p.grad) for n, p in M.named_parameters()}
+                np.save(os.path.join(GOLD, f'train_{tag}_out.npy'), out.detach().numpy())
+                np.save(os.path.join(GOLD, f'train_{tag}_xin_f0idx.npy'),
+                        x_in[:, :, 80:].argmax(-1).numpy().astype(np.int16))
+                np.save(os.path.join(GOLD, f'train_{tag}_xin_mel.npy'), x_in[:, :, :80].detach().numpy())
+            opt.step()
+            if it == 0:
+                rec['params_after'] = {n: tensor_stats(p) for n, p in M.named_parameters()}
+            rec['losses'].append(float(loss.detach()))
+        if tag in JSON_TAGS:
+            steps[tag] = rec
+        else:
+            save_train_rec(tag, rec)
+    if not only or set(only) & set(JSON_TAGS):
+        json.dump(steps, open(path, 'w'))
+
+
 def main():
     mods = import_reference()
     if mods is None:
@@ -132,6 +222,9 @@ def main():
     torch.set_num_threads(8)
     if len(sys.argv) > 1 and sys.argv[1] == 'demo_conversion':      # only this fixture
         demo_conversion(ref_model, ref_utils)
+        return 0
+    if len(sys.argv) > 2 and sys.argv[1] == 'train_steps':          # only the named train-step tags, e.g. train_steps b2_t256 b2_t8
+        train_steps(ref_model, ref_utils, only=sys.argv[2:])
         return 0
 
     # ---------------------------------------------------------------- F0: state_dict keys
@@ -242,41 +335,7 @@ def main():
     demo_conversion(ref_model, ref_utils)
 
     # ---------------------------------------------------------------- F4/F5: full train steps (stats + output)
-    steps = {}
-    for tag, B, T, wseed, bseed, dseed, nsteps in (('b2_t128', 2, 128, 3, 31, 41, 3), ('b2_t192', 2, 192, 3, 32, 42, 1),
-                                                   ('b8_t128', 8, 128, 3, 33, 43, 1)):
-        hp = W.default_hparams(max_len_pad=T)
-        w = W.make_weights('G3', hp, wseed)
-        M = ref_model.Generator_3(hp)
-        M.load_state_dict({**{k: torch.from_numpy(v) for k, v in w.items()},
-                           'encoder_1.len_org': torch.tensor(T)})
-        I = ref_model.InterpLnr(hp)
-        opt = torch.optim.Adam(M.parameters(), 1e-4, [0.9, 0.999])                # solver.py:62
-        mel, f0, emb, lens = synth_batch(bseed, B, T, 64 if T == 128 else 96)
-        rec = dict(B=B, T=T, wseed=wseed, bseed=bseed, dseed=dseed, losses=[])
-        torch.manual_seed(dseed)
-        for it in range(nsteps):
-            M.train()
-            x_f0 = torch.cat((mel, f0), -1)                                       # solver.py:160
-            xi = I(x_f0, lens)                                                    # :161
-            q = ref_utils.quantize_f0_torch(xi[:, :, -1])[0]                      # :162
-            x_in = torch.cat((xi[:, :, :-1], q), -1)                              # :163
-            out = M(x_in, mel, emb)                                               # :165
-            loss = torch.nn.functional.mse_loss(mel, out, reduction='mean')       # :166
-            opt.zero_grad()
-            loss.backward()
-            if it == 0:
-                rec['grads'] = {n: tensor_stats(p.grad) for n, p in M.named_parameters()}
-                np.save(os.path.join(GOLD, f'train_{tag}_out.npy'), out.detach().numpy())
-                np.save(os.path.join(GOLD, f'train_{tag}_xin_f0idx.npy'),
-                        x_in[:, :, 80:].argmax(-1).numpy().astype(np.int16))
-                np.save(os.path.join(GOLD, f'train_{tag}_xin_mel.npy'), x_in[:, :, :80].detach().numpy())
-            opt.step()
-            if it == 0:
-                rec['params_after'] = {n: tensor_stats(p) for n, p in M.named_parameters()}
-            rec['losses'].append(float(loss.detach()))
-        steps[tag] = rec
-    json.dump(steps, open(os.path.join(GOLD, 'train_steps.json'), 'w'))
+    train_steps(ref_model, ref_utils)
 
     # ---------------------------------------------------------------- Generator_6 train-mode forward (+ CE grads)
     hp = W.default_hparams(max_len_pad=192)

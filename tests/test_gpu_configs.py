@@ -52,9 +52,12 @@ def stack_draws(draws):
 
 class Case:
     """One engine + one oracle TrainState stepping side by side on the same batch and draws."""
+    draws_fn = staticmethod(draws_for)       # (seed, B, ncalls) -> the resampling draws; the reference's own unless a case is given another source
 
-    def __init__(self, E, kind, B, T, len_lo, wseed, bseed, precision='f32'):
+    def __init__(self, E, kind, B, T, len_lo, wseed, bseed, precision='f32', draws_fn=None):
         self.kind, self.B, self.T = kind, B, T
+        if draws_fn is not None:
+            self.draws_fn = draws_fn
         self.hp = W.default_hparams(max_len_pad=T)
         w = W.make_weights(kind, self.hp, wseed)
         self.eng = E.Engine(kind, self.hp, B, T)
@@ -69,11 +72,14 @@ class Case:
             self.onehot = torch.nn.functional.one_hot(self.qidx, 257).float()
         self.dseed = bseed + 100
 
+    def draws(self, it):
+        return self.draws_fn(self.dseed + it, self.B, self.ncalls)
+
     def step(self, it, kink_bound=2e-5, override=True):
         """Engine: forward, loss, backward (gradients kept), then Adam.  Oracle: the same step taking the engine's ReLU branches.
         Returns dict(loss=(gpu, cpu), out=(gpu, cpu), grads={name: (gpu, cpu)}, before/after params of the engine)."""
         eng, B, T = self.eng, self.B, self.T
-        draws = draws_for(self.dseed + it, B, self.ncalls)
+        draws = self.draws(it)
         if self.kind == 'G3':
             loss = eng.g3_train_step(self.mel, self.f0, self.emb, self.lens, stack_draws(draws), no_adam=True)
         else:
@@ -367,8 +373,10 @@ def test_g6_small_fixture_elementwise_and_trajectory(E):
 BF16_BOUNDS = dict(loss=1e-3, out=4e-2, grad=2e-1, grad_median=2e-2)
 
 
-@pytest.mark.parametrize('case', [('G3', 32, 128, 64), ('G6', 32, 192, 96), ('G3', 64, 192, 96), ('G3', 21, 136, 64), ('G6', 5, 104, 64)],
-                         ids=['config3_g3_32x128', 'config4_g6_32x192', 'config5_g3_64x192', 'ragged_g3_21x136', 'ragged_g6_5x104'])
+@pytest.mark.parametrize('case', [('G3', 32, 128, 64), ('G6', 32, 192, 96), ('G3', 64, 192, 96), ('G3', 21, 136, 64), ('G6', 5, 104, 64),
+                                  ('G3', 2, 256, 96), ('G6', 2, 200, 96)],
+                         ids=['config3_g3_32x128', 'config4_g6_32x192', 'config5_g3_64x192', 'ragged_g3_21x136', 'ragged_g6_5x104',
+                              'g3_2x256', 'g6_2x200'])
 def test_bf16_mode_against_fp32_oracle(E, case):
     kind, B, T, len_lo = case
     c = Case(E, kind, B, T, len_lo, wseed=0 if kind == 'G3' else 4, bseed=700 + B + T, precision='bf16')

@@ -142,7 +142,7 @@ def compare_step(tag, b, ref, la, lb, steps, bf16=False, exact=False):
 
 
 # --------------------------------------------------------------------------------------------- guarded binding
-@pytest.mark.parametrize('B,T', [(16, 128), (64, 128)])
+@pytest.mark.parametrize('B,T', [(16, 128), (64, 128), (16, 256)])
 def test_guarded_g3_train_step_buckets_and_back(E, B, T):
     """Generator_3 train step at (max_batch, max_frames), then the same engine at a smaller bucket (SS_STEP_BUCKET, 5 x 96) and back.
     Each compared step starts both engines from the same weights and a fresh Adam state: in the default (atomic split-K) mode two identical

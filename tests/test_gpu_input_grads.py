@@ -41,16 +41,28 @@ def g3_inputs(seed, B, T):
     return torch.cat((mel, onehot), -1), mel, c_trg
 
 
+def train_draws(seed, B, T):
+    """The three encoder draws of a training forward.  Above 192 frames the stretching ones of tests/test_gpu_frame_range.py, under which
+    every row of the resampled slabs is live (asserted here, on the CPU); the reference's own below."""
+    if T <= 192:
+        return draws_for(seed, B, 3)
+    from tests.test_gpu_frame_range import all_rows_live, stretch_draws
+    draws = stretch_draws(seed, B, 3)
+    for d in draws:
+        all_rows_live(d, np.full(B, T), T)
+    return draws
+
+
 def g3_case(w, hp, B, T, training, seed):
     x_f0, x_org, c_trg = g3_inputs(seed, B, T)
-    return x_f0, x_org, c_trg, draws_for(seed + 500, B, 3) if training else None
+    return x_f0, x_org, c_trg, train_draws(seed + 500, B, T) if training else None
 
 
 def g6_case(w, hp, B, T, training, seed):
     _, x_org, _ = g3_inputs(seed, B, T)
     g = torch.Generator().manual_seed(seed + 1000)
     f0_trg = torch.nn.functional.one_hot(torch.randint(0, 257, (B, T), generator=g), 257).float()
-    return x_org, f0_trg, draws_for(seed + 500, B, 3) if training else None
+    return x_org, f0_trg, train_draws(seed + 500, B, T) if training else None
 
 
 def masks_of(eng, B, T):
@@ -105,7 +117,7 @@ def cuda_leaf(x):
 
 
 # --------------------------------------------------------------------------------------------- 1, 2: Generator_3 module
-@pytest.mark.parametrize('B,T,training', [(2, 128, False), (3, 192, False), (2, 128, True)])
+@pytest.mark.parametrize('B,T,training', [(2, 128, False), (3, 192, False), (2, 128, True), (2, 256, True), (2, 200, True)])
 def test_g3_module_input_grads(B, T, training):
     hp = W.default_hparams(max_len_pad=T)
     w = W.make_weights('G3', hp, 7)
@@ -147,9 +159,9 @@ def test_g3_module_only_requested_inputs_and_dtype():
 
 
 # --------------------------------------------------------------------------------------------- 3: Generator_6 module
-@pytest.mark.parametrize('training', [False, True])
-def test_g6_module_input_grads(training):
-    B, T = 2, 128
+@pytest.mark.parametrize('training,T', [(False, 128), (True, 128), (True, 256)], ids=['False', 'True', 'True-256'])
+def test_g6_module_input_grads(training, T):
+    B = 2
     hp = W.default_hparams(max_len_pad=T)
     w = W.make_weights('G6', hp, 8)
     x_org, f0_trg, draws = g6_case(w, hp, B, T, training, 21)

@@ -19,7 +19,7 @@ import pytest
 import torch
 
 from oracle import interp_np, ref_model, weights as W
-from oracle.gen_fixtures import draws_for, synth_batch
+from oracle.gen_fixtures import draws_for, load_train_rec, synth_batch, train_len_lo
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -385,9 +385,9 @@ def test_bf16_precision_train_step(E):
     assert 1e-4 < worst < 1e-1, worst        # really a different arithmetic, and within the stated bound
 
 
-@pytest.mark.parametrize('tag', ['b2_t128', 'b2_t192', 'b8_t128'])
+@pytest.mark.parametrize('tag', ['b2_t128', 'b2_t192', 'b8_t128', 'b2_t256', 'b2_t8'])
 def test_fused_train_step_against_reference_fixture(E, tag):
-    rec = json.load(open(os.path.join(GOLD, 'train_steps.json')))[tag]
+    rec = load_train_rec(tag, GOLD)
     B, T = rec['B'], rec['T']
     hp = W.default_hparams(max_len_pad=T)
     eng = get_engine(E, 'G3', T, B)
@@ -395,7 +395,7 @@ def test_fused_train_step_against_reference_fixture(E, tag):
     eng.adam_m.zero_()
     eng.adam_v.zero_()
     eng.set_adam(1e-4, 0.9, 0.999, 1e-8, 0)
-    mel, f0, emb, lens = synth_batch(rec['bseed'], B, T, 64 if T == 128 else 96)
+    mel, f0, emb, lens = synth_batch(rec['bseed'], B, T, train_len_lo(T))
     nsteps = len(rec['losses'])
     draws = draws_for(rec['dseed'], B, 4 * nsteps)
     for it in range(nsteps):

@@ -170,13 +170,14 @@ def _draws(seed, B, n):
     return draws_for(seed, B, n)
 
 
-@pytest.mark.parametrize('tag', ['b2_t128', 'b2_t192'])
+@pytest.mark.parametrize('tag', ['b2_t128', 'b2_t192', 'b2_t256', 'b2_t8'])
 def test_train_step(gold_dir, tag):
-    rec = json.load(open(os.path.join(gold_dir, 'train_steps.json')))[tag]
+    from oracle.gen_fixtures import load_train_rec, train_len_lo
+    rec = load_train_rec(tag, gold_dir)
     B, T = rec['B'], rec['T']
     hp = W.default_hparams(max_len_pad=T)
     st = ref_model.TrainState(W.make_weights('G3', hp, rec['wseed']))
-    mel, f0, emb, lens = _synth(rec['bseed'], B, T, 64 if T == 128 else 96)
+    mel, f0, emb, lens = _synth(rec['bseed'], B, T, train_len_lo(T))
     nsteps = len(rec['losses'])
     draws = _draws(rec['dseed'], B, 4 * nsteps)
     for it in range(nsteps):
