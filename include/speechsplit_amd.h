@@ -115,6 +115,31 @@ int ss_g6_backward(ss_engine* e, const float* d_out_dev, void* stream);
  * ss_g6_backward), as ss_g3_backward_inputs.  Errors (nothing enqueued): a Generator_3 engine, no preceding forward. */
 int ss_g6_backward_inputs(ss_engine* e, const float* d_out_dev, float* dx_org_dev, float* df0_trg_dev, void* stream);
 
+/* ---- ragged batches in eval mode (nothing to mirror: the reference converts one utterance per call, and padding a batch changes every
+ *      row's result -- GroupNorm statistics, the reverse LSTM direction and the k=5 convolutions all look across time) ----
+ * A ragged forward takes len i32[B] (caller-owned device memory, read by the kernels in stream order like every other input; it is not
+ * copied into the workspace) next to the usual [B, T, C] inputs:
+ *   - row b of the output, frames [0, len[b]), equals the eval-mode forward of that utterance alone at T = len[b], to the accuracy of any
+ *     eval-mode forward; output frames t >= len[b] are exact zeros (ss_g3_rhythm_ragged: code rows >= len[b] / freq_2);
+ *   - input frames t >= len[b] are never used: they may hold anything, NaN included;
+ *   - len[b] is a multiple of every code factor (freq, freq_2, freq_3) and lies in [factor, T]; T obeys the rules of the eval-mode
+ *     forwards (up to SS_MAX_EVAL_FRAMES, plan within the bound workspace).  Every kernel uses min(max(len[b], 0), T): a length outside
+ *     the contract gives unspecified values in that row only, and nothing is read or written outside the tensors;
+ *   - eval-mode only: training != 0 together with a length array is refused with nothing enqueued, and ss_*_backward* after a ragged
+ *     forward is refused with the eval-only error a forward above max_frames gives; the engine stays usable;
+ *   - len == NULL is exactly ss_g3_forward / ss_g6_forward (with NULL draws) / ss_g3_rhythm, launch for launch; with every len[b] == T the
+ *     result is bit-identical to theirs (the predicates select nothing and the arithmetic is the same).
+ * Where the lengths act: the staging of the inputs writes zeros behind each row's end; every GroupNorm takes its statistics over the row's
+ * own frames (1 / (16 len[b])) and writes zeros behind them, which with the zero halo rows is the padding the next convolution sees in a
+ * run of the utterance alone; every recurrence zeroes the state of a row at frames behind its end, so the reverse direction reaches the
+ * row's last frame with the zero state; the copy of the head's output to the caller writes zeros there instead of the bias.  A batch
+ * costs what its longest row costs: sort by length (speechsplit_amd.convert.plan_batches). */
+int ss_g3_forward_ragged(ss_engine* e, const float* x_f0_dev, const float* x_org_dev, const float* c_trg_dev, const int* len_dev, int B,
+                         int T, int training, float* out_dev, void* stream);
+int ss_g3_rhythm_ragged(ss_engine* e, const float* x_org_dev, const int* len_dev, int B, int T, float* codes_dev, void* stream);
+int ss_g6_forward_ragged(ss_engine* e, const float* x_org_dev, const float* f0_trg_dev, const int* len_dev, int B, int T, int training,
+                         float* out_dev, void* stream);
+
 /* ---- Solver.train step body (solver.py:157-172), fused: cat(mel,f0) -> InterpLnr -> quantize_f0 -> G -> mse(mean)
  *      -> backward -> Adam.  mel [B,T,80], f0 [B,T,1] (-1e10 = unvoiced), emb [B,82], len_org i32[B];
  *      scales/len_seg [4][B*7] (outer call first).  T must equal hp.max_len_pad (model.py:105,157).
@@ -280,6 +305,11 @@ int ss_op_gemm(const float* a_dev, long lda, const float* b_dev, long ldb, float
  * holds its exchange tiles and flags: 4*ceil(B/16)*(H/16)^2*1024 + 8192 bytes (the hook zeroes them: the tiles carry step tags). */
 int ss_op_lstm_fwd(float* gates_dev, const float* whh_f_dev, const float* whh_b_dev, float* out_dev, float* csave_dev,
                    float* scratch_dev, long scratch_floats, int B, int T, int H, void* stream);
+/* ss_op_lstm_fwd over a ragged batch (len_dev i32[B], see ss_g3_forward_ragged; NULL: ss_op_lstm_fwd itself): row b's recurrence covers
+ * frames [0, len[b]) -- the reverse direction starts at frame len[b] - 1 from the zero state -- and out / csave hold zeros for t >= len[b].
+ * The gates rows t >= len[b] may hold anything on entry (NaN included) and are unspecified on exit.  Forward only. */
+int ss_op_lstm_fwd_ragged(float* gates_dev, const float* whh_f_dev, const float* whh_b_dev, float* out_dev, float* csave_dev,
+                          float* scratch_dev, long scratch_floats, const int* len_dev, int B, int T, int H, void* stream);
 /* BPTT of the same: d_out [B,T+4,2H]; gates is replaced by the pre-activation gradients. */
 int ss_op_lstm_bwd(float* gates_dev, const float* whh_f_dev, const float* whh_b_dev, const float* d_out_dev,
                    const float* csave_dev, float* scratch_dev, long scratch_floats, int B, int T, int H, void* stream);
@@ -314,6 +344,11 @@ long ss_op_conv_block_scratch(int B, int T, int Ci, int Co);
 int ss_op_conv_block(const float* x_dev, const float* w_dev, const float* bias_dev, const float* gamma_dev, const float* beta_dev,
                      const float* dy_dev, float* y_dev, float* dx_dev, float* gw_dev, float* gb_dev, float* ggamma_dev,
                      float* gbeta_dev, float* scratch_dev, long scratch_floats, int B, int T, int Ci, int Co, void* stream);
+/* The forward of ss_op_conv_block over a ragged batch (len_dev i32[B]; NULL: the plain forward): x rows t >= len[b] are never read, the
+ * GroupNorm statistics of row b run over its len[b] frames, y rows t >= len[b] are zeros.  T up to SS_MAX_EVAL_FRAMES; same scratch. */
+int ss_op_conv_block_ragged(const float* x_dev, const float* w_dev, const float* bias_dev, const float* gamma_dev, const float* beta_dev,
+                            const int* len_dev, float* y_dev, float* scratch_dev, long scratch_floats, int B, int T, int Ci, int Co,
+                            void* stream);
 /* The ReLU branch the engine took in conv block `block` ("enc1.c1_0" .. "enc1.c2_2", "enc3.c_0" .. "enc3.c_2", "enc2.c") of
  * the last forward: mask [B,T,Co] dense, 1.0f where the GroupNorm output is > 0.  A GroupNorm output within fp32 rounding
  * of 0 may fall on either side in two correct implementations; parity tests hand this mask to the oracle so that the

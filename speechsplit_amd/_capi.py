@@ -40,6 +40,9 @@ SYMBOLS = {
     'ss_g3_backward': (_i, [_vp, _fp, _vp]),
     'ss_g3_backward_inputs': (_i, [_vp, _fp, _fp, _fp, _fp, _vp]),
     'ss_g3_rhythm': (_i, [_vp, _fp, _i, _i, _fp, _vp]),
+    'ss_g3_forward_ragged': (_i, [_vp, _fp, _fp, _fp, _ip, _i, _i, _i, _fp, _vp]),
+    'ss_g3_rhythm_ragged': (_i, [_vp, _fp, _ip, _i, _i, _fp, _vp]),
+    'ss_g6_forward_ragged': (_i, [_vp, _fp, _fp, _ip, _i, _i, _i, _fp, _vp]),
     'ss_g6_forward': (_i, [_vp, _fp, _fp, _fp, _ip, _i, _i, _i, _fp, _vp]),
     'ss_g6_backward': (_i, [_vp, _fp, _vp]),
     'ss_g6_backward_inputs': (_i, [_vp, _fp, _fp, _fp, _vp]),
@@ -70,12 +73,14 @@ SYMBOLS = {
     'ss_set_lockstep': (_i, [_vp, _i]),
     'ss_op_gemm': (_i, [_fp, _l, _fp, _l, _fp, _l, _fp, _i, _i, _i, _i, _i, _vp]),
     'ss_op_lstm_fwd': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _vp]),
+    'ss_op_lstm_fwd_ragged': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _l, _ip, _i, _i, _i, _vp]),
     'ss_op_lstm_bwd': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _vp]),
     'ss_op_lstm_wgrad': (_i, [_fp, _fp, _l, _fp, _fp, _fp, _fp, _fp, _l, _l, _i, _i, _vp]),
     'ss_op_split_image': (_i, [_fp, _l, _l, _i, _f, _fp, _l, _vp]),
     'ss_op_gemm_img': (_i, [_fp, _l, _fp, _l, _fp, _l, _fp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _l, _fp, _vp, _vp]),
     'ss_op_conv_block_scratch': (_l, [_i, _i, _i, _i]),
     'ss_op_conv_block': (_i, [_fp] * 13 + [_l, _i, _i, _i, _i, _vp]),
+    'ss_op_conv_block_ragged': (_i, [_fp] * 5 + [_ip, _fp, _fp, _l, _i, _i, _i, _i, _vp]),
     'ss_debug_relu_mask': (_i, [_vp, C.c_char_p, _fp, _vp]),
     'ss_melspec_frames': (_i, [_i]),
     'ss_melspec': (_i, [_vp, _i, _vp, _i, _fp, _vp]),

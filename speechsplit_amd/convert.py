@@ -7,6 +7,10 @@ padding / quantisation (``pad_seq_to_2`` to 192 frames, zero-padded F0 -> ``quan
 is the schedule: the notebook runs seven batch-1 forwards, here the seven conditions are ONE batch-7 forward of the HIP
 engine (every operator on the path is per-utterance, so the rows are the notebook's results).
 The vocoder cell (WaveNet, external checkpoint) is out of scope.
+
+``convert_batch`` is the same step for MANY pairs: every pair keeps its own ``conversion_frames()`` length and the forwards run as
+ragged eval-mode batches (``lengths=``: every row comes out as if it had been run alone at its own length), sorted by length with
+``plan_batches`` because a batch costs what its longest row costs.
 """
 import numpy as np
 import torch
@@ -64,4 +68,60 @@ def demo_conversion(G, P, sbmt_i, sbmt_j, max_len_pad=192, device='cuda:0', cond
     for n, c in enumerate(conditions):
         keep = len_trg if 'R' in c else len_org
         res.append(('{}_{}_{}_{}'.format(sbmt_i[0], sbmt_j[0], uid_org, c), out[n, :keep, :].cpu().numpy()))
+    return res
+
+
+def plan_batches(lengths, max_rows):
+    """Batches for ragged forwards over utterances of the given lengths (host only): the indices sorted by length (ties in their given
+    order) and cut into runs of at most max_rows.  Returns a list of index lists; every index appears exactly once, the batches come in
+    non-decreasing order of their T, and a batch's T is its longest (= last) member's length."""
+    max_rows = int(max_rows)
+    if max_rows < 1:
+        raise ValueError('plan_batches: max_rows must be at least 1')
+    order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
+    return [order[k:k + max_rows] for k in range(0, len(order), max_rows)]
+
+
+def _pad_rows(rows, T):
+    """[1, T_r, C] tensors -> [len(rows), T, C], zeros behind each row's own frames"""
+    out = rows[0].new_zeros(len(rows), T, rows[0].shape[-1])
+    for n, r in enumerate(rows):
+        out[n, :r.shape[1]] = r[0]
+    return out
+
+
+def convert_batch(G, P, pairs, max_len_pad=192, max_rows=16, device='cuda:0', conditions=CONDITIONS):
+    """demo_conversion for many pairs: pairs = [(sbmt_i, sbmt_j), ...] -> [demo_conversion(G, P, sbmt_i, sbmt_j, ...) per pair], the same
+    names and shapes.  Every pair is padded to its OWN conversion_frames(); Generator_6 runs as ragged batches over the pairs and
+    Generator_3 as ragged batches over pairs x conditions, both in plan_batches order with at most max_rows rows per forward."""
+    prep = []
+    for sbmt_i, sbmt_j in pairs:
+        T = conversion_frames((sbmt_i[2][2], sbmt_j[2][2]), max_len_pad)
+        prep.append((T, _prepare(sbmt_i, T, device), _prepare(sbmt_j, T, device)))
+    # F0 conversion: one row per pair
+    oh_con = [None] * len(pairs)
+    with torch.no_grad():
+        for batch in plan_batches([p[0] for p in prep], max_rows):
+            lens = [prep[k][0] for k in batch]
+            logits = P(_pad_rows([prep[k][1][0] for k in batch], lens[-1]), _pad_rows([prep[k][2][1] for k in batch], lens[-1]), lengths=lens)
+            for n, k in enumerate(batch):
+                lg = logits[n, :lens[n]]
+                oh_con[k] = torch.nn.functional.one_hot(lg.argmax(dim=-1), lg.shape[-1]).to(lg.dtype)[None]
+    # the conditions of every pair: one row each
+    rows = []                                          # (pair, condition index, x_f0, x_rh, emb, T)
+    for k, (T, (x_org, oh_org, emb_org, _, _), (x_trg, _, emb_trg, _, _)) in enumerate(prep):
+        xf_org, xf_trg = torch.cat((x_org, oh_org), -1), torch.cat((x_org, oh_con[k]), -1)
+        for n, c in enumerate(conditions):
+            rows.append((k, n, xf_trg if 'F' in c else xf_org, x_trg if 'R' in c else x_org, emb_trg if 'U' in c else emb_org, T))
+    res = [[None] * len(conditions) for _ in pairs]
+    with torch.no_grad():
+        for batch in plan_batches([r[5] for r in rows], max_rows):
+            lens = [rows[i][5] for i in batch]
+            out = G(_pad_rows([rows[i][2] for i in batch], lens[-1]), _pad_rows([rows[i][3] for i in batch], lens[-1]),
+                    torch.cat([rows[i][4] for i in batch]), lengths=lens)
+            for m, i in enumerate(batch):
+                k, n = rows[i][0], rows[i][1]
+                (sbmt_i, sbmt_j), c = pairs[k], conditions[n]
+                keep = prep[k][2][3] if 'R' in c else prep[k][1][3]
+                res[k][n] = ('{}_{}_{}_{}'.format(sbmt_i[0], sbmt_j[0], prep[k][1][4], c), out[m, :keep, :].cpu().numpy())
     return res

@@ -35,36 +35,48 @@ __device__ __forceinline__ float block_group_sum(float v, float* red, float* out
 __device__ __forceinline__ float gn_h(float x, float mean, float rstd) { return __fmul_rn(__fsub_rn(x, mean), rstd); }
 __device__ __forceinline__ float gn_z(float h, float ga, float be) { return __fmaf_rn(h, ga, be); }
 
+// Row length of a ragged eval-mode batch (RAG instantiations only): frames t >= len[b] of row b are padding.  Clamped to [0, T], so a
+// length outside the contract spoils its own row and nothing else.
+__device__ __forceinline__ int ragged_len(const int* __restrict__ len, int b, int T) { return min(max(len[b], 0), T); }
+
+// RAG (ragged eval-mode batch): the statistics are taken over the row's own L = len[b] frames (inv_n = 1 / (16 L)), frames t >= L are never
+// read and their outputs are stored as zeros -- with the zero halo rows, the padding the next k=5 convolution sees in a run of the utterance
+// alone.  RAG = false is the kernel as it was (len unused).
+template <bool RAG>
 __global__ __launch_bounds__(256) void gn_relu_fwd_kernel(const float* __restrict__ x, long x_ld, long x_bs,
                                                           float* __restrict__ y, long y_ld, long y_bs,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                          float* __restrict__ stats, int T, int C) {
+                                                          float* __restrict__ stats, const int* __restrict__ len, int T, int C) {
     __shared__ float red[256];
     __shared__ float g4[4];
     const int tid = threadIdx.x, l16 = tid & 15, rg = tid >> 4;
     const int b = blockIdx.y;
     const int c = blockIdx.x * 64 + l16 * 4;
     const int nit = (T + 15) >> 4;
+    int L = RAG ? ragged_len(len, b, T) : T;                // frames that count
     const float* xb = x + b * x_bs + (long)HALO * x_ld + c;
     f32x4 v[GN_MAXIT];
     float s = 0.f;
 #pragma unroll
     for (int it = 0; it < GN_MAXIT; ++it) {
         const int t = rg + it * 16;
-        if (it < nit && t < T) {
+        if (it < nit && t < L) {
             v[it] = *reinterpret_cast<const f32x4*>(xb + (long)t * x_ld);
             s += (v[it][0] + v[it][1]) + (v[it][2] + v[it][3]);
         } else {
             v[it] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
-    const float inv_n = 1.0f / (16.0f * (float)T);
+    const float inv_n = 1.0f / (16.0f * (float)L);
     const float mean = block_group_sum(s, red, g4, tid) * inv_n;
+    // RAG: the sixteen (t < L) lane masks are recomputed by each of the three loops instead of being carried across the two reductions in
+    // scalar registers (which spilled): the compiler must not know that L is the same value
+    if constexpr (RAG) asm volatile("" : "+s"(L));
     float ss = 0.f;
 #pragma unroll
     for (int it = 0; it < GN_MAXIT; ++it) {
         const int t = rg + it * 16;
-        if (it < nit && t < T) {
+        if (it < nit && t < L) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float dlt = __fsub_rn(v[it][j], mean);
@@ -82,6 +94,7 @@ __global__ __launch_bounds__(256) void gn_relu_fwd_kernel(const float* __restric
     const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c);
     const f32x4 be = *reinterpret_cast<const f32x4*>(beta + c);
     float* yb = y + b * y_bs + (long)HALO * y_ld + c;
+    if constexpr (RAG) asm volatile("" : "+s"(L));
 #pragma unroll
     for (int it = 0; it < GN_MAXIT; ++it) {
         const int t = rg + it * 16;
@@ -92,6 +105,7 @@ __global__ __launch_bounds__(256) void gn_relu_fwd_kernel(const float* __restric
                 const float z = gn_z(gn_h(v[it][j], mean, rstd), ga[j], be[j]);
                 o[j] = z > 0.f ? z : 0.f;
             }
+            if (RAG && t >= L) o = f32x4{0.f, 0.f, 0.f, 0.f};
             *reinterpret_cast<f32x4*>(yb + (long)t * y_ld) = o;
         }
     }
@@ -131,9 +145,11 @@ __device__ __forceinline__ double chunk_sum(const double* __restrict__ part, lon
 }
 
 // pass 0: sum of x; pass 1: sum of (x - mean)^2 (mean from the pass-0 partials in part0).  part_out[(b * C/16 + g) * nch + chunk]
-template <int PASS>
+// RAG (ragged eval-mode batch, see gn_relu_fwd_kernel): rows t >= len[b] are not read; a chunk wholly past the length writes 0.0 into its
+// slot, so the chunk-order sums -- and with them the bits of every run -- do not depend on what the padding holds.
+template <int PASS, bool RAG>
 __global__ __launch_bounds__(256) void gn_long_stats_kernel(const float* __restrict__ x, long x_ld, long x_bs, const double* __restrict__ part0,
-                                                            double* __restrict__ part_out, int T, int C) {
+                                                            double* __restrict__ part_out, const int* __restrict__ len, int T, int C) {
     __shared__ double red[256];
     __shared__ double ps[4 * GN_MAXCH];
     __shared__ float m4[4];
@@ -142,7 +158,8 @@ __global__ __launch_bounds__(256) void gn_long_stats_kernel(const float* __restr
     const int c = blockIdx.y * 64 + l16 * 4;
     const long G = C >> 4;
     const long grow0 = (long)b * G + blockIdx.y * 4;          // first of the workgroup's four groups
-    const float inv_n = 1.0f / (16.0f * (float)T);
+    const int L = RAG ? ragged_len(len, b, T) : T;
+    const float inv_n = 1.0f / (16.0f * (float)L);
     if (PASS == 1) {
         const double sum = chunk_sum(part0, grow0, nch, ps, tid);
         if (tid < 4) m4[tid] = (float)sum * inv_n;
@@ -154,7 +171,7 @@ __global__ __launch_bounds__(256) void gn_long_stats_kernel(const float* __restr
 #pragma unroll
     for (int it = 0; it < GN_CHUNK / 16; ++it) {
         const int t = chunk * GN_CHUNK + rg + it * 16;
-        if (t < T) {
+        if (t < L) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (long)t * x_ld);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -171,9 +188,11 @@ __global__ __launch_bounds__(256) void gn_long_stats_kernel(const float* __restr
     if (tid < 4) part_out[(grow0 + tid) * nch + chunk] = gs;
 }
 
+template <bool RAG>
 __global__ __launch_bounds__(256) void gn_long_out_kernel(const float* __restrict__ x, long x_ld, long x_bs, float* __restrict__ y, long y_ld, long y_bs,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ stats,
-                                                          const double* __restrict__ part0, const double* __restrict__ part1, int T, int C) {
+                                                          const double* __restrict__ part0, const double* __restrict__ part1, const int* __restrict__ len,
+                                                          int T, int C) {
     __shared__ double ps[2][4 * GN_MAXCH];
     __shared__ float m4[4], r4[4];
     const int tid = threadIdx.x, l16 = tid & 15, rg = tid >> 4;
@@ -181,7 +200,8 @@ __global__ __launch_bounds__(256) void gn_long_out_kernel(const float* __restric
     const int c = blockIdx.y * 64 + l16 * 4;
     const long G = C >> 4;
     const long grow0 = (long)b * G + blockIdx.y * 4;
-    const float inv_n = 1.0f / (16.0f * (float)T);
+    const int L = RAG ? ragged_len(len, b, T) : T;
+    const float inv_n = 1.0f / (16.0f * (float)L);
     const double sum = chunk_sum(part0, grow0, nch, ps[0], tid);
     const double sum2 = chunk_sum(part1, grow0, nch, ps[1], tid);
     if (tid < 4) {
@@ -204,7 +224,7 @@ __global__ __launch_bounds__(256) void gn_long_out_kernel(const float* __restric
 #pragma unroll
     for (int it = 0; it < GN_CHUNK / 16; ++it) {
         const int t = chunk * GN_CHUNK + rg + it * 16;
-        if (t < T) {
+        if (t < L) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (long)t * x_ld);
             f32x4 o;
 #pragma unroll
@@ -213,6 +233,8 @@ __global__ __launch_bounds__(256) void gn_long_out_kernel(const float* __restric
                 o[j] = z > 0.f ? z : 0.f;
             }
             *reinterpret_cast<f32x4*>(yb + (long)t * y_ld) = o;
+        } else if (RAG && t < T) {
+            *reinterpret_cast<f32x4*>(yb + (long)t * y_ld) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
 }
@@ -566,13 +588,17 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ i
     }
 }
 
+// RAG (ragged eval-mode batch): rows t >= len[b] of the source are not read, the destination gets zeros there
+template <bool RAG>
 __global__ __launch_bounds__(256) void copy_rows_kernel(const float* __restrict__ src, long s_ld, long s_bs,
-                                                        float* __restrict__ dst, long d_ld, long d_bs, int T, int C) {
+                                                        float* __restrict__ dst, long d_ld, long d_bs, const int* __restrict__ len, int T, int C) {
     const int b = blockIdx.y;
     const long n = (long)T * C;
+    const int L = RAG ? ragged_len(len, b, T) : T;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const int t = (int)(i / C), c = (int)(i - (long)t * C);
-        dst[b * d_bs + t * d_ld + c] = src[b * s_bs + t * s_ld + c];
+        if (RAG && t >= L) dst[b * d_bs + t * d_ld + c] = 0.f;
+        else dst[b * d_bs + t * d_ld + c] = src[b * s_bs + t * s_ld + c];
     }
 }
 
@@ -999,11 +1025,14 @@ __global__ __launch_bounds__(256) void adam_prepare_clip_kernel(AdamState* st, C
 }  // namespace
 
 hipError_t gn_relu_fwd(const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, const float* gamma,
-                       const float* beta, float* stats, int B, int T, int C, hipStream_t s, double* scratch) {
+                       const float* beta, float* stats, int B, int T, int C, hipStream_t s, double* scratch, const int* len) {
     if (C % 64 != 0 || T < 1) return hipErrorInvalidValue;
     if (T <= 16 * GN_MAXIT) {
-        hipLaunchKernelGGL(gn_relu_fwd_kernel, dim3(C / 64, B), dim3(256), 0, s, x, x_ld, x_bs, y, y_ld, y_bs, gamma, beta, stats,
-                           T, C);
+        if (len)
+            hipLaunchKernelGGL(gn_relu_fwd_kernel<true>, dim3(C / 64, B), dim3(256), 0, s, x, x_ld, x_bs, y, y_ld, y_bs, gamma, beta, stats, len, T, C);
+        else
+            hipLaunchKernelGGL(gn_relu_fwd_kernel<false>, dim3(C / 64, B), dim3(256), 0, s, x, x_ld, x_bs, y, y_ld, y_bs, gamma, beta, stats,
+                               len, T, C);
         return hipGetLastError();
     }
     // long sequence: chunk partials in scratch (gn_relu_fwd_scratch_bytes), three launches
@@ -1012,9 +1041,15 @@ hipError_t gn_relu_fwd(const float* x, long x_ld, long x_bs, float* y, long y_ld
     double* part0 = scratch;
     double* part1 = scratch + (long)B * (C / 16) * nch;
     const dim3 grid(nch, C / 64, B);
-    hipLaunchKernelGGL(gn_long_stats_kernel<0>, grid, dim3(256), 0, s, x, x_ld, x_bs, nullptr, part0, T, C);
-    hipLaunchKernelGGL(gn_long_stats_kernel<1>, grid, dim3(256), 0, s, x, x_ld, x_bs, part0, part1, T, C);
-    hipLaunchKernelGGL(gn_long_out_kernel, grid, dim3(256), 0, s, x, x_ld, x_bs, y, y_ld, y_bs, gamma, beta, stats, part0, part1, T, C);
+    if (len) {
+        hipLaunchKernelGGL((gn_long_stats_kernel<0, true>), grid, dim3(256), 0, s, x, x_ld, x_bs, nullptr, part0, len, T, C);
+        hipLaunchKernelGGL((gn_long_stats_kernel<1, true>), grid, dim3(256), 0, s, x, x_ld, x_bs, part0, part1, len, T, C);
+        hipLaunchKernelGGL(gn_long_out_kernel<true>, grid, dim3(256), 0, s, x, x_ld, x_bs, y, y_ld, y_bs, gamma, beta, stats, part0, part1, len, T, C);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((gn_long_stats_kernel<0, false>), grid, dim3(256), 0, s, x, x_ld, x_bs, nullptr, part0, len, T, C);
+    hipLaunchKernelGGL((gn_long_stats_kernel<1, false>), grid, dim3(256), 0, s, x, x_ld, x_bs, part0, part1, len, T, C);
+    hipLaunchKernelGGL(gn_long_out_kernel<false>, grid, dim3(256), 0, s, x, x_ld, x_bs, y, y_ld, y_bs, gamma, beta, stats, part0, part1, len, T, C);
     return hipGetLastError();
 }
 
@@ -1093,10 +1128,11 @@ hipError_t colsum_bias(const float* in, long ld, int R, int C, float* bih0, floa
 }
 
 hipError_t copy_rows(const float* src, long s_ld, long s_bs, float* dst, long d_ld, long d_bs, int B, int T, int C,
-                     hipStream_t s) {
+                     hipStream_t s, const int* len) {
     int gx = cdiv((long)T * C, 256);
     if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(copy_rows_kernel, dim3(gx, B), dim3(256), 0, s, src, s_ld, s_bs, dst, d_ld, d_bs, T, C);
+    if (len) hipLaunchKernelGGL(copy_rows_kernel<true>, dim3(gx, B), dim3(256), 0, s, src, s_ld, s_bs, dst, d_ld, d_bs, len, T, C);
+    else hipLaunchKernelGGL(copy_rows_kernel<false>, dim3(gx, B), dim3(256), 0, s, src, s_ld, s_bs, dst, d_ld, d_bs, len, T, C);
     return hipGetLastError();
 }
 

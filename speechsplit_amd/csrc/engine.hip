@@ -271,6 +271,7 @@ struct ss_engine {
         bool xf_img_valid = false;         // its gathers wrote xf_img
         bool grads_zeroed = false;         // fused training step: the gradient arena was zeroed on a branch stream during the forward
         bool bwd_sync_zeroed = false;      // the same for the backward recurrences' sync words / exchange tiles and the work-queue words
+        bool ragged = false;               // it ran over per-row lengths (ss_*_forward_ragged): eval-only, no backward exists for it
     } fwd;
     // ---- bookkeeping of the backward in flight: written by the decoder's lstm_bwd, read later in the same backward (and by
     // speaker_input_grad behind it); backward_decoder starts it from zero
@@ -1135,8 +1136,10 @@ float* grad_img_of(ss_engine* e, const float* p, long R) {
 // y = relu(GN(conv5(x)))   x: slab view (ld), y: slab view
 // gather (nullable): the resampling plan of the training forward -- GroupNorm + ReLU + gather in one kernel straight into gy / gy_img (the
 // resampled slab and its image at the first real row and the block's first column); y is then not written
+// lens (nullable; eval-mode forwards only): per-row lengths of a ragged batch, device i32[B] -- the GroupNorm takes its statistics over each
+// row's own frames and writes zeros behind them (the convolution itself is row-wise over a slab whose padded rows its producer zeroed)
 int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, const InterpPlan* gather = nullptr, float* gy = nullptr, long gy_ld = 0,
-                   float* gy_img = nullptr, hipEvent_t gather_ready = nullptr) {
+                   float* gy_img = nullptr, hipEvent_t gather_ready = nullptr, const int* lens = nullptr) {
     const int B = e->curB, T = e->curT;
     const long TP = T + 2 * HALO;
     GemmDesc d{};
@@ -1177,7 +1180,7 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
     }
     {
         Prof pr(e, SS_PROF_GN, s);
-        HIPCHK(gn_relu_fwd(cb.cout, cb.Co, TP * cb.Co, y.p, y.ld, TP * y.ld, e->P + cb.ga, e->P + cb.be, cb.stats, B, T, cb.Co, s, gn_scratch));
+        HIPCHK(gn_relu_fwd(cb.cout, cb.Co, TP * cb.Co, y.p, y.ld, TP * y.ld, e->P + cb.ga, e->P + cb.be, cb.stats, B, T, cb.Co, s, gn_scratch, lens));
     }
     return 0;
 }
@@ -1312,7 +1315,7 @@ int lstm_prep(ss_engine* e, LstmBlk& lb, PrepTable& tb, hipStream_t s) {
 }
 
 // Decoder-size BLSTM: one persistent launch per layer, or one launch per time step (persist = 0 / a batch the persistent kernels do not take).
-int lstm_big_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
+int lstm_big_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s, const int* lens) {
     const int B = e->curB, T = e->curT, H = lb.H;
     const long TP = T + 2 * HALO;
     const bool persist = g_persist && lstm_seq_supported(B, H);
@@ -1368,14 +1371,14 @@ int lstm_big_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
                 Prof pr(e, SS_PROF_REC_FWD, s, 2.0 * 2 * B * T * 4.0 * H * H);
                 HIPCHK(lstm_seq_fwd(lb.gates[l], e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.hf_l(l), lb.out[l], lb.csave[l],
                                     lb.sync_f(l), e->sticky, compact ? lb.xp0 : nullptr, compact ? lb.xf : 0, lb.out_img_valid ? lb.out_img[l] : nullptr, B, T, H,
-                                    false, false, s, e->img16() ? 1 | 2 : 0));      // 16-bit data path: bf16 images (1), products of the high fp16 pieces only (2)
+                                    false, false, s, e->img16() ? 1 | 2 : 0, lens));      // 16-bit data path: bf16 images (1), products of the high fp16 pieces only (2)
             }
             if (pw) CHK(fork_join(e, e->side3, s));
             continue;
         }
         HIPCHK(hipMemsetAsync(lb.hf, 0, 2 * half * 4, s));
         for (int st = 0; st < T; ++st)
-            HIPCHK(lstm_step_fwd(lb.gates[l], lb.wfrag[l], lb.hf + (st & 1) * half, lb.hf + ((st & 1) ^ 1) * half, lb.out[l], lb.csave[l], B, T, H, st, s));
+            HIPCHK(lstm_step_fwd(lb.gates[l], lb.wfrag[l], lb.hf + (st & 1) * half, lb.hf + ((st & 1) ^ 1) * half, lb.out[l], lb.csave[l], B, T, H, st, s, lens));
     }
     return 0;
 }
@@ -1383,8 +1386,9 @@ int lstm_big_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
 // the decoder's layer 0 runs on the compact (one row per block of repeated frames) form of its input
 static bool dec_compact(const ss_engine* e) { return g_compact0 && e->ld.xf > 0 && e->ld.big() && g_persist && lstm_seq_supported(e->curB, e->ld.H); }
 
-int lstm_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
-    if (lb.big()) return lstm_big_fwd(e, lb, x, s);
+// lens (nullable): per-row lengths of a ragged eval-mode batch; every recurrence of the block zeroes the state of rows behind their end
+int lstm_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s, const int* lens = nullptr) {
+    if (lb.big()) return lstm_big_fwd(e, lb, x, s, lens);
     const int B = e->curB, T = e->curT, H = lb.H;
     const long TP = T + 2 * HALO;
     for (int l = 0; l < lb.L; ++l) {
@@ -1411,7 +1415,7 @@ int lstm_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s) {
         {
             Prof pr(e, SS_PROF_ENC_REC, s);
             HIPCHK(lstm_small_fwd(lb.gates[l], e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.out[l], lb.csave[l], B, T, H,
-                                  s));
+                                  s, lens));
         }
     }
     return 0;
@@ -1831,7 +1835,10 @@ int act_scales_all(ss_engine* e, hipStream_t s) {
 
 // ---- whole-model schedules ---------------------------------------------------------------------------------
 // Encoder_7 (G3) / Encoder_6 (G6) trunk + their LSTMs, Encoder_t, decoder, head.  Inputs already in in_mel/in_f0/org/emb.
-int forward_core(ss_engine* e, bool training, const float* scales, const int* len_seg, int draw0, hipStream_t s, const FusedForward& fused = {}) {
+// lens (nullable; eval mode only): per-row lengths of a ragged batch (device i32[B], caller-owned, read in stream order).  The staging
+// of the inputs has zeroed the padded frames; here every GroupNorm and every recurrence takes the lengths, everything else is row-wise.
+int forward_core(ss_engine* e, bool training, const float* scales, const int* len_seg, int draw0, hipStream_t s, const FusedForward& fused = {},
+                 const int* lens = nullptr) {
     const int B = e->curB, T = e->curT;
     e->part_off = 0;           // split-K scratch: every launch of a step gets its own region; the previous step is through (stream order) when this one's first kernel runs
     const long TP = T + 2 * HALO;
@@ -1913,8 +1920,9 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
         // instead of silently overflowing to inf.
         if ((g_fwd_f16x2 || g_bwd_f16x2) && e->precision == SS_PRECISION_F32 && e->sticky) HIPCHK(param_guard(e->P, e->arena, 2048.0f, e->sticky, b2));
         // Encoder_t (model.py:74-89)
-        CHK(conv_block_fwd(e, e->ct, Slab{e->org, e->hp.dim_freq}, Slab{e->act_t, e->hp.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, b2));
-        CHK(lstm_fwd(e, e->lt, Slab{e->act_t, e->hp.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, b2));
+        CHK(conv_block_fwd(e, e->ct, Slab{e->org, e->hp.dim_freq}, Slab{e->act_t, e->hp.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, b2, nullptr, nullptr, 0,
+                           nullptr, nullptr, lens));
+        CHK(lstm_fwd(e, e->lt, Slab{e->act_t, e->hp.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, b2, lens));
         return 0;
     };
     for (int i = 0; i < 3; ++i) {
@@ -1934,8 +1942,8 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
                 CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s, &pl, e->xf[i] + HALO * CE, CE, gi, i == 0 ? plans : nullptr));
                 continue;
             }
-            CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, b1));
-            CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s));
+            CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, b1, nullptr, nullptr, 0, nullptr, nullptr, lens));
+            CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s, nullptr, nullptr, 0, nullptr, nullptr, lens));
             if (training) {
                 InterpPlan& pl = e->plan[draw0 + i];
                 if (i == 0) {
@@ -1952,10 +1960,10 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
         // one chain on `s` (Generator_6's single stack; Generator_3 without branch streams)
         if (g3) {
             Slab x1 = i == 0 ? Slab{e->in_mel, e->hp.dim_freq} : Slab{e->xf[i - 1], CE, nullptr, e->act_scale + e->c1[i - 1].scale_i};
-            CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s));
+            CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s, nullptr, nullptr, 0, nullptr, nullptr, lens));
         }
         Slab x2 = i == 0 ? Slab{e->in_f0, e->f0p} : Slab{e->xf[i - 1] + off2, CE, nullptr, e->act_scale + e->c2[i - 1].scale_i};
-        CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, s));
+        CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, s, nullptr, nullptr, 0, nullptr, nullptr, lens));
         if (training) {
             // one warp for both streams (model.py:202-206), len_seq = max_len_pad for every utterance (:105,157,203)
             InterpPlan& pl = e->plan[draw0 + i];
@@ -1970,8 +1978,8 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
         if (indep) CHK(fork_join(e, b2, b1));      // the pitch chain does not wait for the content chain
         else CHK(fork_join(e, s, b1));
     }
-    CHK(lstm_fwd(e, e->l2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, b1));
-    if (g3) CHK(lstm_fwd(e, e->l1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, s));
+    CHK(lstm_fwd(e, e->l2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, b1, lens));
+    if (g3) CHK(lstm_fwd(e, e->l1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, s, lens));
     if (par) CHK(fork_join(e, b1, s));
     // decoder input (model.py:301-309 / 341-347)
     CodeSrc src[3];
@@ -1993,7 +2001,7 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
         if (dec_compact(e)) HIPCHK(build_dec_in_compact(src, n, nullptr, 0, e->dec_in_dim, e->ld.xc, e->dec_in_dim, B, T, e->ld.xf, s));
         else HIPCHK(build_dec_in(src, n, nullptr, 0, e->dec_in_dim, e->dec_in, e->dec_in_dim, B, T, s));
     }
-    CHK(lstm_fwd(e, e->ld, dec_compact(e) ? Slab{e->ld.xc, e->dec_in_dim} : Slab{e->dec_in, e->dec_in_dim}, s));
+    CHK(lstm_fwd(e, e->ld, dec_compact(e) ? Slab{e->ld.xc, e->dec_in_dim} : Slab{e->dec_in, e->dec_in_dim}, s, lens));
     // LinearNorm head (model.py:253 / 277)
     const long HD = 2L * e->ld.H;
     GemmDesc d{};
@@ -2014,6 +2022,7 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     PGEMM_FWD_ON(SS_PROF_HEAD, d, s);
     e->fwd.training = training;
     e->fwd.enc_plan0 = draw0;
+    e->fwd.ragged = lens != nullptr;
     e->fwd.have = true;
     return 0;
 }
@@ -2339,23 +2348,25 @@ int speaker_input_grad(ss_engine* e, float* dc, hipStream_t s) {
 // ================================================================================================ C ABI
 namespace {
 
-int stage_g3_inputs(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, int B, int T, hipStream_t s) {
+// lens (nullable): ragged batch -- frames t >= len[b] of the inputs are not read, the slabs get zeros there
+int stage_g3_inputs(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, int B, int T, hipStream_t s, const int* lens = nullptr) {
     const ss_hparams& h = e->hp;
     const long TP = T + 2 * HALO;
     const int CI = h.dim_freq + h.dim_f0;      // 337
     // split x_f0 [B,T,337] into the mel slab and the (channel-padded) f0 slab (model.py:196-197)
-    HIPCHK(copy_rows(x_f0, CI, (long)T * CI, e->in_mel + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq, B, T, h.dim_freq, s));
-    HIPCHK(copy_rows(x_f0 + h.dim_freq, CI, (long)T * CI, e->in_f0 + HALO * e->f0p, e->f0p, TP * e->f0p, B, T, h.dim_f0, s));
+    HIPCHK(copy_rows(x_f0, CI, (long)T * CI, e->in_mel + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq, B, T, h.dim_freq, s, lens));
+    HIPCHK(copy_rows(x_f0 + h.dim_freq, CI, (long)T * CI, e->in_f0 + HALO * e->f0p, e->f0p, TP * e->f0p, B, T, h.dim_f0, s, lens));
     HIPCHK(copy_rows(x_org, h.dim_freq, (long)T * h.dim_freq, e->org + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq, B, T,
-                     h.dim_freq, s));
+                     h.dim_freq, s, lens));
     HIPCHK(hipMemcpyAsync(e->emb, c_trg, (long)B * h.dim_spk_emb * 4, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
-int export_out(ss_engine* e, float* out, int B, int T, hipStream_t s) {
+// lens (nullable): ragged batch -- the head is row-wise and leaves its bias in the padded frames of the slab; the caller's tensor gets zeros
+int export_out(ss_engine* e, float* out, int B, int T, hipStream_t s, const int* lens = nullptr) {
     const long TP = T + 2 * HALO;
     const int C = e->head_out;
-    HIPCHK(copy_rows(e->out_slab + HALO * C, C, TP * C, out, C, (long)T * C, B, T, C, s));
+    HIPCHK(copy_rows(e->out_slab + HALO * C, C, TP * C, out, C, (long)T * C, B, T, C, s, lens));
     return 0;
 }
 
@@ -2664,12 +2675,13 @@ static int backward_check(const ss_engine* e) {
     if (e->curT > e->maxT)
         return fail("backward: the last forward ran T above max_frames, which is eval-only (GroupNorm backward, training and input "
                     "gradients keep T <= max_frames <= 256)");
+    if (e->fwd.ragged)
+        return fail("backward: the last forward ran over per-row lengths (a ragged batch), which is eval-only (no gradient exists for it)");
     return 0;
 }
 
-int ss_g3_forward(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, const float* scales,
-                  const int* len_seg, int B, int T, int training, float* out, void* stream) {
-    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_forward on a Generator_6 engine");
+static int g3_forward(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, const float* scales, const int* len_seg,
+                      const int* lens, int B, int T, int training, float* out, void* stream) {
     CHK(entry_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;
@@ -2678,10 +2690,24 @@ int ss_g3_forward(ss_engine* e, const float* x_f0, const float* x_org, const flo
         return fail("train-mode forward needs T == max_len_pad (InterpLnr pads to max_len_pad, model.py:370)");
     if (training && (!scales || !len_seg)) return fail("train-mode forward needs the InterpLnr draws");
     CHK(geometry(e, B, T, s, !training));
-    CHK(stage_g3_inputs(e, x_f0, x_org, c_trg, B, T, s));
-    CHK(forward_core(e, training != 0, scales, len_seg, 0, s));
-    if (out) CHK(export_out(e, out, B, T, s));
+    CHK(stage_g3_inputs(e, x_f0, x_org, c_trg, B, T, s, lens));
+    CHK(forward_core(e, training != 0, scales, len_seg, 0, s, {}, lens));
+    if (out) CHK(export_out(e, out, B, T, s, lens));
     return 0;
+}
+
+int ss_g3_forward(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, const float* scales,
+                  const int* len_seg, int B, int T, int training, float* out, void* stream) {
+    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_forward on a Generator_6 engine");
+    return g3_forward(e, x_f0, x_org, c_trg, scales, len_seg, nullptr, B, T, training, out, stream);
+}
+
+int ss_g3_forward_ragged(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, const int* len_dev, int B, int T, int training,
+                         float* out, void* stream) {
+    if (!e) return fail("ss_g3_forward_ragged: null engine");
+    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_forward_ragged on an engine that is not a Generator_3");
+    if (training && len_dev) return fail("ss_g3_forward_ragged: ragged batches are eval-only (training != 0 with a length array)");
+    return g3_forward(e, x_f0, x_org, c_trg, nullptr, nullptr, len_dev, B, T, training, out, stream);
 }
 
 int ss_g3_backward(ss_engine* e, const float* d_out, void* stream) {
@@ -2711,8 +2737,7 @@ int ss_g3_backward_inputs(ss_engine* e, const float* d_out, float* dx_f0, float*
     return 0;
 }
 
-int ss_g3_rhythm(ss_engine* e, const float* x_org, int B, int T, float* codes, void* stream) {
-    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_rhythm on a Generator_6 engine");
+static int g3_rhythm(ss_engine* e, const float* x_org, const int* lens, int B, int T, float* codes, void* stream) {
     Own own(e, stream);
     hipStream_t s = own.s;
     CHK(geometry(e, B, T, s, true));
@@ -2720,7 +2745,7 @@ int ss_g3_rhythm(ss_engine* e, const float* x_org, int B, int T, float* codes, v
     const ss_hparams& h = e->hp;
     const long TP = T + 2 * HALO;
     HIPCHK(copy_rows(x_org, h.dim_freq, (long)T * h.dim_freq, e->org + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq, B, T,
-                     h.dim_freq, s));
+                     h.dim_freq, s, lens));
     CHK(conv_pack_all(e, e->ct, s));
     PrepTable tb;
     tb.n = 0;
@@ -2728,8 +2753,9 @@ int ss_g3_rhythm(ss_engine* e, const float* x_org, int B, int T, float* codes, v
     CHK(lstm_prep(e, e->lt, tb, s));
     HIPCHK(prep_run(tb, s));
     CHK(act_scales_all(e, s));
-    CHK(conv_block_fwd(e, e->ct, Slab{e->org, h.dim_freq}, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, s));
-    CHK(lstm_fwd(e, e->lt, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, s));
+    CHK(conv_block_fwd(e, e->ct, Slab{e->org, h.dim_freq}, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, s, nullptr, nullptr, 0, nullptr, nullptr, lens));
+    CHK(lstm_fwd(e, e->lt, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, s, lens));
+    // (ragged: the recurrence left zeros behind every row's end, so the codes of the padded blocks come out as zeros without a predicate)
     // codes = cat(fwd[:, 7::8], bwd[:, ::8]) (model.py:84-87): reuse the decoder-input assembler on a 2H-wide row (in d_ot's own geometry:
     // padding columns written zero, halo rows untouched) and pick t % freq == 0
     const int W = 2 * h.dim_neck_2;
@@ -2741,9 +2767,19 @@ int ss_g3_rhythm(ss_engine* e, const float* x_org, int B, int T, float* codes, v
     return 0;
 }
 
-int ss_g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, const float* scales, const int* len_seg, int B,
-                  int T, int training, float* out, void* stream) {
-    if (e->kind != SS_GENERATOR_6) return fail("ss_g6_forward on a Generator_3 engine");
+int ss_g3_rhythm(ss_engine* e, const float* x_org, int B, int T, float* codes, void* stream) {
+    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_rhythm on a Generator_6 engine");
+    return g3_rhythm(e, x_org, nullptr, B, T, codes, stream);
+}
+
+int ss_g3_rhythm_ragged(ss_engine* e, const float* x_org, const int* len_dev, int B, int T, float* codes, void* stream) {
+    if (!e) return fail("ss_g3_rhythm_ragged: null engine");
+    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_rhythm_ragged on an engine that is not a Generator_3");
+    return g3_rhythm(e, x_org, len_dev, B, T, codes, stream);
+}
+
+static int g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, const float* scales, const int* len_seg, const int* lens, int B,
+                      int T, int training, float* out, void* stream) {
     CHK(entry_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;
@@ -2754,11 +2790,25 @@ int ss_g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, const f
     const ss_hparams& h = e->hp;
     const long TP = T + 2 * HALO;
     HIPCHK(copy_rows(x_org, h.dim_freq, (long)T * h.dim_freq, e->org + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq, B, T,
-                     h.dim_freq, s));
-    HIPCHK(copy_rows(f0_trg, h.dim_f0, (long)T * h.dim_f0, e->in_f0 + HALO * e->f0p, e->f0p, TP * e->f0p, B, T, h.dim_f0, s));
-    CHK(forward_core(e, training != 0, scales, len_seg, 0, s));
-    if (out) CHK(export_out(e, out, B, T, s));
+                     h.dim_freq, s, lens));
+    HIPCHK(copy_rows(f0_trg, h.dim_f0, (long)T * h.dim_f0, e->in_f0 + HALO * e->f0p, e->f0p, TP * e->f0p, B, T, h.dim_f0, s, lens));
+    CHK(forward_core(e, training != 0, scales, len_seg, 0, s, {}, lens));
+    if (out) CHK(export_out(e, out, B, T, s, lens));
     return 0;
+}
+
+int ss_g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, const float* scales, const int* len_seg, int B,
+                  int T, int training, float* out, void* stream) {
+    if (e->kind != SS_GENERATOR_6) return fail("ss_g6_forward on a Generator_3 engine");
+    return g6_forward(e, x_org, f0_trg, scales, len_seg, nullptr, B, T, training, out, stream);
+}
+
+int ss_g6_forward_ragged(ss_engine* e, const float* x_org, const float* f0_trg, const int* len_dev, int B, int T, int training, float* out,
+                         void* stream) {
+    if (!e) return fail("ss_g6_forward_ragged: null engine");
+    if (e->kind != SS_GENERATOR_6) return fail("ss_g6_forward_ragged on an engine that is not a Generator_6");
+    if (training && len_dev) return fail("ss_g6_forward_ragged: ragged batches are eval-only (training != 0 with a length array)");
+    return g6_forward(e, x_org, f0_trg, nullptr, nullptr, len_dev, B, T, training, out, stream);
 }
 
 int ss_g6_backward(ss_engine* e, const float* d_out, void* stream) {
@@ -3174,8 +3224,8 @@ int ss_tune(const char* key, int value) {
     );
 }
 
-int ss_op_lstm_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch,
-                   long scratch_floats, int B, int T, int H, void* stream) {
+static int op_lstm_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch,
+                       long scratch_floats, const int* len, int B, int T, int H, void* stream) {
     hipStream_t s = S(stream);
     if (H > 32) {
         const long half = 2L * (((B + 15) / 16) * 16) * H, wn = 2L * 4 * H * H;
@@ -3183,17 +3233,28 @@ int ss_op_lstm_fwd(float* gates, const float* whh_f, const float* whh_b, float* 
         float* hf = scratch + wn;
         if (g_persist && lstm_seq_supported(B, H) && wn * 4 >= lstm_seq_xbytes(B, H, false)) {
             // exchange buffer in the (unused) packed-weight area, counters behind it
-            HIPCHK(lstm_seq_fwd(gates, whh_f, whh_b, scratch, out, csave, (unsigned*)hf, nullptr, nullptr, 0, nullptr, B, T, H, true, g_op_time_major != 0, s));
+            HIPCHK(lstm_seq_fwd(gates, whh_f, whh_b, scratch, out, csave, (unsigned*)hf, nullptr, nullptr, 0, nullptr, B, T, H, true, g_op_time_major != 0, s, 0, len));
             return 0;
         }
         HIPCHK(lstm_pack_w(whh_f, whh_b, scratch, H, 0, s));
         HIPCHK(hipMemsetAsync(hf, 0, 2 * half * 4, s));
         for (int st = 0; st < T; ++st)
-            HIPCHK(lstm_step_fwd(gates, scratch, hf + (st & 1) * half, hf + ((st & 1) ^ 1) * half, out, csave, B, T, H, st, s));
+            HIPCHK(lstm_step_fwd(gates, scratch, hf + (st & 1) * half, hf + ((st & 1) ^ 1) * half, out, csave, B, T, H, st, s, len));
     } else {
-        HIPCHK(lstm_small_fwd(gates, whh_f, whh_b, out, csave, B, T, H, s));
+        HIPCHK(lstm_small_fwd(gates, whh_f, whh_b, out, csave, B, T, H, s, len));
     }
     return 0;
+}
+
+int ss_op_lstm_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch,
+                   long scratch_floats, int B, int T, int H, void* stream) {
+    return op_lstm_fwd(gates, whh_f, whh_b, out, csave, scratch, scratch_floats, nullptr, B, T, H, stream);
+}
+
+int ss_op_lstm_fwd_ragged(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch,
+                          long scratch_floats, const int* len_dev, int B, int T, int H, void* stream) {
+    if (!gates || !whh_f || !whh_b || !out || !csave || B < 1 || T < 1) return fail("ss_op_lstm_fwd_ragged: null pointer or empty shape");
+    return op_lstm_fwd(gates, whh_f, whh_b, out, csave, scratch, scratch_floats, len_dev, B, T, H, stream);
 }
 
 int ss_op_lstm_bwd(float* gates, const float* whh_f, const float* whh_b, const float* d_out, const float* csave,
@@ -3293,9 +3354,9 @@ long ss_op_conv_block_scratch(int B, int T, int Ci, int Co) {
     return 2 * np + 2L * Co * 5 * Cp + (long)Ci * 5 * Co + R * (2 * Cp + 3L * Co) + 2L * B * (Co / 16) + 64 + gn;
 }
 
-int ss_op_conv_block(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, const float* dy,
-                     float* y, float* dx, float* gw, float* gb, float* ggamma, float* gbeta, float* scratch, long scratch_floats,
-                     int B, int T, int Ci, int Co, void* stream) {
+static int op_conv_block(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, const float* dy,
+                         float* y, float* dx, float* gw, float* gb, float* ggamma, float* gbeta, float* scratch, long scratch_floats,
+                         const int* len, int B, int T, int Ci, int Co, void* stream) {
     hipStream_t s = S(stream);
     if (!x || !w || !bias || !gamma || !beta || !y || !scratch) return fail("ss_op_conv_block: null pointer");
     if (Co % 64 || T < 1 || B < 1) return fail("ss_op_conv_block: needs Co % 64 == 0, B >= 1 and T >= 1");
@@ -3346,9 +3407,9 @@ int ss_op_conv_block(const float* x, const float* w, const float* bias, const fl
     HIPCHK(hipMemcpyAsync(e.P + cb.b, bias, Co * 4L, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(e.P + cb.ga, gamma, Co * 4L, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(e.P + cb.be, beta, Co * 4L, hipMemcpyDeviceToDevice, s));
-    HIPCHK(copy_rows(x, Ci, (long)T * Ci, xs + HALO * cb.Cp, cb.Cp, TP * cb.Cp, B, T, Ci, s));
+    HIPCHK(copy_rows(x, Ci, (long)T * Ci, xs + HALO * cb.Cp, cb.Cp, TP * cb.Cp, B, T, Ci, s, len));
     CHK(conv_pack_all(&e, cb, s));
-    CHK(conv_block_fwd(&e, cb, Slab{xs, cb.Cp}, Slab{ys, Co}, s));
+    CHK(conv_block_fwd(&e, cb, Slab{xs, cb.Cp}, Slab{ys, Co}, s, nullptr, nullptr, 0, nullptr, nullptr, len));
     HIPCHK(copy_rows(ys + HALO * Co, Co, TP * Co, y, Co, (long)T * Co, B, T, Co, s));
     if (dy) {
         if (!gw || !gb || !ggamma || !gbeta) return fail("ss_op_conv_block: backward needs the gradient outputs");
@@ -3362,6 +3423,18 @@ int ss_op_conv_block(const float* x, const float* w, const float* bias, const fl
         if (dx) HIPCHK(copy_rows(dxs + HALO * cb.Cp, cb.Cp, TP * cb.Cp, dx, Ci, (long)T * Ci, B, T, Ci, s));
     }
     return 0;
+}
+
+int ss_op_conv_block(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, const float* dy,
+                     float* y, float* dx, float* gw, float* gb, float* ggamma, float* gbeta, float* scratch, long scratch_floats,
+                     int B, int T, int Ci, int Co, void* stream) {
+    return op_conv_block(x, w, bias, gamma, beta, dy, y, dx, gw, gb, ggamma, gbeta, scratch, scratch_floats, nullptr, B, T, Ci, Co, stream);
+}
+
+int ss_op_conv_block_ragged(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, const int* len_dev,
+                            float* y, float* scratch, long scratch_floats, int B, int T, int Ci, int Co, void* stream) {
+    return op_conv_block(x, w, bias, gamma, beta, nullptr, y, nullptr, nullptr, nullptr, nullptr, nullptr, scratch, scratch_floats, len_dev, B, T,
+                         Ci, Co, stream);
 }
 
 const char* ss_stream_report(const ss_engine* e) { return e ? e->stream_report.c_str() : ""; }

@@ -38,7 +38,10 @@ hipError_t interp_scatter(const InterpPlan& p, const float* dy, long dy_ld, long
 // GroupNorm(16 channels per group, eps 1e-5, biased variance over 16 x T) + ReLU on rows [HALO, HALO+T) of haloed slabs.
 hipError_t gn_relu_fwd(const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, const float* gamma,
                        const float* beta, float* stats /*[B, C/16, 2] mean, rstd*/, int B, int T, int C, hipStream_t s,
-                       double* scratch = nullptr);
+                       double* scratch = nullptr, const int* len = nullptr);
+// len (nullable; device i32[B], eval-mode forwards only): a RAGGED batch.  Row b holds len[b] frames (every kernel that takes it uses
+// min(max(len[b], 0), T)); the frames behind them are padding that is never read: the statistics run over t < len[b] with
+// inv_n = 1 / (16 len[b]) and the outputs for t >= len[b] are zeros.  nullptr launches the kernels as compiled without the predicate.
 // T <= 256: one register-resident kernel, scratch unused.  T > 256 (eval-mode inference only; no backward exists for it): three
 // chunked launches that need gn_relu_fwd_scratch_bytes(B, T, C) bytes of scratch (8-byte aligned) for their float64 chunk partials.
 long gn_relu_fwd_scratch_bytes(int B, int T, int C);
@@ -68,8 +71,9 @@ hipError_t colsum_acc(const float* in, long ld, int R, int C, float* out, double
 // column sums of a BLSTM layer's [R][2 x C] gradient slab added to (b_ih, b_hh) of both directions
 hipError_t colsum_bias(const float* in, long ld, int R, int C, float* bih0, float* bhh0, float* bih1, float* bhh1, double* part, unsigned* ctr,
                        hipStream_t s);
+// len (nullable, as gn_relu_fwd): source rows t >= len[b] are not read and the destination gets zeros there
 hipError_t copy_rows(const float* src, long s_ld, long s_bs, float* dst, long d_ld, long d_bs, int B, int T, int C,
-                     hipStream_t s);
+                     hipStream_t s, const int* len = nullptr);
 // batch assembly from a device-resident corpus: see collate_kernel (crop rows, clip mel to [0,1], pad mel with 0 / F0 with -1e10)
 hipError_t collate(const float* mel_cat, const float* f0_cat, const float* emb_tab, const long* row0, const int* len,
                    const int* item, int B, int T, int C, int E, float* mel, float* f0, float* emb, hipStream_t s);
@@ -225,8 +229,10 @@ hipError_t f0_normalize(const double* f0, int n, float* out, hipStream_t s);
 constexpr int lstm_small_ld(int H) { return (H > 32 || (H & (H - 1)) == 0) ? 2 * H : (2 * H + 3) & ~3; }
 // gates: [B, TP, 8H] holds x.W_ih^T + b_ih + b_hh on entry (column = dir*4H + gate*H + j, gate order i,f,g,o) and the
 // activated gates on exit.  out: [B, TP, lstm_small_ld(H)].  csave: the cell states, same geometry.  whh: [2][4H][H].  H in 1..32.
+// len (nullable; device i32[B]): ragged eval-mode batch.  Row b's recurrence covers its own L = min(max(len[b], 0), T) frames (the reverse
+// direction starts at frame L - 1 from the zero state); out and csave are zero for t >= L; gates rows t >= L are neither read nor written.
 hipError_t lstm_small_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, int B, int T,
-                          int H, hipStream_t s);
+                          int H, hipStream_t s, const int* len = nullptr);
 // d_out: [B, TP, lstm_small_ld(H)] gradient of out.  gates is replaced in place by the pre-activation gradients.
 hipError_t lstm_small_bwd(float* gates, const float* whh_f, const float* whh_b, const float* d_out, const float* csave,
                           int B, int T, int H, hipStream_t s);
@@ -238,8 +244,9 @@ hipError_t lstm_small_bwd(float* gates, const float* whh_f, const float* whh_b, 
 //   hf     [2 ping-pong][2][ceil(B/16)][H/16][64][4]    h(t)   written by the forward epilogue, zero before step 0
 //   gf     [2 ping-pong][2][ceil(B/16)][4H/16][64][4]   da(t)  written by the backward epilogue, zero before step 0
 hipError_t lstm_pack_w(const float* whh_f, const float* whh_b, float* frag, int H, int transposed, hipStream_t s);
+// len (nullable; device i32[B]): ragged eval-mode batch, rows at frames t >= min(max(len[b], 0), T) leave the step with c = h = 0
 hipError_t lstm_step_fwd(float* gates, const float* wfrag, const float* hf_cur, float* hf_next, float* out, float* csave,
-                         int B, int T, int H, int step, hipStream_t s);
+                         int B, int T, int H, int step, hipStream_t s, const int* len = nullptr);
 // dc: [2][B][H] running cell-state gradient (no initialisation needed).
 hipError_t lstm_step_bwd(float* gates, const float* wfragT, const float* gf_cur, float* gf_next, const float* d_out,
                          const float* csave, float* dc, int B, int T, int H, int step, hipStream_t s);
@@ -259,7 +266,7 @@ long lstm_seq_xbytes(int B, int H, bool backward);
 // sticky (nullable): engine-wide word, host-visible, that a launch ORs 1 into when its bounded wait expires (never cleared by a step)
 hipError_t lstm_seq_fwd(float* gates, const float* whh_f, const float* whh_b, void* xbuf, float* out, float* csave,
                         unsigned* sync, unsigned* sticky, const float* xc, int xf, float* out_img, int B, int T, int H, bool zero_state,
-                        bool time_major, hipStream_t s, int img_bf16 = 0);       // img_bf16 bit 0: out_img is the plain bf16 tensor, not a format-v2 image; bit 1: products from the high fp16 pieces alone
+                        bool time_major, hipStream_t s, int img_bf16 = 0, const int* len = nullptr);       // len (nullable; device i32[B]): ragged eval-mode batch -- after the cell update of a step at frame t, rows with t >= min(max(len[b], 0), T) take c = h = 0 (select), and the zero h goes through the hand-off with the step's tag.  img_bf16 bit 0: out_img is the plain bf16 tensor, not a format-v2 image; bit 1: products from the high fp16 pieces alone
 // amax (nullable): device word that receives max |pre-activation gradient| written (atomic max of the float's bit pattern;
 // zero it first) -- the scale the fp16 x 2 GEMMs that consume the gradient slab need
 // gbias_f / gbias_b (nullable): [2][4H] gradient accumulators of (b_ih, b_hh) of the forward / reverse direction; the kernel

@@ -370,13 +370,18 @@ __device__ __forceinline__ void xb_store(unsigned char* xb_plane0, long plane_st
 
 // grid = ngroups * (H/16), block = 64*NW.   sync (LSTM_SEQ_SYNC_WORDS, all zero on entry, like xb): [0] abort word,
 // [1 + group] XCD masks, [64 + 32 * group + member] completion flags
-template <int H, int NW, bool TAG, bool HI>
+// RAG (ragged eval-mode batch; len = device i32[B]): after the cell update of a step at frame t, a row with t >= min(max(len[b], 0), T) takes
+// c = h = 0 -- a select, so non-finite values a padded frame's pre-activations may hold stay in that frame's own gate rows.  The reverse
+// direction thereby reaches the row's last frame with the zero state a run of the utterance alone starts from, and the forward direction
+// stores zeros behind the end.  The masked h goes through xb_store with the step's tag like any other (the consumers poll on it), and the
+// storing wave's copies take the masked values: out, csave and the bf16 image hold zeros there.  RAG = false compiles the predicate out.
+template <int H, int NW, bool TAG, bool HI, bool RAG>
 __global__ __launch_bounds__(64 * (NW + 2)) void lstm_seq_fwd_kernel(float* __restrict__ gates, const float* __restrict__ whh_f,
                                                                const float* __restrict__ whh_b, unsigned char* __restrict__ xb,
                                                                float* __restrict__ out, float* __restrict__ csave,
                                                                unsigned* __restrict__ sync, unsigned* __restrict__ sticky,
                                                                const float* __restrict__ xc, int xf, float* __restrict__ out_img, int B, int T,
-                                                               int nbt, int prio) {
+                                                               int nbt, int prio, const int* __restrict__ len) {
     // out_img (nullable): the pre-split image of `out` for the GEMMs that consume it (common.h GemmDesc::a_pre), written beside it
     // xc (nullable): the input projections in COMPACT form [B][T / xf][8H] -- the layer's input repeats in blocks of xf frames (the
     // decoder's up-sampled codes, model.py:301-309), so they were computed once per block; `gates` is then only written
@@ -527,6 +532,8 @@ __global__ __launch_bounds__(64 * (NW + 2)) void lstm_seq_fwd_kernel(float* __re
     const int j = jt * 16 + jj;
     const bool cell = tid < 256;
     float c_state = 0.f, h_val = 0.f;
+    int row_len = T;                                       // RAG: frames of this cell thread's utterance (rows past B mirror the last one)
+    if constexpr (RAG) row_len = min(max(len[bt * 16 + bi < B ? bt * 16 + bi : B - 1], 0), T);
 
     for (int st = 0; st < T; ++st) {
         f32x4 acc[4];
@@ -618,6 +625,11 @@ __global__ __launch_bounds__(64 * (NW + 2)) void lstm_seq_fwd_kernel(float* __re
             const float gi = sigmoidf_(pre[0]), gf = sigmoidf_(pre[1]), gg = ss_gate(pre[2], 2.0f), go = sigmoidf_(pre[3]);
             c_state = gf * c_state + gi * gg;
             h_val = go * ss_tanh(c_state);
+            if constexpr (RAG) {
+                const bool pad = tau_of(st) - HALO >= row_len;
+                c_state = pad ? 0.f : c_state;
+                h_val = pad ? 0.f : h_val;
+            }
             // the hand-off payload: write-through, first (rows past B carry garbage nobody stores downstream)
             if (!(diag & 2)) xb_store<HI>(xwr + ((st + 1) & 1) * half, plane, j, bi, h_val, local, TAG ? (int)tag_of(st + 1) : -1);
             float(*sb)[16][16] = st_buf[st & 1];         // slab copies: the storing wave picks them up behind the next barrier
@@ -1079,7 +1091,7 @@ static int seq_prio_arg(bool time_major, bool img_bf16 = false) {
 
 hipError_t lstm_seq_fwd(float* gates, const float* whh_f, const float* whh_b, void* xbuf, float* out, float* csave,
                         unsigned* sync, unsigned* sticky, const float* xc, int xf, float* out_img, int B, int T, int H, bool zero_state,
-                        bool time_major, hipStream_t s, int img_bf16) {
+                        bool time_major, hipStream_t s, int img_bf16, const int* len) {
     if (xc && (xf < 1 || T % xf)) return hipErrorInvalidValue;
     const int nbt = (B + 15) / 16;
     if (!lstm_seq_supported(B, H)) return hipErrorInvalidValue;
@@ -1095,12 +1107,14 @@ hipError_t lstm_seq_fwd(float* gates, const float* whh_f, const float* whh_b, vo
     // round-robin placement) 2.47 -> 2.03; groups that span XCDs, whose polls and write-through payload cross the fabric,
     // 3.10 -> 3.23 (B = 16) and 3.00 -> 3.47 (B = 48).  The backward gains either way (3.13 -> 2.98, 3.40 -> 2.49, 4.13 -> 3.25).
     const bool tag = g_seq_tag && (2 * nbt <= 8 || (2 * nbt) % 8 == 0);      // groups expected on one XCD each (seq_slots)
-#define SS_SEQ_FWD(HH, NWW, TG, HI_, GRID, BLK) hipLaunchKernelGGL((lstm_seq_fwd_kernel<HH, NWW, TG, HI_>), dim3(GRID), dim3(BLK), 0, s, gates, whh_f, whh_b, xb, out, csave, sync, sticky, xc, xf, out_img, B, T, nbt, pa)
+#define SS_SEQ_FWD_R(HH, NWW, TG, HI_, RG, GRID, BLK) hipLaunchKernelGGL((lstm_seq_fwd_kernel<HH, NWW, TG, HI_, RG>), dim3(GRID), dim3(BLK), 0, s, gates, whh_f, whh_b, xb, out, csave, sync, sticky, xc, xf, out_img, B, T, nbt, pa, len)
+#define SS_SEQ_FWD(HH, NWW, TG, HI_, GRID, BLK) do { if (len) SS_SEQ_FWD_R(HH, NWW, TG, HI_, true, GRID, BLK); else SS_SEQ_FWD_R(HH, NWW, TG, HI_, false, GRID, BLK); } while (0)
     if (H == 512 && tag) { if (hi) SS_SEQ_FWD(512, 8, true, true, seq_slots(nbt) * 32, 640); else SS_SEQ_FWD(512, 8, true, false, seq_slots(nbt) * 32, 640); }
     else if (H == 512)   { if (hi) SS_SEQ_FWD(512, 8, false, true, seq_slots(nbt) * 32, 640); else SS_SEQ_FWD(512, 8, false, false, seq_slots(nbt) * 32, 640); }
     else if (tag)        { if (hi) SS_SEQ_FWD(256, 4, true, true, seq_slots(nbt) * 16, 384); else SS_SEQ_FWD(256, 4, true, false, seq_slots(nbt) * 16, 384); }
     else                 { if (hi) SS_SEQ_FWD(256, 4, false, true, seq_slots(nbt) * 16, 384); else SS_SEQ_FWD(256, 4, false, false, seq_slots(nbt) * 16, 384); }
 #undef SS_SEQ_FWD
+#undef SS_SEQ_FWD_R
     return hipGetLastError();
 }
 

@@ -27,18 +27,38 @@ namespace {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return ss_sigmoid(x); }
 
+// Ragged eval-mode batches (len != nullptr; forward kernels only).  A workgroup owns one (utterance, direction), so the row's length
+// L = min(max(len[b], 0), T) is uniform in it and the predicate "state := 0 at frames t >= L" needs no per-step select: the forward
+// direction walks frames 0 .. L-1, the reverse direction L-1 .. 0 -- both from the zero state, which is what the masked walk over all T
+// frames would hand them -- and the frames behind get their zeros (h and c) from small_zero_tail.  The padded frames' pre-activations are
+// never read (they may hold anything) and their activated gates are not written: nothing reads those in eval mode.  len == nullptr gives
+// L = T, the loops as they were and an empty tail.
+__device__ __forceinline__ int small_len(const int* __restrict__ len, int b, int T) { return len ? min(max(len[b], 0), T) : T; }
+template <int H, int NT>
+__device__ __forceinline__ void small_zero_tail(float* __restrict__ out, float* __restrict__ csave, int b, int dir, int L, int T, int n) {
+    constexpr int OS = lstm_small_ld(H);
+    const long base = ((long)b * (T + 2 * HALO) + HALO + L) * OS + dir * H;
+    for (int i = n; i < (T - L) * H; i += NT) {
+        const long o = base + (long)(i / H) * OS + i % H;
+        out[o] = 0.f;
+        csave[o] = 0.f;
+    }
+}
+
 template <int H>
 __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_kernel(float* __restrict__ gates,
                                                                                    const float* __restrict__ whh_f,
                                                                                    const float* __restrict__ whh_b,
                                                                                    float* __restrict__ out,
-                                                                                   float* __restrict__ csave, int T, int prio) {
+                                                                                   float* __restrict__ csave, int T, int prio,
+                                                                                   const int* __restrict__ len) {
     if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (SMALL_PRIO)
     constexpr int OS = lstm_small_ld(H);           // row stride of out / csave
     __shared__ float hs[H];
     __shared__ float gs[4 * H];
     const int b = blockIdx.x, dir = blockIdx.y, n = threadIdx.x;
     const int TP = T + 2 * HALO;
+    const int L = small_len(len, b, T);
     const float* whh = dir ? whh_b : whh_f;
     const bool gate_thread = n < 4 * H;
     float w[H];
@@ -47,13 +67,13 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_kern
     if (n < H) hs[n] = 0.f;
     float c = 0.f;
     float* grow = gates + (long)b * TP * (8 * H) + dir * 4 * H + n;
-    auto tau_of = [&](int s) { return HALO + (dir == 0 ? s : T - 1 - s); };
-    float x_next = gate_thread ? grow[(long)tau_of(0) * (8 * H)] : 0.f;
+    auto tau_of = [&](int s) { return HALO + (dir == 0 ? s : L - 1 - s); };
+    float x_next = gate_thread && L > 0 ? grow[(long)tau_of(0) * (8 * H)] : 0.f;
     __syncthreads();
-    for (int s = 0; s < T; ++s) {
+    for (int s = 0; s < L; ++s) {
         const int tau = tau_of(s);
         const float xn = x_next;
-        if (s + 1 < T && gate_thread) x_next = grow[(long)tau_of(s + 1) * (8 * H)];
+        if (s + 1 < L && gate_thread) x_next = grow[(long)tau_of(s + 1) * (8 * H)];
         if (gate_thread) {
             float acc = xn;
 #pragma unroll
@@ -73,6 +93,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_kern
         }
         __syncthreads();
     }
+    small_zero_tail<H, (4 * H > 64 ? 4 * H : 64)>(out, csave, b, dir, L, T, n);
 }
 
 template <int H>
@@ -177,7 +198,8 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_lds_
                                                                                        const float* __restrict__ whh_f,
                                                                                        const float* __restrict__ whh_b,
                                                                                        float* __restrict__ out,
-                                                                                       float* __restrict__ csave, int T, int prio) {
+                                                                                       float* __restrict__ csave, int T, int prio,
+                                                                                       const int* __restrict__ len) {
     if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (SMALL_PRIO)
     constexpr int NT = 4 * H > 64 ? 4 * H : 64;
     constexpr int OS = lstm_small_ld(H);
@@ -187,6 +209,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_lds_
     __shared__ float gs[4 * H];
     const int b = blockIdx.x, dir = blockIdx.y, n = threadIdx.x;
     const int TP = T + 2 * HALO;
+    const int L = small_len(len, b, T);
     const float* whh = dir ? whh_b : whh_f;
     const bool gate_thread = n < 4 * H;
     float w[H];
@@ -195,12 +218,12 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_lds_
     if (n < H) hs[n] = 0.f;
     float c = 0.f;
     float* g0 = gates + (long)b * TP * (8 * H) + dir * 4 * H;
-    auto tau_of = [&](int s) { return HALO + (dir == 0 ? s : T - 1 - s); };
+    auto tau_of = [&](int s) { return HALO + (dir == 0 ? s : L - 1 - s); };
     // 4H floats per row = H float4; row stride 2H float4
-    stage_rows<NT, H, 16>(reinterpret_cast<const float4*>(g0), reinterpret_cast<float4*>(xs), T, n, tau_of);
+    stage_rows<NT, H, 16>(reinterpret_cast<const float4*>(g0), reinterpret_cast<float4*>(xs), L, n, tau_of);
     float* grow = g0 + n;
     lds_barrier();
-    for (int s = 0; s < T; ++s) {
+    for (int s = 0; s < L; ++s) {
         const int tau = tau_of(s);
         if (gate_thread) {
             float acc = xs[s * 4 * H + n];
@@ -221,6 +244,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_lds_
         }
         lds_barrier();
     }
+    small_zero_tail<H, NT>(out, csave, b, dir, L, T, n);
 }
 
 // Single-wave variant for 4H <= 64 (H = 1 .. 16): all gate threads sit in one wave, so a step needs no LDS exchange and no
@@ -230,7 +254,7 @@ __global__ __launch_bounds__((4 * H > 64 ? 4 * H : 64)) void lstm_small_fwd_lds_
 template <int H>
 __global__ __launch_bounds__(64) void lstm_small_fwd_wave_kernel(float* __restrict__ gates, const float* __restrict__ whh_f,
                                                                  const float* __restrict__ whh_b, float* __restrict__ out,
-                                                                 float* __restrict__ csave, int T, int prio) {
+                                                                 float* __restrict__ csave, int T, int prio, const int* __restrict__ len) {
     if (prio) __builtin_amdgcn_s_setprio(3);       // latency chains: issue ahead of co-resident GEMM waves (SMALL_PRIO)
     static_assert(4 * H <= 64, "one wave");
     constexpr int OS = lstm_small_ld(H);
@@ -238,23 +262,24 @@ __global__ __launch_bounds__(64) void lstm_small_fwd_wave_kernel(float* __restri
     float* xs = dyn;
     const int b = blockIdx.x, dir = blockIdx.y, n = threadIdx.x;
     const int TP = T + 2 * HALO;
+    const int L = small_len(len, b, T);
     const float* whh = dir ? whh_b : whh_f;
     const bool gate_thread = n < 4 * H;
     float w[H];
 #pragma unroll
     for (int k = 0; k < H; ++k) w[k] = gate_thread ? whh[n * H + k] : 0.f;
     float* g0 = gates + (long)b * TP * (8 * H) + dir * 4 * H;
-    auto tau_of = [&](int s) { return HALO + (dir == 0 ? s : T - 1 - s); };
-    stage_rows<64, H, 16>(reinterpret_cast<const float4*>(g0), reinterpret_cast<float4*>(xs), T, n, tau_of);
+    auto tau_of = [&](int s) { return HALO + (dir == 0 ? s : L - 1 - s); };
+    stage_rows<64, H, 16>(reinterpret_cast<const float4*>(g0), reinterpret_cast<float4*>(xs), L, n, tau_of);
     lds_barrier();
     float* grow = g0 + n;
     const int nn = gate_thread ? n : 0;                      // idle lanes mirror lane 0 (never stored)
     float c = 0.f, h = 0.f;
     float xn = xs[nn];
-    for (int s = 0; s < T; ++s) {
+    for (int s = 0; s < L; ++s) {
         const int tau = tau_of(s);
         float acc = xn;
-        if (s + 1 < T) xn = xs[(s + 1) * 4 * H + nn];         // next step's pre-activation: no dependence on this step
+        if (s + 1 < L) xn = xs[(s + 1) * 4 * H + nn];         // next step's pre-activation: no dependence on this step
 #pragma unroll
         for (int k = 0; k < H; ++k) acc += w[k] * __int_as_float(__builtin_amdgcn_readlane(__float_as_int(h), k));
         const float act = ss_gate(acc, (nn / H == 2) ? 2.0f : 1.0f);
@@ -270,6 +295,7 @@ __global__ __launch_bounds__(64) void lstm_small_fwd_wave_kernel(float* __restri
             csave[o] = c;
         }
     }
+    small_zero_tail<H, 64>(out, csave, b, dir, L, T, n);
 }
 
 // dynamic LDS, all in STEP order of the backward walk: ga[T][4H] activated gates, dd[T][H] d_out, cc[T + 1][H] cell states
@@ -370,24 +396,24 @@ hipError_t allow_lds(K kernel, long bytes) {
 }
 
 template <int H>
-hipError_t fwd_t(float* gates, const float* wf, const float* wb, float* out, float* csave, int B, int T, hipStream_t s) {
+hipError_t fwd_t(float* gates, const float* wf, const float* wb, float* out, float* csave, int B, int T, hipStream_t s, const int* len) {
     constexpr int NT = 4 * H > 64 ? 4 * H : 64;
     const long bytes = (long)T * 4 * H * 4;
     if constexpr (4 * H <= 64) {
         if (g_small_lds == 1 && bytes <= LDS_BUDGET) {
             hipError_t e = allow_lds(lstm_small_fwd_wave_kernel<H>, bytes);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((lstm_small_fwd_wave_kernel<H>), dim3(B, 2), dim3(64), bytes, s, gates, wf, wb, out, csave, T, SMALL_PRIO);
+            hipLaunchKernelGGL((lstm_small_fwd_wave_kernel<H>), dim3(B, 2), dim3(64), bytes, s, gates, wf, wb, out, csave, T, SMALL_PRIO, len);
             return hipGetLastError();
         }
     }
     if (g_small_lds && bytes <= LDS_BUDGET) {
         hipError_t e = allow_lds(lstm_small_fwd_lds_kernel<H>, bytes);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((lstm_small_fwd_lds_kernel<H>), dim3(B, 2), dim3(NT), bytes, s, gates, wf, wb, out, csave, T, SMALL_PRIO);
+        hipLaunchKernelGGL((lstm_small_fwd_lds_kernel<H>), dim3(B, 2), dim3(NT), bytes, s, gates, wf, wb, out, csave, T, SMALL_PRIO, len);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((lstm_small_fwd_kernel<H>), dim3(B, 2), dim3(NT), 0, s, gates, wf, wb, out, csave, T, SMALL_PRIO);
+    hipLaunchKernelGGL((lstm_small_fwd_kernel<H>), dim3(B, 2), dim3(NT), 0, s, gates, wf, wb, out, csave, T, SMALL_PRIO, len);
     return hipGetLastError();
 }
 template <int H>
@@ -406,7 +432,7 @@ hipError_t bwd_t(float* gates, const float* wf, const float* wb, const float* d_
 }
 
 // one instantiation per hidden size 1..32, dispatched through a table (the six power-of-two sizes compile exactly as they did behind a switch)
-using FwdFn = hipError_t (*)(float*, const float*, const float*, float*, float*, int, int, hipStream_t);
+using FwdFn = hipError_t (*)(float*, const float*, const float*, float*, float*, int, int, hipStream_t, const int*);
 using BwdFn = hipError_t (*)(float*, const float*, const float*, const float*, const float*, int, int, hipStream_t);
 template <int... I>
 constexpr std::array<FwdFn, sizeof...(I)> fwd_table(std::integer_sequence<int, I...>) { return {fwd_t<I + 1>...}; }
@@ -418,9 +444,9 @@ constexpr auto kBwd = bwd_table(std::make_integer_sequence<int, 32>{});
 }  // namespace
 
 hipError_t lstm_small_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, int B, int T,
-                          int H, hipStream_t s) {
+                          int H, hipStream_t s, const int* len) {
     if (H < 1 || H > 32) return hipErrorInvalidValue;
-    return kFwd[H - 1](gates, whh_f, whh_b, out, csave, B, T, s);
+    return kFwd[H - 1](gates, whh_f, whh_b, out, csave, B, T, s, len);
 }
 
 hipError_t lstm_small_bwd(float* gates, const float* whh_f, const float* whh_b, const float* d_out, const float* csave,

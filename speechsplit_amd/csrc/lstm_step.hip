@@ -43,7 +43,10 @@ template <int H, int NW, int G>
 __global__ __launch_bounds__(64 * NW) void lstm_step_fwd_kernel(float* __restrict__ gates, const float* __restrict__ wfrag,
                                                                 const float* __restrict__ hf_cur, float* __restrict__ hf_next,
                                                                 float* __restrict__ out, float* __restrict__ csave, int B,
-                                                                int T, int step, int mode) {
+                                                                int T, int step, int mode, const int* __restrict__ len) {
+    // len (nullable): ragged eval-mode batch -- a row whose frame of this step lies at or behind its length leaves the step with
+    // c = h = 0 (a select: whatever the padded frames' pre-activations hold stays in their own gate rows), so the reverse direction
+    // reaches the row's last frame with the zero state and the forward direction stores zeros behind it
     __shared__ float red[NW][4][16][16];
     if (mode == 3) return;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -135,8 +138,9 @@ __global__ __launch_bounds__(64 * NW) void lstm_step_fwd_kernel(float* __restric
         }
         const long o = ((long)b * TP + tau) * (2 * H) + dir * H + j;
         const float gi = sigmoidf_(pre[0]), gf = sigmoidf_(pre[1]), gg = ss_gate(pre[2], 2.0f), go = sigmoidf_(pre[3]);
-        const float c = gf * cp + gi * gg;
-        const float h = go * ss_tanh(c);
+        float c = gf * cp + gi * gg;
+        float h = go * ss_tanh(c);
+        if (len && tau - HALO >= min(max(len[b], 0), T)) c = h = 0.f;
         grow[0] = gi;
         grow[H] = gf;
         grow[2 * H] = gg;
@@ -273,9 +277,9 @@ __global__ __launch_bounds__(256) void lstm_pack_w_kernel(const float* __restric
 
 template <int H, int NW, int G>
 hipError_t fwd_l(float* gates, const float* wfrag, const float* hf_cur, float* hf_next, float* out, float* csave, int B, int T,
-                 int step, hipStream_t s) {
+                 int step, hipStream_t s, const int* len) {
     hipLaunchKernelGGL((lstm_step_fwd_kernel<H, NW, G>), dim3(H / 16, cdiv(B, 16), 2), dim3(64 * NW), 0, s, gates, wfrag, hf_cur,
-                       hf_next, out, csave, B, T, step, g_lstm_mode);
+                       hf_next, out, csave, B, T, step, g_lstm_mode, len);
     return hipGetLastError();
 }
 template <int H, int NW, int G>
@@ -288,7 +292,7 @@ hipError_t bwd_l(float* gates, const float* wfragT, const float* gf_cur, float* 
 
 }  // namespace
 
-#define FWD_ARGS gates, wfrag, hf_cur, hf_next, out, csave, B, T, step, s
+#define FWD_ARGS gates, wfrag, hf_cur, hf_next, out, csave, B, T, step, s, len
 #define BWD_ARGS gates, wfragT, gf_cur, gf_next, d_out, csave, dc, B, T, step, s
 
 hipError_t lstm_pack_w(const float* whh_f, const float* whh_b, float* frag, int H, int transposed, hipStream_t s) {
@@ -297,7 +301,7 @@ hipError_t lstm_pack_w(const float* whh_f, const float* whh_b, float* frag, int 
 }
 
 hipError_t lstm_step_fwd(float* gates, const float* wfrag, const float* hf_cur, float* hf_next, float* out, float* csave,
-                         int B, int T, int H, int step, hipStream_t s) {
+                         int B, int T, int H, int step, hipStream_t s, const int* len) {
     const int nw = g_lstm_nw, g = g_lstm_g;
     switch (H) {
         case 64: return fwd_l<64, 4, 1>(FWD_ARGS);

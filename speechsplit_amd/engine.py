@@ -9,6 +9,7 @@ import torch
 from . import _capi
 
 KIND = {'G3': 3, 'G6': 6, 'interp': 0}
+RAGGED = ('ragged',)                   # Engine._fwd_bt after a forward over per-row lengths: there is no backward for it
 
 
 def _ptr(t):
@@ -30,6 +31,26 @@ def draw_interp(batch, ncalls, hp, generator=None):
     return torch.stack(sc), torch.stack(ls).reshape(ncalls, -1).to(torch.int32)
 
 
+def check_lengths(lengths, B, T, factors=(1,), device=None):
+    """Per-row lengths of a ragged eval-mode batch -> contiguous int32 tensor on `device` (the i32[B] array the ss_*_ragged entry points read).
+    lengths: a host list / array / tensor, or a device int tensor.  What the host can see is validated here -- one length per row, each a
+    multiple of every factor and within [largest factor, T] -- and a ValueError is raised before anything is enqueued; a tensor that already
+    lives on a GPU is checked for its count only (reading it would synchronise), and the kernels clamp what they read to [0, T]."""
+    t = lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths))
+    if t.dim() != 1 or t.numel() != B:
+        raise ValueError(f'speechsplit_amd: lengths must hold one entry per row ({B}), got shape {tuple(t.shape)}')
+    if t.is_floating_point() or t.dtype == torch.bool:
+        raise ValueError('speechsplit_amd: lengths must be integers')
+    if not t.is_cuda:
+        lo = max(int(f) for f in factors)
+        for b, n in enumerate(t.tolist()):
+            if any(n % int(f) for f in factors):
+                raise ValueError(f'speechsplit_amd: lengths[{b}] = {n} is not a multiple of the code factors {tuple(int(f) for f in factors)}')
+            if n < lo or n > T:
+                raise ValueError(f'speechsplit_amd: lengths[{b}] = {n} is outside [{lo}, T = {T}]')
+    return t.to(device=device if device is not None else t.device, dtype=torch.int32).contiguous()
+
+
 class Engine:
     def __init__(self, kind, hp, max_batch, max_frames=None, device=None, alloc=None):
         """alloc(name, shape, dtype): optional provider of every device buffer the engine owns or returns -- the arenas 'params' / 'grads' /
@@ -45,7 +66,7 @@ class Engine:
         self.max_frames = int(max_frames or hp.max_len_pad)
         self._stagers = {}
         self._alloc = alloc
-        self._fwd_bt = None                # (B, T) of the last g3_forward / g6_forward; None after any other forward
+        self._fwd_bt = None                # (B, T) of the last g3_forward / g6_forward (RAGGED: it ran over lengths); None after any other forward
         self._hps = _capi.hparams_struct(hp)
         self.h = self.lib.ss_create(KIND[kind], C.byref(self._hps), self.max_batch, self.max_frames)
         if not self.h:
@@ -152,9 +173,19 @@ class Engine:
             st = self._stagers[key] = DrawStager(self.device, key[0], key[1])
         return st.stage(sc, ls)
 
+    def _lengths(self, lengths, B, T, training=False):
+        """lengths of a ragged eval-mode batch -> device i32[B] (check_lengths); ValueError for what the host can see is wrong, training included."""
+        if training:
+            raise ValueError('speechsplit_amd: lengths (a ragged batch) are for eval-mode forwards only, not training=True')
+        hp = self.hp
+        return check_lengths(lengths, B, T, (hp.freq, hp.freq_2, hp.freq_3), self.device)
+
     # ------------------------------------------------------------------ Generator_3
-    def g3_forward(self, x_f0, x_org, c_trg, draws=None, training=False):
+    def g3_forward(self, x_f0, x_org, c_trg, draws=None, training=False, lengths=None):
+        """lengths (eval mode only): one frame count per row -- a ragged batch (ss_g3_forward_ragged).  Row b of the result equals the
+        forward of that utterance alone at T = lengths[b]; the frames behind are zeros, the input frames behind are never read."""
         B, T, _ = x_org.shape
+        ln = self._lengths(lengths, B, T, training) if lengths is not None else None
         x_f0, x_org, c_trg = self._f(x_f0), self._f(x_org), self._f(c_trg)
         if c_trg.shape[0] != B:
             c_trg = c_trg.expand(B, -1).contiguous()
@@ -162,6 +193,10 @@ class Engine:
         out = self._new('out', (B, T, self.hp.dim_freq))
         self._fwd_bt = None
         self._reserve_eval(B, T, training)
+        if ln is not None:
+            _capi.check(self.lib.ss_g3_forward_ragged(self.h, _ptr(x_f0), _ptr(x_org), _ptr(c_trg), _ptr(ln), B, T, 0, _ptr(out), _stream()))
+            self._fwd_bt = RAGGED                      # eval-only: no input gradients, and ss_*_backward* refuses
+            return out
         _capi.check(self.lib.ss_g3_forward(self.h, _ptr(x_f0), _ptr(x_org), _ptr(c_trg), _ptr(sc), _ptr(ls), B, T,
                                            int(training), _ptr(out), _stream()))
         self._fwd_bt = (B, T)
@@ -175,6 +210,9 @@ class Engine:
         unknown = set(inputs) - set(names)
         if unknown:
             raise ValueError(f'speechsplit_amd: no input named {sorted(unknown)} (expected some of {names})')
+        if self._fwd_bt == RAGGED:
+            raise RuntimeError('speechsplit_amd: backward: the last forward ran over per-row lengths (a ragged batch), which is eval-only '
+                               '(no gradient exists for it)')
         if self._fwd_bt is None:
             raise RuntimeError('speechsplit_amd: input gradients need a preceding g3_forward / g6_forward on this engine')
         B, T = self._fwd_bt
@@ -195,12 +233,17 @@ class Engine:
         _capi.check(self.lib.ss_g3_backward_inputs(self.h, _ptr(d_out), _ptr(dx_f0), _ptr(dx_org), _ptr(dc_trg), _stream()))
         return dx_f0, dx_org, dc_trg
 
-    def g3_rhythm(self, x_org):
-        self._fwd_bt = None
+    def g3_rhythm(self, x_org, lengths=None):
+        """lengths: a ragged batch (ss_g3_rhythm_ragged); the code rows >= lengths[b] / freq_2 of row b are zeros."""
         B, T, _ = x_org.shape
+        ln = self._lengths(lengths, B, T) if lengths is not None else None
+        self._fwd_bt = None
         self._reserve_eval(B, T, False)
         x_org = self._f(x_org)
         codes = self._new('codes', (B, T // self.hp.freq_2, 2 * self.hp.dim_neck_2))
+        if ln is not None:
+            _capi.check(self.lib.ss_g3_rhythm_ragged(self.h, _ptr(x_org), _ptr(ln), B, T, _ptr(codes), _stream()))
+            return codes
         _capi.check(self.lib.ss_g3_rhythm(self.h, _ptr(x_org), B, T, _ptr(codes), _stream()))
         return codes
 
@@ -339,13 +382,19 @@ class Engine:
         return self.loss
 
     # ------------------------------------------------------------------ Generator_6
-    def g6_forward(self, x_org, f0_trg, draws=None, training=False):
+    def g6_forward(self, x_org, f0_trg, draws=None, training=False, lengths=None):
+        """lengths (eval mode only): a ragged batch, as g3_forward (ss_g6_forward_ragged)."""
         B, T, _ = x_org.shape
+        ln = self._lengths(lengths, B, T, training) if lengths is not None else None
         x_org, f0_trg = self._f(x_org), self._f(f0_trg)
         sc, ls = self._draws(draws)
         out = self._new('out', (B, T, self.hp.dim_f0))
         self._fwd_bt = None
         self._reserve_eval(B, T, training)
+        if ln is not None:
+            _capi.check(self.lib.ss_g6_forward_ragged(self.h, _ptr(x_org), _ptr(f0_trg), _ptr(ln), B, T, 0, _ptr(out), _stream()))
+            self._fwd_bt = RAGGED
+            return out
         _capi.check(self.lib.ss_g6_forward(self.h, _ptr(x_org), _ptr(f0_trg), _ptr(sc), _ptr(ls), B, T, int(training),
                                            _ptr(out), _stream()))
         self._fwd_bt = (B, T)
@@ -565,11 +614,11 @@ def gemm_img(a_img, b_img, ta=False, tb=False, bias=None, ksplit=1, cfg=-1, scal
     return c
 
 
-def conv_block(x, w, bias, gamma, beta, dy=None, need_dx=True, scratch=None, out=None):
+def conv_block(x, w, bias, gamma, beta, dy=None, need_dx=True, scratch=None, out=None, lengths=None):
     """Test hook (ss_op_conv_block): relu(GroupNorm(conv5(x))) of one block through the engine's block routines.
     x [B,T,Ci] -> y [B,T,Co]; with dy also (dx, gw, gb, ggamma, gbeta).  The C ABI takes dense tensors: contiguous operands are passed where
     they lie (any base), others are copied.  scratch: pre-placed, at least ss_op_conv_block_scratch() floats; out: dict of pre-placed dense
-    outputs by name (y, dx, gw, gb, ggamma, gbeta)."""
+    outputs by name (y, dx, gw, gb, ggamma, gbeta).  lengths: per-row frame counts of a ragged batch (ss_op_conv_block_ragged; forward only)."""
     lib = _capi.lib()
     B, T, Ci = x.shape
     Co = w.shape[0]
@@ -590,6 +639,13 @@ def conv_block(x, w, bias, gamma, beta, dy=None, need_dx=True, scratch=None, out
         assert tuple(t.shape) == shape and t.is_contiguous(), name
         return t
     y = o('y', B, T, Co)
+    if lengths is not None:
+        if dy is not None:
+            raise ValueError('speechsplit_amd: a ragged conv block runs the forward only')
+        ln = check_lengths(lengths, B, T, (1,), dev)
+        _capi.check(lib.ss_op_conv_block_ragged(_ptr(x), _ptr(w), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(ln), _ptr(y), _ptr(scratch), n,
+                                                B, T, Ci, Co, _stream()))
+        return y
     if dy is None:
         _capi.check(lib.ss_op_conv_block(_ptr(x), _ptr(w), _ptr(bias), _ptr(gamma), _ptr(beta), None, _ptr(y), None, None, None,
                                          None, None, _ptr(scratch), n, B, T, Ci, Co, _stream()))
@@ -657,14 +713,15 @@ def lstm_scratch(B, H, backward, persist=True):
     return n
 
 
-def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None, place=None):
+def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None, place=None, lengths=None):
     """Test hook: one bidirectional LSTM layer through ss_op_lstm_fwd / ss_op_lstm_bwd (the engine's recurrence kernels) with
     the input projection and the weight / input gradients on the engine's GEMM (ss_op_gemm).  w_ih etc. are (forward, reverse)
     pairs with PyTorch's shapes.  Returns out [B,T,2H]; with d_out also (dx, [(gw_ih, gw_hh, gb) per direction]).
     place(name, shape): optional allocator of the recurrences' operands -- 'gates' [R,8H], 'out' / 'csave' / 'd_out' [B,T+4,ld] and
     'scratch_fwd' / 'scratch_bwd' [lstm_scratch(...) floats, at least 1] -- for callers that pre-place them.  It returns a dense tensor that
     the CALLER has initialised as the kernels' contracts ask (halo rows of out / csave / d_out zero, scratch of a persistent recurrence
-    zero); the hook fills gates entirely and the real frames' 2H columns of d_out, nothing else."""
+    zero); the hook fills gates entirely and the real frames' 2H columns of d_out, nothing else.
+    lengths: per-row frame counts of a ragged batch (ss_op_lstm_fwd_ragged; forward only): out[b, lengths[b]:] comes back as zeros."""
     lib = _capi.lib()
     B, T, In = x.shape
     H = w_hh[0].shape[1]
@@ -692,6 +749,13 @@ def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None, place=None):
         for t in (gates, out, csave, scratch):
             assert t.is_contiguous()
     whf, whb = w_hh[0].contiguous(), w_hh[1].contiguous()
+    if lengths is not None:
+        if d_out is not None:
+            raise ValueError('speechsplit_amd: a ragged BLSTM layer runs the forward only')
+        ln = check_lengths(lengths, B, T, (1,), dev)
+        _capi.check(lib.ss_op_lstm_fwd_ragged(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(out), _ptr(csave), _ptr(scratch), scratch.numel(),
+                                              _ptr(ln), B, T, H, _stream()))
+        return out[:, 2:2 + T, :2 * H].clone()
     _capi.check(lib.ss_op_lstm_fwd(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(out), _ptr(csave), _ptr(scratch), scratch.numel(),
                                    B, T, H, _stream()))
     y = out[:, 2:2 + T, :2 * H].clone()

@@ -130,10 +130,10 @@ def _wanted(ctx, first, names):
 
 class _G3Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mod, x_f0, x_org, c_trg, draws, *params):
+    def forward(ctx, mod, x_f0, x_org, c_trg, draws, lengths, *params):
         ctx.mod = mod
         ctx.in_meta = [(t.shape, t.dtype, t.device) for t in (x_f0, x_org, c_trg)]
-        out = mod._eng.g3_forward(x_f0, x_org, c_trg, draws, training=mod.training)
+        out = mod._eng.g3_forward(x_f0, x_org, c_trg, draws, training=mod.training, lengths=lengths)
         ctx.nparams = len(params)
         return out
 
@@ -146,15 +146,15 @@ class _G3Fn(torch.autograd.Function):
         dx = _input_grads(ctx, gi) if want else (None, None, None)
         flat = mod._eng.grads.clone()                 # fresh storage: autograd may keep or accumulate these
         gv = mod._eng.views(flat)
-        return (None,) + dx + (None,) + tuple(gv[n] for n in mod._names)
+        return (None,) + dx + (None, None) + tuple(gv[n] for n in mod._names)
 
 
 class _G6Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mod, x_org, f0_trg, draws, *params):
+    def forward(ctx, mod, x_org, f0_trg, draws, lengths, *params):
         ctx.mod = mod
         ctx.in_meta = [(t.shape, t.dtype, t.device) for t in (x_org, f0_trg)]
-        return mod._eng.g6_forward(x_org, f0_trg, draws, training=mod.training)
+        return mod._eng.g6_forward(x_org, f0_trg, draws, training=mod.training, lengths=lengths)
 
     @staticmethod
     def backward(ctx, d_out):
@@ -165,7 +165,7 @@ class _G6Fn(torch.autograd.Function):
         dx = _input_grads(ctx, gi) if want else (None, None)
         flat = mod._eng.grads.clone()
         gv = mod._eng.views(flat)
-        return (None,) + dx + (None,) + tuple(gv[n] for n in mod._names)
+        return (None,) + dx + (None, None) + tuple(gv[n] for n in mod._names)
 
 
 class _EngineModule(nn.Module):
@@ -221,6 +221,12 @@ class _EngineModule(nn.Module):
         hp = self.hparams_
         return _engine.draw_interp(B, 3, hp) if self.training else None
 
+    def _eval_lengths(self, lengths):
+        """lengths (a ragged batch) are taken in eval mode only"""
+        if lengths is not None and self.training:
+            raise ValueError('speechsplit_amd: lengths (a ragged batch) are for eval mode only: call .eval() first')
+        return lengths
+
     def extra_repr(self):
         return f'speechsplit_amd HIP engine ({self.KIND}), {sum(p.numel() for p in self._plist)} parameters'
 
@@ -229,30 +235,36 @@ class Generator_3(_EngineModule):
     """SpeechSplit model (reference model.py:283-320)."""
     KIND = 'G3'
 
-    def forward(self, x_f0, x_org, c_trg, draws=None):
+    def forward(self, x_f0, x_org, c_trg, draws=None, lengths=None):
+        """lengths (eval mode only): one frame count per row -- row b comes out as the forward of that utterance alone at lengths[b] frames,
+        zeros behind; no gradient exists for such a forward (a backward through it raises the engine's eval-only error)."""
+        lengths = self._eval_lengths(lengths)
         if not x_org.is_cuda:
             raise RuntimeError('speechsplit_amd.Generator_3 runs on a ROCm GPU only: call .to("cuda") first')
         self._ensure_engine(x_org.device, x_org.shape[0])
         if draws is None:
             draws = self._draw(x_org.shape[0])
-        return _G3Fn.apply(self, x_f0, x_org, c_trg, draws, *self._plist)
+        return _G3Fn.apply(self, x_f0, x_org, c_trg, draws, lengths, *self._plist)
 
-    def rhythm(self, x_org):
+    def rhythm(self, x_org, lengths=None):
+        lengths = self._eval_lengths(lengths)
         self._ensure_engine(x_org.device, x_org.shape[0])
-        return self._eng.g3_rhythm(x_org)
+        return self._eng.g3_rhythm(x_org, lengths=lengths)
 
 
 class Generator_6(_EngineModule):
     """F0 converter (reference model.py:324-351)."""
     KIND = 'G6'
 
-    def forward(self, x_org, f0_trg, draws=None):
+    def forward(self, x_org, f0_trg, draws=None, lengths=None):
+        """lengths (eval mode only): a ragged batch, as Generator_3.forward."""
+        lengths = self._eval_lengths(lengths)
         if not x_org.is_cuda:
             raise RuntimeError('speechsplit_amd.Generator_6 runs on a ROCm GPU only: call .to("cuda") first')
         self._ensure_engine(x_org.device, x_org.shape[0])
         if draws is None:
             draws = self._draw(x_org.shape[0])
-        return _G6Fn.apply(self, x_org, f0_trg, draws, *self._plist)
+        return _G6Fn.apply(self, x_org, f0_trg, draws, lengths, *self._plist)
 
 
 class _InterpFn(torch.autograd.Function):
