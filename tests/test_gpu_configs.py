@@ -125,7 +125,9 @@ def check_fp32_step(r, tag):
 
 def check_adam(r, tag, step):
     """(a) the engine's update == torch.optim.Adam's single-tensor formulas on the engine's own gradients (first step only:
-    moments start at zero); (b) against the oracle's weights: hard bound 2.1 * lr, at most 2e-5 of a tensor's elements (or 2) beyond 1e-4 * max|p|."""
+    moments start at zero); (b) against the oracle's weights: hard bound 2.1 * lr, at most 2e-5 of a tensor's elements (or 2) beyond 1e-4 * max|p|.
+    The update itself -- every element, the moments, later steps, other hyper-parameters, every route to the optimiser -- is held to a few ulps
+    of a float64 evaluation in test_gpu_optimizer.py."""
     tot, off = 0, 0
     for n, pc in r['p_cpu'].items():
         pa, pb, g = r['p_after'][n].double(), r['p_before'][n].double(), r['grads_gpu'][n].double()
