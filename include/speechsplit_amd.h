@@ -49,6 +49,10 @@ typedef struct ss_hparams {
                                     GEMMs (they run on an engine stream beside the encoder backward, as in the one-call
                                     step); the consumer of the decoder range orders itself with ss_wait_decoder_grads() */
 
+#define SS_STEP_ACCUMULATE 8 /* ss_*_train_step and the data-parallel steps: this step's backward ADDS its parameter gradients to what the
+                                gradient arena holds instead of starting from zeros; nothing else about the step changes (see "gradient
+                                accumulation" below ss_zero_grads).  Composes with every other flag. */
+
 #define SS_STEP_BUCKET 16 /* ss_*_train_step: T is the length bucket of THIS batch and the step runs with max_len_pad = T (what the
                              reference does when its hparams.max_len_pad is set to the bucket length: InterpLnr pads to it, the
                              encoders' len_org equals it, model.py:105,157,370).  T % 8 == 0, T <= max_frames.  A
@@ -184,7 +188,7 @@ int ss_allreduce_grads(ss_engine* e, long offset, long count, void* stream);
  * own while the backward is still running -- each decoder layer (25 / 25 / 11 MB for Generator_3) as soon as its weight-gradient
  * GEMMs have retired (layer 2 first; they run beside the encoder backward), the head, the two wide layers of the conv trunk as the
  * trunk's backward passes them, and last the few MB that are final only at the end (layer-0 convolutions, encoder BLSTMs, Encoder_t,
- * the status slot); then Adam with the 1/world mean folded in.  flags: 0 or SS_STEP_BUCKET (every rank passes the same T).  loss: this
+ * the status slot); then Adam with the 1/world mean folded in.  flags: 0, SS_STEP_BUCKET (every rank passes the same T) and / or SS_STEP_ACCUMULATE.  loss: this
  * rank's local mean loss.  ss_g6_dp_train_step: the same for Generator_6 (cross-entropy step of ss_g6_train_step).
  * ss_tune("dp_model", R) MODELS an R-rank run on one GPU without a communicator: every collective is replaced by a stand-in kernel of
  * the modelled duration (ring all-reduce over one 153 GB/s xGMI link + 25 us), so a kernel trace shows where each bucket would sit
@@ -209,6 +213,32 @@ int ss_dp_profile_read(ss_engine* e, double* out, int cap);
 int ss_set_adam(ss_engine* e, double lr, double beta1, double beta2, double eps, long step, void* stream);
 int ss_adam_step(ss_engine* e, float grad_scale, void* stream);
 int ss_zero_grads(ss_engine* e, void* stream);
+
+/* ---- gradient accumulation over micro-batches (nothing to mirror: the reference steps once per batch, solver.py:170-172; the semantics are
+ *      those of calling loss.backward() k times between optimizer.zero_grad() and optimizer.step()) ----
+ * SS_STEP_ACCUMULATE on ss_g3_train_step / ss_g6_train_step / ss_g3_dp_train_step / ss_g6_dp_train_step: the step's backward adds its
+ *   parameter gradients to the arena.  A step WITHOUT the flag clears the arena as ever and so starts a new cycle.  In a
+ *   SS_STEP_SPLIT_BACKWARD step the choice is made for the whole backward: the engine remembers it for the ss_train_finish that follows,
+ *   which takes no accumulate flag of its own.  Without the flag every entry point enqueues exactly what it did before the flag existed.
+ *   The arena then holds the plain SUM of the micro-batches' gradients, each the gradient of that micro-batch's own MEAN loss (no 1 / k
+ *   inside).  As everywhere, grad_scale acts only inside the optimiser step and the norm: the caller of ss_*_train_step, ss_adam_step or
+ *   ss_train_finish passes 1 / k (times 1 / world where it all-reduces itself).  The native data-parallel steps fold their mean in
+ *   themselves: 1 / (world * ss_grad_accum_count).
+ *   A cycle of k micro-batches on one GPU:   step(NO_ADAM);   step(NO_ADAM | ACCUMULATE) k - 2 times;   step(ACCUMULATE, grad_scale = 1 / k)
+ *   -- or ss_zero_grads and then k accumulating steps.  Native data parallel: the first k - 1 micro-batches through the plain
+ *   ss_g*_train_step(NO_ADAM [| ACCUMULATE]) (no collective is enqueued by them, communicator or not), the last through
+ *   ss_g*_dp_train_step(ACCUMULATE), whose buckets all-reduce the local sums, each behind that micro-batch's last producer for its range.
+ *   The micro-batches of one cycle may differ in B, in T (SS_STEP_BUCKET) and in route (fused, split, data-parallel): nothing is carried
+ *   in the workspace between them, which a change of shape re-plans.  Each counts 1 / k through grad_scale whatever its size -- the mean of
+ *   the micro-batches' means, which is the mean over the utterances only when they are equally large.  A cycle runs in ONE precision mode
+ *   (ss_set_precision between cycles, not inside one).  Accumulating onto an arena the caller filled adds to it: the rule ss_op_gemm states
+ *   for its C.  The status slot (the arena's last four floats) is overwritten by every backward, never added to.
+ *   loss_dev stays the loss of the micro-batch of that call.  The clipping norm, its coefficient, the non-finite skip and the counters of
+ *   ss_grad_clip_stats belong to the cycle's ONE optimiser step and act on the accumulated (and all-reduced) arena: one non-finite
+ *   micro-batch skips the cycle's update once and counts once.
+ * ss_grad_accum_count: backward passes summed into the arena since it was last cleared (host-side; no synchronisation): 0 after ss_bind and
+ *   ss_zero_grads, 1 after a step or an ss_*_backward* without the flag, k after k - 1 further accumulating steps; 0 for a null engine. */
+long ss_grad_accum_count(const ss_engine* e);
 
 /* ---- clipping by global norm, and refusing non-finite gradients (nothing to mirror: the reference's solver never clips; the semantics are
  *      those of torch.nn.utils.clip_grad_norm_(G.parameters(), max_norm), norm_type 2, placed between backward and optimizer.step()) ----

@@ -62,6 +62,7 @@ SYMBOLS = {
     'ss_set_adam': (_i, [_vp, _d, _d, _d, _d, _l, _vp]),
     'ss_adam_step': (_i, [_vp, _f, _vp]),
     'ss_zero_grads': (_i, [_vp, _vp]),
+    'ss_grad_accum_count': (_l, [_vp]),
     'ss_set_grad_clip': (_i, [_vp, _f, _vp]),
     'ss_grad_norm': (_i, [_vp, _f, _fp, _vp]),
     'ss_grad_clip_stats': (_i, [_vp, _fp, _vp]),

@@ -677,6 +677,17 @@ __global__ __launch_bounds__(256) void conv_unpack_grad_kernel(const float* __re
         g[i] = gp[((long)co * 5 + k) * Cp + ci];
     }
 }
+// accumulating form (SS_STEP_ACCUMULATE): g += this step's packed gradient.  A kernel of its own, so the plain step keeps its instruction stream
+__global__ __launch_bounds__(256) void conv_unpack_grad_acc_kernel(const float* __restrict__ gp, int Co, int Ci, int Cp,
+                                                                   float* __restrict__ g) {
+    const long n = (long)Co * Ci * 5;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int k = (int)(i % 5);
+        const int ci = (int)((i / 5) % Ci);
+        const int co = (int)(i / (5L * Ci));
+        g[i] += gp[((long)co * 5 + k) * Cp + ci];
+    }
+}
 
 // the same for several blocks in one launch (blockIdx.y = block): the one-GPU step unpacks every conv weight gradient at the end of the backward
 __global__ __launch_bounds__(256) void conv_unpack_grads_kernel(ConvUnpackTable tb) {
@@ -687,6 +698,16 @@ __global__ __launch_bounds__(256) void conv_unpack_grads_kernel(ConvUnpackTable 
         const int ci = (int)((i / 5) % t.Ci);
         const int co = (int)(i / (5L * t.Ci));
         t.g[i] = t.gp[((long)co * 5 + k) * t.Cp + ci];
+    }
+}
+__global__ __launch_bounds__(256) void conv_unpack_grads_acc_kernel(ConvUnpackTable tb) {
+    const ConvUnpackTask t = tb.t[blockIdx.y];
+    const long n = (long)t.Co * t.Ci * 5;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int k = (int)(i % 5);
+        const int ci = (int)((i / 5) % t.Ci);
+        const int co = (int)(i / (5L * t.Ci));
+        t.g[i] += t.gp[((long)co * 5 + k) * t.Cp + ci];
     }
 }
 
@@ -1153,10 +1174,11 @@ hipError_t conv_pack(const float* w, int Co, int Ci, int Cp, float* wf, float* w
     return hipGetLastError();
 }
 
-hipError_t conv_unpack_grad(const float* gp, int Co, int Ci, int Cp, float* g, hipStream_t s) {
+hipError_t conv_unpack_grad(const float* gp, int Co, int Ci, int Cp, float* g, hipStream_t s, bool acc) {
     int gr = cdiv((long)Co * Ci * 5, 256);
     if (gr > 2048) gr = 2048;
-    hipLaunchKernelGGL(conv_unpack_grad_kernel, dim3(gr), dim3(256), 0, s, gp, Co, Ci, Cp, g);
+    if (acc) hipLaunchKernelGGL(conv_unpack_grad_acc_kernel, dim3(gr), dim3(256), 0, s, gp, Co, Ci, Cp, g);
+    else hipLaunchKernelGGL(conv_unpack_grad_kernel, dim3(gr), dim3(256), 0, s, gp, Co, Ci, Cp, g);
     return hipGetLastError();
 }
 
@@ -1167,10 +1189,11 @@ hipError_t conv_pack_many(const ConvPackTable& tb, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t conv_unpack_grads(const ConvUnpackTable& tb, hipStream_t s) {
+hipError_t conv_unpack_grads(const ConvUnpackTable& tb, hipStream_t s, bool acc) {
     if (tb.n <= 0) return hipSuccess;
     if (tb.n > CONV_UNPACK_MAX) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(conv_unpack_grads_kernel, dim3(512, tb.n), dim3(256), 0, s, tb);
+    if (acc) hipLaunchKernelGGL(conv_unpack_grads_acc_kernel, dim3(512, tb.n), dim3(256), 0, s, tb);
+    else hipLaunchKernelGGL(conv_unpack_grads_kernel, dim3(512, tb.n), dim3(256), 0, s, tb);
     return hipGetLastError();
 }
 

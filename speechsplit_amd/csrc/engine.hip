@@ -190,6 +190,9 @@ struct Backward {
         float* p = nullptr;
         long ld = 0;
     } in_grad[3];
+    // SS_STEP_ACCUMULATE: this backward ADDS its parameter gradients to what the arena holds -- no arena memset, the conv weight gradients
+    // unpacked with += (every other producer adds already)
+    bool accumulate = false;
     const InputGrad* input_grad_of(const ConvBlk& cb) const {
         for (const InputGrad& t : in_grad)
             if (t.cb == &cb && t.p) return &t;
@@ -213,6 +216,7 @@ struct Backward {
 struct FusedForward {
     const float *late_org = nullptr, *late_emb = nullptr;   // x_org / emb still to be copied in (done on the Encoder_t branch)
     bool prezero = false;                  // zero the gradient arena (and the backward recurrences' start state) on a branch stream meanwhile
+    bool keep_grads = false;               // ... except the arena itself (SS_STEP_ACCUMULATE): the per-backward state is still readied there
 };
 
 // how one lstm_weight_grads call differs from the plain one
@@ -259,6 +263,9 @@ struct ss_engine {
                                            // kernels, read by the host without synchronising; cleared only by ss_clear_abort
 
     float *P = nullptr, *G = nullptr, *Mm = nullptr, *Vv = nullptr;
+    long accum_count = 0;                  // backward passes summed into G since it was last cleared (ss_grad_accum_count; host-side)
+    bool bwd_accumulate = false;           // the backward in flight adds to the arena: chosen where it starts (backward_decoder), read by
+                                           // ss_train_finish for the second half of a SS_STEP_SPLIT_BACKWARD step
     char* ws = nullptr;
     long ws_bytes = 0;
     int curB = 0, curT = 0;
@@ -1244,7 +1251,7 @@ int conv_block_bwd(ss_engine* e, Backward& bw, ConvBlk& cb, Slab dy, Slab x, Sla
     // one-GPU step collects the blocks and unpacks them all in one launch at the end of the backward (backward_encoder) instead of seven
     // small launches on the trunk's dependent chain
     if (bw.unpack_later && bw.unpack.n < CONV_UNPACK_MAX) bw.unpack.t[bw.unpack.n++] = {cb.gp, e->G + cb.w, cb.Co, cb.Ci, cb.Cp};
-    else HIPCHK(conv_unpack_grad(cb.gp, cb.Co, cb.Ci, cb.Cp, e->G + cb.w, dws));
+    else HIPCHK(conv_unpack_grad(cb.gp, cb.Co, cb.Ci, cb.Cp, e->G + cb.w, dws, bw.accumulate));
     if (dx.p) {
         GemmDesc g{};
         g.A = {dy.p, dy.ld, TP * dy.ld, cb.Co, dy.ld};
@@ -1903,8 +1910,8 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
         CHK(lstm_prep(e, e->ld, tb, b2));
         HIPCHK(prep_run(tb, b2));
         if (fused.prezero) {     // nothing touches the gradient arena before the decoder backward; b2 is joined long before
-            HIPCHK(hipMemsetAsync(e->G, 0, e->arena * 4, b2));
-            HIPCHK(hipMemsetAsync(e->amax, 0, 16 * 4, b2));
+            if (!fused.keep_grads) HIPCHK(hipMemsetAsync(e->G, 0, e->arena * 4, b2));
+            HIPCHK(hipMemsetAsync(e->amax, 0, 16 * 4, b2));      // (the gradient slabs' maxima are per backward, accumulating or not)
             e->fwd.grads_zeroed = true;
             // the backward recurrences' group words and exchange tiles (nothing in the forward touches them): zeroed here, the backward
             // needs no fork / memset / join between the head's gradient and its first recurrence (two event hops on the critical path)
@@ -2062,10 +2069,12 @@ int backward_decoder(ss_engine* e, Backward& bw, hipStream_t s, bool late = fals
     const int B = e->curB, T = e->curT;
     const long TP = T + 2 * HALO, R = (long)B * TP;
     if (!e->fwd.grads_zeroed) {
-        HIPCHK(hipMemsetAsync(e->G, 0, e->arena * 4, s));
+        if (!bw.accumulate) HIPCHK(hipMemsetAsync(e->G, 0, e->arena * 4, s));
         HIPCHK(hipMemsetAsync(e->amax, 0, 16 * 4, s));
     }
     e->fwd.grads_zeroed = false;
+    e->bwd_accumulate = bw.accumulate;
+    e->accum_count = bw.accumulate ? e->accum_count + 1 : 1;
     // fragment-major W_hh^T of the decoder recurrences (overwrites the forward layout, no longer needed), beside the head
     const bool persist_dec = e->ld.big() && g_persist && lstm_seq_supported(e->curB, e->ld.H);
     const bool prezeroed = e->fwd.bwd_sync_zeroed && persist_dec;       // the fused step's forward has done it on its branch stream
@@ -2318,7 +2327,7 @@ int backward_encoder(ss_engine* e, Backward& bw, hipStream_t s) {
     if (par) CHK(fork_join(e, b3, s));
     if (dw_off) CHK(fork_join(e, dw_s, s));
     CHK(join_side(e, s));
-    if (bw.unpack.n) HIPCHK(conv_unpack_grads(bw.unpack, s));
+    if (bw.unpack.n) HIPCHK(conv_unpack_grads(bw.unpack, s, bw.accumulate));
     return 0;
 }
 
@@ -2520,6 +2529,8 @@ int ss_bind(ss_engine* e, float* params, float* grads, float* m, float* v, void*
     if (ws_bytes < need) return fail("ss_bind: workspace smaller than ss_workspace_bytes()");
     e->P = params;
     e->G = grads;
+    e->accum_count = 0;
+    e->bwd_accumulate = false;
     e->Mm = m;
     e->Vv = v;
     e->ws = (char*)workspace;
@@ -2666,8 +2677,11 @@ int ss_zero_grads(ss_engine* e, void* stream) {
     if (!e->G) return fail("engine is not bound");
     Own own(e, stream);
     HIPCHK(hipMemsetAsync(e->G, 0, e->arena * 4, own.s));
+    e->accum_count = 0;
     return 0;
 }
+
+long ss_grad_accum_count(const ss_engine* e) { return e ? e->accum_count : 0; }
 
 // every backward: a forward to differentiate, and one that ran within max_frames (nothing is enqueued otherwise)
 static int backward_check(const ss_engine* e) {
@@ -2844,11 +2858,13 @@ static int g3_step_body(ss_engine* e, const float* mel, const float* f0, const f
     HIPCHK(interp_quant(e->plan[0], mel, f0, h.dim_freq, e->in_mel + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq,
                         e->in_f0 + HALO * e->f0p, e->f0p, TP * e->f0p, h.dim_f0, e->qidx, B, s));
     // x_org and the speaker embedding are first read by Encoder_t / the decoder input: their copies ride on the branch stream
-    CHK(forward_core(e, true, scales, len_seg, 1, s, FusedForward{mel, emb, true}));        // solver.py:165
+    const bool accumulate = (flags & SS_STEP_ACCUMULATE) != 0;
+    CHK(forward_core(e, true, scales, len_seg, 1, s, FusedForward{mel, emb, true, accumulate}));        // solver.py:165
     const int C = e->head_out;
     HIPCHK(mse_loss(e->out_slab + HALO * C, C, TP * C, e->org + HALO * C, C, TP * C, e->d_out_slab + HALO * C, C, TP * C, B, T,
                     C, 1.0f, e->loss_part, loss, s));                                       // solver.py:166
     Backward bw;
+    bw.accumulate = accumulate;
     if (flags & SS_STEP_SPLIT_BACKWARD) {         // data parallel: stop once the decoder + head gradients are complete
         CHK(backward_decoder(e, bw, s));          // (not late: nothing of it is left pending for ss_train_finish's backward_encoder)
         if (!(flags & SS_STEP_SPLIT_NO_JOIN)) return join_side(e, s);
@@ -2907,6 +2923,7 @@ int ss_train_finish(ss_engine* e, float grad_scale, int flags, void* stream) {
     if (!e->fwd.have) return fail("ss_train_finish without a preceding ss_*_train_step(SS_STEP_SPLIT_BACKWARD)");
     CHK(backward_check(e));
     Backward bw;               // a backward of its own: the decoder half (an earlier call) left nothing pending, and nothing goes out early
+    bw.accumulate = e->bwd_accumulate;      // ... but the step's choice between adding to the arena and overwriting it holds for both halves
     CHK(backward_encoder(e, bw, s));
     if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_enqueue(e, bw, grad_scale, s));
     return 0;
@@ -2942,6 +2959,7 @@ int ss_g6_train_step(ss_engine* e, const float* mel, const float* f0_onehot, con
     HIPCHK(ce_loss(e->out_slab + HALO * C, C, TP * C, target_idx, e->d_out_slab + HALO * C, C, TP * C, B, T, C, 1.0f,
                    e->loss_part, loss, s));
     Backward bw;
+    bw.accumulate = (flags & SS_STEP_ACCUMULATE) != 0;
     bw.adam_early = !(flags & SS_STEP_NO_ADAM);
     bw.adam_gs = grad_scale;
     CHK(backward_core(e, bw, s));
@@ -3692,7 +3710,9 @@ int ss_allreduce_grads(ss_engine* e, long offset, long count, void* stream) {
 // its four weight-gradient GEMMs retire, the head, the two wide trunk layers, the rest), Adam with the 1 / world mean folded in
 static int dp_step(ss_engine* e, hipStream_t s, const std::function<int(hipStream_t)>& body) {
     const int world = (g_dp_model > 1 && (!e->comm || e->comm_world == 1)) ? g_dp_model : e->comm_world;
-    const float gs = 1.0f / (float)world;
+    // the mean over the ranks and over the micro-batches each of them summed into its arena (SS_STEP_ACCUMULATE; 1 without): the count
+    // includes the backward `body` is about to enqueue, so it is read behind it
+    auto mean_scale = [&]() { return 1.0f / (float)((long)world * (e->accum_count > 0 ? e->accum_count : 1)); };
     CHK(dp_streams(e));
     if (!e->side || !e->side2 || !g_overlap || !g_dp_buckets) {        // no branch streams (or round 2's plan asked for): the plain step, then the arena
         CHK(body(s));
@@ -3702,7 +3722,7 @@ static int dp_step(ss_engine* e, hipStream_t s, const std::function<int(hipStrea
             CHK(allreduce_range(e, k, e->arena - k, s));
             CHK(allreduce_range(e, 0, k, s));
         }
-        return adam_enqueue(e, Backward{}, gs, s);
+        return adam_enqueue(e, Backward{}, mean_scale(), s);
     }
     e->dp_done.clear();
     e->dp_rec.clear();              // ss_dp_profile keeps the LAST step's record
@@ -3712,7 +3732,7 @@ static int dp_step(ss_engine* e, hipStream_t s, const std::function<int(hipStrea
     e->dp_on = false;
     CHK(rc);
     CHK(dp_finish(e, s));
-    return adam_enqueue(e, Backward{}, gs, s);              // the whole arena; the mean is folded into the Adam kernel
+    return adam_enqueue(e, Backward{}, mean_scale(), s);    // the whole arena; the mean is folded into the Adam kernel
 }
 
 int ss_g3_dp_train_step(ss_engine* e, const float* mel, const float* f0, const float* emb, const int* len_org, const float* scales,
@@ -3725,7 +3745,7 @@ int ss_g3_dp_train_step(ss_engine* e, const float* mel, const float* f0, const f
     Own own(e, stream);
     hipStream_t s = own.s;
     CHK(geometry(e, B, T, s));
-    return dp_step(e, s, [&](hipStream_t st) { return g3_step_body(e, mel, f0, emb, len_org, scales, len_seg, B, T, 1.0f, SS_STEP_NO_ADAM, loss, st); });
+    return dp_step(e, s, [&](hipStream_t st) { return g3_step_body(e, mel, f0, emb, len_org, scales, len_seg, B, T, 1.0f, SS_STEP_NO_ADAM | (flags & SS_STEP_ACCUMULATE), loss, st); });
 }
 
 long ss_scratch_fallbacks(const ss_engine* e) { return e ? e->scratch_fallbacks : -1; }
@@ -3766,7 +3786,7 @@ int ss_g6_dp_train_step(ss_engine* e, const float* mel, const float* f0_onehot, 
     Own own(e, stream);
     hipStream_t s = own.s;
     return dp_step(e, s, [&](hipStream_t st) {
-        return ss_g6_train_step(e, mel, f0_onehot, target_idx, scales, len_seg, B, T, 1.0f, (flags & SS_STEP_BUCKET) | SS_STEP_NO_ADAM, loss, (void*)st);
+        return ss_g6_train_step(e, mel, f0_onehot, target_idx, scales, len_seg, B, T, 1.0f, (flags & (SS_STEP_BUCKET | SS_STEP_ACCUMULATE)) | SS_STEP_NO_ADAM, loss, (void*)st);
     });
 }
 

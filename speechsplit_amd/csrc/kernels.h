@@ -93,7 +93,8 @@ struct ConvPackTable {
     int img_bf16;
 };
 hipError_t conv_pack_many(const ConvPackTable& tb, hipStream_t s);
-hipError_t conv_unpack_grad(const float* gp, int Co, int Ci, int Cp, float* g, hipStream_t s);
+// acc: g += the unpacked gradient instead of g = (a step that accumulates onto the arena, SS_STEP_ACCUMULATE); a kernel of its own per form
+hipError_t conv_unpack_grad(const float* gp, int Co, int Ci, int Cp, float* g, hipStream_t s, bool acc = false);
 constexpr int CONV_UNPACK_MAX = 8;
 struct ConvUnpackTask {
     const float* gp;      // packed gradient [Co][5][Cp]
@@ -104,7 +105,7 @@ struct ConvUnpackTable {
     ConvUnpackTask t[CONV_UNPACK_MAX];
     int n;
 };
-hipError_t conv_unpack_grads(const ConvUnpackTable& tb, hipStream_t s);      // several blocks, one launch
+hipError_t conv_unpack_grads(const ConvUnpackTable& tb, hipStream_t s, bool acc = false);      // several blocks, one launch
 hipError_t transpose2d(const float* in, int R, int C, float* out, hipStream_t s);   // out[c][r] = in[r][c]
 // out[i] = a[i] + b[i]
 hipError_t add_vec(const float* a, const float* b, float* out, int n, hipStream_t s);

@@ -247,16 +247,20 @@ class Engine:
         _capi.check(self.lib.ss_g3_rhythm(self.h, _ptr(x_org), B, T, _ptr(codes), _stream()))
         return codes
 
-    def g3_train_step(self, mel, f0, emb, len_org, draws, grad_scale=1.0, no_adam=False, split_backward=False, bucket=False):
+    def g3_train_step(self, mel, f0, emb, len_org, draws, grad_scale=1.0, no_adam=False, split_backward=False, bucket=False,
+                      accumulate=False, split_no_join=False):
         """solver.py:160-172 fused.  split_backward: return after the decoder + head gradients (arena offsets >=
-        self.grad_split) are complete; train_finish() then runs the encoder backward (data-parallel overlap).
-        bucket: the batch's frame count is its length bucket and the step runs with max_len_pad = T (SS_STEP_BUCKET)."""
+        self.grad_split) are complete; train_finish() then runs the encoder backward (data-parallel overlap); split_no_join: without
+        joining the engine stream that carries the decoder's weight gradients (SS_STEP_SPLIT_NO_JOIN).
+        bucket: the batch's frame count is its length bucket and the step runs with max_len_pad = T (SS_STEP_BUCKET).
+        accumulate: the backward ADDS to the gradient arena (SS_STEP_ACCUMULATE).  A cycle of k micro-batches: no_adam=True, then
+        no_adam=True + accumulate=True k - 2 times, then accumulate=True with grad_scale = 1 / k."""
         B, T, _ = mel.shape
         self._fwd_bt = None
         mel, f0, emb, len_org = self._f(mel), self._f(f0), self._f(emb), self._i(len_org)
         sc, ls = self._draws(draws)
         assert sc.shape[0] == 4 and ls.shape[0] == 4
-        flags = (1 if no_adam else 0) | (2 if split_backward else 0) | (16 if bucket else 0)
+        flags = (1 if no_adam else 0) | (2 if split_backward else 0) | (4 if split_no_join else 0) | (8 if accumulate else 0) | (16 if bucket else 0)
         _capi.check(self.lib.ss_g3_train_step(self.h, _ptr(mel), _ptr(f0), _ptr(emb), _ptr(len_org), _ptr(sc), _ptr(ls),
                                               B, T, float(grad_scale), flags, _ptr(self.loss), _stream()))
         return self.loss
@@ -268,7 +272,7 @@ class Engine:
     def grad_split(self):
         return int(self.lib.ss_grad_split(self.h))
 
-    def dp_train_step(self, mel, f0, emb, len_org, draws, world, group=None, schedule='overlap', bucket=False):
+    def dp_train_step(self, mel, f0, emb, len_org, draws, world, group=None, schedule='overlap', bucket=False, accumulate=False):
         """One data-parallel Generator_3 step on this rank's shard: backward, sum of the gradient arena over the ranks in the
         two buckets of dist.bucket_plan (decoder + head + status slot first, then the encoder), the same Adam update on every
         rank with the 1/world mean folded in.  Collectives: torch.distributed (backend 'nccl' = RCCL); the native path without
@@ -282,7 +286,11 @@ class Engine:
             was developed on elide the collective.
         schedule='after': the one-GPU step unchanged, then the buckets; nothing hidden.
         schedule='join': SS_STEP_SPLIT_BACKWARD joins the engine streams, first bucket reduced right away (+0.6 ms at world 1:
-            the decoder's weight-gradient GEMMs then run alone instead of beside the encoder backward)."""
+            the decoder's weight-gradient GEMMs then run alone instead of beside the encoder backward).
+
+        accumulate: this call is the LAST micro-batch of an accumulation cycle whose earlier ones went through
+        g3_train_step(no_adam=True[, accumulate=True]) without any collective: its backward adds to the arena, the buckets reduce the
+        local sums and Adam steps with 1 / (world * grad_accum_count)."""
         from . import dist as D
         self._fwd_bt = None
         k = self.grad_split
@@ -291,10 +299,10 @@ class Engine:
         if schedule == 'overlap' and not side:
             schedule = 'after'                         # engine without branch streams
         if schedule == 'after':
-            self.g3_train_step(mel, f0, emb, len_org, draws, no_adam=True, bucket=bucket)
+            self.g3_train_step(mel, f0, emb, len_org, draws, no_adam=True, bucket=bucket, accumulate=accumulate)
             handles = [D.reduce_bucket(self.grads, lo, hi, group) for lo, hi in plan]
         elif schedule == 'join':
-            self.g3_train_step(mel, f0, emb, len_org, draws, no_adam=True, split_backward=True, bucket=bucket)
+            self.g3_train_step(mel, f0, emb, len_org, draws, no_adam=True, split_backward=True, bucket=bucket, accumulate=accumulate)
             handles = [D.reduce_bucket(self.grads, *plan[0], group)]
             self.train_finish(no_adam=True)
             handles.append(D.reduce_bucket(self.grads, *plan[1], group))
@@ -304,7 +312,7 @@ class Engine:
             mel, f0, emb, len_org = self._f(mel), self._f(f0), self._f(emb), self._i(len_org)
             # SS_STEP_NO_ADAM | SS_STEP_SPLIT_BACKWARD | SS_STEP_SPLIT_NO_JOIN
             _capi.check(self.lib.ss_g3_train_step(self.h, _ptr(mel), _ptr(f0), _ptr(emb), _ptr(len_org), _ptr(sc), _ptr(ls),
-                                                  B, T, 1.0, 1 | 2 | 4 | (16 if bucket else 0), _ptr(self.loss), _stream()))
+                                                  B, T, 1.0, 1 | 2 | 4 | (8 if accumulate else 0) | (16 if bucket else 0), _ptr(self.loss), _stream()))
             if getattr(self, '_side_stream', None) is None:
                 self._side_stream = torch.cuda.ExternalStream(side, device=self.device)
             cs = self._side_stream
@@ -320,15 +328,16 @@ class Engine:
         for h in handles:
             if h is not None:
                 h.wait()                               # the current stream waits for the collectives
-        self.adam_step(1.0 / world)
+        self.adam_step(1.0 / (world * max(self.grad_accum_count, 1)))
         return self.loss
 
-    def dp_g6_train_step(self, mel, f0_onehot, target_idx, draws, world, group=None, bucket=False):
-        """Data-parallel Generator_6 step (BASELINE config 4): the arena is 14 MB, one pass of the bucket plan behind the backward."""
+    def dp_g6_train_step(self, mel, f0_onehot, target_idx, draws, world, group=None, bucket=False, accumulate=False):
+        """Data-parallel Generator_6 step (BASELINE config 4): the arena is 14 MB, one pass of the bucket plan behind the backward.
+        accumulate: the last micro-batch of an accumulation cycle, as in dp_train_step."""
         from . import dist as D
-        self.g6_train_step(mel, f0_onehot, target_idx, draws, no_adam=True, bucket=bucket)
+        self.g6_train_step(mel, f0_onehot, target_idx, draws, no_adam=True, bucket=bucket, accumulate=accumulate)
         D.reduce_arena(self.grads, self.grad_split, group)
-        self.adam_step(1.0 / world)
+        self.adam_step(1.0 / (world * max(self.grad_accum_count, 1)))
         return self.loss
 
     # ---- native RCCL (no PyTorch in the data path): ss_comm_* / ss_g3_dp_train_step of the C ABI
@@ -370,15 +379,16 @@ class Engine:
         hi = self.grads.numel() if hi is None else hi
         _capi.check(self.lib.ss_allreduce_grads(self.h, int(lo), int(hi - lo), _stream()))
 
-    def dp_train_step_native(self, mel, f0, emb, len_org, draws, bucket=False):
+    def dp_train_step_native(self, mel, f0, emb, len_org, draws, bucket=False, accumulate=False):
         """ss_g3_dp_train_step: the overlapped two-bucket schedule with the collectives launched by the engine itself, the
-        decoder bucket ON the engine stream that carries the decoder's weight-gradient GEMMs."""
+        decoder bucket ON the engine stream that carries the decoder's weight-gradient GEMMs.  accumulate: the last micro-batch of an
+        accumulation cycle (SS_STEP_ACCUMULATE): the buckets reduce the local sums, Adam steps with 1 / (world * grad_accum_count)."""
         self._fwd_bt = None
         B, T, _ = mel.shape
         mel, f0, emb, len_org = self._f(mel), self._f(f0), self._f(emb), self._i(len_org)
         sc, ls = self._draws(draws)
         _capi.check(self.lib.ss_g3_dp_train_step(self.h, _ptr(mel), _ptr(f0), _ptr(emb), _ptr(len_org), _ptr(sc), _ptr(ls), B, T,
-                                                 16 if bucket else 0, _ptr(self.loss), _stream()))
+                                                 (16 if bucket else 0) | (8 if accumulate else 0), _ptr(self.loss), _stream()))
         return self.loss
 
     # ------------------------------------------------------------------ Generator_6
@@ -410,16 +420,18 @@ class Engine:
         _capi.check(self.lib.ss_g6_backward_inputs(self.h, _ptr(d_out), _ptr(dx_org), _ptr(df0_trg), _stream()))
         return dx_org, df0_trg
 
-    def g6_train_step(self, mel, f0_onehot, target_idx, draws, grad_scale=1.0, no_adam=False, bucket=False):
+    def g6_train_step(self, mel, f0_onehot, target_idx, draws, grad_scale=1.0, no_adam=False, bucket=False, accumulate=False):
+        """accumulate: the backward adds to the gradient arena (SS_STEP_ACCUMULATE), as in g3_train_step."""
         self._fwd_bt = None
         B, T, _ = mel.shape
         mel, f0_onehot, target_idx = self._f(mel), self._f(f0_onehot), self._i(target_idx)
         sc, ls = self._draws(draws)
         _capi.check(self.lib.ss_g6_train_step(self.h, _ptr(mel), _ptr(f0_onehot), _ptr(target_idx), _ptr(sc), _ptr(ls), B, T,
-                                              float(grad_scale), (1 if no_adam else 0) | (16 if bucket else 0), _ptr(self.loss), _stream()))
+                                              float(grad_scale), (1 if no_adam else 0) | (8 if accumulate else 0) | (16 if bucket else 0), _ptr(self.loss),
+                                              _stream()))
         return self.loss
 
-    def g6_dp_train_step_native(self, mel, f0_onehot, target_idx, draws, bucket=False):
+    def g6_dp_train_step_native(self, mel, f0_onehot, target_idx, draws, bucket=False, accumulate=False):
         """ss_g6_dp_train_step: Generator_6's data-parallel step with the engine's own RCCL communicator (per-layer buckets on the
         engine's communication stream), as dp_train_step_native for Generator_3."""
         self._fwd_bt = None
@@ -427,7 +439,7 @@ class Engine:
         mel, f0_onehot, target_idx = self._f(mel), self._f(f0_onehot), self._i(target_idx)
         sc, ls = self._draws(draws)
         _capi.check(self.lib.ss_g6_dp_train_step(self.h, _ptr(mel), _ptr(f0_onehot), _ptr(target_idx), _ptr(sc), _ptr(ls), B, T,
-                                                 16 if bucket else 0, _ptr(self.loss), _stream()))
+                                                 (16 if bucket else 0) | (8 if accumulate else 0), _ptr(self.loss), _stream()))
         return self.loss
 
     # ------------------------------------------------------------------ optimiser / misc
@@ -471,6 +483,11 @@ class Engine:
 
     def zero_grads(self):
         _capi.check(self.lib.ss_zero_grads(self.h, _stream()))
+
+    @property
+    def grad_accum_count(self):
+        """Backward passes summed into the gradient arena since it was last cleared (ss_grad_accum_count; host-side)."""
+        return int(self.lib.ss_grad_accum_count(self.h))
 
     def interp_forward(self, x, len_seq, scales, len_seg, want_plan=False, out=None):
         """out: optional pre-placed dense outputs (y, i0, lam, counts) instead of fresh ones (i0 / lam / counts may be None)."""

@@ -51,6 +51,13 @@ class Solver(object):
         self.grad_clip = float(clip) if clip is not None else 0.0
         if not self.grad_clip >= 0.0:
             raise ValueError('grad_clip must be 0 / None (off), positive or inf, got {!r}'.format(clip))
+        # gradient accumulation: one optimiser step over accum_steps loader batches (SS_STEP_ACCUMULATE): config.accum_steps, or -- for the
+        # unchanged main.py -- SS_ACCUM_STEPS.  1 (default): the train loop's calls exactly as without it.  num_iters, the checkpoints and the
+        # optimiser state count optimiser steps.
+        accum = getattr(config, 'accum_steps', None) if hasattr(config, 'accum_steps') else (os.environ.get('SS_ACCUM_STEPS') or None)
+        self.accum_steps = int(accum) if accum is not None else 1
+        if self.accum_steps < 1:
+            raise ValueError('accum_steps must be a positive integer, got {!r}'.format(accum))
         self.use_cuda = torch.cuda.is_available()
         if not self.use_cuda:
             raise RuntimeError('speechsplit_amd.Solver needs a ROCm GPU (the engine has no CPU fallback)')
@@ -134,30 +141,57 @@ class Solver(object):
         self.load_optimizer_state_dict(ckpt['optimizer'])
 
     # ---- one iteration of solver.py:141-172 on a collated batch
-    def train_on_batch(self, batch, draws=None):
+    N_DRAWS = 4                    # InterpLnr calls per step: the outer one and Encoder_7's three (SolverF0: Encoder_6's three)
+
+    def _shard(self, batch, draws):
+        """This rank's part of a collated batch and of its draws (drawn here, as the reference does, when none are given)."""
         x_real_org, emb_org, f0_org, len_org = batch
         per_rank = getattr(self.vcc_loader, 'per_rank', False)       # the loader already produced this rank's shard
         Bg = x_real_org.shape[0] * (self.world if per_rank else 1)
         if draws is None:
-            draws = draw_interp(Bg, 4, self.hparams)                 # same generator calls, same order as the reference
+            draws = draw_interp(Bg, self.N_DRAWS, self.hparams)      # same generator calls, same order as the reference
         if self.world > 1:
             if not per_rank:
                 x_real_org, emb_org, f0_org, len_org = _dist.shard_batch(batch, self.rank, self.world)
             draws = _dist.shard_draws(draws[0], draws[1], Bg, self.rank, self.world)
+        return (x_real_org, emb_org, f0_org, len_org), draws
+
+    def _step(self, batch, draws, last=True, accumulate=False, grad_scale=1.0):
+        """One engine step on a collated batch.  last: the step that applies the optimiser (data parallel: the one that all-reduces); otherwise
+        backward only, on this rank alone.  accumulate: the backward adds to the gradient arena."""
+        (x_real_org, emb_org, f0_org, len_org), draws = self._shard(batch, draws)
         to = dict(device=self.device, non_blocking=True)
         # a batch whose frame count is not hparams.max_len_pad is a length bucket (speechsplit_amd/buckets.py): max_len_pad = T
         bucket = x_real_org.shape[1] != self.hparams.max_len_pad
+        args = (x_real_org.to(**to), f0_org.to(**to), emb_org.to(**to), len_org.to(**to), draws)
+        if not last:
+            return self.eng.g3_train_step(*args, no_adam=True, bucket=bucket, accumulate=accumulate)
         if self.world > 1 and self.dp_backend == 'torch':
-            loss = self.eng.dp_train_step(x_real_org.to(**to), f0_org.to(**to), emb_org.to(**to), len_org.to(**to), draws, self.world,
-                                          schedule=self.dp_schedule, bucket=bucket)
-        elif self.world > 1:
-            loss = self.eng.dp_train_step_native(x_real_org.to(**to), f0_org.to(**to), emb_org.to(**to), len_org.to(**to), draws,
-                                                 bucket=bucket)
-        else:
-            loss = self.eng.g3_train_step(x_real_org.to(**to), f0_org.to(**to), emb_org.to(**to), len_org.to(**to), draws,
-                                          bucket=bucket)
+            return self.eng.dp_train_step(*args, self.world, schedule=self.dp_schedule, bucket=bucket, accumulate=accumulate)
+        if self.world > 1:
+            return self.eng.dp_train_step_native(*args, bucket=bucket, accumulate=accumulate)
+        return self.eng.g3_train_step(*args, grad_scale=grad_scale, bucket=bucket, accumulate=accumulate)
+
+    def train_on_batch(self, batch, draws=None):
+        """One optimiser step.  batch: a collated batch, or a LIST of k collated batches (with a list of k draws, or None) -- the
+        micro-batches of one accumulation cycle, whose gradients are summed in the engine's arena and applied once with the mean of their
+        means; each may be a length bucket of its own.  Returns the loss on the device: of the batch, or the mean of the k losses."""
+        if not isinstance(batch[0], (list, tuple)):
+            loss = self._step(batch, draws)
+            self.step_count += 1
+            return loss
+        k = len(batch)
+        draws = [None] * k if draws is None else draws
+        if k < 1 or len(draws) != k:
+            raise ValueError('train_on_batch: a list of k batches takes a list of k draws (or None)')
+        if k == 1:
+            return self.train_on_batch(batch[0], draws[0])
+        total = None
+        for j in range(k):
+            loss = self._step(batch[j], draws[j], last=j == k - 1, accumulate=j > 0, grad_scale=1.0 / k)
+            total = loss.clone() if total is None else total.add_(loss)      # the engine's loss word is rewritten by the next call
         self.step_count += 1
-        return loss
+        return total.div_(k)
 
     # ---- validation on demo.pkl-style data (solver.py:206-227) and the ablation forwards of solver.py:245-251 (no plots)
     def validate(self, validation_pt, ablations=False):
@@ -228,7 +262,7 @@ class Solver(object):
                         skipped_seen = int(host_clip[3])
 
         for i in range(start_iters, self.num_iters):
-            batch = next(data_iter)
+            batch = next(data_iter) if self.accum_steps == 1 else [next(data_iter) for _ in range(self.accum_steps)]
             self.G = self.G.train()
             loss_dev = self.train_on_batch(batch)
             if (i + 1) % self.log_step == 0:
@@ -274,29 +308,23 @@ class SolverF0(Solver):
     against the same classes (demo.ipynb takes their argmax), backward, Adam: ONE `ss_g6_train_step` call.  BASELINE config 4."""
     GENERATOR = Generator_6
 
-    def train_on_batch(self, batch, draws=None):
+    N_DRAWS = 3                    # Encoder_6 resamples three times (model.py:128)
+
+    def _step(self, batch, draws, last=True, accumulate=False, grad_scale=1.0):
         from .utils import quantize_f0_torch
-        x_real_org, emb_org, f0_org, len_org = batch
-        per_rank = getattr(self.vcc_loader, 'per_rank', False)
-        Bg = x_real_org.shape[0] * (self.world if per_rank else 1)
-        if draws is None:
-            draws = draw_interp(Bg, 3, self.hparams)                 # Encoder_6 resamples three times (model.py:128)
-        if self.world > 1:
-            if not per_rank:
-                x_real_org, emb_org, f0_org, len_org = _dist.shard_batch(batch, self.rank, self.world)
-            draws = _dist.shard_draws(draws[0], draws[1], Bg, self.rank, self.world)
+        (x_real_org, emb_org, f0_org, len_org), draws = self._shard(batch, draws)
         to = dict(device=self.device, non_blocking=True)
         mel, f0 = x_real_org.to(**to), f0_org.to(**to)
         onehot, idx = quantize_f0_torch(f0[:, :, 0])
         bucket = mel.shape[1] != self.hparams.max_len_pad
+        args = (mel, onehot, idx.to(torch.int32), draws)
+        if not last:
+            return self.eng.g6_train_step(*args, no_adam=True, bucket=bucket, accumulate=accumulate)
         if self.world > 1 and self.dp_backend == 'torch':
-            loss = self.eng.dp_g6_train_step(mel, onehot, idx.to(torch.int32), draws, self.world, bucket=bucket)
-        elif self.world > 1:
-            loss = self.eng.g6_dp_train_step_native(mel, onehot, idx.to(torch.int32), draws, bucket=bucket)
-        else:
-            loss = self.eng.g6_train_step(mel, onehot, idx.to(torch.int32), draws, bucket=bucket)
-        self.step_count += 1
-        return loss
+            return self.eng.dp_g6_train_step(*args, self.world, bucket=bucket, accumulate=accumulate)
+        if self.world > 1:
+            return self.eng.g6_dp_train_step_native(*args, bucket=bucket, accumulate=accumulate)
+        return self.eng.g6_train_step(*args, grad_scale=grad_scale, bucket=bucket, accumulate=accumulate)
 
     def validate(self, validation_pt, ablations=False):
         raise NotImplementedError('the reference validates Generator_3 only (solver.py:206-227)')
