@@ -6,6 +6,7 @@
 // operate on one fused 768-channel slab, channel concats / splits / transposes are pointer arithmetic, and
 // every contraction is the one fp32 MFMA GEMM.
 #include <dlfcn.h>
+#include <array>
 #include <map>
 #include <string>
 #include <vector>
@@ -166,6 +167,10 @@ struct LstmBlk {
     int xf = 0, xcols = 0;                 // xcols: leading input columns whose gradient is needed (0: all)
     float *xc = nullptr, *xp0 = nullptr, *dgs = nullptr, *d_xc = nullptr;
     bool big() const { return H > 32; }
+    // the block's recurrences run on the persistent kernels (lstm_seq.hip) at the engine's current batch
+    bool persist(const ss_engine* e) const;
+    // ... and its weight-gradient GEMMs are held back until its whole backward chain is through (lstm_bwd)
+    bool defers_weights(const ss_engine* e) const;
     // image of the stacked W_ih of layer l (written by lstm_prep when its rows are whole image groups)
     const float* wimg(int l) const { return (!wcat_img.empty() && wcat_img[l] && in_of(l) % 8 == 0) ? wcat_img[l] : nullptr; }
     int in_of(int l) const { return l == 0 ? In : 2 * H; }
@@ -378,6 +383,41 @@ struct ss_engine {
 };
 
 namespace {
+
+bool LstmBlk::persist(const ss_engine* e) const { return big() && g_persist && lstm_seq_supported(e->curB, H); }
+bool LstmBlk::defers_weights(const ss_engine* e) const { return persist(e) && e->side && g_overlap && g_defer_dw; }
+
+// every conv block, in the order the workspace plan lays them out (carve: packed gradient images, amax / act_scale slots)
+template <class E>
+auto conv_blocks(E& e) -> std::array<decltype(&e.ct), 7> {
+    return {&e.c1[0], &e.c1[1], &e.c1[2], &e.c2[0], &e.c2[1], &e.c2[2], &e.ct};
+}
+
+// ---- named views of the workspace slabs: every pass builds its operands from these
+// Encoder_t's conv block output, the input of its BLSTM
+Slab enc_t_out(const ss_engine* e) { return {e->act_t, e->hp.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}; }
+// input of trunk chain c (1: content, 2: pitch) at layer i: the network input (i = 0) or layer i - 1's output in the fused slab (i = 3: what
+// the chain's BLSTM reads), with the scale word of the block that wrote it; img (nullable): the fused slab's pre-split image
+Slab trunk_in(const ss_engine* e, int c, int i, const float* img = nullptr) {
+    if (i == 0) return c == 1 ? Slab{e->in_mel, e->hp.dim_freq} : Slab{e->in_f0, e->f0p};
+    const int off = (c == 2 && e->kind == SS_GENERATOR_3) ? e->hp.dim_enc : 0;       // first channel of the pitch stream inside the fused slab
+    return {e->xf[i - 1] + off, e->CE, img ? e->ioff(img, off) : nullptr, e->act_scale + (c == 1 ? e->c1 : e->c2)[i - 1].scale_i};
+}
+// the decoder's layer 0 runs on the compact (one row per block of repeated frames) form of its input
+bool dec_compact(const ss_engine* e) { return g_compact0 && e->ld.xf > 0 && e->ld.persist(e); }
+// the decoder's input and input-gradient slabs in the form its layer 0 runs on
+Slab dec_x(const ss_engine* e) { return dec_compact(e) ? Slab{e->ld.xc, e->dec_in_dim} : Slab{e->dec_in, e->dec_in_dim}; }
+Slab dec_dx(const ss_engine* e) { return dec_compact(e) ? Slab{e->ld.d_xc, e->dec_in_dim} : Slab{e->d_dec_in, e->dec_in_dim}; }
+// the code streams that make up the decoder input, in column order (model.py:301-309 / 341-347); returns how many
+int code_srcs(const ss_engine* e, CodeSrc src[3]) {
+    const ss_hparams& h = e->hp;
+    int n = 0, col = 0;
+    auto add = [&](const LstmBlk& lb, int l, float* d_o, int H, int freq) { src[n++] = {lb.out[l], d_o, H, freq, col, (int)lb.ow()}; col += 2 * H; };
+    if (e->kind == SS_GENERATOR_3) add(e->l1, 1, e->d_o1, h.dim_neck, h.freq);
+    add(e->lt, 0, e->d_ot, h.dim_neck_2, h.freq_2);
+    add(e->l2, 0, e->d_o2, h.dim_neck_3, h.freq_3);
+    return n;
+}
 
 long align4(long x) { return (x + 3) & ~3L; }
 
@@ -610,14 +650,14 @@ long carve(E& e, int B, int T) {
     conv_ws(e.ct, "enc2.c");
     {   // packed weight-gradient images of every conv, contiguous so one memset per backward zeroes them all
         long tot = 0;
-        for (auto* cb : {&e.c1[0], &e.c1[1], &e.c1[2], &e.c2[0], &e.c2[1], &e.c2[2], &e.ct}) tot += align4((long)cb->Co * 5 * cb->Cp);
+        for (auto* cb : conv_blocks(e)) tot += align4((long)cb->Co * 5 * cb->Cp);
         put(e.gp_all, tot * 4);
         put(e.amax, 16 * 4);
         if constexpr (assign) {
             e.gp_bytes = tot * 4;
             float* p = e.gp_all;
             int slot = 3;
-            for (ConvBlk* cb : {&e.c1[0], &e.c1[1], &e.c1[2], &e.c2[0], &e.c2[1], &e.c2[2], &e.ct}) {
+            for (ConvBlk* cb : conv_blocks(e)) {
                 cb->gp = cb->Co ? p : nullptr;
                 cb->scale_i = slot - 3;
                 cb->amax_i = slot++;
@@ -807,23 +847,26 @@ int try_img_gemm(ss_engine* e, const GemmDesc& d, hipStream_t st, int klass) {
 }
 
 // scratch of one column-sum launch (kernels.h colsum_acc): float64 partials from the step's bump allocator, counters from the ring
-// (self-resetting; a launch's counters are not handed out again before COLSUM_CTRS / 64 later launches); false: none left, the launch
+// (self-resetting; a launch's counters are not handed out again before COLSUM_CTRS / 64 later launches); null pointers: none left, the launch
 // runs with one workgroup per column block
-bool colsum_scratch(ss_engine* e, int cols, double** part, unsigned** ctr) {
-    *part = nullptr;
-    *ctr = nullptr;
+struct ColScratch {
+    double* part = nullptr;
+    unsigned* ctr = nullptr;
+};
+ColScratch colsum_scratch(ss_engine* e, int cols) {
     const long need = 2 * colsum_scratch_doubles(cols);          // in floats
     const int nb = cdiv(cols, 64);
     if (!e->part || !e->colsum_ctr || nb > ss_engine::COLSUM_CTRS || e->part_off + need > e->part_cap) {
         ++e->scratch_fallbacks;
-        return false;
+        return {};
     }
-    *part = (double*)(e->part + e->part_off);                    // part_off is kept at multiples of 64 floats
+    ColScratch cs;
+    cs.part = (double*)(e->part + e->part_off);                  // part_off is kept at multiples of 64 floats
     e->part_off += (need + 63) & ~63L;
     if (e->colsum_next + nb > ss_engine::COLSUM_CTRS) e->colsum_next = 0;
-    *ctr = e->colsum_ctr + e->colsum_next;
+    cs.ctr = e->colsum_ctr + e->colsum_next;
     e->colsum_next += nb;
-    return true;
+    return cs;
 }
 
 int prof_begin(ss_engine* e, int klass, hipStream_t st, double flops);
@@ -1141,12 +1184,18 @@ float* grad_img_of(ss_engine* e, const float* p, long R) {
 }
 
 // y = relu(GN(conv5(x)))   x: slab view (ld), y: slab view
-// gather (nullable): the resampling plan of the training forward -- GroupNorm + ReLU + gather in one kernel straight into gy / gy_img (the
-// resampled slab and its image at the first real row and the block's first column); y is then not written
-// lens (nullable; eval-mode forwards only): per-row lengths of a ragged batch, device i32[B] -- the GroupNorm takes its statistics over each
-// row's own frames and writes zeros behind them (the convolution itself is row-wise over a slab whose padded rows its producer zeroed)
-int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, const InterpPlan* gather = nullptr, float* gy = nullptr, long gy_ld = 0,
-                   float* gy_img = nullptr, hipEvent_t gather_ready = nullptr, const int* lens = nullptr) {
+struct ConvFwd {
+    // gather (nullable): the resampling plan of the training forward -- GroupNorm + ReLU + gather in one kernel straight into gy / gy_img (the
+    // resampled slab and its image at the first real row and the block's first column), behind gather_ready (nullable); y is then not written
+    const InterpPlan* gather = nullptr;
+    float *gy = nullptr, *gy_img = nullptr;
+    long gy_ld = 0;
+    hipEvent_t gather_ready = nullptr;
+    // lens (nullable; eval-mode forwards only): per-row lengths of a ragged batch, device i32[B] -- the GroupNorm takes its statistics over each
+    // row's own frames and writes zeros behind them (the convolution itself is row-wise over a slab whose padded rows its producer zeroed)
+    const int* lens = nullptr;
+};
+int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, const ConvFwd& o = {}) {
     const int B = e->curB, T = e->curT;
     const long TP = T + 2 * HALO;
     GemmDesc d{};
@@ -1167,13 +1216,11 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
     d.want = CONV_WANT;
     flatten_rows(d, B, T);
     PGEMM_FWD_ON(SS_PROF_CONV_FWD, d, s);
-    if (gather) {
-        if (gather_ready) HIPCHK(hipStreamWaitEvent(s, gather_ready, 0));
-        {
-            Prof pr(e, SS_PROF_GN, s);
-            HIPCHK(gn_relu_gather(cb.cout, cb.Co, TP * cb.Co, gy, gy_ld, TP * gy_ld, gy_img, e->act_scale + cb.scale_i, e->P + cb.ga, e->P + cb.be, cb.stats,
-                                  *gather, B, T, cb.Co, s, e->img16()));
-        }
+    if (o.gather) {
+        if (o.gather_ready) HIPCHK(hipStreamWaitEvent(s, o.gather_ready, 0));
+        Prof pr(e, SS_PROF_GN, s);
+        HIPCHK(gn_relu_gather(cb.cout, cb.Co, TP * cb.Co, o.gy, o.gy_ld, TP * o.gy_ld, o.gy_img, e->act_scale + cb.scale_i, e->P + cb.ga, e->P + cb.be,
+                              cb.stats, *o.gather, B, T, cb.Co, s, e->img16()));
         return 0;
     }
     // T > 256 (eval only): the chunked GroupNorm takes its float64 partials from the step's scratch (one region per block: blocks run
@@ -1185,23 +1232,26 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
         gn_scratch = (double*)(e->part + e->part_off);          // part_off is kept at multiples of 64 floats
         e->part_off += need;
     }
-    {
-        Prof pr(e, SS_PROF_GN, s);
-        HIPCHK(gn_relu_fwd(cb.cout, cb.Co, TP * cb.Co, y.p, y.ld, TP * y.ld, e->P + cb.ga, e->P + cb.be, cb.stats, B, T, cb.Co, s, gn_scratch, lens));
-    }
+    Prof pr(e, SS_PROF_GN, s);
+    HIPCHK(gn_relu_fwd(cb.cout, cb.Co, TP * cb.Co, y.p, y.ld, TP * y.ld, e->P + cb.ga, e->P + cb.be, cb.stats, B, T, cb.Co, s, gn_scratch, o.lens));
     return 0;
 }
 
 // dy: gradient of the block output (slab view, overwritten in place with the conv-output gradient);
 // x: the block's forward input; dx: where to put the input gradient (p == nullptr: not needed)
-// scatter / src (nullable): the block's output was resampled in the forward (training): src is the gradient of the RESAMPLED output (at its
-// first real row and this block's first column, row stride src_ld); the gather's adjoint is taken inside the GroupNorm backward, which
-// writes dy
-// dws (nullable): the weight-gradient GEMM goes to that stream behind an event, the chain on `s` does not wait for it -- the caller keeps dy
-// untouched until dws is joined
 // bw: collects the weight gradient's re-layout (unpack_later) and names the caller buffer of a layer-0 block's input gradient
-int conv_block_bwd(ss_engine* e, Backward& bw, ConvBlk& cb, Slab dy, Slab x, Slab dx, hipStream_t s, const InterpPlan* scatter = nullptr, const float* src = nullptr,
-                   long src_ld = 0, hipStream_t dws = nullptr) {
+struct ConvBwd {
+    // scatter / src (nullable): the block's output was resampled in the forward (training): src is the gradient of the RESAMPLED output (at its
+    // first real row and this block's first column, row stride src_ld); the gather's adjoint is taken inside the GroupNorm backward, which
+    // writes dy
+    const InterpPlan* scatter = nullptr;
+    const float* src = nullptr;
+    long src_ld = 0;
+    // dws (nullable): the weight-gradient GEMM goes to that stream behind an event, the chain on `s` does not wait for it -- the caller keeps dy
+    // untouched until dws is joined
+    hipStream_t dws = nullptr;
+};
+int conv_block_bwd(ss_engine* e, Backward& bw, ConvBlk& cb, Slab dy, Slab x, Slab dx, hipStream_t s, const ConvBwd& o = {}) {
     const int B = e->curB, T = e->curT;
     const long TP = T + 2 * HALO, R = (long)B * TP;
     float* am = (g_bwd_f16x2 && cb.amax_i >= 0) ? e->amax + cb.amax_i : nullptr;
@@ -1212,7 +1262,7 @@ int conv_block_bwd(ss_engine* e, Backward& bw, ConvBlk& cb, Slab dy, Slab x, Sla
     {
         Prof pr(e, SS_PROF_GN, s);
         HIPCHK(gn_relu_bwd(cb.cout, cb.Co, TP * cb.Co, dy.p, dy.ld, TP * dy.ld, e->P + cb.ga, e->P + cb.be, cb.stats,
-                           e->G + cb.ga, e->G + cb.be, e->G + cb.b, am, cb.part, B, T, cb.Co, s, scatter, src, src_ld, TP * src_ld, im16));
+                           e->G + cb.ga, e->G + cb.be, e->G + cb.b, am, cb.part, B, T, cb.Co, s, o.scatter, o.src, o.src_ld, TP * o.src_ld, im16));
     }
     // the conv-output gradient as an image for the image GEMM (scale: the power of two for the maximum gn_relu_bwd has just measured)
     const float* dimg = im16;
@@ -1244,26 +1294,22 @@ int conv_block_bwd(ss_engine* e, Backward& bw, ConvBlk& cb, Slab dy, Slab x, Sla
     d.flags = GEMM_TA | GEMM_TB | GEMM_ACCUM | (am ? GEMM_F16X2 : 0);
     d.amax_a = am;                                  // gradient operand: measured scale; the block input is O(1)
     d.ksplit = pick_ksplit(d.M, d.N, d.K);
-    if (dws && dws != s) CHK(fork_join(e, s, dws));
-    else dws = s;
+    hipStream_t dws = o.dws ? o.dws : s;
+    if (dws != s) CHK(fork_join(e, s, dws));
     PGEMM_ON(SS_PROF_CONV_DW, d, dws);
     // packed [Co][5][Cp] -> the parameter's [Co][Ci][5]: nobody reads it before the optimiser (or, data parallel, the layer's bucket), so the
     // one-GPU step collects the blocks and unpacks them all in one launch at the end of the backward (backward_encoder) instead of seven
     // small launches on the trunk's dependent chain
     if (bw.unpack_later && bw.unpack.n < CONV_UNPACK_MAX) bw.unpack.t[bw.unpack.n++] = {cb.gp, e->G + cb.w, cb.Co, cb.Ci, cb.Cp};
     else HIPCHK(conv_unpack_grad(cb.gp, cb.Co, cb.Ci, cb.Cp, e->G + cb.w, dws, bw.accumulate));
-    if (dx.p) {
+    // input gradient: dy against the flipped taps, T rows per utterance, into rows of stride ldc (utterances cstride apart)
+    auto dx_desc = [&](const float* taps, float* C, long ldc, long cstride) {
         GemmDesc g{};
         g.A = {dy.p, dy.ld, TP * dy.ld, cb.Co, dy.ld};
-        if (dimg) {
-            g.a_pre = dimg;
-            g.a_pre_scale = dsc;
-        }
-        g.B = {cb.wb, 5L * cb.Co, 0, 0, 0};
-        g.b_pre = cb.img_ok() ? cb.wb_img : nullptr;
-        g.C = dx.p + HALO * dx.ld;
-        g.ldc = dx.ld;
-        g.cstride = TP * dx.ld;
+        g.B = {taps, 5L * cb.Co, 0, 0, 0};
+        g.C = C;
+        g.ldc = ldc;
+        g.cstride = cstride;
         g.M = T;
         g.N = cb.Ci;
         g.K = 5 * cb.Co;
@@ -1272,6 +1318,15 @@ int conv_block_bwd(ss_engine* e, Backward& bw, ConvBlk& cb, Slab dy, Slab x, Sla
         g.flags = am ? GEMM_F16X2 : 0;
         g.amax_a = am;
         g.want = CONV_WANT;
+        return g;
+    };
+    if (dx.p) {
+        GemmDesc g = dx_desc(cb.wb, dx.p + HALO * dx.ld, dx.ld, TP * dx.ld);
+        if (dimg) {
+            g.a_pre = dimg;
+            g.a_pre_scale = dsc;
+        }
+        g.b_pre = cb.img_ok() ? cb.wb_img : nullptr;
         flatten_rows(g, B, T);
         PGEMM_ON(SS_PROF_CONV_DX, g, s);
     }
@@ -1281,20 +1336,7 @@ int conv_block_bwd(ss_engine* e, Backward& bw, ConvBlk& cb, Slab dy, Slab x, Sla
         // ever computed or stored, and the halo rows of dy (zero) are what the taps past either end of an utterance read
         if (!cb.wb0) return fail("internal: input gradient asked of a conv block without its tap buffer");
         HIPCHK(conv_pack_dx(e->P + cb.w, cb.Co, cb.Ci, cb.wb0, s));
-        GemmDesc g{};
-        g.A = {dy.p, dy.ld, TP * dy.ld, cb.Co, dy.ld};
-        g.B = {cb.wb0, 5L * cb.Co, 0, 0, 0};
-        g.C = tg->p;
-        g.ldc = tg->ld;
-        g.cstride = (long)T * tg->ld;
-        g.M = T;
-        g.N = cb.Ci;
-        g.K = 5 * cb.Co;
-        g.batch = B;
-        g.ksplit = 1;
-        g.flags = am ? GEMM_F16X2 : 0;
-        g.amax_a = am;
-        g.want = CONV_WANT;
+        GemmDesc g = dx_desc(cb.wb0, tg->p, tg->ld, (long)T * tg->ld);
         PGEMM_ON(SS_PROF_CONV_DX, g, s);
     }
     return 0;
@@ -1305,7 +1347,7 @@ int conv_block_bwd(ss_engine* e, Backward& bw, ConvBlk& cb, Slab dy, Slab x, Sla
 // the fragment-major W_hh of the forward recurrence.  Independent of the activations, so the schedule runs it on a branch.
 int lstm_prep(ss_engine* e, LstmBlk& lb, PrepTable& tb, hipStream_t s) {
     const int H = lb.H;
-    const bool persist = lb.big() && g_persist && lstm_seq_supported(e->curB, H);
+    const bool persist = lb.persist(e);
     for (int l = 0; l < lb.L; ++l) {
         for (int dir = 0; dir < 2; ++dir) {
             const LstmDir& pd = lb.pd[l * 2 + dir];
@@ -1321,11 +1363,31 @@ int lstm_prep(ss_engine* e, LstmBlk& lb, PrepTable& tb, hipStream_t s) {
     return 0;
 }
 
+// input projections of layer l over the slab xi: both directions in one GEMM against the stacked W_ih / summed biases of lstm_prep (N = 8H)
+GemmDesc lstm_proj_desc(const ss_engine* e, const LstmBlk& lb, int l, Slab xi) {
+    const int B = e->curB, T = e->curT, H = lb.H;
+    const long TP = T + 2 * HALO;
+    GemmDesc d{};
+    d.A = {xi.p + HALO * xi.ld, xi.ld, TP * xi.ld, 0, 0};
+    d.B = {lb.wcat[l], lb.in_of(l), 0, 0, 0};
+    d.b_pre = lb.wimg(l);
+    d.C = lb.gates[l] + HALO * 8L * H;
+    d.ldc = 8L * H;
+    d.cstride = TP * 8L * H;
+    d.bias = lb.bsum + (long)l * 8 * H;
+    d.M = T;
+    d.N = 8 * H;
+    d.K = lb.in_of(l);
+    d.batch = B;
+    d.ksplit = 1;
+    flatten_rows(d, B, T);
+    return d;
+}
+
 // Decoder-size BLSTM: one persistent launch per layer, or one launch per time step (persist = 0 / a batch the persistent kernels do not take).
 int lstm_big_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s, const int* lens) {
     const int B = e->curB, T = e->curT, H = lb.H;
-    const long TP = T + 2 * HALO;
-    const bool persist = g_persist && lstm_seq_supported(B, H);
+    const bool persist = lb.persist(e);
     // only fp16 x 2 GEMMs read the hidden states' pre-split images, and only the persistent recurrences write them
     lb.out_img_valid = persist && ((e->precision == SS_PRECISION_F32 && g_fwd_f16x2) || e->img16()) && !lb.out_img.empty() && lb.out_img[0];
     const long half = 2L * (((B + 15) / 16) * 16) * H;       // one of the two ping-pong h(t) tiles of the per-step schedule
@@ -1347,22 +1409,9 @@ int lstm_big_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s, const int* le
             d.batch = 1;
             d.ksplit = 1;
             PGEMM_FWD_ON(SS_PROF_DEC_PROJ0, d, s);
-        } else {   // both directions in one GEMM against the stacked W_ih / summed biases of lstm_prep (N = 8H)
-            GemmDesc d{};
-            d.A = {xi.p + HALO * xi.ld, xi.ld, TP * xi.ld, 0, 0};
+        } else {
+            GemmDesc d = lstm_proj_desc(e, lb, l, xi);
             if (l > 0 && lb.out_img_valid) d.a_pre = e->ioff(lb.out_img[l - 1], HALO * xi.ld);       // written by the layer below's recurrence
-            d.B = {lb.wcat[l], In, 0, 0, 0};
-            d.b_pre = lb.wimg(l);
-            d.C = lb.gates[l] + HALO * 8L * H;
-            d.ldc = 8L * H;
-            d.cstride = TP * 8L * H;
-            d.bias = lb.bsum + (long)l * 8 * H;
-            d.M = T;
-            d.N = 8 * H;
-            d.K = In;
-            d.batch = B;
-            d.ksplit = 1;
-            flatten_rows(d, B, T);
             PGEMM_FWD_ON(l > 0 ? SS_PROF_DEC_PROJ : SS_PROF_DEC_PROJ0, d, s);
         }
         if (persist) {   // start state zeroed by lstm_prep
@@ -1390,40 +1439,17 @@ int lstm_big_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s, const int* le
     return 0;
 }
 
-// the decoder's layer 0 runs on the compact (one row per block of repeated frames) form of its input
-static bool dec_compact(const ss_engine* e) { return g_compact0 && e->ld.xf > 0 && e->ld.big() && g_persist && lstm_seq_supported(e->curB, e->ld.H); }
-
 // lens (nullable): per-row lengths of a ragged eval-mode batch; every recurrence of the block zeroes the state of rows behind their end
 int lstm_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s, const int* lens = nullptr) {
     if (lb.big()) return lstm_big_fwd(e, lb, x, s, lens);
     const int B = e->curB, T = e->curT, H = lb.H;
-    const long TP = T + 2 * HALO;
     for (int l = 0; l < lb.L; ++l) {
-        const int In = lb.in_of(l);
         Slab xi = l == 0 ? x : Slab{lb.out[l - 1], lb.ow()};      // layer 1: K = 2H real columns of the (possibly padded) rows
-        {   // both directions in one GEMM (stacked W_ih and summed biases from lstm_prep)
-            GemmDesc d{};
-            d.A = {xi.p + HALO * xi.ld, xi.ld, TP * xi.ld, 0, 0};
-            d.a_pre_scale = xi.scale;                  // conv-block output (layer 0); hidden states |h| < 1 take the fixed 16
-            d.B = {lb.wcat[l], In, 0, 0, 0};
-            d.b_pre = lb.wimg(l);
-            d.C = lb.gates[l] + HALO * 8L * H;
-            d.ldc = 8L * H;
-            d.cstride = TP * 8L * H;
-            d.bias = lb.bsum + (long)l * 8 * H;
-            d.M = T;
-            d.N = 8 * H;
-            d.K = In;
-            d.batch = B;
-            d.ksplit = 1;
-            flatten_rows(d, B, T);
-            PGEMM_FWD_ON(SS_PROF_ENC_LSTM, d, s);
-        }
-        {
-            Prof pr(e, SS_PROF_ENC_REC, s);
-            HIPCHK(lstm_small_fwd(lb.gates[l], e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.out[l], lb.csave[l], B, T, H,
-                                  s, lens));
-        }
+        GemmDesc d = lstm_proj_desc(e, lb, l, xi);
+        d.a_pre_scale = xi.scale;                  // conv-block output (layer 0); hidden states |h| < 1 take the fixed 16
+        PGEMM_FWD_ON(SS_PROF_ENC_LSTM, d, s);
+        Prof pr(e, SS_PROF_ENC_REC, s);
+        HIPCHK(lstm_small_fwd(lb.gates[l], e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.out[l], lb.csave[l], B, T, H, s, lens));
     }
     return 0;
 }
@@ -1560,10 +1586,8 @@ int lstm_weight_grads(ss_engine* e, Backward& bw, LstmBlk& lb, int l, Slab xi, c
         }
         PGEMM_ON(klass, h, ws);
         if (!bias_done) {
-            double* cpart;
-            unsigned* cctr;
-            colsum_scratch(e, 8 * H, &cpart, &cctr);
-            HIPCHK(colsum_bias(dG, 8L * H, (int)R, 4 * H, e->G + p0.bih, e->G + p0.bhh, e->G + p1.bih, e->G + p1.bhh, cpart, cctr, ws));
+            const ColScratch cs = colsum_scratch(e, 8 * H);
+            HIPCHK(colsum_bias(dG, 8L * H, (int)R, 4 * H, e->G + p0.bih, e->G + p0.bhh, e->G + p1.bih, e->G + p1.bhh, cs.part, cs.ctr, ws));
         }
         if (!compact) return 0;
         // compact layer 0: dW_hh went out batched above, dW_ih comes from the block sums below, per direction
@@ -1591,10 +1615,8 @@ int lstm_weight_grads(ss_engine* e, Backward& bw, LstmBlk& lb, int l, Slab xi, c
         if (img_ok) h.b_pre = dir == 0 ? lb.out_img[l] : e->ioff(lb.out_img[l], 2L * H + H);
         PGEMM_ON(klass, h, wh);
         if (!bias_done) {     // the persistent backward kernel accumulates both bias gradients itself
-            double* cpart;
-            unsigned* cctr;
-            colsum_scratch(e, 4 * H, &cpart, &cctr);
-            HIPCHK(colsum_acc(dGd, 8L * H, (int)R, 4 * H, e->G + pd.bih, cpart, cctr, ws));
+            const ColScratch cs = colsum_scratch(e, 4 * H);
+            HIPCHK(colsum_acc(dGd, 8L * H, (int)R, 4 * H, e->G + pd.bih, cs.part, cs.ctr, ws));
             HIPCHK(hipMemcpyAsync(e->G + pd.bhh, e->G + pd.bih, 4L * H * 4, hipMemcpyDeviceToDevice, ws));
         }
         CHK(dir_bucket(pd, wa, wh));
@@ -1666,6 +1688,19 @@ int lstm_input_grad(ss_engine* e, LstmBlk& lb, int l, Slab dxi, long r0, long nr
     return 0;
 }
 
+// What the gradient launches of layer l agree on: lstm_bwd launches the recurrence, lstm_late_weights possibly much later the GEMMs behind it
+struct LayerGrads {
+    float* am;                // fp16 x 2 gradient GEMMs need the slab's maximum, which only the persistent kernel measures
+    bool bias_in_kernel;      // b_ih and b_hh gradients sit back to back in the arena (registration order): the persistent kernel fills both
+    bool compact0;            // layer 0's input gradient dx is the compact slab: the recurrence also writes the block sums it is taken from
+};
+LayerGrads layer_grads(const ss_engine* e, const LstmBlk& lb, int l, Slab dx = {}) {
+    const bool persist = lb.persist(e);
+    const LstmDir &p0 = lb.pd[l * 2], &p1 = lb.pd[l * 2 + 1];
+    return {(persist && g_bwd_f16x2 && lb.amax0 >= 0) ? e->amax + lb.amax0 + l : nullptr,
+            persist && !g_deterministic && p0.bhh == p0.bih + 4L * lb.H && p1.bhh == p1.bih + 4L * lb.H, l == 0 && lb.xf && dx.p == lb.d_xc};
+}
+
 // d_top: gradient slab of the last layer's output [B,TP,2H]; x: forward input; dx: input-gradient view or null
 // dx_ready (nullable): recorded on `s` right behind the input-gradient GEMM of layer 0, i.e. BEFORE this block's weight-gradient
 // launches go to their branch stream.  A consumer that waits for it is not held up by whatever else shares a hardware queue with
@@ -1679,14 +1714,19 @@ int lstm_bwd(ss_engine* e, Backward& bw, LstmBlk& lb, const float* d_top, Slab x
     const int B = e->curB, T = e->curT, H = lb.H;
     const long TP = T + 2 * HALO, R = (long)B * TP;
     const float* dcur = d_top;
-    const bool persist = lb.big() && g_persist && lstm_seq_supported(B, H);
+    const bool persist = lb.persist(e);
+    // Decoder on the persistent kernels: its weight-gradient GEMMs are held back until the whole recurrence chain
+    // (layer L-1 .. 0 and the input gradients between them) is through.  Co-scheduled they do not fill idle cycles:
+    // they stretch the latency-bound recurrence steps and halve the rate of the input-gradient GEMMs on the critical
+    // path (measured: chain 2.95 ms with the GEMMs beside it against 1.93 ms alone + 0.78 ms of GEMMs), whereas the
+    // encoder backward that follows is a string of small launches they can run beside.
+    const bool defer = lb.defers_weights(e) || late_w;
     // see ss_engine::wq_pool: only with the weight gradients deferred (their usual schedule), on the decoder, where XCDs stay free
-    const bool xcd = persist && &lb == &e->ld && g_xcd_dw && e->side && g_overlap && (g_defer_dw || late_w) && !g_deterministic &&
-                     lstm_seq_free_xcds(B, H) >= 2;
+    const bool xcd = defer && persist && &lb == &e->ld && g_xcd_dw && e->side && g_overlap && !g_deterministic && lstm_seq_free_xcds(B, H) >= 2;
     bool xcd_split[4] = {false, false, false, false};
     // 16-bit data path: the recurrence writes the gradient image itself and every weight-gradient GEMM of a layer is one image launch per
     // operand pair, so the WHOLE layer above goes out beside this layer's recurrence (work-queue form: 144 KB workgroups, one per free CU)
-    const bool early16 = persist && &lb == &e->ld && g_early_dw && e->img16() && e->side && g_overlap && (g_defer_dw || late_w) &&
+    const bool early16 = defer && persist && &lb == &e->ld && g_early_dw && e->img16() && e->side && g_overlap &&
                          !g_deterministic && !e->dp_on && e->wq_pool && lstm_seq_free_xcds(B, H) >= 2 && lb.out_img_valid;
     bool early_ready[4] = {false, false, false, false};
     for (int l = lb.L - 1; l >= 0; --l) {
@@ -1694,11 +1734,7 @@ int lstm_bwd(ss_engine* e, Backward& bw, LstmBlk& lb, const float* d_top, Slab x
         Slab dxi = l == 0 ? dx : Slab{lb.dmid[l & 1], lb.ow()};
         float* dG = lb.gates[l];
         hipStream_t ws = s;
-        // fp16 x 2 gradient GEMMs need the slab's maximum, which only the persistent kernel measures
-        float* am = (persist && g_bwd_f16x2 && lb.amax0 >= 0) ? e->amax + lb.amax0 + l : nullptr;
-        // b_ih and b_hh gradients sit back to back in the arena (registration order): the persistent kernel fills both
-        const bool bias_in_kernel = persist && !g_deterministic && lb.pd[l * 2].bhh == lb.pd[l * 2].bih + 4L * H &&
-                                    lb.pd[l * 2 + 1].bhh == lb.pd[l * 2 + 1].bih + 4L * H;
+        const auto [am, bias_in_kernel, compact0] = layer_grads(e, lb, l, dx);
         if (lb.big()) {
             // persistent: start state zeroed by backward_decoder
             if (persist) {
@@ -1708,24 +1744,20 @@ int lstm_bwd(ss_engine* e, Backward& bw, LstmBlk& lb, const float* d_top, Slab x
                 // only as bf16 when every reader takes the image: weight gradients and input gradient on the image GEMM (layers >= 1: aligned
                 // shapes, both images present; layer 0: compact form -- dW_ih and dX from the block sums, dW_hh from the image), bias sums in the
                 // kernel (not the deterministic mode's column sum over the fp32 slab), weight gradients deferred or not: same readers
-                const bool compact0 = l == 0 && lb.xf && dx.p == lb.d_xc;
                 const bool skip32 = dg16 && bias_in_kernel && lb.out_img_valid && lb.out_img[l] &&
                                     (l == 0 ? compact0 : (lb.wimg(l) != nullptr && lb.in_of(l) % 64 == 0)) && H % 64 == 0;
                 {
                     Prof pr(e, SS_PROF_REC_BWD, s, 2.0 * 2 * B * T * 4.0 * H * H);
                     HIPCHK(lstm_seq_bwd(dG, e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.px_l(l), dcur, lb.csave[l], lb.sync_b(l),
                                         e->sticky, am, bias_in_kernel ? e->G + lb.pd[l * 2].bih : nullptr,
-                                        bias_in_kernel ? e->G + lb.pd[l * 2 + 1].bih : nullptr, (l == 0 && lb.xf && dx.p == lb.d_xc) ? lb.dgs : nullptr,
-                                        (l == 0 && lb.xf && dx.p == lb.d_xc) ? lb.xf : 0, B, T, H, false, false, s, dg16 ? e->dg_img[l] : nullptr, (e->img16() ? 1 : 0) | (skip32 ? 4 : 0)));      // 1: products of the high fp16 pieces only (16-bit data path)
+                                        bias_in_kernel ? e->G + lb.pd[l * 2 + 1].bih : nullptr, compact0 ? lb.dgs : nullptr, compact0 ? lb.xf : 0, B, T, H, false, false, s, dg16 ? e->dg_img[l] : nullptr, (e->img16() ? 1 : 0) | (skip32 ? 4 : 0)));      // 1: products of the high fp16 pieces only (16-bit data path)
                 }
                 if (dg16) e->bwd.dg16_written |= 1 << l;
                 if (skip32) e->bwd.dg32_skipped |= 1 << l;
                 if (early16) {
                     if (l + 1 < lb.L && early_ready[l + 1]) {
                         HIPCHK(seq_gate(lb.sync_b(l), B, H, e->side));          // dispatched once this recurrence's grid is resident
-                        DwRoute queued;
-                        queued.queue = true;
-                        if (const int r = lstm_weight_grads(e, bw, lb, l + 1, Slab{lb.out[l], 2L * H}, am ? e->amax + lb.amax0 + l + 1 : nullptr, true, e->side, queued); r < 0) return r;
+                        if (const int r = lstm_weight_grads(e, bw, lb, l + 1, Slab{lb.out[l], 2L * H}, am ? e->amax + lb.amax0 + l + 1 : nullptr, true, e->side, {.queue = true}); r < 0) return r;
                         e->bwd.dec_w_done |= 1 << (l + 1);
                     }
                     if (l >= 1 && l < 3 && dg16 && bias_in_kernel && lb.out_img[l] && lb.out_img[l - 1] && e->bwd.wq_next + 2 <= ss_engine::WQ_SLOTS) {
@@ -1747,33 +1779,18 @@ int lstm_bwd(ss_engine* e, Backward& bw, LstmBlk& lb, const float* d_top, Slab x
                         e->side_used = true;
                     }
                 }
-            }
-            if (!persist) {      // one launch per time step
+            } else {      // one launch per time step
                 const long half = 2L * (((B + 15) / 16) * 16) * 4 * H;
                 HIPCHK(hipMemsetAsync(lb.gf, 0, 2 * half * 4, s));
                 for (int st = 0; st < T; ++st)
                     HIPCHK(lstm_step_bwd(dG, lb.wfrag[l], lb.gf + (st & 1) * half, lb.gf + ((st & 1) ^ 1) * half, dcur, lb.csave[l], lb.dc, B, T, H, st, s));
             }
         } else {
-            {
-                Prof pr(e, SS_PROF_ENC_REC, s);
-                HIPCHK(lstm_small_bwd(dG, e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, dcur, lb.csave[l], B, T, H, s));
-            }
-        }
-        // Decoder on the persistent kernels: its weight-gradient GEMMs are held back until the whole recurrence chain
-        // (layer L-1 .. 0 and the input gradients between them) is through.  Co-scheduled they do not fill idle cycles:
-        // they stretch the latency-bound recurrence steps and halve the rate of the input-gradient GEMMs on the critical
-        // path (measured: chain 2.95 ms with the GEMMs beside it against 1.93 ms alone + 0.78 ms of GEMMs), whereas the
-        // encoder backward that follows is a string of small launches they can run beside.
-        const bool defer = (persist && e->side && g_overlap && g_defer_dw) || late_w;
-        if (defer) {
-            if (dxi.p) CHK(lstm_input_grad(e, lb, l, dxi, 0, R, am, s));
-            if (l == 0 && dx_ready) HIPCHK(hipEventRecord(dx_ready, s));
-            dcur = dxi.p;
-            continue;
+            Prof pr(e, SS_PROF_ENC_REC, s);
+            HIPCHK(lstm_small_bwd(dG, e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, dcur, lb.csave[l], B, T, H, s));
         }
         // the pre-activation gradients of this layer are complete behind this point
-        if (e->side && g_overlap) {
+        if (!defer && e->side && g_overlap) {
             // decoder: the side stream.  Encoder BLSTMs (a string of ~36 tiny split-K launches): the third branch stream, so
             // that they do not queue behind the decoder's weight gradients, which drain on the side stream until late
             ws = (!lb.big() && e->side3) ? e->side3 : e->side;
@@ -1783,10 +1800,11 @@ int lstm_bwd(ss_engine* e, Backward& bw, LstmBlk& lb, const float* d_top, Slab x
         // input gradient first (the next layer's recurrence needs it)
         if (dxi.p) CHK(lstm_input_grad(e, lb, l, dxi, 0, R, am, s));
         if (l == 0 && dx_ready) HIPCHK(hipEventRecord(dx_ready, s));
-        if (const int r = lstm_weight_grads(e, bw, lb, l, xi, am, bias_in_kernel, ws); r < 0) return r;
+        if (!defer)
+            if (const int r = lstm_weight_grads(e, bw, lb, l, xi, am, bias_in_kernel, ws); r < 0) return r;
         dcur = dxi.p;
     }
-    if (persist && e->side && g_overlap && g_defer_dw && !late_w) {
+    if (lb.defers_weights(e) && !late_w) {
         CHK(fork_join(e, s, e->side));
         e->side_used = true;
         CHK(lstm_late_weights(e, bw, lb, x, e->side));
@@ -1797,14 +1815,12 @@ int lstm_bwd(ss_engine* e, Backward& bw, LstmBlk& lb, const float* d_top, Slab x
 // all layers' weight / bias gradients of a block whose chain ran with deferred weights (the decoder's deferred batch; every block under late_w)
 int lstm_late_weights(ss_engine* e, Backward& bw, LstmBlk& lb, Slab x, hipStream_t ws, int l_hi, int l_lo, DwRoute route) {
     const int H = lb.H;
-    const bool persist = lb.big() && g_persist && lstm_seq_supported(e->curB, H);
     for (int l = l_hi < 0 ? lb.L - 1 : l_hi; l >= l_lo; --l) {       // layers l_hi .. l_lo (default: all, last first)
         if (&lb == &e->ld && ((e->bwd.dec_w_done >> l) & 1)) continue;        // went out beside a recurrence (early_dw)
         Slab xi = l == 0 ? x : Slab{lb.out[l - 1], lb.ow()};
-        float* am = (persist && g_bwd_f16x2 && lb.amax0 >= 0) ? e->amax + lb.amax0 + l : nullptr;
-        const bool bias_in_kernel = persist && !g_deterministic && lb.pd[l * 2].bhh == lb.pd[l * 2].bih + 4L * H && lb.pd[l * 2 + 1].bhh == lb.pd[l * 2 + 1].bih + 4L * H;
+        const LayerGrads lg = layer_grads(e, lb, l);
         route.part = (&lb == &e->ld && ((e->bwd.dec_ih_done >> l) & 1)) ? 2 : 0;
-        const int dir_buckets = lstm_weight_grads(e, bw, lb, l, xi, am, bias_in_kernel, ws, route);
+        const int dir_buckets = lstm_weight_grads(e, bw, lb, l, xi, lg.am, lg.bias_in_kernel, ws, route);
         if (dir_buckets < 0) return dir_buckets;
         // this layer's gradients (both directions: W_ih, W_hh, b_ih, b_hh -- contiguous in the arena) are final (unless each direction has
         // already gone out on its own)
@@ -1827,8 +1843,7 @@ int join_side(ss_engine* e, hipStream_t s) {
 // block's output (as an image or as fp32) take the scale from these words, so no parameter magnitude makes a forward product overflow.
 int act_scales_all(ss_engine* e, hipStream_t s) {
     ActScaleTable tb{};
-    ConvBlk* all[7] = {&e->c1[0], &e->c1[1], &e->c1[2], &e->c2[0], &e->c2[1], &e->c2[2], &e->ct};
-    for (ConvBlk* cb : all) {
+    for (ConvBlk* cb : conv_blocks(*e)) {
         const int i = cb->scale_i;
         if (i < 0 || i >= ACT_SCALE_MAX) return fail("act_scales_all: bad slot");
         tb.gamma[i] = cb->Co ? e->P + cb->ga : e->P;
@@ -1841,11 +1856,43 @@ int act_scales_all(ss_engine* e, hipStream_t s) {
 }
 
 // ---- whole-model schedules ---------------------------------------------------------------------------------
+// The forward's branch-stream work that nobody needs before the trunk is through (see forward_core, which decides where it is enqueued)
+int forward_branch_work(ss_engine* e, const FusedForward& fused, const int* lens, hipStream_t b2) {
+    PrepTable tb;
+    tb.n = 0;
+    tb.img_bf16 = e->img16();
+    if (e->kind == SS_GENERATOR_3) CHK(lstm_prep(e, e->l1, tb, b2));
+    CHK(lstm_prep(e, e->l2, tb, b2));
+    CHK(lstm_prep(e, e->lt, tb, b2));
+    CHK(lstm_prep(e, e->ld, tb, b2));
+    HIPCHK(prep_run(tb, b2));
+    if (fused.prezero) {     // nothing touches the gradient arena before the decoder backward; b2 is joined long before
+        if (!fused.keep_grads) HIPCHK(hipMemsetAsync(e->G, 0, e->arena * 4, b2));
+        HIPCHK(hipMemsetAsync(e->amax, 0, 16 * 4, b2));      // (the gradient slabs' maxima are per backward, accumulating or not)
+        e->fwd.grads_zeroed = true;
+        // the backward recurrences' group words and exchange tiles (nothing in the forward touches them): zeroed here, the backward
+        // needs no fork / memset / join between the head's gradient and its first recurrence (two event hops on the critical path)
+        if (e->ld.persist(e)) {
+            HIPCHK(hipMemsetAsync(e->ld.zb, 0, e->ld.zb_bytes, b2));
+            if (e->wq_pool) HIPCHK(hipMemsetAsync(e->wq_pool, 0, ss_engine::WQ_SLOTS * 16, b2));
+            e->fwd.bwd_sync_zeroed = true;
+        }
+    }
+    // fp16 x 2 products scale WEIGHTS by a fixed 16 (forward and gradient contractions alike, and the persistent recurrences' W_hh):
+    // fine up to |w| < 4094.  Activations carry their own scale (act_scales_all) and gradients their measured one, so the only thing
+    // left to refuse is a parameter beyond 2048 in magnitude, or a non-finite one: the step is then marked invalid (status RANGE)
+    // instead of silently overflowing to inf.
+    if ((g_fwd_f16x2 || g_bwd_f16x2) && e->precision == SS_PRECISION_F32 && e->sticky) HIPCHK(param_guard(e->P, e->arena, 2048.0f, e->sticky, b2));
+    // Encoder_t (model.py:74-89)
+    CHK(conv_block_fwd(e, e->ct, Slab{e->org, e->hp.dim_freq}, enc_t_out(e), b2, {.lens = lens}));
+    CHK(lstm_fwd(e, e->lt, enc_t_out(e), b2, lens));
+    return 0;
+}
+
 // Encoder_7 (G3) / Encoder_6 (G6) trunk + their LSTMs, Encoder_t, decoder, head.  Inputs already in in_mel/in_f0/org/emb.
 // lens (nullable; eval mode only): per-row lengths of a ragged batch (device i32[B], caller-owned, read in stream order).  The staging
 // of the inputs has zeroed the padded frames; here every GroupNorm and every recurrence takes the lengths, everything else is row-wise.
-int forward_core(ss_engine* e, bool training, const float* scales, const int* len_seg, int draw0, hipStream_t s, const FusedForward& fused = {},
-                 const int* lens = nullptr) {
+int forward_core(ss_engine* e, bool training, const float* scales, const int* len_seg, int draw0, hipStream_t s, const FusedForward& fused = {}, const int* lens = nullptr) {
     const int B = e->curB, T = e->curT;
     e->part_off = 0;           // split-K scratch: every launch of a step gets its own region; the previous step is through (stream order) when this one's first kernel runs
     const long TP = T + 2 * HALO;
@@ -1862,8 +1909,7 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     {   // every conv block's per-step weight re-layout (and the images of the packed weights) in one launch
         ConvPackTable pt{};
         pt.img_bf16 = e->img16();
-        ConvBlk* all[7] = {&e->c1[0], &e->c2[0], &e->c1[1], &e->c2[1], &e->c1[2], &e->c2[2], &e->ct};
-        for (ConvBlk* cb : all) {
+        for (ConvBlk* cb : conv_blocks(*e)) {
             if (!cb->Co) continue;
             const bool img = cb->img_ok();
             pt.t[pt.n++] = {e->P + cb->w, cb->wf, cb->wb, img ? cb->wf_img : nullptr, img ? cb->wb_img : nullptr, cb->Co, cb->Ci, cb->Cp};
@@ -1900,57 +1946,27 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     // is ENQUEUED behind the trunk's three layers (it still runs beside them: the host is far ahead of the GPU), so that on a shared
     // hardware queue it can never sit in front of trunk launches.
     const bool prio_fwd = par && g_prio_order;
-    auto branch_work = [&]() -> int {
-        PrepTable tb;
-        tb.n = 0;
-        tb.img_bf16 = e->img16();
-        if (g3) CHK(lstm_prep(e, e->l1, tb, b2));
-        CHK(lstm_prep(e, e->l2, tb, b2));
-        CHK(lstm_prep(e, e->lt, tb, b2));
-        CHK(lstm_prep(e, e->ld, tb, b2));
-        HIPCHK(prep_run(tb, b2));
-        if (fused.prezero) {     // nothing touches the gradient arena before the decoder backward; b2 is joined long before
-            if (!fused.keep_grads) HIPCHK(hipMemsetAsync(e->G, 0, e->arena * 4, b2));
-            HIPCHK(hipMemsetAsync(e->amax, 0, 16 * 4, b2));      // (the gradient slabs' maxima are per backward, accumulating or not)
-            e->fwd.grads_zeroed = true;
-            // the backward recurrences' group words and exchange tiles (nothing in the forward touches them): zeroed here, the backward
-            // needs no fork / memset / join between the head's gradient and its first recurrence (two event hops on the critical path)
-            if (e->ld.big() && g_persist && lstm_seq_supported(e->curB, e->ld.H)) {
-                HIPCHK(hipMemsetAsync(e->ld.zb, 0, e->ld.zb_bytes, b2));
-                if (e->wq_pool) HIPCHK(hipMemsetAsync(e->wq_pool, 0, ss_engine::WQ_SLOTS * 16, b2));
-                e->fwd.bwd_sync_zeroed = true;
-            }
-        }
-        // fp16 x 2 products scale WEIGHTS by a fixed 16 (forward and gradient contractions alike, and the persistent recurrences' W_hh):
-        // fine up to |w| < 4094.  Activations carry their own scale (act_scales_all) and gradients their measured one, so the only thing
-        // left to refuse is a parameter beyond 2048 in magnitude, or a non-finite one: the step is then marked invalid (status RANGE)
-        // instead of silently overflowing to inf.
-        if ((g_fwd_f16x2 || g_bwd_f16x2) && e->precision == SS_PRECISION_F32 && e->sticky) HIPCHK(param_guard(e->P, e->arena, 2048.0f, e->sticky, b2));
-        // Encoder_t (model.py:74-89)
-        CHK(conv_block_fwd(e, e->ct, Slab{e->org, e->hp.dim_freq}, Slab{e->act_t, e->hp.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, b2, nullptr, nullptr, 0,
-                           nullptr, nullptr, lens));
-        CHK(lstm_fwd(e, e->lt, Slab{e->act_t, e->hp.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, b2, lens));
-        return 0;
-    };
     for (int i = 0; i < 3; ++i) {
         float* y = training ? e->act : e->xf[i];
         // Issue order matters: a cross-stream wait on ROCm holds for everything the other stream had been handed when
         // the WAIT was issued, not only up to the recorded event (measured: the trunk stalled ~250 us behind the tiny
         // launches of b2's work).  So: first trunk layer, and only then the rest of b2's work.
-        if (i == 1 && !prio_fwd) CHK(branch_work());
+        if (i == 1 && !prio_fwd) CHK(forward_branch_work(e, fused, lens, b2));
         if (indep) {
             const float* im = (e->fwd.xf_img_valid && i > 0) ? e->xf_img[i - 1] : nullptr;
-            Slab x1 = i == 0 ? Slab{e->in_mel, e->hp.dim_freq} : Slab{e->xf[i - 1], CE, im, e->act_scale + e->c1[i - 1].scale_i};
-            Slab x2 = i == 0 ? Slab{e->in_f0, e->f0p} : Slab{e->xf[i - 1] + off2, CE, im ? e->ioff(im, off2) : nullptr, e->act_scale + e->c2[i - 1].scale_i};
+            const Slab x1 = trunk_in(e, 1, i, im), x2 = trunk_in(e, 2, i, im);
             if (training && g_gn_gather) {       // conv -> [GroupNorm + ReLU + gather] per stack: the normalised slab is never written
-                InterpPlan& pl = e->plan[draw0 + i];
                 float* gi = (e->fwd.xf_img_valid && e->xf_img[i]) ? e->ioff(e->xf_img[i], HALO * CE) : nullptr;
-                CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, b1, &pl, e->xf[i] + HALO * CE + off2, CE, gi ? e->ioff(gi, off2) : nullptr, i == 0 ? plans : nullptr));
-                CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s, &pl, e->xf[i] + HALO * CE, CE, gi, i == 0 ? plans : nullptr));
+                const InterpPlan* pl = &e->plan[draw0 + i];
+                float* gy = e->xf[i] + HALO * CE;
+                hipEvent_t ready = i == 0 ? plans : nullptr;
+                CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, b1,
+                                   {.gather = pl, .gy = gy + off2, .gy_img = gi ? e->ioff(gi, off2) : nullptr, .gy_ld = CE, .gather_ready = ready}));
+                CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s, {.gather = pl, .gy = gy, .gy_img = gi, .gy_ld = CE, .gather_ready = ready}));
                 continue;
             }
-            CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, b1, nullptr, nullptr, 0, nullptr, nullptr, lens));
-            CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s, nullptr, nullptr, 0, nullptr, nullptr, lens));
+            CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, b1, {.lens = lens}));
+            CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s, {.lens = lens}));
             if (training) {
                 InterpPlan& pl = e->plan[draw0 + i];
                 if (i == 0) {
@@ -1965,12 +1981,8 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
             continue;
         }
         // one chain on `s` (Generator_6's single stack; Generator_3 without branch streams)
-        if (g3) {
-            Slab x1 = i == 0 ? Slab{e->in_mel, e->hp.dim_freq} : Slab{e->xf[i - 1], CE, nullptr, e->act_scale + e->c1[i - 1].scale_i};
-            CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s, nullptr, nullptr, 0, nullptr, nullptr, lens));
-        }
-        Slab x2 = i == 0 ? Slab{e->in_f0, e->f0p} : Slab{e->xf[i - 1] + off2, CE, nullptr, e->act_scale + e->c2[i - 1].scale_i};
-        CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, s, nullptr, nullptr, 0, nullptr, nullptr, lens));
+        if (g3) CHK(conv_block_fwd(e, e->c1[i], trunk_in(e, 1, i), Slab{y, CE}, s, {.lens = lens}));
+        CHK(conv_block_fwd(e, e->c2[i], trunk_in(e, 2, i), Slab{y + off2, CE}, s, {.lens = lens}));
         if (training) {
             // one warp for both streams (model.py:202-206), len_seq = max_len_pad for every utterance (:105,157,203)
             InterpPlan& pl = e->plan[draw0 + i];
@@ -1979,42 +1991,29 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
             HIPCHK(interp_gather(pl, e->act + HALO * CE, CE, TP * CE, e->xf[i] + HALO * CE, CE, TP * CE, CE, B, s));
         }
     }
-    if (prio_fwd) CHK(branch_work());
+    if (prio_fwd) CHK(forward_branch_work(e, fused, lens, b2));
     if (par) {
         CHK(fork_join(e, b2, s));                  // bias sums of every block are ready (and Encoder_t is done)
         if (indep) CHK(fork_join(e, b2, b1));      // the pitch chain does not wait for the content chain
         else CHK(fork_join(e, s, b1));
     }
-    CHK(lstm_fwd(e, e->l2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, b1, lens));
-    if (g3) CHK(lstm_fwd(e, e->l1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, s, lens));
+    CHK(lstm_fwd(e, e->l2, trunk_in(e, 2, 3), b1, lens));
+    if (g3) CHK(lstm_fwd(e, e->l1, trunk_in(e, 1, 3), s, lens));
     if (par) CHK(fork_join(e, b1, s));
     // decoder input (model.py:301-309 / 341-347)
     CodeSrc src[3];
-    int n = 0;
+    const int n = code_srcs(e, src);
     const ss_hparams& h = e->hp;
-    if (g3) {
-        src[n++] = {e->l1.out[1], e->d_o1, h.dim_neck, h.freq, 0, (int)e->l1.ow()};
-        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 2 * h.dim_neck, (int)e->lt.ow()};
-        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck + 2 * h.dim_neck_2, (int)e->l2.ow()};
-        if (dec_compact(e))
-            HIPCHK(build_dec_in_compact(src, n, e->emb, h.dim_spk_emb, 2 * h.dim_neck + 2 * h.dim_neck_2 + 2 * h.dim_neck_3, e->ld.xc,
-                                        e->dec_in_dim, B, T, e->ld.xf, s));
-        else
-            HIPCHK(build_dec_in(src, n, e->emb, h.dim_spk_emb, 2 * h.dim_neck + 2 * h.dim_neck_2 + 2 * h.dim_neck_3, e->dec_in,
-                                e->dec_in_dim, B, T, s));
-    } else {
-        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 0, (int)e->lt.ow()};
-        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck_2, (int)e->l2.ow()};
-        if (dec_compact(e)) HIPCHK(build_dec_in_compact(src, n, nullptr, 0, e->dec_in_dim, e->ld.xc, e->dec_in_dim, B, T, e->ld.xf, s));
-        else HIPCHK(build_dec_in(src, n, nullptr, 0, e->dec_in_dim, e->dec_in, e->dec_in_dim, B, T, s));
-    }
-    CHK(lstm_fwd(e, e->ld, dec_compact(e) ? Slab{e->ld.xc, e->dec_in_dim} : Slab{e->dec_in, e->dec_in_dim}, s, lens));
+    const float* emb = g3 ? e->emb : nullptr;       // Generator_3: the speaker embedding fills the columns behind the three codes
+    const int emb_dim = g3 ? h.dim_spk_emb : 0, emb_col = g3 ? 2 * h.dim_neck + 2 * h.dim_neck_2 + 2 * h.dim_neck_3 : e->dec_in_dim;
+    if (dec_compact(e)) HIPCHK(build_dec_in_compact(src, n, emb, emb_dim, emb_col, e->ld.xc, e->dec_in_dim, B, T, e->ld.xf, s));
+    else HIPCHK(build_dec_in(src, n, emb, emb_dim, emb_col, e->dec_in, e->dec_in_dim, B, T, s));
+    CHK(lstm_fwd(e, e->ld, dec_x(e), s, lens));
     // LinearNorm head (model.py:253 / 277)
     const long HD = 2L * e->ld.H;
     GemmDesc d{};
     d.A = {e->ld.out[e->ld.L - 1] + HALO * HD, HD, TP * HD, 0, 0};
-    if (e->ld.out_img_valid)
-        d.a_pre = e->ioff(e->ld.out_img[e->ld.L - 1], HALO * HD);
+    if (e->ld.out_img_valid) d.a_pre = e->ioff(e->ld.out_img[e->ld.L - 1], HALO * HD);
     d.B = {e->P + e->head_w, HD, 0, 0, 0};
     d.C = e->out_slab + HALO * e->head_out;
     d.ldc = e->head_out;
@@ -2052,12 +2051,8 @@ int head_weight_grads(ss_engine* e, hipStream_t st) {
     a.flags = GEMM_TA | GEMM_TB | GEMM_ACCUM;
     a.ksplit = pick_ksplit(a.M, a.N, a.K);
     PGEMM_ON(SS_PROF_HEAD, a, st);
-    {
-        double* cpart;
-        unsigned* cctr;
-        colsum_scratch(e, e->head_out, &cpart, &cctr);
-        HIPCHK(colsum_acc(e->d_out_slab, e->head_out, (int)R, e->head_out, e->G + e->head_b, cpart, cctr, st));
-    }
+    const ColScratch cs = colsum_scratch(e, e->head_out);
+    HIPCHK(colsum_acc(e->d_out_slab, e->head_out, (int)R, e->head_out, e->G + e->head_b, cs.part, cs.ctr, st));
     CHK(dp_bucket(e, e->head_w, e->status_off - e->head_w, st));       // (the status slot behind it rides the step's last bucket)
     return 0;
 }
@@ -2076,15 +2071,14 @@ int backward_decoder(ss_engine* e, Backward& bw, hipStream_t s, bool late = fals
     e->bwd_accumulate = bw.accumulate;
     e->accum_count = bw.accumulate ? e->accum_count + 1 : 1;
     // fragment-major W_hh^T of the decoder recurrences (overwrites the forward layout, no longer needed), beside the head
-    const bool persist_dec = e->ld.big() && g_persist && lstm_seq_supported(e->curB, e->ld.H);
-    const bool prezeroed = e->fwd.bwd_sync_zeroed && persist_dec;       // the fused step's forward has done it on its branch stream
+    const bool prezeroed = e->fwd.bwd_sync_zeroed && e->ld.persist(e);       // the fused step's forward has done it on its branch stream
     e->fwd.bwd_sync_zeroed = false;
     const bool par = e->side2 && g_overlap && !prezeroed;
     hipStream_t b2 = par ? e->side2 : s;
     if (par) CHK(fork_join(e, s, b2));
     e->bwd = {};
     if (e->ld.big() && !prezeroed) {
-        if (g_persist && lstm_seq_supported(e->curB, e->ld.H)) {
+        if (e->ld.persist(e)) {
             // the group counters of every layer and their exchange tiles (tags start at 0)
             HIPCHK(hipMemsetAsync(e->ld.zb, 0, e->ld.zb_bytes, b2));
             if (e->wq_pool) HIPCHK(hipMemsetAsync(e->wq_pool, 0, ss_engine::WQ_SLOTS * 16, b2));
@@ -2096,27 +2090,24 @@ int backward_decoder(ss_engine* e, Backward& bw, hipStream_t s, bool late = fals
     // head.  Only its input gradient is on the critical path; when the decoder's weight gradients are deferred to the side
     // stream (lstm_bwd), the head's weight / bias gradients go with them instead of running in front of the first recurrence.
     const long HD = 2L * e->ld.H;
-    const bool defer_head = e->ld.big() && g_persist && lstm_seq_supported(B, e->ld.H) && e->side && g_overlap && g_defer_dw;
+    const bool defer_head = e->ld.defers_weights(e);
     late = late && defer_head;
     bw.dec_w_pending = late;
-    {
-        if (!defer_head) CHK(head_weight_grads(e, s));
-        GemmDesc g{};
-        g.A = {e->d_out_slab, e->head_out, 0, 0, 0};
-        g.B = {e->P + e->head_w, HD, 0, 0, 0};
-        g.C = e->d_top;
-        g.ldc = HD;
-        g.M = (int)R;
-        g.N = (int)HD;
-        g.K = e->head_out;
-        g.batch = 1;
-        g.flags = GEMM_TB;
-        g.ksplit = 1;
-        PGEMM_ON(SS_PROF_HEAD, g, s);
-    }
+    if (!defer_head) CHK(head_weight_grads(e, s));
+    GemmDesc g{};
+    g.A = {e->d_out_slab, e->head_out, 0, 0, 0};
+    g.B = {e->P + e->head_w, HD, 0, 0, 0};
+    g.C = e->d_top;
+    g.ldc = HD;
+    g.M = (int)R;
+    g.N = (int)HD;
+    g.K = e->head_out;
+    g.batch = 1;
+    g.flags = GEMM_TB;
+    g.ksplit = 1;
+    PGEMM_ON(SS_PROF_HEAD, g, s);
     if (par) CHK(fork_join(e, b2, s));
-    if (dec_compact(e)) CHK(lstm_bwd(e, bw, e->ld, e->d_top, Slab{e->ld.xc, e->dec_in_dim}, Slab{e->ld.d_xc, e->dec_in_dim}, s, nullptr, late));
-    else CHK(lstm_bwd(e, bw, e->ld, e->d_top, Slab{e->dec_in, e->dec_in_dim}, Slab{e->d_dec_in, e->dec_in_dim}, s, nullptr, late));
+    CHK(lstm_bwd(e, bw, e->ld, e->d_top, dec_x(e), dec_dx(e), s, nullptr, late));
     if (late) HIPCHK(hipEventRecord(e->ev_join[1], s));          // the chain is through: what the side stream's batch waits for
     else if (defer_head) CHK(head_weight_grads(e, e->side));      // behind the decoder's weight gradients, ordered after the chain by lstm_bwd's fork
                                                             // (measured: on the third branch stream instead 6.395 vs 6.365 ms)
@@ -2124,6 +2115,78 @@ int backward_decoder(ss_engine* e, Backward& bw, hipStream_t s, bool late = fals
     // status slot (part of the decoder bucket, so a data-parallel all-reduce carries it to every rank's Adam kernel)
     if (e->sticky) HIPCHK(status_publish(e->sticky, e->G + e->status_off, s));
     return 0;
+}
+
+// The early range's optimiser work (Backward::adam_early: one GPU, Adam inside the step) on the side stream, right behind the last of
+// the decoder's and the head's weight gradients
+int early_update(ss_engine* e, Backward& bw) {
+    if (!bw.adam_early || e->dp_on || !e->Mm || !e->Vv) return 0;
+    // every persistent recurrence and the parameter guard ran before the event this stream waited for: the status word is final
+    const long from = ss_grad_split(e);
+    if (e->clip_max > 0.0f) {
+        // clipping: no element may be updated before the norm of the whole arena is known -- this range's share of the sum
+        // of squares takes the early update's place beside the encoder backward (adam_enqueue finalises)
+        if (from == clip_split(e)) {
+            Prof pr(e, SS_PROF_ADAM, e->side);
+            HIPCHK(grad_sumsq(e->G, e->segs, from, e->status_off, e->clip_part + clip_wgs_lo(e), e->side));
+            bw.clip_early_from = from;
+        }
+    } else if (from % 4 == 0 && from < e->arena) {
+        HIPCHK(adam_prepare(e->adam, e->sticky, nullptr, e->side));
+        Prof pr(e, SS_PROF_ADAM, e->side);
+        HIPCHK(adam_range(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, bw.adam_gs, e->side));
+        bw.adam_early_from = from;
+    }
+    return 0;
+}
+
+// backward_decoder(late) left the decoder's and the head's weight gradients to backward_encoder, which enqueues them in pieces
+struct DecLate {
+    int next = -1;                                   // next decoder layer whose weight gradients are still to be enqueued
+    hipStream_t other[2] = {nullptr, nullptr};       // streams other than the side stream that carry some of them (tail split)
+};
+// the decoder's layers dl.next .. l_lo and, with its layer 0, the head's weight gradients, behind the decoder chain (ev_join[1]): on ws
+// (null: the side stream), the reverse direction's dW_ih / dW_hh on over_ih / over_hh where given (DwRoute)
+int dec_late(ss_engine* e, Backward& bw, DecLate& dl, int l_lo, hipStream_t ws = nullptr, hipStream_t over_ih = nullptr, hipStream_t over_hh = nullptr) {
+    if (dl.next < l_lo) return 0;
+    if (!ws) ws = e->side;
+    auto behind_chain = [&](hipStream_t o) -> int {      // a stream other than the side stream: noted for the join at the end
+        if (dl.other[0] != o && dl.other[1] != o) dl.other[dl.other[0] ? 1 : 0] = o;
+        HIPCHK(hipStreamWaitEvent(o, e->ev_join[1], 0));
+        return 0;
+    };
+    for (hipStream_t o : {over_ih, over_hh})
+        if (o && o != ws && o != e->side) CHK(behind_chain(o));
+    if (dl.next == e->ld.L - 1) HIPCHK(hipStreamWaitEvent(e->side, e->ev_join[1], 0));
+    if (ws != e->side) CHK(behind_chain(ws));
+    CHK(lstm_late_weights(e, bw, e->ld, dec_x(e), ws, dl.next, l_lo, {.over_ih = over_ih, .over_hh = over_hh}));
+    dl.next = l_lo - 1;
+    if (l_lo == 0) {
+        CHK(head_weight_grads(e, ws));
+        bw.dec_w_pending = false;
+        for (hipStream_t o : dl.other)
+            if (o) CHK(fork_join(e, o, e->side));      // one join for the end of the step; the early optimiser update reads what they wrote
+        CHK(early_update(e, bw));
+    }
+    e->side_used = true;
+    return 0;
+}
+
+// Tail split (g_dec_tail_split = m, one-GPU step): on the side stream alone the decoder's twelve weight-gradient GEMMs end ~450 us after every
+// other stream -- its last layers and the head go behind streams that end early instead.  s: main, b2: pitch, b3: third; null: the side stream
+struct TailSplit {
+    hipStream_t l2_hh, l1, l1_ih, l1_hh, l0;      // layer 2's reverse dW_hh; layer 1, its reverse dW_ih and dW_hh; layer 0 + head
+};
+TailSplit dec_tail_split(int m, hipStream_t s, hipStream_t b2, hipStream_t b3) {
+    TailSplit t{};
+    //                        m:        1        2        3    4        5        6
+    t.l1 = m == 4 || m == 5 ? b3 : (m == 6 ? b2 : nullptr);
+    t.l0 = m == 1 || m == 5 ? b2 : (m == 2 || m == 6 || m >= 7 ? b3 : (m == 3 ? s : nullptr));
+    // 7-9: as 2, and layer 1's reverse direction leaves the side stream as well: 7: dW_ih -> third, dW_hh -> pitch stream; 8: both -> third; 9: dW_hh -> third
+    t.l1_ih = m == 7 || m == 8 ? b3 : nullptr;
+    t.l1_hh = m == 7 ? b2 : (m == 8 || m == 9 || m == 10 ? b3 : nullptr);
+    t.l2_hh = m == 10 ? b3 : nullptr;      // 10: as 9, and layer 2's reverse dW_hh -> third as well
+    return t;
 }
 
 // everything below the decoder input: code gradients, encoder BLSTMs, conv trunks.  Touches only gradient-arena
@@ -2136,16 +2199,9 @@ int backward_encoder(ss_engine* e, Backward& bw, hipStream_t s) {
     const bool g3 = e->kind == SS_GENERATOR_3;
     const bool training = e->fwd.training;
     const ss_hparams& h = e->hp;
+    // ---- phase 1: code gradients and forks
     CodeSrc src[3];
-    int n = 0;
-    if (g3) {
-        src[n++] = {e->l1.out[1], e->d_o1, h.dim_neck, h.freq, 0, (int)e->l1.ow()};
-        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 2 * h.dim_neck, (int)e->lt.ow()};
-        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck + 2 * h.dim_neck_2, (int)e->l2.ow()};
-    } else {
-        src[n++] = {e->lt.out[0], e->d_ot, h.dim_neck_2, h.freq_2, 0, (int)e->lt.ow()};
-        src[n++] = {e->l2.out[0], e->d_o2, h.dim_neck_3, h.freq_3, 2 * h.dim_neck_2, (int)e->l2.ow()};
-    }
+    const int n = code_srcs(e, src);
     if (dec_compact(e)) HIPCHK(dec_in_grad_compact(src, n, e->ld.d_xc, e->dec_in_dim, B, T, e->ld.xf, s));
     else HIPCHK(dec_in_grad(src, n, e->d_dec_in, e->dec_in_dim, B, T, s));
     const int off2 = g3 ? h.dim_enc : 0;
@@ -2167,77 +2223,27 @@ int backward_encoder(ss_engine* e, Backward& bw, hipStream_t s) {
     CHK(zero_conv_grads(e, b2));                   // long done when the first conv weight gradient starts (b2 joins s, b3 forks after)
     if (prio && b3 != b2) CHK(fork_join(e, b2, b3));      // Encoder_t's conv weight gradient accumulates into its zeroed image before b3 sees lstm_2's event
     if (par && !prio) CHK(fork_join(e, b2, b3));
-    // encoder BLSTMs -> gradient of the last fused slab
+    // ---- phase 2: encoder BLSTM chains -> gradient of the last fused slab
     const bool early = par && !e->l2.big();         // the join event of the lstm_2 branch is taken as soon as its last kernel is queued
-    CHK(lstm_bwd(e, bw, e->l2, e->d_o2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, Slab{e->d_xf + off2, CE}, b2, (early || prio) ? e->ev_join[0] : nullptr, prio));
+    CHK(lstm_bwd(e, bw, e->l2, e->d_o2, trunk_in(e, 2, 3), Slab{e->d_xf + off2, CE}, b2, (early || prio) ? e->ev_join[0] : nullptr, prio));
     if (g3) {
-        CHK(lstm_bwd(e, bw, e->l1, e->d_o1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, Slab{e->d_xf, CE}, s, nullptr, prio));
+        CHK(lstm_bwd(e, bw, e->l1, e->d_o1, trunk_in(e, 1, 3), Slab{e->d_xf, CE}, s, nullptr, prio));
         if (prio) HIPCHK(hipEventRecord(e->ev_join[3], s));                 // lstm_1's chain done: its weight gradients may start
     }
     if (!prio) {
         // Encoder_t
-        CHK(lstm_bwd(e, bw, e->lt, e->d_ot, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, Slab{e->d_act_t, h.dim_enc_2}, b3));
+        CHK(lstm_bwd(e, bw, e->lt, e->d_ot, enc_t_out(e), Slab{e->d_act_t, h.dim_enc_2}, b3));
         CHK(conv_block_bwd(e, bw, e->ct, Slab{e->d_act_t, h.dim_enc_2}, Slab{e->org, h.dim_freq}, Slab{nullptr, 0}, b3));
     }
     if (early || prio) HIPCHK(hipStreamWaitEvent(s, e->ev_join[0], 0));
     else if (par) CHK(fork_join(e, b2, s));
-    // backward_decoder(late): the decoder's (layers l_hi .. l_lo) and, with its layer 0, the head's weight gradients, behind the decoder chain
-    int dec_next = bw.dec_w_pending ? e->ld.L - 1 : -1;       // next decoder layer whose weight gradients are still to be enqueued
-    hipStream_t dec_other[2] = {nullptr, nullptr};      // streams other than the side stream that carry decoder weight gradients (tail split)
-    auto dec_late = [&](int l_lo, hipStream_t ws = nullptr, hipStream_t over_ih = nullptr, hipStream_t over_hh = nullptr) -> int {
-        if (dec_next < l_lo) return 0;
-        if (!ws) ws = e->side;
-        for (hipStream_t o : {over_ih, over_hh})
-            if (o && o != ws && o != e->side) {
-                if (dec_other[0] != o && dec_other[1] != o) dec_other[dec_other[0] ? 1 : 0] = o;
-                HIPCHK(hipStreamWaitEvent(o, e->ev_join[1], 0));
-            }
-        if (dec_next == e->ld.L - 1) HIPCHK(hipStreamWaitEvent(e->side, e->ev_join[1], 0));
-        if (ws != e->side) {
-            if (dec_other[0] != ws && dec_other[1] != ws) dec_other[dec_other[0] ? 1 : 0] = ws;
-            HIPCHK(hipStreamWaitEvent(ws, e->ev_join[1], 0));
-        }
-        DwRoute route;
-        route.over_ih = over_ih;
-        route.over_hh = over_hh;
-        CHK(lstm_late_weights(e, bw, e->ld, dec_compact(e) ? Slab{e->ld.xc, e->dec_in_dim} : Slab{e->dec_in, e->dec_in_dim}, ws, dec_next, l_lo, route));
-        dec_next = l_lo - 1;
-        if (l_lo == 0) {
-            CHK(head_weight_grads(e, ws));
-            bw.dec_w_pending = false;
-            for (hipStream_t o : dec_other)
-                if (o) CHK(fork_join(e, o, e->side));      // one join for the end of the step; the early optimiser update below reads what they wrote
-            if (bw.adam_early && !e->dp_on && e->Mm && e->Vv) {
-                // every persistent recurrence and the parameter guard ran before the event this stream waited for: the status word is final
-                const long from = ss_grad_split(e);
-                if (e->clip_max > 0.0f) {
-                    // clipping: no element may be updated before the norm of the whole arena is known -- this range's share of the sum
-                    // of squares takes the early update's place beside the encoder backward (adam_enqueue finalises)
-                    if (from == clip_split(e)) {
-                        {
-                            Prof pr(e, SS_PROF_ADAM, e->side);
-                            HIPCHK(grad_sumsq(e->G, e->segs, from, e->status_off, e->clip_part + clip_wgs_lo(e), e->side));
-                        }
-                        bw.clip_early_from = from;
-                    }
-                } else if (from % 4 == 0 && from < e->arena) {
-                    HIPCHK(adam_prepare(e->adam, e->sticky, nullptr, e->side));
-                    {
-                        Prof pr(e, SS_PROF_ADAM, e->side);
-                        HIPCHK(adam_range(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, bw.adam_gs, e->side));
-                    }
-                    bw.adam_early_from = from;
-                }
-            }
-        }
-        e->side_used = true;
-        return 0;
-    };
+    // ---- phase 3: conv trunk, last layer first (data parallel: the decoder's late weight gradients between its layers)
+    DecLate dl{bw.dec_w_pending ? e->ld.L - 1 : -1};
     // Data parallel: the communication stream executes its collectives in the order they are ENQUEUED, so the buckets are enqueued in the
     // order they become final -- decoder layer L-1, trunk layer 2, decoder layer L-2, trunk layer 1, the rest of the decoder + head --
     // instead of every decoder bucket in front of (or behind) every trunk bucket.  (One GPU: the decoder's weight gradients stay behind
     // the trunk in enqueue order, see prio_order.)
-    if (e->dp_on) CHK(dec_late(e->ld.L - 1));
+    if (e->dp_on) CHK(dec_late(e, bw, dl, e->ld.L - 1));
     // Encoder_7's content (512 ch) and pitch (256 ch) stacks are independent chains in the backward as in the forward (forward_core):
     // each block's output gradient comes from its own BLSTM / its own upper block, its input gradient goes to its own lower block, and the two
     // write disjoint columns of the shared slabs.  The pitch chain never leaves the stream lstm_2's backward ran on (second branch stream), beside the
@@ -2253,7 +2259,6 @@ int backward_encoder(ss_engine* e, Backward& bw, hipStream_t s) {
     // weight gradients off the dependent chain (g_conv_dw_off): Generator_6's single chain, the second branch stream is idle behind lstm's backward
     const bool dw_off = g_conv_dw_off == 1 && training && !g3 && par && prio && !e->dp_on && g_gn_gather && bw.unpack_later && b2 != s && e->d_act_l[0] && e->d_act_l[1];
     hipStream_t dw_s = dw_off ? b2 : nullptr;
-    // conv trunk, last layer first
     for (int i = 2; i >= 0; --i) {
         float* dy = e->d_xf;
         // training: the adjoint of the layer's resampling, d_xf -> d_act; fused into each block's GroupNorm backward (g_gn_gather) or as a pass of its own
@@ -2269,61 +2274,50 @@ int backward_encoder(ss_engine* e, Backward& bw, hipStream_t s) {
         // the resampled activations also exist as pre-split images when the forward's gathers wrote them (training, independent trunk chains)
         const float* bim = (training && e->fwd.xf_img_valid && i > 0) ? e->xf_img[i - 1] : nullptr;
         if (!chain_par && i == 0 && g3 && par && !e->dp_on) CHK(fork_join(e, s, b2));      // tail_par below: the pitch block's stream forks BEFORE the content block is enqueued
-        if (g3) {
-            Slab x1 = i == 0 ? Slab{e->in_mel, h.dim_freq} : Slab{e->xf[i - 1], CE, bim, e->act_scale + e->c1[i - 1].scale_i};
-            CHK(conv_block_bwd(e, bw, e->c1[i], Slab{dy, CE}, x1, i > 0 ? Slab{dxbuf, CE} : Slab{nullptr, 0}, s, sc, sc_src, CE));
-        }
-        Slab x2 = i == 0 ? Slab{e->in_f0, e->f0p} : Slab{e->xf[i - 1] + off2, CE, bim ? e->ioff(bim, off2) : nullptr, e->act_scale + e->c2[i - 1].scale_i};
+        if (g3) CHK(conv_block_bwd(e, bw, e->c1[i], Slab{dy, CE}, trunk_in(e, 1, i, bim), i > 0 ? Slab{dxbuf, CE} : Slab{}, s, {.scatter = sc, .src = sc_src, .src_ld = CE}));
         // Layer 0 is the step's tail: the decoder's weight gradients are through by then, and each of its two weight-gradient GEMMs alone
         // fills half the chip's workgroup slots -- the pitch block runs on the second branch stream beside the content block.  (Not under
         // data parallelism, where that stream carries the collectives.)
         const bool tail_par = chain_par || (i == 0 && g3 && par && !e->dp_on);
         hipStream_t s2 = tail_par ? (chain_par ? cs : b2) : s;
-        CHK(conv_block_bwd(e, bw, e->c2[i], Slab{dy + off2, CE}, x2, i > 0 ? Slab{dxbuf + off2, CE} : Slab{nullptr, 0}, s2, sc, sc_src + off2, CE, (dw_off && i > 0) ? dw_s : nullptr));
+        CHK(conv_block_bwd(e, bw, e->c2[i], Slab{dy + off2, CE}, trunk_in(e, 2, i, bim), i > 0 ? Slab{dxbuf + off2, CE} : Slab{}, s2,
+                           {.scatter = sc, .src = sc_src + off2, .src_ld = CE, .dws = (dw_off && i > 0) ? dw_s : nullptr}));
         if (tail_par && (!chain_par || (i == 0 && !e->dp_on))) CHK(fork_join(e, b2, s));      // (chain_par: the two chains meet once, behind layer 0; data parallel: where the third branch stream joins below)
         if (i > 0) {           // the two wide layers' parameters (weight, bias, GroupNorm affine: contiguous) are final; layer 0 rides the last bucket
             if (g3) CHK(dp_bucket(e, e->c1[i].w, e->c1[i].be + e->c1[i].Co - e->c1[i].w, s));
             CHK(dp_bucket(e, e->c2[i].w, e->c2[i].be + e->c2[i].Co - e->c2[i].w, s2));
-            if (e->dp_on) CHK(dec_late(i == 2 ? (e->ld.L >= 3 ? e->ld.L - 2 : 0) : 0));      // next decoder layer(s) behind this trunk layer's buckets
+            if (e->dp_on) CHK(dec_late(e, bw, dl, i == 2 ? (e->ld.L >= 3 ? e->ld.L - 2 : 0) : 0));      // next decoder layer(s) behind this trunk layer's buckets
         }
         if (!training && i > 0) {
             // eval mode has no resampling between layers: the next (lower) layer reads its output gradient from d_xf
             HIPCHK(hipMemcpyAsync(e->d_xf, e->d_act, R * CE * 4, hipMemcpyDeviceToDevice, s));
         }
     }
-    // ---- everything that only has to be finished by the end of the step
-    // (tail split: on the side stream alone the decoder's twelve weight-gradient GEMMs end ~450 us after every other stream -- its last layer and
-    // the head go behind a stream that ends early instead)
+    // ---- phase 4: everything that only has to be finished by the end of the step
     if (!e->dp_on && prio && chain_par && bw.dec_w_pending && e->ld.L == 3 && g_dec_tail_split) {
-        const int m = g_dec_tail_split;
-        //                              m:        1        2        3    4        5        6
-        hipStream_t for_l1 = m == 4 || m == 5 ? b3 : (m == 6 ? b2 : nullptr);                    // layer 1 (nullptr: side stream)
-        hipStream_t for_l0 = m == 1 || m == 5 ? b2 : (m == 2 || m == 6 || m >= 7 ? b3 : (m == 3 ? s : nullptr));   // layer 0 + head
-        // 7-9: as 2, and layer 1's reverse direction leaves the side stream as well: 7: dW_ih -> third, dW_hh -> pitch stream; 8: both -> third; 9: dW_hh -> third
-        hipStream_t l1_ih = m == 7 || m == 8 ? b3 : nullptr, l1_hh = m == 7 ? b2 : (m == 8 || m == 9 ? b3 : nullptr);
-        CHK(dec_late(2, nullptr, nullptr, m == 10 ? b3 : nullptr));      // 10: as 9, and layer 2's reverse dW_hh -> third as well
-        if (m == 10) l1_hh = b3;
-        CHK(dec_late(1, for_l1, l1_ih, l1_hh));
-        CHK(dec_late(0, for_l0));
-        if (for_l1 == b2 || for_l0 == b2 || l1_hh == b2) CHK(fork_join(e, b2, s));
+        const TailSplit t = dec_tail_split(g_dec_tail_split, s, b2, b3);
+        CHK(dec_late(e, bw, dl, 2, nullptr, nullptr, t.l2_hh));
+        CHK(dec_late(e, bw, dl, 1, t.l1, t.l1_ih, t.l1_hh));
+        CHK(dec_late(e, bw, dl, 0, t.l0));
+        if (t.l1 == b2 || t.l0 == b2 || t.l1_hh == b2) CHK(fork_join(e, b2, s));
     }
-    CHK(dec_late(0));
+    CHK(dec_late(e, bw, dl, 0));
     if (prio) {
         // Encoder_t's backward first: its input (d_ot from dec_in_grad) is the earliest thing this stream waits for, and it is a dependent chain of
         // five launches; the BLSTMs' weight gradients (all three blocks: ONE fused launch) only have to be done by the end of the step
         // (Generator_6 32 x 192 bf16 2.26 -> 2.23 ms, 16 x 128 3.20 -> 3.18 against the BLSTMs' weight gradients in front; headline unchanged)
         HIPCHK(hipStreamWaitEvent(b3, e->ev_join[2], 0));                   // d_ot from dec_in_grad
-        CHK(lstm_bwd(e, bw, e->lt, e->d_ot, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, Slab{e->d_act_t, h.dim_enc_2}, b3));
+        CHK(lstm_bwd(e, bw, e->lt, e->d_ot, enc_t_out(e), Slab{e->d_act_t, h.dim_enc_2}, b3));
         CHK(conv_block_bwd(e, bw, e->ct, Slab{e->d_act_t, h.dim_enc_2}, Slab{e->org, h.dim_freq}, Slab{nullptr, 0}, b3));
         HIPCHK(hipStreamWaitEvent(b3, e->ev_join[0], 0));                   // lstm_2's pre-activation gradients (and the zeroed conv images)
-        CHK(lstm_late_weights(e, bw, e->l2, Slab{e->xf[2] + off2, CE, nullptr, e->act_scale + e->c2[2].scale_i}, b3));
+        CHK(lstm_late_weights(e, bw, e->l2, trunk_in(e, 2, 3), b3));
         if (g3) {
             HIPCHK(hipStreamWaitEvent(b3, e->ev_join[3], 0));
-            CHK(lstm_late_weights(e, bw, e->l1, Slab{e->xf[2], CE, nullptr, e->act_scale + e->c1[2].scale_i}, b3));
+            CHK(lstm_late_weights(e, bw, e->l1, trunk_in(e, 1, 3), b3));
         }
         CHK(wgrad_flush(e, bw, b3));               // Encoder_t's, lstm_2's and both layers of lstm_1's: one launch
     }
-
+    // ---- phase 5: joins
     if (par) CHK(fork_join(e, b3, s));
     if (dw_off) CHK(fork_join(e, dw_s, s));
     CHK(join_side(e, s));
@@ -2767,14 +2761,18 @@ static int g3_rhythm(ss_engine* e, const float* x_org, const int* lens, int B, i
     CHK(lstm_prep(e, e->lt, tb, s));
     HIPCHK(prep_run(tb, s));
     CHK(act_scales_all(e, s));
-    CHK(conv_block_fwd(e, e->ct, Slab{e->org, h.dim_freq}, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, s, nullptr, nullptr, 0, nullptr, nullptr, lens));
-    CHK(lstm_fwd(e, e->lt, Slab{e->act_t, h.dim_enc_2, nullptr, e->act_scale + e->ct.scale_i}, s, lens));
+    CHK(conv_block_fwd(e, e->ct, Slab{e->org, h.dim_freq}, enc_t_out(e), s, {.lens = lens}));
+    CHK(lstm_fwd(e, e->lt, enc_t_out(e), s, lens));
     // (ragged: the recurrence left zeros behind every row's end, so the codes of the padded blocks come out as zeros without a predicate)
     // codes = cat(fwd[:, 7::8], bwd[:, ::8]) (model.py:84-87): reuse the decoder-input assembler on a 2H-wide row (in d_ot's own geometry:
     // padding columns written zero, halo rows untouched) and pick t % freq == 0
     const int W = 2 * h.dim_neck_2;
     const long OW = e->lt.ow();
-    CodeSrc src{e->lt.out[0], nullptr, h.dim_neck_2, h.freq_2, 0, (int)OW};
+    CodeSrc tab[3];
+    code_srcs(e, tab);
+    CodeSrc src = tab[1];           // Encoder_t's row of the table (Generator_3), here alone at column 0 and without a gradient slab
+    src.d_o = nullptr;
+    src.col = 0;
     HIPCHK(build_dec_in(&src, 1, nullptr, 0, W, e->d_ot, (int)OW, B, T, s));
     HIPCHK(copy_rows(e->d_ot + HALO * OW, (long)h.freq_2 * OW, TP * OW, codes, W, (long)(T / h.freq_2) * W, B, T / h.freq_2, W, s));
     e->fwd.have = false;
@@ -3354,8 +3352,7 @@ int ss_debug_relu_mask(ss_engine* e, const char* block, float* mask, void* strea
     if (!e->curB) return fail("ss_debug_relu_mask: no forward has run");
     auto it = e->dbg.find(std::string(block) + ".conv");
     if (it == e->dbg.end()) return fail(std::string("ss_debug_relu_mask: no such conv block: ") + block);
-    ConvBlk* all[7] = {&e->c1[0], &e->c1[1], &e->c1[2], &e->c2[0], &e->c2[1], &e->c2[2], &e->ct};
-    for (ConvBlk* cb : all)
+    for (ConvBlk* cb : conv_blocks(*e))
         if (cb->Co && cb->cout == it->second.first) {
             const long TP = e->curT + 2 * HALO;
             HIPCHK(gn_relu_mask(cb->cout, cb->Co, TP * cb->Co, e->P + cb->ga, e->P + cb->be, cb->stats, mask, e->curB, e->curT,
@@ -3427,7 +3424,7 @@ static int op_conv_block(const float* x, const float* w, const float* bias, cons
     HIPCHK(hipMemcpyAsync(e.P + cb.be, beta, Co * 4L, hipMemcpyDeviceToDevice, s));
     HIPCHK(copy_rows(x, Ci, (long)T * Ci, xs + HALO * cb.Cp, cb.Cp, TP * cb.Cp, B, T, Ci, s, len));
     CHK(conv_pack_all(&e, cb, s));
-    CHK(conv_block_fwd(&e, cb, Slab{xs, cb.Cp}, Slab{ys, Co}, s, nullptr, nullptr, 0, nullptr, nullptr, len));
+    CHK(conv_block_fwd(&e, cb, Slab{xs, cb.Cp}, Slab{ys, Co}, s, {.lens = len}));
     HIPCHK(copy_rows(ys + HALO * Co, Co, TP * Co, y, Co, (long)T * Co, B, T, Co, s));
     if (dy) {
         if (!gw || !gb || !ggamma || !gbeta) return fail("ss_op_conv_block: backward needs the gradient outputs");
