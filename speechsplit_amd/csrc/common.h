@@ -123,7 +123,7 @@ hipError_t gemm_phase_probe(unsigned long long out[24], bool reset);
 // series for tanh where the quotient form would cancel: a few ulp.
 #ifdef __HIPCC__
 // operand with a measured maximum m: the power of two that brings m into [128, 256) (256x headroom below fp16's 65504), capped
-// so that an all-zero / denormal tensor cannot produce an infinite scale (same rule as gemm_bf16x3.hip's pow2_scale)
+// at 2^60 so that an all-zero / denormal tensor cannot produce an infinite scale
 __device__ __forceinline__ float pow2_scale_of(float m) {
     const int e = (int)((__float_as_uint(m) >> 23) & 0xFFu);
     int se = 261 - e;
@@ -146,10 +146,9 @@ __device__ __forceinline__ float ss_lerp_rn(float ol, float a, float l, float b)
     const float q = l * b;
     return p + q;
 }
-// Four consecutive values -> packed fp16 pieces of 16 x the values, (h0 h1, h2 h3, l0 l1, l2 l3), h = fp16(16 v) to nearest,
-// l = fp16(16 v - h) -- exactly what the GEMM's in-loop split produces with its fixed scale.  ss_store_group puts them into an image.
-__device__ __forceinline__ uint4 ss_split_group(float v0, float v1, float v2, float v3) {
-    const float s = 16.0f;
+// Four consecutive values -> packed fp16 pieces of s x the values (s a power of two), (h0 h1, h2 h3, l0 l1, l2 l3), h = fp16(s v) to
+// nearest, l = fp16(s v - h) -- exactly what the GEMM's in-loop split produces.  ss_store_group puts them into an image.
+__device__ __forceinline__ uint4 ss_split_group_s(float v0, float v1, float v2, float v3, float s) {
     uint4 r;
     asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(r.x) : "v"(v0), "v"(s));
     asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(r.x) : "v"(v1), "v"(s));
@@ -174,8 +173,6 @@ __device__ __forceinline__ void ss_store_group(float* at, uint4 g) {
 // Four consecutive values into an image at ELEMENT index `elem` from the image's base.  bf16 == 0: format v2 (fp16 x 2 pieces of scale * v);
 // bf16 != 0 (the 16-bit data path, SS_PRECISION_BF16): the image is the plain bf16 tensor -- 8 bytes at 2 * elem, round to nearest even
 // (v_cvt_pk_bf16_f32; a NaN stays a NaN), no scale.
-__device__ __forceinline__ uint4 ss_split_group_s(float v0, float v1, float v2, float v3, float s);
-__device__ __forceinline__ void ss_store_group(float* at, uint4 g);
 __device__ __forceinline__ uint2 ss_pack_bf16x4(float v0, float v1, float v2, float v3) {
     typedef __bf16 bf2_t __attribute__((ext_vector_type(2)));
     typedef float f2_t __attribute__((ext_vector_type(2)));
@@ -185,19 +182,6 @@ __device__ __forceinline__ uint2 ss_pack_bf16x4(float v0, float v1, float v2, fl
 __device__ __forceinline__ void ss_store_img4(float* img, long elem, float v0, float v1, float v2, float v3, float scale, int bf16) {
     if (bf16) *reinterpret_cast<uint2*>(reinterpret_cast<char*>(img) + 2 * elem) = ss_pack_bf16x4(v0, v1, v2, v3);
     else ss_store_group(img + elem, ss_split_group_s(v0, v1, v2, v3, scale));
-}
-// the same with a caller-supplied power-of-two scale
-__device__ __forceinline__ uint4 ss_split_group_s(float v0, float v1, float v2, float v3, float s) {
-    uint4 r;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(r.x) : "v"(v0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(r.x) : "v"(v1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(r.y) : "v"(v2), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(r.y) : "v"(v3), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r.z) : "v"(v0), "v"(s), "v"(r.x));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(r.z) : "v"(v1), "v"(s), "v"(r.x));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r.w) : "v"(v2), "v"(s), "v"(r.y));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(r.w) : "v"(v3), "v"(s), "v"(r.y));
-    return r;
 }
 // sigmoid: 1 / (1 + 2^(-x log2 e)) on the hardware exp2 / rcp (1 ulp each).  The product x * log2(e) rounded to fp32 puts a RELATIVE error of
 // |x| * 9e-8 into e^-x; relative to the sigmoid that is weighted by e^-x / (1 + e^-x), so the ABSOLUTE error stays below 2 ulp of the result's

@@ -1045,9 +1045,12 @@ __global__ __launch_bounds__(256) void adam_prepare_clip_kernel(AdamState* st, C
 
 }  // namespace
 
-hipError_t gn_relu_fwd(const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, const float* gamma,
-                       const float* beta, float* stats, int B, int T, int C, hipStream_t s, double* scratch, const int* len) {
+hipError_t gn_relu_fwd(CRows xr, Rows yr, const float* gamma, const float* beta, float* stats, int B, int T, int C, hipStream_t s, double* scratch,
+                       const int* len) {
     if (C % 64 != 0 || T < 1) return hipErrorInvalidValue;
+    const float* x = xr.row0();           // the kernels add the halo themselves
+    float* y = yr.row0();
+    const long x_ld = xr.ld, x_bs = xr.bs, y_ld = yr.ld, y_bs = yr.bs;
     if (T <= 16 * GN_MAXIT) {
         if (len)
             hipLaunchKernelGGL(gn_relu_fwd_kernel<true>, dim3(C / 64, B), dim3(256), 0, s, x, x_ld, x_bs, y, y_ld, y_bs, gamma, beta, stats, len, T, C);
@@ -1079,28 +1082,30 @@ long gn_relu_fwd_scratch_bytes(int B, int T, int C) {
     return 2L * B * (C / 16) * ((T + GN_CHUNK - 1) / GN_CHUNK) * (long)sizeof(double);
 }
 
-hipError_t gn_relu_gather(const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, float* y_img, const float* img_scale,
-                          const float* gamma, const float* beta, float* stats, const InterpPlan& p, int B, int T, int C, hipStream_t s, int img_bf16) {
-    if (C % 64 != 0 || T > 16 * GN_MAXIT || p.T != T || y_ld % 4 || y_bs % 4 || (((size_t)y) & 15)) return hipErrorInvalidValue;
-    if (y_img && (y_ld % 8 || y_bs % 8 || (((size_t)y_img) & (img_bf16 ? 15 : 31)))) y_img = nullptr;             // image format v2: groups of eight (bf16: 16-byte fragments)
+hipError_t gn_relu_gather(CRows x, Rows y, const float* gamma, const float* beta, float* stats, const InterpPlan& p, int B, int T, int C, hipStream_t s,
+                          const GnGather& o) {
+    if (C % 64 != 0 || T > 16 * GN_MAXIT || p.T != T || y.ld % 4 || y.bs % 4 || (((size_t)y.p) & 15)) return hipErrorInvalidValue;
+    float* y_img = o.y_img;
+    if (y_img && (y.ld % 8 || y.bs % 8 || (((size_t)y_img) & (o.img_bf16 ? 15 : 31)))) y_img = nullptr;             // image format v2: groups of eight (bf16: 16-byte fragments)
     const int lds = (T + 1) * 64 * 4;
     auto kern = T <= 128 ? gn_relu_gather_kernel<8> : (T <= 192 ? gn_relu_gather_kernel<12> : gn_relu_gather_kernel<GN_MAXIT>);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(C / 64, B), dim3(256), lds, s, x, x_ld, x_bs, y, y_ld, y_bs, y_img, img_scale, gamma, beta,
-                       stats, T, C, p.P, p.i0, p.lam, p.nrows, img_bf16);
+    hipLaunchKernelGGL(kern, dim3(C / 64, B), dim3(256), lds, s, x.row0(), x.ld, x.bs, y.p, y.ld, y.bs, y_img, o.img_scale, gamma, beta,
+                       stats, T, C, p.P, p.i0, p.lam, p.nrows, o.img_bf16 ? 1 : 0);
     return hipGetLastError();
 }
 
-hipError_t gn_relu_bwd(const float* x, long x_ld, long x_bs, float* dy, long dy_ld, long dy_bs, const float* gamma,
-                       const float* beta, const float* stats, float* g_gamma, float* g_beta, float* g_bias, float* amax, float* part,
-                       int B, int T, int C, hipStream_t s, const InterpPlan* scatter, const float* src, long src_ld, long src_bs, float* dy_img) {
+hipError_t gn_relu_bwd(CRows x, Rows dy, const float* gamma, const float* beta, const float* stats, float* g_gamma, float* g_beta, float* g_bias, int B,
+                       int T, int C, hipStream_t s, const GnBwd& o) {
+    const InterpPlan* scatter = o.scatter;
+    const CRows src = o.src;
     if (C % 64 != 0 || T > 16 * GN_MAXIT) return hipErrorInvalidValue;
-    if (dy_img && (dy_ld % 8 || dy_bs % 8 || (((size_t)dy_img) & 7))) return hipErrorInvalidValue;
-    if (scatter && (!src || scatter->T != T || scatter->P > 16 * GN_MAXIT + 2 || src_ld % 4 || src_bs % 4 || (((size_t)src) & 15))) return hipErrorInvalidValue;
-    if (!g_deterministic) part = nullptr;      // per-utterance sums to scratch + ordered reduce only where the order matters; f32 atomics otherwise
+    if (o.dy_img && (dy.ld % 8 || dy.bs % 8 || (((size_t)o.dy_img) & 7))) return hipErrorInvalidValue;
+    if (scatter && (!src.p || scatter->T != T || scatter->P > 16 * GN_MAXIT + 2 || src.ld % 4 || src.bs % 4 || (((size_t)src.p) & 15))) return hipErrorInvalidValue;
+    float* part = g_deterministic ? o.part : nullptr;      // per-utterance sums to scratch + ordered reduce only where the order matters; f32 atomics otherwise
     // (an 8-iteration instantiation for T <= 128 makes hipcc hoist every source-row load: 418 registers unbounded, spills when bounded)
     auto kern = T <= 192 ? gn_relu_bwd_kernel<12> : gn_relu_bwd_kernel<GN_MAXIT>;
     const int lds = scatter ? scatter->P * 64 * 4 : 0;                    // the utterance's source rows of the block's 64 channels
@@ -1108,18 +1113,17 @@ hipError_t gn_relu_bwd(const float* x, long x_ld, long x_bs, float* dy, long dy_
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(C / 64, B), dim3(256), lds, s, x, x_ld, x_bs, dy, dy_ld, dy_bs, gamma, beta,
-                       stats, g_gamma, g_beta, g_bias, reinterpret_cast<unsigned*>(amax), part, B, T, C, scatter ? src : nullptr, src_ld, src_bs,
-                       scatter ? scatter->P : 0, scatter ? scatter->lam : nullptr, scatter ? scatter->start : nullptr, dy_img);
+    hipLaunchKernelGGL(kern, dim3(C / 64, B), dim3(256), lds, s, x.row0(), x.ld, x.bs, dy.row0(), dy.ld, dy.bs, gamma, beta,
+                       stats, g_gamma, g_beta, g_bias, reinterpret_cast<unsigned*>(o.amax), part, B, T, C, scatter ? src.p : nullptr, src.ld, src.bs,
+                       scatter ? scatter->P : 0, scatter ? scatter->lam : nullptr, scatter ? scatter->start : nullptr, o.dy_img);
     if (part) hipLaunchKernelGGL(gn_part_reduce_kernel, dim3(cdiv(3 * C, 256)), dim3(256), 0, s, part, B, C, g_gamma, g_beta, g_bias);
     return hipGetLastError();
 }
 
-hipError_t gn_relu_mask(const float* x, long x_ld, long x_bs, const float* gamma, const float* beta, const float* stats,
-                        float* mask, int B, int T, int C, hipStream_t s) {
+hipError_t gn_relu_mask(CRows x, const float* gamma, const float* beta, const float* stats, float* mask, int B, int T, int C, hipStream_t s) {
     int gx = cdiv((long)T * C, 256 * 4);
     if (gx < 1) gx = 1;
-    hipLaunchKernelGGL(gn_relu_mask_kernel, dim3(gx, B), dim3(256), 0, s, x, x_ld, x_bs, gamma, beta, stats, mask, T, C);
+    hipLaunchKernelGGL(gn_relu_mask_kernel, dim3(gx, B), dim3(256), 0, s, x.row0(), x.ld, x.bs, gamma, beta, stats, mask, T, C);
     return hipGetLastError();
 }
 
@@ -1148,12 +1152,11 @@ hipError_t colsum_bias(const float* in, long ld, int R, int C, float* bih0, floa
     return colsum_launch(in, ld, R, C, 2 * C, part, ctr, bih0, bhh0, bih1, bhh1, s);
 }
 
-hipError_t copy_rows(const float* src, long s_ld, long s_bs, float* dst, long d_ld, long d_bs, int B, int T, int C,
-                     hipStream_t s, const int* len) {
+hipError_t copy_rows(CRows src, Rows dst, int B, int T, int C, hipStream_t s, const int* len) {
     int gx = cdiv((long)T * C, 256);
     if (gx > 64) gx = 64;
-    if (len) hipLaunchKernelGGL(copy_rows_kernel<true>, dim3(gx, B), dim3(256), 0, s, src, s_ld, s_bs, dst, d_ld, d_bs, len, T, C);
-    else hipLaunchKernelGGL(copy_rows_kernel<false>, dim3(gx, B), dim3(256), 0, s, src, s_ld, s_bs, dst, d_ld, d_bs, len, T, C);
+    if (len) hipLaunchKernelGGL(copy_rows_kernel<true>, dim3(gx, B), dim3(256), 0, s, src.p, src.ld, src.bs, dst.p, dst.ld, dst.bs, len, T, C);
+    else hipLaunchKernelGGL(copy_rows_kernel<false>, dim3(gx, B), dim3(256), 0, s, src.p, src.ld, src.bs, dst.p, dst.ld, dst.bs, len, T, C);
     return hipGetLastError();
 }
 
@@ -1251,20 +1254,18 @@ hipError_t dec_in_grad(const CodeSrc* src, int nsrc, const float* d_dec_in, int 
     return hipGetLastError();
 }
 
-hipError_t mse_loss(const float* out, long o_ld, long o_bs, const float* tgt, long t_ld, long t_bs, float* d_out, long d_ld,
-                    long d_bs, int B, int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s) {
+hipError_t mse_loss(CRows out, CRows tgt, Rows d_out, int B, int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s) {
     const int gx = 8;
     const double n = (double)B * T * C;
-    hipLaunchKernelGGL(mse_kernel, dim3(gx, B), dim3(256), 0, s, out, o_ld, o_bs, tgt, t_ld, t_bs, d_out, d_ld, d_bs, T, C,
+    hipLaunchKernelGGL(mse_kernel, dim3(gx, B), dim3(256), 0, s, out.p, out.ld, out.bs, tgt.p, tgt.ld, tgt.bs, d_out.p, d_out.ld, d_out.bs, T, C,
                        (float)(2.0 / n) * grad_scale, partials);
     hipLaunchKernelGGL(finish_loss_kernel, dim3(1), dim3(256), 0, s, partials, gx * B, (float)(1.0 / n), loss);
     return hipGetLastError();
 }
 
-hipError_t ce_loss(const float* logits, long o_ld, long o_bs, const int* tgt, float* d_out, long d_ld, long d_bs, int B,
-                   int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s) {
+hipError_t ce_loss(CRows logits, const int* tgt, Rows d_out, int B, int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s) {
     const double n = (double)B * T;
-    hipLaunchKernelGGL(ce_kernel, dim3(T, B), dim3(64), 0, s, logits, o_ld, o_bs, tgt, d_out, d_ld, d_bs, T, C,
+    hipLaunchKernelGGL(ce_kernel, dim3(T, B), dim3(64), 0, s, logits.p, logits.ld, logits.bs, tgt, d_out.p, d_out.ld, d_out.bs, T, C,
                        (float)(1.0 / n) * grad_scale, partials);
     hipLaunchKernelGGL(finish_loss_kernel, dim3(1), dim3(256), 0, s, partials, B * T, (float)(1.0 / n), loss);
     return hipGetLastError();

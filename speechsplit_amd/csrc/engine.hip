@@ -183,6 +183,7 @@ struct Slab {   // view of a haloed slab: p points at slab row 0, first channel 
     long ld = 0;
     const float* img = nullptr;      // the slab's pre-split image at the same position, if its producer wrote one (GemmDesc::a_pre / b_pre)
     const float* scale = nullptr;    // device word: power-of-two scale of the fp16 x 2 split of this slab's values (null: 16); conv-block outputs carry one
+    Rows rows(int T) const { return Rows::slab(p, ld, T); }      // its T real frames, as the launchers of kernels.h take them
 };
 
 // What the functions of ONE backward pass (and the optimiser step behind it) tell each other.  The ABI entry point makes one on its stack
@@ -1186,10 +1187,10 @@ float* grad_img_of(ss_engine* e, const float* p, long R) {
 // y = relu(GN(conv5(x)))   x: slab view (ld), y: slab view
 struct ConvFwd {
     // gather (nullable): the resampling plan of the training forward -- GroupNorm + ReLU + gather in one kernel straight into gy / gy_img (the
-    // resampled slab and its image at the first real row and the block's first column), behind gather_ready (nullable); y is then not written
+    // resampled slab from the block's first column on, and its image at gy's position), behind gather_ready (nullable); y is then not written
     const InterpPlan* gather = nullptr;
-    float *gy = nullptr, *gy_img = nullptr;
-    long gy_ld = 0;
+    Rows gy;
+    float* gy_img = nullptr;
     hipEvent_t gather_ready = nullptr;
     // lens (nullable; eval-mode forwards only): per-row lengths of a ragged batch, device i32[B] -- the GroupNorm takes its statistics over each
     // row's own frames and writes zeros behind them (the convolution itself is row-wise over a slab whose padded rows its producer zeroed)
@@ -1219,8 +1220,8 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
     if (o.gather) {
         if (o.gather_ready) HIPCHK(hipStreamWaitEvent(s, o.gather_ready, 0));
         Prof pr(e, SS_PROF_GN, s);
-        HIPCHK(gn_relu_gather(cb.cout, cb.Co, TP * cb.Co, o.gy, o.gy_ld, TP * o.gy_ld, o.gy_img, e->act_scale + cb.scale_i, e->P + cb.ga, e->P + cb.be,
-                              cb.stats, *o.gather, B, T, cb.Co, s, e->img16()));
+        HIPCHK(gn_relu_gather(CRows::slab(cb.cout, cb.Co, T), o.gy, e->P + cb.ga, e->P + cb.be, cb.stats, *o.gather, B, T, cb.Co, s,
+                              {.y_img = o.gy_img, .img_scale = e->act_scale + cb.scale_i, .img_bf16 = e->img16()}));
         return 0;
     }
     // T > 256 (eval only): the chunked GroupNorm takes its float64 partials from the step's scratch (one region per block: blocks run
@@ -1233,7 +1234,7 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
         e->part_off += need;
     }
     Prof pr(e, SS_PROF_GN, s);
-    HIPCHK(gn_relu_fwd(cb.cout, cb.Co, TP * cb.Co, y.p, y.ld, TP * y.ld, e->P + cb.ga, e->P + cb.be, cb.stats, B, T, cb.Co, s, gn_scratch, o.lens));
+    HIPCHK(gn_relu_fwd(CRows::slab(cb.cout, cb.Co, T), y.rows(T), e->P + cb.ga, e->P + cb.be, cb.stats, B, T, cb.Co, s, gn_scratch, o.lens));
     return 0;
 }
 
@@ -1241,12 +1242,10 @@ int conv_block_fwd(ss_engine* e, ConvBlk& cb, Slab x, Slab y, hipStream_t s, con
 // x: the block's forward input; dx: where to put the input gradient (p == nullptr: not needed)
 // bw: collects the weight gradient's re-layout (unpack_later) and names the caller buffer of a layer-0 block's input gradient
 struct ConvBwd {
-    // scatter / src (nullable): the block's output was resampled in the forward (training): src is the gradient of the RESAMPLED output (at its
-    // first real row and this block's first column, row stride src_ld); the gather's adjoint is taken inside the GroupNorm backward, which
-    // writes dy
+    // scatter / src (nullable): the block's output was resampled in the forward (training): src is the gradient of the RESAMPLED output (from
+    // this block's first column on); the gather's adjoint is taken inside the GroupNorm backward, which writes dy
     const InterpPlan* scatter = nullptr;
-    const float* src = nullptr;
-    long src_ld = 0;
+    CRows src;
     // dws (nullable): the weight-gradient GEMM goes to that stream behind an event, the chain on `s` does not wait for it -- the caller keeps dy
     // untouched until dws is joined
     hipStream_t dws = nullptr;
@@ -1261,8 +1260,8 @@ int conv_block_bwd(ss_engine* e, Backward& bw, ConvBlk& cb, Slab dy, Slab x, Sla
     float* im16 = (i16 && cb.Co % 8 == 0 && dy.ld % 8 == 0) ? grad_img_of(e, dy.p, R) : nullptr;
     {
         Prof pr(e, SS_PROF_GN, s);
-        HIPCHK(gn_relu_bwd(cb.cout, cb.Co, TP * cb.Co, dy.p, dy.ld, TP * dy.ld, e->P + cb.ga, e->P + cb.be, cb.stats,
-                           e->G + cb.ga, e->G + cb.be, e->G + cb.b, am, cb.part, B, T, cb.Co, s, o.scatter, o.src, o.src_ld, TP * o.src_ld, im16));
+        HIPCHK(gn_relu_bwd(CRows::slab(cb.cout, cb.Co, T), dy.rows(T), e->P + cb.ga, e->P + cb.be, cb.stats, e->G + cb.ga, e->G + cb.be, e->G + cb.b, B, T, cb.Co, s,
+                           {.amax = am, .part = cb.part, .scatter = o.scatter, .src = o.src, .dy_img = im16}));
     }
     // the conv-output gradient as an image for the image GEMM (scale: the power of two for the maximum gn_relu_bwd has just measured)
     const float* dimg = im16;
@@ -1421,13 +1420,15 @@ int lstm_big_fwd(ss_engine* e, LstmBlk& lb, Slab x, hipStream_t s, const int* le
             const bool pw = e->side3 && g_overlap && !compact && B > 32;
             if (pw) {
                 CHK(fork_join(e, s, e->side3));
-                HIPCHK(slab_prewarm(lb.gates[l], 8 * H, nullptr, nullptr, 2 * H, e->amax, B, T, false, e->side3));
+                HIPCHK(slab_prewarm(lb.gates[l], 8 * H, e->amax, B, T, e->side3, {.cn = 2 * H}));
             }
             {
                 Prof pr(e, SS_PROF_REC_FWD, s, 2.0 * 2 * B * T * 4.0 * H * H);
-                HIPCHK(lstm_seq_fwd(lb.gates[l], e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.hf_l(l), lb.out[l], lb.csave[l],
-                                    lb.sync_f(l), e->sticky, compact ? lb.xp0 : nullptr, compact ? lb.xf : 0, lb.out_img_valid ? lb.out_img[l] : nullptr, B, T, H,
-                                    false, false, s, e->img16() ? 1 | 2 : 0, lens));      // 16-bit data path: bf16 images (1), products of the high fp16 pieces only (2)
+                // 16-bit data path: bf16 images, products of the high fp16 pieces only
+                HIPCHK(lstm_seq_fwd(lb.gates[l], e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.hf_l(l), lb.out[l], lb.csave[l], lb.sync_f(l), B, T, H, s,
+                                    {.sticky = e->sticky, .xc = compact ? lb.xp0 : nullptr, .xf = compact ? lb.xf : 0,
+                                     .out_img = lb.out_img_valid ? lb.out_img[l] : nullptr, .img_bf16 = e->img16(), .hi_only = e->img16(),
+                                     .state_zeroed = true, .len = lens}));
             }
             if (pw) CHK(fork_join(e, e->side3, s));
             continue;
@@ -1748,9 +1749,11 @@ int lstm_bwd(ss_engine* e, Backward& bw, LstmBlk& lb, const float* d_top, Slab x
                                     (l == 0 ? compact0 : (lb.wimg(l) != nullptr && lb.in_of(l) % 64 == 0)) && H % 64 == 0;
                 {
                     Prof pr(e, SS_PROF_REC_BWD, s, 2.0 * 2 * B * T * 4.0 * H * H);
-                    HIPCHK(lstm_seq_bwd(dG, e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.px_l(l), dcur, lb.csave[l], lb.sync_b(l),
-                                        e->sticky, am, bias_in_kernel ? e->G + lb.pd[l * 2].bih : nullptr,
-                                        bias_in_kernel ? e->G + lb.pd[l * 2 + 1].bih : nullptr, compact0 ? lb.dgs : nullptr, compact0 ? lb.xf : 0, B, T, H, false, false, s, dg16 ? e->dg_img[l] : nullptr, (e->img16() ? 1 : 0) | (skip32 ? 4 : 0)));      // 1: products of the high fp16 pieces only (16-bit data path)
+                    HIPCHK(lstm_seq_bwd(dG, e->P + lb.pd[l * 2].whh, e->P + lb.pd[l * 2 + 1].whh, lb.px_l(l), dcur, lb.csave[l], lb.sync_b(l), B, T, H, s,
+                                        {.sticky = e->sticky, .amax = am, .gbias_f = bias_in_kernel ? e->G + lb.pd[l * 2].bih : nullptr,
+                                         .gbias_b = bias_in_kernel ? e->G + lb.pd[l * 2 + 1].bih : nullptr, .dgs = compact0 ? lb.dgs : nullptr,
+                                         .xf = compact0 ? lb.xf : 0, .dimg = dg16 ? e->dg_img[l] : nullptr, .img_only = skip32,
+                                         .hi_only = e->img16(), .state_zeroed = true}));      // hi_only: the 16-bit data path
                 }
                 if (dg16) e->bwd.dg16_written |= 1 << l;
                 if (skip32) e->bwd.dg32_skipped |= 1 << l;
@@ -1921,8 +1924,7 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     if (par) CHK(fork_join(e, s, b2));
     if (fused.late_org) {
         const ss_hparams& hh = e->hp;
-        HIPCHK(copy_rows(fused.late_org, hh.dim_freq, (long)T * hh.dim_freq, e->org + HALO * hh.dim_freq, hh.dim_freq, TP * hh.dim_freq, B, T,
-                         hh.dim_freq, b2));
+        HIPCHK(copy_rows(CRows::dense(fused.late_org, hh.dim_freq, T), Rows::slab(e->org, hh.dim_freq, T), B, T, hh.dim_freq, b2));
         if (fused.late_emb) HIPCHK(hipMemcpyAsync(e->emb, fused.late_emb, (long)B * hh.dim_spk_emb * 4, hipMemcpyDeviceToDevice, b2));
     }
     // Encoder_7's content (512 ch) and pitch (256 ch) stacks only share the random-resampling PLAN of each layer (model.py:199-206: one
@@ -1958,11 +1960,11 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
             if (training && g_gn_gather) {       // conv -> [GroupNorm + ReLU + gather] per stack: the normalised slab is never written
                 float* gi = (e->fwd.xf_img_valid && e->xf_img[i]) ? e->ioff(e->xf_img[i], HALO * CE) : nullptr;
                 const InterpPlan* pl = &e->plan[draw0 + i];
-                float* gy = e->xf[i] + HALO * CE;
+                const Rows gy = Rows::slab(e->xf[i], CE, T);
                 hipEvent_t ready = i == 0 ? plans : nullptr;
                 CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, b1,
-                                   {.gather = pl, .gy = gy + off2, .gy_img = gi ? e->ioff(gi, off2) : nullptr, .gy_ld = CE, .gather_ready = ready}));
-                CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s, {.gather = pl, .gy = gy, .gy_img = gi, .gy_ld = CE, .gather_ready = ready}));
+                                   {.gather = pl, .gy = gy.col(off2), .gy_img = gi ? e->ioff(gi, off2) : nullptr, .gather_ready = ready}));
+                CHK(conv_block_fwd(e, e->c1[i], x1, Slab{y, CE}, s, {.gather = pl, .gy = gy, .gy_img = gi, .gather_ready = ready}));
                 continue;
             }
             CHK(conv_block_fwd(e, e->c2[i], x2, Slab{y + off2, CE}, b1, {.lens = lens}));
@@ -1974,9 +1976,9 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
                     HIPCHK(hipStreamWaitEvent(s, plans, 0));
                 }
                 float* gi = (e->fwd.xf_img_valid && !e->img16() && e->xf_img[i]) ? e->xf_img[i] + HALO * CE : nullptr;      // (the separate gather writes format-v2 images only)
-                HIPCHK(interp_gather(pl, e->act + HALO * CE + off2, CE, TP * CE, e->xf[i] + HALO * CE + off2, CE, TP * CE, CE - off2, B, b1,
-                                     gi ? gi + off2 : nullptr, e->act_scale + e->c2[i].scale_i));
-                HIPCHK(interp_gather(pl, e->act + HALO * CE, CE, TP * CE, e->xf[i] + HALO * CE, CE, TP * CE, off2, B, s, gi, e->act_scale + e->c1[i].scale_i));
+                const Rows a = Rows::slab(e->act, CE, T), xf = Rows::slab(e->xf[i], CE, T);
+                HIPCHK(interp_gather(pl, a.col(off2), xf.col(off2), CE - off2, B, b1, gi ? gi + off2 : nullptr, e->act_scale + e->c2[i].scale_i));
+                HIPCHK(interp_gather(pl, a, xf, off2, B, s, gi, e->act_scale + e->c1[i].scale_i));
             }
             continue;
         }
@@ -1988,7 +1990,7 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
             InterpPlan& pl = e->plan[draw0 + i];
             HIPCHK(interp_plan(pl, scales + (long)(draw0 + i) * B * S7, len_seg + (long)(draw0 + i) * B * S7, nullptr,
                                e->hp.max_len_pad, B, s));
-            HIPCHK(interp_gather(pl, e->act + HALO * CE, CE, TP * CE, e->xf[i] + HALO * CE, CE, TP * CE, CE, B, s));
+            HIPCHK(interp_gather(pl, Rows::slab(e->act, CE, T), Rows::slab(e->xf[i], CE, T), CE, B, s));
         }
     }
     if (prio_fwd) CHK(forward_branch_work(e, fused, lens, b2));
@@ -2263,9 +2265,9 @@ int backward_encoder(ss_engine* e, Backward& bw, hipStream_t s) {
         float* dy = e->d_xf;
         // training: the adjoint of the layer's resampling, d_xf -> d_act; fused into each block's GroupNorm backward (g_gn_gather) or as a pass of its own
         const InterpPlan* sc = (training && g_gn_gather) ? &e->plan[e->fwd.enc_plan0 + i] : nullptr;
-        const float* sc_src = e->d_xf + HALO * CE;
+        const CRows sc_src = CRows::slab(e->d_xf, CE, T);
         if (training) {
-            if (!sc) HIPCHK(interp_scatter(e->plan[e->fwd.enc_plan0 + i], e->d_xf + HALO * CE, CE, TP * CE, e->d_act + HALO * CE, CE, TP * CE, CE, B, s));
+            if (!sc) HIPCHK(interp_scatter(e->plan[e->fwd.enc_plan0 + i], sc_src, Rows::slab(e->d_act, CE, T), CE, B, s));
             dy = (dw_off && i > 0) ? e->d_act_l[i - 1] : e->d_act;
         }
         // input gradients of layer i become d_xf (the gradient of xf[i-1]); dy is consumed before it is overwritten
@@ -2274,14 +2276,14 @@ int backward_encoder(ss_engine* e, Backward& bw, hipStream_t s) {
         // the resampled activations also exist as pre-split images when the forward's gathers wrote them (training, independent trunk chains)
         const float* bim = (training && e->fwd.xf_img_valid && i > 0) ? e->xf_img[i - 1] : nullptr;
         if (!chain_par && i == 0 && g3 && par && !e->dp_on) CHK(fork_join(e, s, b2));      // tail_par below: the pitch block's stream forks BEFORE the content block is enqueued
-        if (g3) CHK(conv_block_bwd(e, bw, e->c1[i], Slab{dy, CE}, trunk_in(e, 1, i, bim), i > 0 ? Slab{dxbuf, CE} : Slab{}, s, {.scatter = sc, .src = sc_src, .src_ld = CE}));
+        if (g3) CHK(conv_block_bwd(e, bw, e->c1[i], Slab{dy, CE}, trunk_in(e, 1, i, bim), i > 0 ? Slab{dxbuf, CE} : Slab{}, s, {.scatter = sc, .src = sc_src}));
         // Layer 0 is the step's tail: the decoder's weight gradients are through by then, and each of its two weight-gradient GEMMs alone
         // fills half the chip's workgroup slots -- the pitch block runs on the second branch stream beside the content block.  (Not under
         // data parallelism, where that stream carries the collectives.)
         const bool tail_par = chain_par || (i == 0 && g3 && par && !e->dp_on);
         hipStream_t s2 = tail_par ? (chain_par ? cs : b2) : s;
         CHK(conv_block_bwd(e, bw, e->c2[i], Slab{dy + off2, CE}, trunk_in(e, 2, i, bim), i > 0 ? Slab{dxbuf + off2, CE} : Slab{}, s2,
-                           {.scatter = sc, .src = sc_src + off2, .src_ld = CE, .dws = (dw_off && i > 0) ? dw_s : nullptr}));
+                           {.scatter = sc, .src = sc_src.col(off2), .dws = (dw_off && i > 0) ? dw_s : nullptr}));
         if (tail_par && (!chain_par || (i == 0 && !e->dp_on))) CHK(fork_join(e, b2, s));      // (chain_par: the two chains meet once, behind layer 0; data parallel: where the third branch stream joins below)
         if (i > 0) {           // the two wide layers' parameters (weight, bias, GroupNorm affine: contiguous) are final; layer 0 rides the last bucket
             if (g3) CHK(dp_bucket(e, e->c1[i].w, e->c1[i].be + e->c1[i].Co - e->c1[i].w, s));
@@ -2354,29 +2356,26 @@ namespace {
 // lens (nullable): ragged batch -- frames t >= len[b] of the inputs are not read, the slabs get zeros there
 int stage_g3_inputs(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, int B, int T, hipStream_t s, const int* lens = nullptr) {
     const ss_hparams& h = e->hp;
-    const long TP = T + 2 * HALO;
     const int CI = h.dim_freq + h.dim_f0;      // 337
     // split x_f0 [B,T,337] into the mel slab and the (channel-padded) f0 slab (model.py:196-197)
-    HIPCHK(copy_rows(x_f0, CI, (long)T * CI, e->in_mel + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq, B, T, h.dim_freq, s, lens));
-    HIPCHK(copy_rows(x_f0 + h.dim_freq, CI, (long)T * CI, e->in_f0 + HALO * e->f0p, e->f0p, TP * e->f0p, B, T, h.dim_f0, s, lens));
-    HIPCHK(copy_rows(x_org, h.dim_freq, (long)T * h.dim_freq, e->org + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq, B, T,
-                     h.dim_freq, s, lens));
+    const CRows x = CRows::dense(x_f0, CI, T);
+    HIPCHK(copy_rows(x, Rows::slab(e->in_mel, h.dim_freq, T), B, T, h.dim_freq, s, lens));
+    HIPCHK(copy_rows(x.col(h.dim_freq), Rows::slab(e->in_f0, e->f0p, T), B, T, h.dim_f0, s, lens));
+    HIPCHK(copy_rows(CRows::dense(x_org, h.dim_freq, T), Rows::slab(e->org, h.dim_freq, T), B, T, h.dim_freq, s, lens));
     HIPCHK(hipMemcpyAsync(e->emb, c_trg, (long)B * h.dim_spk_emb * 4, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
 // lens (nullable): ragged batch -- the head is row-wise and leaves its bias in the padded frames of the slab; the caller's tensor gets zeros
 int export_out(ss_engine* e, float* out, int B, int T, hipStream_t s, const int* lens = nullptr) {
-    const long TP = T + 2 * HALO;
     const int C = e->head_out;
-    HIPCHK(copy_rows(e->out_slab + HALO * C, C, TP * C, out, C, (long)T * C, B, T, C, s, lens));
+    HIPCHK(copy_rows(CRows::slab(e->out_slab, C, T), Rows::dense(out, C, T), B, T, C, s, lens));
     return 0;
 }
 
 int import_dout(ss_engine* e, const float* d_out, int B, int T, hipStream_t s) {
-    const long TP = T + 2 * HALO;
     const int C = e->head_out;
-    HIPCHK(copy_rows(d_out, C, (long)T * C, e->d_out_slab + HALO * C, C, TP * C, B, T, C, s));
+    HIPCHK(copy_rows(CRows::dense(d_out, C, T), Rows::slab(e->d_out_slab, C, T), B, T, C, s));
     return 0;
 }
 
@@ -2751,9 +2750,7 @@ static int g3_rhythm(ss_engine* e, const float* x_org, const int* lens, int B, i
     CHK(geometry(e, B, T, s, true));
     e->part_off = 0;           // step scratch (long-sequence GroupNorm): as at the start of forward_core
     const ss_hparams& h = e->hp;
-    const long TP = T + 2 * HALO;
-    HIPCHK(copy_rows(x_org, h.dim_freq, (long)T * h.dim_freq, e->org + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq, B, T,
-                     h.dim_freq, s, lens));
+    HIPCHK(copy_rows(CRows::dense(x_org, h.dim_freq, T), Rows::slab(e->org, h.dim_freq, T), B, T, h.dim_freq, s, lens));
     CHK(conv_pack_all(e, e->ct, s));
     PrepTable tb;
     tb.n = 0;
@@ -2774,7 +2771,9 @@ static int g3_rhythm(ss_engine* e, const float* x_org, const int* lens, int B, i
     src.d_o = nullptr;
     src.col = 0;
     HIPCHK(build_dec_in(&src, 1, nullptr, 0, W, e->d_ot, (int)OW, B, T, s));
-    HIPCHK(copy_rows(e->d_ot + HALO * OW, (long)h.freq_2 * OW, TP * OW, codes, W, (long)(T / h.freq_2) * W, B, T / h.freq_2, W, s));
+    CRows every = CRows::slab(e->d_ot, OW, T);
+    every.ld *= h.freq_2;           // every freq_2-th frame
+    HIPCHK(copy_rows(every, Rows::dense(codes, W, T / h.freq_2), B, T / h.freq_2, W, s));
     e->fwd.have = false;
     return 0;
 }
@@ -2800,10 +2799,8 @@ static int g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, con
     if (training && (!scales || !len_seg)) return fail("train-mode forward needs the InterpLnr draws");
     CHK(geometry(e, B, T, s, !training));
     const ss_hparams& h = e->hp;
-    const long TP = T + 2 * HALO;
-    HIPCHK(copy_rows(x_org, h.dim_freq, (long)T * h.dim_freq, e->org + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq, B, T,
-                     h.dim_freq, s, lens));
-    HIPCHK(copy_rows(f0_trg, h.dim_f0, (long)T * h.dim_f0, e->in_f0 + HALO * e->f0p, e->f0p, TP * e->f0p, B, T, h.dim_f0, s, lens));
+    HIPCHK(copy_rows(CRows::dense(x_org, h.dim_freq, T), Rows::slab(e->org, h.dim_freq, T), B, T, h.dim_freq, s, lens));
+    HIPCHK(copy_rows(CRows::dense(f0_trg, h.dim_f0, T), Rows::slab(e->in_f0, e->f0p, T), B, T, h.dim_f0, s, lens));
     CHK(forward_core(e, training != 0, scales, len_seg, 0, s, {}, lens));
     if (out) CHK(export_out(e, out, B, T, s, lens));
     return 0;
@@ -2849,18 +2846,16 @@ static int g3_step_body(ss_engine* e, const float* mel, const float* f0, const f
                         const float* scales, const int* len_seg, int B, int T, float grad_scale, int flags, float* loss,
                         hipStream_t s) {
     const ss_hparams& h = e->hp;
-    const long TP = T + 2 * HALO;
     prof_tick(e);
     // solver.py:160-163: resample [mel | f0] with the utterance lengths, re-quantise the f0 channel
     HIPCHK(interp_plan(e->plan[0], scales, len_seg, len_org, 0, B, s));
-    HIPCHK(interp_quant(e->plan[0], mel, f0, h.dim_freq, e->in_mel + HALO * h.dim_freq, h.dim_freq, TP * h.dim_freq,
-                        e->in_f0 + HALO * e->f0p, e->f0p, TP * e->f0p, h.dim_f0, e->qidx, B, s));
+    HIPCHK(interp_quant(e->plan[0], mel, f0, h.dim_freq, Rows::slab(e->in_mel, h.dim_freq, T), Rows::slab(e->in_f0, e->f0p, T), h.dim_f0, e->qidx, B, s));
     // x_org and the speaker embedding are first read by Encoder_t / the decoder input: their copies ride on the branch stream
     const bool accumulate = (flags & SS_STEP_ACCUMULATE) != 0;
     CHK(forward_core(e, true, scales, len_seg, 1, s, FusedForward{mel, emb, true, accumulate}));        // solver.py:165
     const int C = e->head_out;
-    HIPCHK(mse_loss(e->out_slab + HALO * C, C, TP * C, e->org + HALO * C, C, TP * C, e->d_out_slab + HALO * C, C, TP * C, B, T,
-                    C, 1.0f, e->loss_part, loss, s));                                       // solver.py:166
+    HIPCHK(mse_loss(CRows::slab(e->out_slab, C, T), CRows::slab(e->org, C, T), Rows::slab(e->d_out_slab, C, T), B, T, C, 1.0f, e->loss_part, loss,
+                    s));                                                                    // solver.py:166
     Backward bw;
     bw.accumulate = accumulate;
     if (flags & SS_STEP_SPLIT_BACKWARD) {         // data parallel: stop once the decoder + head gradients are complete
@@ -2952,10 +2947,8 @@ int ss_g6_train_step(ss_engine* e, const float* mel, const float* f0_onehot, con
     hipStream_t s = own.s;
     prof_tick(e);
     CHK(ss_g6_forward(e, mel, f0_onehot, scales, len_seg, B, T, 1, nullptr, (void*)s));
-    const long TP = T + 2 * HALO;
     const int C = e->head_out;
-    HIPCHK(ce_loss(e->out_slab + HALO * C, C, TP * C, target_idx, e->d_out_slab + HALO * C, C, TP * C, B, T, C, 1.0f,
-                   e->loss_part, loss, s));
+    HIPCHK(ce_loss(CRows::slab(e->out_slab, C, T), target_idx, Rows::slab(e->d_out_slab, C, T), B, T, C, 1.0f, e->loss_part, loss, s));
     Backward bw;
     bw.accumulate = (flags & SS_STEP_ACCUMULATE) != 0;
     bw.adam_early = !(flags & SS_STEP_NO_ADAM);
@@ -3000,7 +2993,7 @@ int ss_interp_forward(ss_engine* e, const float* x, const int* len_seq, const fl
     if ((long)B * (T + 1) > (long)e->curB * (e->curT + 1)) return fail("ss_interp_forward: plan storage too small");
     const int P = pl.P;
     HIPCHK(interp_plan(pl, scales, len_seg, len_seq, 0, B, s));
-    HIPCHK(interp_gather(pl, x, C, (long)T * C, y, C, (long)P * C, C, B, s));
+    HIPCHK(interp_gather(pl, CRows::dense(x, C, T), Rows::dense(y, C, P), C, B, s));
     if (i0) HIPCHK(hipMemcpyAsync(i0, pl.i0, (long)B * P * 4, hipMemcpyDeviceToDevice, s));
     if (lam) HIPCHK(hipMemcpyAsync(lam, pl.lam, (long)B * P * 4, hipMemcpyDeviceToDevice, s));
     if (counts) HIPCHK(hipMemcpyAsync(counts, pl.counts, (long)B * 4, hipMemcpyDeviceToDevice, s));
@@ -3015,7 +3008,7 @@ int ss_interp_backward(ss_engine* e, const float* dy, int B, int T, int C, float
     InterpPlan pl = e->plan[3];
     pl.T = T;
     const int P = pl.P;
-    HIPCHK(interp_scatter(pl, dy, C, (long)P * C, dx, C, (long)T * C, C, B, s));
+    HIPCHK(interp_scatter(pl, CRows::dense(dy, C, P), Rows::dense(dx, C, T), C, B, s));
     return 0;
 }
 
@@ -3249,7 +3242,7 @@ static int op_lstm_fwd(float* gates, const float* whh_f, const float* whh_b, flo
         float* hf = scratch + wn;
         if (g_persist && lstm_seq_supported(B, H) && wn * 4 >= lstm_seq_xbytes(B, H, false)) {
             // exchange buffer in the (unused) packed-weight area, counters behind it
-            HIPCHK(lstm_seq_fwd(gates, whh_f, whh_b, scratch, out, csave, (unsigned*)hf, nullptr, nullptr, 0, nullptr, B, T, H, true, g_op_time_major != 0, s, 0, len));
+            HIPCHK(lstm_seq_fwd(gates, whh_f, whh_b, scratch, out, csave, (unsigned*)hf, B, T, H, s, {.time_major = g_op_time_major != 0, .len = len}));
             return 0;
         }
         HIPCHK(lstm_pack_w(whh_f, whh_b, scratch, H, 0, s));
@@ -3283,8 +3276,8 @@ int ss_op_lstm_bwd(float* gates, const float* whh_f, const float* whh_b, const f
         float* dc = gf + 2 * half;
         const long xbytes = lstm_seq_xbytes(B, H, true);
         if (g_persist && lstm_seq_supported(B, H) && scratch_floats * 4 >= xbytes + 4L * LSTM_SEQ_SYNC_WORDS) {     // [exchange tiles][flags]
-            HIPCHK(lstm_seq_bwd(gates, whh_f, whh_b, scratch, d_out, csave, (unsigned*)((char*)scratch + xbytes), nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, T,
-                                H, true, g_op_time_major != 0, s));
+            HIPCHK(lstm_seq_bwd(gates, whh_f, whh_b, scratch, d_out, csave, (unsigned*)((char*)scratch + xbytes), B, T, H, s,
+                                {.time_major = g_op_time_major != 0}));
             return 0;
         }
         HIPCHK(lstm_pack_w(whh_f, whh_b, scratch, H, 1, s));
@@ -3354,9 +3347,7 @@ int ss_debug_relu_mask(ss_engine* e, const char* block, float* mask, void* strea
     if (it == e->dbg.end()) return fail(std::string("ss_debug_relu_mask: no such conv block: ") + block);
     for (ConvBlk* cb : conv_blocks(*e))
         if (cb->Co && cb->cout == it->second.first) {
-            const long TP = e->curT + 2 * HALO;
-            HIPCHK(gn_relu_mask(cb->cout, cb->Co, TP * cb->Co, e->P + cb->ga, e->P + cb->be, cb->stats, mask, e->curB, e->curT,
-                                cb->Co, S(stream)));
+            HIPCHK(gn_relu_mask(CRows::slab(cb->cout, cb->Co, e->curT), e->P + cb->ga, e->P + cb->be, cb->stats, mask, e->curB, e->curT, cb->Co, S(stream)));
             return 0;
         }
     return fail("ss_debug_relu_mask: block has no storage");
@@ -3422,20 +3413,20 @@ static int op_conv_block(const float* x, const float* w, const float* bias, cons
     HIPCHK(hipMemcpyAsync(e.P + cb.b, bias, Co * 4L, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(e.P + cb.ga, gamma, Co * 4L, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(e.P + cb.be, beta, Co * 4L, hipMemcpyDeviceToDevice, s));
-    HIPCHK(copy_rows(x, Ci, (long)T * Ci, xs + HALO * cb.Cp, cb.Cp, TP * cb.Cp, B, T, Ci, s, len));
+    HIPCHK(copy_rows(CRows::dense(x, Ci, T), Rows::slab(xs, cb.Cp, T), B, T, Ci, s, len));
     CHK(conv_pack_all(&e, cb, s));
     CHK(conv_block_fwd(&e, cb, Slab{xs, cb.Cp}, Slab{ys, Co}, s, {.lens = len}));
-    HIPCHK(copy_rows(ys + HALO * Co, Co, TP * Co, y, Co, (long)T * Co, B, T, Co, s));
+    HIPCHK(copy_rows(CRows::slab(ys, Co, T), Rows::dense(y, Co, T), B, T, Co, s));
     if (dy) {
         if (!gw || !gb || !ggamma || !gbeta) return fail("ss_op_conv_block: backward needs the gradient outputs");
-        HIPCHK(copy_rows(dy, Co, (long)T * Co, dys + HALO * Co, Co, TP * Co, B, T, Co, s));
+        HIPCHK(copy_rows(CRows::dense(dy, Co, T), Rows::slab(dys, Co, T), B, T, Co, s));
         Backward bw;
         CHK(conv_block_bwd(&e, bw, cb, Slab{dys, Co}, Slab{xs, cb.Cp}, dx ? Slab{dxs, cb.Cp} : Slab{nullptr, 0}, s));
         HIPCHK(hipMemcpyAsync(gw, e.G + cb.w, (long)Co * Ci * 5 * 4, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipMemcpyAsync(gb, e.G + cb.b, Co * 4L, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipMemcpyAsync(ggamma, e.G + cb.ga, Co * 4L, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipMemcpyAsync(gbeta, e.G + cb.be, Co * 4L, hipMemcpyDeviceToDevice, s));
-        if (dx) HIPCHK(copy_rows(dxs + HALO * cb.Cp, cb.Cp, TP * cb.Cp, dx, Ci, (long)T * Ci, B, T, Ci, s));
+        if (dx) HIPCHK(copy_rows(CRows::slab(dxs, cb.Cp, T), Rows::dense(dx, Ci, T), B, T, Ci, s));
     }
     return 0;
 }

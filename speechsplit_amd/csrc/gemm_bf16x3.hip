@@ -56,14 +56,6 @@ __device__ __forceinline__ void split2(float x0, float x1, unsigned& h, unsigned
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 constexpr float F16_SCALE = 16.0f;          // operands bounded by construction: |x| up to 4094 survives
-// operand with a measured maximum m: the power of two that brings m into [128, 256) (256x headroom below fp16's 65504),
-// capped at 2^60 so that an all-zero / denormal tensor cannot produce an infinite scale
-__device__ __forceinline__ float pow2_scale(float m) {
-    const int e = (int)((__float_as_uint(m) >> 23) & 0xFFu);
-    int se = 261 - e;
-    se = se < 1 ? 1 : (se > 187 ? 187 : se);
-    return __uint_as_float((unsigned)se << 23);
-}
 // Four instructions per PAIR of values: the mixed-precision fma scales, subtracts the fp16 piece it reads straight out of the
 // packed register, rounds once and writes the chosen half of the destination (hipcc's own code for the plain C++ form: seven).
 // The split sits on the same issue port as the MFMAs -- 4 cycles per vector instruction, 8 of its 32 per MFMA -- so with 128 x 128
@@ -199,8 +191,8 @@ __global__ __launch_bounds__(WS ? 512 : 256, (NPL == 2 && !WS && !PROBE) ? 3 : 1
 
     typedef f32x4 Slot;
     // fp16 x 2 only: per-operand power-of-two scales (measured maximum or the fixed one), undone in the epilogue
-    const float sc_a = NPL == 2 ? (((d.flags & GEMM_A_PRE) || !d.amax_a) ? (d.a_pre_scale ? *d.a_pre_scale : F16_SCALE) : pow2_scale(*d.amax_a)) : 1.0f;
-    const float sc_b = NPL == 2 ? (((d.flags & GEMM_B_PRE) || !d.amax_b) ? (d.b_pre_scale ? *d.b_pre_scale : F16_SCALE) : pow2_scale(*d.amax_b)) : 1.0f;
+    const float sc_a = NPL == 2 ? (((d.flags & GEMM_A_PRE) || !d.amax_a) ? (d.a_pre_scale ? *d.a_pre_scale : F16_SCALE) : pow2_scale_of(*d.amax_a)) : 1.0f;
+    const float sc_b = NPL == 2 ? (((d.flags & GEMM_B_PRE) || !d.amax_b) ? (d.b_pre_scale ? *d.b_pre_scale : F16_SCALE) : pow2_scale_of(*d.amax_b)) : 1.0f;
     // full: the whole k-tile lies inside [kbeg, kend), so the load needs no predicate at all (rows / columns past the
     // matrix edge read row / column 0: their products land in accumulator entries the epilogue never stores).
     auto fetch = [&](const Operand& op, bool T, bool TRX, const float*& p, int& w, bool ok, int kpos, bool full) -> Slot {

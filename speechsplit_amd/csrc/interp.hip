@@ -174,26 +174,23 @@ hipError_t interp_plan(const InterpPlan& p, const float* scales, const int* len_
     return hipGetLastError();
 }
 
-hipError_t interp_gather(const InterpPlan& p, const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, int C,
-                         int B, hipStream_t s, float* y_img, const float* img_scale) {
-    if (y_img && (C % 8 || x_ld % 4 || y_ld % 8 || x_bs % 4 || y_bs % 8 || (((size_t)x | (size_t)y) & 15) || (((size_t)y_img) & 31))) y_img = nullptr;     // image format v2: groups of eight
+hipError_t interp_gather(const InterpPlan& p, CRows x, Rows y, int C, int B, hipStream_t s, float* y_img, const float* img_scale) {
+    if (y_img && (C % 8 || x.ld % 4 || y.ld % 8 || x.bs % 4 || y.bs % 8 || (((size_t)x.p | (size_t)y.p) & 15) || (((size_t)y_img) & 31))) y_img = nullptr;     // image format v2: groups of eight
     const int threads = y_img ? (C >= 512 ? 128 : 64) : (C >= 256 ? 256 : (C >= 128 ? 128 : 64));
-    hipLaunchKernelGGL(interp_gather_kernel, dim3(p.P, B), dim3(threads), 0, s, x, x_ld, x_bs, y, y_ld, y_bs, C, p.P, p.i0,
+    hipLaunchKernelGGL(interp_gather_kernel, dim3(p.P, B), dim3(threads), 0, s, x.p, x.ld, x.bs, y.p, y.ld, y.bs, C, p.P, p.i0,
                        p.lam, p.nrows, y_img, img_scale);
     return hipGetLastError();
 }
 
-hipError_t interp_quant(const InterpPlan& p, const float* mel, const float* f0, int CM, float* ymel, long ym_ld, long ym_bs,
-                        float* yoh, long yo_ld, long yo_bs, int NOH, int* qidx, int B, hipStream_t s) {
-    hipLaunchKernelGGL(interp_quant_kernel, dim3(p.P, B), dim3(128), 0, s, mel, f0, p.T, CM, ymel, ym_ld, ym_bs, yoh, yo_ld,
-                       yo_bs, NOH, qidx, p.P, p.i0, p.lam, p.nrows);
+hipError_t interp_quant(const InterpPlan& p, const float* mel, const float* f0, int CM, Rows ymel, Rows yoh, int NOH, int* qidx, int B, hipStream_t s) {
+    hipLaunchKernelGGL(interp_quant_kernel, dim3(p.P, B), dim3(128), 0, s, mel, f0, p.T, CM, ymel.p, ymel.ld, ymel.bs, yoh.p, yoh.ld,
+                       yoh.bs, NOH, qidx, p.P, p.i0, p.lam, p.nrows);
     return hipGetLastError();
 }
 
-hipError_t interp_scatter(const InterpPlan& p, const float* dy, long dy_ld, long dy_bs, float* dx, long dx_ld, long dx_bs,
-                          int C, int B, hipStream_t s) {
+hipError_t interp_scatter(const InterpPlan& p, CRows dy, Rows dx, int C, int B, hipStream_t s) {
     const int threads = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
-    hipLaunchKernelGGL(interp_scatter_kernel, dim3(p.T, B), dim3(threads), 0, s, dy, dy_ld, dy_bs, dx, dx_ld, dx_bs, C, p.P,
+    hipLaunchKernelGGL(interp_scatter_kernel, dim3(p.T, B), dim3(threads), 0, s, dy.p, dy.ld, dy.bs, dx.p, dx.ld, dx.bs, C, p.P,
                        p.T, p.lam, p.start);
     return hipGetLastError();
 }

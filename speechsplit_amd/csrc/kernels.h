@@ -11,6 +11,26 @@ namespace ss {
 
 constexpr int HALO = 2;
 
+// B utterances of rows: row t of utterance b starts at p + b * bs + t * ld (floats).  For EVERY launcher that takes one, p is frame 0, the
+// first real row; the launchers whose kernels add the halo themselves (the GroupNorm family) step back to slab row 0 inside.
+struct CRows {
+    const float* p = nullptr;
+    long ld = 0, bs = 0;
+    static CRows slab(const float* row0, long ld, long T) { return {row0 + HALO * ld, ld, (T + 2 * HALO) * ld}; }      // a haloed slab, from its row 0
+    static CRows dense(const float* p, long C, long T) { return {p, C, T * C}; }                                        // a caller's [B][T][C]
+    CRows col(long c) const { return {p + c, ld, bs}; }            // the same rows from column c on
+    const float* row0() const { return p - HALO * ld; }
+};
+struct Rows {             // the same, writable
+    float* p = nullptr;
+    long ld = 0, bs = 0;
+    static Rows slab(float* row0, long ld, long T) { return {row0 + HALO * ld, ld, (T + 2 * HALO) * ld}; }
+    static Rows dense(float* p, long C, long T) { return {p, C, T * C}; }
+    Rows col(long c) const { return {p + c, ld, bs}; }
+    float* row0() const { return p - HALO * ld; }
+    operator CRows() const { return {p, ld, bs}; }
+};
+
 // ---------------------------------------------------------------- interp.hip
 struct InterpPlan {
     int S;          // segments per utterance (max_len_seq / min_len_seg + 1 = 7)
@@ -27,43 +47,44 @@ hipError_t interp_plan(const InterpPlan& p, const float* scales, const int* len_
                        int len_seq_const, int B, hipStream_t s);
 // y_img (nullable): also write the pre-split image of y (GemmDesc::a_pre), same geometry as y
 // img_scale (nullable: 16): device word with the power-of-two scale the image is split with (act_scales)
-hipError_t interp_gather(const InterpPlan& p, const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, int C,
-                         int B, hipStream_t s, float* y_img = nullptr, const float* img_scale = nullptr);
-hipError_t interp_quant(const InterpPlan& p, const float* mel, const float* f0, int CM, float* ymel, long ym_ld, long ym_bs,
-                        float* yoh, long yo_ld, long yo_bs, int NOH, int* qidx, int B, hipStream_t s);
-hipError_t interp_scatter(const InterpPlan& p, const float* dy, long dy_ld, long dy_bs, float* dx, long dx_ld, long dx_bs,
-                          int C, int B, hipStream_t s);
+hipError_t interp_gather(const InterpPlan& p, CRows x, Rows y, int C, int B, hipStream_t s, float* y_img = nullptr, const float* img_scale = nullptr);
+hipError_t interp_quant(const InterpPlan& p, const float* mel, const float* f0, int CM, Rows ymel, Rows yoh, int NOH, int* qidx, int B, hipStream_t s);
+hipError_t interp_scatter(const InterpPlan& p, CRows dy, Rows dx, int C, int B, hipStream_t s);
 
 // ---------------------------------------------------------------- elementwise.hip
 // GroupNorm(16 channels per group, eps 1e-5, biased variance over 16 x T) + ReLU on rows [HALO, HALO+T) of haloed slabs.
-hipError_t gn_relu_fwd(const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, const float* gamma,
-                       const float* beta, float* stats /*[B, C/16, 2] mean, rstd*/, int B, int T, int C, hipStream_t s,
-                       double* scratch = nullptr, const int* len = nullptr);
+hipError_t gn_relu_fwd(CRows x, Rows y, const float* gamma, const float* beta, float* stats /*[B, C/16, 2] mean, rstd*/, int B, int T, int C,
+                       hipStream_t s, double* scratch = nullptr, const int* len = nullptr);
 // len (nullable; device i32[B], eval-mode forwards only): a RAGGED batch.  Row b holds len[b] frames (every kernel that takes it uses
 // min(max(len[b], 0), T)); the frames behind them are padding that is never read: the statistics run over t < len[b] with
 // inv_n = 1 / (16 len[b]) and the outputs for t >= len[b] are zeros.  nullptr launches the kernels as compiled without the predicate.
 // T <= 256: one register-resident kernel, scratch unused.  T > 256 (eval-mode inference only; no backward exists for it): three
 // chunked launches that need gn_relu_fwd_scratch_bytes(B, T, C) bytes of scratch (8-byte aligned) for their float64 chunk partials.
 long gn_relu_fwd_scratch_bytes(int B, int T, int C);
-// the same followed by the training forward's random resampling of the block output (interp_gather), in one pass: y / y_img are the
-// resampled slab and its image AT the first real row and the block's first column (p.P output rows); bit-identical to the two kernels
-// img_bf16: y_img is the plain bf16 tensor (element offsets, 2 bytes each) instead of a format-v2 image (common.h ss_store_img4)
-hipError_t gn_relu_gather(const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, float* y_img, const float* img_scale,
-                          const float* gamma, const float* beta, float* stats, const InterpPlan& p, int B, int T, int C, hipStream_t s, int img_bf16 = 0);
+// the same followed by the training forward's random resampling of the block output (interp_gather), in one pass: y is the resampled
+// slab from the block's first column on (p.P output rows); bit-identical to the two kernels
+struct GnGather {
+    float* y_img = nullptr;             // the image of y, at y's position
+    const float* img_scale = nullptr;   // as interp_gather's
+    bool img_bf16 = false;              // y_img is the plain bf16 tensor (element offsets, 2 bytes each) instead of a format-v2 image (common.h ss_store_img4)
+};
+hipError_t gn_relu_gather(CRows x, Rows y, const float* gamma, const float* beta, float* stats, const InterpPlan& p, int B, int T, int C,
+                          hipStream_t s, const GnGather& o = {});
 // dy (grad of the ReLU output) is replaced in place by the grad of the GroupNorm input (= conv output).
 // g_gamma / g_beta / g_bias [C]: every utterance's d_gamma, d_beta, d_convbias are ACCUMULATED here (f32 atomics).
-// amax (nullable): receives max |conv-output gradient| written, as for lstm_seq_bwd.
-// part (nullable): [B][3][C] scratch; in deterministic mode the per-utterance sums go there and are added in utterance order.
-// scatter / src (nullable): take the adjoint of the training forward's gather on the fly from src (the gradient of the resampled output, at its
-// first real row and the block's first column) instead of reading dy (interp_scatter fused in; dy is then only written)
-hipError_t gn_relu_bwd(const float* x, long x_ld, long x_bs, float* dy, long dy_ld, long dy_bs, const float* gamma,
-                       const float* beta, const float* stats, float* g_gamma, float* g_beta, float* g_bias, float* amax, float* part,
-                       int B, int T, int C, hipStream_t s,
-                       const InterpPlan* scatter = nullptr, const float* src = nullptr, long src_ld = 0, long src_bs = 0,
-                       float* dy_img = nullptr);      // dy_img: dy also as a plain bf16 tensor (same geometry; halo rows are the caller's: zero)
+struct GnBwd {
+    float* amax = nullptr;              // receives max |conv-output gradient| written, as for lstm_seq_bwd
+    float* part = nullptr;              // [B][3][C] scratch; in deterministic mode the per-utterance sums go there and are added in utterance order
+    // scatter / src: take the adjoint of the training forward's gather on the fly from src (the gradient of the resampled output, from the
+    // block's first column on) instead of reading dy (interp_scatter fused in; dy is then only written)
+    const InterpPlan* scatter = nullptr;
+    CRows src;
+    float* dy_img = nullptr;            // dy also as a plain bf16 tensor, at slab row 0 (same geometry; halo rows are the caller's: zero)
+};
+hipError_t gn_relu_bwd(CRows x, Rows dy, const float* gamma, const float* beta, const float* stats, float* g_gamma, float* g_beta, float* g_bias,
+                       int B, int T, int C, hipStream_t s, const GnBwd& o = {});
 // test hook: mask [B, T, C] dense = 1.0f where the block's GroupNorm output is > 0 (the ReLU branch the kernels above take)
-hipError_t gn_relu_mask(const float* x, long x_ld, long x_bs, const float* gamma, const float* beta, const float* stats,
-                        float* mask, int B, int T, int C, hipStream_t s);
+hipError_t gn_relu_mask(CRows x, const float* gamma, const float* beta, const float* stats, float* mask, int B, int T, int C, hipStream_t s);
 // out[c] += sum_r in[r*ld + c], float64 accumulation in a fixed order (elementwise.hip).  part / ctr (nullable): scratch of
 // colsum_scratch_doubles(columns) float64 words and cdiv(columns, 64) zeroed counters (left zero again); without them one workgroup per 64 columns
 long colsum_scratch_doubles(int cols);
@@ -72,8 +93,7 @@ hipError_t colsum_acc(const float* in, long ld, int R, int C, float* out, double
 hipError_t colsum_bias(const float* in, long ld, int R, int C, float* bih0, float* bhh0, float* bih1, float* bhh1, double* part, unsigned* ctr,
                        hipStream_t s);
 // len (nullable, as gn_relu_fwd): source rows t >= len[b] are not read and the destination gets zeros there
-hipError_t copy_rows(const float* src, long s_ld, long s_bs, float* dst, long d_ld, long d_bs, int B, int T, int C,
-                     hipStream_t s, const int* len = nullptr);
+hipError_t copy_rows(CRows src, Rows dst, int B, int T, int C, hipStream_t s, const int* len = nullptr);
 // batch assembly from a device-resident corpus: see collate_kernel (crop rows, clip mel to [0,1], pad mel with 0 / F0 with -1e10)
 hipError_t collate(const float* mel_cat, const float* f0_cat, const float* emb_tab, const long* row0, const int* len,
                    const int* item, int B, int T, int C, int E, float* mel, float* f0, float* emb, hipStream_t s);
@@ -141,12 +161,9 @@ hipError_t build_dec_in_compact(const CodeSrc* src, int nsrc, const float* emb, 
 hipError_t dec_in_grad_compact(const CodeSrc* src, int nsrc, const float* d_xc, int ld, int B, int T, int f, hipStream_t s);
 
 // loss = mean((tgt - out)^2) over B*T*C real elements (solver.py:166); d_out = 2 (out - tgt) / N * scale
-hipError_t mse_loss(const float* out, long o_ld, long o_bs, const float* tgt, long t_ld, long t_bs, float* d_out,
-                    long d_ld, long d_bs, int B, int T, int C, float grad_scale, float* partials, float* loss,
-                    hipStream_t s);
+hipError_t mse_loss(CRows out, CRows tgt, Rows d_out, int B, int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s);
 // softmax cross-entropy over C classes against integer targets; mean over B*T rows
-hipError_t ce_loss(const float* logits, long o_ld, long o_bs, const int* tgt, float* d_out, long d_ld, long d_bs, int B,
-                   int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s);
+hipError_t ce_loss(CRows logits, const int* tgt, Rows d_out, int B, int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s);
 
 struct AdamState {        // device-resident so a captured graph can replay the step
     double lr, beta1, beta2, eps;
@@ -256,25 +273,47 @@ hipError_t lstm_step_bwd(float* gates, const float* wfragT, const float* gf_cur,
 // gates / out / csave / d_out as above; whh_* are the parameter tensors themselves ([4H][H] row-major): each workgroup
 // splits its slice into fp16 x 2 pieces once and keeps it in registers.  xbuf = lstm_seq_xbytes() bytes of exchange buffer
 // (forward: h(t) as fp16 pieces in MFMA fragment order; backward: partial-dh tiles, whose dwords carry their step's tag in bit 0),
-// sync = LSTM_SEQ_SYNC_WORDS unsigned words (completion flags, XCD masks, abort word at [0]); both must be all zero at launch:
-// zero_state = false means the caller has zeroed them itself.  time_major: the slabs are [T+4][B][C] instead of [B][T+4][C].
+// sync = LSTM_SEQ_SYNC_WORDS unsigned words (completion flags, XCD masks, abort word at [0]); both must be all zero at launch.
 constexpr int LSTM_SEQ_SYNC_WORDS = 2048;   // [0] abort, [1..) XCD masks per group, [64 + 32*group + member] completion flags
 bool lstm_seq_supported(int B, int H);
 long lstm_seq_xbytes(int B, int H, bool backward);
-// out_img (fwd, nullable): pre-split image of `out` (GemmDesc::a_pre / b_pre), same shape
-// xc / xf (fwd), dgs / xf (bwd), nullable: a layer whose input repeats in blocks of xf frames -- input projections given once per block
-// [B][T/xf][8H]; pre-activation gradients additionally written summed per block [B][T/xf][8H]
-// sticky (nullable): engine-wide word, host-visible, that a launch ORs 1 into when its bounded wait expires (never cleared by a step)
-hipError_t lstm_seq_fwd(float* gates, const float* whh_f, const float* whh_b, void* xbuf, float* out, float* csave,
-                        unsigned* sync, unsigned* sticky, const float* xc, int xf, float* out_img, int B, int T, int H, bool zero_state,
-                        bool time_major, hipStream_t s, int img_bf16 = 0, const int* len = nullptr);       // len (nullable; device i32[B]): ragged eval-mode batch -- after the cell update of a step at frame t, rows with t >= min(max(len[b], 0), T) take c = h = 0 (select), and the zero h goes through the hand-off with the step's tag.  img_bf16 bit 0: out_img is the plain bf16 tensor, not a format-v2 image; bit 1: products from the high fp16 pieces alone
-// amax (nullable): device word that receives max |pre-activation gradient| written (atomic max of the float's bit pattern;
-// zero it first) -- the scale the fp16 x 2 GEMMs that consume the gradient slab need
-// gbias_f / gbias_b (nullable): [2][4H] gradient accumulators of (b_ih, b_hh) of the forward / reverse direction; the kernel
-// adds the sum over utterances and time of the pre-activation gradients to both halves (f32 atomics)
-hipError_t lstm_seq_bwd(float* gates, const float* whh_f, const float* whh_b, void* xbuf, const float* d_out,
-                        const float* csave, unsigned* sync, unsigned* sticky, float* amax, float* gbias_f, float* gbias_b, float* dgs, int xf,
-                        int B, int T, int H, bool zero_state, bool time_major, hipStream_t s, float* dimg = nullptr, int hi = 0);      // dimg: the gradients also as a plain bf16 tensor (slab geometry); hi bit 0: products from the high fp16 pieces alone, bit 2 (with dimg): the gradients ONLY as the bf16 tensor
+// A launch on exchange tags or sync words that are not zero waits out its bounded spin and sets the sticky abort word, so the launcher
+// zeroes both itself unless state_zeroed says that the caller has.
+struct SeqFwd {
+    unsigned* sticky = nullptr;    // engine-wide word, host-visible, that a launch ORs 1 into when its bounded wait expires (never cleared by a step)
+    // xc / xf: a layer whose input repeats in blocks of xf frames -- input projections given once per block [B][T/xf][8H]
+    const float* xc = nullptr;
+    int xf = 0;
+    float* out_img = nullptr;      // pre-split image of `out` (GemmDesc::a_pre / b_pre), same shape
+    bool img_bf16 = false;         // out_img is the plain bf16 tensor, not a format-v2 image
+    bool hi_only = false;          // products from the high fp16 pieces alone
+    bool state_zeroed = false;     // the caller has zeroed xbuf and sync itself
+    bool time_major = false;       // the slabs are [T+4][B][C] instead of [B][T+4][C]
+    // ragged eval-mode batch, device i32[B] -- after the cell update of a step at frame t, rows with t >= min(max(len[b], 0), T) take
+    // c = h = 0 (select), and the zero h goes through the hand-off with the step's tag
+    const int* len = nullptr;
+};
+hipError_t lstm_seq_fwd(float* gates, const float* whh_f, const float* whh_b, void* xbuf, float* out, float* csave, unsigned* sync, int B, int T,
+                        int H, hipStream_t s, const SeqFwd& o = {});
+struct SeqBwd {
+    unsigned* sticky = nullptr;    // as SeqFwd's
+    // device word that receives max |pre-activation gradient| written (atomic max of the float's bit pattern; zero it first) -- the scale
+    // the fp16 x 2 GEMMs that consume the gradient slab need
+    float* amax = nullptr;
+    // [2][4H] gradient accumulators of (b_ih, b_hh) of the forward / reverse direction; the kernel adds the sum over utterances and time
+    // of the pre-activation gradients to both halves (f32 atomics)
+    float *gbias_f = nullptr, *gbias_b = nullptr;
+    // dgs / xf: a layer whose input repeats in blocks of xf frames -- pre-activation gradients additionally written summed per block
+    // [B][T/xf][8H]
+    float* dgs = nullptr;
+    int xf = 0;
+    float* dimg = nullptr;         // the gradients also as a plain bf16 tensor (slab geometry)
+    bool img_only = false;         // (with dimg) the gradients ONLY as the bf16 tensor
+    bool hi_only = false;          // products from the high fp16 pieces alone
+    bool state_zeroed = false, time_major = false;      // as SeqFwd's
+};
+hipError_t lstm_seq_bwd(float* gates, const float* whh_f, const float* whh_b, void* xbuf, const float* d_out, const float* csave, unsigned* sync,
+                        int B, int T, int H, hipStream_t s, const SeqBwd& o = {});
 
 // ---- lstm_wgrad.hip: weight and bias gradients of the encoder BLSTMs (H <= 32), every layer of every block in one launch
 constexpr int WGRAD_MAX = 8;
@@ -307,7 +346,12 @@ int lstm_seq_free_xcds(int B, int H);
 
 // streaming pre-read (results unused) of the slabs a persistent recurrence is about to consume: wide [rows][cw] (gates) and one or two
 // narrow ones [rows][cn] (cell states; output gradient), both ends of the sequence first.  Meant for a side stream, beside the recurrence.
-hipError_t slab_prewarm(const float* wide, int cw, const float* n0, const float* n1, int cn, float* sink, int B, int T, bool time_major, hipStream_t s);
+struct Prewarm {
+    const float *n0 = nullptr, *n1 = nullptr;      // the narrow slabs
+    int cn = 0;                                    // their row width
+    bool time_major = false;                       // as SeqFwd's
+};
+hipError_t slab_prewarm(const float* wide, int cw, float* sink, int B, int T, hipStream_t s, const Prewarm& o = {});
 
 // ---------------------------------------------------------------- input_grads.hip (gradients w.r.t. the network inputs, on request)
 // conv weight [Co][Ci][5] -> input-gradient pack wb [Ci][5][Co] (taps flipped) alone, any Ci / Co (the layer-0 blocks)

@@ -129,40 +129,7 @@ __device__ __forceinline__ int lds_peek(const int* p) {
     return v;
 }
 
-__device__ __forceinline__ void store_sc1(float* p, float v) {
-    __hip_atomic_store(reinterpret_cast<unsigned*>(p), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// exact 3-way truncation split of fp32 into bf16 pieces x = h + m + l (see gemm_bf16x3.hip); returns the three 16-bit patterns
-__device__ __forceinline__ void split1(float x, unsigned& h, unsigned& m, unsigned& l) {
-    const unsigned b = __float_as_uint(x);
-    const float r = x - __uint_as_float(b & 0xFFFF0000u);
-    const unsigned c = __float_as_uint(r);
-    const float q = r - __uint_as_float(c & 0xFFFF0000u);
-    h = b >> 16;
-    m = c >> 16;
-    l = __float_as_uint(q) >> 16;
-}
-
-// eight fp32 values -> three bf16x8 MFMA fragments
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8& fh, bf16x8& fm, bf16x8& fl) {
-    u32x4 H4, M4, L4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        unsigned h0, m0, l0, h1, m1, l1;
-        split1(x[2 * i], h0, m0, l0);
-        split1(x[2 * i + 1], h1, m1, l1);
-        H4[i] = h0 | (h1 << 16);
-        M4[i] = m0 | (m1 << 16);
-        L4[i] = l0 | (l1 << 16);
-    }
-    fh = __builtin_bit_cast(bf16x8, H4);
-    fm = __builtin_bit_cast(bf16x8, M4);
-    fl = __builtin_bit_cast(bf16x8, L4);
-}
 
 // fp16 x 2 split (forward recurrence: |h| < 1 and the weights are bounded, so fixed power-of-two scales are safe):
 // y = scale * x = h + l, h = fp16(y) to nearest, l = fp16(y - h): 22 significand bits where the residual is a normal fp16
@@ -188,12 +155,6 @@ __device__ __forceinline__ void split8_f16(const float (&x)[8], float scale, f16
     fh = __builtin_bit_cast(f16x8, H4);
     fl = __builtin_bit_cast(f16x8, L4);
 }
-__device__ __forceinline__ f32x4 mfma3(const f16x8 (&a)[2], const f16x8 (&b)[2], f32x4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[1], acc, 0, 0, 0);     // h.l
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], b[0], acc, 0, 0, 0);     // l.h
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[0], acc, 0, 0, 0);     // h.h   (l.l is below 2^-22)
-    return acc;
-}
 // max over the 16 lanes of a row (all lanes get it); v >= 0, so the bit patterns order like the values
 __device__ __forceinline__ float row16_max(float v) {
     int x = __float_as_int(v);
@@ -203,8 +164,8 @@ __device__ __forceinline__ float row16_max(float v) {
     x = max(x, __builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, true));      // row_ror:8
     return __int_as_float(x);
 }
-// The same three products for N independent accumulators, interleaved so that consecutive MFMAs never depend on each other;
-// per accumulator the order of the terms is that of mfma3 (bit-identical results).
+// acc[i] += a . b(i) for N independent accumulators from three products of the fp16 pieces (l.l is below 2^-22), interleaved so that
+// consecutive MFMAs never depend on each other; per accumulator the order of the terms is h.l, l.h, h.h.
 template <int N, typename BF>
 __device__ __forceinline__ void mfma3_each(const f16x8 (&a)[2], BF&& b, f32x4 (&acc)[N]) {
 #pragma unroll
@@ -233,21 +194,6 @@ __device__ __forceinline__ void load2x2_sc1(const unsigned char* p0, const unsig
         : "memory");
 }
 
-// N 16-byte write-through-coherent loads 1 KiB apart from each base, issued and waited for inside ONE asm statement:
-// hipcc does not track asm loads, so the destination registers must not be visible to it before the data has landed.
-__device__ __forceinline__ void load2x3_sc1(const unsigned char* p0, const unsigned char* p1, const unsigned char* p2, u32x4 (&r)[2][3]) {
-    asm volatile(
-        "global_load_dwordx4 %0, %6, off sc1\n\t"
-        "global_load_dwordx4 %1, %7, off sc1\n\t"
-        "global_load_dwordx4 %2, %8, off sc1\n\t"
-        "global_load_dwordx4 %3, %6, off offset:1024 sc1\n\t"
-        "global_load_dwordx4 %4, %7, off offset:1024 sc1\n\t"
-        "global_load_dwordx4 %5, %8, off offset:1024 sc1\n\t"
-        "s_waitcnt vmcnt(0)"
-        : "=&v"(r[0][0]), "=&v"(r[0][1]), "=&v"(r[0][2]), "=&v"(r[1][0]), "=&v"(r[1][1]), "=&v"(r[1][2])
-        : "v"(p0), "v"(p1), "v"(p2)
-        : "memory");
-}
 __device__ __forceinline__ void load4_sc1(const unsigned char* p, u32x4 (&r)[4]) {
     asm volatile(
         "global_load_dwordx4 %0, %4, off sc1\n\t"
@@ -267,17 +213,6 @@ __device__ __forceinline__ void load2_sc1(const unsigned char* p, u32x4 (&r)[2])
         : "=&v"(r[0]), "=&v"(r[1])
         : "v"(p)
         : "memory");
-}
-
-// fp32-grade product on the bf16 pipe: acc += a . b with a = (ah, am, al), b = (bh, bm, bl); smallest terms first
-__device__ __forceinline__ f32x4 mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], acc, 0, 0, 0);
-    return acc;
 }
 
 // XCD the workgroup runs on.  The L2 is shared (and coherent) inside one XCD only: a group whose members all sit on the
@@ -1084,25 +1019,32 @@ long lstm_seq_xbytes(int B, int H, bool backward) {
 }
 
 static int seq_slots(int nbt) { return 2 * nbt <= 8 ? 8 : 2 * nbt; }       // group slots per member index (see the kernels)
-static int seq_prio_arg(bool time_major, bool img_bf16 = false) {
+// the kernels' prio word; bit 31 is the forward's SeqFwd::img_bf16 and the backward's SeqBwd::img_only (which needs a dimg)
+static int seq_prio_arg(bool time_major, bool bit31) {
     return (int)((unsigned)(g_seq_prio & 0xFFFF) | ((unsigned)(g_seq_spin_log2 & 31) << 16) | (time_major ? 1u << 21 : 0u) |      // (bits 22-26, the backward kernel's warm-up lead: 0 = its default)
-                 ((unsigned)(g_seq_var & 15) << 27) | (img_bf16 ? 1u << 31 : 0u));
+                 ((unsigned)(g_seq_var & 15) << 27) | (bit31 ? 1u << 31 : 0u));
 }
+static int seq_prio_arg(const SeqFwd& o) { return seq_prio_arg(o.time_major, o.img_bf16); }
+static int seq_prio_arg(const SeqBwd& o) { return seq_prio_arg(o.time_major, o.dimg && o.img_only); }
 
-hipError_t lstm_seq_fwd(float* gates, const float* whh_f, const float* whh_b, void* xbuf, float* out, float* csave,
-                        unsigned* sync, unsigned* sticky, const float* xc, int xf, float* out_img, int B, int T, int H, bool zero_state,
-                        bool time_major, hipStream_t s, int img_bf16, const int* len) {
+hipError_t lstm_seq_fwd(float* gates, const float* whh_f, const float* whh_b, void* xbuf, float* out, float* csave, unsigned* sync, int B, int T, int H,
+                        hipStream_t s, const SeqFwd& o) {
+    unsigned* sticky = o.sticky;
+    const float* xc = o.xc;
+    const int xf = o.xf;
+    float* out_img = o.out_img;
+    const int* len = o.len;
     if (xc && (xf < 1 || T % xf)) return hipErrorInvalidValue;
     const int nbt = (B + 15) / 16;
     if (!lstm_seq_supported(B, H)) return hipErrorInvalidValue;
-    if (zero_state) {
+    if (!o.state_zeroed) {
         hipError_t e = hipMemsetAsync(sync, 0, LSTM_SEQ_SYNC_WORDS * sizeof(unsigned), s);
         if (e == hipSuccess) e = hipMemsetAsync(xbuf, 0, lstm_seq_xbytes(B, H, false), s);
         if (e != hipSuccess) return e;
     }
     unsigned char* xb = static_cast<unsigned char*>(xbuf);
-    const int pa = seq_prio_arg(time_major, (img_bf16 & 1) != 0);
-    const bool hi = (img_bf16 & 2) != 0;              // 16-bit data path: the recurrent product from the high fp16 pieces alone
+    const int pa = seq_prio_arg(o);
+    const bool hi = o.hi_only;                        // 16-bit data path: the recurrent product from the high fp16 pieces alone
     // Measured (tools/kbench.py seqtag, us per step flags -> tagged): groups that sit on one XCD each (B = 64: 8 groups under the
     // round-robin placement) 2.47 -> 2.03; groups that span XCDs, whose polls and write-through payload cross the fabric,
     // 3.10 -> 3.23 (B = 16) and 3.00 -> 3.47 (B = 48).  The backward gains either way (3.13 -> 2.98, 3.40 -> 2.49, 4.13 -> 3.25).
@@ -1118,23 +1060,24 @@ hipError_t lstm_seq_fwd(float* gates, const float* whh_f, const float* whh_b, vo
     return hipGetLastError();
 }
 
-hipError_t lstm_seq_bwd(float* gates, const float* whh_f, const float* whh_b, void* xbuf, const float* d_out,
-                        const float* csave, unsigned* sync, unsigned* sticky, float* amax, float* gbias_f, float* gbias_b, float* dgs, int xf,
-                        int B, int T, int H, bool zero_state, bool time_major, hipStream_t s, float* dimg, int hi) {
+hipError_t lstm_seq_bwd(float* gates, const float* whh_f, const float* whh_b, void* xbuf, const float* d_out, const float* csave, unsigned* sync, int B,
+                        int T, int H, hipStream_t s, const SeqBwd& o) {
+    unsigned* sticky = o.sticky;
+    float *gbias_f = o.gbias_f, *gbias_b = o.gbias_b, *dgs = o.dgs, *dimg = o.dimg;
+    const int xf = o.xf;
     if (dgs && (xf < 1 || T % xf)) return hipErrorInvalidValue;
     const int nbt = (B + 15) / 16;
     if (!lstm_seq_supported(B, H)) return hipErrorInvalidValue;
-    if (zero_state) {
+    if (!o.state_zeroed) {
         hipError_t e = hipMemsetAsync(sync, 0, LSTM_SEQ_SYNC_WORDS * sizeof(unsigned), s);
         if (e == hipSuccess) e = hipMemsetAsync(xbuf, 0, lstm_seq_xbytes(B, H, true), s);       // every tag starts at 0
         if (e != hipSuccess) return e;
     }
     unsigned char* xb = static_cast<unsigned char*>(xbuf);
-    unsigned* am = reinterpret_cast<unsigned*>(amax);
+    unsigned* am = reinterpret_cast<unsigned*>(o.amax);
     const dim3 grid(seq_slots(nbt) * (H / 16)), block(640);
-    const int pa = seq_prio_arg(time_major, dimg != nullptr && (hi & 4) != 0);       // hi bit 2: skip the fp32 copy of the gradients (bit 31 of the kernel's prio word)
-    hi &= 1;
-    if (hi) {
+    const int pa = seq_prio_arg(o);
+    if (o.hi_only) {
         if (H == 512) hipLaunchKernelGGL((lstm_seq_bwd_kernel<512, 8, true>), grid, block, 0, s, gates, whh_f, whh_b, xb, d_out, csave, sync, sticky, am, gbias_f, gbias_b, dgs, xf, B, T, nbt, pa, dimg);
         else          hipLaunchKernelGGL((lstm_seq_bwd_kernel<256, 8, true>), grid, block, 0, s, gates, whh_f, whh_b, xb, d_out, csave, sync, sticky, am, gbias_f, gbias_b, dgs, xf, B, T, nbt, pa, dimg);
     } else if (H == 512) hipLaunchKernelGGL((lstm_seq_bwd_kernel<512, 8, false>), grid, block, 0, s, gates, whh_f, whh_b, xb, d_out, csave, sync, sticky, am, gbias_f, gbias_b, dgs, xf, B, T, nbt, pa, dimg);
@@ -1174,10 +1117,10 @@ int lstm_seq_free_xcds(int B, int H) {
     return 8 - 2 * nbt;
 }
 
-hipError_t slab_prewarm(const float* wide, int cw, const float* n0, const float* n1, int cn, float* sink, int B, int T, bool time_major, hipStream_t s) {
-    if (cw % 4 || cn % 4) return hipErrorInvalidValue;
+hipError_t slab_prewarm(const float* wide, int cw, float* sink, int B, int T, hipStream_t s, const Prewarm& o) {
+    if (cw % 4 || o.cn % 4) return hipErrorInvalidValue;
     const int chunks = ((T + 1) / 2 + PREWARM_R - 1) / PREWARM_R;
-    hipLaunchKernelGGL(slab_prewarm_kernel, dim3(chunks * B), dim3(256), 0, s, wide, cw, n0, n1, cn, sink, B, T, time_major ? 1 : 0);
+    hipLaunchKernelGGL(slab_prewarm_kernel, dim3(chunks * B), dim3(256), 0, s, wide, cw, o.n0, o.n1, o.cn, sink, B, T, o.time_major ? 1 : 0);
     return hipGetLastError();
 }
 

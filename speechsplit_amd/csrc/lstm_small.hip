@@ -25,8 +25,6 @@ int g_small_lds = 1;     // 1: LDS-staged kernels (single-wave variant where it 
 
 namespace {
 
-__device__ __forceinline__ float sigmoidf_(float x) { return ss_sigmoid(x); }
-
 // Ragged eval-mode batches (len != nullptr; forward kernels only).  A workgroup owns one (utterance, direction), so the row's length
 // L = min(max(len[b], 0), T) is uniform in it and the predicate "state := 0 at frames t >= L" needs no per-step select: the forward
 // direction walks frames 0 .. L-1, the reverse direction L-1 .. 0 -- both from the zero state, which is what the masked walk over all T
