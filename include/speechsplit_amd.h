@@ -63,9 +63,29 @@ typedef struct ss_hparams {
 const char* ss_last_error(void);
 int ss_abi_version(void);
 
-/* model.py:285-295 / 327-334 (constructor).  No device memory is touched until ss_bind.
- * The bottleneck widths hp->dim_neck, dim_neck_2 and dim_neck_3 may each be any of 1..32 (the reference takes any positive value; wider
- * bottlenecks are refused).  The down-sampling factors freq, freq_2 and freq_3 may differ; every T must be a multiple of all three. */
+/* model.py:285-295 / 327-334 (constructor).  No device memory is touched until ss_bind.  What each field of ss_hparams may be; anything
+ * else returns NULL with an ss_last_error() that names the field and the accepted set, before anything is built (DESIGN.md section 1
+ * has the audit behind every bound, tests/test_capi_hparams.py and tests/test_gpu_hparams.py a test at a non-default value of every free
+ * field and a refusal test of every bound):
+ *   dim_neck, dim_neck_2, dim_neck_3   free: each any of 1..32 (the reference takes any positive value; wider bottlenecks are refused).
+ *   freq, freq_2, freq_3               free: may differ; every T must be a multiple of all three (checked per call).
+ *   dim_enc, dim_enc_2, dim_enc_3      free: each a multiple of 64 in 64..1024 (the GroupNorm kernels work on 64-channel tiles).
+ *   dim_freq                           free: a multiple of 4 in 32..512.  The mel slabs' rows are dim_freq floats apart and each tap of a
+ *                                      layer-0 convolution reads dim_freq rounded up to 4 columns of them: another width would read past
+ *                                      the rows, and behind the slab's last row past the slab.
+ *   dim_spk_emb                        free: 1..1024, odd values included (one thread per column in the speaker-gradient kernel).
+ *   dim_f0                             Generator_3: FIXED at 257 -- the training step quantises the resampled F0 itself into 256 bins plus
+ *                                      unvoiced (utils.py:62-74).  Generator_6, which takes the one-hot and the target index as inputs:
+ *                                      free in 32..512; target indices must lie in [0, dim_f0).
+ *   chs_grp                            FIXED at 16.
+ *   min_len_seg, max_len_seg           free: 1 <= min_len_seg < max_len_seg <= 32 (segment lengths are drawn from [min_len_seg,
+ *                                      max_len_seg), model.py:399-402; a segment's 2 * max_len_seg candidate positions are the lanes of
+ *                                      one wavefront).
+ *   max_len_seq                        free: 1..512.  An utterance is resampled in S = max_len_seq / min_len_seg + 1 segments
+ *                                      (model.py:365): every `[B*7]` below is [B*S], 7 at the defaults.
+ *   max_len_pad                        free: 1..512; a training step runs with T == max_len_pad (or SS_STEP_BUCKET).
+ * Wherever this header writes 80, 82, 257 or 337 for a tensor's last dimension it means dim_freq, dim_spk_emb, dim_f0 and
+ * dim_freq + dim_f0.  max_batch >= 1, 8 <= max_frames <= 256.  The decoders' widths (512 / 256) are not in the struct. */
 ss_engine* ss_create(int kind, const ss_hparams* hp, int max_batch, int max_frames);
 void ss_destroy(ss_engine* e);
 

@@ -64,10 +64,11 @@ def tensor_stats(t):
                 pos=pos.tolist(), val=[float(a[p]) for p in pos])
 
 
-def synth_batch(seed, B, T, len_lo=64):
-    """Synthetic batch as SURVEY.md section 8(d) / BASELINE.md section 4 describes it."""
+def synth_batch(seed, B, T, len_lo=64, dim_freq=80, dim_spk_emb=82):
+    """Synthetic batch as SURVEY.md section 8(d) / BASELINE.md section 4 describes it; dim_freq / dim_spk_emb: the mel and speaker widths of
+    a non-default hparams set (the generator calls, and so the default batch, stay as they are)."""
     g = torch.Generator().manual_seed(seed)
-    mel = torch.rand(B, T, 80, generator=g)
+    mel = torch.rand(B, T, dim_freq, generator=g)
     f0 = torch.rand(B, T, 1, generator=g)
     uv = torch.rand(B, T, 1, generator=g) < 0.4
     lens = torch.randint(len_lo, T + 1, (B,), generator=g)
@@ -75,8 +76,8 @@ def synth_batch(seed, B, T, len_lo=64):
     pad = tt >= lens[:, None, None]
     f0 = torch.where(uv | pad, torch.full_like(f0, -1e10), f0)
     mel = torch.where(pad, torch.zeros_like(mel), mel)
-    spk = torch.randint(0, 82, (B,), generator=g)
-    emb = torch.nn.functional.one_hot(spk, 82).float()
+    spk = torch.randint(0, dim_spk_emb, (B,), generator=g)
+    emb = torch.nn.functional.one_hot(spk, dim_spk_emb).float()
     return mel, f0, emb, lens
 
 

@@ -2392,19 +2392,38 @@ ss_engine* ss_create(int kind, const ss_hparams* hp, int max_batch, int max_fram
         fail("ss_create: kind must be SS_GENERATOR_3, SS_GENERATOR_6 or SS_INTERP_ONLY");
         return nullptr;
     }
-    if (hp->chs_grp != 16 || hp->dim_enc % 64 || hp->dim_enc_2 % 64 || hp->dim_enc_3 % 64) {
-        fail("ss_create: this build needs chs_grp == 16 and conv widths that are multiples of 64");
+    // Every field is either inside the set the header states for it or refused here, before anything is built ("Hyper-parameters", has
+    // the kernel-by-kernel audit behind each bound)
+    auto refuse = [](const char* msg) -> ss_engine* {
+        fail(msg);
         return nullptr;
-    }
-    if (2 * hp->max_len_seg > 64 || hp->max_len_pad > 512 || max_frames > 256 || max_frames < 8 || max_batch < 1) {
-        fail("ss_create: limits are 2*max_len_seg <= 64, max_len_pad <= 512, 8 <= max_frames <= 256");
-        return nullptr;
-    }
+    };
+    if (hp->chs_grp != 16) return refuse("ss_create: chs_grp must be 16 (the GroupNorm kernels work on 64-channel tiles of four 16-channel groups)");
+    for (int c : {hp->dim_enc, hp->dim_enc_2, hp->dim_enc_3})
+        if (c < 64 || c > 1024 || c % 64) return refuse("ss_create: conv widths (dim_enc, dim_enc_2, dim_enc_3) must be multiples of 64 in 64..1024");
+    if (hp->max_len_pad < 1 || hp->max_len_pad > 512 || max_frames > 256 || max_frames < 8 || max_batch < 1)
+        return refuse("ss_create: limits are 1 <= max_len_pad <= 512, 8 <= max_frames <= 256, max_batch >= 1");
+    // InterpLnr (model.py:365, 389, 399-402): the plan kernel gives every candidate position of a segment one lane of a wavefront
+    // (2 * max_len_seg <= 64), the segment count is max_len_seq / min_len_seg + 1 and the lengths are drawn from [min_len_seg, max_len_seg)
+    if (hp->min_len_seg < 1 || hp->min_len_seg >= hp->max_len_seg || hp->max_len_seg > 32)
+        return refuse("ss_create: segment lengths must satisfy 1 <= min_len_seg < max_len_seg <= 32");
+    if (hp->max_len_seq < 1 || hp->max_len_seq > 512) return refuse("ss_create: max_len_seq must be in 1..512");
     for (int hdim : {hp->dim_neck, hp->dim_neck_2, hp->dim_neck_3}) {
-        if (hdim < 1 || hdim > 32) {      // the encoder BLSTMs' single-launch recurrences and fused weight gradients (H <= 32)
-            fail("ss_create: bottleneck widths (dim_neck, dim_neck_2, dim_neck_3) must be in 1..32");
-            return nullptr;
-        }
+        if (hdim < 1 || hdim > 32)      // the encoder BLSTMs' single-launch recurrences and fused weight gradients (H <= 32)
+            return refuse("ss_create: bottleneck widths (dim_neck, dim_neck_2, dim_neck_3) must be in 1..32");
+    }
+    if (kind != SS_INTERP_ONLY) {
+        // the mel slabs' rows are dim_freq floats apart and the k = 5 convolutions read align4(dim_freq) columns per tap: a width that is no
+        // multiple of 4 would read past each row and, at the slab's last row, past the slab; K segments shorter than a k-tile (32) never ran
+        if (hp->dim_freq < 32 || hp->dim_freq > 512 || hp->dim_freq % 4)
+            return refuse("ss_create: dim_freq must be a multiple of 4 in 32..512");
+        // one thread per speaker column in the speaker-gradient kernel's 1024-thread workgroup
+        if (hp->dim_spk_emb < 1 || hp->dim_spk_emb > 1024) return refuse("ss_create: dim_spk_emb must be in 1..1024");
+        // Generator_3 quantises the resampled F0 itself into 256 bins + unvoiced (utils.py:62-74); Generator_6 takes the one-hot as an input
+        if (kind == SS_GENERATOR_3 && hp->dim_f0 != 257)
+            return refuse("ss_create: dim_f0 must be 257 for Generator_3 (the F0 quantiser has 256 bins plus unvoiced)");
+        if (kind == SS_GENERATOR_6 && (hp->dim_f0 < 32 || hp->dim_f0 > 512))
+            return refuse("ss_create: dim_f0 must be in 32..512 for Generator_6");
     }
     ss_engine* e = new ss_engine();
     e->kind = kind;

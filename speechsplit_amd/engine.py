@@ -7,8 +7,9 @@ import numpy as np
 import torch
 
 from . import _capi
+from .hparams import check_hparams  # noqa: F401  (the host-side form of the refusals Engine() raises)
 
-KIND = {'G3': 3, 'G6': 6, 'interp': 0}
+KIND ={'G3': 3, 'G6': 6, 'interp': 0}
 RAGGED = ('ragged',)                   # Engine._fwd_bt after a forward over per-row lengths: there is no backward for it
 
 

@@ -53,6 +53,22 @@ def default_hparams(**over):
     return hp
 
 
+def check_hparams(kind, hp, max_batch=1, max_frames=None):
+    """Raise ValueError with the library's own message -- it names the field and the accepted values (include/speechsplit_amd.h,
+    ss_create) -- for hyper-parameters the engine refuses; Engine(kind, hp, ...) raises the same text.  kind: 'G3', 'G6' or 'interp'.
+    Host only: no device is touched.  Returns hp."""
+    import ctypes
+    from . import _capi
+    lib = _capi.lib()
+    hps = _capi.hparams_struct(hp)
+    frames = int(max_frames or min(max(int(hp.max_len_pad), 8), 256))
+    h = lib.ss_create({'G3': 3, 'G6': 6, 'interp': 0}[kind], ctypes.byref(hps), int(max_batch), frames)
+    if not h:
+        raise ValueError('speechsplit_amd: ' + lib.ss_last_error().decode())
+    lib.ss_destroy(h)
+    return hp
+
+
 hparams = default_hparams()
 
 
