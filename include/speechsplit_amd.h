@@ -451,7 +451,14 @@ int ss_tune(const char* key, int value);
  *   Contractions without images (layer-0 convolutions over the 80 / 264-channel inputs, the decoder's 164-column layer-0 input, the head's
  *   weights, the encoder BLSTM projections) round their fp32 operands to bf16 inside round 2's GEMM kernel; the encoder BLSTMs' weight
  *   gradients are exact fp32 sums in both modes (csrc/lstm_wgrad.hip).  ss_tune("bf16_img", 0) selects round 3's form of the
- *   mode (fp32 slabs only, operands rounded inside the GEMM, fp16 x 2 recurrences) for A/B runs. */
+ *   mode (fp32 slabs only, operands rounded inside the GEMM, fp16 x 2 recurrences) for A/B runs.
+ * When it may be called.  On any engine, bound or not, stepped or not, BETWEEN steps or accumulation cycles.  The two modes lay the image
+ *   buffers out differently, so the next call that runs a forward (train step, ss_*_forward*, ss_g3_rhythm*) plans the workspace again and
+ *   re-zeroes it, as after a change of (B, T): its result does not depend on what the engine ran in the other mode
+ *   (tests/test_gpu_same_shape_history.py).  That costs one memset per switch (0.1 - 0.2 ms) and nothing per step; the same holds for
+ *   ss_tune("bf16_img").  A change of the precision DISCARDS the forward in flight: a forward of one precision cannot be differentiated
+ *   in the other, so ss_*_backward*, ss_train_finish after it fail ("without a preceding ...") until a new forward has run.  Setting
+ *   the precision the engine already has changes nothing. */
 #define SS_PRECISION_F32 0
 #define SS_PRECISION_BF16 1
 int ss_set_precision(ss_engine* e, int precision);

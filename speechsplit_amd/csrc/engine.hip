@@ -275,6 +275,7 @@ struct ss_engine {
     char* ws = nullptr;
     long ws_bytes = 0;
     int curB = 0, curT = 0;
+    int cur_img16 = -1;                    // img16() when geometry() last zeroed the plan: the byte layout the zero halo rows of the images hold for
     // ---- what a forward leaves for its backward (possibly a later ABI call): set by forward_core, cleared as a whole wherever the
     // geometry or the workspace changes
     struct FwdState {
@@ -729,15 +730,20 @@ int geometry(ss_engine* e, int B, int T, hipStream_t s, bool eval = false) {
     if (T > SS_MAX_EVAL_FRAMES) return fail("eval-mode forward: T above SS_MAX_EVAL_FRAMES (8192)");
     if (e->kind != SS_INTERP_ONLY && (T % e->hp.freq || T % e->hp.freq_2 || T % e->hp.freq_3))
         return fail("T must be a multiple of the code down-sampling factors (model.py:87,223-227)");
-    if (B == e->curB && T == e->curT) return 0;
+    // The plan is what was zeroed: the shape AND the image format.  The 16-bit data path reads the image buffers as plain bf16 tensors at
+    // half the byte offsets (ioff), so after a switch of ss_set_precision / ss_tune("bf16_img") the byte ranges that are halo rows in the
+    // new layout hold pieces of real rows written in the old one -- and no producer of an image ever writes a halo row.
+    const int img16 = e->img16() ? 1 : 0;
+    if (B == e->curB && T == e->curT && img16 == e->cur_img16) return 0;
     const long need = carve(std::as_const(*e), B, T);
     if (need > e->ws_bytes) return fail("workspace too small for this batch / frames: grow it to ss_plan_bytes(B, T) with ss_set_workspace");
-    // new geometry: halo rows move, so everything the new plan uses, except the Adam state (first 256 bytes), is re-zeroed
-    // (0.1 - 0.2 ms per switch at batch 64: the price of a length-bucket change, SS_STEP_BUCKET)
+    // new geometry or image format: halo rows move, so everything the new plan uses, except the Adam state (first 256 bytes), is re-zeroed
+    // (0.1 - 0.2 ms per switch at batch 64: the price of a length-bucket change, SS_STEP_BUCKET, or of a precision switch)
     HIPCHK(hipMemsetAsync(e->ws + 256, 0, need - 256, s));
     carve(*e, B, T);
     e->curB = B;
     e->curT = T;
+    e->cur_img16 = img16;
     e->fwd = {};
     return 0;
 }
@@ -3094,6 +3100,7 @@ int ss_op_gemm_img(const float* a_img, long lda, const float* b_img, long ldb, f
 int ss_set_precision(ss_engine* e, int precision) {
     if (!e) return fail("ss_set_precision: null engine");
     if (precision != SS_PRECISION_F32 && precision != SS_PRECISION_BF16) return fail("ss_set_precision: unknown precision");
+    if (precision != e->precision) e->fwd = {};      // a forward of the other precision cannot be differentiated: its backward is refused
     e->precision = precision;
     return 0;
 }

@@ -356,7 +356,9 @@ def test_history_independence_is_bit_exact_in_deterministic_mode(E, kind):
     """ss_tune("deterministic", 1): a fresh engine A and an engine B that has first run a larger bucket, a bf16 step (then back to f32), an
     input-gradient backward and a long eval forward that moved its workspace -- then weights reloaded, Adam moments zeroed, step counter 0 --
     run the same three train steps at a (B, T) below the maximum: losses and parameter arenas bit-identical.  The split-K choice of a
-    contraction is a function of its shape alone (engine.hip pick_ksplit), not of the workspace size, so A keeps its ordinary workspace."""
+    contraction is a function of its shape alone (engine.hip pick_ksplit), not of the workspace size, so A keeps its ordinary workspace.
+    Every switch of precision or call kind here coincides with a change of (B, T), which re-zeroes the workspace (engine.hip geometry):
+    history at an UNCHANGED shape is what tests/test_gpu_same_shape_history.py holds."""
     Bm, Tm, B, T = 12, 192, 6, 128
     hp = W.default_hparams(max_len_pad=Tm)
     step = g3_step if kind == 'G3' else g6_step
