@@ -304,6 +304,35 @@ int ss_melspec(const double* wav_dev, int n, const double* mel_basis_dev, int n_
  * [-1, 1] and mapped to [0, 1] for voiced frames, mean / std over the voiced frames (utils.py:35-42). */
 int ss_f0_normalize(const double* f0_dev, int n, float* out_dev, void* stream);
 
+/* ---- Griffin-Lim vocoder: mel spectrograms back to waveforms (the checkpoint-free stand-in for demo.ipynb's WaveNet cell) ----
+ * The inverse of ss_melspec's chain: mel [0, 1] -> amplitude 10^((100 mel - 100 + 16) / 20) -> linear magnitude through a CALLER-SUPPLIED
+ * float64 inv_basis [n_mels][513] (the Python layer passes numpy.linalg.pinv of the [513][n_mels] basis), floored at `floor` >= 0 ->
+ * Griffin-Lim with momentum as published (Perraudin et al. 2013, librosa's form) over ss_melspec's STFT (reflect padding by 512, periodic
+ * Hann window, 1024-point transform, hop 256) and its inverse (window, overlap-add in frame order, division by the sum of the squared windows
+ * of the frames that cover a sample -- 1.5 inside, down to 1.25 at the kept edges -- trimmed by 512 at both ends):
+ *     ang = exp(i phase0); tprev = 0; n_iter times { r = STFT(ISTFT(mag ang)); a = r - momentum / (1 + momentum) tprev; tprev = r;
+ *     ang = a / (|a| + 1e-16) }; wav = ISTFT(mag ang).
+ * float64 throughout, a real FFT in LDS, no atomics: the same bits on every run.  phase0 [B][max_frames][513] is an input like every draw of
+ * this ABI (NULL: zeros).  No engine needed, no allocation inside, asynchronous on `stream`.
+ * Shapes: mel [B][max_frames][n_mels], mag [B][max_frames][513], spec [B][max_frames][513][2] (re, im),
+ * wav [B][ss_griffinlim_samples(max_frames)]; F frames are 256 (F - 1) samples, and ss_melspec_frames of that is F again.
+ * frames_dev i32[B] (NULL: every row has max_frames): row b is the result of running that utterance alone at
+ * min(max(frames[b], 4), max_frames) frames -- a count outside 4 .. max_frames spoils that row only; mel / mag / spec / phase0 frames at or
+ * beyond it are never read (they may hold NaN), output samples (and mag / spec frames) beyond it are exact zeros.
+ * Refused before anything is enqueued, with a message that names the argument: null required pointers, B < 1, max_frames outside
+ * 4 .. SS_MAX_EVAL_FRAMES, n_mels outside 1 .. 4096, n_iter outside 0 .. 1024, momentum outside [0, 1) or NaN, negative or NaN floor,
+ * scratch_bytes below ss_griffinlim_scratch_bytes(B, max_frames) or scratch_dev not 256-byte aligned. */
+int  ss_griffinlim_samples(int frames);                      /* 256 * (frames - 1); 0 for frames < 4 */
+long ss_griffinlim_scratch_bytes(int B, int max_frames);     /* host only; -1 + ss_last_error on bad arguments */
+int  ss_mel_to_linear(const float* mel_dev, const double* inv_basis_dev, const int* frames_dev, int B, int max_frames,
+                      int n_mels, double floor, double* mag_dev, void* stream);
+int  ss_griffinlim(const double* mag_dev, const double* phase0_dev, const int* frames_dev, int B, int max_frames, int n_iter,
+                   double momentum, double* wav_dev, void* scratch_dev, long scratch_bytes, void* stream);
+/* test hooks, each half alone: spec [B][max_frames][513][2] (re, im); ss_op_istft takes the same scratch as ss_griffinlim */
+int  ss_op_stft (const double* wav_dev,  const int* frames_dev, int B, int max_frames, double* spec_dev, void* stream);
+int  ss_op_istft(const double* spec_dev, const int* frames_dev, int B, int max_frames, double* wav_dev,
+                 void* scratch_dev, long scratch_bytes, void* stream);
+
 /* Batch producer on the GPU side (replaces the host loop of MyCollator.__call__, reference data_loader.py:101-128, for a
  * corpus kept resident in HBM): utterance b of the batch is rows [row0[b], row0[b] + len[b]) of the concatenated corpus
  * mel_cat [rows, n_mel] / f0_cat [rows]; the host only draws the crops (same generator calls, same order as the reference).

@@ -6,7 +6,8 @@ padding / quantisation (``pad_seq_to_2`` to 192 frames, zero-padded F0 -> ``quan
 (``Generator_6`` logits -> argmax -> one-hot) and the same outputs ``[(name, mel[:len])]`` as the notebook.  What differs
 is the schedule: the notebook runs seven batch-1 forwards, here the seven conditions are ONE batch-7 forward of the HIP
 engine (every operator on the path is per-utterance, so the rows are the notebook's results).
-The vocoder cell (WaveNet, external checkpoint) is out of scope.
+The notebook's vocoder cell (WaveNet, external checkpoint) is out of scope; ``conversion_waveforms`` turns the mels into audio with the
+checkpoint-free Griffin-Lim vocoder instead (vocoder.py).
 
 ``convert_batch`` is the same step for MANY pairs: every pair keeps its own ``conversion_frames()`` length and the forwards run as
 ragged eval-mode batches (``lengths=``: every row comes out as if it had been run alone at its own length), sorted by length with
@@ -125,3 +126,19 @@ def convert_batch(G, P, pairs, max_len_pad=192, max_rows=16, device='cuda:0', co
                 keep = prep[k][2][3] if 'R' in c else prep[k][1][3]
                 res[k][n] = ('{}_{}_{}_{}'.format(sbmt_i[0], sbmt_j[0], prep[k][1][4], c), out[m, :keep, :].cpu().numpy())
     return res
+
+
+def conversion_waveforms(results, **kw):
+    """demo_conversion's output ``[(name, mel[len, 80])]`` -> ``[(name, wav float64[256 (len - 1)])]`` at 16 kHz through the Griffin-Lim
+    vocoder; convert_batch's output (one such list per pair) -> one such list per pair.  All the mels go through ONE vocoder.griffin_lim call
+    (ragged batches of at most ``max_rows`` rows); keyword arguments are handed on to it."""
+    from . import vocoder                               # vocoder imports plan_batches from here
+    results = list(results)
+    nested = bool(results) and isinstance(results[0], list)
+    flat = [r for pair in results for r in pair] if nested else results
+    wavs = vocoder.griffin_lim([mel for _, mel in flat], **kw)
+    out = [(name, wav) for (name, _), wav in zip(flat, wavs)]
+    if not nested:
+        return out
+    it = iter(out)
+    return [[next(it) for _ in pair] for pair in results]

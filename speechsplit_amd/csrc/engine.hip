@@ -3006,6 +3006,72 @@ int ss_f0_normalize(const double* f0, int n, float* out, void* stream) {
     return 0;
 }
 
+// ---- Griffin-Lim vocoder (vocoder.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+namespace {
+int voc_shape(const char* who, int B, int max_frames) {
+    if (B < 1 || B > VOC_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
+    if (max_frames < 4 || max_frames > SS_MAX_EVAL_FRAMES)
+        return fail(std::string(who) + ": max_frames outside 4 .. SS_MAX_EVAL_FRAMES (reflect padding needs 4 frames)");
+    return 0;
+}
+int voc_scratch(const char* who, int B, int max_frames, const void* scratch, long scratch_bytes) {
+    if (!scratch) return fail(std::string(who) + ": null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail(std::string(who) + ": scratch_dev is not 256-byte aligned");
+    if (scratch_bytes < vocoder_scratch_bytes(B, max_frames))
+        return fail(std::string(who) + ": scratch_bytes below ss_griffinlim_scratch_bytes(B, max_frames)");
+    return 0;
+}
+}  // namespace
+
+int ss_griffinlim_samples(int frames) { return frames >= 4 ? 256 * (frames - 1) : 0; }
+
+long ss_griffinlim_scratch_bytes(int B, int max_frames) {
+    CHK(voc_shape("ss_griffinlim_scratch_bytes", B, max_frames));
+    return vocoder_scratch_bytes(B, max_frames);
+}
+
+int ss_mel_to_linear(const float* mel, const double* inv_basis, const int* frames, int B, int max_frames, int n_mels, double floor,
+                     double* mag, void* stream) {
+    if (!mel) return fail("ss_mel_to_linear: null pointer: mel_dev");
+    if (!inv_basis) return fail("ss_mel_to_linear: null pointer: inv_basis_dev");
+    if (!mag) return fail("ss_mel_to_linear: null pointer: mag_dev");
+    CHK(voc_shape("ss_mel_to_linear", B, max_frames));
+    if (n_mels < 1 || n_mels > VOC_MAX_MELS) return fail("ss_mel_to_linear: n_mels outside 1 .. 4096");
+    if (!(floor >= 0.0)) return fail("ss_mel_to_linear: floor is negative or NaN");
+    HIPCHK(mel_to_linear(mel, inv_basis, frames, B, max_frames, n_mels, floor, mag, S(stream)));
+    return 0;
+}
+
+int ss_griffinlim(const double* mag, const double* phase0, const int* frames, int B, int max_frames, int n_iter, double momentum,
+                  double* wav, void* scratch, long scratch_bytes, void* stream) {
+    if (!mag) return fail("ss_griffinlim: null pointer: mag_dev");
+    if (!wav) return fail("ss_griffinlim: null pointer: wav_dev");
+    CHK(voc_shape("ss_griffinlim", B, max_frames));
+    if (n_iter < 0 || n_iter > 1024) return fail("ss_griffinlim: n_iter outside 0 .. 1024");
+    if (!(momentum >= 0.0 && momentum < 1.0)) return fail("ss_griffinlim: momentum outside [0, 1) or NaN");
+    CHK(voc_scratch("ss_griffinlim", B, max_frames, scratch, scratch_bytes));
+    HIPCHK(griffinlim(mag, phase0, frames, B, max_frames, n_iter, momentum, wav, vocoder_scratch(scratch, B, max_frames), S(stream)));
+    return 0;
+}
+
+int ss_op_stft(const double* wav, const int* frames, int B, int max_frames, double* spec, void* stream) {
+    if (!wav) return fail("ss_op_stft: null pointer: wav_dev");
+    if (!spec) return fail("ss_op_stft: null pointer: spec_dev");
+    CHK(voc_shape("ss_op_stft", B, max_frames));
+    HIPCHK(stft(wav, frames, B, max_frames, spec, S(stream)));
+    return 0;
+}
+
+int ss_op_istft(const double* spec, const int* frames, int B, int max_frames, double* wav, void* scratch, long scratch_bytes,
+                void* stream) {
+    if (!spec) return fail("ss_op_istft: null pointer: spec_dev");
+    if (!wav) return fail("ss_op_istft: null pointer: wav_dev");
+    CHK(voc_shape("ss_op_istft", B, max_frames));
+    CHK(voc_scratch("ss_op_istft", B, max_frames, scratch, scratch_bytes));
+    HIPCHK(istft(spec, frames, B, max_frames, wav, vocoder_scratch(scratch, B, max_frames).frame_buf, S(stream)));
+    return 0;
+}
+
 int ss_interp_forward(ss_engine* e, const float* x, const int* len_seq, const float* scales, const int* len_seg, int B, int T,
                       int C, float* y, int* i0, float* lam, int* counts, void* stream) {
     Own own(e, stream);

@@ -240,6 +240,30 @@ hipError_t melspec(const double* x, int n, const double* mel, int n_mels, float*
 // utils.py:35-42 with mean / std over the voiced frames (make_spect_f0.py:64-66); -1e10 marks unvoiced frames
 hipError_t f0_normalize(const double* f0, int n, float* out, hipStream_t s);
 
+// ---------------------------------------------------------------- vocoder.hip  (Griffin-Lim: mel -> linear magnitude -> waveform, float64)
+// Shapes: mel [B][max_frames][n_mels] f32, mag [B][max_frames][513], spec [B][max_frames][513][2] (re, im), wav [B][256 (max_frames - 1)].
+// frames (nullable; device i32[B]): row b has F_b = min(max(frames[b], 4), max_frames) frames and 256 (F_b - 1) samples; it is computed as if
+// it were alone, mel / mag / spec / phase0 frames at or beyond F_b are never read, outputs behind a row's own extent are zeros.
+constexpr int VOC_MAX_ROWS = 65535;   // the batch is the grid's y dimension
+constexpr int VOC_MAX_MELS = 4096;    // one frame's amplitudes sit in LDS
+struct VocoderScratch {
+    double* frame_buf;   // [B][max_frames][1024]   window * irfft of every frame, what the overlap-add gathers from
+    double* proj;        // [B][max_frames][513][2] S ang, the spectrum the next ISTFT takes
+    double* tprev;       // [B][max_frames][513][2] the previous round's STFT
+};
+long vocoder_scratch_bytes(int B, int max_frames);
+VocoderScratch vocoder_scratch(void* base, int B, int max_frames);
+// mag = max(floor, 10^((100 mel - 100 + 16) / 20) . inv_basis), inv_basis [n_mels][513]
+hipError_t mel_to_linear(const float* mel, const double* inv_basis, const int* frames, int B, int max_frames, int n_mels, double floor,
+                         double* mag, hipStream_t s);
+// melspec_kernel's framing with a 1024-point FFT in LDS, one workgroup per frame
+hipError_t stft(const double* wav, const int* frames, int B, int max_frames, double* spec, hipStream_t s);
+// window * irfft per frame into frame_buf, then a gather per output sample over the frames that cover it, over the sum of their squared windows
+hipError_t istft(const double* spec, const int* frames, int B, int max_frames, double* wav, double* frame_buf, hipStream_t s);
+// Griffin-Lim with momentum (see vocoder.hip); phase0 [B][max_frames][513] or nullptr (zeros).  1 + 3 n_iter + 2 launches.
+hipError_t griffinlim(const double* mag, const double* phase0, const int* frames, int B, int max_frames, int n_iter, double momentum,
+                      double* wav, const VocoderScratch& sc, hipStream_t s);
+
 // ---------------------------------------------------------------- lstm_small.hip  (hidden <= 32: whole recurrence in one launch)
 // Row stride of a small BLSTM's output, cell-state and output-gradient slabs: 2H for H a power of two (the default widths keep their
 // layout), else 2H rounded up to a multiple of 4 floats (16-byte rows: vector loads and the GEMMs' aligned path).  The padding columns

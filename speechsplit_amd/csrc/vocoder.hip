@@ -1,0 +1,291 @@
+// Griffin-Lim vocoder: mel spectrogram -> linear magnitude -> waveform, the checkpoint-free stand-in for the last cell of the reference's
+// demo.ipynb (which needs wavenet_vocoder and an external checkpoint).  It inverts exactly what features.hip computes: the reference's
+// pySTFT framing (utils.py:18-31: reflect padding by 512, periodic Hann window, 1024-point rfft, hop 256) and the dB / [0, 1] scaling of
+// make_spect_f0.py:59-60.  The algorithm is Griffin-Lim with momentum as published (Perraudin, Balazs, Sondergaard 2013; librosa's form):
+//
+//     ang = exp(i phase0);  tprev = 0
+//     n_iter times:  r = STFT(ISTFT(S ang));  a = r - momentum / (1 + momentum) tprev;  tprev = r;  ang = a / (|a| + 1e-16)
+//     x = ISTFT(S ang)
+//
+// One iteration is three launches: irfft_kernel (one workgroup per frame: S ang -> windowed time frame), ola_kernel (a gather per output
+// sample over the <= 4 frames that cover it, in frame order, divided by the sum of their squared windows; no atomics) and stft_kernel with the
+// projection (a, tprev, S ang) in its epilogue.  Nothing waits across workgroups, so the result is the same bits on every run.
+//
+// Arithmetic: float64 throughout, as features.hip -- the iteration amplifies a transform's rounding by about 10^4 over 32 rounds (measured in
+// numpy), which float32 transforms would turn into an audible-level disagreement with any reference.  The transform is a real FFT:
+// 60 rounds of a transform and its inverse over a batch of conditions is where features.hip's direct DFT (1024 x 513 multiply-adds a frame)
+// stops being cheap.  1024-point complex radix-2 decimation in frequency, in place in LDS, output read in bit-reversed order; the twiddles come
+// from sincospi, exact to double rounding.
+//
+// Batches: row b has its own frame count F_b = min(max(frames[b], 4), max_frames) and n_b = 256 (F_b - 1) samples; every kernel computes row b
+// as if it were alone, never reads a spectrogram frame at or beyond F_b, and writes exact zeros behind n_b.
+#include "common.h"
+#include "kernels.h"
+
+namespace ss {
+
+namespace {
+
+constexpr int NFFT = 1024, HOP = 256, NBIN = NFFT / 2 + 1, LOGN = 10, NT = 256;
+
+struct FftLds {
+    double re[NFFT], im[NFFT];          // the transform, in place
+    double wr[NFFT / 2], wi[NFFT / 2];  // exp(-2 pi i t / 1024), t < 512
+};
+
+__host__ __device__ inline double hann(int i) { return 0.5 - 0.5 * cospi((double)i / (double)(NFFT / 2)); }
+
+__host__ __device__ inline int row_frames(const int* frames, int b, int max_frames) {
+    const int F = frames ? frames[b] : max_frames;
+    return F < 4 ? 4 : (F > max_frames ? max_frames : F);
+}
+
+__host__ __device__ inline int brev10(int k) {
+    unsigned v = (unsigned)k;
+    v = ((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1);
+    v = ((v >> 2) & 0x33333333u) | ((v & 0x33333333u) << 2);
+    v = ((v >> 4) & 0x0F0F0F0Fu) | ((v & 0x0F0F0F0Fu) << 4);
+    v = ((v >> 8) & 0x00FF00FFu) | ((v & 0x00FF00FFu) << 8);
+    v = (v >> 16) | (v << 16);
+    return (int)(v >> (32 - LOGN));
+}
+
+// reflect-padded sample (numpy.pad mode='reflect': the edge sample is not repeated); needs n >= 513
+__host__ __device__ inline double padded(const double* __restrict__ x, int n, int i) {
+    int j = i - NFFT / 2;
+    if (j < 0) j = -j;
+    if (j >= n) j = 2 * (n - 1) - j;
+    return x[j];
+}
+
+// The phases of a transform; the kernels put a workgroup barrier between any two of them.
+__host__ __device__ inline void fft_twiddles(FftLds& L, int tid) {
+    for (int t = tid; t < NFFT / 2; t += NT) {
+        double s, c;
+        sincospi((double)t / (double)(NFFT / 2), &s, &c);
+        L.wr[t] = c;
+        L.wi[t] = -s;
+    }
+}
+
+// stage s of 10: butterflies of span 512 >> s; inverse conjugates the twiddles.  X[k] ends up at brev10(k).
+__host__ __device__ inline void fft_stage(FftLds& L, int tid, int s, bool inverse) {
+    const int half = (NFFT / 2) >> s;
+    for (int b = tid; b < NFFT / 2; b += NT) {
+        const int j = b & (half - 1);
+        const int i0 = ((b - j) << 1) + j, i1 = i0 + half;
+        const double c = L.wr[j << s], sn = inverse ? -L.wi[j << s] : L.wi[j << s];
+        const double ur = L.re[i0], ui = L.im[i0], vr = L.re[i1], vi = L.im[i1];
+        L.re[i0] = ur + vr;
+        L.im[i0] = ui + vi;
+        const double dr = ur - vr, di = ui - vi;
+        L.re[i1] = dr * c - di * sn;
+        L.im[i1] = dr * sn + di * c;
+    }
+}
+
+__host__ __device__ inline void stft_load(FftLds& L, int tid, const double* __restrict__ x, int n, int f) {
+    for (int i = tid; i < NFFT; i += NT) {
+        L.re[i] = hann(i) * padded(x, n, f * HOP + i);
+        L.im[i] = 0.0;
+    }
+}
+
+// bins 0..512 of the frame's transform -> out [513][2].  With the projection (mag != nullptr): a = r - coef tprev, tprev = r,
+// out = mag a / (|a| + 1e-16), the spectrum the next ISTFT takes.
+__host__ __device__ inline void stft_store(const FftLds& L, int tid, double* __restrict__ out, const double* __restrict__ mag,
+                                           double* __restrict__ tprev, double coef) {
+    for (int k = tid; k < NBIN; k += NT) {
+        const int p = brev10(k);
+        const double rr = L.re[p], ri = L.im[p];
+        if (!mag) {
+            out[2 * k] = rr;
+            out[2 * k + 1] = ri;
+            continue;
+        }
+        const double ar = rr - coef * tprev[2 * k], ai = ri - coef * tprev[2 * k + 1];
+        tprev[2 * k] = rr;
+        tprev[2 * k + 1] = ri;
+        const double d = hypot(ar, ai) + 1e-16;
+        out[2 * k] = mag[k] * (ar / d);
+        out[2 * k + 1] = mag[k] * (ai / d);
+    }
+}
+
+// numpy.fft.irfft's reading of a half spectrum: the imaginary parts of bins 0 and 512 are ignored, the rest is mirrored conjugated
+__host__ __device__ inline void irfft_load(FftLds& L, int tid, const double* __restrict__ spec) {
+    for (int k = tid; k < NBIN; k += NT) {
+        const bool edge = k == 0 || k == NFFT / 2;
+        const double r = spec[2 * k], i = edge ? 0.0 : spec[2 * k + 1];
+        L.re[k] = r;
+        L.im[k] = i;
+        if (!edge) {
+            L.re[NFFT - k] = r;
+            L.im[NFFT - k] = -i;
+        }
+    }
+}
+
+__host__ __device__ inline void irfft_store(const FftLds& L, int tid, double* __restrict__ frame) {
+    for (int t = tid; t < NFFT; t += NT) frame[t] = (L.re[brev10(t)] * (1.0 / NFFT)) * hann(t);
+}
+
+// sample j of a row with F frames: the frames that cover padded position j + 512, in frame order, over the sum of their squared windows
+__host__ __device__ inline double ola_sample(const double* __restrict__ fb, int F, int j) {
+    const int p = j + NFFT / 2, q = p / HOP;
+    const int lo = q - 3 > 0 ? q - 3 : 0, hi = q < F - 1 ? q : F - 1;
+    double acc = 0.0, nrm = 0.0;
+    for (int f = lo; f <= hi; ++f) {
+        const int i = p - f * HOP;
+        const double w = hann(i);
+        acc += fb[(long)f * NFFT + i];
+        nrm += w * w;
+    }
+    return acc / nrm;
+}
+
+// grid = (max_frames, B), block = 256.  wav [B][256 (max_frames - 1)]; out / mag / tprev [B][max_frames][513] (x 2 for the complex ones).
+// Plain (mag == nullptr): spec rows at or beyond the row's frames are zeros.  Projection: those blocks touch nothing.
+__global__ __launch_bounds__(NT) void stft_kernel(const double* __restrict__ wav, const int* __restrict__ frames, int max_frames,
+                                                  double* __restrict__ out, const double* __restrict__ mag, double* __restrict__ tprev,
+                                                  double coef) {
+    __shared__ FftLds L;
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int F = row_frames(frames, b, max_frames);
+    const long fr = (long)b * max_frames + f;
+    out += fr * (2 * NBIN);
+    if (f >= F) {
+        if (!mag)
+            for (int k = tid; k < 2 * NBIN; k += NT) out[k] = 0.0;
+        return;
+    }
+    fft_twiddles(L, tid);
+    stft_load(L, tid, wav + (long)b * HOP * (max_frames - 1), HOP * (F - 1), f);
+    __syncthreads();
+    for (int s = 0; s < LOGN; ++s) {
+        fft_stage(L, tid, s, false);
+        __syncthreads();
+    }
+    stft_store(L, tid, out, mag ? mag + fr * NBIN : nullptr, mag ? tprev + fr * (2 * NBIN) : nullptr, coef);
+}
+
+// grid = (max_frames, B), block = 256: spec [B][max_frames][513][2] -> frame_buf [B][max_frames][1024] = window * irfft, frames < F_b only
+__global__ __launch_bounds__(NT) void irfft_kernel(const double* __restrict__ spec, const int* __restrict__ frames, int max_frames,
+                                                   double* __restrict__ frame_buf) {
+    __shared__ FftLds L;
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    if (f >= row_frames(frames, b, max_frames)) return;
+    const long fr = (long)b * max_frames + f;
+    fft_twiddles(L, tid);
+    irfft_load(L, tid, spec + fr * (2 * NBIN));
+    __syncthreads();
+    for (int s = 0; s < LOGN; ++s) {
+        fft_stage(L, tid, s, true);
+        __syncthreads();
+    }
+    irfft_store(L, tid, frame_buf + fr * NFFT);
+}
+
+// grid = (max_frames - 1, B), block = 256: one output sample per thread; zeros behind the row's own samples
+__global__ __launch_bounds__(NT) void ola_kernel(const double* __restrict__ frame_buf, const int* __restrict__ frames, int max_frames,
+                                                 double* __restrict__ wav) {
+    const int b = blockIdx.y, j = blockIdx.x * NT + threadIdx.x;
+    const int F = row_frames(frames, b, max_frames);
+    wav[(long)b * HOP * (max_frames - 1) + j] = j < HOP * (F - 1) ? ola_sample(frame_buf + (long)b * max_frames * NFFT, F, j) : 0.0;
+}
+
+// grid = (max_frames, B), block = 256: proj = mag exp(i phase0) (phase0 == nullptr: mag), tprev = 0, frames < F_b only
+__global__ __launch_bounds__(NT) void gl_init_kernel(const double* __restrict__ mag, const double* __restrict__ phase0,
+                                                     const int* __restrict__ frames, int max_frames, double* __restrict__ proj,
+                                                     double* __restrict__ tprev) {
+    const int f = blockIdx.x, b = blockIdx.y;
+    if (f >= row_frames(frames, b, max_frames)) return;
+    const long fr = (long)b * max_frames + f;
+    for (int k = threadIdx.x; k < NBIN; k += NT) {
+        const double m = mag[fr * NBIN + k];
+        double s = 0.0, c = 1.0;
+        if (phase0) sincos(phase0[fr * NBIN + k], &s, &c);
+        proj[(fr * NBIN + k) * 2] = m * c;
+        proj[(fr * NBIN + k) * 2 + 1] = m * s;
+        tprev[(fr * NBIN + k) * 2] = 0.0;
+        tprev[(fr * NBIN + k) * 2 + 1] = 0.0;
+    }
+}
+
+// grid = (max_frames, B), block = 256, dynamic LDS = n_mels doubles: the inverse of melspec_kernel's last two lines, then the projection
+// onto the linear bins through a caller-supplied [n_mels][513] matrix.  Rows at or beyond the row's frames: mel is not read, mag is zeros.
+__global__ __launch_bounds__(NT) void mel_to_linear_kernel(const float* __restrict__ mel, const double* __restrict__ inv_basis,
+                                                           const int* __restrict__ frames, int max_frames, int n_mels, double floor,
+                                                           double* __restrict__ mag) {
+    extern __shared__ double amp[];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const long fr = (long)b * max_frames + f;
+    if (f >= row_frames(frames, b, max_frames)) {
+        for (int k = tid; k < NBIN; k += NT) mag[fr * NBIN + k] = 0.0;
+        return;
+    }
+    for (int m = tid; m < n_mels; m += NT) amp[m] = pow(10.0, (100.0 * (double)mel[fr * n_mels + m] - 100.0 + 16.0) / 20.0);
+    __syncthreads();
+    for (int k = tid; k < NBIN; k += NT) {
+        double s = 0.0;
+        for (int m = 0; m < n_mels; ++m) s += amp[m] * inv_basis[(long)m * NBIN + k];
+        mag[fr * NBIN + k] = fmax(floor, s);
+    }
+}
+
+constexpr long align256(long n) { return (n + 255) & ~255L; }
+
+}  // namespace
+
+long vocoder_scratch_bytes(int B, int max_frames) {
+    const long fr = (long)B * max_frames;
+    return align256(fr * NFFT * 8) + 2 * align256(fr * NBIN * 16);
+}
+
+VocoderScratch vocoder_scratch(void* base, int B, int max_frames) {
+    const long fr = (long)B * max_frames;
+    char* p = (char*)base;
+    VocoderScratch sc;
+    sc.frame_buf = (double*)p;
+    sc.proj = (double*)(p + align256(fr * NFFT * 8));
+    sc.tprev = (double*)(p + align256(fr * NFFT * 8) + align256(fr * NBIN * 16));
+    return sc;
+}
+
+hipError_t mel_to_linear(const float* mel, const double* inv_basis, const int* frames, int B, int max_frames, int n_mels, double floor,
+                         double* mag, hipStream_t s) {
+    if (B < 1 || B > VOC_MAX_ROWS || max_frames < 4 || n_mels < 1 || n_mels > VOC_MAX_MELS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mel_to_linear_kernel, dim3(max_frames, B), dim3(NT), n_mels * sizeof(double), s, mel, inv_basis, frames, max_frames,
+                       n_mels, floor, mag);
+    return hipGetLastError();
+}
+
+hipError_t stft(const double* wav, const int* frames, int B, int max_frames, double* spec, hipStream_t s) {
+    if (B < 1 || B > VOC_MAX_ROWS || max_frames < 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stft_kernel, dim3(max_frames, B), dim3(NT), 0, s, wav, frames, max_frames, spec, (const double*)nullptr,
+                       (double*)nullptr, 0.0);
+    return hipGetLastError();
+}
+
+hipError_t istft(const double* spec, const int* frames, int B, int max_frames, double* wav, double* frame_buf, hipStream_t s) {
+    if (B < 1 || B > VOC_MAX_ROWS || max_frames < 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(irfft_kernel, dim3(max_frames, B), dim3(NT), 0, s, spec, frames, max_frames, frame_buf);
+    hipLaunchKernelGGL(ola_kernel, dim3(max_frames - 1, B), dim3(NT), 0, s, (const double*)frame_buf, frames, max_frames, wav);
+    return hipGetLastError();
+}
+
+hipError_t griffinlim(const double* mag, const double* phase0, const int* frames, int B, int max_frames, int n_iter, double momentum,
+                      double* wav, const VocoderScratch& sc, hipStream_t s) {
+    if (B < 1 || B > VOC_MAX_ROWS || max_frames < 4 || n_iter < 0) return hipErrorInvalidValue;
+    const dim3 grid(max_frames, B);
+    const double coef = momentum / (1.0 + momentum);
+    hipLaunchKernelGGL(gl_init_kernel, grid, dim3(NT), 0, s, mag, phase0, frames, max_frames, sc.proj, sc.tprev);
+    for (int it = 0; it < n_iter; ++it) {
+        hipError_t e = istft(sc.proj, frames, B, max_frames, wav, sc.frame_buf, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(stft_kernel, grid, dim3(NT), 0, s, (const double*)wav, frames, max_frames, sc.proj, mag, sc.tprev, coef);
+    }
+    return istft(sc.proj, frames, B, max_frames, wav, sc.frame_buf, s);
+}
+
+}  // namespace ss

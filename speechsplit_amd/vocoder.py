@@ -1,0 +1,136 @@
+"""Mel spectrograms back to waveforms: a Griffin-Lim vocoder on the GPU (csrc/vocoder.hip through the C ABI), the checkpoint-free stand-in
+for the last cell of the reference's demo.ipynb (WaveNet with an external checkpoint, which stays out of scope).
+
+It inverts what this project itself defines (features.py / csrc/features.hip): the [0, 1] dB scale and the mel basis of `melspectrogram`,
+and the 1024-point periodic-Hann STFT at hop 256 with reflect padding.  The mel basis is inverted by its pseudo-inverse
+(`numpy.linalg.pinv`; librosa's NNLS is not available), floored, and Griffin-Lim with momentum (Perraudin et al. 2013, librosa's form)
+finds a phase.  L frames become 256 (L - 1) samples, and `melspectrogram` of those has L frames again.  float64 throughout; the same bits on
+every run; the starting phases are inputs, drawn on the host.  No engine needed."""
+import ctypes as C
+import wave
+
+import numpy as np
+import torch
+
+from . import _capi, features
+from .convert import plan_batches
+
+NBIN = 513
+MIN_FRAMES = 4                                     # reflect padding by 512 needs 513 samples
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+_PINV = {}
+
+
+def _inv_basis(mel_basis):
+    """float64 [n_mels, 513]: the pseudo-inverse of the [513, n_mels] basis `melspectrogram` takes (None: the project's own filter bank)"""
+    if mel_basis is None:
+        if None not in _PINV:
+            _PINV[None] = np.linalg.pinv(features.mel_filter_bank().T.astype(np.float64))
+        return _PINV[None]
+    mb = np.asarray(mel_basis, np.float64)
+    if mb.ndim != 2 or mb.shape[0] != NBIN:
+        raise ValueError('mel_basis must be [513, n_mels] (1024-point transform)')
+    return np.linalg.pinv(mb)
+
+
+def _mel_to_linear(mel_dev, inv_dev, frames_dev, floor):
+    """mel_dev float32 [B, T, n_mels], inv_dev float64 [n_mels, 513], frames_dev int32 [B] or None -> float64 [B, T, 513], all on one device"""
+    B, T, n_mels = mel_dev.shape
+    mag = torch.empty(B, T, NBIN, dtype=torch.float64, device=mel_dev.device)
+    _capi.check(_capi.lib().ss_mel_to_linear(_ptr(mel_dev), _ptr(inv_dev), _ptr(frames_dev), B, T, n_mels, float(floor), _ptr(mag), _stream()))
+    return mag
+
+
+def mel_to_linear(mel, mel_basis=None, floor=1e-10, device='cuda'):
+    """mel float [L, n_mels] on `melspectrogram`'s [0, 1] dB scale -> float64 [L, 513] tensor on `device`:
+    max(floor, 10^((100 mel - 100 + 16) / 20) . pinv(mel_basis)).  mel_basis [513, n_mels] defaults to features.mel_filter_bank().T."""
+    m = torch.as_tensor(np.ascontiguousarray(mel, dtype=np.float32)).to(device)
+    if m.dim() != 2 or m.shape[0] < MIN_FRAMES:
+        raise ValueError(f'mel_to_linear: mel must be [L, n_mels] with L >= {MIN_FRAMES}')
+    inv = torch.as_tensor(_inv_basis(mel_basis)).to(device)
+    if inv.shape[0] != m.shape[1]:
+        raise ValueError(f'mel_to_linear: mel has {m.shape[1]} bands, the basis {inv.shape[0]}')
+    return _mel_to_linear(m[None], inv, None, floor)[0]
+
+
+def griffin_lim_mag(mag_dev, phase0_dev, frames_dev, n_iter, momentum):
+    """The C call on device tensors: mag float64 [B, T, 513], phase0 the same or None (zeros), frames int32 [B] or None ->
+    float64 [B, 256 (T - 1)]; row b's samples beyond 256 (frames[b] - 1) are zeros."""
+    lib = _capi.lib()
+    B, T = mag_dev.shape[:2]
+    nbytes = lib.ss_griffinlim_scratch_bytes(B, T)
+    if nbytes < 0:
+        _capi.check(-1)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=mag_dev.device)
+    wav = torch.empty(B, lib.ss_griffinlim_samples(T), dtype=torch.float64, device=mag_dev.device)
+    _capi.check(lib.ss_griffinlim(_ptr(mag_dev), _ptr(phase0_dev), _ptr(frames_dev), B, T, int(n_iter), float(momentum), _ptr(wav),
+                                  _ptr(scratch), nbytes, _stream()))
+    return wav
+
+
+def prepare(mels, phases=None, generator=None):
+    """Host side of griffin_lim: (single, [mel float32 [L, n_mels]], [phase float64 [L, 513]] or None).  phases: None draws uniform
+    [-pi, pi) phases from `generator` (default numpy.random.default_rng(0)) per utterance, in INPUT order -- so the draws, and with them the
+    result, do not depend on how the utterances are batched; 'zero' starts from zero phases; else one [L, 513] array per utterance."""
+    single = not isinstance(mels, (list, tuple))
+    ms = [np.ascontiguousarray(m, dtype=np.float32) for m in ([mels] if single else mels)]
+    for m in ms:
+        if m.ndim != 2 or m.shape[0] < MIN_FRAMES or m.shape[1] != ms[0].shape[1]:
+            raise ValueError(f'griffin_lim: every mel must be [L, n_mels] with L >= {MIN_FRAMES} and one n_mels')
+    if isinstance(phases, str):
+        if phases != 'zero':
+            raise ValueError("griffin_lim: phases is None, 'zero' or one [L, 513] array per utterance")
+        return single, ms, None
+    if phases is None:
+        gen = generator if generator is not None else np.random.default_rng(0)
+        ps = [gen.uniform(-np.pi, np.pi, (m.shape[0], NBIN)) for m in ms]
+    else:
+        ps = [np.ascontiguousarray(p, dtype=np.float64) for p in ([phases] if single else phases)]
+        if len(ps) != len(ms) or any(p.shape != (m.shape[0], NBIN) for p, m in zip(ps, ms)):
+            raise ValueError('griffin_lim: phases must hold one [L, 513] array per utterance')
+    return single, ms, ps
+
+
+def griffin_lim(mels, n_iter=60, momentum=0.99, phases=None, generator=None, max_rows=16, device='cuda', mel_basis=None, floor=1e-10):
+    """One mel [L, 80] (or a list of them, any lengths >= 4) -> float64 numpy waveform(s) of 256 (L - 1) samples at 16 kHz, in input order.
+    The utterances run as ragged batches of at most max_rows rows in convert.plan_batches order; every row is the result of running it alone,
+    so the result does not depend on max_rows.  phases / generator: see prepare()."""
+    single, ms, ps = prepare(mels, phases, generator)
+    inv = torch.as_tensor(_inv_basis(mel_basis)).to(device)
+    if ms and inv.shape[0] != ms[0].shape[1]:
+        raise ValueError(f'griffin_lim: mel has {ms[0].shape[1]} bands, the basis {inv.shape[0]}')
+    out = [None] * len(ms)
+    for batch in plan_batches([m.shape[0] for m in ms], max_rows):
+        lens = [ms[i].shape[0] for i in batch]
+        T = lens[-1]
+        mel = np.zeros((len(batch), T, ms[0].shape[1]), np.float32)
+        ph = np.zeros((len(batch), T, NBIN)) if ps is not None else None
+        for n, i in enumerate(batch):
+            mel[n, :lens[n]] = ms[i]
+            if ph is not None:
+                ph[n, :lens[n]] = ps[i]
+        frames = torch.tensor(lens, dtype=torch.int32, device=device)
+        mag = _mel_to_linear(torch.from_numpy(mel).to(device), inv, frames, floor)
+        wav = griffin_lim_mag(mag, torch.from_numpy(ph).to(device) if ph is not None else None, frames, n_iter, momentum).cpu().numpy()
+        for n, i in enumerate(batch):
+            out[i] = wav[n, :256 * (lens[n] - 1)].copy()
+    return out[0] if single else out
+
+
+def save_wav(path, wav, sr=16000):
+    """16-bit mono PCM through the standard library's `wave`; samples are clipped to [-1, 1]"""
+    pcm = np.round(np.clip(np.asarray(wav, np.float64), -1.0, 1.0) * 32767.0).astype('<i2')
+    with wave.open(path, 'wb') as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(int(sr))
+        f.writeframes(pcm.tobytes())
