@@ -304,6 +304,55 @@ int ss_melspec(const double* wav_dev, int n, const double* mel_basis_dev, int n_
  * [-1, 1] and mapped to [0, 1] for voiced frames, mean / std over the voiced frames (utils.py:35-42). */
 int ss_f0_normalize(const double* f0_dev, int n, float* out_dev, void* stream);
 
+/* ---- pitch tracker: waveforms to F0 tracks (the stand-in for make_spect_f0.py:64's `pysptk.sptk.rapt`, which is not pinned here) ----
+ * The published core of RAPT (Talkin 1995, "A robust algorithm for pitch tracking"): normalised cross-correlation candidates per frame plus
+ * dynamic programming over the frames, with Talkin's published constants.  NOT a port of SPTK's rapt and no parity with it is claimed: RAPT's
+ * spectral-stationarity term (it needs LPC) and its two-rate search are left out.  The output follows RAPT's otype=2 convention -- ln(F0 in
+ * Hz), -1e10 for unvoiced frames, one value per 256-sample hop, ss_melspec_frames(n) values -- so ss_f0_normalize takes it unchanged.
+ *
+ * Constants: fs = 16000, hop = 256, correlation window w = 120, CAND_TR = 0.3, N_CANDS = 20 (19 voiced states plus the unvoiced one),
+ * LAG_WT = 0.3, FREQ_WT = 0.02, DOUBL_C = 0.35, VTRAN_C = 0.005, VTR_A_C = 0.5, VO_BIAS = 0, A_FACT = 10000.
+ * Inputs: x float64 [n], scale (the Python layer passes 32768, as the reference does), lo, hi in Hz.  Lmin = floor(16000 / hi),
+ * Lmax = ceil(16000 / lo), K = Lmax - Lmin + 1, S = w + Lmax, F = n / 256 + 1 = ss_melspec_frames(n).
+ * Per frame i, independent of every other frame:
+ *   1. z_j = scale x[s + j], 0 <= j < S, s = 256 i - S / 2 (integer division), zero wherever s + j is outside [0, n).
+ *      mu = sum_j z_j / S; y = z - mu for all S entries.
+ *   2. e_k = sum_{j=k}^{k+w-1} y_j^2; phi_k = sum_{j<w} y_j y_{j+k} / sqrt(e_0 e_k + A_FACT) for Lmin <= k <= Lmax; phimax = max_k phi_k;
+ *      rms_i = sqrt(sum_{j<S} y_j^2 / S + 1).
+ *   3. Lag k is a voiced candidate when Lmin < k < Lmax, phi_k > phi_{k-1}, phi_k >= phi_{k+1}, phi_k > 0 and phi_k >= CAND_TR phimax.
+ *      den = phi_{k-1} - 2 phi_k + phi_{k+1}; delta = 0.5 (phi_{k-1} - phi_{k+1}) / den if den < 0, else 0; L = k + delta;
+ *      v = phi_k - 0.25 (phi_{k-1} - phi_{k+1}) delta.  The 19 largest v are kept, the smaller lag first on equal v.  State 0 is
+ *      "unvoiced", states 1.. are the kept candidates in that order.
+ *   4. Local cost d(0) = VO_BIAS + max(phimax, 0); d = 1 - v (1 - LAG_WT L / Lmax) for a voiced state.
+ * Over the frames of one utterance: D_0 = d_0; D_i(a) = d_i(a) + min_b [D_{i-1}(b) + t_i(b -> a)], the lowest b on a tie, with
+ * rr_i = rms_i / rms_{i-1} and
+ *      t(unvoiced -> unvoiced) = 0;  t(unvoiced -> voiced) = VTRAN_C + VTR_A_C / rr_i;  t(voiced -> unvoiced) = VTRAN_C + VTR_A_C rr_i;
+ *      t(voiced b -> voiced a) = FREQ_WT min(|xi|, DOUBL_C + |xi - ln 2|, DOUBL_C + |xi + ln 2|), xi = ln(L_a / L_b).
+ * The end state is the argmin of D_{F-1} (the lowest index on a tie); backtrack from there.  f0_i = ln(16000 / L) for a voiced state,
+ * -1e10 for state 0.
+ * Arithmetic: float64, no atomics, the same bits on every run.  Order of the sums: mu and sum y^2 -- thread t of 256 adds its entries
+ * j = t, t + 256, t + 512 in that order, then a pairwise tree over the 256 partials (t += t + s, s = 128, 64 .. 1); the three w-long sums of a
+ * lag (sum y_j y_{j+k}, e_k and e_0; e_k is summed directly, not carried from e_{k-1}) run j = 0 .. w - 1 in order; xi is taken as
+ * ln L_a - ln L_b; the minimum over b runs b = 0, 1, .. with a strict <.  Multiply-adds may be fused.
+ *
+ * Shapes: wav [B][max_n], f0 [B][F], phi [B][F][K], rms [B][F] with F = ss_melspec_frames(max_n).  No engine needed, no allocation inside,
+ * asynchronous on `stream`.  n_dev i32[B] (NULL: every row has max_n samples): row b is, bit for bit, the result of running that utterance
+ * alone at min(max(n[b], 513), max_n) samples -- a length outside 513 .. max_n spoils that row only; samples at or beyond it are never read
+ * (they may hold NaN); f0 beyond the row's own F is -1e10 (ss_collate's padding), phi and rms beyond it are exact zeros; the hook
+ * ss_op_pitch_dp never reads phi or rms there.
+ * Refused before anything is enqueued, with a message that names the argument: null required pointers, B outside 1 .. 65535, max_n outside
+ * 513 .. 256 (SS_MAX_EVAL_FRAMES - 1), lo_hz / hi_hz NaN or not positive, not lo_hz < hi_hz, Lmin < 16 (hi_hz above 1000), Lmax > 400
+ * (lo_hz below 40) or K < 3, scale not finite or <= 0, scratch_bytes below ss_pitch_scratch_bytes(B, max_n, lo_hz, hi_hz) or scratch_dev
+ * not 256-byte aligned. */
+long ss_pitch_scratch_bytes(int B, int max_n, double lo_hz, double hi_hz);            /* host only; -1 + ss_last_error on bad arguments */
+int  ss_pitch_track(const double* wav_dev, const int* n_dev, int B, int max_n, double scale, double lo_hz, double hi_hz,
+                    double* f0_dev, void* scratch_dev, long scratch_bytes, void* stream);   /* f0 [B][ss_melspec_frames(max_n)] */
+/* test hooks, each half alone; ss_op_pitch_dp takes the same scratch as ss_pitch_track */
+int  ss_op_nccf(const double* wav_dev, const int* n_dev, int B, int max_n, double scale, double lo_hz, double hi_hz,
+                double* phi_dev /* [B][F][K] */, double* rms_dev /* [B][F] */, void* stream);
+int  ss_op_pitch_dp(const double* phi_dev, const double* rms_dev, const int* n_dev, int B, int max_n, double lo_hz, double hi_hz,
+                    double* f0_dev, void* scratch_dev, long scratch_bytes, void* stream);
+
 /* ---- Griffin-Lim vocoder: mel spectrograms back to waveforms (the checkpoint-free stand-in for demo.ipynb's WaveNet cell) ----
  * The inverse of ss_melspec's chain: mel [0, 1] -> amplitude 10^((100 mel - 100 + 16) / 20) -> linear magnitude through a CALLER-SUPPLIED
  * float64 inv_basis [n_mels][513] (the Python layer passes numpy.linalg.pinv of the [513][n_mels] basis), floored at `floor` >= 0 ->

@@ -86,6 +86,10 @@ SYMBOLS = {
     'ss_melspec_frames': (_i, [_i]),
     'ss_melspec': (_i, [_vp, _i, _vp, _i, _fp, _vp]),
     'ss_f0_normalize': (_i, [_vp, _i, _fp, _vp]),
+    'ss_pitch_scratch_bytes': (_l, [_i, _i, _d, _d]),
+    'ss_pitch_track': (_i, [_vp, _ip, _i, _i, _d, _d, _d, _vp, _vp, _l, _vp]),
+    'ss_op_nccf': (_i, [_vp, _ip, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
+    'ss_op_pitch_dp': (_i, [_vp, _vp, _ip, _i, _i, _d, _d, _vp, _vp, _l, _vp]),
     'ss_griffinlim_samples': (_i, [_i]),
     'ss_griffinlim_scratch_bytes': (_l, [_i, _i]),
     'ss_mel_to_linear': (_i, [_fp, _vp, _ip, _i, _i, _i, _d, _vp, _vp]),

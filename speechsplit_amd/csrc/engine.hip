@@ -3006,6 +3006,73 @@ int ss_f0_normalize(const double* f0, int n, float* out, void* stream) {
     return 0;
 }
 
+// ---- pitch tracker (pitch.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+namespace {
+int pitch_shape(const char* who, int B, int max_n, double lo_hz, double hi_hz, PitchLags* g) {
+    if (B < 1 || B > PITCH_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
+    if (max_n < 513 || max_n > 256 * (SS_MAX_EVAL_FRAMES - 1))
+        return fail(std::string(who) + ": max_n outside 513 .. 256 * (SS_MAX_EVAL_FRAMES - 1)");
+    if (!(lo_hz > 0.0)) return fail(std::string(who) + ": lo_hz is NaN or not positive");
+    if (!(hi_hz > 0.0)) return fail(std::string(who) + ": hi_hz is NaN or not positive");
+    if (!(lo_hz < hi_hz)) return fail(std::string(who) + ": lo_hz is not below hi_hz");
+    if (!(floor(16000.0 / hi_hz) >= PITCH_MIN_LAG)) return fail(std::string(who) + ": hi_hz above 1000 (the shortest lag would be below 16 samples)");
+    if (!(ceil(16000.0 / lo_hz) <= PITCH_MAX_LAG)) return fail(std::string(who) + ": lo_hz below 40 (the longest lag would be above 400 samples)");
+    if (!pitch_lags(lo_hz, hi_hz, g)) return fail(std::string(who) + ": lo_hz .. hi_hz covers fewer than 3 lags");
+    return 0;
+}
+int pitch_scratch_ok(const char* who, int B, int max_n, const PitchLags& g, const void* scratch, long scratch_bytes) {
+    if (!scratch) return fail(std::string(who) + ": null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail(std::string(who) + ": scratch_dev is not 256-byte aligned");
+    if (scratch_bytes < pitch_scratch_bytes(B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1))
+        return fail(std::string(who) + ": scratch_bytes below ss_pitch_scratch_bytes(B, max_n, lo_hz, hi_hz)");
+    return 0;
+}
+}  // namespace
+
+long ss_pitch_scratch_bytes(int B, int max_n, double lo_hz, double hi_hz) {
+    PitchLags g;
+    CHK(pitch_shape("ss_pitch_scratch_bytes", B, max_n, lo_hz, hi_hz, &g));
+    return pitch_scratch_bytes(B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1);
+}
+
+int ss_pitch_track(const double* wav, const int* n, int B, int max_n, double scale, double lo_hz, double hi_hz, double* f0, void* scratch,
+                   long scratch_bytes, void* stream) {
+    PitchLags g;
+    if (!wav) return fail("ss_pitch_track: null pointer: wav_dev");
+    if (!f0) return fail("ss_pitch_track: null pointer: f0_dev");
+    CHK(pitch_shape("ss_pitch_track", B, max_n, lo_hz, hi_hz, &g));
+    if (!(scale > 0.0) || std::isinf(scale)) return fail("ss_pitch_track: scale is not finite or not positive");
+    CHK(pitch_scratch_ok("ss_pitch_track", B, max_n, g, scratch, scratch_bytes));
+    const PitchScratch sc = pitch_scratch(scratch, B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1);
+    HIPCHK(pitch_nccf(wav, n, B, max_n, scale, g, sc.phi, sc.rms, S(stream)));
+    HIPCHK(pitch_dp(sc.phi, sc.rms, n, B, max_n, g, f0, sc, S(stream)));
+    return 0;
+}
+
+int ss_op_nccf(const double* wav, const int* n, int B, int max_n, double scale, double lo_hz, double hi_hz, double* phi, double* rms,
+               void* stream) {
+    PitchLags g;
+    if (!wav) return fail("ss_op_nccf: null pointer: wav_dev");
+    if (!phi) return fail("ss_op_nccf: null pointer: phi_dev");
+    if (!rms) return fail("ss_op_nccf: null pointer: rms_dev");
+    CHK(pitch_shape("ss_op_nccf", B, max_n, lo_hz, hi_hz, &g));
+    if (!(scale > 0.0) || std::isinf(scale)) return fail("ss_op_nccf: scale is not finite or not positive");
+    HIPCHK(pitch_nccf(wav, n, B, max_n, scale, g, phi, rms, S(stream)));
+    return 0;
+}
+
+int ss_op_pitch_dp(const double* phi, const double* rms, const int* n, int B, int max_n, double lo_hz, double hi_hz, double* f0,
+                   void* scratch, long scratch_bytes, void* stream) {
+    PitchLags g;
+    if (!phi) return fail("ss_op_pitch_dp: null pointer: phi_dev");
+    if (!rms) return fail("ss_op_pitch_dp: null pointer: rms_dev");
+    if (!f0) return fail("ss_op_pitch_dp: null pointer: f0_dev");
+    CHK(pitch_shape("ss_op_pitch_dp", B, max_n, lo_hz, hi_hz, &g));
+    CHK(pitch_scratch_ok("ss_op_pitch_dp", B, max_n, g, scratch, scratch_bytes));
+    HIPCHK(pitch_dp(phi, rms, n, B, max_n, g, f0, pitch_scratch(scratch, B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1), S(stream)));
+    return 0;
+}
+
 // ---- Griffin-Lim vocoder (vocoder.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
 namespace {
 int voc_shape(const char* who, int B, int max_frames) {

@@ -264,6 +264,36 @@ hipError_t istft(const double* spec, const int* frames, int B, int max_frames, d
 hipError_t griffinlim(const double* mag, const double* phase0, const int* frames, int B, int max_frames, int n_iter, double momentum,
                       double* wav, const VocoderScratch& sc, hipStream_t s);
 
+// ---------------------------------------------------------------- pitch.hip  (RAPT-style pitch tracker: waveform -> ln F0 per hop, float64)
+// Shapes: wav [B][max_n], phi [B][F][K], rms [B][F], f0 [B][F] with F = max_n / 256 + 1 and K = lmax - lmin + 1 lags.
+// n (nullable; device i32[B]): row b has n_b = min(max(n[b], 513), max_n) samples and F_b = n_b / 256 + 1 frames; it is computed as if it were
+// alone, samples at or beyond n_b are never read, phi / rms beyond F_b are zeros and f0 beyond F_b is -1e10.
+constexpr int PITCH_MAX_ROWS = 65535;                      // the batch is the grid's y dimension
+constexpr int PITCH_STATES = 20;                           // the unvoiced state and at most 19 candidates per frame
+constexpr int PITCH_MIN_LAG = 16, PITCH_MAX_LAG = 400;     // 1000 Hz .. 40 Hz at 16 kHz: the segment (120 + lmax samples) sits in LDS
+struct PitchLags {
+    int lmin, lmax;      // floor(16000 / hi_hz), ceil(16000 / lo_hz)
+};
+// false if a bound is NaN or not positive, not lo < hi, or the lags leave PITCH_MIN_LAG .. PITCH_MAX_LAG or are fewer than 3
+bool pitch_lags(double lo_hz, double hi_hz, PitchLags* g);
+struct PitchScratch {
+    double* phi;         // [B][F][K]   the NCCF (ss_pitch_track only; the hook takes the caller's)
+    double* rms;         // [B][F]      likewise
+    double* cost;        // [B][F][20]  local cost per state
+    double* lag;         // [B][F][20]  refined lag per state (entry 0 unused)
+    double* lnlag;       // [B][F][20]  its logarithm
+    int* cnt;            // [B][F]      states in use
+    unsigned char* bp;   // [B][F][32]  backpointers
+};
+long pitch_scratch_bytes(int B, int max_frames, int K);
+PitchScratch pitch_scratch(void* base, int B, int max_frames, int K);
+// steps 1 and 2 of the header's algorithm: one workgroup per (frame, utterance)
+hipError_t pitch_nccf(const double* wav, const int* n, int B, int max_n, double scale, const PitchLags& g, double* phi, double* rms,
+                      hipStream_t s);
+// steps 3 and 4, the recurrence and the backtrack: a frame-parallel candidate kernel, then one wavefront per utterance
+hipError_t pitch_dp(const double* phi, const double* rms, const int* n, int B, int max_n, const PitchLags& g, double* f0,
+                    const PitchScratch& sc, hipStream_t s);
+
 // ---------------------------------------------------------------- lstm_small.hip  (hidden <= 32: whole recurrence in one launch)
 // Row stride of a small BLSTM's output, cell-state and output-gradient slabs: 2H for H a power of two (the default widths keep their
 // layout), else 2H rounded up to a multiple of 4 floats (16-byte rows: vector loads and the GEMMs' aligned path).  The padding columns

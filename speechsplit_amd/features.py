@@ -1,22 +1,36 @@
-"""Offline feature extraction (reference make_spect_f0.py:48-73 with utils.py:10-42) -- SURVEY.md section 8(f) row N4.
+"""Offline feature extraction (reference make_spect_f0.py with utils.py:10-42) -- SURVEY.md section 8(f) row N4: a recording in, the
+(mel, f0) pair the model consumes out.  `extract` is the reference's loop body, `make_spect_f0` its directory walk.
 
 What runs where.  Host (scipy / numpy, float64, as the reference): the 5th-order 30 Hz Butterworth high-pass applied forwards
-and backwards (`signal.filtfilt`, make_spect_f0.py:53) and the 1e-6 dither from the per-speaker generator (:54) -- a sequential
-recurrence over the waveform.  GPU (csrc/features.hip through the C ABI): STFT magnitude -> mel projection -> dB -> [0, 1]
-scaling, and the F0 normalisation.  The mel filter bank (`librosa.filters.mel`, make_spect_f0.py:15) is restated here from the published
-algorithm (`mel_filter_bank`: Slaney's Auditory-Toolbox mel scale and area normalisation, librosa's defaults) -- parity against librosa itself
-is UNPINNED (it is absent in this environment, so nothing of the reference's could be run to produce a vector); the function is pinned against
-hand-computed closed-form values of the published definition for three filters (linear region, across 1 kHz, top band:
-tests/test_capi_host.py::test_mel_filter_bank_closed_form_slaney_values) and against its published properties.  NOT built: RAPT (`pysptk.sptk.rapt`, :63 -- a third-party C algorithm with no source here): the raw F0 track is an input.
+and backwards (`signal.filtfilt`, make_spect_f0.py:54) and the 1e-6 dither from the per-speaker generator (:55) -- a sequential
+recurrence over the waveform.  GPU (csrc/features.hip and csrc/pitch.hip through the C ABI): STFT magnitude -> mel projection -> dB ->
+[0, 1] scaling, the pitch track, and the F0 normalisation.
+
+Two parts of the reference come from libraries that are absent here, and both are restated from the published algorithm instead:
+  * the mel filter bank (`librosa.filters.mel`, make_spect_f0.py:15): `mel_filter_bank`, Slaney's Auditory-Toolbox mel scale and area
+    normalisation with librosa's defaults.  Parity against librosa itself is UNPINNED (nothing of the reference's could be run to produce a
+    vector); the function is pinned against hand-computed closed-form values of the published definition for three filters (linear
+    region, across 1 kHz, top band: tests/test_capi_host.py::test_mel_filter_bank_closed_form_slaney_values) and its published properties.
+  * the F0 track (`pysptk.sptk.rapt`, :64): `pitch_track`, the published core of RAPT (Talkin 1995: normalised cross-correlation
+    candidates plus dynamic programming, Talkin's constants) in RAPT's otype=2 output convention -- ln(F0 in Hz), -1e10 for unvoiced frames,
+    one value per 256-sample hop.  It is a Talkin-style tracker, NOT a port of SPTK: the spectral-stationarity term and the two-rate search
+    are left out (include/speechsplit_amd.h states the algorithm completely), and agreement with SPTK's own RAPT stays UNPINNED.  It is
+    pinned against a float64 numpy restatement (tests/pitch_ref.py) and against harmonic tones of known F0.
 The spectrogram half is pinned by tests/golden/features.npz, generated from the reference's own `butter_highpass` / `pySTFT` /
 `speaker_normalization`."""
 import ctypes as C
+import os
+import pickle
+import wave
 
 import numpy as np
 import torch
 from scipy import signal
 
 from . import _capi
+from .convert import plan_batches
+
+MIN_SAMPLES = 513                                  # reflect padding by 512
 
 
 def _hz_to_mel(f):
@@ -96,3 +110,105 @@ def normalize_f0(f0_rapt, device='cuda'):
     _capi.check(lib.ss_f0_normalize(C.c_void_p(f.data_ptr()), f.numel(), C.c_void_p(out.data_ptr()),
                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
+
+
+def f0_range(gender):
+    """make_spect_f0.py:40-45: the search range in Hz by the speaker's gender"""
+    if gender == 'M':
+        return 50, 250
+    if gender == 'F':
+        return 100, 600
+    raise ValueError(f"f0_range: gender must be 'M' or 'F', not {gender!r}")
+
+
+def pitch_track_dev(wav_dev, n_dev, lo, hi, scale=32768.0):
+    """The C call on device tensors: wav float64 [B, max_n], n int32 [B] or None (every row has max_n samples) -> float64 [B, frames] of
+    ln(F0 in Hz), -1e10 for unvoiced frames and behind a row's own frames."""
+    lib = _capi.lib()
+    B, max_n = wav_dev.shape
+    nbytes = lib.ss_pitch_scratch_bytes(B, max_n, float(lo), float(hi))
+    if nbytes < 0:
+        _capi.check(-1)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=wav_dev.device)
+    f0 = torch.empty(B, lib.ss_melspec_frames(max_n), dtype=torch.float64, device=wav_dev.device)
+    _capi.check(lib.ss_pitch_track(C.c_void_p(wav_dev.data_ptr()), C.c_void_p(n_dev.data_ptr()) if n_dev is not None else None, B, max_n,
+                                   float(scale), float(lo), float(hi), C.c_void_p(f0.data_ptr()), C.c_void_p(scratch.data_ptr()), nbytes,
+                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return f0
+
+
+def pitch_track(wavs, lo, hi, max_rows=16, device='cuda'):
+    """make_spect_f0.py:64 with the Talkin-style tracker of csrc/pitch.hip in place of `sptk.rapt(wav.astype(np.float32) * 32768, fs, 256,
+    min=lo, max=hi, otype=2)`.  One float64 waveform [n] at 16 kHz (or a list of them, any lengths >= 513) -> float64 numpy track(s)
+    [n // 256 + 1] in input order.  The samples are rounded through float32 and scaled by 32768, as the reference does.  The utterances run
+    as ragged batches of at most max_rows rows in convert.plan_batches order; every row is the result of running it alone, so the result
+    does not depend on max_rows."""
+    single = not isinstance(wavs, (list, tuple))
+    ws = [np.ascontiguousarray(w, dtype=np.float64).astype(np.float32).astype(np.float64) for w in ([wavs] if single else wavs)]
+    for w in ws:
+        if w.ndim != 1 or w.shape[0] < MIN_SAMPLES:
+            raise ValueError(f'pitch_track: every waveform must be [n] with n >= {MIN_SAMPLES}')
+    out = [None] * len(ws)
+    for batch in plan_batches([w.shape[0] for w in ws], max_rows):
+        lens = [ws[i].shape[0] for i in batch]
+        wav = np.zeros((len(batch), lens[-1]))
+        for r, i in enumerate(batch):
+            wav[r, :lens[r]] = ws[i]
+        f0 = pitch_track_dev(torch.from_numpy(wav).to(device), torch.tensor(lens, dtype=torch.int32, device=device), lo, hi).cpu().numpy()
+        for r, i in enumerate(batch):
+            out[i] = f0[r, :lens[r] // 256 + 1].copy()
+    return out[0] if single else out
+
+
+def read_wav(path):
+    """16-bit mono PCM at 16 kHz through the standard library's `wave` -> float64 [n] in [-1, 1) (samples / 32768, as soundfile reads
+    them): the counterpart of vocoder.save_wav.  Any other format is refused by name."""
+    with wave.open(path, 'rb') as f:
+        ch, width, sr, n = f.getnchannels(), f.getsampwidth(), f.getframerate(), f.getnframes()
+        if ch != 1:
+            raise ValueError(f'read_wav: {path}: {ch} channels; mono only')
+        if width != 2:
+            raise ValueError(f'read_wav: {path}: {8 * width}-bit samples; 16-bit PCM only')
+        if sr != 16000:
+            raise ValueError(f'read_wav: {path}: sample rate {sr}; 16000 Hz only')
+        pcm = np.frombuffer(f.readframes(n), '<i2')
+    return pcm.astype(np.float64) / 32768.0
+
+
+def extract(x, prng, gender, device='cuda', mel_basis=None, unvoiced=0.0):
+    """The loop body of make_spect_f0.py:49-74 for one recording x float64 [n] at 16 kHz: (S float32 [F, 80], f0_norm float32 [F]).
+    prng is the speaker's numpy RandomState (the dither draws from it, so recordings of one speaker go through in the reference's order).
+    mel_basis [513, n_mels] defaults to mel_filter_bank().T, the reference's.  f0_norm is in [0, 1] on voiced frames and `unvoiced` elsewhere:
+    0 by default, which `quantize_f0` reads as unvoiced (<= 0); the reference's speaker_normalization leaves its -1e10 marker in those frames
+    (utils.py:39-41 touch the voiced frames only), and that is what its files carry -- make_spect_f0 passes unvoiced=-1e10."""
+    wav = preprocess_wav(np.asarray(x, np.float64), prng)
+    S = melspectrogram(wav, mel_filter_bank().T.astype(np.float64) if mel_basis is None else mel_basis, device).cpu().numpy()
+    lo, hi = f0_range(gender)
+    f0_rapt = pitch_track(wav, lo, hi, device=device)
+    f0_norm = normalize_f0(f0_rapt, device).cpu().numpy()
+    assert len(S) == len(f0_rapt)
+    return S.astype(np.float32), np.where(f0_rapt != -1e10, f0_norm, np.float32(unvoiced)).astype(np.float32)
+
+
+def make_spect_f0(root_dir='assets/wavs', target_dir='assets/spmel', target_dir_f0='assets/raptf0', spk2gen='assets/spk2gen.pkl',
+                  device='cuda'):
+    """The directory walk of make_spect_f0.py:28-74: root_dir/<speaker>/<name>.wav -> target_dir/<speaker>/<name>.npy (S, float32 [F, 80])
+    and target_dir_f0/<speaker>/<name>.npy (f0_norm, float32 [F], -1e10 in unvoiced frames as the reference's files); speakers and files in sorted order, one RandomState(int(speaker[1:])) per
+    speaker.  spk2gen: a {speaker: 'M' | 'F'} dict, or the path of the reference's pickle of one.  Returns the (speaker, name) pairs written."""
+    if not isinstance(spk2gen, dict):
+        with open(spk2gen, 'rb') as f:
+            spk2gen = pickle.load(f)
+    dir_name, subdirs, _ = next(os.walk(root_dir))
+    done = []
+    for subdir in sorted(subdirs):
+        os.makedirs(os.path.join(target_dir, subdir), exist_ok=True)
+        os.makedirs(os.path.join(target_dir_f0, subdir), exist_ok=True)
+        _, _, files = next(os.walk(os.path.join(dir_name, subdir)))
+        f0_range(spk2gen[subdir])                                      # an unknown gender stops the walk before anything is written
+        prng = np.random.RandomState(int(subdir[1:]))
+        for name in sorted(files):
+            S, f0_norm = extract(read_wav(os.path.join(dir_name, subdir, name)), prng, spk2gen[subdir], device, unvoiced=-1e10)
+            np.save(os.path.join(target_dir, subdir, name[:-4]), S, allow_pickle=False)
+            np.save(os.path.join(target_dir_f0, subdir, name[:-4]), f0_norm, allow_pickle=False)
+            done.append((subdir, name[:-4]))
+    return done
