@@ -731,27 +731,19 @@ def lstm_scratch(B, H, backward, persist=True):
     return n
 
 
-def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None, place=None, lengths=None):
-    """Test hook: one bidirectional LSTM layer through ss_op_lstm_fwd / ss_op_lstm_bwd (the engine's recurrence kernels) with
-    the input projection and the weight / input gradients on the engine's GEMM (ss_op_gemm).  w_ih etc. are (forward, reverse)
-    pairs with PyTorch's shapes.  Returns out [B,T,2H]; with d_out also (dx, [(gw_ih, gw_hh, gb) per direction]).
-    place(name, shape): optional allocator of the recurrences' operands -- 'gates' [R,8H], 'out' / 'csave' / 'd_out' [B,T+4,ld] and
-    'scratch_fwd' / 'scratch_bwd' [lstm_scratch(...) floats, at least 1] -- for callers that pre-place them.  It returns a dense tensor that
-    the CALLER has initialised as the kernels' contracts ask (halo rows of out / csave / d_out zero, scratch of a persistent recurrence
-    zero); the hook fills gates entirely and the real frames' 2H columns of d_out, nothing else.
-    lengths: per-row frame counts of a ragged batch (ss_op_lstm_fwd_ragged; forward only): out[b, lengths[b]:] comes back as zeros."""
+def _blstm_recurrence_slabs(gates_real, w_hh, d_out, lengths, place, want_act):
+    """The recurrences of one BLSTM layer on haloed slabs: gates_real [B,T,8H] pre-activations -> (gates, out, csave, act) with gates
+    [R,8H] holding the activated gates (no d_out) or the pre-activation gradients (d_out given), out / csave [B,T+4,ld] and act a clone
+    of the real frames' activated gates taken before the backward overwrites them (want_act only, else None)."""
     lib = _capi.lib()
-    B, T, In = x.shape
+    B, T, H8 = gates_real.shape
     H = w_hh[0].shape[1]
+    assert H8 == 8 * H
     OW = small_lstm_ld(H)                                                   # row stride of out / csave / d_out
-    dev = x.device
-    wcat = torch.cat([w_ih[0], w_ih[1]], 0).contiguous()                    # [8H, In]
-    bsum = torch.cat([b_ih[0] + b_hh[0], b_ih[1] + b_hh[1]]).contiguous()
-    xs = _slab(x)
+    dev = gates_real.device
     R = B * (T + 4)
     gates = torch.zeros(R, 8 * H, device=dev) if place is None else place('gates', (R, 8 * H))
-    g_real = gemm(xs.view(R, In), wcat, bsum)                               # all rows, halo rows are then re-zeroed
-    gates.copy_(g_real)
+    gates.view(B, T + 4, 8 * H)[:, 2:2 + T] = gates_real
     gates.view(B, T + 4, 8 * H)[:, :2] = 0
     gates.view(B, T + 4, 8 * H)[:, T + 2:] = 0
     B16 = (B + 15) // 16 * 16
@@ -767,18 +759,19 @@ def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None, place=None, lengths=None)
         for t in (gates, out, csave, scratch):
             assert t.is_contiguous()
     whf, whb = w_hh[0].contiguous(), w_hh[1].contiguous()
+    real = lambda: gates.view(B, T + 4, 8 * H)[:, 2:2 + T].clone()
     if lengths is not None:
         if d_out is not None:
             raise ValueError('speechsplit_amd: a ragged BLSTM layer runs the forward only')
         ln = check_lengths(lengths, B, T, (1,), dev)
         _capi.check(lib.ss_op_lstm_fwd_ragged(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(out), _ptr(csave), _ptr(scratch), scratch.numel(),
                                               _ptr(ln), B, T, H, _stream()))
-        return out[:, 2:2 + T, :2 * H].clone()
+        return gates, out, csave, real() if want_act else None
     _capi.check(lib.ss_op_lstm_fwd(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(out), _ptr(csave), _ptr(scratch), scratch.numel(),
                                    B, T, H, _stream()))
-    y = out[:, 2:2 + T, :2 * H].clone()
+    act = real() if want_act else None
     if d_out is None:
-        return y
+        return gates, out, csave, act
     if place is None:
         ds = _slab(torch.nn.functional.pad(d_out.to(dev), (0, OW - 2 * H)))
         scratch_b.zero_()
@@ -788,6 +781,46 @@ def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None, place=None, lengths=None)
         ds[:, 2:2 + T, :2 * H] = d_out.to(dev)
     _capi.check(lib.ss_op_lstm_bwd(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(ds), _ptr(csave), _ptr(scratch_b), scratch_b.numel(),
                                    B, T, H, _stream()))
+    return gates, out, csave, act
+
+
+def blstm_recurrence(gates, w_hh, d_out=None, lengths=None, place=None):
+    """Test hook: the recurrences of one bidirectional LSTM layer (ss_op_lstm_fwd / _ragged, and with d_out ss_op_lstm_bwd) on the CALLER's
+    pre-activations.  gates [B,T,8H]: x.W_ih^T + b of the forward direction in columns [0,4H), of the reverse direction in [4H,8H), gate
+    order i, f, g, o; w_hh: (forward, reverse) [4H,H].  Returns (out [B,T,2H], csave [B,T,2H], act [B,T,8H], dgates [B,T,8H] or None),
+    halo rows stripped: act is what the forward left in the gates slab (the activated gates), copied before the backward replaces it by the
+    pre-activation gradients dgates.  lengths: a ragged batch (forward only): out / csave are zero and act is unspecified at t >= lengths[b].
+    place: as for blstm_layer."""
+    B, T, H8 = gates.shape
+    H = H8 // 8
+    slab, out, csave, act = _blstm_recurrence_slabs(gates.to(dtype=torch.float32), w_hh, d_out, lengths, place, True)
+    dgates = slab.view(B, T + 4, 8 * H)[:, 2:2 + T].clone() if d_out is not None else None
+    return out[:, 2:2 + T, :2 * H].clone(), csave[:, 2:2 + T, :2 * H].clone(), act, dgates
+
+
+def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None, place=None, lengths=None):
+    """Test hook: one bidirectional LSTM layer through ss_op_lstm_fwd / ss_op_lstm_bwd (the engine's recurrence kernels) with
+    the input projection and the weight / input gradients on the engine's GEMM (ss_op_gemm): the projection, then the recurrences as
+    blstm_recurrence runs them, then the gradient GEMMs.  w_ih etc. are (forward, reverse)
+    pairs with PyTorch's shapes.  Returns out [B,T,2H]; with d_out also (dx, [(gw_ih, gw_hh, gb) per direction]).
+    place(name, shape): optional allocator of the recurrences' operands -- 'gates' [R,8H], 'out' / 'csave' / 'd_out' [B,T+4,ld] and
+    'scratch_fwd' / 'scratch_bwd' [lstm_scratch(...) floats, at least 1] -- for callers that pre-place them.  It returns a dense tensor that
+    the CALLER has initialised as the kernels' contracts ask (halo rows of out / csave / d_out zero, scratch of a persistent recurrence
+    zero); the hook fills gates entirely and the real frames' 2H columns of d_out, nothing else.
+    lengths: per-row frame counts of a ragged batch (ss_op_lstm_fwd_ragged; forward only): out[b, lengths[b]:] comes back as zeros."""
+    B, T, In = x.shape
+    H = w_hh[0].shape[1]
+    OW = small_lstm_ld(H)                                                   # row stride of out / csave / d_out
+    dev = x.device
+    wcat = torch.cat([w_ih[0], w_ih[1]], 0).contiguous()                    # [8H, In]
+    bsum = torch.cat([b_ih[0] + b_hh[0], b_ih[1] + b_hh[1]]).contiguous()
+    xs = _slab(x)
+    R = B * (T + 4)
+    g_real = gemm(xs.view(R, In), wcat, bsum)                               # all rows; the recurrence hook takes the real frames
+    gates, out, csave, _ = _blstm_recurrence_slabs(g_real.view(B, T + 4, 8 * H)[:, 2:2 + T], w_hh, d_out, lengths, place, False)
+    y = out[:, 2:2 + T, :2 * H].clone()
+    if d_out is None:
+        return y
     dG = gates.view(R, 8 * H)                                               # pre-activation gradients, halo rows zero
     dx = gemm(dG, wcat, tb=True).view(B, T + 4, In)[:, 2:2 + T].clone()     # dX = dG . W_ih (both directions)
     grads = []
