@@ -353,6 +353,51 @@ int  ss_op_nccf(const double* wav_dev, const int* n_dev, int B, int max_n, doubl
 int  ss_op_pitch_dp(const double* phi_dev, const double* rms_dev, const int* n_dev, int B, int max_n, double lo_hz, double hi_hz,
                     double* f0_dev, void* scratch_dev, long scratch_bytes, void* stream);
 
+/* ---- batched feature extraction: make_spect_f0.py:49-71 on ragged batches of recordings (filter, dither, mel spectrogram, F0 normalisation;
+ * the pitch track between them is ss_pitch_track above, which takes the same wav / n_dev / B / max_n) ----
+ * One length vector serves every call: n_dev i32[B] (NULL: every row has max_n samples).  Every kernel clamps n[b] into [513, max_n]:
+ * row b has n_b = min(max(n[b], 513), max_n) samples and F_b = n_b / 256 + 1 frames of F = ss_melspec_frames(max_n) -- a length outside
+ * 513 .. max_n spoils that row only.  Row b is, bit for bit, the result of running that utterance alone; nothing at or beyond n_b (F_b for
+ * ss_f0_normalize_batch) is read -- it may hold NaN; defined filler is written behind it.  No atomics, every sum in a fixed order: the same
+ * bits on every run.  No engine needed, no allocation inside, asynchronous on `stream`.
+ *
+ * ss_filtfilt: scipy.signal.filtfilt(b, a, x) for 6 coefficients (a 5th-order filter; scipy's default odd extension by
+ * padlen = 3 * 6 = 18), then the scaling and dither of make_spect_f0.py:54-55.  No other order is provided.  x, dither, y: float64
+ * [B][max_n], distinct buffers.  b[6], a[6], zi[5] are HOST arrays, read at call time (the Python layer computes them with signal.butter /
+ * signal.lfilter_zi, as mel_basis is an input); a[0] must be exactly 1.  The reference's filter (30 Hz high-pass, poles at
+ * |z| = 0.988 .. 0.996) is ill-conditioned in scipy's direct form: any other arrangement of the arithmetic lands ~3e-7 of max |y| away from
+ * scipy's result, which moves the mel spectrogram by more than 1e-6.  So the result is DEFINED as this sequence of IEEE double operations --
+ * every product and every sum rounded to double on its own, no fused multiply-add -- and equals scipy's to the bit:
+ *   Extension.  With i = j - 18 for j in [0, n + 36): ext[j] = 2 x[0] - x[-i] for i < 0; ext[j] = x[i] for 0 <= i < n;
+ *               ext[j] = 2 x[n-1] - x[2(n-1) - i] for i >= n.
+ *   Step.       step(u): y = b0*u + z0; z_i = (b_{i+1}*u + z_{i+1}) - a_{i+1}*y for i = 0..3; z4 = b5*u - a5*y; returns y.
+ *   Pass 1.     z = zi * ext[0]; v[j] = step(ext[j]), j ascending.
+ *   Pass 2.     z = zi * v[n+35]; w[j] = step(v[j]), j descending.
+ *   Output.     y[i] = w[i + 18], 0 <= i < n.
+ *   Epilogue.   out[i] = y[i]*gain + (r[i] - 0.5)*dither_scale, rounded step by step, r = dither_dev (the host's prng.rand values: the draw
+ *               is the speaker's numpy stream and stays on the host); dither_dev == NULL: out[i] = y[i]*gain.  gain = 0.96 and
+ *               dither_scale = 1e-06 are make_spect_f0.py:54-55 exactly.  The odd-length fix of :52-53 changes n and stays in Python.
+ * Zeros are written behind n_b.  scratch: the first pass's output, [B][max_n + 36] doubles, rounded up to 256 bytes.
+ *
+ * ss_melspec_batch: ss_melspec's chain on every row -- reflect padding by 512 about the row's OWN ends, periodic Hann window, 1024 points,
+ * hop 256, mel projection (the 513-term sum in bin order), dB floor and offsets, [0, 1] scaling -- with the vocoder's 1024-point FFT in
+ * place of ss_melspec's direct DFT (the two agree to ~1e-13 before the float32 cast).  mel_basis: float64 [513][n_mels];
+ * out: float32 [B][F][n_mels], zeros in frames at or beyond F_b.
+ *
+ * ss_f0_normalize_batch: f0 float64 [B][F] (ss_pitch_track's output) -> float32 [B][F]: voiced frames (f0 != -1e10) of row b come out with
+ * the bits of ss_f0_normalize on that row's F_b frames alone; unvoiced frames and frames at or beyond F_b get (float)unvoiced.
+ *
+ * Refused before anything is enqueued, with a message that names the argument: null required pointers, B outside 1 .. 65535, max_n outside
+ * 513 .. 256 (SS_MAX_EVAL_FRAMES - 1) (ss_pitch_track's range), a[0] != 1, a b / a / zi entry, gain or dither_scale that is not finite,
+ * scratch_bytes below ss_filtfilt_scratch_bytes(B, max_n) or scratch_dev not 256-byte aligned, n_mels < 1, unvoiced NaN. */
+long ss_filtfilt_scratch_bytes(int B, int max_n);                                     /* host only; -1 + ss_last_error on bad arguments */
+int  ss_filtfilt(const double* x_dev, const int* n_dev, int B, int max_n, const double* b, const double* a, const double* zi,
+                 double gain, const double* dither_dev, double dither_scale, double* y_dev, void* scratch_dev, long scratch_bytes,
+                 void* stream);
+int  ss_melspec_batch(const double* wav_dev, const int* n_dev, int B, int max_n, const double* mel_basis_dev, int n_mels,
+                      float* out_dev, void* stream);
+int  ss_f0_normalize_batch(const double* f0_dev, const int* n_dev, int B, int max_n, double unvoiced, float* out_dev, void* stream);
+
 /* ---- Griffin-Lim vocoder: mel spectrograms back to waveforms (the checkpoint-free stand-in for demo.ipynb's WaveNet cell) ----
  * The inverse of ss_melspec's chain: mel [0, 1] -> amplitude 10^((100 mel - 100 + 16) / 20) -> linear magnitude through a CALLER-SUPPLIED
  * float64 inv_basis [n_mels][513] (the Python layer passes numpy.linalg.pinv of the [513][n_mels] basis), floored at `floor` >= 0 ->

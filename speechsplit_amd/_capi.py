@@ -90,6 +90,10 @@ SYMBOLS = {
     'ss_pitch_track': (_i, [_vp, _ip, _i, _i, _d, _d, _d, _vp, _vp, _l, _vp]),
     'ss_op_nccf': (_i, [_vp, _ip, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
     'ss_op_pitch_dp': (_i, [_vp, _vp, _ip, _i, _i, _d, _d, _vp, _vp, _l, _vp]),
+    'ss_filtfilt_scratch_bytes': (_l, [_i, _i]),
+    'ss_filtfilt': (_i, [_vp, _ip, _i, _i, _vp, _vp, _vp, _d, _vp, _d, _vp, _vp, _l, _vp]),
+    'ss_melspec_batch': (_i, [_vp, _ip, _i, _i, _vp, _i, _fp, _vp]),
+    'ss_f0_normalize_batch': (_i, [_vp, _ip, _i, _i, _d, _fp, _vp]),
     'ss_griffinlim_samples': (_i, [_i]),
     'ss_griffinlim_scratch_bytes': (_l, [_i, _i]),
     'ss_mel_to_linear': (_i, [_fp, _vp, _ip, _i, _i, _i, _d, _vp, _vp]),

@@ -3073,6 +3073,67 @@ int ss_op_pitch_dp(const double* phi, const double* rms, const int* n, int B, in
     return 0;
 }
 
+// ---- batched feature extraction (filtfilt.hip, features.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+namespace {
+int feat_shape(const char* who, int B, int max_n) {
+    if (B < 1 || B > FEAT_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
+    if (max_n < 513 || max_n > 256 * (SS_MAX_EVAL_FRAMES - 1))
+        return fail(std::string(who) + ": max_n outside 513 .. 256 * (SS_MAX_EVAL_FRAMES - 1)");
+    return 0;
+}
+}  // namespace
+
+long ss_filtfilt_scratch_bytes(int B, int max_n) {
+    CHK(feat_shape("ss_filtfilt_scratch_bytes", B, max_n));
+    return filtfilt_scratch_bytes(B, max_n);
+}
+
+int ss_filtfilt(const double* x, const int* n, int B, int max_n, const double* b, const double* a, const double* zi, double gain,
+                const double* dither, double dither_scale, double* y, void* scratch, long scratch_bytes, void* stream) {
+    if (!x) return fail("ss_filtfilt: null pointer: x_dev");
+    if (!b) return fail("ss_filtfilt: null pointer: b");
+    if (!a) return fail("ss_filtfilt: null pointer: a");
+    if (!zi) return fail("ss_filtfilt: null pointer: zi");
+    if (!y) return fail("ss_filtfilt: null pointer: y_dev");
+    CHK(feat_shape("ss_filtfilt", B, max_n));
+    FiltCoef c;
+    for (int i = 0; i < FILT_NCOEF; ++i) {
+        if (!std::isfinite(b[i])) return fail("ss_filtfilt: b[" + std::to_string(i) + "] is not finite");
+        if (!std::isfinite(a[i])) return fail("ss_filtfilt: a[" + std::to_string(i) + "] is not finite");
+        if (i < FILT_NCOEF - 1 && !std::isfinite(zi[i])) return fail("ss_filtfilt: zi[" + std::to_string(i) + "] is not finite");
+        c.b[i] = b[i];
+        c.a[i] = a[i];
+        if (i < FILT_NCOEF - 1) c.zi[i] = zi[i];
+    }
+    if (a[0] != 1.0) return fail("ss_filtfilt: a[0] is not exactly 1 (normalise b and a on the host, as scipy does)");
+    if (!std::isfinite(gain)) return fail("ss_filtfilt: gain is not finite");
+    if (!std::isfinite(dither_scale)) return fail("ss_filtfilt: dither_scale is not finite");
+    if (!scratch) return fail("ss_filtfilt: null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail("ss_filtfilt: scratch_dev is not 256-byte aligned");
+    if (scratch_bytes < filtfilt_scratch_bytes(B, max_n)) return fail("ss_filtfilt: scratch_bytes below ss_filtfilt_scratch_bytes(B, max_n)");
+    HIPCHK(filtfilt(x, n, B, max_n, c, gain, dither, dither_scale, y, (double*)scratch, S(stream)));
+    return 0;
+}
+
+int ss_melspec_batch(const double* wav, const int* n, int B, int max_n, const double* mel_basis, int n_mels, float* out, void* stream) {
+    if (!wav) return fail("ss_melspec_batch: null pointer: wav_dev");
+    if (!mel_basis) return fail("ss_melspec_batch: null pointer: mel_basis_dev");
+    if (!out) return fail("ss_melspec_batch: null pointer: out_dev");
+    CHK(feat_shape("ss_melspec_batch", B, max_n));
+    if (n_mels < 1) return fail("ss_melspec_batch: n_mels below 1");
+    HIPCHK(melspec_batch(wav, n, B, max_n, mel_basis, n_mels, out, S(stream)));
+    return 0;
+}
+
+int ss_f0_normalize_batch(const double* f0, const int* n, int B, int max_n, double unvoiced, float* out, void* stream) {
+    if (!f0) return fail("ss_f0_normalize_batch: null pointer: f0_dev");
+    if (!out) return fail("ss_f0_normalize_batch: null pointer: out_dev");
+    CHK(feat_shape("ss_f0_normalize_batch", B, max_n));
+    if (std::isnan(unvoiced)) return fail("ss_f0_normalize_batch: unvoiced is NaN");
+    HIPCHK(f0_normalize_batch(f0, n, B, max_n, unvoiced, out, S(stream)));
+    return 0;
+}
+
 // ---- Griffin-Lim vocoder (vocoder.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
 namespace {
 int voc_shape(const char* who, int B, int max_frames) {

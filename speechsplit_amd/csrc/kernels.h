@@ -240,6 +240,25 @@ hipError_t melspec(const double* x, int n, const double* mel, int n_mels, float*
 // utils.py:35-42 with mean / std over the voiced frames (make_spect_f0.py:64-66); -1e10 marks unvoiced frames
 hipError_t f0_normalize(const double* f0, int n, float* out, hipStream_t s);
 
+// ragged batches.  n (nullable; device i32[B]): row b has n_b = min(max(n[b], 513), max_n) samples and F_b = n_b / 256 + 1 frames of
+// F = max_n / 256 + 1; it is computed as if it were alone, samples at or beyond n_b are never read, frames at or beyond F_b are filler.
+constexpr int FEAT_MAX_ROWS = 65535;   // the batch is the grid's y dimension
+// wav [B][max_n] -> out [B][F][n_mels] float32 with the FFT of fft_lds.h; zeros in frames at or beyond F_b
+hipError_t melspec_batch(const double* wav, const int* n, int B, int max_n, const double* mel, int n_mels, float* out, hipStream_t s);
+// f0 [B][F] -> out [B][F] float32: f0_normalize on each row's own F_b frames; `unvoiced` in unvoiced frames and behind F_b
+hipError_t f0_normalize_batch(const double* f0, const int* n, int B, int max_n, double unvoiced, float* out, hipStream_t s);
+
+// ---------------------------------------------------------------- filtfilt.hip  (scipy.signal.filtfilt to the bit, float64)
+// x, dither (nullable), y [B][max_n]; scratch [B][max_n + 36] doubles.  y = filtfilt(b, a, x) * gain + (dither - 0.5) * dither_scale on each
+// row's own n_b samples, zeros behind them.  The coefficients travel by value (struct FiltCoef, filtfilt_step.h).
+constexpr int FILT_NCOEF = 6, FILT_PAD = 3 * FILT_NCOEF;    // scipy's default padlen = 3 * max(len(a), len(b))
+struct FiltCoef {
+    double b[FILT_NCOEF], a[FILT_NCOEF], zi[FILT_NCOEF - 1];
+};
+long filtfilt_scratch_bytes(int B, int max_n);
+hipError_t filtfilt(const double* x, const int* n, int B, int max_n, const FiltCoef& c, double gain, const double* dither,
+                    double dither_scale, double* y, double* scratch, hipStream_t s);
+
 // ---------------------------------------------------------------- vocoder.hip  (Griffin-Lim: mel -> linear magnitude -> waveform, float64)
 // Shapes: mel [B][max_frames][n_mels] f32, mag [B][max_frames][513], spec [B][max_frames][513][2] (re, im), wav [B][256 (max_frames - 1)].
 // frames (nullable; device i32[B]): row b has F_b = min(max(frames[b], 4), max_frames) frames and 256 (F_b - 1) samples; it is computed as if

@@ -1,10 +1,14 @@
 """Offline feature extraction (reference make_spect_f0.py with utils.py:10-42) -- SURVEY.md section 8(f) row N4: a recording in, the
 (mel, f0) pair the model consumes out.  `extract` is the reference's loop body, `make_spect_f0` its directory walk.
 
-What runs where.  Host (scipy / numpy, float64, as the reference): the 5th-order 30 Hz Butterworth high-pass applied forwards
-and backwards (`signal.filtfilt`, make_spect_f0.py:54) and the 1e-6 dither from the per-speaker generator (:55) -- a sequential
-recurrence over the waveform.  GPU (csrc/features.hip and csrc/pitch.hip through the C ABI): STFT magnitude -> mel projection -> dB ->
-[0, 1] scaling, the pitch track, and the F0 normalisation.
+What runs where.  `extract` (one recording, the default): the 5th-order 30 Hz Butterworth high-pass applied forwards and backwards
+(`signal.filtfilt`, make_spect_f0.py:54) and the 1e-6 dither from the per-speaker generator (:55) run on the host in scipy / numpy; the STFT
+magnitude -> mel projection -> dB -> [0, 1] scaling, the pitch track and the F0 normalisation run on the GPU (csrc/features.hip and
+csrc/pitch.hip through the C ABI).  `extract_batch` (a speaker's recordings at once; `make_spect_f0(..., max_rows=N)`): only the odd-length fix
+and the dither DRAW stay on the host -- it is the speaker's numpy stream.  The recordings and their draws go to the device in one copy and
+run as ragged batches through ss_filtfilt (csrc/filtfilt.hip: scipy's filtfilt to the bit, then the scaling and dither), ss_melspec_batch (the
+vocoder's FFT in place of the direct DFT), ss_pitch_track and ss_f0_normalize_batch; one copy per batch brings the results back.  Its F0 is
+`extract`'s to the bit and its spectrogram within 1e-6.
 
 Two parts of the reference come from libraries that are absent here, and both are restated from the published algorithm instead:
   * the mel filter bank (`librosa.filters.mel`, make_spect_f0.py:15): `mel_filter_bank`, Slaney's Auditory-Toolbox mel scale and area
@@ -137,6 +141,55 @@ def pitch_track_dev(wav_dev, n_dev, lo, hi, scale=32768.0):
     return f0
 
 
+def filtfilt_dev(x_dev, n_dev, b, a, zi, gain=1.0, dither_dev=None, dither_scale=0.0):
+    """The C call on device tensors: x float64 [B, max_n], n int32 [B] or None, host coefficients b [6], a [6] (a[0] == 1), zi [5],
+    dither float64 [B, max_n] of uniform draws or None -> float64 [B, max_n]: scipy.signal.filtfilt(b, a, row) * gain + (dither - 0.5) *
+    dither_scale on each row's own samples, bit for bit, zeros behind them.  Only 6 coefficients (a 5th-order filter, pad length 18)."""
+    lib = _capi.lib()
+    b, a, zi = (np.ascontiguousarray(v, dtype=np.float64) for v in (b, a, zi))
+    for name, v, k in (('b', b, 6), ('a', a, 6), ('zi', zi, 5)):
+        if v.shape != (k,):
+            raise ValueError(f'filtfilt_dev: {name} must have {k} entries (6 coefficients, pad length 18: the only order provided), not {v.shape}')
+    B, max_n = x_dev.shape
+    nbytes = lib.ss_filtfilt_scratch_bytes(B, max_n)
+    if nbytes < 0:
+        _capi.check(-1)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=x_dev.device)
+    y = torch.empty_like(x_dev)
+    ptr = lambda v: v.ctypes.data_as(C.c_void_p)
+    _capi.check(lib.ss_filtfilt(C.c_void_p(x_dev.data_ptr()), C.c_void_p(n_dev.data_ptr()) if n_dev is not None else None, B, max_n,
+                                ptr(b), ptr(a), ptr(zi), float(gain), C.c_void_p(dither_dev.data_ptr()) if dither_dev is not None else None,
+                                float(dither_scale), C.c_void_p(y.data_ptr()), C.c_void_p(scratch.data_ptr()), nbytes,
+                                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return y
+
+
+def melspec_batch_dev(wav_dev, n_dev, mel_basis_dev):
+    """The C call on device tensors: wav float64 [B, max_n], n int32 [B] or None, mel_basis float64 [513, n_mels] -> float32
+    [B, frames, n_mels], zeros behind a row's own frames."""
+    lib = _capi.lib()
+    B, max_n = wav_dev.shape
+    if mel_basis_dev.shape[0] != 513:
+        raise ValueError('mel_basis must be [513, n_mels] (1024-point transform)')
+    out = torch.empty(B, lib.ss_melspec_frames(max_n), mel_basis_dev.shape[1], device=wav_dev.device)
+    _capi.check(lib.ss_melspec_batch(C.c_void_p(wav_dev.data_ptr()), C.c_void_p(n_dev.data_ptr()) if n_dev is not None else None, B, max_n,
+                                     C.c_void_p(mel_basis_dev.data_ptr()), mel_basis_dev.shape[1], C.c_void_p(out.data_ptr()),
+                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def f0_normalize_batch_dev(f0_dev, n_dev, max_n, unvoiced=0.0):
+    """The C call on device tensors: f0 float64 [B, frames] (pitch_track_dev's output for max_n samples), n int32 [B] or None -> float32
+    [B, frames]: normalize_f0 on each row's own frames, `unvoiced` in unvoiced frames and behind them."""
+    lib = _capi.lib()
+    B = f0_dev.shape[0]
+    out = torch.empty(B, f0_dev.shape[1], device=f0_dev.device)
+    _capi.check(lib.ss_f0_normalize_batch(C.c_void_p(f0_dev.data_ptr()), C.c_void_p(n_dev.data_ptr()) if n_dev is not None else None, B,
+                                          int(max_n), float(unvoiced), C.c_void_p(out.data_ptr()),
+                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
 def pitch_track(wavs, lo, hi, max_rows=16, device='cuda'):
     """make_spect_f0.py:64 with the Talkin-style tracker of csrc/pitch.hip in place of `sptk.rapt(wav.astype(np.float32) * 32768, fs, 256,
     min=lo, max=hi, otype=2)`.  One float64 waveform [n] at 16 kHz (or a list of them, any lengths >= 513) -> float64 numpy track(s)
@@ -190,11 +243,72 @@ def extract(x, prng, gender, device='cuda', mel_basis=None, unvoiced=0.0):
     return S.astype(np.float32), np.where(f0_rapt != -1e10, f0_norm, np.float32(unvoiced)).astype(np.float32)
 
 
+def stage_batches(xs, prng, max_rows):
+    """The host side of extract_batch: the odd-length fix (make_spect_f0.py:52-53) on every recording, the dither draws from the speaker's
+    generator IN INPUT ORDER (so they do not depend on max_rows), then the plan_batches batches packed into one float64 buffer.  Returns
+    (flat, lens, batches): batch k = (indices, offset, B, max_n) has its recordings at flat[offset : offset + B * max_n] as [B, max_n] (zeros
+    behind each row) and their draws in the B * max_n entries after that; lens int32 holds the batches' row lengths one after another."""
+    xs = [np.ascontiguousarray(x, dtype=np.float64) for x in xs]
+    for i, x in enumerate(xs):
+        if x.ndim != 1:
+            raise ValueError(f'extract_batch: recording {i} must be [n], not {x.shape}')
+        if x.shape[0] % 256 == 0:
+            xs[i] = x = np.concatenate((x, np.array([1e-06])), axis=0)
+        if x.shape[0] < MIN_SAMPLES:
+            raise ValueError(f'extract_batch: recording {i} has {x.shape[0]} samples; every recording must be [n] with n >= {MIN_SAMPLES}')
+    draws = [prng.rand(x.shape[0]) for x in xs]
+    plan = plan_batches([x.shape[0] for x in xs], max_rows)
+    batches, off = [], 0
+    for idx in plan:
+        B, max_n = len(idx), xs[idx[-1]].shape[0]
+        batches.append((idx, off, B, max_n))
+        off += 2 * B * max_n
+    flat = np.zeros(off)
+    for idx, o, B, max_n in batches:
+        xb, rb = flat[o:o + B * max_n].reshape(B, max_n), flat[o + B * max_n:o + 2 * B * max_n].reshape(B, max_n)
+        for r, i in enumerate(idx):
+            xb[r, :xs[i].shape[0]] = xs[i]
+            rb[r, :xs[i].shape[0]] = draws[i]
+    lens = np.array([xs[i].shape[0] for idx, _, _, _ in batches for i in idx], dtype=np.int32)
+    return flat, lens, batches
+
+
+def extract_batch(xs, prng, gender, max_rows=16, device='cuda', mel_basis=None, unvoiced=0.0):
+    """`extract` for a speaker's recordings xs (a list of float64 [n] at 16 kHz) with the whole chain on the GPU: a list of (S, f0_norm), the
+    same as calling `extract` on each recording in order with the same prng -- f0_norm to the bit, S within 1e-6 (an FFT in place of the direct
+    DFT).  The recordings and their dither draws go up in one copy and run as ragged batches of at most max_rows rows in plan_batches order;
+    every row is the result of running it alone, so the result does not depend on max_rows.  One copy per batch brings S and f0_norm back."""
+    lo, hi = f0_range(gender)
+    flat, lens, batches = stage_batches(xs, prng, max_rows)
+    b, a = butter_highpass(30, 16000, order=5)
+    zi = signal.lfilter_zi(b, a)
+    mb = torch.as_tensor(np.ascontiguousarray(mel_filter_bank().T if mel_basis is None else mel_basis, dtype=np.float64)).to(device)
+    flat_dev, lens_dev = torch.from_numpy(flat).to(device), torch.from_numpy(lens).to(device)
+    out, row = [None] * len(xs), 0
+    for idx, o, B, max_n in batches:
+        x = flat_dev[o:o + B * max_n].view(B, max_n)
+        r = flat_dev[o + B * max_n:o + 2 * B * max_n].view(B, max_n)
+        n = lens_dev[row:row + B]
+        wav = filtfilt_dev(x, n, b, a, zi, 0.96, r, 1e-06)
+        S = melspec_batch_dev(wav, n, mb)
+        f0 = pitch_track_dev(wav.float().double(), n, lo, hi)               # the float32 round trip of make_spect_f0.py:64
+        f0n = f0_normalize_batch_dev(f0, n, max_n, unvoiced)
+        F, M = S.shape[1], S.shape[2]
+        both = torch.cat((S.reshape(B, F * M), f0n), dim=1).cpu().numpy()
+        for k, i in enumerate(idx):
+            Fi = int(lens[row + k]) // 256 + 1
+            out[i] = (both[k, :F * M].reshape(F, M)[:Fi].copy(), both[k, F * M:F * M + Fi].copy())
+        row += B
+    return out
+
+
 def make_spect_f0(root_dir='assets/wavs', target_dir='assets/spmel', target_dir_f0='assets/raptf0', spk2gen='assets/spk2gen.pkl',
-                  device='cuda'):
+                  device='cuda', max_rows=None):
     """The directory walk of make_spect_f0.py:28-74: root_dir/<speaker>/<name>.wav -> target_dir/<speaker>/<name>.npy (S, float32 [F, 80])
     and target_dir_f0/<speaker>/<name>.npy (f0_norm, float32 [F], -1e10 in unvoiced frames as the reference's files); speakers and files in sorted order, one RandomState(int(speaker[1:])) per
-    speaker.  spk2gen: a {speaker: 'M' | 'F'} dict, or the path of the reference's pickle of one.  Returns the (speaker, name) pairs written."""
+    speaker.  spk2gen: a {speaker: 'M' | 'F'} dict, or the path of the reference's pickle of one.  max_rows=None runs `extract` file by file; an
+    integer runs each speaker's files through `extract_batch` in batches of at most that many rows (the same F0 files, mel files within
+    1e-6).  Returns the (speaker, name) pairs written."""
     if not isinstance(spk2gen, dict):
         with open(spk2gen, 'rb') as f:
             spk2gen = pickle.load(f)
@@ -206,8 +320,13 @@ def make_spect_f0(root_dir='assets/wavs', target_dir='assets/spmel', target_dir_
         _, _, files = next(os.walk(os.path.join(dir_name, subdir)))
         f0_range(spk2gen[subdir])                                      # an unknown gender stops the walk before anything is written
         prng = np.random.RandomState(int(subdir[1:]))
-        for name in sorted(files):
-            S, f0_norm = extract(read_wav(os.path.join(dir_name, subdir, name)), prng, spk2gen[subdir], device, unvoiced=-1e10)
+        names = sorted(files)
+        if max_rows is not None:
+            feats = extract_batch([read_wav(os.path.join(dir_name, subdir, name)) for name in names], prng, spk2gen[subdir], max_rows,
+                                  device, unvoiced=-1e10) if names else []
+        for k, name in enumerate(names):
+            S, f0_norm = feats[k] if max_rows is not None else extract(read_wav(os.path.join(dir_name, subdir, name)), prng,
+                                                                       spk2gen[subdir], device, unvoiced=-1e10)
             np.save(os.path.join(target_dir, subdir, name[:-4]), S, allow_pickle=False)
             np.save(os.path.join(target_dir_f0, subdir, name[:-4]), f0_norm, allow_pickle=False)
             done.append((subdir, name[:-4]))
