@@ -506,6 +506,12 @@ int ss_op_lstm_wgrad(const float* dg_dev, const float* x_dev, long x_ld, const f
  *                      (needed when both operands are reduction-major and K % 32 != 0).  cfg: -1 = choose the tile, 0 = 256 x 256,
  *                      1 = 128 x 128, 2 = 256 x 128. */
 int ss_op_split_image(const float* src_dev, long ld, long rows, int cols, float scale, float* img_dev, long ldi, void* stream);
+/* ss_op_gemm in its fp16 x 2 mode (flags: 1 = A stored [K,M], 2 = B stored [K,N]) as the engine's weight-gradient launches call it: each operand
+ * optionally comes with its image (split with the scale 16; null = none), which the kernel takes where the form it picks can load that operand
+ * in whole groups -- the pipelined k-loop of ss_tune("gemm_pipe") brings an image of B in by LDS-DMA -- and with part_dev (ksplit * M * N
+ * floats, nullable) a split-K launch writes partial slabs that are added into C in a fixed order instead of meeting there through atomics. */
+int ss_op_gemm_pre(const float* a_dev, long lda, const float* a_img_dev, const float* b_dev, long ldb, const float* b_img_dev, float* c_dev, long ldc,
+                   float* part_dev, int M, int N, int K, int flags, int ksplit, void* stream);
 int ss_op_gemm_img(const float* a_img_dev, long lda, const float* b_img_dev, long ldb, float* c_dev, long ldc, const float* bias_dev, int M, int N,
                    int K, int flags, int ksplit, int cfg, float scale_a, float scale_b, int a_seglen, long a_segstride, float* part_dev,
                    const void* zeros_dev, void* stream);
@@ -539,7 +545,8 @@ int ss_debug_relu_mask(ss_engine* e, const char* block, float* mask_dev, void* s
  * read their slabs as [T+4,B,C]; persistent kernels only -- a layout experiment); schedule of the end of the backward (round 4,
  * tools/real_timeline.py): "dec_tail_split" 0..10 (which stream takes the decoder's layer-0 / layer-1 and the head's weight gradients; default 9),
  * "conv_dw_off" 0|1 (Generator_6: conv weight gradients off the trunk's dependent chain), "early_dw" 0|1 (16-bit mode: a decoder
- * layer's weight gradients beside the next backward recurrence, off).  The timing experiments that produce WRONG results ("lstm_mode",
+ * layer's weight gradients beside the next backward recurrence, off); "gemm_pipe" 0|1 (fp16 x 2 GEMM: the pipelined k-loop for launches
+ * whose B operand is an image and both operands are reduction-major -- the weight gradients; default 1, same results bit for bit).  The timing experiments that produce WRONG results ("lstm_mode",
  * "gemm_diag", "seq_prio" > 1) are compiled out of this library; `make -C speechsplit_amd/csrc diag` builds
  * libspeechsplit_hip_diag.so with them for tools/ (never loaded by the package unless SS_DIAG_LIB=1 is set). */
 int ss_tune(const char* key, int value);

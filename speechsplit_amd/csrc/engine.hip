@@ -25,7 +25,7 @@ using namespace ss;
 
 namespace ss {
 extern int g_small_lds, g_gemm_tr, g_deterministic;
-extern int g_lstm_nw, g_lstm_g, g_lstm_mode, g_gemm_want, g_gemm_diag, g_seq_prio, g_gemm_mode, g_seq_spin_log2, g_seq_tag, g_seq_var, g_gemm_ws;
+extern int g_lstm_nw, g_lstm_g, g_lstm_mode, g_gemm_want, g_gemm_diag, g_seq_prio, g_gemm_mode, g_seq_spin_log2, g_seq_tag, g_seq_var, g_gemm_ws, g_gemm_pipe;
 int g_fwd_f16x2 = 1;   // 1: forward contractions (operands bounded by construction: mel, one-hot, GroupNorm/ReLU outputs, |h| < 1, weights)
                        //    use the fp16 x 2 split (3 MFMAs) instead of bf16 x 3 (6 MFMAs); gradients keep bf16 x 3 (their range is not bounded)
 int g_bwd_f16x2 = 1;   // 1: the decoder's and the conv trunk's gradient GEMMs also use fp16 x 2: the gradient operand is scaled by the power
@@ -1663,7 +1663,9 @@ int lstm_input_grad(ss_engine* e, LstmBlk& lb, int l, Slab dxi, long r0, long nr
     g.B = {lb.wcat[l], In, 0, 0, 0};
     // (round 2's kernel measured SLOWER with the weight image in format v2 on this transposing-read operand -- 573 us per step with it, 532
     // without -- so only the 16-bit data path, whose image GEMM reads it, passes that image)
-    g.b_pre = e->img16() ? lb.wimg(l) : nullptr;
+    // The pipelined k-loop (ss_tune("gemm_pipe"), round 5) brings that image in by LDS-DMA and gains from it; the split it saves is the same
+    // split (fixed scale 16), so the result keeps its bits.
+    g.b_pre = (e->img16() || (g_gemm_pipe && lb.big())) ? lb.wimg(l) : nullptr;
     const bool dg16 = e->img16() && &lb == &e->ld && l < 3 && ((e->bwd.dg16_written >> l) & 1);      // the gradient slab's bf16 image (backward recurrence's storing wave)
     if (dg16) g.a_pre = e->ioff(e->dg_img[l], r0 * 8L * H);
     g.C = dxi.p + r0 * dxi.ld;
@@ -3249,6 +3251,28 @@ int ss_op_gemm(const float* a, long lda, const float* b, long ldb, float* c, lon
     return 0;
 }
 
+int ss_op_gemm_pre(const float* a, long lda, const float* a_img, const float* b, long ldb, const float* b_img, float* c, long ldc, float* part, int M,
+                   int N, int K, int flags, int ksplit, void* stream) {
+    if (!a || !b || !c) return fail("ss_op_gemm_pre: null pointer");
+    GemmDesc d{};
+    d.A = {a, lda, 0, 0, 0};
+    d.B = {b, ldb, 0, 0, 0};
+    d.a_pre = a_img;
+    d.b_pre = b_img;
+    d.C = c;
+    d.ldc = ldc;
+    d.M = M;
+    d.N = N;
+    d.K = K;
+    d.batch = 1;
+    d.ksplit = ksplit < 1 ? 1 : ksplit;
+    d.part = part;
+    d.want = 1;           // the largest tile the shape admits, whatever the number of workgroups: the form under test
+    d.flags = (flags & 1 ? GEMM_TA : 0) | (flags & 2 ? GEMM_TB : 0) | GEMM_F16X2 | (d.ksplit > 1 ? GEMM_ACCUM : 0);
+    HIPCHK(launch_gemm(d, S(stream)));
+    return 0;
+}
+
 int ss_op_split_image(const float* src, long ld, long rows, int cols, float scale, float* img, long ldi, void* stream) {
     if (!src || !img) return fail("ss_op_split_image: null pointer");
     HIPCHK(split_image(src, ld, rows, cols, nullptr, scale, img, ldi, nullptr, S(stream)));
@@ -3416,6 +3440,7 @@ int ss_tune(const char* key, int value) {
         {"dp_model", &g_dp_model, 0, 64},
         {"dp_buckets", &g_dp_buckets, 0, 1},
         {"gemm_ws", &g_gemm_ws, 0, 2},
+        {"gemm_pipe", &g_gemm_pipe, 0, 1},
         {"seq_spin_log2", &g_seq_spin_log2, 0, 24},
         {"overlap", &g_overlap, 0, 1},
         {"defer_dw", &g_defer_dw, 0, 1},

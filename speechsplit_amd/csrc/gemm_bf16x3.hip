@@ -21,6 +21,8 @@ int g_gemm_tr = 1;       // transposing LDS reads for reduction-major operands o
 int g_gemm_ws = 0;        // 128 x 128 fp16 x 2 tiles: 1 = the wave-specialised (512-thread) form where it measured faster in isolation, 2 = always,
                           // 0 = never (default: in the training step, where two convolutions share the chip anyway, 1 measured 0.02 ms slower)
 int g_gemm_mode = 1;      // 0: exact-fp32 MFMA kernel (gemm_f32.hip), 1: bf16x3 kernel whenever operands are 16-byte aligned
+int g_gemm_pipe = 1;      // fp16 x 2, 256 threads: 1 = the pipelined k-loop (PIPE below) for the launches it covers, 0 = the one-buffer loop everywhere.
+                          // Same results bit for bit.
 
 namespace {
 
@@ -104,16 +106,41 @@ __device__ __forceinline__ u32x4 tr_frag(const unsigned char* plane, int o_lo, i
 // per k-tile.  A multiplier wave and a staging wave share each SIMD: the split's VALU work issues in the shadow of the MFMAs
 // instead of in front of them (in the 256-thread form every wave does both, one after the other, and a k-tile's loads have one
 // MFMA phase -- ~0.4 us -- to arrive).
-template <int BM, int BN, bool TA, bool TB, int NPL, bool PROBE = false, bool TR = false, bool WS = false>
+//
+// PIPE (256 threads, fp16 x 2, 128 x 128; B reduction-major through the transposing-read image and given as a pre-split IMAGE, A the same or
+// K-contiguous without K segments, fp32 or an image: template flag APRE; ss_tune("gemm_pipe")):
+// the same k-loop with a deeper load pipeline and nothing else changed -- same products, same order, same epilogue, so bit-identical
+// results.  The one-buffer loop below has ONE k-tile in flight per workgroup (requested behind the first barrier, needed at the
+// split in front of the next one: a multiply phase of 24 MFMAs, ~0.3-0.4 us, to land in) and its __syncthreads() drain the wave's
+// loads.  Here
+//   * B, which needs no vector ALU work, goes global -> LDS by LDS-DMA into a ring of two slots (tile t in slot t & 1): one
+//     wave-instruction fills 4 k-rows of one plane, lane-linear, with the XOR swizzle of lds_off_t applied to the per-lane SOURCE
+//     column; tile t + 1 is requested as soon as the split of tile t is stored -- in front of the first barrier -- and is waited for
+//     with a counted s_waitcnt vmcnt in front of the first barrier of tile t + 1;
+//   * the 16 VGPRs that frees hold a second register set for A, whose loads are requested TWO k-tiles ahead (plain loads that hipcc
+//     counts: its wait in front of the split of tile t leaves tile t + 1 and the DMAs in flight);
+//   * both barriers order LDS traffic only (lds_barrier()).
+// So while tile t is multiplied, A(t + 1), A(t + 2) and B(t + 1) are in flight.  The loop runs over the WHOLE k-tiles only and every
+// request in it is unconditional (the tile index is clamped instead); a slice's last, partial k-tile is multiplied behind the loop from
+// predicated register loads of both operands, as in the one-buffer loop -- an LDS-DMA cannot write the zeros the rows past the slice's
+// end need.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage; all four instances 3 waves per SIMD, 49,536 bytes of static LDS -- three
+// workgroups are 145 KB of a CU's 160): TN with A fp32 168 VGPRs and 28 bytes of scratch (three address pairs spilled in front of the
+// loop and reloaded behind it, no scratch access inside it), TN with A an image 168 / 0, NN-tb with A fp32 168 / 0, with A an image 162 / 0.
+// The loop's waits as compiled: vmcnt(7) .. vmcnt(4) / vmcnt(4) in front of the split of the even / odd tile, vmcnt(8) in front of the
+// first barrier, none at the second.
+// Measured alone on the chip (tools/gemm_pipe_bench.py, profiles/r05/gemm_pipe.txt): 0.87 - 0.92 of the one-buffer loop's time.
+template <int BM, int BN, bool TA, bool TB, int NPL, bool PROBE = false, bool TR = false, bool WS = false, bool PIPE = false, bool APRE = false>
 __global__ __launch_bounds__(WS ? 512 : 256, (NPL == 2 && !WS && !PROBE) ? 3 : 1) void gemm_bf16x3_kernel(const GemmDesc d) {
     constexpr bool TRA = TR && TA && BM == 128, TRB = TR && TB && BN == 128;
+    static_assert(!PIPE || (NPL == 2 && !WS && !PROBE && TRB && BM == 128 && (TRA || !TA)), "pipelined form: fp16 x 2, 128 x 128, B through the transposing-read image");
     constexpr int MI = BM / 64, NI = BN / 64;
     // plane stride in bytes.  fp16 x 2: 64 bytes of padding between the hi and the lo plane -- a staged IMAGE slot is 16 bytes of ONE
     // piece, neighbouring lanes store hi / lo chunks of the same position, and without the shift each such pair hits the same banks
     constexpr int PA = BM * 64 + (NPL == 2 ? 64 : 0), PB = BN * 64 + (NPL == 2 ? 64 : 0);
-    constexpr int NBUF = WS ? 2 : 1;
+    constexpr int NBUF = WS ? 2 : 1, NBUFB = (WS || PIPE) ? 2 : 1;
     __shared__ __attribute__((aligned(16))) unsigned char As[NBUF * NPL * PA];
-    __shared__ __attribute__((aligned(16))) unsigned char Bs[NBUF * NPL * PB];
+    __shared__ __attribute__((aligned(16))) unsigned char Bs[NBUFB * NPL * PB];
     // a slot = 4 consecutive k of one row of the tile.  K-contiguous operand: one float4 (8 slots per row, lanes along k);
     // reduction-major operand: four dword loads down the source rows, lanes along the tile rows (coalesced)
     constexpr int NA = BM * BK / 4 / 256, NB = BN * BK / 4 / 256;
@@ -186,8 +213,10 @@ __global__ __launch_bounds__(WS ? 512 : 256, (NPL == 2 && !WS && !PROBE) ? 3 : 1
     };
 #pragma unroll
     for (int i = 0; i < NA; ++i) setup(d.A, Ab, TA, TRA, m0, d.M, BM, tid + i * 256, pa[i], wa[i], oka[i]);
+    if constexpr (!PIPE) {       // (pipelined form: B has one source pointer per lane, see its loop)
 #pragma unroll
-    for (int i = 0; i < NB; ++i) setup(d.B, Bb, TB, TRB, n0, d.N, BN, tid + i * 256, pb[i], wb[i], okb[i]);
+        for (int i = 0; i < NB; ++i) setup(d.B, Bb, TB, TRB, n0, d.N, BN, tid + i * 256, pb[i], wb[i], okb[i]);
+    }
 
     typedef f32x4 Slot;
     // fp16 x 2 only: per-operand power-of-two scales (measured maximum or the fixed one), undone in the epilogue
@@ -298,10 +327,10 @@ __global__ __launch_bounds__(WS ? 512 : 256, (NPL == 2 && !WS && !PROBE) ? 3 : 1
     const int ta_lo = lds_off_t(kg * 8 + tq, wm * (BM / 2) + (lane & 16) + 4 * tpp), ta_hi = lds_off_t(kg * 8 + 4 + tq, wm * (BM / 2) + (lane & 16) + 4 * tpp);
     const int tb_lo = lds_off_t(kg * 8 + tq, wn * (BN / 2) + (lane & 16) + 4 * tpp), tb_hi = lds_off_t(kg * 8 + 4 + tq, wn * (BN / 2) + (lane & 16) + 4 * tpp);
     const int nfull = (kend - kbeg) / BK;           // k-tiles that need no bounds checks
-    // one k-tile's products out of LDS buffer `buf`
-    auto multiply = [&](int buf) {
-        const unsigned char* Ab_ = As + buf * NPL * PA;
-        const unsigned char* Bb_ = Bs + buf * NPL * PB;
+    // one k-tile's products out of LDS buffers `bufa` of A and `bufb` of B
+    auto multiply = [&](int bufa, int bufb) {
+        const unsigned char* Ab_ = As + bufa * NPL * PA;
+        const unsigned char* Bb_ = Bs + bufb * NPL * PB;
 #pragma unroll
         for (int ks16 = 0; ks16 < BK / 16; ++ks16) {
             bf16x8 a[NPL][MI], b[NPL][NI];
@@ -378,8 +407,116 @@ __global__ __launch_bounds__(WS ? 512 : 256, (NPL == 2 && !WS && !PROBE) ? 3 : 1
         }
         lds_barrier();
         for (int kt = 0; kt < nk; ++kt) {
-            multiply(kt & 1);
+            multiply(kt & 1, kt & 1);
             lds_barrier();
+        }
+    } else if constexpr (PIPE) {
+        typedef __attribute__((address_space(3))) void* lds_vp;
+        // B by LDS-DMA.  Wave-instruction (wave, j) writes 1 KB = k-rows 16 * (j & 1) + 4 * wave .. + 3 of plane j >> 1, lane l the 16 bytes
+        // at chunk position l & 15 of k-row .. + (l >> 4): by lds_off_t that position holds the column group (l & 15) ^ (((k & 3) << 2) |
+        // ((k >> 2) & 3)) = (l & 15) ^ (((l >> 4) << 2) | wave), the same for all four.  Its hi pieces are the first 16 bytes of the
+        // image's group of eight, its lo pieces the second.  A group past the matrix edge reads group 0 of the row (as `setup`).
+        const int krl = lane >> 4;
+        const float* pq;
+        {
+            const int c = n0 + 8 * ((lane & 15) ^ ((krl << 2) | wave));
+            const int cc = c < d.N ? c : 0;                    // N % 8 == 0 (launcher): a group is inside or outside as a whole
+            const int sg = d.B.seglen ? cc / d.B.seglen : 0;
+            pq = Bb + (long)(kbeg + 4 * wave + krl) * d.B.ld + (long)sg * d.B.segstride + (d.B.seglen ? cc - sg * d.B.seglen : cc);
+        }
+        const long b16 = 16 * d.B.ld;
+        const long stepb = (long)BK * d.B.ld, stepa = TA ? (long)BK * d.A.ld : BK;      // (K-contiguous A: no K segments, launcher)
+        // Every request of the loop is unconditional, so that each tile is exactly NA loads + 4 DMAs on the wave's vmcnt queue and hipcc has
+        // no control flow to count loads across: the tile index is CLAMPED to the last whole tile instead (its last requests repeat that
+        // tile into a register set / a slot nobody reads any more; they are waited for behind the loop).
+        // The DMAs are asm statements, which hipcc does not count: its own waits -- for the registers of A(t) in front of the split -- then
+        // come out as if only A's loads were on the queue, vmcnt(NA), which on the real queue [A(t) B(t) A(t + 1)] retires exactly what the
+        // first barrier of tile t needs anyway.  (__builtin_amdgcn_global_load_lds beside plain loads makes hipcc wait vmcnt(0) for every
+        // register of A and again in front of the fragment reads of B.)  An LDS-DMA has no destination register, so rule (1) at the top of
+        // lstm_seq.hip does not bear on it; M0, the LDS base of the DMA, is written in the statement that reads it and put back.
+        const unsigned ldsb = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_vp)(Bs + wave * 1024));
+        auto dma16 = [&](const float* src, unsigned dst) {
+            unsigned keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+        };
+        auto issue_b = [&](int slot) {       // the tile pq points at -> slot
+            const unsigned sb = ldsb + slot * NPL * PB;
+            dma16(pq, sb);
+            dma16(pq + b16, sb + 4096);
+            dma16(pq + 4, sb + PB);
+            dma16(pq + b16 + 4, sb + PB + 4096);
+        };
+        auto load_a = [&](Slot (&qa)[NA]) {  // the tile pa[] points at
+#pragma unroll
+            for (int i = 0; i < NA; ++i) qa[i] = *reinterpret_cast<const f32x4*>(pa[i]);
+        };
+        auto advance_a = [&](bool yes) {
+            const long by = yes ? stepa : 0;
+#pragma unroll
+            for (int i = 0; i < NA; ++i) pa[i] += by;
+        };
+        // whole tile t: A(t) is in register set `qa` (requested two tiles ago), B(t) on its way into slot t & 1
+        auto step = [&](Slot (&qa)[NA], int t) {
+#pragma unroll
+            for (int i = 0; i < NA; ++i) sstore_one(As, PA, TA, TRA, BM, tid + i * 256, qa[i], sc_a, APRE);
+            // slot (t + 1) & 1 was last read by the multiply of tile t - 1, which every wave has left through the barrier behind it
+            pq += t + 1 < nfull ? stepb : 0;
+            issue_b((t + 1) & 1);
+            // my DMAs of B(t) have landed: younger than they are the NA loads of A(t + 1) and the 4 DMAs of B(t + 1)
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NA + 4) : "memory");
+            lds_barrier();
+            advance_a(t + 2 < nfull);
+            load_a(qa);                            // A(t + 2)
+            __builtin_amdgcn_sched_barrier(0);     // (hipcc sinks the requests to the end of the multiply otherwise)
+            multiply(0, t & 1);
+            lds_barrier();
+        };
+        Slot sa[NA];                               // second register set of A (ra is the first)
+        if (nfull > 0) {
+            load_a(ra);
+            issue_b(0);
+            advance_a(1 < nfull);
+            load_a(sa);
+            // (two plain loop bodies and no `break` between them: with one, hipcc's loop gets a second edge into its header, on which the
+            // other register set's loads look OLDER than the ones about to be read, and its wait in front of the split becomes vmcnt(0))
+            int t = 0;
+            for (; t + 1 < nfull; t += 2) {
+                step(ra, t);
+                step(sa, t + 1);
+            }
+            if (t < nfull) step(ra, t);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the repeated requests: nothing of mine is on its way into LDS any more
+        }
+        if (nk > nfull) {
+            // The slice's last k-tile is a partial one: predicated loads through registers for both operands, as the one-buffer loop (an
+            // LDS-DMA cannot write the zeros the rows past the slice's end need).  B goes into the slot tile nfull - 1 was read from:
+            // the other one may still be receiving another wave's repeated request.
+            const int slot = (nfull + 1) & 1;
+            const int k0 = kbeg + nfull * BK;
+#pragma unroll
+            for (int i = 0; i < NA; ++i) {
+                const int f = tid + i * 256;
+                const float* p;
+                int w;
+                bool ok;
+                setup(d.A, Ab, TA, TRA, m0, d.M, BM, f, p, w, ok);
+                p += TA ? (long)nfull * BK * d.A.ld : nfull * BK;
+                const Slot s = fetch(d.A, TA, TRA, p, w, ok, TRA ? k0 + f / 32 : k0 + (f % 8) * 4, false);
+                sstore_one(As, PA, TA, TRA, BM, f, s, sc_a, APRE);
+            }
+#pragma unroll
+            for (int i = 0; i < NB; ++i) {
+                const int f = tid + i * 256;
+                const float* p;
+                int w;
+                bool ok;
+                setup(d.B, Bb, TB, TRB, n0, d.N, BN, f, p, w, ok);
+                p += (long)nfull * BK * d.B.ld;
+                const Slot s = fetch(d.B, TB, TRB, p, w, ok, k0 + f / 32, false);
+                sstore_one(Bs + slot * NPL * PB, PB, TB, TRB, BN, f, s, sc_b, true);
+            }
+            lds_barrier();
+            multiply(0, slot);
         }
     } else {
     if (nk > 0) gload(kbeg, false);
@@ -396,7 +533,7 @@ __global__ __launch_bounds__(WS ? 512 : 256, (NPL == 2 && !WS && !PROBE) ? 3 : 1
         } else if (kt + 1 < nfull) gload(kbeg + (kt + 1) * BK, true);
         else if (kt + 1 < nk) gload(kbeg + (kt + 1) * BK, false);
         if (PROBE) { t1 = __builtin_readcyclecounter(); ph[2] += t1 - t0; t0 = t1; }
-        multiply(0);
+        multiply(0, 0);
         if (PROBE) { t1 = __builtin_readcyclecounter(); ph[3] += t1 - t0; t0 = t1; }
         if (!GDIAG(d, 32)) __syncthreads();        // all fragment reads done before the planes are overwritten
         if (PROBE) { t1 = __builtin_readcyclecounter(); ph[4] += t1 - t0; }
@@ -477,6 +614,15 @@ hipError_t launch_cfg(const GemmDesc& din, hipStream_t s) {
             if constexpr (CAN_WS) {
                 if ((d.flags & GEMM_F16X2) && ws && !d.diag) {
                     hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, TA, TB, 2, false, true, true>), grid, dim3(512), 0, s, d);
+                    return hipGetLastError();
+                }
+            }
+            // The pipelined k-loop where it has what it needs: a reduction-major B that comes as an image (LDS-DMA) -- the weight gradients of
+            // the decoder BLSTMs and of the convolutions (TN), the decoder's input gradients against the stacked weights' image (NN with tb)
+            if constexpr (TB && BM == 128 && BN == 128) {
+                if (g_gemm_pipe && (d.flags & GEMM_F16X2) && (d.flags & GEMM_B_PRE) && (TA || d.A.seglen == 0)) {
+                    if (d.flags & GEMM_A_PRE) hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, TA, TB, 2, false, true, false, true, true>), grid, dim3(256), 0, s, d);
+                    else hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, TA, TB, 2, false, true, false, true, false>), grid, dim3(256), 0, s, d);
                     return hipGetLastError();
                 }
             }

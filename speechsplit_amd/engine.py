@@ -844,8 +844,11 @@ def tune(key, value):
     _capi.check(_capi.lib().ss_tune(key.encode(), int(value)))
 
 
-def gemm(a, b, bias=None, ta=False, tb=False, ksplit=1, out=None, bf16=False, f16x2=False):
-    """Test hook for the MFMA GEMM: C[M,N] = A(m,k) B(n,k) (+bias).  a: [M,K] or [K,M] if ta; b: [N,K] or [K,N] if tb."""
+def gemm(a, b, bias=None, ta=False, tb=False, ksplit=1, out=None, bf16=False, f16x2=False, a_img=None, b_img=None, part=None, as_engine=False):
+    """Test hook for the MFMA GEMM: C[M,N] = A(m,k) B(n,k) (+bias).  a: [M,K] or [K,M] if ta; b: [N,K] or [K,N] if tb.
+    as_engine (f16x2 only, ss_op_gemm_pre): the launch as the engine's weight gradients make it -- the largest tile the shape admits, the
+    operands' images a_img / b_img (split_image, same strides as a / b) where given, and for ksplit > 1 partial slabs in `part`
+    (ksplit * M * N floats) added in a fixed order instead of atomics."""
     lib = _capi.lib()
     M = a.shape[1] if ta else a.shape[0]
     K = a.shape[0] if ta else a.shape[1]
@@ -853,6 +856,15 @@ def gemm(a, b, bias=None, ta=False, tb=False, ksplit=1, out=None, bf16=False, f1
     assert (b.shape[0] if tb else b.shape[1]) == K
     c = torch.zeros(M, N, device=a.device) if out is None else out
     assert tuple(c.shape) == (M, N) and c.stride(1) == 1
+    if as_engine:
+        assert f16x2 and not bf16 and bias is None
+        assert a_img is None or (a_img.shape == a.shape and a_img.stride() == a.stride())
+        assert b_img is None or (b_img.shape == b.shape and b_img.stride() == b.stride())
+        assert part is None or part.numel() >= ksplit * M * N
+        _capi.check(lib.ss_op_gemm_pre(_ptr(a), a.stride(0), _ptr(a_img), _ptr(b), b.stride(0), _ptr(b_img), _ptr(c), c.stride(0), _ptr(part), M, N, K,
+                                       (1 if ta else 0) | (2 if tb else 0), ksplit, _stream()))
+        return c
+    assert a_img is None and b_img is None and part is None
     _capi.check(lib.ss_op_gemm(_ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(c), c.stride(0), _ptr(bias), M, N, K,
                                (1 if ta else 0) | (2 if tb else 0) | (8 if bf16 else 0) | (16 if f16x2 else 0), ksplit, _stream()))
     return c
