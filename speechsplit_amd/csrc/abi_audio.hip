@@ -1,0 +1,233 @@
+// C entry points of the audio / data front end (include/speechsplit_amd.h): collation, mel spectrograms, F0 normalisation, the pitch
+// tracker, batched feature extraction and the Griffin-Lim vocoder.  None of them takes an engine: each checks its arguments, refuses by
+// the argument's name through ss_last_error() and hands the rest to the launchers of kernels.h.
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "abi.h"
+#include "kernels.h"
+#include "../../include/speechsplit_amd.h"
+
+using namespace ss;
+
+extern "C" {
+
+int ss_collate(const float* mel_cat, const float* f0_cat, const float* emb_tab, const long* row0, const int* len, const int* item,
+               int B, int T, int n_mel, int emb_dim, float* mel, float* f0, float* emb, void* stream) {
+    if (!mel_cat || !f0_cat || !emb_tab || !row0 || !len || !item || !mel || !f0 || !emb) return fail("ss_collate: null pointer");
+    if (B <= 0 || T <= 0 || n_mel <= 0 || emb_dim <= 0) return fail("ss_collate: bad shape");
+    HIPCHK(collate(mel_cat, f0_cat, emb_tab, row0, len, item, B, T, n_mel, emb_dim, mel, f0, emb, S(stream)));
+    return 0;
+}
+
+int ss_melspec_frames(int n) { return n >= 513 ? (n + 256) / 256 : 0; }
+
+int ss_melspec(const double* wav, int n, const double* mel_basis, int n_mels, float* out, void* stream) {
+    if (!wav || !mel_basis || !out) return fail("ss_melspec: null pointer");
+    if (n < 513) return fail("ss_melspec: at least 513 samples (reflect padding by 512)");
+    HIPCHK(melspec(wav, n, mel_basis, n_mels, out, ss_melspec_frames(n), S(stream)));
+    return 0;
+}
+
+int ss_f0_normalize(const double* f0, int n, float* out, void* stream) {
+    if (!f0 || !out || n < 1) return fail("ss_f0_normalize: bad arguments");
+    HIPCHK(f0_normalize(f0, n, out, S(stream)));
+    return 0;
+}
+
+// ---- pitch tracker (pitch.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+namespace {
+int pitch_shape(const char* who, int B, int max_n, double lo_hz, double hi_hz, PitchLags* g) {
+    if (B < 1 || B > PITCH_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
+    if (max_n < 513 || max_n > 256 * (SS_MAX_EVAL_FRAMES - 1))
+        return fail(std::string(who) + ": max_n outside 513 .. 256 * (SS_MAX_EVAL_FRAMES - 1)");
+    if (!(lo_hz > 0.0)) return fail(std::string(who) + ": lo_hz is NaN or not positive");
+    if (!(hi_hz > 0.0)) return fail(std::string(who) + ": hi_hz is NaN or not positive");
+    if (!(lo_hz < hi_hz)) return fail(std::string(who) + ": lo_hz is not below hi_hz");
+    if (!(floor(16000.0 / hi_hz) >= PITCH_MIN_LAG)) return fail(std::string(who) + ": hi_hz above 1000 (the shortest lag would be below 16 samples)");
+    if (!(ceil(16000.0 / lo_hz) <= PITCH_MAX_LAG)) return fail(std::string(who) + ": lo_hz below 40 (the longest lag would be above 400 samples)");
+    if (!pitch_lags(lo_hz, hi_hz, g)) return fail(std::string(who) + ": lo_hz .. hi_hz covers fewer than 3 lags");
+    return 0;
+}
+int pitch_scratch_ok(const char* who, int B, int max_n, const PitchLags& g, const void* scratch, long scratch_bytes) {
+    if (!scratch) return fail(std::string(who) + ": null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail(std::string(who) + ": scratch_dev is not 256-byte aligned");
+    if (scratch_bytes < pitch_scratch_bytes(B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1))
+        return fail(std::string(who) + ": scratch_bytes below ss_pitch_scratch_bytes(B, max_n, lo_hz, hi_hz)");
+    return 0;
+}
+}  // namespace
+
+long ss_pitch_scratch_bytes(int B, int max_n, double lo_hz, double hi_hz) {
+    PitchLags g;
+    CHK(pitch_shape("ss_pitch_scratch_bytes", B, max_n, lo_hz, hi_hz, &g));
+    return pitch_scratch_bytes(B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1);
+}
+
+int ss_pitch_track(const double* wav, const int* n, int B, int max_n, double scale, double lo_hz, double hi_hz, double* f0, void* scratch,
+                   long scratch_bytes, void* stream) {
+    PitchLags g;
+    if (!wav) return fail("ss_pitch_track: null pointer: wav_dev");
+    if (!f0) return fail("ss_pitch_track: null pointer: f0_dev");
+    CHK(pitch_shape("ss_pitch_track", B, max_n, lo_hz, hi_hz, &g));
+    if (!(scale > 0.0) || std::isinf(scale)) return fail("ss_pitch_track: scale is not finite or not positive");
+    CHK(pitch_scratch_ok("ss_pitch_track", B, max_n, g, scratch, scratch_bytes));
+    const PitchScratch sc = pitch_scratch(scratch, B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1);
+    HIPCHK(pitch_nccf(wav, n, B, max_n, scale, g, sc.phi, sc.rms, S(stream)));
+    HIPCHK(pitch_dp(sc.phi, sc.rms, n, B, max_n, g, f0, sc, S(stream)));
+    return 0;
+}
+
+int ss_op_nccf(const double* wav, const int* n, int B, int max_n, double scale, double lo_hz, double hi_hz, double* phi, double* rms,
+               void* stream) {
+    PitchLags g;
+    if (!wav) return fail("ss_op_nccf: null pointer: wav_dev");
+    if (!phi) return fail("ss_op_nccf: null pointer: phi_dev");
+    if (!rms) return fail("ss_op_nccf: null pointer: rms_dev");
+    CHK(pitch_shape("ss_op_nccf", B, max_n, lo_hz, hi_hz, &g));
+    if (!(scale > 0.0) || std::isinf(scale)) return fail("ss_op_nccf: scale is not finite or not positive");
+    HIPCHK(pitch_nccf(wav, n, B, max_n, scale, g, phi, rms, S(stream)));
+    return 0;
+}
+
+int ss_op_pitch_dp(const double* phi, const double* rms, const int* n, int B, int max_n, double lo_hz, double hi_hz, double* f0,
+                   void* scratch, long scratch_bytes, void* stream) {
+    PitchLags g;
+    if (!phi) return fail("ss_op_pitch_dp: null pointer: phi_dev");
+    if (!rms) return fail("ss_op_pitch_dp: null pointer: rms_dev");
+    if (!f0) return fail("ss_op_pitch_dp: null pointer: f0_dev");
+    CHK(pitch_shape("ss_op_pitch_dp", B, max_n, lo_hz, hi_hz, &g));
+    CHK(pitch_scratch_ok("ss_op_pitch_dp", B, max_n, g, scratch, scratch_bytes));
+    HIPCHK(pitch_dp(phi, rms, n, B, max_n, g, f0, pitch_scratch(scratch, B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1), S(stream)));
+    return 0;
+}
+
+// ---- batched feature extraction (filtfilt.hip, features.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+namespace {
+int feat_shape(const char* who, int B, int max_n) {
+    if (B < 1 || B > FEAT_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
+    if (max_n < 513 || max_n > 256 * (SS_MAX_EVAL_FRAMES - 1))
+        return fail(std::string(who) + ": max_n outside 513 .. 256 * (SS_MAX_EVAL_FRAMES - 1)");
+    return 0;
+}
+}  // namespace
+
+long ss_filtfilt_scratch_bytes(int B, int max_n) {
+    CHK(feat_shape("ss_filtfilt_scratch_bytes", B, max_n));
+    return filtfilt_scratch_bytes(B, max_n);
+}
+
+int ss_filtfilt(const double* x, const int* n, int B, int max_n, const double* b, const double* a, const double* zi, double gain,
+                const double* dither, double dither_scale, double* y, void* scratch, long scratch_bytes, void* stream) {
+    if (!x) return fail("ss_filtfilt: null pointer: x_dev");
+    if (!b) return fail("ss_filtfilt: null pointer: b");
+    if (!a) return fail("ss_filtfilt: null pointer: a");
+    if (!zi) return fail("ss_filtfilt: null pointer: zi");
+    if (!y) return fail("ss_filtfilt: null pointer: y_dev");
+    CHK(feat_shape("ss_filtfilt", B, max_n));
+    FiltCoef c;
+    for (int i = 0; i < FILT_NCOEF; ++i) {
+        if (!std::isfinite(b[i])) return fail("ss_filtfilt: b[" + std::to_string(i) + "] is not finite");
+        if (!std::isfinite(a[i])) return fail("ss_filtfilt: a[" + std::to_string(i) + "] is not finite");
+        if (i < FILT_NCOEF - 1 && !std::isfinite(zi[i])) return fail("ss_filtfilt: zi[" + std::to_string(i) + "] is not finite");
+        c.b[i] = b[i];
+        c.a[i] = a[i];
+        if (i < FILT_NCOEF - 1) c.zi[i] = zi[i];
+    }
+    if (a[0] != 1.0) return fail("ss_filtfilt: a[0] is not exactly 1 (normalise b and a on the host, as scipy does)");
+    if (!std::isfinite(gain)) return fail("ss_filtfilt: gain is not finite");
+    if (!std::isfinite(dither_scale)) return fail("ss_filtfilt: dither_scale is not finite");
+    if (!scratch) return fail("ss_filtfilt: null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail("ss_filtfilt: scratch_dev is not 256-byte aligned");
+    if (scratch_bytes < filtfilt_scratch_bytes(B, max_n)) return fail("ss_filtfilt: scratch_bytes below ss_filtfilt_scratch_bytes(B, max_n)");
+    HIPCHK(filtfilt(x, n, B, max_n, c, gain, dither, dither_scale, y, (double*)scratch, S(stream)));
+    return 0;
+}
+
+int ss_melspec_batch(const double* wav, const int* n, int B, int max_n, const double* mel_basis, int n_mels, float* out, void* stream) {
+    if (!wav) return fail("ss_melspec_batch: null pointer: wav_dev");
+    if (!mel_basis) return fail("ss_melspec_batch: null pointer: mel_basis_dev");
+    if (!out) return fail("ss_melspec_batch: null pointer: out_dev");
+    CHK(feat_shape("ss_melspec_batch", B, max_n));
+    if (n_mels < 1) return fail("ss_melspec_batch: n_mels below 1");
+    HIPCHK(melspec_batch(wav, n, B, max_n, mel_basis, n_mels, out, S(stream)));
+    return 0;
+}
+
+int ss_f0_normalize_batch(const double* f0, const int* n, int B, int max_n, double unvoiced, float* out, void* stream) {
+    if (!f0) return fail("ss_f0_normalize_batch: null pointer: f0_dev");
+    if (!out) return fail("ss_f0_normalize_batch: null pointer: out_dev");
+    CHK(feat_shape("ss_f0_normalize_batch", B, max_n));
+    if (std::isnan(unvoiced)) return fail("ss_f0_normalize_batch: unvoiced is NaN");
+    HIPCHK(f0_normalize_batch(f0, n, B, max_n, unvoiced, out, S(stream)));
+    return 0;
+}
+
+// ---- Griffin-Lim vocoder (vocoder.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+namespace {
+int voc_shape(const char* who, int B, int max_frames) {
+    if (B < 1 || B > VOC_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
+    if (max_frames < 4 || max_frames > SS_MAX_EVAL_FRAMES)
+        return fail(std::string(who) + ": max_frames outside 4 .. SS_MAX_EVAL_FRAMES (reflect padding needs 4 frames)");
+    return 0;
+}
+int voc_scratch(const char* who, int B, int max_frames, const void* scratch, long scratch_bytes) {
+    if (!scratch) return fail(std::string(who) + ": null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail(std::string(who) + ": scratch_dev is not 256-byte aligned");
+    if (scratch_bytes < vocoder_scratch_bytes(B, max_frames))
+        return fail(std::string(who) + ": scratch_bytes below ss_griffinlim_scratch_bytes(B, max_frames)");
+    return 0;
+}
+}  // namespace
+
+int ss_griffinlim_samples(int frames) { return frames >= 4 ? 256 * (frames - 1) : 0; }
+
+long ss_griffinlim_scratch_bytes(int B, int max_frames) {
+    CHK(voc_shape("ss_griffinlim_scratch_bytes", B, max_frames));
+    return vocoder_scratch_bytes(B, max_frames);
+}
+
+int ss_mel_to_linear(const float* mel, const double* inv_basis, const int* frames, int B, int max_frames, int n_mels, double floor,
+                     double* mag, void* stream) {
+    if (!mel) return fail("ss_mel_to_linear: null pointer: mel_dev");
+    if (!inv_basis) return fail("ss_mel_to_linear: null pointer: inv_basis_dev");
+    if (!mag) return fail("ss_mel_to_linear: null pointer: mag_dev");
+    CHK(voc_shape("ss_mel_to_linear", B, max_frames));
+    if (n_mels < 1 || n_mels > VOC_MAX_MELS) return fail("ss_mel_to_linear: n_mels outside 1 .. 4096");
+    if (!(floor >= 0.0)) return fail("ss_mel_to_linear: floor is negative or NaN");
+    HIPCHK(mel_to_linear(mel, inv_basis, frames, B, max_frames, n_mels, floor, mag, S(stream)));
+    return 0;
+}
+
+int ss_griffinlim(const double* mag, const double* phase0, const int* frames, int B, int max_frames, int n_iter, double momentum,
+                  double* wav, void* scratch, long scratch_bytes, void* stream) {
+    if (!mag) return fail("ss_griffinlim: null pointer: mag_dev");
+    if (!wav) return fail("ss_griffinlim: null pointer: wav_dev");
+    CHK(voc_shape("ss_griffinlim", B, max_frames));
+    if (n_iter < 0 || n_iter > 1024) return fail("ss_griffinlim: n_iter outside 0 .. 1024");
+    if (!(momentum >= 0.0 && momentum < 1.0)) return fail("ss_griffinlim: momentum outside [0, 1) or NaN");
+    CHK(voc_scratch("ss_griffinlim", B, max_frames, scratch, scratch_bytes));
+    HIPCHK(griffinlim(mag, phase0, frames, B, max_frames, n_iter, momentum, wav, vocoder_scratch(scratch, B, max_frames), S(stream)));
+    return 0;
+}
+
+int ss_op_stft(const double* wav, const int* frames, int B, int max_frames, double* spec, void* stream) {
+    if (!wav) return fail("ss_op_stft: null pointer: wav_dev");
+    if (!spec) return fail("ss_op_stft: null pointer: spec_dev");
+    CHK(voc_shape("ss_op_stft", B, max_frames));
+    HIPCHK(stft(wav, frames, B, max_frames, spec, S(stream)));
+    return 0;
+}
+
+int ss_op_istft(const double* spec, const int* frames, int B, int max_frames, double* wav, void* scratch, long scratch_bytes,
+                void* stream) {
+    if (!spec) return fail("ss_op_istft: null pointer: spec_dev");
+    if (!wav) return fail("ss_op_istft: null pointer: wav_dev");
+    CHK(voc_shape("ss_op_istft", B, max_frames));
+    CHK(voc_scratch("ss_op_istft", B, max_frames, scratch, scratch_bytes));
+    HIPCHK(istft(spec, frames, B, max_frames, wav, vocoder_scratch(scratch, B, max_frames).frame_buf, S(stream)));
+    return 0;
+}
+
+}  // extern "C"

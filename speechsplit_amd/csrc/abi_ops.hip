@@ -1,0 +1,279 @@
+// Engine-free kernel hooks of the C ABI (include/speechsplit_amd.h): single GEMM / image / LSTM launches for the tests and tools/, the
+// placement probes and ss_tune.  None of them takes an engine.
+#include <string>
+
+#include "abi.h"
+#include "knobs.h"
+#include "kernels.h"
+#include "../../include/speechsplit_amd.h"
+
+using namespace ss;
+
+namespace ss {
+int g_op_time_major = 0;   // experiment: ss_op_lstm_fwd / _bwd take time-major slabs [T+4, B, C] (persistent kernels only)
+static unsigned* g_img_wq = nullptr;      // queue words (+ placement log) of the test hook's work-queue launches
+constexpr long IMG_WQ_BYTES = 16 + 16 * 1024;
+int g_img_xcc = 0;      // ss_op_gemm_img (test hook): run the image GEMM in its work-queue form on the XCDs of this mask
+}
+
+extern "C" {
+
+int ss_op_gemm(const float* a, long lda, const float* b, long ldb, float* c, long ldc, const float* bias, int M, int N, int K,
+               int flags, int ksplit, void* stream) {
+    GemmDesc d{};
+    d.A = {a, lda, 0, 0, 0};
+    d.B = {b, ldb, 0, 0, 0};
+    d.C = c;
+    d.ldc = ldc;
+    d.bias = bias;
+    d.M = M;
+    d.N = N;
+    d.K = K;
+    d.batch = 1;
+    d.ksplit = ksplit < 1 ? 1 : ksplit;
+    d.flags = (flags & 1 ? GEMM_TA : 0) | (flags & 2 ? GEMM_TB : 0) | (flags & 8 ? GEMM_BF16 : 0) | (flags & 16 ? GEMM_F16X2 : 0) | (d.ksplit > 1 ? GEMM_ACCUM : 0);
+    HIPCHK(launch_gemm(d, S(stream)));
+    return 0;
+}
+
+int ss_op_gemm_pre(const float* a, long lda, const float* a_img, const float* b, long ldb, const float* b_img, float* c, long ldc, float* part, int M,
+                   int N, int K, int flags, int ksplit, void* stream) {
+    if (!a || !b || !c) return fail("ss_op_gemm_pre: null pointer");
+    GemmDesc d{};
+    d.A = {a, lda, 0, 0, 0};
+    d.B = {b, ldb, 0, 0, 0};
+    d.a_pre = a_img;
+    d.b_pre = b_img;
+    d.C = c;
+    d.ldc = ldc;
+    d.M = M;
+    d.N = N;
+    d.K = K;
+    d.batch = 1;
+    d.ksplit = ksplit < 1 ? 1 : ksplit;
+    d.part = part;
+    d.want = 1;           // the largest tile the shape admits, whatever the number of workgroups: the form under test
+    d.flags = (flags & 1 ? GEMM_TA : 0) | (flags & 2 ? GEMM_TB : 0) | GEMM_F16X2 | (d.ksplit > 1 ? GEMM_ACCUM : 0);
+    HIPCHK(launch_gemm(d, S(stream)));
+    return 0;
+}
+
+int ss_op_split_image(const float* src, long ld, long rows, int cols, float scale, float* img, long ldi, void* stream) {
+    if (!src || !img) return fail("ss_op_split_image: null pointer");
+    HIPCHK(split_image(src, ld, rows, cols, nullptr, scale, img, ldi, nullptr, S(stream)));
+    return 0;
+}
+
+int ss_op_gemm_img(const float* a_img, long lda, const float* b_img, long ldb, float* c, long ldc, const float* bias, int M, int N, int K, int flags,
+                   int ksplit, int cfg, float scale_a, float scale_b, int a_seglen, long a_segstride, float* part, const void* zeros, void* stream) {
+    static float* sc = nullptr;           // the two scales as device words (test hook: one call at a time)
+    if (!sc) HIPCHK(hipMalloc((void**)&sc, 256));
+    const float h[2] = {scale_a, scale_b};
+    HIPCHK(hipMemcpyAsync(sc, h, sizeof(h), hipMemcpyHostToDevice, S(stream)));
+    ImgGemmDesc d{};
+    d.A = {a_img, lda, 0, a_seglen, a_segstride};
+    d.B = {b_img, ldb, 0, 0, 0};
+    d.C = c;
+    d.ldc = ldc;
+    d.bias = bias;
+    d.M = M;
+    d.N = N;
+    d.K = K;
+    d.batch = 1;
+    d.ksplit = ksplit < 1 ? 1 : ksplit;
+    d.flags = (flags & 1 ? GEMM_TA : 0) | (flags & 2 ? GEMM_TB : 0) | (flags & 4 ? GEMM_ACCUM : 0);
+    d.bf16 = (flags & 8) ? 1 : 0;           // single-piece form: the operands are plain bf16 matrices, ld in elements
+    d.part = part;
+    d.scale_a = d.bf16 ? nullptr : sc;
+    d.scale_b = d.bf16 ? nullptr : sc + 1;
+    d.zeros = zeros;
+    d.cfg = cfg;
+    d.diag = g_gemm_diag;
+    if (g_img_xcc) {                      // test hook for the work-queue form: ss_tune("img_xcc", mask of allowed XCDs; 255 = queue without a filter)
+        if (!g_img_wq) HIPCHK(hipMalloc((void**)&g_img_wq, IMG_WQ_BYTES));
+        HIPCHK(hipMemsetAsync(g_img_wq, 0, (g_img_xcc & 0x100) ? IMG_WQ_BYTES : 8, S(stream)));
+        d.wq = g_img_wq;
+        d.xcc_allow = (unsigned)g_img_xcc;
+    }
+    if (!gemm_img_supported(d)) return fail("ss_op_gemm_img: shape / alignment not supported by the image GEMM");
+    HIPCHK(launch_gemm_img(d, S(stream)));
+    return 0;
+}
+
+// Where do the workgroups of a launch go?  n_wg workgroups of `threads` threads and lds_bytes of LDS each record (XCC_ID register, HW_ID
+// register) in launch order; each then idles `hold_ticks` (100 MHz) so that the whole grid has to be resident at once.
+__global__ void xcc_map_kernel(unsigned* out, long long hold_ticks) {
+    extern __shared__ unsigned char xcc_map_lds[];
+    if (threadIdx.x == 0) {
+        unsigned x, h;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(h));
+        out[2 * blockIdx.x] = x;
+        out[2 * blockIdx.x + 1] = h;
+        xcc_map_lds[0] = (unsigned char)x;
+    }
+    const long long t0 = wall_clock64();
+    while (wall_clock64() - t0 < hold_ticks) __builtin_amdgcn_s_sleep(8);
+}
+int ss_debug_xcc_map(int n_wg, int threads, int lds_bytes, int hold_us, unsigned* out_dev, void* stream) {
+    if (!out_dev || n_wg < 1 || threads < 64 || threads > 1024 || lds_bytes < 0 || lds_bytes > 160 * 1024 || hold_us < 0 || hold_us > 2000)
+        return fail("ss_debug_xcc_map: bad arguments");
+    if (lds_bytes > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)xcc_map_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    hipLaunchKernelGGL(xcc_map_kernel, dim3(n_wg), dim3(threads), lds_bytes, S(stream), out_dev, (long long)hold_us * 100);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int ss_debug_img_wq(unsigned* out_host, int words) {
+    if (!out_host || words < 1 || words * 4L > IMG_WQ_BYTES || !g_img_wq) return fail("ss_debug_img_wq: nothing logged / bad size");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out_host, g_img_wq, words * 4L, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int ss_debug_gemm_phases(unsigned long long* out24, int reset) {
+    if (!out24) return fail("ss_debug_gemm_phases: null pointer");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(gemm_phase_probe(out24, reset != 0));
+    return 0;
+}
+
+int ss_tune(const char* key, int value) {
+    struct Key {
+        const char* name;
+        int* target;
+        int lo, hi;      // accepted values: lo <= value <= hi
+    };
+    constexpr int MAXV = 0x7fffffff;
+    static const Key keys[] = {
+        {"lstm_nw", &g_lstm_nw, 4, 16},      // 4, 8 or 16 (checked below)
+        {"lstm_g", &g_lstm_g, 0, 16},
+#ifdef SS_DIAG
+        {"lstm_mode", &g_lstm_mode, 0, 4},
+        {"gemm_diag", &g_gemm_diag, 0, 2047},
+        {"seq_prio", &g_seq_prio, 0, 65535},
+#else
+        {"seq_prio", &g_seq_prio, 0, 1},
+#endif
+        {"seq_tag", &g_seq_tag, 0, 1},
+        {"op_time_major", &g_op_time_major, 0, 1},
+        {"seq_var", &g_seq_var, 0, 15},
+        {"compact0", &g_compact0, 0, 1},
+        {"bf16_img", &g_bf16_img, 0, 1},
+        {"dp_model", &g_dp_model, 0, 64},
+        {"dp_buckets", &g_dp_buckets, 0, 1},
+        {"gemm_ws", &g_gemm_ws, 0, 2},
+        {"gemm_pipe", &g_gemm_pipe, 0, 1},
+        {"seq_spin_log2", &g_seq_spin_log2, 0, 24},
+        {"overlap", &g_overlap, 0, 1},
+        {"defer_dw", &g_defer_dw, 0, 1},
+        {"dx_batched", &g_dx_batched, 0, 2},
+        {"small_lds", &g_small_lds, 0, 2},
+        {"gemm_tr", &g_gemm_tr, 0, 2},
+        {"own_streams", &g_own_streams, 0, 1},
+        {"conv_dw_off", &g_conv_dw_off, 0, 3},
+        {"dec_tail_split", &g_dec_tail_split, 0, 10},
+        {"early_dw", &g_early_dw, 0, 1},
+        {"xcd_dw", &g_xcd_dw, 0, 1},
+        {"dp_emulate", &g_dp_emulate, 0, 1},
+        {"gn_gather", &g_gn_gather, 0, 1},
+        {"img_xcc", &g_img_xcc, 0, 511},      // bit 8: keep a placement log (ss_debug_img_wq)
+        {"probe_queues", &g_probe_queues, 0, 1},
+        {"prio_order", &g_prio_order, 0, 1},
+        {"deterministic", &g_deterministic, 0, 1},
+        {"persist", &g_persist, 0, 1},
+        {"gemm_want", &g_gemm_want, 1, MAXV},
+        {"gemm_mode", &g_gemm_mode, 0, 1},
+        {"fwd_f16x2", &g_fwd_f16x2, 0, 1},
+        {"bwd_f16x2", &g_bwd_f16x2, 0, 1},
+    };
+    const std::string k = key ? key : "";
+    for (const Key& t : keys) {
+        if (k != t.name) continue;
+        if (value < t.lo || value > t.hi || (t.target == &g_lstm_nw && value != 4 && value != 8 && value != 16)) break;
+        *t.target = value;
+        return 0;
+    }
+    return fail("ss_tune: unknown key or bad value: " + k
+#ifndef SS_DIAG
+                     + " (the wrong-result timing modes lstm_mode / gemm_diag / seq_prio > 1 exist only in the -DSS_DIAG build: make diag)"
+#endif
+    );
+}
+
+static int op_lstm_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch,
+                       long scratch_floats, const int* len, int B, int T, int H, void* stream) {
+    hipStream_t s = S(stream);
+    if (H > 32) {
+        const long half = 2L * (((B + 15) / 16) * 16) * H, wn = 2L * 4 * H * H;
+        if (!scratch || scratch_floats < wn + 2 * half) return fail("ss_op_lstm_fwd: scratch too small");
+        float* hf = scratch + wn;
+        if (g_persist && lstm_seq_supported(B, H) && wn * 4 >= lstm_seq_xbytes(B, H, false)) {
+            // exchange buffer in the (unused) packed-weight area, counters behind it
+            HIPCHK(lstm_seq_fwd(gates, whh_f, whh_b, scratch, out, csave, (unsigned*)hf, B, T, H, s, {.time_major = g_op_time_major != 0, .len = len}));
+            return 0;
+        }
+        HIPCHK(lstm_pack_w(whh_f, whh_b, scratch, H, 0, s));
+        HIPCHK(hipMemsetAsync(hf, 0, 2 * half * 4, s));
+        for (int st = 0; st < T; ++st)
+            HIPCHK(lstm_step_fwd(gates, scratch, hf + (st & 1) * half, hf + ((st & 1) ^ 1) * half, out, csave, B, T, H, st, s, len));
+    } else {
+        HIPCHK(lstm_small_fwd(gates, whh_f, whh_b, out, csave, B, T, H, s, len));
+    }
+    return 0;
+}
+
+int ss_op_lstm_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch,
+                   long scratch_floats, int B, int T, int H, void* stream) {
+    return op_lstm_fwd(gates, whh_f, whh_b, out, csave, scratch, scratch_floats, nullptr, B, T, H, stream);
+}
+
+int ss_op_lstm_fwd_ragged(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch,
+                          long scratch_floats, const int* len_dev, int B, int T, int H, void* stream) {
+    if (!gates || !whh_f || !whh_b || !out || !csave || B < 1 || T < 1) return fail("ss_op_lstm_fwd_ragged: null pointer or empty shape");
+    return op_lstm_fwd(gates, whh_f, whh_b, out, csave, scratch, scratch_floats, len_dev, B, T, H, stream);
+}
+
+int ss_op_lstm_bwd(float* gates, const float* whh_f, const float* whh_b, const float* d_out, const float* csave,
+                   float* scratch, long scratch_floats, int B, int T, int H, void* stream) {
+    hipStream_t s = S(stream);
+    if (H > 32) {
+        const long half = 2L * (((B + 15) / 16) * 16) * 4 * H, wn = 2L * 4 * H * H;
+        if (!scratch || scratch_floats < wn + 2 * half + 2L * B * H) return fail("ss_op_lstm_bwd: scratch too small");
+        float* gf = scratch + wn;
+        float* dc = gf + 2 * half;
+        const long xbytes = lstm_seq_xbytes(B, H, true);
+        if (g_persist && lstm_seq_supported(B, H) && scratch_floats * 4 >= xbytes + 4L * LSTM_SEQ_SYNC_WORDS) {     // [exchange tiles][flags]
+            HIPCHK(lstm_seq_bwd(gates, whh_f, whh_b, scratch, d_out, csave, (unsigned*)((char*)scratch + xbytes), B, T, H, s,
+                                {.time_major = g_op_time_major != 0}));
+            return 0;
+        }
+        HIPCHK(lstm_pack_w(whh_f, whh_b, scratch, H, 1, s));
+        HIPCHK(hipMemsetAsync(gf, 0, 2 * half * 4, s));
+        for (int st = 0; st < T; ++st)
+            HIPCHK(lstm_step_bwd(gates, scratch, gf + (st & 1) * half, gf + ((st & 1) ^ 1) * half, d_out, csave, dc, B, T, H, st, s));
+    } else {
+        HIPCHK(lstm_small_bwd(gates, whh_f, whh_b, d_out, csave, B, T, H, s));
+    }
+    return 0;
+}
+
+int ss_op_lstm_wgrad(const float* dg, const float* x, long x_ld, const float* hout, float* gwih, float* gwhh, float* gb, float* scratch, long scratch_floats,
+                     long R, int H, int In, void* stream) {
+    if (H < 1 || H > 32 || In < 1 || R < 1) return fail("ss_op_lstm_wgrad: H in 1..32, In >= 1");
+    WgradTable w{};
+    w.n = 1;
+    w.tiles_total = lstm_small_wgrad_tiles(H, In);
+    w.row_groups = 16;
+    const long need = (long)w.tiles_total * w.row_groups * 4096, ctr_floats = (w.tiles_total + 63) & ~63L;
+    if (!scratch || scratch_floats < need + ctr_floats) return fail("ss_op_lstm_wgrad: scratch too small");
+    w.part = scratch;
+    w.ctr = (unsigned*)(scratch + need);
+    HIPCHK(hipMemsetAsync(w.ctr, 0, ctr_floats * 4, S(stream)));
+    // gwih [2][4H][In], gwhh [2][4H][H], gb [2][2][4H] (b_ih then b_hh per direction): accumulated into, as the engine's gradient arena is
+    w.t[0] = WgradTask{dg, x, x_ld, hout, gwih, gwih + 4L * H * In, gwhh, gwhh + 4L * H * H, gb, gb + 4L * H, gb + 8L * H, gb + 12L * H, H, In, R, 0, 2 * H};
+    HIPCHK(lstm_small_wgrad(w, S(stream)));
+    return 0;
+}
+
+}  // extern "C"

@@ -1,11 +1,10 @@
 // HBM/L2-bound kernels of the SpeechSplit path: GroupNorm+ReLU (fwd/bwd), bias/affine gradient sums, weight
 // re-layouts, decoder-input assembly, losses and the flat Adam update.
 #include "common.h"
+#include "knobs.h"
 #include "kernels.h"
 
 namespace ss {
-
-extern int g_deterministic;
 
 namespace {
 

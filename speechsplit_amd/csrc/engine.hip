@@ -18,14 +18,14 @@
 #include <cstdio>
 
 #include "common.h"
+#include "abi.h"
+#include "knobs.h"
 #include "kernels.h"
 #include "../../include/speechsplit_amd.h"
 
 using namespace ss;
 
 namespace ss {
-extern int g_small_lds, g_gemm_tr, g_deterministic;
-extern int g_lstm_nw, g_lstm_g, g_lstm_mode, g_gemm_want, g_gemm_diag, g_seq_prio, g_gemm_mode, g_seq_spin_log2, g_seq_tag, g_seq_var, g_gemm_ws, g_gemm_pipe;
 int g_fwd_f16x2 = 1;   // 1: forward contractions (operands bounded by construction: mel, one-hot, GroupNorm/ReLU outputs, |h| < 1, weights)
                        //    use the fp16 x 2 split (3 MFMAs) instead of bf16 x 3 (6 MFMAs); gradients keep bf16 x 3 (their range is not bounded)
 int g_bwd_f16x2 = 1;   // 1: the decoder's and the conv trunk's gradient GEMMs also use fp16 x 2: the gradient operand is scaled by the power
@@ -43,7 +43,6 @@ int g_bf16_img = 1;        // SS_PRECISION_BF16: the 16-bit data path (round 4) 
                            // (a decoder layer whose gradient consumers all read the bf16 tensor does not get the fp32 copy of its pre-activation gradients,
                            // and the persistent recurrences multiply the high fp16 pieces only: one MFMA per product, half the forward's payload)
 int g_compact0 = 1;        // decoder layer 0: input projections, input gradient and W_ih gradient once per block of repeated input frames
-int g_op_time_major = 0;   // experiment: ss_op_lstm_fwd / _bwd take time-major slabs [T+4, B, C] (persistent kernels only)
 int g_persist = 1;     // 1: decoder recurrences run as ONE persistent launch per layer (lstm_seq.hip) when the batch fits
 // (hipGraph capture + replay of the fused step: built and measured in rounds 1-3 -- no gain while the step is GPU-bound, and a crash inside
 // the ROCm 7.2 runtime's hipGraphLaunch with more parallel branches -- and deleted in round 4; the step is enqueued eagerly.)
@@ -58,8 +57,6 @@ int g_prio_order = 1;  // 1: within every phase the critical-path launches are E
                        //    queues; when two engine streams share one (other streams in the process, e.g. RCCL's, shift the assignment), enqueue
                        //    order is execution order, and filler work enqueued first would run in front of the critical path.
 int g_probe_queues = 1; // 1: ss_bind measures which candidate streams share a hardware queue and picks branch streams that do not (pick_streams)
-static unsigned* g_img_wq = nullptr;      // queue words (+ placement log) of the test hook's work-queue launches
-constexpr long IMG_WQ_BYTES = 16 + 16 * 1024;
 int g_gn_gather = 1;    // training forward of the independent trunk chains: GroupNorm + ReLU + resampling gather in one kernel (gn_relu_gather)
 int g_conv_dw_off = 1;      // Generator_6 (one trunk chain, the second branch stream idle behind lstm's backward): the conv blocks' weight-gradient GEMMs leave
                         // the dependent chain gn backward -> input gradient -> next block for that stream; every block then keeps its own conv-output
@@ -88,26 +85,16 @@ int g_xcd_dw = 0;       // decoder W_ih gradients beside the backward recurrence
                         // recurrence, but each recurrence stretches by ~40 us (its operand fetches share HBM with the GEMM's streams), the image
                         // pass and the split-K reduce land beside the input-gradient GEMM on the critical path, and at B <= 32 the encoder
                         // backward that loses the work is chain-bound, not throughput-bound (profiles/r03/xcd_overlap.txt)
-int g_img_xcc = 0;      // ss_op_gemm_img (test hook): run the image GEMM in its work-queue form on the XCDs of this mask
-}
 
-namespace {
-
+// the error string behind ss_last_error(): ONE object for every translation unit that refuses through fail() (abi.h)
 thread_local std::string g_err;
 int fail(const std::string& m) {
     g_err = m;
     return -1;
 }
-#define HIPCHK(x)                                                                      \
-    do {                                                                               \
-        hipError_t _e = (x);                                                           \
-        if (_e != hipSuccess) return fail(std::string(#x) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-#define CHK(x)                 \
-    do {                       \
-        int _r = (x);          \
-        if (_r != 0) return _r; \
-    } while (0)
+}
+
+namespace {
 
 struct ParamInfo {
     std::string name;
@@ -715,9 +702,6 @@ long carve(E& e, int B, int T) {
 
 namespace {
 
-hipStream_t S(void* s) { return (hipStream_t)s; }
-
-
 // eval: the call is an eval-mode forward (ss_g3_forward / ss_g6_forward with training == 0, ss_g3_rhythm).  Those may run T beyond
 // max_frames, up to SS_MAX_EVAL_FRAMES, whenever the plan for (B, T) fits the bound workspace; everything that trains or differentiates
 // keeps T <= max_frames (<= 256: the register-resident GroupNorm backward and the fused gathers).
@@ -999,106 +983,6 @@ struct Own {
     Own(const Own&) = delete;
     Own& operator=(const Own&) = delete;
 };
-
-
-// ---- hardware-queue probe ---------------------------------------------------------------------------------------------------------
-// HIP multiplexes a process's streams onto a few in-order hardware queues (4 by default) and does not say which stream got which.
-// Two streams on one queue execute strictly one after the other, so the step's branches lose the concurrency they exist for:
-// measured 6.34 ms with the four engine streams on four queues against 7.22 ms with the side stream on the main stream's queue
-// (profiles/r02/stream_order_effect.txt; which case one gets depends on how many streams the process -- PyTorch, RCCL -- created
-// before).  The serialisation is also what makes the assignment MEASURABLE: a kernel that spins for ~400 us on stream A delays a
-// trivial kernel on stream B only if A and B share a queue.
-__global__ void queue_probe_spin_kernel(long long ticks) {      // wall_clock64: constant 100 MHz
-    const long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-}
-__global__ void queue_probe_nop_kernel() {}
-
-// true if a and b are served by the same hardware queue
-bool same_queue(hipStream_t a, hipStream_t b, hipEvent_t ea, hipEvent_t eb0, hipEvent_t eb1) {
-    constexpr long long SPIN_TICKS = 40000;                       // 400 us
-    (void)hipStreamSynchronize(a);
-    (void)hipStreamSynchronize(b);
-    hipLaunchKernelGGL(queue_probe_spin_kernel, dim3(1), dim3(1), 0, a, SPIN_TICKS);
-    (void)hipEventRecord(ea, a);
-    (void)hipEventRecord(eb0, b);
-    hipLaunchKernelGGL(queue_probe_nop_kernel, dim3(1), dim3(1), 0, b);
-    (void)hipEventRecord(eb1, b);
-    // poll (a blocking wait may wake up later than the spin lasts): b's kernel finished -- had a's spin finished by then?  On separate
-    // queues b is done after a few microseconds and the spin is not.
-    bool spin_done = false;
-    for (long polls = 0;; ++polls) {
-        const bool a_done = hipEventQuery(ea) == hipSuccess;
-        if (hipEventQuery(eb1) == hipSuccess) {
-            spin_done = a_done;
-            break;
-        }
-        if (a_done || polls > 20000000L) {              // the spin ended first: b was held up behind it (or the device does not answer: count it as shared)
-            spin_done = true;
-            break;
-        }
-    }
-    (void)hipStreamSynchronize(a);
-    return spin_done;
-}
-// the same measurement, repeated when it says "shared": a co-tenant of the GPU that delays stream b for the length of the spin makes separate
-// queues look shared once; it does not do so three times in a row
-bool same_queue_voted(hipStream_t a, hipStream_t b, hipEvent_t ea, hipEvent_t eb0, hipEvent_t eb1) {
-    for (int i = 0; i < 3; ++i)
-        if (!same_queue(a, b, ea, eb0, eb1)) return false;
-    return true;
-}
-
-// Choose the engine's three branch streams from a pool of fresh streams so that they and `main` sit on four different hardware queues
-// (as far as the device's queue count allows); the rest of the pool is destroyed.
-int pick_streams(ss_engine* e, hipStream_t main) {
-    constexpr int POOL = 10;
-    struct Guard {               // whatever is still in here when the function returns -- early on an error, or at its end -- is destroyed
-        hipStream_t pool[POOL] = {};
-        hipEvent_t ev[3] = {};
-        ~Guard() {
-            for (auto& st : pool)
-                if (st) (void)hipStreamDestroy(st);
-            for (auto& x : ev)
-                if (x) (void)hipEventDestroy(x);
-        }
-    } gd;
-    hipStream_t(&pool)[POOL] = gd.pool;
-    hipEvent_t(&ev)[3] = gd.ev;
-    for (auto& x : ev) HIPCHK(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-    for (auto& st : pool) {
-        HIPCHK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, 0));      // (created with the lowest priority instead: measured 5.78 vs 5.80 ms, not done)
-        hipLaunchKernelGGL(queue_probe_nop_kernel, dim3(1), dim3(1), 0, st);      // first use of a stream sets its queue up: not inside a measurement
-    }
-    hipLaunchKernelGGL(queue_probe_nop_kernel, dim3(1), dim3(1), 0, main);
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<hipStream_t> chosen;
-    char buf[64];
-    e->stream_report.clear();
-    for (int pass = 0; pass < 2 && chosen.size() < 3; ++pass)       // pass 1: accept streams that only differ from the main stream's queue
-        for (int i = 0; i < POOL && chosen.size() < 3; ++i) {
-            if (!pool[i]) continue;
-            bool clash = same_queue_voted(main, pool[i], ev[0], ev[1], ev[2]);
-            for (size_t k = 0; k < chosen.size() && !clash && pass == 0; ++k) clash = same_queue_voted(chosen[k], pool[i], ev[0], ev[1], ev[2]);
-            if (!clash) {
-                std::snprintf(buf, sizeof buf, "%scandidate %d%s", chosen.empty() ? "" : ", ", i, pass ? " (shares a queue with another branch)" : "");
-                e->stream_report += buf;
-                chosen.push_back(pool[i]);
-                pool[i] = nullptr;
-            }
-        }
-    for (int i = 0; i < POOL && chosen.size() < 3; ++i)             // a device with fewer queues than streams: take what is there
-        if (pool[i]) {
-            chosen.push_back(pool[i]);
-            pool[i] = nullptr;
-            e->stream_report += " +fallback";
-        }
-    e->side = chosen[0];
-    e->side2 = chosen[1];
-    e->side3 = chosen[2];
-    e->stream_report = "branch streams on hardware queues of their own: " + e->stream_report;
-    return 0;
-}
 
 // a training step begins: is it one of the bracketed ones (ss_profile_sample)?
 void prof_tick(ss_engine* e) {
@@ -2574,7 +2458,11 @@ int ss_bind(ss_engine* e, float* params, float* grads, float* m, float* v, void*
         if (g_own_streams) HIPCHK(hipStreamCreateWithFlags(&e->main_s, hipStreamNonBlocking));
         if (g_probe_queues) {
             // branch streams chosen by MEASURING which candidates share a hardware queue with the stream the step will be issued on
-            CHK(pick_streams(e, (g_own_streams && e->main_s) ? e->main_s : S(stream)));
+            hipStream_t branch[3];
+            CHK(pick_streams((g_own_streams && e->main_s) ? e->main_s : S(stream), branch, e->stream_report));
+            e->side = branch[0];
+            e->side2 = branch[1];
+            e->side3 = branch[2];
         } else {
             // (the side stream at the lowest priority: measured 2.3x SLOWER, 35 ms vs 14.8 ms per step -- the low-priority queue starves
             // behind 768 tiny step launches)
@@ -2985,223 +2873,6 @@ int ss_g6_train_step(ss_engine* e, const float* mel, const float* f0_onehot, con
     return 0;
 }
 
-int ss_collate(const float* mel_cat, const float* f0_cat, const float* emb_tab, const long* row0, const int* len, const int* item,
-               int B, int T, int n_mel, int emb_dim, float* mel, float* f0, float* emb, void* stream) {
-    if (!mel_cat || !f0_cat || !emb_tab || !row0 || !len || !item || !mel || !f0 || !emb) return fail("ss_collate: null pointer");
-    if (B <= 0 || T <= 0 || n_mel <= 0 || emb_dim <= 0) return fail("ss_collate: bad shape");
-    HIPCHK(collate(mel_cat, f0_cat, emb_tab, row0, len, item, B, T, n_mel, emb_dim, mel, f0, emb, S(stream)));
-    return 0;
-}
-
-int ss_melspec_frames(int n) { return n >= 513 ? (n + 256) / 256 : 0; }
-
-int ss_melspec(const double* wav, int n, const double* mel_basis, int n_mels, float* out, void* stream) {
-    if (!wav || !mel_basis || !out) return fail("ss_melspec: null pointer");
-    if (n < 513) return fail("ss_melspec: at least 513 samples (reflect padding by 512)");
-    HIPCHK(melspec(wav, n, mel_basis, n_mels, out, ss_melspec_frames(n), S(stream)));
-    return 0;
-}
-
-int ss_f0_normalize(const double* f0, int n, float* out, void* stream) {
-    if (!f0 || !out || n < 1) return fail("ss_f0_normalize: bad arguments");
-    HIPCHK(f0_normalize(f0, n, out, S(stream)));
-    return 0;
-}
-
-// ---- pitch tracker (pitch.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
-namespace {
-int pitch_shape(const char* who, int B, int max_n, double lo_hz, double hi_hz, PitchLags* g) {
-    if (B < 1 || B > PITCH_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
-    if (max_n < 513 || max_n > 256 * (SS_MAX_EVAL_FRAMES - 1))
-        return fail(std::string(who) + ": max_n outside 513 .. 256 * (SS_MAX_EVAL_FRAMES - 1)");
-    if (!(lo_hz > 0.0)) return fail(std::string(who) + ": lo_hz is NaN or not positive");
-    if (!(hi_hz > 0.0)) return fail(std::string(who) + ": hi_hz is NaN or not positive");
-    if (!(lo_hz < hi_hz)) return fail(std::string(who) + ": lo_hz is not below hi_hz");
-    if (!(floor(16000.0 / hi_hz) >= PITCH_MIN_LAG)) return fail(std::string(who) + ": hi_hz above 1000 (the shortest lag would be below 16 samples)");
-    if (!(ceil(16000.0 / lo_hz) <= PITCH_MAX_LAG)) return fail(std::string(who) + ": lo_hz below 40 (the longest lag would be above 400 samples)");
-    if (!pitch_lags(lo_hz, hi_hz, g)) return fail(std::string(who) + ": lo_hz .. hi_hz covers fewer than 3 lags");
-    return 0;
-}
-int pitch_scratch_ok(const char* who, int B, int max_n, const PitchLags& g, const void* scratch, long scratch_bytes) {
-    if (!scratch) return fail(std::string(who) + ": null pointer: scratch_dev");
-    if ((uintptr_t)scratch % 256) return fail(std::string(who) + ": scratch_dev is not 256-byte aligned");
-    if (scratch_bytes < pitch_scratch_bytes(B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1))
-        return fail(std::string(who) + ": scratch_bytes below ss_pitch_scratch_bytes(B, max_n, lo_hz, hi_hz)");
-    return 0;
-}
-}  // namespace
-
-long ss_pitch_scratch_bytes(int B, int max_n, double lo_hz, double hi_hz) {
-    PitchLags g;
-    CHK(pitch_shape("ss_pitch_scratch_bytes", B, max_n, lo_hz, hi_hz, &g));
-    return pitch_scratch_bytes(B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1);
-}
-
-int ss_pitch_track(const double* wav, const int* n, int B, int max_n, double scale, double lo_hz, double hi_hz, double* f0, void* scratch,
-                   long scratch_bytes, void* stream) {
-    PitchLags g;
-    if (!wav) return fail("ss_pitch_track: null pointer: wav_dev");
-    if (!f0) return fail("ss_pitch_track: null pointer: f0_dev");
-    CHK(pitch_shape("ss_pitch_track", B, max_n, lo_hz, hi_hz, &g));
-    if (!(scale > 0.0) || std::isinf(scale)) return fail("ss_pitch_track: scale is not finite or not positive");
-    CHK(pitch_scratch_ok("ss_pitch_track", B, max_n, g, scratch, scratch_bytes));
-    const PitchScratch sc = pitch_scratch(scratch, B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1);
-    HIPCHK(pitch_nccf(wav, n, B, max_n, scale, g, sc.phi, sc.rms, S(stream)));
-    HIPCHK(pitch_dp(sc.phi, sc.rms, n, B, max_n, g, f0, sc, S(stream)));
-    return 0;
-}
-
-int ss_op_nccf(const double* wav, const int* n, int B, int max_n, double scale, double lo_hz, double hi_hz, double* phi, double* rms,
-               void* stream) {
-    PitchLags g;
-    if (!wav) return fail("ss_op_nccf: null pointer: wav_dev");
-    if (!phi) return fail("ss_op_nccf: null pointer: phi_dev");
-    if (!rms) return fail("ss_op_nccf: null pointer: rms_dev");
-    CHK(pitch_shape("ss_op_nccf", B, max_n, lo_hz, hi_hz, &g));
-    if (!(scale > 0.0) || std::isinf(scale)) return fail("ss_op_nccf: scale is not finite or not positive");
-    HIPCHK(pitch_nccf(wav, n, B, max_n, scale, g, phi, rms, S(stream)));
-    return 0;
-}
-
-int ss_op_pitch_dp(const double* phi, const double* rms, const int* n, int B, int max_n, double lo_hz, double hi_hz, double* f0,
-                   void* scratch, long scratch_bytes, void* stream) {
-    PitchLags g;
-    if (!phi) return fail("ss_op_pitch_dp: null pointer: phi_dev");
-    if (!rms) return fail("ss_op_pitch_dp: null pointer: rms_dev");
-    if (!f0) return fail("ss_op_pitch_dp: null pointer: f0_dev");
-    CHK(pitch_shape("ss_op_pitch_dp", B, max_n, lo_hz, hi_hz, &g));
-    CHK(pitch_scratch_ok("ss_op_pitch_dp", B, max_n, g, scratch, scratch_bytes));
-    HIPCHK(pitch_dp(phi, rms, n, B, max_n, g, f0, pitch_scratch(scratch, B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1), S(stream)));
-    return 0;
-}
-
-// ---- batched feature extraction (filtfilt.hip, features.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
-namespace {
-int feat_shape(const char* who, int B, int max_n) {
-    if (B < 1 || B > FEAT_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
-    if (max_n < 513 || max_n > 256 * (SS_MAX_EVAL_FRAMES - 1))
-        return fail(std::string(who) + ": max_n outside 513 .. 256 * (SS_MAX_EVAL_FRAMES - 1)");
-    return 0;
-}
-}  // namespace
-
-long ss_filtfilt_scratch_bytes(int B, int max_n) {
-    CHK(feat_shape("ss_filtfilt_scratch_bytes", B, max_n));
-    return filtfilt_scratch_bytes(B, max_n);
-}
-
-int ss_filtfilt(const double* x, const int* n, int B, int max_n, const double* b, const double* a, const double* zi, double gain,
-                const double* dither, double dither_scale, double* y, void* scratch, long scratch_bytes, void* stream) {
-    if (!x) return fail("ss_filtfilt: null pointer: x_dev");
-    if (!b) return fail("ss_filtfilt: null pointer: b");
-    if (!a) return fail("ss_filtfilt: null pointer: a");
-    if (!zi) return fail("ss_filtfilt: null pointer: zi");
-    if (!y) return fail("ss_filtfilt: null pointer: y_dev");
-    CHK(feat_shape("ss_filtfilt", B, max_n));
-    FiltCoef c;
-    for (int i = 0; i < FILT_NCOEF; ++i) {
-        if (!std::isfinite(b[i])) return fail("ss_filtfilt: b[" + std::to_string(i) + "] is not finite");
-        if (!std::isfinite(a[i])) return fail("ss_filtfilt: a[" + std::to_string(i) + "] is not finite");
-        if (i < FILT_NCOEF - 1 && !std::isfinite(zi[i])) return fail("ss_filtfilt: zi[" + std::to_string(i) + "] is not finite");
-        c.b[i] = b[i];
-        c.a[i] = a[i];
-        if (i < FILT_NCOEF - 1) c.zi[i] = zi[i];
-    }
-    if (a[0] != 1.0) return fail("ss_filtfilt: a[0] is not exactly 1 (normalise b and a on the host, as scipy does)");
-    if (!std::isfinite(gain)) return fail("ss_filtfilt: gain is not finite");
-    if (!std::isfinite(dither_scale)) return fail("ss_filtfilt: dither_scale is not finite");
-    if (!scratch) return fail("ss_filtfilt: null pointer: scratch_dev");
-    if ((uintptr_t)scratch % 256) return fail("ss_filtfilt: scratch_dev is not 256-byte aligned");
-    if (scratch_bytes < filtfilt_scratch_bytes(B, max_n)) return fail("ss_filtfilt: scratch_bytes below ss_filtfilt_scratch_bytes(B, max_n)");
-    HIPCHK(filtfilt(x, n, B, max_n, c, gain, dither, dither_scale, y, (double*)scratch, S(stream)));
-    return 0;
-}
-
-int ss_melspec_batch(const double* wav, const int* n, int B, int max_n, const double* mel_basis, int n_mels, float* out, void* stream) {
-    if (!wav) return fail("ss_melspec_batch: null pointer: wav_dev");
-    if (!mel_basis) return fail("ss_melspec_batch: null pointer: mel_basis_dev");
-    if (!out) return fail("ss_melspec_batch: null pointer: out_dev");
-    CHK(feat_shape("ss_melspec_batch", B, max_n));
-    if (n_mels < 1) return fail("ss_melspec_batch: n_mels below 1");
-    HIPCHK(melspec_batch(wav, n, B, max_n, mel_basis, n_mels, out, S(stream)));
-    return 0;
-}
-
-int ss_f0_normalize_batch(const double* f0, const int* n, int B, int max_n, double unvoiced, float* out, void* stream) {
-    if (!f0) return fail("ss_f0_normalize_batch: null pointer: f0_dev");
-    if (!out) return fail("ss_f0_normalize_batch: null pointer: out_dev");
-    CHK(feat_shape("ss_f0_normalize_batch", B, max_n));
-    if (std::isnan(unvoiced)) return fail("ss_f0_normalize_batch: unvoiced is NaN");
-    HIPCHK(f0_normalize_batch(f0, n, B, max_n, unvoiced, out, S(stream)));
-    return 0;
-}
-
-// ---- Griffin-Lim vocoder (vocoder.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
-namespace {
-int voc_shape(const char* who, int B, int max_frames) {
-    if (B < 1 || B > VOC_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
-    if (max_frames < 4 || max_frames > SS_MAX_EVAL_FRAMES)
-        return fail(std::string(who) + ": max_frames outside 4 .. SS_MAX_EVAL_FRAMES (reflect padding needs 4 frames)");
-    return 0;
-}
-int voc_scratch(const char* who, int B, int max_frames, const void* scratch, long scratch_bytes) {
-    if (!scratch) return fail(std::string(who) + ": null pointer: scratch_dev");
-    if ((uintptr_t)scratch % 256) return fail(std::string(who) + ": scratch_dev is not 256-byte aligned");
-    if (scratch_bytes < vocoder_scratch_bytes(B, max_frames))
-        return fail(std::string(who) + ": scratch_bytes below ss_griffinlim_scratch_bytes(B, max_frames)");
-    return 0;
-}
-}  // namespace
-
-int ss_griffinlim_samples(int frames) { return frames >= 4 ? 256 * (frames - 1) : 0; }
-
-long ss_griffinlim_scratch_bytes(int B, int max_frames) {
-    CHK(voc_shape("ss_griffinlim_scratch_bytes", B, max_frames));
-    return vocoder_scratch_bytes(B, max_frames);
-}
-
-int ss_mel_to_linear(const float* mel, const double* inv_basis, const int* frames, int B, int max_frames, int n_mels, double floor,
-                     double* mag, void* stream) {
-    if (!mel) return fail("ss_mel_to_linear: null pointer: mel_dev");
-    if (!inv_basis) return fail("ss_mel_to_linear: null pointer: inv_basis_dev");
-    if (!mag) return fail("ss_mel_to_linear: null pointer: mag_dev");
-    CHK(voc_shape("ss_mel_to_linear", B, max_frames));
-    if (n_mels < 1 || n_mels > VOC_MAX_MELS) return fail("ss_mel_to_linear: n_mels outside 1 .. 4096");
-    if (!(floor >= 0.0)) return fail("ss_mel_to_linear: floor is negative or NaN");
-    HIPCHK(mel_to_linear(mel, inv_basis, frames, B, max_frames, n_mels, floor, mag, S(stream)));
-    return 0;
-}
-
-int ss_griffinlim(const double* mag, const double* phase0, const int* frames, int B, int max_frames, int n_iter, double momentum,
-                  double* wav, void* scratch, long scratch_bytes, void* stream) {
-    if (!mag) return fail("ss_griffinlim: null pointer: mag_dev");
-    if (!wav) return fail("ss_griffinlim: null pointer: wav_dev");
-    CHK(voc_shape("ss_griffinlim", B, max_frames));
-    if (n_iter < 0 || n_iter > 1024) return fail("ss_griffinlim: n_iter outside 0 .. 1024");
-    if (!(momentum >= 0.0 && momentum < 1.0)) return fail("ss_griffinlim: momentum outside [0, 1) or NaN");
-    CHK(voc_scratch("ss_griffinlim", B, max_frames, scratch, scratch_bytes));
-    HIPCHK(griffinlim(mag, phase0, frames, B, max_frames, n_iter, momentum, wav, vocoder_scratch(scratch, B, max_frames), S(stream)));
-    return 0;
-}
-
-int ss_op_stft(const double* wav, const int* frames, int B, int max_frames, double* spec, void* stream) {
-    if (!wav) return fail("ss_op_stft: null pointer: wav_dev");
-    if (!spec) return fail("ss_op_stft: null pointer: spec_dev");
-    CHK(voc_shape("ss_op_stft", B, max_frames));
-    HIPCHK(stft(wav, frames, B, max_frames, spec, S(stream)));
-    return 0;
-}
-
-int ss_op_istft(const double* spec, const int* frames, int B, int max_frames, double* wav, void* scratch, long scratch_bytes,
-                void* stream) {
-    if (!spec) return fail("ss_op_istft: null pointer: spec_dev");
-    if (!wav) return fail("ss_op_istft: null pointer: wav_dev");
-    CHK(voc_shape("ss_op_istft", B, max_frames));
-    CHK(voc_scratch("ss_op_istft", B, max_frames, scratch, scratch_bytes));
-    HIPCHK(istft(spec, frames, B, max_frames, wav, vocoder_scratch(scratch, B, max_frames).frame_buf, S(stream)));
-    return 0;
-}
-
 int ss_interp_forward(ss_engine* e, const float* x, const int* len_seq, const float* scales, const int* len_seg, int B, int T,
                       int C, float* y, int* i0, float* lam, int* counts, void* stream) {
     Own own(e, stream);
@@ -3230,88 +2901,6 @@ int ss_interp_backward(ss_engine* e, const float* dy, int B, int T, int C, float
     pl.T = T;
     const int P = pl.P;
     HIPCHK(interp_scatter(pl, CRows::dense(dy, C, P), Rows::dense(dx, C, T), C, B, s));
-    return 0;
-}
-
-int ss_op_gemm(const float* a, long lda, const float* b, long ldb, float* c, long ldc, const float* bias, int M, int N, int K,
-               int flags, int ksplit, void* stream) {
-    GemmDesc d{};
-    d.A = {a, lda, 0, 0, 0};
-    d.B = {b, ldb, 0, 0, 0};
-    d.C = c;
-    d.ldc = ldc;
-    d.bias = bias;
-    d.M = M;
-    d.N = N;
-    d.K = K;
-    d.batch = 1;
-    d.ksplit = ksplit < 1 ? 1 : ksplit;
-    d.flags = (flags & 1 ? GEMM_TA : 0) | (flags & 2 ? GEMM_TB : 0) | (flags & 8 ? GEMM_BF16 : 0) | (flags & 16 ? GEMM_F16X2 : 0) | (d.ksplit > 1 ? GEMM_ACCUM : 0);
-    HIPCHK(launch_gemm(d, S(stream)));
-    return 0;
-}
-
-int ss_op_gemm_pre(const float* a, long lda, const float* a_img, const float* b, long ldb, const float* b_img, float* c, long ldc, float* part, int M,
-                   int N, int K, int flags, int ksplit, void* stream) {
-    if (!a || !b || !c) return fail("ss_op_gemm_pre: null pointer");
-    GemmDesc d{};
-    d.A = {a, lda, 0, 0, 0};
-    d.B = {b, ldb, 0, 0, 0};
-    d.a_pre = a_img;
-    d.b_pre = b_img;
-    d.C = c;
-    d.ldc = ldc;
-    d.M = M;
-    d.N = N;
-    d.K = K;
-    d.batch = 1;
-    d.ksplit = ksplit < 1 ? 1 : ksplit;
-    d.part = part;
-    d.want = 1;           // the largest tile the shape admits, whatever the number of workgroups: the form under test
-    d.flags = (flags & 1 ? GEMM_TA : 0) | (flags & 2 ? GEMM_TB : 0) | GEMM_F16X2 | (d.ksplit > 1 ? GEMM_ACCUM : 0);
-    HIPCHK(launch_gemm(d, S(stream)));
-    return 0;
-}
-
-int ss_op_split_image(const float* src, long ld, long rows, int cols, float scale, float* img, long ldi, void* stream) {
-    if (!src || !img) return fail("ss_op_split_image: null pointer");
-    HIPCHK(split_image(src, ld, rows, cols, nullptr, scale, img, ldi, nullptr, S(stream)));
-    return 0;
-}
-
-int ss_op_gemm_img(const float* a_img, long lda, const float* b_img, long ldb, float* c, long ldc, const float* bias, int M, int N, int K, int flags,
-                   int ksplit, int cfg, float scale_a, float scale_b, int a_seglen, long a_segstride, float* part, const void* zeros, void* stream) {
-    static float* sc = nullptr;           // the two scales as device words (test hook: one call at a time)
-    if (!sc) HIPCHK(hipMalloc((void**)&sc, 256));
-    const float h[2] = {scale_a, scale_b};
-    HIPCHK(hipMemcpyAsync(sc, h, sizeof(h), hipMemcpyHostToDevice, S(stream)));
-    ImgGemmDesc d{};
-    d.A = {a_img, lda, 0, a_seglen, a_segstride};
-    d.B = {b_img, ldb, 0, 0, 0};
-    d.C = c;
-    d.ldc = ldc;
-    d.bias = bias;
-    d.M = M;
-    d.N = N;
-    d.K = K;
-    d.batch = 1;
-    d.ksplit = ksplit < 1 ? 1 : ksplit;
-    d.flags = (flags & 1 ? GEMM_TA : 0) | (flags & 2 ? GEMM_TB : 0) | (flags & 4 ? GEMM_ACCUM : 0);
-    d.bf16 = (flags & 8) ? 1 : 0;           // single-piece form: the operands are plain bf16 matrices, ld in elements
-    d.part = part;
-    d.scale_a = d.bf16 ? nullptr : sc;
-    d.scale_b = d.bf16 ? nullptr : sc + 1;
-    d.zeros = zeros;
-    d.cfg = cfg;
-    d.diag = g_gemm_diag;
-    if (g_img_xcc) {                      // test hook for the work-queue form: ss_tune("img_xcc", mask of allowed XCDs; 255 = queue without a filter)
-        if (!g_img_wq) HIPCHK(hipMalloc((void**)&g_img_wq, IMG_WQ_BYTES));
-        HIPCHK(hipMemsetAsync(g_img_wq, 0, (g_img_xcc & 0x100) ? IMG_WQ_BYTES : 8, S(stream)));
-        d.wq = g_img_wq;
-        d.xcc_allow = (unsigned)g_img_xcc;
-    }
-    if (!gemm_img_supported(d)) return fail("ss_op_gemm_img: shape / alignment not supported by the image GEMM");
-    HIPCHK(launch_gemm_img(d, S(stream)));
     return 0;
 }
 
@@ -3375,182 +2964,6 @@ int ss_profile_timeline(ss_engine* e, double* out, int cap) {
         out[3 * i + 2] = b * 1e3;
     }
     return n;
-}
-
-// Where do the workgroups of a launch go?  n_wg workgroups of `threads` threads and lds_bytes of LDS each record (XCC_ID register, HW_ID
-// register) in launch order; each then idles `hold_ticks` (100 MHz) so that the whole grid has to be resident at once.
-__global__ void xcc_map_kernel(unsigned* out, long long hold_ticks) {
-    extern __shared__ unsigned char xcc_map_lds[];
-    if (threadIdx.x == 0) {
-        unsigned x, h;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(h));
-        out[2 * blockIdx.x] = x;
-        out[2 * blockIdx.x + 1] = h;
-        xcc_map_lds[0] = (unsigned char)x;
-    }
-    const long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < hold_ticks) __builtin_amdgcn_s_sleep(8);
-}
-int ss_debug_xcc_map(int n_wg, int threads, int lds_bytes, int hold_us, unsigned* out_dev, void* stream) {
-    if (!out_dev || n_wg < 1 || threads < 64 || threads > 1024 || lds_bytes < 0 || lds_bytes > 160 * 1024 || hold_us < 0 || hold_us > 2000)
-        return fail("ss_debug_xcc_map: bad arguments");
-    if (lds_bytes > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)xcc_map_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    hipLaunchKernelGGL(xcc_map_kernel, dim3(n_wg), dim3(threads), lds_bytes, S(stream), out_dev, (long long)hold_us * 100);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-int ss_debug_img_wq(unsigned* out_host, int words) {
-    if (!out_host || words < 1 || words * 4L > IMG_WQ_BYTES || !g_img_wq) return fail("ss_debug_img_wq: nothing logged / bad size");
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out_host, g_img_wq, words * 4L, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int ss_debug_gemm_phases(unsigned long long* out24, int reset) {
-    if (!out24) return fail("ss_debug_gemm_phases: null pointer");
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(gemm_phase_probe(out24, reset != 0));
-    return 0;
-}
-
-int ss_tune(const char* key, int value) {
-    struct Key {
-        const char* name;
-        int* target;
-        int lo, hi;      // accepted values: lo <= value <= hi
-    };
-    constexpr int MAXV = 0x7fffffff;
-    static const Key keys[] = {
-        {"lstm_nw", &g_lstm_nw, 4, 16},      // 4, 8 or 16 (checked below)
-        {"lstm_g", &g_lstm_g, 0, 16},
-#ifdef SS_DIAG
-        {"lstm_mode", &g_lstm_mode, 0, 4},
-        {"gemm_diag", &g_gemm_diag, 0, 2047},
-        {"seq_prio", &g_seq_prio, 0, 65535},
-#else
-        {"seq_prio", &g_seq_prio, 0, 1},
-#endif
-        {"seq_tag", &g_seq_tag, 0, 1},
-        {"op_time_major", &g_op_time_major, 0, 1},
-        {"seq_var", &g_seq_var, 0, 15},
-        {"compact0", &g_compact0, 0, 1},
-        {"bf16_img", &g_bf16_img, 0, 1},
-        {"dp_model", &g_dp_model, 0, 64},
-        {"dp_buckets", &g_dp_buckets, 0, 1},
-        {"gemm_ws", &g_gemm_ws, 0, 2},
-        {"gemm_pipe", &g_gemm_pipe, 0, 1},
-        {"seq_spin_log2", &g_seq_spin_log2, 0, 24},
-        {"overlap", &g_overlap, 0, 1},
-        {"defer_dw", &g_defer_dw, 0, 1},
-        {"dx_batched", &g_dx_batched, 0, 2},
-        {"small_lds", &g_small_lds, 0, 2},
-        {"gemm_tr", &g_gemm_tr, 0, 2},
-        {"own_streams", &g_own_streams, 0, 1},
-        {"conv_dw_off", &g_conv_dw_off, 0, 3},
-        {"dec_tail_split", &g_dec_tail_split, 0, 10},
-        {"early_dw", &g_early_dw, 0, 1},
-        {"xcd_dw", &g_xcd_dw, 0, 1},
-        {"dp_emulate", &g_dp_emulate, 0, 1},
-        {"gn_gather", &g_gn_gather, 0, 1},
-        {"img_xcc", &g_img_xcc, 0, 511},      // bit 8: keep a placement log (ss_debug_img_wq)
-        {"probe_queues", &g_probe_queues, 0, 1},
-        {"prio_order", &g_prio_order, 0, 1},
-        {"deterministic", &g_deterministic, 0, 1},
-        {"persist", &g_persist, 0, 1},
-        {"gemm_want", &g_gemm_want, 1, MAXV},
-        {"gemm_mode", &g_gemm_mode, 0, 1},
-        {"fwd_f16x2", &g_fwd_f16x2, 0, 1},
-        {"bwd_f16x2", &g_bwd_f16x2, 0, 1},
-    };
-    const std::string k = key ? key : "";
-    for (const Key& t : keys) {
-        if (k != t.name) continue;
-        if (value < t.lo || value > t.hi || (t.target == &g_lstm_nw && value != 4 && value != 8 && value != 16)) break;
-        *t.target = value;
-        return 0;
-    }
-    return fail("ss_tune: unknown key or bad value: " + k
-#ifndef SS_DIAG
-                     + " (the wrong-result timing modes lstm_mode / gemm_diag / seq_prio > 1 exist only in the -DSS_DIAG build: make diag)"
-#endif
-    );
-}
-
-static int op_lstm_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch,
-                       long scratch_floats, const int* len, int B, int T, int H, void* stream) {
-    hipStream_t s = S(stream);
-    if (H > 32) {
-        const long half = 2L * (((B + 15) / 16) * 16) * H, wn = 2L * 4 * H * H;
-        if (!scratch || scratch_floats < wn + 2 * half) return fail("ss_op_lstm_fwd: scratch too small");
-        float* hf = scratch + wn;
-        if (g_persist && lstm_seq_supported(B, H) && wn * 4 >= lstm_seq_xbytes(B, H, false)) {
-            // exchange buffer in the (unused) packed-weight area, counters behind it
-            HIPCHK(lstm_seq_fwd(gates, whh_f, whh_b, scratch, out, csave, (unsigned*)hf, B, T, H, s, {.time_major = g_op_time_major != 0, .len = len}));
-            return 0;
-        }
-        HIPCHK(lstm_pack_w(whh_f, whh_b, scratch, H, 0, s));
-        HIPCHK(hipMemsetAsync(hf, 0, 2 * half * 4, s));
-        for (int st = 0; st < T; ++st)
-            HIPCHK(lstm_step_fwd(gates, scratch, hf + (st & 1) * half, hf + ((st & 1) ^ 1) * half, out, csave, B, T, H, st, s, len));
-    } else {
-        HIPCHK(lstm_small_fwd(gates, whh_f, whh_b, out, csave, B, T, H, s, len));
-    }
-    return 0;
-}
-
-int ss_op_lstm_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch,
-                   long scratch_floats, int B, int T, int H, void* stream) {
-    return op_lstm_fwd(gates, whh_f, whh_b, out, csave, scratch, scratch_floats, nullptr, B, T, H, stream);
-}
-
-int ss_op_lstm_fwd_ragged(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch,
-                          long scratch_floats, const int* len_dev, int B, int T, int H, void* stream) {
-    if (!gates || !whh_f || !whh_b || !out || !csave || B < 1 || T < 1) return fail("ss_op_lstm_fwd_ragged: null pointer or empty shape");
-    return op_lstm_fwd(gates, whh_f, whh_b, out, csave, scratch, scratch_floats, len_dev, B, T, H, stream);
-}
-
-int ss_op_lstm_bwd(float* gates, const float* whh_f, const float* whh_b, const float* d_out, const float* csave,
-                   float* scratch, long scratch_floats, int B, int T, int H, void* stream) {
-    hipStream_t s = S(stream);
-    if (H > 32) {
-        const long half = 2L * (((B + 15) / 16) * 16) * 4 * H, wn = 2L * 4 * H * H;
-        if (!scratch || scratch_floats < wn + 2 * half + 2L * B * H) return fail("ss_op_lstm_bwd: scratch too small");
-        float* gf = scratch + wn;
-        float* dc = gf + 2 * half;
-        const long xbytes = lstm_seq_xbytes(B, H, true);
-        if (g_persist && lstm_seq_supported(B, H) && scratch_floats * 4 >= xbytes + 4L * LSTM_SEQ_SYNC_WORDS) {     // [exchange tiles][flags]
-            HIPCHK(lstm_seq_bwd(gates, whh_f, whh_b, scratch, d_out, csave, (unsigned*)((char*)scratch + xbytes), B, T, H, s,
-                                {.time_major = g_op_time_major != 0}));
-            return 0;
-        }
-        HIPCHK(lstm_pack_w(whh_f, whh_b, scratch, H, 1, s));
-        HIPCHK(hipMemsetAsync(gf, 0, 2 * half * 4, s));
-        for (int st = 0; st < T; ++st)
-            HIPCHK(lstm_step_bwd(gates, scratch, gf + (st & 1) * half, gf + ((st & 1) ^ 1) * half, d_out, csave, dc, B, T, H, st, s));
-    } else {
-        HIPCHK(lstm_small_bwd(gates, whh_f, whh_b, d_out, csave, B, T, H, s));
-    }
-    return 0;
-}
-
-int ss_op_lstm_wgrad(const float* dg, const float* x, long x_ld, const float* hout, float* gwih, float* gwhh, float* gb, float* scratch, long scratch_floats,
-                     long R, int H, int In, void* stream) {
-    if (H < 1 || H > 32 || In < 1 || R < 1) return fail("ss_op_lstm_wgrad: H in 1..32, In >= 1");
-    WgradTable w{};
-    w.n = 1;
-    w.tiles_total = lstm_small_wgrad_tiles(H, In);
-    w.row_groups = 16;
-    const long need = (long)w.tiles_total * w.row_groups * 4096, ctr_floats = (w.tiles_total + 63) & ~63L;
-    if (!scratch || scratch_floats < need + ctr_floats) return fail("ss_op_lstm_wgrad: scratch too small");
-    w.part = scratch;
-    w.ctr = (unsigned*)(scratch + need);
-    HIPCHK(hipMemsetAsync(w.ctr, 0, ctr_floats * 4, S(stream)));
-    // gwih [2][4H][In], gwhh [2][4H][H], gb [2][2][4H] (b_ih then b_hh per direction): accumulated into, as the engine's gradient arena is
-    w.t[0] = WgradTask{dg, x, x_ld, hout, gwih, gwih + 4L * H * In, gwhh, gwhh + 4L * H * H, gb, gb + 4L * H, gb + 8L * H, gb + 12L * H, H, In, R, 0, 2 * H};
-    HIPCHK(lstm_small_wgrad(w, S(stream)));
-    return 0;
 }
 
 int ss_check(ss_engine* e, void* stream) {

@@ -5,6 +5,8 @@
 // the k=5 "same" convolution its zero padding, give the LSTM recurrences h(-1) = c(-1) = 0 without a branch, and
 // let every weight-gradient contraction run as ONE GEMM over the flat row index b*TP + row.
 #pragma once
+#include <string>
+
 #include "common.h"
 
 namespace ss {
@@ -433,5 +435,10 @@ hipError_t conv_pack_dx(const float* w, int Co, int Ci, float* wb, hipStream_t s
 // the gradient of a per-utterance input row that a BLSTM layer sees at every frame (the decoder's speaker columns).  Fixed-order fp32 sums.
 hipError_t spk_grad(const float* dg, long ld, long b_stride, int rows, const float* w_f, const float* w_r, long w_ld, int col0, int H4, int E,
                     float* out, int B, hipStream_t s);
+
+// ---------------------------------------------------------------- queue_probe.hip (ss_bind)
+// three fresh streams that, as far as the device's queue count allows, share no hardware queue with `main` or each other; `report` says
+// which candidates were taken.  0, or -1 with ss_last_error() set.
+int pick_streams(hipStream_t main, hipStream_t branch[3], std::string& report);
 
 }  // namespace ss
