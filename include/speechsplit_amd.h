@@ -398,6 +398,30 @@ int  ss_melspec_batch(const double* wav_dev, const int* n_dev, int B, int max_n,
                       float* out_dev, void* stream);
 int  ss_f0_normalize_batch(const double* f0_dev, const int* n_dev, int B, int max_n, double unvoiced, float* out_dev, void* stream);
 
+/* ss_resample: recordings of any sample rate to the chain's 16 kHz (or back) -- scipy.signal.resample_poly(x, up, down) with a CALLER-SUPPLIED
+ * filter, on ragged batches.  The ragged-batch rules are the ones above, with 1 in place of 513: row b has n_b = min(max(n[b], 1), max_n)
+ * input samples and m_b = ceil(n_b up / down) output samples; M = ceil(max_n up / down) = ss_resample_len(max_n, up, down) columns are
+ * written; a length outside 1 .. max_n spoils that row only; row b is, bit for bit, the result of running that recording alone.
+ * x: float64 [B][max_n]; y: float64 [B][M]; h: float64 [n_taps] ON THE DEVICE, n_taps odd, half = (n_taps - 1) / 2.  h is an input, as
+ * mel_basis and b, a, zi are: the Python layer passes scipy's own design for the reduced up / down,
+ *     h = scipy.signal.firwin(20 max(up, down) + 1, 1 / max(up, down), window=('kaiser', 5.0)) * up.
+ * The result is DEFINED as this sequence of IEEE double operations -- every product and every sum rounded to double on its own, no fused
+ * multiply-add -- and equals resample_poly's to the bit (summing the same taps in descending order already differs in the last place):
+ *     y[b][m] = 0.0 + sum over k of x[b][k] * h[m*down + half - k*up],   0 <= m < m_b,
+ * the sum over exactly those k with 0 <= k < n_b and 0 <= m*down + half - k*up < n_taps, k ascending: acc = 0.0; then acc = acc + x[b][k] * h[..]
+ * for each such k in turn.  An output no tap reaches is 0.0.  Exact zeros are written in columns m_b .. M - 1.  x[b][k] for k >= n_b is never
+ * read and may hold NaN: the range of k is a bound of the loop, not a zero tap multiplied in (NaN * 0 is NaN).  All index arithmetic is
+ * in long.  No atomics, nothing crosses rows or outputs: the same bits on every run.  No engine needed, no allocation inside, asynchronous on
+ * `stream`.  scratch: ss_resample_scratch_bytes(up, n_taps) bytes, 256-byte aligned; that is 0 today (the kernel reads h as it is given), and
+ * scratch_dev may then be NULL.
+ * Refused before anything is enqueued, with a message that names the argument: null x_dev / h_dev / y_dev, B outside 1 .. 65535, max_n < 1,
+ * up or down outside 1 .. 1024, n_taps < 1 or even, max_n whose M does not fit an int (the 16 kHz chain behind it takes an int max_n),
+ * scratch_bytes below ss_resample_scratch_bytes(up, n_taps), scratch_dev NULL while bytes are needed or not 256-byte aligned. */
+long ss_resample_len(long n, int up, int down);              /* host only: ceil(n * up / down); -1 + ss_last_error on bad arguments (n outside 0 .. 2^40) */
+long ss_resample_scratch_bytes(int up, int n_taps);          /* host only; may be 0; -1 + ss_last_error on bad arguments */
+int  ss_resample(const double* x_dev, const int* n_dev, int B, int max_n, int up, int down, const double* h_dev, int n_taps,
+                 double* y_dev, void* scratch_dev, long scratch_bytes, void* stream);
+
 /* ---- Griffin-Lim vocoder: mel spectrograms back to waveforms (the checkpoint-free stand-in for demo.ipynb's WaveNet cell) ----
  * The inverse of ss_melspec's chain: mel [0, 1] -> amplitude 10^((100 mel - 100 + 16) / 20) -> linear magnitude through a CALLER-SUPPLIED
  * float64 inv_basis [n_mels][513] (the Python layer passes numpy.linalg.pinv of the [513][n_mels] basis), floored at `floor` >= 0 ->

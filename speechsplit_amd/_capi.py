@@ -95,6 +95,9 @@ SYMBOLS = {
     'ss_filtfilt': (_i, [_vp, _ip, _i, _i, _vp, _vp, _vp, _d, _vp, _d, _vp, _vp, _l, _vp]),
     'ss_melspec_batch': (_i, [_vp, _ip, _i, _i, _vp, _i, _fp, _vp]),
     'ss_f0_normalize_batch': (_i, [_vp, _ip, _i, _i, _d, _fp, _vp]),
+    'ss_resample_len': (_l, [_l, _i, _i]),
+    'ss_resample_scratch_bytes': (_l, [_i, _i]),
+    'ss_resample': (_i, [_vp, _ip, _i, _i, _i, _i, _vp, _i, _vp, _vp, _l, _vp]),
     'ss_griffinlim_samples': (_i, [_i]),
     'ss_griffinlim_scratch_bytes': (_l, [_i, _i]),
     'ss_mel_to_linear': (_i, [_fp, _vp, _ip, _i, _i, _i, _d, _vp, _vp]),

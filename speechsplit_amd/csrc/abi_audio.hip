@@ -1,5 +1,5 @@
 // C entry points of the audio / data front end (include/speechsplit_amd.h): collation, mel spectrograms, F0 normalisation, the pitch
-// tracker, batched feature extraction and the Griffin-Lim vocoder.  None of them takes an engine: each checks its arguments, refuses by
+// tracker, batched feature extraction, the resampler and the Griffin-Lim vocoder.  None of them takes an engine: each checks its arguments, refuses by
 // the argument's name through ss_last_error() and hands the rest to the launchers of kernels.h.
 #include <cmath>
 #include <cstdint>
@@ -161,6 +161,51 @@ int ss_f0_normalize_batch(const double* f0, const int* n, int B, int max_n, doub
     CHK(feat_shape("ss_f0_normalize_batch", B, max_n));
     if (std::isnan(unvoiced)) return fail("ss_f0_normalize_batch: unvoiced is NaN");
     HIPCHK(f0_normalize_batch(f0, n, B, max_n, unvoiced, out, S(stream)));
+    return 0;
+}
+
+// ---- rational-rate resampler (resample.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+namespace {
+int resample_rates(const char* who, int up, int down) {
+    if (up < 1 || up > RESAMPLE_MAX_RATE) return fail(std::string(who) + ": up outside 1 .. 1024");
+    if (down < 1 || down > RESAMPLE_MAX_RATE) return fail(std::string(who) + ": down outside 1 .. 1024");
+    return 0;
+}
+int resample_taps(const char* who, int n_taps) {
+    if (n_taps < 1) return fail(std::string(who) + ": n_taps below 1");
+    if (n_taps % 2 == 0) return fail(std::string(who) + ": n_taps is even (the filter needs a centre tap)");
+    return 0;
+}
+}  // namespace
+
+long ss_resample_len(long n, int up, int down) {
+    if (n < 0 || n > (1L << 40)) return fail("ss_resample_len: n outside 0 .. 2^40");
+    CHK(resample_rates("ss_resample_len", up, down));
+    return resample_len(n, up, down);
+}
+
+long ss_resample_scratch_bytes(int up, int n_taps) {
+    if (up < 1 || up > RESAMPLE_MAX_RATE) return fail("ss_resample_scratch_bytes: up outside 1 .. 1024");
+    CHK(resample_taps("ss_resample_scratch_bytes", n_taps));
+    return resample_scratch_bytes(up, n_taps);
+}
+
+int ss_resample(const double* x, const int* n, int B, int max_n, int up, int down, const double* h, int n_taps, double* y, void* scratch,
+                long scratch_bytes, void* stream) {
+    if (!x) return fail("ss_resample: null pointer: x_dev");
+    if (!h) return fail("ss_resample: null pointer: h_dev");
+    if (!y) return fail("ss_resample: null pointer: y_dev");
+    if (B < 1 || B > FEAT_MAX_ROWS) return fail("ss_resample: B outside 1 .. 65535");
+    if (max_n < 1) return fail("ss_resample: max_n below 1");
+    CHK(resample_rates("ss_resample", up, down));
+    CHK(resample_taps("ss_resample", n_taps));
+    if (resample_len(max_n, up, down) > 2147483647L)
+        return fail("ss_resample: max_n: M = ceil(max_n up / down) does not fit an int (the 16 kHz chain behind it takes an int max_n)");
+    const long need = resample_scratch_bytes(up, n_taps);
+    if (scratch_bytes < need) return fail("ss_resample: scratch_bytes below ss_resample_scratch_bytes(up, n_taps)");
+    if (need > 0 && !scratch) return fail("ss_resample: null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail("ss_resample: scratch_dev is not 256-byte aligned");
+    HIPCHK(resample(x, n, B, max_n, up, down, h, n_taps, y, S(stream)));
     return 0;
 }
 

@@ -261,6 +261,15 @@ long filtfilt_scratch_bytes(int B, int max_n);
 hipError_t filtfilt(const double* x, const int* n, int B, int max_n, const FiltCoef& c, double gain, const double* dither,
                     double dither_scale, double* y, double* scratch, hipStream_t s);
 
+// ---------------------------------------------------------------- resample.hip  (scipy.signal.resample_poly to the bit, float64)
+// x [B][max_n], h [n_taps] (device; n_taps odd), y [B][M], M = resample_len(max_n, up, down).  n (nullable; device i32[B]): row b has
+// n_b = min(max(n[b], 1), max_n) samples and m_b = resample_len(n_b, up, down) outputs; y[b][m] = 0.0 + sum_k x[b][k] h[m down + half - k up]
+// over the k in [0, n_b) whose tap exists, k ascending; zeros in columns m_b .. M - 1; x at or beyond n_b is never read.
+constexpr int RESAMPLE_MAX_RATE = 1024;
+long resample_len(long n, int up, int down);                 // ceil(n up / down)
+long resample_scratch_bytes(int up, int n_taps);             // 0: the kernel reads h as it is given
+hipError_t resample(const double* x, const int* n, int B, int max_n, int up, int down, const double* h, int n_taps, double* y, hipStream_t s);
+
 // ---------------------------------------------------------------- vocoder.hip  (Griffin-Lim: mel -> linear magnitude -> waveform, float64)
 // Shapes: mel [B][max_frames][n_mels] f32, mag [B][max_frames][513], spec [B][max_frames][513][2] (re, im), wav [B][256 (max_frames - 1)].
 // frames (nullable; device i32[B]): row b has F_b = min(max(frames[b], 4), max_frames) frames and 256 (F_b - 1) samples; it is computed as if

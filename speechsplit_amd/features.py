@@ -10,6 +10,11 @@ run as ragged batches through ss_filtfilt (csrc/filtfilt.hip: scipy's filtfilt t
 vocoder's FFT in place of the direct DFT), ss_pitch_track and ss_f0_normalize_batch; one copy per batch brings the results back.  Its F0 is
 `extract`'s to the bit and its spectrogram within 1e-6.
 
+Sample rates.  The chain runs at 16 kHz, as the reference asserts (make_spect_f0.py:51).  Recordings at any other rate are brought there
+first by `resample` / `resample_dev` (csrc/resample.hip: scipy.signal.resample_poly with scipy's default filter, to the bit, on ragged
+batches): `extract(..., sr=)`, `extract_batch_sr` and `make_spect_f0(..., resample=True)`, which reads files with `read_audio`.  The defaults
+are the 16 kHz path unchanged; `read_wav` still refuses every other rate by name.
+
 Two parts of the reference come from libraries that are absent here, and both are restated from the published algorithm instead:
   * the mel filter bank (`librosa.filters.mel`, make_spect_f0.py:15): `mel_filter_bank`, Slaney's Auditory-Toolbox mel scale and area
     normalisation with librosa's defaults.  Parity against librosa itself is UNPINNED (nothing of the reference's could be run to produce a
@@ -23,6 +28,7 @@ Two parts of the reference come from libraries that are absent here, and both ar
 The spectrogram half is pinned by tests/golden/features.npz, generated from the reference's own `butter_highpass` / `pySTFT` /
 `speaker_normalization`."""
 import ctypes as C
+import math
 import os
 import pickle
 import wave
@@ -190,6 +196,81 @@ def f0_normalize_batch_dev(f0_dev, n_dev, max_n, unvoiced=0.0):
     return out
 
 
+def rate_ratio(sr_in, sr_out=16000):
+    """(up, down) of a conversion from sr_in to sr_out Hz, reduced as scipy.signal.resample_poly reduces them"""
+    if int(sr_in) != sr_in or int(sr_out) != sr_out or sr_in < 1 or sr_out < 1:
+        raise ValueError(f'rate_ratio: sample rates must be positive integers, not {sr_in!r} -> {sr_out!r}')
+    g = math.gcd(int(sr_in), int(sr_out))
+    up, down = int(sr_out) // g, int(sr_in) // g
+    if up > 1024 or down > 1024:
+        raise ValueError(f'rate_ratio: {sr_in} -> {sr_out} Hz reduces to {up}/{down}; both must be at most 1024')
+    return up, down
+
+
+def resample_filter(up, down):
+    """The FIR scipy.signal.resample_poly designs by default for the reduced up / down: a Kaiser-5.0 windowed sinc of 20 max(up, down) + 1
+    taps with its cutoff at the lower of the two Nyquist rates, scaled by up.  float64 [n_taps]; ss_resample takes it as an input."""
+    top = max(up, down)
+    return signal.firwin(20 * top + 1, 1.0 / top, window=('kaiser', 5.0)) * up
+
+
+def resample_len(n, up, down):
+    """ss_resample_len: the output samples of n input samples, ceil(n up / down)"""
+    return -(-int(n) * up // down)
+
+
+def resample_dev(x_dev, n_dev, up, down, h_dev):
+    """The C call on device tensors: x float64 [B, max_n], n int32 [B] or None, h float64 [n_taps] -> float64 [B, ceil(max_n up / down)]:
+    scipy.signal.resample_poly(row, up, down, window=h / up) on each row's own samples, bit for bit, zeros behind its own outputs."""
+    lib = _capi.lib()
+    B, max_n = x_dev.shape
+    M = lib.ss_resample_len(max_n, up, down)
+    nbytes = lib.ss_resample_scratch_bytes(up, h_dev.numel())
+    if M < 0 or nbytes < 0:
+        _capi.check(-1)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=x_dev.device)
+    y = torch.empty(B, M, dtype=torch.float64, device=x_dev.device)
+    _capi.check(lib.ss_resample(C.c_void_p(x_dev.data_ptr()), C.c_void_p(n_dev.data_ptr()) if n_dev is not None else None, B, max_n, up, down,
+                                C.c_void_p(h_dev.data_ptr()), h_dev.numel(), C.c_void_p(y.data_ptr()),
+                                C.c_void_p(scratch.data_ptr()) if nbytes else None, nbytes,
+                                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return y
+
+
+def _resample_group(xs, up, down, max_rows, device):
+    """recordings of one rate (float64 [n] each) through resample_dev as ragged batches in plan_batches order -> one device tensor
+    [ceil(n up / down)] a recording, in input order.  Nothing is brought back and nothing waits for the device."""
+    h = torch.from_numpy(resample_filter(up, down)).to(device)
+    out = [None] * len(xs)
+    for batch in plan_batches([x.shape[0] for x in xs], max_rows):
+        lens = [xs[i].shape[0] for i in batch]
+        rows = np.zeros((len(batch), lens[-1]))
+        for r, i in enumerate(batch):
+            rows[r, :lens[r]] = xs[i]
+        y = resample_dev(torch.from_numpy(rows).to(device), torch.tensor(lens, dtype=torch.int32, device=device), up, down, h)
+        for r, i in enumerate(batch):
+            out[i] = y[r, :resample_len(lens[r], up, down)]
+    return out
+
+
+def resample(xs, sr_in, sr_out=16000, max_rows=16, device='cuda'):
+    """scipy.signal.resample_poly(x, sr_out, sr_in) on the GPU (csrc/resample.hip), to the bit.  One float64 waveform [n] (or a list of
+    them, any lengths >= 1) at sr_in Hz -> float64 numpy [ceil(n sr_out / sr_in)] in input order.  The recordings run as ragged batches of at
+    most max_rows rows in convert.plan_batches order; every row is the result of running it alone, so the result does not depend on max_rows.
+    sr_in == sr_out returns copies, as scipy does."""
+    single = not isinstance(xs, (list, tuple))
+    ws = [np.ascontiguousarray(x, dtype=np.float64) for x in ([xs] if single else xs)]
+    for i, w in enumerate(ws):
+        if w.ndim != 1 or w.shape[0] < 1:
+            raise ValueError(f'resample: recording {i} must be [n] with n >= 1, not {w.shape}')
+    up, down = rate_ratio(sr_in, sr_out)
+    if up == down:
+        out = [w.copy() for w in ws]
+    else:
+        out = [y.cpu().numpy() for y in _resample_group(ws, up, down, max_rows, device)]
+    return out[0] if single else out
+
+
 def pitch_track(wavs, lo, hi, max_rows=16, device='cuda'):
     """make_spect_f0.py:64 with the Talkin-style tracker of csrc/pitch.hip in place of `sptk.rapt(wav.astype(np.float32) * 32768, fs, 256,
     min=lo, max=hi, otype=2)`.  One float64 waveform [n] at 16 kHz (or a list of them, any lengths >= 513) -> float64 numpy track(s)
@@ -228,13 +309,43 @@ def read_wav(path):
     return pcm.astype(np.float64) / 32768.0
 
 
-def extract(x, prng, gender, device='cuda', mel_basis=None, unvoiced=0.0):
+def read_audio(path):
+    """Mono PCM of 8, 16, 24 or 32 bits at ANY sample rate through the standard library's `wave` -> (x float64 [n], sr).  Samples are scaled
+    by 2^(bits - 1), 8-bit ones (unsigned in the file) centred on 128 first, as soundfile reads them.  Float and extensible WAV files and more
+    than one channel are refused by name."""
+    try:
+        f = wave.open(path, 'rb')
+    except wave.Error as e:
+        raise ValueError(f'read_audio: {path}: {e}; integer PCM WAV only (float and extensible formats are not read)') from None
+    with f:
+        ch, width, sr, n = f.getnchannels(), f.getsampwidth(), f.getframerate(), f.getnframes()
+        if ch != 1:
+            raise ValueError(f'read_audio: {path}: {ch} channels; mono only')
+        if width not in (1, 2, 3, 4):
+            raise ValueError(f'read_audio: {path}: {8 * width}-bit samples; 8, 16, 24 or 32-bit PCM only')
+        raw = np.frombuffer(f.readframes(n), np.uint8)
+    if width == 1:
+        pcm = raw.astype(np.int64) - 128
+    elif width == 3:
+        b = raw.reshape(-1, 3).astype(np.int64)
+        pcm = b[:, 0] | b[:, 1] << 8 | b[:, 2] << 16
+        pcm = pcm - ((pcm & 0x800000) << 1)                                # sign of the 24-bit value
+    else:
+        pcm = raw.view('<i2' if width == 2 else '<i4')
+    return pcm.astype(np.float64) / float(1 << (8 * width - 1)), sr
+
+
+def extract(x, prng, gender, device='cuda', mel_basis=None, unvoiced=0.0, sr=16000):
     """The loop body of make_spect_f0.py:49-74 for one recording x float64 [n] at 16 kHz: (S float32 [F, 80], f0_norm float32 [F]).
+    A recording at another rate `sr` is brought to 16 kHz first (`resample`: scipy.signal.resample_poly on the GPU, to the bit).
     prng is the speaker's numpy RandomState (the dither draws from it, so recordings of one speaker go through in the reference's order).
     mel_basis [513, n_mels] defaults to mel_filter_bank().T, the reference's.  f0_norm is in [0, 1] on voiced frames and `unvoiced` elsewhere:
     0 by default, which `quantize_f0` reads as unvoiced (<= 0); the reference's speaker_normalization leaves its -1e10 marker in those frames
     (utils.py:39-41 touch the voiced frames only), and that is what its files carry -- make_spect_f0 passes unvoiced=-1e10."""
-    wav = preprocess_wav(np.asarray(x, np.float64), prng)
+    x = np.asarray(x, np.float64)
+    if sr != 16000:
+        x = resample(x, sr, 16000, device=device)
+    wav = preprocess_wav(x, prng)
     S = melspectrogram(wav, mel_filter_bank().T.astype(np.float64) if mel_basis is None else mel_basis, device).cpu().numpy()
     lo, hi = f0_range(gender)
     f0_rapt = pitch_track(wav, lo, hi, device=device)
@@ -278,37 +389,107 @@ def extract_batch(xs, prng, gender, max_rows=16, device='cuda', mel_basis=None, 
     same as calling `extract` on each recording in order with the same prng -- f0_norm to the bit, S within 1e-6 (an FFT in place of the direct
     DFT).  The recordings and their dither draws go up in one copy and run as ragged batches of at most max_rows rows in plan_batches order;
     every row is the result of running it alone, so the result does not depend on max_rows.  One copy per batch brings S and f0_norm back."""
-    lo, hi = f0_range(gender)
+    f0_range(gender)                                                    # an unknown gender stops the call before a draw is made
     flat, lens, batches = stage_batches(xs, prng, max_rows)
-    b, a = butter_highpass(30, 16000, order=5)
-    zi = signal.lfilter_zi(b, a)
-    mb = torch.as_tensor(np.ascontiguousarray(mel_filter_bank().T if mel_basis is None else mel_basis, dtype=np.float64)).to(device)
+    chain = _Chain(gender, device, mel_basis, unvoiced)
     flat_dev, lens_dev = torch.from_numpy(flat).to(device), torch.from_numpy(lens).to(device)
     out, row = [None] * len(xs), 0
     for idx, o, B, max_n in batches:
         x = flat_dev[o:o + B * max_n].view(B, max_n)
         r = flat_dev[o + B * max_n:o + 2 * B * max_n].view(B, max_n)
-        n = lens_dev[row:row + B]
-        wav = filtfilt_dev(x, n, b, a, zi, 0.96, r, 1e-06)
-        S = melspec_batch_dev(wav, n, mb)
-        f0 = pitch_track_dev(wav.float().double(), n, lo, hi)               # the float32 round trip of make_spect_f0.py:64
-        f0n = f0_normalize_batch_dev(f0, n, max_n, unvoiced)
-        F, M = S.shape[1], S.shape[2]
-        both = torch.cat((S.reshape(B, F * M), f0n), dim=1).cpu().numpy()
-        for k, i in enumerate(idx):
-            Fi = int(lens[row + k]) // 256 + 1
-            out[i] = (both[k, :F * M].reshape(F, M)[:Fi].copy(), both[k, F * M:F * M + Fi].copy())
+        for i, feats in zip(idx, chain(x, r, lens_dev[row:row + B], lens[row:row + B])):
+            out[i] = feats
         row += B
     return out
 
 
+class _Chain:
+    """The four device calls of extract_batch on one batch: x, r float64 [B, max_n] (recordings after the odd-length fix, their dither draws)
+    and the rows' lengths on the device (n) and on the host (lens) -> [(S, f0_norm)] a row, after one copy back."""
+
+    def __init__(self, gender, device, mel_basis, unvoiced):
+        self.lo, self.hi = f0_range(gender)
+        self.b, self.a = butter_highpass(30, 16000, order=5)
+        self.zi = signal.lfilter_zi(self.b, self.a)
+        self.mb = torch.as_tensor(np.ascontiguousarray(mel_filter_bank().T if mel_basis is None else mel_basis, dtype=np.float64)).to(device)
+        self.unvoiced = unvoiced
+
+    def __call__(self, x, r, n, lens):
+        B, max_n = x.shape
+        wav = filtfilt_dev(x, n, self.b, self.a, self.zi, 0.96, r, 1e-06)
+        S = melspec_batch_dev(wav, n, self.mb)
+        f0 = pitch_track_dev(wav.float().double(), n, self.lo, self.hi)     # the float32 round trip of make_spect_f0.py:64
+        f0n = f0_normalize_batch_dev(f0, n, max_n, self.unvoiced)
+        F, M = S.shape[1], S.shape[2]
+        both = torch.cat((S.reshape(B, F * M), f0n), dim=1).cpu().numpy()
+        out = []
+        for k in range(B):
+            Fi = int(lens[k]) // 256 + 1
+            out.append((both[k, :F * M].reshape(F, M)[:Fi].copy(), both[k, F * M:F * M + Fi].copy()))
+        return out
+
+
+def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis=None, unvoiced=0.0):
+    """`extract_batch` for recordings at any sample rate: sr is one rate in Hz for all of xs, or one a recording.  The same as
+    extract_batch([scipy.signal.resample_poly(x, 16000, sr) ...], prng, gender, ...), to the bit, with the resampling on the GPU in front of the
+    chain and nothing brought back between them: the recordings are grouped by rate and each group runs through ss_resample as ragged batches in
+    plan_batches order; the odd-length fix and the dither draws then apply to the RESAMPLED lengths -- ceil(n 16000 / sr), which the host knows
+    without waiting for the device -- with the draws in input order; then extract_batch's four calls on batches of the resampled recordings.
+    With every rate 16000 this IS extract_batch: the same calls on the same data."""
+    xs = [np.ascontiguousarray(x, dtype=np.float64) for x in xs]
+    srs = [sr] * len(xs) if np.ndim(sr) == 0 else list(sr)
+    if len(srs) != len(xs):
+        raise ValueError(f'extract_batch_sr: {len(srs)} sample rates for {len(xs)} recordings')
+    if all(s == 16000 for s in srs):
+        return extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced)
+    ratios = [rate_ratio(s, 16000) for s in srs]
+    for i, x in enumerate(xs):
+        if x.ndim != 1 or x.shape[0] < 1:
+            raise ValueError(f'extract_batch_sr: recording {i} must be [n], not {x.shape}')
+    own = [resample_len(x.shape[0], up, down) for x, (up, down) in zip(xs, ratios)]      # samples at 16 kHz
+    lens = [m + 1 if m % 256 == 0 else m for m in own]                                     # after the odd-length fix
+    for i, n in enumerate(lens):
+        if n < MIN_SAMPLES:
+            raise ValueError(f'extract_batch_sr: recording {i} has {n} samples at 16 kHz; every recording must have n >= {MIN_SAMPLES}')
+    f0_range(gender)
+    draws = [prng.rand(n) for n in lens]                                                   # input order, whatever the grouping
+    wav16 = [None] * len(xs)                                                               # device tensors [own[i]]
+    for ratio in sorted(set(ratios)):
+        group = [i for i, q in enumerate(ratios) if q == ratio]
+        if ratio == (1, 1):
+            ys = [torch.from_numpy(xs[i]).to(device) for i in group]
+        else:
+            ys = _resample_group([xs[i] for i in group], ratio[0], ratio[1], max_rows, device)
+        for i, y in zip(group, ys):
+            wav16[i] = y
+    chain = _Chain(gender, device, mel_basis, unvoiced)
+    out = [None] * len(xs)
+    for idx in plan_batches(lens, max_rows):
+        B, max_n = len(idx), lens[idx[-1]]
+        x = torch.zeros(B, max_n, dtype=torch.float64, device=device)
+        rb = np.zeros((B, max_n))
+        for k, i in enumerate(idx):
+            x[k, :own[i]] = wav16[i]
+            if lens[i] > own[i]:
+                x[k, own[i]] = 1e-06
+            rb[k, :lens[i]] = draws[i]
+        rows = [lens[i] for i in idx]
+        for i, feats in zip(idx, chain(x, torch.from_numpy(rb).to(device), torch.tensor(rows, dtype=torch.int32, device=device), rows)):
+            out[i] = feats
+    return out
+
+
 def make_spect_f0(root_dir='assets/wavs', target_dir='assets/spmel', target_dir_f0='assets/raptf0', spk2gen='assets/spk2gen.pkl',
-                  device='cuda', max_rows=None):
+                  device='cuda', resample=False, max_rows=None):
     """The directory walk of make_spect_f0.py:28-74: root_dir/<speaker>/<name>.wav -> target_dir/<speaker>/<name>.npy (S, float32 [F, 80])
     and target_dir_f0/<speaker>/<name>.npy (f0_norm, float32 [F], -1e10 in unvoiced frames as the reference's files); speakers and files in sorted order, one RandomState(int(speaker[1:])) per
     speaker.  spk2gen: a {speaker: 'M' | 'F'} dict, or the path of the reference's pickle of one.  max_rows=None runs `extract` file by file; an
     integer runs each speaker's files through `extract_batch` in batches of at most that many rows (the same F0 files, mel files within
-    1e-6).  Returns the (speaker, name) pairs written."""
+    1e-6).  resample=False reads 16 kHz files only (`read_wav`, which refuses every other rate by name, as the reference asserts); True reads
+    mono PCM of any rate and width (`read_audio`) and brings it to 16 kHz on the GPU first, writing the files the 16 kHz path writes for
+    scipy.signal.resample_poly(x, 16000, sr).  Returns the (speaker, name) pairs written."""
+    if not isinstance(resample, bool):
+        raise TypeError(f'make_spect_f0: resample must be True or False, not {resample!r} (max_rows goes by keyword)')
     if not isinstance(spk2gen, dict):
         with open(spk2gen, 'rb') as f:
             spk2gen = pickle.load(f)
@@ -321,12 +502,18 @@ def make_spect_f0(root_dir='assets/wavs', target_dir='assets/spmel', target_dir_
         f0_range(spk2gen[subdir])                                      # an unknown gender stops the walk before anything is written
         prng = np.random.RandomState(int(subdir[1:]))
         names = sorted(files)
+        read = (lambda name: read_audio(os.path.join(dir_name, subdir, name))) if resample else \
+            (lambda name: (read_wav(os.path.join(dir_name, subdir, name)), 16000))
         if max_rows is not None:
-            feats = extract_batch([read_wav(os.path.join(dir_name, subdir, name)) for name in names], prng, spk2gen[subdir], max_rows,
-                                  device, unvoiced=-1e10) if names else []
+            recs = [read(name) for name in names]
+            feats = extract_batch_sr([x for x, _ in recs], [sr for _, sr in recs], prng, spk2gen[subdir], max_rows, device,
+                                     unvoiced=-1e10) if names else []
         for k, name in enumerate(names):
-            S, f0_norm = feats[k] if max_rows is not None else extract(read_wav(os.path.join(dir_name, subdir, name)), prng,
-                                                                       spk2gen[subdir], device, unvoiced=-1e10)
+            if max_rows is not None:
+                S, f0_norm = feats[k]
+            else:
+                x, sr = read(name)
+                S, f0_norm = extract(x, prng, spk2gen[subdir], device, unvoiced=-1e10, sr=sr)
             np.save(os.path.join(target_dir, subdir, name[:-4]), S, allow_pickle=False)
             np.save(os.path.join(target_dir_f0, subdir, name[:-4]), f0_norm, allow_pickle=False)
             done.append((subdir, name[:-4]))
