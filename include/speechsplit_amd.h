@@ -510,6 +510,37 @@ int ss_op_lstm_fwd_ragged(float* gates_dev, const float* whh_f_dev, const float*
 /* BPTT of the same: d_out [B,T+4,2H]; gates is replaced by the pre-activation gradients. */
 int ss_op_lstm_bwd(float* gates_dev, const float* whh_f_dev, const float* whh_b_dev, const float* d_out_dev,
                    const float* csave_dev, float* scratch_dev, long scratch_floats, int B, int T, int H, void* stream);
+/* The two persistent recurrences (H in {256,512}) launched with every option the engine passes them.  Slabs, weights and d_out as for
+ * ss_op_lstm_fwd / _bwd.  No fall-back: a shape the persistent kernels do not take, an option without its operand, a misplaced image or a
+ * short scratch is refused before anything is enqueued.  scratch: 8*ceil(B/16)*(H/32)*1024 + 8192 bytes (forward) /
+ * 4*ceil(B/16)*(H/16)^2*1024 + 8192 bytes (backward), 16-byte aligned -- the exchange buffer and the sync words, which the hooks zero.
+ * Every optional pointer may be NULL (option off).
+ *   forward
+ *     xc_dev / xf     the layer's input repeats in blocks of xf frames (xf >= 1, T % xf == 0): the pre-activations are given once per block,
+ *                     [B][T/xf][8H], and the gates slab is only written (what it holds on entry is not read).
+ *     out_img_dev     the operand image of `out`, written beside it: the geometry of the out slab [B][T+4][2H]; real rows only (halo rows
+ *                     and the rows of padded utterances are not written).  img_bf16 == 0: format v2 with the scale 16 (what
+ *                     ss_op_split_image makes of out), base 32-byte aligned; img_bf16 != 0: the plain bf16 tensor (2 bytes per element,
+ *                     round to nearest even), base 8-byte aligned.
+ *     hi_only         the recurrent product from the high fp16 pieces of h and W_hh alone (the 16-bit data path).
+ *     len_dev         i32[B], a ragged batch as for ss_op_lstm_fwd_ragged; out, csave and the image hold zeros for t >= len[b].
+ *   backward
+ *     amax_dev        one word: receives max |pre-activation gradient| over the real rows by an atomic max on the float's bit pattern, so
+ *                     it only ever grows: zero it first.
+ *     gbias_f_dev /   [2][4H] each, (b_ih, b_hh) gradient accumulators of the forward / reverse direction: the sum over utterances and
+ *     gbias_b_dev     time of the pre-activation gradients is ADDED to both halves (one float64 sum per tile of 16 utterances, f32 atomics).
+ *     dgs_dev / xf    the pre-activation gradients additionally summed per block of xf frames, [B][T/xf][8H], every element overwritten;
+ *                     fp32 sums in walking order (forward direction: t descending, reverse direction: ascending).
+ *     dimg_dev        the pre-activation gradients once more as a plain bf16 tensor of the gates slab's geometry [B][T+4][8H] (real rows
+ *                     only), base 8-byte aligned.  img_only != 0 (needs dimg_dev): the fp32 slab is NOT written and keeps the forward's
+ *                     activated gates; every other output is as without it.
+ *     hi_only         as the forward's, for da . W_hh. */
+int ss_op_lstm_seq_fwd(float* gates_dev, const float* whh_f_dev, const float* whh_b_dev, float* out_dev, float* csave_dev, float* scratch_dev,
+                       long scratch_floats, const float* xc_dev, int xf, float* out_img_dev, int img_bf16, int hi_only, const int* len_dev,
+                       int B, int T, int H, void* stream);
+int ss_op_lstm_seq_bwd(float* gates_dev, const float* whh_f_dev, const float* whh_b_dev, const float* d_out_dev, const float* csave_dev,
+                       float* scratch_dev, long scratch_floats, float* amax_dev, float* gbias_f_dev, float* gbias_b_dev, float* dgs_dev, int xf,
+                       float* dimg_dev, int img_only, int hi_only, int B, int T, int H, void* stream);
 /* Test hook for the fused weight / bias gradient kernel of the encoder BLSTMs (csrc/lstm_wgrad.hip; hidden size <= 32): from the pre-activation
  * gradients dg [R][8H], the layer input x [R][In] (row stride x_ld) and the layer output hout [R][2H] (haloed slabs flattened to R rows, halo
  * rows zero) ACCUMULATE dW_ih [2][4H][In], dW_hh [2][4H][H] and the bias gradients gb [2][2][4H] (b_ih, b_hh per direction).  scratch:

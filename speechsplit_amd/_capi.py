@@ -76,6 +76,10 @@ SYMBOLS = {
     'ss_op_lstm_fwd': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _vp]),
     'ss_op_lstm_fwd_ragged': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _l, _ip, _i, _i, _i, _vp]),
     'ss_op_lstm_bwd': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _l, _i, _i, _i, _vp]),
+    # gates, whh_f, whh_b, out, csave, scratch, floats, xc, xf, out_img, img_bf16, hi_only, len, B, T, H, stream
+    'ss_op_lstm_seq_fwd': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _l, _fp, _i, _fp, _i, _i, _ip, _i, _i, _i, _vp]),
+    # gates, whh_f, whh_b, d_out, csave, scratch, floats, amax, gbias_f, gbias_b, dgs, xf, dimg, img_only, hi_only, B, T, H, stream
+    'ss_op_lstm_seq_bwd': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _l, _fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _i, _vp]),
     'ss_op_lstm_wgrad': (_i, [_fp, _fp, _l, _fp, _fp, _fp, _fp, _fp, _l, _l, _i, _i, _vp]),
     'ss_op_split_image': (_i, [_fp, _l, _l, _i, _f, _fp, _l, _vp]),
     'ss_op_gemm_pre': (_i, [_fp, _l, _fp, _fp, _l, _fp, _fp, _l, _fp, _i, _i, _i, _i, _i, _vp]),

@@ -258,6 +258,60 @@ int ss_op_lstm_bwd(float* gates, const float* whh_f, const float* whh_b, const f
     return 0;
 }
 
+// The persistent recurrences with every option the engine passes them (SeqFwd / SeqBwd, kernels.h) -- no fall-back to the per-step kernels:
+// whatever the persistent kernels cannot run is refused before anything is enqueued.
+static long op_seq_scratch_floats(int B, int H, bool backward) { return lstm_seq_xbytes(B, H, backward) / 4 + LSTM_SEQ_SYNC_WORDS; }
+static bool misaligned(const void* p, size_t a) { return ((size_t)p & (a - 1)) != 0; }
+
+int ss_op_lstm_seq_fwd(float* gates, const float* whh_f, const float* whh_b, float* out, float* csave, float* scratch, long scratch_floats,
+                       const float* xc, int xf, float* out_img, int img_bf16, int hi_only, const int* len, int B, int T, int H, void* stream) {
+    if (!gates || !whh_f || !whh_b || !out || !csave || !scratch) return fail("ss_op_lstm_seq_fwd: null pointer");
+    if (B < 1 || T < 1 || H < 1) return fail("ss_op_lstm_seq_fwd: empty shape");
+    if (xc && (xf < 1 || T % xf != 0)) return fail("ss_op_lstm_seq_fwd: xc_dev needs xf >= 1 and T % xf == 0");
+    if (misaligned(gates, 16) || misaligned(whh_f, 16) || misaligned(whh_b, 16) || misaligned(out, 16) || misaligned(csave, 16) || misaligned(xc, 16) ||
+        misaligned(scratch, 16))
+        return fail("ss_op_lstm_seq_fwd: an operand is not 16-byte aligned");
+    if (out_img && !img_bf16 && misaligned(out_img, 32)) return fail("ss_op_lstm_seq_fwd: out_img_dev (format v2) is not 32-byte aligned");
+    if (out_img && img_bf16 && misaligned(out_img, 8)) return fail("ss_op_lstm_seq_fwd: out_img_dev (bf16) is not 8-byte aligned");
+    if (scratch_floats < op_seq_scratch_floats(B, H, false)) return fail("ss_op_lstm_seq_fwd: scratch too small");
+    if (!lstm_seq_supported(B, H)) return fail("ss_op_lstm_seq_fwd: shape not supported by the persistent kernels");
+    SeqFwd o{};
+    o.xc = xc;
+    o.xf = xc ? xf : 0;
+    o.out_img = out_img;
+    o.img_bf16 = out_img && img_bf16;
+    o.hi_only = hi_only != 0;
+    o.len = len;
+    HIPCHK(lstm_seq_fwd(gates, whh_f, whh_b, scratch, out, csave, (unsigned*)((char*)scratch + lstm_seq_xbytes(B, H, false)), B, T, H, S(stream), o));
+    return 0;
+}
+
+int ss_op_lstm_seq_bwd(float* gates, const float* whh_f, const float* whh_b, const float* d_out, const float* csave, float* scratch,
+                       long scratch_floats, float* amax, float* gbias_f, float* gbias_b, float* dgs, int xf, float* dimg, int img_only, int hi_only,
+                       int B, int T, int H, void* stream) {
+    if (!gates || !whh_f || !whh_b || !d_out || !csave || !scratch) return fail("ss_op_lstm_seq_bwd: null pointer");
+    if (B < 1 || T < 1 || H < 1) return fail("ss_op_lstm_seq_bwd: empty shape");
+    if (dgs && (xf < 1 || T % xf != 0)) return fail("ss_op_lstm_seq_bwd: dgs_dev needs xf >= 1 and T % xf == 0");
+    if (img_only && !dimg) return fail("ss_op_lstm_seq_bwd: img_only without dimg_dev");
+    if (misaligned(gates, 16) || misaligned(whh_f, 16) || misaligned(whh_b, 16) || misaligned(d_out, 16) || misaligned(csave, 16) || misaligned(dgs, 16) ||
+        misaligned(scratch, 16) || misaligned(amax, 4) || misaligned(gbias_f, 4) || misaligned(gbias_b, 4))
+        return fail("ss_op_lstm_seq_bwd: an operand is not 16-byte aligned (amax_dev, gbias_*_dev: 4-byte)");
+    if (dimg && misaligned(dimg, 8)) return fail("ss_op_lstm_seq_bwd: dimg_dev (bf16) is not 8-byte aligned");
+    if (scratch_floats < op_seq_scratch_floats(B, H, true)) return fail("ss_op_lstm_seq_bwd: scratch too small");
+    if (!lstm_seq_supported(B, H)) return fail("ss_op_lstm_seq_bwd: shape not supported by the persistent kernels");
+    SeqBwd o{};
+    o.amax = amax;
+    o.gbias_f = gbias_f;
+    o.gbias_b = gbias_b;
+    o.dgs = dgs;
+    o.xf = dgs ? xf : 0;
+    o.dimg = dimg;
+    o.img_only = img_only != 0;
+    o.hi_only = hi_only != 0;
+    HIPCHK(lstm_seq_bwd(gates, whh_f, whh_b, scratch, d_out, csave, (unsigned*)((char*)scratch + lstm_seq_xbytes(B, H, true)), B, T, H, S(stream), o));
+    return 0;
+}
+
 int ss_op_lstm_wgrad(const float* dg, const float* x, long x_ld, const float* hout, float* gwih, float* gwhh, float* gb, float* scratch, long scratch_floats,
                      long R, int H, int In, void* stream) {
     if (H < 1 || H > 32 || In < 1 || R < 1) return fail("ss_op_lstm_wgrad: H in 1..32, In >= 1");

@@ -860,7 +860,9 @@ __global__ __launch_bounds__(64 * (NW + 2)) void lstm_seq_bwd_kernel(float* __re
             }
 #pragma unroll
             for (int i = 0; i < PW; ++i) {
-                const f32x4 v = __builtin_bit_cast(f32x4, r[i]);
+                // the tag bit is taken out again: left in, a partial sum of exactly zero arrives as 2^-149 under tag 1, and a layer whose
+                // output gradient is zero produced denormal pre-activation gradients (and an amax of ~1e-44) instead of zeros
+                const f32x4 v = __builtin_bit_cast(f32x4, r[i] & 0xFFFFFFFEu);
                 part += v;
             }
         }

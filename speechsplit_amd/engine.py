@@ -731,10 +731,11 @@ def lstm_scratch(B, H, backward, persist=True):
     return n
 
 
-def _blstm_recurrence_slabs(gates_real, w_hh, d_out, lengths, place, want_act):
+def _blstm_recurrence_slabs(gates_real, w_hh, d_out, lengths, place, want_act, seq=None):
     """The recurrences of one BLSTM layer on haloed slabs: gates_real [B,T,8H] pre-activations -> (gates, out, csave, act) with gates
     [R,8H] holding the activated gates (no d_out) or the pre-activation gradients (d_out given), out / csave [B,T+4,ld] and act a clone
-    of the real frames' activated gates taken before the backward overwrites them (want_act only, else None)."""
+    of the real frames' activated gates taken before the backward overwrites them (want_act only, else None).
+    seq (seq_recurrence): the option pointers of ss_op_lstm_seq_fwd / _bwd, which then run in the place of ss_op_lstm_fwd / _bwd."""
     lib = _capi.lib()
     B, T, H8 = gates_real.shape
     H = w_hh[0].shape[1]
@@ -760,9 +761,22 @@ def _blstm_recurrence_slabs(gates_real, w_hh, d_out, lengths, place, want_act):
             assert t.is_contiguous()
     whf, whb = w_hh[0].contiguous(), w_hh[1].contiguous()
     real = lambda: gates.view(B, T + 4, 8 * H)[:, 2:2 + T].clone()
+    if lengths is not None and d_out is not None:
+        raise ValueError('speechsplit_amd: a ragged BLSTM layer runs the forward only')
+    if seq is not None:
+        ln = None if lengths is None else check_lengths(lengths, B, T, (1,), dev)
+        _capi.check(lib.ss_op_lstm_seq_fwd(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(out), _ptr(csave), _ptr(scratch), scratch.numel(), _ptr(seq['xc']),
+                                           int(seq['xf']), _ptr(seq['out_img']), int(seq['img_bf16']), int(seq['hi_only']), _ptr(ln), B, T, H, _stream()))
+        act = real() if want_act else None
+        if d_out is None:
+            return gates, out, csave, act
+        ds = _slab(d_out.to(dev))
+        scratch_b.zero_()
+        _capi.check(lib.ss_op_lstm_seq_bwd(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(ds), _ptr(csave), _ptr(scratch_b), scratch_b.numel(),
+                                           _ptr(seq['amax']), _ptr(seq['gbias_f']), _ptr(seq['gbias_b']), _ptr(seq['dgs']), int(seq['xf']),
+                                           _ptr(seq['dimg']), int(seq['img_only']), int(seq['hi_only']), B, T, H, _stream()))
+        return gates, out, csave, act
     if lengths is not None:
-        if d_out is not None:
-            raise ValueError('speechsplit_amd: a ragged BLSTM layer runs the forward only')
         ln = check_lengths(lengths, B, T, (1,), dev)
         _capi.check(lib.ss_op_lstm_fwd_ragged(_ptr(gates), _ptr(whf), _ptr(whb), _ptr(out), _ptr(csave), _ptr(scratch), scratch.numel(),
                                               _ptr(ln), B, T, H, _stream()))
@@ -796,6 +810,62 @@ def blstm_recurrence(gates, w_hh, d_out=None, lengths=None, place=None):
     slab, out, csave, act = _blstm_recurrence_slabs(gates.to(dtype=torch.float32), w_hh, d_out, lengths, place, True)
     dgates = slab.view(B, T + 4, 8 * H)[:, 2:2 + T].clone() if d_out is not None else None
     return out[:, 2:2 + T, :2 * H].clone(), csave[:, 2:2 + T, :2 * H].clone(), act, dgates
+
+
+SEQ_GUARD = 4096          # bytes of guard region behind every side output seq_recurrence returns, beside the padded utterances' room
+SEQ_FILL = 0xA5           # the byte those guards and the images are pre-filled with
+
+
+def seq_recurrence(pre_or_xc, w_hh, d_out=None, *, xf=0, out_img=None, hi_only=False, lengths=None, amax0=None, gbias0=None, dgs=False,
+                   dimg=False, img_only=False):
+    """Test hook (ss_op_lstm_seq_fwd / _bwd): the persistent recurrences (H in {256, 512}) launched with the options the engine passes them;
+    no fall-back, what the persistent kernels cannot run raises.  pre_or_xc: the pre-activations [B,T,8H], or with xf > 0 their compact
+    form [B,T/xf,8H] (the input repeats in blocks of xf frames) -- the gates slab then starts with NaN in every real row, which the kernel
+    only writes.  out_img: 'v2' or 'bf16'; amax0: the start value of the amax word; gbias0 [8H]: start value of both halves (b_ih, b_hh)
+    of the bias-gradient accumulators, forward direction in [0,4H); dgs / dimg / img_only: SeqBwd's (dgs sums per block of xf frames, xf = 0:
+    of one frame).  Returns a dict: out, csave, act, dgates as blstm_recurrence returns them (dgates: the real rows of the gates slab after the
+    backward, so under img_only the activated gates it kept) and every requested side output as a RAW uint8 tensor with a guard region of
+    SEQ_FILL behind it -- for the per-utterance outputs (out_img, dimg, dgs) the room the 16 ceil(B/16) - B padded utterances of the last batch
+    tile would take, then SEQ_GUARD bytes; SEQ_GUARD bytes for amax and gbias: out_img / dimg over the whole haloed slab ([B,T+4,2H] / [B,T+4,8H] elements of 4 bytes (v2) or 2 (bf16), pre-filled
+    with SEQ_FILL), amax (4 bytes), gbias ([2 directions][2 halves][4H] floats), dgs ([B,T/xf,8H] floats, pre-filled with NaN)."""
+    pre_or_xc = pre_or_xc.to(dtype=torch.float32).contiguous()
+    dev = pre_or_xc.device
+    B, Tc, H8 = pre_or_xc.shape
+    H = H8 // 8
+    T = Tc * xf if xf > 0 else Tc
+    bxf = xf if xf > 0 else 1
+    if out_img not in (None, 'v2', 'bf16'):
+        raise ValueError("speechsplit_amd: out_img is None, 'v2' or 'bf16'")
+
+    pad = (B + 15) // 16 * 16 - B                            # utterances a kernel that lost its b < B test would also write
+
+    def raw(nbytes, fill=None, per_utt=0):
+        t = torch.full((nbytes + pad * per_utt + SEQ_GUARD,), SEQ_FILL, dtype=torch.uint8, device=dev)
+        if fill is not None:
+            t[:nbytes].view(torch.float32).copy_(fill.reshape(-1))
+        return t
+    side = {}
+    if out_img:
+        side['out_img'] = raw(B * (T + 4) * 2 * H * (4 if out_img == 'v2' else 2), None, (T + 4) * 2 * H * (4 if out_img == 'v2' else 2))
+    if d_out is not None:
+        if amax0 is not None:
+            side['amax'] = raw(4, torch.tensor([float(amax0)], device=dev))
+        if gbias0 is not None:
+            g0 = torch.as_tensor(gbias0, dtype=torch.float32, device=dev).view(2, 1, 4 * H).expand(2, 2, 4 * H).contiguous()
+            side['gbias'] = raw(4 * 16 * H, g0)
+        if dgs:
+            side['dgs'] = raw(4 * B * (T // bxf) * 8 * H, torch.full((B * (T // bxf) * 8 * H,), float('nan'), device=dev), 4 * (T // bxf) * 8 * H)
+        if dimg:
+            side['dimg'] = raw(2 * B * (T + 4) * 8 * H, None, 2 * (T + 4) * 8 * H)
+    fl = lambda name, off=0: side[name][off:].view(torch.float32) if name in side else None
+    seq = dict(xc=pre_or_xc if xf > 0 else None, xf=bxf if (xf > 0 or dgs) else 0, out_img=fl('out_img'), img_bf16=out_img == 'bf16',
+               hi_only=hi_only, amax=fl('amax'), gbias_f=fl('gbias'), gbias_b=fl('gbias', 4 * 8 * H), dgs=fl('dgs'), dimg=fl('dimg'), img_only=img_only)
+    gates_real = torch.full((B, T, 8 * H), float('nan'), device=dev) if xf > 0 else pre_or_xc
+    slab, out, csave, act = _blstm_recurrence_slabs(gates_real, w_hh, d_out, lengths, None, True, seq)
+    res = dict(out=out[:, 2:2 + T, :2 * H].clone(), csave=csave[:, 2:2 + T, :2 * H].clone(), act=act,
+               dgates=slab.view(B, T + 4, 8 * H)[:, 2:2 + T].clone() if d_out is not None else None)
+    res.update(side)
+    return res
 
 
 def blstm_layer(x, w_ih, w_hh, b_ih, b_hh, d_out=None, place=None, lengths=None):

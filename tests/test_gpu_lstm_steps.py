@@ -1,7 +1,8 @@
 """The LSTM recurrence kernels (csrc/lstm_small.hip, lstm_step.hip, lstm_seq.hip) step by step against float64 (pytest -m gpu): every
 kernel family, at the smallest shapes that still select it, gets the caller's pre-activations through engine.blstm_recurrence and its own
 saved state (activated gates, cell states, outputs, pre-activation gradients) goes through the checks of lstm_ref.py -- F1 .. F3 and B1 over
-the five scenarios with W_hh = 0; F1, F2 and the chain budget B2 with trained-scale W_hh; F1 / F2 and the zero tails on a ragged forward with
+the five scenarios with W_hh = 0; F1, F2, the recurrent products per step F4 / B3 (each family's operand rounding, lstm_ref.operands_of) and
+the chain budget B2 with trained-scale W_hh; F1 / F2 and the zero tails on a ragged forward with
 NaN behind each row's length; bit-identical repeats of the `extreme` scenario.  The checks, their bars and where the bars come from are in
 lstm_ref.py's docstring; test_lstm_ref_selftest.py proves on the CPU that they accept correct fp32 code and report the wrong variants.
 Every test prints the ratios it measured before it asserts (a pass is <= 1)."""
@@ -70,17 +71,22 @@ def test_steps_with_zero_whh(fam, scenario):
 @pytest.mark.parametrize('ws', [3, 6])
 @pytest.mark.parametrize('fam', FAMILIES, ids=FAMILY_IDS)
 def test_chain_budget_with_trained_scale_whh(fam, ws):
-    """W_hh ~ U(+-ws / sqrt(H)): F1 and F2 still hold on the saved state, and out / dgates / dW_hh stay within B2 of float64."""
-    name, H, B, T, _ = fam
+    """W_hh ~ U(+-ws / sqrt(H)): F1 and F2 still hold on the saved state, every step's recurrent product W_hh h(t-1) / da(t+1) W_hh is the
+    family's (F4, B3), and out / dgates / dW_hh stay within B2 of float64."""
+    name, H, B, T, knobs = fam
     pre, w, d = R.trained(B, T, H, ws)
     r = run(fam, pre, w, d)
     assert all(np.isfinite(v).all() for v in r.values()), (name, ws, 'non-finite output')
     f1, f2 = R.check_f1(r['act'], r['csave']), R.check_f2(r['act'], r['csave'], r['out'])
+    ops = R.operands_of(H, knobs, B=B)
+    f4, b3 = R.check_f4(pre, r['act'], r['out'], w, ops), R.check_b3(r['act'], r['csave'], d, r['dgates'], w, ops)
     r['dw_hh'] = R.dw_hh(r['dgates'], r['out'])
     b2 = R.check_b2(r, R.layer64(pre, w, d), R.layer32(pre, w, d, R.TorchF32))
-    print(f'lstm_steps {name} ws {ws}: F1 {f1:.3f} F2 {f2:.3f} B2 (engine / fp32 error, ratio to bar) ' +
+    print(f'lstm_steps {name} ws {ws}: F1 {f1:.3f} F2 {f2:.3f} F4 {f4:.3f} B3 {b3:.3f} ({ops.mode}{" tagged" if ops.tagged else ""}) '
+          'B2 (engine / fp32 error, ratio to bar) ' +
           ' '.join(f'{k} {e:.2e}/{e32:.2e} {q:.3f}' for k, (e, e32, q) in b2.items()))
     assert f1 <= 1.0 and f2 <= 1.0, (name, ws, f1, f2)
+    assert f4 <= 1.0 and b3 <= 1.0, (name, ws, f4, b3)
     assert all(q <= 1.0 for _, _, q in b2.values()), (name, ws, b2)
 
 
