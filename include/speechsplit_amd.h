@@ -570,6 +570,41 @@ int ss_op_gemm_pre(const float* a_dev, long lda, const float* a_img_dev, const f
 int ss_op_gemm_img(const float* a_img_dev, long lda, const float* b_img_dev, long ldb, float* c_dev, long ldc, const float* bias_dev, int M, int N,
                    int K, int flags, int ksplit, int cfg, float scale_a, float scale_b, int a_seglen, long a_segstride, float* part_dev,
                    const void* zeros_dev, void* stream);
+/* Descriptor-level TEST HOOKS of the two GEMM launchers: one plain struct carries every field a product launch sets, and the hook hands it to
+ * the launcher unchanged (launch_gemm / launch_gemm_img in speechsplit_amd/csrc/common.h, where each field is specified) and does nothing else.
+ * An operand's element (row, col) of batch b lives at p + b * bstride + row * ld + (col / seglen) * segstride + col % seglen (seglen == 0:
+ * + col), all in elements; the result at c + b * cstride + m * ldc + n.  flags: 1 = A stored [K,M], 2 = B stored [K,N], 4 = accumulate into C;
+ * ss_op_gemm_desc also 8 = bf16-rounded operands, 16 = fp16 x 2 split.  row_period > 0: row m is stored only if (m + row_off) % row_period
+ * lies in [row_lo, row_hi).  Every optional pointer may be NULL.
+ *   ss_op_gemm_desc      want: least number of workgroups the tile choice should produce (0: the library default).  amax_a / amax_b: device
+ *                        words holding max|operand| (fp16 x 2: the scale is the power of two that brings it into [128, 256)); a_pre / b_pre:
+ *                        the operand's image (same geometry); a_pre_scale / b_pre_scale: device words holding a fixed scale (NULL: 16);
+ *                        part: batch * ksplit * M * N floats for the ordered split-K (NULL: atomics).
+ *   ss_op_gemm_img_desc  a / b are IMAGES (bf16 != 0: plain bf16 tensors, 2 bytes per element).  rm_T > 0 (A K-contiguous, rm_T >= 32):
+ *                        logical row m of A and C is memory row (m / rm_T) * rm_TP + m % rm_T.  scale_a / scale_b: device words (NULL: 16);
+ *                        zeros: >= 1 KB of zero bytes; cfg: -1 .. 3 as ss_op_gemm_img.  The work-queue form stays with ss_op_gemm_img.
+ * Refused before anything is enqueued, each with its own ss_last_error text: a null descriptor or a null a / b / c, a negative size, an
+ * unknown flag, a row mask outside its period, ksplit > 1 without the accumulate flag (ss_op_gemm_desc) or without part (ss_op_gemm_img_desc),
+ * and whatever the image GEMM does not support (its alignment rules, rm_T with a row mask, a row mask with ksplit > 1). */
+typedef struct ss_gemm_desc {
+    const float *a, *b;
+    float* c;
+    const float *bias, *amax_a, *amax_b, *a_pre, *b_pre, *a_pre_scale, *b_pre_scale;
+    float* part;
+    long lda, a_bstride, a_segstride, ldb, b_bstride, b_segstride, ldc, cstride;
+    int a_seglen, b_seglen, M, N, K, batch, flags, want, row_period, row_off, row_lo, row_hi, ksplit;
+} ss_gemm_desc;
+typedef struct ss_gemm_img_desc {
+    const void *a, *b;
+    float* c;
+    const float *bias, *scale_a, *scale_b;
+    float* part;
+    const void* zeros;
+    long lda, a_bstride, a_segstride, ldb, b_bstride, b_segstride, ldc, cstride;
+    int a_seglen, b_seglen, M, N, K, batch, flags, row_period, row_off, row_lo, row_hi, rm_T, rm_TP, ksplit, cfg, bf16;
+} ss_gemm_img_desc;
+int ss_op_gemm_desc(const ss_gemm_desc* desc, void* stream);
+int ss_op_gemm_img_desc(const ss_gemm_img_desc* desc, void* stream);
 /* One relu(GroupNorm(ConvNorm(x))) block (model.py:61-67,76-77; 16 channels per group) through the engine's own block
  * routines, forward and -- when dy is given -- backward.  x [B,T,Ci], w [Co,Ci,5], bias/gamma/beta [Co], y/dy [B,T,Co],
  * dx [B,T,Ci] (nullable), gw [Co,Ci,5], gb/ggamma/gbeta [Co]; scratch of ss_op_conv_block_scratch() floats.  T <= 256 with a

@@ -22,6 +22,24 @@ def hparams_struct(hp):
     return SSHparams(**{n: int(getattr(hp, n)) for n in HP_FIELDS})
 
 
+GEMM_DESC_PTRS = ('a', 'b', 'c', 'bias', 'amax_a', 'amax_b', 'a_pre', 'b_pre', 'a_pre_scale', 'b_pre_scale', 'part')
+GEMM_IMG_DESC_PTRS = ('a', 'b', 'c', 'bias', 'scale_a', 'scale_b', 'part', 'zeros')
+GEMM_DESC_LONGS = ('lda', 'a_bstride', 'a_segstride', 'ldb', 'b_bstride', 'b_segstride', 'ldc', 'cstride')
+GEMM_DESC_INTS = ('a_seglen', 'b_seglen', 'M', 'N', 'K', 'batch', 'flags', 'want', 'row_period', 'row_off', 'row_lo', 'row_hi', 'ksplit')
+GEMM_IMG_DESC_INTS = ('a_seglen', 'b_seglen', 'M', 'N', 'K', 'batch', 'flags', 'row_period', 'row_off', 'row_lo', 'row_hi', 'rm_T', 'rm_TP', 'ksplit', 'cfg',
+                      'bf16')
+
+
+class SSGemmDesc(C.Structure):
+    """ss_gemm_desc (test hook ss_op_gemm_desc): every GemmDesc field a product launch sets."""
+    _fields_ = [(n, C.c_void_p) for n in GEMM_DESC_PTRS] + [(n, C.c_long) for n in GEMM_DESC_LONGS] + [(n, C.c_int) for n in GEMM_DESC_INTS]
+
+
+class SSGemmImgDesc(C.Structure):
+    """ss_gemm_img_desc (test hook ss_op_gemm_img_desc): the same for ImgGemmDesc."""
+    _fields_ = [(n, C.c_void_p) for n in GEMM_IMG_DESC_PTRS] + [(n, C.c_long) for n in GEMM_DESC_LONGS] + [(n, C.c_int) for n in GEMM_IMG_DESC_INTS]
+
+
 # every symbol include/speechsplit_amd.h declares: name -> (restype, argtypes)
 _vp, _fp, _ip, _i, _l, _f, _d = C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 SYMBOLS = {
@@ -84,6 +102,8 @@ SYMBOLS = {
     'ss_op_split_image': (_i, [_fp, _l, _l, _i, _f, _fp, _l, _vp]),
     'ss_op_gemm_pre': (_i, [_fp, _l, _fp, _fp, _l, _fp, _fp, _l, _fp, _i, _i, _i, _i, _i, _vp]),
     'ss_op_gemm_img': (_i, [_fp, _l, _fp, _l, _fp, _l, _fp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _l, _fp, _vp, _vp]),
+    'ss_op_gemm_desc': (_i, [C.POINTER(SSGemmDesc), _vp]),
+    'ss_op_gemm_img_desc': (_i, [C.POINTER(SSGemmImgDesc), _vp]),
     'ss_op_conv_block_scratch': (_l, [_i, _i, _i, _i]),
     'ss_op_conv_block': (_i, [_fp] * 13 + [_l, _i, _i, _i, _i, _vp]),
     'ss_op_conv_block_ragged': (_i, [_fp] * 5 + [_ip, _fp, _fp, _l, _i, _i, _i, _i, _vp]),

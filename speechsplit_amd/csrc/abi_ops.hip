@@ -100,6 +100,87 @@ int ss_op_gemm_img(const float* a_img, long lda, const float* b_img, long ldb, f
     return 0;
 }
 
+// Descriptor-level test hooks: every field a product launch sets, handed to the launcher unchanged.  Every refusal is made before anything
+// is enqueued.
+int ss_op_gemm_desc(const ss_gemm_desc* g, void* stream) {
+    if (!g) return fail("ss_op_gemm_desc: null descriptor");
+    if (!g->a || !g->b || !g->c) return fail("ss_op_gemm_desc: null pointer (a, b and c are required)");
+    if (g->M < 0 || g->N < 0 || g->K < 0 || g->batch < 0 || g->ksplit < 0 || g->want < 0 || g->a_seglen < 0 || g->b_seglen < 0)
+        return fail("ss_op_gemm_desc: negative size");
+    if (g->flags & ~(GEMM_TA | GEMM_TB | GEMM_ACCUM | GEMM_BF16 | GEMM_F16X2)) return fail("ss_op_gemm_desc: unknown flag");
+    if (g->ksplit > 1 && !(g->flags & GEMM_ACCUM)) return fail("ss_op_gemm_desc: ksplit > 1 needs the accumulate flag (C zeroed or live)");
+    if (g->row_period < 0 || (g->row_period > 0 && (g->row_off < 0 || g->row_lo < 0 || g->row_hi > g->row_period || g->row_lo > g->row_hi)))
+        return fail("ss_op_gemm_desc: bad row mask");
+    GemmDesc d{};
+    d.A = {g->a, g->lda, g->a_bstride, g->a_seglen, g->a_segstride};
+    d.B = {g->b, g->ldb, g->b_bstride, g->b_seglen, g->b_segstride};
+    d.C = g->c;
+    d.ldc = g->ldc;
+    d.cstride = g->cstride;
+    d.bias = g->bias;
+    d.M = g->M;
+    d.N = g->N;
+    d.K = g->K;
+    d.batch = g->batch;
+    d.flags = g->flags;
+    d.want = g->want;
+    d.row_period = g->row_period;
+    d.row_off = g->row_off;
+    d.row_lo = g->row_lo;
+    d.row_hi = g->row_hi;
+    d.ksplit = g->ksplit < 1 ? 1 : g->ksplit;
+    d.amax_a = g->amax_a;
+    d.amax_b = g->amax_b;
+    d.a_pre = g->a_pre;
+    d.b_pre = g->b_pre;
+    d.a_pre_scale = g->a_pre_scale;
+    d.b_pre_scale = g->b_pre_scale;
+    d.part = g->part;
+    HIPCHK(launch_gemm(d, S(stream)));
+    return 0;
+}
+
+int ss_op_gemm_img_desc(const ss_gemm_img_desc* g, void* stream) {
+    if (!g) return fail("ss_op_gemm_img_desc: null descriptor");
+    if (!g->a || !g->b || !g->c) return fail("ss_op_gemm_img_desc: null pointer (a, b and c are required)");
+    if (g->M < 0 || g->N < 0 || g->K < 0 || g->batch < 0 || g->ksplit < 0 || g->a_seglen < 0 || g->b_seglen < 0 || g->rm_T < 0 || g->rm_TP < 0)
+        return fail("ss_op_gemm_img_desc: negative size");
+    if (g->flags & ~(GEMM_TA | GEMM_TB | GEMM_ACCUM)) return fail("ss_op_gemm_img_desc: unknown flag");
+    if (g->ksplit > 1 && !g->part) return fail("ss_op_gemm_img_desc: ksplit > 1 needs part_dev");
+    if (g->row_period < 0 || (g->row_period > 0 && (g->row_off < 0 || g->row_lo < 0 || g->row_hi > g->row_period || g->row_lo > g->row_hi)))
+        return fail("ss_op_gemm_img_desc: bad row mask");
+    if (g->rm_T > 0 && g->rm_TP < g->rm_T) return fail("ss_op_gemm_img_desc: rm_TP < rm_T");
+    if (g->cfg < -1 || g->cfg > 3) return fail("ss_op_gemm_img_desc: cfg outside -1 .. 3");
+    ImgGemmDesc d{};
+    d.A = {g->a, g->lda, g->a_bstride, g->a_seglen, g->a_segstride};
+    d.B = {g->b, g->ldb, g->b_bstride, g->b_seglen, g->b_segstride};
+    d.C = g->c;
+    d.ldc = g->ldc;
+    d.cstride = g->cstride;
+    d.bias = g->bias;
+    d.M = g->M;
+    d.N = g->N;
+    d.K = g->K;
+    d.batch = g->batch < 1 ? 1 : g->batch;
+    d.ksplit = g->ksplit < 1 ? 1 : g->ksplit;
+    d.flags = g->flags;
+    d.row_period = g->row_period;
+    d.row_off = g->row_off;
+    d.row_lo = g->row_lo;
+    d.row_hi = g->row_hi;
+    d.rm_T = g->rm_T;
+    d.rm_TP = g->rm_TP;
+    d.part = g->part;
+    d.bf16 = g->bf16 ? 1 : 0;
+    d.scale_a = d.bf16 ? nullptr : g->scale_a;
+    d.scale_b = d.bf16 ? nullptr : g->scale_b;
+    d.zeros = g->zeros;
+    d.cfg = g->cfg;
+    if (!gemm_img_supported(d)) return fail("ss_op_gemm_img_desc: shape / alignment / option not supported by the image GEMM");
+    HIPCHK(launch_gemm_img(d, S(stream)));
+    return 0;
+}
+
 // Where do the workgroups of a launch go?  n_wg workgroups of `threads` threads and lds_bytes of LDS each record (XCC_ID register, HW_ID
 // register) in launch order; each then idles `hold_ticks` (100 MHz) so that the whole grid has to be resident at once.
 __global__ void xcc_map_kernel(unsigned* out, long long hold_ticks) {

@@ -548,6 +548,7 @@ bool gemm_img_supported(const ImgGemmDesc& d) {
     if (d.N % 4) return false;
     if ((ta || tb) && d.K % KT && !d.zeros) return false;
     if (d.rm_T && (d.rm_T < 32 || ta || d.row_period)) return false;
+    if (d.row_period && d.ksplit > 1) return false;     // the partial slabs carry no mask: splitk_reduce would write the masked rows
     return ok(d.A, ta, d.M) && ok(d.B, tb, d.N);
 }
 

@@ -938,3 +938,53 @@ def gemm(a, b, bias=None, ta=False, tb=False, ksplit=1, out=None, bf16=False, f1
     _capi.check(lib.ss_op_gemm(_ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(c), c.stride(0), _ptr(bias), M, N, K,
                                (1 if ta else 0) | (2 if tb else 0) | (8 if bf16 else 0) | (16 if f16x2 else 0), ksplit, _stream()))
     return c
+
+
+def _at(buf, off):
+    """Device address of element `off` of the flat buffer `buf` (None: null)."""
+    return None if buf is None else buf.data_ptr() + int(off) * buf.element_size()
+
+
+def _geom(g):
+    """Operand geometry (off, ld, bstride=0, seglen=0, segstride=0), all in elements."""
+    g = tuple(int(v) for v in g)
+    return g + (0,) * (5 - len(g))
+
+
+def gemm_desc(a, a_geom, b, b_geom, c, c_geom, M, N, K, *, batch=1, ta=False, tb=False, accumulate=False, bf16=False, f16x2=False, bias=None,
+              want=0, row_mask=(0, 0, 0, 0), ksplit=1, amax_a=None, amax_b=None, a_img=None, b_img=None, a_pre_scale=None, b_pre_scale=None,
+              part=None):
+    """Test hook (ss_op_gemm_desc): one launch_gemm call with every descriptor field a product launch sets.  a, b, c are FLAT buffers --
+    segmented and batched operands overlap, so they have no tensor shape; a_geom / b_geom = (off, ld, bstride, seglen, segstride) and
+    c_geom = (off, ldc, cstride) place the matrices in them, in elements.  a_img / b_img: flat image buffers of the same geometry;
+    amax_* / *_pre_scale: one-element device tensors; row_mask = (period, off, lo, hi); part: batch * ksplit * M * N floats."""
+    ao, lda, abs_, asl, ass = _geom(a_geom)
+    bo, ldb, bbs, bsl, bss = _geom(b_geom)
+    co, ldc, cs = _geom(c_geom)[:3]
+    d = _capi.SSGemmDesc(a=_at(a, ao), b=_at(b, bo), c=_at(c, co), bias=_at(bias, 0), amax_a=_at(amax_a, 0), amax_b=_at(amax_b, 0), a_pre=_at(a_img, ao),
+                         b_pre=_at(b_img, bo), a_pre_scale=_at(a_pre_scale, 0), b_pre_scale=_at(b_pre_scale, 0), part=_at(part, 0), lda=lda, a_bstride=abs_,
+                         a_segstride=ass, ldb=ldb, b_bstride=bbs, b_segstride=bss, ldc=ldc, cstride=cs, a_seglen=asl, b_seglen=bsl, M=M, N=N, K=K,
+                         batch=batch, flags=(1 if ta else 0) | (2 if tb else 0) | (4 if accumulate else 0) | (8 if bf16 else 0) | (16 if f16x2 else 0),
+                         want=want, row_period=row_mask[0], row_off=row_mask[1], row_lo=row_mask[2], row_hi=row_mask[3], ksplit=ksplit)
+    _capi.check(_capi.lib().ss_op_gemm_desc(C.byref(d), _stream()))
+    return c
+
+
+def gemm_img_desc(a_img, a_geom, b_img, b_geom, c, c_geom, M, N, K, *, batch=1, ta=False, tb=False, accumulate=False, bias=None,
+                  row_mask=(0, 0, 0, 0), rm=(0, 0), ksplit=1, part=None, scale_a=None, scale_b=None, zeros=None, cfg=-1):
+    """Test hook (ss_op_gemm_img_desc): one launch_gemm_img call.  Flat buffers and geometry as gemm_desc (offsets and strides in ELEMENTS of
+    the underlying matrix); torch.bfloat16 image buffers select the single-piece form.  rm = (rm_T, rm_TP); scale_a / scale_b: one-element
+    device tensors (None: 16); zeros: >= 1 KB of zero bytes (None: a shared buffer)."""
+    bf16 = a_img.dtype == torch.bfloat16
+    assert (b_img.dtype == torch.bfloat16) == bf16
+    ao, lda, abs_, asl, ass = _geom(a_geom)
+    bo, ldb, bbs, bsl, bss = _geom(b_geom)
+    co, ldc, cs = _geom(c_geom)[:3]
+    z = _ZEROS.setdefault(str(c.device), torch.zeros(1024, device=c.device)) if zeros is None else zeros
+    d = _capi.SSGemmImgDesc(a=_at(a_img, ao), b=_at(b_img, bo), c=_at(c, co), bias=_at(bias, 0), scale_a=_at(scale_a, 0), scale_b=_at(scale_b, 0),
+                            part=_at(part, 0), zeros=_at(z, 0), lda=lda, a_bstride=abs_, a_segstride=ass, ldb=ldb, b_bstride=bbs, b_segstride=bss, ldc=ldc,
+                            cstride=cs, a_seglen=asl, b_seglen=bsl, M=M, N=N, K=K, batch=batch,
+                            flags=(1 if ta else 0) | (2 if tb else 0) | (4 if accumulate else 0), row_period=row_mask[0], row_off=row_mask[1],
+                            row_lo=row_mask[2], row_hi=row_mask[3], rm_T=rm[0], rm_TP=rm[1], ksplit=ksplit, cfg=cfg, bf16=1 if bf16 else 0)
+    _capi.check(_capi.lib().ss_op_gemm_img_desc(C.byref(d), _stream()))
+    return c
