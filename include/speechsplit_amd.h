@@ -374,8 +374,8 @@ int  ss_op_pitch_dp(const double* phi_dev, const double* rms_dev, const int* n_d
  *   Pass 1.     z = zi * ext[0]; v[j] = step(ext[j]), j ascending.
  *   Pass 2.     z = zi * v[n+35]; w[j] = step(v[j]), j descending.
  *   Output.     y[i] = w[i + 18], 0 <= i < n.
- *   Epilogue.   out[i] = y[i]*gain + (r[i] - 0.5)*dither_scale, rounded step by step, r = dither_dev (the host's prng.rand values: the draw
- *               is the speaker's numpy stream and stays on the host); dither_dev == NULL: out[i] = y[i]*gain.  gain = 0.96 and
+ *   Epilogue.   out[i] = y[i]*gain + (r[i] - 0.5)*dither_scale, rounded step by step, r = dither_dev (prng.rand values of the speaker's numpy stream:
+ *               drawn on the host, or on the device by ss_mt19937_rand and ss_dither_rows below); dither_dev == NULL: out[i] = y[i]*gain.  gain = 0.96 and
  *               dither_scale = 1e-06 are make_spect_f0.py:54-55 exactly.  The odd-length fix of :52-53 changes n and stays in Python.
  * Zeros are written behind n_b.  scratch: the first pass's output, [B][max_n + 36] doubles, rounded up to 256 bytes.
  *
@@ -421,6 +421,35 @@ long ss_resample_len(long n, int up, int down);              /* host only: ceil(
 long ss_resample_scratch_bytes(int up, int n_taps);          /* host only; may be 0; -1 + ss_last_error on bad arguments */
 int  ss_resample(const double* x_dev, const int* n_dev, int B, int max_n, int up, int down, const double* h_dev, int n_taps,
                  double* y_dev, void* scratch_dev, long scratch_bytes, void* stream);
+
+/* ss_mt19937_rand: the dither draw of make_spect_f0.py:55 on the device -- numpy.random.RandomState.rand(count) continued from a
+ * caller-supplied generator state, bit for bit in every draw and in the state left behind.
+ * state_dev: unsigned [625] ON THE DEVICE, read and written in place: state[0 .. 623] is numpy's `key`, state[624] numpy's `pos` in 0 .. 624
+ * (RandomState.get_state()[1] and [2]).  A pos above 624 cannot be refused on the host; the kernel treats it as 624.
+ *   Recurrence.  N = 624, M = 397, A = 0x9908b0df.  x[0 .. 623] = key; for n >= 0, with y = (x[n] & 0x80000000) | (x[n+1] & 0x7fffffff):
+ *                x[n+624] = x[n+397] ^ (y >> 1) ^ ((y & 1) ? A : 0).
+ *   Tempering.   temper(y): y ^= y >> 11; y ^= (y << 7) & 0x9d2c5680; y ^= (y << 15) & 0xefc60000; y ^= y >> 18.
+ *   Stream.      word j is w[j] = temper(x[pos + j]).
+ *   Draw.        out[i] = ((w[2i] >> 5) * 67108864.0 + (w[2i+1] >> 6)) / 9007199254740992.0, 0 <= i < count.  Every operation of the
+ *                conversion is exact in double: there is no rounding and no contraction question.
+ *   State after. count == 0: the state is unchanged, nothing is written and nothing is enqueued.  Otherwise, with tot = pos + 2 count and
+ *                k = (tot - 1) / 624 (integer division): key' = x[624k .. 624k + 623] and pos' = tot - 624k.  That is what numpy holds after
+ *                the same draws: the whole regenerated block, even when it is partly consumed (k == 0: the key as it was).
+ * Two calls of c1 and c2 draws are one call of c1 + c2.  Word n + 624 needs nothing newer than n + 397, so 227 consecutive words are independent
+ * and no more: a call is a chain of about 2 count / 227 dependent steps walked by ONE workgroup (there is no cheap jump-ahead, and none is
+ * built).  No atomics, no allocation inside, no engine needed, asynchronous on `stream`.
+ *
+ * ss_dither_rows: the contiguous stream gathered into the [B][max_n] layout ss_filtfilt takes as dither_dev.  draws_dev: float64 [count];
+ * first_dev: long [B] and n_dev: int [B], both ON THE DEVICE and read in stream order; out_dev: float64 [B][max_n].  Row b has
+ * n_b = min(max(n[b], 0), max_n) draws: out[b][i] = draws[first[b] + i] for i < n_b, and exact zeros behind n_b.  A first[b] outside
+ * [0, count - n_b] spoils that row only: it is clamped into [0, max(count - n_b, 0)], and a column whose draw would still lie at or beyond
+ * count (n_b above count) is zero, so nothing outside draws[0 .. count) is read.  All index arithmetic is in long.
+ *
+ * Refused before anything is enqueued, with a message that names the argument: null state_dev, draws_dev, first_dev, n_dev or out_dev
+ * (ss_mt19937_rand's out_dev may be NULL only when count == 0), count outside 0 .. 2^40, B outside 1 .. 65535, max_n < 1. */
+int  ss_mt19937_rand(unsigned* state_dev /* [625] in/out */, long count, double* out_dev /* [count] */, void* stream);
+int  ss_dither_rows(const double* draws_dev, long count, const long* first_dev, const int* n_dev, int B, int max_n,
+                    double* out_dev /* [B][max_n] */, void* stream);
 
 /* ---- Griffin-Lim vocoder: mel spectrograms back to waveforms (the checkpoint-free stand-in for demo.ipynb's WaveNet cell) ----
  * The inverse of ss_melspec's chain: mel [0, 1] -> amplitude 10^((100 mel - 100 + 16) / 20) -> linear magnitude through a CALLER-SUPPLIED

@@ -122,6 +122,8 @@ SYMBOLS = {
     'ss_resample_len': (_l, [_l, _i, _i]),
     'ss_resample_scratch_bytes': (_l, [_i, _i]),
     'ss_resample': (_i, [_vp, _ip, _i, _i, _i, _i, _vp, _i, _vp, _vp, _l, _vp]),
+    'ss_mt19937_rand': (_i, [_vp, _l, _vp, _vp]),
+    'ss_dither_rows': (_i, [_vp, _l, _vp, _ip, _i, _i, _vp, _vp]),
     'ss_griffinlim_samples': (_i, [_i]),
     'ss_griffinlim_scratch_bytes': (_l, [_i, _i]),
     'ss_mel_to_linear': (_i, [_fp, _vp, _ip, _i, _i, _i, _d, _vp, _vp]),

@@ -1,5 +1,5 @@
 // C entry points of the audio / data front end (include/speechsplit_amd.h): collation, mel spectrograms, F0 normalisation, the pitch
-// tracker, batched feature extraction, the resampler and the Griffin-Lim vocoder.  None of them takes an engine: each checks its arguments, refuses by
+// tracker, batched feature extraction, the resampler, numpy's MT19937 stream and the Griffin-Lim vocoder.  None of them takes an engine: each checks its arguments, refuses by
 // the argument's name through ss_last_error() and hands the rest to the launchers of kernels.h.
 #include <cmath>
 #include <cstdint>
@@ -206,6 +206,27 @@ int ss_resample(const double* x, const int* n, int B, int max_n, int up, int dow
     if (need > 0 && !scratch) return fail("ss_resample: null pointer: scratch_dev");
     if ((uintptr_t)scratch % 256) return fail("ss_resample: scratch_dev is not 256-byte aligned");
     HIPCHK(resample(x, n, B, max_n, up, down, h, n_taps, y, S(stream)));
+    return 0;
+}
+
+// ---- numpy's MT19937 stream and the dither gather (mtrand.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+int ss_mt19937_rand(unsigned* state, long count, double* out, void* stream) {
+    if (!state) return fail("ss_mt19937_rand: null pointer: state_dev");
+    if (count < 0 || count > MT_MAX_COUNT) return fail("ss_mt19937_rand: count outside 0 .. 2^40");
+    if (count > 0 && !out) return fail("ss_mt19937_rand: null pointer: out_dev (it may be NULL only when count is 0)");
+    HIPCHK(mt19937_rand(state, count, out, S(stream)));
+    return 0;
+}
+
+int ss_dither_rows(const double* draws, long count, const long* first, const int* n, int B, int max_n, double* out, void* stream) {
+    if (!draws) return fail("ss_dither_rows: null pointer: draws_dev");
+    if (!first) return fail("ss_dither_rows: null pointer: first_dev");
+    if (!n) return fail("ss_dither_rows: null pointer: n_dev");
+    if (!out) return fail("ss_dither_rows: null pointer: out_dev");
+    if (count < 0 || count > MT_MAX_COUNT) return fail("ss_dither_rows: count outside 0 .. 2^40");
+    if (B < 1 || B > FEAT_MAX_ROWS) return fail("ss_dither_rows: B outside 1 .. 65535");
+    if (max_n < 1) return fail("ss_dither_rows: max_n below 1");
+    HIPCHK(dither_rows(draws, count, first, n, B, max_n, out, S(stream)));
     return 0;
 }
 

@@ -270,6 +270,16 @@ long resample_len(long n, int up, int down);                 // ceil(n up / down
 long resample_scratch_bytes(int up, int n_taps);             // 0: the kernel reads h as it is given
 hipError_t resample(const double* x, const int* n, int B, int max_n, int up, int down, const double* h, int n_taps, double* y, hipStream_t s);
 
+// ---------------------------------------------------------------- mtrand.hip  (numpy.random.RandomState.rand to the bit: MT19937)
+// state u32[625] on the device, in/out: numpy's key [624], then pos (above 624 reads as 624).  out [count] float64: draw i is
+// ((w[2i] >> 5) 2^26 + (w[2i+1] >> 6)) / 2^53 of the tempered stream words w from pos on.  Afterwards the state is what numpy holds after the
+// same draws: the whole last regenerated block and pos' = pos + 2 count - 624 ((pos + 2 count - 1) / 624).  count == 0: nothing is enqueued.
+constexpr long MT_MAX_COUNT = 1L << 40;
+hipError_t mt19937_rand(unsigned* state, long count, double* out, hipStream_t s);
+// draws [count], first i64[B], n i32[B] (all device) -> out [B][max_n]: out[b][i] = draws[first[b] + i] for i < n_b = min(max(n[b], 0), max_n),
+// zeros behind; first[b] is clamped into [0, max(count - n_b, 0)] and nothing outside draws[0 .. count) is read
+hipError_t dither_rows(const double* draws, long count, const long* first, const int* n, int B, int max_n, double* out, hipStream_t s);
+
 // ---------------------------------------------------------------- vocoder.hip  (Griffin-Lim: mel -> linear magnitude -> waveform, float64)
 // Shapes: mel [B][max_frames][n_mels] f32, mag [B][max_frames][513], spec [B][max_frames][513][2] (re, im), wav [B][256 (max_frames - 1)].
 // frames (nullable; device i32[B]): row b has F_b = min(max(frames[b], 4), max_frames) frames and 256 (F_b - 1) samples; it is computed as if

@@ -8,7 +8,11 @@ csrc/pitch.hip through the C ABI).  `extract_batch` (a speaker's recordings at o
 and the dither DRAW stay on the host -- it is the speaker's numpy stream.  The recordings and their draws go to the device in one copy and
 run as ragged batches through ss_filtfilt (csrc/filtfilt.hip: scipy's filtfilt to the bit, then the scaling and dither), ss_melspec_batch (the
 vocoder's FFT in place of the direct DFT), ss_pitch_track and ss_f0_normalize_batch; one copy per batch brings the results back.  Its F0 is
-`extract`'s to the bit and its spectrogram within 1e-6.
+`extract`'s to the bit and its spectrogram within 1e-6.  With `device_draws=True` (a keyword of `extract_batch_sr` and
+`make_spect_f0_batched`; `extract_batch` and `make_spect_f0` keep their pinned argument lists) the draw runs on the device too: `rand_dev` (csrc/mtrand.hip)
+continues the speaker's generator -- numpy's MT19937 stream and its conversion to double, bit for bit -- for all the recordings' draws at once
+and hands the state back to prng; ss_dither_rows gathers each batch's rows out of that stream, and the upload carries the recordings only.
+The same numbers, so the same features; the default (False) makes exactly the host's calls.
 
 Sample rates.  The chain runs at 16 kHz, as the reference asserts (make_spect_f0.py:51).  Recordings at any other rate are brought there
 first by `resample` / `resample_dev` (csrc/resample.hip: scipy.signal.resample_poly with scipy's default filter, to the bit, on ragged
@@ -196,6 +200,44 @@ def f0_normalize_batch_dev(f0_dev, n_dev, max_n, unvoiced=0.0):
     return out
 
 
+def rand_dev(prng, count, device='cuda'):
+    """`prng.rand(count)` on the GPU (csrc/mtrand.hip: numpy's MT19937 stream, to the bit): a float64 device tensor [count], and prng left
+    exactly where prng.rand(count) would have left it.  The generator's key and pos go up (625 words), ss_mt19937_rand continues them, the 625
+    words come back and are put into prng with set_state; has_gauss and cached_gaussian are carried over unchanged.  prng must be a
+    numpy.random.RandomState on MT19937: anything else is a TypeError (a Generator or another bit generator is another stream)."""
+    if not isinstance(prng, np.random.RandomState):
+        raise TypeError(f'rand_dev: prng must be a numpy.random.RandomState, not {type(prng).__name__}')
+    st = prng.get_state(legacy=False)
+    if st.get('bit_generator') != 'MT19937':
+        raise TypeError(f"rand_dev: prng must run on MT19937, not {st.get('bit_generator')!r}")
+    count = int(count)
+    if count < 0:
+        raise ValueError(f'rand_dev: count must not be negative, not {count}')
+    out = torch.empty(count, dtype=torch.float64, device=device)
+    if count == 0:
+        return out
+    words = np.empty(625, dtype=np.uint32)
+    words[:624] = st['state']['key']
+    words[624] = st['state']['pos']
+    state = torch.from_numpy(words.view(np.int32)).to(device)
+    _capi.check(_capi.lib().ss_mt19937_rand(C.c_void_p(state.data_ptr()), count, C.c_void_p(out.data_ptr()),
+                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    words = state.cpu().numpy().view(np.uint32)
+    prng.set_state(('MT19937', words[:624].copy(), int(words[624]), int(st['has_gauss']), float(st['gauss'])))
+    return out
+
+
+def dither_rows_dev(draws_dev, first_dev, n_dev, max_n):
+    """The C call on device tensors: draws float64 [count], first int64 [B], n int32 [B] -> float64 [B, max_n]: row b holds
+    draws[first[b] : first[b] + n[b]], zeros behind -- the dither layout filtfilt_dev takes."""
+    B = first_dev.shape[0]
+    out = torch.empty(B, int(max_n), dtype=torch.float64, device=draws_dev.device)
+    _capi.check(_capi.lib().ss_dither_rows(C.c_void_p(draws_dev.data_ptr()), draws_dev.numel(), C.c_void_p(first_dev.data_ptr()),
+                                           C.c_void_p(n_dev.data_ptr()), B, int(max_n), C.c_void_p(out.data_ptr()),
+                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
 def rate_ratio(sr_in, sr_out=16000):
     """(up, down) of a conversion from sr_in to sr_out Hz, reduced as scipy.signal.resample_poly reduces them"""
     if int(sr_in) != sr_in or int(sr_out) != sr_out or sr_in < 1 or sr_out < 1:
@@ -354,11 +396,12 @@ def extract(x, prng, gender, device='cuda', mel_basis=None, unvoiced=0.0, sr=160
     return S.astype(np.float32), np.where(f0_rapt != -1e10, f0_norm, np.float32(unvoiced)).astype(np.float32)
 
 
-def stage_batches(xs, prng, max_rows):
+def stage_batches(xs, prng, max_rows, host_draws=True):
     """The host side of extract_batch: the odd-length fix (make_spect_f0.py:52-53) on every recording, the dither draws from the speaker's
     generator IN INPUT ORDER (so they do not depend on max_rows), then the plan_batches batches packed into one float64 buffer.  Returns
     (flat, lens, batches): batch k = (indices, offset, B, max_n) has its recordings at flat[offset : offset + B * max_n] as [B, max_n] (zeros
-    behind each row) and their draws in the B * max_n entries after that; lens int32 holds the batches' row lengths one after another."""
+    behind each row) and their draws in the B * max_n entries after that; lens int32 holds the batches' row lengths one after another.
+    host_draws=False (the draw on the device) makes no draw and leaves the draws' halves out: flat is half as long."""
     xs = [np.ascontiguousarray(x, dtype=np.float64) for x in xs]
     for i, x in enumerate(xs):
         if x.ndim != 1:
@@ -367,36 +410,62 @@ def stage_batches(xs, prng, max_rows):
             xs[i] = x = np.concatenate((x, np.array([1e-06])), axis=0)
         if x.shape[0] < MIN_SAMPLES:
             raise ValueError(f'extract_batch: recording {i} has {x.shape[0]} samples; every recording must be [n] with n >= {MIN_SAMPLES}')
-    draws = [prng.rand(x.shape[0]) for x in xs]
+    draws = [prng.rand(x.shape[0]) for x in xs] if host_draws else None
     plan = plan_batches([x.shape[0] for x in xs], max_rows)
     batches, off = [], 0
     for idx in plan:
         B, max_n = len(idx), xs[idx[-1]].shape[0]
         batches.append((idx, off, B, max_n))
-        off += 2 * B * max_n
+        off += (2 if host_draws else 1) * B * max_n
     flat = np.zeros(off)
     for idx, o, B, max_n in batches:
-        xb, rb = flat[o:o + B * max_n].reshape(B, max_n), flat[o + B * max_n:o + 2 * B * max_n].reshape(B, max_n)
+        xb = flat[o:o + B * max_n].reshape(B, max_n)
         for r, i in enumerate(idx):
             xb[r, :xs[i].shape[0]] = xs[i]
-            rb[r, :xs[i].shape[0]] = draws[i]
+        if host_draws:
+            rb = flat[o + B * max_n:o + 2 * B * max_n].reshape(B, max_n)
+            for r, i in enumerate(idx):
+                rb[r, :xs[i].shape[0]] = draws[i]
     lens = np.array([xs[i].shape[0] for idx, _, _, _ in batches for i in idx], dtype=np.int32)
     return flat, lens, batches
+
+
+def _draw_offsets(lens_in_order, batches):
+    """where each batch row's draws begin in one prng.rand(sum of the lengths): the prefix sums of the lengths IN INPUT ORDER, listed in the
+    batches' row order (int64, one after another as stage_batches lists the lengths)"""
+    start = np.concatenate(([0], np.cumsum(lens_in_order, dtype=np.int64)[:-1])) if len(lens_in_order) else np.zeros(0, np.int64)
+    return np.array([start[i] for idx in batches for i in idx], dtype=np.int64)
 
 
 def extract_batch(xs, prng, gender, max_rows=16, device='cuda', mel_basis=None, unvoiced=0.0):
     """`extract` for a speaker's recordings xs (a list of float64 [n] at 16 kHz) with the whole chain on the GPU: a list of (S, f0_norm), the
     same as calling `extract` on each recording in order with the same prng -- f0_norm to the bit, S within 1e-6 (an FFT in place of the direct
     DFT).  The recordings and their dither draws go up in one copy and run as ragged batches of at most max_rows rows in plan_batches order;
-    every row is the result of running it alone, so the result does not depend on max_rows.  One copy per batch brings S and f0_norm back."""
+    every row is the result of running it alone, so the result does not depend on max_rows.  One copy per batch brings S and f0_norm back.
+    (Its argument list is pinned; the draw on the device is `extract_batch_sr(xs, 16000, ..., device_draws=True)`.)"""
+    return _extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced, False)
+
+
+def _extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced, device_draws):
+    """extract_batch, with the draw on the host or (device_draws) on the GPU: one `rand_dev` for the sum of the (fixed-up) lengths in input
+    order -- the same numbers, and prng is left in the same state -- and one ss_dither_rows a batch hands each row its stretch; the upload
+    then carries the recordings only."""
     f0_range(gender)                                                    # an unknown gender stops the call before a draw is made
-    flat, lens, batches = stage_batches(xs, prng, max_rows)
+    flat, lens, batches = stage_batches(xs, prng, max_rows, **({'host_draws': False} if device_draws else {}))
     chain = _Chain(gender, device, mel_basis, unvoiced)
     flat_dev, lens_dev = torch.from_numpy(flat).to(device), torch.from_numpy(lens).to(device)
+    if device_draws:
+        own = np.zeros(len(xs), dtype=np.int64)                         # the fixed-up lengths in input order
+        own[[i for idx, _, _, _ in batches for i in idx]] = lens
+        draws = rand_dev(prng, int(own.sum()), device)
+        first_dev = torch.from_numpy(_draw_offsets(own, [idx for idx, _, _, _ in batches])).to(device)
     out, row = [None] * len(xs), 0
     for idx, o, B, max_n in batches:
         x = flat_dev[o:o + B * max_n].view(B, max_n)
-        r = flat_dev[o + B * max_n:o + 2 * B * max_n].view(B, max_n)
+        if device_draws:
+            r = dither_rows_dev(draws, first_dev[row:row + B], lens_dev[row:row + B], max_n)
+        else:
+            r = flat_dev[o + B * max_n:o + 2 * B * max_n].view(B, max_n)
         for i, feats in zip(idx, chain(x, r, lens_dev[row:row + B], lens[row:row + B])):
             out[i] = feats
         row += B
@@ -429,18 +498,22 @@ class _Chain:
         return out
 
 
-def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis=None, unvoiced=0.0):
+def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis=None, unvoiced=0.0, *, device_draws=False):
     """`extract_batch` for recordings at any sample rate: sr is one rate in Hz for all of xs, or one a recording.  The same as
     extract_batch([scipy.signal.resample_poly(x, 16000, sr) ...], prng, gender, ...), to the bit, with the resampling on the GPU in front of the
     chain and nothing brought back between them: the recordings are grouped by rate and each group runs through ss_resample as ragged batches in
     plan_batches order; the odd-length fix and the dither draws then apply to the RESAMPLED lengths -- ceil(n 16000 / sr), which the host knows
     without waiting for the device -- with the draws in input order; then extract_batch's four calls on batches of the resampled recordings.
-    With every rate 16000 this IS extract_batch: the same calls on the same data."""
+    With every rate 16000 this IS extract_batch: the same calls on the same data.  device_draws=True makes the dither draw on the GPU: one
+    `rand_dev` for the sum of the fixed-up (resampled) lengths in input order -- the same numbers, prng left in the same state -- and one
+    ss_dither_rows a batch; the default makes exactly the host's calls."""
     xs = [np.ascontiguousarray(x, dtype=np.float64) for x in xs]
     srs = [sr] * len(xs) if np.ndim(sr) == 0 else list(sr)
     if len(srs) != len(xs):
         raise ValueError(f'extract_batch_sr: {len(srs)} sample rates for {len(xs)} recordings')
     if all(s == 16000 for s in srs):
+        if device_draws:
+            return _extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced, True)
         return extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced)
     ratios = [rate_ratio(s, 16000) for s in srs]
     for i, x in enumerate(xs):
@@ -452,7 +525,12 @@ def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis
         if n < MIN_SAMPLES:
             raise ValueError(f'extract_batch_sr: recording {i} has {n} samples at 16 kHz; every recording must have n >= {MIN_SAMPLES}')
     f0_range(gender)
-    draws = [prng.rand(n) for n in lens]                                                   # input order, whatever the grouping
+    plan = plan_batches(lens, max_rows)
+    if device_draws:
+        draws = rand_dev(prng, sum(lens), device)                                          # input order, whatever the grouping
+        first_dev = torch.from_numpy(_draw_offsets(lens, plan)).to(device)
+    else:
+        draws = [prng.rand(n) for n in lens]                                               # input order, whatever the grouping
     wav16 = [None] * len(xs)                                                               # device tensors [own[i]]
     for ratio in sorted(set(ratios)):
         group = [i for i, q in enumerate(ratios) if q == ratio]
@@ -463,19 +541,23 @@ def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis
         for i, y in zip(group, ys):
             wav16[i] = y
     chain = _Chain(gender, device, mel_basis, unvoiced)
-    out = [None] * len(xs)
-    for idx in plan_batches(lens, max_rows):
+    out, row = [None] * len(xs), 0
+    for idx in plan:
         B, max_n = len(idx), lens[idx[-1]]
         x = torch.zeros(B, max_n, dtype=torch.float64, device=device)
-        rb = np.zeros((B, max_n))
+        rb = None if device_draws else np.zeros((B, max_n))
         for k, i in enumerate(idx):
             x[k, :own[i]] = wav16[i]
             if lens[i] > own[i]:
                 x[k, own[i]] = 1e-06
-            rb[k, :lens[i]] = draws[i]
+            if not device_draws:
+                rb[k, :lens[i]] = draws[i]
         rows = [lens[i] for i in idx]
-        for i, feats in zip(idx, chain(x, torch.from_numpy(rb).to(device), torch.tensor(rows, dtype=torch.int32, device=device), rows)):
+        n_dev = torch.tensor(rows, dtype=torch.int32, device=device)
+        r = dither_rows_dev(draws, first_dev[row:row + B], n_dev, max_n) if device_draws else torch.from_numpy(rb).to(device)
+        for i, feats in zip(idx, chain(x, r, n_dev, rows)):
             out[i] = feats
+        row += B
     return out
 
 
@@ -487,7 +569,26 @@ def make_spect_f0(root_dir='assets/wavs', target_dir='assets/spmel', target_dir_
     integer runs each speaker's files through `extract_batch` in batches of at most that many rows (the same F0 files, mel files within
     1e-6).  resample=False reads 16 kHz files only (`read_wav`, which refuses every other rate by name, as the reference asserts); True reads
     mono PCM of any rate and width (`read_audio`) and brings it to 16 kHz on the GPU first, writing the files the 16 kHz path writes for
-    scipy.signal.resample_poly(x, 16000, sr).  Returns the (speaker, name) pairs written."""
+    scipy.signal.resample_poly(x, 16000, sr).  Returns the (speaker, name) pairs written.  (Its argument list is pinned; the batched walk
+    with its further options is `make_spect_f0_batched`.)"""
+    return _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, False)
+
+
+def make_spect_f0_batched(root_dir='assets/wavs', target_dir='assets/spmel', target_dir_f0='assets/raptf0', spk2gen='assets/spk2gen.pkl',
+                          max_rows=16, *, device='cuda', resample=False, device_draws=False):
+    """`make_spect_f0(..., max_rows=max_rows)`, the walk through `extract_batch_sr`, with that path's own options by keyword.
+    device_draws=True draws each speaker's dither on the GPU (`rand_dev`: numpy's stream to the bit), so the files written are the same,
+    byte for byte.  Returns the (speaker, name) pairs written."""
+    if isinstance(max_rows, bool) or not isinstance(max_rows, int) or max_rows < 1:
+        raise ValueError(f'make_spect_f0_batched: max_rows must be a positive integer, not {max_rows!r}')
+    if not isinstance(device_draws, bool):
+        raise TypeError(f'make_spect_f0_batched: device_draws must be True or False, not {device_draws!r}')
+    return _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, device_draws)
+
+
+def _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, device_draws):
+    """make_spect_f0's walk; device_draws is handed to extract_batch_sr only when it is set, so that the default makes the earlier calls"""
+    more = {'device_draws': True} if device_draws else {}
     if not isinstance(resample, bool):
         raise TypeError(f'make_spect_f0: resample must be True or False, not {resample!r} (max_rows goes by keyword)')
     if not isinstance(spk2gen, dict):
@@ -507,7 +608,7 @@ def make_spect_f0(root_dir='assets/wavs', target_dir='assets/spmel', target_dir_
         if max_rows is not None:
             recs = [read(name) for name in names]
             feats = extract_batch_sr([x for x, _ in recs], [sr for _, sr in recs], prng, spk2gen[subdir], max_rows, device,
-                                     unvoiced=-1e10) if names else []
+                                     unvoiced=-1e10, **more) if names else []
         for k, name in enumerate(names):
             if max_rows is not None:
                 S, f0_norm = feats[k]
