@@ -164,6 +164,44 @@ int ss_g3_rhythm_ragged(ss_engine* e, const float* x_org_dev, const int* len_dev
 int ss_g6_forward_ragged(ss_engine* e, const float* x_org_dev, const float* f0_trg_dev, const int* len_dev, int B, int T, int training,
                          float* out_dev, void* stream);
 
+/* ---- codes: the encoders alone, and the decoder on codes the caller supplies (eval mode only; nothing to mirror beyond model.py:84-87,
+ *      194-229, 301-309: the reference only ever decodes what it has just encoded) ----
+ * The model's product is its bottleneck codes -- content (codes_x), rhythm (codes_r), pitch (codes_f0) -- plus the speaker row.  These four
+ * calls split an eval-mode forward at them, so that codes of different utterances can be recombined, edited, cached, or decoded for many
+ * speakers from one encode.  Asynchronous on `stream` like their neighbours.
+ *   - a code is dense, caller-owned fp32 [B, T / factor, 2 * dim_neck*]: cat(forward half of the encoder BLSTM's output sampled at the LAST
+ *     frame of each block of `factor` frames, backward half at the FIRST), exactly what model.py:223-227 and :84-87 return.  Factors and
+ *     widths: codes_x freq / dim_neck, codes_r freq_2 / dim_neck_2, codes_f0 freq_3 / dim_neck_3;
+ *   - encode runs the encoders of an eval-mode forward and nothing behind them: no decoder recurrence, decoder projection or head launch
+ *     (ss_profile counts none in SS_PROF_REC_FWD, SS_PROF_DEC_PROJ, SS_PROF_DEC_PROJ0, SS_PROF_HEAD).  One launch then writes every
+ *     requested code; any output pointer may be NULL (that code is not written), all NULL is an error.  The codes are the bytes the
+ *     forward's decoder-input assembly reads (ss_g3_encode's codes_r is ss_g3_rhythm's result bit for bit);
+ *   - decode assembles the decoder input from the caller's codes and speaker rows c_trg [B, dim_spk_emb] (up-sampling every code by its
+ *     factor, model.py:301-309 / 341-347), then runs the decoder BLSTM and the head exactly as the forward does, after the decoder's own
+ *     weight preparation and the parameter guard.  No conv block, GroupNorm or encoder recurrence launch (none in SS_PROF_CONV_FWD,
+ *     SS_PROF_GN, SS_PROF_ENC_REC).  decode(encode(x)) is bit-identical to the eval-mode forward of x at the same (B, T, len);
+ *   - B and T obey the rules of the eval-mode forwards: 1 <= B <= max_batch, T a multiple of every code factor, up to SS_MAX_EVAL_FRAMES,
+ *     plan within the bound workspace; ss_plan_bytes(e, B, T) is sufficient for both calls;
+ *   - len_dev != NULL is a ragged batch under the length rules of ss_g3_forward_ragged.  encode never uses input frames t >= len[b] and
+ *     writes exact zeros in code rows at or beyond len[b] / factor.  decode never reads code rows at or beyond len[b] / factor (they may
+ *     hold anything, NaN included) and its output frames t >= len[b] are exact zeros.  With every len[b] == T the result is bit-identical
+ *     to the dense call (len_dev == NULL);
+ *   - afterwards no forward is left to differentiate: ss_*_backward* is refused with the "backward without a preceding forward" error,
+ *     and the engine stays usable;
+ *   - refused with nothing enqueued, in a message that names the call: the wrong kind of engine, an engine that is not bound, a NULL
+ *     required pointer (every input, decode's out, all of encode's outputs), B or T outside the rules above. */
+int ss_g3_encode(ss_engine* e, const float* x_f0_dev, const float* x_org_dev, const int* len_dev /* NULL: dense */, int B, int T,
+                 float* codes_x_dev /* [B, T/freq, 2*dim_neck] or NULL */, float* codes_r_dev /* [B, T/freq_2, 2*dim_neck_2] or NULL */,
+                 float* codes_f0_dev /* [B, T/freq_3, 2*dim_neck_3] or NULL */, void* stream);
+int ss_g3_decode(ss_engine* e, const float* codes_x_dev, const float* codes_r_dev, const float* codes_f0_dev,
+                 const float* c_trg_dev /* [B, dim_spk_emb] */, const int* len_dev /* NULL: dense */, int B, int T,
+                 float* out_dev /* [B, T, dim_freq] */, void* stream);
+/* Generator_6: codes_r (Encoder_t, freq_2 / dim_neck_2) and codes_f0 (Encoder_6, freq_3 / dim_neck_3); out [B, T, dim_f0] logits */
+int ss_g6_encode(ss_engine* e, const float* x_org_dev, const float* f0_trg_dev, const int* len_dev, int B, int T, float* codes_r_dev,
+                 float* codes_f0_dev, void* stream);
+int ss_g6_decode(ss_engine* e, const float* codes_r_dev, const float* codes_f0_dev, const int* len_dev, int B, int T, float* out_dev,
+                 void* stream);
+
 /* ---- Solver.train step body (solver.py:157-172), fused: cat(mel,f0) -> InterpLnr -> quantize_f0 -> G -> mse(mean)
  *      -> backward -> Adam.  mel [B,T,80], f0 [B,T,1] (-1e10 = unvoiced), emb [B,82], len_org i32[B];
  *      scales/len_seg [4][B*7] (outer call first).  T must equal hp.max_len_pad (model.py:105,157).

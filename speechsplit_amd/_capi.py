@@ -62,6 +62,12 @@ SYMBOLS = {
     'ss_g3_rhythm_ragged': (_i, [_vp, _fp, _ip, _i, _i, _fp, _vp]),
     'ss_g6_forward_ragged': (_i, [_vp, _fp, _fp, _ip, _i, _i, _i, _fp, _vp]),
     'ss_g6_forward': (_i, [_vp, _fp, _fp, _fp, _ip, _i, _i, _i, _fp, _vp]),
+    # e, x_f0, x_org, len, B, T, codes_x, codes_r, codes_f0, stream / e, codes_x, codes_r, codes_f0, c_trg, len, B, T, out, stream
+    'ss_g3_encode': (_i, [_vp, _fp, _fp, _ip, _i, _i, _fp, _fp, _fp, _vp]),
+    'ss_g3_decode': (_i, [_vp, _fp, _fp, _fp, _fp, _ip, _i, _i, _fp, _vp]),
+    # e, x_org, f0_trg, len, B, T, codes_r, codes_f0, stream / e, codes_r, codes_f0, len, B, T, out, stream
+    'ss_g6_encode': (_i, [_vp, _fp, _fp, _ip, _i, _i, _fp, _fp, _vp]),
+    'ss_g6_decode': (_i, [_vp, _fp, _fp, _ip, _i, _i, _fp, _vp]),
     'ss_g6_backward': (_i, [_vp, _fp, _vp]),
     'ss_g6_backward_inputs': (_i, [_vp, _fp, _fp, _fp, _vp]),
     'ss_g3_train_step': (_i, [_vp, _fp, _fp, _fp, _ip, _fp, _ip, _i, _i, _f, _i, _fp, _vp]),

@@ -72,6 +72,44 @@ def demo_conversion(G, P, sbmt_i, sbmt_j, max_len_pad=192, device='cuda:0', cond
     return res
 
 
+def demo_conversion_codes(G, P, sbmt_i, sbmt_j, max_len_pad=192, device='cuda:0', conditions=CONDITIONS):
+    """demo_conversion through the codes: the same names and shapes, from ONE batch-2 encode and one decode of the recombined codes
+    instead of a forward (three encoders each) per condition.  In eval mode the content code depends on the mel columns alone, the pitch code
+    on the one-hot columns alone and the rhythm code on x_org alone (reference model.py:194-229), so the seven conditions hold only these
+    codes: row 0 of the encode is ([x_org | oh_org], x_org), row 1 is ([x_org | oh_con], x_trg)."""
+    T = conversion_frames((sbmt_i[2][2], sbmt_j[2][2]), max_len_pad)
+    x_org, oh_org, emb_org, len_org, uid_org = _prepare(sbmt_i, T, device)
+    x_trg, oh_trg, emb_trg, len_trg, _ = _prepare(sbmt_j, T, device)
+    oh_con, _ = convert_f0(P, x_org, oh_trg)
+    with torch.no_grad():
+        cx, cr, cf = G.encode(torch.cat((torch.cat((x_org, oh_org), -1), torch.cat((x_org, oh_con), -1))), torch.cat((x_org, x_trg)))
+        rh = torch.tensor([1 if 'R' in c else 0 for c in conditions], device=cx.device)
+        f0 = torch.tensor([1 if 'F' in c else 0 for c in conditions], device=cx.device)
+        emb = torch.cat([emb_trg if 'U' in c else emb_org for c in conditions])
+        out = G.decode(cx[:1].expand(len(conditions), -1, -1), cr[rh], cf[f0], emb)
+    res = []
+    for n, c in enumerate(conditions):
+        keep = len_trg if 'R' in c else len_org
+        res.append(('{}_{}_{}_{}'.format(sbmt_i[0], sbmt_j[0], uid_org, c), out[n, :keep, :].cpu().numpy()))
+    return res
+
+
+def convert_speakers(G, entry, embs, max_len_pad=192, device='cuda:0'):
+    """One utterance decoded for every speaker row of embs [N, dim_spk_emb] from a SINGLE encode: entry is a demo.pkl-style
+    ``[speaker, emb, (mel[L,80], f0[L], L, uid)]``; returns the mels as one device tensor [N, L, 80].  Row n equals
+    ``G(x_f0, x_org, embs[n:n+1])[0, :L]`` of the padded utterance; the N - 1 repeated runs of the three encoders are what is saved."""
+    T = conversion_frames((entry[2][2],), max_len_pad)
+    x_org, oh_org, _, length, _ = _prepare(entry, T, device)
+    embs = torch.as_tensor(embs, dtype=torch.float32).to(device)
+    if embs.dim() != 2 or embs.shape[0] < 1:
+        raise ValueError(f'convert_speakers: embs must be [N, dim_spk_emb] with N >= 1, got {tuple(embs.shape)}')
+    N = embs.shape[0]
+    with torch.no_grad():
+        cx, cr, cf = G.encode(torch.cat((x_org, oh_org), -1), x_org)
+        out = G.decode(cx.expand(N, -1, -1), cr.expand(N, -1, -1), cf.expand(N, -1, -1), embs)
+    return out[:, :length]
+
+
 def plan_batches(lengths, max_rows):
     """Batches for ragged forwards over utterances of the given lengths (host only): the indices sorted by length (ties in their given
     order) and cut into runs of at most max_rows.  Returns a list of index lists; every index appears exactly once, the batches come in

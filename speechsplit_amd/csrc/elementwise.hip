@@ -810,6 +810,98 @@ __global__ __launch_bounds__(256) void build_dec_in_compact_kernel(CodeSrcPack p
     }
 }
 
+// ---- codes in and out (ss_g3_encode / ss_g3_decode and the Generator_6 pair): pure data movement, columns fastest
+struct CodeOutPack {
+    CodeOut s[3];
+    int n;
+};
+
+// Every requested code from the encoder BLSTM output slabs in one launch: dst[b][blk] = cat(fwd half of frame blk * f + f - 1, bwd half of
+// frame blk * f) (model.py:84-87, 223-227), zeros for blk >= len[b] / f.  grid = (x, B, sources), block 256; a source whose halves are whole
+// float4s (H % 4 == 0, 16-byte aligned rows on both sides: CodeOut::vec) moves as float4, the others by the element (2H can be 2).
+template <bool RAG>
+__global__ __launch_bounds__(256) void export_codes_kernel(CodeOutPack p, const int* __restrict__ len, int T) {
+    const CodeOut c = p.s[blockIdx.z];
+    const int b = blockIdx.y;
+    const long TP = T + 2 * HALO;
+    const int W = 2 * c.H, nb = T / c.freq;
+    const int live = RAG ? ragged_len(len, b, T) / c.freq : nb;        // code rows of this utterance
+    const float* o = c.o + (long)b * TP * c.ld;
+    float* dst = c.dst + (long)b * nb * W;
+    if (c.vec) {
+        const int Q = W / 4, n = nb * Q;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+            const int blk = i / Q, cc = (i - blk * Q) * 4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (blk < live) {
+                const int ts = cc < c.H ? blk * c.freq + c.freq - 1 : blk * c.freq;
+                v = *reinterpret_cast<const float4*>(o + (long)(ts + HALO) * c.ld + cc);
+            }
+            *reinterpret_cast<float4*>(dst + (long)blk * W + cc) = v;
+        }
+        return;
+    }
+    const int n = nb * W;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const int blk = i / W, cc = i - blk * W;
+        float v = 0.f;
+        if (blk < live) {
+            const int ts = cc < c.H ? blk * c.freq + c.freq - 1 : blk * c.freq;
+            v = o[(long)(ts + HALO) * c.ld + cc];
+        }
+        dst[i] = v;
+    }
+}
+
+struct CodeInPack {
+    CodeIn s[3];
+    int n;
+};
+
+// column c of utterance b's decoder-input row at frame t, for dec_in_from_codes_kernel.  L: the utterance's frames (code rows at or beyond
+// L / f_i are not read: zero)
+__device__ __forceinline__ float dec_in_code_value(const CodeInPack& p, const float* __restrict__ emb, int emb_dim, int emb_col, int b, int t,
+                                                   int c, int T, int L) {
+    if (c >= emb_col && c < emb_col + emb_dim) return emb[(long)b * emb_dim + c - emb_col];      // c_trg broadcast over time (model.py:309)
+    for (int i = 0; i < p.n; ++i) {
+        const int W = 2 * p.s[i].H, col = p.s[i].col;
+        if (c >= col && c < col + W) {
+            const int f = p.s[i].freq, blk = t / f;
+            return blk < L / f ? p.s[i].p[((long)b * (T / f) + blk) * W + c - col] : 0.f;       // repeat_interleave(f) of the code
+        }
+    }
+    return 0.f;           // padding columns
+}
+
+// The decoder input from dense caller-owned codes [B, T / f_i, 2 H_i] and speaker rows [B, emb_dim], in the geometry of build_dec_in_kernel
+// (slab, rows == T, rstep == 1: [B, TP, ld], halo rows untouched) or of build_dec_in_compact_kernel (rows == T / f, rstep == f: xc
+// [B, T / f, ld]); padding columns written zero.  RAG: rows at or behind len[b] are zeros and their codes are not read.
+// grid = (rows, B), block 256.  VEC (ld % 4 == 0 and a 16-byte aligned base): each thread gathers four columns and stores one float4.
+template <bool RAG, bool VEC>
+__global__ __launch_bounds__(256) void dec_in_from_codes_kernel(CodeInPack p, const float* __restrict__ emb, int emb_dim, int emb_col,
+                                                                float* __restrict__ dst, int ld, int T, int rows, int rstep,
+                                                                int slab, const int* __restrict__ len) {
+    const int r = blockIdx.x, b = blockIdx.y;
+    const int t = r * rstep;
+    const int L = RAG ? ragged_len(len, b, T) : T;
+    const bool live = t < L;
+    float* row = slab ? dst + ((long)b * (T + 2 * HALO) + t + HALO) * ld : dst + ((long)b * rows + r) * ld;
+    if (VEC) {
+        for (int c = threadIdx.x * 4; c < ld; c += 256 * 4) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (live) {
+                v.x = dec_in_code_value(p, emb, emb_dim, emb_col, b, t, c, T, L);
+                v.y = dec_in_code_value(p, emb, emb_dim, emb_col, b, t, c + 1, T, L);
+                v.z = dec_in_code_value(p, emb, emb_dim, emb_col, b, t, c + 2, T, L);
+                v.w = dec_in_code_value(p, emb, emb_dim, emb_col, b, t, c + 3, T, L);
+            }
+            *reinterpret_cast<float4*>(row + c) = v;
+        }
+        return;
+    }
+    for (int c = threadIdx.x; c < ld; c += 256) row[c] = live ? dec_in_code_value(p, emb, emb_dim, emb_col, b, t, c, T, L) : 0.f;
+}
+
 // gradient of the same: d_xc [B][T / f][ld] already holds the sum over each block's frames.  grid = (T, B)
 __global__ __launch_bounds__(128) void dec_in_grad_compact_kernel(CodeSrcPack p, const float* __restrict__ d_xc, int ld, int T, int f) {
     const int t = blockIdx.x, b = blockIdx.y;
@@ -1232,6 +1324,44 @@ hipError_t build_dec_in_compact(const CodeSrc* src, int nsrc, const float* emb, 
     p.n = nsrc;
     for (int i = 0; i < nsrc; ++i) p.s[i] = src[i];
     hipLaunchKernelGGL(build_dec_in_compact_kernel, dim3(T / f, B), dim3(256), 0, s, p, emb, emb_dim, emb_col, xc, ld, T, f);
+    return hipGetLastError();
+}
+
+hipError_t export_codes(const CodeOut* out, int n, int B, int T, hipStream_t s, const int* len) {
+    if (n < 1 || n > 3 || B < 1 || T < 1) return hipErrorInvalidValue;
+    CodeOutPack p{};
+    p.n = n;
+    long most = 0;
+    for (int i = 0; i < n; ++i) {
+        CodeOut c = out[i];
+        if (!c.o || !c.dst || c.H < 1 || c.freq < 1 || T % c.freq || c.ld < 2 * c.H) return hipErrorInvalidValue;
+        c.vec = c.H % 4 == 0 && c.ld % 4 == 0 && ((uintptr_t)c.o | (uintptr_t)c.dst) % 16 == 0;
+        p.s[i] = c;
+        const long el = (long)(T / c.freq) * 2 * c.H / (c.vec ? 4 : 1);
+        if (el > most) most = el;
+    }
+    int gx = cdiv(most, 256);
+    if (gx > 64) gx = 64;
+    if (len) hipLaunchKernelGGL(export_codes_kernel<true>, dim3(gx, B, n), dim3(256), 0, s, p, len, T);
+    else hipLaunchKernelGGL(export_codes_kernel<false>, dim3(gx, B, n), dim3(256), 0, s, p, len, T);
+    return hipGetLastError();
+}
+
+hipError_t dec_in_from_codes(const CodeIn* src, int nsrc, const float* emb, int emb_dim, int emb_col, float* dst, int ld, int B, int T, int f,
+                             hipStream_t s, const int* len) {
+    if (nsrc < 1 || nsrc > 3 || f < 0 || (f && T % f) || B < 1 || T < 1 || !dst || (emb_dim && !emb) || emb_col + emb_dim > ld) return hipErrorInvalidValue;
+    CodeInPack p{};
+    p.n = nsrc;
+    for (int i = 0; i < nsrc; ++i) {
+        p.s[i] = src[i];
+        if (!src[i].p || src[i].H < 1 || src[i].freq < 1 || T % src[i].freq || src[i].col + 2 * src[i].H > ld) return hipErrorInvalidValue;
+        if (f && src[i].freq != f) return hipErrorInvalidValue;        // the compact form is one row per block of EVERY code
+    }
+    const int rows = f ? T / f : T, rstep = f ? f : 1, slab = f ? 0 : 1;
+    const bool vec = ld % 4 == 0 && (uintptr_t)dst % 16 == 0;
+    auto k = len ? (vec ? dec_in_from_codes_kernel<true, true> : dec_in_from_codes_kernel<true, false>)
+                 : (vec ? dec_in_from_codes_kernel<false, true> : dec_in_from_codes_kernel<false, false>);
+    hipLaunchKernelGGL(k, dim3(rows, B), dim3(256), 0, s, p, emb, emb_dim, emb_col, dst, ld, T, rows, rstep, slab, len);
     return hipGetLastError();
 }
 

@@ -1752,14 +1752,15 @@ int act_scales_all(ss_engine* e, hipStream_t s) {
 
 // ---- whole-model schedules ---------------------------------------------------------------------------------
 // The forward's branch-stream work that nobody needs before the trunk is through (see forward_core, which decides where it is enqueued)
-int forward_branch_work(ss_engine* e, const FusedForward& fused, const int* lens, hipStream_t b2) {
+// dec_prep: the decoder's weight re-layouts ride along (every forward; not ss_g*_encode, which runs nothing of the decoder)
+int forward_branch_work(ss_engine* e, const FusedForward& fused, const int* lens, hipStream_t b2, bool dec_prep) {
     PrepTable tb;
     tb.n = 0;
     tb.img_bf16 = e->img16();
     if (e->kind == SS_GENERATOR_3) CHK(lstm_prep(e, e->l1, tb, b2));
     CHK(lstm_prep(e, e->l2, tb, b2));
     CHK(lstm_prep(e, e->lt, tb, b2));
-    CHK(lstm_prep(e, e->ld, tb, b2));
+    if (dec_prep) CHK(lstm_prep(e, e->ld, tb, b2));
     HIPCHK(prep_run(tb, b2));
     if (fused.prezero) {     // nothing touches the gradient arena before the decoder backward; b2 is joined long before
         if (!fused.keep_grads) HIPCHK(hipMemsetAsync(e->G, 0, e->arena * 4, b2));
@@ -1784,13 +1785,12 @@ int forward_branch_work(ss_engine* e, const FusedForward& fused, const int* lens
     return 0;
 }
 
-// Encoder_7 (G3) / Encoder_6 (G6) trunk + their LSTMs, Encoder_t, decoder, head.  Inputs already in in_mel/in_f0/org/emb.
-// lens (nullable; eval mode only): per-row lengths of a ragged batch (device i32[B], caller-owned, read in stream order).  The staging
-// of the inputs has zeroed the padded frames; here every GroupNorm and every recurrence takes the lengths, everything else is row-wise.
-int forward_core(ss_engine* e, bool training, const float* scales, const int* len_seg, int draw0, hipStream_t s, const FusedForward& fused = {}, const int* lens = nullptr) {
+// The encoder part: everything up to the encoder BLSTMs' outputs, joined on `s` (plus, on the branch stream, the decoder's weight prep).
+// dec_prep = false: without the decoder's weight prep (ss_g3_encode / ss_g6_encode).
+int forward_encoders(ss_engine* e, bool training, const float* scales, const int* len_seg, int draw0, hipStream_t s, const FusedForward& fused, const int* lens,
+                     bool dec_prep = true) {
     const int B = e->curB, T = e->curT;
     e->part_off = 0;           // split-K scratch: every launch of a step gets its own region; the previous step is through (stream order) when this one's first kernel runs
-    const long TP = T + 2 * HALO;
     const int CE = e->CE;
     const bool g3 = e->kind == SS_GENERATOR_3;
     const int S7 = e->plan[0].S;
@@ -1845,7 +1845,7 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
         // Issue order matters: a cross-stream wait on ROCm holds for everything the other stream had been handed when
         // the WAIT was issued, not only up to the recorded event (measured: the trunk stalled ~250 us behind the tiny
         // launches of b2's work).  So: first trunk layer, and only then the rest of b2's work.
-        if (i == 1 && !prio_fwd) CHK(forward_branch_work(e, fused, lens, b2));
+        if (i == 1 && !prio_fwd) CHK(forward_branch_work(e, fused, lens, b2, dec_prep));
         if (indep) {
             const float* im = (e->fwd.xf_img_valid && i > 0) ? e->xf_img[i - 1] : nullptr;
             const Slab x1 = trunk_in(e, 1, i, im), x2 = trunk_in(e, 2, i, im);
@@ -1885,7 +1885,7 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
             HIPCHK(interp_gather(pl, Rows::slab(e->act, CE, T), Rows::slab(e->xf[i], CE, T), CE, B, s));
         }
     }
-    if (prio_fwd) CHK(forward_branch_work(e, fused, lens, b2));
+    if (prio_fwd) CHK(forward_branch_work(e, fused, lens, b2, dec_prep));
     if (par) {
         CHK(fork_join(e, b2, s));                  // bias sums of every block are ready (and Encoder_t is done)
         if (indep) CHK(fork_join(e, b2, b1));      // the pitch chain does not wait for the content chain
@@ -1894,13 +1894,33 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     CHK(lstm_fwd(e, e->l2, trunk_in(e, 2, 3), b1, lens));
     if (g3) CHK(lstm_fwd(e, e->l1, trunk_in(e, 1, 3), s, lens));
     if (par) CHK(fork_join(e, b1, s));
+    return 0;
+}
+
+// Codes and speaker rows a caller hands in (ss_g3_decode / ss_g6_decode) in place of the encoder slabs: dense fp32, [B, T / f_i, 2 H_i] in the
+// column order of code_srcs, c_trg [B, dim_spk_emb] (Generator_3)
+struct CallerCodes {
+    const float* codes[3];
+    const float* c_trg;
+};
+
+// The decoder part, on `s`: the decoder input (from the encoder slabs, or from `from`), the decoder BLSTM and the head.
+int forward_decoder(ss_engine* e, hipStream_t s, const int* lens, const CallerCodes* from = nullptr) {
+    const int B = e->curB, T = e->curT;
+    const long TP = T + 2 * HALO;
+    const bool g3 = e->kind == SS_GENERATOR_3;
     // decoder input (model.py:301-309 / 341-347)
     CodeSrc src[3];
     const int n = code_srcs(e, src);
     const ss_hparams& h = e->hp;
-    const float* emb = g3 ? e->emb : nullptr;       // Generator_3: the speaker embedding fills the columns behind the three codes
+    const float* emb = g3 ? (from ? from->c_trg : e->emb) : nullptr;       // Generator_3: the speaker embedding fills the columns behind the three codes
     const int emb_dim = g3 ? h.dim_spk_emb : 0, emb_col = g3 ? 2 * h.dim_neck + 2 * h.dim_neck_2 + 2 * h.dim_neck_3 : e->dec_in_dim;
-    if (dec_compact(e)) HIPCHK(build_dec_in_compact(src, n, emb, emb_dim, emb_col, e->ld.xc, e->dec_in_dim, B, T, e->ld.xf, s));
+    if (from) {
+        CodeIn in[3];
+        for (int i = 0; i < n; ++i) in[i] = {from->codes[i], src[i].H, src[i].freq, src[i].col};
+        if (dec_compact(e)) HIPCHK(dec_in_from_codes(in, n, emb, emb_dim, emb_col, e->ld.xc, e->dec_in_dim, B, T, e->ld.xf, s, lens));
+        else HIPCHK(dec_in_from_codes(in, n, emb, emb_dim, emb_col, e->dec_in, e->dec_in_dim, B, T, 0, s, lens));
+    } else if (dec_compact(e)) HIPCHK(build_dec_in_compact(src, n, emb, emb_dim, emb_col, e->ld.xc, e->dec_in_dim, B, T, e->ld.xf, s));
     else HIPCHK(build_dec_in(src, n, emb, emb_dim, emb_col, e->dec_in, e->dec_in_dim, B, T, s));
     CHK(lstm_fwd(e, e->ld, dec_x(e), s, lens));
     // LinearNorm head (model.py:253 / 277)
@@ -1920,6 +1940,15 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     d.ksplit = 1;
     flatten_rows(d, B, T);
     PGEMM_FWD_ON(SS_PROF_HEAD, d, s);
+    return 0;
+}
+
+// Encoder_7 (G3) / Encoder_6 (G6) trunk + their LSTMs, Encoder_t, decoder, head.  Inputs already in in_mel/in_f0/org/emb.
+// lens (nullable; eval mode only): per-row lengths of a ragged batch (device i32[B], caller-owned, read in stream order).  The staging
+// of the inputs has zeroed the padded frames; here every GroupNorm and every recurrence takes the lengths, everything else is row-wise.
+int forward_core(ss_engine* e, bool training, const float* scales, const int* len_seg, int draw0, hipStream_t s, const FusedForward& fused = {}, const int* lens = nullptr) {
+    CHK(forward_encoders(e, training, scales, len_seg, draw0, s, fused, lens));
+    CHK(forward_decoder(e, s, lens));
     e->fwd.training = training;
     e->fwd.enc_plan0 = draw0;
     e->fwd.ragged = lens != nullptr;
@@ -2702,6 +2731,97 @@ int ss_g3_rhythm_ragged(ss_engine* e, const float* x_org, const int* len_dev, in
     if (!e) return fail("ss_g3_rhythm_ragged: null engine");
     if (e->kind != SS_GENERATOR_3) return fail("ss_g3_rhythm_ragged on an engine that is not a Generator_3");
     return g3_rhythm(e, x_org, len_dev, B, T, codes, stream);
+}
+
+// ---- codes: the encoders alone, and the decoder on codes the caller supplies (eval mode only; see the header's "codes" section) ----
+// what every one of the four refuses before anything is enqueued; `call` names the entry point in the message
+static int codes_check(const ss_engine* e, int kind, const char* call, bool ptrs_ok, int B, int T) {
+    const std::string c(call);
+    if (!e) return fail(c + ": null engine");
+    if (e->kind != kind) return fail(c + " on an engine that is not a " + (kind == SS_GENERATOR_3 ? "Generator_3" : "Generator_6"));
+    if (!e->ws) return fail(c + ": engine is not bound (call ss_bind first)");
+    if (!ptrs_ok) return fail(c + ": null pointer (every input is required, and at least one output)");
+    if (B < 1 || B > e->maxB) return fail(c + ": batch outside 1 .. max_batch given to ss_create");
+    if (T < 1 || T > SS_MAX_EVAL_FRAMES) return fail(c + ": T outside 1 .. SS_MAX_EVAL_FRAMES (8192)");
+    if (T % e->hp.freq || T % e->hp.freq_2 || T % e->hp.freq_3) return fail(c + ": T must be a multiple of the code down-sampling factors (model.py:87,223-227)");
+    if (carve(*e, B, T) > e->ws_bytes) return fail(c + ": workspace too small for this batch / frames: grow it to ss_plan_bytes(B, T) with ss_set_workspace");
+    return 0;
+}
+
+// after the encoder part: every requested code (NULL: not wanted) in one launch, in the column order of code_srcs
+static int export_requested_codes(ss_engine* e, float* const* codes, int B, int T, hipStream_t s, const int* lens) {
+    CodeSrc src[3];
+    const int n = code_srcs(e, src);
+    CodeOut out[3];
+    int m = 0;
+    for (int i = 0; i < n; ++i)
+        if (codes[i]) out[m++] = {src[i].o, codes[i], src[i].H, src[i].freq, src[i].ld, 0};
+    HIPCHK(export_codes(out, m, B, T, s, lens));
+    return 0;
+}
+
+// the decoder on the caller's codes: its weight prep and the parameter guard as forward_branch_work runs them, then forward_decoder
+static int decode_codes(ss_engine* e, const CallerCodes& cc, const int* lens, int B, int T, float* out, void* stream) {
+    CHK(entry_check(e));
+    Own own(e, stream);
+    hipStream_t s = own.s;
+    CHK(geometry(e, B, T, s, true));
+    e->part_off = 0;
+    e->fwd.have = false;           // the decoder's slabs are overwritten: whatever forward ran before has no backward any more
+    PrepTable tb;
+    tb.n = 0;
+    tb.img_bf16 = e->img16();
+    CHK(lstm_prep(e, e->ld, tb, s));
+    HIPCHK(prep_run(tb, s));
+    if ((g_fwd_f16x2 || g_bwd_f16x2) && e->precision == SS_PRECISION_F32 && e->sticky) HIPCHK(param_guard(e->P, e->arena, 2048.0f, e->sticky, s));
+    CHK(forward_decoder(e, s, lens, &cc));
+    CHK(export_out(e, out, B, T, s, lens));
+    return 0;
+}
+
+int ss_g3_encode(ss_engine* e, const float* x_f0, const float* x_org, const int* len_dev, int B, int T, float* codes_x, float* codes_r,
+                 float* codes_f0, void* stream) {
+    CHK(codes_check(e, SS_GENERATOR_3, "ss_g3_encode", x_f0 && x_org && (codes_x || codes_r || codes_f0), B, T));
+    CHK(entry_check(e));
+    Own own(e, stream);
+    hipStream_t s = own.s;
+    CHK(geometry(e, B, T, s, true));
+    e->fwd.have = false;
+    const ss_hparams& h = e->hp;
+    const CRows x = CRows::dense(x_f0, h.dim_freq + h.dim_f0, T);          // as stage_g3_inputs, without the speaker rows
+    HIPCHK(copy_rows(x, Rows::slab(e->in_mel, h.dim_freq, T), B, T, h.dim_freq, s, len_dev));
+    HIPCHK(copy_rows(x.col(h.dim_freq), Rows::slab(e->in_f0, e->f0p, T), B, T, h.dim_f0, s, len_dev));
+    HIPCHK(copy_rows(CRows::dense(x_org, h.dim_freq, T), Rows::slab(e->org, h.dim_freq, T), B, T, h.dim_freq, s, len_dev));
+    CHK(forward_encoders(e, false, nullptr, nullptr, 0, s, {}, len_dev, false));
+    float* const codes[3] = {codes_x, codes_r, codes_f0};
+    return export_requested_codes(e, codes, B, T, s, len_dev);
+}
+
+int ss_g3_decode(ss_engine* e, const float* codes_x, const float* codes_r, const float* codes_f0, const float* c_trg, const int* len_dev, int B,
+                 int T, float* out, void* stream) {
+    CHK(codes_check(e, SS_GENERATOR_3, "ss_g3_decode", codes_x && codes_r && codes_f0 && c_trg && out, B, T));
+    return decode_codes(e, CallerCodes{{codes_x, codes_r, codes_f0}, c_trg}, len_dev, B, T, out, stream);
+}
+
+int ss_g6_encode(ss_engine* e, const float* x_org, const float* f0_trg, const int* len_dev, int B, int T, float* codes_r, float* codes_f0,
+                 void* stream) {
+    CHK(codes_check(e, SS_GENERATOR_6, "ss_g6_encode", x_org && f0_trg && (codes_r || codes_f0), B, T));
+    CHK(entry_check(e));
+    Own own(e, stream);
+    hipStream_t s = own.s;
+    CHK(geometry(e, B, T, s, true));
+    e->fwd.have = false;
+    const ss_hparams& h = e->hp;
+    HIPCHK(copy_rows(CRows::dense(x_org, h.dim_freq, T), Rows::slab(e->org, h.dim_freq, T), B, T, h.dim_freq, s, len_dev));
+    HIPCHK(copy_rows(CRows::dense(f0_trg, h.dim_f0, T), Rows::slab(e->in_f0, e->f0p, T), B, T, h.dim_f0, s, len_dev));
+    CHK(forward_encoders(e, false, nullptr, nullptr, 0, s, {}, len_dev, false));
+    float* const codes[3] = {codes_r, codes_f0, nullptr};
+    return export_requested_codes(e, codes, B, T, s, len_dev);
+}
+
+int ss_g6_decode(ss_engine* e, const float* codes_r, const float* codes_f0, const int* len_dev, int B, int T, float* out, void* stream) {
+    CHK(codes_check(e, SS_GENERATOR_6, "ss_g6_decode", codes_r && codes_f0 && out, B, T));
+    return decode_codes(e, CallerCodes{{codes_r, codes_f0, nullptr}, nullptr}, len_dev, B, T, out, stream);
 }
 
 static int g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, const float* scales, const int* len_seg, const int* lens, int B,

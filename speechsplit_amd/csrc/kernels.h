@@ -161,6 +161,25 @@ hipError_t dec_in_grad(const CodeSrc* src, int nsrc, const float* d_dec_in, int 
 hipError_t build_dec_in_compact(const CodeSrc* src, int nsrc, const float* emb, int emb_dim, int emb_col, float* xc, int ld, int B, int T,
                                 int f, hipStream_t s);
 hipError_t dec_in_grad_compact(const CodeSrc* src, int nsrc, const float* d_xc, int ld, int B, int T, int f, hipStream_t s);
+// ---- codes as caller-owned tensors (ss_g3_encode / ss_g3_decode / ss_g6_encode / ss_g6_decode): a code is dense fp32 [B, T / freq, 2H],
+//      cat(forward half at the last frame of each block, backward half at the first) (model.py:84-87, 223-227)
+struct CodeOut {          // one code to export from an encoder BLSTM's output slab
+    const float* o;       // [B, TP, ld], the 2*H real columns first
+    float* dst;           // [B, T / freq, 2H]
+    int H, freq, ld;
+    int vec;              // set by export_codes: the halves move as float4
+};
+// every code of the table in ONE launch (up to three); len (nullable, i32[B]): zeros in code rows at or beyond len[b] / freq
+hipError_t export_codes(const CodeOut* out, int n, int B, int T, hipStream_t s, const int* len = nullptr);
+struct CodeIn {           // one code feeding the decoder input
+    const float* p;       // [B, T / freq, 2H]
+    int H, freq, col;     // col: first column inside the decoder input
+};
+// The decoder input from codes and speaker rows emb [B, emb_dim] (emb_dim 0: none), in either form decoder layer 0 consumes: f == 0 the
+// slab dst [B, TP, ld] (halo rows untouched, as build_dec_in), f > 0 the compact dst [B, T / f, ld] (every code's freq == f, as
+// build_dec_in_compact).  Padding columns are written zero.  len (nullable): rows at or behind len[b] are zeros, their codes are not read.
+hipError_t dec_in_from_codes(const CodeIn* src, int nsrc, const float* emb, int emb_dim, int emb_col, float* dst, int ld, int B, int T, int f,
+                             hipStream_t s, const int* len = nullptr);
 
 // loss = mean((tgt - out)^2) over B*T*C real elements (solver.py:166); d_out = 2 (out - tgt) / N * scale
 hipError_t mse_loss(CRows out, CRows tgt, Rows d_out, int B, int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s);

@@ -248,6 +248,99 @@ class Engine:
         _capi.check(self.lib.ss_g3_rhythm(self.h, _ptr(x_org), B, T, _ptr(codes), _stream()))
         return codes
 
+    # ------------------------------------------------------------------ codes (eval mode only)
+    def code_shapes(self, B, T):
+        """{name: shape} of the dense codes of a (B, T) batch: 'x' (content, Generator_3 only), 'r' (rhythm), 'f0' (pitch)."""
+        hp = self.hp
+        s = {'r': (B, T // hp.freq_2, 2 * hp.dim_neck_2), 'f0': (B, T // hp.freq_3, 2 * hp.dim_neck_3)}
+        if self.kind == 'G3':
+            s['x'] = (B, T // hp.freq, 2 * hp.dim_neck)
+        return s
+
+    def _codes_call(self, B, T, lengths):
+        """What the four code calls share: lengths -> device i32[B], no forward left to differentiate, workspace reserved as g3_rhythm does."""
+        ln = self._lengths(lengths, B, T) if lengths is not None else None
+        self._fwd_bt = None
+        self._reserve_eval(B, T, False)
+        return ln
+
+    def _code_arg(self, name, t, shape):
+        t = self._f(t)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f'speechsplit_amd: {name} must have shape {tuple(shape)}, got {tuple(t.shape)}')
+        return t
+
+    def _want(self, want, names):
+        want = tuple(names) if want is None else tuple(want)
+        if not want or set(want) - set(names):
+            raise ValueError(f'speechsplit_amd: want must name at least one of {tuple(names)}, got {want}')
+        return want
+
+    def g3_encode(self, x_f0, x_org, lengths=None, want=None):
+        """The encoders of an eval-mode forward alone (ss_g3_encode) -> (codes_x, codes_r, codes_f0), dense [B, T / factor, 2 * dim_neck*].
+        want: names among ('x', 'r', 'f0') to compute the codes for (default all); the others come back as None.
+        lengths: a ragged batch; the code rows >= lengths[b] / factor of row b are zeros."""
+        B, T, _ = x_org.shape
+        want = self._want(want, ('x', 'r', 'f0'))
+        hp = self.hp
+        x_f0 = self._code_arg('x_f0', x_f0, (B, T, hp.dim_freq + hp.dim_f0))
+        x_org = self._code_arg('x_org', x_org, (B, T, hp.dim_freq))
+        ln = self._codes_call(B, T, lengths)
+        shp = self.code_shapes(B, T)
+        cx, cr, cf = (self._new('codes_' + n, shp[n]) if n in want else None for n in ('x', 'r', 'f0'))
+        _capi.check(self.lib.ss_g3_encode(self.h, _ptr(x_f0), _ptr(x_org), _ptr(ln), B, T, _ptr(cx), _ptr(cr), _ptr(cf), _stream()))
+        return cx, cr, cf
+
+    def g3_decode(self, codes_x, codes_r, codes_f0, c_trg, lengths=None):
+        """The decoder and head of an eval-mode forward on codes the caller supplies (ss_g3_decode) -> mel [B, T, dim_freq], T = freq_2 *
+        codes_r.shape[1].  c_trg: [B, dim_spk_emb], or one row for every utterance.  lengths: a ragged batch; code rows at or beyond
+        lengths[b] / factor are never read, output frames >= lengths[b] are zeros."""
+        hp = self.hp
+        if codes_r.dim() != 3:
+            raise ValueError(f'speechsplit_amd: codes_r must be [B, T / freq_2, 2 * dim_neck_2], got {tuple(codes_r.shape)}')
+        B, T = codes_r.shape[0], codes_r.shape[1] * hp.freq_2
+        if T % hp.freq or T % hp.freq_3:
+            raise ValueError(f'speechsplit_amd: codes_r implies T = {T}, which is not a multiple of the code factors {(hp.freq, hp.freq_2, hp.freq_3)}')
+        shp = self.code_shapes(B, T)
+        cx, cr, cf = (self._code_arg('codes_' + n, t, shp[n]) for n, t in (('x', codes_x), ('r', codes_r), ('f0', codes_f0)))
+        c_trg = self._f(c_trg)
+        if c_trg.dim() != 2 or c_trg.shape[1] != hp.dim_spk_emb or c_trg.shape[0] not in (1, B):
+            raise ValueError(f'speechsplit_amd: c_trg must be [{B} or 1, {hp.dim_spk_emb}], got {tuple(c_trg.shape)}')
+        if c_trg.shape[0] != B:
+            c_trg = c_trg.expand(B, -1).contiguous()
+        ln = self._codes_call(B, T, lengths)
+        out = self._new('out', (B, T, hp.dim_freq))
+        _capi.check(self.lib.ss_g3_decode(self.h, _ptr(cx), _ptr(cr), _ptr(cf), _ptr(c_trg), _ptr(ln), B, T, _ptr(out), _stream()))
+        return out
+
+    def g6_encode(self, x_org, f0_trg, lengths=None, want=None):
+        """Generator_6's encoders alone (ss_g6_encode) -> (codes_r, codes_f0); want, lengths as g3_encode with the names ('r', 'f0')."""
+        B, T, _ = x_org.shape
+        want = self._want(want, ('r', 'f0'))
+        hp = self.hp
+        x_org = self._code_arg('x_org', x_org, (B, T, hp.dim_freq))
+        f0_trg = self._code_arg('f0_trg', f0_trg, (B, T, hp.dim_f0))
+        ln = self._codes_call(B, T, lengths)
+        shp = self.code_shapes(B, T)
+        cr, cf = (self._new('codes_' + n, shp[n]) if n in want else None for n in ('r', 'f0'))
+        _capi.check(self.lib.ss_g6_encode(self.h, _ptr(x_org), _ptr(f0_trg), _ptr(ln), B, T, _ptr(cr), _ptr(cf), _stream()))
+        return cr, cf
+
+    def g6_decode(self, codes_r, codes_f0, lengths=None):
+        """Generator_6's decoder and head on the caller's codes (ss_g6_decode) -> logits [B, T, dim_f0]; lengths as g3_decode."""
+        hp = self.hp
+        if codes_r.dim() != 3:
+            raise ValueError(f'speechsplit_amd: codes_r must be [B, T / freq_2, 2 * dim_neck_2], got {tuple(codes_r.shape)}')
+        B, T = codes_r.shape[0], codes_r.shape[1] * hp.freq_2
+        if T % hp.freq or T % hp.freq_3:
+            raise ValueError(f'speechsplit_amd: codes_r implies T = {T}, which is not a multiple of the code factors {(hp.freq, hp.freq_2, hp.freq_3)}')
+        shp = self.code_shapes(B, T)
+        cr, cf = (self._code_arg('codes_' + n, t, shp[n]) for n, t in (('r', codes_r), ('f0', codes_f0)))
+        ln = self._codes_call(B, T, lengths)
+        out = self._new('out', (B, T, hp.dim_f0))
+        _capi.check(self.lib.ss_g6_decode(self.h, _ptr(cr), _ptr(cf), _ptr(ln), B, T, _ptr(out), _stream()))
+        return out
+
     def g3_train_step(self, mel, f0, emb, len_org, draws, grad_scale=1.0, no_adam=False, split_backward=False, bucket=False,
                       accumulate=False, split_no_join=False):
         """solver.py:160-172 fused.  split_backward: return after the decoder + head gradients (arena offsets >=

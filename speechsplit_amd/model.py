@@ -227,6 +227,19 @@ class _EngineModule(nn.Module):
             raise ValueError('speechsplit_amd: lengths (a ragged batch) are for eval mode only: call .eval() first')
         return lengths
 
+    def _codes_entry(self, call, tensors, lengths):
+        """What encode / decode check before they reach the engine: eval mode, a GPU, and no gradient asked of them (they are not
+        autograd-connected: their results carry no graph)."""
+        name = f'speechsplit_amd.{type(self).__name__}.{call}'
+        if self.training:
+            raise RuntimeError(f'{name} is eval-mode only (no resampling draws, no gradients): call .eval() first')
+        if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+            raise RuntimeError(f'{name} is not autograd-connected: an input requires grad; detach it or call under torch.no_grad()')
+        if not tensors[0].is_cuda:
+            raise RuntimeError(f'{name} runs on a ROCm GPU only: call .to("cuda") first')
+        self._ensure_engine(tensors[0].device, tensors[0].shape[0])
+        return lengths
+
     def extra_repr(self):
         return f'speechsplit_amd HIP engine ({self.KIND}), {sum(p.numel() for p in self._plist)} parameters'
 
@@ -251,6 +264,19 @@ class Generator_3(_EngineModule):
         self._ensure_engine(x_org.device, x_org.shape[0])
         return self._eng.g3_rhythm(x_org, lengths=lengths)
 
+    def encode(self, x_f0, x_org, lengths=None):
+        """The three bottleneck codes of an eval-mode forward (reference model.py:194-229, 84-87) without the decoder:
+        (codes_x [B, T/freq, 2*dim_neck], codes_2 [B, T/freq_2, 2*dim_neck_2], codes_f0 [B, T/freq_3, 2*dim_neck_3]).  Eval mode only, not
+        autograd-connected.  lengths: a ragged batch; code rows behind each row's end are zeros."""
+        lengths = self._codes_entry('encode', (x_org, x_f0), lengths)
+        return self._eng.g3_encode(x_f0, x_org, lengths=lengths)
+
+    def decode(self, codes_x, codes_2, codes_f0, c_trg, lengths=None):
+        """The decoder on codes the caller supplies (model.py:301-312): decode(*encode(x_f0, x_org), c_trg) is forward(x_f0, x_org, c_trg)
+        bit for bit; codes of different utterances may be mixed freely.  Eval mode only, not autograd-connected."""
+        lengths = self._codes_entry('decode', (codes_2, codes_x, codes_f0, c_trg), lengths)
+        return self._eng.g3_decode(codes_x, codes_2, codes_f0, c_trg, lengths=lengths)
+
 
 class Generator_6(_EngineModule):
     """F0 converter (reference model.py:324-351)."""
@@ -265,6 +291,17 @@ class Generator_6(_EngineModule):
         if draws is None:
             draws = self._draw(x_org.shape[0])
         return _G6Fn.apply(self, x_org, f0_trg, draws, lengths, *self._plist)
+
+    def encode(self, x_org, f0_trg, lengths=None):
+        """(codes_2 [B, T/freq_2, 2*dim_neck_2], codes_f0 [B, T/freq_3, 2*dim_neck_3]) of an eval-mode forward (model.py:337-347), as
+        Generator_3.encode."""
+        lengths = self._codes_entry('encode', (x_org, f0_trg), lengths)
+        return self._eng.g6_encode(x_org, f0_trg, lengths=lengths)
+
+    def decode(self, codes_2, codes_f0, lengths=None):
+        """The decoder on the caller's codes -> logits [B, T, dim_f0], as Generator_3.decode."""
+        lengths = self._codes_entry('decode', (codes_2, codes_f0), lengths)
+        return self._eng.g6_decode(codes_2, codes_f0, lengths=lengths)
 
 
 class _InterpFn(torch.autograd.Function):
