@@ -615,6 +615,56 @@ int ss_op_lstm_seq_bwd(float* gates_dev, const float* whh_f_dev, const float* wh
  * slabs and one arrival counter per tile; H in 1..32, hout rows 2H apart. */
 int ss_op_lstm_wgrad(const float* dg_dev, const float* x_dev, long x_ld, const float* hout_dev, float* gwih_dev, float* gwhh_dev, float* gb_dev,
                      float* scratch_dev, long scratch_floats, long R, int H, int In, void* stream);
+/* The GroupNorm + ReLU kernels (speechsplit_amd/csrc/elementwise.hip; 16 channels per group, eps 1e-5 inside the square root, biased variance
+ * over 16 x T) on the CALLER's haloed slabs, in every form the engine launches.  The hooks call the kernel launchers and nothing else: no
+ * convolution, no engine, no copy into private slabs.  A slab pointer is slab row 0: frame t of utterance b is row t + 2, at
+ * p + b * bs + (t + 2) * ld floats, with ld >= C, ld % 4 == 0, bs % 4 == 0 and a 16-byte aligned base -- so a block inside a wider slab is
+ * its first column with the slab's strides.  The two halo rows on either side of an INPUT slab (x, and dy without the scatter form) are zero;
+ * the halo rows of the outputs y (plain and ragged form) and dy are neither read nor written.  gamma / beta [C] 16-byte aligned,
+ * stats [B][C/16][2] = (mean, rstd) per group, C % 64 == 0, B >= 1, T >= 1.  Every optional pointer may be NULL (option off).
+ * Refused before anything is enqueued, each with its own ss_last_error text: a null pointer, C % 64 != 0, T < 1, T > 256 with a backward, a
+ * mask, a gather or a scatter, T > SS_MAX_EVAL_FRAMES, a short or misaligned scratch, a stride or base that breaks the rules above, an
+ * incomplete plan, P outside 1 .. 258, and an image that is misplaced (y_ld % 8, y_bs % 8, base alignment) -- the launcher would drop such
+ * an image silently; the hook never returns success without the image it was asked for.
+ *   ss_op_gn_relu_scratch  bytes of scratch ss_op_gn_relu_fwd needs: 0 for T <= 256, else 2 * B * (C/16) * ceil(T/64) float64 words (8-byte aligned).
+ *   ss_op_gn_relu_fwd
+ *     plain form     y rows [2, 2 + T) = relu(gamma * (x - mean) * rstd + beta), stats written.  T <= 256: one register-resident launch;
+ *                    T > 256: three chunked launches with float64 partial sums in scratch_dev.
+ *     len_dev        i32[B], the ragged form: the statistics of row b run over its L = min(max(len[b], 0), T) frames, x rows t >= L are never
+ *                    read (they may hold NaN), y rows t >= L are zeros.  A row with len[b] == 0 gives zeros in y and disturbs no other row;
+ *                    its stats entries are then NaN (0 * inf: the mean of no frames) -- harmless, eval mode has no backward.
+ *     i0_dev, lam_dev [B][P], nrows_dev [B], P
+ *                    the gather form (T <= 256; excludes len_dev): y is the RESAMPLED output, P real rows at y rows [2, 2 + P), row r <
+ *                    nrows[b] = (1 - lam[r]) * act[i0[r]] + lam[r] * act[i0[r] + 1] (three roundings; act row T reads as zeros), rows r >=
+ *                    nrows[b] zeros; the normalised slab itself is not written.  stats as the plain form's, bit for bit.
+ *     y_img_dev      (gather form only) the image of y, in the geometry of the y slab (real rows only): img_bf16 == 0 format v2 split with
+ *                    *img_scale_dev (NULL: 16), base 32-byte aligned; img_bf16 != 0 the plain bf16 tensor (2 bytes per element, round to
+ *                    nearest even), base 16-byte aligned.  Both need y_ld % 8 == 0 and y_bs % 8 == 0.
+ *   ss_op_gn_relu_mask     mask [B][T][C] dense = 1.0f where the GroupNorm output z > 0, from x and stats (the branch every kernel here takes).
+ *   ss_op_gn_relu_bwd      T <= 256.  dy (gradient of the ReLU output) is replaced in place, real rows only, by the gradient of x; the sums over
+ *                    utterances and time of d_gamma, d_beta and d_x are ADDED to g_gamma_dev, g_beta_dev, g_bias_dev [C] (f32 atomics).
+ *     amax_dev       one word: receives max |dx| by an atomic max on the float's bit pattern, so it only ever grows: zero it first.
+ *     part_dev       [B][3][C] floats of scratch, used only under ss_tune("deterministic", 1) (ignored otherwise, as in the launcher): the
+ *                    per-utterance sums go there and are added to the accumulators in utterance order, so that repeats agree in every bit.
+ *     lam_dev [B][P], start_dev [B][T+1], P, src_dev, src_ld, src_bs
+ *                    the scatter form: dy on entry is NOT read; the gradient of the ReLU output is the adjoint of the gather taken from src,
+ *                    the gradient of the resampled output (a slab of P real rows, as the gather form's y):
+ *                    dy[t] = sum_{i0[r] == t} (1 - lam[r]) src[r] + sum_{i0[r] == t - 1} lam[r] src[r] over r < nrows.
+ *     dy_img_dev     dx once more as a plain bf16 tensor of the dy slab's geometry (real rows only; round to nearest even), base 8-byte
+ *                    aligned, dy_ld % 8 == 0 and dy_bs % 8 == 0.
+ * PLAN CONTRACT.  Plans are device-resident: the hooks cannot validate their contents, the caller must.  0 <= i0[b][r] < T and i0 non-decreasing
+ * in r for r < nrows[b]; 0 <= nrows[b] <= P <= 258; start[b][i] = number of rows r < nrows[b] with i0[b][r] < i, for i in 0 .. T (so it is
+ * non-decreasing and start[b][T] = nrows[b] <= P), as csrc/interp.hip defines it.  The Python wrappers assert this on the host. */
+long ss_op_gn_relu_scratch(int B, int T, int C);
+int ss_op_gn_relu_fwd(const float* x_dev, long x_ld, long x_bs, float* y_dev, long y_ld, long y_bs, const float* gamma_dev, const float* beta_dev,
+                      float* stats_dev, const int* len_dev, const int* i0_dev, const float* lam_dev, const int* nrows_dev, int P, float* y_img_dev,
+                      const float* img_scale_dev, int img_bf16, void* scratch_dev, long scratch_bytes, int B, int T, int C, void* stream);
+int ss_op_gn_relu_mask(const float* x_dev, long x_ld, long x_bs, const float* gamma_dev, const float* beta_dev, const float* stats_dev,
+                       float* mask_dev, int B, int T, int C, void* stream);
+int ss_op_gn_relu_bwd(const float* x_dev, long x_ld, long x_bs, float* dy_dev, long dy_ld, long dy_bs, const float* gamma_dev, const float* beta_dev,
+                      const float* stats_dev, float* g_gamma_dev, float* g_beta_dev, float* g_bias_dev, float* amax_dev, float* part_dev,
+                      const float* lam_dev, const int* start_dev, int P, const float* src_dev, long src_ld, long src_bs, float* dy_img_dev, int B,
+                      int T, int C, void* stream);
 /* The GEMM over operand images (speechsplit_amd/csrc/gemm_img.hip), the engine's default for every large contraction: an IMAGE has the
  * geometry of its fp32 matrix (4 bytes per element) with every aligned group of 8 elements along the contiguous axis replaced by 16 bytes of
  * hi pieces and 16 bytes of lo pieces of the fp16 x 2 split of scale * x (scale a power of two).

@@ -105,6 +105,13 @@ SYMBOLS = {
     # gates, whh_f, whh_b, d_out, csave, scratch, floats, amax, gbias_f, gbias_b, dgs, xf, dimg, img_only, hi_only, B, T, H, stream
     'ss_op_lstm_seq_bwd': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _l, _fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _i, _vp]),
     'ss_op_lstm_wgrad': (_i, [_fp, _fp, _l, _fp, _fp, _fp, _fp, _fp, _l, _l, _i, _i, _vp]),
+    'ss_op_gn_relu_scratch': (_l, [_i, _i, _i]),
+    # x, x_ld, x_bs, y, y_ld, y_bs, gamma, beta, stats, len, i0, lam, nrows, P, y_img, img_scale, img_bf16, scratch, bytes, B, T, C, stream
+    'ss_op_gn_relu_fwd': (_i, [_fp, _l, _l, _fp, _l, _l, _fp, _fp, _fp, _ip, _ip, _fp, _ip, _i, _fp, _fp, _i, _vp, _l, _i, _i, _i, _vp]),
+    # x, x_ld, x_bs, gamma, beta, stats, mask, B, T, C, stream
+    'ss_op_gn_relu_mask': (_i, [_fp, _l, _l, _fp, _fp, _fp, _fp, _i, _i, _i, _vp]),
+    # x, x_ld, x_bs, dy, dy_ld, dy_bs, gamma, beta, stats, g_gamma, g_beta, g_bias, amax, part, lam, start, P, src, src_ld, src_bs, dy_img, B, T, C, stream
+    'ss_op_gn_relu_bwd': (_i, [_fp, _l, _l, _fp, _l, _l, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _ip, _i, _fp, _l, _l, _fp, _i, _i, _i, _vp]),
     'ss_op_split_image': (_i, [_fp, _l, _l, _i, _f, _fp, _l, _vp]),
     'ss_op_gemm_pre': (_i, [_fp, _l, _fp, _fp, _l, _fp, _fp, _l, _fp, _i, _i, _i, _i, _i, _vp]),
     'ss_op_gemm_img': (_i, [_fp, _l, _fp, _l, _fp, _l, _fp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _l, _fp, _vp, _vp]),

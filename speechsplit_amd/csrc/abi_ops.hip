@@ -411,4 +411,118 @@ int ss_op_lstm_wgrad(const float* dg, const float* x, long x_ld, const float* ho
     return 0;
 }
 
+// The GroupNorm + ReLU family (elementwise.hip) on the CALLER's haloed slabs, every form and option the engine launches: the hooks call the
+// launchers of kernels.h and nothing else -- no convolution, no engine, no copy.  Whatever a launcher would refuse, silently drop (the image
+// of gn_relu_gather) or leave to its caller is refused here before anything is enqueued.
+static const char* gn_rows_bad(const float* p, long ld, long bs, int C) {
+    if (ld < C) return "row stride below C";
+    if (ld % 4 || bs % 4) return "row / batch stride is not a multiple of 4 floats";
+    if (misaligned(p, 16)) return "base is not 16-byte aligned";
+    return nullptr;
+}
+#define GN_ROWS(who, name, p, ld, bs)                                                                    \
+    if (const char* _m = gn_rows_bad(p, ld, bs, C)) return fail(std::string(who) + ": " + name + ": " + _m)
+
+long ss_op_gn_relu_scratch(int B, int T, int C) {
+    if (B < 1 || T < 1 || C < 64 || C % 64) return 0;
+    return gn_relu_fwd_scratch_bytes(B, T, C);
+}
+
+int ss_op_gn_relu_fwd(const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs, const float* gamma, const float* beta, float* stats,
+                      const int* len, const int* i0, const float* lam, const int* nrows, int P, float* y_img, const float* img_scale, int img_bf16,
+                      void* scratch, long scratch_bytes, int B, int T, int C, void* stream) {
+    const char* who = "ss_op_gn_relu_fwd";
+    if (!x || !y || !gamma || !beta || !stats) return fail("ss_op_gn_relu_fwd: null pointer");
+    if (B < 1 || T < 1) return fail("ss_op_gn_relu_fwd: needs B >= 1 and T >= 1");
+    if (C < 64 || C % 64) return fail("ss_op_gn_relu_fwd: needs C % 64 == 0");
+    if (T > SS_MAX_EVAL_FRAMES) return fail("ss_op_gn_relu_fwd: T above SS_MAX_EVAL_FRAMES (8192)");
+    const bool gather = i0 || lam || nrows;
+    if (gather && !(i0 && lam && nrows)) return fail("ss_op_gn_relu_fwd: the gather form needs i0_dev, lam_dev and nrows_dev");
+    if (gather && (P < 1 || P > 258)) return fail("ss_op_gn_relu_fwd: the gather form needs 1 <= P <= 258");
+    if (gather && T > 256) return fail("ss_op_gn_relu_fwd: T > 256 runs the plain and ragged forms only (no gather)");
+    if (gather && len) return fail("ss_op_gn_relu_fwd: len_dev and a plan exclude each other");
+    if (y_img && !gather) return fail("ss_op_gn_relu_fwd: y_img_dev without a plan (only the gather form writes an image)");
+    GN_ROWS(who, "x", x, x_ld, x_bs);
+    GN_ROWS(who, "y", y, y_ld, y_bs);
+    if (misaligned(gamma, 16) || misaligned(beta, 16) || misaligned(stats, 4) || misaligned(len, 4) || misaligned(i0, 4) || misaligned(lam, 4) ||
+        misaligned(nrows, 4) || misaligned(img_scale, 4))
+        return fail("ss_op_gn_relu_fwd: gamma_dev / beta_dev are not 16-byte aligned, or a word array is not 4-byte aligned");
+    if (y_img) {
+        if (y_ld % 8 || y_bs % 8) return fail("ss_op_gn_relu_fwd: y_img_dev needs y_ld % 8 == 0 and y_bs % 8 == 0");
+        if (!img_bf16 && misaligned(y_img, 32)) return fail("ss_op_gn_relu_fwd: y_img_dev (format v2) is not 32-byte aligned");
+        if (img_bf16 && misaligned(y_img, 16)) return fail("ss_op_gn_relu_fwd: y_img_dev (bf16) is not 16-byte aligned");
+    }
+    if (gather) {
+        InterpPlan p{};
+        p.P = P;
+        p.T = T;
+        p.i0 = const_cast<int*>(i0);
+        p.lam = const_cast<float*>(lam);
+        p.nrows = const_cast<int*>(nrows);
+        GnGather o{};
+        o.y_img = y_img ? reinterpret_cast<float*>(reinterpret_cast<char*>(y_img) + (long)HALO * y_ld * (img_bf16 ? 2 : 4)) : nullptr;
+        o.img_scale = img_scale;
+        o.img_bf16 = y_img && img_bf16;
+        HIPCHK(gn_relu_gather(CRows{x + HALO * x_ld, x_ld, x_bs}, Rows{y + HALO * y_ld, y_ld, y_bs}, gamma, beta, stats, p, B, T, C, S(stream), o));
+        return 0;
+    }
+    const long need = gn_relu_fwd_scratch_bytes(B, T, C);
+    if (need && (!scratch || scratch_bytes < need)) return fail("ss_op_gn_relu_fwd: scratch too small (ss_op_gn_relu_scratch)");
+    if (need && misaligned(scratch, 8)) return fail("ss_op_gn_relu_fwd: scratch_dev is not 8-byte aligned");
+    HIPCHK(gn_relu_fwd(CRows{x + HALO * x_ld, x_ld, x_bs}, Rows{y + HALO * y_ld, y_ld, y_bs}, gamma, beta, stats, B, T, C, S(stream),
+                       need ? static_cast<double*>(scratch) : nullptr, len));
+    return 0;
+}
+
+int ss_op_gn_relu_mask(const float* x, long x_ld, long x_bs, const float* gamma, const float* beta, const float* stats, float* mask, int B, int T,
+                       int C, void* stream) {
+    if (!x || !gamma || !beta || !stats || !mask) return fail("ss_op_gn_relu_mask: null pointer");
+    if (B < 1 || T < 1) return fail("ss_op_gn_relu_mask: needs B >= 1 and T >= 1");
+    if (C < 64 || C % 64) return fail("ss_op_gn_relu_mask: needs C % 64 == 0");
+    if (T > 256) return fail("ss_op_gn_relu_mask: T > 256 has no backward and no mask");
+    GN_ROWS("ss_op_gn_relu_mask", "x", x, x_ld, x_bs);
+    if (misaligned(gamma, 4) || misaligned(beta, 4) || misaligned(stats, 4) || misaligned(mask, 4))
+        return fail("ss_op_gn_relu_mask: an operand is not 4-byte aligned");
+    HIPCHK(gn_relu_mask(CRows{x + HALO * x_ld, x_ld, x_bs}, gamma, beta, stats, mask, B, T, C, S(stream)));
+    return 0;
+}
+
+int ss_op_gn_relu_bwd(const float* x, long x_ld, long x_bs, float* dy, long dy_ld, long dy_bs, const float* gamma, const float* beta,
+                      const float* stats, float* g_gamma, float* g_beta, float* g_bias, float* amax, float* part, const float* lam, const int* start,
+                      int P, const float* src, long src_ld, long src_bs, float* dy_img, int B, int T, int C, void* stream) {
+    const char* who = "ss_op_gn_relu_bwd";
+    if (!x || !dy || !gamma || !beta || !stats || !g_gamma || !g_beta || !g_bias) return fail("ss_op_gn_relu_bwd: null pointer");
+    if (B < 1 || T < 1) return fail("ss_op_gn_relu_bwd: needs B >= 1 and T >= 1");
+    if (C < 64 || C % 64) return fail("ss_op_gn_relu_bwd: needs C % 64 == 0");
+    if (T > 256) return fail("ss_op_gn_relu_bwd: T > 256 has no backward");
+    const bool scatter = lam || start || src;
+    if (scatter && !(lam && start && src)) return fail("ss_op_gn_relu_bwd: the scatter form needs lam_dev, start_dev and src_dev");
+    if (scatter && (P < 1 || P > 258)) return fail("ss_op_gn_relu_bwd: the scatter form needs 1 <= P <= 258");
+    GN_ROWS(who, "x", x, x_ld, x_bs);
+    GN_ROWS(who, "dy", dy, dy_ld, dy_bs);
+    if (scatter) GN_ROWS(who, "src", src, src_ld, src_bs);
+    if (misaligned(gamma, 16) || misaligned(beta, 16) || misaligned(stats, 4) || misaligned(g_gamma, 4) || misaligned(g_beta, 4) ||
+        misaligned(g_bias, 4) || misaligned(amax, 4) || misaligned(part, 4) || misaligned(lam, 4) || misaligned(start, 4))
+        return fail("ss_op_gn_relu_bwd: gamma_dev / beta_dev are not 16-byte aligned, or a word array is not 4-byte aligned");
+    if (dy_img && (dy_ld % 8 || dy_bs % 8)) return fail("ss_op_gn_relu_bwd: dy_img_dev needs dy_ld % 8 == 0 and dy_bs % 8 == 0");
+    if (dy_img && misaligned(dy_img, 8)) return fail("ss_op_gn_relu_bwd: dy_img_dev (bf16) is not 8-byte aligned");
+    InterpPlan p{};
+    p.P = P;
+    p.T = T;
+    p.lam = const_cast<float*>(lam);
+    p.start = const_cast<int*>(start);
+    GnBwd o{};
+    o.amax = amax;
+    o.part = part;
+    if (scatter) {
+        o.scatter = &p;
+        o.src = CRows{src + HALO * src_ld, src_ld, src_bs};
+    }
+    o.dy_img = dy_img;
+    HIPCHK(gn_relu_bwd(CRows{x + HALO * x_ld, x_ld, x_bs}, Rows{dy + HALO * dy_ld, dy_ld, dy_bs}, gamma, beta, stats, g_gamma, g_beta, g_bias, B, T, C,
+                       S(stream), o));
+    return 0;
+}
+#undef GN_ROWS
+
 }  // extern "C"

@@ -769,6 +769,129 @@ def conv_block(x, w, bias, gamma, beta, dy=None, need_dx=True, scratch=None, out
     return y, dx, gw, gb, gg, gbe
 
 
+def check_gn_plan(T, P, i0=None, lam=None, nrows=None, start=None):
+    """The plan contract of ss_op_gn_relu_fwd / _bwd (include/speechsplit_amd.h), asserted on the HOST before a launch -- the hooks cannot see
+    the contents of a device-resident plan, and a plan outside the contract would make the kernels index outside their tiles.  Raises
+    ValueError.  (Test hooks: the device-to-host copy this takes is of no concern.)"""
+    if not 1 <= P <= 258:
+        raise ValueError(f'speechsplit_amd: plan: P = {P} outside 1 .. 258')
+    B = None
+    for name, t, shape_tail, dt in (('i0', i0, (P,), torch.int32), ('lam', lam, (P,), torch.float32), ('nrows', nrows, (), torch.int32),
+                                    ('start', start, (T + 1,), torch.int32)):
+        if t is None:
+            continue
+        if t.dtype != dt or not t.is_contiguous() or tuple(t.shape[1:]) != shape_tail or (B is not None and t.shape[0] != B):
+            raise ValueError(f'speechsplit_amd: plan: {name} must be a contiguous {dt} tensor [B{"".join(f", {s}" for s in shape_tail)}]')
+        B = t.shape[0]
+    if nrows is not None:
+        n = nrows.cpu().numpy()
+        if (n < 0).any() or (n > P).any():
+            raise ValueError('speechsplit_amd: plan: nrows outside 0 .. P')
+        if i0 is not None:
+            h = i0.cpu().numpy()
+            for b in range(B):
+                live = h[b, :n[b]]
+                if live.size and (live.min() < 0 or live.max() >= T or (np.diff(live) < 0).any()):
+                    raise ValueError(f'speechsplit_amd: plan: i0[{b}] leaves 0 .. T - 1 or decreases within its live rows')
+    if lam is not None and not bool(torch.isfinite(lam).all()):
+        raise ValueError('speechsplit_amd: plan: lam is not finite')
+    if start is not None:
+        s = start.cpu().numpy()
+        if (s < 0).any() or (s > P).any() or (np.diff(s, axis=1) < 0).any() or (s[:, 0] != 0).any():
+            raise ValueError('speechsplit_amd: plan: start must rise from 0 and stay within 0 .. P')
+        if nrows is not None and (s[:, T] != nrows.cpu().numpy()).any():
+            raise ValueError('speechsplit_amd: plan: start[b][T] != nrows[b]')
+    return B
+
+
+def gn_plan_start(i0, nrows, T):
+    """start [B, T+1] i32 as csrc/interp.hip defines it: start[b][i] = number of rows r < nrows[b] with i0[b][r] < i."""
+    h, n = i0.cpu().numpy(), nrows.cpu().numpy()
+    st = np.stack([np.searchsorted(h[b, :n[b]], np.arange(T + 1), side='left') for b in range(h.shape[0])]).astype(np.int32)
+    return torch.from_numpy(st).to(i0.device)
+
+
+def _gn_rows(t, B, rows, C, name):
+    """A haloed slab view [B, rows + 4, C] with unit channel stride -> (pointer to slab row 0, ld, bs)."""
+    if t.dim() != 3 or tuple(t.shape) != (B, rows + 4, C) or t.stride(2) != 1 or t.dtype != torch.float32:
+        raise ValueError(f'speechsplit_amd: {name} must be a float32 slab view [B, {rows} + 4, C] with unit channel stride, got {tuple(t.shape)}')
+    return _ptr(t), t.stride(1), (t.stride(0) if B > 1 else (rows + 4) * t.stride(1))
+
+
+def gn_relu_scratch(B, T, C):
+    """Bytes of scratch gn_relu_fwd needs (ss_op_gn_relu_scratch): 0 for T <= 256."""
+    return int(_capi.lib().ss_op_gn_relu_scratch(B, T, C))
+
+
+def gn_relu_fwd(x, y, gamma, beta, stats, lengths=None, plan=None, y_img=None, img_scale=None, scratch=None):
+    """Test hook (ss_op_gn_relu_fwd): the GroupNorm + ReLU forward kernels on the CALLER's haloed slabs, nothing copied.  x [B, T+4, C] and y
+    [B, T+4, C] (gather form: [B, P+4, C]) are slab VIEWS (any row / batch stride the header allows); gamma / beta [C]; stats [B, C/16, 2] is
+    written.  lengths: device i32[B], the ragged form.  plan = (i0 [B,P] i32, lam [B,P] f32, nrows [B] i32): the gather form; the plan
+    contract is asserted on the host first (check_gn_plan).  y_img: the image of y in y's geometry -- a float32 view like y (format v2, split
+    with the device word img_scale, None: 16) or a bfloat16 view like y (plain bf16).  scratch: a tensor of at least gn_relu_scratch(B, T, C)
+    bytes for T > 256."""
+    B, TP, Cc = x.shape
+    T = TP - 4
+    xp, x_ld, x_bs = _gn_rows(x, B, T, Cc, 'x')
+    i0 = lam = nrows = None
+    P = 0
+    if plan is not None:
+        i0, lam, nrows = plan
+        P = i0.shape[1]
+        if check_gn_plan(T, P, i0=i0, lam=lam, nrows=nrows) != B:
+            raise ValueError('speechsplit_amd: plan: batch size differs from x')
+    yp, y_ld, y_bs = _gn_rows(y, B, P if plan is not None else T, Cc, 'y')
+    bf16 = y_img is not None and y_img.dtype == torch.bfloat16
+    if y_img is not None:
+        if tuple(y_img.shape) != tuple(y.shape) or y_img.stride() != y.stride() or y_img.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("speechsplit_amd: y_img must have y's shape and strides (float32: format v2, bfloat16: plain)")
+    if lengths is not None and (lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,) or not lengths.is_contiguous()):
+        raise ValueError('speechsplit_amd: lengths must be a contiguous device i32[B]')
+    assert gamma.is_contiguous() and beta.is_contiguous() and stats.is_contiguous() and tuple(stats.shape) == (B, Cc // 16, 2)
+    _capi.check(_capi.lib().ss_op_gn_relu_fwd(xp, x_ld, x_bs, yp, y_ld, y_bs, _ptr(gamma), _ptr(beta), _ptr(stats), _ptr(lengths), _ptr(i0), _ptr(lam),
+                                              _ptr(nrows), P, _ptr(y_img), _ptr(img_scale), 1 if bf16 else 0, _ptr(scratch),
+                                              scratch.numel() * scratch.element_size() if scratch is not None else 0, B, T, Cc, _stream()))
+    return y
+
+
+def gn_relu_mask(x, gamma, beta, stats, out=None):
+    """Test hook (ss_op_gn_relu_mask): mask [B, T, C] dense, 1.0 where the GroupNorm output is > 0 -- the branch the kernels take."""
+    B, TP, Cc = x.shape
+    T = TP - 4
+    xp, x_ld, x_bs = _gn_rows(x, B, T, Cc, 'x')
+    m = torch.empty(B, T, Cc, device=x.device) if out is None else out
+    assert m.is_contiguous() and tuple(m.shape) == (B, T, Cc)
+    _capi.check(_capi.lib().ss_op_gn_relu_mask(xp, x_ld, x_bs, _ptr(gamma), _ptr(beta), _ptr(stats), _ptr(m), B, T, Cc, _stream()))
+    return m
+
+
+def gn_relu_bwd(x, dy, gamma, beta, stats, g_gamma, g_beta, g_bias, amax=None, part=None, scatter=None, src=None, dy_img=None):
+    """Test hook (ss_op_gn_relu_bwd): the GroupNorm + ReLU backward kernel on the caller's slabs.  x, dy [B, T+4, C] slab views; dy is
+    replaced in place by the gradient of x; g_gamma / g_beta / g_bias [C] are accumulated into.  amax: one float32 word; part: [B, 3, C]
+    (used under tune('deterministic', 1) only).  scatter = (lam [B,P] f32, start [B,T+1] i32) with src [B, P+4, C] (slab view): the fused
+    adjoint of the gather -- the contract is asserted on the host first.  dy_img: a bfloat16 view with dy's shape and strides."""
+    B, TP, Cc = x.shape
+    T = TP - 4
+    xp, x_ld, x_bs = _gn_rows(x, B, T, Cc, 'x')
+    dp, d_ld, d_bs = _gn_rows(dy, B, T, Cc, 'dy')
+    lam = start = None
+    P, sp, s_ld, s_bs = 0, C.c_void_p(0), 0, 0
+    if scatter is not None:
+        lam, start = scatter
+        P = lam.shape[1]
+        if check_gn_plan(T, P, lam=lam, start=start) != B:
+            raise ValueError('speechsplit_amd: plan: batch size differs from x')
+        sp, s_ld, s_bs = _gn_rows(src, B, P, Cc, 'src')
+    if dy_img is not None and (tuple(dy_img.shape) != tuple(dy.shape) or dy_img.stride() != dy.stride() or dy_img.dtype != torch.bfloat16):
+        raise ValueError("speechsplit_amd: dy_img must be a bfloat16 view with dy's shape and strides")
+    if part is not None:
+        assert part.is_contiguous() and part.numel() >= B * 3 * Cc
+    _capi.check(_capi.lib().ss_op_gn_relu_bwd(xp, x_ld, x_bs, dp, d_ld, d_bs, _ptr(gamma), _ptr(beta), _ptr(stats), _ptr(g_gamma), _ptr(g_beta),
+                                              _ptr(g_bias), _ptr(amax), _ptr(part), _ptr(lam), _ptr(start), P, sp, s_ld, s_bs, _ptr(dy_img), B, T, Cc,
+                                              _stream()))
+    return dy
+
+
 def _slab(x):
     """[B,T,C] -> haloed slab [B,T+4,C] (kernels.h: frame t at row t+2, zero halo rows)."""
     B, T, Cc = x.shape
