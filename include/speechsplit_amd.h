@@ -513,6 +513,41 @@ int  ss_mel_to_linear(const float* mel_dev, const double* inv_basis_dev, const i
                       int n_mels, double floor, double* mag_dev, void* stream);
 int  ss_griffinlim(const double* mag_dev, const double* phase0_dev, const int* frames_dev, int B, int max_frames, int n_iter,
                    double momentum, double* wav_dev, void* scratch_dev, long scratch_bytes, void* stream);
+/* Non-negative mel inversion: ss_mel_to_linear's floored pseudo-inverse is not consistent with the mel it was given (a mel is the basis
+ * applied to a non-negative spectrum, so an exact non-negative solution exists); projected FISTA started from it is.  Per frame, with
+ * Bm the [513][n_mels] mel basis, P = inv_basis [n_mels][513] and amp_m = 10^((100 mel_m - 100 + 16) / 20):
+ *     x = max(amp . P, 0);  y = x;  t = 1
+ *     n_iter times:
+ *         r  = y . Bm - amp                      (n_mels values)
+ *         g  = r . Bm^T                          (513 values)
+ *         xn = max(y - step g, 0)
+ *         tn = (1 + sqrt(1 + 4 t^2)) / 2
+ *         y  = xn + ((t - 1) / tn) (xn - x);  t = tn;  x = xn
+ *     mag = max(x, floor)
+ * `step` is an argument (the Python layer passes 1 / lambda_max(Bm^T Bm) from numpy.linalg.eigvalsh; 1 / 1.7994e-3 for the project's bank).
+ * float64 throughout.  A bin that no band covers has g = 0 and keeps its starting value.  With n_iter == 0 the result is ss_mel_to_linear's
+ * to the bit: the starting product is accumulated in its order, m ascending.  A band's sum y . Bm runs over the band's run of bins in bin
+ * order (from 0, amp subtracted last), a bin's sum r . Bm^T over the bands that cover it in band order; one workgroup per frame runs the whole
+ * iteration in one launch, no atomics: the same bits on every run.  Shapes, frames_dev and the ragged rules are ss_mel_to_linear's.
+ *
+ * The basis reaches the kernel PACKED, because every band of a mel filter bank is non-zero on one contiguous run of bins (the project's
+ * bank: 941 non-zero weights, longest run 34) and the packed form sits in LDS for the whole iteration, where the dense one (328 KB) could not.
+ * ss_mel_nnls_pack (host only) makes it from basis_host [513][n_mels]; the layout, 2 n_mels + W doubles for W non-zero weights:
+ *     packed[2 m]     first bin of band m's run      (as a double; 0 for a band with no weight)
+ *     packed[2 m + 1] length of the run, 0 .. 513    (as a double)
+ *     packed[2 n_mels ...]  the weights: band 0's run in bin order, then band 1's, ... (band m's start at the sum of the lengths before it)
+ * It returns the number of doubles the packed form takes and writes them when packed_host is non-NULL and cap_doubles is at least that
+ * (NULL or a smaller cap: the size query alone).  It returns -1 and sets ss_last_error for a NULL basis_host, n_mels outside 1 .. 4096, a
+ * weight that is negative or not finite, a band whose non-zero weights are not one contiguous run, and a packed size above 3072 doubles: what
+ * the kernel's LDS image (packed form, amp, r and y: at most 40980 bytes) is sized for.
+ * ss_mel_to_linear_nnls copies packed_dev [packed_doubles] to LDS and clamps every first bin and run length it reads there into the 513 bins
+ * and the packed_doubles - 2 n_mels weights, so a corrupt buffer changes numbers, never addresses.  Refused before anything is enqueued, as
+ * ss_mel_to_linear and: NULL packed_dev, packed_doubles outside 2 n_mels .. 515 n_mels (it disagrees with n_mels) or above 3072, n_iter
+ * outside 0 .. 100000, step not finite and positive. */
+long ss_mel_nnls_pack(const double* basis_host /* [513][n_mels] */, int n_mels, double* packed_host, long cap_doubles);
+int  ss_mel_to_linear_nnls(const float* mel_dev, const double* inv_basis_dev, const double* packed_dev, long packed_doubles,
+                           const int* frames_dev, int B, int max_frames, int n_mels, int n_iter, double step, double floor,
+                           double* mag_dev, void* stream);
 /* test hooks, each half alone: spec [B][max_frames][513][2] (re, im); ss_op_istft takes the same scratch as ss_griffinlim */
 int  ss_op_stft (const double* wav_dev,  const int* frames_dev, int B, int max_frames, double* spec_dev, void* stream);
 int  ss_op_istft(const double* spec_dev, const int* frames_dev, int B, int max_frames, double* wav_dev,

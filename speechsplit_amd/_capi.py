@@ -141,6 +141,9 @@ SYMBOLS = {
     'ss_griffinlim_scratch_bytes': (_l, [_i, _i]),
     'ss_mel_to_linear': (_i, [_fp, _vp, _ip, _i, _i, _i, _d, _vp, _vp]),
     'ss_griffinlim': (_i, [_vp, _vp, _ip, _i, _i, _i, _d, _vp, _vp, _l, _vp]),
+    # basis_host, n_mels, packed_host, cap / mel, inv_basis, packed, packed_doubles, frames, B, max_frames, n_mels, n_iter, step, floor, mag, stream
+    'ss_mel_nnls_pack': (_l, [_vp, _i, _vp, _l]),
+    'ss_mel_to_linear_nnls': (_i, [_fp, _vp, _vp, _l, _ip, _i, _i, _i, _i, _d, _d, _vp, _vp]),
     'ss_op_stft': (_i, [_vp, _ip, _i, _i, _vp, _vp]),
     'ss_op_istft': (_i, [_vp, _ip, _i, _i, _vp, _vp, _l, _vp]),
     'ss_collate': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

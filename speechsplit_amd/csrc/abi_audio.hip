@@ -266,6 +266,68 @@ int ss_mel_to_linear(const float* mel, const double* inv_basis, const int* frame
     return 0;
 }
 
+static_assert(NNLS_MAX_PACKED == 3072 && VOC_MAX_MELS == 4096, "the refusals below and the header spell these numbers out");
+
+long ss_mel_nnls_pack(const double* basis, int n_mels, double* packed, long cap_doubles) {
+    if (!basis) return fail("ss_mel_nnls_pack: null pointer: basis_host");
+    if (n_mels < 1 || n_mels > VOC_MAX_MELS) return fail("ss_mel_nnls_pack: n_mels outside 1 .. 4096");
+    const int nbin = 513;
+    long nnz = 0;
+    for (int m = 0; m < n_mels; ++m) {
+        int first = -1, last = -1, count = 0;
+        for (int k = 0; k < nbin; ++k) {
+            const double v = basis[(long)k * n_mels + m];
+            if (!(v >= 0.0) || std::isinf(v))
+                return fail("ss_mel_nnls_pack: basis_host: band " + std::to_string(m) + ", bin " + std::to_string(k) +
+                            ": the weight is negative or not finite");
+            if (v > 0.0) {
+                if (first < 0) first = k;
+                last = k;
+                ++count;
+            }
+        }
+        if (count && last - first + 1 != count)
+            return fail("ss_mel_nnls_pack: basis_host: the non-zero weights of band " + std::to_string(m) + " are not one contiguous run of bins");
+        nnz += count;
+    }
+    const long size = 2L * n_mels + nnz;
+    if (size > NNLS_MAX_PACKED)
+        return fail("ss_mel_nnls_pack: the packed basis takes " + std::to_string(size) + " doubles, beyond the 3072 the kernel's LDS holds");
+    if (packed && cap_doubles >= size) {
+        double* w = packed + 2L * n_mels;
+        for (int m = 0; m < n_mels; ++m) {
+            int first = 0, len = 0;
+            for (int k = 0; k < nbin; ++k)
+                if (basis[(long)k * n_mels + m] > 0.0) {
+                    if (!len) first = k;
+                    *w++ = basis[(long)k * n_mels + m];
+                    ++len;
+                }
+            packed[2 * m] = (double)first;
+            packed[2 * m + 1] = (double)len;
+        }
+    }
+    return size;
+}
+
+int ss_mel_to_linear_nnls(const float* mel, const double* inv_basis, const double* packed, long packed_doubles, const int* frames, int B,
+                          int max_frames, int n_mels, int n_iter, double step, double floor, double* mag, void* stream) {
+    if (!mel) return fail("ss_mel_to_linear_nnls: null pointer: mel_dev");
+    if (!inv_basis) return fail("ss_mel_to_linear_nnls: null pointer: inv_basis_dev");
+    if (!packed) return fail("ss_mel_to_linear_nnls: null pointer: packed_dev");
+    if (!mag) return fail("ss_mel_to_linear_nnls: null pointer: mag_dev");
+    CHK(voc_shape("ss_mel_to_linear_nnls", B, max_frames));
+    if (n_mels < 1 || n_mels > VOC_MAX_MELS) return fail("ss_mel_to_linear_nnls: n_mels outside 1 .. 4096");
+    if (packed_doubles < 2L * n_mels || packed_doubles > 515L * n_mels)
+        return fail("ss_mel_to_linear_nnls: packed_doubles disagrees with n_mels (2 n_mels + the number of weights, at most 513 a band)");
+    if (packed_doubles > NNLS_MAX_PACKED) return fail("ss_mel_to_linear_nnls: packed_doubles beyond the 3072 the kernel's LDS holds");
+    if (n_iter < 0 || n_iter > 100000) return fail("ss_mel_to_linear_nnls: n_iter outside 0 .. 100000");
+    if (!(step > 0.0) || std::isinf(step)) return fail("ss_mel_to_linear_nnls: step is not finite and positive");
+    if (!(floor >= 0.0)) return fail("ss_mel_to_linear_nnls: floor is negative or NaN");
+    HIPCHK(mel_to_linear_nnls(mel, inv_basis, packed, packed_doubles, frames, B, max_frames, n_mels, n_iter, step, floor, mag, S(stream)));
+    return 0;
+}
+
 int ss_griffinlim(const double* mag, const double* phase0, const int* frames, int B, int max_frames, int n_iter, double momentum,
                   double* wav, void* scratch, long scratch_bytes, void* stream) {
     if (!mag) return fail("ss_griffinlim: null pointer: mag_dev");

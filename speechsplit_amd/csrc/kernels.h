@@ -315,6 +315,14 @@ VocoderScratch vocoder_scratch(void* base, int B, int max_frames);
 // mag = max(floor, 10^((100 mel - 100 + 16) / 20) . inv_basis), inv_basis [n_mels][513]
 hipError_t mel_to_linear(const float* mel, const double* inv_basis, const int* frames, int B, int max_frames, int n_mels, double floor,
                          double* mag, hipStream_t s);
+// Non-negative mel inversion by projected FISTA, one workgroup per frame, the whole iteration in one launch (see vocoder.hip).  packed is
+// ss_mel_nnls_pack's form of the [513][n_mels] basis: per band (first bin, run length), then the bands' runs of weights; it sits in LDS with
+// amp, r and y, mel_nnls_lds_bytes(n_mels, packed_doubles) bytes -- at NNLS_MAX_PACKED no more than 40980, under the 64 KiB a launch gets
+// without asking.  n_iter == 0 is mel_to_linear to the bit.
+constexpr long NNLS_MAX_PACKED = 3072;
+long mel_nnls_lds_bytes(int n_mels, long packed_doubles);
+hipError_t mel_to_linear_nnls(const float* mel, const double* inv_basis, const double* packed, long packed_doubles, const int* frames, int B,
+                              int max_frames, int n_mels, int n_iter, double step, double floor, double* mag, hipStream_t s);
 // melspec_kernel's framing with a 1024-point FFT in LDS, one workgroup per frame
 hipError_t stft(const double* wav, const int* frames, int B, int max_frames, double* spec, hipStream_t s);
 // window * irfft per frame into frame_buf, then a gather per output sample over the frames that cover it, over the sum of their squared windows

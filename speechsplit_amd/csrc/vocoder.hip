@@ -17,6 +17,10 @@
 // stops being cheap.  1024-point complex radix-2 decimation in frequency, in place in LDS, output read in bit-reversed order; the twiddles come
 // from sincospi, exact to double rounding.
 //
+// Mel -> linear: mel_to_linear_kernel applies a caller-supplied pseudo-inverse and floors; mel_nnls_kernel goes on from there to the
+// non-negative magnitude whose mel is the given one, by projected FISTA, the whole iteration of a frame in one launch with the banded mel
+// basis packed in LDS (include/speechsplit_amd.h, ss_mel_to_linear_nnls; zero iterations are mel_to_linear_kernel to the bit).
+//
 // Batches: row b has its own frame count F_b = min(max(frames[b], 4), max_frames) and n_b = 256 (F_b - 1) samples; every kernel computes row b
 // as if it were alone, never reads a spectrogram frame at or beyond F_b, and writes exact zeros behind n_b.
 #include "common.h"
@@ -132,9 +136,114 @@ __global__ __launch_bounds__(NT) void mel_to_linear_kernel(const float* __restri
     }
 }
 
+// grid = (max_frames, B), block = 256, dynamic LDS = nnls_lds_bytes(n_mels, packed_doubles): non-negative mel inversion by projected FISTA
+// (include/speechsplit_amd.h, ss_mel_to_linear_nnls), the whole iteration of one frame inside one launch.  The basis arrives packed by
+// ss_mel_nnls_pack -- per band (first bin, run length), then every band's run of weights -- and is unpacked once into LDS; x and y of bins
+// tid, tid + 256 and (thread 0) 512 stay in registers; per iteration y goes to LDS, a barrier, thread m < n_mels sums band m over its run in
+// bin order, a barrier, every thread sums its bins' gradient over the covering bands in band order.  No global traffic inside the loop, no
+// atomics, every sum in one fixed order.  Every index taken from `packed` is clamped: first bin into 0 .. 512, run length into what is left
+// of the 513 bins and of the packed weights, so a corrupt buffer changes numbers, never addresses.  Rows at or beyond the row's frames: mel
+// is not read, mag is zeros.  The starting product is mel_to_linear_kernel's, term for term.
+__global__ __launch_bounds__(NT) void mel_nnls_kernel(const float* __restrict__ mel, const double* __restrict__ inv_basis,
+                                                      const double* __restrict__ packed, int packed_doubles,
+                                                      const int* __restrict__ frames, int max_frames, int n_mels, int n_iter, double step,
+                                                      double floor, double* __restrict__ mag) {
+    extern __shared__ double lds[];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const long fr = (long)b * max_frames + f;
+    if (f >= row_frames(frames, b, max_frames)) {
+        for (int k = tid; k < NBIN; k += NT) mag[fr * NBIN + k] = 0.0;
+        return;
+    }
+    const int nnz = packed_doubles - 2 * n_mels;
+    double* w = lds;                    // [nnz]
+    double* amp = w + nnz;              // [n_mels]
+    double* r = amp + n_mels;           // [n_mels]
+    double* ys = r + n_mels;            // [NBIN + 1]
+    int* lo = (int*)(ys + NBIN + 1);    // [n_mels]      first bin of band m
+    int* off = lo + n_mels;             // [n_mels + 1]  band m's weights are w[off[m] .. off[m + 1])
+    for (int m = tid; m < n_mels; m += NT) {
+        amp[m] = pow(10.0, (100.0 * (double)mel[fr * n_mels + m] - 100.0 + 16.0) / 20.0);
+        const double first = packed[2 * m];
+        lo[m] = first >= 0.0 ? (first <= (double)(NBIN - 1) ? (int)first : NBIN - 1) : 0;       // NaN: 0
+    }
+    for (int i = tid; i < nnz; i += NT) w[i] = packed[2 * n_mels + i];
+    __syncthreads();
+    if (tid == 0) {
+        int o = 0;
+        for (int m = 0; m < n_mels; ++m) {
+            const double run = packed[2 * m + 1];
+            int len = run >= 0.0 ? (run <= (double)NBIN ? (int)run : NBIN) : 0;                 // NaN: 0
+            len = min(len, min(NBIN - lo[m], nnz - o));
+            off[m] = o;
+            o += len;
+        }
+        off[n_mels] = o;
+    }
+    __syncthreads();
+
+    constexpr int PER = (NBIN + NT - 1) / NT;   // 3: bins tid, tid + 256, tid + 512
+    double x[PER], y[PER];
+    int mfirst[PER], mlast[PER];                // the bands that cover the bin lie in mfirst .. mlast (empty: mfirst > mlast)
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int k = tid + j * NT;
+        x[j] = y[j] = 0.0;
+        mfirst[j] = n_mels;
+        mlast[j] = -1;
+        if (k < NBIN) {
+            double s = 0.0;
+            for (int m = 0; m < n_mels; ++m) s += amp[m] * inv_basis[(long)m * NBIN + k];
+            x[j] = y[j] = fmax(s, 0.0);
+            for (int m = 0; m < n_mels; ++m)
+                if (k >= lo[m] && k - lo[m] < off[m + 1] - off[m]) {
+                    mfirst[j] = min(mfirst[j], m);
+                    mlast[j] = m;
+                }
+        }
+    }
+    double t = 1.0;
+    for (int it = 0; it < n_iter; ++it) {
+#pragma unroll
+        for (int j = 0; j < PER; ++j)
+            if (tid + j * NT < NBIN) ys[tid + j * NT] = y[j];
+        __syncthreads();
+        for (int m = tid; m < n_mels; m += NT) {
+            const int o = off[m], len = off[m + 1] - o, k0 = lo[m];
+            double s = 0.0;
+            for (int i = 0; i < len; ++i) s += ys[k0 + i] * w[o + i];
+            r[m] = s - amp[m];
+        }
+        __syncthreads();
+        const double tn = (1.0 + sqrt(1.0 + 4.0 * t * t)) / 2.0;
+        const double beta = (t - 1.0) / tn;
+        t = tn;
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int k = tid + j * NT;
+            double g = 0.0;
+            for (int m = mfirst[j]; m <= mlast[j]; ++m) {
+                const int i = k - lo[m];
+                if (i >= 0 && i < off[m + 1] - off[m]) g += r[m] * w[off[m] + i];
+            }
+            const double xn = fmax(y[j] - step * g, 0.0);
+            y[j] = xn + beta * (xn - x[j]);
+            x[j] = xn;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j)
+        if (tid + j * NT < NBIN) mag[fr * NBIN + tid + j * NT] = fmax(x[j], floor);
+}
+
 constexpr long align256(long n) { return (n + 255) & ~255L; }
 
 }  // namespace
+
+long mel_nnls_lds_bytes(int n_mels, long packed_doubles) {
+    // weights, amp, r, y as doubles; first bins and offsets as ints
+    return (packed_doubles + NBIN + 1) * 8 + (2L * n_mels + 1) * 4;
+}
 
 long vocoder_scratch_bytes(int B, int max_frames) {
     const long fr = (long)B * max_frames;
@@ -156,6 +265,16 @@ hipError_t mel_to_linear(const float* mel, const double* inv_basis, const int* f
     if (B < 1 || B > VOC_MAX_ROWS || max_frames < 4 || n_mels < 1 || n_mels > VOC_MAX_MELS) return hipErrorInvalidValue;
     hipLaunchKernelGGL(mel_to_linear_kernel, dim3(max_frames, B), dim3(NT), n_mels * sizeof(double), s, mel, inv_basis, frames, max_frames,
                        n_mels, floor, mag);
+    return hipGetLastError();
+}
+
+hipError_t mel_to_linear_nnls(const float* mel, const double* inv_basis, const double* packed, long packed_doubles, const int* frames, int B,
+                              int max_frames, int n_mels, int n_iter, double step, double floor, double* mag, hipStream_t s) {
+    if (B < 1 || B > VOC_MAX_ROWS || max_frames < 4 || n_mels < 1 || n_iter < 0 || packed_doubles < 2L * n_mels ||
+        packed_doubles > NNLS_MAX_PACKED)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mel_nnls_kernel, dim3(max_frames, B), dim3(NT), mel_nnls_lds_bytes(n_mels, packed_doubles), s, mel, inv_basis, packed,
+                       (int)packed_doubles, frames, max_frames, n_mels, n_iter, step, floor, mag);
     return hipGetLastError();
 }
 

@@ -3,8 +3,9 @@ for the last cell of the reference's demo.ipynb (WaveNet with an external checkp
 
 It inverts what this project itself defines (features.py / csrc/features.hip): the [0, 1] dB scale and the mel basis of `melspectrogram`,
 and the 1024-point periodic-Hann STFT at hop 256 with reflect padding.  The mel basis is inverted by its pseudo-inverse
-(`numpy.linalg.pinv`; librosa's NNLS is not available), floored, and Griffin-Lim with momentum (Perraudin et al. 2013, librosa's form)
-finds a phase.  L frames become 256 (L - 1) samples, and `melspectrogram` of those has L frames again.  float64 throughout; the same bits on
+(`numpy.linalg.pinv`), floored -- the default, inversion='pinv' -- or, with inversion='nnls', by the non-negative solution that projected
+FISTA reaches from there on the device (ss_mel_to_linear_nnls: what librosa does with NNLS, here without an external library), and
+Griffin-Lim with momentum (Perraudin et al. 2013, librosa's form) finds a phase.  L frames become 256 (L - 1) samples, and `melspectrogram` of those has L frames again.  float64 throughout; the same bits on
 every run; the starting phases are inputs, drawn on the host.  No engine needed."""
 import ctypes as C
 import wave
@@ -42,6 +43,45 @@ def _inv_basis(mel_basis):
     return np.linalg.pinv(mb)
 
 
+INVERSIONS = ('pinv', 'nnls')
+_NNLS = {}
+
+
+def _check_inversion(who, inversion):
+    if inversion not in INVERSIONS:
+        raise ValueError(f"{who}: inversion is 'pinv' or 'nnls', not {inversion!r}")
+
+
+def _nnls_basis(mel_basis):
+    """(packed float64 [2 n_mels + weights], step): ss_mel_nnls_pack's form of the [513, n_mels] basis and 1 / lambda_max(B^T B);
+    packed once for the project's own filter bank (None), as _inv_basis"""
+    if mel_basis is None and None in _NNLS:
+        return _NNLS[None]
+    mb = np.ascontiguousarray(features.mel_filter_bank().T if mel_basis is None else mel_basis, dtype=np.float64)
+    if mb.ndim != 2 or mb.shape[0] != NBIN:
+        raise ValueError('mel_basis must be [513, n_mels] (1024-point transform)')
+    lib = _capi.lib()
+    size = lib.ss_mel_nnls_pack(C.c_void_p(mb.ctypes.data), mb.shape[1], None, 0)
+    if size < 0:
+        _capi.check(-1)
+    packed = np.empty(size, np.float64)
+    if lib.ss_mel_nnls_pack(C.c_void_p(mb.ctypes.data), mb.shape[1], C.c_void_p(packed.ctypes.data), size) != size:
+        _capi.check(-1)
+    out = packed, 1.0 / float(np.linalg.eigvalsh(mb.T @ mb)[-1])
+    if mel_basis is None:
+        _NNLS[None] = out
+    return out
+
+
+def _mel_to_linear_nnls(mel_dev, inv_dev, packed_dev, frames_dev, n_iter, step, floor):
+    """_mel_to_linear's shapes, packed_dev float64 [2 n_mels + weights]: n_iter rounds of projected FISTA from the clipped pseudo-inverse"""
+    B, T, n_mels = mel_dev.shape
+    mag = torch.empty(B, T, NBIN, dtype=torch.float64, device=mel_dev.device)
+    _capi.check(_capi.lib().ss_mel_to_linear_nnls(_ptr(mel_dev), _ptr(inv_dev), _ptr(packed_dev), packed_dev.numel(), _ptr(frames_dev), B, T,
+                                                  n_mels, int(n_iter), float(step), float(floor), _ptr(mag), _stream()))
+    return mag
+
+
 def _mel_to_linear(mel_dev, inv_dev, frames_dev, floor):
     """mel_dev float32 [B, T, n_mels], inv_dev float64 [n_mels, 513], frames_dev int32 [B] or None -> float64 [B, T, 513], all on one device"""
     B, T, n_mels = mel_dev.shape
@@ -50,15 +90,21 @@ def _mel_to_linear(mel_dev, inv_dev, frames_dev, floor):
     return mag
 
 
-def mel_to_linear(mel, mel_basis=None, floor=1e-10, device='cuda'):
+def mel_to_linear(mel, mel_basis=None, floor=1e-10, device='cuda', inversion='pinv', nnls_iter=200):
     """mel float [L, n_mels] on `melspectrogram`'s [0, 1] dB scale -> float64 [L, 513] tensor on `device`:
-    max(floor, 10^((100 mel - 100 + 16) / 20) . pinv(mel_basis)).  mel_basis [513, n_mels] defaults to features.mel_filter_bank().T."""
+    max(floor, 10^((100 mel - 100 + 16) / 20) . pinv(mel_basis)).  mel_basis [513, n_mels] defaults to features.mel_filter_bank().T.
+    inversion='nnls': nnls_iter rounds of projected FISTA from there towards the non-negative magnitude whose mel is the given one
+    (ss_mel_to_linear_nnls; step 1 / lambda_max(B^T B)), then the floor."""
+    _check_inversion('mel_to_linear', inversion)
     m = torch.as_tensor(np.ascontiguousarray(mel, dtype=np.float32)).to(device)
     if m.dim() != 2 or m.shape[0] < MIN_FRAMES:
         raise ValueError(f'mel_to_linear: mel must be [L, n_mels] with L >= {MIN_FRAMES}')
     inv = torch.as_tensor(_inv_basis(mel_basis)).to(device)
     if inv.shape[0] != m.shape[1]:
         raise ValueError(f'mel_to_linear: mel has {m.shape[1]} bands, the basis {inv.shape[0]}')
+    if inversion == 'nnls':
+        packed, step = _nnls_basis(mel_basis)
+        return _mel_to_linear_nnls(m[None], inv, torch.as_tensor(packed).to(device), None, nnls_iter, step, floor)[0]
     return _mel_to_linear(m[None], inv, None, floor)[0]
 
 
@@ -100,14 +146,19 @@ def prepare(mels, phases=None, generator=None):
     return single, ms, ps
 
 
-def griffin_lim(mels, n_iter=60, momentum=0.99, phases=None, generator=None, max_rows=16, device='cuda', mel_basis=None, floor=1e-10):
+def griffin_lim(mels, n_iter=60, momentum=0.99, phases=None, generator=None, max_rows=16, device='cuda', mel_basis=None, floor=1e-10,
+                inversion='pinv', nnls_iter=200):
     """One mel [L, 80] (or a list of them, any lengths >= 4) -> float64 numpy waveform(s) of 256 (L - 1) samples at 16 kHz, in input order.
     The utterances run as ragged batches of at most max_rows rows in convert.plan_batches order; every row is the result of running it alone,
-    so the result does not depend on max_rows.  phases / generator: see prepare()."""
+    so the result does not depend on max_rows.  phases / generator: see prepare().  inversion / nnls_iter: see mel_to_linear()."""
+    _check_inversion('griffin_lim', inversion)
     single, ms, ps = prepare(mels, phases, generator)
     inv = torch.as_tensor(_inv_basis(mel_basis)).to(device)
     if ms and inv.shape[0] != ms[0].shape[1]:
         raise ValueError(f'griffin_lim: mel has {ms[0].shape[1]} bands, the basis {inv.shape[0]}')
+    if inversion == 'nnls':
+        packed, step = _nnls_basis(mel_basis)
+        packed = torch.as_tensor(packed).to(device)
     out = [None] * len(ms)
     for batch in plan_batches([m.shape[0] for m in ms], max_rows):
         lens = [ms[i].shape[0] for i in batch]
@@ -119,7 +170,10 @@ def griffin_lim(mels, n_iter=60, momentum=0.99, phases=None, generator=None, max
             if ph is not None:
                 ph[n, :lens[n]] = ps[i]
         frames = torch.tensor(lens, dtype=torch.int32, device=device)
-        mag = _mel_to_linear(torch.from_numpy(mel).to(device), inv, frames, floor)
+        if inversion == 'nnls':
+            mag = _mel_to_linear_nnls(torch.from_numpy(mel).to(device), inv, packed, frames, nnls_iter, step, floor)
+        else:
+            mag = _mel_to_linear(torch.from_numpy(mel).to(device), inv, frames, floor)
         wav = griffin_lim_mag(mag, torch.from_numpy(ph).to(device) if ph is not None else None, frames, n_iter, momentum).cpu().numpy()
         for n, i in enumerate(batch):
             out[i] = wav[n, :256 * (lens[n] - 1)].copy()

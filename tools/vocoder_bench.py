@@ -2,8 +2,11 @@
 """GPU time of the Griffin-Lim vocoder (csrc/vocoder.hip), ONE process, device events, median / min / max over --reps after --warmup:
   * ss_griffinlim on --rows x --frames x --iters (default 7 x 192 x 60: the seven conditions of one demo conversion), in milliseconds;
   * per frame, the FFT-based ss_op_stft against the direct-DFT ss_melspec (features.hip; it also does the mel projection, 8 % of its
-    multiply-adds) on the same --frames frames of one waveform, alternated call by call, --inner calls per timed window.
-    python tools/vocoder_bench.py [--rows 7] [--frames 192] [--iters 60] [--reps 30] [--warmup 5] [--inner 20]
+    multiply-adds) on the same --frames frames of one waveform, alternated call by call, --inner calls per timed window;
+  * the mel inversion as a stage of its own, on the same --rows x --frames mels of the project's filter bank: ss_mel_to_linear against
+    ss_mel_to_linear_nnls at every count of --nnls-iters (default 50 and 200), one call per timed window, alternated call by call, in
+    milliseconds and as a fraction of ss_griffinlim's median on this run.
+    python tools/vocoder_bench.py [--rows 7] [--frames 192] [--iters 60] [--reps 30] [--warmup 5] [--inner 20] [--nnls-iters 50 200]
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -27,8 +30,9 @@ def main():
     ap.add_argument('--reps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--inner', type=int, default=20)
+    ap.add_argument('--nnls-iters', type=int, nargs='+', default=[50, 200])
     a = ap.parse_args()
-    from speechsplit_amd import _capi, vocoder
+    from speechsplit_amd import _capi, features, vocoder
     lib = _capi.lib()
     dev = torch.device('cuda:0')
     B, T = a.rows, a.frames
@@ -43,6 +47,13 @@ def main():
     p = lambda t: C.c_void_p(t.data_ptr())
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     assert lib.ss_melspec_frames(n) == T
+    # the inversion's inputs: mels of non-negative spectra through the project's bank (what a mel is), its pseudo-inverse and packed form
+    bank = features.mel_filter_bank().T.astype(np.float64)
+    mel_in = 20.0 * np.log10(np.maximum(1e-5, (rng.uniform(0.0, 1.0, (B, T, 513)) ** 4) @ bank)) - 16.0
+    mel_in = torch.from_numpy(((mel_in + 100.0) / 100.0).astype(np.float32)).to(dev)
+    inv = torch.from_numpy(np.linalg.pinv(bank)).to(dev)
+    packed, step = vocoder._nnls_basis(None)
+    packed = torch.from_numpy(packed).to(dev)
 
     def gl():
         vocoder.griffin_lim_mag(mag, ph, None, a.iters, 0.99)
@@ -55,10 +66,17 @@ def main():
         for _ in range(a.inner):
             _capi.check(lib.ss_melspec(p(wav), n, p(basis), 80, p(mel), s))
 
+    def pinv():
+        vocoder._mel_to_linear(mel_in, inv, None, 1e-10)
+
+    def nnls(n_iter):
+        return lambda: vocoder._mel_to_linear_nnls(mel_in, inv, packed, None, n_iter, step, 1e-10)
+
+    stages = [('griffinlim', gl), ('stft_fft', fft), ('melspec_dft', dft), ('mel_pinv', pinv)] + [(f'mel_nnls_{k}', nnls(k)) for k in a.nnls_iters]
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    times = {'griffinlim': [], 'stft_fft': [], 'melspec_dft': []}
+    times = {tag: [] for tag, _ in stages}
     for it in range(a.warmup + a.reps):
-        for tag, fn in (('griffinlim', gl), ('stft_fft', fft), ('melspec_dft', dft)):
+        for tag, fn in stages:
             ev[0].record()
             fn()
             ev[1].record()
@@ -73,7 +91,10 @@ def main():
                       'launches': 3 + 3 * a.iters,
                       'us_per_frame_median': {k: round(v, 4) for k, v in per_frame.items()},
                       'call_ms_minmax': {k: [round(min(times[k]) / a.inner, 5), round(max(times[k]) / a.inner, 5)] for k in per_frame},
-                      'dft_over_fft': round(per_frame['melspec_dft'] / per_frame['stft_fft'], 2)}))
+                      'dft_over_fft': round(per_frame['melspec_dft'] / per_frame['stft_fft'], 2),
+                      'inversion_ms_median': {k: round(med[k], 4) for k in med if k.startswith('mel_')},
+                      'inversion_ms_minmax': {k: [round(min(times[k]), 4), round(max(times[k]), 4)] for k in med if k.startswith('mel_')},
+                      'inversion_over_griffinlim': {k: round(med[k] / med['griffinlim'], 4) for k in med if k.startswith('mel_')}}))
 
 
 if __name__ == '__main__':
