@@ -700,6 +700,69 @@ int ss_op_gn_relu_bwd(const float* x_dev, long x_ld, long x_bs, float* dy_dev, l
                       const float* stats_dev, float* g_gamma_dev, float* g_beta_dev, float* g_bias_dev, float* amax_dev, float* part_dev,
                       const float* lam_dev, const int* start_dev, int P, const float* src_dev, long src_ld, long src_bs, float* dy_img_dev, int B,
                       int T, int C, void* stream);
+/* The kernels that stand between the heavy families in a training step (speechsplit_amd/csrc/elementwise.hip, input_grads.hip), engine-free
+ * and on the CALLER's memory: the hooks hand their views to the kernel launchers and do nothing else -- no engine, no copy into private
+ * buffers, so memory around an operand is the caller's to watch.  A VIEW is (p, ld, bs): row t of utterance b starts at p + b * bs + t * ld
+ * floats, p being frame 0 (no halo is added).  Every refusal is made before anything is enqueued, each with its own ss_last_error text.
+ *   ss_op_mse_loss   loss = mean over B T C of (out - tgt)^2 (float64 sum of 8 B fp32 block partials, rounded once);
+ *                    d_out = (out - tgt) * (float(2 / (B T C)) * grad_scale), C columns of every row, nothing else written.
+ *                    partials_dev: at least 8 B floats of scratch; loss_dev: one float.  Refused: a null pointer, B / T / C below 1, a row
+ *                    stride below C.
+ *   ss_op_ce_loss    softmax cross-entropy of logits [B][T][C] (a view) against tgt_dev i32 [B][T] dense, mean over the B T rows;
+ *                    d_out = (softmax - onehot) * (float(1 / (B T)) * grad_scale).  partials_dev: at least B T floats (the per-row losses);
+ *                    loss_dev: one float.  The result depends on a row's logits only through their differences from the row maximum
+ *                    (shift-invariant: logits near 1000 are as accurate as logits near 0).  TARGETS MUST LIE IN [0, C): they are read on the
+ *                    device and NOT CHECKED there -- an out-of-range target reads outside the row.  Refused: a null pointer, B / T / C
+ *                    below 1, a row stride below C.
+ *   ss_op_colsum_scratch_doubles(cols)
+ *                    float64 words of scratch the chunked column sum needs: (ceil(1024 / nb) + 1) * nb * 64 with nb = ceil(cols / 64);
+ *                    0 for cols < 1.
+ *   ss_op_colsum     column sums of in [R][cols] (row stride ld), float64 accumulation in a fixed order, ADDED to the outputs (one fp32
+ *                    rounding of the sum, one of the addition).  two_dir == 0: cols = C, o0[c] += sum (o1 .. o3 must be NULL).
+ *                    two_dir != 0: cols = 2 C, columns [0, C) go to o0 and (if not NULL) o1, columns [C, 2 C) to o2 and (if not NULL) o3
+ *                    -- the (b_ih, b_hh) pairs of a BLSTM's two directions.  part_dev / ctr_dev both NULL: the single-chunk form, one
+ *                    workgroup per 64 columns.  Both given: up to min(ceil(1024 / nb), ceil(R / 16)) row chunks per column block hand
+ *                    float64 partials through part_dev; ctr_dev holds one arrival counter per column block, ZERO on entry and zero again
+ *                    when the launch retires, used by nobody else meanwhile.  The sums are the same bits whatever the arrival order.
+ *                    Refused: a null in / o0, two_dir without o2, R or C below 1, ld < cols, one of part / ctr without the other,
+ *                    part_doubles below ss_op_colsum_scratch_doubles(cols), ctr_words below ceil(cols / 64), a misaligned scratch.
+ *   ss_op_dec_in     the decoder input from up to four encoder BLSTM output slabs (ss_code_src: o [B][T+4][ld_i] haloed, the 2 H real
+ *                    columns first) and the speaker rows emb [B][emb_dim] (emb_dim 0: none).  Columns [col, col + H) of frame t are the
+ *                    forward half at the LAST frame of t's block of freq frames, [col + H, col + 2 H) the backward half at its FIRST frame;
+ *                    columns [emb_col, emb_col + emb_dim) the speaker row; every other column of the ld is written zero.  f == 0: the
+ *                    slab form, dst [B][T+4][ld], rows [2, 2 + T) written, halo rows untouched.  f > 0: the compact form, dst [B][T/f][ld],
+ *                    one row per block (every source's freq == f).  Column ranges must not overlap (not checked).
+ *   ss_op_dec_in_grad  the adjoint: d_o [B][T+4][ld_i] of every source gets, in its 2 H real columns of rows [2, 2 + T) and nowhere else,
+ *                    the sum over the block's freq frames (fp32, frames ascending) of d_in's columns at the one frame of the block where
+ *                    the half was sampled, and zero at every other frame.  f == 0: d_in is the slab [B][T+4][ld]; f > 0: d_in is
+ *                    [B][T/f][ld] and already holds the sums.
+ *   ss_op_dec_in_codes  ss_op_dec_in by way of dense codes (up to three sources): export the codes into codes_dev (at least the sum over
+ *                    the sources of B (T / freq_i) 2 H_i floats, each rounded up to 4; 16-byte aligned), then build dst from them.
+ *                    Refused by all three: a null pointer, nsrc outside 1 .. 4 (codes: 3), B / T below 1, T % freq_i != 0, columns
+ *                    beyond ld, ld_i < 2 H_i, f that does not divide T, the compact form with a freq_i != f.
+ *   ss_op_spk_grad   out [B][E] = sum_g (sum over rows r of dg[b][r][g]) * W(g, col0 + j), g < 2 H4, W = [w_f ; w_r] ([H4][w_ld] each);
+ *                    dg row r of utterance b at dg + b * b_stride + r * ld.  Fixed order throughout.  Refused: a null pointer, E outside
+ *                    1 .. 1024, H4 / rows / B below 1, more than 64 KiB of LDS (2 H4 + floor(1024 / E) E floats), ld < 2 H4,
+ *                    w_ld < col0 + E. */
+typedef struct ss_code_src {
+    const float* o;       /* forward: the BLSTM output slab */
+    float* d_o;           /* backward: its gradient slab */
+    int H, freq, col, ld;
+} ss_code_src;
+int ss_op_mse_loss(const float* out_dev, long out_ld, long out_bs, const float* tgt_dev, long tgt_ld, long tgt_bs, float* d_out_dev, long d_ld,
+                   long d_bs, int B, int T, int C, float grad_scale, float* partials_dev, float* loss_dev, void* stream);
+int ss_op_ce_loss(const float* logits_dev, long ld, long bs, const int* tgt_dev, float* d_out_dev, long d_ld, long d_bs, int B, int T, int C,
+                  float grad_scale, float* partials_dev, float* loss_dev, void* stream);
+long ss_op_colsum_scratch_doubles(int cols);
+int ss_op_colsum(const float* in_dev, long ld, int R, int C, int two_dir, float* o0_dev, float* o1_dev, float* o2_dev, float* o3_dev,
+                 double* part_dev, long part_doubles, unsigned* ctr_dev, int ctr_words, void* stream);
+int ss_op_dec_in(const ss_code_src* src, int nsrc, const float* emb_dev, int emb_dim, int emb_col, float* dst_dev, int ld, int B, int T, int f,
+                 void* stream);
+int ss_op_dec_in_grad(const ss_code_src* src, int nsrc, const float* d_in_dev, int ld, int B, int T, int f, void* stream);
+int ss_op_dec_in_codes(const ss_code_src* src, int nsrc, const float* emb_dev, int emb_dim, int emb_col, float* codes_dev, long codes_floats,
+                       float* dst_dev, int ld, int B, int T, int f, void* stream);
+int ss_op_spk_grad(const float* dg_dev, long ld, long b_stride, int rows, const float* w_f_dev, const float* w_r_dev, long w_ld, int col0, int H4,
+                   int E, float* out_dev, int B, void* stream);
 /* The GEMM over operand images (speechsplit_amd/csrc/gemm_img.hip), the engine's default for every large contraction: an IMAGE has the
  * geometry of its fp32 matrix (4 bytes per element) with every aligned group of 8 elements along the contiguous axis replaced by 16 bytes of
  * hi pieces and 16 bytes of lo pieces of the fp16 x 2 split of scale * x (scale a power of two).

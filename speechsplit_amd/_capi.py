@@ -40,6 +40,11 @@ class SSGemmImgDesc(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in GEMM_IMG_DESC_PTRS] + [(n, C.c_long) for n in GEMM_DESC_LONGS] + [(n, C.c_int) for n in GEMM_IMG_DESC_INTS]
 
 
+class SSCodeSrc(C.Structure):
+    """ss_code_src (test hooks ss_op_dec_in*): one encoder BLSTM output slab feeding the decoder input."""
+    _fields_ = [('o', C.c_void_p), ('d_o', C.c_void_p), ('H', C.c_int), ('freq', C.c_int), ('col', C.c_int), ('ld', C.c_int)]
+
+
 # every symbol include/speechsplit_amd.h declares: name -> (restype, argtypes)
 _vp, _fp, _ip, _i, _l, _f, _d = C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 SYMBOLS = {
@@ -112,6 +117,20 @@ SYMBOLS = {
     'ss_op_gn_relu_mask': (_i, [_fp, _l, _l, _fp, _fp, _fp, _fp, _i, _i, _i, _vp]),
     # x, x_ld, x_bs, dy, dy_ld, dy_bs, gamma, beta, stats, g_gamma, g_beta, g_bias, amax, part, lam, start, P, src, src_ld, src_bs, dy_img, B, T, C, stream
     'ss_op_gn_relu_bwd': (_i, [_fp, _l, _l, _fp, _l, _l, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _ip, _i, _fp, _l, _l, _fp, _i, _i, _i, _vp]),
+    # out, ld, bs, tgt, ld, bs, d_out, ld, bs, B, T, C, grad_scale, partials, loss, stream
+    'ss_op_mse_loss': (_i, [_fp, _l, _l, _fp, _l, _l, _fp, _l, _l, _i, _i, _i, _f, _fp, _fp, _vp]),
+    # logits, ld, bs, tgt, d_out, ld, bs, B, T, C, grad_scale, partials, loss, stream
+    'ss_op_ce_loss': (_i, [_fp, _l, _l, _ip, _fp, _l, _l, _i, _i, _i, _f, _fp, _fp, _vp]),
+    'ss_op_colsum_scratch_doubles': (_l, [_i]),
+    # in, ld, R, C, two_dir, o0, o1, o2, o3, part, part_doubles, ctr, ctr_words, stream
+    'ss_op_colsum': (_i, [_fp, _l, _i, _i, _i, _fp, _fp, _fp, _fp, _vp, _l, _vp, _i, _vp]),
+    # src, nsrc, emb, emb_dim, emb_col, dst, ld, B, T, f, stream / src, nsrc, d_in, ld, B, T, f, stream
+    'ss_op_dec_in': (_i, [C.POINTER(SSCodeSrc), _i, _fp, _i, _i, _fp, _i, _i, _i, _i, _vp]),
+    'ss_op_dec_in_grad': (_i, [C.POINTER(SSCodeSrc), _i, _fp, _i, _i, _i, _i, _vp]),
+    # src, nsrc, emb, emb_dim, emb_col, codes, codes_floats, dst, ld, B, T, f, stream
+    'ss_op_dec_in_codes': (_i, [C.POINTER(SSCodeSrc), _i, _fp, _i, _i, _fp, _l, _fp, _i, _i, _i, _i, _vp]),
+    # dg, ld, b_stride, rows, w_f, w_r, w_ld, col0, H4, E, out, B, stream
+    'ss_op_spk_grad': (_i, [_fp, _l, _l, _i, _fp, _fp, _l, _i, _i, _i, _fp, _i, _vp]),
     'ss_op_split_image': (_i, [_fp, _l, _l, _i, _f, _fp, _l, _vp]),
     'ss_op_gemm_pre': (_i, [_fp, _l, _fp, _fp, _l, _fp, _fp, _l, _fp, _i, _i, _i, _i, _i, _vp]),
     'ss_op_gemm_img': (_i, [_fp, _l, _fp, _l, _fp, _l, _fp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _l, _fp, _vp, _vp]),

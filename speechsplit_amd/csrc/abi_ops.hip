@@ -525,4 +525,118 @@ int ss_op_gn_relu_bwd(const float* x, long x_ld, long x_bs, float* dy, long dy_l
 }
 #undef GN_ROWS
 
+// The kernels between the heavy families of a training step -- the two losses, the column sums, the decoder input with its gradient and the
+// speaker-embedding contraction -- on the CALLER's views: the hooks hand (pointer, ld, bs) to the launchers of kernels.h and nothing else,
+// no private copy.  Every refusal is made before anything is enqueued.
+int ss_op_mse_loss(const float* out, long out_ld, long out_bs, const float* tgt, long tgt_ld, long tgt_bs, float* d_out, long d_ld, long d_bs, int B,
+                   int T, int C, float grad_scale, float* partials, float* loss, void* stream) {
+    if (!out || !tgt || !d_out || !partials || !loss) return fail("ss_op_mse_loss: null pointer");
+    if (B < 1 || T < 1 || C < 1) return fail("ss_op_mse_loss: needs B >= 1, T >= 1 and C >= 1");
+    if (out_ld < C || tgt_ld < C || d_ld < C) return fail("ss_op_mse_loss: row stride below C");
+    HIPCHK(mse_loss(CRows{out, out_ld, out_bs}, CRows{tgt, tgt_ld, tgt_bs}, Rows{d_out, d_ld, d_bs}, B, T, C, grad_scale, partials, loss, S(stream)));
+    return 0;
+}
+
+int ss_op_ce_loss(const float* logits, long ld, long bs, const int* tgt, float* d_out, long d_ld, long d_bs, int B, int T, int C, float grad_scale,
+                  float* partials, float* loss, void* stream) {
+    if (!logits || !tgt || !d_out || !partials || !loss) return fail("ss_op_ce_loss: null pointer");
+    if (B < 1 || T < 1 || C < 1) return fail("ss_op_ce_loss: needs B >= 1, T >= 1 and C >= 1");
+    if (ld < C || d_ld < C) return fail("ss_op_ce_loss: row stride below C");
+    HIPCHK(ce_loss(CRows{logits, ld, bs}, tgt, Rows{d_out, d_ld, d_bs}, B, T, C, grad_scale, partials, loss, S(stream)));
+    return 0;
+}
+
+long ss_op_colsum_scratch_doubles(int cols) { return cols < 1 ? 0 : colsum_scratch_doubles(cols); }
+
+int ss_op_colsum(const float* in, long ld, int R, int C, int two_dir, float* o0, float* o1, float* o2, float* o3, double* part, long part_doubles,
+                 unsigned* ctr, int ctr_words, void* stream) {
+    if (!in || !o0) return fail("ss_op_colsum: null pointer (in_dev and o0_dev are required)");
+    if (R < 1 || C < 1 || C > (1 << 24)) return fail("ss_op_colsum: needs R >= 1 and 1 <= C <= 2^24");
+    if (two_dir && !o2) return fail("ss_op_colsum: the two-direction form needs o2_dev");
+    if (!two_dir && (o1 || o2 || o3)) return fail("ss_op_colsum: the single-direction form writes o0_dev only (o1_dev .. o3_dev must be NULL)");
+    const int cols = two_dir ? 2 * C : C;
+    if (ld < cols) return fail("ss_op_colsum: row stride below the number of columns");
+    if ((part == nullptr) != (ctr == nullptr)) return fail("ss_op_colsum: part_dev and ctr_dev come together (both NULL: the single-chunk form)");
+    if (part) {
+        if (part_doubles < colsum_scratch_doubles(cols)) return fail("ss_op_colsum: part_dev too small (ss_op_colsum_scratch_doubles)");
+        if (ctr_words < (cols + 63) / 64) return fail("ss_op_colsum: fewer than ceil(cols / 64) counters");
+        if (misaligned(part, 8) || misaligned(ctr, 4)) return fail("ss_op_colsum: part_dev is not 8-byte aligned or ctr_dev not 4-byte aligned");
+    }
+    if (two_dir) HIPCHK(colsum_bias(in, ld, R, C, o0, o1, o2, o3, part, ctr, S(stream)));
+    else HIPCHK(colsum_acc(in, ld, R, C, o0, part, ctr, S(stream)));
+    return 0;
+}
+
+// what dec_in_from_codes refuses (T % freq, columns beyond ld, compact with a freq != f), for slab sources, plus ld_i < 2 H_i
+static const char* dec_in_bad(const ss_code_src* src, int nsrc, int max_src, bool backward, const float* emb, int emb_dim, int emb_col, const float* io,
+                              int ld, int B, int T, int f) {
+    if (!src || !io) return "null pointer";
+    if (nsrc < 1 || nsrc > max_src) return "number of sources out of range";
+    if (B < 1 || T < 1 || ld < 1) return "needs B >= 1, T >= 1 and ld >= 1";
+    if (f < 0 || (f && T % f)) return "f must be 0 (slab form) or a divisor of T (compact form)";
+    if (emb_dim < 0 || emb_col < 0 || (emb_dim && !emb && !backward)) return "bad speaker columns, or emb_dim > 0 without emb_dev";
+    if ((long)emb_col + emb_dim > ld) return "speaker columns beyond ld";
+    for (int i = 0; i < nsrc; ++i) {
+        const ss_code_src& c = src[i];
+        if (backward ? !c.d_o : !c.o) return "a source's slab pointer is null";
+        if (c.H < 1 || c.freq < 1 || c.col < 0) return "a source needs H >= 1, freq >= 1 and col >= 0";
+        if (T % c.freq) return "T is not a multiple of a source's freq";
+        if ((long)c.col + 2L * c.H > ld) return "a source's columns lie beyond ld";
+        if (c.ld < 2L * c.H) return "a source's row stride is below 2 H";
+        if (f && c.freq != f) return "the compact form needs every source's freq == f";
+    }
+    return nullptr;
+}
+static void code_srcs(const ss_code_src* src, int nsrc, CodeSrc* out) {
+    for (int i = 0; i < nsrc; ++i) out[i] = CodeSrc{src[i].o, src[i].d_o, src[i].H, src[i].freq, src[i].col, src[i].ld};
+}
+
+int ss_op_dec_in(const ss_code_src* src, int nsrc, const float* emb, int emb_dim, int emb_col, float* dst, int ld, int B, int T, int f, void* stream) {
+    if (const char* m = dec_in_bad(src, nsrc, 4, false, emb, emb_dim, emb_col, dst, ld, B, T, f)) return fail(std::string("ss_op_dec_in: ") + m);
+    CodeSrc cs[4];
+    code_srcs(src, nsrc, cs);
+    if (f) HIPCHK(build_dec_in_compact(cs, nsrc, emb, emb_dim, emb_col, dst, ld, B, T, f, S(stream)));
+    else HIPCHK(build_dec_in(cs, nsrc, emb, emb_dim, emb_col, dst, ld, B, T, S(stream)));
+    return 0;
+}
+
+int ss_op_dec_in_grad(const ss_code_src* src, int nsrc, const float* d_in, int ld, int B, int T, int f, void* stream) {
+    if (const char* m = dec_in_bad(src, nsrc, 4, true, nullptr, 0, 0, d_in, ld, B, T, f)) return fail(std::string("ss_op_dec_in_grad: ") + m);
+    CodeSrc cs[4];
+    code_srcs(src, nsrc, cs);
+    if (f) HIPCHK(dec_in_grad_compact(cs, nsrc, d_in, ld, B, T, f, S(stream)));
+    else HIPCHK(dec_in_grad(cs, nsrc, d_in, ld, B, T, S(stream)));
+    return 0;
+}
+
+int ss_op_dec_in_codes(const ss_code_src* src, int nsrc, const float* emb, int emb_dim, int emb_col, float* codes, long codes_floats, float* dst, int ld,
+                       int B, int T, int f, void* stream) {
+    if (const char* m = dec_in_bad(src, nsrc, 3, false, emb, emb_dim, emb_col, dst, ld, B, T, f)) return fail(std::string("ss_op_dec_in_codes: ") + m);
+    long need = 0;
+    for (int i = 0; i < nsrc; ++i) need += ((long)B * (T / src[i].freq) * 2 * src[i].H + 3) / 4 * 4;
+    if (!codes || codes_floats < need || misaligned(codes, 16)) return fail("ss_op_dec_in_codes: codes_dev too small or not 16-byte aligned");
+    CodeOut co[3];
+    CodeIn ci[3];
+    float* p = codes;
+    for (int i = 0; i < nsrc; ++i) {
+        co[i] = CodeOut{src[i].o, p, src[i].H, src[i].freq, src[i].ld, 0};
+        ci[i] = CodeIn{p, src[i].H, src[i].freq, src[i].col};
+        p += ((long)B * (T / src[i].freq) * 2 * src[i].H + 3) / 4 * 4;
+    }
+    HIPCHK(export_codes(co, nsrc, B, T, S(stream)));
+    HIPCHK(dec_in_from_codes(ci, nsrc, emb, emb_dim, emb_col, dst, ld, B, T, f, S(stream)));
+    return 0;
+}
+
+int ss_op_spk_grad(const float* dg, long ld, long b_stride, int rows, const float* w_f, const float* w_r, long w_ld, int col0, int H4, int E, float* out,
+                   int B, void* stream) {
+    if (!dg || !w_f || !w_r || !out) return fail("ss_op_spk_grad: null pointer");
+    if (E < 1 || E > 1024 || H4 < 1 || rows < 1 || B < 1 || col0 < 0 || b_stride < 0) return fail("ss_op_spk_grad: needs 1 <= E <= 1024, H4 >= 1, rows >= 1, B >= 1, col0 >= 0");
+    if ((2L * H4 + (1024 / E) * E) * 4 > 64 * 1024) return fail("ss_op_spk_grad: 2 H4 + floor(1024 / E) E floats exceed 64 KiB of LDS");
+    if (ld < 2L * H4) return fail("ss_op_spk_grad: row stride below 2 H4");
+    if (w_ld < (long)col0 + E) return fail("ss_op_spk_grad: w_ld below col0 + E");
+    HIPCHK(spk_grad(dg, ld, b_stride, rows, w_f, w_r, w_ld, col0, H4, E, out, B, S(stream)));
+    return 0;
+}
+
 }  // extern "C"

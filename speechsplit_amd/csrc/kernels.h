@@ -183,7 +183,8 @@ hipError_t dec_in_from_codes(const CodeIn* src, int nsrc, const float* emb, int 
 
 // loss = mean((tgt - out)^2) over B*T*C real elements (solver.py:166); d_out = 2 (out - tgt) / N * scale
 hipError_t mse_loss(CRows out, CRows tgt, Rows d_out, int B, int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s);
-// softmax cross-entropy over C classes against integer targets; mean over B*T rows
+// softmax cross-entropy over C classes against integer targets in [0, C) (not checked on the device); mean over B*T rows.  Shift-invariant:
+// the log-softmax is (x - max) - log(sum exp(x - max)), never through max + log(..)
 hipError_t ce_loss(CRows logits, const int* tgt, Rows d_out, int B, int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s);
 
 struct AdamState {        // device-resident so a captured graph can replay the step

@@ -926,6 +926,109 @@ def lstm_wgrad(dg, x, hout, scratch=None, out=None):
     return gwih, gwhh, gb
 
 
+def _view3(t, name, dtype=torch.float32):
+    """A [B, T, C] view with unit channel stride -> (pointer to frame 0 of utterance 0, ld, bs)."""
+    if t.dim() != 3 or t.stride(2) != 1 or t.dtype != dtype:
+        raise ValueError(f'speechsplit_amd: {name} must be a [B, T, C] view with unit channel stride, got {tuple(t.shape)}')
+    return _ptr(t), t.stride(1), t.stride(0)
+
+
+def mse_loss(out, tgt, d_out, partials, loss, grad_scale=1.0):
+    """Test hook (ss_op_mse_loss): the MSE loss kernels on the caller's [B, T, C] views.  d_out is written, partials (>= 8 B floats) is
+    scratch, loss one float."""
+    B, T, Cc = out.shape
+    assert tuple(tgt.shape) == (B, T, Cc) and tuple(d_out.shape) == (B, T, Cc) and partials.numel() >= 8 * B
+    (op, o_ld, o_bs), (tp, t_ld, t_bs), (dp, d_ld, d_bs) = _view3(out, 'out'), _view3(tgt, 'tgt'), _view3(d_out, 'd_out')
+    _capi.check(_capi.lib().ss_op_mse_loss(op, o_ld, o_bs, tp, t_ld, t_bs, dp, d_ld, d_bs, B, T, Cc, float(grad_scale), _ptr(partials), _ptr(loss),
+                                           _stream()))
+    return loss
+
+
+def ce_loss(logits, tgt, d_out, partials, loss, grad_scale=1.0):
+    """Test hook (ss_op_ce_loss): softmax cross-entropy on the caller's [B, T, C] views against tgt i32 [B, T] (dense).  The targets are
+    asserted to lie in [0, C) here, on the host: the device does not check them."""
+    B, T, Cc = logits.shape
+    assert tuple(d_out.shape) == (B, T, Cc) and partials.numel() >= B * T
+    if tgt.dtype != torch.int32 or tuple(tgt.shape) != (B, T) or not tgt.is_contiguous():
+        raise ValueError('speechsplit_amd: tgt must be a contiguous i32 [B, T]')
+    if int(tgt.min()) < 0 or int(tgt.max()) >= Cc:
+        raise ValueError('speechsplit_amd: ce_loss: a target lies outside [0, C)')
+    (lp, l_ld, l_bs), (dp, d_ld, d_bs) = _view3(logits, 'logits'), _view3(d_out, 'd_out')
+    _capi.check(_capi.lib().ss_op_ce_loss(lp, l_ld, l_bs, _ptr(tgt), dp, d_ld, d_bs, B, T, Cc, float(grad_scale), _ptr(partials), _ptr(loss),
+                                          _stream()))
+    return loss
+
+
+def colsum_scratch_doubles(cols):
+    """float64 words of scratch the chunked column sum needs (ss_op_colsum_scratch_doubles)."""
+    return int(_capi.lib().ss_op_colsum_scratch_doubles(cols))
+
+
+def colsum(x, outs, two_dir=False, part=None, ctr=None):
+    """Test hook (ss_op_colsum): column sums of x [R, cols] (a view, unit column stride) ADDED to outs: (o0,) with cols = C, or
+    (o0, o1, o2, o3) with cols = 2 C (o1 / o3 may be None).  part (float64) / ctr (i32, zero): the chunked form's scratch."""
+    R, cols = x.shape
+    assert x.stride(1) == 1 and x.dtype == torch.float32
+    outs = tuple(outs) + (None,) * (4 - len(outs))
+    Cc = cols // 2 if two_dir else cols
+    assert not two_dir or cols % 2 == 0
+    assert all(o is None or (o.is_contiguous() and o.numel() >= Cc) for o in outs)
+    assert part is None or part.dtype == torch.float64
+    assert ctr is None or ctr.dtype == torch.int32
+    _capi.check(_capi.lib().ss_op_colsum(_ptr(x), x.stride(0) if R > 1 else max(cols, x.stride(0)), R, Cc, 1 if two_dir else 0, *[_ptr(o) for o in outs],
+                                         _ptr(part), part.numel() if part is not None else 0, _ptr(ctr), ctr.numel() if ctr is not None else 0,
+                                         _stream()))
+    return outs
+
+
+def _code_srcs(srcs, B, T, grad):
+    """[(slab view [B, T+4, 2H] with row stride ld and batch stride (T+4) ld, H, freq, col)] -> the ss_code_src array."""
+    arr = (_capi.SSCodeSrc * len(srcs))()
+    for i, (t, H, freq, col) in enumerate(srcs):
+        if tuple(t.shape) != (B, T + 4, 2 * H) or t.stride(2) != 1 or t.dtype != torch.float32 or (B > 1 and t.stride(0) != (T + 4) * t.stride(1)):
+            raise ValueError(f'speechsplit_amd: source {i} must be a float32 slab view [B, T + 4, 2H] whose utterances follow each other')
+        arr[i] = _capi.SSCodeSrc(None if grad else t.data_ptr(), t.data_ptr() if grad else None, H, freq, col, t.stride(1))
+    return arr
+
+
+def dec_in(srcs, emb, emb_col, dst, T, f=0, via_codes=None):
+    """Test hook (ss_op_dec_in): the decoder input from encoder BLSTM output slabs srcs = [(o, H, freq, col)] and speaker rows emb [B, E]
+    (None: no speaker columns) into dst: [B, T+4, ld] contiguous (f == 0, halo rows untouched) or [B, T/f, ld] (f > 0, the compact form).
+    via_codes: a float32 scratch tensor -- go through dense codes instead (ss_op_dec_in_codes: export_codes, then dec_in_from_codes)."""
+    B, rows, ld = dst.shape
+    assert dst.is_contiguous() and rows == (T // f if f else T + 4)
+    E = 0 if emb is None else emb.shape[1]
+    assert emb is None or (emb.is_contiguous() and emb.shape[0] == B)
+    arr = _code_srcs(srcs, B, T, False)
+    if via_codes is not None:
+        _capi.check(_capi.lib().ss_op_dec_in_codes(arr, len(srcs), _ptr(emb), E, emb_col, _ptr(via_codes), via_codes.numel(), _ptr(dst), ld, B, T, f,
+                                                   _stream()))
+    else:
+        _capi.check(_capi.lib().ss_op_dec_in(arr, len(srcs), _ptr(emb), E, emb_col, _ptr(dst), ld, B, T, f, _stream()))
+    return dst
+
+
+def dec_in_grad(srcs, d_in, T, f=0):
+    """Test hook (ss_op_dec_in_grad): the adjoint of dec_in.  srcs = [(d_o, H, freq, col)], the gradient slabs written (real columns of
+    real rows only); d_in [B, T+4, ld] contiguous (f == 0) or the block sums [B, T/f, ld] (f > 0)."""
+    B, rows, ld = d_in.shape
+    assert d_in.is_contiguous() and rows == (T // f if f else T + 4)
+    arr = _code_srcs(srcs, B, T, True)
+    _capi.check(_capi.lib().ss_op_dec_in_grad(arr, len(srcs), _ptr(d_in), ld, B, T, f, _stream()))
+
+
+def spk_grad(dg, w_f, w_r, col0, E, out):
+    """Test hook (ss_op_spk_grad): the speaker-embedding contraction.  dg [B, rows, 2 H4] (a view), w_f / w_r [H4, >= col0 + E] (views),
+    out [B, E] contiguous: out[b] = (sum over rows of dg[b]) . [w_f ; w_r][:, col0 : col0 + E]."""
+    B, rows, G = dg.shape
+    H4 = G // 2
+    assert dg.stride(2) == 1 and w_f.stride(1) == 1 and w_r.stride(1) == 1 and w_f.stride(0) == w_r.stride(0) and w_f.shape[0] == H4 == w_r.shape[0]
+    assert out.is_contiguous() and tuple(out.shape) == (B, E)
+    _capi.check(_capi.lib().ss_op_spk_grad(_ptr(dg), dg.stride(1), dg.stride(0), rows, _ptr(w_f), _ptr(w_r), w_f.stride(0), col0, H4, E, _ptr(out), B,
+                                           _stream()))
+    return out
+
+
 def small_lstm_ld(H):
     """Row stride of the output / cell-state / output-gradient slabs of a BLSTM layer (kernels.h lstm_small_ld): 2H, rounded up to a
     multiple of 4 floats when H <= 32 is not a power of two."""
