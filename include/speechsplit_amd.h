@@ -553,6 +553,56 @@ int  ss_op_stft (const double* wav_dev,  const int* frames_dev, int B, int max_f
 int  ss_op_istft(const double* spec_dev, const int* frames_dev, int B, int max_frames, double* wav_dev,
                  void* scratch_dev, long scratch_bytes, void* stream);
 
+/* ---- conversion scores: mel-cepstral distortion along a dynamic-time-warping (DTW) path, and F0 / voicing error along the same path ----
+ * Nothing to mirror: the reference never scores a conversion.  What a converted utterance is compared with -- the source, or a recording of
+ * the target speaker -- has another length (a rhythm conversion changes it by construction), so the comparison runs along an alignment.
+ *
+ * Cepstra.  mel f32 [B][max_t][n_mels], dct f64 [n_ceps][n_mels] (the host computes it), out f64 [B][max_t][n_ceps]:
+ *     c[b][t][d] = sum_m dct[d][m] * (double)mel[b][t][m],  m = 0, 1, ... in order; multiply-adds may be fused.
+ * The Python layer passes rows d = 1 .. n_ceps of the orthonormal DCT-II, sqrt(2 / n_mels) cos(pi d (m + 1/2) / n_mels); row 0, the level,
+ * is left out.  Rows at or beyond len[b] are exact zeros.
+ *
+ * Frame distance.  d(i, j) = scale * sqrt(sum_k (fx[i][k] - fy[j][k])^2): k runs in order, the root comes after the sum and `scale` is
+ * applied after the root.  This project's mels are S = (dB + 100) / 100, so ln|A| = (100 S - 84) ln 10 / 20 and the usual
+ * (10 / ln 10) sqrt(2 sum dc^2) of the log-amplitude cepstra is scale = 50 sqrt(2) on the cepstra of S; the Python layer passes that value.
+ *
+ * DTW.  Steps (1,1), (1,0), (0,1), each of weight 1; both ends are fixed.
+ *     D(0,0) = d(0,0);   D(i,j) = d(i,j) + min(D(i-1,j-1), D(i-1,j), D(i,j-1)),   predecessors outside the lattice are absent.
+ * The candidates are tried in that order with a strict <: on a tie the diagonal wins, then (i-1, j).  Backtrack from (Tx-1, Ty-1) to (0,0);
+ * the path is reported first step to last as (i, j) pairs, P is its length, max(Tx, Ty) <= P <= Tx + Ty - 1;
+ * total = D(Tx-1, Ty-1) and mcd = total / P.  There is no band and no slope constraint.
+ *
+ * F0 along the path.  f0x [B][max_tx], f0y [B][max_ty] follow ss_pitch_track's convention: ln Hz, -1e10 for unvoiced frames; a frame is
+ * voiced when its value is finite and > -1e9.  Over the P steps (lx = f0x[i], ly = f0y[j]): n_vv counts the steps where both frames are
+ * voiced, n_vu those where exactly one is;
+ *     f0_rmse_cents = (1200 / ln 2) sqrt(sum (lx - ly)^2 / n_vv)            NaN when n_vv == 0
+ *     f0_corr       = sxy / sqrt(sxx syy), the Pearson correlation of (lx, ly) over the both-voiced steps: the means first, then the
+ *                     centred sums sxx, syy, sxy                              NaN when n_vv < 2 or sxx or syy is 0
+ *     vuv_error     = n_vu / P
+ * Sums run in path order, one term at a time.
+ *
+ * Float64 throughout, no atomics: the same bits on every run, and a pair inside a ragged batch gives, bit for bit, what it gives alone (D
+ * depends on one add per cell, so the kernel's tiling cannot show).  No engine needed, no allocation inside, asynchronous on `stream`.
+ * Shapes: fx [B][max_tx][dim], fy [B][max_ty][dim]; out [B][3] = total, P, mcd; path i32 [B][max_tx + max_ty - 1][2], entries beyond P
+ * are -1; path_len i32 [B]; stats out [B][5] = n_vv, n_vu, f0_rmse_cents, f0_corr, vuv_error.  path_dev and path_len_dev of the DTW call are
+ * both NULL (totals only) or both given.  The statistics call clamps every path entry into the lattice and path_len into
+ * 0 .. max_tx + max_ty - 1 (NULL: that many), so a corrupt path changes numbers, never addresses.
+ * len_dev / tx_dev / ty_dev i32[B] (NULL: every row is full): row b is the result of running that pair alone at min(max(len[b], 1), max)
+ * frames -- a length outside 1 .. max spoils that row only; frames at or beyond it are never read (they may hold NaN).
+ * The scratch (backpointers of 2 bits a cell, and one boundary row of D a pair):
+ *     B * (align256(max_tx * ceil(max_ty / 4)) + align256(8 max_ty)) bytes, in long arithmetic.
+ * Refused before anything is enqueued, with a message that names the argument: null required pointers, B outside 1 .. 65535, max_t / max_tx /
+ * max_ty outside 1 .. SS_MAX_EVAL_FRAMES, n_mels outside 1 .. 128, n_ceps or dim outside 1 .. 40, scale not finite or <= 0, path_dev and
+ * path_len_dev not both NULL or both given, scratch_bytes below what the scratch query returns, scratch_dev not 256-byte aligned. */
+int  ss_mel_cepstra(const float* mel_dev, const int* len_dev, int B, int max_t, int n_mels, const double* dct_dev, int n_ceps,
+                    double* out_dev, void* stream);
+long ss_dtw_scratch_bytes(int B, int max_tx, int max_ty);     /* host only; -1 + ss_last_error on bad arguments */
+int  ss_dtw(const double* fx_dev, const int* tx_dev, const double* fy_dev, const int* ty_dev, int B, int max_tx, int max_ty, int dim,
+            double scale, double* out_dev /* [B][3] total, P, mcd */, int* path_dev /* [B][max_tx+max_ty-1][2] or NULL */,
+            int* path_len_dev /* [B] or NULL */, void* scratch_dev, long scratch_bytes, void* stream);
+int  ss_path_f0_stats(const int* path_dev, const int* path_len_dev, const double* f0x_dev, const double* f0y_dev, int B, int max_tx,
+                      int max_ty, double* out_dev /* [B][5] n_vv, n_vu, f0_rmse_cents, f0_corr, vuv_error */, void* stream);
+
 /* Batch producer on the GPU side (replaces the host loop of MyCollator.__call__, reference data_loader.py:101-128, for a
  * corpus kept resident in HBM): utterance b of the batch is rows [row0[b], row0[b] + len[b]) of the concatenated corpus
  * mel_cat [rows, n_mel] / f0_cat [rows]; the host only draws the crops (same generator calls, same order as the reference).

@@ -165,6 +165,12 @@ SYMBOLS = {
     'ss_mel_to_linear_nnls': (_i, [_fp, _vp, _vp, _l, _ip, _i, _i, _i, _i, _d, _d, _vp, _vp]),
     'ss_op_stft': (_i, [_vp, _ip, _i, _i, _vp, _vp]),
     'ss_op_istft': (_i, [_vp, _ip, _i, _i, _vp, _vp, _l, _vp]),
+    # mel, len, B, max_t, n_mels, dct, n_ceps, out, stream / fx, tx, fy, ty, B, max_tx, max_ty, dim, scale, out, path, path_len, scratch, bytes, stream
+    'ss_mel_cepstra': (_i, [_fp, _ip, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'ss_dtw_scratch_bytes': (_l, [_i, _i, _i]),
+    'ss_dtw': (_i, [_vp, _ip, _vp, _ip, _i, _i, _i, _i, _d, _vp, _ip, _ip, _vp, _l, _vp]),
+    # path, path_len, f0x, f0y, B, max_tx, max_ty, out, stream
+    'ss_path_f0_stats': (_i, [_ip, _ip, _vp, _vp, _i, _i, _i, _vp, _vp]),
     'ss_collate': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'ss_set_precision': (_i, [_vp, _i]),
     'ss_profile': (_i, [_vp, C.c_uint]),

@@ -180,3 +180,23 @@ def conversion_waveforms(results, **kw):
         return out
     it = iter(out)
     return [[next(it) for _ in pair] for pair in results]
+
+
+def conversion_scores(results, targets, **kw):
+    """demo_conversion's output ``[(name, mel[len, 80])]`` and one target mel per entry -> ``[(name, score dict)]``: the mel-cepstral
+    distortion of each converted mel against its target along a DTW path (metrics.mcd_dtw; with ``f0x=`` / ``f0y=`` tracks, flat in the same
+    order, also the F0 and voicing error).  convert_batch's output (one such list per pair) with targets nested the same way -> one such
+    list per pair.  All the mels go through ONE metrics.mcd_dtw call; keyword arguments are handed on to it."""
+    from . import metrics                               # metrics imports plan_batches from here
+    results, targets = list(results), list(targets)
+    nested = bool(results) and isinstance(results[0], list)
+    flat = [r for pair in results for r in pair] if nested else results
+    flat_t = [t for pair in targets for t in pair] if nested else targets
+    if len(flat_t) != len(flat) or (nested and [len(p) for p in targets] != [len(p) for p in results]):
+        raise ValueError('conversion_scores: targets must hold one mel per result, nested as results is')
+    scores = metrics.mcd_dtw([mel for _, mel in flat], flat_t, **kw)
+    out = [(name, s) for (name, _), s in zip(flat, scores)]
+    if not nested:
+        return out
+    it = iter(out)
+    return [[next(it) for _ in pair] for pair in results]

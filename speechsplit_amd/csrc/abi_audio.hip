@@ -1,5 +1,5 @@
 // C entry points of the audio / data front end (include/speechsplit_amd.h): collation, mel spectrograms, F0 normalisation, the pitch
-// tracker, batched feature extraction, the resampler, numpy's MT19937 stream and the Griffin-Lim vocoder.  None of them takes an engine: each checks its arguments, refuses by
+// tracker, batched feature extraction, the resampler, numpy's MT19937 stream, the Griffin-Lim vocoder and the conversion scores.  None of them takes an engine: each checks its arguments, refuses by
 // the argument's name through ss_last_error() and hands the rest to the launchers of kernels.h.
 #include <cmath>
 #include <cstdint>
@@ -355,6 +355,63 @@ int ss_op_istft(const double* spec, const int* frames, int B, int max_frames, do
     CHK(voc_shape("ss_op_istft", B, max_frames));
     CHK(voc_scratch("ss_op_istft", B, max_frames, scratch, scratch_bytes));
     HIPCHK(istft(spec, frames, B, max_frames, wav, vocoder_scratch(scratch, B, max_frames).frame_buf, S(stream)));
+    return 0;
+}
+
+// ---- conversion scores (dtw.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+namespace {
+int dtw_shape(const char* who, int B, int max_tx, int max_ty) {
+    if (B < 1 || B > DTW_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
+    if (max_tx < 1 || max_tx > SS_MAX_EVAL_FRAMES) return fail(std::string(who) + ": max_tx outside 1 .. SS_MAX_EVAL_FRAMES");
+    if (max_ty < 1 || max_ty > SS_MAX_EVAL_FRAMES) return fail(std::string(who) + ": max_ty outside 1 .. SS_MAX_EVAL_FRAMES");
+    return 0;
+}
+}  // namespace
+
+static_assert(DTW_MAX_DIM == 40 && DTW_MAX_ROWS == 65535, "the refusals below and the header spell these numbers out");
+
+int ss_mel_cepstra(const float* mel, const int* len, int B, int max_t, int n_mels, const double* dct, int n_ceps, double* out, void* stream) {
+    if (!mel) return fail("ss_mel_cepstra: null pointer: mel_dev");
+    if (!dct) return fail("ss_mel_cepstra: null pointer: dct_dev");
+    if (!out) return fail("ss_mel_cepstra: null pointer: out_dev");
+    if (B < 1 || B > DTW_MAX_ROWS) return fail("ss_mel_cepstra: B outside 1 .. 65535");
+    if (max_t < 1 || max_t > SS_MAX_EVAL_FRAMES) return fail("ss_mel_cepstra: max_t outside 1 .. SS_MAX_EVAL_FRAMES");
+    if (n_mels < 1 || n_mels > 128) return fail("ss_mel_cepstra: n_mels outside 1 .. 128");
+    if (n_ceps < 1 || n_ceps > DTW_MAX_DIM) return fail("ss_mel_cepstra: n_ceps outside 1 .. 40");
+    HIPCHK(mel_cepstra(mel, len, B, max_t, n_mels, dct, n_ceps, out, S(stream)));
+    return 0;
+}
+
+long ss_dtw_scratch_bytes(int B, int max_tx, int max_ty) {
+    CHK(dtw_shape("ss_dtw_scratch_bytes", B, max_tx, max_ty));
+    return dtw_scratch_bytes(B, max_tx, max_ty);
+}
+
+int ss_dtw(const double* fx, const int* tx, const double* fy, const int* ty, int B, int max_tx, int max_ty, int dim, double scale,
+           double* out, int* path, int* path_len, void* scratch, long scratch_bytes, void* stream) {
+    if (!fx) return fail("ss_dtw: null pointer: fx_dev");
+    if (!fy) return fail("ss_dtw: null pointer: fy_dev");
+    if (!out) return fail("ss_dtw: null pointer: out_dev");
+    CHK(dtw_shape("ss_dtw", B, max_tx, max_ty));
+    if (dim < 1 || dim > DTW_MAX_DIM) return fail("ss_dtw: dim outside 1 .. 40");
+    if (!(scale > 0.0) || std::isinf(scale)) return fail("ss_dtw: scale is not finite or not positive");
+    if (!path != !path_len) return fail("ss_dtw: path_dev and path_len_dev must both be given or both be NULL");
+    if (!scratch) return fail("ss_dtw: null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail("ss_dtw: scratch_dev is not 256-byte aligned");
+    if (scratch_bytes < dtw_scratch_bytes(B, max_tx, max_ty))
+        return fail("ss_dtw: scratch_bytes below ss_dtw_scratch_bytes(B, max_tx, max_ty)");
+    HIPCHK(dtw(fx, tx, fy, ty, B, max_tx, max_ty, dim, scale, out, path, path_len, dtw_scratch(scratch, B, max_tx, max_ty), S(stream)));
+    return 0;
+}
+
+int ss_path_f0_stats(const int* path, const int* path_len, const double* f0x, const double* f0y, int B, int max_tx, int max_ty, double* out,
+                     void* stream) {
+    if (!path) return fail("ss_path_f0_stats: null pointer: path_dev");
+    if (!f0x) return fail("ss_path_f0_stats: null pointer: f0x_dev");
+    if (!f0y) return fail("ss_path_f0_stats: null pointer: f0y_dev");
+    if (!out) return fail("ss_path_f0_stats: null pointer: out_dev");
+    CHK(dtw_shape("ss_path_f0_stats", B, max_tx, max_ty));
+    HIPCHK(path_f0_stats(path, path_len, f0x, f0y, B, max_tx, max_ty, out, S(stream)));
     return 0;
 }
 

@@ -362,6 +362,30 @@ hipError_t pitch_nccf(const double* wav, const int* n, int B, int max_n, double 
 hipError_t pitch_dp(const double* phi, const double* rms, const int* n, int B, int max_n, const PitchLags& g, double* f0,
                     const PitchScratch& sc, hipStream_t s);
 
+// ---------------------------------------------------------------- dtw.hip  (conversion scores: cepstra, DTW path and cost, F0 error along a path)
+// Shapes: mel [B][max_t][n_mels] f32, dct [n_ceps][n_mels], cepstra [B][max_t][n_ceps]; fx [B][max_tx][dim], fy [B][max_ty][dim],
+// out [B][3] (total, P, mcd), path [B][max_tx + max_ty - 1][2] (i, j; -1 beyond P), path_len [B]; f0x [B][max_tx], f0y [B][max_ty],
+// stats [B][5] (n_vv, n_vu, f0_rmse_cents, f0_corr, vuv_error).  Lengths (nullable; device i32[B]): a row has min(max(len[b], 1), max)
+// frames, is computed as if it were alone, and frames at or beyond its length are never read.
+constexpr int DTW_MAX_ROWS = 65535;   // ss_dtw_scratch_bytes' corner: the product stays inside a long
+constexpr int DTW_MAX_DIM = 40;       // a row of fx sits in registers: 80 VGPRs at 40 doubles
+constexpr int DTW_STRIP = 64;         // rows of the lattice swept at a time, one per lane of a wavefront
+struct DtwScratch {
+    unsigned char* bp;   // [B][bp_stride]    backpointers, 2 bits a cell: row i of a pair at i * ceil(max_ty / 4)
+    double* brow;        // [B][brow_stride]  the bottom row of D of the strip before
+    long bp_stride, brow_stride;
+};
+long dtw_scratch_bytes(int B, int max_tx, int max_ty);
+DtwScratch dtw_scratch(void* base, int B, int max_tx, int max_ty);
+hipError_t mel_cepstra(const float* mel, const int* len, int B, int max_t, int n_mels, const double* dct, int n_ceps, double* out,
+                       hipStream_t s);
+// one workgroup of four wavefronts per pair: the recurrence over row strips, the backtrack and the path, in one launch; path and path_len
+// may both be nullptr
+hipError_t dtw(const double* fx, const int* tx, const double* fy, const int* ty, int B, int max_tx, int max_ty, int dim, double scale,
+               double* out, int* path, int* path_len, const DtwScratch& sc, hipStream_t s);
+hipError_t path_f0_stats(const int* path, const int* path_len, const double* f0x, const double* f0y, int B, int max_tx, int max_ty,
+                         double* out, hipStream_t s);
+
 // ---------------------------------------------------------------- lstm_small.hip  (hidden <= 32: whole recurrence in one launch)
 // Row stride of a small BLSTM's output, cell-state and output-gradient slabs: 2H for H a power of two (the default widths keep their
 // layout), else 2H rounded up to a multiple of 4 floats (16-byte rows: vector loads and the GEMMs' aligned path).  The padding columns
