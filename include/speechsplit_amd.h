@@ -548,6 +548,70 @@ long ss_mel_nnls_pack(const double* basis_host /* [513][n_mels] */, int n_mels, 
 int  ss_mel_to_linear_nnls(const float* mel_dev, const double* inv_basis_dev, const double* packed_dev, long packed_doubles,
                            const int* frames_dev, int B, int max_frames, int n_mels, int n_iter, double step, double floor,
                            double* mag_dev, void* stream);
+/* F0-guided harmonic mel inversion and harmonic start phases.  Above about 1 kHz the mel bands are wider than the harmonic spacing, so
+ * both routes above hand Griffin-Lim a smooth spectrum with no harmonics in it.  With an F0 track a voiced frame is not 513 unknowns
+ * against n_mels equations but one amplitude per harmonic at a known frequency.  The F0 has to BELONG to the mel: 5 % off, the harmonic
+ * phases are worse than random ones.  All of it is float64.
+ *
+ * Constants.  fs = 16000, N = 1024, hop = 256, 513 bins, D = fs / N = 15.625 Hz.  f_top (1000 .. 8000 Hz; the Python layer passes 7600,
+ * the bank's fmax) is the highest harmonic frequency.
+ *
+ * Voiced frames.  f0_hz [B][max_frames] is in Hz (the Python layer converts from ss_pitch_track's ln Hz / -1e10, so the device takes no
+ * exponential).  A frame is VOICED when f = f0_hz is finite and 40 <= f <= 1000; anything else -- 0, NaN, negative, out of range -- is
+ * unvoiced and never an error.
+ *
+ * Per voiced frame, with amp_m = 10^((100 mel_m - 100 + 16) / 20), Bm the [513][n_mels] basis and P = inv_basis:
+ *   1. H = min(floor(f_top / f), 190) harmonics; harmonic h = 1 .. H sits at the fractional bin p_h = (h f) / D.
+ *   2. Atoms.  Dm[k][h] = 512 W(k - p_h), where W(d) = 0.5 s(d) + 0.25 s(d - 1) + 0.25 s(d + 1) for |d| < 2 and 0 otherwise, and
+ *      s(x) = sin(pi x) / (pi x), s(0) = 1: the main lobe of the periodic Hann window's transform for a unit cosine (in this form because
+ *      the closed form sin(pi d) / (2 pi d (1 - d^2)) cancels near d = +-1).  An atom touches at most the four bins
+ *      floor(p_h) - 1 .. floor(p_h) + 2; bins above 512 are dropped.
+ *   3. Fit.  a = argmin over a >= 0 of || (Dm a) Bm - amp ||^2 by projected FISTA from a = 0: ss_mel_to_linear_nnls's loop with
+ *      A = Bm^T Dm in place of Bm,
+ *          a = 0;  y = a;  t = 1
+ *          n_iter times:  r = (Dm y) Bm - amp;  g = Dm^T (Bm r);  an = max(y - step g, 0);  tn = (1 + sqrt(1 + 4 t^2)) / 2
+ *                         y = an + ((t - 1) / tn) (an - a);  t = tn;  a = an
+ *      step = 1 / L with L = (max over h of sum_m A[m][h]) (max over m of sum_h A[m][h]) = ||A||_1 ||A||_inf >= lambda_max(A^T A)
+ *      (every entry of A is non-negative), computed per frame on the device; step = 0 when L is 0.  A is never formed:
+ *      sum_h A[m][h] = ((Dm 1) Bm)_m and sum_m A[m][h] = (Dm^T (Bm 1))_h, through the loop's own three products.
+ *      Orders: a bin's (Dm y)_k runs over the harmonics that cover it in ascending h; a band's sum over its run of bins in bin order (from
+ *      0, amp subtracted last); a bin's (Bm r)_k over the bands that cover it in band order; a harmonic's g_h over its four bins in bin order.
+ *   4. mag_h = Dm a;  res_m = max(amp_m - (mag_h Bm)_m, 0);  mag_n = max(res P, 0) (m ascending, as ss_mel_to_linear).
+ *   5. mag = max(sqrt(mag_h^2 + mag_n^2), floor) and the harmonic share w = mag_h / sqrt(mag_h^2 + mag_n^2), 0 where both are 0.
+ *
+ * Unvoiced frames.  mag_dev is IN and OUT: the caller first fills it by either route above; unvoiced frames keep what is there and get
+ * w = 0, so with an all-unvoiced f0_hz the result is that route's to the bit.
+ *
+ * Start phases.  The fundamental's phase at the frame centres, in cycles, reduced at every step (hop / fs / 2 = 0.008):
+ *     u_0 = 0;   u_i = frac(u_{i-1} + 0.008 (f_{i-1} + f_i))  when frames i - 1 and i are both voiced;
+ *     u_i = 0 when frame i is voiced and frame i - 1 is not (and on unvoiced frames);   frac(t) = t - floor(t);   no operation is fused,
+ *     so u is what numpy computes, to the bit.
+ * Bin k of a voiced frame belongs to harmonic h_k = min(max(rint(k / p_1), 1), H), ties to even; its harmonic phase is
+ * phi_h = 2 pi frac(h_k u_i + 0.5 (k mod 2)) -- the half cycle is e^{-i pi k}: the frame starts 512 samples before its centre.  Then
+ *     phase0 = arg(w e^{i phi_h} + sqrt(max(1 - w^2, 0)) e^{i phi_rand}),   phi_rand = rand_phase_dev's element (NULL: 0).
+ * Unvoiced frames, and elements whose sum is exactly 0, keep phi_rand.  ss_griffinlim is unchanged: it receives mag and phase0.
+ *
+ * Kernel.  One workgroup of 256 threads per (frame, row) runs the whole fit in one launch with no global traffic inside the loop, no
+ * atomics and every sum in one fixed order: the same bits on every run.  The basis sits in LDS in ss_mel_nnls_pack's form -- the same
+ * buffer, the same 3072-double cap and the same clamping, so a corrupt buffer changes numbers, never addresses -- beside amp, r, the
+ * 513-bin model, its gradient and the harmonics' atoms (41804 bytes for 80 bands at the cap, at most 53452).  u is a serial recurrence:
+ * one wave per row runs it in registers, 64 frames per load; the fill runs per (frame, row) over 513 bins.
+ * Shapes: mel [B][max_frames][n_mels] f32; f0_hz [B][max_frames]; mag, share, rand_phase, phase0 [B][max_frames][513].  frames_dev and the
+ * ragged rules are ss_mel_to_linear's: row b is bit for bit the result of running it alone at min(max(frames[b], 4), max_frames) frames;
+ * nothing at or beyond them is read in mel, f0_hz, share or rand_phase (they may hold NaN); there mag is left as the caller's route wrote
+ * it, and share and phase0 are zeros.  No engine needed, no allocation inside, asynchronous on `stream`.
+ * Refused before anything is enqueued, with a message that names the argument: null required pointers (rand_phase_dev may be NULL),
+ * B < 1, max_frames outside 4 .. SS_MAX_EVAL_FRAMES, n_mels outside 1 .. 4096, packed_doubles outside 2 n_mels .. 515 n_mels or above 3072,
+ * f_top outside 1000 .. 8000 or NaN, n_iter outside 0 .. 100000, negative or NaN floor, scratch_bytes below
+ * ss_harmonic_phase_scratch_bytes(B, max_frames) or scratch_dev not 256-byte aligned. */
+int  ss_mel_to_linear_harmonic(const float* mel_dev, const double* f0_hz_dev, const double* inv_basis_dev, const double* packed_dev,
+                               long packed_doubles, const int* frames_dev, int B, int max_frames, int n_mels, double f_top, int n_iter,
+                               double floor, double* mag_dev /* in/out */, double* share_dev /* out */, void* stream);
+long ss_harmonic_phase_scratch_bytes(int B, int max_frames); /* host only; -1 + ss_last_error on bad arguments */
+int  ss_harmonic_phase(const double* f0_hz_dev, const double* share_dev, const double* rand_phase_dev, const int* frames_dev, int B,
+                       int max_frames, double f_top, double* phase0_dev /* out */, void* scratch_dev, long scratch_bytes, void* stream);
+/* test hook: the recurrence alone, u_dev [B][max_frames] (zeros on unvoiced frames and behind a row's own) */
+int  ss_op_harmonic_u(const double* f0_hz_dev, const int* frames_dev, int B, int max_frames, double* u_dev, void* stream);
 /* test hooks, each half alone: spec [B][max_frames][513][2] (re, im); ss_op_istft takes the same scratch as ss_griffinlim */
 int  ss_op_stft (const double* wav_dev,  const int* frames_dev, int B, int max_frames, double* spec_dev, void* stream);
 int  ss_op_istft(const double* spec_dev, const int* frames_dev, int B, int max_frames, double* wav_dev,

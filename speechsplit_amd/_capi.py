@@ -163,6 +163,12 @@ SYMBOLS = {
     # basis_host, n_mels, packed_host, cap / mel, inv_basis, packed, packed_doubles, frames, B, max_frames, n_mels, n_iter, step, floor, mag, stream
     'ss_mel_nnls_pack': (_l, [_vp, _i, _vp, _l]),
     'ss_mel_to_linear_nnls': (_i, [_fp, _vp, _vp, _l, _ip, _i, _i, _i, _i, _d, _d, _vp, _vp]),
+    # mel, f0_hz, inv_basis, packed, packed_doubles, frames, B, max_frames, n_mels, f_top, n_iter, floor, mag, share, stream
+    'ss_mel_to_linear_harmonic': (_i, [_fp, _vp, _vp, _vp, _l, _ip, _i, _i, _i, _d, _i, _d, _vp, _vp, _vp]),
+    'ss_harmonic_phase_scratch_bytes': (_l, [_i, _i]),
+    # f0_hz, share, rand_phase, frames, B, max_frames, f_top, phase0, scratch, scratch_bytes, stream
+    'ss_harmonic_phase': (_i, [_vp, _vp, _vp, _ip, _i, _i, _d, _vp, _vp, _l, _vp]),
+    'ss_op_harmonic_u': (_i, [_vp, _ip, _i, _i, _vp, _vp]),
     'ss_op_stft': (_i, [_vp, _ip, _i, _i, _vp, _vp]),
     'ss_op_istft': (_i, [_vp, _ip, _i, _i, _vp, _vp, _l, _vp]),
     # mel, len, B, max_t, n_mels, dct, n_ceps, out, stream / fx, tx, fy, ty, B, max_tx, max_ty, dim, scale, out, path, path_len, scratch, bytes, stream

@@ -166,14 +166,22 @@ def convert_batch(G, P, pairs, max_len_pad=192, max_rows=16, device='cuda:0', co
     return res
 
 
-def conversion_waveforms(results, **kw):
+def conversion_waveforms(results, f0s=None, **kw):
     """demo_conversion's output ``[(name, mel[len, 80])]`` -> ``[(name, wav float64[256 (len - 1)])]`` at 16 kHz through the Griffin-Lim
     vocoder; convert_batch's output (one such list per pair) -> one such list per pair.  All the mels go through ONE vocoder.griffin_lim call
-    (ragged batches of at most ``max_rows`` rows); keyword arguments are handed on to it."""
+    (ragged batches of at most ``max_rows`` rows); keyword arguments are handed on to it.  ``f0s``: one F0 track per entry (ln Hz, -1e10
+    unvoiced, as long as its mel; features.f0_from_norm makes one), nested as ``results`` is: the harmonic route of vocoder.griffin_lim."""
     from . import vocoder                               # vocoder imports plan_batches from here
     results = list(results)
     nested = bool(results) and isinstance(results[0], list)
     flat = [r for pair in results for r in pair] if nested else results
+    if f0s is not None:
+        f0s = list(f0s)
+        if nested and (len(f0s) != len(results) or [len(p) for p in f0s] != [len(p) for p in results]):
+            raise ValueError('conversion_waveforms: f0s must hold one track per result, nested as results is')
+        kw['f0'] = [t for pair in f0s for t in pair] if nested else f0s
+        if len(kw['f0']) != len(flat):
+            raise ValueError('conversion_waveforms: f0s must hold one track per result, nested as results is')
     wavs = vocoder.griffin_lim([mel for _, mel in flat], **kw)
     out = [(name, wav) for (name, _), wav in zip(flat, wavs)]
     if not nested:

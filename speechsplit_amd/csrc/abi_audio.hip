@@ -328,6 +328,58 @@ int ss_mel_to_linear_nnls(const float* mel, const double* inv_basis, const doubl
     return 0;
 }
 
+static_assert(HARM_MAX == 190, "the header spells this number out");
+
+int ss_mel_to_linear_harmonic(const float* mel, const double* f0_hz, const double* inv_basis, const double* packed, long packed_doubles,
+                              const int* frames, int B, int max_frames, int n_mels, double f_top, int n_iter, double floor, double* mag,
+                              double* share, void* stream) {
+    if (!mel) return fail("ss_mel_to_linear_harmonic: null pointer: mel_dev");
+    if (!f0_hz) return fail("ss_mel_to_linear_harmonic: null pointer: f0_hz_dev");
+    if (!inv_basis) return fail("ss_mel_to_linear_harmonic: null pointer: inv_basis_dev");
+    if (!packed) return fail("ss_mel_to_linear_harmonic: null pointer: packed_dev");
+    if (!mag) return fail("ss_mel_to_linear_harmonic: null pointer: mag_dev");
+    if (!share) return fail("ss_mel_to_linear_harmonic: null pointer: share_dev");
+    CHK(voc_shape("ss_mel_to_linear_harmonic", B, max_frames));
+    if (n_mels < 1 || n_mels > VOC_MAX_MELS) return fail("ss_mel_to_linear_harmonic: n_mels outside 1 .. 4096");
+    if (packed_doubles < 2L * n_mels || packed_doubles > 515L * n_mels)
+        return fail("ss_mel_to_linear_harmonic: packed_doubles disagrees with n_mels (2 n_mels + the number of weights, at most 513 a band)");
+    if (packed_doubles > NNLS_MAX_PACKED) return fail("ss_mel_to_linear_harmonic: packed_doubles beyond the 3072 the kernel's LDS holds");
+    if (!(f_top >= 1000.0 && f_top <= 8000.0)) return fail("ss_mel_to_linear_harmonic: f_top outside 1000 .. 8000 or NaN");
+    if (n_iter < 0 || n_iter > 100000) return fail("ss_mel_to_linear_harmonic: n_iter outside 0 .. 100000");
+    if (!(floor >= 0.0)) return fail("ss_mel_to_linear_harmonic: floor is negative or NaN");
+    HIPCHK(mel_to_linear_harmonic(mel, f0_hz, inv_basis, packed, packed_doubles, frames, B, max_frames, n_mels, f_top, n_iter, floor, mag,
+                                  share, S(stream)));
+    return 0;
+}
+
+long ss_harmonic_phase_scratch_bytes(int B, int max_frames) {
+    CHK(voc_shape("ss_harmonic_phase_scratch_bytes", B, max_frames));
+    return harmonic_phase_scratch_bytes(B, max_frames);
+}
+
+int ss_harmonic_phase(const double* f0_hz, const double* share, const double* rand_phase, const int* frames, int B, int max_frames,
+                      double f_top, double* phase0, void* scratch, long scratch_bytes, void* stream) {
+    if (!f0_hz) return fail("ss_harmonic_phase: null pointer: f0_hz_dev");
+    if (!share) return fail("ss_harmonic_phase: null pointer: share_dev");
+    if (!phase0) return fail("ss_harmonic_phase: null pointer: phase0_dev");
+    CHK(voc_shape("ss_harmonic_phase", B, max_frames));
+    if (!(f_top >= 1000.0 && f_top <= 8000.0)) return fail("ss_harmonic_phase: f_top outside 1000 .. 8000 or NaN");
+    if (!scratch) return fail("ss_harmonic_phase: null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail("ss_harmonic_phase: scratch_dev is not 256-byte aligned");
+    if (scratch_bytes < harmonic_phase_scratch_bytes(B, max_frames))
+        return fail("ss_harmonic_phase: scratch_bytes below ss_harmonic_phase_scratch_bytes(B, max_frames)");
+    HIPCHK(harmonic_phase(f0_hz, share, rand_phase, frames, B, max_frames, f_top, phase0, (double*)scratch, S(stream)));
+    return 0;
+}
+
+int ss_op_harmonic_u(const double* f0_hz, const int* frames, int B, int max_frames, double* u, void* stream) {
+    if (!f0_hz) return fail("ss_op_harmonic_u: null pointer: f0_hz_dev");
+    if (!u) return fail("ss_op_harmonic_u: null pointer: u_dev");
+    CHK(voc_shape("ss_op_harmonic_u", B, max_frames));
+    HIPCHK(harmonic_u(f0_hz, frames, B, max_frames, u, S(stream)));
+    return 0;
+}
+
 int ss_griffinlim(const double* mag, const double* phase0, const int* frames, int B, int max_frames, int n_iter, double momentum,
                   double* wav, void* scratch, long scratch_bytes, void* stream) {
     if (!mag) return fail("ss_griffinlim: null pointer: mag_dev");

@@ -324,6 +324,21 @@ constexpr long NNLS_MAX_PACKED = 3072;
 long mel_nnls_lds_bytes(int n_mels, long packed_doubles);
 hipError_t mel_to_linear_nnls(const float* mel, const double* inv_basis, const double* packed, long packed_doubles, const int* frames, int B,
                               int max_frames, int n_mels, int n_iter, double step, double floor, double* mag, hipStream_t s);
+// F0-guided harmonic inversion (see vocoder.hip and the header): on the voiced frames of f0_hz [B][max_frames] (Hz; voiced: 40 .. 1000) one
+// amplitude per harmonic is fitted to the mel by projected FISTA, one workgroup per frame, and mag (in/out) and share (out) are written;
+// every other frame keeps its mag and gets share 0.  The LDS image is the NNLS one plus the model, its gradient and the harmonics' atoms:
+// mel_harmonic_lds_bytes(n_mels, packed_doubles), 41804 bytes for 80 bands at NNLS_MAX_PACKED and at most 53452 (1536 empty bands).
+constexpr int HARM_MAX = 190;         // harmonics a frame can have: 7600 / 40
+long mel_harmonic_lds_bytes(int n_mels, long packed_doubles);
+hipError_t mel_to_linear_harmonic(const float* mel, const double* f0_hz, const double* inv_basis, const double* packed, long packed_doubles,
+                                  const int* frames, int B, int max_frames, int n_mels, double f_top, int n_iter, double floor,
+                                  double* mag, double* share, hipStream_t s);
+// u [B][max_frames]: the fundamental's phase at the frame centres in cycles, one wave per row (the recurrence is serial)
+long harmonic_phase_scratch_bytes(int B, int max_frames);
+hipError_t harmonic_u(const double* f0_hz, const int* frames, int B, int max_frames, double* u, hipStream_t s);
+// harmonic_u into u, then phase0 = arg(share e^{i phi_h} + sqrt(1 - share^2) e^{i rand}) on voiced frames, rand elsewhere (nullptr: zeros)
+hipError_t harmonic_phase(const double* f0_hz, const double* share, const double* rand, const int* frames, int B, int max_frames,
+                          double f_top, double* phase0, double* u, hipStream_t s);
 // melspec_kernel's framing with a 1024-point FFT in LDS, one workgroup per frame
 hipError_t stft(const double* wav, const int* frames, int B, int max_frames, double* spec, hipStream_t s);
 // window * irfft per frame into frame_buf, then a gather per output sample over the frames that cover it, over the sum of their squared windows

@@ -19,7 +19,10 @@
 //
 // Mel -> linear: mel_to_linear_kernel applies a caller-supplied pseudo-inverse and floors; mel_nnls_kernel goes on from there to the
 // non-negative magnitude whose mel is the given one, by projected FISTA, the whole iteration of a frame in one launch with the banded mel
-// basis packed in LDS (include/speechsplit_amd.h, ss_mel_to_linear_nnls; zero iterations are mel_to_linear_kernel to the bit).
+// basis packed in LDS (include/speechsplit_amd.h, ss_mel_to_linear_nnls; zero iterations are mel_to_linear_kernel to the bit).  With an F0
+// track, mel_harmonic_kernel overwrites the voiced frames with one fitted amplitude per harmonic plus a noise part, and harmonic_u_kernel /
+// harmonic_phase_kernel turn the track and the harmonic share into the phases Griffin-Lim starts from (ss_mel_to_linear_harmonic,
+// ss_harmonic_phase).
 //
 // Batches: row b has its own frame count F_b = min(max(frames[b], 4), max_frames) and n_b = 256 (F_b - 1) samples; every kernel computes row b
 // as if it were alone, never reads a spectrogram frame at or beyond F_b, and writes exact zeros behind n_b.
@@ -236,9 +239,306 @@ __global__ __launch_bounds__(NT) void mel_nnls_kernel(const float* __restrict__ 
         if (tid + j * NT < NBIN) mag[fr * NBIN + tid + j * NT] = fmax(x[j], floor);
 }
 
+// ---- F0-guided harmonic inversion (include/speechsplit_amd.h, ss_mel_to_linear_harmonic / ss_harmonic_phase)
+constexpr double HARM_BIN_HZ = 15.625;      // 16000 / 1024
+
+// finite and inside 40 .. 1000 Hz; NaN compares false
+__device__ inline bool harm_voiced(double f) { return f >= 40.0 && f <= 1000.0; }
+
+__device__ inline int harm_count(double f, double f_top) {
+    const double h = floor(f_top / f);
+    return h < (double)HARM_MAX ? (h > 1.0 ? (int)h : 1) : HARM_MAX;
+}
+
+__device__ inline double sincpi(double x) { return x == 0.0 ? 1.0 : sinpi(x) / (M_PI * x); }
+
+// the main lobe of the periodic Hann window's transform, as three shifted sincs: the closed form cancels near d = +-1
+__device__ inline double hann_lobe(double d) {
+    return fabs(d) < 2.0 ? 0.5 * sincpi(d) + 0.25 * sincpi(d - 1.0) + 0.25 * sincpi(d + 1.0) : 0.0;
+}
+
+// grid = (max_frames, B), block = 256, dynamic LDS = mel_harmonic_lds_bytes(n_mels, packed_doubles): one amplitude per harmonic of the
+// frame's F0 by projected FISTA from zero, the whole fit of one frame inside one launch.  The basis is mel_nnls_kernel's packed image with
+// the same clamping; beside it sit amp, r, the 513-bin model and its gradient, and -- because a bin's model is a gather over the
+// harmonics that cover it -- every harmonic's y, first bin and four weights.  Thread h - 1 keeps harmonic h's atom, a and y in registers.
+// Per round: the bins' model over the covering harmonics in ascending h, a barrier, band m's sum over its run in bin order (thread m), a
+// barrier, the bins' gradient over the covering bands in band order, a barrier, each harmonic's four-term dot product and the projected
+// update, a barrier.  No global traffic inside the loop, no atomics, every sum in one fixed order.  The step bound comes out of the same
+// three passes run once on ones.  Frames at or beyond the row's, and unvoiced frames: mel is not read, mag is left as it is, share is zeros.
+__global__ __launch_bounds__(NT) void mel_harmonic_kernel(const float* __restrict__ mel, const double* __restrict__ f0_hz,
+                                                          const double* __restrict__ inv_basis, const double* __restrict__ packed,
+                                                          int packed_doubles, const int* __restrict__ frames, int max_frames, int n_mels,
+                                                          double f_top, int n_iter, double floor_, double* __restrict__ mag,
+                                                          double* __restrict__ share) {
+    extern __shared__ double lds[];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const long fr = (long)b * max_frames + f;
+    const double hz = f < row_frames(frames, b, max_frames) ? f0_hz[fr] : 0.0;
+    if (!harm_voiced(hz)) {
+        for (int k = tid; k < NBIN; k += NT) share[fr * NBIN + k] = 0.0;
+        return;
+    }
+    const int H = harm_count(hz, f_top);
+    const int nnz = packed_doubles - 2 * n_mels;
+    double* w = lds;                        // [nnz]
+    double* amp = w + nnz;                  // [n_mels]
+    double* r = amp + n_mels;               // [n_mels]
+    double* model = r + n_mels;             // [NBIN + 1]
+    double* grad = model + NBIN + 1;        // [NBIN + 1]
+    double* ys = grad + NBIN + 1;           // [HARM_MAX]
+    double* aw = ys + HARM_MAX;             // [HARM_MAX][4]  harmonic h's weights on bins k0 .. k0 + 3
+    int* lo = (int*)(aw + 4 * HARM_MAX);    // [n_mels]      first bin of band m
+    int* off = lo + n_mels;                 // [n_mels + 1]  band m's weights are w[off[m] .. off[m + 1])
+    int* k0s = off + n_mels + 1;            // [HARM_MAX]    first bin of harmonic h's atom
+    for (int m = tid; m < n_mels; m += NT) {
+        amp[m] = pow(10.0, (100.0 * (double)mel[fr * n_mels + m] - 100.0 + 16.0) / 20.0);
+        const double first = packed[2 * m];
+        lo[m] = first >= 0.0 ? (first <= (double)(NBIN - 1) ? (int)first : NBIN - 1) : 0;       // NaN: 0
+    }
+    for (int i = tid; i < nnz; i += NT) w[i] = packed[2 * n_mels + i];
+    int k0 = 0;
+    double wt[4] = {0.0, 0.0, 0.0, 0.0};
+    if (tid < H) {
+        const double p = ((double)(tid + 1) * hz) / HARM_BIN_HZ;
+        const double base = floor(p) - 1.0;
+        k0 = base >= 0.0 ? (base <= (double)(NBIN - 1) ? (int)base : NBIN - 1) : 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            wt[j] = k0 + j < NBIN ? 512.0 * hann_lobe((double)(k0 + j) - p) : 0.0;
+            aw[4 * tid + j] = wt[j];
+        }
+        k0s[tid] = k0;
+        ys[tid] = 1.0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int o = 0;
+        for (int m = 0; m < n_mels; ++m) {
+            const double run = packed[2 * m + 1];
+            int len = run >= 0.0 ? (run <= (double)NBIN ? (int)run : NBIN) : 0;                 // NaN: 0
+            len = min(len, min(NBIN - lo[m], nnz - o));
+            off[m] = o;
+            o += len;
+        }
+        off[n_mels] = o;
+    }
+    __syncthreads();
+
+    constexpr int PER = (NBIN + NT - 1) / NT;   // 3: bins tid, tid + 256 and (thread 0) 512
+    int mfirst[PER], mlast[PER];                // the bands that cover the bin lie in mfirst .. mlast (empty: mfirst > mlast)
+    int hfirst[PER], hlast[PER];                // likewise the harmonics (0-based)
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int k = tid + j * NT;
+        mfirst[j] = n_mels;
+        hfirst[j] = H;
+        mlast[j] = hlast[j] = -1;
+        if (k < NBIN) {
+            for (int m = 0; m < n_mels; ++m)
+                if (k >= lo[m] && k - lo[m] < off[m + 1] - off[m]) {
+                    mfirst[j] = min(mfirst[j], m);
+                    mlast[j] = m;
+                }
+            for (int h = 0; h < H; ++h)
+                if (k >= k0s[h] && k - k0s[h] < 4) {
+                    hfirst[j] = min(hfirst[j], h);
+                    hlast[j] = h;
+                }
+        }
+    }
+    // the three passes of a round; the caller puts a barrier between any two
+    auto bins_model = [&]() {                   // model = D ys
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int k = tid + j * NT;
+            if (k >= NBIN) continue;
+            double s = 0.0;
+            for (int h = hfirst[j]; h <= hlast[j]; ++h) {
+                const int i = k - k0s[h];
+                if (i >= 0 && i < 4) s += aw[4 * h + i] * ys[h];
+            }
+            model[k] = s;
+        }
+    };
+    auto band_sum = [&](int m) {                // (model B)_m
+        const int o = off[m], len = off[m + 1] - o, kb = lo[m];
+        double s = 0.0;
+        for (int i = 0; i < len; ++i) s += model[kb + i] * w[o + i];
+        return s;
+    };
+    auto bins_grad = [&]() {                    // grad = B r
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const int k = tid + j * NT;
+            if (k >= NBIN) continue;
+            double g = 0.0;
+            for (int m = mfirst[j]; m <= mlast[j]; ++m) {
+                const int i = k - lo[m];
+                if (i >= 0 && i < off[m + 1] - off[m]) g += r[m] * w[off[m] + i];
+            }
+            grad[k] = g;
+        }
+    };
+    auto atom_dot = [&]() {                     // (D^T grad)_h; a weight behind bin 512 is zero and its index is held inside
+        double g = 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) g += wt[j] * grad[min(k0 + j, NBIN - 1)];
+        return g;
+    };
+
+    // L = ||A||_1 ||A||_inf for A = B^T D, which is never formed: its row sums are the band sums of the model of ones, its column sums
+    // the atoms' dot products with the gradient of ones
+    bins_model();
+    __syncthreads();
+    for (int m = tid; m < n_mels; m += NT) r[m] = band_sum(m);
+    __syncthreads();
+    double rows = 0.0;
+    for (int m = 0; m < n_mels; ++m) rows = fmax(rows, r[m]);
+    __syncthreads();
+    for (int m = tid; m < n_mels; m += NT) r[m] = 1.0;
+    __syncthreads();
+    bins_grad();
+    __syncthreads();
+    if (tid < H) ys[tid] = atom_dot();
+    __syncthreads();
+    double cols = 0.0;
+    for (int h = 0; h < H; ++h) cols = fmax(cols, ys[h]);
+    __syncthreads();
+    const double L = rows * cols;
+    const double step = L > 0.0 ? 1.0 / L : 0.0;
+
+    double a = 0.0, y = 0.0, t = 1.0;
+    if (tid < H) ys[tid] = 0.0;
+    __syncthreads();
+    for (int it = 0; it < n_iter; ++it) {
+        bins_model();
+        __syncthreads();
+        for (int m = tid; m < n_mels; m += NT) r[m] = band_sum(m) - amp[m];
+        __syncthreads();
+        bins_grad();
+        __syncthreads();
+        const double tn = (1.0 + sqrt(1.0 + 4.0 * t * t)) / 2.0;
+        const double beta = (t - 1.0) / tn;
+        t = tn;
+        if (tid < H) {
+            const double an = fmax(y - step * atom_dot(), 0.0);
+            y = an + beta * (an - a);
+            a = an;
+            ys[tid] = y;
+        }
+        __syncthreads();
+    }
+    if (tid < H) ys[tid] = a;
+    __syncthreads();
+    bins_model();                               // mag_h
+    __syncthreads();
+    for (int m = tid; m < n_mels; m += NT) r[m] = fmax(amp[m] - band_sum(m), 0.0);
+    __syncthreads();
+    for (int k = tid; k < NBIN; k += NT) {
+        double s = 0.0;
+        for (int m = 0; m < n_mels; ++m) s += r[m] * inv_basis[(long)m * NBIN + k];
+        const double mh = model[k], mn = fmax(s, 0.0);
+        const double q = sqrt(mh * mh + mn * mn);
+        mag[fr * NBIN + k] = fmax(q, floor_);
+        share[fr * NBIN + k] = q > 0.0 ? mh / q : 0.0;
+    }
+}
+
+// grid = B, block = 64 (one wave per row): the fundamental's phase at the frame centres, in cycles.  The recurrence is serial; the wave
+// loads 64 frames at a time, every lane forms its frame's increment, and the chain then runs in registers over the broadcast increments,
+// so no step waits for memory.  Unfused, so that the result is numpy's to the bit.  u is zero on unvoiced frames and behind the row's own.
+__global__ __launch_bounds__(64) void harmonic_u_kernel(const double* __restrict__ f0_hz, const int* __restrict__ frames, int max_frames,
+                                                        double* __restrict__ u) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int F = row_frames(frames, b, max_frames);
+    f0_hz += (long)b * max_frames;
+    u += (long)b * max_frames;
+    double carry = 0.0;
+    for (int i0 = 0; i0 < max_frames; i0 += 64) {
+        const int i = i0 + lane;
+        const double fi = i < F ? f0_hz[i] : 0.0, fp = i >= 1 && i < F ? f0_hz[i - 1] : 0.0;
+        const int chained = harm_voiced(fi) && harm_voiced(fp);
+        const double inc = chained ? 0.008 * (fp + fi) : 0.0;
+        double mine = 0.0;
+        for (int j = 0; j < 64; ++j) {
+            const double tj = carry + __shfl(inc, j);
+            carry = __shfl(chained, j) ? tj - floor(tj) : 0.0;
+            if (lane == j) mine = carry;
+        }
+        if (i < max_frames) u[i] = mine;
+    }
+}
+
+// grid = (max_frames, B), block = 256: phase0 = arg(w e^{i phi_h} + sqrt(1 - w^2) e^{i phi_rand}) on voiced frames, phi_rand elsewhere
+// (rand == nullptr: zeros); frames at or beyond the row's: nothing is read, phase0 is zeros
+__global__ __launch_bounds__(NT) void harmonic_phase_kernel(const double* __restrict__ f0_hz, const double* __restrict__ share,
+                                                            const double* __restrict__ rand, const double* __restrict__ u,
+                                                            const int* __restrict__ frames, int max_frames, double f_top,
+                                                            double* __restrict__ phase0) {
+#pragma clang fp contract(off)
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const long fr = (long)b * max_frames + f;
+    if (f >= row_frames(frames, b, max_frames)) {
+        for (int k = tid; k < NBIN; k += NT) phase0[fr * NBIN + k] = 0.0;
+        return;
+    }
+    const double hz = f0_hz[fr];
+    if (!harm_voiced(hz)) {
+        for (int k = tid; k < NBIN; k += NT) phase0[fr * NBIN + k] = rand ? rand[fr * NBIN + k] : 0.0;
+        return;
+    }
+    const double ui = u[fr], p1 = hz / HARM_BIN_HZ, H = (double)harm_count(hz, f_top);
+    for (int k = tid; k < NBIN; k += NT) {
+        const double wk = share[fr * NBIN + k], pr = rand ? rand[fr * NBIN + k] : 0.0;
+        const double hk = fmin(fmax(rint((double)k / p1), 1.0), H);
+        const double tk = hk * ui + 0.5 * (double)(k & 1);
+        double sh, ch, sr, cr;
+        sincospi(2.0 * (tk - floor(tk)), &sh, &ch);
+        sincos(pr, &sr, &cr);
+        const double c = sqrt(fmax(1.0 - wk * wk, 0.0));
+        const double re = wk * ch + c * cr, im = wk * sh + c * sr;
+        phase0[fr * NBIN + k] = re == 0.0 && im == 0.0 ? pr : atan2(im, re);
+    }
+}
+
 constexpr long align256(long n) { return (n + 255) & ~255L; }
 
 }  // namespace
+
+long mel_harmonic_lds_bytes(int n_mels, long packed_doubles) {
+    // weights, amp, r, model, gradient, the harmonics' y and four weights as doubles; bands' first bins and offsets, atoms' first bins as ints
+    return (packed_doubles + 2L * (NBIN + 1) + 5L * HARM_MAX) * 8 + (2L * n_mels + 1 + HARM_MAX) * 4;
+}
+
+long harmonic_phase_scratch_bytes(int B, int max_frames) { return align256((long)B * max_frames * 8); }
+
+hipError_t mel_to_linear_harmonic(const float* mel, const double* f0_hz, const double* inv_basis, const double* packed, long packed_doubles,
+                                  const int* frames, int B, int max_frames, int n_mels, double f_top, int n_iter, double floor,
+                                  double* mag, double* share, hipStream_t s) {
+    if (B < 1 || B > VOC_MAX_ROWS || max_frames < 4 || n_mels < 1 || n_iter < 0 || packed_doubles < 2L * n_mels ||
+        packed_doubles > NNLS_MAX_PACKED || !(f_top >= 1000.0 && f_top <= 8000.0))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mel_harmonic_kernel, dim3(max_frames, B), dim3(NT), mel_harmonic_lds_bytes(n_mels, packed_doubles), s, mel, f0_hz,
+                       inv_basis, packed, (int)packed_doubles, frames, max_frames, n_mels, f_top, n_iter, floor, mag, share);
+    return hipGetLastError();
+}
+
+hipError_t harmonic_u(const double* f0_hz, const int* frames, int B, int max_frames, double* u, hipStream_t s) {
+    if (B < 1 || B > VOC_MAX_ROWS || max_frames < 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(harmonic_u_kernel, dim3(B), dim3(64), 0, s, f0_hz, frames, max_frames, u);
+    return hipGetLastError();
+}
+
+hipError_t harmonic_phase(const double* f0_hz, const double* share, const double* rand, const int* frames, int B, int max_frames,
+                          double f_top, double* phase0, double* u, hipStream_t s) {
+    if (!(f_top >= 1000.0 && f_top <= 8000.0)) return hipErrorInvalidValue;
+    hipError_t e = harmonic_u(f0_hz, frames, B, max_frames, u, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(harmonic_phase_kernel, dim3(max_frames, B), dim3(NT), 0, s, f0_hz, share, rand, (const double*)u, frames, max_frames,
+                       f_top, phase0);
+    return hipGetLastError();
+}
 
 long mel_nnls_lds_bytes(int n_mels, long packed_doubles) {
     // weights, amp, r, y as doubles; first bins and offsets as ints

@@ -126,6 +126,21 @@ def normalize_f0(f0_rapt, device='cuda'):
     return out
 
 
+def f0_from_norm(f0norm, mean, std):
+    """The inverse of the reference's speaker normalisation (utils.py:35-42), on the host: the normalised contour [n] in [0, 1] with 0 on
+    unvoiced frames, plus the mean and standard deviation of a speaker's voiced ln F0 -> float64 [n] in pitch_track's convention:
+    ln F0 = (2 f0norm - 1) 4 std + mean on voiced frames, -1e10 where f0norm is 0.  It is how a converted utterance gets the Hz contour
+    vocoder.griffin_lim(f0=...) takes: the contour the model was fed, with the statistics of the speaker whose pitch the output carries.
+    (The normalisation clips at +-4 std, so a clipped frame comes back at the clip.)"""
+    x = np.asarray(f0norm, np.float64)
+    mean, std = float(mean), float(std)
+    if x.ndim != 1:
+        raise ValueError('f0_from_norm: f0norm must be [n]')
+    if not (np.isfinite(mean) and np.isfinite(std) and std > 0.0):
+        raise ValueError('f0_from_norm: mean must be finite and std finite and positive')
+    return np.where(x != 0.0, (2.0 * x - 1.0) * 4.0 * std + mean, -1e10)
+
+
 def f0_range(gender):
     """make_spect_f0.py:40-45: the search range in Hz by the speaker's gender"""
     if gender == 'M':

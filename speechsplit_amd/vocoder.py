@@ -5,7 +5,9 @@ It inverts what this project itself defines (features.py / csrc/features.hip): t
 and the 1024-point periodic-Hann STFT at hop 256 with reflect padding.  The mel basis is inverted by its pseudo-inverse
 (`numpy.linalg.pinv`), floored -- the default, inversion='pinv' -- or, with inversion='nnls', by the non-negative solution that projected
 FISTA reaches from there on the device (ss_mel_to_linear_nnls: what librosa does with NNLS, here without an external library), and
-Griffin-Lim with momentum (Perraudin et al. 2013, librosa's form) finds a phase.  L frames become 256 (L - 1) samples, and `melspectrogram` of those has L frames again.  float64 throughout; the same bits on
+Griffin-Lim with momentum (Perraudin et al. 2013, librosa's form) finds a phase.  With an F0 track (`f0=`) the voiced frames are replaced by
+a harmonic fit -- one amplitude per harmonic, ss_mel_to_linear_harmonic -- and the phase search starts from harmonic phases
+(ss_harmonic_phase); without one nothing changes.  L frames become 256 (L - 1) samples, and `melspectrogram` of those has L frames again.  float64 throughout; the same bits on
 every run; the starting phases are inputs, drawn on the host.  No engine needed."""
 import ctypes as C
 import wave
@@ -90,11 +92,58 @@ def _mel_to_linear(mel_dev, inv_dev, frames_dev, floor):
     return mag
 
 
-def mel_to_linear(mel, mel_basis=None, floor=1e-10, device='cuda', inversion='pinv', nnls_iter=200):
+def f0_hz(f0):
+    """A track in features.pitch_track's convention (ln Hz, -1e10 on unvoiced frames) -> float64 Hz, 0 on unvoiced frames: what the
+    harmonic calls take.  Anything that is not finite counts as unvoiced."""
+    f = np.asarray(f0, np.float64)
+    ok = np.isfinite(f) & (f > -1e9)
+    with np.errstate(over='ignore'):
+        hz = np.exp(np.where(ok, f, 0.0))
+    return np.where(ok & np.isfinite(hz), hz, 0.0)
+
+
+def _check_f0(who, f0, lens):
+    """one track -> [track]; every track's length must be its mel's"""
+    tracks = list(f0) if isinstance(f0, (list, tuple)) else [f0]
+    tracks = [np.asarray(t, np.float64) for t in tracks]
+    if len(tracks) != len(lens) or any(t.ndim != 1 or t.shape[0] != n for t, n in zip(tracks, lens)):
+        raise ValueError(f'{who}: f0 must hold one track per mel, each as long as its mel')
+    return [f0_hz(t) for t in tracks]
+
+
+def _mel_to_linear_harmonic(mel_dev, f0hz_dev, inv_dev, packed_dev, frames_dev, n_iter, f_top, floor, mag_dev):
+    """_mel_to_linear's shapes, f0hz_dev float64 [B, T] in Hz, mag_dev [B, T, 513] filled by either route: the voiced frames of mag_dev are
+    overwritten with the harmonic fit (ss_mel_to_linear_harmonic); returns the harmonic share float64 [B, T, 513]"""
+    B, T, n_mels = mel_dev.shape
+    share = torch.empty(B, T, NBIN, dtype=torch.float64, device=mel_dev.device)
+    _capi.check(_capi.lib().ss_mel_to_linear_harmonic(_ptr(mel_dev), _ptr(f0hz_dev), _ptr(inv_dev), _ptr(packed_dev), packed_dev.numel(),
+                                                      _ptr(frames_dev), B, T, n_mels, float(f_top), int(n_iter), float(floor), _ptr(mag_dev),
+                                                      _ptr(share), _stream()))
+    return share
+
+
+def _harmonic_phase(f0hz_dev, share_dev, rand_dev, frames_dev, f_top):
+    """f0hz_dev [B, T], share_dev [B, T, 513], rand_dev the same or None (zeros) -> the start phases float64 [B, T, 513]"""
+    lib = _capi.lib()
+    B, T = f0hz_dev.shape
+    nbytes = lib.ss_harmonic_phase_scratch_bytes(B, T)
+    if nbytes < 0:
+        _capi.check(-1)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=f0hz_dev.device)
+    phase0 = torch.empty(B, T, NBIN, dtype=torch.float64, device=f0hz_dev.device)
+    _capi.check(lib.ss_harmonic_phase(_ptr(f0hz_dev), _ptr(share_dev), _ptr(rand_dev), _ptr(frames_dev), B, T, float(f_top), _ptr(phase0),
+                                      _ptr(scratch), nbytes, _stream()))
+    return phase0
+
+
+def mel_to_linear(mel, mel_basis=None, floor=1e-10, device='cuda', inversion='pinv', nnls_iter=200, f0=None, harmonic_iter=50,
+                  f_top=7600.0, return_share=False):
     """mel float [L, n_mels] on `melspectrogram`'s [0, 1] dB scale -> float64 [L, 513] tensor on `device`:
     max(floor, 10^((100 mel - 100 + 16) / 20) . pinv(mel_basis)).  mel_basis [513, n_mels] defaults to features.mel_filter_bank().T.
     inversion='nnls': nnls_iter rounds of projected FISTA from there towards the non-negative magnitude whose mel is the given one
-    (ss_mel_to_linear_nnls; step 1 / lambda_max(B^T B)), then the floor."""
+    (ss_mel_to_linear_nnls; step 1 / lambda_max(B^T B)), then the floor.
+    f0 [L] (features.pitch_track's convention; it has to belong to this mel): the voiced frames are replaced by the harmonic fit of
+    ss_mel_to_linear_harmonic, harmonic_iter rounds, harmonics up to f_top Hz.  return_share: (magnitude, harmonic share [L, 513])."""
     _check_inversion('mel_to_linear', inversion)
     m = torch.as_tensor(np.ascontiguousarray(mel, dtype=np.float32)).to(device)
     if m.dim() != 2 or m.shape[0] < MIN_FRAMES:
@@ -102,10 +151,18 @@ def mel_to_linear(mel, mel_basis=None, floor=1e-10, device='cuda', inversion='pi
     inv = torch.as_tensor(_inv_basis(mel_basis)).to(device)
     if inv.shape[0] != m.shape[1]:
         raise ValueError(f'mel_to_linear: mel has {m.shape[1]} bands, the basis {inv.shape[0]}')
-    if inversion == 'nnls':
+    hz = _check_f0('mel_to_linear', f0, [m.shape[0]])[0] if f0 is not None else None
+    if inversion == 'nnls' or hz is not None:
         packed, step = _nnls_basis(mel_basis)
-        return _mel_to_linear_nnls(m[None], inv, torch.as_tensor(packed).to(device), None, nnls_iter, step, floor)[0]
-    return _mel_to_linear(m[None], inv, None, floor)[0]
+        packed = torch.as_tensor(packed).to(device)
+    if inversion == 'nnls':
+        mag = _mel_to_linear_nnls(m[None], inv, packed, None, nnls_iter, step, floor)
+    else:
+        mag = _mel_to_linear(m[None], inv, None, floor)
+    if hz is None:
+        return (mag[0], torch.zeros_like(mag[0])) if return_share else mag[0]
+    share = _mel_to_linear_harmonic(m[None], torch.from_numpy(hz[None]).to(device), inv, packed, None, harmonic_iter, f_top, floor, mag)
+    return (mag[0], share[0]) if return_share else mag[0]
 
 
 def griffin_lim_mag(mag_dev, phase0_dev, frames_dev, n_iter, momentum):
@@ -147,16 +204,21 @@ def prepare(mels, phases=None, generator=None):
 
 
 def griffin_lim(mels, n_iter=60, momentum=0.99, phases=None, generator=None, max_rows=16, device='cuda', mel_basis=None, floor=1e-10,
-                inversion='pinv', nnls_iter=200):
+                inversion='pinv', nnls_iter=200, f0=None, harmonic_iter=50, f_top=7600.0):
     """One mel [L, 80] (or a list of them, any lengths >= 4) -> float64 numpy waveform(s) of 256 (L - 1) samples at 16 kHz, in input order.
     The utterances run as ragged batches of at most max_rows rows in convert.plan_batches order; every row is the result of running it alone,
-    so the result does not depend on max_rows.  phases / generator: see prepare().  inversion / nnls_iter: see mel_to_linear()."""
+    so the result does not depend on max_rows.  phases / generator: see prepare().  inversion / nnls_iter: see mel_to_linear().
+    f0: one track or a list matching `mels` (features.pitch_track's convention: ln Hz, -1e10 unvoiced; each as long as its mel, and it has
+    to belong to that mel -- features.f0_from_norm gives a converted utterance's).  The chosen inversion fills the magnitude, the harmonic
+    fit (harmonic_iter rounds, harmonics up to f_top Hz) overwrites the voiced frames, and Griffin-Lim starts from the harmonic phases mixed
+    with the drawn (or given, or zero) ones by the harmonic share.  Without f0 nothing changes."""
     _check_inversion('griffin_lim', inversion)
     single, ms, ps = prepare(mels, phases, generator)
     inv = torch.as_tensor(_inv_basis(mel_basis)).to(device)
     if ms and inv.shape[0] != ms[0].shape[1]:
         raise ValueError(f'griffin_lim: mel has {ms[0].shape[1]} bands, the basis {inv.shape[0]}')
-    if inversion == 'nnls':
+    hzs = _check_f0('griffin_lim', f0, [m.shape[0] for m in ms]) if f0 is not None else None
+    if inversion == 'nnls' or hzs is not None:
         packed, step = _nnls_basis(mel_basis)
         packed = torch.as_tensor(packed).to(device)
     out = [None] * len(ms)
@@ -174,7 +236,15 @@ def griffin_lim(mels, n_iter=60, momentum=0.99, phases=None, generator=None, max
             mag = _mel_to_linear_nnls(torch.from_numpy(mel).to(device), inv, packed, frames, nnls_iter, step, floor)
         else:
             mag = _mel_to_linear(torch.from_numpy(mel).to(device), inv, frames, floor)
-        wav = griffin_lim_mag(mag, torch.from_numpy(ph).to(device) if ph is not None else None, frames, n_iter, momentum).cpu().numpy()
+        ph = torch.from_numpy(ph).to(device) if ph is not None else None
+        if hzs is not None:
+            hz = np.zeros((len(batch), T))
+            for n, i in enumerate(batch):
+                hz[n, :lens[n]] = hzs[i]
+            hz = torch.from_numpy(hz).to(device)
+            share = _mel_to_linear_harmonic(torch.from_numpy(mel).to(device), hz, inv, packed, frames, harmonic_iter, f_top, floor, mag)
+            ph = _harmonic_phase(hz, share, ph, frames, f_top)
+        wav = griffin_lim_mag(mag, ph, frames, n_iter, momentum).cpu().numpy()
         for n, i in enumerate(batch):
             out[i] = wav[n, :256 * (lens[n] - 1)].copy()
     return out[0] if single else out

@@ -5,8 +5,12 @@
     multiply-adds) on the same --frames frames of one waveform, alternated call by call, --inner calls per timed window;
   * the mel inversion as a stage of its own, on the same --rows x --frames mels of the project's filter bank: ss_mel_to_linear against
     ss_mel_to_linear_nnls at every count of --nnls-iters (default 50 and 200), one call per timed window, alternated call by call, in
-    milliseconds and as a fraction of ss_griffinlim's median on this run.
+    milliseconds and as a fraction of ss_griffinlim's median on this run;
+  * the F0-guided harmonic route on the same mels, every frame voiced (the worst case; per row a slow glide between 90 and 230 Hz):
+    ss_mel_to_linear_harmonic alone (the magnitude already filled) at every count of --harmonic-iters (default 25 and 50),
+    ss_harmonic_phase, and its serial part alone (ss_op_harmonic_u: one wave per row), the same way.
     python tools/vocoder_bench.py [--rows 7] [--frames 192] [--iters 60] [--reps 30] [--warmup 5] [--inner 20] [--nnls-iters 50 200]
+                                  [--harmonic-iters 25 50]
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -31,6 +35,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--inner', type=int, default=20)
     ap.add_argument('--nnls-iters', type=int, nargs='+', default=[50, 200])
+    ap.add_argument('--harmonic-iters', type=int, nargs='+', default=[25, 50])
     a = ap.parse_args()
     from speechsplit_amd import _capi, features, vocoder
     lib = _capi.lib()
@@ -72,7 +77,24 @@ def main():
     def nnls(n_iter):
         return lambda: vocoder._mel_to_linear_nnls(mel_in, inv, packed, None, n_iter, step, 1e-10)
 
-    stages = [('griffinlim', gl), ('stft_fft', fft), ('melspec_dft', dft), ('mel_pinv', pinv)] + [(f'mel_nnls_{k}', nnls(k)) for k in a.nnls_iters]
+    # the harmonic route: every frame voiced, a glide per row; mag_h / share_h are the call's in/out and out buffers
+    f0hz = torch.from_numpy(np.stack([110.0 + 20.0 * r + (20.0 + 10.0 * r) * np.sin(np.arange(T) / 17.0 + r) for r in range(B)])).to(dev)
+    mag_h = vocoder._mel_to_linear(mel_in, inv, None, 1e-10)
+    share_h = torch.rand(B, T, 513, dtype=torch.float64, device=dev)
+    u_buf = torch.empty(B, T, dtype=torch.float64, device=dev)
+
+    def harmonic(n_iter):
+        return lambda: _capi.check(lib.ss_mel_to_linear_harmonic(p(mel_in), p(f0hz), p(inv), p(packed), packed.numel(), None, B, T, 80, 7600.0,
+                                                                  n_iter, 1e-10, p(mag_h), p(share_h), s))
+
+    def hphase():
+        vocoder._harmonic_phase(f0hz, share_h, ph, None, 7600.0)
+
+    def hu():
+        _capi.check(lib.ss_op_harmonic_u(p(f0hz), None, B, T, p(u_buf), s))
+
+    harm = [(f'mel_harmonic_{k}', harmonic(k)) for k in a.harmonic_iters] + [('harmonic_phase', hphase), ('harmonic_u', hu)]
+    stages = [('griffinlim', gl), ('stft_fft', fft), ('melspec_dft', dft), ('mel_pinv', pinv)] + [(f'mel_nnls_{k}', nnls(k)) for k in a.nnls_iters] + harm
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     times = {tag: [] for tag, _ in stages}
     for it in range(a.warmup + a.reps):
@@ -94,7 +116,9 @@ def main():
                       'dft_over_fft': round(per_frame['melspec_dft'] / per_frame['stft_fft'], 2),
                       'inversion_ms_median': {k: round(med[k], 4) for k in med if k.startswith('mel_')},
                       'inversion_ms_minmax': {k: [round(min(times[k]), 4), round(max(times[k]), 4)] for k in med if k.startswith('mel_')},
-                      'inversion_over_griffinlim': {k: round(med[k] / med['griffinlim'], 4) for k in med if k.startswith('mel_')}}))
+                      'inversion_over_griffinlim': {k: round(med[k] / med['griffinlim'], 4) for k in med if k.startswith('mel_')},
+                      'harmonic_ms_median': {k: round(med[k], 4) for k, _ in harm},
+                      'harmonic_ms_minmax': {k: [round(min(times[k]), 4), round(max(times[k]), 4)] for k, _ in harm}}))
 
 
 if __name__ == '__main__':
