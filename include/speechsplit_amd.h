@@ -345,7 +345,8 @@ int ss_f0_normalize(const double* f0_dev, int n, float* out_dev, void* stream);
 /* ---- pitch tracker: waveforms to F0 tracks (the stand-in for make_spect_f0.py:64's `pysptk.sptk.rapt`, which is not pinned here) ----
  * The published core of RAPT (Talkin 1995, "A robust algorithm for pitch tracking"): normalised cross-correlation candidates per frame plus
  * dynamic programming over the frames, with Talkin's published constants.  NOT a port of SPTK's rapt and no parity with it is claimed: RAPT's
- * spectral-stationarity term (it needs LPC) and its two-rate search are left out.  The output follows RAPT's otype=2 convention -- ln(F0 in
+ * two-rate search is left out, and its spectral-stationarity term (an LPC analysis per frame) is optional and off by default -- see
+ * "spectral stationarity" below (ss_pitch_track_stat).  The output follows RAPT's otype=2 convention -- ln(F0 in
  * Hz), -1e10 for unvoiced frames, one value per 256-sample hop, ss_melspec_frames(n) values -- so ss_f0_normalize takes it unchanged.
  *
  * Constants: fs = 16000, hop = 256, correlation window w = 120, CAND_TR = 0.3, N_CANDS = 20 (19 voiced states plus the unvoiced one),
@@ -390,6 +391,45 @@ int  ss_op_nccf(const double* wav_dev, const int* n_dev, int B, int max_n, doubl
                 double* phi_dev /* [B][F][K] */, double* rms_dev /* [B][F] */, void* stream);
 int  ss_op_pitch_dp(const double* phi_dev, const double* rms_dev, const int* n_dev, int B, int max_n, double lo_hz, double hi_hz,
                     double* f0_dev, void* scratch_dev, long scratch_bytes, void* stream);
+
+/* ---- pitch tracker, spectral stationarity: RAPT's third voicing-transition term (off unless these entry points are called) ----
+ * In RAPT the cost of switching between voiced and unvoiced has a constant, a level-ratio part and a spectral part that makes a switch
+ * cheap where the short-time spectrum changes and expensive where it stands still.  This is the published term -- Talkin 1995, and
+ * get_f0's get_stationarity / get_similarity as published -- with the published constants; as for the rest of the tracker, no parity with
+ * SPTK is claimed.  What it does NOT take from get_f0: rr stays the ratio of the NCCF segments' rms (get_f0 takes it from these windows).
+ *
+ * Constants: STAT_W = 480 (a 30 ms window), STAT_GAP = 320 (20 ms between the two windows' centres), LPC_ORD = 18 (2 + fs / 1000),
+ * PREEMP = 0.4, ff = 1 / (1 + 10^-3) (the 30 dB stabilising floor), VTR_S_C = 0.5, and the offsets 0.8 and 0.2 of S below.
+ * Frame i >= 1 has two windows: A centred on sample 256 i - 160 and B centred on sample 256 i + 160.  Per window centred on c, on the
+ * tracker's scaled samples z = scale x (zero wherever the index is outside [0, n)):
+ *      s = c - 240;  u_j = z[s + j], 0 <= j <= 480;  y_j = w_j (u_{j+1} - PREEMP u_j), j < 480, w_j = 0.5 - 0.5 cos(2 pi (j + 0.5) / 480);
+ *      r_k = sum_{j < 480 - k} y_j y_{j+k}, k = 0 .. 18.
+ *      If r_0 == 0: rho = a = (1, 0, .., 0) and E = 1.  Otherwise rho_0 = 1, rho_k = ff r_k / r_0, and Levinson-Durbin from a = (1), E = 1:
+ *      for m = 1 .. 18: kappa = -(rho_m + sum_{q=1}^{m-1} a_q rho_{m-q}) / E;  a'_q = a_q + kappa a_{m-q} for q < m;  a'_m = kappa;
+ *      E <- E (1 - kappa^2).
+ * Itakura distortion of B's predictor on A's signal: c_0 = sum_q (a^B_q)^2, c_k = 2 sum_{q=0}^{18-k} a^B_q a^B_{q+k},
+ *      d = (c_0 + sum_{k=1}^{18} c_k rho^A_k) / E^A;   S_i = min(0.2 / (max(d, 1) - 0.8), 1).
+ * In exact arithmetic d >= 1, so 0 < S <= 1 and the outer min does nothing; in float64 0.2 / (1 - 0.8) is 1 + 2^-52, which it cuts off.
+ * S_0 is unused and stored as an exact 0; beyond a row's own F the entries are exact zeros, as for phi and rms.
+ * Transitions: VTR_S_C S_i is added to t(unvoiced -> voiced) and to t(voiced -> unvoiced) into frame i and to nothing else, as
+ * (VTRAN_C + VTR_A_C / rr_i) + VTR_S_C S_i and (VTRAN_C + VTR_A_C rr_i) + VTR_S_C S_i: a track of zeros gives ss_pitch_track's bits.
+ * Order of the sums: each r_k is cut into 24 chunks j = 20 c .. 20 c + 19, c = 0 .. 23, with y_j taken as 0 for j >= 480 (those terms add
+ * exact zeros); thread 10 c + 5 w + g of 256 (w = 0 for A, 1 for B; g = 0 .. 4) adds the terms of chunk c for the lags k = 4 g .. 4 g + 3
+ * (k <= 18), each lag in index order from zero, then thread 19 w + k adds that sum's 24 partials in chunk order, from p_0:
+ * (((p_0 + p_1) + p_2) + ..) + p_23.  The Levinson sum starts from rho_m and adds a_q rho_{m-q} for q = 1, 2, ..; c_k adds
+ * q = 0, 1, .. from zero (then doubles); d's numerator starts from c_0 and adds c_k rho^A_k for k = 1, 2, ..  Multiply-adds may be fused.
+ *
+ * ss_pitch_track_stat: ss_pitch_track's arguments, rules and refusals, with a scratch of ss_pitch_stat_scratch_bytes (that of
+ * ss_pitch_scratch_bytes plus the S track [B][F], 256-byte aligned); it runs the NCCF, the stationarity, the candidates and the
+ * recurrence.  Hooks: ss_op_pitch_stationarity writes S [B][F] alone (refused: null wav_dev / stat_dev, B, max_n, scale as above);
+ * ss_op_pitch_dp_stat is ss_op_pitch_dp (same scratch) with stat_dev [B][F], also refused when null; it never reads stat beyond a row's F. */
+long ss_pitch_stat_scratch_bytes(int B, int max_n, double lo_hz, double hi_hz);       /* host only; -1 + ss_last_error on bad arguments */
+int  ss_pitch_track_stat(const double* wav_dev, const int* n_dev, int B, int max_n, double scale, double lo_hz, double hi_hz,
+                         double* f0_dev, void* scratch_dev, long scratch_bytes, void* stream);
+int  ss_op_pitch_stationarity(const double* wav_dev, const int* n_dev, int B, int max_n, double scale, double* stat_dev /* [B][F] */,
+                              void* stream);
+int  ss_op_pitch_dp_stat(const double* phi_dev, const double* rms_dev, const double* stat_dev, const int* n_dev, int B, int max_n,
+                         double lo_hz, double hi_hz, double* f0_dev, void* scratch_dev, long scratch_bytes, void* stream);
 
 /* ---- batched feature extraction: make_spect_f0.py:49-71 on ragged batches of recordings (filter, dither, mel spectrogram, F0 normalisation;
  * the pitch track between them is ss_pitch_track above, which takes the same wav / n_dev / B / max_n) ----

@@ -147,6 +147,10 @@ SYMBOLS = {
     'ss_pitch_track': (_i, [_vp, _ip, _i, _i, _d, _d, _d, _vp, _vp, _l, _vp]),
     'ss_op_nccf': (_i, [_vp, _ip, _i, _i, _d, _d, _d, _vp, _vp, _vp]),
     'ss_op_pitch_dp': (_i, [_vp, _vp, _ip, _i, _i, _d, _d, _vp, _vp, _l, _vp]),
+    'ss_pitch_stat_scratch_bytes': (_l, [_i, _i, _d, _d]),
+    'ss_pitch_track_stat': (_i, [_vp, _ip, _i, _i, _d, _d, _d, _vp, _vp, _l, _vp]),
+    'ss_op_pitch_stationarity': (_i, [_vp, _ip, _i, _i, _d, _vp, _vp]),
+    'ss_op_pitch_dp_stat': (_i, [_vp, _vp, _vp, _ip, _i, _i, _d, _d, _vp, _vp, _l, _vp]),
     'ss_filtfilt_scratch_bytes': (_l, [_i, _i]),
     'ss_filtfilt': (_i, [_vp, _ip, _i, _i, _vp, _vp, _vp, _d, _vp, _d, _vp, _vp, _l, _vp]),
     'ss_melspec_batch': (_i, [_vp, _ip, _i, _i, _vp, _i, _fp, _vp]),

@@ -75,7 +75,7 @@ int ss_pitch_track(const double* wav, const int* n, int B, int max_n, double sca
     CHK(pitch_scratch_ok("ss_pitch_track", B, max_n, g, scratch, scratch_bytes));
     const PitchScratch sc = pitch_scratch(scratch, B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1);
     HIPCHK(pitch_nccf(wav, n, B, max_n, scale, g, sc.phi, sc.rms, S(stream)));
-    HIPCHK(pitch_dp(sc.phi, sc.rms, n, B, max_n, g, f0, sc, S(stream)));
+    HIPCHK(pitch_dp(sc.phi, sc.rms, nullptr, n, B, max_n, g, f0, sc, S(stream)));
     return 0;
 }
 
@@ -99,7 +99,58 @@ int ss_op_pitch_dp(const double* phi, const double* rms, const int* n, int B, in
     if (!f0) return fail("ss_op_pitch_dp: null pointer: f0_dev");
     CHK(pitch_shape("ss_op_pitch_dp", B, max_n, lo_hz, hi_hz, &g));
     CHK(pitch_scratch_ok("ss_op_pitch_dp", B, max_n, g, scratch, scratch_bytes));
-    HIPCHK(pitch_dp(phi, rms, n, B, max_n, g, f0, pitch_scratch(scratch, B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1), S(stream)));
+    HIPCHK(pitch_dp(phi, rms, nullptr, n, B, max_n, g, f0, pitch_scratch(scratch, B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1), S(stream)));
+    return 0;
+}
+
+// ---- the same with RAPT's spectral-stationarity term (stat_kernel, dp_kernel<true>)
+long ss_pitch_stat_scratch_bytes(int B, int max_n, double lo_hz, double hi_hz) {
+    PitchLags g;
+    CHK(pitch_shape("ss_pitch_stat_scratch_bytes", B, max_n, lo_hz, hi_hz, &g));
+    return pitch_stat_scratch_bytes(B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1);
+}
+
+int ss_pitch_track_stat(const double* wav, const int* n, int B, int max_n, double scale, double lo_hz, double hi_hz, double* f0,
+                        void* scratch, long scratch_bytes, void* stream) {
+    PitchLags g;
+    if (!wav) return fail("ss_pitch_track_stat: null pointer: wav_dev");
+    if (!f0) return fail("ss_pitch_track_stat: null pointer: f0_dev");
+    CHK(pitch_shape("ss_pitch_track_stat", B, max_n, lo_hz, hi_hz, &g));
+    if (!(scale > 0.0) || std::isinf(scale)) return fail("ss_pitch_track_stat: scale is not finite or not positive");
+    const int F = ss_melspec_frames(max_n), K = g.lmax - g.lmin + 1;
+    if (!scratch) return fail("ss_pitch_track_stat: null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail("ss_pitch_track_stat: scratch_dev is not 256-byte aligned");
+    if (scratch_bytes < pitch_stat_scratch_bytes(B, F, K))
+        return fail("ss_pitch_track_stat: scratch_bytes below ss_pitch_stat_scratch_bytes(B, max_n, lo_hz, hi_hz)");
+    const PitchScratch sc = pitch_scratch(scratch, B, F, K);
+    double* stat = pitch_stat_track(scratch, B, F, K);
+    HIPCHK(pitch_nccf(wav, n, B, max_n, scale, g, sc.phi, sc.rms, S(stream)));
+    HIPCHK(pitch_stationarity(wav, n, B, max_n, scale, stat, S(stream)));
+    HIPCHK(pitch_dp(sc.phi, sc.rms, stat, n, B, max_n, g, f0, sc, S(stream)));
+    return 0;
+}
+
+int ss_op_pitch_stationarity(const double* wav, const int* n, int B, int max_n, double scale, double* stat, void* stream) {
+    if (!wav) return fail("ss_op_pitch_stationarity: null pointer: wav_dev");
+    if (!stat) return fail("ss_op_pitch_stationarity: null pointer: stat_dev");
+    if (B < 1 || B > PITCH_MAX_ROWS) return fail("ss_op_pitch_stationarity: B outside 1 .. 65535");
+    if (max_n < 513 || max_n > 256 * (SS_MAX_EVAL_FRAMES - 1))
+        return fail("ss_op_pitch_stationarity: max_n outside 513 .. 256 * (SS_MAX_EVAL_FRAMES - 1)");
+    if (!(scale > 0.0) || std::isinf(scale)) return fail("ss_op_pitch_stationarity: scale is not finite or not positive");
+    HIPCHK(pitch_stationarity(wav, n, B, max_n, scale, stat, S(stream)));
+    return 0;
+}
+
+int ss_op_pitch_dp_stat(const double* phi, const double* rms, const double* stat, const int* n, int B, int max_n, double lo_hz, double hi_hz,
+                        double* f0, void* scratch, long scratch_bytes, void* stream) {
+    PitchLags g;
+    if (!phi) return fail("ss_op_pitch_dp_stat: null pointer: phi_dev");
+    if (!rms) return fail("ss_op_pitch_dp_stat: null pointer: rms_dev");
+    if (!stat) return fail("ss_op_pitch_dp_stat: null pointer: stat_dev");
+    if (!f0) return fail("ss_op_pitch_dp_stat: null pointer: f0_dev");
+    CHK(pitch_shape("ss_op_pitch_dp_stat", B, max_n, lo_hz, hi_hz, &g));
+    CHK(pitch_scratch_ok("ss_op_pitch_dp_stat", B, max_n, g, scratch, scratch_bytes));
+    HIPCHK(pitch_dp(phi, rms, stat, n, B, max_n, g, f0, pitch_scratch(scratch, B, ss_melspec_frames(max_n), g.lmax - g.lmin + 1), S(stream)));
     return 0;
 }
 

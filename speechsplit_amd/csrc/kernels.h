@@ -370,12 +370,18 @@ struct PitchScratch {
 };
 long pitch_scratch_bytes(int B, int max_frames, int K);
 PitchScratch pitch_scratch(void* base, int B, int max_frames, int K);
+// the same scratch with the stationarity track S [B][F] behind it (256-byte aligned), and where that track begins
+long pitch_stat_scratch_bytes(int B, int max_frames, int K);
+double* pitch_stat_track(void* base, int B, int max_frames, int K);
 // steps 1 and 2 of the header's algorithm: one workgroup per (frame, utterance)
 hipError_t pitch_nccf(const double* wav, const int* n, int B, int max_n, double scale, const PitchLags& g, double* phi, double* rms,
                       hipStream_t s);
-// steps 3 and 4, the recurrence and the backtrack: a frame-parallel candidate kernel, then one wavefront per utterance
-hipError_t pitch_dp(const double* phi, const double* rms, const int* n, int B, int max_n, const PitchLags& g, double* f0,
+// steps 3 and 4, the recurrence and the backtrack: a frame-parallel candidate kernel, then one wavefront per utterance.  stat [B][F]
+// (nullable): the stationarity track, added to the voicing transitions (dp_kernel<true>); null runs the tracker without the term
+hipError_t pitch_dp(const double* phi, const double* rms, const double* stat, const int* n, int B, int max_n, const PitchLags& g, double* f0,
                     const PitchScratch& sc, hipStream_t s);
+// the header's "spectral stationarity": S_i per frame from two LPC analyses, one workgroup per (frame, utterance); stat [B][F]
+hipError_t pitch_stationarity(const double* wav, const int* n, int B, int max_n, double scale, double* stat, hipStream_t s);
 
 // ---------------------------------------------------------------- dtw.hip  (conversion scores: cepstra, DTW path and cost, F0 error along a path)
 // Shapes: mel [B][max_t][n_mels] f32, dct [n_ceps][n_mels], cepstra [B][max_t][n_ceps]; fx [B][max_tx][dim], fy [B][max_ty][dim],

@@ -1,7 +1,8 @@
 // Pitch tracker: waveform -> F0 track, the stand-in for the reference's `pysptk.sptk.rapt` call (make_spect_f0.py:64).  It is the published
 // core of RAPT (Talkin 1995, "A robust algorithm for pitch tracking"): normalised cross-correlation (NCCF) candidates per frame, then dynamic
 // programming over the frames, with Talkin's published constants.  It is NOT a port of SPTK's rapt and claims no parity with it: RAPT's
-// spectral-stationarity term (it needs LPC) and its two-rate search (a decimated first pass) are left out.  The output follows RAPT's
+// two-rate search (a decimated first pass) is left out, and its spectral-stationarity term (an LPC analysis per frame) is optional and
+// off by default (ss_pitch_track_stat: stat_kernel and dp_kernel<true> below).  The output follows RAPT's
 // otype=2 convention -- ln(F0 in Hz), -1e10 for unvoiced frames, one value per 256-sample hop -- so f0_normalize takes it unchanged.
 // include/speechsplit_amd.h states the algorithm completely; tests/pitch_ref.py restates it in numpy.
 //
@@ -24,6 +25,23 @@
 //                 go to scratch; the backtrack reads one row of them per frame across the lanes and selects by shuffle, so its loads do not
 //                 depend on the path.  Bound: F sequential steps -- latency, not throughput: about one
 //                 global-load round trip per frame (the one-frame prefetch is shorter than that latency, and the barrier waits for it).
+//                 dp_kernel<true> also fetches S_i one step ahead, beside rms, and adds VTR_S_C S_i to the two voicing transitions;
+//                 dp_kernel<false> is the arithmetic above and nothing else.
+//   stat_kernel   (ss_pitch_track_stat only, between nccf and cand) one workgroup per (frame, utterance).  The 801 samples that the frame's
+//                 two 30 ms windows cover together are staged in LDS once; both pre-emphasised, windowed signals (2 x 480) are formed there
+//                 (the staging buffer then holds the partial sums).
+//                 The 38 (window, lag) autocorrelation sums are cut into 24 chunks of 20 terms (y_j = 0 for j >= 480): thread t < 240
+//                 takes chunk t / 10 of four consecutive lags of one window (t % 10: window, lag group) in index order, sliding
+//                 y_{j+k} through registers -- two LDS reads for four multiply-adds, where one lag a thread pays two for one -- and
+//                 thread t < 38 adds its sum's 24 partials in chunk order.  The two Levinson recursions (18 dependent steps: 171
+//                 multiply-adds in the inner products, as many in the updates, a division per step) run side by side in lanes 0 and 1
+//                 of one wavefront, each serially with a in registers (fully unrolled; rho sits in LDS, where 38 threads put
+//                 ff r_k / r_0, and is read at constant offsets off the dependent chain): the header fixes index order for the
+//                 recursion's inner products, so spreading a step over lanes would leave the products serial and pay a shuffle per term
+//                 for the update alone; two lanes of ONE wavefront, because a serial lane costs its wavefront's whole issue slot
+//                 whatever the number of lanes in use.  Then 19 threads form c_k, one thread the distortion and S.  Bound: 38 x 480
+//                 multiply-adds from LDS per frame, 18 k, a fifth of the NCCF's at K = 257, plus ~0.8 k dependent double operations of
+//                 one wavefront per frame -- the latter is what the time is.
 //
 // Batches: row b has n_b = min(max(n[b], 513), max_n) samples and F_b = n_b / 256 + 1 frames; every kernel computes row b as if it were alone
 // and never reads a sample at or beyond n_b; phi / rms beyond F_b are exact zeros, f0 beyond F_b is -1e10.
@@ -41,6 +59,14 @@ constexpr int MAXS = W + PITCH_MAX_LAG;                        // 520
 constexpr int MAXK = PITCH_MAX_LAG - PITCH_MIN_LAG + 1;        // 385
 constexpr double FS = 16000.0, CAND_TR = 0.3, LAG_WT = 0.3, FREQ_WT = 0.02, DOUBL_C = 0.35, VTRAN_C = 0.005, VTR_A_C = 0.5, VO_BIAS = 0.0,
                  A_FACT = 10000.0, UNVOICED = -1e10, LN2 = 0.69314718055994530942;
+// the spectral-stationarity term: 30 ms windows whose centres are 20 ms apart, LPC order 2 + fs / 1000
+constexpr int STAT_W = 480, STAT_GAP = 320, LPC_ORD = 18, STAT_SPAN = STAT_W + STAT_GAP + 1, STAT_SUMS = 2 * (LPC_ORD + 1);
+// the autocorrelation sums: a thread takes 4 consecutive lags of one window over one chunk of 20 terms; 5 lag groups x 2 windows x 24 chunks
+constexpr int STAT_CHUNK = 20, STAT_CHUNKS = STAT_W / STAT_CHUNK, STAT_LAGS = 4, STAT_GROUPS = (LPC_ORD + STAT_LAGS) / STAT_LAGS,
+              STAT_PAD = 24, STAT_LD = STAT_W + STAT_PAD + 24;   // a window's row: 480 values, zeros behind them; 528 = 16 mod 32 apart in LDS banks
+constexpr double PREEMP = 0.4, STAT_FF = 1.0 / (1.0 + 1e-3), VTR_S_C = 0.5, TWO_PI = 6.28318530717958647693;
+static_assert(2 * STAT_GROUPS * STAT_CHUNKS <= NT && STAT_CHUNKS * STAT_CHUNK == STAT_W, "one thread per (window, lag group, chunk)");
+static_assert(STAT_GROUPS * STAT_LAGS - 1 <= STAT_PAD && STAT_PAD <= NT, "the last chunk's reads stay inside the zeros");
 
 __device__ inline int row_samples(const int* n, int b, int max_n) {
     const int v = n ? n[b] : max_n;
@@ -176,8 +202,11 @@ __global__ __launch_bounds__(NT) void cand_kernel(const double* __restrict__ phi
     }
 }
 
-// grid = B, block = 64 (one wavefront).  f0 [B][max_frames]; bp [B][max_frames][BPLD] bytes.
-__global__ __launch_bounds__(64) void dp_kernel(const double* __restrict__ rms, const double* __restrict__ cost,
+// grid = B, block = 64 (one wavefront).  f0 [B][max_frames]; bp [B][max_frames][BPLD] bytes.  STAT: stat [B][max_frames], read at frames
+// 1 .. F_b - 1 only; without it stat is not touched.
+template <bool STAT>
+__global__ __launch_bounds__(64) void dp_kernel(const double* __restrict__ rms, const double* __restrict__ stat,
+                                                const double* __restrict__ cost,
                                                 const double* __restrict__ lag, const double* __restrict__ lnlag,
                                                 const int* __restrict__ cnt, const int* __restrict__ n, int max_n, int max_frames,
                                                 unsigned char* __restrict__ bp, double* __restrict__ f0) {
@@ -194,18 +223,24 @@ __global__ __launch_bounds__(64) void dp_kernel(const double* __restrict__ rms, 
     __syncthreads();
     // frame i's operands are fetched one step ahead: they do not depend on the recurrence
     int c_n = cnt[base + 1];
-    double d_n = cost[(base + 1) * NST + sl], ln_n = lnlag[(base + 1) * NST + sl], r_n = rms[base + 1] / rms[base];
+    double d_n = cost[(base + 1) * NST + sl], ln_n = lnlag[(base + 1) * NST + sl], r_n = rms[base + 1] / rms[base], s_n = 0.0;
+    if constexpr (STAT) s_n = stat[base + 1];
     for (int i = 1; i < F; ++i) {
         const int ci = c_n, cur = i & 1, prv = cur ^ 1;
-        const double d = d_n, ln_a = ln_n, rr = r_n;
+        const double d = d_n, ln_a = ln_n, rr = r_n, sp = s_n;
         if (i + 1 < F) {
             c_n = cnt[base + i + 1];
             d_n = cost[(base + i + 1) * NST + sl];
             ln_n = lnlag[(base + i + 1) * NST + sl];
             r_n = rms[base + i + 1] / rms[base + i];
+            if constexpr (STAT) s_n = stat[base + i + 1];
         }
         if (lane < ci) {
-            const double up = VTRAN_C + VTR_A_C / rr, down = VTRAN_C + VTR_A_C * rr;   // unvoiced -> voiced, voiced -> unvoiced
+            double up = VTRAN_C + VTR_A_C / rr, down = VTRAN_C + VTR_A_C * rr;         // unvoiced -> voiced, voiced -> unvoiced
+            if constexpr (STAT) {
+                up += VTR_S_C * sp;
+                down += VTR_S_C * sp;
+            }
             double best = Dl[prv][0] + (lane == 0 ? 0.0 : up);
             int arg = 0;
             for (int q = 1; q < cprev; ++q) {
@@ -247,6 +282,125 @@ __global__ __launch_bounds__(64) void dp_kernel(const double* __restrict__ rms, 
     for (int i = F + lane; i < max_frames; i += 64) f0[base + i] = UNVOICED;
 }
 
+// Levinson-Durbin on rho [LPC_ORD + 1] (LDS, read at constant offsets: the reads do not depend on the recursion), serially in the calling
+// lane with a in registers (every loop unrolls).  Per step the inner product starts from rho_m and adds a_q rho_{m-q} for q = 1 .. m - 1 in
+// order; a_q and a_{m-q} are updated together from their old values.  rho = (1, 0, ..) leaves a = (1, 0, ..) and E = 1.
+__device__ inline void levinson(const double* rho, double (&a)[LPC_ORD + 1], double& E) {
+    a[0] = 1.0;
+#pragma unroll
+    for (int k = 1; k <= LPC_ORD; ++k) a[k] = 0.0;
+    E = 1.0;
+#pragma unroll
+    for (int m = 1; m <= LPC_ORD; ++m) {
+        double acc = rho[m];
+#pragma unroll
+        for (int q = 1; q < m; ++q) acc += a[q] * rho[m - q];
+        const double kappa = -acc / E;
+#pragma unroll
+        for (int q = 1; 2 * q <= m; ++q) {
+            const double lo = a[q], hi = a[m - q];
+            a[q] = lo + kappa * hi;
+            if (2 * q < m) a[m - q] = hi + kappa * lo;
+        }
+        a[m] = kappa;
+        E = E * (1.0 - kappa * kappa);
+    }
+}
+
+// grid = (max_frames, B), block = 256.  wav [B][max_n]; stat [B][max_frames]: S_i for 1 <= i < F_b, exact zeros at frame 0 and beyond F_b.
+__global__ __launch_bounds__(NT) void stat_kernel(const double* __restrict__ wav, const int* __restrict__ n, int max_n, int max_frames,
+                                                  double scale, double* __restrict__ stat) {
+    __shared__ double buf[STAT_CHUNKS * STAT_SUMS];               // u: samples 256 f - 400 .. 256 f + 400; once y is formed, the partial sums
+    __shared__ double y[2][STAT_LD];                              // window A (centred 160 samples before the frame), window B (160 after)
+    __shared__ double r[STAT_SUMS], rho[STAT_SUMS];               // r^A_0 .. r^A_18, r^B_0 .. r^B_18, and rho likewise
+    __shared__ double a_b[LPC_ORD + 1], c[LPC_ORD + 1], e_a;
+    static_assert(STAT_SPAN <= STAT_CHUNKS * STAT_SUMS, "u fits where the partial sums go");
+    double* u = buf;
+    double(*part)[STAT_SUMS] = reinterpret_cast<double(*)[STAT_SUMS]>(buf);
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int nb = row_samples(n, b, max_n), F = nb / HOP + 1;
+    const long fr = (long)b * max_frames + f;
+    if (f == 0 || f >= F) {
+        if (tid == 0) stat[fr] = 0.0;
+        return;
+    }
+    const double* x = wav + (long)b * max_n;
+    const int start = HOP * f - (STAT_GAP + STAT_W) / 2;
+    for (int j = tid; j < STAT_SPAN; j += NT) {
+        const int i = start + j;
+        u[j] = (i >= 0 && i < nb) ? scale * x[i] : 0.0;
+    }
+    __syncthreads();
+    for (int j = tid; j < STAT_W; j += NT) {
+        const double w = 0.5 - 0.5 * cos(TWO_PI * ((double)j + 0.5) / (double)STAT_W);
+        y[0][j] = w * (u[j + 1] - PREEMP * u[j]);
+        y[1][j] = w * (u[STAT_GAP + j + 1] - PREEMP * u[STAT_GAP + j]);
+    }
+    if (tid < STAT_PAD) y[0][STAT_W + tid] = y[1][STAT_W + tid] = 0.0;               // y_j = 0 for j >= 480: every chunk has 20 terms
+    __syncthreads();
+    if (tid < 2 * STAT_GROUPS * STAT_CHUNKS) {
+        // lags k0 .. k0 + 3 of one window over j = j0 .. j0 + 19: y_{j+k0} .. y_{j+k0+3} slide through registers, so a step reads two values
+        // for four multiply-adds.  (The fifth group's fourth lag would be 19: computed, not stored.)
+        const int ch = tid / (2 * STAT_GROUPS), g = tid % (2 * STAT_GROUPS), w = g / STAT_GROUPS, k0 = STAT_LAGS * (g % STAT_GROUPS);
+        const double* v = y[w];
+        const int j0 = STAT_CHUNK * ch;                           // j + k0 + 3 <= 479 + 19: inside the zeros
+        double v0 = v[j0 + k0], v1 = v[j0 + k0 + 1], v2 = v[j0 + k0 + 2], a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+        for (int j = j0; j < j0 + STAT_CHUNK; ++j) {
+            const double h = v[j], v3 = v[j + k0 + 3];
+            a0 += h * v0;
+            a1 += h * v1;
+            a2 += h * v2;
+            a3 += h * v3;
+            v0 = v1;
+            v1 = v2;
+            v2 = v3;
+        }
+        double* out = part[ch] + w * (LPC_ORD + 1) + k0;
+        out[0] = a0;
+        out[1] = a1;
+        out[2] = a2;
+        if (k0 + 3 <= LPC_ORD) out[3] = a3;
+    }
+    __syncthreads();
+    if (tid < STAT_SUMS) {
+        double acc = part[0][tid];
+#pragma unroll
+        for (int ch = 1; ch < STAT_CHUNKS; ++ch) acc += part[ch][tid];
+        r[tid] = acc;
+    }
+    __syncthreads();
+    if (tid < STAT_SUMS) {                                        // rho_0 = 1, rho_k = ff r_k / r_0; all zeros behind rho_0 when r_0 == 0
+        const int k = tid % (LPC_ORD + 1);
+        const double r0 = r[tid - k];
+        rho[tid] = k == 0 ? 1.0 : (r0 == 0.0 ? 0.0 : STAT_FF * r[tid] / r0);
+    }
+    __syncthreads();
+    if (tid < 2) {                                                // lanes 0 and 1 of one wavefront: window A, window B, one instruction stream
+        double a[LPC_ORD + 1], E;
+        levinson(rho + (tid ? LPC_ORD + 1 : 0), a, E);
+        if (tid == 0) {
+            e_a = E;
+        } else {
+#pragma unroll
+            for (int k = 0; k <= LPC_ORD; ++k) a_b[k] = a[k];
+        }
+    }
+    __syncthreads();
+    if (tid <= LPC_ORD) {                                         // c_0 = sum a_q^2, c_k = 2 sum_{q <= 18 - k} a_q a_{q+k}, q in order
+        double acc = 0.0;
+        for (int q = 0; q + tid <= LPC_ORD; ++q) acc += a_b[q] * a_b[q + tid];
+        c[tid] = tid ? 2.0 * acc : acc;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double acc = c[0];
+        for (int k = 1; k <= LPC_ORD; ++k) acc += c[k] * rho[k];
+        const double d = acc / e_a;
+        stat[fr] = fmin(0.2 / (fmax(d, 1.0) - 0.8), 1.0);
+    }
+}
+
 constexpr long align256(long n) { return (n + 255) & ~255L; }
 
 }  // namespace
@@ -264,6 +418,10 @@ long pitch_scratch_bytes(int B, int max_frames, int K) {
     const long fr = (long)B * max_frames;
     return align256(fr * K * 8) + align256(fr * 8) + 3 * align256(fr * NST * 8) + align256(fr * 4) + align256(fr * BPLD);
 }
+
+long pitch_stat_scratch_bytes(int B, int max_frames, int K) { return pitch_scratch_bytes(B, max_frames, K) + align256((long)B * max_frames * 8); }
+
+double* pitch_stat_track(void* base, int B, int max_frames, int K) { return (double*)((char*)base + pitch_scratch_bytes(B, max_frames, K)); }
 
 PitchScratch pitch_scratch(void* base, int B, int max_frames, int K) {
     const long fr = (long)B * max_frames;
@@ -294,14 +452,25 @@ hipError_t pitch_nccf(const double* wav, const int* n, int B, int max_n, double 
     return hipGetLastError();
 }
 
-hipError_t pitch_dp(const double* phi, const double* rms, const int* n, int B, int max_n, const PitchLags& g, double* f0,
+hipError_t pitch_dp(const double* phi, const double* rms, const double* stat, const int* n, int B, int max_n, const PitchLags& g, double* f0,
                     const PitchScratch& sc, hipStream_t s) {
     if (B < 1 || B > PITCH_MAX_ROWS || max_n < 513 || g.lmin < PITCH_MIN_LAG || g.lmax > PITCH_MAX_LAG || g.lmax - g.lmin + 1 < 3)
         return hipErrorInvalidValue;
     const int max_frames = max_n / HOP + 1;
     hipLaunchKernelGGL(cand_kernel, dim3(max_frames, B), dim3(NT), 0, s, phi, n, max_n, max_frames, g, sc.cost, sc.lag, sc.lnlag, sc.cnt);
-    hipLaunchKernelGGL(dp_kernel, dim3(B), dim3(64), 0, s, rms, (const double*)sc.cost, (const double*)sc.lag, (const double*)sc.lnlag,
-                       (const int*)sc.cnt, n, max_n, max_frames, sc.bp, f0);
+    if (stat)
+        hipLaunchKernelGGL(dp_kernel<true>, dim3(B), dim3(64), 0, s, rms, stat, (const double*)sc.cost, (const double*)sc.lag,
+                           (const double*)sc.lnlag, (const int*)sc.cnt, n, max_n, max_frames, sc.bp, f0);
+    else
+        hipLaunchKernelGGL(dp_kernel<false>, dim3(B), dim3(64), 0, s, rms, stat, (const double*)sc.cost, (const double*)sc.lag,
+                           (const double*)sc.lnlag, (const int*)sc.cnt, n, max_n, max_frames, sc.bp, f0);
+    return hipGetLastError();
+}
+
+hipError_t pitch_stationarity(const double* wav, const int* n, int B, int max_n, double scale, double* stat, hipStream_t s) {
+    if (B < 1 || B > PITCH_MAX_ROWS || max_n < 513) return hipErrorInvalidValue;
+    const int max_frames = max_n / HOP + 1;
+    hipLaunchKernelGGL(stat_kernel, dim3(max_frames, B), dim3(NT), 0, s, wav, n, max_n, max_frames, scale, stat);
     return hipGetLastError();
 }
 

@@ -26,9 +26,10 @@ Two parts of the reference come from libraries that are absent here, and both ar
     region, across 1 kHz, top band: tests/test_capi_host.py::test_mel_filter_bank_closed_form_slaney_values) and its published properties.
   * the F0 track (`pysptk.sptk.rapt`, :64): `pitch_track`, the published core of RAPT (Talkin 1995: normalised cross-correlation
     candidates plus dynamic programming, Talkin's constants) in RAPT's otype=2 output convention -- ln(F0 in Hz), -1e10 for unvoiced frames,
-    one value per 256-sample hop.  It is a Talkin-style tracker, NOT a port of SPTK: the spectral-stationarity term and the two-rate search
-    are left out (include/speechsplit_amd.h states the algorithm completely), and agreement with SPTK's own RAPT stays UNPINNED.  It is
-    pinned against a float64 numpy restatement (tests/pitch_ref.py) and against harmonic tones of known F0.
+    one value per 256-sample hop.  It is a Talkin-style tracker, NOT a port of SPTK: the two-rate search is left out and the
+    spectral-stationarity term is off unless `stationarity=True` asks for it (`pitch_track`, `extract_opt`, `extract_batch_sr`,
+    `make_spect_f0_opt`; include/speechsplit_amd.h states the algorithm completely), and agreement with SPTK's own RAPT stays UNPINNED.
+    It is pinned against float64 numpy restatements (tests/pitch_ref.py, tests/pitch_stat_ref.py) and against harmonic tones of known F0.
 The spectrogram half is pinned by tests/golden/features.npz, generated from the reference's own `butter_highpass` / `pySTFT` /
 `speaker_normalization`."""
 import ctypes as C
@@ -150,19 +151,29 @@ def f0_range(gender):
     raise ValueError(f"f0_range: gender must be 'M' or 'F', not {gender!r}")
 
 
-def pitch_track_dev(wav_dev, n_dev, lo, hi, scale=32768.0):
+def _stat_flag(who, stationarity):
+    """the `stationarity` option of `who`: True or False, anything else is refused by name"""
+    if not isinstance(stationarity, bool):
+        raise TypeError(f'{who}: stationarity must be True or False, not {stationarity!r}')
+    return stationarity
+
+
+def pitch_track_dev(wav_dev, n_dev, lo, hi, scale=32768.0, *, stationarity=False):
     """The C call on device tensors: wav float64 [B, max_n], n int32 [B] or None (every row has max_n samples) -> float64 [B, frames] of
-    ln(F0 in Hz), -1e10 for unvoiced frames and behind a row's own frames."""
+    ln(F0 in Hz), -1e10 for unvoiced frames and behind a row's own frames.  stationarity=True runs ss_pitch_track_stat: the tracker with
+    RAPT's spectral-stationarity term in the voicing transitions (an LPC analysis per frame); False is ss_pitch_track."""
+    _stat_flag('pitch_track_dev', stationarity)
     lib = _capi.lib()
     B, max_n = wav_dev.shape
-    nbytes = lib.ss_pitch_scratch_bytes(B, max_n, float(lo), float(hi))
+    size, track = (lib.ss_pitch_stat_scratch_bytes, lib.ss_pitch_track_stat) if stationarity else (lib.ss_pitch_scratch_bytes, lib.ss_pitch_track)
+    nbytes = size(B, max_n, float(lo), float(hi))
     if nbytes < 0:
         _capi.check(-1)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=wav_dev.device)
     f0 = torch.empty(B, lib.ss_melspec_frames(max_n), dtype=torch.float64, device=wav_dev.device)
-    _capi.check(lib.ss_pitch_track(C.c_void_p(wav_dev.data_ptr()), C.c_void_p(n_dev.data_ptr()) if n_dev is not None else None, B, max_n,
-                                   float(scale), float(lo), float(hi), C.c_void_p(f0.data_ptr()), C.c_void_p(scratch.data_ptr()), nbytes,
-                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    _capi.check(track(C.c_void_p(wav_dev.data_ptr()), C.c_void_p(n_dev.data_ptr()) if n_dev is not None else None, B, max_n,
+                    float(scale), float(lo), float(hi), C.c_void_p(f0.data_ptr()), C.c_void_p(scratch.data_ptr()), nbytes,
+                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return f0
 
 
@@ -328,12 +339,14 @@ def resample(xs, sr_in, sr_out=16000, max_rows=16, device='cuda'):
     return out[0] if single else out
 
 
-def pitch_track(wavs, lo, hi, max_rows=16, device='cuda'):
+def pitch_track(wavs, lo, hi, max_rows=16, device='cuda', *, stationarity=False):
     """make_spect_f0.py:64 with the Talkin-style tracker of csrc/pitch.hip in place of `sptk.rapt(wav.astype(np.float32) * 32768, fs, 256,
     min=lo, max=hi, otype=2)`.  One float64 waveform [n] at 16 kHz (or a list of them, any lengths >= 513) -> float64 numpy track(s)
     [n // 256 + 1] in input order.  The samples are rounded through float32 and scaled by 32768, as the reference does.  The utterances run
     as ragged batches of at most max_rows rows in convert.plan_batches order; every row is the result of running it alone, so the result
-    does not depend on max_rows."""
+    does not depend on max_rows.  stationarity=True adds RAPT's spectral-stationarity term (`pitch_track_dev`); with False the calls and the
+    bits are those of the tracker without it."""
+    more = {'stationarity': True} if _stat_flag('pitch_track', stationarity) else {}
     single = not isinstance(wavs, (list, tuple))
     ws = [np.ascontiguousarray(w, dtype=np.float64).astype(np.float32).astype(np.float64) for w in ([wavs] if single else wavs)]
     for w in ws:
@@ -345,7 +358,7 @@ def pitch_track(wavs, lo, hi, max_rows=16, device='cuda'):
         wav = np.zeros((len(batch), lens[-1]))
         for r, i in enumerate(batch):
             wav[r, :lens[r]] = ws[i]
-        f0 = pitch_track_dev(torch.from_numpy(wav).to(device), torch.tensor(lens, dtype=torch.int32, device=device), lo, hi).cpu().numpy()
+        f0 = pitch_track_dev(torch.from_numpy(wav).to(device), torch.tensor(lens, dtype=torch.int32, device=device), lo, hi, **more).cpu().numpy()
         for r, i in enumerate(batch):
             out[i] = f0[r, :lens[r] // 256 + 1].copy()
     return out[0] if single else out
@@ -398,14 +411,26 @@ def extract(x, prng, gender, device='cuda', mel_basis=None, unvoiced=0.0, sr=160
     prng is the speaker's numpy RandomState (the dither draws from it, so recordings of one speaker go through in the reference's order).
     mel_basis [513, n_mels] defaults to mel_filter_bank().T, the reference's.  f0_norm is in [0, 1] on voiced frames and `unvoiced` elsewhere:
     0 by default, which `quantize_f0` reads as unvoiced (<= 0); the reference's speaker_normalization leaves its -1e10 marker in those frames
-    (utils.py:39-41 touch the voiced frames only), and that is what its files carry -- make_spect_f0 passes unvoiced=-1e10."""
+    (utils.py:39-41 touch the voiced frames only), and that is what its files carry -- make_spect_f0 passes unvoiced=-1e10.
+    (Its argument list is pinned; `extract_opt` takes the same and `stationarity` by keyword.)"""
+    return _extract(x, prng, gender, device, mel_basis, unvoiced, sr, False)
+
+
+def extract_opt(x, prng, gender, *, device='cuda', mel_basis=None, unvoiced=0.0, sr=16000, stationarity=False):
+    """`extract` with its options by keyword, and the one it cannot take: stationarity=True tracks the pitch with RAPT's
+    spectral-stationarity term (`pitch_track(..., stationarity=True)`).  With False it is `extract`: the same calls, the same bits."""
+    return _extract(x, prng, gender, device, mel_basis, unvoiced, sr, _stat_flag('extract_opt', stationarity))
+
+
+def _extract(x, prng, gender, device, mel_basis, unvoiced, sr, stationarity):
+    """extract's body; `stationarity` is handed to pitch_track only when it is set, so that the default makes the earlier calls"""
     x = np.asarray(x, np.float64)
     if sr != 16000:
         x = resample(x, sr, 16000, device=device)
     wav = preprocess_wav(x, prng)
     S = melspectrogram(wav, mel_filter_bank().T.astype(np.float64) if mel_basis is None else mel_basis, device).cpu().numpy()
     lo, hi = f0_range(gender)
-    f0_rapt = pitch_track(wav, lo, hi, device=device)
+    f0_rapt = pitch_track(wav, lo, hi, device=device, **({'stationarity': True} if stationarity else {}))
     f0_norm = normalize_f0(f0_rapt, device).cpu().numpy()
     assert len(S) == len(f0_rapt)
     return S.astype(np.float32), np.where(f0_rapt != -1e10, f0_norm, np.float32(unvoiced)).astype(np.float32)
@@ -461,13 +486,13 @@ def extract_batch(xs, prng, gender, max_rows=16, device='cuda', mel_basis=None, 
     return _extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced, False)
 
 
-def _extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced, device_draws):
+def _extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced, device_draws, stationarity=False):
     """extract_batch, with the draw on the host or (device_draws) on the GPU: one `rand_dev` for the sum of the (fixed-up) lengths in input
     order -- the same numbers, and prng is left in the same state -- and one ss_dither_rows a batch hands each row its stretch; the upload
     then carries the recordings only."""
     f0_range(gender)                                                    # an unknown gender stops the call before a draw is made
     flat, lens, batches = stage_batches(xs, prng, max_rows, **({'host_draws': False} if device_draws else {}))
-    chain = _Chain(gender, device, mel_basis, unvoiced)
+    chain = _Chain(gender, device, mel_basis, unvoiced, stationarity)
     flat_dev, lens_dev = torch.from_numpy(flat).to(device), torch.from_numpy(lens).to(device)
     if device_draws:
         own = np.zeros(len(xs), dtype=np.int64)                         # the fixed-up lengths in input order
@@ -491,8 +516,9 @@ class _Chain:
     """The four device calls of extract_batch on one batch: x, r float64 [B, max_n] (recordings after the odd-length fix, their dither draws)
     and the rows' lengths on the device (n) and on the host (lens) -> [(S, f0_norm)] a row, after one copy back."""
 
-    def __init__(self, gender, device, mel_basis, unvoiced):
+    def __init__(self, gender, device, mel_basis, unvoiced, stationarity=False):
         self.lo, self.hi = f0_range(gender)
+        self.more = {'stationarity': True} if stationarity else {}         # handed to pitch_track_dev only when it is set
         self.b, self.a = butter_highpass(30, 16000, order=5)
         self.zi = signal.lfilter_zi(self.b, self.a)
         self.mb = torch.as_tensor(np.ascontiguousarray(mel_filter_bank().T if mel_basis is None else mel_basis, dtype=np.float64)).to(device)
@@ -502,7 +528,7 @@ class _Chain:
         B, max_n = x.shape
         wav = filtfilt_dev(x, n, self.b, self.a, self.zi, 0.96, r, 1e-06)
         S = melspec_batch_dev(wav, n, self.mb)
-        f0 = pitch_track_dev(wav.float().double(), n, self.lo, self.hi)     # the float32 round trip of make_spect_f0.py:64
+        f0 = pitch_track_dev(wav.float().double(), n, self.lo, self.hi, **self.more)     # the float32 round trip of make_spect_f0.py:64
         f0n = f0_normalize_batch_dev(f0, n, max_n, self.unvoiced)
         F, M = S.shape[1], S.shape[2]
         both = torch.cat((S.reshape(B, F * M), f0n), dim=1).cpu().numpy()
@@ -513,7 +539,8 @@ class _Chain:
         return out
 
 
-def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis=None, unvoiced=0.0, *, device_draws=False):
+def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis=None, unvoiced=0.0, *, device_draws=False,
+                     stationarity=False):
     """`extract_batch` for recordings at any sample rate: sr is one rate in Hz for all of xs, or one a recording.  The same as
     extract_batch([scipy.signal.resample_poly(x, 16000, sr) ...], prng, gender, ...), to the bit, with the resampling on the GPU in front of the
     chain and nothing brought back between them: the recordings are grouped by rate and each group runs through ss_resample as ragged batches in
@@ -521,12 +548,17 @@ def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis
     without waiting for the device -- with the draws in input order; then extract_batch's four calls on batches of the resampled recordings.
     With every rate 16000 this IS extract_batch: the same calls on the same data.  device_draws=True makes the dither draw on the GPU: one
     `rand_dev` for the sum of the fixed-up (resampled) lengths in input order -- the same numbers, prng left in the same state -- and one
-    ss_dither_rows a batch; the default makes exactly the host's calls."""
+    ss_dither_rows a batch; the default makes exactly the host's calls.  stationarity=True tracks the pitch with RAPT's
+    spectral-stationarity term (`pitch_track_dev(..., stationarity=True)`); with False the calls and the bits are today's.  (`extract_batch`'s
+    argument list is pinned, so this is also the batched entry point for that option at 16 kHz.)"""
+    _stat_flag('extract_batch_sr', stationarity)
     xs = [np.ascontiguousarray(x, dtype=np.float64) for x in xs]
     srs = [sr] * len(xs) if np.ndim(sr) == 0 else list(sr)
     if len(srs) != len(xs):
         raise ValueError(f'extract_batch_sr: {len(srs)} sample rates for {len(xs)} recordings')
     if all(s == 16000 for s in srs):
+        if stationarity:
+            return _extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced, bool(device_draws), True)
         if device_draws:
             return _extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced, True)
         return extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced)
@@ -555,7 +587,7 @@ def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis
             ys = _resample_group([xs[i] for i in group], ratio[0], ratio[1], max_rows, device)
         for i, y in zip(group, ys):
             wav16[i] = y
-    chain = _Chain(gender, device, mel_basis, unvoiced)
+    chain = _Chain(gender, device, mel_basis, unvoiced, stationarity)
     out, row = [None] * len(xs), 0
     for idx in plan:
         B, max_n = len(idx), lens[idx[-1]]
@@ -585,7 +617,7 @@ def make_spect_f0(root_dir='assets/wavs', target_dir='assets/spmel', target_dir_
     1e-6).  resample=False reads 16 kHz files only (`read_wav`, which refuses every other rate by name, as the reference asserts); True reads
     mono PCM of any rate and width (`read_audio`) and brings it to 16 kHz on the GPU first, writing the files the 16 kHz path writes for
     scipy.signal.resample_poly(x, 16000, sr).  Returns the (speaker, name) pairs written.  (Its argument list is pinned; the batched walk
-    with its further options is `make_spect_f0_batched`.)"""
+    with its further options is `make_spect_f0_batched`, and `make_spect_f0_opt` takes every option, `stationarity` among them.)"""
     return _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, False)
 
 
@@ -601,9 +633,26 @@ def make_spect_f0_batched(root_dir='assets/wavs', target_dir='assets/spmel', tar
     return _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, device_draws)
 
 
-def _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, device_draws):
-    """make_spect_f0's walk; device_draws is handed to extract_batch_sr only when it is set, so that the default makes the earlier calls"""
+def make_spect_f0_opt(root_dir='assets/wavs', target_dir='assets/spmel', target_dir_f0='assets/raptf0', spk2gen='assets/spk2gen.pkl', *,
+                      device='cuda', resample=False, max_rows=None, device_draws=False, stationarity=False):
+    """The walk of `make_spect_f0` (max_rows=None: file by file) and of `make_spect_f0_batched` (an integer) with every option by keyword,
+    and the one their pinned argument lists cannot take: stationarity=True tracks the pitch with RAPT's spectral-stationarity term.  With
+    False it writes the files those two write.  Returns the (speaker, name) pairs written."""
+    if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, int) or max_rows < 1):
+        raise ValueError(f'make_spect_f0_opt: max_rows must be None or a positive integer, not {max_rows!r}')
+    if not isinstance(device_draws, bool):
+        raise TypeError(f'make_spect_f0_opt: device_draws must be True or False, not {device_draws!r}')
+    if device_draws and max_rows is None:
+        raise ValueError('make_spect_f0_opt: device_draws needs the batched walk (max_rows)')
+    return _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, device_draws,
+                 _stat_flag('make_spect_f0_opt', stationarity))
+
+
+def _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, device_draws, stationarity=False):
+    """make_spect_f0's walk; device_draws and stationarity are handed on only when they are set, so that the default makes the earlier calls"""
     more = {'device_draws': True} if device_draws else {}
+    if stationarity:
+        more['stationarity'] = True
     if not isinstance(resample, bool):
         raise TypeError(f'make_spect_f0: resample must be True or False, not {resample!r} (max_rows goes by keyword)')
     if not isinstance(spk2gen, dict):
@@ -629,7 +678,8 @@ def _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_ro
                 S, f0_norm = feats[k]
             else:
                 x, sr = read(name)
-                S, f0_norm = extract(x, prng, spk2gen[subdir], device, unvoiced=-1e10, sr=sr)
+                S, f0_norm = _extract(x, prng, spk2gen[subdir], device, None, -1e10, sr, True) if stationarity else \
+                    extract(x, prng, spk2gen[subdir], device, unvoiced=-1e10, sr=sr)
             np.save(os.path.join(target_dir, subdir, name[:-4]), S, allow_pickle=False)
             np.save(os.path.join(target_dir_f0, subdir, name[:-4]), f0_norm, allow_pickle=False)
             done.append((subdir, name[:-4]))

@@ -3,6 +3,8 @@
 float64 numpy restatement (tests/pitch_ref.py) on the same box:
   * ss_pitch_track on --rows utterances of --seconds each (default 64 x 3 s: 188 frames a row) for the ranges (50, 250) and (100, 600), in
     milliseconds, and its two halves alone (ss_op_nccf; ss_op_pitch_dp = candidates + dynamic programming);
+  * the same with RAPT's spectral-stationarity term: ss_pitch_track_stat, ss_op_pitch_stationarity alone (the LPC analysis per frame) and
+    ss_op_pitch_dp_stat (candidates + dynamic programming with the term), in the same run;
   * pitch_ref.track on the first --ref-rows of the same utterances (wall clock, one pass), per utterance, and whether the two agree there.
     python tools/pitch_bench.py [--rows 64] [--seconds 3] [--reps 20] [--warmup 3] [--ref-rows 4]
 The utterances are harmonic glides with pauses and noise, seeded per row.  Prints one JSON line."""
@@ -41,6 +43,7 @@ def main():
     a = ap.parse_args()
     from speechsplit_amd import _capi
     from tests import pitch_ref as R
+    from tests import pitch_stat_ref as Q
     lib = _capi.lib()
     dev = torch.device('cuda:0')
     B, n = a.rows, int(a.seconds * 16000)
@@ -58,10 +61,16 @@ def main():
         f0 = torch.empty(B, F, dtype=torch.float64, device=dev)
         phi = torch.empty(B, F, K, dtype=torch.float64, device=dev)
         rms = torch.empty(B, F, dtype=torch.float64, device=dev)
+        stat = torch.empty(B, F, dtype=torch.float64, device=dev)
+        nbytes_stat = lib.ss_pitch_stat_scratch_bytes(B, n, lo, hi)
+        scratch_stat = torch.empty(nbytes_stat, dtype=torch.uint8, device=dev)
         calls = {
             'pitch_track': lambda: lib.ss_pitch_track(p(wav), None, B, n, 32768.0, lo, hi, p(f0), p(scratch), nbytes, s),
             'nccf': lambda: lib.ss_op_nccf(p(wav), None, B, n, 32768.0, lo, hi, p(phi), p(rms), s),
             'candidates_dp': lambda: lib.ss_op_pitch_dp(p(phi), p(rms), None, B, n, lo, hi, p(f0), p(scratch), nbytes, s),
+            'pitch_track_stat': lambda: lib.ss_pitch_track_stat(p(wav), None, B, n, 32768.0, lo, hi, p(f0), p(scratch_stat), nbytes_stat, s),
+            'stationarity': lambda: lib.ss_op_pitch_stationarity(p(wav), None, B, n, 32768.0, p(stat), s),
+            'candidates_dp_stat': lambda: lib.ss_op_pitch_dp_stat(p(phi), p(rms), p(stat), None, B, n, lo, hi, p(f0), p(scratch), nbytes, s),
         }
         times = {k: [] for k in calls}
         for it in range(a.warmup + a.reps):
@@ -78,6 +87,10 @@ def main():
         refs = [R.track(host[b], lo, hi) for b in range(min(a.ref_rows, B))]
         ref_ms = (time.perf_counter() - t0) * 1e3 / max(len(refs), 1)
         same = all(np.array_equal(R.voiced(r), R.voiced(g)) and np.allclose(r, g, rtol=1e-10, atol=0.0) for r, g in zip(refs, got))
+        _capi.check(calls['pitch_track_stat']())
+        got_stat = f0.cpu().numpy()
+        refs_stat = [Q.track_stat(host[b], lo, hi) for b in range(min(a.ref_rows, B))]
+        same_stat = all(np.array_equal(R.voiced(r), R.voiced(g)) and np.allclose(r, g, rtol=1e-10, atol=0.0) for r, g in zip(refs_stat, got_stat))
         med = {k: statistics.median(v) for k, v in times.items()}
         out['ranges'][f'{int(lo)}-{int(hi)}'] = {
             'lags': K, 'scratch_mib': round(nbytes / 2 ** 20, 2),
@@ -85,6 +98,7 @@ def main():
             'ms_minmax': {k: [round(min(v), 4), round(max(v), 4)] for k, v in times.items()},
             'us_per_utterance': round(med['pitch_track'] * 1e3 / B, 2),
             'voiced_fraction': round(float(R.voiced(got).mean()), 3),
+            'voiced_fraction_stat': round(float(R.voiced(got_stat).mean()), 3), 'stat_agrees_with_numpy': bool(same_stat),
             'numpy_ms_per_utterance': round(ref_ms, 1), 'numpy_rows': len(refs), 'agrees_with_numpy': bool(same),
             'numpy_over_gpu': round(ref_ms / (med['pitch_track'] / B), 1)}
     print(json.dumps(out))
