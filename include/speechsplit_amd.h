@@ -917,6 +917,136 @@ int ss_op_dec_in_codes(const ss_code_src* src, int nsrc, const float* emb_dev, i
                        float* dst_dev, int ld, int B, int T, int f, void* stream);
 int ss_op_spk_grad(const float* dg_dev, long ld, long b_stride, int rows, const float* w_f_dev, const float* w_r_dev, long w_ld, int col0, int H4,
                    int E, float* out_dev, int B, void* stream);
+/* The fused weight gradients of the encoder BLSTMs (speechsplit_amd/csrc/lstm_wgrad.hip) as the engine launches them: a TABLE of 1 .. 8 tasks
+ * in one launch, each with its own H (1 .. 32), In, R and strides, on the CALLER's memory.  Per task, with dg [R][8 H] dense, x [R][In] (row
+ * stride x_ld) and hout [R][2 H] (row stride h_ld; the columns behind 2 H are never read), for both directions d:
+ *     gwih[d][n][k] += sum_r dg[r][d 4H + n] x[r][k]                  gwih [2][4 H][In]
+ *     gwhh[0][n][k] += sum_r dg[r + 1][n] hout[r][k]                  gwhh [2][4 H][H]    (r + 1 < R)
+ *     gwhh[1][n][k] += sum_r dg[r][4H + n] hout[r + 1][H + k]         (r + 1 < R)
+ *     gb[d][0][n] and gb[d][1][n] += sum_r dg[r][d 4H + n]            gb [2][2][4 H]      (b_ih and b_hh have the same gradient)
+ * ROW 0 OF dg MUST BE ZERO (it is a halo row in every slab): the forward direction's bias is summed beside its W_hh, over dg[r + 1], so a
+ * non-zero row 0 would be missing from gb[0].  Not checked: dg is device data.
+ * The rows are cut into row_groups groups of ceil(ceil(R / row_groups) / 64) 64 rows (the last ones may be empty); a group's sum is one fp32
+ * chain of fused multiply-adds in row order, the groups' sums are added in float64 in group order, rounded to fp32 once and added (fp32) to
+ * what the output holds.  The same bits on every call, whatever the order the workgroups arrive in.  part_dev: scratch of at least
+ * ss_op_lstm_wgrad_table_floats(t, n, row_groups) = tiles row_groups 4096 floats, 16-byte aligned; ctr_dev: at least
+ * ss_op_lstm_wgrad_table_counters(t, n) = tiles words, ZERO on entry and zero again when the launch retires (tiles: the sum over the tasks of
+ * ceil(8 H / 64) (ceil(In / 64) + (4 H % 64 == 0 ? 1 : 2))).  Both size functions return 0 for a table the hook would refuse.  Refused before
+ * anything is enqueued: a null pointer, n outside 1 .. 8, row_groups outside 1 .. 1024, H outside 1 .. 32, In or R below 1, x_ld < In,
+ * h_ld < 2 H, dg not 16-byte aligned, more than 65535 tiles, scratch or counters too small or misaligned. */
+typedef struct ss_wgrad_task {
+    const float* dg;
+    const float* x;
+    long x_ld;
+    const float* hout;
+    long h_ld;
+    float *gwih, *gwhh, *gb;
+    int H, In;
+    long R;
+} ss_wgrad_task;
+long ss_op_lstm_wgrad_table_floats(const ss_wgrad_task* t, int n, int row_groups);
+int ss_op_lstm_wgrad_table_counters(const ss_wgrad_task* t, int n);
+int ss_op_lstm_wgrad_table(const ss_wgrad_task* t, int n, int row_groups, float* part_dev, long part_floats, unsigned* ctr_dev, int ctr_words,
+                           void* stream);
+/* The random-resampling kernels (speechsplit_amd/csrc/interp.hip; reference InterpLnr, model.py:355-436, and quantize_f0_torch,
+ * utils.py:62-74), engine-free and on the CALLER's memory: each hook hands its arguments to one kernel launcher and does nothing else.
+ * Every refusal is made before anything is enqueued.  A PLAN for B utterances is (i0 i32 [B][P], lam f32 [B][P], nrows i32 [B]) and, for the
+ * adjoint, start i32 [B][T + 1].
+ *   ss_op_interp_plan  the index path, bit-exact to the reference: per utterance b and segment s < S, candidate j < ncand has the fp32
+ *                    quotient q = j / scales[b S + s] (IEEE division), fl = floor(q), lam = q - fl, and is KEPT when fl < len_seg[b S + s] - 1
+ *                    and fl + off < len - 1, off being the sum of the utterance's earlier len_seg and len = len_seq_dev[b] (len_seq_dev
+ *                    NULL: len_seq_const).  The kept candidates in (s, j) order are the output rows: counts[b] is their number,
+ *                    nrows[b] = min(counts[b], P), i0[b][r] = fl + off and lam[b][r] for r < nrows[b], and ZERO in both for nrows[b] <= r < P.
+ *                    start[b][i] = the number of rows r < nrows[b] with i0[b][r] < i, for i = 0 .. T (i0 is non-decreasing in r).  Any S,
+ *                    ncand <= 64, P <= 512 and T.  The scales must be positive with j / scale inside an int, and len_seq <= T if the plan is to
+ *                    index T frames: both are device data, NOT CHECKED.  Refused: a null pointer (len_seq_dev may be NULL), B / S / T below 1,
+ *                    ncand outside 1 .. 64, P outside 1 .. 512, len_seq_const outside 0 .. T when it is used.
+ *   ss_op_interp_gather  y(b, r, c) = (1 - lam) * x(b, i0, c) + lam * x(b, i0 + 1, c) for r < nrows[b] -- fp32, the two products and the sum
+ *                    rounded separately, subnormal products kept (no flush to zero) -- and +0.0 for nrows[b] <= r < P; x and y are VIEWS
+ *                    (p, ld, bs) with p at frame 0.  Rows of x other than i0 and i0 + 1 of a live row are never read.  y_img_dev (nullable):
+ *                    also the image of y (what ss_op_split_image makes of y at the scale *img_scale_dev, NULL: 16), same geometry as y.
+ *                    Refused: a null pointer, B / P outside 1 .. 65535, C below 1, a row stride below C, img_scale_dev without y_img_dev, and
+ *                    an image when C % 8, x_ld % 4, x_bs % 4, y_ld % 8 or y_bs % 8 is not 0, x / y is not 16-byte or y_img not 32-byte aligned
+ *                    (the launcher would drop the image silently).
+ *   ss_op_interp_quant  the training step's outer resampling: mel [B][T][CM] and f0 [B][T] dense.  ymel(b, r, c < CM) as the gather; f as
+ *                    the gather of f0; the class q = 0 when not f > 0 (unvoiced, -0.0, NaN), else min(rint(f * 255) + 1, NOH - 1), rint
+ *                    to nearest even, the product in fp32; qidx[b][r] = q; yoh(b, r, c) = (c == q) for ALL yo_ld columns of the row (the
+ *                    padding columns behind NOH are written zero).  Rows nrows[b] <= r < P: ymel zeros, class 0.  f * 255 must fit an int
+ *                    (not checked).  Refused: a null pointer, B / P outside 1 .. 65535, T below 2, CM below 1, NOH below 2, ym_ld < CM,
+ *                    yo_ld < NOH.
+ *   ss_op_interp_scatter  the gather's adjoint through start: dx(b, i, c) = sum over the rows r with i0 = i, ascending, of (1 - lam_r)
+ *                    dy(b, r, c), then over the rows with i0 = i - 1 of lam_r dy(b, r, c): one fp32 chain of fused multiply-adds from 0, the
+ *                    weight 1 - lam_r rounded to fp32 first.  Every frame i < T of every utterance is written: +0.0 where no row contributes.
+ *                    The same bits on every call.  Refused: a null pointer, B / P outside 1 .. 65535, T or C below 1, a row stride below C. */
+int ss_op_interp_plan(const float* scales_dev, const int* len_seg_dev, const int* len_seq_dev, int len_seq_const, int S, int ncand, int P, int T,
+                      int B, int* i0_dev, float* lam_dev, int* nrows_dev, int* counts_dev, int* start_dev, void* stream);
+int ss_op_interp_gather(const int* i0_dev, const float* lam_dev, const int* nrows_dev, int P, const float* x_dev, long x_ld, long x_bs, float* y_dev,
+                        long y_ld, long y_bs, int C, int B, float* y_img_dev, const float* img_scale_dev, void* stream);
+int ss_op_interp_quant(const int* i0_dev, const float* lam_dev, const int* nrows_dev, int P, int T, const float* mel_dev, const float* f0_dev, int CM,
+                       float* ymel_dev, long ym_ld, long ym_bs, float* yoh_dev, long yo_ld, long yo_bs, int NOH, int* qidx_dev, int B, void* stream);
+int ss_op_interp_scatter(const float* lam_dev, const int* start_dev, int P, int T, const float* dy_dev, long dy_ld, long dy_bs, float* dx_dev,
+                         long dx_ld, long dx_bs, int C, int B, void* stream);
+/* The re-layout and guard kernels of a training step (speechsplit_amd/csrc/elementwise.hip, input_grads.hip), engine-free and on the CALLER's
+ * memory like the hooks above: each hands its operands to one kernel launcher and does nothing else.  Every move is exact: no hook here
+ * rounds anything but the images.  An IMAGE beside an fp32 tensor of n elements is, with img_bf16 == 0, what ss_op_split_image makes of that
+ * tensor at scale 16 (n % 8 == 0, base 32-byte aligned) and, with img_bf16 != 0, the tensor rounded to bf16 (to nearest even; 2 bytes per
+ * element, base 8-byte aligned).  Every refusal is made before anything is enqueued.
+ *   ss_op_conv_pack  conv weight w [Co][Ci][5] -> the forward pack wf [Co][5][Cp], wf[co][k][c] = w[co][c][k] for c < Ci and ZERO for
+ *                    Ci <= c < Cp, and (wb_dev not NULL) the input-gradient pack wb [Ci][5][Co], wb[ci][k][co] = w[co][ci][4 - k] (taps
+ *                    flipped); wf_img / wb_img (nullable): their images.  Refused: a null w / wf, a dimension below 1, Co % 4 != 0,
+ *                    Cp % 4 != 0, Cp below Ci, wb_img without wb, wf / wb not 16-byte aligned, an image that breaks the rule above.
+ *   ss_op_conv_pack_many  1 .. 8 such tasks in one launch, the same bits as one ss_op_conv_pack each.
+ *   ss_op_conv_pack_dx  wb [Ci][5][Co] alone, for any Ci and Co.
+ *   ss_op_conv_unpack  packed weight gradient gp [Co][5][Cp] -> g [Co][Ci][5], g[co][ci][k] = gp[co][k][ci] (acc == 0) or g += (acc != 0);
+ *                    the columns Ci <= c < Cp of gp are never read.  ss_op_conv_unpack_many: 1 .. 8 tasks in one launch.  Refused: a null
+ *                    pointer, a dimension below 1, Cp below Ci.
+ *   ss_op_prep       1 .. 48 tasks dst[i] = a[i] + b[i] (b NULL: dst is a COPY OF THE BITS of a, -0.0 and NaN payloads included), i < n, and
+ *                    (img not NULL) the image of dst.  A task moves as float4 when n % 4 == 0 and a, b, dst are 16-byte aligned, else
+ *                    element by element, with the same result.  Refused: a null a / dst, n below 1, a task with an image that could not
+ *                    take the float4 path (the kernel would drop the image), an image that breaks the rule above.
+ *   ss_op_transpose  out [C][R] = in [R][C]^T, both dense.  Refused: a null pointer, R or C below 1, R above 65535 * 32.
+ *   ss_op_copy_rows  dst(b, t, c) = src(b, t, c) for c < C, both VIEWS (p, ld, bs) as above.  len_dev (nullable; i32 [B]): rows at or beyond
+ *                    L_b = min(max(len[b], 0), T) of src are never read and dst gets +0.0 there.  Nothing else of dst is written (halo
+ *                    rows and row gaps keep their bits).  Refused: a null src / dst, B outside 1 .. 65535, T or C below 1, a row stride
+ *                    below C.
+ *   ss_op_act_scales  out[i] for 1 .. 8 blocks: with bound = fmaf(sqrtf(16 T), max|gamma_i|, max|beta_i|) over the block's C_i channels
+ *                    (fp32, one fused multiply-add), out[i] = min(16, the largest power of two s >= 2^-20 with
+ *                    bound * s <= 32768).  A bound of +inf KEEPS 16: no scale makes that block's products finite, ss_op_param_guard's kernel
+ *                    reports the parameter and the step that computed the scale is skipped.  A NaN element does not enter the maxima (the
+ *                    guard reports it as well).  C_i == 0: bound 0, 16.  Refused: a null array, n outside 1 .. 8, T below 1, C_i < 0, a null
+ *                    gamma_i / beta_i with C_i > 0.
+ *   ss_op_param_guard  *sticky_dev |= SS_STATUS_RANGE if any of p[0 .. n) is NaN, infinite or has |p| >= limit; no other bit of the word
+ *                    changes and a clean arena leaves it as it was.  Refused: a null pointer, n not a positive multiple of 4, p_dev not
+ *                    16-byte aligned. */
+typedef struct ss_conv_pack_task {
+    const float* w;
+    float *wf, *wb, *wf_img, *wb_img;
+    int Co, Ci, Cp;
+} ss_conv_pack_task;
+typedef struct ss_conv_unpack_task {
+    const float* gp;
+    float* g;
+    int Co, Ci, Cp;
+} ss_conv_unpack_task;
+typedef struct ss_prep_task {
+    const float* a;
+    const float* b;
+    float* dst;
+    long n;
+    float* img;
+} ss_prep_task;
+int ss_op_conv_pack(const float* w_dev, int Co, int Ci, int Cp, float* wf_dev, float* wb_dev, float* wf_img_dev, float* wb_img_dev, int img_bf16,
+                    void* stream);
+int ss_op_conv_pack_many(const ss_conv_pack_task* t, int n, int img_bf16, void* stream);
+int ss_op_conv_pack_dx(const float* w_dev, int Co, int Ci, float* wb_dev, void* stream);
+int ss_op_conv_unpack(const float* gp_dev, int Co, int Ci, int Cp, float* g_dev, int acc, void* stream);
+int ss_op_conv_unpack_many(const ss_conv_unpack_task* t, int n, int acc, void* stream);
+int ss_op_prep(const ss_prep_task* t, int n, int img_bf16, void* stream);
+int ss_op_transpose(const float* in_dev, int R, int C, float* out_dev, void* stream);
+int ss_op_copy_rows(const float* src_dev, long s_ld, long s_bs, float* dst_dev, long d_ld, long d_bs, const int* len_dev, int B, int T, int C,
+                    void* stream);
+int ss_op_act_scales(const float* const* gamma_dev, const float* const* beta_dev, const int* C, int n, int T, float* out_dev, void* stream);
+int ss_op_param_guard(const float* p_dev, long n, float limit, unsigned* sticky_dev, void* stream);
 /* The GEMM over operand images (speechsplit_amd/csrc/gemm_img.hip), the engine's default for every large contraction: an IMAGE has the
  * geometry of its fp32 matrix (4 bytes per element) with every aligned group of 8 elements along the contiguous axis replaced by 16 bytes of
  * hi pieces and 16 bytes of lo pieces of the fp16 x 2 split of scale * x (scale a power of two).

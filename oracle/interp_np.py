@@ -55,6 +55,17 @@ def interp_plan(scales, len_seg, len_seq, max_len_seg=32, max_len_pad=192):
     return i0, lm, counts, nrows
 
 
+def interp_start(i0, nrows, T):
+    """Inverse map the collision-free backward reads: start[b, i] = #{r < nrows[b] : i0[b, r] < i} for i = 0 .. T, int32[B, T + 1].
+    Counted from the definition (i0 is non-decreasing in r, but nothing here relies on it)."""
+    B = i0.shape[0]
+    start = np.zeros((B, T + 1), np.int32)
+    grid = np.arange(T + 1)[:, None]
+    for b in range(B):
+        start[b] = (i0[b, : int(nrows[b])][None, :] < grid).sum(1)
+    return start
+
+
 def interp_apply(x, i0, lam, nrows):
     """Value path (model.py:426-430, 368-377): y = (1-lam)*x[i0] + lam*x[i0+1], zero padded."""
     x = np.asarray(x, dtype=np.float32)

@@ -45,6 +45,27 @@ class SSCodeSrc(C.Structure):
     _fields_ = [('o', C.c_void_p), ('d_o', C.c_void_p), ('H', C.c_int), ('freq', C.c_int), ('col', C.c_int), ('ld', C.c_int)]
 
 
+class SSConvPackTask(C.Structure):
+    """ss_conv_pack_task (test hook ss_op_conv_pack_many): one conv weight and its packs / images."""
+    _fields_ = [(n, C.c_void_p) for n in ('w', 'wf', 'wb', 'wf_img', 'wb_img')] + [(n, C.c_int) for n in ('Co', 'Ci', 'Cp')]
+
+
+class SSConvUnpackTask(C.Structure):
+    """ss_conv_unpack_task (test hook ss_op_conv_unpack_many): one packed weight gradient and the gradient it unpacks into."""
+    _fields_ = [('gp', C.c_void_p), ('g', C.c_void_p)] + [(n, C.c_int) for n in ('Co', 'Ci', 'Cp')]
+
+
+class SSWgradTask(C.Structure):
+    """ss_wgrad_task (test hook ss_op_lstm_wgrad_table): one BLSTM layer's operands and gradient outputs."""
+    _fields_ = [('dg', C.c_void_p), ('x', C.c_void_p), ('x_ld', C.c_long), ('hout', C.c_void_p), ('h_ld', C.c_long), ('gwih', C.c_void_p),
+                ('gwhh', C.c_void_p), ('gb', C.c_void_p), ('H', C.c_int), ('In', C.c_int), ('R', C.c_long)]
+
+
+class SSPrepTask(C.Structure):
+    """ss_prep_task (test hook ss_op_prep): dst = a + b (b NULL: a copy) over n floats, img (nullable) the image of dst."""
+    _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('dst', C.c_void_p), ('n', C.c_long), ('img', C.c_void_p)]
+
+
 # every symbol include/speechsplit_amd.h declares: name -> (restype, argtypes)
 _vp, _fp, _ip, _i, _l, _f, _d = C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 SYMBOLS = {
@@ -131,6 +152,32 @@ SYMBOLS = {
     'ss_op_dec_in_codes': (_i, [C.POINTER(SSCodeSrc), _i, _fp, _i, _i, _fp, _l, _fp, _i, _i, _i, _i, _vp]),
     # dg, ld, b_stride, rows, w_f, w_r, w_ld, col0, H4, E, out, B, stream
     'ss_op_spk_grad': (_i, [_fp, _l, _l, _i, _fp, _fp, _l, _i, _i, _i, _fp, _i, _vp]),
+    # tasks, n, row_groups / tasks, n / tasks, n, row_groups, part, part_floats, ctr, ctr_words, stream
+    'ss_op_lstm_wgrad_table_floats': (_l, [C.POINTER(SSWgradTask), _i, _i]),
+    'ss_op_lstm_wgrad_table_counters': (_i, [C.POINTER(SSWgradTask), _i]),
+    'ss_op_lstm_wgrad_table': (_i, [C.POINTER(SSWgradTask), _i, _i, _fp, _l, _vp, _i, _vp]),
+    # scales, len_seg, len_seq, len_seq_const, S, ncand, P, T, B, i0, lam, nrows, counts, start, stream
+    'ss_op_interp_plan': (_i, [_fp, _ip, _ip, _i, _i, _i, _i, _i, _i, _ip, _fp, _ip, _ip, _ip, _vp]),
+    # i0, lam, nrows, P, x, x_ld, x_bs, y, y_ld, y_bs, C, B, y_img, img_scale, stream
+    'ss_op_interp_gather': (_i, [_ip, _fp, _ip, _i, _fp, _l, _l, _fp, _l, _l, _i, _i, _fp, _fp, _vp]),
+    # i0, lam, nrows, P, T, mel, f0, CM, ymel, ym_ld, ym_bs, yoh, yo_ld, yo_bs, NOH, qidx, B, stream
+    'ss_op_interp_quant': (_i, [_ip, _fp, _ip, _i, _i, _fp, _fp, _i, _fp, _l, _l, _fp, _l, _l, _i, _ip, _i, _vp]),
+    # lam, start, P, T, dy, dy_ld, dy_bs, dx, dx_ld, dx_bs, C, B, stream
+    'ss_op_interp_scatter': (_i, [_fp, _ip, _i, _i, _fp, _l, _l, _fp, _l, _l, _i, _i, _vp]),
+    # w, Co, Ci, Cp, wf, wb, wf_img, wb_img, img_bf16, stream / tasks, n, img_bf16, stream / w, Co, Ci, wb, stream
+    'ss_op_conv_pack': (_i, [_fp, _i, _i, _i, _fp, _fp, _fp, _fp, _i, _vp]),
+    'ss_op_conv_pack_many': (_i, [C.POINTER(SSConvPackTask), _i, _i, _vp]),
+    'ss_op_conv_pack_dx': (_i, [_fp, _i, _i, _fp, _vp]),
+    # gp, Co, Ci, Cp, g, acc, stream / tasks, n, acc, stream
+    'ss_op_conv_unpack': (_i, [_fp, _i, _i, _i, _fp, _i, _vp]),
+    'ss_op_conv_unpack_many': (_i, [C.POINTER(SSConvUnpackTask), _i, _i, _vp]),
+    'ss_op_prep': (_i, [C.POINTER(SSPrepTask), _i, _i, _vp]),
+    'ss_op_transpose': (_i, [_fp, _i, _i, _fp, _vp]),
+    # src, s_ld, s_bs, dst, d_ld, d_bs, len, B, T, C, stream
+    'ss_op_copy_rows': (_i, [_fp, _l, _l, _fp, _l, _l, _ip, _i, _i, _i, _vp]),
+    # gamma[], beta[], C[], n, T, out, stream / p, n, limit, sticky, stream
+    'ss_op_act_scales': (_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_i), _i, _i, _fp, _vp]),
+    'ss_op_param_guard': (_i, [_fp, _l, _f, _vp, _vp]),
     'ss_op_split_image': (_i, [_fp, _l, _l, _i, _f, _fp, _l, _vp]),
     'ss_op_gemm_pre': (_i, [_fp, _l, _fp, _fp, _l, _fp, _fp, _l, _fp, _i, _i, _i, _i, _i, _vp]),
     'ss_op_gemm_img': (_i, [_fp, _l, _fp, _l, _fp, _l, _fp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _l, _fp, _vp, _vp]),

@@ -639,4 +639,284 @@ int ss_op_spk_grad(const float* dg, long ld, long b_stride, int rows, const floa
     return 0;
 }
 
+// lstm_small_wgrad as the engine launches it: a table of tasks, each with its own H, In, R and strides, the caller's row_groups, scratch and
+// counters.  The table's tiles are laid out task after task (tile0), as the engine's table is.
+static const char* wgrad_table_bad(const ss_wgrad_task* t, int n, int row_groups, long* tiles_out) {
+    if (!t) return "null pointer";
+    if (n < 1 || n > WGRAD_MAX) return "number of tasks out of range (1 .. 8)";
+    if (row_groups < 1 || row_groups > 1024) return "row_groups outside 1 .. 1024";
+    long tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const ss_wgrad_task& k = t[i];
+        if (!k.dg || !k.x || !k.hout || !k.gwih || !k.gwhh || !k.gb) return "a task's pointer is null";
+        if (k.H < 1 || k.H > 32 || k.In < 1 || k.R < 1) return "a task needs H in 1 .. 32, In >= 1 and R >= 1";
+        if (k.x_ld < k.In) return "a task's x_ld is below In";
+        if (k.h_ld < 2L * k.H || k.h_ld > (1L << 30)) return "a task's h_ld is below 2 H";
+        if (misaligned(k.dg, 16)) return "a task's dg is not 16-byte aligned";
+        if (misaligned(k.x, 4) || misaligned(k.hout, 4) || misaligned(k.gwih, 4) || misaligned(k.gwhh, 4) || misaligned(k.gb, 4))
+            return "a task's operand is not 4-byte aligned";
+        tiles += lstm_small_wgrad_tiles(k.H, k.In);
+    }
+    if (tiles > 65535) return "more than 65535 tiles";
+    *tiles_out = tiles;
+    return nullptr;
+}
+
+long ss_op_lstm_wgrad_table_floats(const ss_wgrad_task* t, int n, int row_groups) {
+    long tiles = 0;
+    return wgrad_table_bad(t, n, row_groups, &tiles) ? 0 : tiles * row_groups * 4096;
+}
+
+int ss_op_lstm_wgrad_table_counters(const ss_wgrad_task* t, int n) {
+    long tiles = 0;
+    return wgrad_table_bad(t, n, 1, &tiles) ? 0 : (int)tiles;
+}
+
+int ss_op_lstm_wgrad_table(const ss_wgrad_task* t, int n, int row_groups, float* part, long part_floats, unsigned* ctr, int ctr_words, void* stream) {
+    long tiles = 0;
+    if (const char* m = wgrad_table_bad(t, n, row_groups, &tiles)) return fail(std::string("ss_op_lstm_wgrad_table: ") + m);
+    if (!part || part_floats < tiles * row_groups * 4096) return fail("ss_op_lstm_wgrad_table: part_dev too small (ss_op_lstm_wgrad_table_floats)");
+    if (!ctr || ctr_words < tiles) return fail("ss_op_lstm_wgrad_table: fewer counters than tiles (ss_op_lstm_wgrad_table_counters)");
+    if (misaligned(part, 16) || misaligned(ctr, 4)) return fail("ss_op_lstm_wgrad_table: part_dev is not 16-byte aligned or ctr_dev not 4-byte aligned");
+    WgradTable w{};
+    w.n = n;
+    w.row_groups = row_groups;
+    w.part = part;
+    w.ctr = ctr;
+    int tile0 = 0;
+    for (int i = 0; i < n; ++i) {
+        const ss_wgrad_task& k = t[i];
+        const long H = k.H;
+        w.t[i] = WgradTask{k.dg, k.x, k.x_ld, k.hout, k.gwih, k.gwih + 4 * H * k.In, k.gwhh, k.gwhh + 4 * H * H, k.gb, k.gb + 4 * H, k.gb + 8 * H, k.gb + 12 * H,
+                           k.H, k.In, k.R, tile0, (int)k.h_ld};
+        tile0 += lstm_small_wgrad_tiles(k.H, k.In);
+    }
+    w.tiles_total = tile0;
+    HIPCHK(lstm_small_wgrad(w, S(stream)));
+    return 0;
+}
+
+// The random-resampling kernels (interp.hip) on the CALLER's memory, plan and value path apart: the hooks hand their arguments to
+// interp_plan / interp_gather / interp_quant / interp_scatter and nothing else.  What the launchers refuse (P above 512, ncand above 64),
+// silently drop (interp_gather's image when its alignment rule fails) or leave to the caller is refused here before anything is enqueued.
+int ss_op_interp_plan(const float* scales, const int* len_seg, const int* len_seq, int len_seq_const, int n_seg, int ncand, int P, int T, int B,
+                      int* i0, float* lam, int* nrows, int* counts, int* start, void* stream) {
+    if (!scales || !len_seg || !i0 || !lam || !nrows || !counts || !start) return fail("ss_op_interp_plan: null pointer");
+    if (B < 1 || n_seg < 1 || T < 1) return fail("ss_op_interp_plan: needs B >= 1, S >= 1 and T >= 1");
+    if (ncand < 1 || ncand > 64) return fail("ss_op_interp_plan: ncand outside 1 .. 64");
+    if (P < 1 || P > 512) return fail("ss_op_interp_plan: P outside 1 .. 512");
+    if (!len_seq && (len_seq_const < 0 || len_seq_const > T)) return fail("ss_op_interp_plan: len_seq_const outside 0 .. T");
+    if (misaligned(scales, 4) || misaligned(len_seg, 4) || misaligned(len_seq, 4) || misaligned(i0, 4) || misaligned(lam, 4) || misaligned(nrows, 4) ||
+        misaligned(counts, 4) || misaligned(start, 4))
+        return fail("ss_op_interp_plan: a word array is not 4-byte aligned");
+    InterpPlan p{n_seg, ncand, P, T, i0, lam, nrows, counts, start};
+    HIPCHK(interp_plan(p, scales, len_seg, len_seq, len_seq_const, B, S(stream)));
+    return 0;
+}
+
+static const char* plan_rows_bad(const void* a, const void* b, const void* c, int P, int B) {
+    if (!a || !b || !c) return "null pointer";
+    if (B < 1 || B > 65535) return "B outside 1 .. 65535";
+    if (P < 1 || P > 65535) return "P outside 1 .. 65535";
+    if (misaligned(a, 4) || misaligned(b, 4) || misaligned(c, 4)) return "a word array is not 4-byte aligned";
+    return nullptr;
+}
+
+int ss_op_interp_gather(const int* i0, const float* lam, const int* nrows, int P, const float* x, long x_ld, long x_bs, float* y, long y_ld, long y_bs,
+                        int C, int B, float* y_img, const float* img_scale, void* stream) {
+    if (const char* m = plan_rows_bad(i0, lam, nrows, P, B)) return fail(std::string("ss_op_interp_gather: ") + m);
+    if (!x || !y) return fail("ss_op_interp_gather: null pointer");
+    if (C < 1 || x_ld < C || y_ld < C) return fail("ss_op_interp_gather: needs C >= 1 and row strides of at least C");
+    if (misaligned(x, 4) || misaligned(y, 4) || misaligned(img_scale, 4)) return fail("ss_op_interp_gather: an operand is not 4-byte aligned");
+    if (img_scale && !y_img) return fail("ss_op_interp_gather: img_scale_dev without y_img_dev");
+    if (y_img && (C % 8 || x_ld % 4 || y_ld % 8 || x_bs % 4 || y_bs % 8 || misaligned(x, 16) || misaligned(y, 16) || misaligned(y_img, 32)))
+        return fail("ss_op_interp_gather: y_img_dev needs C % 8 == 0, x_ld % 4 == 0, x_bs % 4 == 0, y_ld % 8 == 0, y_bs % 8 == 0, x_dev and y_dev 16-byte "
+                    "aligned and y_img_dev 32-byte aligned (the launcher would drop the image)");
+    InterpPlan p{};
+    p.P = P;
+    p.i0 = const_cast<int*>(i0);
+    p.lam = const_cast<float*>(lam);
+    p.nrows = const_cast<int*>(nrows);
+    HIPCHK(interp_gather(p, CRows{x, x_ld, x_bs}, Rows{y, y_ld, y_bs}, C, B, S(stream), y_img, img_scale));
+    return 0;
+}
+
+int ss_op_interp_quant(const int* i0, const float* lam, const int* nrows, int P, int T, const float* mel, const float* f0, int CM, float* ymel,
+                       long ym_ld, long ym_bs, float* yoh, long yo_ld, long yo_bs, int NOH, int* qidx, int B, void* stream) {
+    if (const char* m = plan_rows_bad(i0, lam, nrows, P, B)) return fail(std::string("ss_op_interp_quant: ") + m);
+    if (!mel || !f0 || !ymel || !yoh || !qidx) return fail("ss_op_interp_quant: null pointer");
+    if (T < 2 || CM < 1 || NOH < 2) return fail("ss_op_interp_quant: needs T >= 2, CM >= 1 and NOH >= 2");
+    if (ym_ld < CM || yo_ld < NOH) return fail("ss_op_interp_quant: row stride below CM (ymel) or below NOH (yoh)");
+    if (misaligned(mel, 4) || misaligned(f0, 4) || misaligned(ymel, 4) || misaligned(yoh, 4) || misaligned(qidx, 4))
+        return fail("ss_op_interp_quant: an operand is not 4-byte aligned");
+    InterpPlan p{};
+    p.P = P;
+    p.T = T;
+    p.i0 = const_cast<int*>(i0);
+    p.lam = const_cast<float*>(lam);
+    p.nrows = const_cast<int*>(nrows);
+    HIPCHK(interp_quant(p, mel, f0, CM, Rows{ymel, ym_ld, ym_bs}, Rows{yoh, yo_ld, yo_bs}, NOH, qidx, B, S(stream)));
+    return 0;
+}
+
+int ss_op_interp_scatter(const float* lam, const int* start, int P, int T, const float* dy, long dy_ld, long dy_bs, float* dx, long dx_ld, long dx_bs,
+                         int C, int B, void* stream) {
+    if (const char* m = plan_rows_bad(lam, start, dy, P, B)) return fail(std::string("ss_op_interp_scatter: ") + m);
+    if (!dx) return fail("ss_op_interp_scatter: null pointer");
+    if (T < 1 || C < 1 || dy_ld < C || dx_ld < C) return fail("ss_op_interp_scatter: needs T >= 1, C >= 1 and row strides of at least C");
+    if (misaligned(dx, 4)) return fail("ss_op_interp_scatter: an operand is not 4-byte aligned");
+    InterpPlan p{};
+    p.P = P;
+    p.T = T;
+    p.lam = const_cast<float*>(lam);
+    p.start = const_cast<int*>(start);
+    HIPCHK(interp_scatter(p, CRows{dy, dy_ld, dy_bs}, Rows{dx, dx_ld, dx_bs}, C, B, S(stream)));
+    return 0;
+}
+
+// The re-layout and guard kernels (elementwise.hip, input_grads.hip) on the CALLER's memory: weight packs and their images, gradient unpacks,
+// the parameter prep table, transpose, row copies, the activation scales and the parameter guard.  Each hook calls its launcher and nothing
+// else; what the launcher would refuse, silently drop (an image whose alignment rule fails) or leave to its caller is refused here first.
+// an image of `n` elements beside its fp32 tensor: format v2 is written in whole groups of 8 from a 32-byte aligned base, bf16 8 bytes at a time
+static const char* img_bad(const float* img, long n, int img_bf16) {
+    if (!img) return nullptr;
+    if (img_bf16) return misaligned(img, 8) ? "a bf16 image is not 8-byte aligned" : nullptr;
+    if (n % 8) return "a format-v2 image needs an element count that is a multiple of 8";
+    return misaligned(img, 32) ? "a format-v2 image is not 32-byte aligned" : nullptr;
+}
+static const char* conv_pack_bad(const float* w, int Co, int Ci, int Cp, const float* wf, const float* wb, const float* wf_img, const float* wb_img,
+                                 int img_bf16) {
+    if (!w || !wf) return "null pointer (w and wf are required)";
+    if (Co < 1 || Ci < 1 || Cp < 1) return "needs Co >= 1, Ci >= 1 and Cp >= 1";
+    if (Co % 4 || Cp % 4) return "needs Co % 4 == 0 and Cp % 4 == 0";
+    if (Cp < Ci) return "Cp below Ci";
+    if (wb_img && !wb) return "wb_img without wb";
+    if (misaligned(w, 4) || misaligned(wf, 16) || misaligned(wb, 16)) return "w is not 4-byte aligned, or wf / wb not 16-byte aligned";
+    if (const char* m = img_bad(wf_img, (long)Co * 5 * Cp, img_bf16)) return m;
+    return img_bad(wb_img, (long)Ci * 5 * Co, img_bf16);
+}
+
+int ss_op_conv_pack(const float* w, int Co, int Ci, int Cp, float* wf, float* wb, float* wf_img, float* wb_img, int img_bf16, void* stream) {
+    if (const char* m = conv_pack_bad(w, Co, Ci, Cp, wf, wb, wf_img, wb_img, img_bf16)) return fail(std::string("ss_op_conv_pack: ") + m);
+    HIPCHK(conv_pack(w, Co, Ci, Cp, wf, wb, wf_img, wb_img, S(stream), img_bf16 != 0));
+    return 0;
+}
+
+int ss_op_conv_pack_many(const ss_conv_pack_task* t, int n, int img_bf16, void* stream) {
+    if (!t) return fail("ss_op_conv_pack_many: null pointer");
+    if (n < 1 || n > 8) return fail("ss_op_conv_pack_many: number of tasks out of range (1 .. 8)");
+    ConvPackTable tb{};
+    tb.n = n;
+    tb.img_bf16 = img_bf16 != 0;
+    for (int i = 0; i < n; ++i) {
+        if (const char* m = conv_pack_bad(t[i].w, t[i].Co, t[i].Ci, t[i].Cp, t[i].wf, t[i].wb, t[i].wf_img, t[i].wb_img, img_bf16))
+            return fail(std::string("ss_op_conv_pack_many: ") + m);
+        tb.t[i] = ConvPackTask{t[i].w, t[i].wf, t[i].wb, t[i].wf_img, t[i].wb_img, t[i].Co, t[i].Ci, t[i].Cp};
+    }
+    HIPCHK(conv_pack_many(tb, S(stream)));
+    return 0;
+}
+
+int ss_op_conv_pack_dx(const float* w, int Co, int Ci, float* wb, void* stream) {
+    if (!w || !wb) return fail("ss_op_conv_pack_dx: null pointer");
+    if (Co < 1 || Ci < 1) return fail("ss_op_conv_pack_dx: needs Co >= 1 and Ci >= 1");
+    if (misaligned(w, 4) || misaligned(wb, 4)) return fail("ss_op_conv_pack_dx: an operand is not 4-byte aligned");
+    HIPCHK(conv_pack_dx(w, Co, Ci, wb, S(stream)));
+    return 0;
+}
+
+static const char* conv_unpack_bad(const float* gp, int Co, int Ci, int Cp, const float* g) {
+    if (!gp || !g) return "null pointer";
+    if (Co < 1 || Ci < 1 || Cp < 1) return "needs Co >= 1, Ci >= 1 and Cp >= 1";
+    if (Cp < Ci) return "Cp below Ci";
+    if (misaligned(gp, 4) || misaligned(g, 4)) return "an operand is not 4-byte aligned";
+    return nullptr;
+}
+
+int ss_op_conv_unpack(const float* gp, int Co, int Ci, int Cp, float* g, int acc, void* stream) {
+    if (const char* m = conv_unpack_bad(gp, Co, Ci, Cp, g)) return fail(std::string("ss_op_conv_unpack: ") + m);
+    HIPCHK(conv_unpack_grad(gp, Co, Ci, Cp, g, S(stream), acc != 0));
+    return 0;
+}
+
+int ss_op_conv_unpack_many(const ss_conv_unpack_task* t, int n, int acc, void* stream) {
+    if (!t) return fail("ss_op_conv_unpack_many: null pointer");
+    if (n < 1 || n > CONV_UNPACK_MAX) return fail("ss_op_conv_unpack_many: number of tasks out of range (1 .. 8)");
+    ConvUnpackTable tb{};
+    tb.n = n;
+    for (int i = 0; i < n; ++i) {
+        if (const char* m = conv_unpack_bad(t[i].gp, t[i].Co, t[i].Ci, t[i].Cp, t[i].g)) return fail(std::string("ss_op_conv_unpack_many: ") + m);
+        tb.t[i] = ConvUnpackTask{t[i].gp, t[i].g, t[i].Co, t[i].Ci, t[i].Cp};
+    }
+    HIPCHK(conv_unpack_grads(tb, S(stream), acc != 0));
+    return 0;
+}
+
+int ss_op_prep(const ss_prep_task* t, int n, int img_bf16, void* stream) {
+    if (!t) return fail("ss_op_prep: null pointer");
+    if (n < 1 || n > PREP_MAX) return fail("ss_op_prep: number of tasks out of range (1 .. 48)");
+    PrepTable tb{};
+    tb.n = n;
+    tb.img_bf16 = img_bf16 != 0;
+    for (int i = 0; i < n; ++i) {
+        const ss_prep_task& k = t[i];
+        if (!k.a || !k.dst) return fail("ss_op_prep: a task's a or dst is null");
+        if (k.n < 1) return fail("ss_op_prep: a task needs n >= 1");
+        if (misaligned(k.a, 4) || misaligned(k.b, 4) || misaligned(k.dst, 4)) return fail("ss_op_prep: an operand is not 4-byte aligned");
+        if (k.img) {     // the kernel writes the image on its float4 path only
+            if (k.n % 4 || misaligned(k.a, 16) || misaligned(k.b, 16) || misaligned(k.dst, 16))
+                return fail("ss_op_prep: a task with an image needs n % 4 == 0 and a, b, dst 16-byte aligned");
+            if (const char* m = img_bad(k.img, k.n, img_bf16)) return fail(std::string("ss_op_prep: ") + m);
+        }
+        tb.t[i] = PrepTask{k.a, k.b, k.dst, k.n, k.img};
+    }
+    HIPCHK(prep_run(tb, S(stream)));
+    return 0;
+}
+
+int ss_op_transpose(const float* in, int R, int C, float* out, void* stream) {
+    if (!in || !out) return fail("ss_op_transpose: null pointer");
+    if (R < 1 || C < 1) return fail("ss_op_transpose: needs R >= 1 and C >= 1");
+    if (R > 65535 * 32) return fail("ss_op_transpose: R above 65535 * 32 (the row tiles are the grid's y dimension)");
+    if (misaligned(in, 4) || misaligned(out, 4)) return fail("ss_op_transpose: an operand is not 4-byte aligned");
+    HIPCHK(transpose2d(in, R, C, out, S(stream)));
+    return 0;
+}
+
+int ss_op_copy_rows(const float* src, long s_ld, long s_bs, float* dst, long d_ld, long d_bs, const int* len, int B, int T, int C, void* stream) {
+    if (!src || !dst) return fail("ss_op_copy_rows: null pointer");
+    if (B < 1 || B > 65535 || T < 1 || C < 1) return fail("ss_op_copy_rows: needs 1 <= B <= 65535, T >= 1 and C >= 1");
+    if (s_ld < C || d_ld < C) return fail("ss_op_copy_rows: row stride below C");
+    if (misaligned(src, 4) || misaligned(dst, 4) || misaligned(len, 4)) return fail("ss_op_copy_rows: an operand is not 4-byte aligned");
+    HIPCHK(copy_rows(CRows{src, s_ld, s_bs}, Rows{dst, d_ld, d_bs}, B, T, C, S(stream), len));
+    return 0;
+}
+
+int ss_op_act_scales(const float* const* gamma, const float* const* beta, const int* C, int n, int T, float* out, void* stream) {
+    if (!gamma || !beta || !C || !out) return fail("ss_op_act_scales: null pointer");
+    if (n < 1 || n > ACT_SCALE_MAX) return fail("ss_op_act_scales: number of blocks out of range (1 .. 8)");
+    if (T < 1) return fail("ss_op_act_scales: needs T >= 1");
+    if (misaligned(out, 4)) return fail("ss_op_act_scales: out_dev is not 4-byte aligned");
+    ActScaleTable tb{};
+    tb.n = n;
+    for (int i = 0; i < n; ++i) {
+        if (C[i] < 0) return fail("ss_op_act_scales: a block's C is negative");
+        if (C[i] && (!gamma[i] || !beta[i])) return fail("ss_op_act_scales: a block with C > 0 needs gamma and beta");
+        if (misaligned(gamma[i], 4) || misaligned(beta[i], 4)) return fail("ss_op_act_scales: gamma / beta is not 4-byte aligned");
+        tb.gamma[i] = gamma[i];
+        tb.beta[i] = beta[i];
+        tb.C[i] = C[i];
+    }
+    HIPCHK(act_scales(tb, T, out, S(stream)));
+    return 0;
+}
+
+int ss_op_param_guard(const float* p, long n, float limit, unsigned* sticky, void* stream) {
+    if (!p || !sticky) return fail("ss_op_param_guard: null pointer");
+    if (n < 4 || n % 4) return fail("ss_op_param_guard: n must be a positive multiple of 4");
+    if (misaligned(p, 16) || misaligned(sticky, 4)) return fail("ss_op_param_guard: p_dev is not 16-byte aligned or sticky_dev not 4-byte aligned");
+    HIPCHK(param_guard(p, n, limit, sticky, S(stream)));
+    return 0;
+}
+
 }  // extern "C"

@@ -749,7 +749,8 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepTable tb) {
             if (t.img) ss_store_img4(t.img, 4 * i, v.x, v.y, v.z, v.w, 16.0f, tb.img_bf16);
         }
     } else {
-        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < t.n; i += stride) t.dst[i] = t.a[i] + (t.b ? t.b[i] : 0.f);
+        // (a copy moves the bits, as the float4 path does: a + 0.f would turn -0.0 into +0.0)
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < t.n; i += stride) t.dst[i] = t.b ? t.a[i] + t.b[i] : t.a[i];
     }
 }
 
@@ -1439,10 +1440,13 @@ __global__ __launch_bounds__(256) void act_scale_kernel(ActScaleTable tb, float 
     if (threadIdx.x == 0) {
         mg = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
         mb = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
-        const float bound = rt * mg + mb;
+        const float bound = __builtin_fmaf(rt, mg, mb);     // (one rounding, stated in the header: what the contracted rt * mg + mb compiled to)
         float sc = 16.0f;
-        // (a non-finite bound keeps 16: the parameter guard reports that case)
-        while (sc > 1.0f / 1048576.0f && bound * sc > 32768.0f) sc *= 0.5f;
+        // A bound that is not finite keeps 16: no scale makes such a block's products finite, the parameter guard reports the parameter and
+        // the step is skipped, so the word stays what every other operand uses.  (+inf comes from an infinite parameter or from rt * mg
+        // overflowing.  A NaN ELEMENT does not enter the maxima -- fmaxf returns its other operand -- so the bound itself is never NaN.)
+        if (bound < __builtin_inff())
+            while (sc > 1.0f / 1048576.0f && bound * sc > 32768.0f) sc *= 0.5f;
         out[b] = sc;
     }
 }

@@ -244,7 +244,9 @@ hipError_t adam_range_clip(float* p, const float* g, float* m, float* v, long n,
 hipError_t status_publish(const unsigned* sticky, float* status, hipStream_t s);
 // Scale of the fp16 x 2 split for the OUTPUT of each conv block (GroupNorm + ReLU, then resampled: a convex combination), from its affine
 // parameters: |y| <= sqrt(16 T) max|gamma| + max|beta| = bound; out[i] = min(16, largest power of two with bound * scale <= 32768).
-// 16 -- the scale every other forward operand uses -- whenever bound <= 2048, i.e. for any sane GroupNorm affine.
+// 16 -- the scale every other forward operand uses -- whenever bound <= 2048, i.e. for any sane GroupNorm affine.  The floor is 2^-20.
+// A bound of +inf (an infinite parameter, or sqrt(16 T) max|gamma| overflowing) keeps 16: param_guard reports it and the step is skipped.
+// NaN elements do not enter the maxima (fmaxf); param_guard reports them too.
 constexpr int ACT_SCALE_MAX = 8;
 struct ActScaleTable {
     const float* gamma[ACT_SCALE_MAX];

@@ -9,7 +9,8 @@
 //     dW_hh[0][n][k] = sum_r dG[r + 1][n] * Hout[r][k]              h(t-1) of the forward direction is one slab row earlier
 //     dW_hh[1][n][k] = sum_r dG[r][4H + n] * Hout[r + 1][H + k]     ... of the reverse direction one row later
 //     db_ih[d][n] = db_hh[d][n] = sum_r dG[r][d*4H + n]
-// (flat sums over all R = B * (T + 4) slab rows: halo rows of dG and Hout are zero, kernels.h).  Plain fp32 FMAs on the vector ALU -- exact
+// (flat sums over all R = B * (T + 4) slab rows: halo rows of dG and Hout are zero, kernels.h -- the forward bias NEEDS row 0 of dG to be
+// zero: it is summed in the forward h tile, whose dG operand is row r + 1, so row 0 never enters it).  Plain fp32 FMAs on the vector ALU -- exact
 // products, the reference's arithmetic -- in chains of at most R / row_groups rows, the row groups' partial tiles met in float64 in a
 // FIXED order by the last workgroup of a tile to arrive (the fence-free hand-over of elementwise.hip's column sums): deterministic, and far more
 // accurate than the 32 arrival-order atomics of 6-MFMA split products it replaces.

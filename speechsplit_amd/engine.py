@@ -1029,6 +1029,175 @@ def spk_grad(dg, w_f, w_r, col0, E, out):
     return out
 
 
+def _dp(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _wgrad_tasks(tasks):
+    """[(dg [R, 8H] contiguous, x [R, In] view, hout [R, 2H] view, gwih, gwhh, gb flat)] -> the ss_wgrad_task array"""
+    arr = (_capi.SSWgradTask * len(tasks))()
+    for i, (dg, x, hout, gwih, gwhh, gb) in enumerate(tasks):
+        R, In = x.shape
+        H = hout.shape[1] // 2
+        if tuple(dg.shape) != (R, 8 * H) or not dg.is_contiguous() or hout.shape[0] != R or x.stride(1) != 1 or hout.stride(1) != 1:
+            raise ValueError(f'speechsplit_amd: wgrad task {i}: dg must be a contiguous [R, 8H], x [R, In] and hout [R, 2H] views with unit column stride')
+        if gwih.numel() != 8 * H * In or gwhh.numel() != 8 * H * H or gb.numel() != 16 * H:
+            raise ValueError(f'speechsplit_amd: wgrad task {i}: gwih / gwhh / gb must hold [2, 4H, In] / [2, 4H, H] / [2, 2, 4H] floats')
+        arr[i] = _capi.SSWgradTask(dg.data_ptr(), x.data_ptr(), x.stride(0) if R > 1 else max(In, x.stride(0)), hout.data_ptr(),
+                                   hout.stride(0) if R > 1 else max(2 * H, hout.stride(0)), gwih.data_ptr(), gwhh.data_ptr(), gb.data_ptr(), H, In, R)
+    return arr
+
+
+def lstm_wgrad_table_sizes(tasks, row_groups):
+    """(floats of scratch, counter words) an lstm_wgrad_table launch of these tasks needs"""
+    arr = _wgrad_tasks(tasks)
+    return (int(_capi.lib().ss_op_lstm_wgrad_table_floats(arr, len(tasks), row_groups)), int(_capi.lib().ss_op_lstm_wgrad_table_counters(arr, len(tasks))))
+
+
+def lstm_wgrad_table(tasks, row_groups, part, ctr):
+    """Test hook (ss_op_lstm_wgrad_table): the fused encoder-BLSTM weight gradients of up to eight tasks in one launch, ADDED to each task's
+    gwih / gwhh / gb.  part: float32 scratch, ctr: i32 counters, zero on entry (zero again afterwards)."""
+    assert part.dtype == torch.float32 and ctr.dtype == torch.int32 and part.is_contiguous() and ctr.is_contiguous()
+    _capi.check(_capi.lib().ss_op_lstm_wgrad_table(_wgrad_tasks(tasks), len(tasks), row_groups, _ptr(part), part.numel(), _ptr(ctr), ctr.numel(), _stream()))
+
+
+def _words(t, dtype, n, name):
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() != n:
+        raise ValueError(f'speechsplit_amd: {name} must be a contiguous {dtype} tensor of {n} elements')
+    return _ptr(t)
+
+
+def interp_plan(scales, len_seg, len_seq, T, P, ncand, i0, lam, nrows, counts, start):
+    """Test hook (ss_op_interp_plan): the resampling plan of B utterances from their draws.  scales f32 [B, S], len_seg i32 [B, S], len_seq
+    i32 [B] (or an int: every utterance's length) -> i0 i32 [B, P], lam f32 [B, P], nrows / counts i32 [B], start i32 [B, T + 1], all given."""
+    B, S = scales.shape
+    const = isinstance(len_seq, int)
+    i32, f32 = torch.int32, torch.float32
+    _capi.check(_capi.lib().ss_op_interp_plan(
+        _words(scales, f32, B * S, 'scales'), _words(len_seg, i32, B * S, 'len_seg'), _ptr(None) if const else _words(len_seq, i32, B, 'len_seq'),
+        len_seq if const else 0, S, ncand, P, T, B, _words(i0, i32, B * P, 'i0'), _words(lam, f32, B * P, 'lam'), _words(nrows, i32, B, 'nrows'),
+        _words(counts, i32, B, 'counts'), _words(start, i32, B * (T + 1), 'start'), _stream()))
+
+
+def interp_gather(i0, lam, nrows, x, y, y_img=None, img_scale=None):
+    """Test hook (ss_op_interp_gather): y [B, P, C] = the resampled x [B, T, C] (views, frame 0 first); y_img: a view with y's strides."""
+    B, P = i0.shape
+    Cc = x.shape[2]
+    assert tuple(y.shape) == (B, P, Cc) and x.shape[0] == B
+    (xp, x_ld, x_bs), (yp, y_ld, y_bs) = _view3(x, 'x'), _view3(y, 'y')
+    assert y_img is None or (y_img.stride() == y.stride() and tuple(y_img.shape) == tuple(y.shape))
+    i32, f32 = torch.int32, torch.float32
+    _capi.check(_capi.lib().ss_op_interp_gather(_words(i0, i32, B * P, 'i0'), _words(lam, f32, B * P, 'lam'), _words(nrows, i32, B, 'nrows'), P, xp, x_ld,
+                                                x_bs, yp, y_ld, y_bs, Cc, B, _ptr(y_img), _ptr(img_scale), _stream()))
+    return y
+
+
+def interp_quant(i0, lam, nrows, mel, f0, ymel, yoh, noh, qidx):
+    """Test hook (ss_op_interp_quant): mel [B, T, CM] and f0 [B, T] contiguous -> ymel [B, P, CM] (a view), yoh [B, P, yo_ld] (a view whose
+    row stride is its width: every column of the row is written) and qidx i32 [B, P]."""
+    B, P = i0.shape
+    T, CM = mel.shape[1], mel.shape[2]
+    assert mel.is_contiguous() and f0.is_contiguous() and tuple(f0.shape) == (B, T) and tuple(ymel.shape) == (B, P, CM)
+    assert tuple(yoh.shape[:2]) == (B, P) and yoh.stride(1) == yoh.shape[2]
+    (mp, m_ld, m_bs), (op, o_ld, o_bs) = _view3(ymel, 'ymel'), _view3(yoh, 'yoh')
+    i32, f32 = torch.int32, torch.float32
+    _capi.check(_capi.lib().ss_op_interp_quant(_words(i0, i32, B * P, 'i0'), _words(lam, f32, B * P, 'lam'), _words(nrows, i32, B, 'nrows'), P, T,
+                                               _ptr(mel), _ptr(f0), CM, mp, m_ld, m_bs, op, o_ld, o_bs, noh, _words(qidx, i32, B * P, 'qidx'), B,
+                                               _stream()))
+
+
+def interp_scatter(lam, start, dy, dx):
+    """Test hook (ss_op_interp_scatter): dx [B, T, C] = the adjoint of interp_gather applied to dy [B, P, C] (views)."""
+    B, P = lam.shape
+    T, Cc = dx.shape[1], dx.shape[2]
+    assert tuple(dy.shape) == (B, P, Cc) and dx.shape[0] == B
+    (yp, y_ld, y_bs), (xp, x_ld, x_bs) = _view3(dy, 'dy'), _view3(dx, 'dx')
+    _capi.check(_capi.lib().ss_op_interp_scatter(_words(lam, torch.float32, B * P, 'lam'), _words(start, torch.int32, B * (T + 1), 'start'), P, T, yp,
+                                                 y_ld, y_bs, xp, x_ld, x_bs, Cc, B, _stream()))
+    return dx
+
+
+def conv_pack(w, Cp, wf, wb=None, wf_img=None, wb_img=None, img_bf16=False):
+    """Test hook (ss_op_conv_pack): w [Co, Ci, 5] contiguous -> wf [Co, 5, Cp] (+ wb [Ci, 5, Co], + their images), all flat device tensors."""
+    Co, Ci, K = w.shape
+    assert K == 5 and w.is_contiguous() and w.dtype == torch.float32
+    _capi.check(_capi.lib().ss_op_conv_pack(_ptr(w), Co, Ci, Cp, _ptr(wf), _ptr(wb), _ptr(wf_img), _ptr(wb_img), 1 if img_bf16 else 0, _stream()))
+
+
+def conv_pack_many(tasks, img_bf16=False):
+    """Test hook (ss_op_conv_pack_many): tasks = [(w, Cp, wf, wb, wf_img, wb_img)] as conv_pack's arguments, one launch."""
+    arr = (_capi.SSConvPackTask * len(tasks))()
+    for i, (w, Cp, wf, wb, wf_img, wb_img) in enumerate(tasks):
+        Co, Ci, K = w.shape
+        assert K == 5 and w.is_contiguous() and w.dtype == torch.float32
+        arr[i] = _capi.SSConvPackTask(_dp(w), _dp(wf), _dp(wb), _dp(wf_img), _dp(wb_img), Co, Ci, Cp)
+    _capi.check(_capi.lib().ss_op_conv_pack_many(arr, len(tasks), 1 if img_bf16 else 0, _stream()))
+
+
+def conv_pack_dx(w, wb):
+    """Test hook (ss_op_conv_pack_dx): w [Co, Ci, 5] contiguous -> wb [Ci, 5, Co], any Ci and Co."""
+    Co, Ci, K = w.shape
+    assert K == 5 and w.is_contiguous() and w.dtype == torch.float32
+    _capi.check(_capi.lib().ss_op_conv_pack_dx(_ptr(w), Co, Ci, _ptr(wb), _stream()))
+
+
+def conv_unpack(gp, Co, Ci, Cp, g, acc=False):
+    """Test hook (ss_op_conv_unpack): packed gradient gp [Co, 5, Cp] -> g [Co, Ci, 5] (acc: added to g), flat device tensors."""
+    _capi.check(_capi.lib().ss_op_conv_unpack(_ptr(gp), Co, Ci, Cp, _ptr(g), 1 if acc else 0, _stream()))
+
+
+def conv_unpack_many(tasks, acc=False):
+    """Test hook (ss_op_conv_unpack_many): tasks = [(gp, Co, Ci, Cp, g)], one launch."""
+    arr = (_capi.SSConvUnpackTask * len(tasks))()
+    for i, (gp, Co, Ci, Cp, g) in enumerate(tasks):
+        arr[i] = _capi.SSConvUnpackTask(_dp(gp), _dp(g), Co, Ci, Cp)
+    _capi.check(_capi.lib().ss_op_conv_unpack_many(arr, len(tasks), 1 if acc else 0, _stream()))
+
+
+def prep(tasks, img_bf16=False):
+    """Test hook (ss_op_prep): tasks = [(a, b or None, dst, n, img or None)] over flat device tensors: dst[:n] = a[:n] + b[:n], or a copy."""
+    arr = (_capi.SSPrepTask * len(tasks))()
+    for i, (a, b, dst, n, img) in enumerate(tasks):
+        arr[i] = _capi.SSPrepTask(_dp(a), _dp(b), _dp(dst), n, _dp(img))
+    _capi.check(_capi.lib().ss_op_prep(arr, len(tasks), 1 if img_bf16 else 0, _stream()))
+
+
+def transpose(x, out):
+    """Test hook (ss_op_transpose): out [C, R] = x [R, C]^T, both contiguous."""
+    R, Cc = x.shape
+    assert x.is_contiguous() and out.is_contiguous() and out.numel() == R * Cc and x.dtype == torch.float32
+    _capi.check(_capi.lib().ss_op_transpose(_ptr(x), R, Cc, _ptr(out), _stream()))
+    return out
+
+
+def copy_rows(src, dst, lengths=None):
+    """Test hook (ss_op_copy_rows): dst[b, t, :] = src[b, t, :] over [B, T, C] views (frame 0 first; a slab is passed as slab[:, 2:2 + T]);
+    lengths (i32 [B] on the device): zeros at and beyond each row's length, whose source rows are not read."""
+    B, T, Cc = src.shape
+    assert tuple(dst.shape) == (B, T, Cc) and (lengths is None or (lengths.dtype == torch.int32 and lengths.numel() == B))
+    (sp, s_ld, s_bs), (dp, d_ld, d_bs) = _view3(src, 'src'), _view3(dst, 'dst')
+    _capi.check(_capi.lib().ss_op_copy_rows(sp, s_ld, s_bs, dp, d_ld, d_bs, _ptr(lengths), B, T, Cc, _stream()))
+    return dst
+
+
+def act_scales(affines, T, out):
+    """Test hook (ss_op_act_scales): affines = [(gamma, beta)] (1-D views of equal length, or (None, None) for an absent block) -> out[i]."""
+    n = len(affines)
+    g = (C.c_void_p * n)(*[_dp(a) for a, _ in affines])
+    b = (C.c_void_p * n)(*[_dp(a) for _, a in affines])
+    cs = (C.c_int * n)(*[0 if a is None else a.numel() for a, _ in affines])
+    assert all(a is None or (a.stride(0) == 1 and bb.stride(0) == 1 and a.numel() == bb.numel()) for a, bb in affines) and out.numel() >= n
+    _capi.check(_capi.lib().ss_op_act_scales(g, b, cs, n, T, _ptr(out), _stream()))
+    return out
+
+
+def param_guard(p, limit, sticky):
+    """Test hook (ss_op_param_guard): sticky (one i32 word) |= 4 if an element of the flat p is not finite or has |p| >= limit."""
+    assert p.dtype == torch.float32 and p.dim() == 1 and p.stride(0) == 1 and sticky.dtype == torch.int32
+    _capi.check(_capi.lib().ss_op_param_guard(_ptr(p), p.numel(), float(limit), _ptr(sticky), _stream()))
+    return sticky
+
+
 def small_lstm_ld(H):
     """Row stride of the output / cell-state / output-gradient slabs of a BLSTM layer (kernels.h lstm_small_ld): 2H, rounded up to a
     multiple of 4 floats when H <= 32 is not a power of two."""
