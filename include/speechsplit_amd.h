@@ -202,6 +202,49 @@ int ss_g6_encode(ss_engine* e, const float* x_org_dev, const float* f0_trg_dev, 
 int ss_g6_decode(ss_engine* e, const float* codes_r_dev, const float* codes_f0_dev, const int* len_dev, int B, int T, float* out_dev,
                  void* stream);
 
+/* ---- differentiable decode: train the decoder, the head and speaker rows on GIVEN codes, and gradients with respect to the codes ----
+ * ss_*_decode above is forward only.  These calls run the same computation on a dense batch, keep its state, and differentiate it down to
+ * the codes and the speaker rows -- with the encoders out of the picture: adapting to a new speaker from cached codes, code-space
+ * optimisation, saliency per code.  Asynchronous on `stream` like their neighbours.
+ *   - ss_g3_decode_train / ss_g6_decode_train: ss_*_decode's computation (same launches, same bits in out) under the rules of everything
+ *     that differentiates: 1 <= B <= max_batch, T <= max_frames, T a multiple of every code factor, plan within the bound workspace.  No
+ *     len_dev: ragged forwards have no backward.  Both precision modes.  out is required;
+ *   - ss_g3_decode_backward / ss_g6_decode_backward: d_out [B, T, head width] is the gradient of the caller's loss with respect to out.
+ *     Writes the gradient arena's decoder + head range [ss_grad_split(e), arena) and the status slot.  flags: 0 or SS_STEP_ACCUMULATE.
+ *     Without SS_STEP_ACCUMULATE the WHOLE arena is cleared first, as every backward does, so the encoder range holds exact zeros; with
+ *     it the gradients are added to what the arena holds and ss_grad_accum_count counts the call.  Any of d_codes_* and dc_trg may be NULL
+ *     (not computed); all NULL gives parameter gradients only.  A code gradient is dense fp32 with the shape of its code: element
+ *     [b][blk][c] is the sum of the decoder-input gradient over the block's `factor` frames, frames ascending, in one launch for all
+ *     requested codes, without atomics (the same bits on every run).  dc_trg is [B, dim_spk_emb], per row and NOT summed over the batch,
+ *     as ss_g3_backward_inputs returns it.  When the call returns (in stream order) the side stream's weight gradients are joined;
+ *   - neither call launches a conv block, a GroupNorm, an encoder recurrence, an encoder BLSTM GEMM or an InterpLnr kernel (ss_profile
+ *     counts none in SS_PROF_CONV_*, SS_PROF_GN, SS_PROF_ENC_REC, SS_PROF_ENC_LSTM, SS_PROF_WGRAD);
+ *   - ss_adam_step_decoder: ss_adam_step restricted to [ss_grad_split(e), arena).  The encoder range of the parameters and of both
+ *     moments keeps its bits; the step counter advances by one (a following ss_adam_step uses step + 1).  Clipping (ss_set_grad_clip),
+ *     the non-finite skip and the status word act as for ss_adam_step; the norm is taken over the WHOLE arena as it stands (exact zeros in
+ *     the encoder range after a non-accumulating decode backward);
+ *   - ss_g3_decode_train_step: decode, MSE against target_mel [B, T, dim_freq] (mean, as ss_g3_train_step; loss: one device float), the
+ *     backward, and ss_adam_step_decoder's update, in one call.  flags: SS_STEP_NO_ADAM (stop behind the backward) and / or
+ *     SS_STEP_ACCUMULATE; every other flag is refused.  dc_trg (nullable) as above: what an optimiser over speaker rows needs;
+ *   - state: after ss_*_decode_train only ss_*_decode_backward is valid -- ss_*_backward*, ss_train_finish are refused with a message that
+ *     says the last forward was a decode.  ss_*_decode_backward is refused after a full forward, after a plain ss_*_decode / ss_*_encode
+ *     and with no forward at all.  The engine stays usable after each refusal;
+ *   - refused with nothing enqueued, in a message that names the call: the wrong kind of engine, an engine that is not bound, a NULL
+ *     required pointer, B or T outside the rules above (T > max_frames included), flags outside the accepted set, a member of a
+ *     data-parallel group (the data-parallel steps have no decode form). */
+int ss_g3_decode_train(ss_engine* e, const float* codes_x_dev, const float* codes_r_dev, const float* codes_f0_dev,
+                       const float* c_trg_dev /* [B, dim_spk_emb] */, int B, int T, float* out_dev /* [B, T, dim_freq] */, void* stream);
+int ss_g3_decode_backward(ss_engine* e, const float* d_out_dev, float* d_codes_x_dev /* nullable */, float* d_codes_r_dev /* nullable */,
+                          float* d_codes_f0_dev /* nullable */, float* dc_trg_dev /* [B, dim_spk_emb], nullable */, int flags, void* stream);
+int ss_g6_decode_train(ss_engine* e, const float* codes_r_dev, const float* codes_f0_dev, int B, int T, float* out_dev /* [B, T, dim_f0] */,
+                       void* stream);
+int ss_g6_decode_backward(ss_engine* e, const float* d_out_dev, float* d_codes_r_dev /* nullable */, float* d_codes_f0_dev /* nullable */,
+                          int flags, void* stream);
+int ss_adam_step_decoder(ss_engine* e, float grad_scale, void* stream);
+int ss_g3_decode_train_step(ss_engine* e, const float* codes_x_dev, const float* codes_r_dev, const float* codes_f0_dev, const float* c_trg_dev,
+                            const float* target_mel_dev, int B, int T, float grad_scale, int flags, float* loss_dev,
+                            float* dc_trg_dev /* nullable */, void* stream);
+
 /* ---- Solver.train step body (solver.py:157-172), fused: cat(mel,f0) -> InterpLnr -> quantize_f0 -> G -> mse(mean)
  *      -> backward -> Adam.  mel [B,T,80], f0 [B,T,1] (-1e10 = unvoiced), emb [B,82], len_org i32[B];
  *      scales/len_seg [4][B*7] (outer call first).  T must equal hp.max_len_pad (model.py:105,157).
@@ -890,6 +933,11 @@ int ss_op_gn_relu_bwd(const float* x_dev, long x_ld, long x_bs, float* dy_dev, l
  *                    the sum over the block's freq frames (fp32, frames ascending) of d_in's columns at the one frame of the block where
  *                    the half was sampled, and zero at every other frame.  f == 0: d_in is the slab [B][T+4][ld]; f > 0: d_in is
  *                    [B][T/f][ld] and already holds the sums.
+ *   ss_op_dec_in_codes_grad  the adjoint with respect to DENSE codes (what ss_*_decode_backward runs; up to three sources in one launch):
+ *                    d_o of source i is here the dense code gradient [B][T/freq_i][2 H_i] (ld_i is only checked to be >= 2 H_i, o is not
+ *                    read) and gets, per element, the sum over the block's freq_i frames (fp32, frames ascending, no atomics) of d_in's
+ *                    column col_i + c.  f == 0: d_in is the slab [B][T+4][ld]; f > 0: d_in is [B][T/f][ld] and already holds the sums.
+ *                    Nothing outside the dense code gradients is written; of d_in only rows [2, 2 + T) and the sources' columns are read.
  *   ss_op_dec_in_codes  ss_op_dec_in by way of dense codes (up to three sources): export the codes into codes_dev (at least the sum over
  *                    the sources of B (T / freq_i) 2 H_i floats, each rounded up to 4; 16-byte aligned), then build dst from them.
  *                    Refused by all three: a null pointer, nsrc outside 1 .. 4 (codes: 3), B / T below 1, T % freq_i != 0, columns
@@ -913,6 +961,7 @@ int ss_op_colsum(const float* in_dev, long ld, int R, int C, int two_dir, float*
 int ss_op_dec_in(const ss_code_src* src, int nsrc, const float* emb_dev, int emb_dim, int emb_col, float* dst_dev, int ld, int B, int T, int f,
                  void* stream);
 int ss_op_dec_in_grad(const ss_code_src* src, int nsrc, const float* d_in_dev, int ld, int B, int T, int f, void* stream);
+int ss_op_dec_in_codes_grad(const ss_code_src* src, int nsrc, const float* d_in_dev, int ld, int B, int T, int f, void* stream);
 int ss_op_dec_in_codes(const ss_code_src* src, int nsrc, const float* emb_dev, int emb_dim, int emb_col, float* codes_dev, long codes_floats,
                        float* dst_dev, int ld, int B, int T, int f, void* stream);
 int ss_op_spk_grad(const float* dg_dev, long ld, long b_stride, int rows, const float* w_f_dev, const float* w_r_dev, long w_ld, int col0, int H4,

@@ -94,6 +94,15 @@ SYMBOLS = {
     # e, x_org, f0_trg, len, B, T, codes_r, codes_f0, stream / e, codes_r, codes_f0, len, B, T, out, stream
     'ss_g6_encode': (_i, [_vp, _fp, _fp, _ip, _i, _i, _fp, _fp, _vp]),
     'ss_g6_decode': (_i, [_vp, _fp, _fp, _ip, _i, _i, _fp, _vp]),
+    # e, codes_x, codes_r, codes_f0, c_trg, B, T, out, stream / e, d_out, d_codes_x, d_codes_r, d_codes_f0, dc_trg, flags, stream
+    'ss_g3_decode_train': (_i, [_vp, _fp, _fp, _fp, _fp, _i, _i, _fp, _vp]),
+    'ss_g3_decode_backward': (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _vp]),
+    # e, codes_r, codes_f0, B, T, out, stream / e, d_out, d_codes_r, d_codes_f0, flags, stream
+    'ss_g6_decode_train': (_i, [_vp, _fp, _fp, _i, _i, _fp, _vp]),
+    'ss_g6_decode_backward': (_i, [_vp, _fp, _fp, _fp, _i, _vp]),
+    'ss_adam_step_decoder': (_i, [_vp, _f, _vp]),
+    # e, codes_x, codes_r, codes_f0, c_trg, target_mel, B, T, grad_scale, flags, loss, dc_trg, stream
+    'ss_g3_decode_train_step': (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _f, _i, _fp, _fp, _vp]),
     'ss_g6_backward': (_i, [_vp, _fp, _vp]),
     'ss_g6_backward_inputs': (_i, [_vp, _fp, _fp, _fp, _vp]),
     'ss_g3_train_step': (_i, [_vp, _fp, _fp, _fp, _ip, _fp, _ip, _i, _i, _f, _i, _fp, _vp]),
@@ -148,6 +157,7 @@ SYMBOLS = {
     # src, nsrc, emb, emb_dim, emb_col, dst, ld, B, T, f, stream / src, nsrc, d_in, ld, B, T, f, stream
     'ss_op_dec_in': (_i, [C.POINTER(SSCodeSrc), _i, _fp, _i, _i, _fp, _i, _i, _i, _i, _vp]),
     'ss_op_dec_in_grad': (_i, [C.POINTER(SSCodeSrc), _i, _fp, _i, _i, _i, _i, _vp]),
+    'ss_op_dec_in_codes_grad': (_i, [C.POINTER(SSCodeSrc), _i, _fp, _i, _i, _i, _i, _vp]),
     # src, nsrc, emb, emb_dim, emb_col, codes, codes_floats, dst, ld, B, T, f, stream
     'ss_op_dec_in_codes': (_i, [C.POINTER(SSCodeSrc), _i, _fp, _i, _i, _fp, _l, _fp, _i, _i, _i, _i, _vp]),
     # dg, ld, b_stride, rows, w_f, w_r, w_ld, col0, H4, E, out, B, stream

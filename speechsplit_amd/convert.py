@@ -166,6 +166,66 @@ def convert_batch(G, P, pairs, max_len_pad=192, max_rows=16, device='cuda:0', co
     return res
 
 
+def adapt_speaker(G, entries, steps, lr=1e-4, train_decoder=True, emb0=None, max_rows=16, device='cuda:0'):
+    """Adapt to a new speaker from a few of their utterances with the three encoders frozen: learn one speaker row (and, with
+    train_decoder, fine-tune the decoder and the head) so that decoding each utterance's OWN codes with the row gives back its mel.
+
+    entries: demo.pkl-style ``[speaker, emb f32[1,82], (mel[L,80], f0[L], L, uid)]``.  They are encoded ONCE, in eval mode, as ragged
+    batches in plan_batches order (each at its own length rounded up to the code factors, at most max_rows per forward), and the codes and
+    mels are zero-padded to one training shape [N, T] (T: the longest; it has to fit the engine's max_frames, N its batch).  Then `steps`
+    fused decode steps run (Engine.g3_decode_train_step: decode, MSE, decoder backward, Adam over the decoder + head range from step 0
+    and zeroed moments) -- no encoder forward, no encoder backward, no resampling draws.  The speaker row is updated by
+    ``torch.optim.Adam(lr)`` from the step's per-row dc_trg summed over the batch; it starts at emb0 [1, dim_spk_emb], or at the mean of the
+    entries' own rows.  train_decoder=False: the steps stop behind the backward (SS_STEP_NO_ADAM), so only the row learns and every model
+    parameter keeps its bits.  Returns (row [1, dim_spk_emb] on the device, [loss of every step as float])."""
+    hp = G.hparams_
+    steps = int(steps)
+    if not entries or steps < 0:
+        raise ValueError('adapt_speaker: needs at least one entry and steps >= 0')
+    f = int(np.lcm.reduce([hp.freq, hp.freq_2, hp.freq_3]))
+    lens = [-(-int(e[2][2]) // f) * f for e in entries]
+    N, T = len(entries), max(lens)
+    prep = [_prepare(e, n, device) for e, n in zip(entries, lens)]
+    was_training = G.training
+    G.eval()
+    try:
+        G._ensure_engine(torch.device(device), N)
+        eng = G._eng
+        if T > eng.max_frames or N > eng.max_batch:
+            raise ValueError(f'adapt_speaker: {N} utterances of up to {T} frames exceed the engine\'s training limits '
+                             f'({eng.max_batch} x {eng.max_frames})')
+        shp = eng.code_shapes(N, T)
+        codes = {n: torch.zeros(shp[n], device=device) for n in ('x', 'r', 'f0')}
+        with torch.no_grad():
+            for batch in plan_batches(lens, max_rows):
+                bl = [lens[k] for k in batch]
+                x_org = _pad_rows([prep[k][0] for k in batch], bl[-1])
+                x_f0 = torch.cat((x_org, _pad_rows([prep[k][1] for k in batch], bl[-1])), -1)
+                for n, c in zip(('x', 'r', 'f0'), G.encode(x_f0, x_org, lengths=bl)):
+                    codes[n][batch, :c.shape[1]] = c
+        target = _pad_rows([p[0] for p in prep], T)
+        row = torch.as_tensor(emb0, dtype=torch.float32).to(device).reshape(1, -1).clone() if emb0 is not None else torch.cat([p[2] for p in prep]).mean(0, keepdim=True)
+        if row.shape[1] != hp.dim_spk_emb:
+            raise ValueError(f'adapt_speaker: emb0 must hold dim_spk_emb = {hp.dim_spk_emb} values')
+        row.requires_grad_(True)
+        opt = torch.optim.Adam([row], lr=lr)
+        if train_decoder:
+            lo = eng.grad_split
+            eng.adam_m[lo:].zero_()
+            eng.adam_v[lo:].zero_()
+            eng.set_adam(lr=lr, step=0)
+        losses = []
+        for _ in range(steps):
+            loss, dc = eng.g3_decode_train_step(codes['x'], codes['r'], codes['f0'], row.detach().expand(N, -1), target,
+                                                no_adam=not train_decoder, want_dc_trg=True)
+            losses.append(loss.clone())
+            row.grad = dc.sum(0, keepdim=True)
+            opt.step()
+    finally:
+        G.train(was_training)
+    return row.detach(), [float(v) for v in torch.cat(losses).cpu()] if losses else []
+
+
 def conversion_waveforms(results, f0s=None, **kw):
     """demo_conversion's output ``[(name, mel[len, 80])]`` -> ``[(name, wav float64[256 (len - 1)])]`` at 16 kHz through the Griffin-Lim
     vocoder; convert_batch's output (one such list per pair) -> one such list per pair.  All the mels go through ONE vocoder.griffin_lim call

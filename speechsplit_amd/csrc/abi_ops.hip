@@ -609,6 +609,14 @@ int ss_op_dec_in_grad(const ss_code_src* src, int nsrc, const float* d_in, int l
     return 0;
 }
 
+int ss_op_dec_in_codes_grad(const ss_code_src* src, int nsrc, const float* d_in, int ld, int B, int T, int f, void* stream) {
+    if (const char* m = dec_in_bad(src, nsrc, 3, true, nullptr, 0, 0, d_in, ld, B, T, f)) return fail(std::string("ss_op_dec_in_codes_grad: ") + m);
+    CodeGrad cg[3];
+    for (int i = 0; i < nsrc; ++i) cg[i] = CodeGrad{src[i].d_o, src[i].H, src[i].freq, src[i].col};      // d_o: the DENSE code gradient here
+    HIPCHK(dec_in_codes_grad(cg, nsrc, d_in, ld, B, T, f, S(stream)));
+    return 0;
+}
+
 int ss_op_dec_in_codes(const ss_code_src* src, int nsrc, const float* emb, int emb_dim, int emb_col, float* codes, long codes_floats, float* dst, int ld,
                        int B, int T, int f, void* stream) {
     if (const char* m = dec_in_bad(src, nsrc, 3, false, emb, emb_dim, emb_col, dst, ld, B, T, f)) return fail(std::string("ss_op_dec_in_codes: ") + m);

@@ -273,6 +273,7 @@ struct ss_engine {
         bool grads_zeroed = false;         // fused training step: the gradient arena was zeroed on a branch stream during the forward
         bool bwd_sync_zeroed = false;      // the same for the backward recurrences' sync words / exchange tiles and the work-queue words
         bool ragged = false;               // it ran over per-row lengths (ss_*_forward_ragged): eval-only, no backward exists for it
+        bool decode = false;               // it was ss_*_decode_train: the decoder alone on caller codes, only ss_*_decode_backward may follow
     } fwd;
     // ---- bookkeeping of the backward in flight: written by the decoder's lstm_bwd, read later in the same backward (and by
     // speaker_input_grad behind it); backward_decoder starts it from zero
@@ -1952,6 +1953,7 @@ int forward_core(ss_engine* e, bool training, const float* scales, const int* le
     e->fwd.training = training;
     e->fwd.enc_plan0 = draw0;
     e->fwd.ragged = lens != nullptr;
+    e->fwd.decode = false;
     e->fwd.have = true;
     return 0;
 }
@@ -2623,6 +2625,8 @@ long ss_grad_accum_count(const ss_engine* e) { return e ? e->accum_count : 0; }
 // every backward: a forward to differentiate, and one that ran within max_frames (nothing is enqueued otherwise)
 static int backward_check(const ss_engine* e) {
     if (!e->fwd.have) return fail("backward without a preceding forward");
+    if (e->fwd.decode)
+        return fail("backward: the last forward was a decode (ss_*_decode_train), which ran no encoder: only ss_*_decode_backward can follow it");
     if (e->curT > e->maxT)
         return fail("backward: the last forward ran T above max_frames, which is eval-only (GroupNorm backward, training and input "
                     "gradients keep T <= max_frames <= 256)");
@@ -2822,6 +2826,151 @@ int ss_g6_encode(ss_engine* e, const float* x_org, const float* f0_trg, const in
 int ss_g6_decode(ss_engine* e, const float* codes_r, const float* codes_f0, const int* len_dev, int B, int T, float* out, void* stream) {
     CHK(codes_check(e, SS_GENERATOR_6, "ss_g6_decode", codes_r && codes_f0 && out, B, T));
     return decode_codes(e, CallerCodes{{codes_r, codes_f0, nullptr}, nullptr}, len_dev, B, T, out, stream);
+}
+
+// ---- differentiable decode: the decoder on caller codes, recorded for a backward that stops at the codes (see the header's "codes" section) ----
+// what ss_*_decode_train and ss_g3_decode_train_step refuse before anything is enqueued: codes_check under the rules of everything that differentiates
+static int decode_train_check(const ss_engine* e, int kind, const char* call, bool ptrs_ok, int B, int T) {
+    const std::string c(call);
+    if (!e) return fail(c + ": null engine");
+    if (e->kind != kind) return fail(c + " on an engine that is not a " + (kind == SS_GENERATOR_3 ? "Generator_3" : "Generator_6"));
+    if (!e->ws) return fail(c + ": engine is not bound (call ss_bind first)");
+    if (!ptrs_ok) return fail(c + ": null pointer (every input and output named as required is required)");
+    if (B < 1 || B > e->maxB) return fail(c + ": batch outside 1 .. max_batch given to ss_create");
+    if (T < 1 || T > e->maxT) return fail(c + ": T outside 1 .. max_frames (a decode that is differentiated keeps T <= max_frames, as every backward does)");
+    if (T % e->hp.freq || T % e->hp.freq_2 || T % e->hp.freq_3) return fail(c + ": T must be a multiple of the code down-sampling factors (model.py:87,223-227)");
+    if (carve(*e, B, T) > e->ws_bytes) return fail(c + ": workspace too small for this batch / frames: grow it to ss_plan_bytes(B, T) with ss_set_workspace");
+    return 0;
+}
+
+// decode_codes on a dense batch, without the export, leaving the state a decoder backward needs
+static int decode_train_body(ss_engine* e, const CallerCodes& cc, int B, int T, hipStream_t s) {
+    CHK(geometry(e, B, T, s));
+    e->part_off = 0;
+    e->fwd = {};                   // the decoder's slabs are overwritten: whatever forward ran before has no backward any more
+    PrepTable tb;
+    tb.n = 0;
+    tb.img_bf16 = e->img16();
+    CHK(lstm_prep(e, e->ld, tb, s));
+    HIPCHK(prep_run(tb, s));
+    if ((g_fwd_f16x2 || g_bwd_f16x2) && e->precision == SS_PRECISION_F32 && e->sticky) HIPCHK(param_guard(e->P, e->arena, 2048.0f, e->sticky, s));
+    CHK(forward_decoder(e, s, nullptr, &cc));
+    e->fwd.decode = true;
+    e->fwd.have = true;
+    return 0;
+}
+
+// what ss_*_decode_backward refuses before anything is enqueued
+static int decode_backward_check(const ss_engine* e, int kind, const char* call, const float* d_out, int flags) {
+    const std::string c(call);
+    if (!e) return fail(c + ": null engine");
+    if (e->kind != kind) return fail(c + " on an engine that is not a " + (kind == SS_GENERATOR_3 ? "Generator_3" : "Generator_6"));
+    if (!e->ws || !e->G) return fail(c + ": engine is not bound (call ss_bind first)");
+    if (!d_out) return fail(c + ": null pointer (d_out is required)");
+    if (flags & ~SS_STEP_ACCUMULATE) return fail(c + ": flags other than SS_STEP_ACCUMULATE");
+    if (e->dp_on) return fail(c + ": not available on a member of a data-parallel group");
+    if (!e->fwd.have) return fail(c + " without a preceding ss_*_decode_train (a plain ss_*_decode leaves nothing to differentiate)");
+    if (!e->fwd.decode) return fail(c + ": the last forward was a full forward, not a decode: ss_*_backward* differentiates it");
+    return 0;
+}
+
+// The decoder's backward alone, behind d_out_slab: parameter gradients of [ss_grad_split, arena) and the status slot, then whatever of the
+// code gradients (in code_srcs order; NULL: not wanted) and the speaker-row gradient is asked for; the side stream's weight gradients joined
+static int decode_backward_body(ss_engine* e, float* const* d_codes, float* dc_trg, bool accumulate, hipStream_t s) {
+    Backward bw;
+    bw.accumulate = accumulate;
+    CHK(backward_decoder(e, bw, s));
+    CodeSrc src[3];
+    const int n = code_srcs(e, src);
+    CodeGrad cg[3];
+    int m = 0;
+    for (int i = 0; i < n; ++i)
+        if (d_codes[i]) cg[m++] = {d_codes[i], src[i].H, src[i].freq, src[i].col};
+    if (m) HIPCHK(dec_in_codes_grad(cg, m, dec_dx(e).p, e->dec_in_dim, e->curB, e->curT, dec_compact(e) ? e->ld.xf : 0, s));
+    if (dc_trg) CHK(speaker_input_grad(e, dc_trg, s));
+    return join_side(e, s);
+}
+
+// Adam on [ss_grad_split, arena) alone: the early range's update of the fused step (early_update), with the whole arena's norm when clipping
+static int adam_decoder_enqueue(ss_engine* e, float grad_scale, hipStream_t s) {
+    if (!e->ws || !e->Mm || !e->Vv) return fail("ss_adam_step_decoder: Adam arenas are not bound");
+    const long from = ss_grad_split(e);
+    if (from % 4 || from >= e->arena) return fail("ss_adam_step_decoder: internal: the decoder range does not start on a multiple of 4 floats");
+    if (e->clip_max > 0.0f) {
+        int n = 0;
+        CHK(grad_norm_partials(e, false, s, &n));
+        Prof pr(e, SS_PROF_ADAM, s);
+        HIPCHK(adam_prepare_clip(e->adam, e->clip, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s));
+        HIPCHK(adam_range_clip(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, grad_scale, &e->clip->coef, s));
+        return 0;
+    }
+    Prof pr(e, SS_PROF_ADAM, s);
+    HIPCHK(adam_prepare(e->adam, e->sticky, e->G + e->status_off, s));
+    HIPCHK(adam_range(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, grad_scale, s));
+    return 0;
+}
+
+int ss_g3_decode_train(ss_engine* e, const float* codes_x, const float* codes_r, const float* codes_f0, const float* c_trg, int B, int T, float* out,
+                       void* stream) {
+    CHK(decode_train_check(e, SS_GENERATOR_3, "ss_g3_decode_train", codes_x && codes_r && codes_f0 && c_trg && out, B, T));
+    CHK(entry_check(e));
+    Own own(e, stream);
+    CHK(decode_train_body(e, CallerCodes{{codes_x, codes_r, codes_f0}, c_trg}, B, T, own.s));
+    return export_out(e, out, B, T, own.s);
+}
+
+int ss_g3_decode_backward(ss_engine* e, const float* d_out, float* d_codes_x, float* d_codes_r, float* d_codes_f0, float* dc_trg, int flags,
+                          void* stream) {
+    CHK(decode_backward_check(e, SS_GENERATOR_3, "ss_g3_decode_backward", d_out, flags));
+    Own own(e, stream);
+    CHK(import_dout(e, d_out, e->curB, e->curT, own.s));
+    float* const d_codes[3] = {d_codes_x, d_codes_r, d_codes_f0};
+    return decode_backward_body(e, d_codes, dc_trg, (flags & SS_STEP_ACCUMULATE) != 0, own.s);
+}
+
+int ss_g6_decode_train(ss_engine* e, const float* codes_r, const float* codes_f0, int B, int T, float* out, void* stream) {
+    CHK(decode_train_check(e, SS_GENERATOR_6, "ss_g6_decode_train", codes_r && codes_f0 && out, B, T));
+    CHK(entry_check(e));
+    Own own(e, stream);
+    CHK(decode_train_body(e, CallerCodes{{codes_r, codes_f0, nullptr}, nullptr}, B, T, own.s));
+    return export_out(e, out, B, T, own.s);
+}
+
+int ss_g6_decode_backward(ss_engine* e, const float* d_out, float* d_codes_r, float* d_codes_f0, int flags, void* stream) {
+    CHK(decode_backward_check(e, SS_GENERATOR_6, "ss_g6_decode_backward", d_out, flags));
+    Own own(e, stream);
+    CHK(import_dout(e, d_out, e->curB, e->curT, own.s));
+    float* const d_codes[3] = {d_codes_r, d_codes_f0, nullptr};
+    return decode_backward_body(e, d_codes, nullptr, (flags & SS_STEP_ACCUMULATE) != 0, own.s);
+}
+
+int ss_adam_step_decoder(ss_engine* e, float grad_scale, void* stream) {
+    if (!e) return fail("ss_adam_step_decoder: null engine");
+    if (e->kind == SS_INTERP_ONLY) return fail("ss_adam_step_decoder: an InterpLnr-only engine has no parameters");
+    if (!e->ws) return fail("ss_adam_step_decoder: engine is not bound (call ss_bind first)");
+    CHK(entry_check(e));
+    Own own(e, stream);
+    return adam_decoder_enqueue(e, grad_scale, own.s);
+}
+
+int ss_g3_decode_train_step(ss_engine* e, const float* codes_x, const float* codes_r, const float* codes_f0, const float* c_trg,
+                            const float* target_mel, int B, int T, float grad_scale, int flags, float* loss, float* dc_trg, void* stream) {
+    CHK(decode_train_check(e, SS_GENERATOR_3, "ss_g3_decode_train_step", codes_x && codes_r && codes_f0 && c_trg && target_mel && loss, B, T));
+    if (flags & ~(SS_STEP_NO_ADAM | SS_STEP_ACCUMULATE)) return fail("ss_g3_decode_train_step: flags other than SS_STEP_NO_ADAM and SS_STEP_ACCUMULATE");
+    if (!e->G) return fail("ss_g3_decode_train_step: engine is not bound (call ss_bind first)");
+    if (e->dp_on) return fail("ss_g3_decode_train_step: not available on a member of a data-parallel group");
+    if (!(flags & SS_STEP_NO_ADAM) && (!e->Mm || !e->Vv)) return fail("ss_g3_decode_train_step: Adam arenas are not bound (pass SS_STEP_NO_ADAM)");
+    CHK(entry_check(e));
+    Own own(e, stream);
+    hipStream_t s = own.s;
+    prof_tick(e);
+    CHK(decode_train_body(e, CallerCodes{{codes_x, codes_r, codes_f0}, c_trg}, B, T, s));
+    const int C = e->head_out;
+    HIPCHK(mse_loss(CRows::slab(e->out_slab, C, T), CRows::dense(target_mel, C, T), Rows::slab(e->d_out_slab, C, T), B, T, C, 1.0f, e->loss_part, loss, s));
+    float* const d_codes[3] = {nullptr, nullptr, nullptr};
+    CHK(decode_backward_body(e, d_codes, dc_trg, (flags & SS_STEP_ACCUMULATE) != 0, s));
+    if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_decoder_enqueue(e, grad_scale, s));
+    return 0;
 }
 
 static int g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, const float* scales, const int* len_seg, const int* lens, int B,

@@ -73,4 +73,71 @@ hipError_t spk_grad(const float* dg, long ld, long b_stride, int rows, const flo
     return hipGetLastError();
 }
 
+// ---- gradients of the CODES a decode ran on (ss_g3_decode_backward / ss_g6_decode_backward) ----
+// The decoder input repeats each code row over its block of freq frames (dec_in_from_codes), so a code element's gradient is the sum of the
+// decoder-input gradient over the block's frames: dst[b][blk][c] = sum_u d_in[row(b, blk * k + u)][col + c], u = 0 .. k - 1 ascending, one
+// thread per element (float4 of elements where the code's columns are whole aligned float4s: CodeGradPack::vec), no atomics -- the same bits
+// on every run.  k = freq rows of the slab [B, TP, ld] (row0 = HALO, rows_b = TP), or k = 1 row of the compact form [B, T / f, ld], which
+// holds the block sums already (row0 = 0, rows_b = T / f).  grid = (x, B, codes), block 256; memory-bound, every input element read once.
+struct CodeGradPack {
+    CodeGrad s[3];
+    int vec[3];
+    int n;
+};
+
+__global__ __launch_bounds__(256) void dec_in_codes_grad_kernel(CodeGradPack p, const float* __restrict__ d_in, int ld, int T, long rows_b, int row0,
+                                                                int compact) {
+    const CodeGrad c = p.s[blockIdx.z];
+    const int b = blockIdx.y;
+    const int W = 2 * c.H, nb = T / c.freq, k = compact ? 1 : c.freq;
+    const float* src = d_in + ((long)b * rows_b + row0) * ld + c.col;
+    float* dst = c.dst + (long)b * nb * W;
+    if (p.vec[blockIdx.z]) {
+        const int Q = W / 4, n = nb * Q;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+            const int blk = i / Q, cc = (i - blk * Q) * 4;
+            const float* r = src + (long)blk * k * ld + cc;
+            float4 acc = *reinterpret_cast<const float4*>(r);
+            for (int u = 1; u < k; ++u) {
+                const float4 v = *reinterpret_cast<const float4*>(r + (long)u * ld);
+                acc.x += v.x;
+                acc.y += v.y;
+                acc.z += v.z;
+                acc.w += v.w;
+            }
+            *reinterpret_cast<float4*>(dst + (long)blk * W + cc) = acc;
+        }
+        return;
+    }
+    const int n = nb * W;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const int blk = i / W, cc = i - blk * W;
+        const float* r = src + (long)blk * k * ld + cc;
+        float acc = r[0];
+        for (int u = 1; u < k; ++u) acc += r[(long)u * ld];
+        dst[i] = acc;
+    }
+}
+
+hipError_t dec_in_codes_grad(const CodeGrad* g, int n, const float* d_in, int ld, int B, int T, int f, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (n < 0 || n > 3 || !d_in || B < 1 || T < 1 || ld < 1 || f < 0 || (f && T % f)) return hipErrorInvalidValue;
+    CodeGradPack p{};
+    p.n = n;
+    int most = 1;
+    for (int i = 0; i < n; ++i) {
+        const CodeGrad& c = g[i];
+        if (!c.dst || c.H < 1 || c.freq < 1 || T % c.freq || c.col < 0 || (long)c.col + 2L * c.H > ld || (f && c.freq != f)) return hipErrorInvalidValue;
+        p.s[i] = c;
+        p.vec[i] = c.H % 2 == 0 && c.col % 4 == 0 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(c.dst) | reinterpret_cast<uintptr_t>(d_in)) % 16 == 0;
+        const int elems = (T / c.freq) * 2 * c.H / (p.vec[i] ? 4 : 1);
+        most = elems > most ? elems : most;
+    }
+    int gx = cdiv(most, 256);
+    if (gx > 64) gx = 64;
+    const long TP = T + 2 * HALO;
+    hipLaunchKernelGGL(dec_in_codes_grad_kernel, dim3(gx, B, n), dim3(256), 0, s, p, d_in, ld, T, f ? (long)(T / f) : TP, f ? 0 : HALO, f ? 1 : 0);
+    return hipGetLastError();
+}
+
 }  // namespace ss

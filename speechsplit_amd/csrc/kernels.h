@@ -180,6 +180,14 @@ struct CodeIn {           // one code feeding the decoder input
 // build_dec_in_compact).  Padding columns are written zero.  len (nullable): rows at or behind len[b] are zeros, their codes are not read.
 hipError_t dec_in_from_codes(const CodeIn* src, int nsrc, const float* emb, int emb_dim, int emb_col, float* dst, int ld, int B, int T, int f,
                              hipStream_t s, const int* len = nullptr);
+struct CodeGrad {         // one code whose gradient is wanted (ss_g3_decode_backward / ss_g6_decode_backward)
+    float* dst;           // [B, T / freq, 2H], dense
+    int H, freq, col;     // col: first column inside the decoder input
+};
+// The adjoint of dec_in_from_codes for the codes (input_grads.hip): dst_i[b][blk][c] = the sum over the block's freq_i frames, frames
+// ascending, of d_in[.][col_i + c].  f == 0: d_in is the slab [B, TP, ld]; f > 0: the compact [B, T / f, ld], which already holds the sums
+// (every freq_i == f).  Up to three codes in ONE launch; fixed order, no atomics.
+hipError_t dec_in_codes_grad(const CodeGrad* g, int n, const float* d_in, int ld, int B, int T, int f, hipStream_t s);
 
 // loss = mean((tgt - out)^2) over B*T*C real elements (solver.py:166); d_out = 2 (out - tgt) / N * scale
 hipError_t mse_loss(CRows out, CRows tgt, Rows d_out, int B, int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s);

@@ -341,6 +341,85 @@ class Engine:
         _capi.check(self.lib.ss_g6_decode(self.h, _ptr(cr), _ptr(cf), _ptr(ln), B, T, _ptr(out), _stream()))
         return out
 
+    # ------------------------------------------------------------------ differentiable decode (decoder + head + speaker rows on given codes)
+    def _decode_args(self, codes, c_trg=None):
+        """Shape checks of g3_decode / g6_decode for the calls that differentiate: codes in the engine's order, dense, no lengths."""
+        hp = self.hp
+        names = ('x', 'r', 'f0') if self.kind == 'G3' else ('r', 'f0')
+        codes_r = codes[names.index('r')]
+        if codes_r.dim() != 3:
+            raise ValueError(f'speechsplit_amd: codes_r must be [B, T / freq_2, 2 * dim_neck_2], got {tuple(codes_r.shape)}')
+        B, T = codes_r.shape[0], codes_r.shape[1] * hp.freq_2
+        if T % hp.freq or T % hp.freq_3:
+            raise ValueError(f'speechsplit_amd: codes_r implies T = {T}, which is not a multiple of the code factors {(hp.freq, hp.freq_2, hp.freq_3)}')
+        shp = self.code_shapes(B, T)
+        codes = tuple(self._code_arg('codes_' + n, t, shp[n]) for n, t in zip(names, codes))
+        if c_trg is not None:
+            c_trg = self._f(c_trg)
+            if c_trg.dim() != 2 or c_trg.shape[1] != hp.dim_spk_emb or c_trg.shape[0] not in (1, B):
+                raise ValueError(f'speechsplit_amd: c_trg must be [{B} or 1, {hp.dim_spk_emb}], got {tuple(c_trg.shape)}')
+            if c_trg.shape[0] != B:
+                c_trg = c_trg.expand(B, -1).contiguous()
+        self._fwd_bt = None
+        return B, T, codes, c_trg
+
+    def g3_decode_train(self, codes_x, codes_r, codes_f0, c_trg):
+        """g3_decode on a dense batch, recorded so that g3_decode_backward can follow (ss_g3_decode_train): T <= max_frames, no lengths."""
+        B, T, (cx, cr, cf), c_trg = self._decode_args((codes_x, codes_r, codes_f0), c_trg)
+        out = self._new('out', (B, T, self.hp.dim_freq))
+        _capi.check(self.lib.ss_g3_decode_train(self.h, _ptr(cx), _ptr(cr), _ptr(cf), _ptr(c_trg), B, T, _ptr(out), _stream()))
+        self._dec_bt = (B, T)
+        return out
+
+    def _decode_grad_buffers(self, names, want):
+        want = tuple(want)
+        if set(want) - set(names):
+            raise ValueError(f'speechsplit_amd: want must name some of {tuple(names)}, got {want}')
+        B, T = getattr(self, '_dec_bt', None) or (1, self.hp.freq_2)      # (no decode ran: the call refuses; the buffers are never written)
+        shp = dict(self.code_shapes(B, T), c_trg=(B, self.hp.dim_spk_emb))
+        return tuple(self._new('d_' + n, shp[n]) if n in want else None for n in names)
+
+    def g3_decode_backward(self, d_out, want=(), accumulate=False):
+        """Backward of the last g3_decode_train (ss_g3_decode_backward): decoder + head gradients into the arena's [grad_split, arena)
+        (the rest exact zeros unless accumulate).  want: names among ('x', 'r', 'f0', 'c_trg') -> (d_codes_x, d_codes_r, d_codes_f0,
+        dc_trg) as fresh tensors, None where not asked for; dc_trg is per row [B, dim_spk_emb]."""
+        dx, dr, df, dc = self._decode_grad_buffers(('x', 'r', 'f0', 'c_trg'), want)
+        d_out = self._f(d_out)
+        _capi.check(self.lib.ss_g3_decode_backward(self.h, _ptr(d_out), _ptr(dx), _ptr(dr), _ptr(df), _ptr(dc), 8 if accumulate else 0, _stream()))
+        return dx, dr, df, dc
+
+    def g3_decode_train_step(self, codes_x, codes_r, codes_f0, c_trg, target_mel, grad_scale=1.0, no_adam=False, accumulate=False,
+                             want_dc_trg=False):
+        """Decode, MSE (mean) against target_mel, backward, Adam over the decoder + head range, in one call (ss_g3_decode_train_step).
+        Returns the device loss, or (loss, dc_trg [B, dim_spk_emb]) with want_dc_trg.  no_adam: stop behind the backward."""
+        B, T, (cx, cr, cf), c_trg = self._decode_args((codes_x, codes_r, codes_f0), c_trg)
+        tgt = self._code_arg('target_mel', target_mel, (B, T, self.hp.dim_freq))
+        dc = self._new('d_c_trg', (B, self.hp.dim_spk_emb)) if want_dc_trg else None
+        self._dec_bt = (B, T)
+        flags = (1 if no_adam else 0) | (8 if accumulate else 0)
+        _capi.check(self.lib.ss_g3_decode_train_step(self.h, _ptr(cx), _ptr(cr), _ptr(cf), _ptr(c_trg), _ptr(tgt), B, T, float(grad_scale), flags,
+                                                     _ptr(self.loss), _ptr(dc), _stream()))
+        return (self.loss, dc) if want_dc_trg else self.loss
+
+    def g6_decode_train(self, codes_r, codes_f0):
+        """g6_decode on a dense batch, recorded for g6_decode_backward (ss_g6_decode_train)."""
+        B, T, (cr, cf), _ = self._decode_args((codes_r, codes_f0))
+        out = self._new('out', (B, T, self.hp.dim_f0))
+        _capi.check(self.lib.ss_g6_decode_train(self.h, _ptr(cr), _ptr(cf), B, T, _ptr(out), _stream()))
+        self._dec_bt = (B, T)
+        return out
+
+    def g6_decode_backward(self, d_out, want=(), accumulate=False):
+        """Backward of the last g6_decode_train (ss_g6_decode_backward); want: names among ('r', 'f0') -> (d_codes_r, d_codes_f0)."""
+        dr, df = self._decode_grad_buffers(('r', 'f0'), want)
+        d_out = self._f(d_out)
+        _capi.check(self.lib.ss_g6_decode_backward(self.h, _ptr(d_out), _ptr(dr), _ptr(df), 8 if accumulate else 0, _stream()))
+        return dr, df
+
+    def adam_step_decoder(self, grad_scale=1.0):
+        """Adam on the decoder + head range [grad_split, arena) alone (ss_adam_step_decoder); the step counter advances by one."""
+        _capi.check(self.lib.ss_adam_step_decoder(self.h, float(grad_scale), _stream()))
+
     def g3_train_step(self, mel, f0, emb, len_org, draws, grad_scale=1.0, no_adam=False, split_backward=False, bucket=False,
                       accumulate=False, split_no_join=False):
         """solver.py:160-172 fused.  split_backward: return after the decoder + head gradients (arena offsets >=
@@ -1015,6 +1094,21 @@ def dec_in_grad(srcs, d_in, T, f=0):
     assert d_in.is_contiguous() and rows == (T // f if f else T + 4)
     arr = _code_srcs(srcs, B, T, True)
     _capi.check(_capi.lib().ss_op_dec_in_grad(arr, len(srcs), _ptr(d_in), ld, B, T, f, _stream()))
+
+
+def dec_in_codes_grad(codes, d_in, T, f=0):
+    """Test hook (ss_op_dec_in_codes_grad): the adjoint of the decoder input with respect to DENSE codes, as ss_*_decode_backward runs it.
+    codes = [(d_code, H, freq, col)], d_code [B, T/freq, 2H] contiguous float32 and written whole; d_in [B, T+4, ld] (f == 0; a view with
+    unit column stride whose utterances follow each other) or the block sums [B, T/f, ld] (f > 0).  One launch for up to three codes."""
+    B, rows, _ = d_in.shape
+    ld = d_in.stride(1)
+    assert d_in.stride(2) == 1 and rows == (T // f if f else T + 4) and (B == 1 or d_in.stride(0) == rows * ld)
+    arr = (_capi.SSCodeSrc * len(codes))()
+    for i, (t, H, freq, col) in enumerate(codes):
+        if tuple(t.shape) != (B, T // freq, 2 * H) or not t.is_contiguous() or t.dtype != torch.float32:
+            raise ValueError(f'speechsplit_amd: code gradient {i} must be a contiguous float32 [B, T / freq, 2H]')
+        arr[i] = _capi.SSCodeSrc(None, t.data_ptr(), H, freq, col, 2 * H)
+    _capi.check(_capi.lib().ss_op_dec_in_codes_grad(arr, len(codes), _ptr(d_in), ld, B, T, f, _stream()))
 
 
 def spk_grad(dg, w_f, w_r, col0, E, out):

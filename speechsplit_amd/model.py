@@ -168,6 +168,33 @@ class _G6Fn(torch.autograd.Function):
         return (None,) + dx + (None, None) + tuple(gv[n] for n in mod._names)
 
 
+class _DecodeFn(torch.autograd.Function):
+    """decode_grad of either generator: the decoder on given codes (and speaker rows), differentiated down to them.  Only the decoder + head
+    parameters are inputs of the node, so the encoders' parameters get no gradient from it (their .grad stays as it is)."""
+
+    @staticmethod
+    def forward(ctx, mod, ninputs, *args):
+        ctx.mod = mod
+        inputs = args[:ninputs]
+        ctx.ninputs = ninputs
+        ctx.in_meta = [(t.shape, t.dtype, t.device) for t in inputs]
+        eng = mod._eng
+        return eng.g3_decode_train(*inputs) if mod.KIND == 'G3' else eng.g6_decode_train(*inputs)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        mod = ctx.mod
+        eng = mod._eng
+        names = ('x', 'r', 'f0', 'c_trg') if mod.KIND == 'G3' else ('r', 'f0')
+        want = _wanted(ctx, 2, names)
+        gi = (eng.g3_decode_backward if mod.KIND == 'G3' else eng.g6_decode_backward)(d_out.contiguous(), want=want)
+        dx = _input_grads(ctx, gi)
+        lo = eng.grad_split
+        flat = eng.grads[lo:].clone()                  # fresh storage, the decoder + head range only
+        gv = {n: flat[o - lo:o - lo + int(np.prod(s))].view(*s) for n, o, s in eng.table if o >= lo}
+        return (None, None) + dx + tuple(gv[n] for n in mod._dec_names())
+
+
 class _EngineModule(nn.Module):
     KIND = None
 
@@ -240,6 +267,19 @@ class _EngineModule(nn.Module):
         self._ensure_engine(tensors[0].device, tensors[0].shape[0])
         return lengths
 
+    def _dec_names(self):
+        """Names of the decoder + head parameters: the arena's [grad_split, arena) range, in registration order."""
+        return [n for n in self._names if n.startswith('decoder.')]
+
+    def _decode_grad(self, inputs):
+        """decode_grad of both generators: any mode (the decoder has no resampling), a GPU, autograd-connected."""
+        name = f'speechsplit_amd.{type(self).__name__}.decode_grad'
+        if not inputs[0].is_cuda:
+            raise RuntimeError(f'{name} runs on a ROCm GPU only: call .to("cuda") first')
+        self._ensure_engine(inputs[0].device, inputs[0].shape[0])
+        dec = [p for n, p in zip(self._names, self._plist) if n.startswith('decoder.')]
+        return _DecodeFn.apply(self, len(inputs), *inputs, *dec)
+
     def extra_repr(self):
         return f'speechsplit_amd HIP engine ({self.KIND}), {sum(p.numel() for p in self._plist)} parameters'
 
@@ -277,6 +317,12 @@ class Generator_3(_EngineModule):
         lengths = self._codes_entry('decode', (codes_2, codes_x, codes_f0, c_trg), lengths)
         return self._eng.g3_decode(codes_x, codes_2, codes_f0, c_trg, lengths=lengths)
 
+    def decode_grad(self, codes_x, codes_2, codes_f0, c_trg):
+        """decode() that autograd can differentiate: gradients go to the decoder + head parameters and to whichever of the codes and c_trg
+        require grad (a code's gradient has the code's shape; c_trg's is per row, summed over the batch for a [1, dim_spk_emb] row).  The
+        encoders' parameters get none.  Dense batches with T <= max_frames; works in .train() and .eval() mode."""
+        return self._decode_grad((codes_x, codes_2, codes_f0, c_trg))
+
 
 class Generator_6(_EngineModule):
     """F0 converter (reference model.py:324-351)."""
@@ -302,6 +348,10 @@ class Generator_6(_EngineModule):
         """The decoder on the caller's codes -> logits [B, T, dim_f0], as Generator_3.decode."""
         lengths = self._codes_entry('decode', (codes_2, codes_f0), lengths)
         return self._eng.g6_decode(codes_2, codes_f0, lengths=lengths)
+
+    def decode_grad(self, codes_2, codes_f0):
+        """decode() that autograd can differentiate, as Generator_3.decode_grad: gradients to the decoder + head parameters and the codes."""
+        return self._decode_grad((codes_2, codes_f0))
 
 
 class _InterpFn(torch.autograd.Function):

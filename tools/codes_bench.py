@@ -9,7 +9,13 @@
     (convert.convert_speakers), and against the batch-N decode alone on codes kept from an earlier encode.
 Before anything is timed the outputs of the variants are compared (relative max-norm, must be below 1e-4).
     python tools/codes_bench.py [--frames 192] [--speakers 16] [--reps 30] [--warmup 5] [--inner 10] [--precision f32]
-Prints one JSON line."""
+Prints one JSON line.
+
+--train: instead, the step times of training on cached codes (the differentiable decode) beside the full training step, one engine, one
+process, device events, median / min / max of --reps runs after --warmup, the variants alternated run by run, at --batches x --train-frames
+(default 64,16 x 128): ss_g3_train_step against the fused ss_g3_decode_train_step on that batch's codes, and the separate calls
+ss_g3_decode_train / ss_g3_decode_backward (with dc_trg) / ss_adam_step_decoder.  One JSON line per batch size.
+    python tools/codes_bench.py --train [--batches 64,16] [--train-frames 128] [--reps 30] [--warmup 5] [--precision f32]"""
 import argparse
 import json
 import os
@@ -22,6 +28,52 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def train_times(a):
+    import numpy as np
+    from oracle import weights as W
+    from oracle.gen_fixtures import draws_for, synth_batch
+    from speechsplit_amd.engine import Engine
+    T = a.train_frames
+    hp = W.default_hparams(max_len_pad=T)
+    for B in [int(b) for b in a.batches.split(',')]:
+        eng = Engine('G3', hp, B, T, device='cuda:0')
+        eng.set_precision(a.precision)
+        eng.load_weights(W.make_weights('G3', hp, 3))
+        eng.set_adam(1e-4, 0.9, 0.999, 1e-8, 0)
+        mel, f0, emb, lens = synth_batch(31, B, T, 64)
+        draws = draws_for(41, B, 4)
+        d = (np.stack([x[0] for x in draws]), np.stack([x[1] for x in draws]))
+        dev = eng.device
+        mel, f0, emb, lens = mel.to(dev), f0.to(dev), emb.to(dev), lens.to(dev)
+        d = (torch.from_numpy(d[0]).to(dev), torch.from_numpy(d[1]).to(dev))
+        onehot = torch.nn.functional.one_hot(torch.randint(0, hp.dim_f0, (B, T), generator=torch.Generator().manual_seed(2)), hp.dim_f0).float().to(dev)
+        codes = eng.g3_encode(torch.cat((mel, onehot), -1), mel)
+        d_out = torch.randn(B, T, hp.dim_freq, device=dev) / (B * T)
+        variants = (('full_step', lambda: eng.g3_train_step(mel, f0, emb, lens, d)),
+                    ('decode_step', lambda: eng.g3_decode_train_step(*codes, emb, mel, want_dc_trg=True)),
+                    ('decode_forward', lambda: eng.g3_decode_train(*codes, emb)),
+                    ('decode_backward', lambda: eng.g3_decode_backward(d_out, want=('c_trg',))),      # (follows decode_forward: the order below)
+                    ('adam_decoder', lambda: eng.adam_step_decoder()))
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        times = {k: [] for k, _ in variants}
+        for it in range(a.warmup + a.reps):
+            for tag, fn in variants:
+                ev[0].record()
+                fn()
+                ev[1].record()
+                torch.cuda.synchronize()
+                if it >= a.warmup:
+                    times[tag].append(ev[0].elapsed_time(ev[1]))
+        eng.check()
+        med = {k: statistics.median(v) for k, v in times.items()}
+        print(json.dumps({'train': True, 'batch': B, 'frames': T, 'precision': a.precision, 'reps': a.reps,
+                          'ms_median': {k: round(v, 4) for k, v in med.items()},
+                          'ms_minmax': {k: [round(min(v), 4), round(max(v), 4)] for k, v in times.items()},
+                          'decode_step_over_full_step': round(med['decode_step'] / med['full_step'], 3),
+                          'separate_calls_sum_ms': round(med['decode_forward'] + med['decode_backward'] + med['adam_decoder'], 4)}))
+        del eng
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--frames', type=int, default=192)
@@ -30,7 +82,14 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--inner', type=int, default=10)
     ap.add_argument('--precision', default='f32', choices=('f32', 'bf16'))
+    ap.add_argument('--train', action='store_true', help='time training on cached codes beside the full training step instead')
+    ap.add_argument('--batches', default='64,16')
+    ap.add_argument('--train-frames', type=int, default=128)
     a = ap.parse_args()
+    if a.train:
+        if not torch.cuda.is_available():
+            raise SystemExit('codes_bench: no GPU (there is nothing to time without one)')
+        return train_times(a)
     from speechsplit_amd import convert, hparams as HPM, model
     if not torch.cuda.is_available():
         raise SystemExit('codes_bench: no GPU (there is nothing to time without one)')
