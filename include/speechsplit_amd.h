@@ -750,6 +750,68 @@ int  ss_dtw(const double* fx_dev, const int* tx_dev, const double* fy_dev, const
 int  ss_path_f0_stats(const int* path_dev, const int* path_len_dev, const double* f0x_dev, const double* f0y_dev, int B, int max_tx,
                       int max_ty, double* out_dev /* [B][5] n_vv, n_vu, f0_rmse_cents, f0_corr, vuv_error */, void* stream);
 
+/* ---- waveform scores: short-time objective intelligibility (STOI) and its extended form (ESTOI) ----
+ * Nothing to mirror: the reference never scores a waveform.  STOI (Taal, Hendriks, Heusdens, Jensen 2011) and ESTOI (Jensen, Taal 2016)
+ * compare a degraded waveform y with a TIME-ALIGNED clean one x.  Float64 throughout.  Both signals are at 10 kHz and have n samples.
+ * eps = 2^-52.  What follows is the whole definition, the order of every sum included; a sum "in order" adds one term at a time, index
+ * ascending, and multiply-adds are not fused.
+ *
+ * Constants.  Frame 256, hop 128, transform 512 points (257 bins).  J bands (15 for the project), segment length N = 30 frames,
+ * beta = -15 dB, dynamic range 40 dB.  Window w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 257), i = 0 .. 255 (numpy.hanning(258)[1:-1]), evaluated
+ * on the host as 0.5 - 0.5 * cos(2.0 * pi * (i + 1) / 257.0) with the C library's cosine.
+ *
+ * Silent-frame removal.  Frames f = 0 .. F-1 start at 128 f, F = floor((n - 256) / 128) + 1 (F = 0 when n < 256).
+ *     e_f = 20 log10(sqrt(sum_i (w[i] x[128 f + i])^2) + eps),   i in order.
+ * Frame f is kept when e_f > max_f e_f - 40.  The K kept frames, in order (inv[c] is the c-th kept frame), are overlap-added at hop 128 into
+ * x' of 128 (K - 1) + 256 samples, and y' is built the same way with x's mask.  The overlap-add is a gather: with c = s / 128, r = s % 128,
+ *     x'[s] = w[r + 128] x[128 inv[c-1] + r + 128]  +  w[r] x[128 inv[c] + r],
+ * the earlier frame's term first; a term whose frame index is outside 0 .. K-1 is absent (the other term is then the sample, unrounded).
+ * The window is applied once and there is no division by a window sum.
+ *
+ * Band envelopes.  Transform frames of x' and y' start at 128 m for m = 0 .. M-1, M = K - 1: the starts strictly below len - 256, as in the
+ * authors' published code (the last full frame is left out).  Each frame is windowed by w, zero-padded to 512 and transformed;
+ *     X[j][m] = sqrt(sum_{k in [lo_j, hi_j)} (re_k^2 + im_k^2)),   k in order, each term the sum of its two squares.
+ * lo and hi are inputs.  The Python layer passes third-octave bands: cf_j = 150 * 2^(j/3), edges cf_j 2^(-1/6) and cf_j 2^(+1/6), each mapped
+ * to the nearest of the bin frequencies k * 10000 / 512:
+ *     lo = 7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174      hi = 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219
+ *
+ * Segments.  S = M - N + 1; segment s is frames s .. s+29 of both envelopes, X_j and Y_j its rows (t = 0 .. 29).
+ * "Normalising" a vector v of c elements: mean = (sum v, in order) / c; v <- v - mean; v <- v / (sqrt(sum v^2, in order) + eps).
+ *   STOI, per band j:  alpha = sqrt(sum_t X_j[t]^2) / (sqrt(sum_t Y_j[t]^2) + eps);   Y'_j[t] = min(alpha Y_j[t], X_j[t] (1 + 10^(15/20)));
+ *         X_j and Y'_j are normalised over t;   d_{s,j} = sum_t X_j[t] Y'_j[t];   d_s = (sum_j d_{s,j}) / J.         Every sum in order.
+ *   ESTOI:  every row of both blocks is normalised over t; then every column of both is normalised over j;
+ *         c_t = sum_j X_j[t] Y_j[t];   d_s = (sum_t c_t) / N.                                                          Every sum in order.
+ * score = (sum_s d_s) / S, s in order.  When S < 1 (fewer than 31 kept frames) the score is NaN and S is reported as 0; the constant the
+ * published code returns in that case is deliberately not copied.
+ *
+ * What this does NOT claim: parity with pystoi is unpinned (that package adds random noise in its normalisation and resamples with its own
+ * filter; the Python layer here resamples with ss_resample).
+ *
+ * Ragged batches.  x_dev, y_dev [B][max_n]; n_dev i32[B] (NULL: every row is full): row b is the result of running that pair alone at
+ * min(max(n[b], 1), max_n) samples, to the bit -- a length outside 1 .. max_n spoils that row only; samples at or beyond it are never
+ * read (they may hold NaN).  No atomics, every sum in a fixed order: the same bits on every run.  No engine needed, no allocation inside,
+ * asynchronous on `stream`.  band_lo / band_hi are HOST arrays of n_bands ints.  out [B][3] = score, S, K as doubles.
+ * The scratch, with F = floor((max_n - 256) / 128) + 1, L = 128 (F - 1) + 256, M = F - 1, S = max(M - 29, 0), every part rounded up to 256
+ * bytes: frame levels 8 B F, the inverse map 4 B F, K 4 B, x' and y' 8 B L each, two envelopes 8 B 32 M each, d_s 8 B S.  Every index read
+ * back from it (inverse map, K) is clamped into the row's own frames: a corrupt scratch changes numbers, never addresses.
+ *
+ * Test hooks.  ss_op_stoi_compact runs the first three stages: e [B][F] (-inf behind a row's frames), inv i32 [B][F] (-1 behind the K kept
+ * frames), k i32 [B], x' and y' [B][L] (zeros behind a row's samples).  With from_map = 1 the energies and the mask are skipped: inv_dev and
+ * k_dev are INPUTS, read with the clamps above, and e_dev may be NULL.  ss_op_stoi_bands gives the envelopes [B][n_bands][Mmax] of sig_dev
+ * [B][max_len] (len_dev i32[B] or NULL, clamped to 1 .. max_len; Mmax = ceil((max_len - 256) / 128); zeros at and behind a row's M frames).
+ *
+ * Refused before anything is enqueued, with a message that names the argument: null required pointers, B outside 1 .. 65535, max_n below
+ * 256 (max_len below 257) or so large that the scratch does not fit a long, n_bands outside 1 .. 32, a band with lo < 0, hi > 257 or
+ * lo >= hi, extended or from_map outside 0 / 1, scratch_bytes below what the scratch query returns, scratch_dev not 256-byte aligned. */
+long ss_stoi_scratch_bytes(int B, int max_n);                 /* host only; -1 + ss_last_error on bad arguments */
+int  ss_stoi(const double* x_dev, const double* y_dev, const int* n_dev, int B, int max_n, const int* band_lo, const int* band_hi,
+             int n_bands, int extended, double* out_dev /* [B][3]: score, S, K */, void* scratch_dev, long scratch_bytes, void* stream);
+int  ss_op_stoi_compact(const double* x_dev, const double* y_dev, const int* n_dev, int B, int max_n, int from_map,
+                        double* e_dev /* [B][F] */, int* inv_dev /* [B][F] */, int* k_dev /* [B] */, double* xp_dev /* [B][L] */,
+                        double* yp_dev /* [B][L] */, void* stream);
+int  ss_op_stoi_bands(const double* sig_dev, const int* len_dev, int B, int max_len, const int* band_lo, const int* band_hi, int n_bands,
+                      double* env_dev /* [B][n_bands][Mmax] */, void* stream);
+
 /* Batch producer on the GPU side (replaces the host loop of MyCollator.__call__, reference data_loader.py:101-128, for a
  * corpus kept resident in HBM): utterance b of the batch is rows [row0[b], row0[b] + len[b]) of the concatenated corpus
  * mel_cat [rows, n_mel] / f0_cat [rows]; the host only draws the crops (same generator calls, same order as the reference).

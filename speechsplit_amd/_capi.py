@@ -238,6 +238,12 @@ SYMBOLS = {
     'ss_dtw': (_i, [_vp, _ip, _vp, _ip, _i, _i, _i, _i, _d, _vp, _ip, _ip, _vp, _l, _vp]),
     # path, path_len, f0x, f0y, B, max_tx, max_ty, out, stream
     'ss_path_f0_stats': (_i, [_ip, _ip, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    # B, max_n / x, y, n, B, max_n, band_lo (host), band_hi (host), n_bands, extended, out, scratch, bytes, stream
+    'ss_stoi_scratch_bytes': (_l, [_i, _i]),
+    'ss_stoi': (_i, [_vp, _vp, _ip, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, _i, _vp, _vp, _l, _vp]),
+    # x, y, n, B, max_n, from_map, e, inv, k, xp, yp, stream / sig, len, B, max_len, band_lo (host), band_hi (host), n_bands, env, stream
+    'ss_op_stoi_compact': (_i, [_vp, _vp, _ip, _i, _i, _i, _vp, _ip, _ip, _vp, _vp, _vp]),
+    'ss_op_stoi_bands': (_i, [_vp, _ip, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, _vp, _vp]),
     'ss_collate': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'ss_set_precision': (_i, [_vp, _i]),
     'ss_profile': (_i, [_vp, C.c_uint]),

@@ -268,3 +268,27 @@ def conversion_scores(results, targets, **kw):
         return out
     it = iter(out)
     return [[next(it) for _ in pair] for pair in results]
+
+
+def conversion_stoi(waveforms, references, **kw):
+    """conversion_waveforms' output ``[(name, wav)]`` and one reference waveform per entry -> ``[(name, score dict)]``: STOI (with
+    ``extended=True`` ESTOI) of each waveform against its reference (metrics.stoi); nested input (one such list per pair) with references
+    nested the same way -> one such list per pair.  All the waveforms go through ONE metrics.stoi call; keyword arguments are handed on to
+    it.  STOI compares sample with sample, so it is defined only where the two are time-aligned: the conditions that keep the rhythm
+    (``F``, ``U``, ``FU``) against their source recording, and any vocoded mel against the recording the mel came from (the vocoder trims
+    exactly its 512 samples of padding, so sample 0 is sample 0).  A condition that converts rhythm (``R``, ``RF``, ``RU``, ``RFU``)
+    changes the timing by construction and has no defined STOI; this function does not know the conditions' meaning and scores what it is
+    given."""
+    from . import metrics                               # metrics imports plan_batches from here
+    waveforms, references = list(waveforms), list(references)
+    nested = bool(waveforms) and isinstance(waveforms[0], list)
+    flat = [w for pair in waveforms for w in pair] if nested else waveforms
+    flat_r = [r for pair in references for r in pair] if nested else references
+    if len(flat_r) != len(flat) or (nested and [len(p) for p in references] != [len(p) for p in waveforms]):
+        raise ValueError('conversion_stoi: references must hold one waveform per entry, nested as waveforms is')
+    scores = metrics.stoi(flat_r, [wav for _, wav in flat], **kw)
+    out = [(name, s) for (name, _), s in zip(flat, scores)]
+    if not nested:
+        return out
+    it = iter(out)
+    return [[next(it) for _ in pair] for pair in waveforms]

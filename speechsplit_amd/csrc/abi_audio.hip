@@ -1,5 +1,5 @@
 // C entry points of the audio / data front end (include/speechsplit_amd.h): collation, mel spectrograms, F0 normalisation, the pitch
-// tracker, batched feature extraction, the resampler, numpy's MT19937 stream, the Griffin-Lim vocoder and the conversion scores.  None of them takes an engine: each checks its arguments, refuses by
+// tracker, batched feature extraction, the resampler, numpy's MT19937 stream, the Griffin-Lim vocoder, the conversion scores and the waveform scores.  None of them takes an engine: each checks its arguments, refuses by
 // the argument's name through ss_last_error() and hands the rest to the launchers of kernels.h.
 #include <cmath>
 #include <cstdint>
@@ -515,6 +515,83 @@ int ss_path_f0_stats(const int* path, const int* path_len, const double* f0x, co
     if (!out) return fail("ss_path_f0_stats: null pointer: out_dev");
     CHK(dtw_shape("ss_path_f0_stats", B, max_tx, max_ty));
     HIPCHK(path_f0_stats(path, path_len, f0x, f0y, B, max_tx, max_ty, out, S(stream)));
+    return 0;
+}
+
+// ---- waveform scores (stoi.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+namespace {
+int stoi_rows(const char* who, int B, int max_n) {
+    if (B < 1 || B > STOI_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
+    if (max_n < STOI_FRAME) return fail(std::string(who) + ": max_n below 256 (one frame)");
+    long bytes = 0;                                       // an int max_n cannot get there today; the check stays with the arithmetic
+    if (__builtin_mul_overflow((long)B * 24L * STOI_MAX_BANDS, (long)max_n, &bytes))
+        return fail(std::string(who) + ": max_n so large that the scratch does not fit a long");
+    return 0;
+}
+int stoi_band_table(const char* who, const int* lo, const int* hi, int n_bands, StoiTables* tb) {
+    if (!lo) return fail(std::string(who) + ": null pointer: band_lo");
+    if (!hi) return fail(std::string(who) + ": null pointer: band_hi");
+    if (n_bands < 1 || n_bands > STOI_MAX_BANDS) return fail(std::string(who) + ": n_bands outside 1 .. 32");
+    for (int j = 0; j < n_bands; ++j) {
+        if (lo[j] < 0) return fail(std::string(who) + ": band_lo[" + std::to_string(j) + "] is negative");
+        if (hi[j] > 257) return fail(std::string(who) + ": band_hi[" + std::to_string(j) + "] is above 257 (the bins of a 512-point transform)");
+        if (lo[j] >= hi[j]) return fail(std::string(who) + ": band_lo[" + std::to_string(j) + "] is not below band_hi[" + std::to_string(j) + "]");
+    }
+    stoi_tables(lo, hi, n_bands, tb);
+    return 0;
+}
+}  // namespace
+
+static_assert(STOI_MAX_ROWS == 65535 && STOI_MAX_BANDS == 32 && STOI_FRAME == 256, "the refusals below and the header spell these numbers out");
+
+long ss_stoi_scratch_bytes(int B, int max_n) {
+    CHK(stoi_rows("ss_stoi_scratch_bytes", B, max_n));
+    return stoi_scratch_bytes(B, max_n);
+}
+
+int ss_stoi(const double* x, const double* y, const int* n, int B, int max_n, const int* band_lo, const int* band_hi, int n_bands,
+            int extended, double* out, void* scratch, long scratch_bytes, void* stream) {
+    StoiTables tb;
+    if (!x) return fail("ss_stoi: null pointer: x_dev");
+    if (!y) return fail("ss_stoi: null pointer: y_dev");
+    if (!out) return fail("ss_stoi: null pointer: out_dev");
+    CHK(stoi_rows("ss_stoi", B, max_n));
+    CHK(stoi_band_table("ss_stoi", band_lo, band_hi, n_bands, &tb));
+    if (extended != 0 && extended != 1) return fail("ss_stoi: extended is neither 0 nor 1");
+    if (!scratch) return fail("ss_stoi: null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail("ss_stoi: scratch_dev is not 256-byte aligned");
+    if (scratch_bytes < stoi_scratch_bytes(B, max_n)) return fail("ss_stoi: scratch_bytes below ss_stoi_scratch_bytes(B, max_n)");
+    HIPCHK(stoi(x, y, n, B, max_n, tb, extended, out, stoi_scratch(scratch, B, max_n), S(stream)));
+    return 0;
+}
+
+int ss_op_stoi_compact(const double* x, const double* y, const int* n, int B, int max_n, int from_map, double* e, int* inv, int* k,
+                       double* xp, double* yp, void* stream) {
+    StoiTables tb;
+    const int lo = 0, hi = 1;
+    if (!x) return fail("ss_op_stoi_compact: null pointer: x_dev");
+    if (!y) return fail("ss_op_stoi_compact: null pointer: y_dev");
+    if (from_map != 0 && from_map != 1) return fail("ss_op_stoi_compact: from_map is neither 0 nor 1");
+    if (!from_map && !e) return fail("ss_op_stoi_compact: null pointer: e_dev (it may be NULL only with from_map)");
+    if (!inv) return fail("ss_op_stoi_compact: null pointer: inv_dev");
+    if (!k) return fail("ss_op_stoi_compact: null pointer: k_dev");
+    if (!xp) return fail("ss_op_stoi_compact: null pointer: xp_dev");
+    if (!yp) return fail("ss_op_stoi_compact: null pointer: yp_dev");
+    CHK(stoi_rows("ss_op_stoi_compact", B, max_n));
+    stoi_tables(&lo, &hi, 1, &tb);
+    HIPCHK(stoi_compact(x, y, n, B, max_n, tb, from_map != 0, e, inv, k, xp, yp, S(stream)));
+    return 0;
+}
+
+int ss_op_stoi_bands(const double* sig, const int* len, int B, int max_len, const int* band_lo, const int* band_hi, int n_bands, double* env,
+                     void* stream) {
+    StoiTables tb;
+    if (!sig) return fail("ss_op_stoi_bands: null pointer: sig_dev");
+    if (!env) return fail("ss_op_stoi_bands: null pointer: env_dev");
+    if (B < 1 || B > STOI_MAX_ROWS) return fail("ss_op_stoi_bands: B outside 1 .. 65535");
+    if (max_len < STOI_FRAME + 1) return fail("ss_op_stoi_bands: max_len below 257 (no transform frame starts strictly below max_len - 256)");
+    CHK(stoi_band_table("ss_op_stoi_bands", band_lo, band_hi, n_bands, &tb));
+    HIPCHK(stoi_bands(sig, len, B, max_len, tb, env, S(stream)));
     return 0;
 }
 

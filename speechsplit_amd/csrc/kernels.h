@@ -417,6 +417,41 @@ hipError_t dtw(const double* fx, const int* tx, const double* fy, const int* ty,
 hipError_t path_f0_stats(const int* path, const int* path_len, const double* f0x, const double* f0y, int B, int max_tx, int max_ty,
                          double* out, hipStream_t s);
 
+// ---------------------------------------------------------------- stoi.hip  (waveform scores: STOI and ESTOI of y against an aligned x at 10 kHz)
+// Shapes: x, y [B][max_n]; with F = stoi_frames(max_n), L = 128 (F - 1) + 256, M = F - 1, S = M - 29 (StoiShape): e [B][F] frame levels in
+// dB, inv i32 [B][F] (inv[slot] = frame, -1 behind the K kept frames), K i32 [B], xp, yp [B][L], envelopes [B][n_bands][M], d [B][S],
+// out [B][3] (score, S, K).  n (nullable; device i32[B]): a row has min(max(n[b], 1), max_n) samples, is computed as if it were alone,
+// and samples at or beyond its length are never read.
+constexpr int STOI_MAX_ROWS = 65535;  // rows ride on gridDim.y
+constexpr int STOI_MAX_BANDS = 32;    // a band per thread of the segment kernel's wavefront, 30 frames of each in its LDS
+constexpr int STOI_FRAME = 256, STOI_HOP = 128, STOI_SEG = 30;
+constexpr double STOI_RANGE_DB = 40.0, STOI_BETA_DB = -15.0;
+__host__ __device__ inline int stoi_frames(int n) { return n >= STOI_FRAME ? (n - STOI_FRAME) / STOI_HOP + 1 : 0; }
+struct StoiTables {                   // passed to the kernels by value: the host's own cosine makes the window
+    double w[STOI_FRAME];             // 0.5 - 0.5 cos(2 pi (i + 1) / 257)
+    int lo[STOI_MAX_BANDS], hi[STOI_MAX_BANDS], n_bands;      // band j sums bins lo[j] .. hi[j] - 1 of the 512-point transform
+};
+struct StoiShape {
+    int F, L, M, S;                   // frames, compacted samples, transform frames and segments a row of max_n samples can have
+};
+struct StoiScratch {
+    double* e;
+    int *inv, *K;
+    double *xp, *yp, *ex, *ey, *d;    // ex, ey are laid out for the n_bands of the call, inside room for STOI_MAX_BANDS
+};
+StoiShape stoi_shape(int max_n);
+int stoi_bands_frames(int max_len);   // transform frames of a signal of max_len samples: the starts 128 m strictly below max_len - 256
+long stoi_scratch_bytes(int B, int max_n);
+StoiScratch stoi_scratch(void* base, int B, int max_n);
+void stoi_tables(const int* band_lo, const int* band_hi, int n_bands, StoiTables* tb);      // host: the window and the band edges
+// energies, mask and map (skipped with from_map: inv and K are then inputs, and e is not touched), then the compacting overlap-add
+hipError_t stoi_compact(const double* x, const double* y, const int* n, int B, int max_n, const StoiTables& tb, bool from_map, double* e,
+                        int* inv, int* K, double* xp, double* yp, hipStream_t s);
+// band envelopes of sig [B][max_len] (len nullable) -> env [B][n_bands][stoi_bands_frames(max_len)]
+hipError_t stoi_bands(const double* sig, const int* len, int B, int max_len, const StoiTables& tb, double* env, hipStream_t s);
+hipError_t stoi(const double* x, const double* y, const int* n, int B, int max_n, const StoiTables& tb, int extended, double* out,
+                const StoiScratch& sc, hipStream_t s);
+
 // ---------------------------------------------------------------- lstm_small.hip  (hidden <= 32: whole recurrence in one launch)
 // Row stride of a small BLSTM's output, cell-state and output-gradient slabs: 2H for H a power of two (the default widths keep their
 // layout), else 2H rounded up to a multiple of 4 floats (16-byte rows: vector loads and the GEMMs' aligned path).  The padding columns

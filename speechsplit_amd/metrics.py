@@ -6,7 +6,10 @@ the mel bands (row 0, the level, is left out); the frame distance is 50 sqrt(2) 
 mels are S = (dB + 100) / 100, so ln|A| = (100 S - 84) ln 10 / 20 and the usual (10 / ln 10) sqrt(2 sum dc^2) in dB becomes that scale on
 the cepstra of S; DTW takes steps (1,1), (1,0), (0,1) of weight 1 with both ends fixed, the diagonal winning a tie, then (i-1, j), with no
 band and no slope constraint; mcd_db is the path's total cost over its length.  F0 tracks are features.pitch_track's: ln Hz, -1e10 for
-unvoiced frames.  float64 throughout; the same bits on every run, whatever the batching.  No engine needed."""
+unvoiced frames.  float64 throughout; the same bits on every run, whatever the batching.  No engine needed.
+
+Waveforms are scored by `stoi` (csrc/stoi.hip): the short-time objective intelligibility measure and its extended form of a degraded
+waveform against a time-aligned clean one, as the header's "waveform scores" section defines them."""
 import ctypes as C
 import math
 
@@ -166,4 +169,125 @@ def mcd_dtw(xs, ys, f0x=None, f0y=None, n_ceps=24, max_rows=16, device='cuda', r
             if return_paths:
                 r['path'] = np.ascontiguousarray(path[n, :int(plen[n])], dtype=np.int32)
             res[i] = r
+    return res[0] if single else res
+
+
+# ---------------------------------------------------------------------------------------------- waveform scores (csrc/stoi.hip)
+STOI_SR = 10000
+STOI_FRAME, STOI_HOP, STOI_NFFT, STOI_BANDS, STOI_FIRST_HZ = 256, 128, 512, 15, 150.0
+
+
+def stoi_bands(n_bands=STOI_BANDS, first_hz=STOI_FIRST_HZ, sr=STOI_SR, n_fft=STOI_NFFT):
+    """(lo, hi), two lists of n_bands ints: third-octave bands with centres first_hz * 2^(j/3) and edges a sixth of an octave either side,
+    each edge at the nearest of the bin frequencies k sr / n_fft; band j sums bins lo[j] .. hi[j] - 1."""
+    f = np.arange(n_fft // 2 + 1, dtype=np.float64) * (sr / n_fft)
+    cf = first_hz * 2.0 ** (np.arange(int(n_bands), dtype=np.float64) / 3.0)
+    lo = [int(np.argmin(np.abs(f - c * 2.0 ** (-1.0 / 6.0)))) for c in cf]
+    hi = [int(np.argmin(np.abs(f - c * 2.0 ** (1.0 / 6.0)))) for c in cf]
+    return lo, hi
+
+
+def stoi_frames(n):
+    """frames of n samples at 10 kHz: floor((n - 256) / 128) + 1, none below 256 samples"""
+    return (int(n) - STOI_FRAME) // STOI_HOP + 1 if n >= STOI_FRAME else 0
+
+
+def _int_array(v):
+    return (C.c_int * len(v))(*[int(a) for a in v])
+
+
+def stoi_dev(x_dev, y_dev, n_dev, extended=False, bands=None):
+    """The C call on device tensors: x, y float64 [B, max_n] at 10 kHz, n int32 [B] or None -> float64 [B, 3] = score, S, K."""
+    lib = _capi.lib()
+    B, max_n = x_dev.shape
+    lo, hi = bands if bands is not None else stoi_bands()
+    nbytes = lib.ss_stoi_scratch_bytes(B, max_n)
+    if nbytes < 0:
+        _capi.check(-1)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=x_dev.device)
+    out = torch.empty(B, 3, dtype=torch.float64, device=x_dev.device)
+    _capi.check(lib.ss_stoi(_ptr(x_dev), _ptr(y_dev), _ptr(n_dev), B, max_n, _int_array(lo), _int_array(hi), len(lo), int(bool(extended)),
+                            _ptr(out), _ptr(scratch), nbytes, _stream(x_dev)))
+    return out
+
+
+def stoi_compact_dev(x_dev, y_dev, n_dev, inv_dev=None, k_dev=None):
+    """The test hook on device tensors: x, y float64 [B, max_n], n int32 [B] or None -> (e float64 [B, F], inv int32 [B, F], K int32 [B],
+    x' and y' float64 [B, 128 (F - 1) + 256]).  With inv_dev and k_dev given the energies and the mask are skipped (e is None) and the
+    gather runs through the given map."""
+    B, max_n = x_dev.shape
+    F = max(stoi_frames(max_n), 1)
+    L = STOI_HOP * (F - 1) + STOI_FRAME
+    from_map = inv_dev is not None
+    e = None if from_map else torch.empty(B, F, dtype=torch.float64, device=x_dev.device)
+    inv = inv_dev if from_map else torch.empty(B, F, dtype=torch.int32, device=x_dev.device)
+    k = k_dev if from_map else torch.empty(B, dtype=torch.int32, device=x_dev.device)
+    xp, yp = (torch.empty(B, L, dtype=torch.float64, device=x_dev.device) for _ in range(2))
+    _capi.check(_capi.lib().ss_op_stoi_compact(_ptr(x_dev), _ptr(y_dev), _ptr(n_dev), B, max_n, int(from_map), _ptr(e), _ptr(inv), _ptr(k),
+                                               _ptr(xp), _ptr(yp), _stream(x_dev)))
+    return e, inv, k, xp, yp
+
+
+def stoi_envelopes_dev(sig_dev, len_dev, bands=None):
+    """The test hook on device tensors: sig float64 [B, max_len], len int32 [B] or None -> float64 [B, n_bands, ceil((max_len - 256) / 128)],
+    zeros at and behind a row's own frames."""
+    B, max_len = sig_dev.shape
+    lo, hi = bands if bands is not None else stoi_bands()
+    M = max(-(-(max_len - STOI_FRAME) // STOI_HOP), 1)
+    env = torch.empty(B, len(lo), M, dtype=torch.float64, device=sig_dev.device)
+    _capi.check(_capi.lib().ss_op_stoi_bands(_ptr(sig_dev), _ptr(len_dev), B, max_len, _int_array(lo), _int_array(hi), len(lo), _ptr(env),
+                                             _stream(sig_dev)))
+    return env
+
+
+def stoi_pairs(refs, degs):
+    """Host side of `stoi`: float64 copies of every pair, each cut to the shorter of the two"""
+    single = not isinstance(refs, (list, tuple))
+    if single:
+        refs, degs = [refs], [degs]
+    if len(refs) != len(degs):
+        raise ValueError(f'stoi: degs: one degraded waveform per reference ({len(degs)} against {len(refs)})')
+    pairs = []
+    for i, (r, d) in enumerate(zip(refs, degs)):
+        r, d = np.ascontiguousarray(r, dtype=np.float64), np.ascontiguousarray(d, dtype=np.float64)
+        if r.ndim != 1 or d.ndim != 1 or r.shape[0] < 1 or d.shape[0] < 1:
+            raise ValueError(f'stoi: pair {i}: waveforms must be [n] with n >= 1, not {r.shape} and {d.shape}')
+        n = min(r.shape[0], d.shape[0])
+        pairs.append((r[:n], d[:n]))
+    return single, pairs
+
+
+def stoi_batch(x, y, n, extended, device):
+    """One ragged batch, host arrays in and out: x, y float64 [B, max_n] at 10 kHz, n the rows' lengths -> out [B, 3]"""
+    n_d = torch.tensor(n, dtype=torch.int32, device=device)
+    return stoi_dev(torch.from_numpy(x).to(device), torch.from_numpy(y).to(device), n_d, extended).cpu().numpy()
+
+
+def stoi(refs, degs, sr=16000, extended=False, max_rows=16, device='cuda'):
+    """STOI (``extended=True``: ESTOI) of degraded waveforms degs[n] against time-aligned clean ones refs[n] (lists of 1-D waveforms at
+    ``sr`` Hz, or one pair): one dict per pair, in input order, with ``stoi`` (the score; NaN when fewer than 31 frames survive the
+    silent-frame removal), ``segments`` (the 30-frame segments averaged over), ``frames_kept`` and ``frames``.  Each pair is cut to the
+    shorter of the two; both are brought to 10 kHz with features.resample (skipped when sr == 10000).  The pairs run as ragged batches of
+    at most max_rows rows in convert.plan_batches order; every row is the result of running it alone, so the bits do not depend on
+    max_rows.  The measure needs sample 0 of one waveform to BE sample 0 of the other: a vocoded mel against the recording it came from,
+    or a conversion that keeps the rhythm against its source."""
+    from . import features                              # features imports plan_batches from convert as this module does
+    single, pairs = stoi_pairs(refs, degs)
+    res = [None] * len(pairs)
+    if not pairs:
+        return res
+    xs, ys = [p[0] for p in pairs], [p[1] for p in pairs]
+    if int(sr) != STOI_SR:
+        both = features.resample(xs + ys, sr, STOI_SR, max_rows=max_rows, device=device)
+        xs, ys = both[:len(pairs)], both[len(pairs):]
+    lens = [x.shape[0] for x in xs]
+    for batch in plan_batches(lens, max_rows):
+        n = [lens[i] for i in batch]
+        max_n = max(n[-1], STOI_FRAME)                  # the C call takes at least one frame's room; a shorter row scores NaN
+        bx, by = np.zeros((len(batch), max_n)), np.zeros((len(batch), max_n))
+        for r, i in enumerate(batch):
+            bx[r, :n[r]], by[r, :n[r]] = xs[i], ys[i]
+        out = stoi_batch(bx, by, n, bool(extended), device)
+        for r, i in enumerate(batch):
+            res[i] = {'stoi': float(out[r, 0]), 'segments': int(out[r, 1]), 'frames_kept': int(out[r, 2]), 'frames': stoi_frames(n[r])}
     return res[0] if single else res
