@@ -1337,6 +1337,16 @@ int ss_debug_xcc_map(int n_wg, int threads, int lds_bytes, int hold_us, unsigned
 /* named internal slab of the last call ("enc1.xf2", "dec.out2", ...); layout [B, T+4, C], frame t at row t+2 */
 int ss_debug_buffer(ss_engine* e, const char* name, float** ptr_dev, long* rows, long* cols);
 int ss_debug_names(ss_engine* e, char* buf, int cap);
+/* The kernel instance the last launch of one kind picked, as text: what = "gemm" (launch_gemm's kernels: "<tile> <NT|NN|TN|TA> <bf16x3|f16x2|bf16|f32>"
+ * followed by " tr" (transposing LDS reads), " ws" (wave-specialised), " pipe" (pipelined k-loop), " apre" (A an image in that loop) or
+ * " scalar" (fp32-MFMA kernel without vector loads), e.g. "128x128 TN f16x2 tr pipe apre"), "lstm_step_fwd" / "lstm_step_bwd" (the
+ * per-step recurrence kernels: "<H> <NW> <G>", e.g. "512 8 4").  A host-side record written when the launcher chooses (process-global, like
+ * the ss_tune knobs that steer the choice; empty before the first launch): no device work and no effect on any launch -- it lets a test that
+ * sets a knob prove which instance ran.  "<kind>_seen": every DISTINCT text of that kind since the last reset, one per line in order of first
+ * appearance (at most 64) -- what a whole training step launched, not only its last launch.  "reset": forgets all of it (returns 0), so that a
+ * text read afterwards was written by a launch made afterwards.  Copies at most n - 1 characters into buf; returns the text's length,
+ * negative for an unknown kind. */
+int ss_debug_last_variant(const char* what, char* buf, int n);
 
 #ifdef __cplusplus
 }

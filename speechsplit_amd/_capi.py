@@ -259,6 +259,7 @@ SYMBOLS = {
     'ss_tune': (_i, [C.c_char_p, _i]),
     'ss_debug_buffer': (_i, [_vp, C.c_char_p, C.POINTER(_vp), C.POINTER(_l), C.POINTER(_l)]),
     'ss_debug_names': (_i, [_vp, C.c_char_p, _i]),
+    'ss_debug_last_variant': (_i, [C.c_char_p, C.c_char_p, _i]),
 }
 
 _lib = None

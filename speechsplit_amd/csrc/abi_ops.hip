@@ -1,6 +1,10 @@
 // Engine-free kernel hooks of the C ABI (include/speechsplit_amd.h): single GEMM / image / LSTM launches for the tests and tools/, the
 // placement probes and ss_tune.  None of them takes an engine.
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
 #include <string>
+#include <vector>
 
 #include "abi.h"
 #include "knobs.h"
@@ -13,6 +17,19 @@ namespace ss {
 int g_op_time_major = 0;   // experiment: ss_op_lstm_fwd / _bwd take time-major slabs [T+4, B, C] (persistent kernels only)
 static unsigned* g_img_wq = nullptr;      // queue words (+ placement log) of the test hook's work-queue launches
 constexpr long IMG_WQ_BYTES = 16 + 16 * 1024;
+// see common.h: the last instance per kind, and every distinct one since ss_debug_last_variant("reset") (at most 64 per kind, first come)
+static char g_last_variant[VARIANT_KINDS][64] = {"", "", ""};
+static std::vector<std::string> g_seen_variants[VARIANT_KINDS];
+void note_variant(int kind, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_last_variant[kind], sizeof g_last_variant[kind], fmt, ap);
+    va_end(ap);
+    std::vector<std::string>& seen = g_seen_variants[kind];
+    for (const std::string& v : seen)
+        if (v == g_last_variant[kind]) return;
+    if (seen.size() < 64) seen.push_back(g_last_variant[kind]);
+}
 int g_img_xcc = 0;      // ss_op_gemm_img (test hook): run the image GEMM in its work-queue form on the XCDs of this mask
 }
 
@@ -217,6 +234,31 @@ int ss_debug_gemm_phases(unsigned long long* out24, int reset) {
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(gemm_phase_probe(out24, reset != 0));
     return 0;
+}
+
+int ss_debug_last_variant(const char* what, char* buf, int n) {
+    static const char* const kinds[VARIANT_KINDS] = {"gemm", "lstm_step_fwd", "lstm_step_bwd"};
+    const std::string w = what ? what : "";
+    if (w == "reset") {      // forget everything: a text read after this was written by a launch made after it
+        for (int k = 0; k < VARIANT_KINDS; ++k) {
+            g_last_variant[k][0] = 0;
+            g_seen_variants[k].clear();
+        }
+        return 0;
+    }
+    for (int k = 0; k < VARIANT_KINDS; ++k) {
+        std::string text;
+        if (w == kinds[k]) text = g_last_variant[k];
+        else if (w == std::string(kinds[k]) + "_seen")
+            for (const std::string& v : g_seen_variants[k]) text += v + "\n";
+        else continue;
+        if (buf && n > 0) {
+            strncpy(buf, text.c_str(), n - 1);
+            buf[n - 1] = 0;
+        }
+        return (int)text.size();
+    }
+    return fail("ss_debug_last_variant: unknown kind: " + w);
 }
 
 int ss_tune(const char* key, int value) {

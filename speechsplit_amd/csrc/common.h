@@ -217,4 +217,10 @@ __device__ __forceinline__ float ss_tanh(float x) {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Host-side record of the kernel instance a launcher picked last (ss_debug_last_variant; defined in abi_ops.hip): plain statics, written at
+// the moment of the choice and read by nothing but that entry point -- no device work, no launch depends on them.
+enum { VARIANT_GEMM, VARIANT_LSTM_STEP_FWD, VARIANT_LSTM_STEP_BWD, VARIANT_KINDS };
+void note_variant(int kind, const char* fmt, ...) __attribute__((format(printf, 2, 3)));      // the last text, and the set of distinct texts since the last reset
+#define SS_NOTE_VARIANT(kind, ...) note_variant(kind, __VA_ARGS__)
+
 }  // namespace ss

@@ -73,6 +73,10 @@ int g_dec_tail_split = 9;   // one-GPU step: on the side stream alone the decode
                         // within 200 us of each other under full contention.  Data parallel: layer 0 + head behind the pitch chain on the third stream
                         // +2.5-4 %; layer 0's forward direction + head at the very end of the third stream's and its reverse direction at the end of
                         // the main stream's enqueue order: 5.245 -> 5.226 ms at 64 x 128, +3-5 % at B <= 32: not done.
+                        // (Until dec_late took the main stream by pointer, a caller on the null stream -- every PyTorch caller on its default stream --
+                        // silently got 0's placement for layer 0 and the head under 3.  The 5.16 quoted for 3 above equals 0's figure and was
+                        // PROBABLY taken on such a caller, i.e. is 0's schedule; that is a supposition, nobody has re-measured it, and the real
+                        // main-stream placement of 3 is unmeasured.)
 int g_early_dw = 0;     // 16-bit data path, B <= 48: decoder layer l + 1's weight gradients as work-queue image GEMMs on the XCDs the backward recurrence of
                         // layer l leaves free (lstm_bwd), instead of beside the encoder backward at the end of the step.  Off: 2.99 -> 2.97 ms at
                         // 32 x 128, 2.68 -> 2.67 at 16, 3.38 -> 3.35 at 48 (tools/real_timeline.py): a work-queue launch ends only when the workgroups
@@ -2069,12 +2073,18 @@ int early_update(ss_engine* e, Backward& bw) {
 struct DecLate {
     int next = -1;                                   // next decoder layer whose weight gradients are still to be enqueued
     hipStream_t other[2] = {nullptr, nullptr};       // streams other than the side stream that carry some of them (tail split)
+    bool main_used = false;                          // ... and the main stream, kept apart: the caller's stream may be the NULL stream
+    hipStream_t main_s = nullptr;
 };
 // the decoder's layers dl.next .. l_lo and, with its layer 0, the head's weight gradients, behind the decoder chain (ev_join[1]): on ws
-// (null: the side stream), the reverse direction's dW_ih / dW_hh on over_ih / over_hh where given (DwRoute)
-int dec_late(ss_engine* e, Backward& bw, DecLate& dl, int l_lo, hipStream_t ws = nullptr, hipStream_t over_ih = nullptr, hipStream_t over_hh = nullptr) {
+// (null: the side stream), the reverse direction's dW_ih / dW_hh on over_ih / over_hh where given (DwRoute).  on_main (nullable): on THAT
+// stream instead of ws -- a pointer, because the main stream is the caller's and PyTorch's default stream is the null handle, which `ws`
+// reads as "the side stream" (dec_tail_split = 3 silently ran as 0 for layer 0 and the head until tests/test_gpu_schedule_knobs.py looked)
+int dec_late(ss_engine* e, Backward& bw, DecLate& dl, int l_lo, hipStream_t ws = nullptr, hipStream_t over_ih = nullptr, hipStream_t over_hh = nullptr,
+             const hipStream_t* on_main = nullptr) {
     if (dl.next < l_lo) return 0;
-    if (!ws) ws = e->side;
+    if (on_main) ws = *on_main;
+    else if (!ws) ws = e->side;
     auto behind_chain = [&](hipStream_t o) -> int {      // a stream other than the side stream: noted for the join at the end
         if (dl.other[0] != o && dl.other[1] != o) dl.other[dl.other[0] ? 1 : 0] = o;
         HIPCHK(hipStreamWaitEvent(o, e->ev_join[1], 0));
@@ -2083,7 +2093,11 @@ int dec_late(ss_engine* e, Backward& bw, DecLate& dl, int l_lo, hipStream_t ws =
     for (hipStream_t o : {over_ih, over_hh})
         if (o && o != ws && o != e->side) CHK(behind_chain(o));
     if (dl.next == e->ld.L - 1) HIPCHK(hipStreamWaitEvent(e->side, e->ev_join[1], 0));
-    if (ws != e->side) CHK(behind_chain(ws));
+    if (on_main) {
+        dl.main_used = true;
+        dl.main_s = ws;
+        HIPCHK(hipStreamWaitEvent(ws, e->ev_join[1], 0));
+    } else if (ws != e->side) CHK(behind_chain(ws));
     CHK(lstm_late_weights(e, bw, e->ld, dec_x(e), ws, dl.next, l_lo, {.over_ih = over_ih, .over_hh = over_hh}));
     dl.next = l_lo - 1;
     if (l_lo == 0) {
@@ -2091,6 +2105,7 @@ int dec_late(ss_engine* e, Backward& bw, DecLate& dl, int l_lo, hipStream_t ws =
         bw.dec_w_pending = false;
         for (hipStream_t o : dl.other)
             if (o) CHK(fork_join(e, o, e->side));      // one join for the end of the step; the early optimiser update reads what they wrote
+        if (dl.main_used) CHK(fork_join(e, dl.main_s, e->side));
         CHK(early_update(e, bw));
     }
     e->side_used = true;
@@ -2101,12 +2116,14 @@ int dec_late(ss_engine* e, Backward& bw, DecLate& dl, int l_lo, hipStream_t ws =
 // other stream -- its last layers and the head go behind streams that end early instead.  s: main, b2: pitch, b3: third; null: the side stream
 struct TailSplit {
     hipStream_t l2_hh, l1, l1_ih, l1_hh, l0;      // layer 2's reverse dW_hh; layer 1, its reverse dW_ih and dW_hh; layer 0 + head
+    bool l0_main;                                 // layer 0 + head on the main stream (whose handle may be null: not expressible in l0)
 };
-TailSplit dec_tail_split(int m, hipStream_t s, hipStream_t b2, hipStream_t b3) {
+TailSplit dec_tail_split(int m, hipStream_t b2, hipStream_t b3) {
     TailSplit t{};
     //                        m:        1        2        3    4        5        6
     t.l1 = m == 4 || m == 5 ? b3 : (m == 6 ? b2 : nullptr);
-    t.l0 = m == 1 || m == 5 ? b2 : (m == 2 || m == 6 || m >= 7 ? b3 : (m == 3 ? s : nullptr));
+    t.l0 = m == 1 || m == 5 ? b2 : (m == 2 || m == 6 || m >= 7 ? b3 : nullptr);
+    t.l0_main = m == 3;
     // 7-9: as 2, and layer 1's reverse direction leaves the side stream as well: 7: dW_ih -> third, dW_hh -> pitch stream; 8: both -> third; 9: dW_hh -> third
     t.l1_ih = m == 7 || m == 8 ? b3 : nullptr;
     t.l1_hh = m == 7 ? b2 : (m == 8 || m == 9 || m == 10 ? b3 : nullptr);
@@ -2220,10 +2237,10 @@ int backward_encoder(ss_engine* e, Backward& bw, hipStream_t s) {
     }
     // ---- phase 4: everything that only has to be finished by the end of the step
     if (!e->dp_on && prio && chain_par && bw.dec_w_pending && e->ld.L == 3 && g_dec_tail_split) {
-        const TailSplit t = dec_tail_split(g_dec_tail_split, s, b2, b3);
+        const TailSplit t = dec_tail_split(g_dec_tail_split, b2, b3);
         CHK(dec_late(e, bw, dl, 2, nullptr, nullptr, t.l2_hh));
         CHK(dec_late(e, bw, dl, 1, t.l1, t.l1_ih, t.l1_hh));
-        CHK(dec_late(e, bw, dl, 0, t.l0));
+        CHK(dec_late(e, bw, dl, 0, t.l0, nullptr, nullptr, t.l0_main ? &s : nullptr));
         if (t.l1 == b2 || t.l0 == b2 || t.l1_hh == b2) CHK(fork_join(e, b2, s));
     }
     CHK(dec_late(e, bw, dl, 0));

@@ -609,10 +609,15 @@ hipError_t launch_cfg(const GemmDesc& din, hipStream_t s) {
     // reduction-major pair of operands loses (dW 158 -> 230: four staging waves issue 32 dword loads per k-tile each).
     constexpr bool CAN_WS = BM == 128 && BN == 128;
     const bool ws = g_gemm_ws == 2 || (g_gemm_ws == 1 && !(TA && TB) && (long)grid.x * grid.y * grid.z <= 320);
+    // the instance picked below, as text (ss_debug_last_variant("gemm")): tile, layout, family, then tr / ws / pipe / apre
+    auto note = [&](const char* family, const char* form) {
+        SS_NOTE_VARIANT(VARIANT_GEMM, "%dx%d %s %s%s", BM, BN, TA ? "TN" : (TB ? "NN" : "NT"), family, form);
+    };
     if constexpr (CAN_TR) {
         if (g_gemm_tr && (g_gemm_tr == 1 || !(TA && TB)) && !(d.flags & GEMM_BF16) && quad_ok(d.A, TA, d.M) && quad_ok(d.B, TB, d.N)) {
             if constexpr (CAN_WS) {
                 if ((d.flags & GEMM_F16X2) && ws && !d.diag) {
+                    note("f16x2", " tr ws");
                     hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, TA, TB, 2, false, true, true>), grid, dim3(512), 0, s, d);
                     return hipGetLastError();
                 }
@@ -621,11 +626,13 @@ hipError_t launch_cfg(const GemmDesc& din, hipStream_t s) {
             // the decoder BLSTMs and of the convolutions (TN), the decoder's input gradients against the stacked weights' image (NN with tb)
             if constexpr (TB && BM == 128 && BN == 128) {
                 if (g_gemm_pipe && (d.flags & GEMM_F16X2) && (d.flags & GEMM_B_PRE) && (TA || d.A.seglen == 0)) {
+                    note("f16x2", (d.flags & GEMM_A_PRE) ? " tr pipe apre" : " tr pipe");
                     if (d.flags & GEMM_A_PRE) hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, TA, TB, 2, false, true, false, true, true>), grid, dim3(256), 0, s, d);
                     else hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, TA, TB, 2, false, true, false, true, false>), grid, dim3(256), 0, s, d);
                     return hipGetLastError();
                 }
             }
+            note((d.flags & GEMM_F16X2) ? "f16x2" : "bf16x3", " tr");
             if (d.flags & GEMM_F16X2) hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, TA, TB, 2, false, true>), grid, dim3(256), 0, s, d);
             else hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, TA, TB, 3, false, true>), grid, dim3(256), 0, s, d);
             return hipGetLastError();
@@ -633,10 +640,12 @@ hipError_t launch_cfg(const GemmDesc& din, hipStream_t s) {
     }
     if constexpr (CAN_WS) {
         if ((d.flags & GEMM_F16X2) && !(d.flags & GEMM_BF16) && ws && !d.diag) {
+            note("f16x2", " ws");
             hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, TA, TB, 2, false, false, true>), grid, dim3(512), 0, s, d);
             return hipGetLastError();
         }
     }
+    note((d.flags & GEMM_BF16) ? "bf16" : ((d.flags & GEMM_F16X2) ? "f16x2" : "bf16x3"), "");
     if (d.flags & GEMM_BF16) hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, TA, TB, 1>), grid, dim3(256), 0, s, d);
     else if (d.flags & GEMM_F16X2) hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, TA, TB, 2>), grid, dim3(256), 0, s, d);
     else if (GDIAG(d, 16) && BM == 128 && BN == 128 && !TA && !TB)

@@ -328,6 +328,7 @@ bool vec_ok(const Operand& o) {
 template <int BM, int BN, bool TA, bool TB>
 hipError_t launch_cfg(const GemmDesc& d, bool vec, hipStream_t s) {
     dim3 grid(cdiv(d.N, BN), cdiv(d.M, BM), d.batch * d.ksplit);
+    SS_NOTE_VARIANT(VARIANT_GEMM, "%dx%d %s f32%s", BM, BN, TA ? (TB ? "TN" : "TA") : (TB ? "NN" : "NT"), vec ? "" : " scalar");
     if (!vec) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 16, TA, TB, false, 1>), grid, dim3(256), 0, s, d);
     else if (g_gemm_diag & 2) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 16, TA, TB, true, 2>), grid, dim3(256), 0, s, d);
     else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, 16, TA, TB, true, 1>), grid, dim3(256), 0, s, d);

@@ -278,6 +278,7 @@ __global__ __launch_bounds__(256) void lstm_pack_w_kernel(const float* __restric
 template <int H, int NW, int G>
 hipError_t fwd_l(float* gates, const float* wfrag, const float* hf_cur, float* hf_next, float* out, float* csave, int B, int T,
                  int step, hipStream_t s, const int* len) {
+    SS_NOTE_VARIANT(VARIANT_LSTM_STEP_FWD, "%d %d %d", H, NW, G);      // the instance the switch below picked: H NW G
     hipLaunchKernelGGL((lstm_step_fwd_kernel<H, NW, G>), dim3(H / 16, cdiv(B, 16), 2), dim3(64 * NW), 0, s, gates, wfrag, hf_cur,
                        hf_next, out, csave, B, T, step, g_lstm_mode, len);
     return hipGetLastError();
@@ -285,6 +286,7 @@ hipError_t fwd_l(float* gates, const float* wfrag, const float* hf_cur, float* h
 template <int H, int NW, int G>
 hipError_t bwd_l(float* gates, const float* wfragT, const float* gf_cur, float* gf_next, const float* d_out, const float* csave,
                  float* dc, int B, int T, int step, hipStream_t s) {
+    SS_NOTE_VARIANT(VARIANT_LSTM_STEP_BWD, "%d %d %d", H, NW, G);      // the instance the switch below picked: H NW G
     hipLaunchKernelGGL((lstm_step_bwd_kernel<H, NW, G>), dim3(H / 16, cdiv(B, 16), 2), dim3(64 * NW), 0, s, gates, wfragT, gf_cur,
                        gf_next, d_out, csave, dc, B, T, step);
     return hipGetLastError();

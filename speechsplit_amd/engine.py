@@ -1496,6 +1496,25 @@ def tune(key, value):
     _capi.check(_capi.lib().ss_tune(key.encode(), int(value)))
 
 
+def last_variant(what):
+    """The kernel instance the last launch of kind 'gemm', 'lstm_step_fwd' or 'lstm_step_bwd' picked, as text (ss_debug_last_variant): a
+    host-side record, so a test that sets a knob can prove which instance ran."""
+    buf = C.create_string_buffer(8192)
+    if _capi.lib().ss_debug_last_variant(what.encode(), buf, len(buf)) < 0:
+        raise ValueError(_capi.lib().ss_last_error().decode())
+    return buf.value.decode()
+
+
+def seen_variants(what):
+    """Every distinct instance of that kind launched since reset_variants(), in order of first appearance (ss_debug_last_variant("<kind>_seen"))."""
+    return last_variant(what + '_seen').splitlines()
+
+
+def reset_variants():
+    """Forget the records: what last_variant / seen_variants return afterwards was written by launches made afterwards."""
+    last_variant('reset')
+
+
 def gemm(a, b, bias=None, ta=False, tb=False, ksplit=1, out=None, bf16=False, f16x2=False, a_img=None, b_img=None, part=None, as_engine=False):
     """Test hook for the MFMA GEMM: C[M,N] = A(m,k) B(n,k) (+bias).  a: [M,K] or [K,M] if ta; b: [N,K] or [K,N] if tb.
     as_engine (f16x2 only, ss_op_gemm_pre): the launch as the engine's weight gradients make it -- the largest tile the shape admits, the

@@ -384,7 +384,10 @@ def recurrent_operands(mode, tagged=False, H=32):
 def operands_of(H, knobs=None, hi_only=False, B=1):
     """The Operands of the kernel family engine.blstm_recurrence selects at hidden size H (csrc/lstm_seq.hip lstm_seq_supported: the
     persistent kernels at H = 256 and 512 unless persist = 0; lstm_seq_fwd: the tagged hand-off under seq_tag = 1 where the 2 ceil(B / 16)
-    groups are expected on one XCD each -- up to 8 groups, or a multiple of 8)."""
+    groups are expected on one XCD each -- up to 8 groups, or a multiple of 8).  Everything else -- H = 64 and 128, and H = 256 / 512 under
+    persist = 0 -- runs csrc/lstm_step.hip, whose operands are `exact` in every instance: lstm_nw (waves that split K) and lstm_g (16-wide
+    chunks requested ahead) move loads between waves and in time, every operand of v_mfma_f32_16x16x4_f32 is the fp32 word in memory, so
+    both keys are ignored here.  (They do change where the fp32 sum is cut: that is what F4 / B3's summation term covers.)"""
     knobs = knobs or {}
     if H in (256, 512) and knobs.get('persist', 1):
         groups = 2 * ((B + 15) // 16)

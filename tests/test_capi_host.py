@@ -257,6 +257,25 @@ def test_roofline_traffic_profile_matches_kernel_sources():
     assert dw and all(r['hbm_read_bytes'] > 0 and r['hbm_write_bytes'] > 0 for r in dw)
 
 
+def test_last_variant_record_is_host_side():
+    """ss_debug_last_variant: every kind answers without a GPU (an empty text before the first launch of that kind), the text is cut to the
+    caller's buffer and stays terminated, an unknown kind is an error with a message."""
+    lib = _capi.lib()
+    buf = C.create_string_buffer(b'x' * 63, 64)
+    for kind in (b'gemm', b'lstm_step_fwd', b'lstm_step_bwd'):
+        n = lib.ss_debug_last_variant(kind, buf, 64)
+        assert 0 <= n < 64 and len(buf.value) == n, (kind, n, buf.value)
+        assert lib.ss_debug_last_variant(kind, None, 0) == n
+        small = C.create_string_buffer(b'yy', 3)
+        assert lib.ss_debug_last_variant(kind, small, 1) == n and small.raw[0:1] == b'\0'
+        assert lib.ss_debug_last_variant(kind + b'_seen', buf, 64) >= 0
+    assert lib.ss_debug_last_variant(b'reset', None, 0) == 0
+    for kind in (b'gemm', b'lstm_step_fwd', b'lstm_step_bwd', b'gemm_seen', b'lstm_step_fwd_seen', b'lstm_step_bwd_seen'):
+        assert lib.ss_debug_last_variant(kind, buf, 64) == 0 and buf.value == b'', kind
+    assert lib.ss_debug_last_variant(b'nope', buf, 64) < 0 and b'unknown kind' in lib.ss_last_error()
+    assert lib.ss_debug_last_variant(None, buf, 64) < 0
+
+
 # ss_tune's keys.  Retired: settled schedule experiments whose default became the only behaviour; ss_tune refuses them like any unknown key.
 # Kept: every key of the product library (the -DSS_DIAG build adds lstm_mode and gemm_diag), with its default value.
 RETIRED_TUNE_KEYS = ('img', 'img_mask', 'bf16_img_mask', 'img_batch', 'img_cfg', 'img_dw_cfg', 'img_dw_wgs', 'dw_wgs', 'conv_want', 'conv_small_old',

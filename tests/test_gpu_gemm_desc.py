@@ -36,7 +36,7 @@ def E():
 
 class Tuned:
     """ss_tune values for the duration of a block, back at the defaults afterwards whatever happens."""
-    DEFAULTS = {'gemm_mode': 1, 'gemm_want': 1024}
+    DEFAULTS = {'gemm_mode': 1, 'gemm_want': 1024, 'gemm_ws': 0, 'gemm_tr': 1, 'gemm_pipe': 1}
 
     def __init__(self, E, **kv):
         self.E, self.kv = E, kv
@@ -133,24 +133,38 @@ def word(v):
 
 
 def launch(E, p, family, *, want=0, part=None, amax=(None, None), pre_scale=(None, None), imgs=(None, None), guard=False, sa=16.0, sb=16.0,
-           tag='', bits_of=None):
+           tag='', bits_of=None, ref=None):
     """One ss_op_gemm_desc launch of problem p judged against gemm_ref; returns the C buffer (numpy).  amax / pre_scale: python floats that
-    are put behind device words; imgs: scales to split the operand images with (None: no image)."""
+    are put behind device words; imgs: scales to split the operand images with (None: no image); guard: A, B, C, the images and the partial
+    slabs end where guard memory begins; ref: reference_of(...) of the same case, where a caller launches it more than once."""
     d = p.d
     fam, kt = judged_as(family, d)
-    ref = R.reference(d.replace(family=fam, kt=kt, sa=sa, sb=sb), p.a, p.b, p.c0, p.bias)
+    ref = ref or reference_of(p, family, sa, sb)
     if guard:
         ga, gb, gc = G.inp(torch.from_numpy(p.a), 'cuda', name='A'), G.inp(torch.from_numpy(p.b), 'cuda', name='B'), \
             G.out((p.c0.size,), 'cuda', fill=torch.from_numpy(p.c0), name='C')
         a, b, c = ga.t, gb.t, gc.t
     else:
         a, b, c = dev(p.a), dev(p.b), dev(p.c0)
-    ai = None if imgs[0] is None else dev(R.pack_image(np.concatenate([p.a, np.zeros(-p.a.size % 8, F32)]), imgs[0]).view(F32).reshape(-1))
-    bi = None if imgs[1] is None else dev(R.pack_image(np.concatenate([p.b, np.zeros(-p.b.size % 8, F32)]), imgs[1]).view(F32).reshape(-1))
+    ai = None if imgs[0] is None else torch.from_numpy(R.pack_image(np.concatenate([p.a, np.zeros(-p.a.size % 8, F32)]), imgs[0]).view(F32).reshape(-1))
+    bi = None if imgs[1] is None else torch.from_numpy(R.pack_image(np.concatenate([p.b, np.zeros(-p.b.size % 8, F32)]), imgs[1]).view(F32).reshape(-1))
     pt = None
-    if part:
-        pt = torch.full((d.batch * d.ksplit * d.M * d.N,), float('nan'), device='cuda')
+    extra = []
+    if guard:
+        gi = [None if x is None else G.inp(x, 'cuda', name=n) for x, n in ((ai, 'A image'), (bi, 'B image'))]
+        extra = [g for g in gi if g is not None]
+        ai, bi = (None if g is None else g.t for g in gi)
+        assert all(g.t.data_ptr() % 32 == 0 for g in extra)          # (an image off its 32-byte alignment would be refused, not read)
+        if part:
+            gp = G.out((d.batch * d.ksplit * d.M * d.N,), 'cuda', fill=float('nan'), name='partial slabs')
+            extra.append(gp)
+            pt = gp.t
+    else:
+        ai, bi = (None if x is None else x.cuda() for x in (ai, bi))
+        if part:
+            pt = torch.full((d.batch * d.ksplit * d.M * d.N,), float('nan'), device='cuda')
     with Tuned(E, gemm_mode=0 if family == 'f32' else 1, gemm_want=want if want > 0 else 1024):
+        E.reset_variants()                                  # a caller that reads ss_debug_last_variant afterwards reads THIS launch's record
         E.gemm_desc(a, d.A.tuple(), b, d.B.tuple(), c, (d.c_off, d.ldc, d.cstride), d.M, d.N, d.K, batch=d.batch, ta=d.ta, tb=d.tb, accumulate=d.accum,
                     bf16=family == 'bf16', f16x2=family == 'f16x2', bias=dev(p.bias), want=want, row_mask=d.row_mask, ksplit=d.ksplit,
                     amax_a=None if amax[0] is None else word(amax[0]), amax_b=None if amax[1] is None else word(amax[1]), a_img=ai, b_img=bi,
@@ -158,7 +172,7 @@ def launch(E, p, family, *, want=0, part=None, amax=(None, None), pre_scale=(Non
                     part=pt)
         torch.cuda.synchronize()
     if guard:
-        G.check_all([ga, gb, gc])
+        G.check_all([ga, gb, gc] + extra)
     out = c.cpu().numpy()
     fails, fig = R.judge(ref, p.c0, out)
     print(f'FIG {tag} family={family} judged_as={fam} want={want} sharp={fig["sharp"]:.3g} honest={fig["honest"]:.3g} untouched={fig["untouched"]}')
@@ -167,6 +181,12 @@ def launch(E, p, family, *, want=0, part=None, amax=(None, None), pre_scale=(Non
     if bits_of is not None:
         assert np.array_equal(out.view(np.uint32), bits_of.view(np.uint32)), (tag, 'bits differ')
     return out
+
+
+def reference_of(p, family, sa=16.0, sb=16.0):
+    """gemm_ref's expected values of problem p as launch_gemm's kernel of `family` computes them."""
+    fam, kt = judged_as(family, p.d)
+    return R.reference(p.d.replace(family=fam, kt=kt, sa=sa, sb=sb), p.a, p.b, p.c0, p.bias)
 
 
 def wants(M, N, batch=1, ksplit=1):

@@ -383,3 +383,16 @@ def test_bf16_bits_and_amax_bits():
     assert R.amax_bits(dg) == int(np.float32(7.0).view(np.uint32)) == int(torch.from_numpy(dg).abs().max().numpy().view(np.uint32))
     assert int(dg.max().view(np.uint32)) != R.amax_bits(dg)        # amax over signed values
     assert R.amax_bits(np.zeros((2, 3, 8), R.F32)) == 0
+
+
+def test_operands_of_per_step_families_ignore_nw_and_g():
+    """The per-step kernels multiply the fp32 words themselves whatever lstm_nw / lstm_g say; the persistent kernels' model is untouched by them."""
+    for H in (64, 128, 256, 512):
+        for nw in (4, 8, 16):
+            for g in (0, 1, 2, 4, 8, 16):
+                ops = R.operands_of(H, dict(persist=0, lstm_nw=nw, lstm_g=g), B=17)
+                assert (ops.mode, ops.tagged) == ('exact', False), (H, nw, g)
+    assert R.operands_of(128, dict(lstm_nw=4)).mode == 'exact'                      # no persistent kernel at H = 128
+    for H in (256, 512):
+        a, b = R.operands_of(H, dict(lstm_nw=4, lstm_g=2), B=5), R.operands_of(H, {}, B=5)
+        assert (a.mode, a.tagged) == (b.mode, b.tagged) == ('f16x2', True)
