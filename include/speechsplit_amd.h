@@ -19,7 +19,19 @@
  *     64..192 frames of the benchmark configurations (tests/test_gpu_frame_range.py);
  *   - the random-resampling draws of InterpLnr (model.py:392-393 rand(B*7)+0.5; :399-402 randint) are INPUTS:
  *     `scales` f32 and `len_seg` i32, one [B*7] row per InterpLnr call in call order.  Given equal draws the
- *     index path is bit-exact against the reference.
+ *     index path is bit-exact against the reference;
+ *   - what EVERY call that takes an engine refuses, in this order, each in a message that starts with the call's name, with nothing
+ *     enqueued and no event recorded on any stream: (1) a NULL engine; (2) the wrong kind of engine -- ss_g3_* need a Generator_3,
+ *     ss_g6_* a Generator_6, everything about parameters, gradients or the optimiser either of the two, ss_interp_* and the host
+ *     getters any kind; the message names the kind the call needs and the kind the engine is; (3) an engine that is not bound as far
+ *     as the call needs: the workspace, the gradient arena, and the Adam arenas wherever an optimiser step is part of the call
+ *     (pass SS_STEP_NO_ADAM to go without); (4) a member of a data-parallel group where the call has no data-parallel form.  Then the
+ *     call's own arguments -- NULL required pointers, B, T, flags outside the accepted set (every shape the planner would refuse is
+ *     refused here, before the call touches a stream) -- and last the status word (ss_status) for the calls that consult it.  Three
+ *     refusals come before (3): a bad argument of ss_set_grad_clip / ss_grad_norm / ss_grad_clip_stats, training != 0 with a length
+ *     array, and "backward without a preceding forward" (ss_*_backward*).  With a NULL engine: ss_destroy is a no-op; ss_status and
+ *     ss_grad_accum_count return 0 and ss_scratch_fallbacks -1 without a message; every other size or offset query returns -1 and
+ *     every pointer-returning call NULL, with the message; ss_check and ss_clear_abort refuse before they synchronise.
  */
 #ifndef SPEECHSPLIT_AMD_H
 #define SPEECHSPLIT_AMD_H

@@ -22,7 +22,14 @@ def hparams_struct(hp):
     return SSHparams(**{n: int(getattr(hp, n)) for n in HP_FIELDS})
 
 
-GEMM_DESC_PTRS = ('a', 'b', 'c', 'bias', 'amax_a', 'amax_b', 'a_pre', 'b_pre', 'a_pre_scale', 'b_pre_scale', 'part')
+# flags of ss_*_train_step, the data-parallel steps and ss_*_decode_backward (the header's SS_STEP_*)
+SS_STEP_NO_ADAM = 1
+SS_STEP_SPLIT_BACKWARD = 2
+SS_STEP_SPLIT_NO_JOIN = 4
+SS_STEP_ACCUMULATE = 8
+SS_STEP_BUCKET = 16
+
+GEMM_DESC_PTRS =('a', 'b', 'c', 'bias', 'amax_a', 'amax_b', 'a_pre', 'b_pre', 'a_pre_scale', 'b_pre_scale', 'part')
 GEMM_IMG_DESC_PTRS = ('a', 'b', 'c', 'bias', 'scale_a', 'scale_b', 'part', 'zeros')
 GEMM_DESC_LONGS = ('lda', 'a_bstride', 'a_segstride', 'ldb', 'b_bstride', 'b_segstride', 'ldc', 'cstride')
 GEMM_DESC_INTS = ('a_seglen', 'b_seglen', 'M', 'N', 'K', 'batch', 'flags', 'want', 'row_period', 'row_off', 'row_lo', 'row_hi', 'ksplit')

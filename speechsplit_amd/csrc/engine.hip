@@ -13,7 +13,7 @@
 #include <algorithm>
 #include <utility>
 #include <type_traits>
-#include <functional>
+#include <iterator>
 #include <cstring>
 #include <cstdio>
 
@@ -238,8 +238,8 @@ struct ss_engine {
     void* comm = nullptr;                  // ncclComm_t of ss_comm_init (RCCL, dlopen'd)
     int comm_rank = 0, comm_world = 1;
     // data-parallel step in flight: gradient ranges are all-reduced on comm_s as soon as their producers are through (dp_bucket).
-    // One step long, but kept on the engine: on the Generator_6 route dp_step's body is the PUBLIC ss_g6_train_step, whose signature
-    // cannot carry it, and dp_done / dp_rec below are filled under it and read after the body (dp_finish, ss_dp_profile_read)
+    // One step long, but kept on the engine: dp_done / dp_rec below are filled under it by the schedule functions (dp_bucket) and read
+    // after the step's backward (dp_finish, ss_dp_profile_read)
     bool dp_on = false;
     hipStream_t comm_s = nullptr;
     hipEvent_t ev_comm = nullptr;
@@ -2293,16 +2293,120 @@ int speaker_input_grad(ss_engine* e, float* dc, hipStream_t s) {
 // ================================================================================================ C ABI
 namespace {
 
-// lens (nullable): ragged batch -- frames t >= len[b] of the inputs are not read, the slabs get zeros there
-int stage_g3_inputs(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, int B, int T, hipStream_t s, const int* lens = nullptr) {
+// ---- the entry guard: what EVERY extern "C" call that takes an engine refuses, in this order, before its own argument checks:
+// a null engine, the wrong kind of engine, an engine that is not bound as far as the call needs, a member of a data-parallel group.
+// Then come the call's own checks, then the status word (entry_check) where the call consults it, and only then its stream scope (Own):
+// a refused call records no event and enqueues nothing.  Every message starts with the call's name.
+// Three places say one of their own refusals BEFORE the binding, because tests from before the guard pin that order on an unbound engine
+// (the call then opens with guard(kind) and runs guard(kind | binding) behind that one check): a bad argument of the three clipping
+// calls, training != 0 with a length array, and a backward with no forward -- whose text ("backward without a preceding forward") is
+// pinned verbatim, without the call's name.
+enum : unsigned {
+    G3 = 1, G6 = 2, GEN = G3 | G6, ANY = GEN | 4,      // kind: that generator, either generator, an InterpLnr-only engine as well
+    WS = 8, GRADS = WS | 16, ADAM = WS | 32,           // binding: the workspace; also the gradient arena; also both Adam arenas
+    NO_DP = 64,                                        // not on a member of a data-parallel group
+};
+int refuse(const char* call, const char* why) { return fail(std::string(call) + why); }
+int guard(const ss_engine* e, const char* call, unsigned need) {
+    if (!e) return refuse(call, ": null engine");
+    const unsigned kind = e->kind == SS_GENERATOR_3 ? G3 : e->kind == SS_GENERATOR_6 ? G6 : 4u;
+    if (!(need & kind))      // the kind the call needs, then the kind the engine was created as (known, not guessed)
+        return fail(std::string(call) + " on an engine that is not a " +
+                    ((need & ANY) == G3 ? "Generator_3" : (need & ANY) == G6 ? "Generator_6" : "Generator_3 or a Generator_6") + ": it is " +
+                    (kind == G3 ? "a Generator_3" : kind == G6 ? "a Generator_6" : "InterpLnr-only"));
+    if (((need & WS) && !e->ws) || ((need & GRADS & ~WS) && !e->G)) return refuse(call, ": engine is not bound (call ss_bind first)");
+    if ((need & ADAM & ~WS) && (!e->Mm || !e->Vv)) return refuse(call, ": Adam arenas are not bound (pass SS_STEP_NO_ADAM where the call takes flags)");
+    if ((need & NO_DP) && e->dp_on) return refuse(call, ": not available on a member of a data-parallel group");
+    return 0;
+}
+unsigned adam_unless(int flags) { return (flags & SS_STEP_NO_ADAM) ? 0u : ADAM; }
+
+// B and T of a call that plans the workspace -- everything geometry() would refuse, said under the call's name before anything is enqueued.
+// eval: an eval-mode forward (T up to SS_MAX_EVAL_FRAMES); everything that trains or differentiates keeps T <= max_frames.
+// replan: the plan is about to change for another reason (max_len_pad), so the current shape says nothing about what fits.
+int shape_check(const ss_engine* e, const char* call, int B, int T, bool eval, bool replan = false) {
+    if (B < 1 || B > e->maxB) return refuse(call, ": batch outside 1 .. max_batch given to ss_create");
+    if (eval && (T < 1 || T > SS_MAX_EVAL_FRAMES)) return refuse(call, ": T outside 1 .. SS_MAX_EVAL_FRAMES (8192)");
+    if (!eval && (T < 1 || T > e->maxT))
+        return refuse(call, ": T outside 1 .. max_frames (everything that trains or is differentiated keeps T <= max_frames <= 256, as every backward does; "
+                        "longer sequences run in eval mode only)");
+    if (e->kind != SS_INTERP_ONLY && (T % e->hp.freq || T % e->hp.freq_2 || T % e->hp.freq_3))
+        return refuse(call, ": T must be a multiple of the code down-sampling factors (model.py:87,223-227)");
+    if ((replan || B != e->curB || T != e->curT) && carve(*e, B, T) > e->ws_bytes)
+        return refuse(call, ": workspace too small for this batch / frames: grow it to ss_plan_bytes(B, T) with ss_set_workspace");
+    return 0;
+}
+
+// Everything that runs InterpLnr inside the model (train-mode forwards, the training steps) needs T == max_len_pad, within max_frames
+int train_len(const ss_engine* e, const char* call, int T, int max_len_pad) {
+    if (T > e->maxT) return refuse(call, ": training: T above max_frames; frames above max_frames (<= 256) run in eval mode only");
+    if (T != max_len_pad)
+        return refuse(call, ": training needs T == max_len_pad (InterpLnr pads to it, model.py:105,157,370); pass SS_STEP_BUCKET for a length-bucketed batch");
+    return 0;
+}
+// The max_len_pad a training STEP at T frames runs with: the one the engine was created with, or T itself under SS_STEP_BUCKET (a step
+// WITHOUT the flag runs with the created one again, whatever bucket came before: speechsplit_amd/solver.py mixes buckets with full-length
+// batches).  Refuses a T that is not that length; nothing is changed here (set_max_len_pad, once the call can no longer be refused).
+int step_len(const ss_engine* e, const char* call, int T, int flags, int* want) {
+    *want = (flags & SS_STEP_BUCKET) ? T : e->bound_max_len_pad;      // the batch's length bucket
+    if ((flags & SS_STEP_BUCKET) && (T < 8 || T % 8)) return refuse(call, ": SS_STEP_BUCKET: T must be a multiple of 8 within the engine's max_frames");
+    return train_len(e, call, T, *want);
+}
+void set_max_len_pad(ss_engine* e, int want) {
+    if (e->hp.max_len_pad == want) return;
+    e->hp.max_len_pad = want;
+    e->curB = e->curT = 0;         // InterpLnr plans are sized by max_len_pad: carve again
+}
+
+// ---- what differs between the two generators, as data (beside code_srcs, which does the same for the codes)
+// One dense caller input: argument `arg` of the call ([B][T][row], its columns from `col` on) is staged in `slab` and read by the layer-0
+// conv block `cb`, whose input gradient is therefore that argument's gradient.  In the order the staging copies are enqueued.
+struct InputSrc {
+    int arg;
+    float* slab;
+    int slab_ld, width, col, row;
+    const ConvBlk* cb;
+};
+int input_srcs(const ss_engine* e, InputSrc in[3]) {
     const ss_hparams& h = e->hp;
-    const int CI = h.dim_freq + h.dim_f0;      // 337
-    // split x_f0 [B,T,337] into the mel slab and the (channel-padded) f0 slab (model.py:196-197)
-    const CRows x = CRows::dense(x_f0, CI, T);
-    HIPCHK(copy_rows(x, Rows::slab(e->in_mel, h.dim_freq, T), B, T, h.dim_freq, s, lens));
-    HIPCHK(copy_rows(x.col(h.dim_freq), Rows::slab(e->in_f0, e->f0p, T), B, T, h.dim_f0, s, lens));
-    HIPCHK(copy_rows(CRows::dense(x_org, h.dim_freq, T), Rows::slab(e->org, h.dim_freq, T), B, T, h.dim_freq, s, lens));
-    HIPCHK(hipMemcpyAsync(e->emb, c_trg, (long)B * h.dim_spk_emb * 4, hipMemcpyDeviceToDevice, s));
+    if (e->kind == SS_GENERATOR_3) {      // (x_f0, x_org): x_f0 = [mel 80 | f0 one-hot 257] splits into the mel and the (channel-padded) f0 slab (model.py:196-197)
+        const int CI = h.dim_freq + h.dim_f0;
+        in[0] = {0, e->in_mel, h.dim_freq, h.dim_freq, 0, CI, &e->c1[0]};
+        in[1] = {0, e->in_f0, e->f0p, h.dim_f0, h.dim_freq, CI, &e->c2[0]};
+        in[2] = {1, e->org, h.dim_freq, h.dim_freq, 0, h.dim_freq, &e->ct};
+        return 3;
+    }
+    in[0] = {0, e->org, h.dim_freq, h.dim_freq, 0, h.dim_freq, &e->ct};      // (x_org, f0_trg): Encoder_t, Encoder_6's stack (model.py:123-140)
+    in[1] = {1, e->in_f0, e->f0p, h.dim_f0, 0, h.dim_f0, &e->c2[0]};
+    return 2;
+}
+bool has_speaker_row(const ss_engine* e) { return e->kind == SS_GENERATOR_3; }
+// first arena offset of the decoder + head parameters (ss_grad_split)
+long grad_split(const ss_engine* e) {
+    for (const auto& p : e->params)
+        if (p.name.rfind("decoder.", 0) == 0) return p.offset;
+    return e->arena;
+}
+
+// x[arg] (NULL: that argument is not part of this call, ss_g3_rhythm) into the slabs, then the speaker rows if given
+// lens (nullable): ragged batch -- frames t >= len[b] of the inputs are not read, the slabs get zeros there
+int stage_inputs(ss_engine* e, const float* const x[2], const float* c_trg, int B, int T, hipStream_t s, const int* lens = nullptr) {
+    InputSrc in[3];
+    const int n = input_srcs(e, in);
+    for (int i = 0; i < n; ++i)
+        if (x[in[i].arg])
+            HIPCHK(copy_rows(CRows::dense(x[in[i].arg], in[i].row, T).col(in[i].col), Rows::slab(in[i].slab, in[i].slab_ld, T), B, T, in[i].width, s, lens));
+    if (c_trg) HIPCHK(hipMemcpyAsync(e->emb, c_trg, (long)B * e->hp.dim_spk_emb * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// one BLSTM block's per-call weight preparation on its own (forward_branch_work batches the blocks of a whole forward)
+int prep_block(ss_engine* e, LstmBlk& lb, hipStream_t s) {
+    PrepTable tb;
+    tb.n = 0;
+    tb.img_bf16 = e->img16();
+    CHK(lstm_prep(e, lb, tb, s));
+    HIPCHK(prep_run(tb, s));
     return 0;
 }
 
@@ -2382,40 +2486,28 @@ void ss_destroy(ss_engine* e) {
         (void)hipDeviceSynchronize();
         (void)hipHostFree(e->sticky);
     }
-    for (auto& ev : e->prof_ev)
+    // every stream of the engine's own drains, then all events go, then the streams
+    const hipStream_t streams[] = {e->side, e->side2, e->side3, e->main_s};
+    for (hipStream_t st : streams)
+        if (st) (void)hipStreamSynchronize(st);
+    std::vector<hipEvent_t> events(e->prof_ev);
+    events.insert(events.end(), e->dp_ev_pool.begin(), e->dp_ev_pool.end());
+    events.insert(events.end(), {e->ev_comm, e->dp_bwd_end});
+    events.insert(events.end(), std::begin(e->ev), std::end(e->ev));
+    events.insert(events.end(), std::begin(e->ev_io), std::end(e->ev_io));
+    events.insert(events.end(), std::begin(e->ev_dec), std::end(e->ev_dec));
+    events.insert(events.end(), std::begin(e->ev_join), std::end(e->ev_join));
+    for (hipEvent_t ev : events)
         if (ev) (void)hipEventDestroy(ev);
-    if (e->side) {
-        (void)hipStreamSynchronize(e->side);
-        for (auto& ev : e->ev)
-            if (ev) (void)hipEventDestroy(ev);
-        (void)hipStreamDestroy(e->side);
-        if (e->ev_comm) (void)hipEventDestroy(e->ev_comm);
-        for (hipEvent_t ev : e->dp_ev_pool) (void)hipEventDestroy(ev);
-        if (e->dp_bwd_end) (void)hipEventDestroy(e->dp_bwd_end);
-        for (hipStream_t st : {e->side2, e->side3})
-            if (st) {
-                (void)hipStreamSynchronize(st);
-                (void)hipStreamDestroy(st);
-            }
-        if (e->main_s) {
-            (void)hipStreamSynchronize(e->main_s);
-            (void)hipStreamDestroy(e->main_s);
-        }
-        {
-            for (auto& ev : e->ev_io)
-                if (ev) (void)hipEventDestroy(ev);
-            for (auto& ev : e->ev_dec)
-                if (ev) (void)hipEventDestroy(ev);
-            for (auto& ev : e->ev_join)
-                if (ev) (void)hipEventDestroy(ev);
-        }
-    }
+    for (hipStream_t st : streams)
+        if (st) (void)hipStreamDestroy(st);
     delete e;
 }
 
-int ss_num_params(const ss_engine* e) { return (int)e->params.size(); }
+int ss_num_params(const ss_engine* e) { return guard(e, "ss_num_params", ANY) ? -1 : (int)e->params.size(); }
 
 int ss_param_info(const ss_engine* e, int i, char* name, int cap, long* offset, int* ndim, long shape[3]) {
+    CHK(guard(e, "ss_param_info", ANY));
     if (i < 0 || i >= (int)e->params.size()) return fail("ss_param_info: index out of range");
     const ParamInfo& p = e->params[i];
     if (name && cap > 0) {
@@ -2429,16 +2521,17 @@ int ss_param_info(const ss_engine* e, int i, char* name, int cap, long* offset, 
     return 0;
 }
 
-long ss_arena_numel(const ss_engine* e) { return e->arena; }
+long ss_arena_numel(const ss_engine* e) { return guard(e, "ss_arena_numel", ANY) ? -1 : e->arena; }
 
 // split-K scratch of the image GEMM behind the planned workspace (never zeroed, independent of the geometry): partial slabs have the
 // size of weight tensors, so 16 arenas' worth holds a step's launches at ksplit <= 8 with room to spare
 static long part_floats(const ss_engine* e) { return e->kind == SS_INTERP_ONLY ? 0 : 16 * ((e->arena + 63) & ~63L) + (32L << 20); }      // + 32 M floats: the small generator's deterministic mode, column sums, fused encoder weight gradients
 static long plan_bytes(const ss_engine* e) { return (carve(*e, e->maxB, e->maxT) + 255) & ~255L; }
-long ss_workspace_bytes(const ss_engine* e) { return plan_bytes(e) + part_floats(e) * 4; }
+static long workspace_bytes(const ss_engine* e) { return plan_bytes(e) + part_floats(e) * 4; }
+long ss_workspace_bytes(const ss_engine* e) { return guard(e, "ss_workspace_bytes", ANY) ? -1 : workspace_bytes(e); }
 
 long ss_plan_bytes(const ss_engine* e, int B, int T) {
-    if (!e) return fail("ss_plan_bytes: null engine");
+    CHK(guard(e, "ss_plan_bytes", ANY));
     if (B < 1 || B > e->maxB) return fail("ss_plan_bytes: batch outside 1 .. max_batch");
     if (T < 8 || T > SS_MAX_EVAL_FRAMES) return fail("ss_plan_bytes: frames outside 8 .. SS_MAX_EVAL_FRAMES");
     if (e->kind != SS_INTERP_ONLY && (T % e->hp.freq || T % e->hp.freq_2 || T % e->hp.freq_3))
@@ -2450,9 +2543,9 @@ static_assert(sizeof(AdamState) <= 256, "the Adam state is the workspace's first
 static_assert(sizeof(AdamState) <= CLIP_STATE_BYTE && CLIP_STATE_BYTE + sizeof(ClipState) <= 256 && CLIP_STATE_BYTE % 16 == 0,
               "the clip state shares those 256 bytes (ss_set_adam rewrites sizeof(AdamState) of them, no more)");
 int ss_set_workspace(ss_engine* e, void* ws_dev, long bytes, void* stream) {
-    if (!e || !e->ws) return fail("ss_set_workspace: engine is not bound (call ss_bind first)");
+    CHK(guard(e, "ss_set_workspace", ANY | WS));
     if (!ws_dev || ((uintptr_t)ws_dev & 255)) return fail("ss_set_workspace: the workspace must be 256-byte aligned");
-    if (bytes < ss_workspace_bytes(e)) return fail("ss_set_workspace: workspace smaller than ss_workspace_bytes()");
+    if (bytes < workspace_bytes(e)) return fail("ss_set_workspace: workspace smaller than ss_workspace_bytes()");
     // nothing may still run on the old workspace once the caller frees it: every stream the engine enqueues on drains first
     HIPCHK(hipStreamSynchronize(S(stream)));
     for (hipStream_t st : {e->main_s, e->side, e->side2, e->side3, e->comm_s})
@@ -2474,10 +2567,11 @@ int ss_set_workspace(ss_engine* e, void* ws_dev, long bytes, void* stream) {
 }
 
 int ss_bind(ss_engine* e, float* params, float* grads, float* m, float* v, void* workspace, long ws_bytes, void* stream) {
+    CHK(guard(e, "ss_bind", ANY));
     if (!workspace || (e->kind != SS_INTERP_ONLY && (!params || !grads))) return fail("ss_bind: null arena");
     if (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)m | (uintptr_t)v | (uintptr_t)workspace) & 255)
         return fail("ss_bind: arenas must be 256-byte aligned");
-    const long need = ss_workspace_bytes(e);
+    const long need = workspace_bytes(e);
     if (ws_bytes < need) return fail("ss_bind: workspace smaller than ss_workspace_bytes()");
     e->P = params;
     e->G = grads;
@@ -2537,7 +2631,7 @@ int ss_bind(ss_engine* e, float* params, float* grads, float* m, float* v, void*
 }
 
 int ss_set_adam(ss_engine* e, double lr, double b1, double b2, double eps, long step, void* stream) {
-    if (!e->ws) return fail("engine is not bound");
+    CHK(guard(e, "ss_set_adam", ANY | WS));
     AdamState st{};
     st.lr = lr;
     st.beta1 = b1;
@@ -2591,16 +2685,17 @@ static int adam_enqueue(ss_engine* e, const Backward& bw, float grad_scale, hipS
 }
 
 int ss_adam_step(ss_engine* e, float grad_scale, void* stream) {
+    CHK(guard(e, "ss_adam_step", GEN | GRADS | ADAM));
     CHK(entry_check(e));
     Own own(e, stream);
     return adam_enqueue(e, Backward{}, grad_scale, own.s);      // a stand-alone optimiser step always covers the whole arena
 }
 
 int ss_set_grad_clip(ss_engine* e, float max_norm, void* stream) {
-    if (!e) return fail("ss_set_grad_clip: null engine");
+    // (the three clip calls say a bad argument before a missing binding: tests/test_capi_grad_clip.py pins that order)
+    CHK(guard(e, "ss_set_grad_clip", GEN));      // (an InterpLnr-only engine has no gradient arena)
     if (!(max_norm >= 0.0f)) return fail("ss_set_grad_clip: max_norm must be 0 (off), positive or +inf; negative and NaN are refused");
-    if (e->kind == SS_INTERP_ONLY) return fail("ss_set_grad_clip: an InterpLnr-only engine has no gradient arena");
-    if (!e->ws || !e->G) return fail("ss_set_grad_clip: engine is not bound (call ss_bind first)");
+    CHK(guard(e, "ss_set_grad_clip", GEN | GRADS));
     if (!e->segs_ok) return fail("ss_set_grad_clip: the parameter table has more runs than GRAD_SEG_MAX");
     Own own(e, stream);
     HIPCHK(hipMemsetAsync(e->clip, 0, sizeof(ClipState), own.s));      // norm, coefficient and both counters start again
@@ -2609,8 +2704,10 @@ int ss_set_grad_clip(ss_engine* e, float max_norm, void* stream) {
 }
 
 int ss_grad_norm(ss_engine* e, float grad_scale, float* norm_dev, void* stream) {
-    if (!e || !norm_dev) return fail("ss_grad_norm: null pointer");
-    if (e->kind == SS_INTERP_ONLY || !e->ws || !e->G) return fail("ss_grad_norm: engine is not bound (call ss_bind first)");
+    CHK(guard(e, "ss_grad_norm", GEN));
+    if (!norm_dev) return fail("ss_grad_norm: null pointer");
+    CHK(guard(e, "ss_grad_norm", GEN | GRADS));
+    if (!e->segs_ok) return fail("ss_grad_norm: the parameter table has more runs than GRAD_SEG_MAX");
     Own own(e, stream);
     int n = 0;
     CHK(grad_norm_partials(e, false, own.s, &n));
@@ -2622,15 +2719,16 @@ int ss_grad_norm(ss_engine* e, float grad_scale, float* norm_dev, void* stream) 
 }
 
 int ss_grad_clip_stats(ss_engine* e, float* out4_dev, void* stream) {
-    if (!e || !out4_dev) return fail("ss_grad_clip_stats: null pointer");
-    if (e->kind == SS_INTERP_ONLY || !e->ws) return fail("ss_grad_clip_stats: engine is not bound (call ss_bind first)");
+    CHK(guard(e, "ss_grad_clip_stats", GEN));
+    if (!out4_dev) return fail("ss_grad_clip_stats: null pointer");
+    CHK(guard(e, "ss_grad_clip_stats", GEN | WS));
     Own own(e, stream);
     HIPCHK(hipMemcpyAsync(out4_dev, e->clip, sizeof(ClipState), hipMemcpyDeviceToDevice, own.s));
     return 0;
 }
 
 int ss_zero_grads(ss_engine* e, void* stream) {
-    if (!e->G) return fail("engine is not bound");
+    CHK(guard(e, "ss_zero_grads", GEN | GRADS));
     Own own(e, stream);
     HIPCHK(hipMemsetAsync(e->G, 0, e->arena * 4, own.s));
     e->accum_count = 0;
@@ -2639,89 +2737,112 @@ int ss_zero_grads(ss_engine* e, void* stream) {
 
 long ss_grad_accum_count(const ss_engine* e) { return e ? e->accum_count : 0; }
 
-// every backward: a forward to differentiate, and one that ran within max_frames (nothing is enqueued otherwise)
-static int backward_check(const ss_engine* e) {
-    if (!e->fwd.have) return fail("backward without a preceding forward");
+// every backward: whether the forward that is there (the caller has looked at fwd.have) can be differentiated by this call
+static int backward_check(const ss_engine* e, const char* call) {
     if (e->fwd.decode)
-        return fail("backward: the last forward was a decode (ss_*_decode_train), which ran no encoder: only ss_*_decode_backward can follow it");
+        return refuse(call, ": the last forward was a decode (ss_*_decode_train), which ran no encoder: only ss_*_decode_backward can follow it");
     if (e->curT > e->maxT)
-        return fail("backward: the last forward ran T above max_frames, which is eval-only (GroupNorm backward, training and input "
-                    "gradients keep T <= max_frames <= 256)");
+        return refuse(call, ": the last forward ran T above max_frames, which is eval-only (GroupNorm backward, training and input "
+                        "gradients keep T <= max_frames <= 256)");
     if (e->fwd.ragged)
-        return fail("backward: the last forward ran over per-row lengths (a ragged batch), which is eval-only (no gradient exists for it)");
+        return refuse(call, ": the last forward ran over per-row lengths (a ragged batch), which is eval-only (no gradient exists for it)");
     return 0;
 }
 
-static int g3_forward(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, const float* scales, const int* len_seg,
-                      const int* lens, int B, int T, int training, float* out, void* stream) {
-    CHK(entry_check(e));
-    Own own(e, stream);
-    hipStream_t s = own.s;
-    if (training && T > e->maxT) return fail("train-mode forward: T above max_frames; longer sequences run in eval mode only");
-    if (training && T != e->hp.max_len_pad)
-        return fail("train-mode forward needs T == max_len_pad (InterpLnr pads to max_len_pad, model.py:370)");
-    if (training && (!scales || !len_seg)) return fail("train-mode forward needs the InterpLnr draws");
+// ---- one body per ss_g3_* / ss_g6_* pair: the public functions pack their pointers in the order of input_srcs' `arg` and name themselves
+// the forward on stream s, behind every refusal (the Generator_6 training step runs it too)
+static int forward_on(ss_engine* e, const float* const x[2], const float* c_trg, const float* scales, const int* len_seg, const int* lens, int B, int T,
+                      bool training, float* out, hipStream_t s) {
     CHK(geometry(e, B, T, s, !training));
-    CHK(stage_g3_inputs(e, x_f0, x_org, c_trg, B, T, s, lens));
-    CHK(forward_core(e, training != 0, scales, len_seg, 0, s, {}, lens));
+    CHK(stage_inputs(e, x, c_trg, B, T, s, lens));
+    CHK(forward_core(e, training, scales, len_seg, 0, s, {}, lens));
     if (out) CHK(export_out(e, out, B, T, s, lens));
     return 0;
 }
-
-int ss_g3_forward(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, const float* scales,
-                  const int* len_seg, int B, int T, int training, float* out, void* stream) {
-    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_forward on a Generator_6 engine");
-    return g3_forward(e, x_f0, x_org, c_trg, scales, len_seg, nullptr, B, T, training, out, stream);
+// behind the guard a forward refuses: training != 0 with lengths, without the draws or at a T that is not max_len_pad
+static int forward_call(ss_engine* e, const char* call, unsigned kind, const float* const x[2], const float* c_trg, const float* scales,
+                        const int* len_seg, const int* lens, int B, int T, int training, float* out, void* stream) {
+    CHK(guard(e, call, kind));
+    if (training && lens) return refuse(call, ": ragged batches are eval-only (training != 0 with a length array)");
+    CHK(guard(e, call, kind | WS));
+    if (!x[0] || !x[1] || (has_speaker_row(e) && !c_trg)) return refuse(call, ": null pointer (every input is required)");
+    if (training) CHK(train_len(e, call, T, e->hp.max_len_pad));
+    if (training && (!scales || !len_seg)) return refuse(call, ": train-mode forward needs the InterpLnr draws");
+    CHK(shape_check(e, call, B, T, !training));
+    CHK(entry_check(e));
+    Own own(e, stream);
+    return forward_on(e, x, c_trg, scales, len_seg, lens, B, T, training != 0, out, own.s);
 }
 
-int ss_g3_forward_ragged(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, const int* len_dev, int B, int T, int training,
-                         float* out, void* stream) {
-    if (!e) return fail("ss_g3_forward_ragged: null engine");
-    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_forward_ragged on an engine that is not a Generator_3");
-    if (training && len_dev) return fail("ss_g3_forward_ragged: ragged batches are eval-only (training != 0 with a length array)");
-    return g3_forward(e, x_f0, x_org, c_trg, nullptr, nullptr, len_dev, B, T, training, out, stream);
-}
-
-int ss_g3_backward(ss_engine* e, const float* d_out, void* stream) {
-    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_backward on a Generator_6 engine");
-    CHK(backward_check(e));
+// d_x (nullable as a whole: the plain backward; each entry nullable): the caller's input-gradient buffers, one per forward argument
+static int backward_call(ss_engine* e, const char* call, unsigned kind, const float* d_out, float* const* d_x, float* dc_trg, void* stream) {
+    CHK(guard(e, call, kind));
+    if (!e->fwd.have) return fail("backward without a preceding forward");
+    CHK(guard(e, call, kind | GRADS));
+    CHK(backward_check(e, call));
+    if (!d_out) return refuse(call, ": null pointer (d_out is required)");
     Own own(e, stream);
     hipStream_t s = own.s;
-    CHK(import_dout(e, d_out, e->curB, e->curT, s));
     Backward bw;
-    return backward_core(e, bw, s);
-}
-
-int ss_g3_backward_inputs(ss_engine* e, const float* d_out, float* dx_f0, float* dx_org, float* dc_trg, void* stream) {
-    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_backward_inputs on a Generator_6 engine");
-    CHK(backward_check(e));
-    Own own(e, stream);
-    hipStream_t s = own.s;
-    const ss_hparams& h = e->hp;
-    const int CI = h.dim_freq + h.dim_f0;
-    Backward bw;
-    bw.in_grad[0] = {&e->c1[0], dx_f0, CI};                                       // x_f0 = [mel 80 | f0 one-hot 257]: the content stack's input ...
-    bw.in_grad[1] = {&e->c2[0], dx_f0 ? dx_f0 + h.dim_freq : nullptr, CI};        // ... and the pitch stack's, side by side in one row
-    bw.in_grad[2] = {&e->ct, dx_org, h.dim_freq};
+    InputSrc in[3];
+    const int n = d_x ? input_srcs(e, in) : 0;
+    for (int i = 0; i < n; ++i) bw.in_grad[i] = {in[i].cb, d_x[in[i].arg] ? d_x[in[i].arg] + in[i].col : nullptr, in[i].row};
     CHK(import_dout(e, d_out, e->curB, e->curT, s));
     CHK(backward_core(e, bw, s));
     if (dc_trg) CHK(speaker_input_grad(e, dc_trg, s));
     return 0;
 }
 
-static int g3_rhythm(ss_engine* e, const float* x_org, const int* lens, int B, int T, float* codes, void* stream) {
+int ss_g3_forward(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, const float* scales,
+                  const int* len_seg, int B, int T, int training, float* out, void* stream) {
+    const float* const x[2] = {x_f0, x_org};
+    return forward_call(e, "ss_g3_forward", G3, x, c_trg, scales, len_seg, nullptr, B, T, training, out, stream);
+}
+
+int ss_g3_forward_ragged(ss_engine* e, const float* x_f0, const float* x_org, const float* c_trg, const int* len_dev, int B, int T, int training,
+                         float* out, void* stream) {
+    const float* const x[2] = {x_f0, x_org};
+    return forward_call(e, "ss_g3_forward_ragged", G3, x, c_trg, nullptr, nullptr, len_dev, B, T, training, out, stream);
+}
+
+int ss_g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, const float* scales, const int* len_seg, int B,
+                  int T, int training, float* out, void* stream) {
+    const float* const x[2] = {x_org, f0_trg};
+    return forward_call(e, "ss_g6_forward", G6, x, nullptr, scales, len_seg, nullptr, B, T, training, out, stream);
+}
+
+int ss_g6_forward_ragged(ss_engine* e, const float* x_org, const float* f0_trg, const int* len_dev, int B, int T, int training, float* out,
+                         void* stream) {
+    const float* const x[2] = {x_org, f0_trg};
+    return forward_call(e, "ss_g6_forward_ragged", G6, x, nullptr, nullptr, nullptr, len_dev, B, T, training, out, stream);
+}
+
+int ss_g3_backward(ss_engine* e, const float* d_out, void* stream) { return backward_call(e, "ss_g3_backward", G3, d_out, nullptr, nullptr, stream); }
+int ss_g6_backward(ss_engine* e, const float* d_out, void* stream) { return backward_call(e, "ss_g6_backward", G6, d_out, nullptr, nullptr, stream); }
+
+int ss_g3_backward_inputs(ss_engine* e, const float* d_out, float* dx_f0, float* dx_org, float* dc_trg, void* stream) {
+    float* const d_x[2] = {dx_f0, dx_org};
+    return backward_call(e, "ss_g3_backward_inputs", G3, d_out, d_x, dc_trg, stream);
+}
+
+int ss_g6_backward_inputs(ss_engine* e, const float* d_out, float* dx_org, float* df0_trg, void* stream) {
+    float* const d_x[2] = {dx_org, df0_trg};
+    return backward_call(e, "ss_g6_backward_inputs", G6, d_out, d_x, nullptr, stream);
+}
+
+static int rhythm_call(ss_engine* e, const char* call, const float* x_org, const int* lens, int B, int T, float* codes, void* stream) {
+    CHK(guard(e, call, G3 | WS));
+    if (!x_org || !codes) return refuse(call, ": null pointer (x_org and codes are required)");
+    CHK(shape_check(e, call, B, T, true));
     Own own(e, stream);
     hipStream_t s = own.s;
     CHK(geometry(e, B, T, s, true));
     e->part_off = 0;           // step scratch (long-sequence GroupNorm): as at the start of forward_core
     const ss_hparams& h = e->hp;
-    HIPCHK(copy_rows(CRows::dense(x_org, h.dim_freq, T), Rows::slab(e->org, h.dim_freq, T), B, T, h.dim_freq, s, lens));
+    const float* const x[2] = {nullptr, x_org};           // Encoder_t's input alone
+    CHK(stage_inputs(e, x, nullptr, B, T, s, lens));
     CHK(conv_pack_all(e, e->ct, s));
-    PrepTable tb;
-    tb.n = 0;
-    tb.img_bf16 = e->img16();
-    CHK(lstm_prep(e, e->lt, tb, s));
-    HIPCHK(prep_run(tb, s));
+    CHK(prep_block(e, e->lt, s));
     CHK(act_scales_all(e, s));
     CHK(conv_block_fwd(e, e->ct, Slab{e->org, h.dim_freq}, enc_t_out(e), s, {.lens = lens}));
     CHK(lstm_fwd(e, e->lt, enc_t_out(e), s, lens));
@@ -2744,30 +2865,15 @@ static int g3_rhythm(ss_engine* e, const float* x_org, const int* lens, int B, i
 }
 
 int ss_g3_rhythm(ss_engine* e, const float* x_org, int B, int T, float* codes, void* stream) {
-    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_rhythm on a Generator_6 engine");
-    return g3_rhythm(e, x_org, nullptr, B, T, codes, stream);
+    return rhythm_call(e, "ss_g3_rhythm", x_org, nullptr, B, T, codes, stream);
 }
 
 int ss_g3_rhythm_ragged(ss_engine* e, const float* x_org, const int* len_dev, int B, int T, float* codes, void* stream) {
-    if (!e) return fail("ss_g3_rhythm_ragged: null engine");
-    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_rhythm_ragged on an engine that is not a Generator_3");
-    return g3_rhythm(e, x_org, len_dev, B, T, codes, stream);
+    return rhythm_call(e, "ss_g3_rhythm_ragged", x_org, len_dev, B, T, codes, stream);
 }
 
-// ---- codes: the encoders alone, and the decoder on codes the caller supplies (eval mode only; see the header's "codes" section) ----
-// what every one of the four refuses before anything is enqueued; `call` names the entry point in the message
-static int codes_check(const ss_engine* e, int kind, const char* call, bool ptrs_ok, int B, int T) {
-    const std::string c(call);
-    if (!e) return fail(c + ": null engine");
-    if (e->kind != kind) return fail(c + " on an engine that is not a " + (kind == SS_GENERATOR_3 ? "Generator_3" : "Generator_6"));
-    if (!e->ws) return fail(c + ": engine is not bound (call ss_bind first)");
-    if (!ptrs_ok) return fail(c + ": null pointer (every input is required, and at least one output)");
-    if (B < 1 || B > e->maxB) return fail(c + ": batch outside 1 .. max_batch given to ss_create");
-    if (T < 1 || T > SS_MAX_EVAL_FRAMES) return fail(c + ": T outside 1 .. SS_MAX_EVAL_FRAMES (8192)");
-    if (T % e->hp.freq || T % e->hp.freq_2 || T % e->hp.freq_3) return fail(c + ": T must be a multiple of the code down-sampling factors (model.py:87,223-227)");
-    if (carve(*e, B, T) > e->ws_bytes) return fail(c + ": workspace too small for this batch / frames: grow it to ss_plan_bytes(B, T) with ss_set_workspace");
-    return 0;
-}
+
+// ---- codes: the encoders alone, and the decoder on codes the caller supplies (see the header's "codes" section) ----
 
 // after the encoder part: every requested code (NULL: not wanted) in one launch, in the column order of code_srcs
 static int export_requested_codes(ss_engine* e, float* const* codes, int B, int T, hipStream_t s, const int* lens) {
@@ -2781,114 +2887,54 @@ static int export_requested_codes(ss_engine* e, float* const* codes, int B, int 
     return 0;
 }
 
-// the decoder on the caller's codes: its weight prep and the parameter guard as forward_branch_work runs them, then forward_decoder
-static int decode_codes(ss_engine* e, const CallerCodes& cc, const int* lens, int B, int T, float* out, void* stream) {
+static int encode_call(ss_engine* e, const char* call, unsigned kind, const float* const x[2], const int* lens, int B, int T, float* const codes[3],
+                       void* stream) {
+    CHK(guard(e, call, kind | WS));
+    if (!x[0] || !x[1] || !(codes[0] || codes[1] || codes[2]))
+        return refuse(call, ": null pointer (every input is required, and at least one output)");
+    CHK(shape_check(e, call, B, T, true));
     CHK(entry_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;
     CHK(geometry(e, B, T, s, true));
-    e->part_off = 0;
-    e->fwd.have = false;           // the decoder's slabs are overwritten: whatever forward ran before has no backward any more
-    PrepTable tb;
-    tb.n = 0;
-    tb.img_bf16 = e->img16();
-    CHK(lstm_prep(e, e->ld, tb, s));
-    HIPCHK(prep_run(tb, s));
+    e->fwd.have = false;
+    CHK(stage_inputs(e, x, nullptr, B, T, s, lens));          // without the speaker rows
+    CHK(forward_encoders(e, false, nullptr, nullptr, 0, s, {}, lens, false));
+    return export_requested_codes(e, codes, B, T, s, lens);
+}
+
+// the decoder's own weight preparation and the parameter guard, as forward_branch_work runs them inside a whole forward
+static int decoder_prep(ss_engine* e, hipStream_t s) {
+    CHK(prep_block(e, e->ld, s));
     if ((g_fwd_f16x2 || g_bwd_f16x2) && e->precision == SS_PRECISION_F32 && e->sticky) HIPCHK(param_guard(e->P, e->arena, 2048.0f, e->sticky, s));
+    return 0;
+}
+
+// The decoder on the caller's codes, on stream s.  train: a dense batch within max_frames, recorded for a backward that stops at the codes
+// (ss_*_decode_backward); otherwise eval mode, nothing left to differentiate.  Either way the decoder's slabs are overwritten: whatever
+// forward ran before has no backward any more.
+static int decode_on(ss_engine* e, const CallerCodes& cc, const int* lens, int B, int T, bool train, hipStream_t s) {
+    CHK(geometry(e, B, T, s, !train));
+    e->part_off = 0;
+    if (train) e->fwd = {};
+    else e->fwd.have = false;
+    CHK(decoder_prep(e, s));
     CHK(forward_decoder(e, s, lens, &cc));
-    CHK(export_out(e, out, B, T, s, lens));
+    if (train) e->fwd.decode = e->fwd.have = true;
     return 0;
 }
 
-int ss_g3_encode(ss_engine* e, const float* x_f0, const float* x_org, const int* len_dev, int B, int T, float* codes_x, float* codes_r,
-                 float* codes_f0, void* stream) {
-    CHK(codes_check(e, SS_GENERATOR_3, "ss_g3_encode", x_f0 && x_org && (codes_x || codes_r || codes_f0), B, T));
+// ss_*_decode (train = false) and the differentiable ss_*_decode_train (see the header's "differentiable decode" section)
+static int decode_call(ss_engine* e, const char* call, unsigned kind, const CallerCodes& cc, const int* lens, int B, int T, bool train, float* out,
+                       void* stream) {
+    CHK(guard(e, call, kind | WS));
+    if (!cc.codes[0] || !cc.codes[1] || (kind == G3 && (!cc.codes[2] || !cc.c_trg)) || !out)
+        return refuse(call, ": null pointer (every input and the output are required)");
+    CHK(shape_check(e, call, B, T, !train));
     CHK(entry_check(e));
     Own own(e, stream);
-    hipStream_t s = own.s;
-    CHK(geometry(e, B, T, s, true));
-    e->fwd.have = false;
-    const ss_hparams& h = e->hp;
-    const CRows x = CRows::dense(x_f0, h.dim_freq + h.dim_f0, T);          // as stage_g3_inputs, without the speaker rows
-    HIPCHK(copy_rows(x, Rows::slab(e->in_mel, h.dim_freq, T), B, T, h.dim_freq, s, len_dev));
-    HIPCHK(copy_rows(x.col(h.dim_freq), Rows::slab(e->in_f0, e->f0p, T), B, T, h.dim_f0, s, len_dev));
-    HIPCHK(copy_rows(CRows::dense(x_org, h.dim_freq, T), Rows::slab(e->org, h.dim_freq, T), B, T, h.dim_freq, s, len_dev));
-    CHK(forward_encoders(e, false, nullptr, nullptr, 0, s, {}, len_dev, false));
-    float* const codes[3] = {codes_x, codes_r, codes_f0};
-    return export_requested_codes(e, codes, B, T, s, len_dev);
-}
-
-int ss_g3_decode(ss_engine* e, const float* codes_x, const float* codes_r, const float* codes_f0, const float* c_trg, const int* len_dev, int B,
-                 int T, float* out, void* stream) {
-    CHK(codes_check(e, SS_GENERATOR_3, "ss_g3_decode", codes_x && codes_r && codes_f0 && c_trg && out, B, T));
-    return decode_codes(e, CallerCodes{{codes_x, codes_r, codes_f0}, c_trg}, len_dev, B, T, out, stream);
-}
-
-int ss_g6_encode(ss_engine* e, const float* x_org, const float* f0_trg, const int* len_dev, int B, int T, float* codes_r, float* codes_f0,
-                 void* stream) {
-    CHK(codes_check(e, SS_GENERATOR_6, "ss_g6_encode", x_org && f0_trg && (codes_r || codes_f0), B, T));
-    CHK(entry_check(e));
-    Own own(e, stream);
-    hipStream_t s = own.s;
-    CHK(geometry(e, B, T, s, true));
-    e->fwd.have = false;
-    const ss_hparams& h = e->hp;
-    HIPCHK(copy_rows(CRows::dense(x_org, h.dim_freq, T), Rows::slab(e->org, h.dim_freq, T), B, T, h.dim_freq, s, len_dev));
-    HIPCHK(copy_rows(CRows::dense(f0_trg, h.dim_f0, T), Rows::slab(e->in_f0, e->f0p, T), B, T, h.dim_f0, s, len_dev));
-    CHK(forward_encoders(e, false, nullptr, nullptr, 0, s, {}, len_dev, false));
-    float* const codes[3] = {codes_r, codes_f0, nullptr};
-    return export_requested_codes(e, codes, B, T, s, len_dev);
-}
-
-int ss_g6_decode(ss_engine* e, const float* codes_r, const float* codes_f0, const int* len_dev, int B, int T, float* out, void* stream) {
-    CHK(codes_check(e, SS_GENERATOR_6, "ss_g6_decode", codes_r && codes_f0 && out, B, T));
-    return decode_codes(e, CallerCodes{{codes_r, codes_f0, nullptr}, nullptr}, len_dev, B, T, out, stream);
-}
-
-// ---- differentiable decode: the decoder on caller codes, recorded for a backward that stops at the codes (see the header's "codes" section) ----
-// what ss_*_decode_train and ss_g3_decode_train_step refuse before anything is enqueued: codes_check under the rules of everything that differentiates
-static int decode_train_check(const ss_engine* e, int kind, const char* call, bool ptrs_ok, int B, int T) {
-    const std::string c(call);
-    if (!e) return fail(c + ": null engine");
-    if (e->kind != kind) return fail(c + " on an engine that is not a " + (kind == SS_GENERATOR_3 ? "Generator_3" : "Generator_6"));
-    if (!e->ws) return fail(c + ": engine is not bound (call ss_bind first)");
-    if (!ptrs_ok) return fail(c + ": null pointer (every input and output named as required is required)");
-    if (B < 1 || B > e->maxB) return fail(c + ": batch outside 1 .. max_batch given to ss_create");
-    if (T < 1 || T > e->maxT) return fail(c + ": T outside 1 .. max_frames (a decode that is differentiated keeps T <= max_frames, as every backward does)");
-    if (T % e->hp.freq || T % e->hp.freq_2 || T % e->hp.freq_3) return fail(c + ": T must be a multiple of the code down-sampling factors (model.py:87,223-227)");
-    if (carve(*e, B, T) > e->ws_bytes) return fail(c + ": workspace too small for this batch / frames: grow it to ss_plan_bytes(B, T) with ss_set_workspace");
-    return 0;
-}
-
-// decode_codes on a dense batch, without the export, leaving the state a decoder backward needs
-static int decode_train_body(ss_engine* e, const CallerCodes& cc, int B, int T, hipStream_t s) {
-    CHK(geometry(e, B, T, s));
-    e->part_off = 0;
-    e->fwd = {};                   // the decoder's slabs are overwritten: whatever forward ran before has no backward any more
-    PrepTable tb;
-    tb.n = 0;
-    tb.img_bf16 = e->img16();
-    CHK(lstm_prep(e, e->ld, tb, s));
-    HIPCHK(prep_run(tb, s));
-    if ((g_fwd_f16x2 || g_bwd_f16x2) && e->precision == SS_PRECISION_F32 && e->sticky) HIPCHK(param_guard(e->P, e->arena, 2048.0f, e->sticky, s));
-    CHK(forward_decoder(e, s, nullptr, &cc));
-    e->fwd.decode = true;
-    e->fwd.have = true;
-    return 0;
-}
-
-// what ss_*_decode_backward refuses before anything is enqueued
-static int decode_backward_check(const ss_engine* e, int kind, const char* call, const float* d_out, int flags) {
-    const std::string c(call);
-    if (!e) return fail(c + ": null engine");
-    if (e->kind != kind) return fail(c + " on an engine that is not a " + (kind == SS_GENERATOR_3 ? "Generator_3" : "Generator_6"));
-    if (!e->ws || !e->G) return fail(c + ": engine is not bound (call ss_bind first)");
-    if (!d_out) return fail(c + ": null pointer (d_out is required)");
-    if (flags & ~SS_STEP_ACCUMULATE) return fail(c + ": flags other than SS_STEP_ACCUMULATE");
-    if (e->dp_on) return fail(c + ": not available on a member of a data-parallel group");
-    if (!e->fwd.have) return fail(c + " without a preceding ss_*_decode_train (a plain ss_*_decode leaves nothing to differentiate)");
-    if (!e->fwd.decode) return fail(c + ": the last forward was a full forward, not a decode: ss_*_backward* differentiates it");
-    return 0;
+    CHK(decode_on(e, cc, lens, B, T, train, own.s));
+    return export_out(e, out, B, T, own.s, lens);
 }
 
 // The decoder's backward alone, behind d_out_slab: parameter gradients of [ss_grad_split, arena) and the status slot, then whatever of the
@@ -2911,7 +2957,7 @@ static int decode_backward_body(ss_engine* e, float* const* d_codes, float* dc_t
 // Adam on [ss_grad_split, arena) alone: the early range's update of the fused step (early_update), with the whole arena's norm when clipping
 static int adam_decoder_enqueue(ss_engine* e, float grad_scale, hipStream_t s) {
     if (!e->ws || !e->Mm || !e->Vv) return fail("ss_adam_step_decoder: Adam arenas are not bound");
-    const long from = ss_grad_split(e);
+    const long from = grad_split(e);
     if (from % 4 || from >= e->arena) return fail("ss_adam_step_decoder: internal: the decoder range does not start on a multiple of 4 floats");
     if (e->clip_max > 0.0f) {
         int n = 0;
@@ -2927,44 +2973,64 @@ static int adam_decoder_enqueue(ss_engine* e, float grad_scale, hipStream_t s) {
     return 0;
 }
 
+// what ss_*_decode_backward refuses before anything is enqueued, then the backward behind the caller's d_out
+static int decode_backward_call(ss_engine* e, const char* call, unsigned kind, const float* d_out, float* const d_codes[3], float* dc_trg, int flags,
+                                void* stream) {
+    CHK(guard(e, call, kind | GRADS | NO_DP));
+    if (!d_out) return refuse(call, ": null pointer (d_out is required)");
+    if (flags & ~SS_STEP_ACCUMULATE) return refuse(call, ": flags other than SS_STEP_ACCUMULATE");
+    if (!e->fwd.have) return refuse(call, " without a preceding ss_*_decode_train (a plain ss_*_decode leaves nothing to differentiate)");
+    if (!e->fwd.decode) return refuse(call, ": the last forward was a full forward, not a decode: ss_*_backward* differentiates it");
+    Own own(e, stream);
+    CHK(import_dout(e, d_out, e->curB, e->curT, own.s));
+    return decode_backward_body(e, d_codes, dc_trg, (flags & SS_STEP_ACCUMULATE) != 0, own.s);
+}
+
+int ss_g3_encode(ss_engine* e, const float* x_f0, const float* x_org, const int* len_dev, int B, int T, float* codes_x, float* codes_r,
+                 float* codes_f0, void* stream) {
+    const float* const x[2] = {x_f0, x_org};
+    float* const codes[3] = {codes_x, codes_r, codes_f0};
+    return encode_call(e, "ss_g3_encode", G3, x, len_dev, B, T, codes, stream);
+}
+
+int ss_g6_encode(ss_engine* e, const float* x_org, const float* f0_trg, const int* len_dev, int B, int T, float* codes_r, float* codes_f0,
+                 void* stream) {
+    const float* const x[2] = {x_org, f0_trg};
+    float* const codes[3] = {codes_r, codes_f0, nullptr};
+    return encode_call(e, "ss_g6_encode", G6, x, len_dev, B, T, codes, stream);
+}
+
+int ss_g3_decode(ss_engine* e, const float* codes_x, const float* codes_r, const float* codes_f0, const float* c_trg, const int* len_dev, int B,
+                 int T, float* out, void* stream) {
+    return decode_call(e, "ss_g3_decode", G3, CallerCodes{{codes_x, codes_r, codes_f0}, c_trg}, len_dev, B, T, false, out, stream);
+}
+
+int ss_g6_decode(ss_engine* e, const float* codes_r, const float* codes_f0, const int* len_dev, int B, int T, float* out, void* stream) {
+    return decode_call(e, "ss_g6_decode", G6, CallerCodes{{codes_r, codes_f0, nullptr}, nullptr}, len_dev, B, T, false, out, stream);
+}
+
 int ss_g3_decode_train(ss_engine* e, const float* codes_x, const float* codes_r, const float* codes_f0, const float* c_trg, int B, int T, float* out,
                        void* stream) {
-    CHK(decode_train_check(e, SS_GENERATOR_3, "ss_g3_decode_train", codes_x && codes_r && codes_f0 && c_trg && out, B, T));
-    CHK(entry_check(e));
-    Own own(e, stream);
-    CHK(decode_train_body(e, CallerCodes{{codes_x, codes_r, codes_f0}, c_trg}, B, T, own.s));
-    return export_out(e, out, B, T, own.s);
+    return decode_call(e, "ss_g3_decode_train", G3, CallerCodes{{codes_x, codes_r, codes_f0}, c_trg}, nullptr, B, T, true, out, stream);
+}
+
+int ss_g6_decode_train(ss_engine* e, const float* codes_r, const float* codes_f0, int B, int T, float* out, void* stream) {
+    return decode_call(e, "ss_g6_decode_train", G6, CallerCodes{{codes_r, codes_f0, nullptr}, nullptr}, nullptr, B, T, true, out, stream);
 }
 
 int ss_g3_decode_backward(ss_engine* e, const float* d_out, float* d_codes_x, float* d_codes_r, float* d_codes_f0, float* dc_trg, int flags,
                           void* stream) {
-    CHK(decode_backward_check(e, SS_GENERATOR_3, "ss_g3_decode_backward", d_out, flags));
-    Own own(e, stream);
-    CHK(import_dout(e, d_out, e->curB, e->curT, own.s));
     float* const d_codes[3] = {d_codes_x, d_codes_r, d_codes_f0};
-    return decode_backward_body(e, d_codes, dc_trg, (flags & SS_STEP_ACCUMULATE) != 0, own.s);
-}
-
-int ss_g6_decode_train(ss_engine* e, const float* codes_r, const float* codes_f0, int B, int T, float* out, void* stream) {
-    CHK(decode_train_check(e, SS_GENERATOR_6, "ss_g6_decode_train", codes_r && codes_f0 && out, B, T));
-    CHK(entry_check(e));
-    Own own(e, stream);
-    CHK(decode_train_body(e, CallerCodes{{codes_r, codes_f0, nullptr}, nullptr}, B, T, own.s));
-    return export_out(e, out, B, T, own.s);
+    return decode_backward_call(e, "ss_g3_decode_backward", G3, d_out, d_codes, dc_trg, flags, stream);
 }
 
 int ss_g6_decode_backward(ss_engine* e, const float* d_out, float* d_codes_r, float* d_codes_f0, int flags, void* stream) {
-    CHK(decode_backward_check(e, SS_GENERATOR_6, "ss_g6_decode_backward", d_out, flags));
-    Own own(e, stream);
-    CHK(import_dout(e, d_out, e->curB, e->curT, own.s));
     float* const d_codes[3] = {d_codes_r, d_codes_f0, nullptr};
-    return decode_backward_body(e, d_codes, nullptr, (flags & SS_STEP_ACCUMULATE) != 0, own.s);
+    return decode_backward_call(e, "ss_g6_decode_backward", G6, d_out, d_codes, nullptr, flags, stream);
 }
 
 int ss_adam_step_decoder(ss_engine* e, float grad_scale, void* stream) {
-    if (!e) return fail("ss_adam_step_decoder: null engine");
-    if (e->kind == SS_INTERP_ONLY) return fail("ss_adam_step_decoder: an InterpLnr-only engine has no parameters");
-    if (!e->ws) return fail("ss_adam_step_decoder: engine is not bound (call ss_bind first)");
+    CHK(guard(e, "ss_adam_step_decoder", GEN | GRADS | ADAM));
     CHK(entry_check(e));
     Own own(e, stream);
     return adam_decoder_enqueue(e, grad_scale, own.s);
@@ -2972,16 +3038,17 @@ int ss_adam_step_decoder(ss_engine* e, float grad_scale, void* stream) {
 
 int ss_g3_decode_train_step(ss_engine* e, const float* codes_x, const float* codes_r, const float* codes_f0, const float* c_trg,
                             const float* target_mel, int B, int T, float grad_scale, int flags, float* loss, float* dc_trg, void* stream) {
-    CHK(decode_train_check(e, SS_GENERATOR_3, "ss_g3_decode_train_step", codes_x && codes_r && codes_f0 && c_trg && target_mel && loss, B, T));
+    const char* call = "ss_g3_decode_train_step";
+    CHK(guard(e, call, G3 | GRADS | adam_unless(flags) | NO_DP));
+    if (!codes_x || !codes_r || !codes_f0 || !c_trg || !target_mel || !loss)
+        return fail("ss_g3_decode_train_step: null pointer (every input and loss are required)");
     if (flags & ~(SS_STEP_NO_ADAM | SS_STEP_ACCUMULATE)) return fail("ss_g3_decode_train_step: flags other than SS_STEP_NO_ADAM and SS_STEP_ACCUMULATE");
-    if (!e->G) return fail("ss_g3_decode_train_step: engine is not bound (call ss_bind first)");
-    if (e->dp_on) return fail("ss_g3_decode_train_step: not available on a member of a data-parallel group");
-    if (!(flags & SS_STEP_NO_ADAM) && (!e->Mm || !e->Vv)) return fail("ss_g3_decode_train_step: Adam arenas are not bound (pass SS_STEP_NO_ADAM)");
+    CHK(shape_check(e, call, B, T, false));
     CHK(entry_check(e));
     Own own(e, stream);
     hipStream_t s = own.s;
     prof_tick(e);
-    CHK(decode_train_body(e, CallerCodes{{codes_x, codes_r, codes_f0}, c_trg}, B, T, s));
+    CHK(decode_on(e, CallerCodes{{codes_x, codes_r, codes_f0}, c_trg}, nullptr, B, T, true, s));
     const int C = e->head_out;
     HIPCHK(mse_loss(CRows::slab(e->out_slab, C, T), CRows::dense(target_mel, C, T), Rows::slab(e->d_out_slab, C, T), B, T, C, 1.0f, e->loss_part, loss, s));
     float* const d_codes[3] = {nullptr, nullptr, nullptr};
@@ -2990,72 +3057,66 @@ int ss_g3_decode_train_step(ss_engine* e, const float* codes_x, const float* cod
     return 0;
 }
 
-static int g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, const float* scales, const int* len_seg, const int* lens, int B,
-                      int T, int training, float* out, void* stream) {
-    CHK(entry_check(e));
-    Own own(e, stream);
-    hipStream_t s = own.s;
-    if (training && T > e->maxT) return fail("train-mode forward: T above max_frames; longer sequences run in eval mode only");
-    if (training && T != e->hp.max_len_pad) return fail("train-mode forward needs T == max_len_pad (model.py:370)");
-    if (training && (!scales || !len_seg)) return fail("train-mode forward needs the InterpLnr draws");
-    CHK(geometry(e, B, T, s, !training));
-    const ss_hparams& h = e->hp;
-    HIPCHK(copy_rows(CRows::dense(x_org, h.dim_freq, T), Rows::slab(e->org, h.dim_freq, T), B, T, h.dim_freq, s, lens));
-    HIPCHK(copy_rows(CRows::dense(f0_trg, h.dim_f0, T), Rows::slab(e->in_f0, e->f0p, T), B, T, h.dim_f0, s, lens));
-    CHK(forward_core(e, training != 0, scales, len_seg, 0, s, {}, lens));
-    if (out) CHK(export_out(e, out, B, T, s, lens));
+
+// ---- the training steps.  The four entry points (one GPU / data parallel, per generator) share everything that can refuse, the prologue
+// behind it and the tail (backward + Adam); the two cores between them really differ.
+struct Step {
+    const float *mel, *f0;            // [B,T,80]; Generator_3: f0 [B,T,1], Generator_6: its one-hot [B,T,257]
+    const float* emb;                 // Generator_3: speaker rows
+    const int* len_org;               // Generator_3: utterance lengths
+    const int* target_idx;            // Generator_6: cross-entropy targets
+    const float* scales;
+    const int* len_seg;
+    int B, T;
+    float grad_scale;
+    int flags;
+    float* loss;
+};
+constexpr int STEP_FLAGS = SS_STEP_NO_ADAM | SS_STEP_SPLIT_BACKWARD | SS_STEP_SPLIT_NO_JOIN | SS_STEP_ACCUMULATE | SS_STEP_BUCKET;
+
+// a step's own argument checks and the status word, behind the guard; *want: the max_len_pad it runs with
+static int step_check(ss_engine* e, const char* call, const Step& a, int* want) {
+    const bool g3 = e->kind == SS_GENERATOR_3;
+    if (!a.mel || !a.f0 || !a.scales || !a.len_seg || !a.loss || (g3 ? !a.emb || !a.len_org : !a.target_idx))
+        return refuse(call, ": null pointer (every input, the draws and loss are required)");
+    if (a.flags & ~STEP_FLAGS) return refuse(call, ": flags outside the SS_STEP_* set");
+    CHK(step_len(e, call, a.T, a.flags, want));
+    const int old = e->hp.max_len_pad;
+    e->hp.max_len_pad = *want;          // the plan is sized by it: ask about the one the step would run with
+    const int rc = shape_check(e, call, a.B, a.T, false, *want != old);
+    e->hp.max_len_pad = old;
+    CHK(rc);
+    return entry_check(e);
+}
+
+// behind the last refusal: the step's max_len_pad, its plan, and whether its launches are bracketed (ss_profile_sample)
+static int step_begin(ss_engine* e, const Step& a, int want, hipStream_t s) {
+    set_max_len_pad(e, want);
+    CHK(geometry(e, a.B, a.T, s));
+    prof_tick(e);
     return 0;
 }
 
-int ss_g6_forward(ss_engine* e, const float* x_org, const float* f0_trg, const float* scales, const int* len_seg, int B,
-                  int T, int training, float* out, void* stream) {
-    if (e->kind != SS_GENERATOR_6) return fail("ss_g6_forward on a Generator_3 engine");
-    return g6_forward(e, x_org, f0_trg, scales, len_seg, nullptr, B, T, training, out, stream);
+// the whole backward, then Adam unless SS_STEP_NO_ADAM
+static int step_tail(ss_engine* e, Backward& bw, float grad_scale, int flags, hipStream_t s) {
+    bw.adam_early = !(flags & SS_STEP_NO_ADAM);   // Adam follows inside this call: its decoder + head range may go out early
+    bw.adam_gs = grad_scale;
+    CHK(backward_core(e, bw, s));                                                           // solver.py:170-171
+    if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_enqueue(e, bw, grad_scale, s));                // solver.py:172
+    return 0;
 }
 
-int ss_g6_forward_ragged(ss_engine* e, const float* x_org, const float* f0_trg, const int* len_dev, int B, int T, int training, float* out,
-                         void* stream) {
-    if (!e) return fail("ss_g6_forward_ragged: null engine");
-    if (e->kind != SS_GENERATOR_6) return fail("ss_g6_forward_ragged on an engine that is not a Generator_6");
-    if (training && len_dev) return fail("ss_g6_forward_ragged: ragged batches are eval-only (training != 0 with a length array)");
-    return g6_forward(e, x_org, f0_trg, nullptr, nullptr, len_dev, B, T, training, out, stream);
-}
-
-int ss_g6_backward(ss_engine* e, const float* d_out, void* stream) {
-    if (e->kind != SS_GENERATOR_6) return fail("ss_g6_backward on a Generator_3 engine");
-    CHK(backward_check(e));
-    Own own(e, stream);
-    hipStream_t s = own.s;
-    CHK(import_dout(e, d_out, e->curB, e->curT, s));
-    Backward bw;
-    return backward_core(e, bw, s);
-}
-
-int ss_g6_backward_inputs(ss_engine* e, const float* d_out, float* dx_org, float* df0_trg, void* stream) {
-    if (e->kind != SS_GENERATOR_6) return fail("ss_g6_backward_inputs on a Generator_3 engine");
-    CHK(backward_check(e));
-    Own own(e, stream);
-    hipStream_t s = own.s;
-    Backward bw;
-    bw.in_grad[0] = {&e->c2[0], df0_trg, e->hp.dim_f0};      // Encoder_6's stack (model.py:123-140)
-    bw.in_grad[1] = {&e->ct, dx_org, e->hp.dim_freq};        // Encoder_t
-    CHK(import_dout(e, d_out, e->curB, e->curT, s));
-    return backward_core(e, bw, s);
-}
-
-static int g3_step_body(ss_engine* e, const float* mel, const float* f0, const float* emb, const int* len_org,
-                        const float* scales, const int* len_seg, int B, int T, float grad_scale, int flags, float* loss,
-                        hipStream_t s) {
+static int g3_step_core(ss_engine* e, const Step& a, float grad_scale, int flags, hipStream_t s) {
     const ss_hparams& h = e->hp;
-    prof_tick(e);
+    const int B = a.B, T = a.T;
     // solver.py:160-163: resample [mel | f0] with the utterance lengths, re-quantise the f0 channel
-    HIPCHK(interp_plan(e->plan[0], scales, len_seg, len_org, 0, B, s));
-    HIPCHK(interp_quant(e->plan[0], mel, f0, h.dim_freq, Rows::slab(e->in_mel, h.dim_freq, T), Rows::slab(e->in_f0, e->f0p, T), h.dim_f0, e->qidx, B, s));
+    HIPCHK(interp_plan(e->plan[0], a.scales, a.len_seg, a.len_org, 0, B, s));
+    HIPCHK(interp_quant(e->plan[0], a.mel, a.f0, h.dim_freq, Rows::slab(e->in_mel, h.dim_freq, T), Rows::slab(e->in_f0, e->f0p, T), h.dim_f0, e->qidx, B, s));
     // x_org and the speaker embedding are first read by Encoder_t / the decoder input: their copies ride on the branch stream
     const bool accumulate = (flags & SS_STEP_ACCUMULATE) != 0;
-    CHK(forward_core(e, true, scales, len_seg, 1, s, FusedForward{mel, emb, true, accumulate}));        // solver.py:165
+    CHK(forward_core(e, true, a.scales, a.len_seg, 1, s, FusedForward{a.mel, a.emb, true, accumulate}));        // solver.py:165
     const int C = e->head_out;
-    HIPCHK(mse_loss(CRows::slab(e->out_slab, C, T), CRows::slab(e->org, C, T), Rows::slab(e->d_out_slab, C, T), B, T, C, 1.0f, e->loss_part, loss,
+    HIPCHK(mse_loss(CRows::slab(e->out_slab, C, T), CRows::slab(e->org, C, T), Rows::slab(e->d_out_slab, C, T), B, T, C, 1.0f, e->loss_part, a.loss,
                     s));                                                                    // solver.py:166
     Backward bw;
     bw.accumulate = accumulate;
@@ -3072,50 +3133,51 @@ static int g3_step_body(ss_engine* e, const float* mel, const float* f0, const f
         }
         return 0;
     }
-    bw.adam_early = !(flags & SS_STEP_NO_ADAM);   // Adam follows inside this call: its decoder + head range may go out early
-    bw.adam_gs = grad_scale;
-    CHK(backward_core(e, bw, s));                                                           // solver.py:170-171
-    if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_enqueue(e, bw, grad_scale, s));                // solver.py:172
-    return 0;
+    return step_tail(e, bw, grad_scale, flags, s);
 }
 
-// Length buckets (SS_STEP_BUCKET): a bucketed step runs with max_len_pad = T; a step WITHOUT the flag runs with the max_len_pad the
-// engine was created with again, whatever bucket came before (a loader that mixes buckets with full-length batches sends the
-// latter without the flag: speechsplit_amd/solver.py).
-static int apply_bucket(ss_engine* e, int T, int flags) {
-    if (T > e->maxT) return fail("training: T above max_frames; frames above max_frames (<= 256) run in eval-mode forwards only");
-    int want = e->bound_max_len_pad;
-    if (flags & SS_STEP_BUCKET) {      // this batch's length bucket: the step runs with max_len_pad = T
-        if (T < 8 || T > e->maxT || T % 8) return fail("SS_STEP_BUCKET: T must be a multiple of 8 within the engine's max_frames");
-        want = T;
-    }
-    if (e->hp.max_len_pad != want) {
-        e->hp.max_len_pad = want;
-        e->curB = e->curT = 0;         // InterpLnr plans are sized by max_len_pad: carve again
-    }
-    return 0;
+// Generator_6 has no fused staging: the train-mode forward as ss_g6_forward runs it, then cross-entropy
+static int g6_step_core(ss_engine* e, const Step& a, float grad_scale, int flags, hipStream_t s) {
+    const float* const x[2] = {a.mel, a.f0};
+    CHK(forward_on(e, x, nullptr, a.scales, a.len_seg, nullptr, a.B, a.T, true, nullptr, s));
+    const int C = e->head_out;
+    HIPCHK(ce_loss(CRows::slab(e->out_slab, C, a.T), a.target_idx, Rows::slab(e->d_out_slab, C, a.T), a.B, a.T, C, 1.0f, e->loss_part, a.loss, s));
+    Backward bw;
+    bw.accumulate = (flags & SS_STEP_ACCUMULATE) != 0;
+    return step_tail(e, bw, grad_scale, flags, s);
+}
+
+static int step_core(ss_engine* e, const Step& a, float grad_scale, int flags, hipStream_t s) {
+    return e->kind == SS_GENERATOR_3 ? g3_step_core(e, a, grad_scale, flags, s) : g6_step_core(e, a, grad_scale, flags, s);
+}
+
+static int train_step_call(ss_engine* e, const char* call, unsigned kind, const Step& a, void* stream) {
+    CHK(guard(e, call, kind | GRADS | adam_unless(a.flags)));
+    int want = 0;
+    CHK(step_check(e, call, a, &want));
+    Own own(e, stream);
+    CHK(step_begin(e, a, want, own.s));
+    return step_core(e, a, a.grad_scale, a.flags & ~SS_STEP_BUCKET, own.s);
 }
 
 int ss_g3_train_step(ss_engine* e, const float* mel, const float* f0, const float* emb, const int* len_org,
                      const float* scales, const int* len_seg, int B, int T, float grad_scale, int flags, float* loss,
                      void* stream) {
-    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_train_step on a Generator_6 engine");
-    CHK(entry_check(e));
-    Own own(e, stream);
-    hipStream_t s = own.s;
-    CHK(apply_bucket(e, T, flags));
-    const ss_hparams& h = e->hp;
-    if (T != h.max_len_pad) return fail("training needs T == max_len_pad (model.py:105,157,370); pass SS_STEP_BUCKET for a length-bucketed batch");
-    CHK(geometry(e, B, T, s));
-    flags &= ~SS_STEP_BUCKET;
-    return g3_step_body(e, mel, f0, emb, len_org, scales, len_seg, B, T, grad_scale, flags, loss, s);
+    return train_step_call(e, "ss_g3_train_step", G3, Step{mel, f0, emb, len_org, nullptr, scales, len_seg, B, T, grad_scale, flags, loss}, stream);
+}
+
+int ss_g6_train_step(ss_engine* e, const float* mel, const float* f0_onehot, const int* target_idx, const float* scales,
+                     const int* len_seg, int B, int T, float grad_scale, int flags, float* loss, void* stream) {
+    return train_step_call(e, "ss_g6_train_step", G6, Step{mel, f0_onehot, nullptr, nullptr, target_idx, scales, len_seg, B, T, grad_scale, flags, loss},
+                           stream);
 }
 
 int ss_train_finish(ss_engine* e, float grad_scale, int flags, void* stream) {
+    CHK(guard(e, "ss_train_finish", GEN | GRADS | adam_unless(flags)));
+    if (!e->fwd.have) return fail("ss_train_finish without a preceding ss_*_train_step(SS_STEP_SPLIT_BACKWARD)");
+    CHK(backward_check(e, "ss_train_finish"));
     Own own(e, stream);
     hipStream_t s = own.s;
-    if (!e->fwd.have) return fail("ss_train_finish without a preceding ss_*_train_step(SS_STEP_SPLIT_BACKWARD)");
-    CHK(backward_check(e));
     Backward bw;               // a backward of its own: the decoder half (an earlier call) left nothing pending, and nothing goes out early
     bw.accumulate = e->bwd_accumulate;      // ... but the step's choice between adding to the arena and overwriting it holds for both halves
     CHK(backward_encoder(e, bw, s));
@@ -3124,6 +3186,7 @@ int ss_train_finish(ss_engine* e, float grad_scale, int flags, void* stream) {
 }
 
 int ss_wait_decoder_grads(ss_engine* e, void* consumer_stream) {
+    CHK(guard(e, "ss_wait_decoder_grads", GEN | WS));
     if (!e->dec_pending) return fail("ss_wait_decoder_grads without a preceding SS_STEP_SPLIT_BACKWARD | SS_STEP_SPLIT_NO_JOIN step");
     hipStream_t c = S(consumer_stream);
     HIPCHK(hipStreamWaitEvent(c, e->ev_dec[0], 0));
@@ -3132,43 +3195,22 @@ int ss_wait_decoder_grads(ss_engine* e, void* consumer_stream) {
     return 0;
 }
 
-void* ss_side_stream(ss_engine* e) { return (void*)e->side; }
+void* ss_side_stream(ss_engine* e) { return guard(e, "ss_side_stream", ANY) ? nullptr : (void*)e->side; }
 
-long ss_grad_split(const ss_engine* e) {
-    for (const auto& p : e->params)
-        if (p.name.rfind("decoder.", 0) == 0) return p.offset;
-    return e->arena;
-}
-
-int ss_g6_train_step(ss_engine* e, const float* mel, const float* f0_onehot, const int* target_idx, const float* scales,
-                     const int* len_seg, int B, int T, float grad_scale, int flags, float* loss, void* stream) {
-    if (e->kind != SS_GENERATOR_6) return fail("ss_g6_train_step on a Generator_3 engine");
-    CHK(apply_bucket(e, T, flags));
-    Own own(e, stream);
-    hipStream_t s = own.s;
-    prof_tick(e);
-    CHK(ss_g6_forward(e, mel, f0_onehot, scales, len_seg, B, T, 1, nullptr, (void*)s));
-    const int C = e->head_out;
-    HIPCHK(ce_loss(CRows::slab(e->out_slab, C, T), target_idx, Rows::slab(e->d_out_slab, C, T), B, T, C, 1.0f, e->loss_part, loss, s));
-    Backward bw;
-    bw.accumulate = (flags & SS_STEP_ACCUMULATE) != 0;
-    bw.adam_early = !(flags & SS_STEP_NO_ADAM);
-    bw.adam_gs = grad_scale;
-    CHK(backward_core(e, bw, s));
-    if (!(flags & SS_STEP_NO_ADAM)) CHK(adam_enqueue(e, bw, grad_scale, s));
-    return 0;
-}
+long ss_grad_split(const ss_engine* e) { return guard(e, "ss_grad_split", ANY) ? -1 : grad_split(e); }
 
 int ss_interp_forward(ss_engine* e, const float* x, const int* len_seq, const float* scales, const int* len_seg, int B, int T,
                       int C, float* y, int* i0, float* lam, int* counts, void* stream) {
+    CHK(guard(e, "ss_interp_forward", ANY | WS));
+    if (!x || !len_seq || !scales || !len_seg || !y) return fail("ss_interp_forward: null pointer (x, len_seq, the draws and y are required)");
+    if (B > e->maxB || T > e->maxT) return fail("ss_interp_forward: batch / frames exceed the engine limits (InterpLnr keeps T <= max_frames)");
+    if (!e->curB) CHK(shape_check(e, "ss_interp_forward", e->maxB, e->maxT, false));      // a first call plans the engine's largest shape
+    if ((long)B * (T + 1) > (e->curB ? (long)e->curB * (e->curT + 1) : (long)e->maxB * (e->maxT + 1))) return fail("ss_interp_forward: plan storage too small");
     Own own(e, stream);
     hipStream_t s = own.s;
-    if (!e->ws) return fail("engine is not bound");
-    if (B > e->maxB || T > e->maxT) return fail("ss_interp_forward: batch / frames exceed the engine limits (InterpLnr keeps T <= max_frames)");
     if (!e->curB) CHK(geometry(e, e->maxB, e->maxT, s));
     InterpPlan pl = e->plan[3];     // standalone calls use the last plan slot with their own T
     pl.T = T;
-    if ((long)B * (T + 1) > (long)e->curB * (e->curT + 1)) return fail("ss_interp_forward: plan storage too small");
     const int P = pl.P;
     HIPCHK(interp_plan(pl, scales, len_seg, len_seq, 0, B, s));
     HIPCHK(interp_gather(pl, CRows::dense(x, C, T), Rows::dense(y, C, P), C, B, s));
@@ -3179,19 +3221,20 @@ int ss_interp_forward(ss_engine* e, const float* x, const int* len_seq, const fl
 }
 
 int ss_interp_backward(ss_engine* e, const float* dy, int B, int T, int C, float* dx, void* stream) {
-    Own own(e, stream);
-    hipStream_t s = own.s;
-    if (!e->ws || !e->curB) return fail("ss_interp_backward without ss_interp_forward");
+    CHK(guard(e, "ss_interp_backward", ANY | WS));
+    if (!e->curB) return fail("ss_interp_backward without ss_interp_forward");
+    if (!dy || !dx) return fail("ss_interp_backward: null pointer (dy and dx are required)");
     if (B > e->maxB || T > e->maxT) return fail("ss_interp_backward: batch / frames exceed the engine limits (InterpLnr keeps T <= max_frames)");
+    Own own(e, stream);
     InterpPlan pl = e->plan[3];
     pl.T = T;
     const int P = pl.P;
-    HIPCHK(interp_scatter(pl, CRows::dense(dy, C, P), Rows::dense(dx, C, T), C, B, s));
+    HIPCHK(interp_scatter(pl, CRows::dense(dy, C, P), Rows::dense(dx, C, T), C, B, own.s));
     return 0;
 }
 
 int ss_set_precision(ss_engine* e, int precision) {
-    if (!e) return fail("ss_set_precision: null engine");
+    CHK(guard(e, "ss_set_precision", ANY));
     if (precision != SS_PRECISION_F32 && precision != SS_PRECISION_BF16) return fail("ss_set_precision: unknown precision");
     if (precision != e->precision) e->fwd = {};      // a forward of the other precision cannot be differentiated: its backward is refused
     e->precision = precision;
@@ -3199,7 +3242,7 @@ int ss_set_precision(ss_engine* e, int precision) {
 }
 
 int ss_profile(ss_engine* e, unsigned class_mask) {
-    if (!e) return fail("ss_profile: null engine");
+    CHK(guard(e, "ss_profile", ANY));
     if (class_mask) e->prof_n = 0;
     e->prof_mask = class_mask;
     e->prof_ctr = 0;
@@ -3208,7 +3251,8 @@ int ss_profile(ss_engine* e, unsigned class_mask) {
 }
 
 int ss_profile_sample(ss_engine* e, int every_nth_step) {
-    if (!e || every_nth_step < 1) return fail("ss_profile_sample: needs an engine and n >= 1");
+    CHK(guard(e, "ss_profile_sample", ANY));
+    if (every_nth_step < 1) return fail("ss_profile_sample: needs n >= 1");
     e->prof_every = every_nth_step;
     e->prof_ctr = 0;
     e->prof_live = true;
@@ -3216,7 +3260,7 @@ int ss_profile_sample(ss_engine* e, int every_nth_step) {
 }
 
 int ss_profile_read(ss_engine* e, int klass, int* launches, double* total_us, double* total_flops) {
-    if (!e) return fail("ss_profile_read: null engine");
+    CHK(guard(e, "ss_profile_read", ANY));
     int n = 0;
     double us = 0, fl = 0;
     for (int i = 0; i < e->prof_n; ++i) {
@@ -3238,7 +3282,8 @@ int ss_profile_read(ss_engine* e, int klass, int* launches, double* total_us, do
 // The brackets of ss_profile as a timeline: per record (class, start, end) in microseconds relative to the first record's start event --
 // timestamps from the real run (no tracing tool slowing the host down), across the engine's streams.  3 doubles per record, enqueue order.
 int ss_profile_timeline(ss_engine* e, double* out, int cap) {
-    if (!e || !out || cap < 0) return fail("ss_profile_timeline: null argument");
+    CHK(guard(e, "ss_profile_timeline", ANY));
+    if (!out || cap < 0) return fail("ss_profile_timeline: null argument");
     const int n = e->prof_n < cap ? e->prof_n : cap;
     for (int i = 0; i < n; ++i) {
         if (hipEventSynchronize(e->prof_ev[2 * i + 1]) != hipSuccess) return fail("ss_profile_timeline: event sync failed");
@@ -3253,6 +3298,7 @@ int ss_profile_timeline(ss_engine* e, double* out, int cap) {
 }
 
 int ss_check(ss_engine* e, void* stream) {
+    CHK(guard(e, "ss_check", ANY));
     HIPCHK(hipStreamSynchronize(S(stream)));
     HIPCHK(hipGetLastError());
     for (LstmBlk* lb : {&e->ld, &e->l1, &e->l2, &e->lt}) {
@@ -3267,7 +3313,7 @@ int ss_check(ss_engine* e, void* stream) {
 }
 
 int ss_clear_abort(ss_engine* e, void* stream) {
-    if (!e) return fail("ss_clear_abort: null engine");
+    CHK(guard(e, "ss_clear_abort", ANY));
     HIPCHK(hipStreamSynchronize(S(stream)));
     if (e->sticky) *(volatile unsigned*)e->sticky = 0u;
     return 0;
@@ -3276,8 +3322,10 @@ int ss_clear_abort(ss_engine* e, void* stream) {
 unsigned ss_status(const ss_engine* e) { return e && e->sticky ? *(volatile unsigned*)e->sticky : 0u; }
 
 int ss_debug_buffer(ss_engine* e, const char* name, float** ptr, long* rows, long* cols) {
+    CHK(guard(e, "ss_debug_buffer", ANY));
+    if (!name || !ptr || !rows || !cols) return fail("ss_debug_buffer: null argument");
     auto it = e->dbg.find(name);
-    if (it == e->dbg.end()) return fail(std::string("no such buffer: ") + name);
+    if (it == e->dbg.end()) return fail(std::string("ss_debug_buffer: no such buffer: ") + name);
     *ptr = it->second.first;
     *rows = (long)e->curB * (e->curT + 2 * HALO);
     *cols = it->second.second;
@@ -3285,7 +3333,8 @@ int ss_debug_buffer(ss_engine* e, const char* name, float** ptr, long* rows, lon
 }
 
 int ss_debug_relu_mask(ss_engine* e, const char* block, float* mask, void* stream) {
-    if (!e || !block || !mask) return fail("ss_debug_relu_mask: null argument");
+    CHK(guard(e, "ss_debug_relu_mask", GEN | WS));
+    if (!block || !mask) return fail("ss_debug_relu_mask: null argument");
     if (!e->curB) return fail("ss_debug_relu_mask: no forward has run");
     auto it = e->dbg.find(std::string(block) + ".conv");
     if (it == e->dbg.end()) return fail(std::string("ss_debug_relu_mask: no such conv block: ") + block);
@@ -3387,9 +3436,10 @@ int ss_op_conv_block_ragged(const float* x, const float* w, const float* bias, c
                          Ci, Co, stream);
 }
 
-const char* ss_stream_report(const ss_engine* e) { return e ? e->stream_report.c_str() : ""; }
+const char* ss_stream_report(const ss_engine* e) { return guard(e, "ss_stream_report", ANY) ? nullptr : e->stream_report.c_str(); }
 
 int ss_debug_names(ss_engine* e, char* buf, int cap) {
+    CHK(guard(e, "ss_debug_names", ANY));
     std::string all;
     for (auto& kv : e->dbg) all += kv.first + "\n";
     if (buf && cap > 0) {
@@ -3601,8 +3651,8 @@ int ss_comm_unique_id(char* id128) {
 }
 
 int ss_comm_init(ss_engine* e, const char* id128, int rank, int world) {
-    if (!e || !id128 || world < 1 || rank < 0 || rank >= world) return fail("ss_comm_init: bad arguments");
-    if (!e->G) return fail("ss_comm_init: engine is not bound");
+    CHK(guard(e, "ss_comm_init", GEN | GRADS));
+    if (!id128 || world < 1 || rank < 0 || rank >= world) return fail("ss_comm_init: bad arguments");
     if (e->comm) return fail("ss_comm_init: the engine already has a communicator");
     CHK(rccl_load());
     NcclId id;
@@ -3617,13 +3667,14 @@ int ss_comm_init(ss_engine* e, const char* id128, int rank, int world) {
 }
 
 int ss_set_lockstep(ss_engine* e, int on) {
-    if (!e) return fail("ss_set_lockstep: null engine");
+    CHK(guard(e, "ss_set_lockstep", ANY));
     e->lockstep = on != 0;
     return 0;
 }
 
 int ss_comm_destroy(ss_engine* e) {
-    if (e && e->comm) {
+    CHK(guard(e, "ss_comm_destroy", ANY));
+    if (e->comm) {
         (void)hipDeviceSynchronize();
         NCCLCHK(g_rccl.CommDestroy(e->comm));
         e->comm = nullptr;
@@ -3633,24 +3684,28 @@ int ss_comm_destroy(ss_engine* e) {
 }
 
 int ss_allreduce_grads(ss_engine* e, long offset, long count, void* stream) {
+    CHK(guard(e, "ss_allreduce_grads", GEN | GRADS));
+    if (offset < 0 || count < 0 || offset + count > e->arena) return fail("ss_allreduce_grads: range outside the gradient arena");
+    if (count && !e->comm && g_dp_model < 2) return fail("ss_allreduce_grads: no communicator: call ss_comm_init first");
     Own own(e, stream);
     return allreduce_range(e, offset, count, own.s);
 }
 
-// common part of the data-parallel steps: `body` enqueues forward + loss + the whole backward (no Adam); the gradient arena is reduced
+// common part of the data-parallel steps: the step's forward + loss + whole backward (no Adam) with the gradient arena reduced
 // in per-layer buckets on the communication stream while the backward is still running (dp_bucket: each of the decoder's layers as
 // its four weight-gradient GEMMs retire, the head, the two wide trunk layers, the rest), Adam with the 1 / world mean folded in
-static int dp_step(ss_engine* e, hipStream_t s, const std::function<int(hipStream_t)>& body) {
+static int dp_step(ss_engine* e, const Step& a, hipStream_t s) {
+    const int flags = SS_STEP_NO_ADAM | (a.flags & SS_STEP_ACCUMULATE);
     const int world = (g_dp_model > 1 && (!e->comm || e->comm_world == 1)) ? g_dp_model : e->comm_world;
     // the mean over the ranks and over the micro-batches each of them summed into its arena (SS_STEP_ACCUMULATE; 1 without): the count
-    // includes the backward `body` is about to enqueue, so it is read behind it
+    // includes the backward the step is about to enqueue, so it is read behind it
     auto mean_scale = [&]() { return 1.0f / (float)((long)world * (e->accum_count > 0 ? e->accum_count : 1)); };
     CHK(dp_streams(e));
     if (!e->side || !e->side2 || !g_overlap || !g_dp_buckets) {        // no branch streams (or round 2's plan asked for): the plain step, then the arena
-        CHK(body(s));
+        CHK(step_core(e, a, 1.0f, flags, s));
         if (g_dp_buckets) CHK(allreduce_range(e, 0, e->arena, s));
         else {
-            const long k = ss_grad_split(e);
+            const long k = grad_split(e);
             CHK(allreduce_range(e, k, e->arena - k, s));
             CHK(allreduce_range(e, 0, k, s));
         }
@@ -3660,30 +3715,38 @@ static int dp_step(ss_engine* e, hipStream_t s, const std::function<int(hipStrea
     e->dp_rec.clear();              // ss_dp_profile keeps the LAST step's record
     e->dp_ev_used = 0;
     e->dp_on = true;
-    const int rc = body(s);
+    const int rc = step_core(e, a, 1.0f, flags, s);
     e->dp_on = false;
     CHK(rc);
     CHK(dp_finish(e, s));
     return adam_enqueue(e, Backward{}, mean_scale(), s);    // the whole arena; the mean is folded into the Adam kernel
 }
 
+static int dp_step_call(ss_engine* e, const char* call, unsigned kind, const Step& a, void* stream) {
+    CHK(guard(e, call, kind | GRADS | ADAM));
+    if (!e->comm && g_dp_model < 2) return refuse(call, ": call ss_comm_init first");
+    int want = 0;
+    CHK(step_check(e, call, a, &want));      // every rank runs the same bucket (speechsplit_amd/buckets.py)
+    Own own(e, stream);
+    CHK(step_begin(e, a, want, own.s));
+    return dp_step(e, a, own.s);
+}
+
 int ss_g3_dp_train_step(ss_engine* e, const float* mel, const float* f0, const float* emb, const int* len_org, const float* scales,
                         const int* len_seg, int B, int T, int flags, float* loss, void* stream) {
-    if (e->kind != SS_GENERATOR_3) return fail("ss_g3_dp_train_step on a Generator_6 engine");
-    if (!e->comm && g_dp_model < 2) return fail("ss_g3_dp_train_step: call ss_comm_init first");
-    CHK(apply_bucket(e, T, flags));      // every rank runs the same bucket (speechsplit_amd/buckets.py)
-    if (T != e->hp.max_len_pad) return fail("training needs T == max_len_pad (model.py:105,157,370); pass SS_STEP_BUCKET for a length-bucketed batch");
-    CHK(entry_check(e));
-    Own own(e, stream);
-    hipStream_t s = own.s;
-    CHK(geometry(e, B, T, s));
-    return dp_step(e, s, [&](hipStream_t st) { return g3_step_body(e, mel, f0, emb, len_org, scales, len_seg, B, T, 1.0f, SS_STEP_NO_ADAM | (flags & SS_STEP_ACCUMULATE), loss, st); });
+    return dp_step_call(e, "ss_g3_dp_train_step", G3, Step{mel, f0, emb, len_org, nullptr, scales, len_seg, B, T, 1.0f, flags, loss}, stream);
+}
+
+int ss_g6_dp_train_step(ss_engine* e, const float* mel, const float* f0_onehot, const int* target_idx, const float* scales, const int* len_seg,
+                        int B, int T, int flags, float* loss, void* stream) {
+    return dp_step_call(e, "ss_g6_dp_train_step", G6, Step{mel, f0_onehot, nullptr, nullptr, target_idx, scales, len_seg, B, T, 1.0f, flags, loss},
+                        stream);
 }
 
 long ss_scratch_fallbacks(const ss_engine* e) { return e ? e->scratch_fallbacks : -1; }
 
 int ss_dp_profile(ss_engine* e, int on) {
-    if (!e) return fail("ss_dp_profile: null engine");
+    CHK(guard(e, "ss_dp_profile", ANY));
     e->dp_prof = on != 0;
     e->dp_rec.clear();
     e->dp_ev_used = 0;
@@ -3691,7 +3754,7 @@ int ss_dp_profile(ss_engine* e, int on) {
 }
 
 int ss_dp_profile_read(ss_engine* e, double* out, int cap) {
-    if (!e) return fail("ss_dp_profile_read: null engine");
+    CHK(guard(e, "ss_dp_profile_read", ANY));
     const int n = (int)e->dp_rec.size();
     if (!out) return n;
     if (n && !e->dp_bwd_end) return fail("ss_dp_profile_read: no data-parallel step has run with the profile on");
@@ -3709,17 +3772,5 @@ int ss_dp_profile_read(ss_engine* e, double* out, int cap) {
     return n < cap ? n : cap;
 }
 
-int ss_g6_dp_train_step(ss_engine* e, const float* mel, const float* f0_onehot, const int* target_idx, const float* scales, const int* len_seg,
-                        int B, int T, int flags, float* loss, void* stream) {
-    if (e->kind != SS_GENERATOR_6) return fail("ss_g6_dp_train_step on a Generator_3 engine");
-    if (!e->comm && g_dp_model < 2) return fail("ss_g6_dp_train_step: call ss_comm_init first");
-    if (T > e->maxT) return fail("training: T above max_frames; frames above max_frames (<= 256) run in eval-mode forwards only");
-    CHK(entry_check(e));
-    Own own(e, stream);
-    hipStream_t s = own.s;
-    return dp_step(e, s, [&](hipStream_t st) {
-        return ss_g6_train_step(e, mel, f0_onehot, target_idx, scales, len_seg, B, T, 1.0f, (flags & (SS_STEP_BUCKET | SS_STEP_ACCUMULATE)) | SS_STEP_NO_ADAM, loss, (void*)st);
-    });
-}
 
 }  // extern "C"

@@ -21,6 +21,13 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def step_flags(no_adam=False, split_backward=False, split_no_join=False, accumulate=False, bucket=False):
+    """The SS_STEP_* word of the training-step entry points from keyword booleans."""
+    return ((_capi.SS_STEP_NO_ADAM if no_adam else 0) | (_capi.SS_STEP_SPLIT_BACKWARD if split_backward else 0)
+            | (_capi.SS_STEP_SPLIT_NO_JOIN if split_no_join else 0) | (_capi.SS_STEP_ACCUMULATE if accumulate else 0)
+            | (_capi.SS_STEP_BUCKET if bucket else 0))
+
+
 def draw_interp(batch, ncalls, hp, generator=None):
     """Draw the InterpLnr randomness exactly as the reference consumes it (model.py:392-393 then 399-402, per
     call, from the default CPU generator unless one is given).  Returns (scales f32[ncalls, B*S], len_seg i32[...])."""
@@ -385,7 +392,7 @@ class Engine:
         dc_trg) as fresh tensors, None where not asked for; dc_trg is per row [B, dim_spk_emb]."""
         dx, dr, df, dc = self._decode_grad_buffers(('x', 'r', 'f0', 'c_trg'), want)
         d_out = self._f(d_out)
-        _capi.check(self.lib.ss_g3_decode_backward(self.h, _ptr(d_out), _ptr(dx), _ptr(dr), _ptr(df), _ptr(dc), 8 if accumulate else 0, _stream()))
+        _capi.check(self.lib.ss_g3_decode_backward(self.h, _ptr(d_out), _ptr(dx), _ptr(dr), _ptr(df), _ptr(dc), step_flags(accumulate=accumulate), _stream()))
         return dx, dr, df, dc
 
     def g3_decode_train_step(self, codes_x, codes_r, codes_f0, c_trg, target_mel, grad_scale=1.0, no_adam=False, accumulate=False,
@@ -396,7 +403,7 @@ class Engine:
         tgt = self._code_arg('target_mel', target_mel, (B, T, self.hp.dim_freq))
         dc = self._new('d_c_trg', (B, self.hp.dim_spk_emb)) if want_dc_trg else None
         self._dec_bt = (B, T)
-        flags = (1 if no_adam else 0) | (8 if accumulate else 0)
+        flags = step_flags(no_adam=no_adam, accumulate=accumulate)
         _capi.check(self.lib.ss_g3_decode_train_step(self.h, _ptr(cx), _ptr(cr), _ptr(cf), _ptr(c_trg), _ptr(tgt), B, T, float(grad_scale), flags,
                                                      _ptr(self.loss), _ptr(dc), _stream()))
         return (self.loss, dc) if want_dc_trg else self.loss
@@ -413,7 +420,7 @@ class Engine:
         """Backward of the last g6_decode_train (ss_g6_decode_backward); want: names among ('r', 'f0') -> (d_codes_r, d_codes_f0)."""
         dr, df = self._decode_grad_buffers(('r', 'f0'), want)
         d_out = self._f(d_out)
-        _capi.check(self.lib.ss_g6_decode_backward(self.h, _ptr(d_out), _ptr(dr), _ptr(df), 8 if accumulate else 0, _stream()))
+        _capi.check(self.lib.ss_g6_decode_backward(self.h, _ptr(d_out), _ptr(dr), _ptr(df), step_flags(accumulate=accumulate), _stream()))
         return dr, df
 
     def adam_step_decoder(self, grad_scale=1.0):
@@ -433,13 +440,13 @@ class Engine:
         mel, f0, emb, len_org = self._f(mel), self._f(f0), self._f(emb), self._i(len_org)
         sc, ls = self._draws(draws)
         assert sc.shape[0] == 4 and ls.shape[0] == 4
-        flags = (1 if no_adam else 0) | (2 if split_backward else 0) | (4 if split_no_join else 0) | (8 if accumulate else 0) | (16 if bucket else 0)
+        flags = step_flags(no_adam, split_backward, split_no_join, accumulate, bucket)
         _capi.check(self.lib.ss_g3_train_step(self.h, _ptr(mel), _ptr(f0), _ptr(emb), _ptr(len_org), _ptr(sc), _ptr(ls),
                                               B, T, float(grad_scale), flags, _ptr(self.loss), _stream()))
         return self.loss
 
     def train_finish(self, grad_scale=1.0, no_adam=True):
-        _capi.check(self.lib.ss_train_finish(self.h, float(grad_scale), 1 if no_adam else 0, _stream()))
+        _capi.check(self.lib.ss_train_finish(self.h, float(grad_scale), step_flags(no_adam=no_adam), _stream()))
 
     @property
     def grad_split(self):
@@ -483,9 +490,9 @@ class Engine:
             sc, ls = self._draws(draws)
             B, T, _ = mel.shape
             mel, f0, emb, len_org = self._f(mel), self._f(f0), self._f(emb), self._i(len_org)
-            # SS_STEP_NO_ADAM | SS_STEP_SPLIT_BACKWARD | SS_STEP_SPLIT_NO_JOIN
+            flags = step_flags(no_adam=True, split_backward=True, split_no_join=True, accumulate=accumulate, bucket=bucket)
             _capi.check(self.lib.ss_g3_train_step(self.h, _ptr(mel), _ptr(f0), _ptr(emb), _ptr(len_org), _ptr(sc), _ptr(ls),
-                                                  B, T, 1.0, 1 | 2 | 4 | (8 if accumulate else 0) | (16 if bucket else 0), _ptr(self.loss), _stream()))
+                                                  B, T, 1.0, flags, _ptr(self.loss), _stream()))
             if getattr(self, '_side_stream', None) is None:
                 self._side_stream = torch.cuda.ExternalStream(side, device=self.device)
             cs = self._side_stream
@@ -561,7 +568,7 @@ class Engine:
         mel, f0, emb, len_org = self._f(mel), self._f(f0), self._f(emb), self._i(len_org)
         sc, ls = self._draws(draws)
         _capi.check(self.lib.ss_g3_dp_train_step(self.h, _ptr(mel), _ptr(f0), _ptr(emb), _ptr(len_org), _ptr(sc), _ptr(ls), B, T,
-                                                 (16 if bucket else 0) | (8 if accumulate else 0), _ptr(self.loss), _stream()))
+                                                 step_flags(accumulate=accumulate, bucket=bucket), _ptr(self.loss), _stream()))
         return self.loss
 
     # ------------------------------------------------------------------ Generator_6
@@ -600,7 +607,7 @@ class Engine:
         mel, f0_onehot, target_idx = self._f(mel), self._f(f0_onehot), self._i(target_idx)
         sc, ls = self._draws(draws)
         _capi.check(self.lib.ss_g6_train_step(self.h, _ptr(mel), _ptr(f0_onehot), _ptr(target_idx), _ptr(sc), _ptr(ls), B, T,
-                                              float(grad_scale), (1 if no_adam else 0) | (8 if accumulate else 0) | (16 if bucket else 0), _ptr(self.loss),
+                                              float(grad_scale), step_flags(no_adam=no_adam, accumulate=accumulate, bucket=bucket), _ptr(self.loss),
                                               _stream()))
         return self.loss
 
@@ -612,7 +619,7 @@ class Engine:
         mel, f0_onehot, target_idx = self._f(mel), self._f(f0_onehot), self._i(target_idx)
         sc, ls = self._draws(draws)
         _capi.check(self.lib.ss_g6_dp_train_step(self.h, _ptr(mel), _ptr(f0_onehot), _ptr(target_idx), _ptr(sc), _ptr(ls), B, T,
-                                                 (16 if bucket else 0) | (8 if accumulate else 0), _ptr(self.loss), _stream()))
+                                                 step_flags(accumulate=accumulate, bucket=bucket), _ptr(self.loss), _stream()))
         return self.loss
 
     # ------------------------------------------------------------------ optimiser / misc
