@@ -377,6 +377,41 @@ int ss_set_grad_clip(ss_engine* e, float max_norm, void* stream);
 int ss_grad_norm(ss_engine* e, float grad_scale, float* norm_dev, void* stream);
 int ss_grad_clip_stats(ss_engine* e, float* out4_dev, void* stream);
 
+/* ---- decoupled weight decay (AdamW) and an exponential moving average of the parameters, inside the optimiser step (nothing to mirror: the
+ *      reference's solver uses plain Adam and keeps no average; the semantics are torch.optim.AdamW's single-tensor update and
+ *      torch.optim.swa_utils.AveragedModel(G, multi_avg_fn=get_ema_multi_avg_fn(decay)).update_parameters(G) after optimizer.step()) ----
+ * In the formulas t is the optimiser step being APPLIED (not skipped on the device: status word, remote status, non-finite norm under clipping).
+ * WEIGHT DECAY: for a decayed element p1 = p * (float)(1 - lr * weight_decay) comes first, lr the current one of ss_set_adam (not lr / bc1), the
+ *   factor formed in double on the device; today's Adam update then acts on p1.  Both moments are unchanged by decay.  which = 0: every parameter
+ *   (AdamW(G.parameters(), weight_decay=wd) exactly); which = 1: tensors with ndim >= 2 only (conv, LSTM weight_ih / weight_hh, linear weights;
+ *   biases and the GroupNorm affine are left alone), from ss_param_info's ndim.  Not built: coupled L2 decay (Adam(weight_decay=...)), amsgrad.
+ * EMA: after an applied optimiser step, for every element of the arena, ema' = ema + w * (p' - ema), p' the fp32 parameter the step has just
+ *   written, w = (float)(1 - d_t), d_t = decay, or with warm-up min(decay, (1 + n) / (10 + n)) with n the number of EMA updates applied so far.
+ *   n lives in device memory beside the Adam state: it survives what that survives (geometry changes, ss_set_workspace, ss_set_adam).
+ * SKIPS: a step skipped on the device changes nothing: neither p, m, v and the step counter (as ever) nor the decay, the average or n.
+ * ACCUMULATION: only the cycle's one optimiser step decays and averages.
+ * DECODER-ONLY STEP (ss_adam_step_decoder, ss_g3_decode_train_step without SS_STEP_NO_ADAM): decay acts on the decayed tensors inside
+ *   [ss_grad_split, arena) only and the encoder range of p, m, v keeps its bits, but the average is still updated over the WHOLE arena, exactly
+ *   once: the encoder range's parameters did not move, its average still approaches them (what AveragedModel.update_parameters does).
+ * Both terms hold, with the same bits, on every route to the optimiser that covers the whole arena (fused step, SS_STEP_BUCKET, SS_STEP_NO_ADAM +
+ * ss_adam_step, ss_train_finish, both data-parallel steps, both generators, clipping on or off): the factors and n are set once per step by the
+ * step's one prepare kernel and every element sees the same values.  With both off -- the default, and what ss_bind restores -- every entry
+ * point enqueues exactly what it did before these calls existed, to the same kernels.
+ * ss_set_weight_decay: 0 = off.  Refused: negative, NaN or infinite weight_decay, which outside {0, 1}.
+ * ss_set_ema: ema_dev is the caller's arena of ss_arena_numel floats, 16-byte aligned; NULL switches the average off.  updates < 0: the average
+ *   starts as a copy of the parameters as they are now, n = 0.  updates >= 0: the buffer is adopted as it stands with n = updates (resuming).
+ *   decay must lie in [0, 1).  The statistics of ss_ema_stats start again.
+ * ss_ema_swap: exchanges the contents of the parameter arena and the EMA arena, gaps included; a second call restores the original bits.  Every
+ *   forward re-lays the weights out from the parameter arena, so no cached image goes stale.  NOTE: a training step or optimiser step taken while
+ *   swapped trains the AVERAGED weights; the engine does not prevent it (speechsplit_amd.Engine.ema_weights() does).
+ * ss_ema_stats: asynchronous device-to-device copy of four floats {EMA updates applied (n), d_t of the last update, weight-decay factor of the
+ *   last applied step, 0}; no synchronisation, as ss_grad_clip_stats.  (Floats: n is exact up to 2^24.)
+ * All four need the optimiser's binding (both Adam arenas) and name a bad argument AFTER a missing binding. */
+int ss_set_weight_decay(ss_engine* e, float weight_decay, int which, void* stream);
+int ss_set_ema(ss_engine* e, float* ema_dev, double decay, int warmup, long updates, void* stream);
+int ss_ema_swap(ss_engine* e, void* stream);
+int ss_ema_stats(ss_engine* e, float* out4_dev, void* stream);
+
 /* ---- InterpLnr as a standalone module (model.py:355-436; solver.py:59,161) ---- */
 /* x [B,T,C], len_seq i32[B], draws [B*7] -> y [B,max_len_pad,C].  Optional outputs (may be NULL): i0 i32[B,P],
  * lam f32[B,P], counts i32[B] (un-truncated, model.py:418). */
@@ -1170,6 +1205,38 @@ int ss_op_copy_rows(const float* src_dev, long s_ld, long s_bs, float* dst_dev, 
                     void* stream);
 int ss_op_act_scales(const float* const* gamma_dev, const float* const* beta_dev, const int* C, int n, int T, float* out_dev, void* stream);
 int ss_op_param_guard(const float* p_dev, long n, float limit, unsigned* sticky_dev, void* stream);
+/* Test hook: the optimiser kernels behind ss_set_weight_decay / ss_set_ema on the caller's own buffers, at any length.  state is 256 bytes of
+ * device scratch that takes the place of the workspace's head; the hook fills it from the scalars below (as ss_set_adam, ss_set_weight_decay and
+ * ss_set_ema would), runs the step's prepare kernel (skip_status: nullable device float, non-zero = the step is skipped) and then
+ *   mode 0: the extended Adam update over the elements [lo, hi) of p, g, m, v and (ema non-null) ema, all given by their BASE; clip_coef > 0
+ *           takes the clipped form with that coefficient; n_runs > 0 the decayed-run table (ss_set_weight_decay's which = 1), 0 decays every element;
+ *   mode 1: ema[i] += w * (p[i] - ema[i]) over [lo, hi) alone; with step < 0 under the state an earlier call left in `state` (nothing is
+ *           copied or waited for and no prepare runs: the one launch, for timing it);
+ *   mode 2: the exchange p[i] <-> ema[i] over [lo, hi) (no state is written, no prepare runs).
+ * lo, hi: multiples of 4; arenas 16-byte aligned; the runs must follow each other without a hole or an overlap and cover [lo, hi).  Refused: null required pointers, a mode outside 0 .. 2, mode 0 with neither term on. */
+typedef struct ss_optim_ext_op {
+    float *p, *m, *v, *ema;
+    const float* g;
+    void* state;
+    const float* skip_status;
+    long lo, hi;
+    double lr, beta1, beta2, eps;
+    long step;
+    float grad_scale, clip_coef, weight_decay;
+    double ema_decay;
+    int ema_warmup;
+    long ema_updates;
+    int n_runs;
+    const long* run_start;
+    const int* run_len;
+    const int* run_decayed;
+    int mode;
+} ss_optim_ext_op;
+int ss_op_optim_ext(const ss_optim_ext_op* op, void* stream);
+/* Test hook, host side only: the runs of [0, arena) by "decayed under ss_set_weight_decay(which = 1)" that an engine of this kind and these
+ * hyper-parameters builds from its parameter table -- up to cap of them into start / len / decayed; returns their number (negative: refused).
+ * The runs cover the arena without a hole: a tensor's run takes the alignment gap behind it, the status slot is the last run, not decayed. */
+int ss_op_wd_runs(int kind, const ss_hparams* hp, long* start, int* len, int* decayed, int cap);
 /* The GEMM over operand images (speechsplit_amd/csrc/gemm_img.hip), the engine's default for every large contraction: an IMAGE has the
  * geometry of its fp32 matrix (4 bytes per element) with every aligned group of 8 elements along the contiguous axis replaced by 16 bytes of
  * hi pieces and 16 bytes of lo pieces of the fp16 x 2 split of scale * x (scale a power of two).

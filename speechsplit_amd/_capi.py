@@ -68,6 +68,15 @@ class SSWgradTask(C.Structure):
                 ('gwhh', C.c_void_p), ('gb', C.c_void_p), ('H', C.c_int), ('In', C.c_int), ('R', C.c_long)]
 
 
+class SSOptimExtOp(C.Structure):
+    """ss_optim_ext_op (test hook ss_op_optim_ext): the weight-decay / EMA optimiser kernels on the caller's buffers."""
+    _fields_ = ([(n, C.c_void_p) for n in ('p', 'm', 'v', 'ema', 'g', 'state', 'skip_status')] + [('lo', C.c_long), ('hi', C.c_long)] +
+                [(n, C.c_double) for n in ('lr', 'beta1', 'beta2', 'eps')] + [('step', C.c_long)] +
+                [(n, C.c_float) for n in ('grad_scale', 'clip_coef', 'weight_decay')] + [('ema_decay', C.c_double), ('ema_warmup', C.c_int),
+                                                                                       ('ema_updates', C.c_long), ('n_runs', C.c_int)] +
+                [('run_start', C.POINTER(C.c_long)), ('run_len', C.POINTER(C.c_int)), ('run_decayed', C.POINTER(C.c_int)), ('mode', C.c_int)])
+
+
 class SSPrepTask(C.Structure):
     """ss_prep_task (test hook ss_op_prep): dst = a + b (b NULL: a copy) over n floats, img (nullable) the image of dst."""
     _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('dst', C.c_void_p), ('n', C.c_long), ('img', C.c_void_p)]
@@ -132,6 +141,10 @@ SYMBOLS = {
     'ss_set_grad_clip': (_i, [_vp, _f, _vp]),
     'ss_grad_norm': (_i, [_vp, _f, _fp, _vp]),
     'ss_grad_clip_stats': (_i, [_vp, _fp, _vp]),
+    'ss_set_weight_decay': (_i, [_vp, _f, _i, _vp]),
+    'ss_set_ema': (_i, [_vp, _fp, _d, _i, _l, _vp]),
+    'ss_ema_swap': (_i, [_vp, _vp]),
+    'ss_ema_stats': (_i, [_vp, _fp, _vp]),
     'ss_interp_forward': (_i, [_vp, _fp, _ip, _fp, _ip, _i, _i, _i, _fp, _ip, _fp, _ip, _vp]),
     'ss_interp_backward': (_i, [_vp, _fp, _i, _i, _i, _fp, _vp]),
     'ss_check': (_i, [_vp, _vp]),
@@ -195,6 +208,8 @@ SYMBOLS = {
     # gamma[], beta[], C[], n, T, out, stream / p, n, limit, sticky, stream
     'ss_op_act_scales': (_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_i), _i, _i, _fp, _vp]),
     'ss_op_param_guard': (_i, [_fp, _l, _f, _vp, _vp]),
+    'ss_op_optim_ext': (_i, [C.POINTER(SSOptimExtOp), _vp]),
+    'ss_op_wd_runs': (_i, [_i, C.POINTER(SSHparams), C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int), _i]),
     'ss_op_split_image': (_i, [_fp, _l, _l, _i, _f, _fp, _l, _vp]),
     'ss_op_gemm_pre': (_i, [_fp, _l, _fp, _fp, _l, _fp, _fp, _l, _fp, _i, _i, _i, _i, _i, _vp]),
     'ss_op_gemm_img': (_i, [_fp, _l, _fp, _l, _fp, _l, _fp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _l, _fp, _vp, _vp]),

@@ -969,4 +969,67 @@ int ss_op_param_guard(const float* p, long n, float limit, unsigned* sticky, voi
     return 0;
 }
 
+int ss_op_optim_ext(const ss_optim_ext_op* o, void* stream) {
+    if (!o || !o->p || !o->state) return fail("ss_op_optim_ext: null pointer (the descriptor, p and state are required)");
+    if (o->mode < 0 || o->mode > 2) return fail("ss_op_optim_ext: mode must be 0 (optimiser step), 1 (ema_range) or 2 (arena_swap)");
+    if (o->lo < 0 || o->hi < o->lo || o->lo % 4 || o->hi % 4) return fail("ss_op_optim_ext: lo and hi must be multiples of 4 with 0 <= lo <= hi");
+    if (misaligned(o->p, 16) || misaligned(o->g, 16) || misaligned(o->m, 16) || misaligned(o->v, 16) || misaligned(o->ema, 16) || misaligned(o->state, 256))
+        return fail("ss_op_optim_ext: arenas must be 16-byte aligned and state 256-byte aligned");
+    if (o->mode == 0 && (!o->g || !o->m || !o->v)) return fail("ss_op_optim_ext: null pointer (an optimiser step needs g, m and v)");
+    if (o->mode != 0 && !o->ema) return fail("ss_op_optim_ext: null pointer (ema_range and arena_swap need ema)");
+    if (!(o->weight_decay >= 0.0f) || !(o->ema_decay >= 0.0 && o->ema_decay < 1.0) || o->n_runs < 0 || o->n_runs > WD_RUN_MAX || (o->n_runs && (!o->run_start || !o->run_len || !o->run_decayed)))
+        return fail("ss_op_optim_ext: weight_decay must be >= 0, ema_decay in [0, 1), n_runs in 0 .. 96 with its three arrays");
+    hipStream_t s = S(stream);
+    if (o->mode == 2) {
+        HIPCHK(arena_swap(o->p + o->lo, o->ema + o->lo, o->hi - o->lo, s));
+        return 0;
+    }
+    if (o->mode == 1 && o->step < 0) {      // the state as an earlier call left it: nothing is copied, nothing waited for, no prepare runs
+        HIPCHK(ema_range(o->ema + o->lo, o->p + o->lo, o->hi - o->lo, (const AdamState*)o->state,
+                         (const OptExtState*)((char*)o->state + OPT_EXT_STATE_BYTE), s));
+        return 0;
+    }
+    // the head of a workspace as ss_bind and the setters leave it: Adam state at byte 0, clip coefficient at 128, the extension at 144
+    alignas(16) char head[256] = {};
+    AdamState* st = (AdamState*)head;
+    ClipState* clip = (ClipState*)(head + CLIP_STATE_BYTE);
+    OptExtState* ext = (OptExtState*)(head + OPT_EXT_STATE_BYTE);
+    st->lr = o->lr;
+    st->beta1 = o->beta1;
+    st->beta2 = o->beta2;
+    st->eps = o->eps;
+    st->step = o->step;
+    clip->coef = o->clip_coef;
+    ext->ema_decay = o->ema_decay;
+    ext->n = o->ema_updates;
+    ext->wd = o->weight_decay;
+    ext->flags = (o->ema ? OPT_EXT_EMA : 0u) | (o->ema_warmup ? OPT_EXT_WARMUP : 0u);
+    HIPCHK(hipMemcpyAsync(o->state, head, 256, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    AdamState* dst = (AdamState*)o->state;
+    AdamExt x;
+    x.ext = (OptExtState*)((char*)o->state + OPT_EXT_STATE_BYTE);
+    x.wd = o->weight_decay > 0.0f;
+    x.ema = o->ema;
+    WdRunTable tb{};
+    if (x.wd && o->n_runs) {
+        tb.n = o->n_runs;
+        for (int k = 0; k < o->n_runs; ++k) {
+            tb.start[k] = o->run_start[k];
+            tb.len[k] = o->run_len[k];
+            tb.decayed[k] = o->run_decayed[k];
+        }
+        x.runs = &tb;
+    }
+    if (!x.on()) return fail("ss_op_optim_ext: neither weight decay nor an EMA arena: that is the plain Adam step");
+    HIPCHK(adam_prepare_ext(dst, x, nullptr, o->skip_status, s));
+    if (o->mode == 1) {
+        HIPCHK(ema_range(o->ema + o->lo, o->p + o->lo, o->hi - o->lo, dst, x.ext, s));
+        return 0;
+    }
+    const float* coef = o->clip_coef > 0.0f ? &((ClipState*)((char*)o->state + CLIP_STATE_BYTE))->coef : nullptr;
+    HIPCHK(adam_range_ext(o->p, o->g, o->m, o->v, o->lo, o->hi, dst, o->grad_scale, coef, x, s));
+    return 0;
+}
+
 }  // extern "C"

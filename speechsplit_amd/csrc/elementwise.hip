@@ -1000,7 +1000,25 @@ __global__ __launch_bounds__(64) void ce_kernel(const float* __restrict__ logits
 // ------------------------------------------------------------------------------------------------ Adam
 // torch.optim.Adam defaults as solver.py:62 constructs it (no amsgrad, no weight decay), single-tensor formulas:
 //   m = lerp(m, g, 1-b1); v = v*b2 + (1-b2) g*g; p -= step_size * m / (sqrt(v)/sqrt(bc2) + eps)
-__global__ void adam_prepare_kernel(AdamState* st, unsigned* sticky, const float* status) {
+// What an applied step sets beyond Adam (kernels.h, OptExtState): behind the skip decisions of both prepare kernels, by their one thread
+__device__ __forceinline__ void opt_ext_prepare(const AdamState* st, OptExtState* ext) {
+    if (!ext) return;
+    ext->decay_mul = (float)(1.0 - st->lr * (double)ext->wd);
+    ext->stats[2] = ext->decay_mul;
+    if (ext->flags & OPT_EXT_EMA) {
+        double d = ext->ema_decay;
+        if (ext->flags & OPT_EXT_WARMUP) {
+            const double n = (double)ext->n;
+            d = fmin(d, (1.0 + n) / (10.0 + n));
+        }
+        ext->ema_w = (float)(1.0 - d);
+        ext->n += 1;
+        ext->stats[0] = (float)ext->n;
+        ext->stats[1] = (float)d;
+    }
+}
+
+__global__ void adam_prepare_kernel(AdamState* st, unsigned* sticky, const float* status, OptExtState* ext) {
     const unsigned mine = sticky ? __hip_atomic_load(sticky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
     const bool remote = status && *status != 0.f;
     if (mine || remote) {          // this step's gradients are garbage somewhere: leave parameters, moments and step alone
@@ -1018,6 +1036,7 @@ __global__ void adam_prepare_kernel(AdamState* st, unsigned* sticky, const float
     st->f_beta1 = (float)st->beta1;
     st->f_beta2 = (float)st->beta2;
     st->f_eps = (float)st->eps;
+    opt_ext_prepare(st, ext);
 }
 
 // CLIP: the gradient is also multiplied by the clip coefficient adam_prepare_clip_kernel left in device memory (exactly 1.0f: the same bits)
@@ -1046,6 +1065,92 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         reinterpret_cast<f32x4*>(p)[i] = pv;
         reinterpret_cast<f32x4*>(m)[i] = mv;
         reinterpret_cast<f32x4*>(v)[i] = vv;
+    }
+}
+
+// adam_kernel with decoupled weight decay (WD) and / or the parameter average (EMA) in the same pass over [lo, hi) of the arenas (base
+// pointers).  TAB: decay on the table's decayed runs only.  The runs tile [lo, hi) (the launcher checks it), so each workgroup takes one
+// contiguous chunk of [lo, hi) and loops over the runs that meet its chunk, its threads striding inside: run bounds are wave-uniform
+// scalar loads, every global access a 16-byte one, and a short run (a bias) occupies the one or two workgroups it falls into instead of
+// costing the whole grid a sweep; an element outside a decayed run is multiplied by 1.0f (its bits).  HBM-bound: 28 B per element, 36
+// with the average.
+struct NoRuns {};
+template <bool CLIP, bool WD, bool EMA, bool TAB>
+__global__ __launch_bounds__(256) void adam_ext_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, float* __restrict__ ema, long lo, long hi,
+                                                       const AdamState* __restrict__ st, const OptExtState* __restrict__ ext, float gscale,
+                                                       const float* __restrict__ coef_p, const std::conditional_t<TAB, WdRunTable, NoRuns> tb) {
+    if (st->skip) return;
+    const float coef = CLIP ? *coef_p : 1.0f;
+    const float step_size = st->step_size, bc2s = st->bc2_sqrt, b2 = st->f_beta2, eps = st->f_eps;
+    const float w1 = (float)(1.0 - st->beta1), w2 = (float)(1.0 - st->beta2);
+    const float decay_mul = WD ? ext->decay_mul : 1.0f, ema_w = EMA ? ext->ema_w : 0.0f;
+    auto span = [&](long a, long b, float mul, long first, long stride) {
+        const long n4 = (b - a) >> 2;
+        f32x4* p4 = reinterpret_cast<f32x4*>(p + a);
+        const f32x4* g4 = reinterpret_cast<const f32x4*>(g + a);
+        f32x4* m4 = reinterpret_cast<f32x4*>(m + a);
+        f32x4* v4 = reinterpret_cast<f32x4*>(v + a);
+        f32x4* e4 = EMA ? reinterpret_cast<f32x4*>(ema + a) : nullptr;
+        for (long i = first; i < n4; i += stride) {
+            f32x4 pv = p4[i];
+            f32x4 gv = g4[i];
+            f32x4 mv = m4[i];
+            f32x4 vv = v4[i];
+            f32x4 ev;
+            if constexpr (EMA) ev = e4[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float gg = CLIP ? (gv[j] * gscale) * coef : gv[j] * gscale;
+                mv[j] = mv[j] + w1 * (gg - mv[j]);
+                vv[j] = vv[j] * b2 + w2 * gg * gg;
+                const float denom = sqrtf(vv[j]) / bc2s + eps;
+                const float p1 = WD ? pv[j] * mul : pv[j];
+                pv[j] = p1 - step_size * (mv[j] / denom);
+                if constexpr (EMA) ev[j] = ev[j] + ema_w * (pv[j] - ev[j]);
+            }
+            p4[i] = pv;
+            m4[i] = mv;
+            v4[i] = vv;
+            if constexpr (EMA) e4[i] = ev;
+        }
+    };
+    if constexpr (TAB) {
+        const long c4 = (((hi - lo) >> 2) + gridDim.x - 1) / gridDim.x;      // float4 elements per workgroup
+        const long clo = lo + 4 * c4 * blockIdx.x;
+        const long chi = clo + 4 * c4 < hi ? clo + 4 * c4 : hi;
+        for (int k = 0; k < tb.n; ++k) {
+            const long a = tb.start[k] > clo ? tb.start[k] : clo;
+            const long end = tb.start[k] + tb.len[k];
+            const long b = end < chi ? end : chi;
+            if (b > a) span(a, b, tb.decayed[k] ? decay_mul : 1.0f, threadIdx.x, 256);
+        }
+    } else {
+        span(lo, hi, decay_mul, blockIdx.x * 256L + threadIdx.x, (long)gridDim.x * 256);
+    }
+}
+
+// the average alone over a range whose parameters this step did not move (the encoder range of a decoder-only step)
+__global__ __launch_bounds__(256) void ema_range_kernel(float* __restrict__ ema, const float* __restrict__ p, long n4,
+                                                        const AdamState* __restrict__ st, const OptExtState* __restrict__ ext) {
+    if (st->skip) return;
+    const float ema_w = ext->ema_w;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];
+        f32x4 ev = reinterpret_cast<f32x4*>(ema)[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ev[j] = ev[j] + ema_w * (pv[j] - ev[j]);
+        reinterpret_cast<f32x4*>(ema)[i] = ev;
+    }
+}
+
+// elementwise exchange of two arenas
+__global__ __launch_bounds__(256) void arena_swap_kernel(float* __restrict__ a, float* __restrict__ b, long n4) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const f32x4 x = reinterpret_cast<f32x4*>(a)[i];
+        const f32x4 y = reinterpret_cast<f32x4*>(b)[i];
+        reinterpret_cast<f32x4*>(a)[i] = y;
+        reinterpret_cast<f32x4*>(b)[i] = x;
     }
 }
 
@@ -1101,7 +1206,8 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
 
 // adam_prepare_kernel with the global norm in front (one workgroup; thread 0 does what adam_prepare_kernel's only thread does)
 __global__ __launch_bounds__(256) void adam_prepare_clip_kernel(AdamState* st, ClipState* clip, unsigned* sticky, const float* status,
-                                                                const double* __restrict__ partials, int n, float gscale, float max_norm) {
+                                                                const double* __restrict__ partials, int n, float gscale, float max_norm,
+                                                                OptExtState* ext) {
     __shared__ double red[4];
     const double tot = partials_sum(partials, n, red);
     if (threadIdx.x != 0) return;
@@ -1135,6 +1241,7 @@ __global__ __launch_bounds__(256) void adam_prepare_clip_kernel(AdamState* st, C
     st->f_beta1 = (float)st->beta1;
     st->f_beta2 = (float)st->beta2;
     st->f_eps = (float)st->eps;
+    opt_ext_prepare(st, ext);
 }
 
 }  // namespace
@@ -1473,14 +1580,14 @@ hipError_t param_guard(const float* p, long n, float limit, unsigned* sticky, hi
 hipError_t adam_step(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, unsigned* sticky,
                      const float* status, hipStream_t s) {
     if (n % 4 != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, sticky, status);
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, sticky, status, (OptExtState*)nullptr);
     return adam_range(p, g, m, v, n, st, grad_scale, s);
 }
 
 // the update of one range of the arenas under the step state an earlier adam_prepare set (a step may update its ranges as their
 // gradients become final)
 hipError_t adam_prepare(AdamState* st, unsigned* sticky, const float* status, hipStream_t s) {
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, sticky, status);
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, sticky, status, (OptExtState*)nullptr);
     return hipGetLastError();
 }
 hipError_t adam_range(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, hipStream_t s) {
@@ -1512,7 +1619,89 @@ hipError_t grad_norm_finish(const double* partials, int n, float grad_scale, flo
 }
 hipError_t adam_prepare_clip(AdamState* st, ClipState* clip, unsigned* sticky, const float* status, const double* partials, int n,
                              float grad_scale, float max_norm, hipStream_t s) {
-    hipLaunchKernelGGL(adam_prepare_clip_kernel, dim3(1), dim3(256), 0, s, st, clip, sticky, status, partials, n, grad_scale, max_norm);
+    hipLaunchKernelGGL(adam_prepare_clip_kernel, dim3(1), dim3(256), 0, s, st, clip, sticky, status, partials, n, grad_scale, max_norm,
+                       (OptExtState*)nullptr);
+    return hipGetLastError();
+}
+
+// ---- weight decay and the parameter average (kernels.h, AdamExt)
+hipError_t adam_prepare_ext(AdamState* st, const AdamExt& x, unsigned* sticky, const float* status, hipStream_t s) {
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, sticky, status, x.on() ? x.ext : (OptExtState*)nullptr);
+    return hipGetLastError();
+}
+hipError_t adam_prepare_clip_ext(AdamState* st, ClipState* clip, const AdamExt& x, unsigned* sticky, const float* status, const double* partials,
+                                 int n, float grad_scale, float max_norm, hipStream_t s) {
+    hipLaunchKernelGGL(adam_prepare_clip_kernel, dim3(1), dim3(256), 0, s, st, clip, sticky, status, partials, n, grad_scale, max_norm,
+                       x.on() ? x.ext : (OptExtState*)nullptr);
+    return hipGetLastError();
+}
+
+namespace {
+template <bool CLIP, bool WD, bool EMA, bool TAB>
+void adam_ext_launch(int blocks, float* p, const float* g, float* m, float* v, long lo, long hi, AdamState* st, float grad_scale,
+                     const float* coef, const AdamExt& x, hipStream_t s) {
+    if constexpr (TAB)
+        hipLaunchKernelGGL((adam_ext_kernel<CLIP, WD, EMA, true>), dim3(blocks), dim3(256), 0, s, p, g, m, v, x.ema, lo, hi, st, x.ext, grad_scale,
+                           coef, *x.runs);
+    else
+        hipLaunchKernelGGL((adam_ext_kernel<CLIP, WD, EMA, false>), dim3(blocks), dim3(256), 0, s, p, g, m, v, x.ema, lo, hi, st, x.ext, grad_scale,
+                           coef, NoRuns{});
+}
+template <bool CLIP>
+void adam_ext_pick(int blocks, float* p, const float* g, float* m, float* v, long lo, long hi, AdamState* st, float grad_scale,
+                   const float* coef, const AdamExt& x, hipStream_t s) {
+    const bool tab = x.wd && x.runs;
+    if (x.wd && x.ema) {
+        if (tab) adam_ext_launch<CLIP, true, true, true>(blocks, p, g, m, v, lo, hi, st, grad_scale, coef, x, s);
+        else adam_ext_launch<CLIP, true, true, false>(blocks, p, g, m, v, lo, hi, st, grad_scale, coef, x, s);
+    } else if (x.wd) {
+        if (tab) adam_ext_launch<CLIP, true, false, true>(blocks, p, g, m, v, lo, hi, st, grad_scale, coef, x, s);
+        else adam_ext_launch<CLIP, true, false, false>(blocks, p, g, m, v, lo, hi, st, grad_scale, coef, x, s);
+    } else {
+        adam_ext_launch<CLIP, false, true, false>(blocks, p, g, m, v, lo, hi, st, grad_scale, coef, x, s);
+    }
+}
+}  // namespace
+
+hipError_t adam_range_ext(float* p, const float* g, float* m, float* v, long lo, long hi, AdamState* st, float grad_scale, const float* coef,
+                          const AdamExt& x, hipStream_t s) {
+    if (lo < 0 || hi < lo) return hipErrorInvalidValue;
+    if (!x.on()) return coef ? adam_range_clip(p + lo, g + lo, m + lo, v + lo, hi - lo, st, grad_scale, coef, s)
+                             : adam_range(p + lo, g + lo, m + lo, v + lo, hi - lo, st, grad_scale, s);
+    if (lo % 4 != 0 || hi % 4 != 0 || (((size_t)p | (size_t)g | (size_t)m | (size_t)v | (size_t)x.ema) & 15)) return hipErrorInvalidValue;
+    if (x.wd && x.runs) {       // the runs must be float4 spans that follow each other without a hole or an overlap and cover [lo, hi):
+                                // checked here, not trusted (the kernel hands each workgroup a chunk of [lo, hi) and the runs inside it)
+        const WdRunTable& t = *x.runs;
+        if (t.n < 1 || t.n > WD_RUN_MAX) return hipErrorInvalidValue;
+        for (int k = 0; k < t.n; ++k) {
+            if (t.start[k] % 4 != 0 || t.len[k] % 4 != 0 || t.len[k] <= 0 || t.start[k] < 0) return hipErrorInvalidValue;
+            if (k && t.start[k] != t.start[k - 1] + t.len[k - 1]) return hipErrorInvalidValue;
+        }
+        if (hi > lo && (t.start[0] > lo || t.start[t.n - 1] + t.len[t.n - 1] < hi)) return hipErrorInvalidValue;
+    }
+    if (hi == lo) return hipSuccess;
+    long blocks = ((hi - lo) / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (coef) adam_ext_pick<true>((int)blocks, p, g, m, v, lo, hi, st, grad_scale, coef, x, s);
+    else adam_ext_pick<false>((int)blocks, p, g, m, v, lo, hi, st, grad_scale, coef, x, s);
+    return hipGetLastError();
+}
+
+hipError_t ema_range(float* ema, const float* p, long n, const AdamState* st, const OptExtState* ext, hipStream_t s) {
+    if (!ema || !p || !ext || n % 4 != 0 || n < 0 || (((size_t)ema | (size_t)p) & 15)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    long blocks = (n / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(ema_range_kernel, dim3((int)blocks), dim3(256), 0, s, ema, p, n / 4, st, ext);
+    return hipGetLastError();
+}
+
+hipError_t arena_swap(float* a, float* b, long n, hipStream_t s) {
+    if (!a || !b || a == b || n % 4 != 0 || n < 0 || (((size_t)a | (size_t)b) & 15)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    long blocks = (n / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(arena_swap_kernel, dim3((int)blocks), dim3(256), 0, s, a, b, n / 4);
     return hipGetLastError();
 }
 

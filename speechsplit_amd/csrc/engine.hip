@@ -306,6 +306,14 @@ struct ss_engine {
     double* clip_part = nullptr;
     GradSegTable segs{};                   // runs of parameter elements of the arena (build_table)
     bool segs_ok = false;
+    // Decoupled weight decay and the parameter average (ss_set_weight_decay / ss_set_ema; kernels.h, OptExtState).  Host side: which form
+    // of the update every route enqueues (opt_ext); device side: the factors and the update counter, set by the step's one prepare.
+    float wd = 0.0f;                       // 0 off
+    int wd_which = 0;                      // 0 every element, 1 tensors with ndim >= 2 only (wd_runs)
+    float* ema = nullptr;                  // the caller's average arena; NULL off
+    OptExtState* ext = nullptr;            // workspace byte 144, beside the Adam and clip states
+    WdRunTable wd_runs{};                  // runs of [0, arena) by "decayed under which = 1" (build_table)
+    bool wd_runs_ok = false;
 
     // components
     ConvBlk c1[3], c2[3], ct;              // Encoder_7 stream 1 / stream 2 (or Encoder_6 in c2), Encoder_t
@@ -513,6 +521,28 @@ void build_table(ss_engine* e) {
             e->segs_ok = false;
         }
     }
+    // runs by "decayed under ss_set_weight_decay(which = 1)": a tensor's run reaches to the next tensor (its alignment gap included), tensors
+    // of the same class that follow each other merge, the status slot closes the table -- [0, arena) without a hole
+    e->wd_runs.n = 0;
+    e->wd_runs_ok = true;
+    for (size_t i = 0; i <= e->params.size(); ++i) {
+        WdRunTable& w = e->wd_runs;
+        const bool slot = i == e->params.size();
+        const long start = slot ? e->status_off : e->params[i].offset;
+        const long end = slot ? e->arena : (i + 1 < e->params.size() ? e->params[i + 1].offset : e->status_off);
+        const int dec = !slot && e->params[i].ndim >= 2;
+        if (start % 4 || end % 4 || end < start || end - start >= (1L << 31)) {
+            e->wd_runs_ok = false;
+        } else if (w.n && w.decayed[w.n - 1] == dec && w.start[w.n - 1] + w.len[w.n - 1] == start && w.len[w.n - 1] + (end - start) < (1L << 31)) {
+            w.len[w.n - 1] += (int)(end - start);
+        } else if (w.n < WD_RUN_MAX) {
+            w.start[w.n] = start;
+            w.len[w.n] = (int)(end - start);
+            w.decayed[w.n++] = dec;
+        } else {
+            e->wd_runs_ok = false;
+        }
+    }
     e->f0p = (int)((h.dim_f0 + 7) & ~7);      // a multiple of 8: the packed conv weights of convolutions_2[0] then have rows of whole image groups
     for (int i = 0; i < 3; ++i) {
         e->c1[i].need_dx = i > 0;
@@ -614,6 +644,7 @@ long carve(E& e, int B, int T) {
     };
     put(e.adam, sizeof(AdamState));                    // first: survives geometry changes (offset 0)
     if constexpr (assign) e.clip = (ClipState*)((char*)e.adam + CLIP_STATE_BYTE);      // same 256 bytes
+    if constexpr (assign) e.ext = (OptExtState*)((char*)e.adam + OPT_EXT_STATE_BYTE);
     if (e.kind != SS_INTERP_ONLY) put(e.clip_part, 2L * GRAD_SUMSQ_MAX_WGS * sizeof(double));     // scratch, geometry-independent (offset 256)
     if (e.kind == SS_INTERP_ONLY) {                    // a bare InterpLnr module only needs one plan
         for (int i = 0; i < 4; ++i) interp_ws(e.plan[i], i == 3);
@@ -884,6 +915,16 @@ long clip_split(const ss_engine* e) {
     return (k % 4 == 0 && k > 0 && k < e->status_off) ? k : 0;
 }
 int clip_wgs_lo(const ss_engine* e) { return clip_split(e) > 0 ? grad_sumsq_wgs(clip_split(e)) : 0; }
+// what every optimiser step of this engine does beyond Adam (ss_set_weight_decay, ss_set_ema): !on() while both are off, and every
+// route then enqueues exactly what it did before they existed
+AdamExt opt_ext(const ss_engine* e) {
+    AdamExt x;
+    x.ext = e->ext;
+    x.wd = e->wd > 0.0f;
+    x.runs = (x.wd && e->wd_which == 1) ? &e->wd_runs : nullptr;
+    x.ema = e->ema;
+    return x;
+}
 
 // launch the pending encoder-BLSTM weight-gradient tasks (one kernel for all of them) on `st`: everything they read must be complete in
 // st's order.  Scratch: partial tiles from the step's bump allocator, arrival counters from the column sums' ring.
@@ -2061,9 +2102,16 @@ int early_update(ss_engine* e, Backward& bw) {
             bw.clip_early_from = from;
         }
     } else if (from % 4 == 0 && from < e->arena) {
-        HIPCHK(adam_prepare(e->adam, e->sticky, nullptr, e->side));
-        Prof pr(e, SS_PROF_ADAM, e->side);
-        HIPCHK(adam_range(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, bw.adam_gs, e->side));
+        const AdamExt x = opt_ext(e);
+        if (x.on()) {         // decay and the average ride in the same launch; the step's ONE prepare sets their factors for both ranges
+            HIPCHK(adam_prepare_ext(e->adam, x, e->sticky, nullptr, e->side));
+            Prof pr(e, SS_PROF_ADAM, e->side);
+            HIPCHK(adam_range_ext(e->P, e->G, e->Mm, e->Vv, from, e->arena, e->adam, bw.adam_gs, nullptr, x, e->side));
+        } else {
+            HIPCHK(adam_prepare(e->adam, e->sticky, nullptr, e->side));
+            Prof pr(e, SS_PROF_ADAM, e->side);
+            HIPCHK(adam_range(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, bw.adam_gs, e->side));
+        }
         bw.adam_early_from = from;
     }
     return 0;
@@ -2542,6 +2590,9 @@ long ss_plan_bytes(const ss_engine* e, int B, int T) {
 static_assert(sizeof(AdamState) <= 256, "the Adam state is the workspace's first 256 bytes");
 static_assert(sizeof(AdamState) <= CLIP_STATE_BYTE && CLIP_STATE_BYTE + sizeof(ClipState) <= 256 && CLIP_STATE_BYTE % 16 == 0,
               "the clip state shares those 256 bytes (ss_set_adam rewrites sizeof(AdamState) of them, no more)");
+static_assert(OPT_EXT_STATE_BYTE >= CLIP_STATE_BYTE + (long)sizeof(ClipState) && OPT_EXT_STATE_BYTE + sizeof(OptExtState) <= 256 &&
+                  OPT_EXT_STATE_BYTE % 16 == 0 && offsetof(OptExtState, stats) == 0,
+              "the weight-decay / EMA state shares those 256 bytes too (its four stats words are handed out as one float4)");
 int ss_set_workspace(ss_engine* e, void* ws_dev, long bytes, void* stream) {
     CHK(guard(e, "ss_set_workspace", ANY | WS));
     if (!ws_dev || ((uintptr_t)ws_dev & 255)) return fail("ss_set_workspace: the workspace must be 256-byte aligned");
@@ -2619,6 +2670,9 @@ int ss_bind(ss_engine* e, float* params, float* grads, float* m, float* v, void*
         for (auto& ev : e->ev_join) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
     e->clip_max = 0.0f;       // the workspace (clip state included) starts zero: clipping is off until ss_set_grad_clip
+    e->wd = 0.0f;             // ... and so are weight decay and the parameter average (their device state is zero as well)
+    e->wd_which = 0;
+    e->ema = nullptr;
     AdamState st{};
     st.lr = 1e-4;
     st.beta1 = 0.9;
@@ -2663,6 +2717,26 @@ static int grad_norm_partials(ss_engine* e, bool have_hi, hipStream_t s, int* n)
 // bw: the backward this update follows, for what it has already sent to the side stream (a fresh one: nothing, the whole arena here)
 static int adam_enqueue(ss_engine* e, const Backward& bw, float grad_scale, hipStream_t s) {
     if (!e->ws || !e->Mm || !e->Vv) return fail("ss_adam_step: Adam arenas are not bound");
+    const AdamExt x = opt_ext(e);
+    if (x.on()) {             // weight decay and / or the parameter average: the same three schedules, the extended launches
+        if (e->clip_max > 0.0f) {
+            const bool have_hi = bw.clip_early_from >= 0 && bw.clip_early_from == clip_split(e);
+            int n = 0;
+            CHK(grad_norm_partials(e, have_hi, s, &n));
+            Prof pr(e, SS_PROF_ADAM, s);
+            HIPCHK(adam_prepare_clip_ext(e->adam, e->clip, x, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s));
+            HIPCHK(adam_range_ext(e->P, e->G, e->Mm, e->Vv, 0, e->arena, e->adam, grad_scale, &e->clip->coef, x, s));
+            return 0;
+        }
+        Prof pr(e, SS_PROF_ADAM, s);
+        if (bw.adam_early_from >= 0) {     // early_update prepared the step and updated [adam_early_from, arena): the rest under the same state
+            HIPCHK(adam_range_ext(e->P, e->G, e->Mm, e->Vv, 0, bw.adam_early_from, e->adam, grad_scale, nullptr, x, s));
+            return 0;
+        }
+        HIPCHK(adam_prepare_ext(e->adam, x, e->sticky, e->G + e->status_off, s));
+        HIPCHK(adam_range_ext(e->P, e->G, e->Mm, e->Vv, 0, e->arena, e->adam, grad_scale, nullptr, x, s));
+        return 0;
+    }
     if (e->clip_max > 0.0f) {              // global norm over the whole (all-reduced) arena, then ONE update launch with the coefficient
         const bool have_hi = bw.clip_early_from >= 0 && bw.clip_early_from == clip_split(e);
         int n = 0;
@@ -2724,6 +2798,72 @@ int ss_grad_clip_stats(ss_engine* e, float* out4_dev, void* stream) {
     CHK(guard(e, "ss_grad_clip_stats", GEN | WS));
     Own own(e, stream);
     HIPCHK(hipMemcpyAsync(out4_dev, e->clip, sizeof(ClipState), hipMemcpyDeviceToDevice, own.s));
+    return 0;
+}
+
+int ss_set_weight_decay(ss_engine* e, float weight_decay, int which, void* stream) {
+    CHK(guard(e, "ss_set_weight_decay", GEN | GRADS | ADAM));
+    if (!(weight_decay >= 0.0f) || !(weight_decay <= 3.402823466e+38f))
+        return fail("ss_set_weight_decay: weight_decay must be 0 (off) or positive and finite; negative, NaN and inf are refused");
+    if (which != 0 && which != 1) return fail("ss_set_weight_decay: which must be 0 (every parameter) or 1 (tensors with ndim >= 2 only)");
+    if (which == 1 && !e->wd_runs_ok) return fail("ss_set_weight_decay: the parameter table has more runs than WD_RUN_MAX");
+    Own own(e, stream);
+    // the device keeps the value the prepare kernels form the factor from (the host copy is pageable: the call returns once it is there)
+    HIPCHK(hipMemcpyAsync(&e->ext->wd, &weight_decay, sizeof(float), hipMemcpyHostToDevice, own.s));
+    HIPCHK(hipStreamSynchronize(own.s));
+    e->wd = weight_decay;
+    e->wd_which = which;
+    return 0;
+}
+
+int ss_op_wd_runs(int kind, const ss_hparams* hp, long* start, int* len, int* decayed, int cap) {
+    if (!start || !len || !decayed || cap < 0) return fail("ss_op_wd_runs: null pointer or negative cap");
+    ss_engine* e = ss_create(kind, hp, 1, 64);      // host side only: the parameter table and what build_table derives from it
+    if (!e) return -1;
+    const bool ok = e->kind != SS_INTERP_ONLY && e->wd_runs_ok;
+    const int n = ok ? e->wd_runs.n : 0;
+    for (int k = 0; k < n && k < cap; ++k) {
+        start[k] = e->wd_runs.start[k];
+        len[k] = e->wd_runs.len[k];
+        decayed[k] = e->wd_runs.decayed[k];
+    }
+    ss_destroy(e);
+    return ok ? n : fail("ss_op_wd_runs: an InterpLnr-only engine has no parameters, or the table has more runs than WD_RUN_MAX");
+}
+
+int ss_set_ema(ss_engine* e, float* ema_dev, double decay, int warmup, long updates, void* stream) {
+    CHK(guard(e, "ss_set_ema", GEN | GRADS | ADAM));
+    if (ema_dev && !(decay >= 0.0 && decay < 1.0)) return fail("ss_set_ema: decay must lie in [0, 1)");
+    if (ema_dev && ((uintptr_t)ema_dev & 15)) return fail("ss_set_ema: the EMA arena must be 16-byte aligned");
+    if (ema_dev && (ema_dev == e->P || ema_dev == e->G || ema_dev == e->Mm || ema_dev == e->Vv))
+        return fail("ss_set_ema: the EMA arena must be an arena of its own");
+    Own own(e, stream);
+    OptExtState st{};         // everything but wd starts again: the counter, the factors, the stats
+    st.ema_decay = ema_dev ? decay : 0.0;
+    st.n = ema_dev && updates > 0 ? updates : 0;
+    st.wd = e->wd;
+    st.flags = ema_dev ? (OPT_EXT_EMA | (warmup ? OPT_EXT_WARMUP : 0u)) : 0u;
+    st.stats[0] = (float)st.n;
+    if (ema_dev && updates < 0) HIPCHK(hipMemcpyAsync(ema_dev, e->P, e->arena * 4, hipMemcpyDeviceToDevice, own.s));
+    HIPCHK(hipMemcpyAsync(e->ext, &st, sizeof(st), hipMemcpyHostToDevice, own.s));
+    HIPCHK(hipStreamSynchronize(own.s));
+    e->ema = ema_dev;
+    return 0;
+}
+
+int ss_ema_swap(ss_engine* e, void* stream) {
+    CHK(guard(e, "ss_ema_swap", GEN | GRADS | ADAM));
+    if (!e->ema) return fail("ss_ema_swap: no EMA arena (call ss_set_ema first)");
+    Own own(e, stream);
+    HIPCHK(arena_swap(e->P, e->ema, e->arena, own.s));
+    return 0;
+}
+
+int ss_ema_stats(ss_engine* e, float* out4_dev, void* stream) {
+    CHK(guard(e, "ss_ema_stats", GEN | GRADS | ADAM));
+    if (!out4_dev) return fail("ss_ema_stats: null pointer");
+    Own own(e, stream);
+    HIPCHK(hipMemcpyAsync(out4_dev, e->ext->stats, 4 * sizeof(float), hipMemcpyDeviceToDevice, own.s));
     return 0;
 }
 
@@ -2959,6 +3099,19 @@ static int adam_decoder_enqueue(ss_engine* e, float grad_scale, hipStream_t s) {
     if (!e->ws || !e->Mm || !e->Vv) return fail("ss_adam_step_decoder: Adam arenas are not bound");
     const long from = grad_split(e);
     if (from % 4 || from >= e->arena) return fail("ss_adam_step_decoder: internal: the decoder range does not start on a multiple of 4 floats");
+    const AdamExt x = opt_ext(e);
+    if (x.on()) {             // decay inside the range only; the average over the WHOLE arena once: fused behind the update in the range,
+                              // a plain pass over the encoder range, whose parameters did not move but whose average still approaches them
+        const bool clip = e->clip_max > 0.0f;
+        int n = 0;
+        if (clip) CHK(grad_norm_partials(e, false, s, &n));
+        Prof pr(e, SS_PROF_ADAM, s);
+        if (clip) HIPCHK(adam_prepare_clip_ext(e->adam, e->clip, x, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s));
+        else HIPCHK(adam_prepare_ext(e->adam, x, e->sticky, e->G + e->status_off, s));
+        HIPCHK(adam_range_ext(e->P, e->G, e->Mm, e->Vv, from, e->arena, e->adam, grad_scale, clip ? &e->clip->coef : nullptr, x, s));
+        if (x.ema) HIPCHK(ema_range(x.ema, e->P, from, e->adam, e->ext, s));
+        return 0;
+    }
     if (e->clip_max > 0.0f) {
         int n = 0;
         CHK(grad_norm_partials(e, false, s, &n));

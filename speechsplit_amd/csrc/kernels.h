@@ -248,6 +248,53 @@ hipError_t adam_prepare_clip(AdamState* st, ClipState* clip, unsigned* sticky, c
 // adam_range with g * grad_scale * *coef (a coefficient of exactly 1.0f gives adam_range's bits)
 hipError_t adam_range_clip(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, const float* coef,
                            hipStream_t s);
+// ---- decoupled weight decay (torch.optim.AdamW, single-tensor formulas) and an exponential moving average of the parameters
+// (torch.optim.swa_utils.get_ema_avg_fn), both inside the optimiser step.  For an APPLIED step t (AdamState::skip == 0):
+//   decayed element:  p1 = p * decay_mul, decay_mul = (float)(1 - lr * wd) with the current lr (not lr / bc1); Adam then acts on p1
+//   every element:    ema' = ema + ema_w * (p' - ema), p' the parameter the step has just written, ema_w = (float)(1 - d_t),
+//                     d_t = decay, or with warm-up min(decay, (1 + n) / (10 + n)), n = EMA updates applied before this one
+// A skipped step changes none of it.  Device-resident beside AdamState and ClipState in the workspace's first 256 bytes (byte 144): the
+// prepare kernels form decay_mul and ema_w in double and advance n behind their skip decisions, once per step, so every range of one step
+// sees the same values.
+struct OptExtState {
+    float stats[4];       // {n, d_t of the last update, decay_mul of the last step, 0}: handed out as one float4 (ss_ema_stats)
+    double ema_decay;
+    long n;               // EMA updates applied
+    float wd, decay_mul, ema_w;
+    unsigned flags;       // OPT_EXT_EMA: the average is on; OPT_EXT_WARMUP: d_t warms up
+};
+constexpr long OPT_EXT_STATE_BYTE = 144;
+constexpr unsigned OPT_EXT_EMA = 1u, OPT_EXT_WARMUP = 2u;
+// Runs of the arena by "decayed or not" for weight decay on the tensors with ndim >= 2 only.  The runs cover [0, arena) without a hole
+// (a tensor's run takes the alignment gap behind it; the status slot is the last run), so starts and lengths are multiples of 4 floats.
+constexpr int WD_RUN_MAX = 96;
+struct WdRunTable {
+    int n;
+    int len[WD_RUN_MAX];
+    int decayed[WD_RUN_MAX];
+    long start[WD_RUN_MAX];
+};
+// What an optimiser step does beyond Adam.  ext (nullable: both terms off -- the launchers below then do exactly what they did before
+// the terms existed); wd: decay is on; runs (nullable: every element is decayed); ema (nullable: no average), the arena's base.
+struct AdamExt {
+    OptExtState* ext = nullptr;
+    bool wd = false;
+    const WdRunTable* runs = nullptr;
+    float* ema = nullptr;
+    bool on() const { return ext && (wd || ema); }
+};
+// adam_prepare / adam_prepare_clip that also set the step's decay_mul, ema_w and n (x.on(); otherwise the plain ones)
+hipError_t adam_prepare_ext(AdamState* st, const AdamExt& x, unsigned* sticky, const float* status, hipStream_t s);
+hipError_t adam_prepare_clip_ext(AdamState* st, ClipState* clip, const AdamExt& x, unsigned* sticky, const float* status, const double* partials,
+                                 int n, float grad_scale, float max_norm, hipStream_t s);
+// adam_range / adam_range_clip (coef non-null) over the elements [lo, hi) of arenas given by their BASE pointers, with decay and the fused
+// average under the step state the prepare set (lo, hi multiples of 4).  !x.on(): the plain launch on the offset pointers.
+hipError_t adam_range_ext(float* p, const float* g, float* m, float* v, long lo, long hi, AdamState* st, float grad_scale, const float* coef,
+                          const AdamExt& x, hipStream_t s);
+// ema[i] += ema_w * (p[i] - ema[i]) over n floats (a multiple of 4) under the step state: nothing when the step was skipped
+hipError_t ema_range(float* ema, const float* p, long n, const AdamState* st, const OptExtState* ext, hipStream_t s);
+// a[i] <-> b[i] over n floats (a multiple of 4)
+hipError_t arena_swap(float* a, float* b, long n, hipStream_t s);
 // *status = (*sticky != 0)   (one thread; enqueued behind the decoder's recurrences, in front of the all-reduce that sums it)
 hipError_t status_publish(const unsigned* sticky, float* status, hipStream_t s);
 // Scale of the fp16 x 2 split for the OUTPUT of each conv block (GroupNorm + ReLU, then resampled: a convex combination), from its affine

@@ -399,6 +399,7 @@ class Engine:
                              want_dc_trg=False):
         """Decode, MSE (mean) against target_mel, backward, Adam over the decoder + head range, in one call (ss_g3_decode_train_step).
         Returns the device loss, or (loss, dc_trg [B, dim_spk_emb]) with want_dc_trg.  no_adam: stop behind the backward."""
+        self._no_training_on_ema('g3_decode_train_step')
         B, T, (cx, cr, cf), c_trg = self._decode_args((codes_x, codes_r, codes_f0), c_trg)
         tgt = self._code_arg('target_mel', target_mel, (B, T, self.hp.dim_freq))
         dc = self._new('d_c_trg', (B, self.hp.dim_spk_emb)) if want_dc_trg else None
@@ -425,6 +426,7 @@ class Engine:
 
     def adam_step_decoder(self, grad_scale=1.0):
         """Adam on the decoder + head range [grad_split, arena) alone (ss_adam_step_decoder); the step counter advances by one."""
+        self._no_training_on_ema('adam_step_decoder')
         _capi.check(self.lib.ss_adam_step_decoder(self.h, float(grad_scale), _stream()))
 
     def g3_train_step(self, mel, f0, emb, len_org, draws, grad_scale=1.0, no_adam=False, split_backward=False, bucket=False,
@@ -435,6 +437,7 @@ class Engine:
         bucket: the batch's frame count is its length bucket and the step runs with max_len_pad = T (SS_STEP_BUCKET).
         accumulate: the backward ADDS to the gradient arena (SS_STEP_ACCUMULATE).  A cycle of k micro-batches: no_adam=True, then
         no_adam=True + accumulate=True k - 2 times, then accumulate=True with grad_scale = 1 / k."""
+        self._no_training_on_ema('g3_train_step')
         B, T, _ = mel.shape
         self._fwd_bt = None
         mel, f0, emb, len_org = self._f(mel), self._f(f0), self._f(emb), self._i(len_org)
@@ -446,6 +449,7 @@ class Engine:
         return self.loss
 
     def train_finish(self, grad_scale=1.0, no_adam=True):
+        self._no_training_on_ema('train_finish')
         _capi.check(self.lib.ss_train_finish(self.h, float(grad_scale), step_flags(no_adam=no_adam), _stream()))
 
     @property
@@ -471,6 +475,7 @@ class Engine:
         accumulate: this call is the LAST micro-batch of an accumulation cycle whose earlier ones went through
         g3_train_step(no_adam=True[, accumulate=True]) without any collective: its backward adds to the arena, the buckets reduce the
         local sums and Adam steps with 1 / (world * grad_accum_count)."""
+        self._no_training_on_ema('dp_train_step')
         from . import dist as D
         self._fwd_bt = None
         k = self.grad_split
@@ -514,6 +519,7 @@ class Engine:
     def dp_g6_train_step(self, mel, f0_onehot, target_idx, draws, world, group=None, bucket=False, accumulate=False):
         """Data-parallel Generator_6 step (BASELINE config 4): the arena is 14 MB, one pass of the bucket plan behind the backward.
         accumulate: the last micro-batch of an accumulation cycle, as in dp_train_step."""
+        self._no_training_on_ema('dp_g6_train_step')
         from . import dist as D
         self.g6_train_step(mel, f0_onehot, target_idx, draws, no_adam=True, bucket=bucket, accumulate=accumulate)
         D.reduce_arena(self.grads, self.grad_split, group)
@@ -563,6 +569,7 @@ class Engine:
         """ss_g3_dp_train_step: the overlapped two-bucket schedule with the collectives launched by the engine itself, the
         decoder bucket ON the engine stream that carries the decoder's weight-gradient GEMMs.  accumulate: the last micro-batch of an
         accumulation cycle (SS_STEP_ACCUMULATE): the buckets reduce the local sums, Adam steps with 1 / (world * grad_accum_count)."""
+        self._no_training_on_ema('dp_train_step_native')
         self._fwd_bt = None
         B, T, _ = mel.shape
         mel, f0, emb, len_org = self._f(mel), self._f(f0), self._f(emb), self._i(len_org)
@@ -602,6 +609,7 @@ class Engine:
 
     def g6_train_step(self, mel, f0_onehot, target_idx, draws, grad_scale=1.0, no_adam=False, bucket=False, accumulate=False):
         """accumulate: the backward adds to the gradient arena (SS_STEP_ACCUMULATE), as in g3_train_step."""
+        self._no_training_on_ema('g6_train_step')
         self._fwd_bt = None
         B, T, _ = mel.shape
         mel, f0_onehot, target_idx = self._f(mel), self._f(f0_onehot), self._i(target_idx)
@@ -614,6 +622,7 @@ class Engine:
     def g6_dp_train_step_native(self, mel, f0_onehot, target_idx, draws, bucket=False, accumulate=False):
         """ss_g6_dp_train_step: Generator_6's data-parallel step with the engine's own RCCL communicator (per-layer buckets on the
         engine's communication stream), as dp_train_step_native for Generator_3."""
+        self._no_training_on_ema('g6_dp_train_step_native')
         self._fwd_bt = None
         B, T, _ = mel.shape
         mel, f0_onehot, target_idx = self._f(mel), self._f(f0_onehot), self._i(target_idx)
@@ -624,6 +633,7 @@ class Engine:
 
     # ------------------------------------------------------------------ optimiser / misc
     def adam_step(self, grad_scale=1.0):
+        self._no_training_on_ema('adam_step')
         _capi.check(self.lib.ss_adam_step(self.h, float(grad_scale), _stream()))
 
     def set_grad_clip(self, max_norm):
@@ -644,6 +654,77 @@ class Engine:
         out = self._new('grad_clip_stats', (4,))
         _capi.check(self.lib.ss_grad_clip_stats(self.h, _ptr(out), _stream()))
         return out
+
+    # ------------------------------------------------------------------ weight decay / parameter EMA
+    WD_WHICH = {'all': 0, 'weights': 1}
+    ema = None                             # the average's arena while set_ema is on (a flat tensor like params)
+    _ema_swapped = False
+
+    def set_weight_decay(self, wd, which='all'):
+        """torch.optim.AdamW's decoupled weight decay inside every optimiser step (ss_set_weight_decay): None / 0 off (default).  which:
+        'all' every parameter (AdamW(G.parameters(), weight_decay=wd)), 'weights' tensors with ndim >= 2 only (biases and the GroupNorm
+        affine are left alone)."""
+        if which not in self.WD_WHICH:
+            raise ValueError(f"set_weight_decay: which must be 'all' or 'weights', not {which!r}")
+        _capi.check(self.lib.ss_set_weight_decay(self.h, float(wd or 0.0), self.WD_WHICH[which], _stream()))
+
+    def set_ema(self, decay, warmup=False, state=None):
+        """An exponential moving average of the parameters, updated inside every applied optimiser step (ss_set_ema): ema += (1 - d) * (p - ema),
+        d = decay, or with warmup min(decay, (1 + n) / (10 + n)).  decay None switches it off.  The arena comes from the engine's allocator
+        ('ema') and is self.ema / ema_views().  state = (tensor, updates): resume from a flat arena-sized average and its update count;
+        otherwise the average starts as a copy of the parameters with zero updates."""
+        if self._ema_swapped:
+            raise RuntimeError('set_ema inside ema_weights(): the parameters and their average are exchanged')
+        if decay is None:
+            _capi.check(self.lib.ss_set_ema(self.h, None, 0.0, 0, 0, _stream()))
+            self.ema = None
+            return
+        if self.ema is None:
+            with torch.cuda.device(self.device):
+                self.ema = self._new('ema', (self.params.numel(),), zero=True)
+        updates = -1
+        if state is not None:
+            t, updates = state
+            t = torch.as_tensor(t)
+            assert t.numel() == self.ema.numel() and int(updates) >= 0, 'set_ema: state = (arena-sized tensor, updates >= 0)'
+            self.ema.copy_(t.reshape(-1).to(device=self.device, dtype=torch.float32))
+        _capi.check(self.lib.ss_set_ema(self.h, _ptr(self.ema), float(decay), int(bool(warmup)), int(updates), _stream()))
+
+    def ema_views(self):
+        if self.ema is None:
+            raise RuntimeError('ema_views: no EMA (call set_ema first)')
+        return self.views(self.ema)
+
+    def ema_stats(self):
+        """Device tensor [4], no synchronisation (ss_ema_stats): EMA updates applied, d of the last update, weight-decay factor of the last
+        applied step, 0."""
+        out = self._new('ema_stats', (4,))
+        _capi.check(self.lib.ss_ema_stats(self.h, _ptr(out), _stream()))
+        return out
+
+    def ema_weights(self):
+        """Context manager: the engine runs on the averaged weights inside (ss_ema_swap on entry and again on exit, which restores the
+        parameters' bits).  Training and optimiser steps raise inside: they would train the average."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def swapped():
+            if self.ema is None:
+                raise RuntimeError('ema_weights: no EMA (call set_ema first)')
+            if self._ema_swapped:
+                raise RuntimeError('ema_weights: already inside ema_weights()')
+            _capi.check(self.lib.ss_ema_swap(self.h, _stream()))
+            self._ema_swapped = True
+            try:
+                yield self
+            finally:
+                self._ema_swapped = False
+                _capi.check(self.lib.ss_ema_swap(self.h, _stream()))
+        return swapped()
+
+    def _no_training_on_ema(self, what):
+        if self._ema_swapped:
+            raise RuntimeError(f'{what} inside ema_weights(): the step would train the averaged weights')
 
     def check(self):
         """Synchronise and raise if a kernel reported an asynchronous failure."""

@@ -24,6 +24,35 @@ from .staging import DevicePrefetcher
 from .utils import pad_seq_to_2, quantize_f0_numpy
 
 
+def _option(config, name, env, environ):
+    """config.<name>, or -- for the unchanged main.py, whose config has no such attribute -- the environment variable (empty: unset)"""
+    return getattr(config, name, None) if hasattr(config, name) else (environ.get(env) or None)
+
+
+def optim_ext_options(config, environ=None):
+    """(weight_decay, weight_decay_which, ema_decay or None, ema_warmup) from config.weight_decay / SS_WEIGHT_DECAY, config.weight_decay_which /
+    SS_WEIGHT_DECAY_WHICH ('all' | 'weights'), config.ema_decay / SS_EMA_DECAY and config.ema_warmup / SS_EMA_WARMUP, read the way grad_clip
+    is read.  Defaults: no decay, 'all', no average, no warm-up.  Needs no device."""
+    environ = os.environ if environ is None else environ
+    wd = _option(config, 'weight_decay', 'SS_WEIGHT_DECAY', environ)
+    wd = float(wd) if wd is not None else 0.0
+    if not (0.0 <= wd < float('inf')):
+        raise ValueError('weight_decay must be 0 / None (off) or positive and finite, got {!r}'.format(wd))
+    which = _option(config, 'weight_decay_which', 'SS_WEIGHT_DECAY_WHICH', environ) or 'all'
+    if which not in ('all', 'weights'):
+        raise ValueError("weight_decay_which must be 'all' or 'weights', got {!r}".format(which))
+    decay = _option(config, 'ema_decay', 'SS_EMA_DECAY', environ)
+    decay = float(decay) if decay is not None else None
+    if decay is not None and not (0.0 <= decay < 1.0):
+        raise ValueError('ema_decay must lie in [0, 1) (None: no average), got {!r}'.format(decay))
+    warm = _option(config, 'ema_warmup', 'SS_EMA_WARMUP', environ)
+    if isinstance(warm, str):
+        if warm.strip().lower() not in ('0', '1', 'true', 'false', 'yes', 'no', 'on', 'off'):
+            raise ValueError('ema_warmup must be a boolean (0 / 1), got {!r}'.format(warm))
+        warm = warm.strip().lower() in ('1', 'true', 'yes', 'on')
+    return wd, which, decay, bool(warm)
+
+
 class Solver(object):
     """Solver for training"""
 
@@ -58,6 +87,9 @@ class Solver(object):
         self.accum_steps = int(accum) if accum is not None else 1
         if self.accum_steps < 1:
             raise ValueError('accum_steps must be a positive integer, got {!r}'.format(accum))
+        # decoupled weight decay (AdamW) and an exponential moving average of the parameters, both inside the engine's optimiser step
+        # (Engine.set_weight_decay / set_ema); off by default, and then nothing is called and the checkpoints are the reference's
+        self.weight_decay, self.weight_decay_which, self.ema_decay, self.ema_warmup = optim_ext_options(config)
         self.use_cuda = torch.cuda.is_available()
         if not self.use_cuda:
             raise RuntimeError('speechsplit_amd.Solver needs a ROCm GPU (the engine has no CPU fallback)')
@@ -85,10 +117,15 @@ class Solver(object):
         self.step_count = 0
         if self.grad_clip:
             self.eng.set_grad_clip(self.grad_clip)
+        if self.weight_decay:
+            self.eng.set_weight_decay(self.weight_decay, self.weight_decay_which)
         if self.world > 1:
             _dist.init('nccl', self.device)
             import torch.distributed as dist
             dist.broadcast(self.eng.params, src=0)   # identical replicas
+        if self.ema_decay is not None:               # the average starts as a copy of the (broadcast) parameters
+            self.eng.set_ema(self.ema_decay, self.ema_warmup)
+        if self.world > 1:
             self.eng.set_lockstep(True)              # never refuse a step on the status word: check() reports it on every rank at the same iteration
             # the engine's own RCCL communicator: its data-parallel step launches the collectives on the engine's streams and costs
             # nothing over the one-GPU step, where torch.distributed's path measured +0.5 ms
@@ -107,9 +144,11 @@ class Solver(object):
         mv, vv = self.eng.views(self.eng.adam_m), self.eng.views(self.eng.adam_v)
         state = {i: {'step': torch.tensor(float(self.step_count)), 'exp_avg': mv[n].detach().cpu().clone(),
                      'exp_avg_sq': vv[n].detach().cpu().clone()} for i, n in enumerate(self.G._names)}
-        group = {'lr': self.g_lr, 'betas': (self.beta1, self.beta2), 'eps': 1e-8, 'weight_decay': 0, 'amsgrad': False,
+        group = {'lr': self.g_lr, 'betas': (self.beta1, self.beta2), 'eps': 1e-8, 'weight_decay': self.weight_decay or 0, 'amsgrad': False,
                  'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
                  'params': list(range(len(self.G._names)))}
+        if self.weight_decay:
+            group['weight_decay_which'] = self.weight_decay_which
         return {'state': state if self.step_count else {}, 'param_groups': [group]}
 
     def load_optimizer_state_dict(self, sd):
@@ -127,11 +166,28 @@ class Solver(object):
             step = int(st['step'])
         self.step_count = step
         self.eng.set_adam(self.g_lr, self.beta1, self.beta2, group.get('eps', 1e-8), step)
+        # A decay the checkpoint was trained with wins, as its lr and betas do.  A checkpoint WITHOUT one (every checkpoint from before the
+        # option existed stores 0) leaves a configured decay in force: that is how decay is switched on for a run that is under way.
+        stored = float(group.get('weight_decay') or 0.0)
+        if stored:
+            which = group.get('weight_decay_which', 'all')
+            if self.weight_decay and (self.weight_decay, self.weight_decay_which) != (stored, which) and self.rank == 0:
+                print('Note: the checkpoint\'s weight decay {} ({}) replaces the configured {} ({})'.format(
+                    stored, which, self.weight_decay, self.weight_decay_which))
+            self.weight_decay, self.weight_decay_which = stored, which
+            self.eng.set_weight_decay(stored, which)
+        elif self.weight_decay and self.rank == 0:
+            print('Note: the checkpoint was written without weight decay; the configured {} ({}) applies from here on'.format(
+                self.weight_decay, self.weight_decay_which))
 
     def save_model(self, it):
         G_path = os.path.join(self.model_save_dir, '{}-G.ckpt'.format(it))
-        torch.save({'model': {k: v.detach().cpu() for k, v in self.G.state_dict().items()},
-                    'optimizer': self.optimizer_state_dict()}, G_path)
+        ckpt = {'model': {k: v.detach().cpu() for k, v in self.G.state_dict().items()}, 'optimizer': self.optimizer_state_dict()}
+        if self.eng.ema is not None:      # the average under the model's keys (buffers as they are: it loads into a fresh generator), and its update count
+            ema = self.eng.ema_views()
+            ckpt['model_ema'] = {k: (ema[k] if k in ema else v).detach().cpu().clone() for k, v in ckpt['model'].items()}
+            ckpt['ema_updates'] = int(self.eng.ema_stats()[0].item())
+        torch.save(ckpt, G_path)
 
     def restore_model(self, resume_iters):
         print('Loading the trained models from step {}...'.format(resume_iters))
@@ -139,6 +195,21 @@ class Solver(object):
         ckpt = torch.load(G_path, map_location=lambda storage, loc: storage, weights_only=False)
         self.G.load_state_dict(ckpt['model'])
         self.load_optimizer_state_dict(ckpt['optimizer'])
+        if self.ema_decay is not None:
+            if 'model_ema' in ckpt:       # the average and its update count back; parameters without an average of their own start one
+                flat = self.eng.params.clone()
+                views = self.eng.views(flat)
+                for k, v in ckpt['model_ema'].items():
+                    if k in views:
+                        views[k].copy_(v)
+                self.eng.set_ema(self.ema_decay, self.ema_warmup, state=(flat, int(ckpt.get('ema_updates', 0))))
+            else:
+                if self.rank == 0:
+                    print('Note: the checkpoint holds no parameter average; the EMA starts from the restored parameters')
+                self.eng.set_ema(self.ema_decay, self.ema_warmup)
+        elif 'model_ema' in ckpt and self.rank == 0:
+            print('Warning: the checkpoint holds a parameter average (\'model_ema\', {} updates) but no ema_decay is configured: it is not '
+                  'restored and the next checkpoint will not carry one'.format(ckpt.get('ema_updates', 0)))
 
     # ---- one iteration of solver.py:141-172 on a collated batch
     N_DRAWS = 4                    # InterpLnr calls per step: the outer one and Encoder_7's three (SolverF0: Encoder_6's three)
@@ -194,9 +265,13 @@ class Solver(object):
         return total.div_(k)
 
     # ---- validation on demo.pkl-style data (solver.py:206-227) and the ablation forwards of solver.py:245-251 (no plots)
-    def validate(self, validation_pt, ablations=False):
+    def validate(self, validation_pt, ablations=False, ema=False):
         """validation_pt: list of [speaker, emb f32[1,82], (mel f32[L,80], f0 f32[L], L, uid)] (assets/demo.pkl layout).
-        Returns (mean sum-reduced MSE, per-utterance dict of outputs).  G stays in eval mode afterwards, as in the reference."""
+        Returns (mean sum-reduced MSE, per-utterance dict of outputs).  G stays in eval mode afterwards, as in the reference.
+        ema: on the averaged weights (inside Engine.ema_weights(); the parameters have their bits back afterwards)."""
+        if ema:
+            with self.eng.ema_weights():
+                return self.validate(validation_pt, ablations)
         import numpy as np
         self.G = self.G.eval()
         losses, outs = [], {}
@@ -296,6 +371,9 @@ class Solver(object):
                 flush(True)
                 val_loss, _ = self.validate(validation_pt)
                 print('Validation loss: {}'.format(val_loss))
+                if self.eng.ema is not None:
+                    val_loss, _ = self.validate(validation_pt, ema=True)
+                    print('Validation loss (EMA): {}'.format(val_loss))
         flush(True)
         self.eng.check()                                          # the last steps too (synchronises)
 
@@ -326,5 +404,5 @@ class SolverF0(Solver):
             return self.eng.g6_dp_train_step_native(*args, bucket=bucket, accumulate=accumulate)
         return self.eng.g6_train_step(*args, grad_scale=grad_scale, bucket=bucket, accumulate=accumulate)
 
-    def validate(self, validation_pt, ablations=False):
+    def validate(self, validation_pt, ablations=False, ema=False):
         raise NotImplementedError('the reference validates Generator_3 only (solver.py:206-227)')
