@@ -412,6 +412,43 @@ int ss_set_ema(ss_engine* e, float* ema_dev, double decay, int warmup, long upda
 int ss_ema_swap(ss_engine* e, void* stream);
 int ss_ema_stats(ss_engine* e, float* out4_dev, void* stream);
 
+/* ---- learning-rate warm-up and decay inside the optimiser step, keyed on the device's own step counter (nothing to mirror: the reference's
+ *      solver trains at a constant rate; the closed forms are those of torch.optim.lr_scheduler) ----
+ * DEFINITION (float64 on the device, one thread, once per APPLIED step, every product and sum rounded on its own).  base is the lr of
+ *   ss_set_adam.  t is the optimiser step being applied: 1-based, already incremented, exactly the t of the bias corrections.  s = t - 1.
+ *   WARM-UP of W = warmup_steps >= 0 steps from the factor sf = warmup_start, 0 < sf <= 1:
+ *     if W > 0 and s < W:  lr_t = base * (sf + (1 - sf) * ((double)s / (double)W))
+ *   MAIN PART otherwise, with k = s - W, N = total_steps, P = period:
+ *     kind 1 constant                         lr_t = base
+ *     kind 2 cosine      (N >= 1, min_lr)     kk = min(k, N); lr_t = min_lr + (base - min_lr) * (0.5 * (1 + cospi((double)kk / (double)N)))
+ *     kind 3 linear      (N >= 1, min_lr)     kk = min(k, N); lr_t = base + (min_lr - base) * ((double)kk / (double)N)
+ *     kind 4 exponential (0 < gamma <= 1)     lr_t = max(base * pow(gamma, (double)k), min_lr)
+ *     kind 5 step        (gamma, P >= 1)      lr_t = max(base * pow(gamma, (double)(k / P)), min_lr), integer division
+ *   kind 0 is off: lr_t = base, the default and what ss_bind restores.
+ * CONSUMERS: step_size = (float)(lr_t / bc1) and, under ss_set_weight_decay, the decay factor (float)(1 - lr_t * weight_decay).  Nothing else
+ *   changes: the moments, the EMA, the clip coefficient and the bias corrections are what they were.
+ * IN TORCH: SequentialLR(opt, [LinearLR(opt, sf, 1.0, W), main], [W]), or main alone when W = 0, with main = CosineAnnealingLR(T_max=N,
+ *   eta_min=min_lr), LinearLR(1.0, min_lr / base, N), ExponentialLR(gamma) or StepLR(P, gamma), the rate read before each optimizer.step().
+ *   Two deliberate differences: past N, cosine and linear STAY at min_lr (torch's cosine turns back up); and min_lr also floors the two
+ *   geometric kinds (with min_lr = 0 they are torch's).
+ * SKIPS: a step skipped on the device (status word, remote status, non-finite norm under clipping) leaves t alone, so the next applied step
+ *   carries the rate of the SAME t; the words of ss_lr_stats do not move either.
+ * POSITION: the schedule reads t, so ss_set_adam(..., step) positions it, and a run resumed from a checkpoint's step count lands on the right
+ *   point without any further state.  In an accumulation cycle t counts optimiser steps, not micro-batches.
+ * The options live in device memory beside the Adam state and survive what it survives (geometry changes, ss_set_workspace, ss_set_adam).
+ * Every route to the optimiser picks the rate up from its one prepare kernel: the fused step, SS_STEP_BUCKET, SS_STEP_NO_ADAM + ss_adam_step,
+ * ss_train_finish, both data-parallel steps, ss_adam_step_decoder, ss_g3_decode_train_step, both generators, both precisions.  With kind 0
+ * every entry point enqueues exactly the kernels and arguments it did before these calls existed.
+ * ss_set_lr_schedule: refused, with nothing enqueued: an engine without the optimiser's binding (both Adam arenas); then a kind outside
+ *   0 .. 5; and for a kind other than 0: warmup_steps < 0; warmup_start outside (0, 1] or NaN; total_steps < 1 for cosine and linear; gamma
+ *   outside (0, 1] or NaN for exponential and step; period < 1 for step; a negative or non-finite min_lr.  Options the kind does not read
+ *   are ignored.  The words of ss_lr_stats start again (zero, and the kind).  Both calls name a bad argument AFTER a missing binding.
+ * ss_lr_stats: asynchronous device-to-device copy of four floats {(float)lr_t of the last applied step, (float)(lr_t / base), t, kind}; no
+ *   synchronisation, as ss_grad_clip_stats.  (Floats: t is exact up to 2^24.) */
+int ss_set_lr_schedule(ss_engine* e, int kind, int warmup_steps, double warmup_start, int total_steps, double gamma, int period, double min_lr,
+                       void* stream);
+int ss_lr_stats(ss_engine* e, float* out4_dev, void* stream);
+
 /* ---- InterpLnr as a standalone module (model.py:355-436; solver.py:59,161) ---- */
 /* x [B,T,C], len_seq i32[B], draws [B*7] -> y [B,max_len_pad,C].  Optional outputs (may be NULL): i0 i32[B,P],
  * lam f32[B,P], counts i32[B] (un-truncated, model.py:418). */
@@ -1237,6 +1274,11 @@ int ss_op_optim_ext(const ss_optim_ext_op* op, void* stream);
  * hyper-parameters builds from its parameter table -- up to cap of them into start / len / decayed; returns their number (negative: refused).
  * The runs cover the arena without a hole: a tensor's run takes the alignment gap behind it, the status slot is the last run, not decayed. */
 int ss_op_wd_runs(int kind, const ss_hparams* hp, long* start, int* len, int* decayed, int cap);
+/* Test hook, engine-free: lr_dev[i] = lr_t of ss_set_lr_schedule's definition at t = steps_dev[i] (n device longs -> n device doubles), by the
+ * __device__ function the optimiser's prepare kernels call, one thread per value.  Refused: what ss_set_lr_schedule refuses, null pointers,
+ * n outside 1 .. 2^24. */
+int ss_op_lr_schedule(int kind, double base, int warmup_steps, double warmup_start, int total_steps, double gamma, int period, double min_lr,
+                      const long* steps_dev, long n, double* lr_dev, void* stream);
 /* The GEMM over operand images (speechsplit_amd/csrc/gemm_img.hip), the engine's default for every large contraction: an IMAGE has the
  * geometry of its fp32 matrix (4 bytes per element) with every aligned group of 8 elements along the contiguous axis replaced by 16 bytes of
  * hi pieces and 16 bytes of lo pieces of the fp16 x 2 split of scale * x (scale a power of two).

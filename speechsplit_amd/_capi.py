@@ -145,6 +145,8 @@ SYMBOLS = {
     'ss_set_ema': (_i, [_vp, _fp, _d, _i, _l, _vp]),
     'ss_ema_swap': (_i, [_vp, _vp]),
     'ss_ema_stats': (_i, [_vp, _fp, _vp]),
+    'ss_set_lr_schedule': (_i, [_vp, _i, _i, _d, _i, _d, _i, _d, _vp]),
+    'ss_lr_stats': (_i, [_vp, _fp, _vp]),
     'ss_interp_forward': (_i, [_vp, _fp, _ip, _fp, _ip, _i, _i, _i, _fp, _ip, _fp, _ip, _vp]),
     'ss_interp_backward': (_i, [_vp, _fp, _i, _i, _i, _fp, _vp]),
     'ss_check': (_i, [_vp, _vp]),
@@ -210,6 +212,7 @@ SYMBOLS = {
     'ss_op_param_guard': (_i, [_fp, _l, _f, _vp, _vp]),
     'ss_op_optim_ext': (_i, [C.POINTER(SSOptimExtOp), _vp]),
     'ss_op_wd_runs': (_i, [_i, C.POINTER(SSHparams), C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int), _i]),
+    'ss_op_lr_schedule': (_i, [_i, _d, _i, _d, _i, _d, _i, _d, _vp, _l, _vp, _vp]),
     'ss_op_split_image': (_i, [_fp, _l, _l, _i, _f, _fp, _l, _vp]),
     'ss_op_gemm_pre': (_i, [_fp, _l, _fp, _fp, _l, _fp, _fp, _l, _fp, _i, _i, _i, _i, _i, _vp]),
     'ss_op_gemm_img': (_i, [_fp, _l, _fp, _l, _fp, _l, _fp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _l, _fp, _vp, _vp]),

@@ -1032,4 +1032,23 @@ int ss_op_optim_ext(const ss_optim_ext_op* o, void* stream) {
     return 0;
 }
 
+int ss_op_lr_schedule(int kind, double base, int warmup_steps, double warmup_start, int total_steps, double gamma, int period, double min_lr,
+                      const long* steps_dev, long n, double* lr_dev, void* stream) {
+    if (const char* why = lr_schedule_refusal(kind, warmup_steps, warmup_start, total_steps, gamma, period, min_lr))
+        return fail(std::string("ss_op_lr_schedule: ") + why);
+    if (!steps_dev || !lr_dev) return fail("ss_op_lr_schedule: null pointer");
+    if (n < 1 || n > (1L << 24)) return fail("ss_op_lr_schedule: n must lie in 1 .. 2^24");
+    if (misaligned(steps_dev, 8) || misaligned(lr_dev, 8)) return fail("ss_op_lr_schedule: steps_dev and lr_dev must be 8-byte aligned");
+    LrSchedState q{};         // as ss_set_lr_schedule leaves it on the device
+    q.kind = kind;
+    q.W = warmup_steps;
+    q.sf = warmup_start;
+    q.N = total_steps > 0 ? total_steps : 1;
+    q.gamma = gamma;
+    q.P = period > 0 ? period : 1;
+    q.min_lr = min_lr;
+    HIPCHK(lr_schedule_eval(q, base, steps_dev, n, lr_dev, S(stream)));
+    return 0;
+}
+
 }  // extern "C"

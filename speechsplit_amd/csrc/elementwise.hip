@@ -1001,9 +1001,9 @@ __global__ __launch_bounds__(64) void ce_kernel(const float* __restrict__ logits
 // torch.optim.Adam defaults as solver.py:62 constructs it (no amsgrad, no weight decay), single-tensor formulas:
 //   m = lerp(m, g, 1-b1); v = v*b2 + (1-b2) g*g; p -= step_size * m / (sqrt(v)/sqrt(bc2) + eps)
 // What an applied step sets beyond Adam (kernels.h, OptExtState): behind the skip decisions of both prepare kernels, by their one thread
-__device__ __forceinline__ void opt_ext_prepare(const AdamState* st, OptExtState* ext) {
+__device__ __forceinline__ void opt_ext_prepare(const double lr_t, OptExtState* ext) {
     if (!ext) return;
-    ext->decay_mul = (float)(1.0 - st->lr * (double)ext->wd);
+    ext->decay_mul = (float)(1.0 - lr_t * (double)ext->wd);
     ext->stats[2] = ext->decay_mul;
     if (ext->flags & OPT_EXT_EMA) {
         double d = ext->ema_decay;
@@ -1018,7 +1018,51 @@ __device__ __forceinline__ void opt_ext_prepare(const AdamState* st, OptExtState
     }
 }
 
-__global__ void adam_prepare_kernel(AdamState* st, unsigned* sticky, const float* status, OptExtState* ext) {
+// The learning rate of the applied step t (kernels.h, LrSchedState): float64, every product and sum rounded on its own (no fma), so the
+// value is the one a float64 restatement of the same operations gives up to pow and cospi
+__device__ __noinline__ double lr_schedule(const LrSchedState& q, const double base, const long t) {
+#pragma clang fp contract(off)
+    const long s = t - 1;
+    if (q.kind == LR_OFF) return base;
+    if (q.W > 0 && s < (long)q.W) return base * (q.sf + (1.0 - q.sf) * ((double)s / (double)q.W));
+    const long k = s - (long)q.W;
+    switch (q.kind) {
+        case LR_COSINE: {
+            const long kk = k < (long)q.N ? k : (long)q.N;
+            return q.min_lr + (base - q.min_lr) * (0.5 * (1.0 + cospi((double)kk / (double)q.N)));
+        }
+        case LR_LINEAR: {
+            const long kk = k < (long)q.N ? k : (long)q.N;
+            return base + (q.min_lr - base) * ((double)kk / (double)q.N);
+        }
+        case LR_EXPONENTIAL:
+            return fmax(base * pow(q.gamma, (double)k), q.min_lr);
+        case LR_STEP:
+            return fmax(base * pow(q.gamma, (double)(k / (long)q.P)), q.min_lr);
+        default:
+            return base;      // LR_CONSTANT
+    }
+}
+
+// the applied step's rate and its stats words: right behind st->step += 1 in both prepare kernels, by their one thread.  sch NULL: the
+// base rate, and nothing else is read or written
+__device__ __forceinline__ double lr_prepare(const AdamState* st, LrSchedState* sch) {
+    if (!sch) return st->lr;
+    const double lr_t = lr_schedule(*sch, st->lr, st->step);
+    sch->stats[0] = (float)lr_t;
+    sch->stats[1] = (float)(lr_t / st->lr);
+    sch->stats[2] = (float)st->step;
+    sch->stats[3] = (float)sch->kind;
+    return lr_t;
+}
+
+__global__ __launch_bounds__(64) void lr_schedule_eval_kernel(const LrSchedState q, const double base, const long* __restrict__ steps, long n,
+                                                              double* __restrict__ lr) {
+    const long i = blockIdx.x * 64L + threadIdx.x;
+    if (i < n) lr[i] = lr_schedule(q, base, steps[i]);
+}
+
+__global__ void adam_prepare_kernel(AdamState* st, unsigned* sticky, const float* status, OptExtState* ext, LrSchedState* sch) {
     const unsigned mine = sticky ? __hip_atomic_load(sticky, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
     const bool remote = status && *status != 0.f;
     if (mine || remote) {          // this step's gradients are garbage somewhere: leave parameters, moments and step alone
@@ -1031,12 +1075,13 @@ __global__ void adam_prepare_kernel(AdamState* st, unsigned* sticky, const float
     const double t = (double)st->step;
     const double bc1 = 1.0 - pow(st->beta1, t);
     const double bc2 = 1.0 - pow(st->beta2, t);
-    st->step_size = (float)(st->lr / bc1);
+    const double lr_t = lr_prepare(st, sch);
+    st->step_size = (float)(lr_t / bc1);
     st->bc2_sqrt = (float)sqrt(bc2);
     st->f_beta1 = (float)st->beta1;
     st->f_beta2 = (float)st->beta2;
     st->f_eps = (float)st->eps;
-    opt_ext_prepare(st, ext);
+    opt_ext_prepare(lr_t, ext);
 }
 
 // CLIP: the gradient is also multiplied by the clip coefficient adam_prepare_clip_kernel left in device memory (exactly 1.0f: the same bits)
@@ -1207,7 +1252,7 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
 // adam_prepare_kernel with the global norm in front (one workgroup; thread 0 does what adam_prepare_kernel's only thread does)
 __global__ __launch_bounds__(256) void adam_prepare_clip_kernel(AdamState* st, ClipState* clip, unsigned* sticky, const float* status,
                                                                 const double* __restrict__ partials, int n, float gscale, float max_norm,
-                                                                OptExtState* ext) {
+                                                                OptExtState* ext, LrSchedState* sch) {
     __shared__ double red[4];
     const double tot = partials_sum(partials, n, red);
     if (threadIdx.x != 0) return;
@@ -1236,12 +1281,13 @@ __global__ __launch_bounds__(256) void adam_prepare_clip_kernel(AdamState* st, C
     const double t = (double)st->step;
     const double bc1 = 1.0 - pow(st->beta1, t);
     const double bc2 = 1.0 - pow(st->beta2, t);
-    st->step_size = (float)(st->lr / bc1);
+    const double lr_t = lr_prepare(st, sch);
+    st->step_size = (float)(lr_t / bc1);
     st->bc2_sqrt = (float)sqrt(bc2);
     st->f_beta1 = (float)st->beta1;
     st->f_beta2 = (float)st->beta2;
     st->f_eps = (float)st->eps;
-    opt_ext_prepare(st, ext);
+    opt_ext_prepare(lr_t, ext);
 }
 
 }  // namespace
@@ -1578,16 +1624,16 @@ hipError_t param_guard(const float* p, long n, float limit, unsigned* sticky, hi
 }
 
 hipError_t adam_step(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, unsigned* sticky,
-                     const float* status, hipStream_t s) {
+                     const float* status, hipStream_t s, LrSchedState* sch) {
     if (n % 4 != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, sticky, status, (OptExtState*)nullptr);
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, sticky, status, (OptExtState*)nullptr, sch);
     return adam_range(p, g, m, v, n, st, grad_scale, s);
 }
 
 // the update of one range of the arenas under the step state an earlier adam_prepare set (a step may update its ranges as their
 // gradients become final)
-hipError_t adam_prepare(AdamState* st, unsigned* sticky, const float* status, hipStream_t s) {
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, sticky, status, (OptExtState*)nullptr);
+hipError_t adam_prepare(AdamState* st, unsigned* sticky, const float* status, hipStream_t s, LrSchedState* sch) {
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, sticky, status, (OptExtState*)nullptr, sch);
     return hipGetLastError();
 }
 hipError_t adam_range(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, hipStream_t s) {
@@ -1618,21 +1664,21 @@ hipError_t grad_norm_finish(const double* partials, int n, float grad_scale, flo
     return hipGetLastError();
 }
 hipError_t adam_prepare_clip(AdamState* st, ClipState* clip, unsigned* sticky, const float* status, const double* partials, int n,
-                             float grad_scale, float max_norm, hipStream_t s) {
+                             float grad_scale, float max_norm, hipStream_t s, LrSchedState* sch) {
     hipLaunchKernelGGL(adam_prepare_clip_kernel, dim3(1), dim3(256), 0, s, st, clip, sticky, status, partials, n, grad_scale, max_norm,
-                       (OptExtState*)nullptr);
+                       (OptExtState*)nullptr, sch);
     return hipGetLastError();
 }
 
 // ---- weight decay and the parameter average (kernels.h, AdamExt)
-hipError_t adam_prepare_ext(AdamState* st, const AdamExt& x, unsigned* sticky, const float* status, hipStream_t s) {
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, sticky, status, x.on() ? x.ext : (OptExtState*)nullptr);
+hipError_t adam_prepare_ext(AdamState* st, const AdamExt& x, unsigned* sticky, const float* status, hipStream_t s, LrSchedState* sch) {
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(1), 0, s, st, sticky, status, x.on() ? x.ext : (OptExtState*)nullptr, sch);
     return hipGetLastError();
 }
 hipError_t adam_prepare_clip_ext(AdamState* st, ClipState* clip, const AdamExt& x, unsigned* sticky, const float* status, const double* partials,
-                                 int n, float grad_scale, float max_norm, hipStream_t s) {
+                                 int n, float grad_scale, float max_norm, hipStream_t s, LrSchedState* sch) {
     hipLaunchKernelGGL(adam_prepare_clip_kernel, dim3(1), dim3(256), 0, s, st, clip, sticky, status, partials, n, grad_scale, max_norm,
-                       x.on() ? x.ext : (OptExtState*)nullptr);
+                       x.on() ? x.ext : (OptExtState*)nullptr, sch);
     return hipGetLastError();
 }
 
@@ -1693,6 +1739,13 @@ hipError_t ema_range(float* ema, const float* p, long n, const AdamState* st, co
     long blocks = (n / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(ema_range_kernel, dim3((int)blocks), dim3(256), 0, s, ema, p, n / 4, st, ext);
+    return hipGetLastError();
+}
+
+hipError_t lr_schedule_eval(const LrSchedState& q, double base, const long* steps, long n, double* lr, hipStream_t s) {
+    if (!steps || !lr || n < 0 || n > (1L << 24)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(lr_schedule_eval_kernel, dim3((int)((n + 63) / 64)), dim3(64), 0, s, q, base, steps, n, lr);
     return hipGetLastError();
 }
 

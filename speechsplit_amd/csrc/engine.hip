@@ -314,6 +314,10 @@ struct ss_engine {
     OptExtState* ext = nullptr;            // workspace byte 144, beside the Adam and clip states
     WdRunTable wd_runs{};                  // runs of [0, arena) by "decayed under which = 1" (build_table)
     bool wd_runs_ok = false;
+    // Learning-rate schedule (ss_set_lr_schedule; kernels.h, LrSchedState).  Host side: whether the prepare kernels get the state's address
+    // (lr_sched); device side: the options and the stats words of the last applied step.
+    int lr_kind = 0;                       // LR_OFF
+    LrSchedState* sch = nullptr;           // workspace byte 192, beside the Adam, clip and weight-decay / EMA states
 
     // components
     ConvBlk c1[3], c2[3], ct;              // Encoder_7 stream 1 / stream 2 (or Encoder_6 in c2), Encoder_t
@@ -645,6 +649,7 @@ long carve(E& e, int B, int T) {
     put(e.adam, sizeof(AdamState));                    // first: survives geometry changes (offset 0)
     if constexpr (assign) e.clip = (ClipState*)((char*)e.adam + CLIP_STATE_BYTE);      // same 256 bytes
     if constexpr (assign) e.ext = (OptExtState*)((char*)e.adam + OPT_EXT_STATE_BYTE);
+    if constexpr (assign) e.sch = (LrSchedState*)((char*)e.adam + LR_SCHED_STATE_BYTE);
     if (e.kind != SS_INTERP_ONLY) put(e.clip_part, 2L * GRAD_SUMSQ_MAX_WGS * sizeof(double));     // scratch, geometry-independent (offset 256)
     if (e.kind == SS_INTERP_ONLY) {                    // a bare InterpLnr module only needs one plan
         for (int i = 0; i < 4; ++i) interp_ws(e.plan[i], i == 3);
@@ -925,6 +930,9 @@ AdamExt opt_ext(const ss_engine* e) {
     x.ema = e->ema;
     return x;
 }
+// the schedule state for the step's prepare kernel (ss_set_lr_schedule): NULL while it is off, and every route then enqueues the
+// arguments it did before the schedule existed
+LrSchedState* lr_sched(const ss_engine* e) { return e->lr_kind != LR_OFF ? e->sch : nullptr; }
 
 // launch the pending encoder-BLSTM weight-gradient tasks (one kernel for all of them) on `st`: everything they read must be complete in
 // st's order.  Scratch: partial tiles from the step's bump allocator, arrival counters from the column sums' ring.
@@ -2104,11 +2112,11 @@ int early_update(ss_engine* e, Backward& bw) {
     } else if (from % 4 == 0 && from < e->arena) {
         const AdamExt x = opt_ext(e);
         if (x.on()) {         // decay and the average ride in the same launch; the step's ONE prepare sets their factors for both ranges
-            HIPCHK(adam_prepare_ext(e->adam, x, e->sticky, nullptr, e->side));
+            HIPCHK(adam_prepare_ext(e->adam, x, e->sticky, nullptr, e->side, lr_sched(e)));
             Prof pr(e, SS_PROF_ADAM, e->side);
             HIPCHK(adam_range_ext(e->P, e->G, e->Mm, e->Vv, from, e->arena, e->adam, bw.adam_gs, nullptr, x, e->side));
         } else {
-            HIPCHK(adam_prepare(e->adam, e->sticky, nullptr, e->side));
+            HIPCHK(adam_prepare(e->adam, e->sticky, nullptr, e->side, lr_sched(e)));
             Prof pr(e, SS_PROF_ADAM, e->side);
             HIPCHK(adam_range(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, bw.adam_gs, e->side));
         }
@@ -2593,6 +2601,9 @@ static_assert(sizeof(AdamState) <= CLIP_STATE_BYTE && CLIP_STATE_BYTE + sizeof(C
 static_assert(OPT_EXT_STATE_BYTE >= CLIP_STATE_BYTE + (long)sizeof(ClipState) && OPT_EXT_STATE_BYTE + sizeof(OptExtState) <= 256 &&
                   OPT_EXT_STATE_BYTE % 16 == 0 && offsetof(OptExtState, stats) == 0,
               "the weight-decay / EMA state shares those 256 bytes too (its four stats words are handed out as one float4)");
+static_assert(LR_SCHED_STATE_BYTE >= OPT_EXT_STATE_BYTE + (long)sizeof(OptExtState) && LR_SCHED_STATE_BYTE + sizeof(LrSchedState) <= 256 &&
+                  LR_SCHED_STATE_BYTE % 16 == 0 && offsetof(LrSchedState, stats) == 0,
+              "and so does the learning-rate schedule, behind them");
 int ss_set_workspace(ss_engine* e, void* ws_dev, long bytes, void* stream) {
     CHK(guard(e, "ss_set_workspace", ANY | WS));
     if (!ws_dev || ((uintptr_t)ws_dev & 255)) return fail("ss_set_workspace: the workspace must be 256-byte aligned");
@@ -2673,6 +2684,7 @@ int ss_bind(ss_engine* e, float* params, float* grads, float* m, float* v, void*
     e->wd = 0.0f;             // ... and so are weight decay and the parameter average (their device state is zero as well)
     e->wd_which = 0;
     e->ema = nullptr;
+    e->lr_kind = LR_OFF;      // ... and the learning-rate schedule
     AdamState st{};
     st.lr = 1e-4;
     st.beta1 = 0.9;
@@ -2724,7 +2736,7 @@ static int adam_enqueue(ss_engine* e, const Backward& bw, float grad_scale, hipS
             int n = 0;
             CHK(grad_norm_partials(e, have_hi, s, &n));
             Prof pr(e, SS_PROF_ADAM, s);
-            HIPCHK(adam_prepare_clip_ext(e->adam, e->clip, x, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s));
+            HIPCHK(adam_prepare_clip_ext(e->adam, e->clip, x, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s, lr_sched(e)));
             HIPCHK(adam_range_ext(e->P, e->G, e->Mm, e->Vv, 0, e->arena, e->adam, grad_scale, &e->clip->coef, x, s));
             return 0;
         }
@@ -2733,7 +2745,7 @@ static int adam_enqueue(ss_engine* e, const Backward& bw, float grad_scale, hipS
             HIPCHK(adam_range_ext(e->P, e->G, e->Mm, e->Vv, 0, bw.adam_early_from, e->adam, grad_scale, nullptr, x, s));
             return 0;
         }
-        HIPCHK(adam_prepare_ext(e->adam, x, e->sticky, e->G + e->status_off, s));
+        HIPCHK(adam_prepare_ext(e->adam, x, e->sticky, e->G + e->status_off, s, lr_sched(e)));
         HIPCHK(adam_range_ext(e->P, e->G, e->Mm, e->Vv, 0, e->arena, e->adam, grad_scale, nullptr, x, s));
         return 0;
     }
@@ -2743,7 +2755,7 @@ static int adam_enqueue(ss_engine* e, const Backward& bw, float grad_scale, hipS
         CHK(grad_norm_partials(e, have_hi, s, &n));
         {
             Prof pr(e, SS_PROF_ADAM, s);
-            HIPCHK(adam_prepare_clip(e->adam, e->clip, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s));
+            HIPCHK(adam_prepare_clip(e->adam, e->clip, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s, lr_sched(e)));
             HIPCHK(adam_range_clip(e->P, e->G, e->Mm, e->Vv, e->arena, e->adam, grad_scale, &e->clip->coef, s));
         }
         return 0;
@@ -2754,7 +2766,7 @@ static int adam_enqueue(ss_engine* e, const Backward& bw, float grad_scale, hipS
         return 0;
     }
     Prof pr(e, SS_PROF_ADAM, s);
-    HIPCHK(adam_step(e->P, e->G, e->Mm, e->Vv, e->arena, e->adam, grad_scale, e->sticky, e->G + e->status_off, s));
+    HIPCHK(adam_step(e->P, e->G, e->Mm, e->Vv, e->arena, e->adam, grad_scale, e->sticky, e->G + e->status_off, s, lr_sched(e)));
     return 0;
 }
 
@@ -2864,6 +2876,37 @@ int ss_ema_stats(ss_engine* e, float* out4_dev, void* stream) {
     if (!out4_dev) return fail("ss_ema_stats: null pointer");
     Own own(e, stream);
     HIPCHK(hipMemcpyAsync(out4_dev, e->ext->stats, 4 * sizeof(float), hipMemcpyDeviceToDevice, own.s));
+    return 0;
+}
+
+int ss_set_lr_schedule(ss_engine* e, int kind, int warmup_steps, double warmup_start, int total_steps, double gamma, int period, double min_lr,
+                       void* stream) {
+    CHK(guard(e, "ss_set_lr_schedule", GEN | GRADS | ADAM));
+    if (const char* why = lr_schedule_refusal(kind, warmup_steps, warmup_start, total_steps, gamma, period, min_lr))
+        return fail(std::string("ss_set_lr_schedule: ") + why);
+    Own own(e, stream);
+    LrSchedState st{};        // the stats words start again: no step has been applied under this schedule
+    st.kind = kind;
+    if (kind != LR_OFF) {
+        st.W = warmup_steps;
+        st.sf = warmup_start;
+        st.N = total_steps > 0 ? total_steps : 1;
+        st.gamma = gamma;
+        st.P = period > 0 ? period : 1;
+        st.min_lr = min_lr;
+        st.stats[3] = (float)kind;
+    }
+    HIPCHK(hipMemcpyAsync(e->sch, &st, sizeof(st), hipMemcpyHostToDevice, own.s));
+    HIPCHK(hipStreamSynchronize(own.s));
+    e->lr_kind = kind;
+    return 0;
+}
+
+int ss_lr_stats(ss_engine* e, float* out4_dev, void* stream) {
+    CHK(guard(e, "ss_lr_stats", GEN | GRADS | ADAM));
+    if (!out4_dev) return fail("ss_lr_stats: null pointer");
+    Own own(e, stream);
+    HIPCHK(hipMemcpyAsync(out4_dev, e->sch->stats, 4 * sizeof(float), hipMemcpyDeviceToDevice, own.s));
     return 0;
 }
 
@@ -3106,8 +3149,8 @@ static int adam_decoder_enqueue(ss_engine* e, float grad_scale, hipStream_t s) {
         int n = 0;
         if (clip) CHK(grad_norm_partials(e, false, s, &n));
         Prof pr(e, SS_PROF_ADAM, s);
-        if (clip) HIPCHK(adam_prepare_clip_ext(e->adam, e->clip, x, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s));
-        else HIPCHK(adam_prepare_ext(e->adam, x, e->sticky, e->G + e->status_off, s));
+        if (clip) HIPCHK(adam_prepare_clip_ext(e->adam, e->clip, x, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s, lr_sched(e)));
+        else HIPCHK(adam_prepare_ext(e->adam, x, e->sticky, e->G + e->status_off, s, lr_sched(e)));
         HIPCHK(adam_range_ext(e->P, e->G, e->Mm, e->Vv, from, e->arena, e->adam, grad_scale, clip ? &e->clip->coef : nullptr, x, s));
         if (x.ema) HIPCHK(ema_range(x.ema, e->P, from, e->adam, e->ext, s));
         return 0;
@@ -3116,12 +3159,12 @@ static int adam_decoder_enqueue(ss_engine* e, float grad_scale, hipStream_t s) {
         int n = 0;
         CHK(grad_norm_partials(e, false, s, &n));
         Prof pr(e, SS_PROF_ADAM, s);
-        HIPCHK(adam_prepare_clip(e->adam, e->clip, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s));
+        HIPCHK(adam_prepare_clip(e->adam, e->clip, e->sticky, e->G + e->status_off, e->clip_part, n, grad_scale, e->clip_max, s, lr_sched(e)));
         HIPCHK(adam_range_clip(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, grad_scale, &e->clip->coef, s));
         return 0;
     }
     Prof pr(e, SS_PROF_ADAM, s);
-    HIPCHK(adam_prepare(e->adam, e->sticky, e->G + e->status_off, s));
+    HIPCHK(adam_prepare(e->adam, e->sticky, e->G + e->status_off, s, lr_sched(e)));
     HIPCHK(adam_range(e->P + from, e->G + from, e->Mm + from, e->Vv + from, e->arena - from, e->adam, grad_scale, s));
     return 0;
 }

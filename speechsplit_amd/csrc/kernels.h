@@ -195,6 +195,7 @@ hipError_t mse_loss(CRows out, CRows tgt, Rows d_out, int B, int T, int C, float
 // the log-softmax is (x - max) - log(sum exp(x - max)), never through max + log(..)
 hipError_t ce_loss(CRows logits, const int* tgt, Rows d_out, int B, int T, int C, float grad_scale, float* partials, float* loss, hipStream_t s);
 
+struct LrSchedState;      // the learning-rate schedule (below); sch, nullable, in the launchers that prepare a step: NULL is "off"
 struct AdamState {        // device-resident so a captured graph can replay the step
     double lr, beta1, beta2, eps;
     long step;
@@ -207,10 +208,10 @@ struct AdamState {        // device-resident so a captured graph can replay the 
 constexpr unsigned SS_STICKY_ABORT = 1u, SS_STICKY_REMOTE = 2u, SS_STICKY_RANGE = 4u;
 // sticky (nullable) / status (nullable: the gradient arena's status slot, summed over the ranks by the all-reduce): when
 // either is non-zero the update is SKIPPED -- parameters, moments and the step counter stay as they are.
-hipError_t adam_prepare(AdamState* st, unsigned* sticky, const float* status, hipStream_t s);
+hipError_t adam_prepare(AdamState* st, unsigned* sticky, const float* status, hipStream_t s, LrSchedState* sch = nullptr);
 hipError_t adam_range(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, hipStream_t s);
 hipError_t adam_step(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, unsigned* sticky,
-                     const float* status, hipStream_t s);
+                     const float* status, hipStream_t s, LrSchedState* sch = nullptr);
 // ---- gradient clipping by global norm (torch.nn.utils.clip_grad_norm_, norm_type 2; no statement of the reference: its solver never clips)
 // Device-resident beside AdamState in the workspace's first 256 bytes (byte 128), so it survives what the Adam state survives.
 struct ClipState {
@@ -244,7 +245,7 @@ hipError_t grad_norm_finish(const double* partials, int n, float grad_scale, flo
 // A norm that is not finite sets st->skip for THIS step only (parameters, moments, step counter untouched; clip->skipped + 1; neither
 // sticky nor the status slot is set); the sticky / status skip of adam_prepare comes first and counts as neither.
 hipError_t adam_prepare_clip(AdamState* st, ClipState* clip, unsigned* sticky, const float* status, const double* partials, int n,
-                             float grad_scale, float max_norm, hipStream_t s);
+                             float grad_scale, float max_norm, hipStream_t s, LrSchedState* sch = nullptr);
 // adam_range with g * grad_scale * *coef (a coefficient of exactly 1.0f gives adam_range's bits)
 hipError_t adam_range_clip(float* p, const float* g, float* m, float* v, long n, AdamState* st, float grad_scale, const float* coef,
                            hipStream_t s);
@@ -284,9 +285,10 @@ struct AdamExt {
     bool on() const { return ext && (wd || ema); }
 };
 // adam_prepare / adam_prepare_clip that also set the step's decay_mul, ema_w and n (x.on(); otherwise the plain ones)
-hipError_t adam_prepare_ext(AdamState* st, const AdamExt& x, unsigned* sticky, const float* status, hipStream_t s);
+hipError_t adam_prepare_ext(AdamState* st, const AdamExt& x, unsigned* sticky, const float* status, hipStream_t s,
+                            LrSchedState* sch = nullptr);
 hipError_t adam_prepare_clip_ext(AdamState* st, ClipState* clip, const AdamExt& x, unsigned* sticky, const float* status, const double* partials,
-                                 int n, float grad_scale, float max_norm, hipStream_t s);
+                                 int n, float grad_scale, float max_norm, hipStream_t s, LrSchedState* sch = nullptr);
 // adam_range / adam_range_clip (coef non-null) over the elements [lo, hi) of arenas given by their BASE pointers, with decay and the fused
 // average under the step state the prepare set (lo, hi multiples of 4).  !x.on(): the plain launch on the offset pointers.
 hipError_t adam_range_ext(float* p, const float* g, float* m, float* v, long lo, long hi, AdamState* st, float grad_scale, const float* coef,
@@ -295,6 +297,39 @@ hipError_t adam_range_ext(float* p, const float* g, float* m, float* v, long lo,
 hipError_t ema_range(float* ema, const float* p, long n, const AdamState* st, const OptExtState* ext, hipStream_t s);
 // a[i] <-> b[i] over n floats (a multiple of 4)
 hipError_t arena_swap(float* a, float* b, long n, hipStream_t s);
+// ---- learning-rate warm-up and decay, keyed on the device's own step counter.  For an APPLIED step t (1-based, the t of the bias
+// corrections), s = t - 1, base = AdamState::lr:
+//   warm-up (W > 0 and s < W):  lr_t = base * (sf + (1 - sf) * (s / W))
+//   otherwise, k = s - W:       constant     base
+//                               cosine       kk = min(k, N); min_lr + (base - min_lr) * (0.5 * (1 + cospi(kk / N)))
+//                               linear       kk = min(k, N); base + (min_lr - base) * (kk / N)
+//                               exponential  max(base * pow(gamma, k), min_lr)
+//                               step         max(base * pow(gamma, k / P), min_lr), integer division
+// in float64 without contraction, by the prepare kernels' one thread right behind st->step += 1: step_size = (float)(lr_t / bc1) and
+// decay_mul = (float)(1 - lr_t * wd) are formed from that one value, so every range of one step sees it.  A skipped step changes none
+// of it.  Device-resident in the workspace's first 256 bytes (byte 192), beside the Adam, clip and weight-decay / EMA states.
+constexpr int LR_OFF = 0, LR_CONSTANT = 1, LR_COSINE = 2, LR_LINEAR = 3, LR_EXPONENTIAL = 4, LR_STEP = 5;
+struct LrSchedState {
+    float stats[4];       // {(float)lr_t of the last applied step, lr_t / base, t, kind}: handed out as one float4 (ss_lr_stats)
+    double sf, gamma, min_lr;
+    int W, N, P, kind;
+};
+constexpr long LR_SCHED_STATE_BYTE = 192;
+// what ss_set_lr_schedule and ss_op_lr_schedule refuse, in one place; NULL: the options are valid
+inline const char* lr_schedule_refusal(int kind, int warmup_steps, double warmup_start, int total_steps, double gamma, int period, double min_lr) {
+    if (kind < LR_OFF || kind > LR_STEP) return "kind must be 0 (off), 1 constant, 2 cosine, 3 linear, 4 exponential or 5 step";
+    if (kind == LR_OFF) return nullptr;         // off reads none of the others
+    if (warmup_steps < 0) return "warmup_steps must be >= 0";
+    if (!(warmup_start > 0.0 && warmup_start <= 1.0)) return "warmup_start must lie in (0, 1]; NaN is refused";
+    if ((kind == LR_COSINE || kind == LR_LINEAR) && total_steps < 1) return "total_steps must be >= 1 for cosine and linear";
+    if ((kind == LR_EXPONENTIAL || kind == LR_STEP) && !(gamma > 0.0 && gamma <= 1.0)) return "gamma must lie in (0, 1]; NaN is refused";
+    if (kind == LR_STEP && period < 1) return "period must be >= 1";
+    if (!(min_lr >= 0.0 && min_lr <= 1.7976931348623157e308)) return "min_lr must be >= 0 and finite; negative, NaN and inf are refused";
+    return nullptr;
+}
+// lr[i] = lr_t at t = steps[i] under the schedule q (q.stats unused) and the base rate: the prepare kernels' own __device__ function,
+// one thread per value (test hook)
+hipError_t lr_schedule_eval(const LrSchedState& q, double base, const long* steps, long n, double* lr, hipStream_t s);
 // *status = (*sticky != 0)   (one thread; enqueued behind the decoder's recurrences, in front of the all-reduce that sums it)
 hipError_t status_publish(const unsigned* sticky, float* status, hipStream_t s);
 // Scale of the fp16 x 2 split for the OUTPUT of each conv block (GroupNorm + ReLU, then resampled: a convex combination), from its affine

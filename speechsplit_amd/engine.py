@@ -702,6 +702,30 @@ class Engine:
         _capi.check(self.lib.ss_ema_stats(self.h, _ptr(out), _stream()))
         return out
 
+    # ------------------------------------------------------------------ learning-rate schedule
+    LR_KINDS = {None: 0, 'off': 0, 'constant': 1, 'cosine': 2, 'linear': 3, 'exponential': 4, 'step': 5}
+
+    def set_lr_schedule(self, kind=None, warmup=0, warmup_start=0.1, total=None, gamma=None, period=None, min_lr=0.0):
+        """Warm-up and decay of the learning rate inside every applied optimiser step, keyed on the device's step counter
+        (ss_set_lr_schedule; the definition is in include/speechsplit_amd.h).  kind: None / 'off' (default), 'constant', 'cosine', 'linear',
+        'exponential' or 'step'.  warmup steps rise linearly from warmup_start * lr to lr; then cosine / linear reach min_lr after total
+        steps and stay there, exponential multiplies by gamma every step and step by gamma every period steps, both floored at min_lr.
+        The base rate stays the lr of set_adam, whose step positions the schedule."""
+        if kind not in self.LR_KINDS:
+            raise ValueError(f"set_lr_schedule: kind must be None, 'off', 'constant', 'cosine', 'linear', 'exponential' or 'step', not {kind!r}")
+        k = self.LR_KINDS[kind]
+        # an option its kind reads has no default: leaving it out is the engine's refusal, by name
+        _capi.check(self.lib.ss_set_lr_schedule(self.h, k, int(warmup), float(warmup_start), int(total) if total is not None else 0,
+                                                float(gamma) if gamma is not None else 0.0, int(period) if period is not None else 0,
+                                                float(min_lr), _stream()))
+
+    def lr_stats(self):
+        """Device tensor [4], no synchronisation (ss_lr_stats): the learning rate of the last applied optimiser step, that rate over the
+        base rate, the step t it belonged to, the schedule's kind (0 off)."""
+        out = self._new('lr_stats', (4,))
+        _capi.check(self.lib.ss_lr_stats(self.h, _ptr(out), _stream()))
+        return out
+
     def ema_weights(self):
         """Context manager: the engine runs on the averaged weights inside (ss_ema_swap on entry and again on exit, which restores the
         parameters' bits).  Training and optimiser steps raise inside: they would train the average."""

@@ -53,6 +53,56 @@ def optim_ext_options(config, environ=None):
     return wd, which, decay, bool(warm)
 
 
+LR_SCHEDULE_KINDS = ('constant', 'cosine', 'linear', 'exponential', 'step')
+
+
+def lr_schedule_options(config, environ=None):
+    """The learning-rate schedule as Engine.set_lr_schedule's keyword arguments, or None (off, the default), from config.lr_schedule /
+    SS_LR_SCHEDULE ('constant' | 'cosine' | 'linear' | 'exponential' | 'step'; None, '' or 'off': off), config.lr_warmup / SS_LR_WARMUP,
+    lr_warmup_start / SS_LR_WARMUP_START, lr_total / SS_LR_TOTAL, lr_gamma / SS_LR_GAMMA, lr_period / SS_LR_PERIOD and lr_min / SS_LR_MIN,
+    read the way optim_ext_options reads its options.  Defaults: no warm-up, from 0.1 of the rate, min 0; for cosine and linear lr_total
+    defaults to config.num_iters - lr_warmup.  gamma (exponential, step) and period (step) have no default.  Needs no device."""
+    environ = os.environ if environ is None else environ
+    kind = _option(config, 'lr_schedule', 'SS_LR_SCHEDULE', environ)
+    if kind is None or kind == 'off':
+        return None
+    if kind not in LR_SCHEDULE_KINDS:
+        raise ValueError("lr_schedule must be None / 'off' or one of {}, got {!r}".format(', '.join(map(repr, LR_SCHEDULE_KINDS)), kind))
+
+    def number(name, env, cast, default):
+        v = _option(config, name, env, environ)
+        return cast(v) if v is not None else default
+
+    warmup = number('lr_warmup', 'SS_LR_WARMUP', int, 0)
+    if warmup < 0:
+        raise ValueError('lr_warmup must be >= 0, got {!r}'.format(warmup))
+    start = number('lr_warmup_start', 'SS_LR_WARMUP_START', float, 0.1)
+    if not (0.0 < start <= 1.0):
+        raise ValueError('lr_warmup_start must lie in (0, 1], got {!r}'.format(start))
+    min_lr = number('lr_min', 'SS_LR_MIN', float, 0.0)
+    if not (0.0 <= min_lr < float('inf')):
+        raise ValueError('lr_min must be >= 0 and finite, got {!r}'.format(min_lr))
+    opts = {'kind': kind, 'warmup': warmup, 'warmup_start': start, 'total': None, 'gamma': None, 'period': None, 'min_lr': min_lr}
+    if kind in ('cosine', 'linear'):
+        total = number('lr_total', 'SS_LR_TOTAL', int, None)
+        if total is None:
+            total = int(config.num_iters) - warmup
+        if total < 1:
+            raise ValueError('lr_total must be >= 1 (default num_iters - lr_warmup), got {!r}'.format(total))
+        opts['total'] = total
+    if kind in ('exponential', 'step'):
+        gamma = number('lr_gamma', 'SS_LR_GAMMA', float, None)
+        if gamma is None or not (0.0 < gamma <= 1.0):
+            raise ValueError('lr_gamma must lie in (0, 1] for {!r} (it has no default), got {!r}'.format(kind, gamma))
+        opts['gamma'] = gamma
+    if kind == 'step':
+        period = number('lr_period', 'SS_LR_PERIOD', int, None)
+        if period is None or period < 1:
+            raise ValueError("lr_period must be >= 1 for 'step' (it has no default), got {!r}".format(period))
+        opts['period'] = period
+    return opts
+
+
 class Solver(object):
     """Solver for training"""
 
@@ -90,6 +140,9 @@ class Solver(object):
         # decoupled weight decay (AdamW) and an exponential moving average of the parameters, both inside the engine's optimiser step
         # (Engine.set_weight_decay / set_ema); off by default, and then nothing is called and the checkpoints are the reference's
         self.weight_decay, self.weight_decay_which, self.ema_decay, self.ema_warmup = optim_ext_options(config)
+        # learning-rate warm-up and decay inside the engine's optimiser step, keyed on the device's step counter (Engine.set_lr_schedule);
+        # off by default, and then nothing is called, the log line and the checkpoints are the reference's.  g_lr stays the base rate.
+        self.lr_schedule = lr_schedule_options(config)
         self.use_cuda = torch.cuda.is_available()
         if not self.use_cuda:
             raise RuntimeError('speechsplit_amd.Solver needs a ROCm GPU (the engine has no CPU fallback)')
@@ -119,6 +172,8 @@ class Solver(object):
             self.eng.set_grad_clip(self.grad_clip)
         if self.weight_decay:
             self.eng.set_weight_decay(self.weight_decay, self.weight_decay_which)
+        if self.lr_schedule:
+            self.eng.set_lr_schedule(**self.lr_schedule)
         if self.world > 1:
             _dist.init('nccl', self.device)
             import torch.distributed as dist
@@ -187,6 +242,8 @@ class Solver(object):
             ema = self.eng.ema_views()
             ckpt['model_ema'] = {k: (ema[k] if k in ema else v).detach().cpu().clone() for k, v in ckpt['model'].items()}
             ckpt['ema_updates'] = int(self.eng.ema_stats()[0].item())
+        if self.lr_schedule:              # the options; the position is the optimiser state's step count
+            ckpt['lr_schedule'] = dict(self.lr_schedule)
         torch.save(ckpt, G_path)
 
     def restore_model(self, resume_iters):
@@ -195,6 +252,17 @@ class Solver(object):
         ckpt = torch.load(G_path, map_location=lambda storage, loc: storage, weights_only=False)
         self.G.load_state_dict(ckpt['model'])
         self.load_optimizer_state_dict(ckpt['optimizer'])
+        # A schedule the checkpoint was trained with wins, as its weight decay does; the restored step count positions it.  A checkpoint
+        # without one leaves a configured schedule in force.
+        stored = ckpt.get('lr_schedule')
+        if stored:
+            if self.lr_schedule and dict(stored) != self.lr_schedule and self.rank == 0:
+                print('Note: the checkpoint\'s learning-rate schedule {} replaces the configured {}'.format(dict(stored), self.lr_schedule))
+            self.lr_schedule = dict(stored)
+            self.eng.set_lr_schedule(**self.lr_schedule)
+        elif self.lr_schedule and self.rank == 0:
+            print('Note: the checkpoint was written without a learning-rate schedule; the configured {} applies from here on'.format(
+                self.lr_schedule))
         if self.ema_decay is not None:
             if 'model_ema' in ckpt:       # the average and its update count back; parameters without an average of their own start one
                 flat = self.eng.params.clone()
@@ -316,13 +384,13 @@ class Solver(object):
         # (non-blocking) and the line is printed once that copy has landed -- an iteration or two later, same text, same order.  A blocking
         # .item() every log_step iterations left the GPU waiting for the host to enqueue the next step again: 0.2 ms per iteration at
         # log_step = 10 (bench.py solver_loop: 5.51 vs 5.29 ms for the bare step).
-        pending = []                                              # (copy-done event, pinned loss, iteration, elapsed text, pinned clip stats or None)
+        pending = []                      # (copy-done event, pinned loss, iteration, elapsed text, pinned clip stats or None, pinned lr stats or None)
         skipped_seen = 0
 
         def flush(block):
             nonlocal skipped_seen
             while pending and (block or pending[0][0].query()):
-                ev, host_loss, it, et, host_clip = pending.pop(0)
+                ev, host_loss, it, et, host_clip, host_lr = pending.pop(0)
                 ev.synchronize()
                 if self.rank == 0:
                     log = "Elapsed [{}], Iteration [{}/{}]".format(et, it, self.num_iters)
@@ -330,6 +398,8 @@ class Solver(object):
                         log += ", {}: {:.8f}".format(tag, float(host_loss))
                     if host_clip is not None:                     # {norm before clipping, coefficient, steps clipped, steps skipped}
                         log += ", G/grad_norm: {:.8f}".format(float(host_clip[0]))
+                    if host_lr is not None:                       # {rate of the last applied step, rate / base, its t, kind}
+                        log += ", lr: {:.8e}".format(float(host_lr[0]))
                     print(log)
                     if host_clip is not None and int(host_clip[3]) > skipped_seen:
                         print('Warning: {} optimiser step(s) skipped so far: their gradients were not finite (by iteration {})'.format(
@@ -359,9 +429,13 @@ class Solver(object):
                 if self.grad_clip:                                # the same pinned non-blocking copy as the loss
                     host_clip = torch.empty(4, dtype=torch.float32).pin_memory()
                     host_clip.copy_(self.eng.grad_clip_stats(), non_blocking=True)
+                host_lr = None
+                if self.lr_schedule:
+                    host_lr = torch.empty(4, dtype=torch.float32).pin_memory()
+                    host_lr.copy_(self.eng.lr_stats(), non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream(self.device))
-                pending.append((ev, host_loss, i + 1, str(datetime.timedelta(seconds=time.time() - start_time))[:-7], host_clip))
+                pending.append((ev, host_loss, i + 1, str(datetime.timedelta(seconds=time.time() - start_time))[:-7], host_clip, host_lr))
             flush(self.world > 1)
             if (i + 1) % self.model_save_step == 0 and self.rank == 0:
                 flush(True)
