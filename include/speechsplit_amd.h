@@ -627,6 +627,58 @@ long ss_resample_scratch_bytes(int up, int n_taps);          /* host only; may b
 int  ss_resample(const double* x_dev, const int* n_dev, int B, int max_n, int up, int down, const double* h_dev, int n_taps,
                  double* y_dev, void* scratch_dev, long scratch_bytes, void* stream);
 
+/* ss_remove_silence: trim the room tone at both ends of a recording and cap the pauses inside it, on ragged batches at the chain's 16 kHz
+ * (nothing to mirror: users of the reference trim with librosa before make_spect_f0.py; parity with librosa.effects.trim / split is NOT
+ * claimed -- this is the definition below, a RELATIVE threshold only, with no absolute gate).
+ * Float64 throughout.  Every product and every sum is rounded to double on its own, no fused multiply-add; a sum "in order" adds one term at
+ * a time, index ascending, starting from its first term.  x: float64 [B][max_n]; n_dev: i32 [B] (NULL: every row is full); row b has
+ * n_b = min(max(n[b], 1), max_n) samples; a length outside 1 .. max_n spoils that row only; nothing at or beyond n_b is read (it may hold
+ * NaN); row b is, bit for bit, the result of running that recording alone.  No atomics, no allocation inside, no engine needed, asynchronous
+ * on `stream`.
+ *   Blocks.    Block j covers samples [256 j, min(256 j + 256, n_b)), j = 0 .. J - 1, J = ceil(n_b / 256); only the last block may be short.
+ *              256 is the chain's mel hop, so a removed block is a removed mel frame.  Jmax = ceil(max_n / 256).
+ *   Levels.    Quarter sums Q_q = sum of x[i]^2 over i in [128 q, min(128 q + 128, n_b)), in order, q = 0 .. ceil(n_b / 128) - 1.  The level of
+ *              block j is the energy of the 512-sample window centred on it, E_j = ((Q_{2j-1} + Q_{2j}) + Q_{2j+1}) + Q_{2j+2}; quarters that
+ *              do not exist (q < 0, or q beyond the last) are left out and the rest are added in that order.  It is a plain SUM, not a mean: a
+ *              window cut by the recording's end counts as quieter.  E_max = max_j E_j (NaN if a level is NaN).
+ *   Activity.  a_j = E_j > ratio * E_max, STRICTLY; `ratio` in (0, 1) is the caller's (the Python layer passes 10 ** (-top_db / 10)); there is
+ *              no logarithm on the device.  If no block is active (only when E_max is 0, or not finite) every block is kept and the row comes
+ *              out as it went in.  Hangover: d_j = any a_i with |i - j| <= hang.
+ *   Kept.      Take the maximal runs of d_j == 0, of length R.  A leading run (it contains block 0) keeps its last min(R, edge) blocks; a
+ *              trailing run (it contains block J - 1) keeps its first min(R, edge) blocks; an interior run is kept whole when pause < 0 or
+ *              R <= pause, otherwise it keeps its first ceil(pause / 2) and its last floor(pause / 2) blocks.  Every block with d_j == 1 is
+ *              kept.  hang, edge >= 0 and pause >= -1 are ints: pause = -1 only trims, edge at or above J only caps pauses.  K blocks are
+ *              kept; inv[c] is the c-th of them, ascending.
+ *   Output.    y is the kept blocks in order: output block c starts at 256 c, and the new length is m_b = 256 (K - 1) + (length of block
+ *              inv[K-1]).  Block c is a copy of block inv[c], to the bit, when c == 0 or inv[c-1] + 1 == inv[c].  At a join
+ *              (inv[c-1] + 1 != inv[c]; write a = inv[c-1]) the first min(128, length of block inv[c]) samples are a cross-fade whose
+ *              fade-out side is the signal that FOLLOWED the last kept block -- below the threshold by construction:
+ *                  y[256 c + r] = x[256 (a + 1) + r] * (1.0 - g[r]) + x[256 inv[c] + r] * g[r]
+ *              the difference 1.0 - g[r] and the two products first, then their sum.  Block a + 1 is always a full block inside the row
+ *              (a + 1 < inv[c] <= J - 1).  g: HOST array [128], an input as STOI's window is; the Python layer passes
+ *              g[r] = 0.5 - 0.5 cos(pi (r + 0.5) / 128) evaluated with the C library's cosine.  Exact zeros are written behind m_b.
+ * y_dev: float64 [B][max_n]; m_dev: i32 [B]; inv_dev: i32 [B][Jmax] with -1 behind the K kept blocks, and k_dev: i32 [B], are outputs and may
+ * each be NULL.  scratch: ss_silence_scratch_bytes(B, max_n) bytes, 256-byte aligned.  Every index a kernel reads back from scratch or from
+ * inv / K is clamped into the row's own blocks and samples: a corrupt map changes numbers, never addresses (K into 1 .. J, a block into
+ * 0 .. J - 1, a sample index to at most n_b - 1, m_b to at most n_b).
+ * Test hooks, each a stage alone.  ss_op_silence_levels: x -> e [B][Jmax], zeros behind J_b.  ss_op_silence_mask: e [B][max_j] and a per-row
+ * block count j_dev (i32 [B]; NULL: max_j; clamped into 1 .. max_j) -> inv [B][max_j], k [B].  ss_op_silence_gather: x, inv, k (INPUTS, read
+ * with the clamps above) -> y, m.
+ * Refused before anything is enqueued, with a message that names the argument: null x_dev / y_dev / m_dev / g / scratch_dev (the hooks: their
+ * own pointers), B outside 1 .. 65535, max_n outside 1 .. 256 (SS_MAX_EVAL_FRAMES - 1) (max_j outside 1 .. SS_MAX_EVAL_FRAMES - 1), ratio not
+ * in (0, 1), hang or edge negative, pause < -1, a g entry that is not finite, scratch_bytes below ss_silence_scratch_bytes(B, max_n),
+ * scratch_dev not 256-byte aligned. */
+long ss_silence_scratch_bytes(int B, int max_n);             /* host only; -1 + ss_last_error on bad arguments */
+int  ss_remove_silence(const double* x_dev, const int* n_dev, int B, int max_n, double ratio, int hang, int edge, int pause,
+                       const double* g /* host [128] */, double* y_dev /* [B][max_n] */, int* m_dev /* [B] */,
+                       int* inv_dev /* [B][Jmax], -1 behind K; nullable */, int* k_dev /* [B]; nullable */, void* scratch_dev,
+                       long scratch_bytes, void* stream);
+int  ss_op_silence_levels(const double* x_dev, const int* n_dev, int B, int max_n, double* e_dev /* [B][Jmax] */, void* stream);
+int  ss_op_silence_mask(const double* e_dev, const int* j_dev, int B, int max_j, double ratio, int hang, int edge, int pause,
+                        int* inv_dev /* [B][max_j] */, int* k_dev /* [B] */, void* stream);
+int  ss_op_silence_gather(const double* x_dev, const int* n_dev, int B, int max_n, const int* inv_dev, const int* k_dev,
+                          const double* g /* host [128] */, double* y_dev, int* m_dev, void* stream);
+
 /* ss_mt19937_rand: the dither draw of make_spect_f0.py:55 on the device -- numpy.random.RandomState.rand(count) continued from a
  * caller-supplied generator state, bit for bit in every draw and in the state left behind.
  * state_dev: unsigned [625] ON THE DEVICE, read and written in place: state[0 .. 623] is numpy's `key`, state[624] numpy's `pos` in 0 .. 624

@@ -240,6 +240,13 @@ SYMBOLS = {
     'ss_resample_len': (_l, [_l, _i, _i]),
     'ss_resample_scratch_bytes': (_l, [_i, _i]),
     'ss_resample': (_i, [_vp, _ip, _i, _i, _i, _i, _vp, _i, _vp, _vp, _l, _vp]),
+    # B, max_n / x, n, B, max_n, ratio, hang, edge, pause, g (host), y, m, inv, k, scratch, bytes, stream
+    'ss_silence_scratch_bytes': (_l, [_i, _i]),
+    'ss_remove_silence': (_i, [_vp, _ip, _i, _i, _d, _i, _i, _i, C.POINTER(_d), _vp, _ip, _ip, _ip, _vp, _l, _vp]),
+    # x, n, B, max_n, e, stream / e, j, B, max_j, ratio, hang, edge, pause, inv, k, stream / x, n, B, max_n, inv, k, g (host), y, m, stream
+    'ss_op_silence_levels': (_i, [_vp, _ip, _i, _i, _vp, _vp]),
+    'ss_op_silence_mask': (_i, [_vp, _ip, _i, _i, _d, _i, _i, _i, _ip, _ip, _vp]),
+    'ss_op_silence_gather': (_i, [_vp, _ip, _i, _i, _ip, _ip, C.POINTER(_d), _vp, _ip, _vp]),
     'ss_mt19937_rand': (_i, [_vp, _l, _vp, _vp]),
     'ss_dither_rows': (_i, [_vp, _l, _vp, _ip, _i, _i, _vp, _vp]),
     'ss_griffinlim_samples': (_i, [_i]),

@@ -1,5 +1,5 @@
 // C entry points of the audio / data front end (include/speechsplit_amd.h): collation, mel spectrograms, F0 normalisation, the pitch
-// tracker, batched feature extraction, the resampler, numpy's MT19937 stream, the Griffin-Lim vocoder, the conversion scores and the waveform scores.  None of them takes an engine: each checks its arguments, refuses by
+// tracker, batched feature extraction, the resampler, silence removal, numpy's MT19937 stream, the Griffin-Lim vocoder, the conversion scores and the waveform scores.  None of them takes an engine: each checks its arguments, refuses by
 // the argument's name through ss_last_error() and hands the rest to the launchers of kernels.h.
 #include <cmath>
 #include <cstdint>
@@ -260,7 +260,89 @@ int ss_resample(const double* x, const int* n, int B, int max_n, int up, int dow
     return 0;
 }
 
-// ---- numpy's MT19937 stream and the dither gather (mtrand.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+// ---- silence removal (silence.hip).  Everything is refused here, by the argument's name, before anything is enqueued.
+namespace {
+int silence_rows(const char* who, int B, int max_n) {
+    if (B < 1 || B > FEAT_MAX_ROWS) return fail(std::string(who) + ": B outside 1 .. 65535");
+    if (max_n < 1 || max_n > 256 * (SS_MAX_EVAL_FRAMES - 1)) return fail(std::string(who) + ": max_n outside 1 .. 256 * (SS_MAX_EVAL_FRAMES - 1)");
+    return 0;
+}
+int silence_options(const char* who, double ratio, int hang, int edge, int pause) {
+    if (!(ratio > 0.0 && ratio < 1.0)) return fail(std::string(who) + ": ratio outside (0, 1) or NaN");
+    if (hang < 0) return fail(std::string(who) + ": hang is negative");
+    if (edge < 0) return fail(std::string(who) + ": edge is negative");
+    if (pause < -1) return fail(std::string(who) + ": pause below -1");
+    return 0;
+}
+int silence_fade(const char* who, const double* g) {
+    if (!g) return fail(std::string(who) + ": null pointer: g");
+    for (int r = 0; r < 128; ++r)
+        if (!std::isfinite(g[r])) return fail(std::string(who) + ": g[" + std::to_string(r) + "] is not finite");
+    return 0;
+}
+}  // namespace
+
+static_assert(SIL_MAX_BLOCKS == SS_MAX_EVAL_FRAMES - 1, "the refusals above and the header spell this bound out");
+
+long ss_silence_scratch_bytes(int B, int max_n) {
+    CHK(silence_rows("ss_silence_scratch_bytes", B, max_n));
+    return silence_scratch_bytes(B, max_n);
+}
+
+int ss_remove_silence(const double* x, const int* n, int B, int max_n, double ratio, int hang, int edge, int pause, const double* g, double* y,
+                      int* m, int* inv, int* k, void* scratch, long scratch_bytes, void* stream) {
+    if (!x) return fail("ss_remove_silence: null pointer: x_dev");
+    if (!y) return fail("ss_remove_silence: null pointer: y_dev");
+    if (!m) return fail("ss_remove_silence: null pointer: m_dev");
+    CHK(silence_rows("ss_remove_silence", B, max_n));
+    CHK(silence_options("ss_remove_silence", ratio, hang, edge, pause));
+    CHK(silence_fade("ss_remove_silence", g));
+    if (!scratch) return fail("ss_remove_silence: null pointer: scratch_dev");
+    if ((uintptr_t)scratch % 256) return fail("ss_remove_silence: scratch_dev is not 256-byte aligned");
+    if (scratch_bytes < silence_scratch_bytes(B, max_n)) return fail("ss_remove_silence: scratch_bytes below ss_silence_scratch_bytes(B, max_n)");
+    const SilenceScratch sc = silence_scratch(scratch, B, max_n);
+    int* inv_w = inv ? inv : sc.inv;
+    int* k_w = k ? k : sc.k;
+    HIPCHK(silence_levels(x, n, B, max_n, sc.e, S(stream)));
+    HIPCHK(silence_mask(sc.e, n, true, B, max_n, ratio, hang, edge, pause, inv_w, k_w, S(stream)));
+    HIPCHK(silence_gather(x, n, B, max_n, inv_w, k_w, g, y, m, S(stream)));
+    return 0;
+}
+
+int ss_op_silence_levels(const double* x, const int* n, int B, int max_n, double* e, void* stream) {
+    if (!x) return fail("ss_op_silence_levels: null pointer: x_dev");
+    if (!e) return fail("ss_op_silence_levels: null pointer: e_dev");
+    CHK(silence_rows("ss_op_silence_levels", B, max_n));
+    HIPCHK(silence_levels(x, n, B, max_n, e, S(stream)));
+    return 0;
+}
+
+int ss_op_silence_mask(const double* e, const int* j, int B, int max_j, double ratio, int hang, int edge, int pause, int* inv, int* k,
+                       void* stream) {
+    if (!e) return fail("ss_op_silence_mask: null pointer: e_dev");
+    if (!inv) return fail("ss_op_silence_mask: null pointer: inv_dev");
+    if (!k) return fail("ss_op_silence_mask: null pointer: k_dev");
+    if (B < 1 || B > FEAT_MAX_ROWS) return fail("ss_op_silence_mask: B outside 1 .. 65535");
+    if (max_j < 1 || max_j > SIL_MAX_BLOCKS) return fail("ss_op_silence_mask: max_j outside 1 .. SS_MAX_EVAL_FRAMES - 1");
+    CHK(silence_options("ss_op_silence_mask", ratio, hang, edge, pause));
+    HIPCHK(silence_mask(e, j, false, B, 256 * max_j, ratio, hang, edge, pause, inv, k, S(stream)));
+    return 0;
+}
+
+int ss_op_silence_gather(const double* x, const int* n, int B, int max_n, const int* inv, const int* k, const double* g, double* y, int* m,
+                         void* stream) {
+    if (!x) return fail("ss_op_silence_gather: null pointer: x_dev");
+    if (!inv) return fail("ss_op_silence_gather: null pointer: inv_dev");
+    if (!k) return fail("ss_op_silence_gather: null pointer: k_dev");
+    if (!y) return fail("ss_op_silence_gather: null pointer: y_dev");
+    if (!m) return fail("ss_op_silence_gather: null pointer: m_dev");
+    CHK(silence_rows("ss_op_silence_gather", B, max_n));
+    CHK(silence_fade("ss_op_silence_gather", g));
+    HIPCHK(silence_gather(x, n, B, max_n, inv, k, g, y, m, S(stream)));
+    return 0;
+}
+
+// ---- numpy's MT19937 stream and the dither gather (mtrand.hip). Everything is refused here, by the argument's name, before anything is enqueued.
 int ss_mt19937_rand(unsigned* state, long count, double* out, void* stream) {
     if (!state) return fail("ss_mt19937_rand: null pointer: state_dev");
     if (count < 0 || count > MT_MAX_COUNT) return fail("ss_mt19937_rand: count outside 0 .. 2^40");

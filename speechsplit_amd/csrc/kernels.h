@@ -382,6 +382,26 @@ long resample_len(long n, int up, int down);                 // ceil(n up / down
 long resample_scratch_bytes(int up, int n_taps);             // 0: the kernel reads h as it is given
 hipError_t resample(const double* x, const int* n, int B, int max_n, int up, int down, const double* h, int n_taps, double* y, hipStream_t s);
 
+// ---------------------------------------------------------------- silence.hip  (trim the ends, cap the pauses: float64, to the bit)
+// x, y [B][max_n]; Jmax = silence_blocks(max_n) blocks of 256 samples; e [B][Jmax] levels (zeros behind a row's J_b blocks); inv [B][Jmax] the
+// kept blocks ascending (-1 behind the K kept ones), k [B]; m [B] the new lengths.  n (nullable; device i32[B]): row b has
+// n_b = min(max(n[b], 1), max_n) samples; nothing at or beyond n_b is read.  include/speechsplit_amd.h states the definition.
+constexpr int SIL_MAX_BLOCKS = 8191;   // 256 * SIL_MAX_BLOCKS samples a row at most: the mask kernel's LDS holds a row's blocks
+struct SilenceScratch {
+    double* e;
+    int *inv, *k;
+};
+int silence_blocks(int max_n);
+long silence_scratch_bytes(int B, int max_n);
+SilenceScratch silence_scratch(void* base, int B, int max_n);
+hipError_t silence_levels(const double* x, const int* n, int B, int max_n, double* e, hipStream_t s);
+// cnt (nullable) holds a row's samples (cnt_is_samples: the n above) or its blocks, clamped into 1 .. Jmax
+hipError_t silence_mask(const double* e, const int* cnt, bool cnt_is_samples, int B, int max_n, double ratio, int hang, int edge, int pause,
+                        int* inv, int* k, hipStream_t s);
+// g: host [128], the fade-in gains; inv and k are read with every index clamped into the row's own blocks
+hipError_t silence_gather(const double* x, const int* n, int B, int max_n, const int* inv, const int* k, const double* g, double* y, int* m,
+                          hipStream_t s);
+
 // ---------------------------------------------------------------- mtrand.hip  (numpy.random.RandomState.rand to the bit: MT19937)
 // state u32[625] on the device, in/out: numpy's key [624], then pos (above 624 reads as 624).  out [count] float64: draw i is
 // ((w[2i] >> 5) 2^26 + (w[2i+1] >> 6)) / 2^53 of the tempered stream words w from pos on.  Afterwards the state is what numpy holds after the

@@ -19,6 +19,13 @@ first by `resample` / `resample_dev` (csrc/resample.hip: scipy.signal.resample_p
 batches): `extract(..., sr=)`, `extract_batch_sr` and `make_spect_f0(..., resample=True)`, which reads files with `read_audio`.  The defaults
 are the 16 kHz path unchanged; `read_wav` still refuses every other rate by name.
 
+Silence.  Nothing above looks at where the speech is.  `remove_silence` / `remove_silence_dev` (csrc/silence.hip) trim the room tone at both
+ends of a recording and cap the pauses inside it, in whole 256-sample blocks (a removed block is a removed mel frame) with a 128-sample
+cross-fade at every join; `Silence` holds the options, and `extract_batch_sr`, `extract_opt` and `make_spect_f0_opt` take one as
+`silence=` (keyword-only, default None: the calls and the bits are unchanged).  It runs at 16 kHz, behind the resampler and in front of the
+odd-length fix and the dither draw.  It is a definition of its own (include/speechsplit_amd.h), pinned to the bit against
+tests/silence_ref.py; parity with `librosa.effects.trim` / `split`, which users of the reference reach for, is UNPINNED.
+
 Two parts of the reference come from libraries that are absent here, and both are restated from the published algorithm instead:
   * the mel filter bank (`librosa.filters.mel`, make_spect_f0.py:15): `mel_filter_bank`, Slaney's Auditory-Toolbox mel scale and area
     normalisation with librosa's defaults.  Parity against librosa itself is UNPINNED (nothing of the reference's could be run to produce a
@@ -339,6 +346,124 @@ def resample(xs, sr_in, sr_out=16000, max_rows=16, device='cuda'):
     return out[0] if single else out
 
 
+class Silence:
+    """The options of silence removal (`remove_silence`, and the `silence=` keyword of `extract_batch_sr`, `extract_opt` and
+    `make_spect_f0_opt`), immutable and validated by name.  top_db: a block of 256 samples is active when the energy of the 512-sample
+    window centred on it lies less than top_db decibels below the loudest block's (finite, > 0; the device gets the ratio
+    10 ** (-top_db / 10) and takes no logarithm).  hang: blocks on either side of an active block that count as speech.  edge: silent blocks
+    kept at either end.  pause: the longest pause, in blocks, left inside; None leaves the pauses alone and only trims.
+    include/speechsplit_amd.h (ss_remove_silence) states the definition completely."""
+    __slots__ = ('top_db', 'hang', 'edge', 'pause')
+
+    def __init__(self, top_db=40.0, hang=2, edge=6, pause=None):
+        if isinstance(top_db, bool) or not isinstance(top_db, (int, float)) or not math.isfinite(top_db) or not top_db > 0:
+            raise ValueError(f'Silence: top_db must be a finite number above 0, not {top_db!r}')
+        if not 0.0 < 10.0 ** (-float(top_db) / 10.0) < 1.0:
+            raise ValueError(f'Silence: top_db must leave the ratio 10 ** (-top_db / 10) inside (0, 1), not {top_db!r}')
+        for name, v in (('hang', hang), ('edge', edge)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 2 ** 31 - 1:
+                raise ValueError(f'Silence: {name} must be an integer in 0 .. 2^31 - 1, not {v!r}')
+        if pause is not None and (isinstance(pause, bool) or not isinstance(pause, int) or not 0 <= pause <= 2 ** 31 - 1):
+            raise ValueError(f'Silence: pause must be None or an integer in 0 .. 2^31 - 1, not {pause!r}')
+        for name, v in (('top_db', float(top_db)), ('hang', hang), ('edge', edge), ('pause', pause)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError('Silence is immutable')
+
+    def __delattr__(self, name):
+        raise AttributeError('Silence is immutable')
+
+    def __repr__(self):
+        return f'Silence(top_db={self.top_db!r}, hang={self.hang!r}, edge={self.edge!r}, pause={self.pause!r})'
+
+    def __eq__(self, other):
+        return isinstance(other, Silence) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+    @property
+    def ratio(self):
+        """what ss_remove_silence takes: the threshold as a share of the loudest block's energy"""
+        return 10.0 ** (-self.top_db / 10.0)
+
+    @property
+    def pause_blocks(self):
+        """what ss_remove_silence takes: -1 for None"""
+        return -1 if self.pause is None else self.pause
+
+
+def _silence_opts(who, opts):
+    if not isinstance(opts, Silence):
+        raise TypeError(f'{who}: silence must be a Silence, not {opts!r}')
+    return opts
+
+
+def silence_fade():
+    """g[r] = 0.5 - 0.5 cos(pi (r + 0.5) / 128), r = 0 .. 127, with the C library's cosine (math.cos): the fade-in gains ss_remove_silence
+    takes as a host array.  float64 [128]."""
+    return np.array([0.5 - 0.5 * math.cos(math.pi * (r + 0.5) / 128.0) for r in range(128)], dtype=np.float64)
+
+
+def remove_silence_dev(x_dev, n_dev, opts):
+    """The C call on device tensors: x float64 [B, max_n], n int32 [B] or None (every row has max_n samples), opts a Silence ->
+    (y float64 [B, max_n], m int32 [B], inv int32 [B, ceil(max_n / 256)], k int32 [B]): each row's kept 256-sample blocks in order with a
+    128-sample cross-fade at every join and zeros behind its new length m; inv lists the kept blocks (-1 behind the k of them)."""
+    _silence_opts('remove_silence_dev', opts)
+    lib = _capi.lib()
+    B, max_n = x_dev.shape
+    nbytes = lib.ss_silence_scratch_bytes(B, max_n)
+    if nbytes < 0:
+        _capi.check(-1)
+    dev = x_dev.device
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    y = torch.empty_like(x_dev)
+    m, k = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)
+    inv = torch.empty(B, (max_n + 255) // 256, dtype=torch.int32, device=dev)
+    g = silence_fade()
+    _capi.check(lib.ss_remove_silence(C.c_void_p(x_dev.data_ptr()), C.c_void_p(n_dev.data_ptr()) if n_dev is not None else None, B, max_n,
+                                      opts.ratio, opts.hang, opts.edge, opts.pause_blocks, g.ctypes.data_as(C.POINTER(C.c_double)),
+                                      C.c_void_p(y.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(inv.data_ptr()), C.c_void_p(k.data_ptr()),
+                                      C.c_void_p(scratch.data_ptr()), nbytes, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return y, m, inv, k
+
+
+def _silence_group(ws, opts, max_rows, device):
+    """recordings at 16 kHz (device tensors or numpy arrays, float64 [n] each) through remove_silence_dev as ragged batches in plan_batches
+    order -> (one device tensor [m] a recording, the new lengths, each recording's kept blocks as a device tensor), in input order.  One small
+    copy per batch brings the new lengths and block counts back; the samples stay on the device."""
+    out, lens, maps = [None] * len(ws), [0] * len(ws), [None] * len(ws)
+    for batch in plan_batches([w.shape[0] for w in ws], max_rows):
+        rows = [ws[i].shape[0] for i in batch]
+        x = torch.zeros(len(batch), rows[-1], dtype=torch.float64, device=device)
+        for r, i in enumerate(batch):
+            x[r, :rows[r]] = torch.as_tensor(ws[i]).to(device)
+        y, m, inv, k = remove_silence_dev(x, torch.tensor(rows, dtype=torch.int32, device=device), opts)
+        mk = torch.stack((m, k)).cpu().numpy()
+        for r, i in enumerate(batch):
+            lens[i] = int(mk[0, r])
+            out[i] = y[r, :lens[i]]
+            maps[i] = inv[r, :int(mk[1, r])]
+    return out, lens, maps
+
+
+def remove_silence(xs, opts=Silence(), max_rows=16, device='cuda', return_maps=False):
+    """Trim the silence at both ends of recordings at 16 kHz and cap the pauses inside them, on the GPU (csrc/silence.hip; `Silence` has the
+    options and include/speechsplit_amd.h the definition).  A list of float64 [n] (any lengths >= 1) -> a list of float64 numpy arrays in input
+    order.  The recordings run as ragged batches of at most max_rows rows in convert.plan_batches order; every row is the result of running it
+    alone, so the result is the same bits whatever max_rows.  return_maps=True returns (ys, invs) with each recording's kept 256-sample
+    blocks, ascending (int32): a removed block is a removed mel frame, so frame-rate data of the original follows by `track[inv]`."""
+    _silence_opts('remove_silence', opts)
+    ws = [np.ascontiguousarray(x, dtype=np.float64) for x in xs]
+    for i, w in enumerate(ws):
+        if w.ndim != 1 or w.shape[0] < 1:
+            raise ValueError(f'remove_silence: recording {i} must be [n] with n >= 1, not {w.shape}')
+    ys, _, maps = _silence_group(ws, opts, max_rows, device)
+    ys = [y.cpu().numpy() for y in ys]
+    return (ys, [v.cpu().numpy() for v in maps]) if return_maps else ys
+
+
 def pitch_track(wavs, lo, hi, max_rows=16, device='cuda', *, stationarity=False):
     """make_spect_f0.py:64 with the Talkin-style tracker of csrc/pitch.hip in place of `sptk.rapt(wav.astype(np.float32) * 32768, fs, 256,
     min=lo, max=hi, otype=2)`.  One float64 waveform [n] at 16 kHz (or a list of them, any lengths >= 513) -> float64 numpy track(s)
@@ -416,17 +541,27 @@ def extract(x, prng, gender, device='cuda', mel_basis=None, unvoiced=0.0, sr=160
     return _extract(x, prng, gender, device, mel_basis, unvoiced, sr, False)
 
 
-def extract_opt(x, prng, gender, *, device='cuda', mel_basis=None, unvoiced=0.0, sr=16000, stationarity=False):
-    """`extract` with its options by keyword, and the one it cannot take: stationarity=True tracks the pitch with RAPT's
-    spectral-stationarity term (`pitch_track(..., stationarity=True)`).  With False it is `extract`: the same calls, the same bits."""
+def extract_opt(x, prng, gender, *, device='cuda', mel_basis=None, unvoiced=0.0, sr=16000, stationarity=False, silence=None):
+    """`extract` with its options by keyword, and the ones it cannot take: stationarity=True tracks the pitch with RAPT's
+    spectral-stationarity term (`pitch_track(..., stationarity=True)`); silence=Silence(...) removes silence at 16 kHz first
+    (`remove_silence`: behind the resampler, in front of the odd-length fix and the dither draw).  With False and None it is `extract`: the
+    same calls, the same bits."""
+    if silence is not None:
+        return _extract(x, prng, gender, device, mel_basis, unvoiced, sr, _stat_flag('extract_opt', stationarity),
+                        _silence_opts('extract_opt', silence))
     return _extract(x, prng, gender, device, mel_basis, unvoiced, sr, _stat_flag('extract_opt', stationarity))
 
 
-def _extract(x, prng, gender, device, mel_basis, unvoiced, sr, stationarity):
-    """extract's body; `stationarity` is handed to pitch_track only when it is set, so that the default makes the earlier calls"""
+def _extract(x, prng, gender, device, mel_basis, unvoiced, sr, stationarity, silence=None):
+    """extract's body; `stationarity` is handed to pitch_track only when it is set, and remove_silence runs only when `silence` is, so that the
+    defaults make the earlier calls"""
     x = np.asarray(x, np.float64)
     if sr != 16000:
         x = resample(x, sr, 16000, device=device)
+    if silence is not None:
+        x = remove_silence([x], silence, device=device)[0]
+        if x.shape[0] + (x.shape[0] % 256 == 0) < MIN_SAMPLES:
+            raise ValueError(f'extract_opt: recording 0 has {x.shape[0]} samples after silence removal; it must have n >= {MIN_SAMPLES}')
     wav = preprocess_wav(x, prng)
     S = melspectrogram(wav, mel_filter_bank().T.astype(np.float64) if mel_basis is None else mel_basis, device).cpu().numpy()
     lo, hi = f0_range(gender)
@@ -539,8 +674,23 @@ class _Chain:
         return out
 
 
+def _to_16k(xs, ratios, max_rows, device):
+    """recordings with their reduced (up, down) to 16 kHz -> one device tensor a recording, in input order: grouped by rate, each group
+    through ss_resample as ragged batches (a recording at 16 kHz is uploaded as it is)"""
+    wav16 = [None] * len(xs)
+    for ratio in sorted(set(ratios)):
+        group = [i for i, q in enumerate(ratios) if q == ratio]
+        if ratio == (1, 1):
+            ys = [torch.from_numpy(xs[i]).to(device) for i in group]
+        else:
+            ys = _resample_group([xs[i] for i in group], ratio[0], ratio[1], max_rows, device)
+        for i, y in zip(group, ys):
+            wav16[i] = y
+    return wav16
+
+
 def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis=None, unvoiced=0.0, *, device_draws=False,
-                     stationarity=False):
+                     stationarity=False, silence=None):
     """`extract_batch` for recordings at any sample rate: sr is one rate in Hz for all of xs, or one a recording.  The same as
     extract_batch([scipy.signal.resample_poly(x, 16000, sr) ...], prng, gender, ...), to the bit, with the resampling on the GPU in front of the
     chain and nothing brought back between them: the recordings are grouped by rate and each group runs through ss_resample as ragged batches in
@@ -550,13 +700,19 @@ def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis
     `rand_dev` for the sum of the fixed-up (resampled) lengths in input order -- the same numbers, prng left in the same state -- and one
     ss_dither_rows a batch; the default makes exactly the host's calls.  stationarity=True tracks the pitch with RAPT's
     spectral-stationarity term (`pitch_track_dev(..., stationarity=True)`); with False the calls and the bits are today's.  (`extract_batch`'s
-    argument list is pinned, so this is also the batched entry point for that option at 16 kHz.)"""
+    argument list is pinned, so this is also the batched entry point for that option at 16 kHz.)  silence=Silence(...) removes silence at
+    16 kHz (`remove_silence_dev`: behind the resampler, in front of the odd-length fix and the draws): the same as extract_batch_sr on the
+    trimmed recordings at 16000 Hz, to the bit.  The new lengths come back in one small copy per batch; the fix, the draws in input order and
+    the 513-sample minimum then apply to them as they apply to resampled lengths, and a recording that ends shorter is refused by its
+    index with its new length.  With None the calls and the bits are today's."""
     _stat_flag('extract_batch_sr', stationarity)
+    if silence is not None:
+        _silence_opts('extract_batch_sr', silence)
     xs = [np.ascontiguousarray(x, dtype=np.float64) for x in xs]
     srs = [sr] * len(xs) if np.ndim(sr) == 0 else list(sr)
     if len(srs) != len(xs):
         raise ValueError(f'extract_batch_sr: {len(srs)} sample rates for {len(xs)} recordings')
-    if all(s == 16000 for s in srs):
+    if silence is None and all(s == 16000 for s in srs):
         if stationarity:
             return _extract_batch(xs, prng, gender, max_rows, device, mel_basis, unvoiced, bool(device_draws), True)
         if device_draws:
@@ -567,9 +723,15 @@ def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis
         if x.ndim != 1 or x.shape[0] < 1:
             raise ValueError(f'extract_batch_sr: recording {i} must be [n], not {x.shape}')
     own = [resample_len(x.shape[0], up, down) for x, (up, down) in zip(xs, ratios)]      # samples at 16 kHz
+    if silence is not None:
+        f0_range(gender)                                                                   # an unknown gender stops the call before any device work
+        wav16, own, _ = _silence_group(_to_16k(xs, ratios, max_rows, device), silence, max_rows, device)
     lens = [m + 1 if m % 256 == 0 else m for m in own]                                     # after the odd-length fix
     for i, n in enumerate(lens):
         if n < MIN_SAMPLES:
+            if silence is not None:
+                raise ValueError(f'extract_batch_sr: recording {i} has {own[i]} samples after silence removal; every recording must have '
+                                 f'n >= {MIN_SAMPLES}')
             raise ValueError(f'extract_batch_sr: recording {i} has {n} samples at 16 kHz; every recording must have n >= {MIN_SAMPLES}')
     f0_range(gender)
     plan = plan_batches(lens, max_rows)
@@ -578,15 +740,8 @@ def extract_batch_sr(xs, sr, prng, gender, max_rows=16, device='cuda', mel_basis
         first_dev = torch.from_numpy(_draw_offsets(lens, plan)).to(device)
     else:
         draws = [prng.rand(n) for n in lens]                                               # input order, whatever the grouping
-    wav16 = [None] * len(xs)                                                               # device tensors [own[i]]
-    for ratio in sorted(set(ratios)):
-        group = [i for i, q in enumerate(ratios) if q == ratio]
-        if ratio == (1, 1):
-            ys = [torch.from_numpy(xs[i]).to(device) for i in group]
-        else:
-            ys = _resample_group([xs[i] for i in group], ratio[0], ratio[1], max_rows, device)
-        for i, y in zip(group, ys):
-            wav16[i] = y
+    if silence is None:
+        wav16 = _to_16k(xs, ratios, max_rows, device)                                      # device tensors [own[i]]
     chain = _Chain(gender, device, mel_basis, unvoiced, stationarity)
     out, row = [None] * len(xs), 0
     for idx in plan:
@@ -634,25 +789,32 @@ def make_spect_f0_batched(root_dir='assets/wavs', target_dir='assets/spmel', tar
 
 
 def make_spect_f0_opt(root_dir='assets/wavs', target_dir='assets/spmel', target_dir_f0='assets/raptf0', spk2gen='assets/spk2gen.pkl', *,
-                      device='cuda', resample=False, max_rows=None, device_draws=False, stationarity=False):
+                      device='cuda', resample=False, max_rows=None, device_draws=False, stationarity=False, silence=None):
     """The walk of `make_spect_f0` (max_rows=None: file by file) and of `make_spect_f0_batched` (an integer) with every option by keyword,
-    and the one their pinned argument lists cannot take: stationarity=True tracks the pitch with RAPT's spectral-stationarity term.  With
-    False it writes the files those two write.  Returns the (speaker, name) pairs written."""
+    and the ones their pinned argument lists cannot take: stationarity=True tracks the pitch with RAPT's spectral-stationarity term;
+    silence=Silence(...) removes silence from every recording at 16 kHz first (`remove_silence`).  With False and None it writes the files
+    those two write.  Returns the (speaker, name) pairs written."""
     if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, int) or max_rows < 1):
         raise ValueError(f'make_spect_f0_opt: max_rows must be None or a positive integer, not {max_rows!r}')
     if not isinstance(device_draws, bool):
         raise TypeError(f'make_spect_f0_opt: device_draws must be True or False, not {device_draws!r}')
     if device_draws and max_rows is None:
         raise ValueError('make_spect_f0_opt: device_draws needs the batched walk (max_rows)')
+    if silence is not None:
+        return _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, device_draws,
+                     _stat_flag('make_spect_f0_opt', stationarity), _silence_opts('make_spect_f0_opt', silence))
     return _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, device_draws,
                  _stat_flag('make_spect_f0_opt', stationarity))
 
 
-def _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, device_draws, stationarity=False):
-    """make_spect_f0's walk; device_draws and stationarity are handed on only when they are set, so that the default makes the earlier calls"""
+def _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_rows, device_draws, stationarity=False, silence=None):
+    """make_spect_f0's walk; device_draws, stationarity and silence are handed on only when they are set, so that the default makes the
+    earlier calls"""
     more = {'device_draws': True} if device_draws else {}
     if stationarity:
         more['stationarity'] = True
+    if silence is not None:
+        more['silence'] = silence
     if not isinstance(resample, bool):
         raise TypeError(f'make_spect_f0: resample must be True or False, not {resample!r} (max_rows goes by keyword)')
     if not isinstance(spk2gen, dict):
@@ -678,8 +840,11 @@ def _walk(root_dir, target_dir, target_dir_f0, spk2gen, device, resample, max_ro
                 S, f0_norm = feats[k]
             else:
                 x, sr = read(name)
-                S, f0_norm = _extract(x, prng, spk2gen[subdir], device, None, -1e10, sr, True) if stationarity else \
-                    extract(x, prng, spk2gen[subdir], device, unvoiced=-1e10, sr=sr)
+                if silence is not None:
+                    S, f0_norm = _extract(x, prng, spk2gen[subdir], device, None, -1e10, sr, stationarity, silence)
+                else:
+                    S, f0_norm = _extract(x, prng, spk2gen[subdir], device, None, -1e10, sr, True) if stationarity else \
+                        extract(x, prng, spk2gen[subdir], device, unvoiced=-1e10, sr=sr)
             np.save(os.path.join(target_dir, subdir, name[:-4]), S, allow_pickle=False)
             np.save(os.path.join(target_dir_f0, subdir, name[:-4]), f0_norm, allow_pickle=False)
             done.append((subdir, name[:-4]))
